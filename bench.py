@@ -14,13 +14,25 @@ sift3d_amd/csrc/sift3d_sharded.c).
     python bench.py --gpus N --strong 1024 ...                # BASELINE configs[3]: ONE 1024^3 volume
                                                               # as N Z-slabs (strong scaling)
 
-Rank 0 prints ONE JSON line: metric/value (Mvoxel/s, whole job), ms_per_step, plus
+Rank 0 prints ONE JSON line: metric/value (Mvoxel/s, whole job), ms_per_step (one timed step), the
+candidate / keypoint counts and stage seconds of the last step.  A plain run does nothing else: set up, warm
+up, time --steps steps, print.
+
+    python bench.py --dump-outputs DIR ...                    # also write the last timed step's outputs
+                                                              # (keypoints, descriptors) as DIR/*.npy
+
+--full adds everything else the benchmark measures or checks, each beside the main line:
+  counts_ok    the main line's candidate -> keypoint counts against the known ones (exit 3 on a mismatch)
+  strong_1024  BASELINE configs[3] (one 1024^3 volume as N Z-slabs), counts checked too
+  value_host_resident  the same steps from a host-resident volume (H2D inside)
   roofline     the dominant pyramid kernel: algorithmic bytes per launch (8 B/voxel per 1-D
                pass) / its average launch time measured here with HIP events,
                against the 8 TB/s HBM3E peak; `pyramid` = the same ratio for the whole
                Gaussian pyramid build (21.63 GB algorithmic at 512^3)
   cpu_baseline the unmodified reference (oracle/_ref, kind "reference") or the oracle
                restatement (kind "port") timed on this host on a bounded sample.
+  details      the per-kernel microbench, every in-step pyramid launch, the pyramid alone, the
+               descriptor kernel's issue model.
 """
 import argparse
 import json
@@ -250,7 +262,7 @@ def register_bench(a, torch, api, hip):
         p2 = descs[1].xyz()[m[hit]]
         T, inl = api.ransac_affine(p1, p2, err_thresh=3.0, num_iter=500, seed=5)
         res.update(match_s=t1 - t0, ransac_s=time.perf_counter() - t1, matches=int(len(hit)),
-                   inliers=int(inl.sum()), T=T, nn2_s=matcher.seconds())
+                   inliers=int(inl.sum()), T=T, nn2_s=matcher.seconds(), m=m, inl=inl)
 
     for _ in range(a.warmup):
         step()
@@ -262,6 +274,16 @@ def register_bench(a, torch, api, hip):
         stat.append((res["match_s"], res["ransac_s"], res["nn2_s"]))
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        # the last step's results: both keypoint lists (descriptor rows, octave-0 voxels), the match of
+        # every row of the first (-1: none), RANSAC's inlier flags and the affine transform
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        written = {}
+        _save(a.dump_outputs, "register_xyz_a", descs[0].xyz(), written)
+        _save(a.dump_outputs, "register_xyz_b", descs[1].xyz(), written)
+        _save(a.dump_outputs, "register_matches", np.asarray(res["m"], np.float64), written)
+        _save(a.dump_outputs, "register_inliers", np.asarray(res["inl"], np.float64), written)
+        _save(a.dump_outputs, "register_affine", np.asarray(res["T"], np.float64), written)
     na, nb = len(descs[0]), len(descs[1])
     nn2 = float(np.median([s[2] for s in stat]))
     flops = 2.0 * 2.0 * na * nb * 768                      # both directions, multiply + add
@@ -364,11 +386,78 @@ def fir_kernel_names(api, n):
     return out
 
 
+# --dump-outputs: what the timed path returned in its last step, as float32 / float64 .npy files, at most
+# DUMP_BYTES in all.  Where a store is larger than its share, a fixed seeded sample of its rows is written
+# (the row numbers beside it) together with column sums over ALL rows, so that two builds compare output for
+# output on the same rows and every row still counts.
+DUMP_BYTES = 60 * 10 ** 6           # below the 64 MB the option promises, .npy headers included
+DUMP_KEYPOINTS = 150000             # keypoint rows: 96 B each (fields + row number)
+DUMP_DESCRIPTORS = 16384            # descriptor rows: 771 float32 + row number (+ keypoint number)
+DUMP_SEED = 20251015
+
+
+def _rows(n, k, salt):
+    """A fixed, seeded, sorted sample of k of n row numbers (all n rows when they fit)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED + salt).choice(n, k, replace=False))
+
+
+def _save(d, name, arr, written):
+    arr = np.ascontiguousarray(arr)
+    assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+    np.save(os.path.join(d, name + ".npy"), arr)
+    written[name] = list(arr.shape)
+
+
+def dump_outputs(d, kp_store, desc_store, desc_keypoint=None):
+    """The keypoint store and descriptor store of the last timed step (what sift3d_detect_keypoints and
+    sift3d_extract_descriptors hand their caller); desc_keypoint: the global keypoint of each descriptor row
+    where a rank holds the descriptors of its own keypoints only (the slab driver)."""
+    os.makedirs(d, exist_ok=True)
+    written = {}
+    recs = kp_store.records()
+    n = len(recs)
+    kf = np.zeros((n, 16), np.float64)      # xd yd zd sd o s strength R[9], for the column sums
+    kf[:, 0], kf[:, 1], kf[:, 2], kf[:, 3] = recs["xd"], recs["yd"], recs["zd"], recs["sd"]
+    kf[:, 4], kf[:, 5], kf[:, 6] = recs["o"], recs["s"], recs["strength"]
+    kf[:, 7:] = recs["R"].reshape(n, 9)
+    kr = _rows(n, DUMP_KEYPOINTS, 1)
+    _save(d, "keypoints_rows", kr.astype(np.float64), written)
+    _save(d, "keypoints_xyzs", kf[kr, 0:4], written)                  # xd, yd, zd, sd
+    _save(d, "keypoints_octave_level", kf[kr, 4:6], written)          # o, s
+    _save(d, "keypoints_strength", recs["strength"][kr].astype(np.float32), written)
+    _save(d, "keypoints_R", recs["R"][kr].astype(np.float32), written)
+    _save(d, "keypoints_column_sums", kf.sum(axis=0), written)
+    m = len(desc_store)
+    mat = desc_store.to_mat_rm() if m else np.zeros((0, 771), np.float32)   # x, y, z, 768 histogram values
+    used = 128 * 12 + kr.size * 96 + 16 * 8 + mat.shape[1] * 8 + 2 * 8
+    per_row = mat.shape[1] * 4 + 16
+    dr = _rows(m, min(DUMP_DESCRIPTORS, max(0, (DUMP_BYTES - used) // per_row)), 2)
+    _save(d, "descriptors_rows", dr.astype(np.float64), written)
+    _save(d, "descriptors", mat[dr].astype(np.float32), written)
+    _save(d, "descriptors_column_sums", mat.astype(np.float64).sum(axis=0), written)
+    if desc_keypoint is not None:
+        _save(d, "descriptors_keypoint", np.asarray(desc_keypoint, np.float64)[dr], written)
+    _save(d, "counts", np.array([n, m], np.float64), written)         # keypoints, descriptors
+    total = sum(os.path.getsize(os.path.join(d, k + ".npy")) for k in written)
+    assert total <= 64 * 10 ** 6, total
+    sys.stderr.write("bench.py: wrote %d arrays (%.1f MB) to %s\n" % (len(written), total / 1e6, d))
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the main line: the count checks, the strong_1024 leg, the "
+                         "host-resident and pyramid-only legs, the per-kernel microbench and roofline, the CPU "
+                         "baseline (each --no-* option below then skips its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (keypoints, descriptors; a fixed "
+                         "seeded sample of the descriptor rows, at most 64 MB in all) as DIR/<name>.npy")
     ap.add_argument("--size", type=int, default=512, help="edge of the (per-GPU) volume")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-micro", action="store_true", help="skip the per-kernel microbench")
@@ -392,6 +481,8 @@ def main():
                     help="N=1 only: run the Z-slab driver (C: sift3d_amd_sharded_*) instead of the "
                          "drop-in API, to measure the driver's own overhead")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started like the one-GPU run (`python bench.py --gpus N ...`), not under torch.distributed.run:
@@ -473,6 +564,7 @@ def main():
                                                  for k in jobs[0].breakdown()})
             pyr_time = jobs[0].pyramid_seconds
             closer = lambda: ([j.close() for j in jobs], [t.close() for t in trs], grp.close())  # noqa: E731
+            leg["outputs"] = lambda: (jobs[0].kp_store, jobs[0].desc_store, jobs[0].own_idx)  # noqa: E731
             job = None
         elif use_api:
             vol = torch.empty((nz_total, n, n), device="cuda")
@@ -491,6 +583,7 @@ def main():
                                  stage_s={k: round(v, 6) for k, v in det.timings().items()})
             pyr_time = lambda: det.timings()["gauss_dev"]  # noqa: E731
             leg.update(det=det, kp=kp, desc=desc, vol=vol)
+            leg["outputs"] = lambda: (kp, desc, None)  # noqa: E731
             closer = lambda: None  # noqa: E731
             job = None
         else:
@@ -503,6 +596,7 @@ def main():
             stats = job.stats
             pyr_time = job.pyramid_seconds
             closer = job.close
+            leg["outputs"] = lambda: (job.kp_store, job.desc_store, job.own_idx)  # noqa: E731
         for _ in range(warmup):
             step()
         if world > 1:
@@ -512,6 +606,8 @@ def main():
         pyr, launches, dclk = [], [], []
         for _ in range(steps):
             step()
+            if not a.full:          # the per-launch figures below feed --full's roofline only
+                continue
             pyr.append(pyr_time())
             if "det" in leg:
                 launches.append(leg["det"].launch_timings())
@@ -525,7 +621,7 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-            if job is not None:
+            if job is not None and a.full:
                 # stage seconds of the last step, max over ranks (so that a scaling curve can be read)
                 bd = job.breakdown()
                 keys = sorted(bd)
@@ -548,6 +644,8 @@ def main():
     nz_total = n if a.strong else n * ranks
     use_api = world == 1 and not a.sharded and not rt
     main_leg = run_leg(n, nz_total, a.steps, a.warmup, use_api)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *main_leg["outputs"]())
     failed = []
 
     def check(tag, strong, edge, st):
@@ -559,14 +657,14 @@ def main():
             failed.append("%s: %d candidates -> %d keypoints, expected %d -> %d" % ((tag,) + got + want))
         return got == want
 
-    main_ok = check("main line", bool(a.strong), n, main_leg["stats"])
+    main_ok = check("main line", bool(a.strong), n, main_leg["stats"]) if a.full else None
     if not use_api:
         main_leg["close"]()
 
     # BASELINE configs[3] beside the main line: ONE 1024^3 volume as N Z-slabs, so that the driver's
     # N = 1, 2, 4, 8 records hold the strong-scaling curve north_star names
     strong_rec = None
-    if not a.strong and not a.no_strong_leg and a.size == 512:
+    if a.full and not a.strong and not a.no_strong_leg and a.size == 512:
         sl = run_leg(1024, 1024, min(a.steps, 3), 1, use_api)
         st = sl["stats"]
         pt = float(np.median(sl["pyr"])) if sl["pyr"] and sl["pyr"][0] else None
@@ -632,6 +730,12 @@ def main():
                                   "single GPU" if world == 1 else "z-slab x%d" % world},
     }
     out.update(main_leg["stats"])
+    if not a.full:
+        # a plain run: the main line is all it measures
+        print(json.dumps(out))
+        sys.stdout.flush()
+        _finish()
+        return
     out["counts_ok"] = main_ok
     if main_leg["per_rank"]:
         out["per_rank_max_s"] = main_leg["per_rank"]

@@ -15,6 +15,7 @@ Fixture families:
   g3_*         end-to-end dumps: level digests, small levels in full, dogmax-free
                candidate list, keypoints (R, sd, stale strength), descriptors, sort order
   g5_*         larger volumes: candidate/keypoint lists, R, descriptor subset + row sums
+  g6_abi       the names the reference library exports and its CLI imports (JSON)
 """
 import argparse
 import hashlib
@@ -274,6 +275,25 @@ def g4_csv():
     return {"g4_csv": dict(kp=int(len(k["strength"])), kp_csv_bytes=len(ktxt), desc_csv_bytes=len(dtxt))}
 
 
+def g6_abi():
+    """The link-level contract as data, for machines without the reference: the names the unmodified
+    reference library exports (libsift3D_ref.so) and the names its own CLI -- cli/kpSift3D.c compiled unchanged
+    against include/sift3d by `make -C oracle ref` -- imports from the library (nm -D of both builds)."""
+    import subprocess
+
+    def names(path, *flags):
+        out = subprocess.check_output(["nm", "-D"] + list(flags) + [path]).decode()
+        return sorted({ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("sift3d_")
+                       and (" T " in ln or " U " in ln)})
+
+    d = {"library_exports": names(os.path.join(HERE, "_ref", "libsift3D_ref.so"), "--defined-only"),
+         "cli_imports": names(os.path.join(HERE, "_ref", "kpSift3D"), "--undefined-only")}
+    with open(os.path.join(OUT, "g6_abi.json"), "w") as f:
+        json.dump(d, f, indent=1)
+        f.write("\n")
+    return {"g6_abi": {k: len(v) for k, v in d.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also 128^3 and 256^3 (minutes)")
@@ -307,6 +327,7 @@ def main():
         "g3_lat": lambda: end_to_end("g3_lattice48", so.synth_lattice(48, seed=7),
                                      input_spec=dict(gen="lattice", n=48, seed=7)),
         "g4_csv": g4_csv,
+        "g6_abi": g6_abi,
     }
     if a.big:
         jobs["g5_128"] = lambda: end_to_end(

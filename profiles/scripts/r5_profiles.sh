@@ -20,16 +20,16 @@ head -c 1200 $O/describe_model.json; echo; python3 -c "
 import json; t=json.load(open('$O/traffic.json'))
 for k,v in sorted(t.items()): print(k, v['hbm_bytes'], v['ratio'])"
 cp $O/traffic.json $O/describe_model.json $R/profiles/
-echo "== bench"; timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2>$O/bench.err; python3 - <<PY
+echo "== bench"; timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2>$O/bench.err; python3 - <<PY
 import json
 d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); d.pop('details',None); print(json.dumps(d)[:3800])
 PY
-echo "== sharded N=1"; timeout -k 10 300 python bench.py --sharded --no-cpu --no-micro --no-host --steps 10 --warmup 3 > $O/bench_sharded1.json 2>/dev/null; tail -c 700 $O/bench_sharded1.json; echo
-echo "== rehearsal 8 ranks (weak main line + strong_1024 sub-record)"; timeout -k 10 900 python bench.py --rehearse-threads 8 --steps 2 --warmup 1 --no-cpu > $O/rehearse8.json 2>$O/rehearse8.err; tail -c 1500 $O/rehearse8.json; echo; tail -3 $O/rehearse8.err
+echo "== sharded N=1"; timeout -k 10 300 python bench.py --full --sharded --no-cpu --no-micro --no-host --steps 10 --warmup 3 > $O/bench_sharded1.json 2>/dev/null; tail -c 700 $O/bench_sharded1.json; echo
+echo "== rehearsal 8 ranks (weak main line + strong_1024 sub-record)"; timeout -k 10 900 python bench.py --full --rehearse-threads 8 --steps 2 --warmup 1 --no-cpu > $O/rehearse8.json 2>$O/rehearse8.err; tail -c 1500 $O/rehearse8.json; echo; tail -3 $O/rehearse8.err
 echo "== register"; timeout -k 10 400 python bench.py --register --steps 3 --warmup 1 > $O/bench_register.json 2>$O/reg.err; tail -c 400 $O/bench_register.json; echo
 cd /tmp && export TMPDIR=/tmp
 echo "== kernel stats (in-step launches only)"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/kstats -o run --output-format csv -- python3 $R/bench.py --no-cpu --no-host --no-micro --no-strong-leg --no-pyramid-leg --steps 10 --warmup 3 > $O/kstats_bench.json 2> $O/kstats.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/kstats -o run --output-format csv -- python3 $R/bench.py --full --no-cpu --no-host --no-micro --no-strong-leg --no-pyramid-leg --steps 10 --warmup 3 > $O/kstats_bench.json 2> $O/kstats.err
 tail -c 900 $O/kstats_bench.json; echo
 echo "== the octave-0 extrema sweep alone"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/sweep -o run --output-format csv -- python3 $R/profiles/microbench/sweep_alone.py > $O/sweep.log 2>&1

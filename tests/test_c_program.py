@@ -1,9 +1,11 @@
 """The drop-in boundary as a C consumer sees it: a program written against the reference's
 public headers (tests/c_program.c) is compiled with gcc against include/sift3d and linked with
 libsift3d_amd.so -- no Python in the loop.  Round 5: the same under the reference library's own
-name -- libsift3D.so.2, the soname the reference installs (/root/reference/sift3d/CMakeLists.txt:11-14)
+name -- libsift3D.so.2, the soname the reference installs (the reference's sift3d/CMakeLists.txt:11-14)
 -- and the reference's own consumer, cli/kpSift3D.c, compiled UNCHANGED against include/sift3d and
-linked with -lsift3D (/root/reference/cli/CMakeLists.txt:3-4, cli/kpSift3D.c:96-146)."""
+linked with -lsift3D (the reference's cli/CMakeLists.txt:3-4, cli/kpSift3D.c:96-146; `make -C oracle ref`
+builds it as oracle/_ref/kpSift3D where the reference sources are at hand)."""
+import json
 import os
 import subprocess
 
@@ -14,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c_program.c")
 
 
-REF_CLI = "/root/reference/cli/kpSift3D.c"
 CLI_BIN = os.path.join(ROOT, "oracle", "_ref", "kpSift3D")   # built by `make -C oracle ref` (build container)
+ABI = os.path.join(ROOT, "tests", "golden", "g6_abi.json")     # what that binary imports (oracle/make_golden.py)
 
 
 def _needed(path):
@@ -53,20 +55,41 @@ def test_reference_soname_artifact(tmp_path):
     assert "libsift3D.so.2" in _needed(exe) and "libsift3d_amd.so" not in _needed(exe)
 
 
-@pytest.mark.refprobe
 def test_reference_cli_compiles_unchanged_and_links(tmp_path):
     """cli/kpSift3D.c -- the reference's own consumer of the API -- compiled as it is against include/sift3d
-    and linked with -lsift3D; without a device it reports the failure the way it would with the reference."""
+    and linked with -lsift3D; without a device it reports the failure the way it would with the reference.
+    Everywhere: every library name its unchanged build imports (tests/golden/g6_abi.json) is declared by
+    include/sift3d and exported by libsift3D.so.2, and a program that takes exactly those names from the
+    headers compiles, links with -lsift3D and loads.  Where `make -C oracle ref` compiled the CLI itself
+    (oracle/_ref/kpSift3D, at build time), that binary is run as well."""
+    import re
     import torch
-    if not os.path.exists(REF_CLI):
-        pytest.skip("needs /root/reference (build container only)")
     from sift3d_amd import _native
     _native.load()
     libdir = os.path.join(ROOT, "sift3d_amd")
-    exe = str(tmp_path / "kpSift3D")
-    subprocess.run(["gcc", "-Wall", "-O2", "-I" + os.path.join(ROOT, "include", "sift3d"), REF_CLI, "-o", exe,
-                    "-L" + libdir, "-lsift3D", "-Wl,-rpath," + libdir], check=True)
+    imports = json.load(open(ABI))["cli_imports"]
+    decl = set()
+    for h in ("sift.h", "imutil.h"):
+        decl |= set(re.findall(r"\b(sift3d_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "sift3d", h)).read()))
+    sym = subprocess.run(["nm", "-D", "--defined-only", os.path.join(libdir, "libsift3D.so.2")], capture_output=True,
+                         text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in sym.splitlines() if ln.strip()}
+    assert len(imports) == 13 and set(imports) <= decl and set(imports) <= exported, sorted(set(imports) - exported)
+    src = tmp_path / "uses_cli_imports.c"
+    src.write_text('#include "imutil.h"\n#include "sift.h"\n#include <stdio.h>\nint main(void) {\n'
+                   + "".join('    printf("%%p\\n", (void *)&%s);\n' % f for f in imports) + "    return 0;\n}\n")
+    exe = str(tmp_path / "uses_cli_imports")
+    subprocess.run(["gcc", "-Wall", "-Werror", "-O2", "-I" + os.path.join(ROOT, "include", "sift3d"), str(src), "-o",
+                    exe, "-L" + libdir, "-lsift3D", "-Wl,-rpath," + libdir], check=True)
     assert "libsift3D.so.2" in _needed(exe)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and len(r.stdout.split()) == len(imports)
+    if not os.path.exists(CLI_BIN):
+        return
+    exe = CLI_BIN
+    assert "libsift3D.so.2" in _needed(exe)
+    und = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True, check=True).stdout
+    assert sorted({ln.split()[-1] for ln in und.splitlines() if ln.split()[-1].startswith("sift3d_")}) == imports
     r = subprocess.run([exe, "--help"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "kpSift3D" in r.stdout
     if torch.cuda.is_available():
