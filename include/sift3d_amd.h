@@ -210,6 +210,35 @@ sift3d_amd_ransac_affine(const double *src, const double *dst, int n, double err
                          uint64_t seed, double *tform, unsigned char *inlier, int *num_inliers);
 
 /* ------------------------------------------------------------------------ */
+/* Resampling: apply an affine map to a volume                               */
+/* ------------------------------------------------------------------------ */
+/* A is 3 x 4 doubles, row-major, a PULL map: output voxel (x, y, z) reads the source at
+ *   q_d = A[d][0] x + ((A[d][1] y + A[d][2] z) + A[d][3])      (double, in this order, unfused)
+ * in octave-0 voxel units -- the units of sift3d_amd_descriptor_store_xyz and of
+ * sift3d_amd_ransac_affine (converting physical, anisotropic units is the caller's job).  To resample
+ * the moving image of a registration into the fixed image's grid, pass the inverse of the
+ * moving -> fixed affine (sift3d_amd_affine_invert).  A sample is inside when 0 <= q_d <= n_d - 1 on
+ * every axis (a NaN is outside); outside voxels get `fill`.
+ *   LINEAR : i = floor(q), f = (float)(q - i), j = min(i + 1, n - 1); lerp(a, b, f) = a + f (b - a) in
+ *            float, along x for the four (y, z) corner rows, then along y, then along z
+ *   NEAREST: the value at floor(q + 0.5)
+ * The arithmetic is fixed: identity maps, integer translations and axis permutations / flips are exact
+ * copies.  Arguments are checked before any device call (-1 on NULL pointers, dims <= 0, an unknown
+ * interp, a non-finite A, overlapping src / dst). */
+#define SIFT3D_AMD_INTERP_NEAREST 0
+#define SIFT3D_AMD_INTERP_LINEAR 1
+/* device buffers, asynchronous on `stream`, no allocation */
+SIFT3D_AMD_API int
+sift3d_hip_warp_affine(const float *d_src, int nx, int ny, int nz, float *d_dst, int ox, int oy, int oz,
+                       const double *A /*12*/, int interp, float fill, void *stream);
+/* host image objects (nc == 1); the output grid is dst's; blocking */
+SIFT3D_AMD_API int
+sift3d_amd_image_warp_affine(const sift3d_image *src, const double *A, int interp, float fill,
+                             sift3d_image *dst);
+/* inverse of the affine map x -> A [x; 1]; -1 when the 3x3 part is singular or not finite */
+SIFT3D_AMD_API int sift3d_amd_affine_invert(const double *A /*12*/, double *Ainv /*12*/);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

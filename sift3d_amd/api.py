@@ -9,6 +9,7 @@ and numpy views; they contain no algorithmic code.
 Volumes are numpy float32 arrays of shape [nz, ny, nx] (x fastest), which is the memory
 layout of sift3d_image_data() (reference: sift3d/imutil.c:520-533).
 """
+import collections
 import ctypes as C
 import os
 
@@ -96,6 +97,8 @@ def lib():
         "sift3d_amd_ransac_affine": (C.c_int, [_f64p, _f64p, C.c_int, C.c_double, C.c_int, C.c_uint64,
                                               _f64p, np.ctypeslib.ndpointer(np.uint8),
                                               C.POINTER(C.c_int)]),
+        "sift3d_amd_image_warp_affine": (C.c_int, [vp, _f64p, C.c_int, C.c_float, vp]),
+        "sift3d_amd_affine_invert": (C.c_int, [_f64p, _f64p]),
         "sift3d_amd_device_available": (C.c_int, []),
         "sift3d_amd_version": (C.c_char_p, []),
         "sift3d_amd_synth_survey": (None, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64]),
@@ -513,3 +516,69 @@ def ransac_affine(src, dst, err_thresh=5.0, num_iter=500, seed=1):
     if rc != 0:
         raise RuntimeError("sift3d_amd_ransac_affine: no model")
     return A.reshape(3, 4), inl[:len(src)].astype(bool)
+
+
+# ---- resampling: apply an affine map to a volume -------------------------------------------------
+INTERP = {"nearest": 0, "linear": 1}
+
+
+def affine_invert(A):
+    """Inverse of the affine map x -> A [x; 1] (3 x 4).  ValueError when the 3 x 3 part is singular."""
+    a = np.ascontiguousarray(A, np.float64).reshape(12).copy()
+    out = np.zeros(12, np.float64)
+    if lib().sift3d_amd_affine_invert(a, out) != 0:
+        raise ValueError("affine_invert: the linear part is singular or not finite")
+    return out.reshape(3, 4)
+
+
+def warp_affine(image_or_array, A, out_shape, interp="linear", fill=0.0):
+    """Resample a host volume (an Image, or a float32 array [nz, ny, nx]) into a grid of
+    out_shape = (oz, oy, ox) through sift3d_amd_image_warp_affine.  A (3 x 4) is a pull map in
+    voxels: output voxel (x, y, z) takes the source at A [x; y; z; 1]; voxels that sample outside
+    get `fill`.  Returns an Image for an Image, an array for an array."""
+    if interp not in INTERP:
+        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    a = np.ascontiguousarray(A, np.float64).reshape(12).copy()
+    src = image_or_array if isinstance(image_or_array, Image) else Image.from_array(image_or_array)
+    oz, oy, ox = out_shape
+    dst = Image(ox, oy, oz)
+    if lib().sift3d_amd_image_warp_affine(src.h, a, INTERP[interp], float(fill), dst.h) != 0:
+        raise RuntimeError("sift3d_amd_image_warp_affine failed")
+    return dst if isinstance(image_or_array, Image) else dst.data().copy()
+
+
+Registration = collections.namedtuple("Registration", "A inliers num_matches warped")
+
+
+def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1, **detector_kw):
+    """Register two volumes (torch CUDA float32 tensors [nz, ny, nx]): detect + describe both,
+    match the descriptors, fit the moving -> fixed affine by RANSAC and resample `moving` into
+    `fixed`'s grid.  detector_kw go to Detector().  Returns Registration(A (3 x 4, moving voxel ->
+    fixed voxel), inliers (mask over the matches), num_matches, warped (tensor shaped like fixed))."""
+    import torch
+    from . import hip
+    for name, v in (("moving", moving), ("fixed", fixed)):
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
+                and v.dim() == 3):
+            raise ValueError("register: %s must be a contiguous 3-D float32 CUDA tensor" % name)
+    if moving.device != fixed.device:
+        raise ValueError("register: moving and fixed are on different devices (%s, %s)"
+                         % (moving.device, fixed.device))
+    torch.cuda.current_stream().synchronize()      # the detector works on its own stream
+    stores = []
+    for v in (moving, fixed):
+        det, kp, desc = Detector(**detector_kw), KeypointStore(), DescriptorStore()
+        desc.keep_device(True)
+        nz, ny, nx = v.shape
+        if det.detect_keypoints_device(v.data_ptr(), nx, ny, nz, kp) != 0:
+            raise RuntimeError("register: detect_keypoints_device failed")
+        if det.extract_descriptors(kp, desc) != 0:
+            raise RuntimeError("register: extract_descriptors failed")
+        stores.append(desc)
+    d_mov, d_fix = stores
+    m = Matcher().match(d_mov, d_fix, nn_thresh)
+    hit = np.nonzero(m >= 0)[0]
+    A, inl = ransac_affine(d_mov.xyz()[hit], d_fix.xyz()[m[hit]], err_thresh, num_iter, seed)
+    warped = torch.empty_like(fixed)
+    hip.warp_affine(moving, warped, affine_invert(A), "linear")
+    return Registration(A, inl, len(hit), warped)

@@ -2435,3 +2435,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* descriptor matching + RANSAC affine (BASELINE config 5) */
 #include "sift3d_register.c"
+
+/* affine resampling of host images, inversion of affine maps */
+#include "sift3d_warp.c"

@@ -92,6 +92,8 @@ def lib():
         "sift3d_hip_describe": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
         "sift3d_hip_set_mesh": (C.c_int, [C.POINTER(C.c_float)]),
         "sift3d_hip_synth_lattice": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]),
+        "sift3d_hip_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_double), C.c_int, C.c_float, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -165,6 +167,31 @@ def nn2(a, b):
                                 d1.data_ptr(), d2.data_ptr(), work.data_ptr(), current_stream()),
            "sift3d_hip_nn2")
     return j[:na], d1[:na], d2[:na]
+
+
+INTERP = {"nearest": 0, "linear": 1}
+
+
+def warp_affine(src, dst, A, interp="linear", fill=0.0):
+    """dst[z, y, x] = src sampled at A [x; y; z; 1] (A: 3 x 4 pull map in voxels; sift3d_hip_warp_affine)
+    on torch CUDA float32 contiguous tensors [nz, ny, nx] / [oz, oy, ox], on torch's current stream;
+    voxels that sample outside src get `fill`."""
+    import torch
+    for t in (src, dst):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.dim() == 3):
+            raise ValueError("warp_affine: src and dst must be contiguous 3-D float32 CUDA tensors")
+    if src.device != dst.device:
+        raise ValueError("warp_affine: src and dst are on different devices")
+    if interp not in INTERP:
+        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    a = np.ascontiguousarray(A, np.float64).reshape(12)
+    nz, ny, nx = src.shape
+    oz, oy, ox = dst.shape
+    _check(lib().sift3d_hip_warp_affine(src.data_ptr(), nx, ny, nz, dst.data_ptr(), ox, oy, oz,
+                                        a.ctypes.data_as(C.POINTER(C.c_double)), INTERP[interp],
+                                        float(fill), current_stream()), "sift3d_hip_warp_affine")
+    return dst
 
 
 def absmax(src, out):
