@@ -239,6 +239,52 @@ sift3d_amd_image_warp_affine(const sift3d_image *src, const double *A, int inter
 SIFT3D_AMD_API int sift3d_amd_affine_invert(const double *A /*12*/, double *Ainv /*12*/);
 
 /* ------------------------------------------------------------------------ */
+/* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
+/* ------------------------------------------------------------------------ */
+/* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code
+ * (traces: dense_rotate, imtypes_private.h:222, sift.c:580,598).  PARITY UNPINNED against
+ * upstream; pinned to this contract instead, built from the reference's per-voxel expressions.
+ * Input I[nz][ny][nx] float (finite), voxel sizes (ux, uy, uz) > 0, window sigma > 0 (world units).
+ * Output D[12][nz][ny][nx] float, planar, channel c = icosahedron vertex c (init_geometry order,
+ * the order of the bins of a sparse descriptor's 12-bin histograms).  Float arithmetic, no contraction:
+ *  1. gradient (IM_GET_GRAD_ISO, sift.c:140-145), neighbours outside clamped to the nearest voxel:
+ *       gx = 0.5f * (I[min(x+1, nx-1)] - I[max(x-1, 0)]);  gx = gx * (1.0f / (float)ux);  same for y, z
+ *  2. bin (icos_hist_bin, sift.c:1253-1290): m2 = gx*gx + gy*gy + gz*gz (left to right); when
+ *     m2 < 1.1920928955078125e-6f all 12 values are +0.0f.  Else the first face in table order that
+ *     cart2bary (sift.c:268-297) accepts; mag = sqrtf(m2), correctly rounded; the vertex whose
+ *     barycentric bary_j is (cart2bary's vertex j, j = x, y, z) gets mag * bary_j, the other 9 channels
+ *     +0.0f.  (The sparse descriptor's bins follow the reference's quirk Q1 -- every face of
+ *     init_geometry swaps v[0] and v[1] but keeps idx[], so bary_x lands in the bin of the other
+ *     vertex.  The dense image does not: channel c holds the weight of direction c, and mirroring the
+ *     volume permutes the channels.)
+ *  3. window: each channel through apply_Sep_FIR_filter (imutil.c:1127-1206), unit 1.0, the taps of
+ *     init_Gauss_filter(sigma) (sift3d_amd_gauss_filter): x, then y, then z, unit_factor =
+ *     (float)(1 / u_axis), the reference's edge rules -- the detector's blur of a level
+ *  4. normalise (normalize_desc, sift.c:1402-1430, without truncation): per voxel
+ *       s = sum_{c=0..11} (double)h_c * h_c  (in c order);  norm = sqrt(s) + DBL_EPSILON;
+ *       inv = (float)(1.0 / norm);  D_c = h_c * inv      (an all-zero voxel stays all zero)
+ * Arguments are checked before any device call: -1 on NULL pointers, dims <= 0, sigma or units not
+ * positive and finite, nc != 1, d_out overlapping d_src or d_work. */
+/* Stages (device buffers, asynchronous on `stream`, no allocation): steps 1 + 2 into d_out (12 planes of
+ * nx*ny*nz floats); step 4 in place on 12 planes of n floats.  Step 3 is sift3d_hip_fir /
+ * sift3d_hip_fir_yz_u1 per plane. */
+SIFT3D_AMD_API int
+sift3d_hip_dense_bin(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz, float *d_out,
+                     void *stream);
+SIFT3D_AMD_API int sift3d_hip_dense_normalize(float *d_hist, size_t n, void *stream);
+/* device scratch of sift3d_amd_dense_descriptors_device: 2 * nx*ny*nz floats (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_dense_work_floats(int nx, int ny, int nz);
+/* the whole descriptor image on device buffers: d_out 12 * nx*ny*nz floats, d_work
+ * sift3d_amd_dense_work_floats(nx, ny, nz) floats; units3 = (ux, uy, uz).  Asynchronous on `stream`, no
+ * allocation, no host synchronisation. */
+SIFT3D_AMD_API int
+sift3d_amd_dense_descriptors_device(const float *d_src, int nx, int ny, int nz, const double *units3,
+                                    double sigma, float *d_out, float *d_work, void *stream);
+/* host image (nc == 1, its units); out: 12 * nx*ny*nz floats, planar.  Blocking. */
+SIFT3D_AMD_API int
+sift3d_amd_image_dense_descriptors(const sift3d_image *im, double sigma, float *out);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

@@ -99,6 +99,7 @@ def lib():
                                               C.POINTER(C.c_int)]),
         "sift3d_amd_image_warp_affine": (C.c_int, [vp, _f64p, C.c_int, C.c_float, vp]),
         "sift3d_amd_affine_invert": (C.c_int, [_f64p, _f64p]),
+        "sift3d_amd_image_dense_descriptors": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_device_available": (C.c_int, []),
         "sift3d_amd_version": (C.c_char_p, []),
         "sift3d_amd_synth_survey": (None, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64]),
@@ -582,3 +583,30 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
     warped = torch.empty_like(fixed)
     hip.warp_affine(moving, warped, affine_invert(A), "linear")
     return Registration(A, inl, len(hit), warped)
+
+
+# ---- dense descriptors: a 12-bin gradient histogram per voxel ------------------------------------
+def dense_descriptors(volume, sigma=1.6, units=None):
+    """Dense descriptor image (contract: include/sift3d_amd.h, "Dense descriptors"): one unit-length
+    12-bin icosahedral gradient histogram per voxel, windowed by a Gaussian of `sigma` world units.
+    A torch CUDA float32 tensor [nz, ny, nx] gives a tensor [12, nz, ny, nx] (torch's current stream);
+    an Image or a float32 array gives a numpy array [12, nz, ny, nx] (blocking).  units = (ux, uy, uz):
+    by default the Image's units, else (1, 1, 1)."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is not None and isinstance(volume, torch.Tensor):
+        from . import hip
+        out = torch.empty((12,) + tuple(volume.shape), dtype=torch.float32, device=volume.device)
+        return hip.dense_descriptors(volume, out, sigma, (1, 1, 1) if units is None else units)
+    if isinstance(volume, Image):
+        if len(volume.shape) != 3:
+            raise ValueError("dense_descriptors: the image must have one channel")
+        im = volume if units is None else Image.from_array(volume.data(), units)
+    else:
+        im = Image.from_array(volume, units)
+    out = np.empty((12,) + im.shape, np.float32)
+    if lib().sift3d_amd_image_dense_descriptors(im.h, float(sigma), out.reshape(-1)) != 0:
+        raise RuntimeError("sift3d_amd_image_dense_descriptors failed")
+    return out

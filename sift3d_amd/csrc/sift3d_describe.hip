@@ -1,5 +1,6 @@
 // sift3d_describe.hip -- the descriptor kernel (k_describe), the icosahedron tables it uses and
-// their C entries (sift3d_hip_set_mesh, sift3d_hip_describe).
+// their C entries (sift3d_hip_set_mesh, sift3d_hip_describe); the dense descriptor kernels, which
+// share those tables (k_dense_bin, k_dense_normalize).
 //
 // A translation unit of its own because it is compiled with -fno-slp-vectorize, like
 // sift3d_fir_yz.hip: packed v_pk_* arithmetic gains nothing on gfx950 and costs this kernel
@@ -8,6 +9,8 @@
 #include "sift3d_kernels_common.h"
 #include "sift3d_math.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
 
 // ---------------------------------------------------------------------------------------
@@ -899,6 +902,167 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Dense descriptors (sift3d_amd_dense_descriptors_device, contract in include/sift3d_amd.h):
+// k_dense_bin writes one 12-bin icosahedral gradient histogram per voxel into 12 planes, the host
+// blurs every plane with the detector's blur, and k_dense_normalize scales each voxel's 12 values
+// to unit length.  Both kernels are plain streaming passes; their bytes are the planes.
+// ---------------------------------------------------------------------------------------
+// ids of the vertices that cart2bary's barycentrics x, y, z of each face belong to, 4 bits each (see
+// sift3d_hip_set_mesh: these are the geometric ids, not the bins of k_describe, which follow Q1)
+__constant__ int c_face_vert[20];
+
+constexpr int DB_TX = 64, DB_TY = 4;   // k_dense_bin block: 64 x-groups by 4 rows
+
+// icos_hist_bin (sift.c:1253-1290) of one gradient: the first face in table order that cart2bary
+// accepts, found as k_describe finds it -- the octant guess, accepted when every barycentric is
+// > 2e-5 (then no other face passes), else the full scan.  w = mag * bary (+0 below the threshold),
+// vid = the face's packed vertex ids.
+__device__ __forceinline__ void dense_bin_one(const float *sface, const int *soct, const int *svert, float gx,
+                                              float gy, float gz, float &w0, float &w1, float &w2, int &vid)
+{
+    const float m2 = gx * gx + gy * gy + gz * gz;        // sift.c:1264
+    w0 = 0.0f; w1 = 0.0f; w2 = 0.0f; vid = 0;
+    if (m2 < 1.1920928955078125e-06f)
+        return;
+    float b0, b1, b2;
+    int fi, f = soct[icos_guess(gx, gy, gz)];
+    bool found = face_eval(reinterpret_cast<const float4 *>(sface + f * FACE_STRIDE), gx, gy, gz, b0, b1, b2, fi) &&
+                 fminf(b0, fminf(b1, b2)) > 2e-5f;
+    if (!found) {
+        for (f = 0; f < 20; f++)
+            if (face_eval(reinterpret_cast<const float4 *>(sface + f * FACE_STRIDE), gx, gy, gz, b0, b1, b2, fi)) {
+                found = true;
+                break;
+            }
+        if (!found)       // unreachable for a finite gradient (sift.c:1288)
+            return;
+    }
+    const float mag = sqrtf(m2);                         // correctly rounded (sift.c:1331)
+    w0 = mag * b0; w1 = mag * b1; w2 = mag * b2;
+    vid = svert[f];
+}
+
+__device__ __forceinline__ float dense_pick(int c, int vid, float w0, float w1, float w2)
+{
+    return c == (vid & 15) ? w0 : c == ((vid >> 4) & 15) ? w1 : c == (vid >> 8) ? w2 : 0.0f;
+}
+
+// V = 4: each thread bins 4 consecutive voxels of a row and stores one float4 per plane (nx % 4 == 0,
+// 16-byte aligned buffers); V = 1: one voxel, scalar stores.
+template <int V>
+__global__ __launch_bounds__(DB_TX * DB_TY) void k_dense_bin(const float *__restrict__ src, float *__restrict__ out,
+                                                             int nx, int ny, int nz, float iux, float iuy, float iuz)
+{
+    __shared__ __attribute__((aligned(16))) float sface[20 * FACE_STRIDE];
+    __shared__ int soct[32], svert[20];
+    const int tid = threadIdx.x + DB_TX * threadIdx.y;
+    for (int i = tid; i < 20 * 16; i += DB_TX * DB_TY)
+        sface[(i >> 4) * FACE_STRIDE + (i & 15)] = c_face16[i];
+    if (tid < 32)
+        soct[tid] = c_oct_face[tid];
+    if (tid < 20)
+        svert[tid] = c_face_vert[tid];
+    __syncthreads();
+    const size_t N = (size_t)nx * (size_t)ny * (size_t)nz;
+    const int x0 = (blockIdx.x * DB_TX + threadIdx.x) * V;
+    if (x0 >= nx)
+        return;
+    for (int z = blockIdx.z; z < nz; z += gridDim.z) {
+        const size_t zs = (size_t)nx * (size_t)ny;
+        const size_t zm = (size_t)(z > 0 ? z - 1 : 0) * zs, zp = (size_t)(z + 1 < nz ? z + 1 : nz - 1) * zs;
+        for (int y = blockIdx.y * DB_TY + threadIdx.y; y < ny; y += gridDim.y * DB_TY) {
+            const size_t pz = (size_t)z * zs, py = (size_t)y * (size_t)nx, row = pz + py;
+            const size_t ym = (size_t)(y > 0 ? y - 1 : 0) * (size_t)nx, yp = (size_t)(y + 1 < ny ? y + 1 : ny - 1) * (size_t)nx;
+            // IM_GET_GRAD_ISO (sift.c:140-145, immacros.h:105-111), neighbours clamped into the volume
+            float c[V + 2], ya[V], yb[V], za[V], zb[V];
+            c[0] = src[row + (x0 > 0 ? x0 - 1 : 0)];
+            c[V + 1] = src[row + (x0 + V < nx ? x0 + V : nx - 1)];
+            if constexpr (V == 4) {
+                const float4 m = ld4(src + row + x0), a = ld4(src + pz + ym + x0), b = ld4(src + pz + yp + x0);
+                const float4 d = ld4(src + zm + py + x0), e = ld4(src + zp + py + x0);
+                c[1] = m.x; c[2] = m.y; c[3] = m.z; c[4] = m.w;
+                ya[0] = a.x; ya[1] = a.y; ya[2] = a.z; ya[3] = a.w;
+                yb[0] = b.x; yb[1] = b.y; yb[2] = b.z; yb[3] = b.w;
+                za[0] = d.x; za[1] = d.y; za[2] = d.z; za[3] = d.w;
+                zb[0] = e.x; zb[1] = e.y; zb[2] = e.z; zb[3] = e.w;
+            } else {
+                c[1] = src[row + x0];
+                ya[0] = src[pz + ym + x0]; yb[0] = src[pz + yp + x0];
+                za[0] = src[zm + py + x0]; zb[0] = src[zp + py + x0];
+            }
+            float w[V][3];
+            int vid[V];
+#pragma unroll
+            for (int k = 0; k < V; k++) {
+                float gx = 0.5f * (c[k + 2] - c[k]);
+                float gy = 0.5f * (yb[k] - ya[k]);
+                float gz = 0.5f * (zb[k] - za[k]);
+                gx = gx * iux; gy = gy * iuy; gz = gz * iuz;
+                dense_bin_one(sface, soct, svert, gx, gy, gz, w[k][0], w[k][1], w[k][2], vid[k]);
+            }
+            float *o = out + row + x0;
+#pragma unroll
+            for (int ch = 0; ch < 12; ch++) {
+                if constexpr (V == 4)
+                    st4(o + (size_t)ch * N, make_float4(dense_pick(ch, vid[0], w[0][0], w[0][1], w[0][2]),
+                                                        dense_pick(ch, vid[1], w[1][0], w[1][1], w[1][2]),
+                                                        dense_pick(ch, vid[2], w[2][0], w[2][1], w[2][2]),
+                                                        dense_pick(ch, vid[3], w[3][0], w[3][1], w[3][2])));
+                else
+                    o[(size_t)ch * N] = dense_pick(ch, vid[0], w[0][0], w[0][1], w[0][2]);
+            }
+        }
+    }
+}
+
+// normalize_desc (sift.c:1402-1430) of one voxel's 12 values, without the truncation step
+__device__ __forceinline__ float dense_inv_norm(const float *h)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < 12; c++)
+        s = s + (double)h[c] * (double)h[c];
+    const double norm = sqrt(s) + 2.220446049250313080847e-16;   // DBL_EPSILON
+    return (float)(1.0 / norm);
+}
+
+// V = 4: four voxels per thread with float4 loads and stores (n % 4 == 0, 16-byte aligned)
+template <int V>
+__global__ __launch_bounds__(256) void k_dense_normalize(float *__restrict__ h, size_t n)
+{
+    const size_t groups = n / V;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
+        float v[12][V];
+#pragma unroll
+        for (int c = 0; c < 12; c++) {
+            if constexpr (V == 4) {
+                const float4 q = ld4(h + (size_t)c * n + g * 4);
+                v[c][0] = q.x; v[c][1] = q.y; v[c][2] = q.z; v[c][3] = q.w;
+            } else {
+                v[c][0] = h[(size_t)c * n + g];
+            }
+        }
+        float inv[V];
+#pragma unroll
+        for (int k = 0; k < V; k++) {
+            float t[12];
+#pragma unroll
+            for (int c = 0; c < 12; c++)
+                t[c] = v[c][k];
+            inv[k] = dense_inv_norm(t);
+        }
+#pragma unroll
+        for (int c = 0; c < 12; c++) {
+            if constexpr (V == 4)
+                st4(h + (size_t)c * n + g * 4,
+                    make_float4(v[c][0] * inv[0], v[c][1] * inv[1], v[c][2] * inv[2], v[c][3] * inv[3]));
+            else
+                h[(size_t)c * n + g] = v[c][0] * inv[0];
+        }
+    }
+}
+
 extern "C" {
 
 // host twin of face_eval's acceptance test (same float expressions; this file is compiled with
@@ -1021,6 +1185,47 @@ int sift3d_hip_set_mesh(const float *faces)
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_bin_off), binoff, sizeof(binoff)));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_face16), f16, sizeof(f16)));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_oct_face), oct, sizeof(oct)));
+    // Dense descriptors: the id of the vertex each barycentric belongs to.  cart2bary's vertices are
+    // v0, v0 + e1, v0 + e2 (rounded); the one among the face's ids whose five faces all have a vertex
+    // there is that vertex's id -- not always idx[j]: init_geometry swaps v0 and v1 and keeps idx (Q1).
+    int vert[20];
+    {
+        float P[20][3][3];
+        for (int f = 0; f < 20; f++)
+            for (int k = 0; k < 3; k++) {
+                const float *r = faces + f * SIFT3D_HIP_FACE_FLOATS;
+                P[f][0][k] = r[k];
+                P[f][1][k] = r[k] + r[3 + k];
+                P[f][2][k] = r[k] + r[6 + k];
+            }
+        auto near = [&](const float *a, int g) {
+            for (int j = 0; j < 3; j++)
+                if (fabsf(a[0] - P[g][j][0]) + fabsf(a[1] - P[g][j][1]) + fabsf(a[2] - P[g][j][2]) < 1e-3f)
+                    return true;
+            return false;
+        };
+        for (int f = 0; f < 20; f++) {
+            vert[f] = 0;
+            for (int j = 0; j < 3; j++) {
+                int id = -1;
+                for (int a = 0; a < 3 && id < 0; a++) {
+                    bool all = true;
+                    for (int g = 0; g < 20; g++)
+                        for (int b = 0; b < 3; b++)
+                            if (idx[g * 3 + b] == idx[f * 3 + a])
+                                all = all && near(P[f][j], g);
+                    if (all)
+                        id = idx[f * 3 + a];
+                }
+                if (id < 0) {
+                    snprintf(g_err, sizeof(g_err), "sift3d_hip_set_mesh: face %d has no vertex id for corner %d", f, j);
+                    return SIFT3D_FAILURE;
+                }
+                vert[f] |= id << (4 * j);
+            }
+        }
+    }
+    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_face_vert), vert, sizeof(vert)));
     return SIFT3D_SUCCESS;
 }
 
@@ -1178,6 +1383,61 @@ int sift3d_hip_describe_wlut(const sift3d_hip_level *d_levels, int nlevels, cons
                              uint32_t n, float *d_hist, float *d_wlut, void *stream)
 {
     return sift3d_hip_describe_wlut2(d_levels, nlevels, d_kp, n, d_hist, nullptr, d_wlut, stream);
+}
+
+static int dense_fail(const char *what, const char *why)
+{
+    snprintf(g_err, sizeof(g_err), "%s: %s", what, why);
+    fprintf(stderr, "sift3d_amd: %s\n", g_err);
+    return SIFT3D_FAILURE;
+}
+
+int sift3d_hip_dense_bin(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz,
+                         float *d_out, void *stream)
+{
+    static const char what[] = "sift3d_hip_dense_bin";
+    if (!d_src || !d_out)
+        return dense_fail(what, "NULL argument");
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return dense_fail(what, "dimensions must be positive");
+    if (!(std::isfinite(ux) && ux > 0 && std::isfinite(uy) && uy > 0 && std::isfinite(uz) && uz > 0))
+        return dense_fail(what, "units must be positive and finite");
+    const size_t n = (size_t)nx * ny * nz;
+    {
+        const uintptr_t s0 = (uintptr_t)d_src, o0 = (uintptr_t)d_out;
+        if (s0 < o0 + 12 * n * sizeof(float) && o0 < s0 + n * sizeof(float))
+            return dense_fail(what, "source and output overlap");
+    }
+    // (1.0f / (float) ux, IM_GET_GRAD_ISO, sift.c:143-145)
+    const float iux = 1.0f / (float)ux, iuy = 1.0f / (float)uy, iuz = 1.0f / (float)uz;
+    const bool vec = nx % 4 == 0 && !((uintptr_t)d_src & 15) && !((uintptr_t)d_out & 15);
+    const int groups = vec ? nx / 4 : nx;
+    const dim3 g((groups + DB_TX - 1) / DB_TX, std::min((ny + DB_TY - 1) / DB_TY, 65535), std::min(nz, 65535));
+    const dim3 b(DB_TX, DB_TY);
+    if (vec)
+        hipLaunchKernelGGL(k_dense_bin<4>, g, b, 0, (hipStream_t)stream, d_src, d_out, nx, ny, nz, iux, iuy, iuz);
+    else
+        hipLaunchKernelGGL(k_dense_bin<1>, g, b, 0, (hipStream_t)stream, d_src, d_out, nx, ny, nz, iux, iuy, iuz);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_hip_dense_normalize(float *d_hist, size_t n, void *stream)
+{
+    if (!d_hist)
+        return dense_fail("sift3d_hip_dense_normalize", "NULL argument");
+    if (!n)
+        return SIFT3D_SUCCESS;
+    const bool vec = n % 4 == 0 && !((uintptr_t)d_hist & 15);
+    const size_t groups = vec ? n / 4 : n;
+    const size_t blocks = (groups + 255) / 256;
+    const unsigned grid = (unsigned)std::min<size_t>(blocks, 65536);
+    if (vec)
+        hipLaunchKernelGGL(k_dense_normalize<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_hist, n);
+    else
+        hipLaunchKernelGGL(k_dense_normalize<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_hist, n);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
 }
 
 } // extern "C"

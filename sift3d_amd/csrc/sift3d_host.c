@@ -1442,7 +1442,8 @@ static int ensure_dog_octave(sift3d_detector *d, int o)
 }
 
 /* apply_Sep_FIR_filter (imutil.c:1127-1206) on the device: x, y, z passes, the two
- * intermediates in scratch volumes, no permute copies */
+ * intermediates in scratch volumes, no permute copies.  dst may be src.  d (may be NULL: no timing)
+ * holds the events of the timed blurs; slot < 0 times nothing */
 /* d_scale_max (first blur of the pyramid only, else NULL): the blur of src / *d_scale_max -- im_scale folded
  * into the x pass; returns 2 without doing anything when the configuration's x pass cannot do that (the
  * caller then scales the image first) */
@@ -1467,7 +1468,7 @@ static int blur_level(sift3d_detector *d, const float *src, float *dst, const in
         a.axis = 0; a.width = f->width; a.taps = f->taps;
         a.unit_factor = (float)(1.0 / lu[0]);
         a.n_glob = dims[2]; a.z_lo = 0; a.z_hi = dims[2];
-        if (slot >= SIFT3D_AMD_TIMED_BLURS)
+        if (!d || slot >= SIFT3D_AMD_TIMED_BLURS)
             slot = -1;
         if (slot >= 0)
             sift3d_hip_event_record(d->ev_blur[slot][0], stream);
@@ -1481,8 +1482,11 @@ static int blur_level(sift3d_detector *d, const float *src, float *dst, const in
             return SIFT3D_FAILURE;
         if (slot >= 0)
             sift3d_hip_event_record(d->ev_blur[slot][1], stream);
-        rc = sift3d_hip_fir_yz_u1(tmp_a, dst, dims[0], dims[1], dims[2], f->taps, f->width,
-                                  dims[2], 0, 0, dims[2], stream);
+        /* (asking first: the fused kernel refuses rows shorter than 4 outright) */
+        rc = sift3d_hip_fir_yz_u1_covers(tmp_a, dst, dims[0], dims[1], f->width, dims[2])
+                 ? sift3d_hip_fir_yz_u1(tmp_a, dst, dims[0], dims[1], dims[2], f->taps, f->width, dims[2], 0, 0,
+                                        dims[2], stream)
+                 : 1;
         if (rc == SIFT3D_SUCCESS) {
             if (slot >= 0) {
                 sift3d_hip_event_record(d->ev_blur[slot][2], stream);
@@ -2438,3 +2442,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* affine resampling of host images, inversion of affine maps */
 #include "sift3d_warp.c"
+
+/* dense descriptor images */
+#include "sift3d_dense.c"

@@ -94,6 +94,12 @@ def lib():
         "sift3d_hip_synth_lattice": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]),
         "sift3d_hip_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                              C.POINTER(C.c_double), C.c_int, C.c_float, vp]),
+        "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                           vp, vp]),
+        "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
+        "sift3d_amd_dense_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_dense_descriptors_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                          C.c_double, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -192,6 +198,62 @@ def warp_affine(src, dst, A, interp="linear", fill=0.0):
                                         a.ctypes.data_as(C.POINTER(C.c_double)), INTERP[interp],
                                         float(fill), current_stream()), "sift3d_hip_warp_affine")
     return dst
+
+
+def _dense_args(src, out, what):
+    import torch
+    for t, dim in ((src, 3), (out, 4)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.dim() == dim):
+            raise ValueError("%s: src must be a contiguous float32 CUDA tensor [nz, ny, nx] and out one of "
+                             "[12, nz, ny, nx]" % what)
+    if out.shape != (12,) + tuple(src.shape):
+        raise ValueError("%s: out has shape %s, not [12, %d, %d, %d]" % ((what, tuple(out.shape)) + tuple(src.shape)))
+    if src.device != out.device:
+        raise ValueError("%s: src and out are on different devices" % what)
+    nz, ny, nx = src.shape
+    return nx, ny, nz
+
+
+def dense_bin(src, out, units=(1, 1, 1)):
+    """Steps 1-2 of the dense descriptor contract (sift3d_hip_dense_bin): per-voxel gradient histograms
+    of src [nz, ny, nx] into out [12, nz, ny, nx] (torch CUDA float32), on torch's current stream."""
+    nx, ny, nz = _dense_args(src, out, "dense_bin")
+    _check(lib().sift3d_hip_dense_bin(src.data_ptr(), nx, ny, nz, *map(float, units), out.data_ptr(),
+                                      current_stream()), "sift3d_hip_dense_bin")
+    return out
+
+
+def dense_normalize(hist):
+    """Step 4 of the dense descriptor contract (sift3d_hip_dense_normalize), in place on a torch CUDA
+    float32 tensor [12, ...] on torch's current stream."""
+    import torch
+    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.float32
+            and hist.is_contiguous() and hist.dim() >= 1 and hist.shape[0] == 12):
+        raise ValueError("dense_normalize: hist must be a contiguous float32 CUDA tensor [12, ...]")
+    _check(lib().sift3d_hip_dense_normalize(hist.data_ptr(), hist.numel() // 12, current_stream()),
+           "sift3d_hip_dense_normalize")
+    return hist
+
+
+def dense_descriptors(src, out, sigma, units=(1, 1, 1), work=None):
+    """Dense descriptor image (sift3d_amd_dense_descriptors_device): out [12, nz, ny, nx] from src
+    [nz, ny, nx], torch CUDA float32, on torch's current stream.  work: a float32 CUDA tensor of at least
+    sift3d_amd_dense_work_floats elements (2 * nz*ny*nx), or None to allocate one here."""
+    import torch
+    nx, ny, nz = _dense_args(src, out, "dense_descriptors")
+    need = lib().sift3d_amd_dense_work_floats(nx, ny, nz)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float32, device=src.device)
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.float32
+            and work.is_contiguous() and work.numel() >= need and work.device == src.device):
+        raise ValueError("dense_descriptors: work must be a contiguous float32 CUDA tensor of >= %d elements "
+                         "on the device of src" % need)
+    u = (C.c_double * 3)(*map(float, units))
+    _check(lib().sift3d_amd_dense_descriptors_device(src.data_ptr(), nx, ny, nz, u, float(sigma), out.data_ptr(),
+                                                     work.data_ptr(), current_stream()),
+           "sift3d_amd_dense_descriptors_device")
+    return out
 
 
 def absmax(src, out):
