@@ -163,7 +163,8 @@ SIFT3D_AMD_API const char *sift3d_amd_version(void);
 /* Registration: descriptor matching + RANSAC affine (BASELINE config 5)     */
 /* ------------------------------------------------------------------------ */
 /* Removed from the reference fork (CHANGES.md:99-103; upstream: README-OLD.md:5) -- no reference
- * code, no oracle: PARITY UNPINNED.  See sift3d_amd/csrc/sift3d_register.c. */
+ * code, no oracle: parity with upstream cannot be pinned.  Matching and RANSAC are pinned bit for bit
+ * to numpy restatements instead (tests/match_restatement.py).  See sift3d_amd/csrc/sift3d_register.c. */
 
 /* Nearest / second-nearest neighbour of each of the nA rows of d_A (nA x dim floats, row-major)
  * among the nB rows of d_B under the squared L2 distance, on the matrix cores

@@ -460,7 +460,7 @@ def gauss_filter(sigma):
     return taps[:w].copy()
 
 
-# ---- registration (BASELINE config 5; parity unpinned: removed from the reference fork) --------
+# ---- registration (BASELINE config 5; removed from the reference fork: pinned to restatements) --
 class Matcher:
     """sift3d_amd_matcher: descriptor matching with reusable device scratch."""
 

@@ -3,10 +3,12 @@
 // BASELINE config 5 ("two volumes: detect + describe both, NN match, RANSAC affine").  The
 // matcher and the RANSAC fit were REMOVED from the reference fork (CHANGES.md:99-103; upstream
 // description README-OLD.md:5), so there is no reference code, no oracle and no fixture for this
-// stage: PARITY UNPINNED.  What is built is the textbook form of what upstream describes --
-// for every descriptor of set A the nearest and second nearest descriptor of set B under the L2
-// distance, accepted by Lowe's ratio test -- validated by recovering a known transform
-// (tests/test_register.py).
+// stage: parity with upstream cannot be pinned.  What is built is the textbook form of what
+// upstream describes -- for every descriptor of set A the nearest and second nearest descriptor
+// of set B under the L2 distance, accepted by Lowe's ratio test.  Every value it returns is pinned
+// bit for bit to a numpy restatement of the arithmetic below (tests/match_restatement.py,
+// tests/test_match.py): the row norms' lane order, the fma chain in group()'s k order, the
+// lexicographic top-2 and the clamp.
 //
 // This is the one dense contraction of the project: |a - b|^2 = |a|^2 + |b|^2 - 2 a.b, an
 // (nA x 768) x (768 x nB) matrix product, done on the matrix cores with
@@ -82,8 +84,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // the 16-byte global loads delivered, no transposition), rows LDK = KC + 4 floats apart.  A lane of an
     // MFMA operand (row = lane & 31, half h = lane >> 5) takes FOUR k at a time with one 16-byte read,
     // k = 8 g + 4 h + {0, 1, 2, 3}: the j-th of the four v_mfma_f32_32x32x2_f32 of group g then multiplies the
-    // k pair (8 g + j, 8 g + 4 + j) -- any pairing will do, a dot product does not care about the order
-    // of its terms, as long as A and B use the same one.  Eight consecutive lanes read rows 36 floats
+    // k pair (8 g + j, 8 g + 4 + j).  A and B must use the same pairing; the pairing also fixes the order of
+    // the fma chain, k = 0, 4, 1, 5, 2, 6, 3, 7 per group, which tests/match_restatement.py restates bit for
+    // bit (another pairing changes the last bits of the distances).  Eight consecutive lanes read rows 36 floats
     // apart: 4-float slots at 0, 4, ..., 28 modulo the 32 banks -- conflict-free; a chunk needs 16
     // 16-byte reads and 8 16-byte stores per lane where the k-major layout needed 64 + 32 4-byte ones.
     // Double-buffered: the global loads of chunk c + 1 are in flight during the 64 MFMAs of chunk c and go

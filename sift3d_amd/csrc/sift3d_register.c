@@ -4,14 +4,15 @@
  * BASELINE config 5.  Upstream SIFT3D "can also perform 3D image registration by matching SIFT3D
  * features and fitting geometric transformations with the RANSAC algorithm" (README-OLD.md:5);
  * this fork REMOVED that code (CHANGES.md:99-103), so there is nothing to cite line by line, no
- * oracle and no fixture: PARITY UNPINNED.  Built from the published description:
+ * oracle and no fixture: parity with upstream cannot be pinned.  Built from the published description:
  *   matching   nearest / second-nearest neighbour under L2 on the 768-float descriptors
  *              (sift3d_hip_nn2, matrix cores), Lowe's ratio test on the two distances, and the
  *              forward-backward check (a match must be mutual);
  *   fitting    12-parameter affine y = A [x; 1] by least squares inside RANSAC: random minimal
  *              samples of 4 matches, inliers by residual, best consensus refit on its inliers.
- * Validated by recovering a known transform between two synthetic volumes
- * (tests/test_register.py). */
+ * The matcher's decisions and RANSAC (the generator, the picks, the fits, the consensus and the refits)
+ * are pinned bit for bit to a numpy restatement (tests/match_restatement.py); the whole flow is
+ * validated by recovering a known transform between two synthetic volumes (tests/test_register.py). */
 
 /* A matcher: one stream, scratch that grows on demand and is reused (no allocation per match). */
 struct sift3d_amd_matcher {

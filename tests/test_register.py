@@ -1,9 +1,11 @@
 """Registration stage (BASELINE config 5): descriptor matching + RANSAC affine.
 
-PARITY UNPINNED: the reference fork removed this code (CHANGES.md:99-103), so there is no oracle
-and no fixture.  The stage is validated by what it must achieve: the matrix-core nearest-neighbour
-kernel against a float64 numpy computation, the RANSAC fit against a known affine under outliers,
-and the whole flow by recovering a known transform between two volumes.
+Parity with upstream cannot be pinned: the reference fork removed this code (CHANGES.md:99-103), so
+there is no oracle and no fixture.  Matching and RANSAC are pinned bit for bit to numpy restatements
+instead (tests/test_match.py, tests/test_match_host.py).  The tests here check what the stage must
+achieve: the matrix-core nearest-neighbour kernel against a float64 numpy computation, the RANSAC fit
+against a known affine under outliers, and the whole flow by recovering a known transform between two
+volumes.
 """
 import numpy as np
 import pytest
