@@ -285,6 +285,62 @@ sift3d_amd_dense_descriptors_device(const float *d_src, int nx, int ny, int nz, 
 SIFT3D_AMD_API int
 sift3d_amd_image_dense_descriptors(const sift3d_image *im, double sigma, float *out);
 
+/* Rotation-invariant dense descriptors: upstream's dense_rotate variant (imtypes_private.h:222,
+ * sift.c:580,598).  Each voxel's window is binned in the voxel's own eigen-frame, so the image follows
+ * the anatomy when the volume is rotated.  Inputs as above: I[nz][ny][nx] float (finite), units > 0,
+ * sigma > 0 (world units).  Output D[12][nz][ny][nx] float, planar, channel c = icosahedron vertex c
+ * (no Q1 swap).  Float arithmetic, no contraction:
+ *  R1. gradient g(q) = IM_GET_GRAD_ISO (sift.c:140-145), taken only at window voxels q, which all lie in
+ *      1 <= x <= nx-2 (same for y, z): no clamping, the values of step 1 above.
+ *  R2. orientation: at every voxel v, vcenter = ((float)x, (float)y, (float)z), assign_eig_ori(I,
+ *      vcenter, sigma) (sift.c:926-1085) exactly:
+ *      window IM_LOOP_SPHERE (sift.c:86-107), radius 3.0 * sigma (ori_rad_fctr; the loop bounds from
+ *      floorf / ceilf of (float)(c -+ rad / (double)(float)u), clipped to 1 .. n-2; disp = ((float)q - c) *
+ *      (float)u, sq = dx*dx + dy*dy + dz*dz in float, inside when !((double)sq > rad * rad)), scan order
+ *      z, y, x; weight w = expf((float)(-0.5 * sq / (sigma * sigma))) (double expression, sift.c:972);
+ *      sums A_ab += (double)g_a * g_b * w (six, double, left to right) and vd_win += g * w (three,
+ *      float), in window order (sift.c:978-987);
+ *      reject when |vd_win|^2 < (float)1e-10 (sift.c:997); eigen-decomposition s3d_eigen3 (cyclic
+ *      Jacobi, sift3d_amd_host_eigen3; ascending L); reject when |L_i / L_{i+1}| > 0.9, i = 0, 1
+ *      (sift.c:1011-1015); for i = 0, 1 the eigenvector of L_{2-i} as float, d = (double)(float dot of
+ *      vd_win and it), sign +1 when d > 0 else -1, column i of R (sift.c:1017-1049); column 2 = column 0
+ *      x column 1 in float (sift.c:1054-1059).  No corner threshold.  A rejected voxel gets R = I and
+ *      keep = 0, a kept one keep = 1.
+ *  R3. histogram: the same sphere, order and weights.  For each window voxel q (extract_descrip,
+ *      sift.c:1497-1502): g' = g(q) * w (float, per component); gr = R^T g' (SIFT3D_MUL_MAT_RM_CVEC
+ *      on the transpose, immacros.h:330: gr_a = R[0][a]*g'x + R[1][a]*g'y + R[2][a]*g'z, left to right);
+ *      gr binned by step 2 above (the m2 threshold, the first face cart2bary accepts, mag * bary_j to
+ *      vertex channel j); accumulated in float from +0, in window order.  R3 uses R whether kept or not.
+ *  R4. normalise: step 4 above, unchanged (sift3d_hip_dense_normalize).
+ * Edge cases: an axis shorter than 3 voxels empties every window (R = I, keep = 0, D = 0); a flat region
+ * is rejected and its D is 0.  Cost grows with the window: about (4/3) pi (3 sigma)^3 / (ux uy uz) window
+ * voxels per voxel, each visited once by R2 and once by R3.  Refused windows: more than 20000 voxels by
+ * that estimate (about 3 sigma / u > 16.8 on an isotropic grid; each launch walks at least one tile's
+ * whole window, so this bounds a launch's length), or more than 509 voxels from the centre on an axis.
+ * Parity: R2 is pinned to the reference's assign_eig_ori through the oracle (orc_orient_slab with
+ * corner_thresh 0).  R3 is this project's own contract: the fork has no dense code.
+ * Arguments are checked before any device call: -1 on NULL pointers, dims <= 0, sigma or units not
+ * positive and finite, nc != 1, an output overlapping the source, R or the work buffer. */
+/* Stages (device buffers, asynchronous on `stream`, no allocation).  R2: d_R 9 planes of nx*ny*nz floats,
+ * element (i, j) of R in plane 3i + j; d_keep nx*ny*nz bytes, or NULL.  R3: d_out 12 unnormalised planes,
+ * from d_R.  Each stage is split into launches of bounded length for wide windows. */
+SIFT3D_AMD_API int
+sift3d_hip_dense_orient(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz, double sigma,
+                        float *d_R, unsigned char *d_keep, void *stream);
+SIFT3D_AMD_API int
+sift3d_hip_dense_rotate_bin(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz,
+                            double sigma, const float *d_R, float *d_out, void *stream);
+/* device scratch of sift3d_amd_dense_descriptors_rotate_device: 9 * nx*ny*nz floats, R (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_dense_rotate_work_floats(int nx, int ny, int nz);
+/* R1-R4 on device buffers: d_out 12 * nx*ny*nz floats, d_work sift3d_amd_dense_rotate_work_floats floats.
+ * Asynchronous on `stream`, no allocation, no host synchronisation. */
+SIFT3D_AMD_API int
+sift3d_amd_dense_descriptors_rotate_device(const float *d_src, int nx, int ny, int nz, const double *units3,
+                                           double sigma, float *d_out, float *d_work, void *stream);
+/* host image (nc == 1, its units); out: 12 * nx*ny*nz floats, planar.  Blocking. */
+SIFT3D_AMD_API int
+sift3d_amd_image_dense_descriptors_rotate(const sift3d_image *im, double sigma, float *out);
+
 /* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */

@@ -100,6 +100,7 @@ def lib():
         "sift3d_amd_image_warp_affine": (C.c_int, [vp, _f64p, C.c_int, C.c_float, vp]),
         "sift3d_amd_affine_invert": (C.c_int, [_f64p, _f64p]),
         "sift3d_amd_image_dense_descriptors": (C.c_int, [vp, C.c_double, _f32p]),
+        "sift3d_amd_image_dense_descriptors_rotate": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_device_available": (C.c_int, []),
         "sift3d_amd_version": (C.c_char_p, []),
         "sift3d_amd_synth_survey": (None, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64]),
@@ -586,27 +587,63 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
 
 
 # ---- dense descriptors: a 12-bin gradient histogram per voxel ------------------------------------
-def dense_descriptors(volume, sigma=1.6, units=None):
-    """Dense descriptor image (contract: include/sift3d_amd.h, "Dense descriptors"): one unit-length
-    12-bin icosahedral gradient histogram per voxel, windowed by a Gaussian of `sigma` world units.
-    A torch CUDA float32 tensor [nz, ny, nx] gives a tensor [12, nz, ny, nx] (torch's current stream);
-    an Image or a float32 array gives a numpy array [12, nz, ny, nx] (blocking).  units = (ux, uy, uz):
-    by default the Image's units, else (1, 1, 1)."""
+def _dense_image(volume, units, what):
+    if isinstance(volume, Image):
+        if len(volume.shape) != 3:
+            raise ValueError("%s: the image must have one channel" % what)
+        return volume if units is None else Image.from_array(volume.data(), units)
+    return Image.from_array(volume, units)
+
+
+def _torch_tensor(volume):
     try:
         import torch
     except ImportError:
-        torch = None
-    if torch is not None and isinstance(volume, torch.Tensor):
+        return False
+    return isinstance(volume, torch.Tensor)
+
+
+def dense_descriptors(volume, sigma=1.6, units=None, rotate=False):
+    """Dense descriptor image (contract: include/sift3d_amd.h, "Dense descriptors"): one unit-length
+    12-bin icosahedral gradient histogram per voxel, windowed by a Gaussian of `sigma` world units.
+    rotate=True: the rotation-invariant variant, each voxel's window binned in its own eigen-frame (see
+    dense_orientations).
+    A torch CUDA float32 tensor [nz, ny, nx] gives a tensor [12, nz, ny, nx] (torch's current stream);
+    an Image or a float32 array gives a numpy array [12, nz, ny, nx] (blocking).  units = (ux, uy, uz):
+    by default the Image's units, else (1, 1, 1)."""
+    if _torch_tensor(volume):
+        import torch
         from . import hip
         out = torch.empty((12,) + tuple(volume.shape), dtype=torch.float32, device=volume.device)
-        return hip.dense_descriptors(volume, out, sigma, (1, 1, 1) if units is None else units)
-    if isinstance(volume, Image):
-        if len(volume.shape) != 3:
-            raise ValueError("dense_descriptors: the image must have one channel")
-        im = volume if units is None else Image.from_array(volume.data(), units)
-    else:
-        im = Image.from_array(volume, units)
+        run = hip.dense_descriptors_rotate if rotate else hip.dense_descriptors
+        return run(volume, out, sigma, (1, 1, 1) if units is None else units)
+    im = _dense_image(volume, units, "dense_descriptors")
     out = np.empty((12,) + im.shape, np.float32)
-    if lib().sift3d_amd_image_dense_descriptors(im.h, float(sigma), out.reshape(-1)) != 0:
-        raise RuntimeError("sift3d_amd_image_dense_descriptors failed")
+    name = "sift3d_amd_image_dense_descriptors_rotate" if rotate else "sift3d_amd_image_dense_descriptors"
+    if getattr(lib(), name)(im.h, float(sigma), out.reshape(-1)) != 0:
+        raise RuntimeError("%s failed" % name)
     return out
+
+
+def dense_orientations(volume, sigma=1.6, units=None):
+    """Every voxel's eigen-orientation, as the reference's assign_eig_ori gives a keypoint's (R2 of the
+    rotating dense contract): (R [3, 3, nz, ny, nx] float32, keep [nz, ny, nx] uint8); rejected voxels
+    get R = I and keep = 0.  A torch CUDA float32 tensor gives tensors on its device (torch's current
+    stream); an Image or a float32 array gives numpy arrays (blocking; the volume goes to the device through
+    torch, and without a device this raises RuntimeError, as dense_descriptors does).  units as
+    dense_descriptors."""
+    import torch
+    from . import hip
+    if _torch_tensor(volume):
+        src, u = volume, (1, 1, 1) if units is None else units
+    else:
+        im = _dense_image(volume, units, "dense_orientations")
+        if not device_available():
+            raise RuntimeError("dense_orientations: no HIP device is available; this library has no CPU path")
+        src, u = torch.from_numpy(np.ascontiguousarray(im.data(), np.float32)).cuda(), im.units
+    R = torch.empty((3, 3) + tuple(src.shape), dtype=torch.float32, device=src.device)
+    keep = torch.empty(tuple(src.shape), dtype=torch.uint8, device=src.device)
+    hip.dense_orient(src, R, keep, sigma, u)
+    if src is volume:
+        return R, keep
+    return R.cpu().numpy(), keep.cpu().numpy()

@@ -1063,6 +1063,252 @@ __global__ __launch_bounds__(256) void k_dense_normalize(float *__restrict__ h, 
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Rotation-invariant dense descriptors (sift3d_amd_dense_descriptors_rotate_device, contract in
+// include/sift3d_amd.h): k_dense_rot<false> orients every voxel (assign_eig_ori, R2), k_dense_rot<true>
+// bins the window's gradients rotated into that frame (R3); k_dense_normalize finishes (R4).
+//
+// One voxel per thread, its window walked serially in the reference's scan order, so every sum keeps
+// the reference's order with no hand-over between lanes.  Every centre is a voxel, so the in-sphere
+// offsets and their weights are the same for all voxels: a workgroup builds that table once in LDS
+// (in chunks of whole rows when it is longer than DR_CAP) and each voxel's own sphere bounds
+// (bounds_d: the borders, and the float rounding of c -+ rad / u) only clip it.
+// ---------------------------------------------------------------------------------------
+constexpr int DR_TX = 64, DR_TY = 4, DR_THREADS = DR_TX * DR_TY;   // a tile: 64 x 4 voxels of one plane
+constexpr int DR_CAP = 1024;                                       // table entries per LDS chunk
+constexpr int DR_MAXR = 511;                                       // |offset| limit of the entry packing
+
+struct DrWin {
+    double rad2, sig2;      // (3 sigma)^2, sigma^2
+    float ux, uy, uz;       // (float) units (sift.c:102-104)
+    int mx, my, mz;         // half extents of the search box, <= DR_MAXR
+};
+
+// IM_LOOP_SPHERE's test (sift.c:102-106) of the offset (i, j, l) from a voxel centre
+__device__ __forceinline__ bool dr_in(const DrWin &W, int i, int j, int l, float &sq)
+{
+    const float dx = (float)i * W.ux, dy = (float)j * W.uy, dz = (float)l * W.uz;
+    sq = dx * dx + dy * dy + dz * dz;
+    return !((double)sq > W.rad2);
+}
+
+// the in-sphere i of row (j, l) are -r..r (sq grows with |i| and is even in i); r, or -1 for none
+__device__ __forceinline__ int dr_row_half(const DrWin &W, int j, int l)
+{
+    float sq;
+    if (!dr_in(W, 0, j, l, sq))
+        return -1;
+    const double rem = W.rad2 - (double)sq;
+    int r = min(W.mx, (int)(sqrt(rem > 0.0 ? rem : 0.0) / (double)W.ux));
+    while (r < W.mx && dr_in(W, r + 1, j, l, sq))
+        r++;
+    while (r > 0 && !dr_in(W, r, j, l, sq))
+        r--;
+    return r;
+}
+
+// The window entries of the rows from `row` on that fit in DR_CAP, in scan order (z, y, x): packed
+// offsets (+512, 10 bits each), the weight of sift.c:972, the offset in floats.  Called by the whole
+// workgroup with the same arguments (the row walk is uniform); the caller synchronises.
+__device__ int dr_build(const DrWin &W, int &row, int4 *__restrict__ tab, long long nx, long long plane)
+{
+    const int wy = 2 * W.my + 1, nrows = wy * (2 * W.mz + 1);
+    const int tid = threadIdx.x + DR_TX * threadIdx.y;
+    int n = 0;
+    for (; row < nrows; row++) {
+        const int j = row % wy - W.my, l = row / wy - W.mz;
+        const int r = dr_row_half(W, j, l), len = r < 0 ? 0 : 2 * r + 1;
+        if (n + len > DR_CAP)
+            break;
+        for (int k = tid; k < len; k += DR_THREADS) {
+            const int i = k - r;
+            float sq;
+            dr_in(W, i, j, l, sq);
+            const float w = s3d_expf((float)(-0.5 * (double)sq / W.sig2));   // sift.c:972
+            const long long off = (long long)i + nx * j + plane * l;
+            tab[n + k] = make_int4((i + 512) | ((j + 512) << 10) | ((l + 512) << 20), __float_as_int(w), (int)off,
+                                   (int)(off >> 32));
+        }
+        n += len;
+    }
+    return n;
+}
+
+// BIN = false: R2 -- R (9 planes, (i, j) in plane 3i + j) and keep (may be NULL).
+// BIN = true: R3 -- 12 unnormalised planes into out, from R.
+// Tiles t0 .. t1 - 1 (tile = tx + ntx * (ty + nty * z)), grid-stride over them.
+template <bool BIN>
+__global__ __launch_bounds__(DR_THREADS) void k_dense_rot(const float *__restrict__ src, int nx, int ny, int nz,
+                                                          DrWin W, float iux, float iuy, float iuz, size_t t0,
+                                                          size_t t1, float *__restrict__ Rp,
+                                                          unsigned char *__restrict__ keep, float *__restrict__ out)
+{
+    __shared__ int4 tab[DR_CAP];
+    __shared__ float hist[BIN ? 12 * DR_THREADS : 1];   // thread-private histograms: hist[c * 256 + tid]
+    __shared__ __attribute__((aligned(16))) float sface[BIN ? 20 * FACE_STRIDE : 1];
+    __shared__ int soct[32], svert[20];
+    const int tid = threadIdx.x + DR_TX * threadIdx.y;
+    if constexpr (BIN) {
+        for (int i = tid; i < 20 * 16; i += DR_THREADS)
+            sface[(i >> 4) * FACE_STRIDE + (i & 15)] = c_face16[i];
+        if (tid < 32)
+            soct[tid] = c_oct_face[tid];
+        if (tid < 20)
+            svert[tid] = c_face_vert[tid];
+    }
+    const long long plane = (long long)nx * ny;
+    const size_t N = (size_t)plane * (size_t)nz;
+    const int nrows = (2 * W.my + 1) * (2 * W.mz + 1);
+    int row = 0;
+    int n = dr_build(W, row, tab, nx, plane);
+    const bool single = row >= nrows;               // (uniform) the whole window is in one chunk
+    __syncthreads();
+    const int ntx = (nx + DR_TX - 1) / DR_TX, nty = (ny + DR_TY - 1) / DR_TY;
+    const double rad = sqrt(W.rad2);
+    // the table's real half extents: the widest in-sphere offset on each axis (an entry (i, j, l) inside
+    // implies (i, 0, 0), (0, j, 0) and (0, 0, l) inside: sq only grows with each term)
+    int hx = dr_row_half(W, 0, 0), hy = 0, hz = 0;
+    {
+        float sq;
+        while (hy < W.my && dr_in(W, 0, hy + 1, 0, sq))
+            hy++;
+        while (hz < W.mz && dr_in(W, 0, 0, hz + 1, sq))
+            hz++;
+    }
+    for (size_t t = t0 + blockIdx.x; t < t1; t += gridDim.x) {
+        const int tx = (int)(t % (size_t)ntx), ty = (int)((t / (size_t)ntx) % (size_t)nty);
+        const int z = (int)(t / ((size_t)ntx * nty));
+        const int x = tx * DR_TX + (int)threadIdx.x, y = ty * DR_TY + (int)threadIdx.y;
+        const bool live = x < nx && y < ny;
+        const size_t vox = (size_t)x + (size_t)nx * y + (size_t)plane * z;
+        // this voxel's sphere bounds (sift.c:86-99) as offsets: they clip the table
+        int xs, xe, ys, ye, zs, ze;
+        bounds_d((float)x, rad, W.ux, nx, xs, xe);
+        bounds_d((float)y, rad, W.uy, ny, ys, ye);
+        bounds_d((float)z, rad, W.uz, nz, zs, ze);
+        const int ilo = xs - x, ihi = xe - x, jlo = ys - y, jhi = ye - y, llo = zs - z, lhi = ze - z;
+        const bool whole = ilo <= -hx && ihi >= hx && jlo <= -hy && jhi >= hy && llo <= -hz && lhi >= hz;
+        const bool fast = __all(whole || !live);    // (wave-uniform) no entry of this wave's voxels is clipped
+        const float *pc = src + (live ? vox : 0);
+        // R2 sums (sift.c:978-987), R3 rotation
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
+        float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+        float R[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+        float *hc = hist + tid;
+        if constexpr (BIN) {
+            if (live)
+#pragma unroll
+                for (int k = 0; k < 9; k++)
+                    R[k] = Rp[(size_t)k * N + vox];
+#pragma unroll
+            for (int c = 0; c < 12; c++)
+                hc[c * DR_THREADS] = 0.0f;
+        }
+        // the six samples of the gradient at a window voxel (window voxels are inside 1..n-2)
+        auto fetch = [&](const int4 e, float *q) {
+            const float *p = pc + ((long long)(unsigned)e.z | ((long long)e.w << 32));
+            q[0] = p[1]; q[1] = p[-1]; q[2] = p[nx]; q[3] = p[-(long long)nx]; q[4] = p[plane]; q[5] = p[-plane];
+        };
+        auto body = [&](const int4 e, const float *q) {
+            // IM_GET_GRAD_ISO (sift.c:140-145, immacros.h:105-111)
+            float gx = 0.5f * (q[0] - q[1]);
+            float gy = 0.5f * (q[2] - q[3]);
+            float gz = 0.5f * (q[4] - q[5]);
+            gx = gx * iux; gy = gy * iuy; gz = gz * iuz;
+            const float w = __int_as_float(e.y);
+            if constexpr (!BIN) {
+                const double dx = gx, dy = gy, dz = gz, dw = w;
+                a0 += dx * dx * dw; a1 += dx * dy * dw; a2 += dx * dz * dw;     // sift.c:978-983
+                a3 += dy * dy * dw; a4 += dy * dz * dw; a5 += dz * dz * dw;
+                vx = vx + gx * w; vy = vy + gy * w; vz = vz + gz * w;           // sift.c:986-987
+            } else {
+                gx = gx * w; gy = gy * w; gz = gz * w;                          // SIFT3D_CVEC_SCALE (sift.c:1497)
+                // R^T g (SIFT3D_MUL_MAT_RM_CVEC on the transpose, immacros.h:330; sift.c:1500)
+                const float rx = R[0] * gx + R[3] * gy + R[6] * gz;
+                const float ry = R[1] * gx + R[4] * gy + R[7] * gz;
+                const float rz = R[2] * gx + R[5] * gy + R[8] * gz;
+                float w0, w1, w2;
+                int vid;
+                dense_bin_one(sface, soct, svert, rx, ry, rz, w0, w1, w2, vid);
+                if (vid) {               // (0: below the m2 threshold, nothing to add)
+                    float *h0 = hc + (vid & 15) * DR_THREADS, *h1 = hc + ((vid >> 4) & 15) * DR_THREADS,
+                          *h2 = hc + (vid >> 8) * DR_THREADS;
+                    *h0 = *h0 + w0;
+                    *h1 = *h1 + w1;
+                    *h2 = *h2 + w2;
+                }
+            }
+        };
+        int crow = 0;
+        for (;;) {
+            if (!single) {
+                __syncthreads();
+                n = dr_build(W, crow, tab, nx, plane);
+                __syncthreads();
+            }
+            if (fast) {
+                if (live)
+                    for (int k = 0; k < n; k++) {
+                        float q[6];
+                        fetch(tab[k], q);
+                        body(tab[k], q);
+                    }
+            } else if (live) {
+                for (int k = 0; k < n; k++) {
+                    const int4 e = tab[k];
+                    const int i = (e.x & 1023) - 512, j = ((e.x >> 10) & 1023) - 512, l = ((e.x >> 20) & 1023) - 512;
+                    if (i >= ilo && i <= ihi && j >= jlo && j <= jhi && l >= llo && l <= lhi) {
+                        float q[6];
+                        fetch(e, q);
+                        body(e, q);
+                    }
+                }
+            }
+            if (single || crow >= nrows)
+                break;
+        }
+        if (!live)
+            continue;
+        if constexpr (BIN) {
+#pragma unroll
+            for (int c = 0; c < 12; c++)
+                out[(size_t)c * N + vox] = hc[c * DR_THREADS];
+        } else {
+            // assign_eig_ori's decision (sift.c:997-1060), as orient_serial, without the corner threshold
+            int kept = 0;
+            if (!(vx * vx + vy * vy + vz * vz < (float)1E-10)) {             // sift.c:997
+                double A[9] = { a0, a1, a2, a1, a3, a4, a2, a4, a5 }, Q[9], Lm[3];
+                s3d_eigen3(A, Q, Lm);                                       // eigen_Mat_rm, imutil.c:984
+                if (!(fabs(Lm[0] / Lm[1]) > 0.90 || fabs(Lm[1] / Lm[2]) > 0.90)) { // sift.c:1011-1015
+                    float v[2][3], S[9];
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const int e = 2 - i;
+                        float ex = (float)Q[0 * 3 + e], ey = (float)Q[1 * 3 + e], ez = (float)Q[2 * 3 + e];
+                        const double d = (double)(vx * ex + vy * ey + vz * ez);   // sift.c:1029
+                        const float sgn = d > 0.0 ? 1.0f : -1.0f;                 // sift.c:1038-1042
+                        ex = ex * sgn; ey = ey * sgn; ez = ez * sgn;
+                        S[0 * 3 + i] = ex; S[1 * 3 + i] = ey; S[2 * 3 + i] = ez;
+                        v[i][0] = ex; v[i][1] = ey; v[i][2] = ez;
+                    }
+                    S[0 * 3 + 2] = v[0][1] * v[1][2] - v[0][2] * v[1][1];           // sift.c:1054-1059
+                    S[1 * 3 + 2] = v[0][2] * v[1][0] - v[0][0] * v[1][2];
+                    S[2 * 3 + 2] = v[0][0] * v[1][1] - v[0][1] * v[1][0];
+#pragma unroll
+                    for (int k = 0; k < 9; k++)
+                        R[k] = S[k];
+                    kept = 1;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 9; k++)
+                Rp[(size_t)k * N + vox] = R[k];
+            if (keep)
+                keep[vox] = (unsigned char)kept;
+        }
+    }
+}
+
 extern "C" {
 
 // host twin of face_eval's acceptance test (same float expressions; this file is compiled with
@@ -1438,6 +1684,80 @@ int sift3d_hip_dense_normalize(float *d_hist, size_t n, void *stream)
         hipLaunchKernelGGL(k_dense_normalize<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_hist, n);
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;
+}
+
+// A launch covers about this many (voxel, window voxel) pairs, so that each launch stays short on a shared
+// device (see DESIGN.md 3.5 for the measured rates).  The smallest launch is one tile, whose waves walk
+// the whole window serially: DR_MAX_WIN bounds that walk (measured: DESIGN.md 3.5), so that no launch
+// is expected to last much above 100 ms.  A wider window is refused, not run in one long launch.
+static const double DR_PAIRS_PER_LAUNCH = 4.0e9;
+static const double DR_MAX_WIN = 20000.0;
+
+static int dense_rot(bool bin, const char *what, const float *d_src, int nx, int ny, int nz, double ux, double uy,
+                     double uz, double sigma, float *d_R, unsigned char *d_keep, float *d_out, void *stream)
+{
+    if (!d_src || !d_R || (bin && !d_out))
+        return dense_fail(what, "NULL argument");
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return dense_fail(what, "dimensions must be positive");
+    if (!(std::isfinite(sigma) && sigma > 0))
+        return dense_fail(what, "sigma must be positive and finite");
+    if (!(std::isfinite(ux) && ux > 0 && std::isfinite(uy) && uy > 0 && std::isfinite(uz) && uz > 0))
+        return dense_fail(what, "units must be positive and finite");
+    DrWin W;
+    W.ux = (float)ux; W.uy = (float)uy; W.uz = (float)uz;
+    const double rad = 3.0 * sigma;                    // ori_rad_fctr, sift.c:936
+    W.rad2 = rad * rad;
+    W.sig2 = sigma * sigma;
+    const double ex = rad / (double)W.ux + 2.0, ey = rad / (double)W.uy + 2.0, ez = rad / (double)W.uz + 2.0;
+    if (!(W.ux > 0 && W.uy > 0 && W.uz > 0) || !(ex <= DR_MAXR && ey <= DR_MAXR && ez <= DR_MAXR))
+        return dense_fail(what, "the window is wider than 509 voxels on an axis");
+    W.mx = (int)ex; W.my = (int)ey; W.mz = (int)ez;
+    // expected window voxels: the sphere's volume in voxels
+    const double win = 4.18879020478639 * (rad / W.ux) * (rad / W.uy) * (rad / W.uz) + 1.0;
+    if (!(win <= DR_MAX_WIN))
+        return dense_fail(what, "the window holds more than 20000 voxels");
+    const size_t n = (size_t)nx * ny * nz;
+    {
+        auto ov = [](const void *a, size_t na, const void *b, size_t nb) {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return b && a0 < b0 + nb && b0 < a0 + na;
+        };
+        const size_t fb = sizeof(float);
+        if (ov(d_R, 9 * n * fb, d_src, n * fb) || (d_keep && (ov(d_keep, n, d_src, n * fb) || ov(d_keep, n, d_R, 9 * n * fb))) ||
+            (bin && (ov(d_out, 12 * n * fb, d_src, n * fb) || ov(d_out, 12 * n * fb, d_R, 9 * n * fb))))
+            return dense_fail(what, "buffers overlap");
+    }
+    const float iux = 1.0f / W.ux, iuy = 1.0f / W.uy, iuz = 1.0f / W.uz;   // IM_GET_GRAD_ISO, sift.c:143-145
+    const size_t ntiles = (size_t)((nx + DR_TX - 1) / DR_TX) * (size_t)((ny + DR_TY - 1) / DR_TY) * (size_t)nz;
+    const double per = DR_PAIRS_PER_LAUNCH / ((double)DR_THREADS * win);
+    const size_t step = per >= (double)ntiles ? ntiles : per < 1.0 ? 1 : (size_t)per;
+    for (size_t t0 = 0; t0 < ntiles; t0 += step) {
+        const size_t t1 = std::min(ntiles, t0 + step);
+        const unsigned grid = (unsigned)std::min<size_t>(t1 - t0, 4096);
+        if (bin)
+            hipLaunchKernelGGL(k_dense_rot<true>, dim3(grid), dim3(DR_TX, DR_TY), 0, (hipStream_t)stream, d_src, nx, ny,
+                               nz, W, iux, iuy, iuz, t0, t1, d_R, nullptr, d_out);
+        else
+            hipLaunchKernelGGL(k_dense_rot<false>, dim3(grid), dim3(DR_TX, DR_TY), 0, (hipStream_t)stream, d_src, nx,
+                               ny, nz, W, iux, iuy, iuz, t0, t1, d_R, d_keep, nullptr);
+        LAUNCH_CHECK();
+    }
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_hip_dense_orient(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz, double sigma,
+                            float *d_R, unsigned char *d_keep, void *stream)
+{
+    return dense_rot(false, "sift3d_hip_dense_orient", d_src, nx, ny, nz, ux, uy, uz, sigma, d_R, d_keep, nullptr,
+                     stream);
+}
+
+int sift3d_hip_dense_rotate_bin(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz,
+                                double sigma, const float *d_R, float *d_out, void *stream)
+{
+    return dense_rot(true, "sift3d_hip_dense_rotate_bin", d_src, nx, ny, nz, ux, uy, uz, sigma,
+                     const_cast<float *>(d_R), nullptr, d_out, stream);
 }
 
 } // extern "C"

@@ -100,6 +100,13 @@ def lib():
         "sift3d_amd_dense_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
         "sift3d_amd_dense_descriptors_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                                           C.c_double, vp, vp, vp]),
+        "sift3d_hip_dense_orient": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                              C.c_double, vp, vp, vp]),
+        "sift3d_hip_dense_rotate_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                  C.c_double, C.c_double, vp, vp, vp]),
+        "sift3d_amd_dense_rotate_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_dense_descriptors_rotate_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int,
+                                                                 C.POINTER(C.c_double), C.c_double, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -253,6 +260,65 @@ def dense_descriptors(src, out, sigma, units=(1, 1, 1), work=None):
     _check(lib().sift3d_amd_dense_descriptors_device(src.data_ptr(), nx, ny, nz, u, float(sigma), out.data_ptr(),
                                                      work.data_ptr(), current_stream()),
            "sift3d_amd_dense_descriptors_device")
+    return out
+
+
+def _dense_r(src, R):
+    import torch
+    nz, ny, nx = src.shape
+    if not (isinstance(R, torch.Tensor) and R.is_cuda and R.dtype == torch.float32 and R.is_contiguous()
+            and tuple(R.shape) == (3, 3, nz, ny, nx) and R.device == src.device):
+        raise ValueError("R must be a contiguous float32 CUDA tensor [3, 3, nz, ny, nx] on the device of src")
+
+
+def dense_orient(src, R, keep=None, sigma=1.6, units=(1, 1, 1)):
+    """R2 of the rotating dense contract (sift3d_hip_dense_orient): every voxel's eigen-orientation R
+    [3, 3, nz, ny, nx] float32 and keep [nz, ny, nx] uint8 (or None) from src [nz, ny, nx], torch CUDA
+    tensors, on torch's current stream."""
+    import torch
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32 and src.is_contiguous()
+            and src.dim() == 3):
+        raise ValueError("dense_orient: src must be a contiguous float32 CUDA tensor [nz, ny, nx]")
+    _dense_r(src, R)
+    if keep is not None and not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.dtype == torch.uint8
+                                 and keep.is_contiguous() and keep.shape == src.shape and keep.device == src.device):
+        raise ValueError("dense_orient: keep must be a contiguous uint8 CUDA tensor shaped like src, or None")
+    nz, ny, nx = src.shape
+    _check(lib().sift3d_hip_dense_orient(src.data_ptr(), nx, ny, nz, *map(float, units), float(sigma), R.data_ptr(),
+                                         None if keep is None else keep.data_ptr(), current_stream()),
+           "sift3d_hip_dense_orient")
+    return R, keep
+
+
+def dense_rotate_bin(src, R, out, sigma=1.6, units=(1, 1, 1)):
+    """R3 of the rotating dense contract (sift3d_hip_dense_rotate_bin): unnormalised histograms out
+    [12, nz, ny, nx] of src's window gradients rotated by R^T, on torch's current stream."""
+    nx, ny, nz = _dense_args(src, out, "dense_rotate_bin")
+    _dense_r(src, R)
+    _check(lib().sift3d_hip_dense_rotate_bin(src.data_ptr(), nx, ny, nz, *map(float, units), float(sigma),
+                                             R.data_ptr(), out.data_ptr(), current_stream()),
+           "sift3d_hip_dense_rotate_bin")
+    return out
+
+
+def dense_descriptors_rotate(src, out, sigma, units=(1, 1, 1), work=None):
+    """Rotation-invariant dense descriptor image (sift3d_amd_dense_descriptors_rotate_device): out
+    [12, nz, ny, nx] from src [nz, ny, nx], torch CUDA float32, on torch's current stream.  work: a float32
+    CUDA tensor of at least sift3d_amd_dense_rotate_work_floats elements (9 * nz*ny*nx), or None to
+    allocate one here."""
+    import torch
+    nx, ny, nz = _dense_args(src, out, "dense_descriptors_rotate")
+    need = lib().sift3d_amd_dense_rotate_work_floats(nx, ny, nz)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float32, device=src.device)
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.float32
+            and work.is_contiguous() and work.numel() >= need and work.device == src.device):
+        raise ValueError("dense_descriptors_rotate: work must be a contiguous float32 CUDA tensor of >= %d "
+                         "elements on the device of src" % need)
+    u = (C.c_double * 3)(*map(float, units))
+    _check(lib().sift3d_amd_dense_descriptors_rotate_device(src.data_ptr(), nx, ny, nz, u, float(sigma),
+                                                            out.data_ptr(), work.data_ptr(), current_stream()),
+           "sift3d_amd_dense_descriptors_rotate_device")
     return out
 
 
