@@ -240,6 +240,68 @@ sift3d_amd_image_warp_affine(const sift3d_image *src, const double *A, int inter
 SIFT3D_AMD_API int sift3d_amd_affine_invert(const double *A /*12*/, double *Ainv /*12*/);
 
 /* ------------------------------------------------------------------------ */
+/* Thin-plate spline: a smooth deformable pull map                            */
+/* ------------------------------------------------------------------------ */
+/* A PULL map in voxel units, like sift3d_hip_warp_affine: output (fixed-grid) voxel p = (x, y, z) reads
+ * the source (moving volume) at q(p).  Control points c_i (fixed voxels, i = 0 .. m-1), weights
+ * w_i in R^3 and an affine A (3 x 4, row-major):
+ *   q_d(p)      = affine_d(p) + (double) s_d(p)
+ *   affine_d(p) = A[d][0] x + ((A[d][1] y + A[d][2] z) + A[d][3])     double, warp_affine's order
+ *   s_d(p)      = float sum over i = 0 .. m-1 in this order, from 0.0f:  s_d = s_d + w_i,d * (-r_i),
+ *                 r_i = sqrtf((dx dx + dy dy) + dz dz), dx = (float) x - cx_i, ...  (float, unfused,
+ *                 correctly rounded sqrt)
+ * The radial basis is phi(r) = -r (the 3-D biharmonic kernel, with the sign that makes it conditionally
+ * positive definite); the weights keep their sign in the contract and in sift3d_amd_tps_fit, and the
+ * DEVICE layout stores them negated (s + (-w) r equals s + w (-r) bit for bit).  c_i and w_i above are
+ * the float32 values of the device layout (sift3d_amd_tps_pack): per point SIFT3D_AMD_TPS_FLOATS floats
+ *   { (float) cx, (float) cy, (float) cz, 0, -(float) wx, -(float) wy, -(float) wz, 0 }.
+ * Inside test, `fill`, LINEAR and NEAREST sampling at q are sift3d_hip_warp_affine's, word for word.  With
+ * all weights zero the result is warp_affine's with the same A, bit for bit. */
+#define SIFT3D_AMD_TPS_MAX_POINTS 16384
+#define SIFT3D_AMD_TPS_FLOATS 8
+/* Fit q = TPS(p) to n point pairs src[i] (fixed voxels) -> dst[i] (moving voxels), n x 3 doubles each.
+ * Solves [Phi + lambda I, P; P^T, 0] [w; a] = [dst; 0] in double (Phi_ij = phi(|c_i - c_j|),
+ * P = [1 x y z], lambda = smoothing): QR of P, Cholesky of the projected (m - 4)^2 block.
+ *   - exact duplicate src points are dropped, the lowest index kept;
+ *   - when more than max_points remain, greedy farthest-point sampling over src thins them: start at the
+ *     first remaining index; repeatedly add the remaining point whose squared distance
+ *     (dx dx + dy dy) + dz dz (double) to its nearest chosen point is largest, the lowest index on ties;
+ *   - the control points keep their input order (ascending index).
+ * Outputs: ctrl (m x 3), weights (m x 3), A (12), *m; ctrl and weights hold max_points rows.
+ * -1 and no output written on: NULL pointers, n < 5, non-finite input, smoothing < 0 or not finite,
+ * max_points < 5 or > SIFT3D_AMD_TPS_MAX_POINTS, fewer than 5 distinct points, coplanar control points,
+ * a failed factorisation or allocation.  OpenMP team of at most 16 threads; the result does not depend
+ * on the team size. */
+SIFT3D_AMD_API int
+sift3d_amd_tps_fit(const double *src, const double *dst, int n, double smoothing, int max_points,
+                   double *ctrl, double *weights, double *A /*12*/, int *m);
+/* q(p) for n points p (n x 3 doubles) in double: affine_d(p) + sum_i w_i,d phi(|p - c_i|), for checking
+ * fits.  -1 on NULL pointers, m < 1 or n < 0. */
+SIFT3D_AMD_API int
+sift3d_amd_tps_apply(const double *ctrl, const double *weights, const double *A, int m, const double *p,
+                     int n, double *q);
+/* the device layout of m points: out holds m * SIFT3D_AMD_TPS_FLOATS floats.  -1 on NULL, m < 1,
+ * m > SIFT3D_AMD_TPS_MAX_POINTS, or a value that is not finite in float. */
+SIFT3D_AMD_API int
+sift3d_amd_tps_pack(const double *ctrl, const double *weights, int m, float *out);
+/* device buffers, asynchronous on `stream`, no allocation.  d_tps: the packed layout (16-byte aligned),
+ * 1 <= m <= SIFT3D_AMD_TPS_MAX_POINTS.  The output is split into launches of consecutive tiles
+ * (64 x 4 x 8 voxels, numbered x, y, then z: whole z-ranges whenever one 8-plane slab fits) so that no
+ * launch is estimated above ~50 ms; the split does not change any result.  Arguments are checked
+ * before any device call (-1 on NULL pointers, dims <= 0, m out of range, an unknown interp, a
+ * non-finite A, a misaligned d_tps, a destination that overlaps the source or d_tps). */
+SIFT3D_AMD_API int
+sift3d_hip_warp_tps(const float *d_src, int nx, int ny, int nz, float *d_dst, int ox, int oy, int oz,
+                    const double *A /*12*/, const float *d_tps, int m, int interp, float fill, void *stream);
+/* the number of launches sift3d_hip_warp_tps makes for this output grid and m (-1 for bad arguments) */
+SIFT3D_AMD_API int sift3d_hip_warp_tps_launches(int ox, int oy, int oz, int m);
+/* host image objects (nc == 1), tps in the packed layout on the host; the output grid is dst's;
+ * blocking.  Also refuses non-finite packed values. */
+SIFT3D_AMD_API int
+sift3d_amd_image_warp_tps(const sift3d_image *src, const double *A, const float *tps, int m, int interp,
+                          float fill, sift3d_image *dst);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -2445,3 +2445,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* dense descriptor images */
 #include "sift3d_dense.c"
+
+/* thin-plate spline: fit, evaluation, device layout, warp of host images */
+#include "sift3d_tps.c"

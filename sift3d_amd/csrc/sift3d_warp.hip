@@ -170,6 +170,118 @@ int warp_fail(const char *why)
     return SIFT3D_FAILURE;
 }
 
+// ---- thin-plate spline: q(p) = affine(p) + (double) s(p), s = sum_i w_i phi(|p - c_i|) ------------------------
+// (contract: include/sift3d_amd.h, "Thin-plate spline").  The radial sum is compute-bound: per voxel-point
+// 3 differences, 3 squares, 2 adds, a correctly rounded sqrt and 3 multiply-adds, all float, unfused.
+//   - a lane keeps TPS_K voxels of one (x, y) column in flight (z = z_tile .. + TPS_K - 1): dx, dy and
+//     dx*dx + dy*dy are the same for all of them, so each point costs 5 instructions per lane plus per voxel
+//     dz, dz*dz, the add, the sqrt and the 3 multiply-adds; the per-voxel part runs on pairs of voxels with
+//     packed f32 arithmetic (v_pk_add_f32 / v_pk_mul_f32), everything but the sqrt;
+//   - the points are wave-uniform: the loop reads them through the constant address space, so they come
+//     in by scalar loads (one 32-byte record per point) and every lane uses the same c_i, w_i;
+//   - a wave is 64 consecutive x of one row, so that the gathers of neighbouring lanes touch neighbouring
+//     source addresses and each plane's results leave with one coalesced 256-byte store;
+//   - a 256-lane workgroup makes a 64 x 4 x TPS_K tile.  Tiles are numbered x fastest, then y, then z, and a
+//     launch covers a contiguous range of them: whole z-slabs (z-ranges) whenever one slab fits the launch
+//     budget (tps_tiles_per_launch).
+// The device layout (sift3d_amd_tps_pack) holds per point {cx, cy, cz, 0, -wx, -wy, -wz, 0}: the sign of
+// phi(r) = -r is folded into the weights, and s + (-w) * r is w * (-r) added to s, bit for bit.
+constexpr int TPS_K = 8;                          // voxels per lane, along z
+constexpr int TPS_TX = 64, TPS_TY = 4;            // a wave per row, 4 rows per workgroup
+constexpr int TPS_TILE = TPS_TX * TPS_TY * TPS_K;
+constexpr unsigned TPS_MAX_GRID = 1u << 24;       // blocks per launch
+// launch budget: no launch is estimated above TPS_BUDGET_S at TPS_S_PER_VOXEL_POINT machine-wide (measured on an
+// MI355X at 512^3: 0.54 ps for m = 256 .. 4096, profiles/microbench/tps_rate_mi355x.txt; rounded up)
+constexpr double TPS_BUDGET_S = 50e-3;
+constexpr double TPS_S_PER_VOXEL_POINT = 0.60e-12;
+
+struct TpsArgs {
+    WarpArgs w;                                  // the affine, the source, the grids, fill (w.vec unused)
+    const float *tps;                            // 8 floats per point (sift3d_amd_tps_pack)
+    int m;
+    int tiles_x, tiles_y;
+    unsigned t0;                                 // this launch: tiles t0 .. t0 + gridDim.x - 1
+};
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(4))) float *tps_cptr;    // constant address space: scalar loads
+
+template <int LINEAR>
+__global__ __launch_bounds__(256) void k_warp_tps(const TpsArgs p)
+{
+    const unsigned t = p.t0 + blockIdx.x;
+    const unsigned tyz = t / (unsigned)p.tiles_x;
+    const int tx = (int)(t - tyz * (unsigned)p.tiles_x);
+    const int ty = (int)(tyz % (unsigned)p.tiles_y), tz = (int)(tyz / (unsigned)p.tiles_y);
+    const int x = tx * TPS_TX + (int)(threadIdx.x & 63), y = ty * TPS_TY + (int)(threadIdx.x >> 6);
+    const int z0 = tz * TPS_K;
+    // lanes past the grid compute (the source reads stay inside it: sample<> is branch-free) and do not store
+    const float xf = (float)x, yf = (float)y;
+    f32x2 zf[TPS_K / 2], sx[TPS_K / 2], sy[TPS_K / 2], sz[TPS_K / 2];
+#pragma unroll
+    for (int k = 0; k < TPS_K / 2; k++) {
+        zf[k] = f32x2{(float)(z0 + 2 * k), (float)(z0 + 2 * k + 1)};
+        sx[k] = sy[k] = sz[k] = f32x2{0.0f, 0.0f};
+    }
+    const tps_cptr pt = (tps_cptr)p.tps;
+#pragma unroll 2
+    for (int i = 0; i < p.m; i++) {
+        const tps_cptr q = pt + SIFT3D_AMD_TPS_FLOATS * i;
+        const float cx = q[0], cy = q[1], cz = q[2];
+        const float wx = q[4], wy = q[5], wz = q[6];                    // -w_i: the sign of phi folded in
+        const float dx = xf - cx, dy = yf - cy;
+        const float hxy = dx * dx + dy * dy;
+#pragma unroll
+        for (int k = 0; k < TPS_K / 2; k++) {
+            const f32x2 dz = zf[k] - cz;
+            const f32x2 r2 = hxy + dz * dz;
+            const f32x2 r = f32x2{sqrtf(r2.x), sqrtf(r2.y)};           // correctly rounded (no -ffast-math)
+            sx[k] = sx[k] + wx * r;
+            sy[k] = sy[k] + wy * r;
+            sz[k] = sz[k] + wz * r;
+        }
+    }
+    // affine part once per column: r_d = (A[d][1] y + A[d][2] z) + A[d][3] depends on z, so it is per voxel
+    const double xd = (double)x, yd = (double)y;
+    const bool col = x < p.w.ox && y < p.w.oy;
+    float *out = p.w.dst + ((size_t)z0 * (size_t)p.w.oy + (size_t)y) * (size_t)p.w.ox + (size_t)x;
+    const size_t plane = (size_t)p.w.oy * (size_t)p.w.ox;
+#pragma unroll
+    for (int k = 0; k < TPS_K; k++) {
+        const double zd = (double)(z0 + k);
+        const float rx = (k & 1) ? sx[k / 2].y : sx[k / 2].x;
+        const float ry = (k & 1) ? sy[k / 2].y : sy[k / 2].x;
+        const float rz = (k & 1) ? sz[k / 2].y : sz[k / 2].x;
+        const double qx = p.w.a[0] * xd + ((p.w.a[1] * yd + p.w.a[2] * zd) + p.w.a[3]) + (double)rx;
+        const double qy = p.w.a[4] * xd + ((p.w.a[5] * yd + p.w.a[6] * zd) + p.w.a[7]) + (double)ry;
+        const double qz = p.w.a[8] * xd + ((p.w.a[9] * yd + p.w.a[10] * zd) + p.w.a[11]) + (double)rz;
+        const float v = sample<LINEAR>(p.w, qx, qy, qz);
+        if (col && z0 + k < p.w.oz)
+            out[(size_t)k * plane] = v;
+    }
+}
+
+int tps_fail(const char *why)
+{
+    snprintf(g_err, sizeof(g_err), "sift3d_hip_warp_tps: %s", why);
+    fprintf(stderr, "sift3d_amd: %s\n", g_err);
+    return SIFT3D_FAILURE;
+}
+
+// tiles per launch: as many as the budget allows (at least one), rounded down to whole z-slabs when a slab fits
+unsigned long long tps_tiles_per_launch(int ox, int oy, int m)
+{
+    const unsigned long long slab = (unsigned long long)((ox + TPS_TX - 1) / TPS_TX) * ((oy + TPS_TY - 1) / TPS_TY);
+    const double per_tile = (double)TPS_TILE * (double)m * TPS_S_PER_VOXEL_POINT;
+    double n = floor(TPS_BUDGET_S / per_tile);
+    if (n > (double)TPS_MAX_GRID)
+        n = (double)TPS_MAX_GRID;
+    unsigned long long c = n < 1.0 ? 1ull : (unsigned long long)n;
+    if (c >= slab)
+        c -= c % slab;
+    return c;
+}
+
 } // namespace
 
 extern "C" {
@@ -217,6 +329,71 @@ int sift3d_hip_warp_affine(const float *d_src, int nx, int ny, int nz, float *d_
                                                                    : k_warp_affine<1>;
     hipLaunchKernelGGL(k, g, b, 0, st, p);
     LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_hip_warp_tps_launches(int ox, int oy, int oz, int m)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0 || m < 1 || m > SIFT3D_AMD_TPS_MAX_POINTS)
+        return -1;
+    const unsigned long long nt = (unsigned long long)((ox + TPS_TX - 1) / TPS_TX) * ((oy + TPS_TY - 1) / TPS_TY) *
+                                  ((oz + TPS_K - 1) / TPS_K);
+    const unsigned long long c = tps_tiles_per_launch(ox, oy, m);
+    const unsigned long long n = (nt + c - 1) / c;
+    return n > 0x7fffffffull ? -1 : (int)n;
+}
+
+int sift3d_hip_warp_tps(const float *d_src, int nx, int ny, int nz, float *d_dst, int ox, int oy, int oz,
+                        const double *A, const float *d_tps, int m, int interp, float fill, void *stream)
+{
+    if (!d_src || !d_dst || !A || !d_tps)
+        return tps_fail("NULL argument");
+    if (nx <= 0 || ny <= 0 || nz <= 0 || ox <= 0 || oy <= 0 || oz <= 0)
+        return tps_fail("dimensions must be positive");
+    if (m < 1 || m > SIFT3D_AMD_TPS_MAX_POINTS)
+        return tps_fail("the number of control points must be in [1, SIFT3D_AMD_TPS_MAX_POINTS]");
+    if (interp != SIFT3D_AMD_INTERP_NEAREST && interp != SIFT3D_AMD_INTERP_LINEAR)
+        return tps_fail("unknown interpolation mode");
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(A[i]))
+            return tps_fail("the affine map is not finite");
+    if ((uintptr_t)d_tps & 15)
+        return tps_fail("the control point records are not 16-byte aligned");
+    {
+        const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst, c0 = (uintptr_t)d_tps;
+        const uintptr_t s1 = s0 + (size_t)nx * ny * nz * sizeof(float), d1 = d0 + (size_t)ox * oy * oz * sizeof(float);
+        const uintptr_t c1 = c0 + (size_t)m * SIFT3D_AMD_TPS_FLOATS * sizeof(float);
+        if ((s0 < d1 && d0 < s1) || (c0 < d1 && d0 < c1))
+            return tps_fail("the destination overlaps the source or the control points");
+    }
+    TpsArgs p;
+    for (int i = 0; i < 12; i++)
+        p.w.a[i] = A[i];
+    p.w.src = d_src;
+    p.w.dst = d_dst;
+    p.w.nx = nx; p.w.ny = ny; p.w.nz = nz;
+    p.w.ox = ox; p.w.oy = oy; p.w.oz = oz;
+    p.w.fill = fill;
+    p.w.tiles_x = p.w.tiles_y = 0;              // k_warp_affine's tiling, unused here
+    p.w.ntiles = 0;
+    p.w.vec = 0;
+    p.tps = d_tps;
+    p.m = m;
+    p.tiles_x = (ox + TPS_TX - 1) / TPS_TX;
+    p.tiles_y = (oy + TPS_TY - 1) / TPS_TY;
+    const unsigned long long nt = (unsigned long long)p.tiles_x * p.tiles_y * ((oz + TPS_K - 1) / TPS_K);
+    if (nt > 0xffffffffull)
+        return tps_fail("output grid too large");
+    const unsigned long long chunk = tps_tiles_per_launch(ox, oy, m);
+    hipStream_t st = (hipStream_t)stream;
+    void (*k)(const TpsArgs) = interp == SIFT3D_AMD_INTERP_NEAREST ? k_warp_tps<0>
+                               : nx >= 2                          ? k_warp_tps<2>
+                                                                  : k_warp_tps<1>;
+    for (unsigned long long t0 = 0; t0 < nt; t0 += chunk) {
+        p.t0 = (unsigned)t0;
+        hipLaunchKernelGGL(k, dim3((unsigned)(nt - t0 < chunk ? nt - t0 : chunk)), dim3(256), 0, st, p);
+        LAUNCH_CHECK();
+    }
     return SIFT3D_SUCCESS;
 }
 

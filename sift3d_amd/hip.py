@@ -94,6 +94,9 @@ def lib():
         "sift3d_hip_synth_lattice": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]),
         "sift3d_hip_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                              C.POINTER(C.c_double), C.c_int, C.c_float, vp]),
+        "sift3d_hip_warp_tps": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_double), vp, C.c_int, C.c_int, C.c_float, vp]),
+        "sift3d_hip_warp_tps_launches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -205,6 +208,38 @@ def warp_affine(src, dst, A, interp="linear", fill=0.0):
                                         a.ctypes.data_as(C.POINTER(C.c_double)), INTERP[interp],
                                         float(fill), current_stream()), "sift3d_hip_warp_affine")
     return dst
+
+
+def warp_tps(src, dst, tps, interp="linear", fill=0.0):
+    """dst[z, y, x] = src sampled at the thin-plate spline q(x, y, z) (sift3d_hip_warp_tps; contract in
+    include/sift3d_amd.h): torch CUDA float32 contiguous tensors [nz, ny, nx] / [oz, oy, ox], on torch's
+    current stream.  tps is an api.TPS (ctrl, weights, A), packed into the device layout by
+    sift3d_amd_tps_pack and uploaded; voxels that sample outside src get `fill`."""
+    import torch
+    from . import api
+    for t in (src, dst):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.dim() == 3):
+            raise ValueError("warp_tps: src and dst must be contiguous 3-D float32 CUDA tensors")
+    if src.device != dst.device:
+        raise ValueError("warp_tps: src and dst are on different devices")
+    if interp not in INTERP:
+        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    a = np.ascontiguousarray(tps.A, np.float64).reshape(12)
+    packed = api.tps_pack(tps.ctrl, tps.weights)
+    d_tps = torch.from_numpy(packed).to(src.device)
+    nz, ny, nx = src.shape
+    oz, oy, ox = dst.shape
+    _check(lib().sift3d_hip_warp_tps(src.data_ptr(), nx, ny, nz, dst.data_ptr(), ox, oy, oz,
+                                     a.ctypes.data_as(C.POINTER(C.c_double)), d_tps.data_ptr(), len(packed),
+                                     INTERP[interp], float(fill), current_stream()), "sift3d_hip_warp_tps")
+    return dst
+
+
+def warp_tps_launches(out_shape, m):
+    """How many launches sift3d_hip_warp_tps splits an output grid (oz, oy, ox) with m points into."""
+    oz, oy, ox = out_shape
+    return int(lib().sift3d_hip_warp_tps_launches(ox, oy, oz, m))
 
 
 def _dense_args(src, out, what):
