@@ -302,6 +302,66 @@ sift3d_amd_image_warp_tps(const sift3d_image *src, const double *A, const float 
                           float fill, sift3d_image *dst);
 
 /* ------------------------------------------------------------------------ */
+/* Displacement fields: export, resampling through a field, Jacobian         */
+/* ------------------------------------------------------------------------ */
+/* A displacement field is float u[3][oz][oy][ox], planar: channel 0 holds x, 1 y, 2 z, in source (moving)
+ * voxels.  It is a PULL map, as for the warps above: output voxel p = (x, y, z) reads the source at
+ * q(p) = p + u(p).  Voxel units only (physical / anisotropic spacing is the caller's job).
+ *
+ * Export (p_d is x, y or z as a double; q_d as in the blocks above):
+ *   affine : u_d = (float)(q_d - (double) p_d), q_d = A[d][0] x + ((A[d][1] y + A[d][2] z) + A[d][3])
+ *            (double, warp_affine's order, unfused)
+ *   TPS    : u_d = (float)((affine_d(p) + (double) s_d(p)) - (double) p_d), s_d the float radial sum of
+ *            "Thin-plate spline" (point order, from 0.0f, unfused, correctly rounded sqrtf).  With all weights
+ *            zero this is the affine export bit for bit (but for the sign of a zero: an affine_d that is
+ *            exactly -0.0 at p_d = 0 becomes +0.0, as adding (double) 0.0f does).
+ * Resampling through a field (nc >= 1 channels, src [nc][nz][ny][nx], dst [nc][oz][oy][ox]): every channel
+ * is sampled at the same point
+ *   q_d = (double) p_d + (double) u_d(p)
+ * with sift3d_hip_warp_affine's inside test, `fill`, LINEAR and NEAREST, word for word (a NaN in the field
+ * samples outside).  So channel c of an nc-channel warp is the single-channel warp of channel c, and when
+ * every u is exact (u = (float)(q - p) with no rounding: the affine field of the identity, of an integer
+ * translation, of axis permutations / flips) the result is warp_affine's with that A, bit for bit.
+ * Jacobian determinant of q(p), per voxel, float unless stated:
+ *   1. g_de = d u_d / d x_e by numpy.gradient's rules: (u[i+1] - u[i-1]) * 0.5f inside, u[1] - u[0] and
+ *      u[n-1] - u[n-2] at the ends, 0 on an axis of length 1;
+ *   2. j_de = (d == e ? 1.0f : 0.0f) + g_de;
+ *   3. det = j00 (j11 j22 - j12 j21) - j01 (j10 j22 - j12 j20) + j02 (j10 j21 - j11 j20) in double, this
+ *      order, unfused, from the float j; 4. rounded to float.
+ * Stats (SIFT3D_AMD_JACOBIAN_STATS_BYTES of device memory, 8-byte aligned; after the call completes):
+ *   bytes 0-7  : uint64 folded, the number of voxels with !(det > 0) (a NaN counts as folded);
+ *   bytes 8-11 : float min, bytes 12-15: float max, of the non-NaN dets (+inf / -inf when there is none).
+ * All three are order-independent, so the result does not depend on the reduction.  The buffer is
+ * initialised on `stream` by the call; its content while the call runs is not the result.
+ * All device entries are asynchronous on `stream`, allocate nothing, use 64-bit offsets and check their
+ * arguments before any device call (-1 on NULL pointers, dims <= 0, nc < 1, m out of range, an unknown
+ * interp, a non-finite A, misalignment: d_tps 16 B, d_stats 8 B, the rest 4 B; an output that overlaps
+ * an input or another output). */
+#define SIFT3D_AMD_JACOBIAN_STATS_BYTES 16
+SIFT3D_AMD_API int sift3d_hip_affine_field(float *d_field, int ox, int oy, int oz, const double *A /*12*/,
+                                           void *stream);
+/* d_tps: the packed layout of "Thin-plate spline".  Launches are split as sift3d_hip_warp_tps's; the split
+ * does not change any result. */
+SIFT3D_AMD_API int sift3d_hip_tps_field(float *d_field, int ox, int oy, int oz, const double *A /*12*/,
+                                        const float *d_tps, int m, void *stream);
+/* the number of launches sift3d_hip_tps_field makes for this output grid and m (-1 for bad arguments) */
+SIFT3D_AMD_API int sift3d_hip_tps_field_launches(int ox, int oy, int oz, int m);
+SIFT3D_AMD_API int
+sift3d_hip_warp_field(const float *d_src, int nx, int ny, int nz, int nc, const float *d_field, int ox, int oy,
+                      int oz, float *d_dst, int interp, float fill, void *stream);
+/* d_det [oz][oy][ox] may be NULL (stats only) */
+SIFT3D_AMD_API int sift3d_hip_jacobian_det(const float *d_field, int ox, int oy, int oz, float *d_det /*NULL*/,
+                                           void *d_stats, void *stream);
+/* host forms, blocking; arguments are checked before the device is touched.  warp_field: host image
+ * objects (nc == 1), the field on the host, shaped by dst's grid (-1 also when dst's data overlaps src's or
+ * the field).  jacobian_det: a host field; det (may be NULL) and the three stats on the host (-1 also when
+ * det overlaps the field). */
+SIFT3D_AMD_API int sift3d_amd_image_warp_field(const sift3d_image *src, const float *field, int interp,
+                                               float fill, sift3d_image *dst);
+SIFT3D_AMD_API int sift3d_amd_jacobian_det(const float *field, int ox, int oy, int oz, float *det /*NULL*/,
+                                           uint64_t *folded, float *min, float *max);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

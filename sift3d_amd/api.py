@@ -104,6 +104,9 @@ def lib():
         "sift3d_amd_tps_apply": (C.c_int, [_f64p, _f64p, _f64p, C.c_int, _f64p, C.c_int, _f64p]),
         "sift3d_amd_tps_pack": (C.c_int, [_f64p, _f64p, C.c_int, _f32p]),
         "sift3d_amd_image_warp_tps": (C.c_int, [vp, _f64p, _f32p, C.c_int, C.c_int, C.c_float, vp]),
+        "sift3d_amd_image_warp_field": (C.c_int, [vp, _f32p, C.c_int, C.c_float, vp]),
+        "sift3d_amd_jacobian_det": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "sift3d_amd_image_dense_descriptors": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_image_dense_descriptors_rotate": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_device_available": (C.c_int, []),
@@ -692,6 +695,79 @@ def register_deformable(moving, fixed, nn_thresh=0.8, err_thresh=DEFORMABLE_ERR_
     warped = torch.empty_like(fixed)
     hip.warp_tps(moving, warped, tps, "linear")
     return DeformableRegistration(A, tps, inl, len(p_mov), warped)
+
+
+# ---- displacement fields: export, resampling through a field, Jacobian -----------------------------
+JacobianStats = collections.namedtuple("JacobianStats", "det folded min max")
+
+
+def displacement_field(transform, out_shape, device=None):
+    """The displacement field u [3, oz, oy, ox] (channels x, y, z; source voxels) of a pull map over a grid of
+    out_shape = (oz, oy, ox): output voxel p reads the source at p + u(p).  transform: a 3 x 4 affine pull map
+    or a TPS (contract: include/sift3d_amd.h, "Displacement fields").  Returns a torch CUDA float32 tensor on
+    `device` (default: the current device), computed on torch's current stream."""
+    import torch
+    from . import hip
+    oz, oy, ox = (int(v) for v in out_shape)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=device if device is not None else "cuda")
+    if isinstance(transform, TPS):
+        return hip.tps_field(field, transform)
+    A = np.asarray(transform, np.float64)
+    if A.shape not in ((3, 4), (12,)):
+        raise ValueError("displacement_field: transform must be a 3 x 4 affine pull map or a TPS")
+    return hip.affine_field(field, A)
+
+
+def _host_field(field, what):
+    f = np.ascontiguousarray(field, np.float32)
+    if f.ndim != 4 or f.shape[0] != 3:
+        raise ValueError("%s: the field must be [3, oz, oy, ox]" % what)
+    return f
+
+
+def warp_field(volume, field, interp="linear", fill=0.0):
+    """Resample `volume` through a displacement field [3, oz, oy, ox]: output voxel p takes the volume at
+    p + field(p); voxels that sample outside get `fill`.  A torch CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]
+    (with a CUDA field) gives a tensor [oz, oy, ox] / [nc, oz, oy, ox] on torch's current stream; an Image or
+    a float32 array (with a host field) goes through the blocking host form, and gives an Image / an array
+    (a 4-D array channel by channel)."""
+    if interp not in INTERP:
+        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    if _torch_tensor(volume):
+        import torch
+        from . import hip
+        out = torch.empty(tuple(volume.shape[:-3]) + tuple(field.shape[1:]), dtype=torch.float32,
+                          device=volume.device)
+        return hip.warp_field(volume, out, field, interp, fill)
+    f = _host_field(field, "warp_field")
+    if not isinstance(volume, Image) and np.ndim(volume) == 4:
+        return np.stack([warp_field(v, f, interp, fill) for v in np.asarray(volume)])
+    src = volume if isinstance(volume, Image) else Image.from_array(volume)
+    _, oz, oy, ox = f.shape
+    dst = Image(ox, oy, oz)
+    if lib().sift3d_amd_image_warp_field(src.h, f.reshape(-1), INTERP[interp], float(fill), dst.h) != 0:
+        raise RuntimeError("sift3d_amd_image_warp_field failed")
+    return dst if isinstance(volume, Image) else dst.data().copy()
+
+
+def jacobian_determinant(field):
+    """Jacobian determinant of p -> p + field(p) by numpy.gradient's differences (contract:
+    include/sift3d_amd.h, "Displacement fields"): JacobianStats(det [oz, oy, ox], folded = the number of voxels
+    with det <= 0 or NaN, min, max of the non-NaN dets).  A CUDA field gives a CUDA det (waits for torch's
+    current stream to read the stats); a host array gives a numpy det (blocking)."""
+    if _torch_tensor(field):
+        import torch
+        from . import hip
+        det = torch.empty(tuple(field.shape[1:]), dtype=torch.float32, device=field.device)
+        return JacobianStats(*hip.jacobian_det(field, det))
+    f = _host_field(field, "jacobian_determinant")
+    _, oz, oy, ox = f.shape
+    det = np.empty((oz, oy, ox), np.float32)
+    folded, mn, mx = C.c_uint64(), C.c_float(), C.c_float()
+    if lib().sift3d_amd_jacobian_det(f.reshape(-1), ox, oy, oz, det.ctypes.data, C.byref(folded), C.byref(mn),
+                                     C.byref(mx)) != 0:
+        raise RuntimeError("sift3d_amd_jacobian_det failed")
+    return JacobianStats(det, int(folded.value), float(mn.value), float(mx.value))
 
 
 # ---- dense descriptors: a 12-bin gradient histogram per voxel ------------------------------------

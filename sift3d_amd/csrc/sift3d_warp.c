@@ -94,3 +94,99 @@ int sift3d_amd_image_warp_affine(const sift3d_image *src, const double *A, int i
     sift3d_hip_free(d_dst);
     return rc;
 }
+
+/* ---- displacement fields: blocking host forms of sift3d_hip_warp_field / sift3d_hip_jacobian_det ---- */
+static int host_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int sift3d_amd_image_warp_field(const sift3d_image *src, const float *field, int interp, float fill,
+                                sift3d_image *dst)
+{
+    float *d_src = NULL, *d_dst = NULL, *d_field = NULL;
+    size_t ns, nd;
+    int rc = SIFT3D_FAILURE;
+    if (!src || !dst || !field || !src->data || !dst->data) {
+        ERR("sift3d_amd_image_warp_field: NULL argument \n");
+        return SIFT3D_FAILURE;
+    }
+    if (src->nc != 1 || dst->nc != 1) {
+        ERR("sift3d_amd_image_warp_field: only single-channel images are supported \n");
+        return SIFT3D_FAILURE;
+    }
+    if (src->nx <= 0 || src->ny <= 0 || src->nz <= 0 || dst->nx <= 0 || dst->ny <= 0 || dst->nz <= 0) {
+        ERR("sift3d_amd_image_warp_field: dimensions must be positive \n");
+        return SIFT3D_FAILURE;
+    }
+    if (interp != SIFT3D_AMD_INTERP_NEAREST && interp != SIFT3D_AMD_INTERP_LINEAR) {
+        ERR("sift3d_amd_image_warp_field: unknown interpolation mode %d \n", interp);
+        return SIFT3D_FAILURE;
+    }
+    ns = sizeof(float) * (size_t)src->nx * src->ny * src->nz;
+    nd = sizeof(float) * (size_t)dst->nx * dst->ny * dst->nz;
+    if (host_overlap(dst->data, nd, src->data, ns) || host_overlap(dst->data, nd, field, 3 * nd)) {
+        ERR("sift3d_amd_image_warp_field: the destination overlaps the source or the field \n");
+        return SIFT3D_FAILURE;
+    }
+    if (!sift3d_amd_device_available()) {
+        ERR("sift3d_amd: no HIP device is available; this library has no CPU path \n");
+        return SIFT3D_FAILURE;
+    }
+    d_src = (float *)sift3d_hip_malloc(ns);
+    d_dst = (float *)sift3d_hip_malloc(nd);
+    d_field = (float *)sift3d_hip_malloc(3 * nd);
+    if (d_src && d_dst && d_field && !sift3d_hip_memcpy_h2d(d_src, src->data, ns, NULL) &&
+        !sift3d_hip_memcpy_h2d(d_field, field, 3 * nd, NULL) &&
+        !sift3d_hip_warp_field(d_src, src->nx, src->ny, src->nz, 1, d_field, dst->nx, dst->ny, dst->nz, d_dst,
+                               interp, fill, NULL) &&
+        !sift3d_hip_memcpy_d2h(dst->data, d_dst, nd, NULL) && !sift3d_hip_stream_sync(NULL))
+        rc = SIFT3D_SUCCESS;
+    sift3d_hip_free(d_src);
+    sift3d_hip_free(d_dst);
+    sift3d_hip_free(d_field);
+    return rc;
+}
+
+int sift3d_amd_jacobian_det(const float *field, int ox, int oy, int oz, float *det, uint64_t *folded, float *min,
+                            float *max)
+{
+    float *d_field = NULL, *d_det = NULL;
+    unsigned char *d_stats = NULL, stats[SIFT3D_AMD_JACOBIAN_STATS_BYTES];
+    size_t nd;
+    int rc = SIFT3D_FAILURE;
+    if (!field || !folded || !min || !max) {
+        ERR("sift3d_amd_jacobian_det: NULL argument \n");
+        return SIFT3D_FAILURE;
+    }
+    if (ox <= 0 || oy <= 0 || oz <= 0) {
+        ERR("sift3d_amd_jacobian_det: dimensions must be positive \n");
+        return SIFT3D_FAILURE;
+    }
+    nd = sizeof(float) * (size_t)ox * oy * oz;
+    if (det && host_overlap(det, nd, field, 3 * nd)) {
+        ERR("sift3d_amd_jacobian_det: det overlaps the field \n");
+        return SIFT3D_FAILURE;
+    }
+    if (!sift3d_amd_device_available()) {
+        ERR("sift3d_amd: no HIP device is available; this library has no CPU path \n");
+        return SIFT3D_FAILURE;
+    }
+    d_field = (float *)sift3d_hip_malloc(3 * nd);
+    d_det = det ? (float *)sift3d_hip_malloc(nd) : NULL;
+    d_stats = (unsigned char *)sift3d_hip_malloc(SIFT3D_AMD_JACOBIAN_STATS_BYTES);
+    if (d_field && (d_det || !det) && d_stats && !sift3d_hip_memcpy_h2d(d_field, field, 3 * nd, NULL) &&
+        !sift3d_hip_jacobian_det(d_field, ox, oy, oz, d_det, d_stats, NULL) &&
+        (!det || !sift3d_hip_memcpy_d2h(det, d_det, nd, NULL)) &&
+        !sift3d_hip_memcpy_d2h(stats, d_stats, sizeof(stats), NULL) && !sift3d_hip_stream_sync(NULL)) {
+        memcpy(folded, stats, 8);
+        memcpy(min, stats + 8, 4);
+        memcpy(max, stats + 12, 4);
+        rc = SIFT3D_SUCCESS;
+    }
+    sift3d_hip_free(d_field);
+    sift3d_hip_free(d_det);
+    sift3d_hip_free(d_stats);
+    return rc;
+}

@@ -97,6 +97,12 @@ def lib():
         "sift3d_hip_warp_tps": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_double), vp, C.c_int, C.c_int, C.c_float, vp]),
         "sift3d_hip_warp_tps_launches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_affine_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp]),
+        "sift3d_hip_tps_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp, C.c_int, vp]),
+        "sift3d_hip_tps_field_launches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_warp_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                            vp, C.c_int, C.c_float, vp]),
+        "sift3d_hip_jacobian_det": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -240,6 +246,96 @@ def warp_tps_launches(out_shape, m):
     """How many launches sift3d_hip_warp_tps splits an output grid (oz, oy, ox) with m points into."""
     oz, oy, ox = out_shape
     return int(lib().sift3d_hip_warp_tps_launches(ox, oy, oz, m))
+
+
+def _field_tensor(t, what, name="field"):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+            and t.dim() == 4 and t.shape[0] == 3):
+        raise ValueError("%s: %s must be a contiguous float32 CUDA tensor [3, oz, oy, ox]" % (what, name))
+
+
+def affine_field(field, A):
+    """field [3, oz, oy, ox] = the displacement field of the pull map A (3 x 4, voxels; sift3d_hip_affine_field),
+    torch CUDA float32, on torch's current stream."""
+    _field_tensor(field, "affine_field")
+    a = np.ascontiguousarray(A, np.float64).reshape(12)
+    _, oz, oy, ox = field.shape
+    _check(lib().sift3d_hip_affine_field(field.data_ptr(), ox, oy, oz, a.ctypes.data_as(C.POINTER(C.c_double)),
+                                         current_stream()), "sift3d_hip_affine_field")
+    return field
+
+
+def tps_field(field, tps):
+    """field [3, oz, oy, ox] = the displacement field of the thin-plate spline tps (an api.TPS;
+    sift3d_hip_tps_field), torch CUDA float32, on torch's current stream."""
+    import torch
+    from . import api
+    _field_tensor(field, "tps_field")
+    a = np.ascontiguousarray(tps.A, np.float64).reshape(12)
+    packed = api.tps_pack(tps.ctrl, tps.weights)
+    d_tps = torch.from_numpy(packed).to(field.device)
+    _, oz, oy, ox = field.shape
+    _check(lib().sift3d_hip_tps_field(field.data_ptr(), ox, oy, oz, a.ctypes.data_as(C.POINTER(C.c_double)),
+                                      d_tps.data_ptr(), len(packed), current_stream()), "sift3d_hip_tps_field")
+    return field
+
+
+def tps_field_launches(out_shape, m):
+    """How many launches sift3d_hip_tps_field splits an output grid (oz, oy, ox) with m points into."""
+    oz, oy, ox = out_shape
+    return int(lib().sift3d_hip_tps_field_launches(ox, oy, oz, m))
+
+
+def warp_field(src, dst, field, interp="linear", fill=0.0):
+    """dst = src sampled at p + field(p) (sift3d_hip_warp_field), torch CUDA float32 contiguous tensors:
+    src [nz, ny, nx] / dst [oz, oy, ox], or src [nc, nz, ny, nx] / dst [nc, oz, oy, ox] (every channel at
+    the same points); field [3, oz, oy, ox].  On torch's current stream; voxels that sample outside get `fill`."""
+    import torch
+    for t in (src, dst):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.dim() in (3, 4)):
+            raise ValueError("warp_field: src and dst must be contiguous 3-D or 4-D float32 CUDA tensors")
+    _field_tensor(field, "warp_field")
+    if src.dim() != dst.dim() or (src.dim() == 4 and src.shape[0] != dst.shape[0]):
+        raise ValueError("warp_field: src %s and dst %s differ in channels" % (tuple(src.shape), tuple(dst.shape)))
+    if tuple(dst.shape[-3:]) != tuple(field.shape[1:]):
+        raise ValueError("warp_field: dst %s does not match the field's grid %s"
+                         % (tuple(dst.shape), tuple(field.shape[1:])))
+    if not (src.device == dst.device == field.device):
+        raise ValueError("warp_field: src, dst and field are not on one device")
+    if interp not in INTERP:
+        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    nc = src.shape[0] if src.dim() == 4 else 1
+    nz, ny, nx = src.shape[-3:]
+    oz, oy, ox = dst.shape[-3:]
+    _check(lib().sift3d_hip_warp_field(src.data_ptr(), nx, ny, nz, nc, field.data_ptr(), ox, oy, oz, dst.data_ptr(),
+                                       INTERP[interp], float(fill), current_stream()), "sift3d_hip_warp_field")
+    return dst
+
+
+JACOBIAN_STATS_BYTES = 16
+
+
+def jacobian_det(field, det=None):
+    """Jacobian determinant of p -> p + field(p) (sift3d_hip_jacobian_det) on torch's current stream: field
+    [3, oz, oy, ox] and det [oz, oy, ox] (or None: stats only) torch CUDA float32.  Returns (det, folded, min,
+    max); reading the three stats waits for the stream."""
+    import torch
+    _field_tensor(field, "jacobian_det")
+    _, oz, oy, ox = field.shape
+    if det is not None and not (isinstance(det, torch.Tensor) and det.is_cuda and det.dtype == torch.float32
+                                and det.is_contiguous() and tuple(det.shape) == (oz, oy, ox)
+                                and det.device == field.device):
+        raise ValueError("jacobian_det: det must be a contiguous float32 CUDA tensor [oz, oy, ox] on the field's "
+                         "device, or None")
+    stats = torch.empty(JACOBIAN_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
+    _check(lib().sift3d_hip_jacobian_det(field.data_ptr(), ox, oy, oz, None if det is None else det.data_ptr(),
+                                         stats.data_ptr(), current_stream()), "sift3d_hip_jacobian_det")
+    raw = stats.view(torch.uint8)[:JACOBIAN_STATS_BYTES].cpu().numpy()
+    folded = int(raw[:8].view(np.uint64)[0])
+    mn, mx = (float(v) for v in raw[8:16].view(np.float32))
+    return det, folded, mn, mx
 
 
 def _dense_args(src, out, what):
