@@ -67,6 +67,15 @@ sift3d_amd_detector_set_dogmax_pass(sift3d_detector *det, int on);
  * keypoints and R bit for bit either way; an A/B switch for tests and profiles. */
 SIFT3D_AMD_API int
 sift3d_amd_detector_set_serial_orientation(sift3d_detector *det, int on);
+/* Candidate list capacity, a diagnostic hook: cap >= 1 waits for the detector's streams, releases the
+ * candidate arrays and makes the next detect start from exactly cap records; 0 restores the default (2^18);
+ * negative values fail.  A detect whose extrema do not fit grows the arrays to count + count / 4 + 1024 and
+ * sweeps again, as it does from the default.  sift3d_amd_detector_candidate_capacity returns the capacity the
+ * arrays have (or the next detect starts from), -1 for a NULL detector. */
+SIFT3D_AMD_API int
+sift3d_amd_detector_set_candidate_capacity(sift3d_detector *det, int cap);
+SIFT3D_AMD_API int
+sift3d_amd_detector_candidate_capacity(const sift3d_detector *det);
 /* Descriptor accumulation (sift3d_extract_descriptors): 0 (default) = automatic: keypoints whose window
  * holds more than ~1.9e5 voxels -- sigma0 * 2^(s/K) above ~2.9 voxels, never with the default parameters --
  * are computed in the reference's accumulation order (their histograms are the reference's bit for bit),
@@ -546,6 +555,9 @@ sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *, const sift3d_keypoin
  * all-gathers) or descriptor gather (4) of this rank fails LOCALLY; 0 clears */
 SIFT3D_AMD_API int sift3d_amd_sharded_inject_failure(sift3d_amd_sharded *, int where);
 SIFT3D_AMD_API int sift3d_amd_sharded_num_candidates(const sift3d_amd_sharded *);
+/* this rank's candidate list capacity (as sift3d_amd_detector_set_candidate_capacity / _candidate_capacity) */
+SIFT3D_AMD_API int sift3d_amd_sharded_set_candidate_capacity(sift3d_amd_sharded *, int cap);
+SIFT3D_AMD_API int sift3d_amd_sharded_candidate_capacity(const sift3d_amd_sharded *);
 /* eight doubles of the last step: [0] Gaussian pyramid (device s, halo exchanges of the blurs inside)
  * [1] detect wall  [2] describe wall  [3] DoG maxima + extrema (device s, incl. the all-reduce)
  * [4] wait for the window halos + orientation (device s)  [5] gathers + global keypoint list (host s)

@@ -81,6 +81,8 @@ def lib():
         "sift3d_amd_detector_set_dogmax_pass": (C.c_int, [vp, C.c_int]),
         "sift3d_amd_detector_set_exact_descriptors": (C.c_int, [vp, C.c_int]),
         "sift3d_amd_detector_set_serial_orientation": (C.c_int, [vp, C.c_int]),
+        "sift3d_amd_detector_set_candidate_capacity": (C.c_int, [vp, C.c_int]),
+        "sift3d_amd_detector_candidate_capacity": (C.c_int, [vp]),
         "sift3d_amd_detector_dogmax": (C.c_int, [vp, vp, C.c_int]),
         "sift3d_amd_copy_level": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, _i32p]),
         "sift3d_amd_keypoint_store_size": (C.c_int, [vp]),
@@ -380,6 +382,16 @@ class Detector:
     def set_dogmax_pass(self, on):
         """A/B switch: octave 0's dogmax scan as a pass of its own (True) or gathered by the extrema sweep."""
         return lib().sift3d_amd_detector_set_dogmax_pass(self.h, int(bool(on)))
+
+    def set_candidate_capacity(self, cap):
+        """Diagnostic hook: the next detect starts from a candidate list of exactly `cap` records (0: the
+        default, 2^18); one that does not fit grows the list to count + count // 4 + 1024 and sweeps again."""
+        if lib().sift3d_amd_detector_set_candidate_capacity(self.h, int(cap)) != 0:
+            raise ValueError("sift3d_amd_detector_set_candidate_capacity(%r)" % (cap,))
+
+    def candidate_capacity(self):
+        """Records the candidate list holds (or the next detect starts from)."""
+        return lib().sift3d_amd_detector_candidate_capacity(self.h)
 
     def dogmax(self):
         """max|DoG| of every DoG level of the last detect call (float32, octave-major)."""

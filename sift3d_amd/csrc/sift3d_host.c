@@ -148,6 +148,7 @@ struct _sift3d_detector {
     sift3d_hip_level *h_levels, *d_levels;
     sift3d_hip_cand *d_cand, *h_cand;
     uint32_t cand_cap;
+    uint32_t cand_cap0;    /* capacity the next detect starts from while none is allocated (0: 2^18) */
     float *h_R;            /* page-locked, device-visible: the orientation kernels write here */
     int32_t *h_keep;
     void *d_work;
@@ -1097,6 +1098,35 @@ int sift3d_amd_detector_set_dogmax_pass(sift3d_detector *d, int on)
     return SIFT3D_SUCCESS;
 }
 
+/* the candidate arrays' capacity (they are grown by the detect call that overflows them) */
+int sift3d_amd_detector_set_candidate_capacity(sift3d_detector *d, int cap)
+{
+    if (!d || cap < 0)
+        return SIFT3D_FAILURE;
+    /* (the orientation kernels of the last detect write into the page-locked arrays: all streams done first) */
+    if ((d->stream && sift3d_hip_stream_sync(d->stream)) || (d->oct_stream && sift3d_hip_stream_sync(d->oct_stream)) ||
+        (d->side_stream && sift3d_hip_stream_sync(d->side_stream)))
+        return SIFT3D_FAILURE;
+    sift3d_hip_free(d->d_cand);
+    sift3d_hip_host_free(d->h_cand);
+    sift3d_hip_host_free(d->h_R);
+    sift3d_hip_host_free(d->h_keep);
+    d->d_cand = NULL;
+    d->h_cand = NULL;
+    d->h_R = NULL;
+    d->h_keep = NULL;
+    d->cand_cap = 0;
+    d->cand_cap0 = (uint32_t)cap;
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_detector_candidate_capacity(const sift3d_detector *d)
+{
+    if (!d)
+        return -1;
+    return (int)(d->cand_cap ? d->cand_cap : d->cand_cap0 ? d->cand_cap0 : (1u << 18));
+}
+
 int sift3d_amd_detector_set_serial_orientation(sift3d_detector *d, int on)
 {
     if (!d)
@@ -1848,7 +1878,7 @@ static int detect_on_device(sift3d_detector *d, const float *d_vol, int nx, int 
         printf("detect_extrema: Requires at least 3 levels per octave, provided only %d \n", d->ndl);
         return SIFT3D_FAILURE;
     }
-    if (ensure_cand_capacity(d, d->cand_cap ? d->cand_cap : (1u << 18)))
+    if (ensure_cand_capacity(d, d->cand_cap ? d->cand_cap : d->cand_cap0 ? d->cand_cap0 : (1u << 18)))
         return SIFT3D_FAILURE;
     for (attempt = 0; attempt < 2; attempt++) {
         int split = 0;

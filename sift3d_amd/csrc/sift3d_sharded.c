@@ -106,6 +106,7 @@ struct sift3d_amd_sharded {
     float *d_R;
     int32_t *d_keep;
     uint32_t cand_cap;
+    uint32_t cand_cap0;              /* capacity the next detect starts from while none is allocated (0: 2^18) */
     void *d_xchg, *h_xchg;           /* the ranks' gathered blocks (device); the final list (pinned host) */
     size_t xchg_bytes, hxchg_cap;
     void *d_cnt, *h_cnt, *d_tab, *h_tab, *d_out, *d_pack;   /* counts, segment tables, list, scan scratch */
@@ -519,6 +520,32 @@ int sift3d_amd_sharded_inject_failure(sift3d_amd_sharded *S, int where)
     return SIFT3D_SUCCESS;
 }
 
+/* this rank's candidate arrays: released, the next detect starts from `cap` (0: 2^18); grown by a detect
+ * that overflows them */
+int sift3d_amd_sharded_set_candidate_capacity(sift3d_amd_sharded *S, int cap)
+{
+    if (!S || cap < 0)
+        return SIFT3D_FAILURE;
+    if ((S->stream && sift3d_hip_stream_sync(S->stream)) || (S->comm_stream && sift3d_hip_stream_sync(S->comm_stream)) ||
+        (S->oct_stream && sift3d_hip_stream_sync(S->oct_stream)) ||
+        (S->side_stream && sift3d_hip_stream_sync(S->side_stream)))
+        return SIFT3D_FAILURE;
+    sift3d_hip_free(S->d_cand); sift3d_hip_free(S->d_R); sift3d_hip_free(S->d_keep);
+    S->d_cand = NULL;
+    S->d_R = NULL;
+    S->d_keep = NULL;
+    S->cand_cap = 0;
+    S->cand_cap0 = (uint32_t)cap;
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_sharded_candidate_capacity(const sift3d_amd_sharded *S)
+{
+    if (!S)
+        return -1;
+    return (int)(S->cand_cap ? S->cand_cap : S->cand_cap0 ? S->cand_cap0 : (1u << 18));
+}
+
 /* apply_Sep_FIR_filter (imutil.c:1127-1206) on a level: src -> dst (same geometry).  Sharded
  * octaves: x (and y) on the owned planes, halo exchange of the z pass's input overlapped with the
  * z pass of the interior planes. */
@@ -846,7 +873,7 @@ int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
 
     /* detect_extrema (sift.c:735-871) on the owned planes, assign_orientations (sift.c:1109-1167)
      * for the local candidates */
-    SH_DO(sh_ensure_cand(S, S->cand_cap ? S->cand_cap : (1u << 18)));
+    SH_DO(sh_ensure_cand(S, S->cand_cap ? S->cand_cap : S->cand_cap0 ? S->cand_cap0 : (1u << 18)));
     for (attempt = 0; attempt < 2 && !S->failed; attempt++) {
         /* with every octave on the DoG-free sweep: the sweeps of octaves >= 1 (short launches) beside
          * octave 0's on a second stream, then scan + emission in octave order

@@ -68,6 +68,8 @@ def _lib():
                                                             vp, C.c_int]
         L.sift3d_amd_sharded_inject_failure.argtypes = [vp, C.c_int]
         L.sift3d_amd_sharded_num_candidates.argtypes = [vp]
+        L.sift3d_amd_sharded_set_candidate_capacity.argtypes = [vp, C.c_int]
+        L.sift3d_amd_sharded_candidate_capacity.argtypes = [vp]
         L.sift3d_amd_sharded_timings.restype = C.POINTER(C.c_double)
         L.sift3d_amd_sharded_timings.argtypes = [vp]
         L.sift3d_amd_sharded_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -399,6 +401,16 @@ class CShardedSift3D:
         """Test hook: the next detect (1, 2, 3) / descriptor gather (4) of this rank fails locally; 0 clears."""
         if _lib().sift3d_amd_sharded_inject_failure(self.h, int(where)) != 0:
             raise ValueError("sift3d_amd_sharded_inject_failure(%r)" % (where,))
+
+    def set_candidate_capacity(self, cap):
+        """Diagnostic hook: this rank's next detect starts from a candidate list of exactly `cap` records (0: the
+        default, 2^18); one that does not fit grows it to count + count // 4 + 1024 and sweeps again."""
+        if _lib().sift3d_amd_sharded_set_candidate_capacity(self.h, int(cap)) != 0:
+            raise ValueError("sift3d_amd_sharded_set_candidate_capacity(%r)" % (cap,))
+
+    def candidate_capacity(self):
+        """Records this rank's candidate list holds (or its next detect starts from)."""
+        return _lib().sift3d_amd_sharded_candidate_capacity(self.h)
 
     def keypoints(self):
         """Global keypoint list as the Python driver's record array."""

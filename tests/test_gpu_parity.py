@@ -657,7 +657,7 @@ def test_orientation_parallel_sums_equal_serial_sums(gpu, oracle_mod, case):
     re-run of the undecided candidates) must give the keypoint list AND the R bits of the path
     that adds every window in the reference's scan order (sift.c:978-990)."""
     api, hip, torch = gpu
-    units, kw = (1.0, 1.0, 1.0), {}
+    units, kw, cap = (1.0, 1.0, 1.0), {}, None
     if case == "lattice160":
         vol = oracle_mod.synth_lattice(160, seed=21)
     elif case == "survey96":
@@ -732,7 +732,7 @@ def test_dogmax_gathered_by_the_sweep_equals_its_own_pass(gpu, oracle_mod, case)
     and keypoints must be those of the two-pass path -- also when the sub-lattice misses the maximum by far
     (spike128: one voxel off the sub-lattice carries it, so the sweep marks nearly every extremum)."""
     api, hip, torch = gpu
-    units, kw = (1.0, 1.0, 1.0), {}
+    units, kw, cap = (1.0, 1.0, 1.0), {}, None
     if case == "lattice160":
         vol = oracle_mod.synth_lattice(160, seed=21)
     elif case == "noise96":
@@ -744,18 +744,25 @@ def test_dogmax_gathered_by_the_sweep_equals_its_own_pass(gpu, oracle_mod, case)
         # rows and planes that are no multiples of the sub-lattice's strides (3 and 5), an odd row count
         vol = np.random.default_rng(6).standard_normal((95, 93, 256)).astype(np.float32)
     elif case == "retry128":
-        # more candidates than the first candidate buffer holds: the sweep runs twice (the maxima it gathers
-        # must come out the same)
+        # more candidates than the first candidate buffer holds (forced to 4096, below octave 0's ~8300): the sweep
+        # runs twice (the maxima it gathers must come out the same)
         vol = np.random.default_rng(5).random((128, 128, 128), dtype=np.float32)
         kw = dict(peak_thresh=0.001, corner_thresh=0.9)
+        cap = 4096
     else:
         vol, units = oracle_mod.synth_survey((72, 60, 80)), (1.0, 1.5, 0.7)
     got = {}
     for own_pass in (True, False):
         det, kp = api.Detector(**kw), api.KeypointStore()
         assert det.set_dogmax_pass(own_pass) == 0
+        if cap is not None:
+            det.set_candidate_capacity(cap)
         assert det.detect_keypoints(api.Image.from_array(vol, units=units), kp) == 0
         got[own_pass] = (det.num_candidates(), kp.records(), det.dogmax())
+        if cap is not None:
+            # the retry ran: the list was grown to count + count / 4 + 1024 (sift3d_host.c, detect_on_device)
+            n = det.num_candidates()
+            assert n > cap and det.candidate_capacity() == n + n // 4 + 1024
     assert got[True][0] == got[False][0] and len(got[True][1]) == len(got[False][1])
     np.testing.assert_array_equal(got[True][2], got[False][2])
     assert (got[True][2] > 0).all()

@@ -214,11 +214,12 @@ def test_config4_1024_sharded_equals_single_gpu():
     torch.cuda.empty_cache()
 
 
-def _run_thread_ranks(world, dims, transport, det_kw=None, seed=5, synth_on_device=False):
+def _run_thread_ranks(world, dims, transport, det_kw=None, seed=5, synth_on_device=False, caps=None):
     """`world` C slab drivers as threads of THIS process on the one device; returns one dict per rank.
     transport: "stream" = the library's stream-ordered thread transport (event-ordered device copies, the
     completion semantics of ncclSend/ncclRecv, no host-side stream sync), "host" = ThreadTransport
-    (drains the stream around every exchange)."""
+    (drains the stream around every exchange).  caps: per rank, the candidate capacity its detect starts from
+    (None: the default)."""
     import threading
     from sift3d_amd import api, sharded_c
     nx, ny, nz = dims
@@ -232,6 +233,9 @@ def _run_thread_ranks(world, dims, transport, det_kw=None, seed=5, synth_on_devi
             det = api.Detector(**det_kw) if det_kw else None
             tr = make(group, rank)
             job = sharded_c.CShardedSift3D(nx, ny, nz, tr, detector=det)
+            if caps is not None and caps[rank] is not None:
+                job.set_candidate_capacity(caps[rank])
+            cap_before = job.candidate_capacity()
             if synth_on_device:
                 job.synth(seed=seed)
             else:
@@ -240,7 +244,8 @@ def _run_thread_ranks(world, dims, transport, det_kw=None, seed=5, synth_on_devi
             job.detect()
             idx, desc = job.describe()
             out[rank] = dict(kp=job.keypoints(), idx=idx.copy(), own=job.in_own, o_shard=job.o_shard,
-                             num_octaves=job.num_octaves, ncand=job.ncand,
+                             num_octaves=job.num_octaves, ncand=job.ncand, cap_before=cap_before,
+                             cap_after=job.candidate_capacity(),
                              mat=desc.to_mat_rm() if len(idx) else np.zeros((0, 771), np.float32))
             job.close()
             tr.close()
@@ -286,6 +291,39 @@ def test_c_slab_driver_over_stream_ordered_transport(world, dims, det_kw):
     covered = np.zeros(len(k), int)
     for g in res:
         assert g["ncand"] == det.num_candidates() and g["o_shard"] >= 1
+        for f in ("o", "s", "xd", "yd", "zd", "sd", "strength", "R"):
+            np.testing.assert_array_equal(g["kp"][f], k[f], err_msg=f)
+        np.testing.assert_array_equal(g["mat"], m[g["idx"]])
+        covered[g["idx"]] += 1
+    np.testing.assert_array_equal(covered, 1)
+
+
+@pytest.mark.parametrize("caps,det_kw", [((1, None), None), ((1, 1), None), ((1, 1), dict(cuboid_extrema=True))])
+def test_c_slab_driver_candidate_overflow(caps, det_kw):
+    """The slab driver's own retry (sift3d_sharded.c, the extrema loop of the detect): a rank whose candidates do
+    not fit grows its list to count + count / 4 + 1024 and sweeps again -- on one rank, on both, and on the
+    per-octave path (cuboid extrema: not every octave on the DoG-free sweep).  The result is the single-GPU
+    detector's bit for bit."""
+    import torch
+    from sift3d_amd import api
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no HIP device is visible")
+    world, dims = 2, (64, 72, 256)
+    res = _run_thread_ranks(world, dims, "stream", det_kw, caps=caps)
+    vol = api.synth_lattice(dims, seed=5)
+    det, kp, desc = api.Detector(**(det_kw or {})), api.KeypointStore(), api.DescriptorStore()
+    assert det.detect_keypoints(api.Image.from_array(vol), kp) == 0
+    assert det.extract_descriptors(kp, desc) == 0
+    k, m, n = kp.records(), desc.to_mat_rm(), det.num_candidates()
+    assert len(k) > 5
+    covered = np.zeros(len(k), int)
+    for cap, g in zip(caps, res):
+        if cap is None:
+            assert g["cap_before"] == g["cap_after"] == 1 << 18
+        else:
+            # grown from the rank's own count (at most the whole list): the sweep ran twice
+            assert g["cap_before"] == cap and 1024 + 1 < g["cap_after"] <= n + n // 4 + 1024
+        assert g["ncand"] == n
         for f in ("o", "s", "xd", "yd", "zd", "sd", "strength", "R"):
             np.testing.assert_array_equal(g["kp"][f], k[f], err_msg=f)
         np.testing.assert_array_equal(g["mat"], m[g["idx"]])
