@@ -76,11 +76,17 @@ SIFT3D_AMD_API int
 sift3d_amd_detector_set_candidate_capacity(sift3d_detector *det, int cap);
 SIFT3D_AMD_API int
 sift3d_amd_detector_candidate_capacity(const sift3d_detector *det);
-/* Descriptor accumulation (sift3d_extract_descriptors): 0 (default) = automatic: keypoints whose window
- * holds more than ~1.9e5 voxels -- sigma0 * 2^(s/K) above ~2.9 voxels, never with the default parameters --
- * are computed in the reference's accumulation order (their histograms are the reference's bit for bit),
- * the others by the fast two-histogram commit (within 1e-5 relative, elementwise); 1 = every keypoint in
- * the reference's order (bit-exact descriptors, ~1.5x the time); -1 = never. */
+/* Descriptor accumulation (sift3d_extract_descriptors): 0 (default) = automatic: keypoints whose OWN window
+ * holds more than ~1.9e5 voxels -- (20 sd)^3 / (ux uy uz 8^o), from the keypoint's own sd and octave, so also
+ * for caller-made keypoints whose sd is not their level's; for detect's keypoints sigma0 * 2^(s/K) above ~2.9
+ * voxels, never with the default parameters -- are computed in the reference's accumulation order (their
+ * histograms are the reference's bit for bit), the others by the fast two-histogram commit (within 1e-5
+ * relative, elementwise); 1 = every keypoint in the reference's order (bit-exact descriptors, ~1.5x the time);
+ * -1 = never.
+ * sift3d_extract_descriptors accepts what the reference's verify_keys accepts (sift.c:1171-1212) and keypoints
+ * of any sd and any finite R (not only rotations); in addition it refuses, before any launch, a keypoint whose
+ * (o, s) is not a level of the pyramid, and one whose window box would span more than 2^32 voxels (its packed
+ * voxel offsets would not fit in 32 bits -- only possible on volumes of more than 2^32 voxels). */
 SIFT3D_AMD_API int
 sift3d_amd_detector_set_exact_descriptors(sift3d_detector *det, int mode);
 /* max|DoG| of every DoG level of the last detect call, out[octave * levels + level] (the values

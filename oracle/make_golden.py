@@ -275,6 +275,209 @@ def g4_csv():
     return {"g4_csv": dict(kp=int(len(k["strength"])), kp_csv_bytes=len(ktxt), desc_csv_bytes=len(dtxt))}
 
 
+def _rotation(rng, reflect=False):
+    """A random orthonormal matrix (QR of a Gaussian one), det +1, or det -1 with `reflect`."""
+    q, r = np.linalg.qr(rng.standard_normal((3, 3)))
+    q = q * np.sign(np.diag(r))
+    if (np.linalg.det(q) < 0) != reflect:
+        q[:, 0] = -q[:, 0]
+    return q.astype(np.float32)
+
+
+def _steps_volume(n, seed):
+    """An axis-aligned step volume: plane x = i holds one PCG64 normal value (every gradient of the
+    interior points along x)."""
+    nx, ny, nz = n
+    c = np.random.Generator(np.random.PCG64(seed)).standard_normal(nx).astype(np.float32)
+    return np.ascontiguousarray(np.broadcast_to(c, (nz, ny, nx)), np.float32)
+
+
+def g7_keypoints(name, vol, input_spec, units=(1, 1, 1), make_lists=None):
+    """Describe on CALLER-MADE keypoint lists (sift.c:1171-1212, 1442-1596): the reference's pyramid of `vol`,
+    then each list of make_lists(probe, rng) -- {case: (os (n, 2), xyzsd (n, 4), R (n, 3, 3))} -- through its
+    own keypoint store.  Stored per case: the list, the reference's verdict (verify_keys), and for accepted
+    lists every descriptor row, desc xyzsd and the projections."""
+    p = refprobe.Probe()
+    assert p.detect(vol, units) == 0
+    d = {"units": np.array(units, np.float64), "dims": np.array(vol.shape[::-1], np.int32),
+         "input_digest": np.array(digest(vol)), "num_octaves": np.array(p.num_octaves),
+         "input_spec": np.array(json.dumps(input_spec))}
+    rng = np.random.Generator(np.random.PCG64(int(hashlib.sha1(name.encode()).hexdigest()[:8], 16)))
+    lists = make_lists(p, rng)
+    info = {}
+    for case, (os_, xyzsd, R) in lists.items():
+        os_ = np.asarray(os_, np.int32).reshape(-1, 2)
+        xyzsd = np.asarray(xyzsd, np.float64).reshape(-1, 4)
+        R = np.asarray(R, np.float32).reshape(-1, 3, 3)
+        assert p.set_keypoints(os_, xyzsd, R) == 0
+        ok = p.describe() == 0
+        d[case + "_os"], d[case + "_xyzsd"], d[case + "_R"] = os_, xyzsd, R
+        d[case + "_ok"] = np.array(ok)
+        if ok:
+            h, x = p.descriptors()
+            assert len(h) == len(os_)
+            d[case + "_hist"] = h
+            d[case + "_desc_xyzsd"] = x
+            d[case + "_proj"] = desc_projection(h)
+        info[case] = int(len(os_)) if ok else "refused"
+    d["cases"] = np.array(json.dumps(list(lists)))
+    p.close()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
+    return {name: info}
+
+
+def _level_sd(p, o, s):
+    return p.level(0, o, s)[2]
+
+
+def _level_dims(p, o):
+    return [int(v) for v in p.level(0, o, 0)[0].shape[::-1]]
+
+
+def _g7_survey64_lists(p, rng):
+    K = 3
+    lists = {}
+
+    def mk(rows, Rs):
+        return (np.array([(o, s) for o, s, _, _ in rows]), np.array([list(c) + [sd] for _, _, c, sd in rows]),
+                np.array(Rs, np.float32))
+
+    def centre(o, frac, margin=4):
+        n = _level_dims(p, o)
+        c = [rng.uniform(margin, v - margin) for v in n]
+        return [v if frac else float(np.floor(v)) for v in c]
+
+    # sub-voxel centres at the level's own sd: the weights are computed per voxel, fractional bounds
+    rows = [(o, s, centre(o, True), _level_sd(p, o, s)) for o in (0, 1) for s in (0, 1, 2) for _ in range(2)]
+    lists["subvox"] = mk(rows, [_rotation(rng) for _ in rows])
+    # integer centres, sd one ulp off the level's (the table is rejected by the bits alone) -- and on it
+    rows = []
+    for o in (0, 1):
+        for s in (0, 1, 2):
+            sd = _level_sd(p, o, s)
+            c = centre(o, False)
+            rows += [(o, s, c, np.nextafter(sd, np.inf)), (o, s, c, np.nextafter(sd, 0.0)), (o, s, c, sd)]
+    lists["ulp"] = mk(rows, [_rotation(rng) for _ in rows])
+    # 0.5x and 2x the level's sd; tiny sd (a window of at most one voxel, or none: a zero histogram)
+    rows = []
+    for o in (0, 1):
+        for s in (0, 2):
+            sd = _level_sd(p, o, s)
+            rows += [(o, s, centre(o, False), 0.5 * sd), (o, s, centre(o, True), 2.0 * sd)]
+    rows += [(0, 0, centre(0, False), 0.02), (0, 1, centre(0, True), 0.02), (1, 0, centre(1, False), 1e-3),
+             (0, 2, [31.5, 30.5, 29.5], 0.05)]
+    lists["scale"] = mk(rows, [_rotation(rng) for _ in rows])
+    # every octave, every level s = -1 .. K + 1 (detect only ever describes 0 .. K - 1)
+    rows = [(o, s, centre(o, s % 2 == 0, margin=2), _level_sd(p, o, s))
+            for o in range(p.num_octaves) for s in range(-1, K + 2)]
+    lists["levels"] = mk(rows, [_rotation(rng) for _ in rows])
+    # random proper rotations and reflections (det -1)
+    rows = [(o, s, centre(o, k % 3 == 0), _level_sd(p, o, s)) for o in (0, 1) for s in (0, 1, 2) for k in range(2)]
+    lists["rot"] = mk(rows, [_rotation(rng, reflect=k % 2 == 1) for k in range(len(rows))])
+    # non-orthonormal R: scaled, anisotropically scaled and sheared
+    Rs = [0.5 * np.eye(3), 2.0 * np.eye(3), 0.7 * _rotation(rng), _rotation(rng) @ np.diag([0.6, 1.0, 1.4]),
+          np.diag([0.8, 0.55, 1.0]) @ _rotation(rng)]
+    for (i, j) in ((0, 1), (1, 2), (2, 0)):
+        S = np.eye(3)
+        S[i, j] = 0.5
+        Rs.append(S)
+        Rs.append(_rotation(rng) @ S)
+    rows = [(k % 2, k % 3, centre(k % 2, k % 2 == 1, margin=6), _level_sd(p, k % 2, k % 3)) for k in range(len(Rs))]
+    lists["nonortho"] = mk(rows, Rs)
+    # borders: xd = 0, xd * 2^o just below nx, windows clipped on all six faces
+    rows = []
+    for o in (0, 2):
+        n = _level_dims(p, o)
+        f = 2.0 ** o
+        lo = [0.0, 0.0, 0.0]
+        hi = [np.nextafter(n[i] * 1.0, 0.0) for i in range(3)]   # xd * 2^o < nx in the octave's voxels
+        assert all(h * f < n0 for h, n0 in zip(hi, _level_dims(p, 0)))
+        rows += [(o, 0, lo, _level_sd(p, o, 0)), (o, 1, hi, _level_sd(p, o, 1))]
+        for ax in range(3):
+            c = [v / 2.0 for v in n]
+            c[ax] = 1.0
+            rows.append((o, 1, list(c), _level_sd(p, o, 1)))
+            c = [v / 2.0 + 0.25 for v in n]
+            c[ax] = n[ax] - 1.5
+            rows.append((o, 2, list(c), _level_sd(p, o, 2)))
+    lists["border"] = mk(rows, [_rotation(rng) for _ in rows])
+    # refusals (verify_keys): each list is two valid keypoints and one offender in the middle
+    nx = _level_dims(p, 0)[0]
+    good = [(0, 0, [20.0, 20.0, 20.0], _level_sd(p, 0, 0)), (1, 1, [10.5, 9.0, 11.0], _level_sd(p, 1, 1))]
+    bad = {"ref_neg": (0, 0, [-1e-9, 20.0, 20.0], _level_sd(p, 0, 0)),
+           "ref_eqnx": (1, 0, [nx / 2.0, 10.0, 10.0], _level_sd(p, 1, 0)),
+           "ref_sd0": (0, 1, [20.0, 21.0, 22.0], 0.0),
+           "ref_sdneg": (0, 1, [20.0, 21.0, 22.0], -1.0),
+           "ref_below_nx": (1, 0, [np.nextafter(nx / 2.0, 0.0), 10.0, 10.0], _level_sd(p, 1, 0))}
+    for case, b in bad.items():
+        rows = [good[0], b, good[1]]
+        lists[case] = mk(rows, [_rotation(rng) for _ in rows])
+    return lists
+
+
+def _g7_aniso_lists(p, rng):
+    rows = []
+    for o in range(p.num_octaves):
+        n = _level_dims(p, o)
+        for s in (-1, 0, 1, 2, 3):
+            for f in (1.0, 1.3):
+                rows.append(((o, s), [rng.uniform(3, v - 3) for v in n] + [f * _level_sd(p, o, s)]))
+    return {"aniso": (np.array([r[0] for r in rows]), np.array([r[1] for r in rows]),
+                      np.array([_rotation(rng) for _ in rows]))}
+
+
+def _g7_axis_lists(p, rng):
+    # R = I and the axis permutations (det +1 and -1) on the step volume: every rotated interior gradient lies on
+    # an icosahedron edge (the x, y, z axes bisect edges of the mesh), so every voxel takes the full face scan
+    perms = [np.eye(3)[list(q)] for q in ((0, 1, 2), (1, 2, 0), (2, 0, 1), (1, 0, 2), (0, 2, 1), (2, 1, 0))]
+    rows, Rs = [], []
+    for k, P in enumerate(perms):
+        for o, s, frac in ((0, 0, False), (0, 1, True), (1, 0, k % 2 == 0)):
+            n = _level_dims(p, o)
+            c = [v / 2.0 + (0.37 if frac else 0.0) for v in n]
+            rows.append(((o, s), c + [_level_sd(p, o, s)]))
+            Rs.append(P)
+    return {"axis": (np.array([r[0] for r in rows]), np.array([r[1] for r in rows]), np.array(Rs, np.float32))}
+
+
+def _g7_wide_lists(p, rng):
+    # one keypoint whose window row spans more than 1024 voxels (sd 64 on a 1300-voxel-wide volume; the box stays
+    # below 2048 voxels on every axis), with R = I and a random rotation; and an ordinary one beside them
+    sd0 = _level_sd(p, 0, 0)
+    rows = [((0, 0), [650.0, 10.0, 10.0, 64.0]), ((0, 1), [649.5, 9.5, 9.75, 60.0]),
+            ((0, 0), [100.0, 10.0, 10.0, sd0])]
+    return {"wide": (np.array([r[0] for r in rows]), np.array([r[1] for r in rows]),
+                     np.array([np.eye(3, dtype=np.float32), _rotation(rng), _rotation(rng)]))}
+
+
+def _g7_switch_lists(p, rng):
+    # level-0/1 keypoints with sd large enough for windows of > 1.9e5 voxels ((20 sd)^3 / (ux uy uz 8^o)), and some
+    # just below that, at integer and fractional centres
+    rows = []
+    for o, s, sd in ((0, 0, 2.5), (0, 0, 3.0), (0, 1, 3.3), (0, 0, 4.0), (0, 1, 6.0), (1, 0, 5.0), (1, 0, 6.4),
+                     (1, 1, 8.0), (0, 0, 2.8), (0, 2, 3.5)):
+        n = _level_dims(p, o)
+        frac = len(rows) % 2 == 1
+        rows.append(((o, s), [v / 2.0 + (0.4 if frac else 0.0) for v in n] + [sd]))
+    return {"switch": (np.array([r[0] for r in rows]), np.array([r[1] for r in rows]),
+                       np.array([_rotation(rng) for _ in rows]))}
+
+
+def g7_all():
+    out = {}
+    out.update(g7_keypoints("g7_survey64", so.synth_survey(64), dict(gen="survey", n=64, nblob=200),
+                            make_lists=_g7_survey64_lists))
+    out.update(g7_keypoints("g7_aniso", so.synth_survey((40, 33, 47)), dict(gen="survey", n=[40, 33, 47]),
+                            units=(1.0, 1.5, 0.7), make_lists=_g7_aniso_lists))
+    out.update(g7_keypoints("g7_axis", _steps_volume((48, 40, 44), 7), dict(gen="steps", n=[48, 40, 44], seed=7),
+                            make_lists=_g7_axis_lists))
+    out.update(g7_keypoints("g7_wide", so.synth_survey((1300, 20, 20)), dict(gen="survey", n=[1300, 20, 20]),
+                            make_lists=_g7_wide_lists))
+    out.update(g7_keypoints("g7_switch", so.synth_survey(96), dict(gen="survey", n=96),
+                            make_lists=_g7_switch_lists))
+    return out
+
+
 def g6_abi():
     """The link-level contract as data, for machines without the reference: the names the unmodified
     reference library exports (libsift3D_ref.so) and the names its own CLI -- cli/kpSift3D.c compiled unchanged
@@ -328,6 +531,8 @@ def main():
                                      input_spec=dict(gen="lattice", n=48, seed=7)),
         "g4_csv": g4_csv,
         "g6_abi": g6_abi,
+        # describe on caller-made keypoint lists (g7_*)
+        "g7": g7_all,
     }
     if a.big:
         jobs["g5_128"] = lambda: end_to_end(

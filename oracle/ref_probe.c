@@ -221,6 +221,30 @@ PROBE int probe_describe(probe_ctx *c)
     return sift3d_extract_descriptors(c->det, c->kp, c->desc);
 }
 
+/* Replace the keypoint store's contents with n caller-made keypoints (describe on keypoints that
+ * did not come from detect): os = (o, s) pairs, xyzsd = (xd, yd, zd, sd), R = 9 floats row-major
+ * each.  The store is resized and its R views re-pointed as the reference does (sift.c:339-369). */
+PROBE int probe_set_kp(probe_ctx *c, int n, const int *os, const double *xyzsd, const float *R)
+{
+    int i;
+    if (n < 1 || resize_Keypoint_store(c->kp, (size_t)n))
+        return -1;
+    for (i = 0; i < n; i++) {
+        sift3d_keypoint *const k = c->kp->buf + i;
+        if (init_Keypoint(k))
+            return -1;
+        k->o = os[2 * i];
+        k->s = os[2 * i + 1];
+        k->xd = xyzsd[4 * i];
+        k->yd = xyzsd[4 * i + 1];
+        k->zd = xyzsd[4 * i + 2];
+        k->sd = xyzsd[4 * i + 3];
+        k->strength = 0.0f;
+        memcpy(k->r_data, R + 9 * i, 9 * sizeof(float));
+    }
+    return 0;
+}
+
 PROBE void probe_sort(probe_ctx *c, int limit)
 {
     sift3d_keypoint_store_sort_by_strength(c->kp, limit);

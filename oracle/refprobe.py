@@ -48,6 +48,7 @@ def lib(cuboid=False):
         L.probe_detect_public.argtypes = [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int]
         L.probe_describe.argtypes = [C.c_void_p]
         L.probe_sort.argtypes = [C.c_void_p, C.c_int]
+        L.probe_set_kp.argtypes = [C.c_void_p, C.c_int, _i32p, _f64p, _f32p]
         for n in ("probe_num_octaves", "probe_num_cand", "probe_num_kp"):
             getattr(L, n).argtypes = [C.c_void_p]
         L.probe_get_cand.argtypes = [C.c_void_p, _i32p, _f32p, _f64p]
@@ -158,6 +159,14 @@ class Probe:
 
     def describe(self):
         return self.L.probe_describe(self.h)
+
+    def set_keypoints(self, os_, xyzsd, R):
+        """Fill the reference's keypoint store: os_ (n, 2) int, xyzsd (n, 4) float64, R (n, 3, 3)."""
+        os_ = np.ascontiguousarray(os_, np.int32).reshape(-1, 2)
+        xyzsd = np.ascontiguousarray(xyzsd, np.float64).reshape(-1, 4)
+        R = np.ascontiguousarray(R, np.float32).reshape(-1, 9)
+        assert len(os_) == len(xyzsd) == len(R)
+        return self.L.probe_set_kp(self.h, len(os_), os_, xyzsd, R)
 
     def sort(self, limit):
         self.L.probe_sort(self.h, int(limit))

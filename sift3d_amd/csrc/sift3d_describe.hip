@@ -200,7 +200,7 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // records of half a batch, field-major: rows 0..7 mag * trilinear weight of the eight cells,
     // 8..10 barycentric weights, 11..13 byte address of bin (base cell, face vertex j)
     __shared__ __attribute__((aligned(16))) float rec_[DWAVES][14][RROW];
-    __shared__ int queue_[DWAVES][DQ];   // xx | yy<<10 | zz<<20, window-relative, in scan order
+    __shared__ int queue_[DWAVES][DQ];   // xx | yy<<xsh | zz<<ysh, window-relative, in scan order
     __shared__ __attribute__((aligned(16))) float sface[20 * FACE_STRIDE]; // c_face16 (per-lane face index)
     __shared__ int soct[32];      // c_oct_face
     __shared__ uint64_t sexp[32]; // s3d_exp2_tab (per-lane index)
@@ -297,6 +297,12 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // memory safety on Z-slabs: never outside the local planes (see k_orient)
     B.zs = max(B.zs, L.z_off + 1);
     B.ze = min(B.ze, L.z_off + L.nz - 2);
+    // Queued voxels are packed as their offsets in the box, xx | yy << xsh | zz << ysh (unsigned), the fields as
+    // wide as the box's extents need (wave-uniform): a window row of any width (the host refuses a box whose
+    // three fields do not fit in 32 bits, sift3d_extract_descriptors)
+    const int xsh = 32 - __builtin_clz((unsigned)max(B.xe - B.xs, 1));
+    const int ysh = xsh + 32 - __builtin_clz((unsigned)max(B.ye - B.ys, 1));
+    const uint32_t xmask = (1u << xsh) - 1u, ymask = (1u << (ysh - xsh)) - 1u;
     // phase B roles: each half-wave commits one voxel per round; its lanes 0..23 are the
     // (trilinear cell corner, face vertex) pairs of that voxel.  Lanes 24..31 repeat lane 0's
     // work (same address, same value: harmless; giving them scratch slots of their own measured
@@ -353,24 +359,24 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     auto prefetch_loads = [&](uint32_t start, int cnt) {
         const int qv = queue[(start + lane) & (DQ - 1)];
         ppk = lane < cnt ? qv : ppk;
-        const int x = B.xs + (ppk & 1023), y = B.ys + ((ppk >> 10) & 1023),
-                  zl = B.zs + (ppk >> 20) - L.z_off;
+        const int x = B.xs + (int)((uint32_t)ppk & xmask), y = B.ys + (int)(((uint32_t)ppk >> xsh) & ymask),
+                  zl = B.zs + (int)((uint32_t)ppk >> ysh) - L.z_off;
         const gfloat_p p = gdata + ((uint64_t)zs32 * (uint32_t)zl + (uint32_t)(x + (int)ys32 * y));
         pv[0] = p[1]; pv[1] = *(p - 1); pv[2] = p[ys32]; pv[3] = *(p - ys32);
         pv[4] = p[zs32]; pv[5] = *(p - zs32);
         if (wtab) {
             // the Gaussian weight is a seventh (L2-resident) load, in flight with the samples
-            const int i = x - icx, j = y - icy, l = B.zs + (ppk >> 20) - icz;
+            const int i = x - icx, j = y - icy, l = B.zs + (int)((uint32_t)ppk >> ysh) - icz;
             pv[6] = wtab[i * i + j * j + l * l];
         }
     };
     auto prefetch_weight = [&]() {
         if (wtab)
             return;
-        const int x = B.xs + (ppk & 1023), y = B.ys + ((ppk >> 10) & 1023);
+        const int x = B.xs + (int)((uint32_t)ppk & xmask), y = B.ys + (int)(((uint32_t)ppk >> xsh) & ymask);
         const float dx = ((float)x - K.cx) * L.ux;                 // sift.c:102-104
         const float dy = ((float)y - K.cy) * L.uy;
-        const float dz = ((float)(B.zs + (ppk >> 20)) - K.cz) * L.uz;
+        const float dz = ((float)(B.zs + (int)((uint32_t)ppk >> ysh)) - K.cz) * L.uz;
         // (queued voxels passed the window test: the argument lies in [-2, 0])
         pv[6] = s3d_expf_in_range(-0.5f * (dx * dx + dy * dy + dz * dz) / sig2, sexp); // sift.c:1498
     };
@@ -505,7 +511,8 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
         commit_write(0);
         {
             COMMIT_BEGIN(coff_a);
-            ROUND(0, x = B.xs + (pk & 1023); y = B.ys + ((pk >> 10) & 1023); z = B.zs + (pk >> 20);
+            ROUND(0, x = B.xs + (int)((uint32_t)pk & xmask); y = B.ys + (int)(((uint32_t)pk >> xsh) & ymask);
+                     z = B.zs + (int)((uint32_t)pk >> ysh);
                      dx = ((float)x - K.cx) * L.ux; KEEP(dx);)             // sift.c:102-104
             ROUND(1, dy = ((float)y - K.cy) * L.uy; dz = ((float)z - K.cz) * L.uz; KEEP(dy); KEEP(dz);
                      // IM_GET_GRAD_ISO (sift.c:140-145, immacros.h:105-111)
@@ -590,13 +597,14 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
             // (valid) voxel and simply fetch it again
             ROUND(0, qv_ = queue[(nstart + lane) & (DQ - 1)];)
             ROUND(1, ppk = lane < ncnt ? qv_ : ppk;
-                     nx_ = B.xs + (ppk & 1023); ny_ = B.ys + ((ppk >> 10) & 1023); nzl_ = B.zs + (ppk >> 20) - L.z_off;
+                     nx_ = B.xs + (int)((uint32_t)ppk & xmask); ny_ = B.ys + (int)(((uint32_t)ppk >> xsh) & ymask);
+                     nzl_ = B.zs + (int)((uint32_t)ppk >> ysh) - L.z_off;
                      np_ = gdata + ((uint64_t)zs32 * (uint32_t)nzl_ + (uint32_t)(nx_ + (int)ys32 * ny_));)
             ROUND(2, pv[0] = np_[1]; pv[1] = *(np_ - 1); pv[2] = np_[ys32]; pv[3] = *(np_ - ys32);)
             // the Gaussian weight is a seventh (L2-resident) load, in flight with the samples (without a
             // table the load is a dummy and prefetch_weight() computes the weight)
             ROUND(3, pv[4] = np_[zs32]; pv[5] = *(np_ - zs32);
-                     const int i = nx_ - icx; const int j = ny_ - icy; const int l = B.zs + (ppk >> 20) - icz;
+                     const int i = nx_ - icx; const int j = ny_ - icy; const int l = B.zs + (int)((uint32_t)ppk >> ysh) - icz;
                      pv[6] = wsrc[(i * i + j * j + l * l) & wmask];)
             // trilinear cell weights (sift.c:1318-1320, 1361-1363): weight = wx * wy * wz,
             // value = mag * weight * bary.  A corner beyond the last cell is skipped by the
@@ -663,10 +671,19 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // that passes the window test lies in the sphere AND in the rotated 4x4x4 cube, so each
     // plane only needs the voxels of a (conservative: +1 voxel, +0.1 %) rectangle around the
     // plane's disc, clipped to the cube's extent along the image axes; the exact per-voxel
-    // test decides.
-    const float cube_x = half_w * (fabsf(R[0]) + fabsf(R[1]) + fabsf(R[2])) * 1.001f;
-    const float cube_y = half_w * (fabsf(R[3]) + fabsf(R[4]) + fabsf(R[5])) * 1.001f;
-    const float cube_z = half_w * (fabsf(R[6]) + fabsf(R[7]) + fabsf(R[8])) * 1.001f;
+    // test decides.  The cube's extent half_w * sum_j |R_ij| holds for an orthonormal R (v = R k); the reference
+    // takes any matrix, so an R whose columns are not orthonormal to 1e-4 (R^T R - I, wave-uniform) is bounded
+    // by the sphere alone.
+    float ortho = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = a; b < 3; b++)
+            ortho = fmaxf(ortho, fabsf(R[a] * R[b] + R[3 + a] * R[3 + b] + R[6 + a] * R[6 + b] - (a == b ? 1.0f : 0.0f)));
+    const bool cube_ok = ortho <= 1e-4f;
+    const float cube_x = cube_ok ? half_w * (fabsf(R[0]) + fabsf(R[1]) + fabsf(R[2])) * 1.001f : rad * 1.001f;
+    const float cube_y = cube_ok ? half_w * (fabsf(R[3]) + fabsf(R[4]) + fabsf(R[5])) * 1.001f : rad * 1.001f;
+    const float cube_z = cube_ok ? half_w * (fabsf(R[6]) + fabsf(R[7]) + fabsf(R[8])) * 1.001f : rad * 1.001f;
     int zs = max(B.zs, (int)floorf(K.cz - cube_z / L.uz - 1.0f));
     int ze = min(B.ze, (int)ceilf(K.cz + cube_z / L.uz + 1.0f));
     if (split) {
@@ -752,7 +769,7 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
 #endif
             in0 = in0 && c0 + 2 * lane < ppe;
             in1 = in1 && c0 + 2 * lane < ppe && xx + 1 < pbx;
-            const int pk0 = (ox + xx) | ((oy + yy) << 10) | ((z - B.zs) << 20);
+            const int pk0 = (int)((uint32_t)(ox + xx) | ((uint32_t)(oy + yy) << xsh) | ((uint32_t)(z - B.zs) << ysh));
             const int pk1 = pk0 + 1;
             xx += r128;
             yy += q128;

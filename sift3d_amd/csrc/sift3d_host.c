@@ -1143,6 +1143,26 @@ int sift3d_amd_detector_set_exact_descriptors(sift3d_detector *d, int mode)
     return SIFT3D_SUCCESS;
 }
 
+/* Bits of the binary representation of v >= 0 (0 for 0) */
+static int pack_bits(long v)
+{
+    int b = 0;
+    for (; v > 0; v >>= 1)
+        b++;
+    return b;
+}
+
+/* The decision of exact_desc_first_level (below) for ONE keypoint, from its own sd and its octave's units
+ * (caller-made keypoints need not carry their level's sd): 1 when its window holds more than 1.9e5 voxels. */
+static int exact_desc_keypoint(int mode, double sd, int o, const double *units)
+{
+    double side;
+    if (mode)
+        return mode > 0;
+    side = 2.0 * (2.0 * sd * 7.071067812 / 1.4142135623730951);
+    return side * side * side / ldexp(units[0] * units[1] * units[2], 3 * o) > 1.9e5;   /* octave o: units * 2^o */
+}
+
 /* First level-in-octave index (s + 1, Gaussian index) whose keypoints take the reference-order descriptor
  * kernel (sift3d_hip_describe_ex); ngl when none does.  A window of level s holds ~ (2 * half)^3 /
  * (ux uy uz) voxels with half = 2 * sd * 7.071 / sqrt(2) (sift.c:1453-1456) and sd / units the same in
@@ -2225,7 +2245,7 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
 {
     const int num = (int)kp->num;
     const double t_start = now_s();
-    int i, lvbad = 0, lv_exact = 0;
+    int i, lvbad = 0;
     size_t n_exact = 0;
     uint64_t rng;
 
@@ -2276,6 +2296,26 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
             return SIFT3D_FAILURE;
         }
     }
+    /* k_describe queues a window voxel as its offsets in the window's box, packed into 32 bits in fields as wide
+     * as the box's extents need (sift3d_describe.hip).  Every box fits when the octave-0 extents do; otherwise a
+     * keypoint whose box does not fit is refused here, before any launch. */
+    if (pack_bits(d->odims[0][0]) + pack_bits(d->odims[0][1]) + pack_bits(d->odims[0][2]) > 32) {
+        for (i = 0; i < num; i++) {
+            const keypoint_t *k = kp->buf + i;
+            const double rad = 14.142135624 * k->sd * (1.0 + 1e-6);       /* sift.c:1453-1454 */
+            int bits = 0, a;
+            for (a = 0; a < 3; a++) {
+                const double lu = ldexp(d->units[a], k->o), ext = 2.0 * rad / lu + 3.0;
+                const int n = d->odims[k->o][a];
+                bits += pack_bits(ext < (double)n ? (long)ext : n);
+            }
+            if (bits > 32) {
+                ERR("sift3d_amd: keypoint %d: its descriptor window (sd %f) spans more than 2^32 voxels of its "
+                    "box \n", i, k->sd);
+                return SIFT3D_FAILURE;
+            }
+        }
+    }
     if ((uint32_t)num > d->kp_cap) {
         const uint32_t cap = (uint32_t)num + (uint32_t)num / 4 + 256;
         sift3d_hip_host_free(d->h_kp);
@@ -2286,48 +2326,50 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
         d->kp_cap = cap;
     }
     {
-        /* Launch order: widest windows first.  The window radius in level voxels grows with
-         * the level index s only (14.14 * sigma0 * 2^(s/K)), and a keypoint of the last level
-         * costs ~4x one of the first; longest-job-first keeps the tail of the one-wave-per-
-         * keypoint kernel short.  row1 sends every histogram to its keypoint's row.
-         * A stable counting sort by level on a few threads: per-thread counts per level, then every
-         * thread places the keypoints of its part of the list. */
+        /* Launch order: the keypoints of the reference-order kernel first, then the others; within each part
+         * widest windows first.  The window radius in level voxels grows with the level index s only
+         * (14.14 * sigma0 * 2^(s/K)) for detect's keypoints, and a keypoint of the last level costs ~4x one of
+         * the first; longest-job-first keeps the tail of the one-wave-per-keypoint kernel short.  row1 sends
+         * every histogram to its keypoint's row.
+         * A stable counting sort by (kernel, level) on a few threads: per-thread counts per bucket, then every
+         * thread places the keypoints of its part of the list.  Bucket b = level (reference-order kernel) or
+         * nlv + level (fast commit): the kernel is chosen per keypoint, from its own sd (exact_desc_keypoint). */
         enum { LV_MAX = 32 };
         const int nt = host_threads((size_t)num), nlv = d->ngl;       /* s + 1 in [0, ngl) */
-        size_t cnt[HOST_THREADS_MAX][LV_MAX], start[HOST_THREADS_MAX][LV_MAX];
+        const int mode = d->exact_desc;
+        size_t cnt[HOST_THREADS_MAX][2 * LV_MAX], start[HOST_THREADS_MAX][2 * LV_MAX];
         if (nlv > LV_MAX) {
             ERR("sift3d_amd: at most %d Gaussian levels per octave are supported \n", LV_MAX);
             return SIFT3D_FAILURE;
         }
         memset(cnt, 0, sizeof(cnt));
-        lv_exact = exact_desc_first_level(d->exact_desc, d->ngl, d->num_kp_levels, d->sigma0, d->units);
+#define DESC_BUCKET(k) ((k)->s + 1 + (exact_desc_keypoint(mode, (k)->sd, (k)->o, d->units) ? 0 : nlv))
 #pragma omp parallel num_threads(nt)
         {
             const int nth = omp_get_num_threads(), t = omp_get_thread_num();  /* (nth <= nt: see above) */
             const size_t lo = (size_t)num * t / nth, hi = (size_t)num * (t + 1) / nth;
             size_t q;
             for (q = lo; q < hi; q++)
-                cnt[t][kp->buf[q].s + 1]++;
+                cnt[t][DESC_BUCKET(kp->buf + q)]++;
 #pragma omp barrier
 #pragma omp single
             {
                 size_t pos = 0;
-                int lv, u;
-                for (lv = nlv - 1; lv >= 0; lv--) {
-                    if (lv == lv_exact - 1)
-                        n_exact = pos;         /* (widest windows first: the exact ones lead the list) */
+                int b, u;
+                for (b = 0; b < 2 * nlv; b++) {
+                    const int bk = b < nlv ? nlv - 1 - b : 3 * nlv - 1 - b;   /* levels descending in each part */
+                    if (b == nlv)
+                        n_exact = pos;         /* (the exact ones lead the list) */
                     for (u = 0; u < nth; u++) {
-                        start[u][lv] = pos;
-                        pos += cnt[u][lv];
+                        start[u][bk] = pos;
+                        pos += cnt[u][bk];
                     }
                 }
-                if (lv_exact <= 0)
-                    n_exact = pos;
             }
             /* (implicit barrier) */
             for (q = lo; q < hi; q++) {
                 const keypoint_t *k = kp->buf + q;
-                sift3d_hip_kp *r = d->h_kp + start[t][k->s + 1]++;
+                sift3d_hip_kp *r = d->h_kp + start[t][DESC_BUCKET(k)]++;
                 memcpy(r->R, k->R, sizeof(r->R));
                 r->cx = (float)k->xd;                  /* sift.c:1474-1476 */
                 r->cy = (float)k->yd;
@@ -2337,6 +2379,7 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
                 r->sd = k->sd;
             }
         }
+#undef DESC_BUCKET
     }
     /* do_extract_descriptors, sift.c:1561-1596 */
     desc->nx = d->odims[0][0];

@@ -203,3 +203,47 @@ def test_error_behaviour(oracle_mod):
     o3 = oracle_mod.Oracle()
     assert o3.set_volume(oracle_mod.synth_survey(16, nblob=4)) == 0
     assert o3.L.orc_set_sigma_n(o3.h, 5.0) != 0  # sigma_n > sigma0 * 2^(-1/K)
+
+
+# ----------------------------------------------------------------------------------------
+# describe on caller-made keypoint lists (tests/golden/g7_*): sub-voxel centres, sd off the
+# level's, levels s = -1 .. K + 1, general / non-orthonormal R, borders, refusals
+# ----------------------------------------------------------------------------------------
+G7 = ["g7_survey64", "g7_aniso", "g7_axis", "g7_wide", "g7_switch"]
+
+
+def g7_cases(g):
+    return json.loads(str(g["cases"]))
+
+
+def g7_records(g, case, dtype):
+    """The keypoint list of one g7 case as records of `dtype` (the oracle's or the API's layout)."""
+    os_, xyzsd, R = g[case + "_os"], g[case + "_xyzsd"], g[case + "_R"]
+    k = np.zeros(len(os_), dtype)
+    k["o"], k["s"] = os_[:, 0], os_[:, 1]
+    for i, f in enumerate(("xd", "yd", "zd", "sd")):
+        k[f] = xyzsd[:, i]
+    k["R"] = R
+    return k
+
+
+@pytest.mark.parametrize("name", G7)
+def test_g7_caller_keypoints(oracle_mod, name):
+    """The restatement's describe on every g7 list: the reference's verdict, and for accepted lists
+    every descriptor row and desc xyzsd bit for bit."""
+    g = util.load(name)
+    vol = util.golden_input(g, oracle_mod)
+    o = oracle_mod.Oracle()
+    assert o.detect(vol, tuple(g["units"])) == 0
+    assert o.num_octaves == int(g["num_octaves"])
+    for case in g7_cases(g):
+        assert o.set_keypoints(g7_records(g, case, oracle_mod.KP_DTYPE)) == 0
+        ok = o.describe() == 0
+        assert ok == bool(g[case + "_ok"]), case
+        if not ok:
+            continue
+        d = o.descriptors()
+        np.testing.assert_array_equal(np.stack([d[k] for k in ("xd", "yd", "zd", "sd")], 1),
+                                      g[case + "_desc_xyzsd"], err_msg=case)
+        np.testing.assert_array_equal(d["hist"], g[case + "_hist"], err_msg=case)
+        assert util.assert_desc_projection(d["hist"], g[case + "_proj"], rtol=1e-12) < 1e-12

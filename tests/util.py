@@ -28,6 +28,11 @@ def golden_input(g, so):
     if spec["gen"] == "survey":
         vol = so.synth_survey(spec["n"] if not isinstance(spec["n"], list) else tuple(spec["n"]),
                               nblob=spec.get("nblob"))
+    elif spec["gen"] == "steps":
+        # an axis-aligned step volume: plane x = i holds one PCG64 normal value (oracle/make_golden.py)
+        nx, ny, nz = spec["n"]
+        c = np.random.Generator(np.random.PCG64(spec["seed"])).standard_normal(nx).astype(np.float32)
+        vol = np.ascontiguousarray(np.broadcast_to(c, (nz, ny, nx)), np.float32)
     else:
         vol = so.synth_lattice(spec["n"], seed=spec["seed"])
     assert digest(vol) == str(g["input_digest"]), "synthetic generator drifted"
