@@ -479,6 +479,63 @@ SIFT3D_AMD_API int
 sift3d_amd_image_dense_descriptors_rotate(const sift3d_image *im, double sigma, float *out);
 
 /* ------------------------------------------------------------------------ */
+/* Dense demons refinement of a displacement field                          */
+/* ------------------------------------------------------------------------ */
+/* Multi-channel demons (Thirion's force with the symmetric, ESM gradient) moves a field until a moving feature
+ * image, warped through it, agrees with a fixed one at every voxel.  No upstream counterpart: pinned to this
+ * contract.  Inputs: fixed F[nc][nz][ny][nx], moving M[nc][mz][my][mx] (shapes may differ), nc >= 1, and a field
+ * u[3][nz][ny][nx] on the fixed grid, a pull map in moving voxels ("Displacement fields").  Voxel units only.
+ *
+ * Force delta = force(F, W, u), W = M warped through u (LINEAR, fill 0; [nc][nz][ny][nx]).  Per fixed voxel p:
+ *   1. inside(p): warp_field's inside test of q_d = (double) p_d + (double) u_d(p) against (mx, my, mz).  Not
+ *      inside: delta(p) = +0.0f on all three channels, and p adds nothing to the statistics.
+ *   2. d_c = F_c(p) - W_c(p) (float).
+ *   3. d_e is the derivative along axis e by step 1 of the Jacobian above (numpy.gradient's rules on the fixed
+ *      grid, float); g_ce = 0.5f * (d_e F_c(p) + d_e W_c(p)), the symmetric gradient.
+ *   4. In double, c = 0 .. nc-1 in order, unfused, every sum from 0.0:
+ *        num_e = sum_c (double) d_c * (double) g_ce
+ *        s_g   = sum_c (((double) g_c0 * g_c0 + (double) g_c1 * g_c1) + (double) g_c2 * g_c2)
+ *        s_d   = sum_c (double) d_c * d_c
+ *   5. den = s_g + a2 * s_d, a2 = alpha * alpha (double); delta_e = den > 0 ? (float)(num_e / den) : +0.0f.
+ * By Cauchy-Schwarz |num| <= sqrt(s_g) sqrt(s_d) and den >= 2 alpha sqrt(s_g) sqrt(s_d), so |delta(p)| <=
+ * 1 / (2 alpha) voxel before rounding: alpha (Thirion's normaliser) caps the step.
+ * Statistics of a call (SIFT3D_AMD_DEMONS_STATS_BYTES, 8-byte aligned): bytes 0-7 double sum = the sum of s_d
+ * over the inside voxels, bytes 8-15 uint64 count = the number of inside voxels.  The sum is reduced from
+ * per-workgroup partials in a fixed order (no float atomics): the same inputs give the same bits on every run;
+ * the order of the sum is not part of the contract.
+ *
+ * Iteration k = 0 .. iterations-1, every stage on `stream`:
+ *   1. W = sift3d_hip_warp_field(M, u, LINEAR, fill 0);
+ *   2. delta, stats[k] = force(F, W, u);
+ *   3. sigma_fluid > 0: each of delta's 3 channels blurred in place by the detector's blur (blur_level) with
+ *      the taps of sift3d_amd_gauss_filter(sigma_fluid), units (1, 1, 1), unit 1.0 (step 3 of "Dense
+ *      descriptors");
+ *   4. u_d = u_d + delta_d per element (float add);
+ *   5. sigma_diffusion > 0: each of u's 3 channels blurred the same way.
+ * iterations == 0 leaves u untouched.
+ *
+ * Arguments are checked before any device call: -1 on NULL pointers, dims <= 0, nc < 1, iterations < 0, alpha
+ * not positive and finite, a sigma negative or not finite, misalignment (d_stats and d_work 8 B, the rest 4 B),
+ * an output (or the work buffer) that overlaps an input, the work buffer or another output.  Asynchronous on
+ * `stream`, no allocation, no host synchronisation, 64-bit offsets. */
+#define SIFT3D_AMD_DEMONS_STATS_BYTES 16
+/* d_work of sift3d_hip_demons_force: the per-workgroup partials */
+#define SIFT3D_AMD_DEMONS_FORCE_WORK_BYTES 32768
+/* one force: d_F, d_W [nc][nz][ny][nx], d_u and d_step [3][nz][ny][nx], d_stats 16 B, d_work
+ * SIFT3D_AMD_DEMONS_FORCE_WORK_BYTES */
+SIFT3D_AMD_API int
+sift3d_hip_demons_force(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx, int my,
+                        int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work, void *stream);
+/* device scratch of sift3d_amd_demons_device, in floats: the force's partials, W (nc planes), delta (3) and the
+ * blur's two intermediates (0 for bad arguments) */
+SIFT3D_AMD_API size_t sift3d_amd_demons_work_floats(int nx, int ny, int nz, int nc);
+/* `iterations` iterations on device buffers: d_u in / out, d_stats 16 B per iteration (iteration k at 16 k) */
+SIFT3D_AMD_API int
+sift3d_amd_demons_device(const float *d_F, int nx, int ny, int nz, const float *d_M, int mx, int my, int mz, int nc,
+                         float *d_u, int iterations, double alpha, double sigma_fluid, double sigma_diffusion,
+                         float *d_work, void *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

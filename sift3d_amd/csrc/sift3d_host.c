@@ -2521,3 +2521,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* thin-plate spline: fit, evaluation, device layout, warp of host images */
 #include "sift3d_tps.c"
+
+/* dense demons refinement of a displacement field */
+#include "sift3d_demons.c"

@@ -116,6 +116,11 @@ def lib():
         "sift3d_amd_dense_rotate_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
         "sift3d_amd_dense_descriptors_rotate_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int,
                                                                  C.POINTER(C.c_double), C.c_double, vp, vp, vp]),
+        "sift3d_hip_demons_force": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_double, vp, vp, vp, vp]),
+        "sift3d_amd_demons_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_demons_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               vp, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -451,6 +456,86 @@ def dense_descriptors_rotate(src, out, sigma, units=(1, 1, 1), work=None):
                                                             out.data_ptr(), work.data_ptr(), current_stream()),
            "sift3d_amd_dense_descriptors_rotate_device")
     return out
+
+
+DEMONS_STATS_BYTES = 16
+DEMONS_FORCE_WORK_BYTES = 32768
+
+
+def _demons_images(F, M, field, what):
+    import torch
+    for t, name in ((F, "fixed"), (M, "moving")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.dim() in (3, 4)):
+            raise ValueError("%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]"
+                             % (what, name))
+    _field_tensor(field, what)
+    nc = F.shape[0] if F.dim() == 4 else 1
+    if M.dim() != F.dim() or (M.shape[0] if M.dim() == 4 else 1) != nc:
+        raise ValueError("%s: fixed %s and moving %s differ in channels" % (what, tuple(F.shape), tuple(M.shape)))
+    if tuple(field.shape[1:]) != tuple(F.shape[-3:]):
+        raise ValueError("%s: the field %s is not on the fixed grid %s" % (what, tuple(field.shape), tuple(F.shape)))
+    if not (F.device == M.device == field.device):
+        raise ValueError("%s: fixed, moving and field are not on one device" % what)
+    nz, ny, nx = F.shape[-3:]
+    mz, my, mx = M.shape[-3:]
+    return nc, (nx, ny, nz), (mx, my, mz)
+
+
+def demons_stats(stats):
+    """(sum float64 array, count uint64 array) of demons statistics (a CUDA tensor of 16-byte records); waits
+    for the stream that wrote them"""
+    import torch
+    raw = stats.view(torch.uint8).cpu().numpy().reshape(-1, DEMONS_STATS_BYTES)
+    return raw[:, :8].copy().view(np.float64)[:, 0], raw[:, 8:].copy().view(np.uint64)[:, 0]
+
+
+def demons_force(F, W, field, step, alpha, moving_shape=None, stats=None, work=None):
+    """One demons force (sift3d_hip_demons_force; contract in include/sift3d_amd.h, "Dense demons refinement"):
+    step [3, nz, ny, nx] from the fixed features F and the warped moving features W ([nz, ny, nx] or
+    [nc, nz, ny, nx]) and the field [3, nz, ny, nx]; moving_shape (mz, my, mx) is the moving grid of the inside
+    test (None: the fixed grid).  torch CUDA float32, on torch's current stream.  Returns the stats tensor
+    (16 bytes; read it with demons_stats)."""
+    import torch
+    nc, (nx, ny, nz), _ = _demons_images(F, W, field, "demons_force")
+    if tuple(W.shape[-3:]) != tuple(F.shape[-3:]):
+        raise ValueError("demons_force: W %s is not on the fixed grid %s" % (tuple(W.shape), tuple(F.shape)))
+    _field_tensor(step, "demons_force", "step")
+    if tuple(step.shape) != tuple(field.shape) or step.device != F.device:
+        raise ValueError("demons_force: step must be shaped like the field, on its device")
+    mz, my, mx = (nz, ny, nx) if moving_shape is None else (int(v) for v in moving_shape)
+    if stats is None:
+        stats = torch.empty(DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
+    if work is None:
+        work = torch.empty(DEMONS_FORCE_WORK_BYTES // 8, dtype=torch.int64, device=F.device)
+    _check(lib().sift3d_hip_demons_force(F.data_ptr(), nx, ny, nz, W.data_ptr(), field.data_ptr(), mx, my, mz, nc,
+                                         float(alpha), step.data_ptr(), stats.data_ptr(), work.data_ptr(),
+                                         current_stream()), "sift3d_hip_demons_force")
+    return stats
+
+
+def demons(F, M, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None):
+    """`iterations` demons iterations (sift3d_amd_demons_device): the field [3, nz, ny, nx] is refined in place so
+    that the moving features M ([mz, my, mx] or [nc, mz, my, mx]) warped through it approach the fixed features F
+    ([nz, ny, nx] / [nc, nz, ny, nx]).  torch CUDA float32, on torch's current stream, no host synchronisation.
+    Returns the stats tensor (16 bytes per iteration; read it with demons_stats)."""
+    import torch
+    nc, (nx, ny, nz), (mx, my, mz) = _demons_images(F, M, field, "demons")
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError("demons: iterations must not be negative")
+    need = lib().sift3d_amd_demons_work_floats(nx, ny, nz, nc)
+    if work is None:
+        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=F.device)
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.is_contiguous()
+            and work.numel() * work.element_size() >= 4 * need and work.device == F.device):
+        raise ValueError("demons: work must be a contiguous CUDA tensor of >= %d bytes on the device of F" % (4 * need))
+    stats = torch.empty(max(iterations, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
+    _check(lib().sift3d_amd_demons_device(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc, field.data_ptr(),
+                                          iterations, float(alpha), float(sigma_fluid), float(sigma_diffusion),
+                                          work.data_ptr(), stats.data_ptr(), current_stream()),
+           "sift3d_amd_demons_device")
+    return stats[:iterations * DEMONS_STATS_BYTES // 8]
 
 
 def absmax(src, out):
