@@ -536,6 +536,81 @@ sift3d_amd_demons_device(const float *d_F, int nx, int ny, int nz, const float *
                          float *d_work, void *d_stats, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Field composition, exponential and inverse                               */
+/* ------------------------------------------------------------------------ */
+/* Fields are float [3][z][y][x] pull maps in the source grid's voxels, as in "Displacement fields".
+ *
+ * Composition sample.  u on grid (ux, uy, uz); v on the output grid (ox, oy, oz), its values in u-grid voxels.
+ * Per output voxel p:
+ *   1. q_d = (double) p_d + (double) v_d(p);
+ *   2. inside: warp_field's inside test of q against u's grid;
+ *   3. qc_d = min(max(q_d, 0), n_d - 1) in double: outside its grid u is extended by its nearest edge value (ITK's
+ *      convention for composition and inversion); for inside voxels qc = q;
+ *   4. s_d = the LINEAR sample of u_d at qc, warp_field's arithmetic word for word (one set of taps for the three
+ *      channels).  For inside voxels s is bit-equal to warp_field(u, v, LINEAR);
+ *   5. a NaN in any v_d(p) makes all three outputs the quiet NaN 0x7fc00000; such a voxel is not inside and adds
+ *      nothing to the statistics.
+ * Modes: SIFT3D_AMD_FIELD_COMPOSE: out_d = v_d + s_d (float add), i.e. w(p) = v(p) + u(p + v(p)), read through v,
+ *   then through u.  SIFT3D_AMD_FIELD_INVERT: out_d = -s_d, one fixed-point step of the inverse of u.
+ * Statistics (SIFT3D_AMD_FIELD_STATS_BYTES, 8-byte aligned) are those of the residual r = v + s (float) whatever
+ * the mode, |r| = sqrt(((double) rx rx + (double) ry ry) + (double) rz rz): bytes 0-7 double sum of |r| and 8-15
+ * double max of |r| (0 when there is no voxel) over the non-NaN voxels, 16-23 uint64 count of non-NaN voxels,
+ * 24-31 uint64 count of inside voxels.  The sum is reduced from per-workgroup partials in a fixed order (no float
+ * atomics), so a call repeats its bits; the order of the sum is not part of the contract; the max and the counts
+ * are exact.  u is assumed finite.  d_out NULL: statistics only.  d_work (SIFT3D_AMD_FIELD_WORK_BYTES, the
+ * partials) may be NULL when d_stats is.
+ *
+ * Exponential by scaling and squaring (K squarings, 0 <= K <= SIFT3D_AMD_FIELD_MAX_SQUARINGS):
+ *   w_0 = v * 2^-K (float multiply), w_{k+1} = COMPOSE(u = w_k, v = w_k), exp(v) = w_K; K == 0 copies v.
+ * Inverse by fixed-point iteration (N >= 0 iterations): d_w holds the initial iterate on the output grid and
+ * receives w_N; w_{k+1} = INVERT(u, w_k), so a converged w satisfies w(q) = -u(q + w(q)).  Stats record k < N is
+ * the residual of w_k (from INVERT pass k), record N that of the returned w_N (a final statistics-only pass): N + 1
+ * records of SIFT3D_AMD_FIELD_STATS_BYTES.  For u fixed -> moving on the fixed grid, w lives on the moving grid
+ * (ox, oy, oz = the moving shape) and maps moving -> fixed.  The iteration contracts when u's Lipschitz constant
+ * L = max_d sum_e max |Delta_e u_d| over grid edges (the infinity-norm constant of the trilinear interpolant; the
+ * clamp is 1-Lipschitz) is below 1: |w_N - w*| <= L^N |w_0 - w*|.
+ *
+ * Diffeomorphic demons (sift3d_amd_demons_device_ex): update SIFT3D_AMD_DEMONS_ADDITIVE is step 4 of "Dense demons
+ * refinement" bit for bit (sift3d_amd_demons_device is it); SIFT3D_AMD_DEMONS_DIFFEOMORPHIC replaces step 4 with
+ *   4'. e = exp(delta) with `squarings` squarings, then u <- COMPOSE(u, e): u_new(p) = e(p) + u(p + e(p))
+ * (Vercauteren et al., Diffeomorphic demons, NeuroImage 2009).  Steps 1-3 and 5 are unchanged.  d_work holds
+ * sift3d_amd_demons_work_floats_ex floats: the additive driver's, plus 6 n for DIFFEOMORPHIC (u_new and the
+ * exponential's second buffer).
+ *
+ * All entries are asynchronous on `stream`, allocate nothing, do not synchronise with the host, use 64-bit offsets
+ * and check their arguments before any device call: -1 on NULL pointers, dims <= 0, K out of range, N < 0, an
+ * unknown mode or update, misalignment (d_stats and d_work 8 B, fields 4 B), an output that overlaps an input, the
+ * work buffer or another output (in-place composition included: neighbours are read). */
+#define SIFT3D_AMD_FIELD_COMPOSE 0
+#define SIFT3D_AMD_FIELD_INVERT 1
+#define SIFT3D_AMD_FIELD_STATS_BYTES 32
+#define SIFT3D_AMD_FIELD_WORK_BYTES 65536
+#define SIFT3D_AMD_FIELD_MAX_SQUARINGS 20
+#define SIFT3D_AMD_DEMONS_ADDITIVE 0
+#define SIFT3D_AMD_DEMONS_DIFFEOMORPHIC 1
+/* one composition sample pass; d_out [3][oz][oy][ox] may be NULL, d_stats may be NULL (then d_work may be too) */
+SIFT3D_AMD_API int
+sift3d_hip_field_compose(const float *d_u, int ux, int uy, int uz, const float *d_v, int ox, int oy, int oz,
+                         float *d_out /*NULL*/, int mode, void *d_stats /*NULL*/, void *d_work, void *stream);
+/* device scratch of sift3d_amd_field_exp_device: 3 ox*oy*oz floats (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_field_exp_work_floats(int ox, int oy, int oz);
+SIFT3D_AMD_API int
+sift3d_amd_field_exp_device(const float *d_v, int ox, int oy, int oz, int squarings, float *d_out, float *d_work,
+                            void *stream);
+/* device scratch of sift3d_amd_field_invert_device: the partials plus 3 ox*oy*oz floats (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_field_invert_work_floats(int ox, int oy, int oz);
+/* d_w [3][oz][oy][ox] in / out; d_stats (iterations + 1) records */
+SIFT3D_AMD_API int
+sift3d_amd_field_invert_device(const float *d_u, int ux, int uy, int uz, float *d_w, int ox, int oy, int oz,
+                               int iterations, float *d_work, void *d_stats, void *stream);
+SIFT3D_AMD_API size_t sift3d_amd_demons_work_floats_ex(int nx, int ny, int nz, int nc, int update);
+SIFT3D_AMD_API int
+sift3d_amd_demons_device_ex(const float *d_F, int nx, int ny, int nz, const float *d_M, int mx, int my, int mz,
+                            int nc, float *d_u, int iterations, double alpha, double sigma_fluid,
+                            double sigma_diffusion, int update, int squarings, float *d_work, void *d_stats,
+                            void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

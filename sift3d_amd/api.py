@@ -11,6 +11,7 @@ layout of sift3d_image_data() (reference: sift3d/imutil.c:520-533).
 """
 import collections
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -874,21 +875,41 @@ def _volume_tensor(v, what, name):
         raise ValueError("%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx]" % (what, name))
 
 
+DEMONS_UPDATES = ("additive", "diffeomorphic")
+
+
+def demons_squarings(alpha):
+    """The squarings of a diffeomorphic update by default: K = max(0, ceil(log2(1 / alpha))).  The force is capped
+    at |delta| <= 1 / (2 alpha) voxel (Cauchy-Schwarz; include/sift3d_amd.h, "Dense demons refinement"); the fluid
+    blur does not raise the max norm, as its taps are non-negative and normalised to sum 1 (gauss_filter, up to a
+    few ulps of float rounding) and its border rule is a convex combination of samples (the mirrored, linearly
+    interpolated extended line); so 2^-K / (2 alpha) <= 0.5 voxel, the criterion of Vercauteren et al. (2009)."""
+    a = float(alpha)
+    if not (math.isfinite(a) and a > 0):
+        raise ValueError("alpha must be positive and finite")
+    return max(0, int(math.ceil(math.log2(1.0 / a))))
+
+
 def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA,
                  sigma_fluid=DEMONS_SIGMA_FLUID, sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors",
-                 sigma=1.6):
+                 sigma=1.6, update="additive", squarings=None):
     """Dense demons refinement (contract: include/sift3d_amd.h, "Dense demons refinement") of a displacement
     field [3, nz, ny, nx] on fixed's grid (a pull map fixed voxel -> moving voxel; None: start from zero) so that
     the moving features warped through it agree with the fixed ones at every voxel.  moving, fixed: torch CUDA
     float32 tensors [nz, ny, nx] (shapes may differ).  features: "descriptors" (the dense descriptor images of
-    both, window sigma, 12 channels) or "intensity" (the volumes themselves: classic demons).  The caller's field
-    is not modified.  Returns DemonsRefinement(field, warped = moving through the field (linear, fill 0),
-    msd [iterations] (the mean of s_d over the voxels that sample inside, per iteration, before its update; NaN
-    when there is none), jacobian = jacobian_determinant(field))."""
+    both, window sigma, 12 channels) or "intensity" (the volumes themselves: classic demons).  update: "additive"
+    (u += delta) or "diffeomorphic" (u <- u o exp(delta), "Field composition, exponential and inverse"), with
+    `squarings` squarings of the exponential; None picks demons_squarings(alpha), which is 0 at the default alpha 2:
+    the update is then u o delta, a composition with the step itself.  The caller's field is not modified.
+    Returns DemonsRefinement(field, warped = moving through the field (linear, fill 0), msd [iterations] (the mean
+    of s_d over the voxels that sample inside, per iteration, before its update; NaN when there is none),
+    jacobian = jacobian_determinant(field))."""
     import torch
     from . import hip
     _volume_tensor(moving, "refine_field", "moving")
     _volume_tensor(fixed, "refine_field", "fixed")
+    if update not in DEMONS_UPDATES:
+        raise ValueError("update must be 'additive' or 'diffeomorphic', not %r" % (update,))
     if features == "descriptors":
         F, M = dense_descriptors(fixed, sigma), dense_descriptors(moving, sigma)
     elif features == "intensity":
@@ -900,7 +921,11 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     else:
         hip._field_tensor(field, "refine_field")
         u = field.clone()
-    stats = hip.demons(F, M, u, iterations, alpha, sigma_fluid, sigma_diffusion)
+    if update == "additive":
+        stats = hip.demons(F, M, u, iterations, alpha, sigma_fluid, sigma_diffusion)
+    else:
+        K = demons_squarings(alpha) if squarings is None else int(squarings)
+        stats = hip.demons(F, M, u, iterations, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
     sums, counts = hip.demons_stats(stats)
     with np.errstate(invalid="ignore", divide="ignore"):
         msd = np.where(counts > 0, sums / np.maximum(counts, 1).astype(np.float64), np.nan)
@@ -909,13 +934,93 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
 
 
 def register_dense(moving, fixed, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA, sigma_fluid=DEMONS_SIGMA_FLUID,
-                   sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, **deformable_kw):
-    """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field.
-    Returns DenseRegistration(A, tps, inliers, num_matches (as register_deformable), field, warped, msd, jacobian
-    (as refine_field))."""
+                   sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, update="additive",
+                   squarings=None, **deformable_kw):
+    """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field (update
+    and squarings as there).  Returns DenseRegistration(A, tps, inliers, num_matches (as register_deformable),
+    field, warped, msd, jacobian (as refine_field))."""
     _volume_tensor(moving, "register_dense", "moving")
     _volume_tensor(fixed, "register_dense", "fixed")
     d = register_deformable(moving, fixed, **deformable_kw)
     u = displacement_field(d.tps, tuple(fixed.shape), fixed.device)
-    r = refine_field(moving, fixed, u, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma)
+    r = refine_field(moving, fixed, u, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma, update,
+                     squarings)
     return DenseRegistration(d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped, r.msd, r.jacobian)
+
+
+# ---- field composition, exponential and inverse ---------------------------------------------------------------
+FieldInverse = collections.namedtuple("FieldInverse", "field residual_max residual_mean inside")
+
+# Fixed-point iterations of invert_field by default.  The step w <- -u(q + w) contracts with the factor L, u's
+# infinity-norm Lipschitz constant (include/sift3d_amd.h), so the error after N steps is at most L^N times the
+# first one: L^N <= 1e-6 at L <= 0.6 takes N >= log(1e-6) / log(0.6) = 27.05, so 28.
+INVERT_ITERATIONS = 28
+
+
+def _cuda_field(t, what, name="field"):
+    from . import hip
+    if not _torch_tensor(t):
+        raise ValueError("%s: %s must be a CUDA tensor" % (what, name))
+    hip._field_tensor(t, what, name)
+
+
+def compose_fields(u, v):
+    """w = u o v on v's grid: w(p) = v(p) + u(p + v(p)), read through v, then through u (u is extended by its
+    edge values outside its grid).  u [3, uz, uy, ux] and v [3, oz, oy, ox]: torch CUDA float32 pull maps, v's
+    values in u-grid voxels.  One kernel on torch's current stream; returns a new tensor shaped like v."""
+    import torch
+    from . import hip
+    _cuda_field(u, "compose_fields", "u")
+    _cuda_field(v, "compose_fields", "v")
+    out = torch.empty_like(v)
+    hip.field_compose(u, v, out, "compose")
+    return out
+
+
+def field_squarings(max_norm):
+    """The smallest K >= 0 with max_norm * 2^-K <= 0.5 voxel"""
+    m = float(max_norm)
+    if not math.isfinite(m):
+        raise ValueError("field_squarings: the field is not finite")
+    K = 0
+    while m * 2.0 ** -K > 0.5:
+        K += 1
+    return K
+
+
+def field_exp(v, squarings=None):
+    """exp(v) by scaling and squaring: w_0 = v 2^-K, w_{k+1} = w_k o w_k.  v [3, oz, oy, ox] torch CUDA float32.
+    squarings None: the smallest K >= 0 with max|v| 2^-K <= 0.5 voxel (Vercauteren et al., 2009); computing max|v|
+    in torch costs one host synchronisation.  Returns a new tensor on torch's current stream."""
+    import torch
+    from . import hip
+    _cuda_field(v, "field_exp", "v")
+    if squarings is None:
+        squarings = field_squarings(float(torch.sqrt((v.double() ** 2).sum(0)).max()))
+    out = torch.empty_like(v)
+    return hip.field_exp(v, out, squarings)
+
+
+def invert_field(u, out_shape, iterations=INVERT_ITERATIONS, init=None):
+    """The inverse of the pull map p -> p + u(p) by fixed-point iteration w <- -u(q + w(q)): u [3, uz, uy, ux]
+    torch CUDA float32 (e.g. fixed -> moving on the fixed grid), w on a grid of out_shape = (oz, oy, ox) (the
+    moving grid), mapping back; init: the first iterate (None: zero).  Converges when u's Lipschitz constant is
+    below 1.  Returns FieldInverse(field, residual_max, residual_mean, inside): per iterate w_0 .. w_N (N + 1
+    values), the max and mean of |w + u(q + w)| over the voxels and the number of voxels whose sample is inside
+    u's grid.  Reads the statistics, so it waits for torch's current stream."""
+    import torch
+    from . import hip
+    _cuda_field(u, "invert_field", "u")
+    oz, oy, ox = (int(s) for s in out_shape)
+    if init is None:
+        w = torch.zeros((3, oz, oy, ox), dtype=torch.float32, device=u.device)
+    else:
+        _cuda_field(init, "invert_field", "init")
+        if tuple(init.shape) != (3, oz, oy, ox):
+            raise ValueError("invert_field: init %s is not [3, %d, %d, %d]" % (tuple(init.shape), oz, oy, ox))
+        w = init.clone()
+    stats = hip.field_invert(u, w, iterations)
+    s, mx, cnt, ins = hip.field_stats(stats)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(cnt > 0, s / np.maximum(cnt, 1).astype(np.float64), np.nan)
+    return FieldInverse(w, mx, mean, ins.astype(np.int64))

@@ -703,6 +703,187 @@ bool overlap(const void *a, size_t na, const void *b, size_t nb)
     return a0 < b0 + nb && b0 < a0 + na;
 }
 
+// ---- field composition (contract: include/sift3d_amd.h, "Field composition, exponential and inverse") -----------
+// k_warp_field with the source u (3 channels) and the field v: the lane's 4 outputs read v (which also gives the
+// add's operand: no extra read), place one set of taps each -- clamped onto u's grid only when outside -- and gather
+// the three channels of u with them; the results leave through the same LDS exchange.  Statistics: per lane, per
+// wave by butterfly, per workgroup through LDS into partial slot blockIdx.x; k_compose_finish combines the slots in a
+// fixed order.  With statistics the grid is min(tiles, CMP_GRID) whatever the device, so the bits of the sum depend on
+// the shapes; without, it is k_warp_field's.
+constexpr unsigned CMP_GRID = SIFT3D_AMD_FIELD_WORK_BYTES / 32;    // slots: sum, max (double), two uint64 counts
+
+struct ComposeArgs {
+    WarpArgs w;                                  // src = u, dst = out (may be null), grids, tiles, vec
+    const float *v;
+    double *psum, *pmax;                         // [CMP_GRID] each
+    unsigned long long *pcnt, *pins;             // [CMP_GRID] each
+};
+
+template <int MODE, int LINEAR, bool STATS>
+__global__ __launch_bounds__(256) void k_field_compose(const ComposeArgs f)
+{
+    const WarpArgs &p = f.w;
+    __shared__ float4 xch[256];
+    __shared__ double s_sum[4], s_max[4];
+    __shared__ unsigned long long s_cnt[4], s_ins[4];
+    float *xs = reinterpret_cast<float *>(xch) + (threadIdx.x & ~15) * 4;
+    const int lx = threadIdx.x & 15, ly = (threadIdx.x >> 4) & 3, lz = threadIdx.x >> 6;
+    const size_t svox = (size_t)p.nx * (size_t)p.ny * (size_t)p.nz;
+    const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;
+    const double hx = (double)(p.nx - 1), hy = (double)(p.ny - 1), hz = (double)(p.nz - 1);
+    double lsum = 0.0, lmax = 0.0;
+    unsigned long long lcnt = 0, lins = 0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        const unsigned n = min(p.ntiles - base, gridDim.x);
+        if (blockIdx.x >= n)
+            break;                                                           // uniform over the block
+        const unsigned t = base + xcd_swizzle(blockIdx.x, n);
+        const unsigned tyz = t / (unsigned)p.tiles_x;
+        const int tx = (int)(t - tyz * (unsigned)p.tiles_x);
+        const int ty = (int)(tyz % (unsigned)p.tiles_y), tz = (int)(tyz / (unsigned)p.tiles_y);
+        const int xt = tx * TX, y = ty * TY + ly, z = tz * TZ + lz;
+        const bool row = y < p.oy && z < p.oz;
+        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+        // outputs past the grid read no field (v = 0), sample inside u and are neither stored nor counted
+        Taps tp[4];
+        float v[4][3];
+        bool live[4], in[4], nan[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            v[k][0] = v[k][1] = v[k][2] = 0.0f;
+            live[k] = row && x < p.ox;
+            if (live[k]) {
+                const float *src = f.v + orow + (size_t)x;
+                v[k][0] = src[0];
+                v[k][1] = src[ovox];
+                v[k][2] = src[2 * ovox];
+            }
+            double qx = (double)x + (double)v[k][0], qy = (double)y + (double)v[k][1];
+            double qz = (double)z + (double)v[k][2];
+            in[k] = (qx >= 0.0) & (qx <= hx) & (qy >= 0.0) & (qy <= hy) & (qz >= 0.0) & (qz <= hz);
+            nan[k] = (qx != qx) | (qy != qy) | (qz != qz);
+            if (!in[k]) {
+                // nearest-edge extension; a NaN stays NaN and taps_at sends it to voxel 0 (the output is NaN)
+                qx = qx < 0.0 ? 0.0 : qx > hx ? hx : qx;
+                qy = qy < 0.0 ? 0.0 : qy > hy ? hy : qy;
+                qz = qz < 0.0 ? 0.0 : qz > hz ? hz : qz;
+            }
+            tp[k] = taps_at<LINEAR>(p, qx, qy, qz);
+        }
+        float o[3][4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float r[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float s = gather<LINEAR>(p.src + (size_t)c * svox, tp[k], 0.0f);
+                r[c] = v[k][c] + s;
+                o[c][k] = nan[k] ? __int_as_float(0x7fc00000) : MODE == SIFT3D_AMD_FIELD_COMPOSE ? r[c] : -s;
+            }
+            if (STATS && live[k] && !nan[k]) {
+                const double m = sqrt(((double)r[0] * r[0] + (double)r[1] * r[1]) + (double)r[2] * r[2]);
+                lsum += m;
+                lmax = fmax(lmax, m);
+                lcnt += 1;
+                lins += in[k] ? 1 : 0;
+            }
+        }
+        if (!p.dst)
+            continue;                                                        // uniform: statistics only
+        const int x0 = xt + 4 * lx;
+        const bool st = row && x0 < p.ox;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            __syncthreads();                                                 // previous exchange's reads done
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                xs[lx + 16 * k] = o[c][k];
+            __syncthreads();
+            const float4 w = xch[threadIdx.x];
+            if (!st)
+                continue;
+            float *out = p.dst + (size_t)c * ovox + orow + (size_t)x0;
+            if (p.vec) {
+                st4(out, w);
+            } else {
+                const float ov[4] = {w.x, w.y, w.z, w.w};
+                const int m = min(4, p.ox - x0);
+#pragma nounroll
+                for (int k = 0; k < m; k++)
+                    out[k] = ov[k];
+            }
+        }
+    }
+    if (!STATS)
+        return;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        lsum += __shfl_xor(lsum, s);
+        lmax = fmax(lmax, __shfl_xor(lmax, s));
+        lcnt += __shfl_xor(lcnt, s);
+        lins += __shfl_xor(lins, s);
+    }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_sum[wv] = lsum;
+        s_max[wv] = lmax;
+        s_cnt[wv] = lcnt;
+        s_ins[wv] = lins;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        f.psum[blockIdx.x] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        f.pmax[blockIdx.x] = fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3]));
+        f.pcnt[blockIdx.x] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+        f.pins[blockIdx.x] = ((s_ins[0] + s_ins[1]) + s_ins[2]) + s_ins[3];
+    }
+}
+
+// the partial slots 0 .. n-1 in a fixed order (k_demons_finish's): lane t takes slots t, t + 256, ... in turn, then
+// a fixed tree; the record is {sum, max, count, inside}
+__global__ __launch_bounds__(256) void k_compose_finish(const ComposeArgs f, unsigned n, double *rec)
+{
+    __shared__ double s_sum[256], s_max[256];
+    __shared__ unsigned long long s_cnt[256], s_ins[256];
+    double a = 0.0, m = 0.0;
+    unsigned long long b = 0, c = 0;
+    for (unsigned i = threadIdx.x; i < n; i += 256) {
+        a += f.psum[i];
+        m = fmax(m, f.pmax[i]);
+        b += f.pcnt[i];
+        c += f.pins[i];
+    }
+    s_sum[threadIdx.x] = a;
+    s_max[threadIdx.x] = m;
+    s_cnt[threadIdx.x] = b;
+    s_ins[threadIdx.x] = c;
+    __syncthreads();
+    for (unsigned s = 128; s >= 1; s >>= 1) {
+        if (threadIdx.x < s) {
+            s_sum[threadIdx.x] = s_sum[threadIdx.x] + s_sum[threadIdx.x + s];
+            s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + s]);
+            s_cnt[threadIdx.x] = s_cnt[threadIdx.x] + s_cnt[threadIdx.x + s];
+            s_ins[threadIdx.x] = s_ins[threadIdx.x] + s_ins[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        rec[0] = s_sum[0];
+        rec[1] = s_max[0];
+        reinterpret_cast<unsigned long long *>(rec)[2] = s_cnt[0];
+        reinterpret_cast<unsigned long long *>(rec)[3] = s_ins[0];
+    }
+}
+
+// dst = src * s per element (the exponential's w_0 = v * 2^-K); dst may be src
+__global__ __launch_bounds__(256) void k_field_scale(float *dst, const float *src, size_t n, float s)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        dst[i] = src[i] * s;
+}
+
 } // namespace
 
 extern "C" {
@@ -977,6 +1158,68 @@ int sift3d_hip_jacobian_det(const float *d_field, int ox, int oy, int oz, float 
     hipLaunchKernelGGL(k_jacobian_det, dim3(grid), dim3(256), 0, st, p);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_jacobian_finish, dim3(1), dim3(64), 0, st, p);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+// Launchers for sift3d_field_ops.c, which has checked every argument (not exported from the library).
+int sift3d_field_compose_launch(const float *d_u, int ux, int uy, int uz, const float *d_v, int ox, int oy, int oz,
+                                float *d_out, int mode, void *d_stats, void *d_work, void *stream)
+{
+    static const char fn[] = "sift3d_hip_field_compose";
+    ComposeArgs f;
+    WarpArgs &p = f.w;
+    for (int i = 0; i < 12; i++)
+        p.a[i] = 0.0;
+    p.src = d_u;
+    p.dst = d_out;
+    p.nx = ux; p.ny = uy; p.nz = uz;
+    p.ox = ox; p.oy = oy; p.oz = oz;
+    p.tiles_x = (ox + TX - 1) / TX;
+    p.tiles_y = (oy + TY - 1) / TY;
+    {
+        const unsigned long long nt = (unsigned long long)p.tiles_x * p.tiles_y * ((oz + TZ - 1) / TZ);
+        if (nt > 0xffffffffull - MAX_GRID)
+            return field_fail(fn, "output grid too large");
+        p.ntiles = (unsigned)nt;
+    }
+    p.fill = 0.0f;
+    p.vec = (ox % 4 == 0) && !((uintptr_t)d_out & 15);
+    f.v = d_v;
+    f.psum = (double *)d_work;
+    f.pmax = f.psum + CMP_GRID;
+    f.pcnt = (unsigned long long *)(f.pmax + CMP_GRID);
+    f.pins = f.pcnt + CMP_GRID;
+    // with statistics a fixed grid of partial slots; without, k_warp_field's grid (one tile per workgroup up to
+    // MAX_GRID): a persistent grid of CMP_GRID workgroups is not resident at once and ends in a tail of its own
+    const bool stats = d_stats != nullptr;
+    const unsigned cap = stats ? CMP_GRID : MAX_GRID;
+    const unsigned grid = p.ntiles < cap ? p.ntiles : cap;
+    void (*k)(const ComposeArgs);
+    if (mode == SIFT3D_AMD_FIELD_COMPOSE)
+        k = ux >= 2 ? (stats ? k_field_compose<SIFT3D_AMD_FIELD_COMPOSE, 2, true> : k_field_compose<SIFT3D_AMD_FIELD_COMPOSE, 2, false>)
+                    : (stats ? k_field_compose<SIFT3D_AMD_FIELD_COMPOSE, 1, true> : k_field_compose<SIFT3D_AMD_FIELD_COMPOSE, 1, false>);
+    else
+        k = ux >= 2 ? (stats ? k_field_compose<SIFT3D_AMD_FIELD_INVERT, 2, true> : k_field_compose<SIFT3D_AMD_FIELD_INVERT, 2, false>)
+                    : (stats ? k_field_compose<SIFT3D_AMD_FIELD_INVERT, 1, true> : k_field_compose<SIFT3D_AMD_FIELD_INVERT, 1, false>);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, f);
+    LAUNCH_CHECK();
+    if (stats) {
+        hipLaunchKernelGGL(k_compose_finish, dim3(1), dim3(256), 0, st, f, grid, (double *)d_stats);
+        LAUNCH_CHECK();
+    }
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_field_scale_launch(float *d_dst, const float *d_src, size_t n, float s, void *stream)
+{
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 8192)
+        blocks = 8192;
+    if (blocks < 1)
+        blocks = 1;
+    hipLaunchKernelGGL(k_field_scale, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_dst, d_src, n, s);
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;
 }

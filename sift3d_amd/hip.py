@@ -121,6 +121,17 @@ def lib():
         "sift3d_amd_demons_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "sift3d_amd_demons_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                                vp, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp]),
+        "sift3d_hip_field_compose": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                               C.c_int, vp, vp, vp]),
+        "sift3d_amd_field_exp_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_field_exp_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_amd_field_invert_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_field_invert_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, vp, vp, vp]),
+        "sift3d_amd_demons_work_floats_ex": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_demons_device_ex": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                  C.c_int, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -514,28 +525,139 @@ def demons_force(F, W, field, step, alpha, moving_shape=None, stats=None, work=N
     return stats
 
 
-def demons(F, M, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None):
-    """`iterations` demons iterations (sift3d_amd_demons_device): the field [3, nz, ny, nx] is refined in place so
-    that the moving features M ([mz, my, mx] or [nc, mz, my, mx]) warped through it approach the fixed features F
-    ([nz, ny, nx] / [nc, nz, ny, nx]).  torch CUDA float32, on torch's current stream, no host synchronisation.
-    Returns the stats tensor (16 bytes per iteration; read it with demons_stats)."""
+DEMONS_UPDATE = {"additive": 0, "diffeomorphic": 1}
+
+
+def demons(F, M, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None, update="additive",
+           squarings=0):
+    """`iterations` demons iterations (sift3d_amd_demons_device, or sift3d_amd_demons_device_ex for
+    update="diffeomorphic"): the field [3, nz, ny, nx] is refined in place so that the moving features M
+    ([mz, my, mx] or [nc, mz, my, mx]) warped through it approach the fixed features F ([nz, ny, nx] /
+    [nc, nz, ny, nx]).  update "additive": u += delta; "diffeomorphic": u <- u o exp(delta) with `squarings`
+    squarings.  torch CUDA float32, on torch's current stream, no host synchronisation.  Returns the stats tensor
+    (16 bytes per iteration; read it with demons_stats)."""
     import torch
     nc, (nx, ny, nz), (mx, my, mz) = _demons_images(F, M, field, "demons")
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError("demons: iterations must not be negative")
-    need = lib().sift3d_amd_demons_work_floats(nx, ny, nz, nc)
+    if update not in DEMONS_UPDATE:
+        raise ValueError("demons: update must be 'additive' or 'diffeomorphic', not %r" % (update,))
+    need = lib().sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, DEMONS_UPDATE[update])
     if work is None:
         work = torch.empty((need + 1) // 2, dtype=torch.float64, device=F.device)
     if not (isinstance(work, torch.Tensor) and work.is_cuda and work.is_contiguous()
             and work.numel() * work.element_size() >= 4 * need and work.device == F.device):
         raise ValueError("demons: work must be a contiguous CUDA tensor of >= %d bytes on the device of F" % (4 * need))
     stats = torch.empty(max(iterations, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
-    _check(lib().sift3d_amd_demons_device(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc, field.data_ptr(),
-                                          iterations, float(alpha), float(sigma_fluid), float(sigma_diffusion),
-                                          work.data_ptr(), stats.data_ptr(), current_stream()),
-           "sift3d_amd_demons_device")
+    if update == "additive":
+        _check(lib().sift3d_amd_demons_device(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc,
+                                              field.data_ptr(), iterations, float(alpha), float(sigma_fluid),
+                                              float(sigma_diffusion), work.data_ptr(), stats.data_ptr(),
+                                              current_stream()), "sift3d_amd_demons_device")
+    else:
+        _check(lib().sift3d_amd_demons_device_ex(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc,
+                                                 field.data_ptr(), iterations, float(alpha), float(sigma_fluid),
+                                                 float(sigma_diffusion), DEMONS_UPDATE[update], int(squarings),
+                                                 work.data_ptr(), stats.data_ptr(), current_stream()),
+               "sift3d_amd_demons_device_ex")
     return stats[:iterations * DEMONS_STATS_BYTES // 8]
+
+
+FIELD_STATS_BYTES = 32
+FIELD_WORK_BYTES = 65536
+FIELD_MAX_SQUARINGS = 20
+FIELD_MODE = {"compose": 0, "invert": 1}
+
+
+def field_stats(stats):
+    """(sum, max float64 arrays, count, inside uint64 arrays) of field composition statistics (a CUDA tensor of
+    32-byte records); waits for the stream that wrote them"""
+    import torch
+    raw = stats.view(torch.uint8).cpu().numpy().reshape(-1, FIELD_STATS_BYTES)
+    f = raw[:, :16].copy().view(np.float64)
+    c = raw[:, 16:].copy().view(np.uint64)
+    return f[:, 0], f[:, 1], c[:, 0], c[:, 1]
+
+
+def _same_device(what, *ts):
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError("%s: the tensors are not on one device" % what)
+
+
+def field_compose(u, v, out=None, mode="compose", stats=None, work=None):
+    """One composition sample pass (sift3d_hip_field_compose; contract in include/sift3d_amd.h, "Field
+    composition, exponential and inverse"): u [3, uz, uy, ux], v and out [3, oz, oy, ox] torch CUDA float32 on
+    torch's current stream.  mode "compose": out = v + u(p + v) (u extended by its edge values outside its grid);
+    "invert": out = -u(p + v).  out None: statistics only.  stats: a CUDA tensor of >= 32 bytes for the residual
+    statistics, True to allocate one, or None for none.  Returns the stats tensor (read it with field_stats) or
+    None."""
+    import torch
+    _field_tensor(u, "field_compose", "u")
+    _field_tensor(v, "field_compose", "v")
+    if mode not in FIELD_MODE:
+        raise ValueError("field_compose: mode must be 'compose' or 'invert', not %r" % (mode,))
+    if out is not None:
+        _field_tensor(out, "field_compose", "out")
+        if out.shape != v.shape:
+            raise ValueError("field_compose: out %s is not shaped like v %s" % (tuple(out.shape), tuple(v.shape)))
+        _same_device("field_compose", u, v, out)
+    _same_device("field_compose", u, v)
+    if stats is True:
+        stats = torch.empty(FIELD_STATS_BYTES // 8, dtype=torch.int64, device=v.device)
+    if stats is not None and work is None:
+        work = torch.empty(FIELD_WORK_BYTES // 8, dtype=torch.int64, device=v.device)
+    if stats is None and out is None:
+        raise ValueError("field_compose: neither out nor stats")
+    _, uz, uy, ux = u.shape
+    _, oz, oy, ox = v.shape
+    _check(lib().sift3d_hip_field_compose(u.data_ptr(), ux, uy, uz, v.data_ptr(), ox, oy, oz,
+                                          None if out is None else out.data_ptr(), FIELD_MODE[mode],
+                                          None if stats is None else stats.data_ptr(),
+                                          None if work is None else work.data_ptr(), current_stream()),
+           "sift3d_hip_field_compose")
+    return stats
+
+
+def field_exp(v, out, squarings, work=None):
+    """out = exp(v) by scaling and squaring (sift3d_amd_field_exp_device): v, out [3, oz, oy, ox] torch CUDA
+    float32, on torch's current stream."""
+    import torch
+    _field_tensor(v, "field_exp", "v")
+    _field_tensor(out, "field_exp", "out")
+    if out.shape != v.shape:
+        raise ValueError("field_exp: out %s is not shaped like v %s" % (tuple(out.shape), tuple(v.shape)))
+    _same_device("field_exp", v, out)
+    _, oz, oy, ox = v.shape
+    need = lib().sift3d_amd_field_exp_work_floats(ox, oy, oz)
+    if work is None:
+        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=v.device)
+    _check(lib().sift3d_amd_field_exp_device(v.data_ptr(), ox, oy, oz, int(squarings), out.data_ptr(),
+                                             work.data_ptr(), current_stream()), "sift3d_amd_field_exp_device")
+    return out
+
+
+def field_invert(u, w, iterations, work=None):
+    """`iterations` fixed-point steps w <- -u(p + w) (sift3d_amd_field_invert_device): u [3, uz, uy, ux], w
+    [3, oz, oy, ox] (the initial iterate in, the result out) torch CUDA float32, on torch's current stream.  Returns
+    the stats tensor: iterations + 1 records of 32 bytes (read them with field_stats)."""
+    import torch
+    _field_tensor(u, "field_invert", "u")
+    _field_tensor(w, "field_invert", "w")
+    _same_device("field_invert", u, w)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError("field_invert: iterations must not be negative")
+    _, uz, uy, ux = u.shape
+    _, oz, oy, ox = w.shape
+    need = lib().sift3d_amd_field_invert_work_floats(ox, oy, oz)
+    if work is None:
+        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=w.device)
+    stats = torch.empty((iterations + 1) * FIELD_STATS_BYTES // 8, dtype=torch.int64, device=w.device)
+    _check(lib().sift3d_amd_field_invert_device(u.data_ptr(), ux, uy, uz, w.data_ptr(), ox, oy, oz, iterations,
+                                                work.data_ptr(), stats.data_ptr(), current_stream()),
+           "sift3d_amd_field_invert_device")
+    return stats
 
 
 def absmax(src, out):
