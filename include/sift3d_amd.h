@@ -611,6 +611,82 @@ sift3d_amd_demons_device_ex(const float *d_F, int nx, int ny, int nz, const floa
                             void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Multi-resolution demons                                                  */
+/* ------------------------------------------------------------------------ */
+/* Demons is local: one iteration moves the field by at most 1 / (2 alpha) voxel and finds only motion within about
+ * a feature's width.  The pyramid solves on grids halved `levels - 1` times first, where a voxel's step is 2, 4, ...
+ * fine voxels and an iteration costs 1/8, 1/64, ... of a fine one.
+ * Grids (the detector's im_downsample_2x convention): coarse voxel i sits at fine voxel 2 i on every axis; a fine
+ * axis of n voxels has c = (n + 1) / 2 (integer division) coarse ones, so an axis of 1 stays 1.  Displacements are in
+ * voxels of the grid they index: a field's values halve going down and double going up.  Float arithmetic, unfused.
+ *
+ * Restriction (sift3d_hip_restrict2): src [nc][nz][ny][nx] -> dst [nc][cz][cy][cx], per channel the separable
+ * binomial (1/4, 1/2, 1/4) on the taps 2 i - 1, 2 i, 2 i + 1, indices clamped onto the grid (edge replication):
+ *   R_x(a)(i) = (0.25f * a[max(2 i - 1, 0)] + 0.5f * a[2 i]) + 0.25f * a[min(2 i + 1, n - 1)]
+ * along x, then the same along y on the result, then along z, then dst = that * scale (float multiply, applied
+ * last; 1.0f for an image, 0.5f for a field going down).  The weights are powers of two: only the adds round.
+ * Consequences: a constant stays that constant; a function linear in the voxel index is sampled at 2 i exactly away
+ * from the clamped faces; NaN and inf propagate as IEEE arithmetic has them (0.25f * inf + 0.5f * -inf is NaN).
+ *
+ * Field prolongation (sift3d_hip_field_prolong2): coarse [3][cz][cy][cx] -> fine [3][nz][ny][nx],
+ * u_fine(p) = 2 L(u_coarse)(p / 2), L the linear interpolation, clamped at the high face where p / 2 passes the
+ * last coarse voxel (even n).  p / 2 is an integer or a half, so per axis, for fine index p with i0 = p / 2 (integer
+ * division) and i1 = min(i0 + (p & 1), c - 1):
+ *   P_x(a)(p) = 0.5f * (a[i0] + a[i1])            (for even or clamped p this is 0.5f * (a + a))
+ * along x, then the same along y on the result, then along z, then fine = 2.0f * that.  Consequences: a constant
+ * field c becomes 2 c; the fine field at the even voxels, halved, is the coarse field bit for bit (barring
+ * overflow); the field of an affine map on the coarse grid becomes the field of that map seen from the fine grid,
+ * exactly when its values are dyadic.
+ *
+ * Pyramid (sift3d_amd_demons_multires_device): level 0 is the finest.  The caller passes, per level, the fixed and
+ * moving feature stacks F_l [nc][nz_l][ny_l][nx_l], M_l [nc][mz_l][my_l][mx_l] and the iterations N_l; every
+ * dimension of level l >= 1, fixed and moving, must be the half (n + 1) / 2 of level l - 1's.  How the stacks are made
+ * is the caller's choice (restrict2 of level l - 1's, or features computed on the restricted volumes).
+ *   1. u_0 = d_u; for l = 1 .. levels-1: u_l = restrict2(u_{l-1}, nc = 3, scale 0.5f).
+ *   2. for l = levels-1 .. 0: N_l iterations of sift3d_amd_demons_device_ex on (F_l, M_l, u_l) with alpha, the sigmas
+ *      (in level-l voxels), update and squarings as given; then, when l > 0, u_{l-1} = field_prolong2(u_l), which
+ *      replaces u_{l-1}.
+ * d_u receives u_0.  levels == 1 is sift3d_amd_demons_device_ex bit for bit.  With levels > 1 the start field only
+ * enters through its restriction, a low-pass: what the binomial removes from it is lost (a spline's field is
+ * smooth and loses little; a caller who wants the start field kept exactly passes levels = 1).
+ * Statistics: one record of SIFT3D_AMD_DEMONS_STATS_BYTES per iteration in the order run, coarsest level first
+ * (N_{levels-1} records, then N_{levels-2}, ...): sum_l N_l records (room for one when the sum is 0).
+ * d_work holds sift3d_amd_demons_multires_work_floats floats: the finest level's demons scratch
+ * (sift3d_amd_demons_work_floats_ex, which every level uses in turn) and the fields u_1 .. u_{levels-1}, each
+ * rounded up to a multiple of 4 floats: about 3 n (1/8 + 1/64 + ...) more.
+ *
+ * All entries are asynchronous on `stream`, allocate nothing, do not synchronise with the host, use 64-bit offsets
+ * and check their arguments before any device call: -1 on NULL pointers (a level's included), dims <= 0, nc < 1, a
+ * scale that is not finite, levels outside [1, SIFT3D_AMD_DEMONS_MAX_LEVELS], dimensions that are not the halving
+ * chain, a negative iteration count, the refusals of sift3d_amd_demons_device_ex for alpha, the sigmas, update and
+ * squarings, misalignment (d_stats and d_work 8 B, the rest 4 B), an output that overlaps an input, the work buffer
+ * or another output.  The transfers use 16-byte accesses on the fine side when nx % 4 == 0 and the buffers are
+ * 16-byte (fine) and 8-byte (restrict2's dst) aligned; the result does not depend on it. */
+#define SIFT3D_AMD_DEMONS_MAX_LEVELS 6
+typedef struct {
+    const float *d_F;          /* fixed features  [nc][nz][ny][nx] */
+    int nx, ny, nz;
+    const float *d_M;          /* moving features [nc][mz][my][mx] */
+    int mx, my, mz;
+    int iterations;            /* of this level, >= 0 */
+} sift3d_amd_demons_level;
+/* d_src [nc][nz][ny][nx] -> d_dst [nc][(nz+1)/2][(ny+1)/2][(nx+1)/2] */
+SIFT3D_AMD_API int
+sift3d_hip_restrict2(const float *d_src, int nx, int ny, int nz, int nc, float *d_dst, float scale, void *stream);
+/* d_coarse [3][(nz+1)/2][(ny+1)/2][(nx+1)/2] -> d_fine [3][nz][ny][nx]; (nx, ny, nz) is the fine grid */
+SIFT3D_AMD_API int
+sift3d_hip_field_prolong2(const float *d_coarse, float *d_fine, int nx, int ny, int nz, void *stream);
+/* device scratch of sift3d_amd_demons_multires_device, in floats, for a finest fixed grid (nx, ny, nz) (0 for bad
+ * arguments) */
+SIFT3D_AMD_API size_t
+sift3d_amd_demons_multires_work_floats(int nx, int ny, int nz, int nc, int update, int levels);
+/* level [levels] (host memory, level 0 the finest); d_u [3][nz_0][ny_0][nx_0] in / out */
+SIFT3D_AMD_API int
+sift3d_amd_demons_multires_device(const sift3d_amd_demons_level *level, int levels, int nc, float *d_u, double alpha,
+                                  double sigma_fluid, double sigma_diffusion, int update, int squarings,
+                                  float *d_work, void *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

@@ -850,6 +850,12 @@ def dense_orientations(volume, sigma=1.6, units=None):
 DemonsRefinement = collections.namedtuple("DemonsRefinement", "field warped msd jacobian")
 DenseRegistration = collections.namedtuple("DenseRegistration",
                                            "A tps inliers num_matches field warped msd jacobian")
+# what refine_field / register_dense return with levels > 1: msd holds every level's iterations in the order run
+# (the coarsest level first) and level_slices[l] is level l's slice of it (level 0 the finest)
+MultiresRefinement = collections.namedtuple("MultiresRefinement", "field warped msd jacobian level_slices")
+MultiresRegistration = collections.namedtuple("MultiresRegistration",
+                                              "A tps inliers num_matches field warped msd jacobian level_slices")
+DEMONS_MAX_LEVELS = 6
 
 # Defaults chosen by a sweep on a case the end-to-end test (tests/test_demons.py) does not use: synth_survey(160,
 # seed 5) under a 3-degree rotation plus eight Gaussian bumps of 4 voxels (sigma 22, seed 77), refining
@@ -892,7 +898,7 @@ def demons_squarings(alpha):
 
 def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA,
                  sigma_fluid=DEMONS_SIGMA_FLUID, sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors",
-                 sigma=1.6, update="additive", squarings=None):
+                 sigma=1.6, update="additive", squarings=None, levels=1, level_iterations=None):
     """Dense demons refinement (contract: include/sift3d_amd.h, "Dense demons refinement") of a displacement
     field [3, nz, ny, nx] on fixed's grid (a pull map fixed voxel -> moving voxel; None: start from zero) so that
     the moving features warped through it agree with the fixed ones at every voxel.  moving, fixed: torch CUDA
@@ -903,13 +909,35 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     the update is then u o delta, a composition with the step itself.  The caller's field is not modified.
     Returns DemonsRefinement(field, warped = moving through the field (linear, fill 0), msd [iterations] (the mean
     of s_d over the voxels that sample inside, per iteration, before its update; NaN when there is none),
-    jacobian = jacobian_determinant(field))."""
+    jacobian = jacobian_determinant(field)).
+    levels > 1: coarse to fine ("Multi-resolution demons").  Both volumes are restricted levels - 1 times
+    (restrict_volume); "intensity" uses the restricted volumes, "descriptors" the dense descriptor images of every
+    level's volumes with the same sigma in that level's voxels (the window doubles in fine voxels per level; a
+    restriction of the 12 channels would not be unit length).  The start field is restricted to the coarsest level
+    (a low-pass: pass levels=1 to keep it exactly), refined there for level_iterations[levels - 1] iterations, handed
+    up and refined again, down to level_iterations[0] on the full grid; level_iterations None: `iterations` at every
+    level.  Returns MultiresRefinement: as above, msd holding every level's iterations in the order run (the
+    coarsest first), and level_slices, where msd[level_slices[l]] is level l's part (level 0 the finest)."""
     import torch
     from . import hip
     _volume_tensor(moving, "refine_field", "moving")
     _volume_tensor(fixed, "refine_field", "fixed")
     if update not in DEMONS_UPDATES:
         raise ValueError("update must be 'additive' or 'diffeomorphic', not %r" % (update,))
+    levels = int(levels)
+    if not 1 <= levels <= DEMONS_MAX_LEVELS:
+        raise ValueError("levels must be in 1 .. %d, not %r" % (DEMONS_MAX_LEVELS, levels))
+    if level_iterations is not None:
+        level_iterations = [int(k) for k in level_iterations]
+        if len(level_iterations) != levels or any(k < 0 for k in level_iterations):
+            raise ValueError("level_iterations must hold one count >= 0 per level")
+    if features not in ("descriptors", "intensity"):
+        raise ValueError("features must be 'descriptors' or 'intensity', not %r" % (features,))
+    if levels > 1:
+        return _refine_field_multires(moving, fixed, field, iterations, alpha, sigma_fluid, sigma_diffusion,
+                                      features, sigma, update, squarings, levels, level_iterations)
+    if level_iterations is not None:
+        iterations = level_iterations[0]
     if features == "descriptors":
         F, M = dense_descriptors(fixed, sigma), dense_descriptors(moving, sigma)
     elif features == "intensity":
@@ -933,18 +961,82 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     return DemonsRefinement(u, warped, msd, jacobian_determinant(u))
 
 
+def _refine_field_multires(moving, fixed, field, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma,
+                           update, squarings, levels, level_iterations):
+    """refine_field with levels > 1 (arguments checked there)"""
+    import torch
+    from . import hip
+    its = [int(iterations)] * levels if level_iterations is None else level_iterations
+    fv, mv = [fixed], [moving]
+    for _ in range(1, levels):
+        fv.append(hip.restrict2(fv[-1]))
+        mv.append(hip.restrict2(mv[-1]))
+    if features == "descriptors":
+        Fs = [dense_descriptors(v, sigma) for v in fv]
+        Ms = [dense_descriptors(v, sigma) for v in mv]
+    else:
+        Fs, Ms = fv, mv
+    if field is None:
+        u = torch.zeros((3,) + tuple(fixed.shape), dtype=torch.float32, device=fixed.device)
+    else:
+        hip._field_tensor(field, "refine_field")
+        u = field.clone()
+    K = 0
+    if update != "additive":
+        K = demons_squarings(alpha) if squarings is None else int(squarings)
+    stats = hip.demons_multires(Fs, Ms, u, its, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
+    sums, counts = hip.demons_stats(stats)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        msd = np.where(counts > 0, sums / np.maximum(counts, 1).astype(np.float64), np.nan)
+    slices, at = [None] * levels, 0
+    for l in range(levels - 1, -1, -1):
+        slices[l] = slice(at, at + its[l])
+        at += its[l]
+    warped = warp_field(moving, u, "linear", 0.0)
+    return MultiresRefinement(u, warped, msd, jacobian_determinant(u), tuple(slices))
+
+
+def restrict_volume(volume, scale=1.0):
+    """The volume (or channel stack) on the grid half as fine ("Multi-resolution demons": coarse voxel i sits at
+    fine voxel 2 i, an axis of n has (n + 1) // 2): the separable binomial (1/4, 1/2, 1/4) with replicated edges,
+    which keeps constants and linear ramps.  volume: a torch CUDA float32 tensor [nz, ny, nx] or [nc, nz, ny, nx];
+    returns a new tensor on torch's current stream.  scale 0.5 restricts a displacement field [3, nz, ny, nx]."""
+    from . import hip
+    if not _torch_tensor(volume):
+        raise ValueError("restrict_volume: the volume must be a CUDA tensor")
+    return hip.restrict2(volume, None, scale)
+
+
+def prolong_field(field, out_shape):
+    """The displacement field [3, cz, cy, cx] carried to the grid out_shape = (nz, ny, nx) twice as fine (every c =
+    (n + 1) // 2): 2 x its linear interpolation at p / 2, so that the fine field describes the same map in fine
+    voxels.  torch CUDA float32; returns a new tensor on torch's current stream."""
+    import torch
+    from . import hip
+    _cuda_field(field, "prolong_field")
+    nz, ny, nx = (int(s) for s in out_shape)
+    if min(nz, ny, nx) < 1 or tuple(field.shape[1:]) != hip.half_shape((nz, ny, nx)):
+        raise ValueError("prolong_field: the field %s is not on the grid under %s" % (tuple(field.shape), (nz, ny, nx)))
+    fine = torch.empty((3, nz, ny, nx), dtype=torch.float32, device=field.device)
+    return hip.field_prolong2(field, fine)
+
+
 def register_dense(moving, fixed, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA, sigma_fluid=DEMONS_SIGMA_FLUID,
                    sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, update="additive",
-                   squarings=None, **deformable_kw):
-    """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field (update
-    and squarings as there).  Returns DenseRegistration(A, tps, inliers, num_matches (as register_deformable),
-    field, warped, msd, jacobian (as refine_field))."""
+                   squarings=None, levels=1, level_iterations=None, **deformable_kw):
+    """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field (update,
+    squarings, levels and level_iterations as there).  Returns DenseRegistration(A, tps, inliers, num_matches (as
+    register_deformable), field, warped, msd, jacobian (as refine_field)); with levels > 1 MultiresRegistration,
+    which adds refine_field's level_slices."""
     _volume_tensor(moving, "register_dense", "moving")
     _volume_tensor(fixed, "register_dense", "fixed")
     d = register_deformable(moving, fixed, **deformable_kw)
     u = displacement_field(d.tps, tuple(fixed.shape), fixed.device)
     r = refine_field(moving, fixed, u, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma, update,
-                     squarings)
+                     squarings, levels, level_iterations)
+    if int(levels) > 1:
+        return MultiresRegistration(d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped, r.msd, r.jacobian,
+                                    r.level_slices)
     return DenseRegistration(d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped, r.msd, r.jacobian)
 
 

@@ -2525,3 +2525,4 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 /* dense demons refinement of a displacement field */
 #include "sift3d_demons.c"
 #include "sift3d_field_ops.c"
+#include "sift3d_multires.c"

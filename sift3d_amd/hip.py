@@ -32,6 +32,11 @@ class Level(C.Structure):
                 ("uz", C.c_float), ("octave", C.c_int), ("sd", C.c_double)]
 
 
+class DemonsLevel(C.Structure):
+    _fields_ = [("d_F", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("d_M", C.c_void_p),
+                ("mx", C.c_int), ("my", C.c_int), ("mz", C.c_int), ("iterations", C.c_int)]
+
+
 CAND_DTYPE = np.dtype([("idx", "u4"), ("tag", "i4"), ("val", "f4")])
 KP_DTYPE = np.dtype([("R", "f4", (9,)), ("cx", "f4"), ("cy", "f4"), ("cz", "f4"),
                      ("level", "i4"), ("row1", "u4"), ("sd", "f8")], align=True)
@@ -132,6 +137,11 @@ def lib():
         "sift3d_amd_demons_device_ex": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                                   C.c_int, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                                   C.c_int, vp, vp, vp]),
+        "sift3d_hip_restrict2": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp]),
+        "sift3d_hip_field_prolong2": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "sift3d_amd_demons_multires_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_demons_multires_device": (C.c_int, [C.POINTER(DemonsLevel), C.c_int, C.c_int, vp, C.c_double,
+                                                        C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -658,6 +668,110 @@ def field_invert(u, w, iterations, work=None):
                                                 work.data_ptr(), stats.data_ptr(), current_stream()),
            "sift3d_amd_field_invert_device")
     return stats
+
+
+DEMONS_MAX_LEVELS = 6
+
+
+def half_shape(shape):
+    """the grid under (nz, ny, nx) in the pyramid: (n + 1) // 2 per axis"""
+    return tuple((int(n) + 1) // 2 for n in shape)
+
+
+def restrict2(src, dst=None, scale=1.0):
+    """dst = src halved on every axis by the separable binomial (1/4, 1/2, 1/4), times `scale`
+    (sift3d_hip_restrict2; contract in include/sift3d_amd.h, "Multi-resolution demons"): src [nz, ny, nx] or
+    [nc, nz, ny, nx], dst the same with every grid axis (n + 1) // 2 (None: allocated), torch CUDA float32
+    contiguous, on torch's current stream.  scale 0.5 restricts a displacement field."""
+    import torch
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32 and src.is_contiguous()
+            and src.dim() in (3, 4)):
+        raise ValueError("restrict2: src must be a contiguous float32 CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]")
+    want = tuple(src.shape[:-3]) + half_shape(src.shape[-3:])
+    if dst is None:
+        dst = torch.empty(want, dtype=torch.float32, device=src.device)
+    if not (isinstance(dst, torch.Tensor) and dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
+            and tuple(dst.shape) == want and dst.device == src.device):
+        raise ValueError("restrict2: dst must be a contiguous float32 CUDA tensor %s on the device of src" % (want,))
+    nc = src.shape[0] if src.dim() == 4 else 1
+    nz, ny, nx = src.shape[-3:]
+    _check(lib().sift3d_hip_restrict2(src.data_ptr(), nx, ny, nz, nc, dst.data_ptr(), float(scale),
+                                      current_stream()), "sift3d_hip_restrict2")
+    return dst
+
+
+def field_prolong2(coarse, fine):
+    """fine = the field `coarse` carried to the grid twice as fine: 2 x its linear interpolation at p / 2
+    (sift3d_hip_field_prolong2; contract in include/sift3d_amd.h, "Multi-resolution demons"): coarse
+    [3, cz, cy, cx], fine [3, nz, ny, nx] with c = (n + 1) // 2 on every axis, torch CUDA float32, on torch's
+    current stream."""
+    _field_tensor(coarse, "field_prolong2", "coarse")
+    _field_tensor(fine, "field_prolong2", "fine")
+    _same_device("field_prolong2", coarse, fine)
+    if tuple(coarse.shape[1:]) != half_shape(fine.shape[1:]):
+        raise ValueError("field_prolong2: coarse %s is not the grid under fine %s"
+                         % (tuple(coarse.shape), tuple(fine.shape)))
+    _, nz, ny, nx = fine.shape
+    _check(lib().sift3d_hip_field_prolong2(coarse.data_ptr(), fine.data_ptr(), nx, ny, nz, current_stream()),
+           "sift3d_hip_field_prolong2")
+    return fine
+
+
+def demons_multires(Fs, Ms, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None,
+                    update="additive", squarings=0):
+    """Coarse-to-fine demons (sift3d_amd_demons_multires_device; contract in include/sift3d_amd.h,
+    "Multi-resolution demons"): Fs, Ms are the fixed and moving feature stacks per level, level 0 the finest, every
+    level the half ((n + 1) // 2 per axis) of the one above; iterations one count per level; the field
+    [3, nz, ny, nx] on Fs[0]'s grid is restricted to the coarsest level, refined there and handed up, in place.
+    torch CUDA float32, on torch's current stream, no host synchronisation.  Returns the stats tensor: 16 bytes per
+    iteration in the order run, the coarsest level's first (read it with demons_stats)."""
+    import torch
+    levels = len(Fs)
+    if not (1 <= levels <= DEMONS_MAX_LEVELS) or len(Ms) != levels:
+        raise ValueError("demons_multires: 1 .. %d levels of fixed and as many of moving features" % DEMONS_MAX_LEVELS)
+    its = [int(k) for k in iterations]
+    if len(its) != levels or any(k < 0 for k in its):
+        raise ValueError("demons_multires: iterations must hold one count >= 0 per level")
+    if update not in DEMONS_UPDATE:
+        raise ValueError("demons_multires: update must be 'additive' or 'diffeomorphic', not %r" % (update,))
+    _field_tensor(field, "demons_multires")
+    tab = (DemonsLevel * levels)()
+    nc0 = None
+    for l, (F, M) in enumerate(zip(Fs, Ms)):
+        u_l = field if l == 0 else None
+        for t, name in ((F, "fixed"), (M, "moving")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                    and t.dim() in (3, 4) and t.device == field.device):
+                raise ValueError("demons_multires: level %d %s must be a contiguous float32 CUDA tensor "
+                                 "[nz, ny, nx] or [nc, nz, ny, nx] on the field's device" % (l, name))
+        nc = F.shape[0] if F.dim() == 4 else 1
+        if M.dim() != F.dim() or (M.shape[0] if M.dim() == 4 else 1) != nc or (nc0 is not None and nc != nc0):
+            raise ValueError("demons_multires: level %d differs in channels" % l)
+        nc0 = nc
+        if u_l is not None and tuple(u_l.shape[1:]) != tuple(F.shape[-3:]):
+            raise ValueError("demons_multires: the field %s is not on the finest fixed grid %s"
+                             % (tuple(field.shape), tuple(F.shape)))
+        if l > 0 and (tuple(F.shape[-3:]) != half_shape(Fs[l - 1].shape[-3:])
+                      or tuple(M.shape[-3:]) != half_shape(Ms[l - 1].shape[-3:])):
+            raise ValueError("demons_multires: level %d is not the half of level %d" % (l, l - 1))
+        nz, ny, nx = F.shape[-3:]
+        mz, my, mx = M.shape[-3:]
+        tab[l] = DemonsLevel(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, its[l])
+    _, nz, ny, nx = field.shape
+    need = lib().sift3d_amd_demons_multires_work_floats(nx, ny, nz, nc0, DEMONS_UPDATE[update], levels)
+    if work is None:
+        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=field.device)
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.is_contiguous()
+            and work.numel() * work.element_size() >= 4 * need and work.device == field.device):
+        raise ValueError("demons_multires: work must be a contiguous CUDA tensor of >= %d bytes on the field's device"
+                         % (4 * need))
+    total = sum(its)
+    stats = torch.empty(max(total, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
+    _check(lib().sift3d_amd_demons_multires_device(tab, levels, nc0, field.data_ptr(), float(alpha),
+                                                   float(sigma_fluid), float(sigma_diffusion), DEMONS_UPDATE[update],
+                                                   int(squarings), work.data_ptr(), stats.data_ptr(),
+                                                   current_stream()), "sift3d_amd_demons_multires_device")
+    return stats[:total * DEMONS_STATS_BYTES // 8]
 
 
 def absmax(src, out):
