@@ -574,7 +574,7 @@ sift3d_amd_demons_device(const float *d_F, int nx, int ny, int nz, const float *
  * refinement" bit for bit (sift3d_amd_demons_device is it); SIFT3D_AMD_DEMONS_DIFFEOMORPHIC replaces step 4 with
  *   4'. e = exp(delta) with `squarings` squarings, then u <- COMPOSE(u, e): u_new(p) = e(p) + u(p + e(p))
  * (Vercauteren et al., Diffeomorphic demons, NeuroImage 2009).  Steps 1-3 and 5 are unchanged.  d_work holds
- * sift3d_amd_demons_work_floats_ex floats: the additive driver's, plus 6 n for DIFFEOMORPHIC (u_new and the
+ * sift3d_amd_demons_work_floats_ex floats: sift3d_amd_demons_work_floats, plus 6 n for DIFFEOMORPHIC (u_new and the
  * exponential's second buffer).
  *
  * All entries are asynchronous on `stream`, allocate nothing, do not synchronise with the host, use 64-bit offsets

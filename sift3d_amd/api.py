@@ -577,10 +577,9 @@ def _matched_points(moving, fixed, nn_thresh, detector_kw, what):
     """Detect + describe both volumes (torch CUDA float32 tensors [nz, ny, nx]) and match the
     descriptors: (moving xyz, fixed xyz) of the matched pairs, in voxels."""
     import torch
+    from . import hip
     for name, v in (("moving", moving), ("fixed", fixed)):
-        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
-                and v.dim() == 3):
-            raise ValueError("%s: %s must be a contiguous 3-D float32 CUDA tensor" % (what, name))
+        hip._tensor(v, "%s: %s must be a contiguous 3-D float32 CUDA tensor" % (what, name), dims=(3,))
     if moving.device != fixed.device:
         raise ValueError("%s: moving and fixed are on different devices (%s, %s)"
                          % (what, moving.device, fixed.device))
@@ -875,10 +874,14 @@ DEMONS_SIGMA_DIFFUSION = 2.0
 
 
 def _volume_tensor(v, what, name):
-    import torch
-    if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
-            and v.dim() == 3):
-        raise ValueError("%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx]" % (what, name))
+    from . import hip
+    hip._tensor(v, "%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx]" % (what, name), dims=(3,))
+
+
+def _mean_or_nan(sums, counts):
+    """sums / counts per record, NaN where the count is 0"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(counts > 0, sums / np.maximum(counts, 1).astype(np.float64), np.nan)
 
 
 DEMONS_UPDATES = ("additive", "diffeomorphic")
@@ -933,39 +936,6 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
             raise ValueError("level_iterations must hold one count >= 0 per level")
     if features not in ("descriptors", "intensity"):
         raise ValueError("features must be 'descriptors' or 'intensity', not %r" % (features,))
-    if levels > 1:
-        return _refine_field_multires(moving, fixed, field, iterations, alpha, sigma_fluid, sigma_diffusion,
-                                      features, sigma, update, squarings, levels, level_iterations)
-    if level_iterations is not None:
-        iterations = level_iterations[0]
-    if features == "descriptors":
-        F, M = dense_descriptors(fixed, sigma), dense_descriptors(moving, sigma)
-    elif features == "intensity":
-        F, M = fixed, moving
-    else:
-        raise ValueError("features must be 'descriptors' or 'intensity', not %r" % (features,))
-    if field is None:
-        u = torch.zeros((3,) + tuple(fixed.shape), dtype=torch.float32, device=fixed.device)
-    else:
-        hip._field_tensor(field, "refine_field")
-        u = field.clone()
-    if update == "additive":
-        stats = hip.demons(F, M, u, iterations, alpha, sigma_fluid, sigma_diffusion)
-    else:
-        K = demons_squarings(alpha) if squarings is None else int(squarings)
-        stats = hip.demons(F, M, u, iterations, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
-    sums, counts = hip.demons_stats(stats)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        msd = np.where(counts > 0, sums / np.maximum(counts, 1).astype(np.float64), np.nan)
-    warped = warp_field(moving, u, "linear", 0.0)
-    return DemonsRefinement(u, warped, msd, jacobian_determinant(u))
-
-
-def _refine_field_multires(moving, fixed, field, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma,
-                           update, squarings, levels, level_iterations):
-    """refine_field with levels > 1 (arguments checked there)"""
-    import torch
-    from . import hip
     its = [int(iterations)] * levels if level_iterations is None else level_iterations
     fv, mv = [fixed], [moving]
     for _ in range(1, levels):
@@ -984,15 +954,18 @@ def _refine_field_multires(moving, fixed, field, iterations, alpha, sigma_fluid,
     K = 0
     if update != "additive":
         K = demons_squarings(alpha) if squarings is None else int(squarings)
-    stats = hip.demons_multires(Fs, Ms, u, its, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
-    sums, counts = hip.demons_stats(stats)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        msd = np.where(counts > 0, sums / np.maximum(counts, 1).astype(np.float64), np.nan)
+    if levels == 1:
+        stats = hip.demons(Fs[0], Ms[0], u, its[0], alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
+    else:
+        stats = hip.demons_multires(Fs, Ms, u, its, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
+    msd = _mean_or_nan(*hip.demons_stats(stats))
+    warped = warp_field(moving, u, "linear", 0.0)
+    if levels == 1:
+        return DemonsRefinement(u, warped, msd, jacobian_determinant(u))
     slices, at = [None] * levels, 0
     for l in range(levels - 1, -1, -1):
         slices[l] = slice(at, at + its[l])
         at += its[l]
-    warped = warp_field(moving, u, "linear", 0.0)
     return MultiresRefinement(u, warped, msd, jacobian_determinant(u), tuple(slices))
 
 
@@ -1013,7 +986,7 @@ def prolong_field(field, out_shape):
     voxels.  torch CUDA float32; returns a new tensor on torch's current stream."""
     import torch
     from . import hip
-    _cuda_field(field, "prolong_field")
+    hip._field_tensor(field, "prolong_field")
     nz, ny, nx = (int(s) for s in out_shape)
     if min(nz, ny, nx) < 1 or tuple(field.shape[1:]) != hip.half_shape((nz, ny, nx)):
         raise ValueError("prolong_field: the field %s is not on the grid under %s" % (tuple(field.shape), (nz, ny, nx)))
@@ -1049,21 +1022,14 @@ FieldInverse = collections.namedtuple("FieldInverse", "field residual_max residu
 INVERT_ITERATIONS = 28
 
 
-def _cuda_field(t, what, name="field"):
-    from . import hip
-    if not _torch_tensor(t):
-        raise ValueError("%s: %s must be a CUDA tensor" % (what, name))
-    hip._field_tensor(t, what, name)
-
-
 def compose_fields(u, v):
     """w = u o v on v's grid: w(p) = v(p) + u(p + v(p)), read through v, then through u (u is extended by its
     edge values outside its grid).  u [3, uz, uy, ux] and v [3, oz, oy, ox]: torch CUDA float32 pull maps, v's
     values in u-grid voxels.  One kernel on torch's current stream; returns a new tensor shaped like v."""
     import torch
     from . import hip
-    _cuda_field(u, "compose_fields", "u")
-    _cuda_field(v, "compose_fields", "v")
+    hip._field_tensor(u, "compose_fields", "u")
+    hip._field_tensor(v, "compose_fields", "v")
     out = torch.empty_like(v)
     hip.field_compose(u, v, out, "compose")
     return out
@@ -1086,7 +1052,7 @@ def field_exp(v, squarings=None):
     in torch costs one host synchronisation.  Returns a new tensor on torch's current stream."""
     import torch
     from . import hip
-    _cuda_field(v, "field_exp", "v")
+    hip._field_tensor(v, "field_exp", "v")
     if squarings is None:
         squarings = field_squarings(float(torch.sqrt((v.double() ** 2).sum(0)).max()))
     out = torch.empty_like(v)
@@ -1102,17 +1068,15 @@ def invert_field(u, out_shape, iterations=INVERT_ITERATIONS, init=None):
     u's grid.  Reads the statistics, so it waits for torch's current stream."""
     import torch
     from . import hip
-    _cuda_field(u, "invert_field", "u")
+    hip._field_tensor(u, "invert_field", "u")
     oz, oy, ox = (int(s) for s in out_shape)
     if init is None:
         w = torch.zeros((3, oz, oy, ox), dtype=torch.float32, device=u.device)
     else:
-        _cuda_field(init, "invert_field", "init")
+        hip._field_tensor(init, "invert_field", "init")
         if tuple(init.shape) != (3, oz, oy, ox):
             raise ValueError("invert_field: init %s is not [3, %d, %d, %d]" % (tuple(init.shape), oz, oy, ox))
         w = init.clone()
     stats = hip.field_invert(u, w, iterations)
     s, mx, cnt, ins = hip.field_stats(stats)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        mean = np.where(cnt > 0, s / np.maximum(cnt, 1).astype(np.float64), np.nan)
-    return FieldInverse(w, mx, mean, ins.astype(np.int64))
+    return FieldInverse(w, mx, _mean_or_nan(s, cnt), ins.astype(np.int64))

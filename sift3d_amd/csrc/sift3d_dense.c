@@ -18,26 +18,14 @@ size_t sift3d_amd_dense_work_floats(int nx, int ny, int nz)
 static int dense_check(const char *what, int nx, int ny, int nz, const double *units3, double sigma)
 {
     int k;
-    if (nx <= 0 || ny <= 0 || nz <= 0) {
-        ERR("%s: dimensions must be positive \n", what);
+    if (check_dims(what, nx, ny, nz))
         return SIFT3D_FAILURE;
-    }
-    if (!isfinite(sigma) || !(sigma > 0)) {
-        ERR("%s: sigma must be positive and finite \n", what);
-        return SIFT3D_FAILURE;
-    }
+    if (!isfinite(sigma) || !(sigma > 0))
+        return refuse(what, "sigma must be positive and finite");
     for (k = 0; k < 3; k++)
-        if (!isfinite(units3[k]) || !(units3[k] > 0)) {
-            ERR("%s: units must be positive and finite \n", what);
-            return SIFT3D_FAILURE;
-        }
+        if (!isfinite(units3[k]) || !(units3[k] > 0))
+            return refuse(what, "units must be positive and finite");
     return SIFT3D_SUCCESS;
-}
-
-static int dense_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 int sift3d_amd_dense_descriptors_device(const float *d_src, int nx, int ny, int nz, const double *units3,
@@ -45,21 +33,17 @@ int sift3d_amd_dense_descriptors_device(const float *d_src, int nx, int ny, int 
 {
     static const char what[] = "sift3d_amd_dense_descriptors_device";
     const int dims[3] = { nx, ny, nz };
-    size_t n;
+    const size_t n = grid_voxels(nx, ny, nz);
+    const range_t out = { d_out, 12 * n * sizeof(float) };
     filter_t f;
     int c, rc = SIFT3D_FAILURE;
-    if (!d_src || !d_out || !d_work || !units3) {
-        ERR("%s: NULL argument \n", what);
-        return SIFT3D_FAILURE;
-    }
+    if (!d_src || !d_out || !d_work || !units3)
+        return refuse(what, "NULL argument");
     if (dense_check(what, nx, ny, nz, units3, sigma))
         return SIFT3D_FAILURE;
-    n = (size_t)nx * ny * nz;
-    if (dense_overlap(d_out, 12 * n * sizeof(float), d_src, n * sizeof(float)) ||
-        dense_overlap(d_out, 12 * n * sizeof(float), d_work, 2 * n * sizeof(float))) {
-        ERR("%s: the output overlaps the source or the work buffer \n", what);
-        return SIFT3D_FAILURE;
-    }
+    if (ranges_overlap(out, (range_t){ d_src, n * sizeof(float) }) ||
+        ranges_overlap(out, (range_t){ d_work, 2 * n * sizeof(float) }))
+        return refuse(what, "the output overlaps the source or the work buffer");
     if (sift3d_amd_init())        /* (the face tables; refuses without a device) */
         return SIFT3D_FAILURE;
     if (gauss_filter(&f, sigma))
@@ -86,14 +70,10 @@ int sift3d_amd_image_dense_descriptors(const sift3d_image *im, double sigma, flo
     double units[3];
     size_t n;
     int rc = SIFT3D_FAILURE;
-    if (!im || !out || !im->data) {
-        ERR("%s: NULL argument \n", what);
-        return SIFT3D_FAILURE;
-    }
-    if (im->nc != 1) {
-        ERR("%s: only single-channel images are supported \n", what);
-        return SIFT3D_FAILURE;
-    }
+    if (!im || !out || !im->data)
+        return refuse(what, "NULL argument");
+    if (im->nc != 1)
+        return refuse(what, "only single-channel images are supported");
     units[0] = im->ux; units[1] = im->uy; units[2] = im->uz;
     if (dense_check(what, im->nx, im->ny, im->nz, units, sigma))
         return SIFT3D_FAILURE;
@@ -128,20 +108,15 @@ int sift3d_amd_dense_descriptors_rotate_device(const float *d_src, int nx, int n
                                                double sigma, float *d_out, float *d_work, void *stream)
 {
     static const char what[] = "sift3d_amd_dense_descriptors_rotate_device";
-    size_t n;
-    if (!d_src || !d_out || !d_work || !units3) {
-        ERR("%s: NULL argument \n", what);
-        return SIFT3D_FAILURE;
-    }
+    const size_t n = grid_voxels(nx, ny, nz);
+    const range_t in = { d_src, n * sizeof(float) };
+    const range_t out[] = { { d_out, 12 * n * sizeof(float) }, { d_work, 9 * n * sizeof(float) } };
+    if (!d_src || !d_out || !d_work || !units3)
+        return refuse(what, "NULL argument");
     if (dense_check(what, nx, ny, nz, units3, sigma))
         return SIFT3D_FAILURE;
-    n = (size_t)nx * ny * nz;
-    if (dense_overlap(d_out, 12 * n * sizeof(float), d_src, n * sizeof(float)) ||
-        dense_overlap(d_out, 12 * n * sizeof(float), d_work, 9 * n * sizeof(float)) ||
-        dense_overlap(d_work, 9 * n * sizeof(float), d_src, n * sizeof(float))) {
-        ERR("%s: the output or the work buffer overlaps another buffer \n", what);
-        return SIFT3D_FAILURE;
-    }
+    if (ranges_aliased(out, 2, &in, 1))
+        return refuse(what, "the output or the work buffer overlaps another buffer");
     if (sift3d_amd_init())        /* (the face tables; refuses without a device) */
         return SIFT3D_FAILURE;
     if (sift3d_hip_dense_orient(d_src, nx, ny, nz, units3[0], units3[1], units3[2], sigma, d_work, NULL, stream) ||
@@ -159,14 +134,10 @@ int sift3d_amd_image_dense_descriptors_rotate(const sift3d_image *im, double sig
     double units[3];
     size_t n;
     int rc = SIFT3D_FAILURE;
-    if (!im || !out || !im->data) {
-        ERR("%s: NULL argument \n", what);
-        return SIFT3D_FAILURE;
-    }
-    if (im->nc != 1) {
-        ERR("%s: only single-channel images are supported \n", what);
-        return SIFT3D_FAILURE;
-    }
+    if (!im || !out || !im->data)
+        return refuse(what, "NULL argument");
+    if (im->nc != 1)
+        return refuse(what, "only single-channel images are supported");
     units[0] = im->ux; units[1] = im->uy; units[2] = im->uz;
     if (dense_check(what, im->nx, im->ny, im->nz, units, sigma))
         return SIFT3D_FAILURE;

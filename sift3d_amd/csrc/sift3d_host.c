@@ -2513,6 +2513,9 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 /* descriptor matching + RANSAC affine (BASELINE config 5) */
 #include "sift3d_register.c"
 
+/* the argument checks that the files below share */
+#include "sift3d_checks.c"
+
 /* affine resampling of host images, inversion of affine maps */
 #include "sift3d_warp.c"
 
@@ -2522,7 +2525,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 /* thin-plate spline: fit, evaluation, device layout, warp of host images */
 #include "sift3d_tps.c"
 
-/* dense demons refinement of a displacement field */
-#include "sift3d_demons.c"
+/* field composition, exponential and inverse; dense demons refinement of a displacement field */
 #include "sift3d_field_ops.c"
-#include "sift3d_multires.c"
+#include "sift3d_demons.c"

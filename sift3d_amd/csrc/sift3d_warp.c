@@ -64,10 +64,9 @@ int sift3d_amd_image_warp_affine(const sift3d_image *src, const double *A, int i
         ERR("sift3d_amd_image_warp_affine: only single-channel images are supported \n");
         return SIFT3D_FAILURE;
     }
-    if (src->nx <= 0 || src->ny <= 0 || src->nz <= 0 || dst->nx <= 0 || dst->ny <= 0 || dst->nz <= 0) {
-        ERR("sift3d_amd_image_warp_affine: dimensions must be positive \n");
+    if (check_dims("sift3d_amd_image_warp_affine", src->nx, src->ny, src->nz) ||
+        check_dims("sift3d_amd_image_warp_affine", dst->nx, dst->ny, dst->nz))
         return SIFT3D_FAILURE;
-    }
     if (interp != SIFT3D_AMD_INTERP_NEAREST && interp != SIFT3D_AMD_INTERP_LINEAR) {
         ERR("sift3d_amd_image_warp_affine: unknown interpolation mode %d \n", interp);
         return SIFT3D_FAILURE;
@@ -96,11 +95,6 @@ int sift3d_amd_image_warp_affine(const sift3d_image *src, const double *A, int i
 }
 
 /* ---- displacement fields: blocking host forms of sift3d_hip_warp_field / sift3d_hip_jacobian_det ---- */
-static int host_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
 
 int sift3d_amd_image_warp_field(const sift3d_image *src, const float *field, int interp, float fill,
                                 sift3d_image *dst)
@@ -116,17 +110,17 @@ int sift3d_amd_image_warp_field(const sift3d_image *src, const float *field, int
         ERR("sift3d_amd_image_warp_field: only single-channel images are supported \n");
         return SIFT3D_FAILURE;
     }
-    if (src->nx <= 0 || src->ny <= 0 || src->nz <= 0 || dst->nx <= 0 || dst->ny <= 0 || dst->nz <= 0) {
-        ERR("sift3d_amd_image_warp_field: dimensions must be positive \n");
+    if (check_dims("sift3d_amd_image_warp_field", src->nx, src->ny, src->nz) ||
+        check_dims("sift3d_amd_image_warp_field", dst->nx, dst->ny, dst->nz))
         return SIFT3D_FAILURE;
-    }
     if (interp != SIFT3D_AMD_INTERP_NEAREST && interp != SIFT3D_AMD_INTERP_LINEAR) {
         ERR("sift3d_amd_image_warp_field: unknown interpolation mode %d \n", interp);
         return SIFT3D_FAILURE;
     }
     ns = sizeof(float) * (size_t)src->nx * src->ny * src->nz;
     nd = sizeof(float) * (size_t)dst->nx * dst->ny * dst->nz;
-    if (host_overlap(dst->data, nd, src->data, ns) || host_overlap(dst->data, nd, field, 3 * nd)) {
+    if (ranges_overlap((range_t){ dst->data, nd }, (range_t){ src->data, ns }) ||
+        ranges_overlap((range_t){ dst->data, nd }, (range_t){ field, 3 * nd })) {
         ERR("sift3d_amd_image_warp_field: the destination overlaps the source or the field \n");
         return SIFT3D_FAILURE;
     }
@@ -160,12 +154,10 @@ int sift3d_amd_jacobian_det(const float *field, int ox, int oy, int oz, float *d
         ERR("sift3d_amd_jacobian_det: NULL argument \n");
         return SIFT3D_FAILURE;
     }
-    if (ox <= 0 || oy <= 0 || oz <= 0) {
-        ERR("sift3d_amd_jacobian_det: dimensions must be positive \n");
+    if (check_dims("sift3d_amd_jacobian_det", ox, oy, oz))
         return SIFT3D_FAILURE;
-    }
     nd = sizeof(float) * (size_t)ox * oy * oz;
-    if (det && host_overlap(det, nd, field, 3 * nd)) {
+    if (det && ranges_overlap((range_t){ det, nd }, (range_t){ field, 3 * nd })) {
         ERR("sift3d_amd_jacobian_det: det overlaps the field \n");
         return SIFT3D_FAILURE;
     }

@@ -220,24 +220,63 @@ def nn2(a, b):
 INTERP = {"nearest": 0, "linear": 1}
 
 
+def _interp(interp):
+    if interp not in INTERP:
+        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    return INTERP[interp]
+
+
+def _tensor(t, msg, dims=None, lead=None, shape=None, device=None, dtype="float32"):
+    """The one tensor check: t must be a contiguous CUDA tensor of `dtype` (None: any) and, where given, of a rank
+    in `dims`, with `lead` channels first, of exactly `shape`, on `device`; ValueError(msg) otherwise."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and (dtype is None or t.dtype == getattr(torch, dtype))
+            and t.is_contiguous() and (dims is None or t.dim() in dims)
+            and (lead is None or (t.dim() >= 1 and t.shape[0] == lead))
+            and (shape is None or tuple(t.shape) == tuple(shape)) and (device is None or t.device == device)):
+        raise ValueError(msg)
+
+
+def _field_tensor(t, what, name="field"):
+    _tensor(t, "%s: %s must be a contiguous float32 CUDA tensor [3, oz, oy, ox]" % (what, name), dims=(4,), lead=3)
+
+
+def _same_device(what, *ts):
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError("%s: the tensors are not on one device" % what)
+
+
+def _work(work, need, like, what, dtype=None):
+    """The work buffer of a driver: `need` floats allocated on the device of `like` when work is None, else the
+    caller's, which must be a contiguous CUDA tensor (of `dtype`, where given) of that many bytes on that device."""
+    import torch
+    if work is None:
+        return torch.empty(need, dtype=torch.float32, device=like.device)
+    _tensor(work, "%s: work must be a contiguous %sCUDA tensor of >= %d bytes on the device of the other tensors"
+            % (what, dtype + " " if dtype else "", 4 * need), device=like.device, dtype=dtype)
+    if work.numel() * work.element_size() < 4 * need:
+        raise ValueError("%s: work holds fewer than %d bytes" % (what, 4 * need))
+    return work
+
+
+def _warp_pair(src, dst, what):
+    for t in (src, dst):
+        _tensor(t, "%s: src and dst must be contiguous 3-D float32 CUDA tensors" % what, dims=(3,))
+    if src.device != dst.device:
+        raise ValueError("%s: src and dst are on different devices" % what)
+
+
 def warp_affine(src, dst, A, interp="linear", fill=0.0):
     """dst[z, y, x] = src sampled at A [x; y; z; 1] (A: 3 x 4 pull map in voxels; sift3d_hip_warp_affine)
     on torch CUDA float32 contiguous tensors [nz, ny, nx] / [oz, oy, ox], on torch's current stream;
     voxels that sample outside src get `fill`."""
-    import torch
-    for t in (src, dst):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                and t.dim() == 3):
-            raise ValueError("warp_affine: src and dst must be contiguous 3-D float32 CUDA tensors")
-    if src.device != dst.device:
-        raise ValueError("warp_affine: src and dst are on different devices")
-    if interp not in INTERP:
-        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    _warp_pair(src, dst, "warp_affine")
+    mode = _interp(interp)
     a = np.ascontiguousarray(A, np.float64).reshape(12)
     nz, ny, nx = src.shape
     oz, oy, ox = dst.shape
     _check(lib().sift3d_hip_warp_affine(src.data_ptr(), nx, ny, nz, dst.data_ptr(), ox, oy, oz,
-                                        a.ctypes.data_as(C.POINTER(C.c_double)), INTERP[interp],
+                                        a.ctypes.data_as(C.POINTER(C.c_double)), mode,
                                         float(fill), current_stream()), "sift3d_hip_warp_affine")
     return dst
 
@@ -249,14 +288,8 @@ def warp_tps(src, dst, tps, interp="linear", fill=0.0):
     sift3d_amd_tps_pack and uploaded; voxels that sample outside src get `fill`."""
     import torch
     from . import api
-    for t in (src, dst):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                and t.dim() == 3):
-            raise ValueError("warp_tps: src and dst must be contiguous 3-D float32 CUDA tensors")
-    if src.device != dst.device:
-        raise ValueError("warp_tps: src and dst are on different devices")
-    if interp not in INTERP:
-        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    _warp_pair(src, dst, "warp_tps")
+    mode = _interp(interp)
     a = np.ascontiguousarray(tps.A, np.float64).reshape(12)
     packed = api.tps_pack(tps.ctrl, tps.weights)
     d_tps = torch.from_numpy(packed).to(src.device)
@@ -264,7 +297,7 @@ def warp_tps(src, dst, tps, interp="linear", fill=0.0):
     oz, oy, ox = dst.shape
     _check(lib().sift3d_hip_warp_tps(src.data_ptr(), nx, ny, nz, dst.data_ptr(), ox, oy, oz,
                                      a.ctypes.data_as(C.POINTER(C.c_double)), d_tps.data_ptr(), len(packed),
-                                     INTERP[interp], float(fill), current_stream()), "sift3d_hip_warp_tps")
+                                     mode, float(fill), current_stream()), "sift3d_hip_warp_tps")
     return dst
 
 
@@ -272,13 +305,6 @@ def warp_tps_launches(out_shape, m):
     """How many launches sift3d_hip_warp_tps splits an output grid (oz, oy, ox) with m points into."""
     oz, oy, ox = out_shape
     return int(lib().sift3d_hip_warp_tps_launches(ox, oy, oz, m))
-
-
-def _field_tensor(t, what, name="field"):
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-            and t.dim() == 4 and t.shape[0] == 3):
-        raise ValueError("%s: %s must be a contiguous float32 CUDA tensor [3, oz, oy, ox]" % (what, name))
 
 
 def affine_field(field, A):
@@ -317,11 +343,8 @@ def warp_field(src, dst, field, interp="linear", fill=0.0):
     """dst = src sampled at p + field(p) (sift3d_hip_warp_field), torch CUDA float32 contiguous tensors:
     src [nz, ny, nx] / dst [oz, oy, ox], or src [nc, nz, ny, nx] / dst [nc, oz, oy, ox] (every channel at
     the same points); field [3, oz, oy, ox].  On torch's current stream; voxels that sample outside get `fill`."""
-    import torch
     for t in (src, dst):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                and t.dim() in (3, 4)):
-            raise ValueError("warp_field: src and dst must be contiguous 3-D or 4-D float32 CUDA tensors")
+        _tensor(t, "warp_field: src and dst must be contiguous 3-D or 4-D float32 CUDA tensors", dims=(3, 4))
     _field_tensor(field, "warp_field")
     if src.dim() != dst.dim() or (src.dim() == 4 and src.shape[0] != dst.shape[0]):
         raise ValueError("warp_field: src %s and dst %s differ in channels" % (tuple(src.shape), tuple(dst.shape)))
@@ -330,13 +353,12 @@ def warp_field(src, dst, field, interp="linear", fill=0.0):
                          % (tuple(dst.shape), tuple(field.shape[1:])))
     if not (src.device == dst.device == field.device):
         raise ValueError("warp_field: src, dst and field are not on one device")
-    if interp not in INTERP:
-        raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+    mode = _interp(interp)
     nc = src.shape[0] if src.dim() == 4 else 1
     nz, ny, nx = src.shape[-3:]
     oz, oy, ox = dst.shape[-3:]
     _check(lib().sift3d_hip_warp_field(src.data_ptr(), nx, ny, nz, nc, field.data_ptr(), ox, oy, oz, dst.data_ptr(),
-                                       INTERP[interp], float(fill), current_stream()), "sift3d_hip_warp_field")
+                                       mode, float(fill), current_stream()), "sift3d_hip_warp_field")
     return dst
 
 
@@ -350,11 +372,9 @@ def jacobian_det(field, det=None):
     import torch
     _field_tensor(field, "jacobian_det")
     _, oz, oy, ox = field.shape
-    if det is not None and not (isinstance(det, torch.Tensor) and det.is_cuda and det.dtype == torch.float32
-                                and det.is_contiguous() and tuple(det.shape) == (oz, oy, ox)
-                                and det.device == field.device):
-        raise ValueError("jacobian_det: det must be a contiguous float32 CUDA tensor [oz, oy, ox] on the field's "
-                         "device, or None")
+    if det is not None:
+        _tensor(det, "jacobian_det: det must be a contiguous float32 CUDA tensor [oz, oy, ox] on the field's "
+                "device, or None", shape=(oz, oy, ox), device=field.device)
     stats = torch.empty(JACOBIAN_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
     _check(lib().sift3d_hip_jacobian_det(field.data_ptr(), ox, oy, oz, None if det is None else det.data_ptr(),
                                          stats.data_ptr(), current_stream()), "sift3d_hip_jacobian_det")
@@ -365,12 +385,9 @@ def jacobian_det(field, det=None):
 
 
 def _dense_args(src, out, what):
-    import torch
     for t, dim in ((src, 3), (out, 4)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                and t.dim() == dim):
-            raise ValueError("%s: src must be a contiguous float32 CUDA tensor [nz, ny, nx] and out one of "
-                             "[12, nz, ny, nx]" % what)
+        _tensor(t, "%s: src must be a contiguous float32 CUDA tensor [nz, ny, nx] and out one of [12, nz, ny, nx]"
+                % what, dims=(dim,))
     if out.shape != (12,) + tuple(src.shape):
         raise ValueError("%s: out has shape %s, not [12, %d, %d, %d]" % ((what, tuple(out.shape)) + tuple(src.shape)))
     if src.device != out.device:
@@ -391,10 +408,7 @@ def dense_bin(src, out, units=(1, 1, 1)):
 def dense_normalize(hist):
     """Step 4 of the dense descriptor contract (sift3d_hip_dense_normalize), in place on a torch CUDA
     float32 tensor [12, ...] on torch's current stream."""
-    import torch
-    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.float32
-            and hist.is_contiguous() and hist.dim() >= 1 and hist.shape[0] == 12):
-        raise ValueError("dense_normalize: hist must be a contiguous float32 CUDA tensor [12, ...]")
+    _tensor(hist, "dense_normalize: hist must be a contiguous float32 CUDA tensor [12, ...]", lead=12)
     _check(lib().sift3d_hip_dense_normalize(hist.data_ptr(), hist.numel() // 12, current_stream()),
            "sift3d_hip_dense_normalize")
     return hist
@@ -404,15 +418,8 @@ def dense_descriptors(src, out, sigma, units=(1, 1, 1), work=None):
     """Dense descriptor image (sift3d_amd_dense_descriptors_device): out [12, nz, ny, nx] from src
     [nz, ny, nx], torch CUDA float32, on torch's current stream.  work: a float32 CUDA tensor of at least
     sift3d_amd_dense_work_floats elements (2 * nz*ny*nx), or None to allocate one here."""
-    import torch
     nx, ny, nz = _dense_args(src, out, "dense_descriptors")
-    need = lib().sift3d_amd_dense_work_floats(nx, ny, nz)
-    if work is None:
-        work = torch.empty(need, dtype=torch.float32, device=src.device)
-    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.float32
-            and work.is_contiguous() and work.numel() >= need and work.device == src.device):
-        raise ValueError("dense_descriptors: work must be a contiguous float32 CUDA tensor of >= %d elements "
-                         "on the device of src" % need)
+    work = _work(work, lib().sift3d_amd_dense_work_floats(nx, ny, nz), src, "dense_descriptors", "float32")
     u = (C.c_double * 3)(*map(float, units))
     _check(lib().sift3d_amd_dense_descriptors_device(src.data_ptr(), nx, ny, nz, u, float(sigma), out.data_ptr(),
                                                      work.data_ptr(), current_stream()),
@@ -421,25 +428,19 @@ def dense_descriptors(src, out, sigma, units=(1, 1, 1), work=None):
 
 
 def _dense_r(src, R):
-    import torch
-    nz, ny, nx = src.shape
-    if not (isinstance(R, torch.Tensor) and R.is_cuda and R.dtype == torch.float32 and R.is_contiguous()
-            and tuple(R.shape) == (3, 3, nz, ny, nx) and R.device == src.device):
-        raise ValueError("R must be a contiguous float32 CUDA tensor [3, 3, nz, ny, nx] on the device of src")
+    _tensor(R, "R must be a contiguous float32 CUDA tensor [3, 3, nz, ny, nx] on the device of src",
+            shape=(3, 3) + tuple(src.shape), device=src.device)
 
 
 def dense_orient(src, R, keep=None, sigma=1.6, units=(1, 1, 1)):
     """R2 of the rotating dense contract (sift3d_hip_dense_orient): every voxel's eigen-orientation R
     [3, 3, nz, ny, nx] float32 and keep [nz, ny, nx] uint8 (or None) from src [nz, ny, nx], torch CUDA
     tensors, on torch's current stream."""
-    import torch
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32 and src.is_contiguous()
-            and src.dim() == 3):
-        raise ValueError("dense_orient: src must be a contiguous float32 CUDA tensor [nz, ny, nx]")
+    _tensor(src, "dense_orient: src must be a contiguous float32 CUDA tensor [nz, ny, nx]", dims=(3,))
     _dense_r(src, R)
-    if keep is not None and not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.dtype == torch.uint8
-                                 and keep.is_contiguous() and keep.shape == src.shape and keep.device == src.device):
-        raise ValueError("dense_orient: keep must be a contiguous uint8 CUDA tensor shaped like src, or None")
+    if keep is not None:
+        _tensor(keep, "dense_orient: keep must be a contiguous uint8 CUDA tensor shaped like src, or None",
+                shape=src.shape, device=src.device, dtype="uint8")
     nz, ny, nx = src.shape
     _check(lib().sift3d_hip_dense_orient(src.data_ptr(), nx, ny, nz, *map(float, units), float(sigma), R.data_ptr(),
                                          None if keep is None else keep.data_ptr(), current_stream()),
@@ -463,15 +464,9 @@ def dense_descriptors_rotate(src, out, sigma, units=(1, 1, 1), work=None):
     [12, nz, ny, nx] from src [nz, ny, nx], torch CUDA float32, on torch's current stream.  work: a float32
     CUDA tensor of at least sift3d_amd_dense_rotate_work_floats elements (9 * nz*ny*nx), or None to
     allocate one here."""
-    import torch
     nx, ny, nz = _dense_args(src, out, "dense_descriptors_rotate")
-    need = lib().sift3d_amd_dense_rotate_work_floats(nx, ny, nz)
-    if work is None:
-        work = torch.empty(need, dtype=torch.float32, device=src.device)
-    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.float32
-            and work.is_contiguous() and work.numel() >= need and work.device == src.device):
-        raise ValueError("dense_descriptors_rotate: work must be a contiguous float32 CUDA tensor of >= %d "
-                         "elements on the device of src" % need)
+    work = _work(work, lib().sift3d_amd_dense_rotate_work_floats(nx, ny, nz), src, "dense_descriptors_rotate",
+                 "float32")
     u = (C.c_double * 3)(*map(float, units))
     _check(lib().sift3d_amd_dense_descriptors_rotate_device(src.data_ptr(), nx, ny, nz, u, float(sigma),
                                                             out.data_ptr(), work.data_ptr(), current_stream()),
@@ -483,24 +478,33 @@ DEMONS_STATS_BYTES = 16
 DEMONS_FORCE_WORK_BYTES = 32768
 
 
-def _demons_images(F, M, field, what):
-    import torch
+def _demons_pair(F, M, what, level=""):
+    """The checks of one demons level's features: F, M [nz, ny, nx] or [nc, nz, ny, nx] with the same channels, on
+    one device.  Returns nc and the two grids (x, y, z)."""
     for t, name in ((F, "fixed"), (M, "moving")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                and t.dim() in (3, 4)):
-            raise ValueError("%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]"
-                             % (what, name))
-    _field_tensor(field, what)
+        _tensor(t, "%s: %s%s must be a contiguous float32 CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]"
+                % (what, level, name), dims=(3, 4))
     nc = F.shape[0] if F.dim() == 4 else 1
     if M.dim() != F.dim() or (M.shape[0] if M.dim() == 4 else 1) != nc:
-        raise ValueError("%s: fixed %s and moving %s differ in channels" % (what, tuple(F.shape), tuple(M.shape)))
-    if tuple(field.shape[1:]) != tuple(F.shape[-3:]):
-        raise ValueError("%s: the field %s is not on the fixed grid %s" % (what, tuple(field.shape), tuple(F.shape)))
-    if not (F.device == M.device == field.device):
-        raise ValueError("%s: fixed, moving and field are not on one device" % what)
+        raise ValueError("%s: %sfixed %s and moving %s differ in channels"
+                         % (what, level, tuple(F.shape), tuple(M.shape)))
+    if F.device != M.device:
+        raise ValueError("%s: %sfixed and moving are not on one device" % (what, level))
     nz, ny, nx = F.shape[-3:]
     mz, my, mx = M.shape[-3:]
     return nc, (nx, ny, nz), (mx, my, mz)
+
+
+def _demons_images(F, M, field, what, level=""):
+    """_demons_pair, and the field [3, nz, ny, nx] on F's grid and device"""
+    out = _demons_pair(F, M, what, level)
+    _field_tensor(field, what)
+    if tuple(field.shape[1:]) != tuple(F.shape[-3:]):
+        raise ValueError("%s: the field %s is not on the fixed grid %s"
+                         % (what, tuple(field.shape), tuple(F.shape)))
+    if field.device != F.device:
+        raise ValueError("%s: fixed, moving and field are not on one device" % what)
+    return out
 
 
 def demons_stats(stats):
@@ -538,39 +542,33 @@ def demons_force(F, W, field, step, alpha, moving_shape=None, stats=None, work=N
 DEMONS_UPDATE = {"additive": 0, "diffeomorphic": 1}
 
 
+def _demons_update(update, what):
+    if update not in DEMONS_UPDATE:
+        raise ValueError("%s: update must be 'additive' or 'diffeomorphic', not %r" % (what, update))
+    return DEMONS_UPDATE[update]
+
+
 def demons(F, M, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None, update="additive",
            squarings=0):
-    """`iterations` demons iterations (sift3d_amd_demons_device, or sift3d_amd_demons_device_ex for
-    update="diffeomorphic"): the field [3, nz, ny, nx] is refined in place so that the moving features M
-    ([mz, my, mx] or [nc, mz, my, mx]) warped through it approach the fixed features F ([nz, ny, nx] /
-    [nc, nz, ny, nx]).  update "additive": u += delta; "diffeomorphic": u <- u o exp(delta) with `squarings`
-    squarings.  torch CUDA float32, on torch's current stream, no host synchronisation.  Returns the stats tensor
-    (16 bytes per iteration; read it with demons_stats)."""
+    """`iterations` demons iterations (sift3d_amd_demons_device_ex): the field [3, nz, ny, nx] is refined in
+    place so that the moving features M ([mz, my, mx] or [nc, mz, my, mx]) warped through it approach the fixed
+    features F ([nz, ny, nx] / [nc, nz, ny, nx]).  update "additive": u += delta (`squarings` is not used);
+    "diffeomorphic": u <- u o exp(delta) with `squarings` squarings.  torch CUDA float32, on torch's current
+    stream, no host synchronisation.  Returns the stats tensor (16 bytes per iteration; read it with
+    demons_stats)."""
     import torch
     nc, (nx, ny, nz), (mx, my, mz) = _demons_images(F, M, field, "demons")
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError("demons: iterations must not be negative")
-    if update not in DEMONS_UPDATE:
-        raise ValueError("demons: update must be 'additive' or 'diffeomorphic', not %r" % (update,))
-    need = lib().sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, DEMONS_UPDATE[update])
-    if work is None:
-        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=F.device)
-    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.is_contiguous()
-            and work.numel() * work.element_size() >= 4 * need and work.device == F.device):
-        raise ValueError("demons: work must be a contiguous CUDA tensor of >= %d bytes on the device of F" % (4 * need))
+    mode = _demons_update(update, "demons")
+    work = _work(work, lib().sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, mode), F, "demons")
     stats = torch.empty(max(iterations, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
-    if update == "additive":
-        _check(lib().sift3d_amd_demons_device(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc,
-                                              field.data_ptr(), iterations, float(alpha), float(sigma_fluid),
-                                              float(sigma_diffusion), work.data_ptr(), stats.data_ptr(),
-                                              current_stream()), "sift3d_amd_demons_device")
-    else:
-        _check(lib().sift3d_amd_demons_device_ex(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc,
-                                                 field.data_ptr(), iterations, float(alpha), float(sigma_fluid),
-                                                 float(sigma_diffusion), DEMONS_UPDATE[update], int(squarings),
-                                                 work.data_ptr(), stats.data_ptr(), current_stream()),
-               "sift3d_amd_demons_device_ex")
+    _check(lib().sift3d_amd_demons_device_ex(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, nc,
+                                             field.data_ptr(), iterations, float(alpha), float(sigma_fluid),
+                                             float(sigma_diffusion), mode, int(squarings) if mode else 0,
+                                             work.data_ptr(), stats.data_ptr(), current_stream()),
+           "sift3d_amd_demons_device_ex")
     return stats[:iterations * DEMONS_STATS_BYTES // 8]
 
 
@@ -588,11 +586,6 @@ def field_stats(stats):
     f = raw[:, :16].copy().view(np.float64)
     c = raw[:, 16:].copy().view(np.uint64)
     return f[:, 0], f[:, 1], c[:, 0], c[:, 1]
-
-
-def _same_device(what, *ts):
-    if any(t.device != ts[0].device for t in ts):
-        raise ValueError("%s: the tensors are not on one device" % what)
 
 
 def field_compose(u, v, out=None, mode="compose", stats=None, work=None):
@@ -632,16 +625,13 @@ def field_compose(u, v, out=None, mode="compose", stats=None, work=None):
 def field_exp(v, out, squarings, work=None):
     """out = exp(v) by scaling and squaring (sift3d_amd_field_exp_device): v, out [3, oz, oy, ox] torch CUDA
     float32, on torch's current stream."""
-    import torch
     _field_tensor(v, "field_exp", "v")
     _field_tensor(out, "field_exp", "out")
     if out.shape != v.shape:
         raise ValueError("field_exp: out %s is not shaped like v %s" % (tuple(out.shape), tuple(v.shape)))
     _same_device("field_exp", v, out)
     _, oz, oy, ox = v.shape
-    need = lib().sift3d_amd_field_exp_work_floats(ox, oy, oz)
-    if work is None:
-        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=v.device)
+    work = _work(work, lib().sift3d_amd_field_exp_work_floats(ox, oy, oz), v, "field_exp")
     _check(lib().sift3d_amd_field_exp_device(v.data_ptr(), ox, oy, oz, int(squarings), out.data_ptr(),
                                              work.data_ptr(), current_stream()), "sift3d_amd_field_exp_device")
     return out
@@ -660,9 +650,7 @@ def field_invert(u, w, iterations, work=None):
         raise ValueError("field_invert: iterations must not be negative")
     _, uz, uy, ux = u.shape
     _, oz, oy, ox = w.shape
-    need = lib().sift3d_amd_field_invert_work_floats(ox, oy, oz)
-    if work is None:
-        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=w.device)
+    work = _work(work, lib().sift3d_amd_field_invert_work_floats(ox, oy, oz), w, "field_invert")
     stats = torch.empty((iterations + 1) * FIELD_STATS_BYTES // 8, dtype=torch.int64, device=w.device)
     _check(lib().sift3d_amd_field_invert_device(u.data_ptr(), ux, uy, uz, w.data_ptr(), ox, oy, oz, iterations,
                                                 work.data_ptr(), stats.data_ptr(), current_stream()),
@@ -684,15 +672,13 @@ def restrict2(src, dst=None, scale=1.0):
     [nc, nz, ny, nx], dst the same with every grid axis (n + 1) // 2 (None: allocated), torch CUDA float32
     contiguous, on torch's current stream.  scale 0.5 restricts a displacement field."""
     import torch
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32 and src.is_contiguous()
-            and src.dim() in (3, 4)):
-        raise ValueError("restrict2: src must be a contiguous float32 CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]")
+    _tensor(src, "restrict2: src must be a contiguous float32 CUDA tensor [nz, ny, nx] or [nc, nz, ny, nx]",
+            dims=(3, 4))
     want = tuple(src.shape[:-3]) + half_shape(src.shape[-3:])
     if dst is None:
         dst = torch.empty(want, dtype=torch.float32, device=src.device)
-    if not (isinstance(dst, torch.Tensor) and dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
-            and tuple(dst.shape) == want and dst.device == src.device):
-        raise ValueError("restrict2: dst must be a contiguous float32 CUDA tensor %s on the device of src" % (want,))
+    _tensor(dst, "restrict2: dst must be a contiguous float32 CUDA tensor %s on the device of src" % (want,),
+            shape=want, device=src.device)
     nc = src.shape[0] if src.dim() == 4 else 1
     nz, ny, nx = src.shape[-3:]
     _check(lib().sift3d_hip_restrict2(src.data_ptr(), nx, ny, nz, nc, dst.data_ptr(), float(scale),
@@ -726,49 +712,34 @@ def demons_multires(Fs, Ms, field, iterations, alpha, sigma_fluid=0.0, sigma_dif
     torch CUDA float32, on torch's current stream, no host synchronisation.  Returns the stats tensor: 16 bytes per
     iteration in the order run, the coarsest level's first (read it with demons_stats)."""
     import torch
+    what = "demons_multires"
     levels = len(Fs)
     if not (1 <= levels <= DEMONS_MAX_LEVELS) or len(Ms) != levels:
         raise ValueError("demons_multires: 1 .. %d levels of fixed and as many of moving features" % DEMONS_MAX_LEVELS)
     its = [int(k) for k in iterations]
     if len(its) != levels or any(k < 0 for k in its):
         raise ValueError("demons_multires: iterations must hold one count >= 0 per level")
-    if update not in DEMONS_UPDATE:
-        raise ValueError("demons_multires: update must be 'additive' or 'diffeomorphic', not %r" % (update,))
-    _field_tensor(field, "demons_multires")
+    mode = _demons_update(update, what)
+    _field_tensor(field, what)
     tab = (DemonsLevel * levels)()
     nc0 = None
     for l, (F, M) in enumerate(zip(Fs, Ms)):
-        u_l = field if l == 0 else None
-        for t, name in ((F, "fixed"), (M, "moving")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                    and t.dim() in (3, 4) and t.device == field.device):
-                raise ValueError("demons_multires: level %d %s must be a contiguous float32 CUDA tensor "
-                                 "[nz, ny, nx] or [nc, nz, ny, nx] on the field's device" % (l, name))
-        nc = F.shape[0] if F.dim() == 4 else 1
-        if M.dim() != F.dim() or (M.shape[0] if M.dim() == 4 else 1) != nc or (nc0 is not None and nc != nc0):
-            raise ValueError("demons_multires: level %d differs in channels" % l)
+        # a level's checks are those of demons; only level 0 has its field here (the others' are in the work buffer)
+        level = "level %d " % l
+        nc, (nx, ny, nz), (mx, my, mz) = (_demons_pair(F, M, what, level) if l else
+                                          _demons_images(F, M, field, what, level))
+        if F.device != field.device or nc0 not in (None, nc):
+            raise ValueError("demons_multires: level %d differs in channels or is not on the field's device" % l)
         nc0 = nc
-        if u_l is not None and tuple(u_l.shape[1:]) != tuple(F.shape[-3:]):
-            raise ValueError("demons_multires: the field %s is not on the finest fixed grid %s"
-                             % (tuple(field.shape), tuple(F.shape)))
-        if l > 0 and (tuple(F.shape[-3:]) != half_shape(Fs[l - 1].shape[-3:])
-                      or tuple(M.shape[-3:]) != half_shape(Ms[l - 1].shape[-3:])):
+        if l and ((nz, ny, nx) != half_shape(Fs[l - 1].shape[-3:]) or (mz, my, mx) != half_shape(Ms[l - 1].shape[-3:])):
             raise ValueError("demons_multires: level %d is not the half of level %d" % (l, l - 1))
-        nz, ny, nx = F.shape[-3:]
-        mz, my, mx = M.shape[-3:]
         tab[l] = DemonsLevel(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, its[l])
     _, nz, ny, nx = field.shape
-    need = lib().sift3d_amd_demons_multires_work_floats(nx, ny, nz, nc0, DEMONS_UPDATE[update], levels)
-    if work is None:
-        work = torch.empty((need + 1) // 2, dtype=torch.float64, device=field.device)
-    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.is_contiguous()
-            and work.numel() * work.element_size() >= 4 * need and work.device == field.device):
-        raise ValueError("demons_multires: work must be a contiguous CUDA tensor of >= %d bytes on the field's device"
-                         % (4 * need))
+    work = _work(work, lib().sift3d_amd_demons_multires_work_floats(nx, ny, nz, nc0, mode, levels), field, what)
     total = sum(its)
     stats = torch.empty(max(total, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
     _check(lib().sift3d_amd_demons_multires_device(tab, levels, nc0, field.data_ptr(), float(alpha),
-                                                   float(sigma_fluid), float(sigma_diffusion), DEMONS_UPDATE[update],
+                                                   float(sigma_fluid), float(sigma_diffusion), mode,
                                                    int(squarings), work.data_ptr(), stats.data_ptr(),
                                                    current_stream()), "sift3d_amd_demons_multires_device")
     return stats[:total * DEMONS_STATS_BYTES // 8]
