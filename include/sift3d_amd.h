@@ -377,6 +377,77 @@ SIFT3D_AMD_API int sift3d_amd_jacobian_det(const float *field, int ox, int oy, i
                                            uint64_t *folded, float *min, float *max);
 
 /* ------------------------------------------------------------------------ */
+/* Cubic B-spline resampling: prefilter and 64-tap sampling                  */
+/* ------------------------------------------------------------------------ */
+/* LINEAR sampling is a low-pass filter: every pass blurs.  The cubic B-spline interpolant (scipy order = 3, ITK
+ * BSpline) does not: the volume is first turned into B-spline coefficients, which are then sampled with the 4 x 4 x 4
+ * cubic B-spline weights.  No upstream counterpart: pinned to this contract (tests/bspline_restatement.py), and
+ * compared with scipy.ndimage (spline_filter / map_coordinates, order 3, mode "mirror") to a derived bound.
+ *
+ * 1. Coefficients (prefilter).  Per axis the coefficients c of a line s of n samples satisfy
+ *      sum_k c[k] beta3(i - k) = s[i],  beta3(0) = 2/3, beta3(+-1) = 1/6,
+ *    on the whole-sample mirror extension (period 2n - 2; scipy's mode "mirror").  The inverse of that filter is the
+ *    two-sided exponential sqrt(3) z1^|k|, z1 = sqrt(3) - 2 = -0.2679..., truncated here to |k| <= H = 16:
+ *      c[i] = acc after:  acc = +0.0f;  for k = H down to 1: acc = acc + h[k] * (s[m(i - k)] + s[m(i + k)]);
+ *                         acc = acc + h[0] * s[i]                    (float, this order, unfused)
+ *      m(j): j reduced into [0, 2n - 2) (mathematical modulus, so it reflects as often as needed when n <= H),
+ *            then 2n - 2 - j when j >= n
+ *      h[k] = (float)(sqrt(3) z1^k), the table SIFT3D_AMD_BSPLINE_TAPS below.
+ *    Every c[i] is a fixed expression of the line, so the result does not depend on how a kernel tiles it.  The
+ *    dropped tail is at most 2 sqrt(3) |z1|^(H+1) / (1 - |z1|) = 8.9e-10 of max|s|: a thirtieth of half a float ulp
+ *    (2^-25 = 3.0e-8) of a result as large as max|s|, and still below half an ulp for results down to max|s| / 33
+ *    (H = 14 leaves 1.2e-8, no margin for smaller results; the largest kept tap, h[16] = 1.2e-9, shows the size).
+ *    An axis of n = 1 is skipped: its pass is the identity.  The passes run x, then y, then z; each reads the result
+ *    of the one before.  (The taps sum to 1 - 2.9e-8 in float: constants are reproduced to rounding, not exactly.)
+ * 2. Sample.  c [nz][ny][nx] are coefficients; q is the sample point, as in the blocks above (the affine pull map
+ *    q_d = A[d][0] x + ((A[d][1] y + A[d][2] z) + A[d][3]) in double, or q_d = (double) p_d + (double) u_d(p) through
+ *    a field).  Inside when 0 <= q_d <= n_d - 1 on every axis (a NaN is outside); outside voxels get `fill`.  Per axis
+ *      i = floor(q), f = (float)(q - i), g = 1.0f - f, taps t_j = m(i - 1 + j), j = 0 .. 3 (m as above; n = 1: 0)
+ *      w0 = ((g * g) * g) * C6             C6  = (float)(1.0 / 6.0) = 0x1.555556p-3f
+ *      w1 = C23 - (0.5f * (f * f)) * (2.0f - f)      C23 = (float)(2.0 / 3.0) = 0x1.555556p-1f
+ *      w2 = C23 - (0.5f * (g * g)) * (2.0f - g)
+ *      w3 = ((f * f) * f) * C6
+ *    dot(w, a) = ((w0 * a0 + w1 * a1) + w2 * a2) + w3 * a3 in float, unfused.  The sum runs along x for the 16
+ *    (y, z) tap rows, r[jz][jy] = dot(wx, c[t_jz][t_jy][t_0..3]); then along y, s[jz] = dot(wy, r[jz][0..3]); then
+ *    along z, value = dot(wz, s[0..3]).
+ *    An identity map reproduces the volume only to rounding (w = (1/6, 2/3, 1/6, 0) undoes the prefilter in float),
+ *    not bit for bit: unlike LINEAR there is no exact-copy promise.
+ * Through a field every channel of an nc-channel coefficient image is sampled at the same point with the same taps
+ * and weights, so channel c of an nc-channel resample is the single-channel resample of channel c.
+ * The device entries are asynchronous on `stream`, allocate nothing, use 64-bit offsets and check their arguments
+ * before any device call: -1 on NULL pointers, dims <= 0, nc < 1, a non-finite A, a buffer that is not 4-byte
+ * aligned, an output (or the work buffer) that overlaps an input, the work buffer or another output.  The
+ * prefilter is not in place: d_coef must not overlap d_src. */
+#define SIFT3D_AMD_BSPLINE_H 16
+#define SIFT3D_AMD_BSPLINE_TAPS                                                                                   \
+    { 0x1.bb67aep+0f, -0x1.db3d74p-2f, 0x1.fd5c5ap-4f, -0x1.10f732p-5f, 0x1.24904cp-7f, -0x1.39919cp-9f,          \
+      0x1.5014fep-11f, -0x1.68362cp-13f, 0x1.8212dap-15f, -0x1.9dcaep-17f, 0x1.bb805ep-19f, -0x1.db57eap-21f,     \
+      0x1.fd78b6p-23f, -0x1.110664p-24f, 0x1.24a096p-26f, -0x1.39a31p-28f, 0x1.5027b4p-30f }
+/* device scratch of sift3d_hip_bspline_prefilter: nx*ny*nz floats, one channel's volume (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_hip_bspline_work_floats(int nx, int ny, int nz);
+/* d_src, d_coef [nc][nz][ny][nx]; channel by channel through d_work */
+SIFT3D_AMD_API int
+sift3d_hip_bspline_prefilter(const float *d_src, int nx, int ny, int nz, int nc, float *d_coef, float *d_work,
+                             void *stream);
+/* d_coef [nz][ny][nx] coefficients -> d_dst [oz][oy][ox] through the affine pull map A */
+SIFT3D_AMD_API int
+sift3d_hip_bspline_warp_affine(const float *d_coef, int nx, int ny, int nz, float *d_dst, int ox, int oy, int oz,
+                               const double *A /*12*/, float fill, void *stream);
+/* d_coef [nc][nz][ny][nx] coefficients -> d_dst [nc][oz][oy][ox] through the field d_field [3][oz][oy][ox] */
+SIFT3D_AMD_API int
+sift3d_hip_bspline_warp_field(const float *d_coef, int nx, int ny, int nz, int nc, const float *d_field, int ox,
+                              int oy, int oz, float *d_dst, float fill, void *stream);
+/* host forms, blocking; arguments are checked before the device is touched.  prefilter: a host volume
+ * [nc][nz][ny][nx] into coef (which must not overlap it).  warp_affine / warp_field: host image objects (nc == 1)
+ * holding SAMPLES; the source is prefiltered on the device, then resampled into dst's grid (the field on the host,
+ * shaped by dst's grid; -1 also when dst's data overlaps src's or the field). */
+SIFT3D_AMD_API int sift3d_amd_bspline_prefilter(const float *src, int nx, int ny, int nz, int nc, float *coef);
+SIFT3D_AMD_API int sift3d_amd_image_bspline_warp_affine(const sift3d_image *src, const double *A, float fill,
+                                                        sift3d_image *dst);
+SIFT3D_AMD_API int sift3d_amd_image_bspline_warp_field(const sift3d_image *src, const float *field, float fill,
+                                                       sift3d_image *dst);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -110,6 +110,9 @@ def lib():
         "sift3d_amd_image_warp_field": (C.c_int, [vp, _f32p, C.c_int, C.c_float, vp]),
         "sift3d_amd_jacobian_det": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "sift3d_amd_bspline_prefilter": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+        "sift3d_amd_image_bspline_warp_affine": (C.c_int, [vp, _f64p, C.c_float, vp]),
+        "sift3d_amd_image_bspline_warp_field": (C.c_int, [vp, _f32p, C.c_float, vp]),
         "sift3d_amd_image_dense_descriptors": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_image_dense_descriptors_rotate": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_device_available": (C.c_int, []),
@@ -780,6 +783,103 @@ def jacobian_determinant(field):
                                      C.byref(mx)) != 0:
         raise RuntimeError("sift3d_amd_jacobian_det failed")
     return JacobianStats(det, int(folded.value), float(mn.value), float(mx.value))
+
+
+# ---- cubic B-spline resampling --------------------------------------------------------------------
+def spline_coefficients(volume):
+    """The cubic B-spline coefficients of a volume (contract: include/sift3d_amd.h, "Cubic B-spline resampling";
+    whole-sample mirror boundaries, scipy's spline_filter(order=3, mode="mirror")).  A torch CUDA tensor
+    [nz, ny, nx] or [nc, nz, ny, nx] gives a tensor on torch's current stream; an Image or a float32 array goes
+    through the blocking host form and gives an array."""
+    if _torch_tensor(volume):
+        from . import hip
+        return hip.bspline_prefilter(volume)
+    src = volume.data() if isinstance(volume, Image) else volume
+    src = np.ascontiguousarray(src, np.float32)
+    if src.ndim not in (3, 4):
+        raise ValueError("spline_coefficients: the volume must be [nz, ny, nx] or [nc, nz, ny, nx]")
+    nc = src.shape[0] if src.ndim == 4 else 1
+    nz, ny, nx = src.shape[-3:]
+    out = np.empty_like(src)
+    if lib().sift3d_amd_bspline_prefilter(src.reshape(-1), nx, ny, nz, nc, out.reshape(-1)) != 0:
+        raise RuntimeError("sift3d_amd_bspline_prefilter failed")
+    return out
+
+
+def _affine_or_none(transform):
+    """the transform as a 3 x 4 float64 array when it is shaped like an affine pull map, else None (a field is not
+    converted to look at it)"""
+    try:
+        if np.shape(transform) not in ((3, 4), (12,)):
+            return None
+        return np.asarray(transform, np.float64).reshape(3, 4)
+    except (TypeError, ValueError):
+        return None
+
+
+def _field_out_shape(out_shape, grid):
+    if out_shape is not None and tuple(int(v) for v in out_shape) != tuple(int(v) for v in grid):
+        raise ValueError("resample_cubic: out_shape %s is not the field's grid %s" % (tuple(out_shape), tuple(grid)))
+
+
+def resample_cubic(volume, transform, out_shape=None, fill=0.0, prefiltered=False):
+    """Resample `volume` with the cubic B-spline interpolant (scipy order 3, mode "mirror" inside the grid): sharper
+    than the linear warps, which blur at every pass.  transform: a 3 x 4 affine pull map, a TPS (both need out_shape
+    = (oz, oy, ox)) or a displacement field [3, oz, oy, ox], whose grid is the output's (out_shape may be omitted;
+    ValueError when it is given and differs); a TPS is exported with displacement_field and sampled through that
+    field.  Voxels that sample outside the volume get `fill`.  prefiltered=True: `volume` already holds
+    spline_coefficients(volume), so that one prefilter serves many resamples of one volume.
+    A torch CUDA tensor [nz, ny, nx] or, through a TPS or a field, [nc, nz, ny, nx] gives a tensor on torch's current
+    stream; an Image or a float32 array [nz, ny, nx] goes through the blocking host forms (an affine or a host field;
+    not prefiltered) and gives an Image / an array."""
+    A = None if isinstance(transform, TPS) or _torch_tensor(transform) else _affine_or_none(transform)
+    if (A is not None or isinstance(transform, TPS)) and out_shape is None:
+        raise ValueError("resample_cubic: an affine or a TPS transform needs out_shape")
+    if _torch_tensor(volume):
+        import torch
+        from . import hip
+        if volume.dim() not in (3, 4):
+            raise ValueError("resample_cubic: the volume must be [nz, ny, nx] or [nc, nz, ny, nx]")
+        if A is None:
+            if isinstance(transform, TPS):
+                transform = displacement_field(transform, out_shape, volume.device)
+            if not _torch_tensor(transform):
+                raise ValueError("resample_cubic: transform must be a 3 x 4 affine pull map, a TPS or a CUDA field "
+                                 "[3, oz, oy, ox]")
+        elif volume.dim() != 3:
+            raise ValueError("resample_cubic: an affine transform takes a volume [nz, ny, nx]; resample a "
+                             "multi-channel volume through displacement_field(A, out_shape)")
+        coef = volume if prefiltered else hip.bspline_prefilter(volume)
+        if A is not None:
+            out = torch.empty(tuple(int(v) for v in out_shape), dtype=torch.float32, device=volume.device)
+            return hip.bspline_warp_affine(coef, out, A, fill)
+        hip._field_tensor(transform, "resample_cubic", "transform")
+        _field_out_shape(out_shape, transform.shape[1:])
+        out = torch.empty(tuple(volume.shape[:-3]) + tuple(transform.shape[1:]), dtype=torch.float32,
+                          device=volume.device)
+        return hip.bspline_warp_field(coef, out, transform, fill)
+    if prefiltered:
+        raise ValueError("resample_cubic: prefiltered=True takes a CUDA tensor of coefficients")
+    if isinstance(transform, TPS):
+        raise ValueError("resample_cubic: a host volume takes an affine or a host field; export the TPS with "
+                         "displacement_field(...).cpu().numpy()")
+    src = volume if isinstance(volume, Image) else Image.from_array(volume)
+    if len(src.shape) != 3:
+        raise ValueError("resample_cubic: the image must have one channel")
+    if A is not None:
+        oz, oy, ox = (int(v) for v in out_shape)
+        dst = Image(ox, oy, oz)
+        if lib().sift3d_amd_image_bspline_warp_affine(src.h, np.ascontiguousarray(A).reshape(12), float(fill),
+                                                      dst.h) != 0:
+            raise RuntimeError("sift3d_amd_image_bspline_warp_affine failed")
+    else:
+        f = _host_field(transform, "resample_cubic")
+        _field_out_shape(out_shape, f.shape[1:])
+        _, oz, oy, ox = f.shape
+        dst = Image(ox, oy, oz)
+        if lib().sift3d_amd_image_bspline_warp_field(src.h, f.reshape(-1), float(fill), dst.h) != 0:
+            raise RuntimeError("sift3d_amd_image_bspline_warp_field failed")
+    return dst if isinstance(volume, Image) else dst.data().copy()
 
 
 # ---- dense descriptors: a 12-bin gradient histogram per voxel ------------------------------------

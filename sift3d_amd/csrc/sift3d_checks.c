@@ -1,5 +1,5 @@
-/* sift3d_checks.c -- the argument checks shared by the entries of sift3d_warp.c, sift3d_dense.c, sift3d_field_ops.c
- * and sift3d_demons.c (included at the end of sift3d_host.c, ahead of them).
+/* sift3d_checks.c -- the argument checks shared by the entries of sift3d_warp.c, sift3d_dense.c, sift3d_field_ops.c,
+ * sift3d_demons.c and sift3d_bspline.c (included at the end of sift3d_host.c, ahead of them).
  *
  * An entry states what it checks with these and refuses with `return refuse(what, why)`: -1 and one line on stderr
  * that names the entry the caller called.  All of it is host arithmetic, so bad input is refused before the device
@@ -63,6 +63,15 @@ static int check_dims(const char *what, int nx, int ny, int nz)
 static int check_channels(const char *what, int nc)
 {
     return nc < 1 ? refuse(what, "the number of channels must be positive") : SIFT3D_SUCCESS;
+}
+
+static int check_affine(const char *what, const double *A)
+{
+    int i;
+    for (i = 0; i < 12; i++)
+        if (!isfinite(A[i]))
+            return refuse(what, "the affine map is not finite");
+    return SIFT3D_SUCCESS;
 }
 
 static int check_iterations(const char *what, int iterations)

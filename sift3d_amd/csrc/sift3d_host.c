@@ -2528,3 +2528,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 /* field composition, exponential and inverse; dense demons refinement of a displacement field */
 #include "sift3d_field_ops.c"
 #include "sift3d_demons.c"
+
+/* cubic B-spline resampling: prefilter and 64-tap sampling */
+#include "sift3d_bspline.c"

@@ -108,6 +108,12 @@ def lib():
         "sift3d_hip_warp_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                             vp, C.c_int, C.c_float, vp]),
         "sift3d_hip_jacobian_det": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_hip_bspline_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_bspline_prefilter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_hip_bspline_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                     C.POINTER(C.c_double), C.c_float, vp]),
+        "sift3d_hip_bspline_warp_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                    C.c_int, vp, C.c_float, vp]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -382,6 +388,62 @@ def jacobian_det(field, det=None):
     folded = int(raw[:8].view(np.uint64)[0])
     mn, mx = (float(v) for v in raw[8:16].view(np.float32))
     return det, folded, mn, mx
+
+
+# ---- cubic B-spline resampling (contract: include/sift3d_amd.h, "Cubic B-spline resampling") -----------------
+def bspline_prefilter(src, dst=None, work=None):
+    """The cubic B-spline coefficients of src (sift3d_hip_bspline_prefilter): torch CUDA float32 contiguous
+    [nz, ny, nx] or [nc, nz, ny, nx], into dst (allocated when None; not src: the prefilter is not in place), on
+    torch's current stream.  work: nz*ny*nx floats of scratch, allocated when None."""
+    import torch
+    _tensor(src, "bspline_prefilter: src must be a contiguous 3-D or 4-D float32 CUDA tensor", dims=(3, 4))
+    if dst is None:
+        dst = torch.empty_like(src)
+    _tensor(dst, "bspline_prefilter: dst must be a contiguous float32 CUDA tensor shaped like src on its device",
+            shape=src.shape, device=src.device)
+    nc = src.shape[0] if src.dim() == 4 else 1
+    nz, ny, nx = src.shape[-3:]
+    work = _work(work, lib().sift3d_hip_bspline_work_floats(nx, ny, nz), src, "bspline_prefilter")
+    _check(lib().sift3d_hip_bspline_prefilter(src.data_ptr(), nx, ny, nz, nc, dst.data_ptr(), work.data_ptr(),
+                                              current_stream()), "sift3d_hip_bspline_prefilter")
+    return dst
+
+
+def bspline_warp_affine(coef, dst, A, fill=0.0):
+    """dst[z, y, x] = the cubic B-spline with coefficients coef (bspline_prefilter) at A [x; y; z; 1] (A: 3 x 4 pull
+    map in voxels; sift3d_hip_bspline_warp_affine): torch CUDA float32 contiguous [nz, ny, nx] / [oz, oy, ox], on
+    torch's current stream; voxels that sample outside get `fill`."""
+    _warp_pair(coef, dst, "bspline_warp_affine")
+    a = np.ascontiguousarray(A, np.float64).reshape(12)
+    nz, ny, nx = coef.shape
+    oz, oy, ox = dst.shape
+    _check(lib().sift3d_hip_bspline_warp_affine(coef.data_ptr(), nx, ny, nz, dst.data_ptr(), ox, oy, oz,
+                                                a.ctypes.data_as(C.POINTER(C.c_double)), float(fill),
+                                                current_stream()), "sift3d_hip_bspline_warp_affine")
+    return dst
+
+
+def bspline_warp_field(coef, dst, field, fill=0.0):
+    """dst = the cubic B-spline with coefficients coef at p + field(p) (sift3d_hip_bspline_warp_field): coef
+    [nz, ny, nx] / dst [oz, oy, ox], or coef [nc, nz, ny, nx] / dst [nc, oz, oy, ox] (every channel at the same
+    points); field [3, oz, oy, ox]; torch CUDA float32 contiguous, on torch's current stream."""
+    for t in (coef, dst):
+        _tensor(t, "bspline_warp_field: coef and dst must be contiguous 3-D or 4-D float32 CUDA tensors", dims=(3, 4))
+    _field_tensor(field, "bspline_warp_field")
+    if coef.dim() != dst.dim() or (coef.dim() == 4 and coef.shape[0] != dst.shape[0]):
+        raise ValueError("bspline_warp_field: coef %s and dst %s differ in channels"
+                         % (tuple(coef.shape), tuple(dst.shape)))
+    if tuple(dst.shape[-3:]) != tuple(field.shape[1:]):
+        raise ValueError("bspline_warp_field: dst %s does not match the field's grid %s"
+                         % (tuple(dst.shape), tuple(field.shape[1:])))
+    _same_device("bspline_warp_field", coef, dst, field)
+    nc = coef.shape[0] if coef.dim() == 4 else 1
+    nz, ny, nx = coef.shape[-3:]
+    oz, oy, ox = dst.shape[-3:]
+    _check(lib().sift3d_hip_bspline_warp_field(coef.data_ptr(), nx, ny, nz, nc, field.data_ptr(), ox, oy, oz,
+                                               dst.data_ptr(), float(fill), current_stream()),
+           "sift3d_hip_bspline_warp_field")
+    return dst
 
 
 def _dense_args(src, out, what):
