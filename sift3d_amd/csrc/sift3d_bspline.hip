@@ -11,10 +11,11 @@
 //     load and store is a coalesced 256-byte row; a tile is 32 outputs along the axis plus the halo in LDS (64 x 64
 //     words), and a lane slides a 40-word register window over its 8 outputs.  The z pass sees the volume as nx*ny
 //     lines side by side, the y pass as nz groups of nx.
-// Gathers.  k_warp_affine's tiles (64 x 4 x 4 outputs per 256-lane workgroup, a lane gathers for 4 x outputs 16
-// apart), tile order and XCD grouping (sift3d_warp.hip).  The four x taps of a (y, z) tap row are one 16-byte load
-// (4-byte aligned: global_load_dwordx4) whenever they are not mirrored (1 <= ix <= nx - 3), four dword loads otherwise.
-#include "sift3d_kernels_common.h"
+// Gathers.  The tiles (64 x 4 x 4 outputs per 256-lane workgroup, a lane gathers for 4 x outputs 16 apart), tile
+// order, XCD grouping, pull map and inside test of sift3d_resample.h.  The four x taps of a (y, z) tap row are one
+// 16-byte load (4-byte aligned: global_load_dwordx4) whenever they are not mirrored (1 <= ix <= nx - 3), four dword
+// loads otherwise.
+#include "sift3d_resample.h"
 
 #include <cmath>
 
@@ -22,8 +23,6 @@ namespace {
 
 constexpr int H = SIFT3D_AMD_BSPLINE_H;
 __constant__ float c_taps[H + 1] = SIFT3D_AMD_BSPLINE_TAPS;
-
-constexpr unsigned MAX_GRID = 1u << 20;
 
 // whole-sample mirror of any int j into [0, n)
 __device__ __forceinline__ int mirror(int j, int n)
@@ -121,27 +120,6 @@ __global__ __launch_bounds__(256) void k_bspline_s(const StrideArgs p)
 }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------
-constexpr int TX = 64, TY = 4, TZ = 4;           // k_warp_affine's tile
-constexpr int NXCD = 8;
-
-struct GridArgs {
-    const float *src;                            // coefficients
-    float *dst;
-    int nx, ny, nz, ox, oy, oz;
-    int tiles_x, tiles_y;
-    unsigned ntiles;                             // < 2^32 - MAX_GRID (checked at launch)
-    float fill;
-    int vec;                                     // 16-byte stores (ox % 4 == 0, dst 16-byte aligned)
-};
-
-// block b of a pass of n blocks -> tile number within the pass: the blocks of one XCD (b % 8) get a contiguous run
-// of tile numbers (sift3d_warp.hip)
-__device__ __forceinline__ unsigned xcd_swizzle(unsigned b, unsigned n)
-{
-    const unsigned g = b % NXCD, k = b / NXCD, q = n / NXCD, r = n % NXCD;
-    return g * q + (g < r ? g : r) + k;
-}
-
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr float C6 = 0x1.555556p-3f, C23 = 0x1.555556p-1f;
@@ -160,20 +138,18 @@ __device__ __forceinline__ float dot4(const float w[4], float a0, float a1, floa
     return ((w[0] * a0 + w[1] * a1) + w[2] * a2) + w[3] * a3;
 }
 
-// where to read and with which weights: once per output voxel
-struct Taps {
+// where to read and with which weights: once per output voxel (p.src holds the coefficients)
+struct CubicTaps {
     size_t ry[4], rz[4];                         // offsets of the four tap rows / planes
     int xt[4];                                   // the four x taps; xt[0] = ix - 1 on the fast path
     float wx[4], wy[4], wz[4];
     bool fast, in;
 };
 
-__device__ __forceinline__ Taps taps_at(const GridArgs &p, double qx, double qy, double qz)
+__device__ __forceinline__ CubicTaps cubic_taps_at(const GridArgs &p, double qx, double qy, double qz)
 {
-    Taps t;
-    // `&`, not `&&`: six compares and one mask (a NaN fails every compare); an outside sample reads around voxel 0
-    const bool in = (qx >= 0.0) & (qx <= (double)(p.nx - 1)) & (qy >= 0.0) & (qy <= (double)(p.ny - 1)) &
-                    (qz >= 0.0) & (qz <= (double)(p.nz - 1));
+    CubicTaps t;
+    const bool in = inside(qx, qy, qz, p.nx, p.ny, p.nz);                    // an outside sample reads around voxel 0
     qx = in ? qx : 0.0;
     qy = in ? qy : 0.0;
     qz = in ? qz : 0.0;
@@ -194,7 +170,7 @@ __device__ __forceinline__ Taps taps_at(const GridArgs &p, double qx, double qy,
     return t;
 }
 
-__device__ __forceinline__ float gather(const float *__restrict__ s, const Taps &t, float fill)
+__device__ __forceinline__ float cubic_gather(const float *__restrict__ s, const CubicTaps &t, float fill)
 {
     float r[4][4];
     if (t.fast) {
@@ -222,68 +198,32 @@ __device__ __forceinline__ float gather(const float *__restrict__ s, const Taps 
     return t.in ? v : fill;
 }
 
-struct AffineArgs {
-    double a[12];
-    GridArgs g;
-};
-
-// k_warp_affine (sift3d_warp.hip) with the cubic sample: the lane's 4 outputs are gathered 16 x apart and regrouped
-// through LDS into one 16-byte store
+// k_warp_affine (sift3d_warp.hip) with the cubic sample
 __global__ __launch_bounds__(256) void k_bspline_warp_affine(const AffineArgs q)
 {
     const GridArgs &p = q.g;
     __shared__ float4 xch[256];
-    float *xs = reinterpret_cast<float *>(xch) + (threadIdx.x & ~15) * 4;    // this row's 64 outputs
-    const int lx = threadIdx.x & 15, ly = (threadIdx.x >> 4) & 3, lz = threadIdx.x >> 6;
+    const int lx = threadIdx.x & 15;
     for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
-        const unsigned n = min(p.ntiles - base, gridDim.x);
-        if (blockIdx.x >= n)
-            return;                                                          // uniform over the block
-        const unsigned t = base + xcd_swizzle(blockIdx.x, n);
-        const unsigned tyz = t / (unsigned)p.tiles_x;
-        const int tx = (int)(t - tyz * (unsigned)p.tiles_x);
-        const int ty = (int)(tyz % (unsigned)p.tiles_y), tz = (int)(tyz / (unsigned)p.tiles_y);
-        const int xt = tx * TX, y = ty * TY + ly, z = tz * TZ + lz;
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            return;
         // rows past the grid are computed and not stored: every lane takes part in the exchange, and every sample
         // reads inside the source
         const double yd = (double)y, zd = (double)z;
-        const double rx = (q.a[1] * yd + q.a[2] * zd) + q.a[3];
-        const double ry = (q.a[5] * yd + q.a[6] * zd) + q.a[7];
-        const double rz = (q.a[9] * yd + q.a[10] * zd) + q.a[11];
+        const double rx = pull_row(q.a, yd, zd), ry = pull_row(q.a + 4, yd, zd), rz = pull_row(q.a + 8, yd, zd);
         float v[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const double xd = (double)(xt + lx + 16 * k);
-            const Taps tp = taps_at(p, q.a[0] * xd + rx, q.a[4] * xd + ry, q.a[8] * xd + rz);
-            v[k] = gather(p.src, tp, p.fill);
+            const CubicTaps tp = cubic_taps_at(p, pull(q.a, xd, rx), pull(q.a + 4, xd, ry), pull(q.a + 8, xd, rz));
+            v[k] = cubic_gather(p.src, tp, p.fill);
         }
-        __syncthreads();                                                     // previous tile's reads done
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            xs[lx + 16 * k] = v[k];
-        __syncthreads();
-        const float4 w = xch[threadIdx.x];
         const int x0 = xt + 4 * lx;
-        if (x0 >= p.ox || y >= p.oy || z >= p.oz)
-            continue;
-        float *out = p.dst + ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox + (size_t)x0;
-        if (p.vec) {
-            st4(out, w);
-        } else {
-            const float o[4] = {w.x, w.y, w.z, w.w};
-            const int m = min(4, p.ox - x0);
-#pragma nounroll
-            for (int k = 0; k < m; k++)
-                out[k] = o[k];
-        }
+        exchange_store(xch, v, p.dst + ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox, x0,
+                       x0 < p.ox && y < p.oy && z < p.oz, p.vec, p.ox);
     }
 }
-
-struct FieldArgs {
-    GridArgs g;
-    const float *field;
-    int nc;
-};
 
 // The same tiles and tile order.  A lane places the taps and weights of one output (44 registers) and gathers every
 // channel with them before it turns to its next output; the values leave as dword stores, 16 lanes of a row writing
@@ -292,18 +232,13 @@ struct FieldArgs {
 __global__ __launch_bounds__(256) void k_bspline_warp_field(const FieldArgs f)
 {
     const GridArgs &p = f.g;
-    const int lx = threadIdx.x & 15, ly = (threadIdx.x >> 4) & 3, lz = threadIdx.x >> 6;
+    const int lx = threadIdx.x & 15;
     const size_t svox = (size_t)p.nx * (size_t)p.ny * (size_t)p.nz;
     const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;
     for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
-        const unsigned n = min(p.ntiles - base, gridDim.x);
-        if (blockIdx.x >= n)
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
             return;
-        const unsigned t = base + xcd_swizzle(blockIdx.x, n);
-        const unsigned tyz = t / (unsigned)p.tiles_x;
-        const int tx = (int)(t - tyz * (unsigned)p.tiles_x);
-        const int ty = (int)(tyz % (unsigned)p.tiles_y), tz = (int)(tyz / (unsigned)p.tiles_y);
-        const int xt = tx * TX, y = ty * TY + ly, z = tz * TZ + lz;
         if (y >= p.oy || z >= p.oz)
             continue;
         const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
@@ -314,37 +249,12 @@ __global__ __launch_bounds__(256) void k_bspline_warp_field(const FieldArgs f)
                 break;
             const float *u = f.field + orow + (size_t)x;
             const float ux = u[0], uy = u[ovox], uz = u[2 * ovox];
-            const Taps tp = taps_at(p, (double)x + (double)ux, (double)y + (double)uy, (double)z + (double)uz);
+            const CubicTaps tp = cubic_taps_at(p, (double)x + (double)ux, (double)y + (double)uy, (double)z + (double)uz);
             float *out = p.dst + orow + (size_t)x;
             for (int c = 0; c < f.nc; c++)
-                out[(size_t)c * ovox] = gather(p.src + (size_t)c * svox, tp, p.fill);
+                out[(size_t)c * ovox] = cubic_gather(p.src + (size_t)c * svox, tp, p.fill);
         }
     }
-}
-
-int bspline_fail(const char *fn, const char *why)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", fn, why);
-    fprintf(stderr, "sift3d_amd: %s\n", g_err);
-    return SIFT3D_FAILURE;
-}
-
-// the output tiling shared by the two gathers; false when the grid has 2^32 - MAX_GRID tiles or more
-bool grid_args(GridArgs &p, const float *d_coef, int nx, int ny, int nz, float *d_dst, int ox, int oy, int oz, float fill)
-{
-    p.src = d_coef;
-    p.dst = d_dst;
-    p.nx = nx; p.ny = ny; p.nz = nz;
-    p.ox = ox; p.oy = oy; p.oz = oz;
-    p.tiles_x = (ox + TX - 1) / TX;
-    p.tiles_y = (oy + TY - 1) / TY;
-    const unsigned long long nt = (unsigned long long)p.tiles_x * p.tiles_y * ((oz + TZ - 1) / TZ);
-    if (nt > 0xffffffffull - MAX_GRID)
-        return false;
-    p.ntiles = (unsigned)nt;
-    p.fill = fill;
-    p.vec = (ox % 4 == 0) && !((uintptr_t)d_dst & 15);
-    return true;
 }
 
 int pass_x(const float *src, float *dst, int nx, int ny, int nz, hipStream_t st)
@@ -425,7 +335,7 @@ int sift3d_bspline_warp_affine_launch(const float *d_coef, int nx, int ny, int n
 {
     AffineArgs q;
     if (!grid_args(q.g, d_coef, nx, ny, nz, d_dst, ox, oy, oz, fill))
-        return bspline_fail("sift3d_hip_bspline_warp_affine", "output grid too large");
+        return launch_fail("sift3d_hip_bspline_warp_affine", "output grid too large");
     for (int i = 0; i < 12; i++)
         q.a[i] = A[i];
     const unsigned grid = q.g.ntiles < MAX_GRID ? q.g.ntiles : MAX_GRID;
@@ -439,7 +349,7 @@ int sift3d_bspline_warp_field_launch(const float *d_coef, int nx, int ny, int nz
 {
     FieldArgs f;
     if (!grid_args(f.g, d_coef, nx, ny, nz, d_dst, ox, oy, oz, fill))
-        return bspline_fail("sift3d_hip_bspline_warp_field", "output grid too large");
+        return launch_fail("sift3d_hip_bspline_warp_field", "output grid too large");
     f.field = d_field;
     f.nc = nc;
     const unsigned grid = f.g.ntiles < MAX_GRID ? f.g.ntiles : MAX_GRID;

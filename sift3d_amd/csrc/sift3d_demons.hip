@@ -14,7 +14,7 @@
 // butterfly, per workgroup through LDS into partial slot blockIdx.x; k_demons_finish adds the slots in a fixed
 // order.  The grid is min(tiles, DEM_GRID) workgroups whatever the device, so the bits of the sum depend on the
 // shape alone.
-#include "sift3d_kernels_common.h"
+#include "sift3d_resample.h"
 
 namespace {
 
@@ -40,12 +40,6 @@ __device__ __forceinline__ float from_left(float v, float edge)
 __device__ __forceinline__ float from_right(float v, float edge)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float dgrad(float lo, float c, float hi, int i, int n)
-{
-    // numpy.gradient: central difference inside, one-sided at the ends; an axis of length 1 has none
-    return n == 1 ? 0.0f : i == 0 ? hi - c : i == n - 1 ? c - lo : (hi - lo) * 0.5f;
 }
 
 // One channel's loads for a lane's DEM_K planes.  f[j], w[j]: the centre at plane z0 - 1 + j (j = 0 .. DEM_K + 1;
@@ -135,9 +129,7 @@ __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
                 const float ux = ub[o], uy = ub[o + vox], uz = ub[o + 2 * vox];
                 const double qx = (double)x + (double)ux, qy = (double)y + (double)uy;
                 const double qz = (double)z + (double)uz;
-                // warp_field's inside test (a NaN is outside)
-                in[k] = (qx >= 0.0) & (qx <= (double)(p.mx - 1)) & (qy >= 0.0) & (qy <= (double)(p.my - 1)) &
-                        (qz >= 0.0) & (qz <= (double)(p.mz - 1));
+                in[k] = inside(qx, qy, qz, p.mx, p.my, p.mz);                // warp_field's (a NaN is outside)
             }
         }
         // Channels outer, the lane's planes inner: the planes z0 - 1 .. z0 + DEM_K of a channel are loaded once and
@@ -161,10 +153,10 @@ __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
                     const float fxm = from_left(fc, cur.ef[k]), fxp = from_right(fc, cur.ef[k]);
                     const float wxm = from_left(wc, cur.ew[k]), wxp = from_right(wc, cur.ew[k]);
                     const float d = fc - wc;
-                    const float g0 = 0.5f * (dgrad(fxm, fc, fxp, x, p.nx) + dgrad(wxm, wc, wxp, x, p.nx));
-                    const float g1 = 0.5f * (dgrad(cur.fym[k], fc, cur.fyp[k], y, p.ny) +
-                                             dgrad(cur.wym[k], wc, cur.wyp[k], y, p.ny));
-                    const float g2 = 0.5f * (dgrad(fl, fc, fh, z, p.nz) + dgrad(wl, wc, wh, z, p.nz));
+                    const float g0 = 0.5f * (grad(fxm, fc, fxp, x, p.nx) + grad(wxm, wc, wxp, x, p.nx));
+                    const float g1 = 0.5f * (grad(cur.fym[k], fc, cur.fyp[k], y, p.ny) +
+                                             grad(cur.wym[k], wc, cur.wyp[k], y, p.ny));
+                    const float g2 = 0.5f * (grad(fl, fc, fh, z, p.nz) + grad(wl, wc, wh, z, p.nz));
                     const double dd = (double)d;
                     n0[k] = n0[k] + dd * (double)g0;
                     n1[k] = n1[k] + dd * (double)g1;
@@ -196,48 +188,25 @@ __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
             }
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        lsum += __shfl_xor(lsum, s);
-        lcnt += __shfl_xor(lcnt, s);
-    }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[wv] = lsum;
-        s_cnt[wv] = lcnt;
-    }
-    __syncthreads();
+    lsum = workgroup_reduce<Add>(lsum, s_sum);
+    lcnt = workgroup_reduce<Add>(lcnt, s_cnt);
     if (threadIdx.x == 0) {
-        p.psum[blockIdx.x] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-        p.pcnt[blockIdx.x] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+        p.psum[blockIdx.x] = lsum;
+        p.pcnt[blockIdx.x] = lcnt;
     }
 }
 
-// the partial slots 0 .. n-1 in a fixed order: lane t adds slots t, t + 256, ... in turn, then a fixed tree
+// the partial slots 0 .. n-1 in a fixed order (finish_reduce)
 __global__ __launch_bounds__(256) void k_demons_finish(const double *psum, const unsigned long long *pcnt, unsigned n,
                                                        double *sum, unsigned long long *cnt)
 {
     __shared__ double s_sum[256];
     __shared__ unsigned long long s_cnt[256];
-    double a = 0.0;
-    unsigned long long b = 0;
-    for (unsigned i = threadIdx.x; i < n; i += 256) {
-        a += psum[i];
-        b += pcnt[i];
-    }
-    s_sum[threadIdx.x] = a;
-    s_cnt[threadIdx.x] = b;
-    __syncthreads();
-    for (unsigned s = 128; s >= 1; s >>= 1) {
-        if (threadIdx.x < s) {
-            s_sum[threadIdx.x] = s_sum[threadIdx.x] + s_sum[threadIdx.x + s];
-            s_cnt[threadIdx.x] = s_cnt[threadIdx.x] + s_cnt[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    const double a = finish_reduce<Add>(psum, n, s_sum);
+    const unsigned long long b = finish_reduce<Add>(pcnt, n, s_cnt);
     if (threadIdx.x == 0) {
-        *sum = s_sum[0];
-        *cnt = s_cnt[0];
+        *sum = a;
+        *cnt = b;
     }
 }
 
@@ -279,10 +248,8 @@ extern "C" int sift3d_demons_force_launch(const float *d_F, int nx, int ny, int 
     p.tiles_x = (nx + DEM_TX - 1) / DEM_TX;
     p.tiles_z = (nz + DEM_K - 1) / DEM_K;
     const unsigned long long nt = (unsigned long long)p.tiles_x * ((ny + DEM_TY - 1) / DEM_TY) * p.tiles_z;
-    if (nt > 0xffffffffull - DEM_GRID) {
-        snprintf(g_err, sizeof(g_err), "sift3d_hip_demons_force: grid too large");
-        return SIFT3D_FAILURE;
-    }
+    if (nt > 0xffffffffull - DEM_GRID)
+        return launch_fail("sift3d_hip_demons_force", "grid too large");
     p.ntiles = (unsigned)nt;
     const unsigned grid = p.ntiles < DEM_GRID ? p.ntiles : DEM_GRID;
     hipStream_t st = (hipStream_t)stream;

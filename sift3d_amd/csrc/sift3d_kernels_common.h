@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -26,6 +27,40 @@ int fail(const char *what, hipError_t e, const char *file, int line);
     } while (0)
 
 #define LAUNCH_CHECK() HIPCHK(hipGetLastError())
+
+// ---- refusals of the device C ABI, before the first device call ----------------------------
+static inline int launch_fail(const char *fn, const char *why)
+{
+    snprintf(g_err, sizeof(g_err), "%s: %s", fn, why);
+    fprintf(stderr, "sift3d_amd: %s\n", g_err);
+    return SIFT3D_FAILURE;
+}
+
+static inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+static inline int check_dims(const char *fn, int nx, int ny, int nz)
+{
+    return nx <= 0 || ny <= 0 || nz <= 0 ? launch_fail(fn, "dimensions must be positive") : SIFT3D_SUCCESS;
+}
+
+static inline int check_interp(const char *fn, int interp)
+{
+    return interp != SIFT3D_AMD_INTERP_NEAREST && interp != SIFT3D_AMD_INTERP_LINEAR
+               ? launch_fail(fn, "unknown interpolation mode")
+               : SIFT3D_SUCCESS;
+}
+
+static inline int check_affine(const char *fn, const double *A)
+{
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(A[i]))
+            return launch_fail(fn, "the affine map is not finite");
+    return SIFT3D_SUCCESS;
+}
 
 // ---- small device helpers ------------------------------------------------------------------
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }

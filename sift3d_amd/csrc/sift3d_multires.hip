@@ -237,10 +237,8 @@ extern "C" int sift3d_restrict2_launch(const float *d_src, int nx, int ny, int n
     p.nx = nx; p.ny = ny; p.nz = nz;
     p.cx = (nx + 1) / 2; p.cy = (ny + 1) / 2; p.cz = (nz + 1) / 2;
     p.scale = scale;
-    if (!mr_tiles(p.cx, p.cy, p.cz, 2, RES_K, nc, p.g)) {
-        snprintf(g_err, sizeof(g_err), "sift3d_hip_restrict2: grid too large");
-        return SIFT3D_FAILURE;
-    }
+    if (!mr_tiles(p.cx, p.cy, p.cz, 2, RES_K, nc, p.g))
+        return launch_fail("sift3d_hip_restrict2", "grid too large");
     // 16-byte loads and 8-byte stores: every fine row 16-byte aligned, every coarse row 8-byte aligned
     const bool vec = nx % 4 == 0 && !((uintptr_t)d_src & 15) && !((uintptr_t)d_dst & 7);
     const unsigned grid = p.g.ntiles < MR_MAX_GRID ? p.g.ntiles : MR_MAX_GRID;
@@ -258,10 +256,8 @@ extern "C" int sift3d_field_prolong2_launch(const float *d_coarse, float *d_fine
     p.coarse = d_coarse; p.fine = d_fine;
     p.nx = nx; p.ny = ny; p.nz = nz;
     p.cx = (nx + 1) / 2; p.cy = (ny + 1) / 2; p.cz = (nz + 1) / 2;
-    if (!mr_tiles(nx, p.cy, nz, 4, PRO_K, 3, p.g)) {               // a lane owns 4 x of two fine rows
-        snprintf(g_err, sizeof(g_err), "sift3d_hip_field_prolong2: grid too large");
-        return SIFT3D_FAILURE;
-    }
+    if (!mr_tiles(nx, p.cy, nz, 4, PRO_K, 3, p.g))                 // a lane owns 4 x of two fine rows
+        return launch_fail("sift3d_hip_field_prolong2", "grid too large");
     const bool vec = nx % 4 == 0 && !((uintptr_t)d_fine & 15);
     const unsigned grid = p.g.ntiles < MR_MAX_GRID ? p.g.ntiles : MR_MAX_GRID;
     if (vec)
