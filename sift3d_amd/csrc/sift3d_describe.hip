@@ -1648,28 +1648,21 @@ int sift3d_hip_describe_wlut(const sift3d_hip_level *d_levels, int nlevels, cons
     return sift3d_hip_describe_wlut2(d_levels, nlevels, d_kp, n, d_hist, nullptr, d_wlut, stream);
 }
 
-static int dense_fail(const char *what, const char *why)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, why);
-    fprintf(stderr, "sift3d_amd: %s\n", g_err);
-    return SIFT3D_FAILURE;
-}
-
 int sift3d_hip_dense_bin(const float *d_src, int nx, int ny, int nz, double ux, double uy, double uz,
                          float *d_out, void *stream)
 {
     static const char what[] = "sift3d_hip_dense_bin";
     if (!d_src || !d_out)
-        return dense_fail(what, "NULL argument");
+        return launch_fail(what, "NULL argument");
     if (nx <= 0 || ny <= 0 || nz <= 0)
-        return dense_fail(what, "dimensions must be positive");
+        return launch_fail(what, "dimensions must be positive");
     if (!(std::isfinite(ux) && ux > 0 && std::isfinite(uy) && uy > 0 && std::isfinite(uz) && uz > 0))
-        return dense_fail(what, "units must be positive and finite");
+        return launch_fail(what, "units must be positive and finite");
     const size_t n = (size_t)nx * ny * nz;
     {
         const uintptr_t s0 = (uintptr_t)d_src, o0 = (uintptr_t)d_out;
         if (s0 < o0 + 12 * n * sizeof(float) && o0 < s0 + n * sizeof(float))
-            return dense_fail(what, "source and output overlap");
+            return launch_fail(what, "source and output overlap");
     }
     // (1.0f / (float) ux, IM_GET_GRAD_ISO, sift.c:143-145)
     const float iux = 1.0f / (float)ux, iuy = 1.0f / (float)uy, iuz = 1.0f / (float)uz;
@@ -1688,7 +1681,7 @@ int sift3d_hip_dense_bin(const float *d_src, int nx, int ny, int nz, double ux, 
 int sift3d_hip_dense_normalize(float *d_hist, size_t n, void *stream)
 {
     if (!d_hist)
-        return dense_fail("sift3d_hip_dense_normalize", "NULL argument");
+        return launch_fail("sift3d_hip_dense_normalize", "NULL argument");
     if (!n)
         return SIFT3D_SUCCESS;
     const bool vec = n % 4 == 0 && !((uintptr_t)d_hist & 15);
@@ -1714,13 +1707,13 @@ static int dense_rot(bool bin, const char *what, const float *d_src, int nx, int
                      double uz, double sigma, float *d_R, unsigned char *d_keep, float *d_out, void *stream)
 {
     if (!d_src || !d_R || (bin && !d_out))
-        return dense_fail(what, "NULL argument");
+        return launch_fail(what, "NULL argument");
     if (nx <= 0 || ny <= 0 || nz <= 0)
-        return dense_fail(what, "dimensions must be positive");
+        return launch_fail(what, "dimensions must be positive");
     if (!(std::isfinite(sigma) && sigma > 0))
-        return dense_fail(what, "sigma must be positive and finite");
+        return launch_fail(what, "sigma must be positive and finite");
     if (!(std::isfinite(ux) && ux > 0 && std::isfinite(uy) && uy > 0 && std::isfinite(uz) && uz > 0))
-        return dense_fail(what, "units must be positive and finite");
+        return launch_fail(what, "units must be positive and finite");
     DrWin W;
     W.ux = (float)ux; W.uy = (float)uy; W.uz = (float)uz;
     const double rad = 3.0 * sigma;                    // ori_rad_fctr, sift.c:936
@@ -1728,12 +1721,12 @@ static int dense_rot(bool bin, const char *what, const float *d_src, int nx, int
     W.sig2 = sigma * sigma;
     const double ex = rad / (double)W.ux + 2.0, ey = rad / (double)W.uy + 2.0, ez = rad / (double)W.uz + 2.0;
     if (!(W.ux > 0 && W.uy > 0 && W.uz > 0) || !(ex <= DR_MAXR && ey <= DR_MAXR && ez <= DR_MAXR))
-        return dense_fail(what, "the window is wider than 509 voxels on an axis");
+        return launch_fail(what, "the window is wider than 509 voxels on an axis");
     W.mx = (int)ex; W.my = (int)ey; W.mz = (int)ez;
     // expected window voxels: the sphere's volume in voxels
     const double win = 4.18879020478639 * (rad / W.ux) * (rad / W.uy) * (rad / W.uz) + 1.0;
     if (!(win <= DR_MAX_WIN))
-        return dense_fail(what, "the window holds more than 20000 voxels");
+        return launch_fail(what, "the window holds more than 20000 voxels");
     const size_t n = (size_t)nx * ny * nz;
     {
         auto ov = [](const void *a, size_t na, const void *b, size_t nb) {
@@ -1743,7 +1736,7 @@ static int dense_rot(bool bin, const char *what, const float *d_src, int nx, int
         const size_t fb = sizeof(float);
         if (ov(d_R, 9 * n * fb, d_src, n * fb) || (d_keep && (ov(d_keep, n, d_src, n * fb) || ov(d_keep, n, d_R, 9 * n * fb))) ||
             (bin && (ov(d_out, 12 * n * fb, d_src, n * fb) || ov(d_out, 12 * n * fb, d_R, 9 * n * fb))))
-            return dense_fail(what, "buffers overlap");
+            return launch_fail(what, "buffers overlap");
     }
     const float iux = 1.0f / W.ux, iuy = 1.0f / W.uy, iuz = 1.0f / W.uz;   // IM_GET_GRAD_ISO, sift.c:143-145
     const size_t ntiles = (size_t)((nx + DR_TX - 1) / DR_TX) * (size_t)((ny + DR_TY - 1) / DR_TY) * (size_t)nz;

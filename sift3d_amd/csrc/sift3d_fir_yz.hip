@@ -491,11 +491,8 @@ int sift3d_hip_fir_yz_u1(const float *d_src, float *d_dst, int nx, int ny, int n
     hipStream_t st = (hipStream_t)stream;
     const int hw = width / 2;
     if (!d_src || !d_dst || d_src == d_dst || nx < 4 || ny < 1 || nz < 1 || !(width & 1) || z_lo < 0 ||
-        z_hi > nz || off < 0 || off + nz > n_glob) {
-        snprintf(g_err, sizeof(g_err), "sift3d_hip_fir_yz_u1: invalid arguments");
-        fprintf(stderr, "sift3d_amd: %s\n", g_err);
-        return SIFT3D_FAILURE;
-    }
+        z_hi > nz || off < 0 || off + nz > n_glob)
+        return launch_fail("sift3d_hip_fir_yz_u1", "invalid arguments");
     // not covered -> the caller runs the y and z passes separately
     if (!sift3d_hip_fir_yz_u1_covers(d_src, d_dst, nx, ny, width, n_glob))
         return 1;

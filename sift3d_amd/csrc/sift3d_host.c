@@ -3,7 +3,7 @@
  * Implements the 27 public symbols of the reference library (the headers under include/sift3d/,
  * reference: sift3d/sift.h, sift3d/imutil.h) with the reference's object semantics,
  * parameter checks and error behaviour, and drives the detect / describe hot path
- * through the device-level C ABI of include/sift3d_amd.h (sift3d_kernels.hip).  There
+ * through the device-level C ABI of include/sift3d_amd.h (the sift3d_*.hip units).  There
  * is NO CPU fallback: without a HIP device the two hot entry points fail loudly.
  *
  * What lives where:

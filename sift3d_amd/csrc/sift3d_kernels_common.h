@@ -1,5 +1,5 @@
 // sift3d_kernels_common.h -- declarations shared by the translation units of the device code
-// (sift3d_kernels.hip; sift3d_fir_yz.hip, which is compiled with other optimiser settings).
+// (every sift3d_*.hip includes it first, so that the pragma below covers the whole unit).
 #ifndef SIFT3D_KERNELS_COMMON_H
 #define SIFT3D_KERNELS_COMMON_H
 
@@ -9,13 +9,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 // Part of the numerical contract: no fused multiply-add anywhere (see sift3d_kernels.hip).
 #pragma clang fp contract(off)
 
 #include "../../include/sift3d_amd.h"
 
-// ---- error plumbing (defined in sift3d_kernels.hip) ----------------------------------------
+// ---- error plumbing (defined in sift3d_device.hip) -----------------------------------------
 extern thread_local char g_err[512];
 int fail(const char *what, hipError_t e, const char *file, int line);
 
@@ -62,11 +63,85 @@ static inline int check_affine(const char *fn, const double *A)
     return SIFT3D_SUCCESS;
 }
 
+// ---- launch geometry of the streaming kernels -----------------------------------------------
+static inline int grid_for(size_t n, int per_thread)
+{
+    size_t b = (n / per_thread + 255) / 256;
+    if (b < 1)
+        b = 1;
+    if (b > 256 * 16)
+        b = 256 * 16; // ~16 blocks per CU, grid-stride beyond that
+    return (int)b;
+}
+
+// streaming reductions: few, long-running workgroups (one atomic each at the end)
+static inline int grid_reduce(size_t n)
+{
+    const int b = grid_for(n, 4);
+    return b < 256 * 4 ? b : 256 * 4;
+}
+
+// ---- run-time integer -> template argument --------------------------------------------------
+// dispatch_int<LO, HI>(v, f) calls f(std::integral_constant<int, v>{}) and returns true where LO <= v <= HI;
+// otherwise it calls nothing and returns false.  dispatch_int_or<LO, HI, ELSE> calls f with ELSE then.
+// What each site does with a value out of range is its own rule:
+//   fir_impl, x pass and sweep pass   fall to 8 (reached with 1 <= hw <= 8 only)
+//   launch_fir_dyad_generic           falls to <0>, the kernels with a run-time tap count
+//   launch_fir_dy_hw                  returns false: the caller goes on to the generic dyadic kernels
+//   the two DoG stacks                fall to 8 (n_gauss is checked against [2, 8] first)
+template <int LO, int HI, class F> static inline bool dispatch_int(int v, F &&f)
+{
+    if constexpr (LO <= HI) {
+        if (v != LO)
+            return dispatch_int<LO + 1, HI>(v, f);
+        f(std::integral_constant<int, LO>{});
+        return true;
+    }
+    return false;
+}
+
+template <int LO, int HI, int ELSE, class F> static inline void dispatch_int_or(int v, F &&f)
+{
+    if (!dispatch_int<LO, HI>(v, f))
+        f(std::integral_constant<int, ELSE>{});
+}
+
 // ---- small device helpers ------------------------------------------------------------------
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// max over the workgroup (256 threads) of non-negative floats, then ONE atomic per workgroup.
+// Same-address atomics serialise at the memory side (~20 ns each): one per wave cost the DoG
+// kernels 1.5 ms at 512^3.  NM maxima at once; non-negative floats order like their bit patterns.
+template <int NM>
+__device__ __forceinline__ void block_max_atomic(const float *m, unsigned *__restrict__ out)
+{
+    __shared__ float red[NM][4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < NM; k++) {
+        const float w = wave_max(m[k]);
+        if (lane == 0)
+            red[k][wave] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < NM) {
+        const float w = fmaxf(fmaxf(red[threadIdx.x][0], red[threadIdx.x][1]),
+                              fmaxf(red[threadIdx.x][2], red[threadIdx.x][3]));
+        if (w > 0.0f)
+            atomicMax(out + threadIdx.x, __float_as_uint(w));
+    }
+}
 
 // ---- 1-D interpolating FIR (convolve_sep_gen, imutil.c:742-861): shared types -----------------
 struct FirTaps {

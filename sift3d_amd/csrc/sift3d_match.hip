@@ -287,11 +287,8 @@ int sift3d_hip_nn2(const float *d_A, int nA, const float *d_B, int nB, int dim, 
 {
     hipStream_t st = (hipStream_t)stream;
     if (!d_A || !d_B || !d_j1 || !d_d1 || !d_d2 || !d_work || nA < 0 || nB < 0 || dim < KC || (dim % KC) ||
-        (((uintptr_t)d_A | (uintptr_t)d_B) & 15)) {
-        snprintf(g_err, sizeof(g_err), "sift3d_hip_nn2: invalid arguments");
-        fprintf(stderr, "sift3d_amd: %s\n", g_err);
-        return SIFT3D_FAILURE;
-    }
+        (((uintptr_t)d_A | (uintptr_t)d_B) & 15))
+        return launch_fail("sift3d_hip_nn2", "invalid arguments");
     if (!nA)
         return SIFT3D_SUCCESS;
     float *nrmA = d_work, *nrmB = d_work + nA;

@@ -82,6 +82,7 @@ def lib():
         "sift3d_hip_nn2": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
         "sift3d_hip_subtract_absmax": (C.c_int, [vp, vp, vp, C.c_size_t, vp, vp]),
         "sift3d_hip_dog_stack": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, vp, vp]),
+        "sift3d_hip_dogmax_stack": (C.c_int, [C.POINTER(vp), C.c_int, C.c_size_t, vp, vp]),
         "sift3d_hip_host_device_ptr": (vp, [vp]),
         "sift3d_hip_downsample2": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
         "sift3d_hip_extrema_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -834,6 +835,19 @@ def dog_stack(gauss, dogs, d_absmax):
     if rc == 1:
         return False
     _check(rc, "sift3d_hip_dog_stack")
+    return True
+
+
+def dogmax_stack(gauss, d_absmax):
+    """The maxima of dog_stack alone: d_absmax[k] = max(d_absmax[k], max |gauss[k] - gauss[k+1]|), no difference
+    stored.  Returns False when the kernel does not cover the case."""
+    n = len(gauss)
+    assert d_absmax.numel() >= n - 1
+    g = (C.c_void_p * n)(*[t.data_ptr() for t in gauss])
+    rc = lib().sift3d_hip_dogmax_stack(g, n, gauss[0].numel(), d_absmax.data_ptr(), current_stream())
+    if rc == 1:
+        return False
+    _check(rc, "sift3d_hip_dogmax_stack")
     return True
 
 

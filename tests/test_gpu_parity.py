@@ -138,6 +138,26 @@ def test_fir_fast_paths_vs_oracle(gpu, oracle_mod, shape):
                                               % (sigma, uf, ax))
 
 
+@pytest.mark.parametrize("shape", [(20, 20, 24),      # rows and planes of whole quads: the 16-byte kernels (V = 4)
+                                   (19, 21, 23),      # scalar kernels (V = 1)
+                                   (2, 3, 512)])      # rows of whole 512-float segments: k_fir_x_u1f (x pass only)
+def test_fir_every_half_width_vs_oracle(gpu, oracle_mod, shape):
+    """Every half width the launchers turn into a template argument (1 ... 8), and 9, which each of them has to
+    pass on to the next, more general kernel: random taps, the four tap spacings of the first four octaves,
+    every axis, bit-identical to the oracle."""
+    api, hip, torch = gpu
+    rng = np.random.default_rng(sum(shape))
+    vol = rng.standard_normal(shape).astype(np.float32)
+    for hw in range(1, 10):
+        taps = rng.standard_normal(2 * hw + 1).astype(np.float32)
+        for uf in (1.0, 0.5, 0.25, 0.125):
+            for ax in ((0,) if shape[2] == 512 else range(3)):
+                want, r = oracle_mod.fir_axis(vol, taps, ax, uf=np.float32(uf), mode=0)
+                assert r == 0
+                got = _fir_gpu(hip, torch, vol, taps, ax, np.float32(uf))
+                np.testing.assert_array_equal(got, want, err_msg="hw %d uf %g axis %d" % (hw, uf, ax))
+
+
 def test_fir_wider_than_the_tap_tables_vs_oracle(gpu, oracle_mod):
     """Filters of more than SIFT3D_HIP_MAX_TAPS = 65 taps (sigma0 above ~7: the reference accepts any sigma0,
     sift.c:553-565, half width ceil(3 sigma), imutil.c:1275-1277) take the literal kernel in chunks of 65 taps,
@@ -292,6 +312,27 @@ def test_scale_dog_downsample(gpu, oracle_mod):
     hip.absmax(z, mz)
     hip.scale(z, out, mz)  # all-zero input: no division (imutil.c:706-707)
     assert float(out.abs().max()) == 0.0
+
+
+def test_dog_stack_every_level_count(gpu):
+    """Every level count the two DoG stack kernels are instantiated for (2 ... 8 Gaussian levels): differences and
+    maxima bit-equal to float32 subtraction and max |.|."""
+    api, hip, torch = gpu
+    rng = np.random.default_rng(11)
+    levels = [rng.standard_normal(4096).astype(np.float32) for _ in range(8)]
+    d_levels = [torch.from_numpy(v).cuda() for v in levels]
+    assert all(t.data_ptr() % 16 == 0 for t in d_levels)
+    for n in range(2, 9):
+        want = [levels[k] - levels[k + 1] for k in range(n - 1)]
+        want_max = np.array([np.abs(w).max() for w in want], np.float32)
+        dd = [torch.full((4096,), float("nan"), device="cuda") for _ in range(n - 1)]
+        mm, mm2 = torch.zeros(n - 1, device="cuda"), torch.zeros(n - 1, device="cuda")
+        assert hip.dog_stack(d_levels[:n], dd, mm)
+        assert hip.dogmax_stack(d_levels[:n], mm2)
+        for k in range(n - 1):
+            np.testing.assert_array_equal(dd[k].cpu().numpy(), want[k], err_msg="%d levels, difference %d" % (n, k))
+        np.testing.assert_array_equal(mm.cpu().numpy(), want_max, err_msg="%d levels, dog_stack" % n)
+        np.testing.assert_array_equal(mm2.cpu().numpy(), want_max, err_msg="%d levels, dogmax_stack" % n)
 
 
 # ----------------------------------------------------------------------------------------
