@@ -448,6 +448,84 @@ SIFT3D_AMD_API int sift3d_amd_image_bspline_warp_field(const sift3d_image *src, 
                                                        sift3d_image *dst);
 
 /* ------------------------------------------------------------------------ */
+/* Similarity measures: MSD, NCC, joint histogram, mutual information, Dice  */
+/* ------------------------------------------------------------------------ */
+/* How well a fixed volume F[oz][oy][ox] agrees with a moving volume M[nz][ny][nx] seen through a pull map, in one
+ * gather-and-reduce pass over the fixed grid: no warped volume is written.  No upstream counterpart: PARITY UNPINNED,
+ * pinned to this contract (tests/similarity_restatement.py).
+ *
+ * The pull map is a 3 x 4 affine, q_d = A[d][0] x + ((A[d][1] y + A[d][2] z) + A[d][3]) (double, this order, unfused:
+ * "Resampling"), or a displacement field u[3][oz][oy][ox], q_d = (double) p_d + (double) u_d(p) ("Displacement
+ * fields").  interp is LINEAR or NEAREST; inside test and sample are sift3d_hip_warp_affine's / _warp_field's, word
+ * for word.  Per fixed voxel p:
+ *   - q outside the moving grid (a NaN is outside): the voxel is skipped and does not count;
+ *   - else f = F(p) and m = the sample: bit for bit what the warp entries write at p.
+ * Both volumes must be finite.
+ * Bins.  B = bins, 2 <= B <= SIFT3D_AMD_SIMILARITY_MAX_BINS (any B, not only powers of two), and per volume a range
+ * lo < hi (finite floats).  All float, unfused:
+ *     s = (float) B / (hi - lo)            once on the host (it must be finite: a range too narrow for float is refused)
+ *     t = (v - lo) * s
+ *     b = t < 0 ? 0 : t >= B ? B - 1 : (int) t
+ * so v == hi lands in the last bin and values past either end clamp into the end bins.
+ * Outputs of a call:
+ *   hist [B][B] uint64, indexed [b_f][b_m]: the exact counts (integer adds: bit-exact however they are reduced);
+ *   stats, SIFT3D_AMD_SIMILARITY_STATS_BYTES, 8-byte aligned:
+ *     bytes 0-7 uint64 count n; then six doubles: sum f, sum m, sum f f, sum m m, sum f m, sum d d, where the products
+ *     are formed in double from the floats (exact) and d = f - m is a float subtraction first (as demons' d_c).
+ *     The sums are per-lane, then per-workgroup partials (one slot per workgroup of a grid of
+ *     min(tiles, SIFT3D_AMD_SIMILARITY_GRID) workgroups, whatever the device; a tile is 64 x 4 x 4 voxels), then the
+ *     slots in a fixed order: a call repeats its bits, and the bits depend on the shapes only.
+ * Both buffers are zeroed / written on `stream` by the call itself.  Every workgroup counts in 32-bit words of its
+ * own before it adds them to hist: it visits at most ceil(tiles / grid) tiles of 1024 voxels, below 2^32 voxels for
+ * every grid the tiling accepts (tiles < 2^32 - 2^20), so no counter wraps.
+ * The entries are asynchronous on `stream`, allocate nothing, use 64-bit offsets and check their arguments before any
+ * device call: -1 on NULL pointers, dims <= 0, bins out of range, a range that is not finite, empty (lo >= hi) or so
+ * narrow that s overflows, an unknown interp, a non-finite A, a misaligned buffer (hist, stats, work: 8 bytes; the
+ * rest 4), an output that overlaps an input, the work buffer or another output, a grid with too many tiles.
+ * d_work: sift3d_amd_similarity_work_bytes() bytes, 8-byte aligned.
+ *
+ * Measures (host, double).  From hist and stats, with n = count (everything NaN when n == 0):
+ *   msd = S_dd / n
+ *   ncc = (S_fm - S_f S_m / n) / sqrt((S_ff - S_f S_f / n) * (S_mm - S_m S_m / n)), 0 when either variance is <= 0
+ *   marginals  r[i] = sum over j = 0 .. B-1 of hist[i][j], c[j] = sum over i = 0 .. B-1 of hist[i][j], in uint64
+ *   N = sum over i of r[i] (uint64; equal to n for the histogram of a call)
+ *   entropy H(counts) = acc after: acc = 0.0; for each count k in order, k != 0: p = (double) k / (double) N,
+ *                       acc = acc - p * log(p)        (natural log, empty bins skipped)
+ *   H_f = H(r[0 .. B-1]), H_m = H(c[0 .. B-1]), H_fm = H(hist in row-major order)
+ *   mi = (H_f + H_m) - H_fm,  nmi = (H_f + H_m) / H_fm, 0 when H_fm is 0.
+ * Label overlap needs no kernel of its own: with NEAREST, lo = 0, hi = L, B = L, s is exactly 1 and hist is the
+ * confusion matrix of the integer labels 0 .. L-1 (fixed label = row).  For label k, row_k = r[k], col_k = c[k]:
+ *   dice_k = 2 h_kk / (row_k + col_k), jaccard_k = h_kk / (row_k + col_k - h_kk): the integers exactly, one double
+ *   division each, NaN for a label absent from both; vol_f[k] = row_k, vol_m[k] = col_k. */
+#define SIFT3D_AMD_SIMILARITY_MAX_BINS 128
+#define SIFT3D_AMD_SIMILARITY_GRID 2048            /* workgroups (and partial slots) of a call, at most */
+#define SIFT3D_AMD_SIMILARITY_STATS_BYTES 56
+typedef struct {
+    uint64_t n;
+    double msd, ncc, mi, nmi, entropy_fixed, entropy_moving, entropy_joint;
+} sift3d_amd_similarity;
+/* bytes of d_work for a call with these arguments (0 for dims <= 0 or bins out of range) */
+SIFT3D_AMD_API size_t sift3d_amd_similarity_work_bytes(int ox, int oy, int oz, int bins);
+/* d_F [oz][oy][ox], d_M [nz][ny][nx], d_hist [bins][bins] uint64, d_stats the record above */
+SIFT3D_AMD_API int
+sift3d_hip_similarity_affine(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                             const double *A /*12*/, int interp, int bins, float lo_f, float hi_f, float lo_m,
+                             float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream);
+/* d_field [3][oz][oy][ox] */
+SIFT3D_AMD_API int
+sift3d_hip_similarity_field(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                            const float *d_field, int interp, int bins, float lo_f, float hi_f, float lo_m,
+                            float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream);
+/* host only: hist [bins][bins] and the stats record, both on the host.  -1 on NULL pointers or bins out of range. */
+SIFT3D_AMD_API int
+sift3d_amd_similarity_measures(const uint64_t *hist, int bins, const void *stats, sift3d_amd_similarity *out);
+/* host only: hist [L][L] a confusion matrix, 1 <= L <= SIFT3D_AMD_SIMILARITY_MAX_BINS; dice, jaccard (double [L])
+ * and vol_f, vol_m (uint64 [L]) may each be NULL.  -1 on a NULL hist or L out of range. */
+SIFT3D_AMD_API int
+sift3d_amd_label_overlap(const uint64_t *hist, int L, double *dice, double *jaccard, uint64_t *vol_f,
+                         uint64_t *vol_m);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -27,6 +27,13 @@ NUM_TIMINGS = 10 + 2 * TIMED_BLURS + 4
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+_u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
+
+
+class _Measures(C.Structure):                               # sift3d_amd_similarity
+    _fields_ = [("n", C.c_uint64)] + [(k, C.c_double) for k in ("msd", "ncc", "mi", "nmi", "entropy_fixed",
+                                                                  "entropy_moving", "entropy_joint")]
+
 
 _bound = None
 
@@ -113,6 +120,8 @@ def lib():
         "sift3d_amd_bspline_prefilter": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
         "sift3d_amd_image_bspline_warp_affine": (C.c_int, [vp, _f64p, C.c_float, vp]),
         "sift3d_amd_image_bspline_warp_field": (C.c_int, [vp, _f32p, C.c_float, vp]),
+        "sift3d_amd_similarity_measures": (C.c_int, [_u64p, C.c_int, vp, C.POINTER(_Measures)]),
+        "sift3d_amd_label_overlap": (C.c_int, [_u64p, C.c_int, _f64p, _f64p, _u64p, _u64p]),
         "sift3d_amd_image_dense_descriptors": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_image_dense_descriptors_rotate": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_device_available": (C.c_int, []),
@@ -880,6 +889,119 @@ def resample_cubic(volume, transform, out_shape=None, fill=0.0, prefiltered=Fals
         if lib().sift3d_amd_image_bspline_warp_field(src.h, f.reshape(-1), float(fill), dst.h) != 0:
             raise RuntimeError("sift3d_amd_image_bspline_warp_field failed")
     return dst if isinstance(volume, Image) else dst.data().copy()
+
+
+# ---- similarity measures ---------------------------------------------------------------------------
+Similarity = collections.namedtuple("Similarity",
+                                    "count msd ncc mi nmi entropy_fixed entropy_moving entropy_joint joint")
+LabelOverlap = collections.namedtuple("LabelOverlap", "confusion dice jaccard volume_fixed volume_moving")
+SIMILARITY_MAX_BINS = 128
+
+
+def similarity_measures(hist, stats):
+    """The measures of a joint histogram [B, B] (counts, indexed [b_fixed, b_moving]) and a moments record (count,
+    [sum f, sum m, sum f f, sum m m, sum f m, sum (f - m)^2]) by sift3d_amd_similarity_measures (host, double):
+    Similarity(count, msd, ncc, mi, nmi, entropy_fixed, entropy_moving, entropy_joint, joint = the histogram as
+    int64).  Everything but the count is NaN when the count is 0."""
+    h = np.ascontiguousarray(hist).astype(np.uint64)
+    if h.ndim != 2 or h.shape[0] != h.shape[1]:
+        raise ValueError("similarity_measures: the histogram must be [B, B]")
+    count, sums = stats
+    rec = np.zeros(7, np.float64)
+    rec[:1].view(np.uint64)[0] = int(count)
+    rec[1:] = np.asarray(sums, np.float64).reshape(6)
+    out = _Measures()
+    if lib().sift3d_amd_similarity_measures(h.reshape(-1), h.shape[0], rec.ctypes.data, C.byref(out)) != 0:
+        raise RuntimeError("sift3d_amd_similarity_measures failed")
+    return Similarity(int(out.n), out.msd, out.ncc, out.mi, out.nmi, out.entropy_fixed, out.entropy_moving,
+                      out.entropy_joint, h.astype(np.int64))
+
+
+def _similarity_volume(v, what, name, device=None):
+    """a volume as a CUDA float32 tensor [nz, ny, nx]: a tensor as it is, an Image or an array uploaded"""
+    import torch
+    if not _torch_tensor(v):
+        a = np.ascontiguousarray(v.data() if isinstance(v, Image) else v, np.float32)
+        if a.ndim != 3:
+            raise ValueError("%s: %s must be a volume [nz, ny, nx]" % (what, name))
+        if not device_available():
+            raise RuntimeError("%s: no HIP device is available; this library has no CPU path" % what)
+        v = torch.from_numpy(a).to(device if device is not None else "cuda")
+    _volume_tensor(v, what, name)
+    return v
+
+
+def _similarity_transform(transform, fixed, what):
+    """None, a 3 x 4 float64 array, or a CUDA field on the fixed grid (a TPS exported, a host field uploaded)"""
+    import torch
+    if transform is None or _torch_tensor(transform):
+        return transform
+    if isinstance(transform, TPS):
+        return displacement_field(transform, tuple(fixed.shape), fixed.device)
+    A = _affine_or_none(transform)
+    if A is not None:
+        return A
+    return torch.from_numpy(_host_field(transform, what)).to(fixed.device)
+
+
+def _own_range(v, given):
+    """(lo, hi) as given, else the volume's own min and max (one host synchronisation); hi = lo + 1 when constant"""
+    import torch
+    if given is not None:
+        lo, hi = given
+        return float(lo), float(hi)
+    lo, hi = (float(t) for t in torch.aminmax(v))
+    return (lo, hi) if hi > lo else (lo, lo + 1.0)
+
+
+def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fixed=None, range_moving=None):
+    """How well `fixed` agrees with `moving` seen through a pull map, in one pass on the device (contract:
+    include/sift3d_amd.h, "Similarity measures"): the fixed voxels whose sample falls inside `moving` give
+    Similarity(count, msd, ncc, mi, nmi, entropy_fixed, entropy_moving, entropy_joint, joint [bins, bins] int64
+    indexed [b_fixed, b_moving]); mutual information and the entropies in nats from the joint histogram.
+    transform: None (the identity; equal shapes), a 3 x 4 affine pull map, a TPS (exported with
+    displacement_field) or a displacement field [3, oz, oy, ox] on the fixed grid.  The volumes are torch CUDA
+    float32 tensors [nz, ny, nx], or Images / arrays, which are uploaded.  A range left None is that volume's own
+    min and max, at the cost of one host synchronisation (a constant volume gets hi = lo + 1); values outside a
+    given range count in the end bins.  Reads the result, so it waits for torch's current stream."""
+    from . import hip
+    F = _similarity_volume(fixed, "similarity", "fixed")
+    M = _similarity_volume(moving, "similarity", "moving", F.device)
+    T = _similarity_transform(transform, F, "similarity")
+    hist, stats = hip.similarity(F, M, T, bins, _own_range(F, range_fixed), _own_range(M, range_moving), interp)
+    return similarity_measures(hist.cpu().numpy(), hip.similarity_stats(stats))
+
+
+def label_overlap(labels_fixed, labels_moving, transform=None, num_labels=None):
+    """Overlap of two label volumes (float-valued integers 0 .. L-1, as warp_field(..., interp="nearest") takes
+    them), the moving one seen through `transform` (as similarity's) with nearest sampling:
+    LabelOverlap(confusion [L, L] int64 indexed [fixed label, moving label], dice [L], jaccard [L] (NaN for a label
+    absent from both), volume_fixed [L], volume_moving [L] in voxels), over the fixed voxels that sample inside the
+    moving volume.  num_labels None: the largest label of either volume + 1 (one host synchronisation).  Labels past
+    L - 1 count as L - 1.  At most 128 labels."""
+    from . import hip
+    F = _similarity_volume(labels_fixed, "label_overlap", "labels_fixed")
+    M = _similarity_volume(labels_moving, "label_overlap", "labels_moving", F.device)
+    T = _similarity_transform(transform, F, "label_overlap")
+    L = int(num_labels) if num_labels is not None else int(max(float(F.max()), float(M.max()))) + 1
+    L = max(L, 2)
+    if L > SIMILARITY_MAX_BINS:
+        raise ValueError("label_overlap: at most %d labels, not %d" % (SIMILARITY_MAX_BINS, L))
+    hist, _ = hip.similarity(F, M, T, L, (0.0, float(L)), (0.0, float(L)), "nearest")
+    return label_overlap_measures(hist.cpu().numpy())
+
+
+def label_overlap_measures(confusion):
+    """LabelOverlap of a confusion matrix [L, L] (sift3d_amd_label_overlap; host)"""
+    h = np.ascontiguousarray(confusion).astype(np.uint64)
+    if h.ndim != 2 or h.shape[0] != h.shape[1]:
+        raise ValueError("label_overlap_measures: the confusion matrix must be [L, L]")
+    L = h.shape[0]
+    dice, jac = np.empty(L, np.float64), np.empty(L, np.float64)
+    vf, vm = np.empty(L, np.uint64), np.empty(L, np.uint64)
+    if lib().sift3d_amd_label_overlap(h.reshape(-1), L, dice, jac, vf, vm) != 0:
+        raise RuntimeError("sift3d_amd_label_overlap failed")
+    return LabelOverlap(h.astype(np.int64), dice, jac, vf.astype(np.int64), vm.astype(np.int64))
 
 
 # ---- dense descriptors: a 12-bin gradient histogram per voxel ------------------------------------

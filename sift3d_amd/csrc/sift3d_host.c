@@ -2531,3 +2531,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* cubic B-spline resampling: prefilter and 64-tap sampling */
 #include "sift3d_bspline.c"
+
+/* similarity measures: joint histogram, moments, and the measures and label overlap computed from them */
+#include "sift3d_similarity.c"

@@ -115,6 +115,13 @@ def lib():
                                                      C.POINTER(C.c_double), C.c_float, vp]),
         "sift3d_hip_bspline_warp_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
                                                     C.c_int, vp, C.c_float, vp]),
+        "sift3d_amd_similarity_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_similarity_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_double), C.c_int, C.c_int, C.c_float, C.c_float,
+                                                   C.c_float, C.c_float, vp, vp, vp, vp]),
+        "sift3d_hip_similarity_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                                  C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp,
+                                                  vp, vp]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -445,6 +452,72 @@ def bspline_warp_field(coef, dst, field, fill=0.0):
                                                dst.data_ptr(), float(fill), current_stream()),
            "sift3d_hip_bspline_warp_field")
     return dst
+
+
+# ---- similarity measures (contract: include/sift3d_amd.h, "Similarity measures") ------------------------------
+SIMILARITY_MAX_BINS = 128
+SIMILARITY_GRID = 2048
+SIMILARITY_STATS_BYTES = 56
+
+
+def similarity_stats(stats):
+    """The record of similarity() on the host, waiting for the stream: (count, float64 [6] = the sums of f, m, f f,
+    m m, f m and (f - m)^2)."""
+    import torch
+    raw = stats.view(torch.uint8)[:SIMILARITY_STATS_BYTES].cpu().numpy()
+    return int(raw[:8].view(np.uint64)[0]), raw[8:].view(np.float64).copy()
+
+
+def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=None, work=None):
+    """The joint histogram and moments of the fixed volume F [oz, oy, ox] and the moving volume M [nz, ny, nx] seen
+    through a pull map (sift3d_hip_similarity_affine / _field), torch CUDA float32 contiguous, on torch's current
+    stream.  transform: a 3 x 4 affine pull map, a field tensor [3, oz, oy, ox], or None: the identity, which needs
+    equal shapes.  range_f, range_m: (lo, hi) of the bins.  Returns (hist int64 [bins, bins] indexed [b_f, b_m],
+    stats): stats is the device record, read with similarity_stats (which waits for the stream), as reading hist
+    does.  hist, work: the caller's buffers (int64 [bins, bins]; sift3d_amd_similarity_work_bytes bytes)."""
+    import torch
+    for t in (F, M):
+        _tensor(t, "similarity: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    mode = _interp(interp)
+    bins = int(bins)
+    if not 2 <= bins <= SIMILARITY_MAX_BINS:
+        raise ValueError("similarity: bins must be in [2, %d]" % SIMILARITY_MAX_BINS)
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    field = None
+    if transform is None:
+        if F.shape != M.shape:
+            raise ValueError("similarity: transform=None needs volumes of one shape, not %s and %s"
+                             % (tuple(F.shape), tuple(M.shape)))
+        transform = np.eye(3, 4)
+    if isinstance(transform, torch.Tensor):
+        field = transform
+        _tensor(field, "similarity: a field must be a contiguous float32 CUDA tensor [3, oz, oy, ox] on F's grid",
+                shape=(3, oz, oy, ox))
+        _same_device("similarity", F, M, field)
+    else:
+        a = np.ascontiguousarray(transform, np.float64)
+        if a.shape not in ((3, 4), (12,)):
+            raise ValueError("similarity: transform must be a 3 x 4 affine pull map, a field tensor or None")
+        a = a.reshape(12)
+        _same_device("similarity", F, M)
+    if hist is None:
+        hist = torch.empty((bins, bins), dtype=torch.int64, device=F.device)
+    _tensor(hist, "similarity: hist must be a contiguous int64 CUDA tensor [bins, bins] on F's device",
+            shape=(bins, bins), device=F.device, dtype="int64")
+    need = lib().sift3d_amd_similarity_work_bytes(ox, oy, oz, bins)
+    work = _work(work, (need + 3) // 4, F, "similarity")
+    stats = torch.empty(SIMILARITY_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
+    (lo_f, hi_f), (lo_m, hi_m) = ((float(np.float32(v)) for v in r) for r in (range_f, range_m))
+    tail = (mode, bins, lo_f, hi_f, lo_m, hi_m, hist.data_ptr(), stats.data_ptr(), work.data_ptr(), current_stream())
+    if field is None:
+        _check(lib().sift3d_hip_similarity_affine(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
+                                                  a.ctypes.data_as(C.POINTER(C.c_double)), *tail),
+               "sift3d_hip_similarity_affine")
+    else:
+        _check(lib().sift3d_hip_similarity_field(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
+                                                 field.data_ptr(), *tail), "sift3d_hip_similarity_field")
+    return hist, stats
 
 
 def _dense_args(src, out, what):
