@@ -1,17 +1,17 @@
 """Candidate-list overflow (-m gpu): the detector starts from a candidate list of 2^18 records; a volume with more
-extrema than that is swept again with the list grown to count + count // 4 + 1024 (sift3d_host.c,
+extrema than that is swept again with the list grown to count + count // 4 + 1024 (sift3d_detect.c,
 detect_on_device; the slab driver's own loop is in tests/test_gpu_sharded.py).  The retry must not change a bit.
 
 Every case runs three times: the GPU with a capacity forced by sift3d_amd_detector_set_candidate_capacity, the
 GPU from the default capacity (which does not overflow), and the oracle.  The capacities are derived from the
 oracle's counts -- n candidates, n0 of them in octave 0 -- so that each of the retry's branches is reached:
 
-- default schedule ("split": `side` and `overlap`, sift3d_host.c:1674-1676, 1890): octave 0's candidates are
+- default schedule ("split": `side` and `overlap`, sift3d_detect.c: detect_begin, build_pyramid): octave 0's candidates are
   emitted and oriented while the smaller octaves are still swept.  A capacity below n0 stops it before the
   orientation (count_a > cap); one in [n0, n) lets octave 0 be oriented, and its records copied, before the
   total turns out not to fit (count_a <= cap < count).  Attempt 1 takes the joined path.
 - per-octave path (`side` == 0: cuboid extrema, num_kp_levels != 3, an octave whose x size is not a multiple of 4):
-  one count after all octaves' emissions, dog_free[o] (sift3d_host.c:1829-1860) choosing the DoG-free sweep or
+  one count after all octaves' emissions, dog_free[o] (sift3d_detect.c: dog_stage) choosing the DoG-free sweep or
   the stored DoG levels per octave.
 """
 import numpy as np
@@ -36,7 +36,7 @@ def gpu():
 
 
 def grown(n):
-    """The capacity a detect of n candidates grows an overflowing list to (sift3d_host.c, detect_on_device)."""
+    """The capacity a detect of n candidates grows an overflowing list to (sift3d_detect.c, extrema_stage)."""
     return n + n // 4 + 1024
 
 
@@ -72,7 +72,7 @@ class Ref:
         self.n0 = int((cand["o"] == 0).sum())
         self.num_octaves = o.num_octaves
         # the split schedule: default keypoint levels, no cuboid extrema, every octave's rows whole quads (`side`,
-        # sift3d_host.c:1674-1676); else the per-octave path
+        # sift3d_detect.c: detect_begin); else the per-octave path
         nx = vol.shape[2]
         self.split = (not kw.get("cuboid_extrema") and kw.get("num_kp_levels", 3) == 3 and self.num_octaves > 1 and
                       all((nx >> o) % 4 == 0 for o in range(self.num_octaves)))
@@ -181,7 +181,7 @@ def run_case(gpu, oracle_mod, vol, kw, split, est=False, **opts):
 
 
 def split_precondition(vol, est):
-    """On the split schedule octave 0 takes EST_OCTAVE (its dogmax gathered by the sweep, sift3d_host.c:1833)
+    """On the split schedule octave 0 takes est_octave (its dogmax gathered by the sweep, sift3d_detect.c)
     when it holds at least 2^21 voxels."""
     assert (vol.size >= 1 << 21) == est
 

@@ -457,14 +457,25 @@ def test_detect_describe_golden(gpu, oracle_mod, name):
 
 @pytest.mark.parametrize("n,gen", [(96, "survey"), (160, "lattice"), ((100, 72, 90), "survey"),
                                    ((130, 126, 122), "lattice"),    # no dimension a multiple of 4
-                                   ((320, 72, 64), "lattice")])     # rows of 1.25 256-voxel extrema tiles
+                                   ((320, 72, 64), "lattice"),      # rows of 1.25 256-voxel extrema tiles
+                                   # ONE octave (smallest side 8..15: one chain, no side streams), rows of whole
+                                   # quads (DoG-free sweep) and ragged ones (stored DoG levels)
+                                   ((12, 16, 20), "noise"), ((9, 13, 15), "noise")])
 def test_detect_describe_vs_oracle(gpu, oracle_mod, n, gen):
     api, hip, torch = gpu
-    vol = oracle_mod.synth_survey(n) if gen == "survey" else oracle_mod.synth_lattice(n, seed=3)
-    det, kp, rc = _run_api(api, vol, device_input=True)
+    kw = {}
+    if gen == "noise":
+        # white noise under the default scales leaves 2..9 candidates in volumes this small, whatever the
+        # threshold: finer scales (same level count, same schedule) give the oracle 183 and 75 keypoints
+        vol = np.random.default_rng(sum(n)).random(n, dtype=np.float32)
+        kw = dict(peak_thresh=0.02, sigma0=0.7, sigma_n=0.3)
+    else:
+        vol = oracle_mod.synth_survey(n) if gen == "survey" else oracle_mod.synth_lattice(n, seed=3)
+    det, kp, rc = _run_api(api, vol, params=kw, device_input=True)
     assert rc == 0
-    o = oracle_mod.Oracle()
+    o = oracle_mod.Oracle(**kw)
     assert o.detect(vol) == 0
+    assert o.num_octaves == 1 or gen != "noise"
     for oc in range(o.num_octaves):
         for s in range(-1, 5):
             np.testing.assert_array_equal(det.level(0, oc, s), o.level(0, oc, s)[0],
@@ -801,7 +812,7 @@ def test_dogmax_gathered_by_the_sweep_equals_its_own_pass(gpu, oracle_mod, case)
         assert det.detect_keypoints(api.Image.from_array(vol, units=units), kp) == 0
         got[own_pass] = (det.num_candidates(), kp.records(), det.dogmax())
         if cap is not None:
-            # the retry ran: the list was grown to count + count / 4 + 1024 (sift3d_host.c, detect_on_device)
+            # the retry ran: the list was grown to count + count / 4 + 1024 (sift3d_detect.c, extrema_stage)
             n = det.num_candidates()
             assert n > cap and det.candidate_capacity() == n + n // 4 + 1024
     assert got[True][0] == got[False][0] and len(got[True][1]) == len(got[False][1])
