@@ -1027,6 +1027,18 @@ sift3d_hip_fir_yz_u1(const float *d_src, float *d_dst, int nx, int ny, int nz, c
 SIFT3D_AMD_API int sift3d_hip_fir_yz_u1_covers(const float *d_src, const float *d_dst, int nx, int ny,
                                                int width, int n_glob);
 
+/* A whole blur of a unit-spaced volume in one launch: dst = FIR_z(FIR_y(FIR_x(src))) over all planes,
+ * bit-identical to sift3d_hip_fir (axis 0) followed by sift3d_hip_fir_yz_u1, without either intermediate
+ * touching HBM.  d_scale_max (or NULL): the blur of src / *d_scale_max as sift3d_hip_fir_x_scaled forms it.
+ * Returns SIFT3D_SUCCESS, SIFT3D_FAILURE, or 1 -- nothing done -- when the configuration is not covered. */
+SIFT3D_AMD_API int
+sift3d_hip_fir_xyz(const float *d_src, float *d_dst, int nx, int ny, int nz, const float *taps, int width,
+                   const float *d_scale_max, void *stream);
+/* 1 when sift3d_hip_fir_xyz covers the blur: tap spacing 1 on all three axes (uf_*: the passes' unit factors),
+ * nx % 64 == 0, ny % 64 == 0, ny >= 128, an odd width <= 17, distinct 16-byte aligned volumes. */
+SIFT3D_AMD_API int sift3d_hip_fir_xyz_covers(const float *d_src, const float *d_dst, int nx, int ny, int nz,
+                                             int width, float uf_x, float uf_y, float uf_z);
+
 /* im_subtract (imutil.c:719-739) fused with the dogmax scan of detect_extrema
  * (sift.c:821-826): dst = a - b and *d_absmax = max(*d_absmax, max|dst|).
  * d_absmax may be NULL. */

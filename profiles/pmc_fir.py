@@ -11,6 +11,9 @@ directories:
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_pyr_fetch -- python3 profiles/pmc_fir.py --pyramid
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_pyr_write -- python3 profiles/pmc_fir.py --pyramid
     python3 profiles/pmc_fir.py --parse <fetch> <write> <pyr fetch> <pyr write> > profiles/traffic.json
+
+The octave-0 blurs of 5 to 11 taps are one k_fir_xyz_dma launch in the pipeline: --parse stores that launch's bytes
+under the k_fir_yz_dma<...> key bench.py looks up for the slot, with "launched" naming the kernel.
 """
 import csv
 import glob
@@ -29,6 +32,8 @@ def _require_built():
     if not os.path.exists(lib):
         sys.exit("%s is missing -- build first: python3 -c \"from sift3d_amd import _native; "
                  "_native.build()\"" % lib)
+
+FUSED_HW = (2, 3, 4, 5)
 
 SIG = [0.5387011637869722, 0.9732939207323564, 1.2262734984654078, 1.5450077936447955,
        1.9465878414647133, 2.4525469969308156]
@@ -52,6 +57,8 @@ def run(n=512, reps=3):
                 hip.fir(src, dst, ax, taps)
         for _ in range(reps):
             hip.fir_yz(src, dst, taps)
+        for _ in range(reps):
+            hip.fir_xyz(src, dst, taps)
     torch.cuda.synchronize()
 
 
@@ -123,10 +130,18 @@ def parse(fetch_dir, write_dir, n=512):
         w = wr.get((k, gx), [0.0])
         fetch_b = 2.0 * 1024.0 * sum(v) / len(v)
         write_b = 1024.0 * sum(w) / len(w)
-        alg = (16 if "yz" in k else 8) * n ** 3
+        alg = (24 if "xyz" in k else 16 if "yz" in k else 8) * n ** 3
         res[k] = dict(fetch_bytes=round(fetch_b), write_bytes=round(write_b),
                       hbm_bytes=round(fetch_b + write_b), algorithmic_bytes=alg,
                       ratio=round((fetch_b + write_b) / float(alg), 3), dispatches=len(v))
+    # bench.py labels the y+z timing slot of a blur k_fir_yz_dma<HW, TY> and looks its bytes up under that name; where
+    # the pipeline launches k_fir_xyz_dma in that slot (FUSED_HW: the table FIR_XYZ_WINS of sift3d_detect.c) the
+    # key carries the bytes of THAT launch, says so in "launched", and keeps the pair's y+z bytes beside them
+    for hw in FUSED_HW:
+        ty = 64 if hw <= 2 else 32
+        slot, one = "k_fir_yz_dma<%d, %d>" % (hw, ty), "k_fir_xyz_dma<%d, %d, false>" % (hw, ty)
+        if one in res:
+            res[slot] = dict(res[one], launched=one, yz_pass_hbm_bytes=res.get(slot, {}).get("hbm_bytes"))
     return res
 
 

@@ -120,6 +120,16 @@ static int ensure_dog_octave(sift3d_detector *d, int o)
     return SIFT3D_SUCCESS;
 }
 
+/* Half widths (bit hw) at which one k_fir_xyz_dma launch beats k_fir_x_u1f + k_fir_yz_dma inside a pyramid
+ * build, the first blur -- which divides by the image's maximum -- included; volumes below FIR_XYZ_MIN_VOXELS
+ * keep the pair: at 128^3 it is faster at every width (profiles/microbench/fir_xyz_mi355x.txt). */
+#define FIR_XYZ_WINS 0x3Cu
+#define FIR_XYZ_MIN_VOXELS ((size_t)256 * 256 * 256)
+static int fir_xyz_wins(int hw, size_t voxels)
+{
+    return hw >= 1 && hw <= 8 && ((FIR_XYZ_WINS >> hw) & 1) && voxels >= FIR_XYZ_MIN_VOXELS;
+}
+
 /* One FIR pass of a blur along `axis` over the whole volume; d_scale_max (x pass only, else NULL): of
  * src / *d_scale_max.  Returns what the launch returns (the scaled x pass: 1 when it cannot do that). */
 static int fir_pass(const float *src, float *dst, const int *dims, const double *lu, const filter_t *f, int axis,
@@ -135,8 +145,10 @@ static int fir_pass(const float *src, float *dst, const int *dims, const double 
     return d_scale_max ? sift3d_hip_fir_x_scaled(&a, d_scale_max, stream) : sift3d_hip_fir(&a, stream);
 }
 
-/* apply_Sep_FIR_filter (imutil.c:1127-1206) on the device: x, y, z passes, the two
- * intermediates in scratch volumes, no permute copies.  dst may be src.  d (may be NULL: no timing)
+/* apply_Sep_FIR_filter (imutil.c:1127-1206) on the device: x, y, z passes, no permute copies.  Octave 0 of
+ * a pyramid (tap spacing 1): ONE launch for the narrow filters on large volumes (fir_xyz_wins: no intermediate
+ * leaves the chip), else the x pass into tmp_a and the fused y+z launch; other spacings: three passes with the
+ * two intermediates in the scratch volumes.  dst may be src.  d (may be NULL: no timing)
  * holds the events of the timed blurs; slot < 0 times nothing */
 /* d_scale_max (first blur of the pyramid only, else NULL): the blur of src / *d_scale_max -- im_scale folded
  * into the x pass; returns 2 without doing anything when the configuration's x pass cannot do that (the
@@ -148,7 +160,7 @@ static int blur_level(sift3d_detector *d, const float *src, float *dst, const in
     const float *in = src;
     float *outs[3] = { tmp_a, tmp_b, dst };
     int ax = 0;
-    /* tap spacing 1 on y and z (octave 0 of a unit-spaced volume): x pass, then the fused
+    /* tap spacing 1 on y and z (octave 0 of a unit-spaced volume): one launch, or the x pass, then the fused
      * y+z kernel -- the y-pass result never goes to HBM */
     if ((float)(1.0 / lu[1]) == 1.0f && (float)(1.0 / lu[2]) == 1.0f) {
         int rc;
@@ -156,6 +168,22 @@ static int blur_level(sift3d_detector *d, const float *src, float *dst, const in
             slot = -1;
         if (slot >= 0)
             sift3d_hip_event_record(d->ev_blur[slot][0], stream);
+        /* the whole blur in one launch where that is covered and measured faster than the pair below: neither
+         * intermediate goes to HBM, tmp_a is not used.  Its time is the slot's y+z time; its x time reads 0.
+         * (The pyramid only -- d is set --: the smoothing passes of the demons and dense drivers were not
+         * measured and keep the pair.) */
+        if (d && fir_xyz_wins(f->width / 2, (size_t)dims[0] * dims[1] * dims[2]) &&
+            sift3d_hip_fir_xyz_covers(src, dst, dims[0], dims[1], dims[2], f->width, (float)(1.0 / lu[0]),
+                                      (float)(1.0 / lu[1]), (float)(1.0 / lu[2]))) {
+            if (sift3d_hip_fir_xyz(src, dst, dims[0], dims[1], dims[2], f->taps, f->width, d_scale_max, stream))
+                return SIFT3D_FAILURE;
+            if (slot >= 0) {
+                sift3d_hip_event_record(d->ev_blur[slot][2], stream);
+                d->yz_timed |= 1u << slot;
+                d->xyz_timed |= 1u << slot;
+            }
+            return SIFT3D_SUCCESS;
+        }
         rc = fir_pass(src, tmp_a, dims, lu, f, 0, d_scale_max, stream);
         if (rc == 1 && d_scale_max)
             return 2;
@@ -285,6 +313,7 @@ static int detect_begin(sift3d_detector *d, detect_run *r, const float *d_vol, i
         sift3d_hip_absmax(d_vol, r->n0, d->d_scalars, d->stream))
         return SIFT3D_FAILURE;
     d->yz_timed = 0;
+    d->xyz_timed = 0;
     d->parts_timed = 0;
     d->pyr_chains = 0;
     /* Default configuration on every octave (and a second stream at hand): the stages after the pyramid run

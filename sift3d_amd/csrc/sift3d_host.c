@@ -125,6 +125,7 @@ struct _sift3d_detector {
     void *ev_blur[SIFT3D_AMD_TIMED_BLURS][3]; /* octave 0, blur s: before its x pass, between x and the fused
                             * y+z launch, after it (on the stream they run on) */
     unsigned yz_timed;     /* bit s: blur s of octave 0 took the fused y+z kernel in the last detect */
+    unsigned xyz_timed;    /* bit s: ... and it was ONE launch for x, y and z (ev_blur[s][1] is not recorded) */
     void *ev_pyr[2];       /* the pyramid's last launch on the octave stream / the side stream */
     int pyr_chains;        /* the last detect built its pyramid on three chains (ev_pyr are recorded) */
     void *ev_oct[32];      /* per octave: its downsampling source level is complete */
@@ -1339,8 +1340,9 @@ const double *sift3d_amd_timings(const sift3d_detector *dc)
         d->t[T_PYRAMID_DEV] = d->t[T_PYRAMID];
         for (b = 0; b < SIFT3D_AMD_TIMED_BLURS; b++) {
             const int on = (d->yz_timed >> b) & 1;
-            d->t[T_BLUR_X + b] = on ? stage_seconds(d->ev_blur[b][0], d->ev_blur[b][1]) : 0.0;
-            d->t[T_BLUR_YZ + b] = on ? stage_seconds(d->ev_blur[b][1], d->ev_blur[b][2]) : 0.0;
+            const int one = (d->xyz_timed >> b) & 1;   /* the fused launch: all of it in the y+z slot, x exactly 0 */
+            d->t[T_BLUR_X + b] = on && !one ? stage_seconds(d->ev_blur[b][0], d->ev_blur[b][1]) : 0.0;
+            d->t[T_BLUR_YZ + b] = on ? stage_seconds(d->ev_blur[b][one ? 0 : 1], d->ev_blur[b][2]) : 0.0;
             if (on)
                 last = b;
         }

@@ -78,6 +78,10 @@ def lib():
         "sift3d_hip_fir": (C.c_int, [C.POINTER(FirArgs), vp]),
         "sift3d_hip_fir_yz_u1": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "sift3d_hip_fir_xyz": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, vp, vp]),
+        "sift3d_hip_fir_xyz_covers": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                               C.c_float]),
+        "sift3d_hip_fir_x_scaled": (C.c_int, [C.POINTER(FirArgs), vp, vp]),
         "sift3d_hip_nn2_work_floats": (C.c_size_t, [C.c_int, C.c_int]),
         "sift3d_hip_nn2": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
         "sift3d_hip_subtract_absmax": (C.c_int, [vp, vp, vp, C.c_size_t, vp, vp]),
@@ -212,6 +216,38 @@ def fir_yz(src, dst, taps, n_glob=None, off=0, z_lo=0, z_hi=None):
     if rc == 1:
         return False
     _check(rc, "sift3d_hip_fir_yz_u1")
+    return True
+
+
+def fir_xyz(src, dst, taps, scale_max=None, unit_factors=(1.0, 1.0, 1.0)):
+    """A whole blur (x, y and z passes, tap spacing 1) in one launch; scale_max (a 1-element CUDA tensor): of
+    src / scale_max.  Returns False, having done nothing, when the configuration is not covered."""
+    nz, ny, nx = src.shape
+    assert src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape
+    taps = np.ascontiguousarray(taps, np.float32)
+    if tuple(unit_factors) != (1.0, 1.0, 1.0) and not lib().sift3d_hip_fir_xyz_covers(
+            src.data_ptr(), dst.data_ptr(), nx, ny, nz, len(taps), *[float(np.float32(u)) for u in unit_factors]):
+        return False
+    rc = lib().sift3d_hip_fir_xyz(src.data_ptr(), dst.data_ptr(), nx, ny, nz,
+                                  taps.ctypes.data_as(C.POINTER(C.c_float)), len(taps),
+                                  None if scale_max is None else scale_max.data_ptr(), current_stream())
+    if rc == 1:
+        return False
+    _check(rc, "sift3d_hip_fir_xyz")
+    return True
+
+
+def fir_x_scaled(src, dst, taps, scale_max):
+    """The x pass (tap spacing 1) of src / scale_max (a 1-element CUDA tensor): im_scale folded in."""
+    nz, ny, nx = src.shape
+    assert src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape
+    taps = np.ascontiguousarray(taps, np.float32)
+    a = FirArgs(src.data_ptr(), dst.data_ptr(), nx, ny, nz, 0, len(taps),
+                taps.ctypes.data_as(C.POINTER(C.c_float)), 1.0, nz, 0, 0, nz, 0)
+    rc = lib().sift3d_hip_fir_x_scaled(C.byref(a), scale_max.data_ptr(), current_stream())
+    if rc == 1:
+        return False
+    _check(rc, "sift3d_hip_fir_x_scaled")
     return True
 
 
