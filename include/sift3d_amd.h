@@ -526,6 +526,135 @@ sift3d_amd_label_overlap(const uint64_t *hist, int L, double *dice, double *jacc
                          uint64_t *vol_m);
 
 /* ------------------------------------------------------------------------ */
+/* Intensity-driven affine refinement: Gauss-Newton on the MSD               */
+/* ------------------------------------------------------------------------ */
+/* Moves a 3 x 4 affine pull map towards a smaller mean squared difference between a fixed volume F[oz][oy][ox] and a
+ * moving volume M[nz][ny][nx] seen through it: the normal equations of a Gauss-Newton step in one gather-and-reduce
+ * pass on the device, the damped (Levenberg-Marquardt) solve and the update on the host, and a driver that iterates
+ * them, optionally coarse to fine.  No upstream counterpart: PARITY UNPINNED, pinned to this contract and its numpy
+ * restatement (tests/affine_refine_restatement.py).
+ *
+ * Sample with gradient.  Pull map, inside test and LINEAR sample are "Similarity measures"' / "Resampling"'s, word for
+ * word: a voxel p whose q falls outside the moving grid (a NaN is outside) is skipped and not counted, and m is what
+ * sift3d_hip_warp_affine writes at p, bit for bit.  With a, b the values at ix, jx of the corner rows 00, 10, 01, 11
+ * (y then z), c.. = lerp(a.., b.., fx) and lerp(a, b, f) = a + f * (b - a), all float, unfused:
+ *     gx = lerp(lerp(b00 - a00, b10 - a10, fy), lerp(b01 - a01, b11 - a11, fy), fz)
+ *     gy = lerp(c10 - c00, c11 - c01, fz)
+ *     gz = lerp(c01, c11, fy) - lerp(c00, c10, fy)
+ * the derivative of the trilinear interpolant from the eight values the sample reads.  On a clamped last plane
+ * (j == i: q on the high face of the grid, or an axis of 1) the difference along that axis is 0.
+ *
+ * Normal equations (sift3d_hip_affine_normal_eqs).  The 12 parameters are centred on the fixed grid,
+ * c = ((ox - 1) / 2, (oy - 1) / 2, (oz - 1) / 2) (exact in double): q = L (p - c) + t, parameter 4 d + j is L[d][j]
+ * for j < 3 and t[d] for j = 3, and P = (x - cx, y - cy, z - cz, 1).  The centring keeps the 12 x 12 system well
+ * scaled.  Per counted voxel e = m - f (a float subtraction), and in double E = e, G_d = g_d, J[4 d + j] = G_d P_j.
+ * The record, SIFT3D_AMD_AFFINE_NORMAL_BYTES, 8-byte aligned:
+ *     uint64 n;  double S_ee = sum E E;  double b[12] = sum J E;  double H[12][12] = sum J J^T,
+ * H stored in full and symmetric bit for bit.  Only the 60 distinct values of H (6 pairs G_d G_e x 10 pairs P_j P_k)
+ * and the 12 of b are summed; how a term is factored and in which order the terms are added is the
+ * implementation's (every term carries at most 8 roundings), but it is a function of the shapes only: per-lane
+ * sums, per-workgroup partials (one slot per workgroup of a grid of min(tiles, SIFT3D_AMD_SIMILARITY_GRID)
+ * workgroups, whatever the device), then the slots in a fixed order.  A call repeats its bytes on any device.  S_ee
+ * is the similarity record's sum d d up to the order of the sum.  The whole record is written on `stream` by the call;
+ * n == 0 leaves it all zero.
+ * The entry is asynchronous on `stream`, allocates nothing, uses 64-bit offsets and checks its arguments before any
+ * device call: -1 on NULL pointers, dims <= 0, a non-finite A, a misaligned buffer (record, work: 8 bytes; the rest
+ * 4), an output that overlaps an input, the work buffer or another output, a grid with too many tiles.
+ * d_work: sift3d_amd_affine_normal_work_bytes() bytes, 8-byte aligned.
+ *
+ * LM step (sift3d_amd_affine_lm_step, host, double).  Bit 4 d + j of free_mask frees parameter (d, j); 0xFFF is the
+ * full affine, 0x888 the translation.  On the free set, K = H + lambda diag(H) (K_ii = H_ii + lambda * H_ii),
+ * K delta = -b by Cholesky (K = C C^T row by row, then the two triangular solves); the other entries of delta are 0.
+ * -1 when n == 0, the mask is empty or has bits past 0xFFF, lambda is negative or not finite, or K is not positive
+ * definite (a free parameter with H_ii == 0 makes it so); delta is then all zero.
+ *
+ * Update (sift3d_amd_affine_apply_delta, host, double, unfused), per row d with L = A[d][0..2]:
+ *     t   = A[d][3] + ((L[0] * cx + L[1] * cy) + L[2] * cz)
+ *     L'[j] = L[j] + delta[4 d + j]
+ *     A_out[d] = [ L' | (t + delta[4 d + 3]) - ((L'[0] * cx + L'[1] * cy) + L'[2] * cz) ]
+ *
+ * Driver (sift3d_amd_affine_refine_device).  Per level, with lambda = lambda0:
+ *   1. evaluate at A (record r, n_first = r.n);
+ *   2. delta = lm_step(r, free_mask, lambda), A' = apply_delta(A, delta), evaluate at A' (record r');
+ *   3. accept when n' >= min_overlap * n_first and S_ee' / n' < S_ee / n.  Accepted: A = A', r = r' (the evaluation is
+ *      the next iteration's record), lambda = max(lambda / lambda_factor, lambda_min).  Rejected: lambda = lambda *
+ *      lambda_factor;
+ *   4. stop when an accepted step moved no corner of the fixed grid by tol voxels or more (CONVERGED; the distance
+ *      |A' p - A p| over the 8 corners p), when lambda > lambda_max (LAMBDA), when the level has made max_evaluations
+ *      evaluations (EVALUATIONS), or when the LM step fails or gives a map that is not finite (LM_FAILED); else 2.
+ * Each iteration therefore costs one kernel pass and one copy of the 1.2 KB record to the host with a wait for the
+ * stream: the host decides the next step, the same trade as sift3d_amd_field_exp_device's single wait.
+ * Levels: level 0 is the given pair; level l's volumes are sift3d_hip_restrict2 (scale 1) of level l - 1's, fixed and
+ * moving, held in d_work.  Coarse voxel i is fine voxel 2 i, so going down a level halves A[:][3] and going up doubles
+ * it; the linear part is unchanged.  The coarsest level runs first.
+ * The result holds the final A (also written to A_io), one entry per evaluation in the order run (MSD = S_ee / n, NaN
+ * when n == 0; n; the lambda of the step that led to it; accepted, 1 for a level's first; the level), their number
+ * (at most levels * max_evaluations) and the stop reason of level 0.  params == NULL takes the defaults.  Once the
+ * arguments have passed the checks the result is valid whatever the call returns (no evaluations, A as given, when
+ * a device call fails before the first).
+ * -1 before any device call on NULL pointers, dims <= 0, a non-finite A, free_mask outside [1, 0xFFF], levels outside
+ * [1, SIFT3D_AMD_DEMONS_MAX_LEVELS], max_evaluations outside [1, SIFT3D_AMD_AFFINE_MAX_EVALUATIONS], lambda0,
+ * lambda_min <= 0, lambda_factor <= 1, lambda_max < lambda0, tol < 0, min_overlap outside [0, 1] (or any of them not
+ * finite), misalignment (d_work 8 B, the volumes 4 B), a work buffer that overlaps a volume.
+ * d_work: sift3d_amd_affine_refine_work_bytes() bytes. */
+#define SIFT3D_AMD_AFFINE_NORMAL_BYTES 1264        /* 8 + 8 + 12 * 8 + 144 * 8 */
+#define SIFT3D_AMD_AFFINE_MAX_EVALUATIONS 128      /* per level */
+#define SIFT3D_AMD_AFFINE_MAX_TRAIL (6 * SIFT3D_AMD_AFFINE_MAX_EVALUATIONS)    /* SIFT3D_AMD_DEMONS_MAX_LEVELS levels */
+#define SIFT3D_AMD_AFFINE_FREE_ALL 0xFFFu
+#define SIFT3D_AMD_AFFINE_FREE_TRANSLATION 0x888u
+#define SIFT3D_AMD_AFFINE_STOP_CONVERGED 0
+#define SIFT3D_AMD_AFFINE_STOP_LAMBDA 1
+#define SIFT3D_AMD_AFFINE_STOP_EVALUATIONS 2
+#define SIFT3D_AMD_AFFINE_STOP_LM_FAILED 3
+typedef struct {
+    unsigned free_mask;        /* 0xFFF */
+    int levels;                /* 1 */
+    int max_evaluations;       /* 30, per level */
+    double lambda0;            /* 1e-3: the damping a level starts with */
+    double lambda_factor;      /* 10: lambda goes down by it on an accepted step, up on a rejected one */
+    double lambda_min;         /* 1e-9: floor */
+    double lambda_max;         /* 1e7: stop above it */
+    double tol;                /* 1e-3 voxels */
+    double min_overlap;        /* 0.5 of the level's first count */
+} sift3d_amd_affine_refine_params;
+typedef struct {
+    double msd;
+    uint64_t n;
+    double lambda;
+    int accepted, level;
+} sift3d_amd_affine_evaluation;
+typedef struct {
+    double A[12];
+    int evaluations, stop;
+    sift3d_amd_affine_evaluation trail[SIFT3D_AMD_AFFINE_MAX_TRAIL];
+} sift3d_amd_affine_refine_result;
+/* bytes of d_work for sift3d_hip_affine_normal_eqs on this fixed grid (0 for dims <= 0) */
+SIFT3D_AMD_API size_t sift3d_amd_affine_normal_work_bytes(int ox, int oy, int oz);
+/* d_F [oz][oy][ox], d_M [nz][ny][nx], d_record the record above */
+SIFT3D_AMD_API int
+sift3d_hip_affine_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                             const double *A /*12*/, void *d_record, void *d_work, void *stream);
+/* host only: record on the host */
+SIFT3D_AMD_API int
+sift3d_amd_affine_lm_step(const void *record, unsigned free_mask, double lambda, double *delta /*12*/);
+/* host only: (ox, oy, oz) is the fixed grid; A_out may be A */
+SIFT3D_AMD_API int
+sift3d_amd_affine_apply_delta(const double *A /*12*/, const double *delta /*12*/, int ox, int oy, int oz,
+                              double *A_out /*12*/);
+SIFT3D_AMD_API void sift3d_amd_affine_refine_default_params(sift3d_amd_affine_refine_params *p);
+/* for bindings that restate the layouts: sizeof the params (0), evaluation (1) and result (2) structs, then
+ * SIFT3D_AMD_AFFINE_NORMAL_BYTES (3), SIFT3D_AMD_AFFINE_MAX_EVALUATIONS (4), the most levels (5); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_affine_refine_struct_bytes(int which);
+/* bytes of d_work for the driver (0 for bad arguments) */
+SIFT3D_AMD_API size_t
+sift3d_amd_affine_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels);
+/* A_io [12] on the host, in / out; waits for `stream` once per evaluation */
+SIFT3D_AMD_API int
+sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                double *A_io, const sift3d_amd_affine_refine_params *params,
+                                sift3d_amd_affine_refine_result *result, void *d_work, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

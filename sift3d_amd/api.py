@@ -612,15 +612,21 @@ def _matched_points(moving, fixed, nn_thresh, detector_kw, what):
     return d_mov.xyz()[hit], d_fix.xyz()[m[hit]]
 
 
-def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1, **detector_kw):
+def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1, refine=False, **detector_kw):
     """Register two volumes (torch CUDA float32 tensors [nz, ny, nx]): detect + describe both,
     match the descriptors, fit the moving -> fixed affine by RANSAC and resample `moving` into
     `fixed`'s grid.  detector_kw go to Detector().  Returns Registration(A (3 x 4, moving voxel ->
-    fixed voxel), inliers (mask over the matches), num_matches, warped (tensor shaped like fixed))."""
+    fixed voxel), inliers (mask over the matches), num_matches, warped (tensor shaped like fixed)).
+    refine=True (or a dict of refine_affine's keyword arguments) runs refine_affine from the RANSAC result and
+    returns RefinedRegistration(A, inliers, num_matches, warped, A_ransac, refinement): A and warped are the refined
+    map and its resampling, A_ransac is what refine=False returns as A, refinement the AffineRefinement."""
     import torch
     from . import hip
     p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
     A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
+    if refine:
+        r = refine_affine(moving, fixed, affine_invert(A), **(refine if isinstance(refine, dict) else {}))
+        return RefinedRegistration(affine_invert(r.A), inl, len(p_mov), r.warped, A, r)
     warped = torch.empty_like(fixed)
     hip.warp_affine(moving, warped, affine_invert(A), "linear")
     return Registration(A, inl, len(p_mov), warped)
@@ -970,6 +976,61 @@ def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fi
     T = _similarity_transform(transform, F, "similarity")
     hist, stats = hip.similarity(F, M, T, bins, _own_range(F, range_fixed), _own_range(M, range_moving), interp)
     return similarity_measures(hist.cpu().numpy(), hip.similarity_stats(stats))
+
+
+# ---- intensity-driven affine refinement ----------------------------------------------------------
+AffineRefinement = collections.namedtuple(
+    "AffineRefinement", "A msd count accepted lambdas levels level_slices evaluations stop warped")
+RefinedRegistration = collections.namedtuple("RefinedRegistration",
+                                             "A inliers num_matches warped A_ransac refinement")
+AFFINE_FREE = {"affine": 0xFFF, "translation": 0x888}
+
+
+def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", **params):
+    """Move the 3 x 4 affine pull map A (fixed voxel -> moving voxel, as similarity's transform; None: the identity,
+    which needs no equal shapes) towards a smaller mean squared difference between `fixed` and `moving` seen through
+    it, by Levenberg-Marquardt steps on the device's Gauss-Newton normal equations (contract: include/sift3d_amd.h,
+    "Intensity-driven affine refinement").  free: "affine" (all 12 parameters), "translation", or a mask whose bit
+    4 d + j frees A[d][j] as centred on the fixed grid.  levels > 1 solves on volumes restricted levels - 1 times
+    first.  params: max_evaluations (per level), lambda0, lambda_factor, lambda_min, lambda_max, tol (voxels),
+    min_overlap.  The sample is linear.  The volumes are torch CUDA float32 tensors [nz, ny, nx], or Images / arrays,
+    which are uploaded.  Returns AffineRefinement(A, msd, count, accepted, lambdas, levels: one entry per evaluation
+    in the order run; level_slices: {level: slice into those}; evaluations; stop: "converged", "lambda",
+    "evaluations" or "lm_failed" of level 0; warped: `moving` through A on the fixed grid).  Waits for torch's
+    current stream once per evaluation."""
+    import torch
+    from . import hip
+    if interp != "linear":
+        raise ValueError("refine_affine: the sample is linear; interp=%r has no gradient" % (interp,))
+    mask = AFFINE_FREE.get(free, free) if isinstance(free, str) else free
+    if isinstance(mask, bool) or not isinstance(mask, (int, np.integer)) or not 1 <= int(mask) <= 0xFFF:
+        raise ValueError("refine_affine: free must be 'affine', 'translation' or a mask in [1, 0xFFF], not %r"
+                         % (free,))
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
+            not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
+        raise ValueError("refine_affine: levels must be in [1, %d]" % hip.AFFINE_MAX_LEVELS)
+    if "max_evaluations" in params and not 1 <= int(params["max_evaluations"]) <= hip.AFFINE_MAX_EVALUATIONS:
+        raise ValueError("refine_affine: max_evaluations must be in [1, %d]" % hip.AFFINE_MAX_EVALUATIONS)
+    A0 = np.eye(3, 4) if A is None else _affine_or_none(A)
+    if A0 is None or not np.isfinite(A0).all():
+        raise ValueError("refine_affine: A must be a finite 3 x 4 affine pull map or None")
+    p = hip.affine_refine_params(free_mask=int(mask), levels=int(levels), **params)
+    F = _similarity_volume(fixed, "refine_affine", "fixed")
+    M = _similarity_volume(moving, "refine_affine", "moving", F.device)
+    res = hip.affine_refine(F, M, A0, p)
+    k = res.evaluations
+    trail = res.trail[:k]
+    lv = np.array([e.level for e in trail], np.int64)
+    slices = {}
+    for l in sorted(set(lv.tolist()), reverse=True):
+        idx = np.nonzero(lv == l)[0]
+        slices[l] = slice(int(idx[0]), int(idx[-1]) + 1)
+    A1 = np.array(res.A[:], np.float64).reshape(3, 4)
+    warped = torch.empty_like(F)
+    hip.warp_affine(M, warped, A1, "linear")
+    return AffineRefinement(A1, np.array([e.msd for e in trail]), np.array([e.n for e in trail], np.int64),
+                            np.array([bool(e.accepted) for e in trail]), np.array([e.lambda_ for e in trail]), lv,
+                            slices, k, hip.AFFINE_STOPS[res.stop], warped)
 
 
 def label_overlap(labels_fixed, labels_moving, transform=None, num_labels=None):

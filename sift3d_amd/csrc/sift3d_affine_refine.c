@@ -1,0 +1,337 @@
+/* sift3d_affine_refine.c -- intensity-driven affine refinement: the checked device entry of the normal equations, the
+ * Levenberg-Marquardt step and the parameter update on the host, and the driver that iterates them
+ * (included at the end of sift3d_host.c, after sift3d_similarity.c).
+ *
+ * The contract is in include/sift3d_amd.h, "Intensity-driven affine refinement"; the kernels are in
+ * sift3d_affine_refine.hip, reached through the launcher below after the checks here.  Arguments are checked before
+ * the device is touched, so bad input is refused on a machine without a GPU too. */
+
+int sift3d_affine_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                                int ny, int nz, const double *A, void *d_record, void *d_work, void *stream);
+
+/* a double per statistic (60 + 12 + 1, and the uint64 count) per partial slot */
+#define AFFINE_NORMAL_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 74 * 8)
+
+size_t sift3d_amd_affine_normal_work_bytes(int ox, int oy, int oz)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0)
+        return 0;
+    return AFFINE_NORMAL_WORK_BYTES;
+}
+
+int sift3d_hip_affine_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const double *A, void *d_record, void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_hip_affine_normal_eqs";
+    if (!d_F || !d_M || !A || !d_record || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) || check_affine(what, A) ||
+        check_aligned(what, ADDR(d_record) | ADDR(d_work), ADDR(d_F) | ADDR(d_M)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) } };
+        const range_t out[] = { { d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES }, { d_work, AFFINE_NORMAL_WORK_BYTES } };
+        if (ranges_aliased(out, 2, in, 2))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_affine_normal_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record, d_work, stream);
+}
+
+/* ---- host arithmetic on a record (the order of every operation is the header's) ---- */
+
+typedef struct {
+    uint64_t n;
+    double see, b[12], H[144];
+} affine_record;
+
+int sift3d_amd_affine_lm_step(const void *record, unsigned free_mask, double lambda, double *delta)
+{
+    static const char what[] = "sift3d_amd_affine_lm_step";
+    affine_record r;
+    double K[144], y[12];
+    int idx[12], m = 0, i, j, k;
+    if (!record || !delta)
+        return refuse(what, "NULL argument");
+    if (!isfinite(lambda) || lambda < 0)
+        return refuse(what, "lambda must be finite and not negative");
+    memcpy(&r, record, sizeof(r));
+    for (i = 0; i < 12; i++) {
+        delta[i] = 0.0;
+        if (free_mask & (1u << i))
+            idx[m++] = i;
+    }
+    if (r.n == 0 || m == 0 || (free_mask & ~0xFFFu))
+        return SIFT3D_FAILURE;
+    /* K = H + lambda diag H on the free set, its lower triangle factored in place: K = C C^T, row by row */
+    for (i = 0; i < m; i++)
+        for (j = 0; j <= i; j++) {
+            const double h = r.H[idx[i] * 12 + idx[j]];
+            K[i * 12 + j] = i == j ? h + lambda * h : h;
+        }
+    for (i = 0; i < m; i++) {
+        for (j = 0; j <= i; j++) {
+            double s = K[i * 12 + j];
+            for (k = 0; k < j; k++)
+                s -= K[i * 12 + k] * K[j * 12 + k];
+            if (i == j) {
+                if (!(s > 0.0) || !isfinite(s))
+                    return SIFT3D_FAILURE;                  /* not positive definite (H_ii == 0 included) */
+                K[i * 12 + i] = sqrt(s);
+            } else
+                K[i * 12 + j] = s / K[j * 12 + j];
+        }
+    }
+    for (i = 0; i < m; i++) {                                /* C y = -b */
+        double s = -r.b[idx[i]];
+        for (k = 0; k < i; k++)
+            s -= K[i * 12 + k] * y[k];
+        y[i] = s / K[i * 12 + i];
+    }
+    for (i = m - 1; i >= 0; i--) {                           /* C^T delta = y */
+        double s = y[i];
+        for (k = i + 1; k < m; k++)
+            s -= K[k * 12 + i] * y[k];
+        y[i] = s / K[i * 12 + i];
+        if (!isfinite(y[i]))
+            return SIFT3D_FAILURE;
+    }
+    for (i = 0; i < m; i++)
+        delta[idx[i]] = y[i];
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_affine_apply_delta(const double *A, const double *delta, int ox, int oy, int oz, double *A_out)
+{
+    static const char what[] = "sift3d_amd_affine_apply_delta";
+    double c[3], out[12];
+    int d, j;
+    if (!A || !delta || !A_out)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz))
+        return SIFT3D_FAILURE;
+    c[0] = (double)(ox - 1) / 2.0;
+    c[1] = (double)(oy - 1) / 2.0;
+    c[2] = (double)(oz - 1) / 2.0;
+    for (d = 0; d < 3; d++) {
+        const double *a = A + 4 * d;
+        double *o = out + 4 * d;
+        const double t = a[3] + ((a[0] * c[0] + a[1] * c[1]) + a[2] * c[2]);
+        for (j = 0; j < 3; j++)
+            o[j] = a[j] + delta[4 * d + j];
+        o[3] = (t + delta[4 * d + 3]) - ((o[0] * c[0] + o[1] * c[1]) + o[2] * c[2]);
+    }
+    memcpy(A_out, out, sizeof(out));
+    return SIFT3D_SUCCESS;
+}
+
+/* ---- the driver ---- */
+
+void sift3d_amd_affine_refine_default_params(sift3d_amd_affine_refine_params *p)
+{
+    if (!p)
+        return;
+    p->free_mask = 0xFFF;
+    p->levels = 1;
+    p->max_evaluations = 30;
+    p->lambda0 = 1e-3;
+    p->lambda_factor = 10.0;
+    p->lambda_min = 1e-9;
+    p->lambda_max = 1e7;
+    p->tol = 1e-3;
+    p->min_overlap = 0.5;
+}
+
+static int affine_params_ok(const sift3d_amd_affine_refine_params *p)
+{
+    return p->free_mask >= 1 && p->free_mask <= 0xFFF && p->levels >= 1 && p->levels <= SIFT3D_AMD_DEMONS_MAX_LEVELS &&
+           p->max_evaluations >= 1 && p->max_evaluations <= SIFT3D_AMD_AFFINE_MAX_EVALUATIONS &&
+           isfinite(p->lambda0) && p->lambda0 > 0 && isfinite(p->lambda_factor) && p->lambda_factor > 1 &&
+           isfinite(p->lambda_min) && p->lambda_min > 0 && isfinite(p->lambda_max) && p->lambda_max >= p->lambda0 &&
+           isfinite(p->tol) && p->tol >= 0 && p->min_overlap >= 0 && p->min_overlap <= 1;
+}
+
+size_t sift3d_amd_affine_refine_struct_bytes(int which)
+{
+    return which == 0   ? sizeof(sift3d_amd_affine_refine_params)
+           : which == 1 ? sizeof(sift3d_amd_affine_evaluation)
+           : which == 2 ? sizeof(sift3d_amd_affine_refine_result)
+           : which == 3 ? (size_t)SIFT3D_AMD_AFFINE_NORMAL_BYTES
+           : which == 4 ? (size_t)SIFT3D_AMD_AFFINE_MAX_EVALUATIONS
+           : which == 5 ? (size_t)SIFT3D_AMD_DEMONS_MAX_LEVELS
+                        : 0;
+}
+
+/* d_work, in bytes: the normal equations' partial slots, the record, then per level l = 1 .. levels-1 the restricted
+ * fixed and moving volumes, each rounded up to a multiple of 16 bytes */
+#define AFFINE_RECORD_PAD ((size_t)(SIFT3D_AMD_AFFINE_NORMAL_BYTES + 15) / 16 * 16)
+
+size_t sift3d_amd_affine_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    size_t total = AFFINE_NORMAL_WORK_BYTES + AFFINE_RECORD_PAD;
+    int l;
+    if (ox <= 0 || oy <= 0 || oz <= 0 || nx <= 0 || ny <= 0 || nz <= 0 || levels < 1 ||
+        levels > SIFT3D_AMD_DEMONS_MAX_LEVELS)
+        return 0;
+    for (l = 1; l < levels; l++) {
+        ox = multires_half(ox); oy = multires_half(oy); oz = multires_half(oz);
+        nx = multires_half(nx); ny = multires_half(ny); nz = multires_half(nz);
+        total += pad4(grid_voxels(ox, oy, oz)) * sizeof(float) + pad4(grid_voxels(nx, ny, nz)) * sizeof(float);
+    }
+    return total;
+}
+
+/* the largest distance by which the maps A and B move a corner of the grid apart */
+static double affine_corner_move(const double *A, const double *B, int ox, int oy, int oz)
+{
+    double worst = 0.0;
+    int c, d;
+    for (c = 0; c < 8; c++) {
+        const double x = c & 1 ? ox - 1 : 0, y = c & 2 ? oy - 1 : 0, z = c & 4 ? oz - 1 : 0;
+        double s = 0.0;
+        for (d = 0; d < 3; d++) {
+            const double *a = A + 4 * d, *b = B + 4 * d;
+            const double e = (b[0] - a[0]) * x + (((b[1] - a[1]) * y + (b[2] - a[2]) * z) + (b[3] - a[3]));
+            s += e * e;
+        }
+        s = sqrt(s);
+        if (!(s <= worst))
+            worst = s;                                      /* a NaN is the largest */
+    }
+    return worst;
+}
+
+typedef struct {
+    const float *F, *M;
+    int ox, oy, oz, nx, ny, nz;
+} affine_level;
+
+/* one evaluation at A on `lv`: the pass, the record's copy to the host and the wait for it */
+static int affine_evaluate(const affine_level *lv, const double *A, void *d_record, void *d_work, void *stream,
+                           affine_record *rec)
+{
+    return sift3d_hip_affine_normal_eqs(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, d_record,
+                                        d_work, stream) ||
+           sift3d_hip_memcpy_d2h(rec, d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES, stream) ||
+           sift3d_hip_stream_sync(stream);
+}
+
+static void affine_trail(sift3d_amd_affine_refine_result *res, const affine_record *rec, double lambda, int accepted,
+                         int level)
+{
+    sift3d_amd_affine_evaluation *e = res->trail + res->evaluations++;
+    e->msd = rec->n ? rec->see / (double)rec->n : NAN;
+    e->n = rec->n;
+    e->lambda = lambda;
+    e->accepted = accepted;
+    e->level = level;
+}
+
+int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    double *A_io, const sift3d_amd_affine_refine_params *params,
+                                    sift3d_amd_affine_refine_result *result, void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_amd_affine_refine_device";
+    sift3d_amd_affine_refine_params prm;
+    affine_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
+    affine_record rec, trial;
+    double A[12], At[12], delta[12];
+    char *w = (char *)d_work;
+    void *d_record;
+    size_t off;
+    int l, i;
+    if (!d_F || !d_M || !A_io || !result || !d_work)
+        return refuse(what, "NULL argument");
+    if (params)
+        prm = *params;
+    else
+        sift3d_amd_affine_refine_default_params(&prm);
+    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) || check_affine(what, A_io))
+        return SIFT3D_FAILURE;
+    if (!affine_params_ok(&prm))
+        return refuse(what, "a parameter is out of range");
+    if (check_aligned(what, ADDR(d_work), ADDR(d_F) | ADDR(d_M)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) } };
+        const range_t out[] = { { d_work, sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.levels) } };
+        if (ranges_aliased(out, 1, in, 2))
+            return refuse(what, ALIASED);
+    }
+    result->evaluations = 0;
+    result->stop = SIFT3D_AMD_AFFINE_STOP_EVALUATIONS;
+    memcpy(result->A, A_io, sizeof(result->A));
+    d_record = w + AFFINE_NORMAL_WORK_BYTES;
+    off = AFFINE_NORMAL_WORK_BYTES + AFFINE_RECORD_PAD;
+    lv[0] = (affine_level){ d_F, d_M, ox, oy, oz, nx, ny, nz };
+    memcpy(A, A_io, sizeof(A));
+    for (l = 1; l < prm.levels; l++) {                       /* level l from level l - 1; A's shift halves */
+        const affine_level *f = lv + l - 1;
+        affine_level *c = lv + l;
+        float *cF = (float *)(w + off), *cM;
+        *c = (affine_level){ NULL, NULL, multires_half(f->ox), multires_half(f->oy), multires_half(f->oz),
+                             multires_half(f->nx), multires_half(f->ny), multires_half(f->nz) };
+        off += pad4(grid_voxels(c->ox, c->oy, c->oz)) * sizeof(float);
+        cM = (float *)(w + off);
+        off += pad4(grid_voxels(c->nx, c->ny, c->nz)) * sizeof(float);
+        if (sift3d_hip_restrict2(f->F, f->ox, f->oy, f->oz, 1, cF, 1.0f, stream) ||
+            sift3d_hip_restrict2(f->M, f->nx, f->ny, f->nz, 1, cM, 1.0f, stream))
+            return SIFT3D_FAILURE;
+        c->F = cF;
+        c->M = cM;
+        for (i = 3; i < 12; i += 4)
+            A[i] = A[i] * 0.5;
+    }
+    for (l = prm.levels - 1; l >= 0; l--) {
+        const affine_level *v = lv + l;
+        double lambda = prm.lambda0;
+        uint64_t n_first;
+        int evals = 1, stop;
+        if (affine_evaluate(v, A, d_record, w, stream, &rec))
+            return SIFT3D_FAILURE;
+        affine_trail(result, &rec, lambda, 1, l);
+        n_first = rec.n;
+        for (;;) {
+            int accept;
+            if (evals >= prm.max_evaluations) {
+                stop = SIFT3D_AMD_AFFINE_STOP_EVALUATIONS;
+                break;
+            }
+            if (sift3d_amd_affine_lm_step(&rec, prm.free_mask, lambda, delta) ||
+                sift3d_amd_affine_apply_delta(A, delta, v->ox, v->oy, v->oz, At) || check_affine(what, At)) {
+                stop = SIFT3D_AMD_AFFINE_STOP_LM_FAILED;
+                break;
+            }
+            if (affine_evaluate(v, At, d_record, w, stream, &trial))
+                return SIFT3D_FAILURE;
+            evals++;
+            accept = trial.n > 0 && (double)trial.n >= prm.min_overlap * (double)n_first &&
+                     trial.see / (double)trial.n < rec.see / (double)rec.n;
+            affine_trail(result, &trial, lambda, accept, l);
+            if (accept) {
+                const double move = affine_corner_move(A, At, v->ox, v->oy, v->oz);
+                memcpy(A, At, sizeof(A));
+                rec = trial;
+                lambda = lambda / prm.lambda_factor;
+                if (lambda < prm.lambda_min)
+                    lambda = prm.lambda_min;
+                if (move < prm.tol) {
+                    stop = SIFT3D_AMD_AFFINE_STOP_CONVERGED;
+                    break;
+                }
+            } else {
+                lambda = lambda * prm.lambda_factor;
+                if (lambda > prm.lambda_max) {
+                    stop = SIFT3D_AMD_AFFINE_STOP_LAMBDA;
+                    break;
+                }
+            }
+        }
+        result->stop = stop;
+        if (l > 0)
+            for (i = 3; i < 12; i += 4)
+                A[i] = A[i] * 2.0;
+    }
+    memcpy(A_io, A, sizeof(A));
+    memcpy(result->A, A, sizeof(A));
+    return SIFT3D_SUCCESS;
+}

@@ -1,0 +1,256 @@
+// sift3d_affine_refine.hip -- the Gauss-Newton normal equations of the mean squared difference over the 12 parameters
+// of an affine pull map, in one gather-and-reduce pass over the fixed grid.
+// Contract: include/sift3d_amd.h, "Intensity-driven affine refinement"; restated in numpy by
+// tests/affine_refine_restatement.py (tests/test_affine_refine.py).
+//
+// The pass is k_similarity<LINEAR, affine> (sift3d_similarity.hip) with the histogram replaced by 73 double sums: the
+// tiles, tile order, XCD grouping, pull map, inside test and sample are sift3d_resample.h's, so m is the warp's value
+// bit for bit; the gradient of the sample comes from the eight corner values the gather holds (gather_grad).  Per
+// voxel 8 B read, nothing written, a few hundred f64 operations: by the arithmetic of DESIGN.md 3.4.8 the pass is bound
+// by f64 VALU work and registers, not by HBM.
+//   - sums: with P = (X, Y, Z, 1) the centred position and G the gradient, H[4d+j][4e+k] = sum G_d G_e P_j P_k has 60
+//     distinct values (6 pairs d <= e x 10 pairs j <= k) and b[4d+j] = sum G_d E P_j has 12; with S_ee, 73 doubles and
+//     the count.  Statistic s = 10 * pair(d, e) + pair(j, k) for H, 60 + 4 d + j for b, 72 for S_ee, 73 the count;
+//   - factored (the default): a lane's y and z are fixed within a tile and it visits 4 values of x, so per voxel it
+//     adds w, w X and (w X) X for the 9 quantities w in {G_d G_e, G_d E} into tile sums (24 adds: b needs no X X),
+//     and once per tile folds those into the 72 accumulators with the tile's Y, Z, Y Y, Y Z, Z Z.  A voxel that is
+//     not counted enters with G = 0 and E = 0, so that the loop has no branches;
+//   - direct (-DSIFT3D_AFFINE_REFINE_NAIVE, kept for profiles/microbench/affine_refine_rate.py): every accumulator
+//     takes w * (P_j P_k) per voxel, 72 multiplies and 72 adds;
+//   - grid: min(tiles, SIFT3D_AMD_SIMILARITY_GRID) workgroups walk the tiles; the size does not depend on the device,
+//     so the bits of the sums depend on the shapes only.  Per-lane sums, the wave by butterfly, the four waves through
+//     LDS as ((w0 + w1) + w2) + w3 into partial slot blockIdx.x, then one finish workgroup per statistic adds the
+//     slots in finish_reduce's fixed order and writes every entry of the record that holds its value: H comes out
+//     full and symmetric bit for bit.
+#include "sift3d_resample.h"
+
+namespace {
+
+constexpr unsigned AFF_GRID = SIFT3D_AMD_SIMILARITY_GRID;
+constexpr int AFF_H = 60, AFF_B = 12;
+constexpr int AFF_SUMS = AFF_H + AFF_B + 1;      // doubles: H's distinct values, b, S_ee
+constexpr int AFF_STATS = AFF_SUMS + 1;          // and the count
+
+struct AffArgs {
+    double a[12];
+    double cx, cy, cz;                           // the centre of the fixed grid
+    GridArgs g;                                  // src = M; ox, oy, oz = F's grid; dst unused
+    const float *F;
+    double *part;                                // [AFF_STATS][AFF_GRID]; row 73 holds uint64
+};
+
+__host__ __device__ constexpr int pair3(int d, int e) { return d == 0 ? e : d == 1 ? 2 + e : 5; }           // d <= e < 3
+__host__ __device__ constexpr int pair4(int j, int k) { return j == 0 ? k : j == 1 ? 3 + k : j == 2 ? 5 + k : 9; }   // j <= k < 4
+
+// (256, 2): the 72 accumulators are 144 VGPRs; the compiler reports 256 VGPRs, two waves per SIMD and nothing spilled
+// (-Rpass-analysis=kernel-resource-usage).  Measured (profiles/microbench/affine_refine_rate_mi355x.txt): 0.888 ms
+// per pass at 512^3, 1.63 x k_similarity's on the same volumes; the direct formulation takes 1.086 ms.
+template <int LINEAR>
+__global__ __launch_bounds__(256, 2) void k_affine_normal(const AffArgs s)
+{
+    __shared__ double slot[AFF_SUMS * 4];
+    __shared__ unsigned long long cslot[4];
+    const GridArgs &p = s.g;
+    const int lx = threadIdx.x & 15;
+    unsigned long long cnt = 0;
+    double see = 0.0;
+    double acc[AFF_H + AFF_B];
+#pragma unroll
+    for (int i = 0; i < AFF_H + AFF_B; i++)
+        acc[i] = 0.0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            break;
+        const bool row = y < p.oy && z < p.oz;
+        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+        const double yd = (double)y, zd = (double)z;
+        const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
+        Taps tp[4];
+        float f[4];
+        bool live[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            live[k] = row && x < p.ox;
+            f[k] = live[k] ? s.F[orow + (size_t)x] : 0.0f;
+            const double xd = (double)x;
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry), pull(s.a + 8, xd, rz));
+        }
+        float m[4], gx[4], gy[4], gz[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            m[k] = gather_grad<LINEAR>(p.src, tp[k], &gx[k], &gy[k], &gz[k]);
+        const double Y = yd - s.cy, Z = zd - s.cz;
+#ifndef SIFT3D_AFFINE_REFINE_NAIVE
+        double s0[9], s1[9], s2[6];
+#pragma unroll
+        for (int i = 0; i < 9; i++)
+            s0[i] = s1[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+            s2[i] = 0.0;
+#endif
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool counted = live[k] && tp[k].in;
+            const float e = m[k] - f[k];
+            const double E = counted ? (double)e : 0.0;
+            const double G[3] = {counted ? (double)gx[k] : 0.0, counted ? (double)gy[k] : 0.0,
+                                 counted ? (double)gz[k] : 0.0};
+            const double X = (double)(xt + lx + 16 * k) - s.cx;
+            cnt += counted ? 1u : 0u;
+            see += E * E;
+#ifndef SIFT3D_AFFINE_REFINE_NAIVE
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+#pragma unroll
+                for (int e2 = d; e2 < 3; e2++) {
+                    const int i = pair3(d, e2);
+                    const double w = G[d] * G[e2];                           // exact: two floats
+                    const double wx = w * X;
+                    s0[i] += w;
+                    s1[i] += wx;
+                    s2[i] += wx * X;
+                }
+                const double w = G[d] * E;
+                s0[6 + d] += w;
+                s1[6 + d] += w * X;
+            }
+#else
+            const double P[4] = {X, Y, Z, 1.0};
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+#pragma unroll
+                for (int e2 = d; e2 < 3; e2++) {
+                    const double w = G[d] * G[e2];
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+#pragma unroll
+                        for (int k2 = j; k2 < 4; k2++)
+                            acc[10 * pair3(d, e2) + pair4(j, k2)] += w * (P[j] * P[k2]);
+                }
+                const double w = G[d] * E;
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    acc[AFF_H + 4 * d + j] += w * P[j];
+            }
+#endif
+        }
+#ifndef SIFT3D_AFFINE_REFINE_NAIVE
+        const double YY = Y * Y, YZ = Y * Z, ZZ = Z * Z;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double *h = acc + 10 * i;
+            h[0] += s2[i];                                                   // X X
+            h[1] += s1[i] * Y;                                               // X Y
+            h[2] += s1[i] * Z;                                               // X Z
+            h[3] += s1[i];                                                   // X 1
+            h[4] += s0[i] * YY;
+            h[5] += s0[i] * YZ;
+            h[6] += s0[i] * Y;
+            h[7] += s0[i] * ZZ;
+            h[8] += s0[i] * Z;
+            h[9] += s0[i];
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            double *b = acc + AFF_H + 4 * d;
+            b[0] += s1[6 + d];
+            b[1] += s0[6 + d] * Y;
+            b[2] += s0[6 + d] * Z;
+            b[3] += s0[6 + d];
+        }
+#endif
+    }
+    // the wave by butterfly (s = 32 .. 1), then the four waves' values through LDS as ((w0 + w1) + w2) + w3
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int i = 0; i < AFF_SUMS; i++) {
+        double v = i < AFF_H + AFF_B ? acc[i] : see;
+#pragma unroll
+        for (int sft = 32; sft >= 1; sft >>= 1)
+            v += __shfl_xor(v, sft);
+        if (lead)
+            slot[4 * i + wave] = v;
+    }
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1)
+        cnt += __shfl_xor(cnt, sft);
+    if (lead)
+        cslot[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x < AFF_SUMS) {
+        const double *v = slot + 4 * threadIdx.x;
+        s.part[(size_t)threadIdx.x * AFF_GRID + blockIdx.x] = ((v[0] + v[1]) + v[2]) + v[3];
+    } else if (threadIdx.x == AFF_SUMS) {
+        reinterpret_cast<unsigned long long *>(s.part)[(size_t)AFF_SUMS * AFF_GRID + blockIdx.x] =
+            ((cslot[0] + cslot[1]) + cslot[2]) + cslot[3];
+    }
+}
+
+// Workgroup s adds the partial slots 0 .. n-1 of statistic s in a fixed order (finish_reduce) and writes every entry
+// of the record {uint64 n; double S_ee; double b[12]; double H[12][12]} that holds it.
+__global__ __launch_bounds__(256) void k_affine_normal_finish(const double *part, unsigned n, double *rec)
+{
+    __shared__ double s_sum[256];
+    __shared__ unsigned long long s_cnt[256];
+    const int st = blockIdx.x;
+    if (st == AFF_SUMS) {
+        const unsigned long long c =
+            finish_reduce<Add>(reinterpret_cast<const unsigned long long *>(part) + (size_t)st * AFF_GRID, n, s_cnt);
+        if (threadIdx.x == 0)
+            reinterpret_cast<unsigned long long *>(rec)[0] = c;
+        return;
+    }
+    const double v = finish_reduce<Add>(part + (size_t)st * AFF_GRID, n, s_sum);
+    if (threadIdx.x != 0)
+        return;
+    double *b = rec + 2, *H = rec + 2 + AFF_B;
+    if (st == AFF_SUMS - 1) {
+        rec[1] = v;
+    } else if (st >= AFF_H) {
+        b[st - AFF_H] = v;
+    } else {
+        for (int d = 0; d < 3; d++)
+            for (int e = d; e < 3; e++)
+                for (int j = 0; j < 4; j++)
+                    for (int k = j; k < 4; k++) {
+                        if (10 * pair3(d, e) + pair4(j, k) != st)
+                            continue;
+                        H[(4 * d + j) * 12 + 4 * e + k] = v;
+                        H[(4 * d + k) * 12 + 4 * e + j] = v;
+                        H[(4 * e + j) * 12 + 4 * d + k] = v;
+                        H[(4 * e + k) * 12 + 4 * d + j] = v;
+                    }
+    }
+}
+
+} // namespace
+
+// Launcher for sift3d_affine_refine.c, which has checked every argument (not exported from the library).
+extern "C" int sift3d_affine_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
+                                           int nx, int ny, int nz, const double *A, void *d_record, void *d_work,
+                                           void *stream)
+{
+    AffArgs s;
+    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+        return launch_fail(fn, "grid too large");
+    for (int i = 0; i < 12; i++)
+        s.a[i] = A[i];
+    s.cx = (double)(ox - 1) / 2.0;
+    s.cy = (double)(oy - 1) / 2.0;
+    s.cz = (double)(oz - 1) / 2.0;
+    s.F = d_F;
+    s.part = (double *)d_work;
+    const unsigned grid = s.g.ntiles < AFF_GRID ? s.g.ntiles : AFF_GRID;
+    hipStream_t st = (hipStream_t)stream;
+    void (*k)(const AffArgs) = nx >= 2 ? k_affine_normal<2> : k_affine_normal<1>;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, s);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_affine_normal_finish, dim3(AFF_STATS), dim3(256), 0, st, (const double *)d_work, grid,
+                       (double *)d_record);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}

@@ -1505,3 +1505,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* similarity measures: joint histogram, moments, and the measures and label overlap computed from them */
 #include "sift3d_similarity.c"
+
+/* intensity-driven affine refinement: normal equations entry, LM step, update and the driver */
+#include "sift3d_affine_refine.c"

@@ -213,6 +213,42 @@ __device__ __forceinline__ float gather(const float *s, const Taps &t, float fil
     return t.in ? v : fill;
 }
 
+// gather<LINEAR>'s value bit for bit (LINEAR 1 and 2 only; no fill: the caller tests t.in) and the derivative of the
+// trilinear interpolant from the same eight corner values, no further loads.  Float, unfused, in gather's names:
+//   gx = lerp(lerp(b00 - a00, b10 - a10, fy), lerp(b01 - a01, b11 - a11, fy), fz)
+//   gy = lerp(c10 - c00, c11 - c01, fz)
+//   gz = lerp(c01, c11, fy) - lerp(c00, c10, fy)
+// On a clamped last plane (j == i: q on the grid's high face, or an axis of 1) both corners are one voxel and the
+// difference along that axis is 0.  (gather itself is not built on this: its kernels compile as they did.)
+template <int LINEAR>
+__device__ __forceinline__ float gather_grad(const float *s, const Taps &t, float *gx, float *gy, float *gz)
+{
+    static_assert(LINEAR == 1 || LINEAR == 2, "gather_grad: linear modes only");
+    float a00, b00, a10, b10, a01, b01, a11, b11;
+    if (LINEAR == 2) {
+        const f32x2u w00 = *reinterpret_cast<const f32x2u *>(s + t.r00 + t.bx);
+        const f32x2u w10 = *reinterpret_cast<const f32x2u *>(s + t.r10 + t.bx);
+        const f32x2u w01 = *reinterpret_cast<const f32x2u *>(s + t.r01 + t.bx);
+        const f32x2u w11 = *reinterpret_cast<const f32x2u *>(s + t.r11 + t.bx);
+        a00 = t.hi ? w00.y : w00.x; b00 = w00.y;
+        a10 = t.hi ? w10.y : w10.x; b10 = w10.y;
+        a01 = t.hi ? w01.y : w01.x; b01 = w01.y;
+        a11 = t.hi ? w11.y : w11.x; b11 = w11.y;
+    } else {
+        a00 = s[t.r00 + t.ix]; b00 = s[t.r00 + t.jx];
+        a10 = s[t.r10 + t.ix]; b10 = s[t.r10 + t.jx];
+        a01 = s[t.r01 + t.ix]; b01 = s[t.r01 + t.jx];
+        a11 = s[t.r11 + t.ix]; b11 = s[t.r11 + t.jx];
+    }
+    const float c00 = lerp(a00, b00, t.fx), c10 = lerp(a10, b10, t.fx);
+    const float c01 = lerp(a01, b01, t.fx), c11 = lerp(a11, b11, t.fx);
+    const float c0 = lerp(c00, c10, t.fy), c1 = lerp(c01, c11, t.fy);
+    *gx = lerp(lerp(b00 - a00, b10 - a10, t.fy), lerp(b01 - a01, b11 - a11, t.fy), t.fz);
+    *gy = lerp(c10 - c00, c11 - c01, t.fz);
+    *gz = c1 - c0;
+    return lerp(c0, c1, t.fz);
+}
+
 template <int LINEAR>
 __device__ __forceinline__ float sample(const GridArgs &p, double qx, double qy, double qz)
 {

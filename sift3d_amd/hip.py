@@ -46,6 +46,27 @@ LEVEL_DTYPE = np.dtype([("data", "u8"), ("nx", "i4"), ("ny", "i4"), ("nz", "i4")
 assert LEVEL_DTYPE.itemsize == C.sizeof(Level)
 assert KP_DTYPE.itemsize == 64 and CAND_DTYPE.itemsize == 12
 
+class AffineRefineParams(C.Structure):                     # sift3d_amd_affine_refine_params
+    _fields_ = [("free_mask", C.c_uint), ("levels", C.c_int), ("max_evaluations", C.c_int),
+                ("lambda0", C.c_double), ("lambda_factor", C.c_double), ("lambda_min", C.c_double),
+                ("lambda_max", C.c_double), ("tol", C.c_double), ("min_overlap", C.c_double)]
+
+
+class AffineEvaluation(C.Structure):                       # sift3d_amd_affine_evaluation
+    _fields_ = [("msd", C.c_double), ("n", C.c_uint64), ("lambda_", C.c_double), ("accepted", C.c_int),
+                ("level", C.c_int)]
+
+
+AFFINE_MAX_EVALUATIONS = 128                               # checked against the library when it is bound (lib())
+AFFINE_MAX_LEVELS = 6
+AFFINE_NORMAL_BYTES = 1264
+
+
+class AffineRefineResult(C.Structure):                     # sift3d_amd_affine_refine_result
+    _fields_ = [("A", C.c_double * 12), ("evaluations", C.c_int), ("stop", C.c_int),
+                ("trail", AffineEvaluation * (AFFINE_MAX_LEVELS * AFFINE_MAX_EVALUATIONS))]
+
+
 _bound = None
 
 
@@ -126,6 +147,18 @@ def lib():
         "sift3d_hip_similarity_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
                                                   C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp,
                                                   vp, vp]),
+        "sift3d_amd_affine_normal_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_affine_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_double), vp, vp, vp]),
+        "sift3d_amd_affine_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, C.POINTER(C.c_double)]),
+        "sift3d_amd_affine_apply_delta": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,
+                                                    C.c_int, C.POINTER(C.c_double)]),
+        "sift3d_amd_affine_refine_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_amd_affine_refine_default_params": (None, [C.POINTER(AffineRefineParams)]),
+        "sift3d_amd_affine_refine_work_bytes": (C.c_size_t, [C.c_int] * 7),
+        "sift3d_amd_affine_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_double), C.POINTER(AffineRefineParams),
+                                                      C.POINTER(AffineRefineResult), vp, vp]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -168,6 +201,13 @@ def lib():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
+    # the layouts and limits restated above are the header's
+    want = (C.sizeof(AffineRefineParams), C.sizeof(AffineEvaluation), C.sizeof(AffineRefineResult),
+            AFFINE_NORMAL_BYTES, AFFINE_MAX_EVALUATIONS, AFFINE_MAX_LEVELS)
+    got = tuple(L.sift3d_amd_affine_refine_struct_bytes(k) for k in range(6))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the affine refinement layouts as %s, the library has %s"
+                           % (want, got))
     _bound = L
     return L
 
@@ -554,6 +594,120 @@ def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=No
         _check(lib().sift3d_hip_similarity_field(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
                                                  field.data_ptr(), *tail), "sift3d_hip_similarity_field")
     return hist, stats
+
+
+# ---- intensity-driven affine refinement (contract: include/sift3d_amd.h, "Intensity-driven affine refinement") ----
+AFFINE_FREE_ALL, AFFINE_FREE_TRANSLATION = 0xFFF, 0x888
+AFFINE_STOPS = ("converged", "lambda", "evaluations", "lm_failed")
+AFFINE_RECORD_DTYPE = np.dtype([("n", "u8"), ("see", "f8"), ("b", "f8", (12,)), ("H", "f8", (12, 12))])
+assert AFFINE_RECORD_DTYPE.itemsize == AFFINE_NORMAL_BYTES
+
+
+def affine_normal_work_bytes(fixed_shape=(1, 1, 1)):
+    """sift3d_amd_affine_normal_work_bytes for a fixed grid (oz, oy, ox)"""
+    oz, oy, ox = (int(v) for v in fixed_shape)
+    return lib().sift3d_amd_affine_normal_work_bytes(ox, oy, oz)
+
+
+def _affine12(A, what):
+    a = np.ascontiguousarray(A, np.float64)
+    if a.shape not in ((3, 4), (12,)):
+        raise ValueError("%s: A must be a 3 x 4 affine pull map" % what)
+    return a.reshape(12).copy()
+
+
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def affine_normal_record(record):
+    """The record of affine_normal_equations() on the host, waiting for the stream: (n, S_ee, b float64 [12],
+    H float64 [12, 12])."""
+    import torch
+    raw = record.view(torch.uint8)[:AFFINE_NORMAL_BYTES].cpu().numpy().view(AFFINE_RECORD_DTYPE)[0]
+    return int(raw["n"]), float(raw["see"]), raw["b"].copy(), raw["H"].copy()
+
+
+def affine_normal_equations(F, M, A, record=None, work=None, raw=False):
+    """The Gauss-Newton normal equations of the mean squared difference of the fixed volume F [oz, oy, ox] and the
+    moving volume M [nz, ny, nx] seen through the 3 x 4 pull map A, over A's 12 parameters centred on F's grid
+    (sift3d_hip_affine_normal_eqs), torch CUDA float32 contiguous, on torch's current stream.  Returns
+    (n, S_ee, b [12], H [12, 12]) on the host (which waits for the stream), or with raw=True the device record (read
+    it with affine_normal_record).  record, work: the caller's buffers (int64 [158]; sift3d_amd_affine_normal_work_bytes
+    bytes)."""
+    import torch
+    for t in (F, M):
+        _tensor(t, "affine_normal_equations: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device("affine_normal_equations", F, M)
+    a = _affine12(A, "affine_normal_equations")
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    if record is None:
+        record = torch.empty(AFFINE_NORMAL_BYTES // 8, dtype=torch.int64, device=F.device)
+    _tensor(record, "affine_normal_equations: record must be a contiguous int64 CUDA tensor [158] on F's device",
+            shape=(AFFINE_NORMAL_BYTES // 8,), device=F.device, dtype="int64")
+    need = lib().sift3d_amd_affine_normal_work_bytes(ox, oy, oz)
+    work = _work(work, (need + 3) // 4, F, "affine_normal_equations")
+    _check(lib().sift3d_hip_affine_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                              record.data_ptr(), work.data_ptr(), current_stream()),
+           "sift3d_hip_affine_normal_eqs")
+    return record if raw else affine_normal_record(record)
+
+
+def affine_lm_step(n, see, b, H, free_mask=AFFINE_FREE_ALL, lam=0.0):
+    """delta float64 [12] of sift3d_amd_affine_lm_step (host): (H + lam diag H) delta = -b on the parameters that
+    free_mask frees, 0 elsewhere; None where the entry refuses (n == 0, an empty mask, not positive definite)."""
+    rec = np.zeros(1, AFFINE_RECORD_DTYPE)
+    rec["n"], rec["see"], rec["b"], rec["H"] = n, see, b, H
+    delta = np.zeros(12)
+    rc = lib().sift3d_amd_affine_lm_step(rec.ctypes.data, int(free_mask) & 0xFFFFFFFF, float(lam), _dptr(delta))
+    return delta if rc == 0 else None
+
+
+def affine_apply_delta(A, delta, fixed_shape):
+    """A' [3, 4] of sift3d_amd_affine_apply_delta (host): A moved by delta, the parameters centred on the grid
+    fixed_shape = (oz, oy, ox)."""
+    a = _affine12(A, "affine_apply_delta")
+    d = np.ascontiguousarray(delta, np.float64).reshape(12)
+    out = np.zeros(12)
+    oz, oy, ox = (int(v) for v in fixed_shape)
+    if lib().sift3d_amd_affine_apply_delta(_dptr(a), _dptr(d), ox, oy, oz, _dptr(out)) != 0:
+        raise ValueError("affine_apply_delta: the grid's dimensions must be positive")
+    return out.reshape(3, 4)
+
+
+def affine_refine_params(**kw):
+    """sift3d_amd_affine_refine_params: the defaults, overridden by free_mask, levels, max_evaluations, lambda0,
+    lambda_factor, lambda_min, lambda_max, tol, min_overlap"""
+    p = AffineRefineParams()
+    lib().sift3d_amd_affine_refine_default_params(C.byref(p))
+    names = [f[0] for f in AffineRefineParams._fields_]
+    for k, v in kw.items():
+        if k not in names:
+            raise ValueError("refine_affine: unknown parameter %r" % (k,))
+        setattr(p, k, v)
+    return p
+
+
+def affine_refine(F, M, A, params=None, work=None):
+    """sift3d_amd_affine_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
+    waits for it once per evaluation).  Returns the AffineRefineResult."""
+    for t in (F, M):
+        _tensor(t, "affine_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device("affine_refine", F, M)
+    a = _affine12(A, "affine_refine")
+    p = params if params is not None else affine_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    need = lib().sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz, p.levels)
+    if need == 0:
+        raise ValueError("affine_refine: levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
+    work = _work(work, (need + 3) // 4, F, "affine_refine")
+    res = AffineRefineResult()
+    _check(lib().sift3d_amd_affine_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                                 C.byref(p), C.byref(res), work.data_ptr(), current_stream()),
+           "sift3d_amd_affine_refine_device")
+    return res
 
 
 def _dense_args(src, out, what):
