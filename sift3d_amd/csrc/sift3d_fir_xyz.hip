@@ -1,18 +1,18 @@
-// sift3d_fir_xyz.hip -- a whole octave-0 blur (x, y and z passes) in ONE launch (k_fir_xyz_dma) and its C entry.
+// sift3d_fir_xyz.hip -- a whole octave-0 blur (x, y and z passes) in ONE launch and its C entry: XyzGeom and the
+// staging geometry of k_fir_xyz_dma, its per-request filter (scale, x edges, x phase, y taps), its z ring and the
+// dynamic-LDS launcher.  The LDS-DMA pipeline it shares with k_fir_yz_dma is in sift3d_fir_dma.h, explained there.
 //
-// Compiled with -fno-slp-vectorize like sift3d_fir_yz.hip, whose kernel k_fir_yz_dma this one is derived
-// from.  Numerical contract and citations as in sift3d_kernels.hip.
-#include "sift3d_kernels_common.h"
+// Compiled with -fno-slp-vectorize like sift3d_fir_yz.hip.  Numerical contract and citations as in
+// sift3d_kernels.hip.
+#include "sift3d_fir_dma.h"
 
 #include <atomic>
 
 // ---- fused x + y + z passes, unit tap spacing -----------------------------------------------------
 // dst = FIR_z(FIR_y(FIR_x(src))) where neither the x-pass nor the y-pass result reaches HBM: the pair
 // k_fir_x_u1f + k_fir_yz_dma writes the x-filtered volume to scratch and reads it back (8 of its ~16.3
-// B/voxel).  The skeleton is k_fir_yz_dma's (sift3d_fir_yz.hip): a workgroup owns a 64(x) x TY(y) column,
-// sweeps a segment along z, the rows of a request go from HBM straight into one of FOUR LDS tiles
-// (global_load_lds_dwordx4) three requests ahead, every wave waits for its own pieces with a counted
-// s_waitcnt vmcnt(N), the request list `seq` and the z register ring are unchanged.  What differs:
+// B/voxel).  A workgroup owns a 64(x) x TY(y) column and sweeps a segment along z as k_fir_yz_dma does.  What
+// differs from that kernel:
 //   * The staged rows are rows of the blur's SOURCE, 64 + 2 * 8 floats wide (HALO = 8 as in k_fir_x_u1f: every
 //     DMA piece stays 16-byte aligned): SQ = 20 quads per row.  A DMA piece is 64 consecutive quads of the
 //     tile (3.2 rows); lane -> (row, quad) = (f / 20, f % 20) of its flat quad index f.  Source addresses are
@@ -34,13 +34,12 @@
 //   HW = 2, TY = 64: 4 x 22 KB + 17 KB + 1.3 KB = 106.3 KB, one 1024-thread workgroup per CU;
 // 4 waves per SIMD either way, as k_fir_yz_dma.
 template <int HW, int TY> struct XyzGeom {
-    static constexpr int TXQ = 16, SQ = 20, HALO = 8, W = 2 * HW + 1, ROWS = TY + 2 * HW, NB = 4;
+    static constexpr int TXQ = DMA_TXQ, SQ = 20, HALO = 8, W = 2 * HW + 1, ROWS = TY + 2 * HW, NB = DMA_NB;
     static constexpr int NT = 16 * TY, NWAVE = NT / 64;
     static constexpr int NQ = ROWS * SQ;               // quads of a staged tile
     static constexpr int NP = (NQ + 63) / 64;          // its DMA pieces (1 KB each; the last one padded)
     static constexpr int TILEQ = NP * 64;
-    static constexpr int SEQ = 320;                    // capacity of the request list (launcher: ts <= 256)
-    static constexpr size_t LDS_BYTES = (size_t)(NB * TILEQ + ROWS * TXQ) * 16 + (SEQ + 1) * 4;
+    static constexpr size_t LDS_BYTES = (size_t)(NB * TILEQ + ROWS * TXQ) * 16 + (DMA_SEQ + 1) * 4;
     static_assert((NP + NWAVE - 1) / NWAVE == 2, "two pieces per wave and request");
     static_assert(HW <= HALO, "halo too small");
 };
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
 {
     typedef XyzGeom<HW, TY> G;
     constexpr int TXQ = G::TXQ, SQ = G::SQ, HALO = G::HALO, W = G::W, ROWS = G::ROWS, NB = G::NB, NT = G::NT;
-    constexpr int NWAVE = G::NWAVE, NQ = G::NQ, NP = G::NP, TILEQ = G::TILEQ, SEQ = G::SEQ;
+    constexpr int NWAVE = G::NWAVE, NQ = G::NQ, NP = G::NP, TILEQ = G::TILEQ;
     extern __shared__ float4 smem[];
     float4 *const stg = smem;                          // [NB][TILEQ]: staged source rows, SQ quads each
     float4 *const xf = smem + NB * TILEQ;              // [ROWS][TXQ]: the x-filtered rows of the open request
@@ -69,30 +68,6 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int endz = nl1, endy = ny - 1, endx = nx - 1;
     const int p0 = blockIdx.z * P.ts;
     const int p1 = min(p0 + P.ts, P.nz);
-
-    // the requests of this workgroup in the order the sweep consumes them (as k_fir_yz_dma)
-    if (tid == 0) {
-        int n = 0;
-        for (int i = p0 - HW; i < p1 + HW && n + 2 <= SEQ; i++) {
-            if (i < 0) {
-                seq[n++] = clampi(-i, 0, nl1);
-            } else if (i >= endz) {
-                const int m = i - endz;
-                if (m <= HW) {
-                    int lo = 0;
-                    for (int mm = 0; mm <= HW; mm++)
-                        lo = mm == m ? Ez.lo[mm] : lo;
-                    seq[n++] = clampi(lo, 0, nl1);
-                    seq[n++] = clampi(lo + 1, 0, nl1);
-                }
-            } else {
-                seq[n++] = i;
-            }
-        }
-        seq[SEQ] = n;
-    }
-    __syncthreads();
-    const int nreq = __builtin_amdgcn_readfirstlane(seq[SEQ]);
 
     // DMA pieces of this wave: piece pc = NWAVE k + wave (beyond the tile: the last piece once more -- the same
     // bytes to the same place -- so that every wave has two pieces per request in flight); lane -> flat quad
@@ -113,32 +88,13 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
         pcoff[k] = (uint32_t)__builtin_amdgcn_readfirstlane(pc * 1024);
     }
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4 *)stg;
-    auto stage = [&](int t) {
-        // request t (clamped: beyond the list a harmless re-request keeps the count of pieces in flight)
-        const int pl = __builtin_amdgcn_readfirstlane(seq[min(t, nreq - 1)]);
+    auto issue = [&](int pl, int b) {
         const float *src = P.src + (size_t)pl * plane;
-        const uint32_t tb = lds0 + (uint32_t)((t & (NB - 1)) * (TILEQ * 16));
-        unsigned keep;
+        const uint32_t tb = lds0 + (uint32_t)(b * (TILEQ * 16));
 #pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const float *g = src + srcoff[k];
-            const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tb + pcoff[k]));
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-        }
+        for (int k = 0; k < 2; k++)
+            dma_load_lds_16(src + srcoff[k], (uint32_t)__builtin_amdgcn_readfirstlane((int)(tb + pcoff[k])));
     };
-    // wait until at most n of this wave's vector-memory operations are outstanding, then the barrier
-    auto wait_barrier = [&](int n) {
-        switch (n) {
-        case 4: asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)\n\ts_barrier" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(7)\n\ts_barrier" ::: "memory"); break;
-        }
-    };
-    // the barrier between two phases that hand data over in LDS
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-
     // x edges (block-uniform): the first tile column mirrors E[-e] = src[e], e = 1 .. HALO; the last one forms
     // E[endx + m], m = 0 .. HW.  Thread -> (row tid / 16 [+ TY], sample tid % 16); positions in floats from the
     // row's start, source sample s at HALO + s - x0
@@ -154,43 +110,22 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
             xw1 = Ex.w1[mm];
         }
     xpos = clampi(xpos, 0, 4 * SQ - 2);
-    // virtual rows E[endy + m], m = 0 .. HW, of this tile (the last tile row of the volume only)
-    const bool yedge = y0 + TY + HW > endy;                    // block-uniform
-    const int em = tid >> 4;                                   // this thread's m (tid < 16 (HW + 1))
-    const int ej = endy + em - (y0 - HW);                      // its tile row
-    const bool efix = yedge && em <= HW && ej < ROWS;
-    int elo = 0;
-    float ew0 = 0.0f, ew1 = 0.0f;
-#pragma unroll
-    for (int mm = 0; mm <= HW; mm++)
-        if (mm == em) {
-            elo = Ey.lo[mm] - (y0 - HW);
-            ew0 = Ey.w0[mm];
-            ew1 = Ey.w1[mm];
-        }
+    const DmaYEdge<HW, ROWS> ye(Ey, y0, TY, endy, ty, qx);
     float smax = 1.0f;
     if (SCALED) {
         smax = *P.scale_max;
         smax = smax != 0.0f ? smax : 1.0f;                     // imutil.c:706-707 (then every sample is 0)
     }
-    int t = 0;          // next request to be consumed
-    int shist = 0;      // stores of the last three iterations (bits 0..2; every wave of a whole tile stores)
-    stage(0);
-    stage(1);
-    stage(2);
-    // x- and y-filtered value of this thread's column for the next request of the list
-    auto xyfilt = [&]() -> float4 {
-        // younger than the pieces of request t: those of t + 1 and t + 2, and this wave's recent stores
-        wait_barrier(4 + __builtin_popcount(shist));
-        stage(t + NB - 1);
-        float4 *const tile = stg + (t & (NB - 1)) * TILEQ;
+    // x- and y-filtered value of this thread's column from staged tile b
+    auto filter = [&](int b) -> float4 {
+        float4 *const tile = stg + b * TILEQ;
         if (SCALED) {
             for (int f = tid; f < NQ; f += NT) {
                 float4 q = tile[f];
                 q.x = q.x / smax; q.y = q.y / smax; q.z = q.z / smax; q.w = q.w / smax;   // imutil.c:711
                 tile[f] = q;
             }
-            lds_barrier();
+            dma_lds_barrier();
         }
         if (xlo || xhi) {
             for (int r = tid >> 4; r < ROWS; r += TY) {
@@ -202,7 +137,7 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
                     row[HALO + 4 * TXQ - 1 + xe] = xw0 * a + xw1 * c;
                 }
             }
-            lds_barrier();
+            dma_lds_barrier();
         }
         // x phase: row-quad (r, qx) of the tile, r = ty and (the first 2 HW rows of threads) ty + TY
 #pragma unroll
@@ -227,63 +162,18 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 xf[r * TXQ + qx] = make_float4(o[0], o[1], o[2], o[3]);
             }
         }
-        lds_barrier();
-        if (yedge) {
-            if (efix) {
-                const float4 a = xf[clampi(elo, 0, ROWS - 1) * TXQ + qx], c = xf[clampi(elo + 1, 0, ROWS - 1) * TXQ + qx];
-                xf[ej * TXQ + qx] = Vec<4>::lerp(ew0, a, ew1, c);
-            }
-            lds_barrier();
-        }
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int dd = -HW; dd <= HW; dd++)
-            Vec<4>::mac(acc, T.k[dd + HW], xf[(ty + HW - dd) * TXQ + qx]);
-        t++;
-        return acc;
+        dma_lds_barrier();
+        return dma_filter_y<HW>(T, ye, xf, qx);
     };
-    // extended-z plane i (outside the volume at the faces): one or two requests (as k_fir_yz_dma)
-    auto ext_z = [&](int i, bool stores) -> float4 {
-        // (the one-request path of its own, as in k_fir_yz_dma, up to 11 taps only: a second inlined copy of the
-        // x phase per ring position puts the ring of the 13- and 15-tap instances into scratch -- 960 and 992
-        // bytes per lane --; the 17-tap instance never had that path, as in k_fir_yz_dma)
-        if (HW < 6 && i < endz) {
-            const float4 yv = xyfilt();
-            shist = ((shist << 1) | (int)stores) & 7;
-            return yv;
-        }
-        int np = 1;
-        float w0 = 1.0f, w1 = 0.0f;
-        if (i >= endz) {
-            const int m = i - endz;
-            np = m > HW ? 0 : 2;
-#pragma unroll
-            for (int mm = 0; mm <= HW; mm++)
-                if (mm == m) {
-                    w0 = Ez.w0[mm];
-                    w1 = Ez.w1[mm];
-                }
-        }
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 1
-        for (int k = 0; k < np; k++) {
-            const float4 yv = xyfilt();
-            // (the store that follows this plane belongs to the LAST of its requests)
-            shist = ((shist << 1) | (int)(stores && k + 1 == np)) & 7;
-            if (k == 0)
-                a = yv;
-            else
-                a = Vec<4>::lerp(w0, a, w1, yv);
-        }
-        if (np == 0)
-            shist = ((shist << 1) | (int)stores) & 7;   // (a store without a request)
-        return a;
-    };
-
+    DmaSweep s = dma_begin<HW>(seq, Ez, 2, p0, p1, 0, endz, P.nz - 1, issue);
+    // extended-z plane r; the one-request path up to 11 taps (see dma_ext_z)
+    auto ext_z = [&](int r, bool stores) -> float4 { return dma_ext_z<HW, 5>(s, Ez, r, endz, stores, issue, filter); };
+    // the z ring, as in k_fir_yz_dma (every wave of a whole tile stores)
     float4 ring[W];
 #pragma unroll
     for (int i = 0; i < W; i++)
         ring[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // warm-up: planes p0 - HW .. p0 + HW - 1 into ring[0 .. 2*HW - 1] (static positions)
 #pragma unroll
     for (int i = 0; i < 2 * HW; i++)
         ring[i] = ext_z(p0 - HW + i, false);
@@ -303,8 +193,7 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
             }
         }
     }
-    // (the re-requests beyond the list are still in flight: they write LDS only)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dma_drain();
 }
 
 template <int HW, int TY, bool SCALED>
@@ -369,30 +258,13 @@ int sift3d_hip_fir_xyz(const float *d_src, float *d_dst, int nx, int ny, int nz,
         return launch_fail("sift3d_hip_fir_xyz", "source and destination overlap");
     FirParams P;
     FirTaps T;
-    memset(&T, 0, sizeof(T));
-    memcpy(T.k, taps, sizeof(float) * width);
-    memset(&P, 0, sizeof(P));
-    P.src = d_src; P.dst = d_dst;
-    P.nx = nx; P.ny = ny; P.nz = nz;
-    P.axis = 2; P.hw = hw; P.uf = 1.0f; P.uhw = hw;
-    P.n_glob = nz; P.z_hi = nz;
+    fir_dma_fill(&P, &T, d_src, d_dst, nx, ny, nz, taps, width);
     P.scale_max = d_scale_max;
-    // z segmentation as sift3d_hip_fir_yz_u1: >= 512 workgroups, segments of at least 32 planes and at most
-    // 256 (the request list)
-    long nseg;
-    {
-        const long blocks_xy = (long)(nx / 64) * (ny / 32);
-        const long want = (512 + blocks_xy - 1) / blocks_xy;
-        const long cap = nz / 32 > 1 ? nz / 32 : 1;
-        nseg = want < cap ? want : cap;
-        if ((nz + nseg - 1) / nseg > 256)
-            nseg = (nz + 255) / 256;
-        P.ts = (int)((nz + nseg - 1) / nseg);
-        nseg = (nz + P.ts - 1) / P.ts;
-    }
+    int nseg;
+    fir_dma_segments((long)(nx / 64) * (ny / 32), nz, &P.ts, &nseg);
     const EdgeTab Ex = edge_table(nx, hw), Ey = edge_table(ny, hw), Ez = edge_table(nz, hw);
     hipError_t e = hipSuccess;
-    dispatch_int_or<1, 8, 8>(hw, [&](auto H) { e = launch_fir_xyz<decltype(H)::value>(P, T, Ex, Ey, Ez, (int)nseg, st); });
+    dispatch_int_or<1, 8, 8>(hw, [&](auto H) { e = launch_fir_xyz<decltype(H)::value>(P, T, Ex, Ey, Ez, nseg, st); });
     HIPCHK(e);
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;

@@ -1,11 +1,13 @@
-// sift3d_fir_yz.hip -- the fused y + z pass of the octave-0 blurs (k_fir_yz_u1) and its C entry.
+// sift3d_fir_yz.hip -- the fused y + z pass of the octave-0 blurs and its C entry: k_fir_yz_u1 (rows loaded
+// through registers, any tile), k_fir_yz_dma (whole 64 x 64 tiles: its staging geometry and y taps; the LDS-DMA
+// pipeline and z sweep it shares with k_fir_xyz_dma are in sift3d_fir_dma.h), and launch_fir_yz, which picks.
 //
 // A translation unit of its own because it is compiled with -fno-slp-vectorize: the SLP
 // vectoriser packs the float4 arithmetic into v_pk_* instructions, which issue no faster on
 // gfx950 but cost this kernel ~40 more VGPRs (a workgroup of 512 threads then no longer fits
 // twice on a CU); the other FIR kernels keep the default (their register-ring sweeps spill
 // without it).  Numerical contract and citations as in sift3d_kernels.hip.
-#include "sift3d_kernels_common.h"
+#include "sift3d_fir_dma.h"
 
 // ---- fused y + z passes, unit factor 1 -------------------------------------------------------
 // dst = FIR_z(FIR_y(src)) without the y-pass result ever reaching HBM.  A workgroup owns a
@@ -219,31 +221,18 @@ __global__ __launch_bounds__(TXQ * TY) __attribute__((amdgpu_waves_per_eu(4, 4))
 }
 
 // ---- the same pass with the tile rows staged by LDS-DMA, three planes ahead ---------------------
-// k_fir_yz_u1 above is bound by latency, not by bytes or arithmetic: one workgroup per CU, one barrier
-// per plane, and the rows of plane p + 1 are requested only while plane p is filtered (the 17-tap
-// instance, which has no registers left for that, requests them when it needs them): 17-20 KB in flight
-// per CU against the ~50 KB that 6 TB/s need at ~2 us of loaded latency; 2.0 (5 taps) to 2.8 us (17 taps)
-// per plane where the arithmetic of a plane takes 0.3-1.1.  Here a plane's TY + 2 HW rows go from HBM
-// straight into one of FOUR LDS tiles (global_load_lds_dwordx4: no staging registers, no ds_write), three
-// requests ahead of the one being filtered: request t + 3 is issued right after the barrier that opens
-// request t -- the buffer it overwrites was last read before that barrier --, each wave waits for its own
-// pieces of request t with a COUNTED s_waitcnt vmcnt(N) before the barrier (N = the younger DMA pieces
-// and stores of the wave, tracked per iteration), never vmcnt(0).  The DMA is inline assembly, so the
-// compiler neither counts it nor drains it (cdna_hip_programming.md, 5.7); the output stores are the
-// only vector-memory operations it sees.  Edges as in k_fir_yz_u1: mirrored rows and planes are source
-// ADDRESSES; the virtual rows of the high y face (E[ny - 1 + m], imutil.c:846-848) are formed in LDS from
-// the two staged rows they interpolate, by the workgroups of the last tile row only (one more barrier
-// there); virtual planes of the high z face from two y-filtered planes, as before.  Arithmetic and tap
-// order are those of the separate passes: bit-identical results.
+// The pipeline (request list, counted waits, z ring) is dma_sweep_z's: see sift3d_fir_dma.h.  This kernel's part
+// is the staging geometry -- a plane's TY + 2 HW rows of 16 quads, extended along y by source ADDRESS (mirrored
+// rows; the real row ny - 1 where a virtual one will be formed) -- and the y taps on the staged tile.  Measured
+// per plane against k_fir_yz_u1: 2.0 (5 taps) to 2.8 us (17 taps) there, where the arithmetic takes 0.3-1.1.
 template <int HW, int TY>
 __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_fir_yz_dma(FirParams P, FirTaps T, EdgeTab Ey, EdgeTab Ez)
 {
-    constexpr int TXQ = 16, W = 2 * HW + 1, ROWS = TY + 2 * HW, ROWS4 = (ROWS + 3) & ~3, NB = 4;
+    constexpr int TXQ = DMA_TXQ, W = 2 * HW + 1, ROWS = TY + 2 * HW, ROWS4 = (ROWS + 3) & ~3, NB = DMA_NB;
     static_assert(2 * HW <= TY && (TY & 3) == 0, "at most two pieces per wave and request");
     constexpr int ND2 = (ROWS4 - TY) / 4;     // waves that stage a second piece (rows TY ..) per request
-    constexpr int SEQ = 320;                  // capacity of the request list (launcher: ts <= 256)
     __shared__ float4 tile[NB][ROWS4][TXQ];
-    __shared__ int seq[SEQ + 1];
+    __shared__ int seq[DMA_SEQ + 1];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int qx = tid % TXQ, ty = tid / TXQ;
@@ -253,37 +242,9 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int nx = P.nx, ny = P.ny;
     const size_t plane = (size_t)nx * ny;
     const bool writer = x < nx && y < ny;
-    const int nl1 = P.nz - 1;
-    const int off = P.off, endz = P.n_glob - 1, endy = ny - 1;
+    const int endy = ny - 1;
     const int p0 = P.z_lo + blockIdx.z * P.ts;
     const int p1 = min(p0 + P.ts, P.z_hi);
-
-    // the y-filter requests of this workgroup, in the order the sweep consumes them: local plane indices
-    // (extended plane r = p0 - HW .. p1 - 1 + HW: its mirror image at the low face, the two planes a
-    // virtual plane interpolates at the high face, none beyond the taps' reach)
-    if (tid == 0) {
-        int n = 0;
-        for (int r = p0 - HW; r < p1 + HW && n + 2 <= SEQ; r++) {
-            const int i = r + off;
-            if (i < 0) {
-                seq[n++] = clampi(-i - off, 0, nl1);
-            } else if (i >= endz) {
-                const int m = i - endz;
-                if (m <= HW) {
-                    int lo = 0;
-                    for (int mm = 0; mm <= HW; mm++)
-                        lo = mm == m ? Ez.lo[mm] : lo;
-                    seq[n++] = clampi(lo - off, 0, nl1);
-                    seq[n++] = clampi(lo + 1 - off, 0, nl1);
-                }
-            } else {
-                seq[n++] = clampi(r, 0, nl1);
-            }
-        }
-        seq[SEQ] = n;
-    }
-    __syncthreads();
-    const int nreq = __builtin_amdgcn_readfirstlane(seq[SEQ]);
 
     // DMA pieces of this wave: piece k covers tile rows 64 k + 4 wave .. + 3 (1 KB = 4 rows of 16 quads);
     // lane -> (row, quad); the source row of tile row j is extended-y index i = y0 - HW + j
@@ -299,126 +260,31 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
     }
     const bool two = wave < ND2;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4 *)&tile[0][0][0];
-    auto stage = [&](int t) {
-        // request t (clamped: beyond the list a harmless re-request keeps the count of pieces in flight)
-        const int pl = __builtin_amdgcn_readfirstlane(seq[min(t, nreq - 1)]);
+    auto issue = [&](int pl, int b) {
         const float *src = P.src + (size_t)pl * plane;
         const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane(
-            (int)(lds0 + (uint32_t)((t & (NB - 1)) * (ROWS4 * TXQ * 16) + 4 * wave * (TXQ * 16))));
-        unsigned keep;
-        const float *g0 = src + srcoff[0];
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(g0), "s"(dst) : "memory");
-        if (two) {
-            const float *g1 = src + srcoff[1];
-            const uint32_t dst1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dst + TY * (TXQ * 16)));
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(g1), "s"(dst1) : "memory");
-        }
+            (int)(lds0 + (uint32_t)(b * (ROWS4 * TXQ * 16) + 4 * wave * (TXQ * 16))));
+        dma_load_lds_16(src + srcoff[0], dst);
+        if (two)
+            dma_load_lds_16(src + srcoff[1], (uint32_t)__builtin_amdgcn_readfirstlane((int)(dst + TY * (TXQ * 16))));
     };
-    // wait until at most n of this wave's vector-memory operations are outstanding, then the barrier
-    auto wait_barrier = [&](int n) {
-        switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)\n\ts_barrier" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)\n\ts_barrier" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)\n\ts_barrier" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(7)\n\ts_barrier" ::: "memory"); break;
-        }
-    };
+    const DmaYEdge<HW, ROWS> ye(Ey, y0, TY, endy, ty, qx);
+    auto filter = [&](int b) -> float4 { return dma_filter_y<HW>(T, ye, &tile[b][0][0], qx); };
     // does this wave issue a store per output plane at all (else it must not count them)
     const bool wave_stores = __builtin_amdgcn_readfirstlane((int)(__ballot(writer) != 0ull)) != 0;
-    // virtual rows E[endy + m], m = 0 .. HW, of this tile (the last tile row of the volume only)
-    const bool yedge = y0 + TY + HW > endy;                    // block-uniform
-    const int em = tid >> 4;                                   // this thread's m (tid < 16 (HW + 1))
-    const int ej = endy + em - (y0 - HW);                      // its tile row
-    const bool efix = yedge && em <= HW && ej < ROWS;
-    int elo = 0;
-    float ew0 = 0.0f, ew1 = 0.0f;
-#pragma unroll
-    for (int mm = 0; mm <= HW; mm++)
-        if (mm == em) {
-            elo = Ey.lo[mm] - (y0 - HW);
-            ew0 = Ey.w0[mm];
-            ew1 = Ey.w1[mm];
-        }
-
-    int t = 0;          // next request to be consumed
-    int shist = 0;      // stores of the last three iterations (bits 0..2)
-    const int nd = two ? 2 : 1;
-    stage(0);
-    stage(1);
-    stage(2);
-    // y-filtered value of this thread's column for the next request of the list
-    auto yfilt = [&]() -> float4 {
-        // younger than the pieces of request t: those of t + 1 and t + 2, and this wave's recent stores
-        wait_barrier(2 * nd + __builtin_popcount(shist));
-        stage(t + NB - 1);
-        const int b = t & (NB - 1);
-        if (yedge) {
-            if (efix) {
-                const float4 a = tile[b][clampi(elo, 0, ROWS - 1)][qx], c = tile[b][clampi(elo + 1, 0, ROWS - 1)][qx];
-                tile[b][ej][qx] = Vec<4>::lerp(ew0, a, ew1, c);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int dd = -HW; dd <= HW; dd++)
-            Vec<4>::mac(acc, T.k[dd + HW], tile[b][ty + HW - dd][qx]);
-        t++;
-        return acc;
-    };
-    // extended-z plane r (local index; outside the slab at the global faces): one or two requests
+    DmaSweep s = dma_begin<HW>(seq, Ez, two ? 2 : 1, p0, p1, P.off, P.n_glob - 1, P.nz - 1, issue);
+    // extended-z plane r (local index); the one-request path at every width but 17 taps
     auto ext_z = [&](int r, bool stores) -> float4 {
-        const int i = r + off;
-        // Every plane but the high face's virtual ones (block-uniform) takes ONE request and nothing else: as a
-        // path of its own it frees the plane loop of the selects and copies that merged it with the two-request
-        // case (~65 of ~340 vector instructions per plane at 13 taps, and the wide instances are bound by their
-        // vector instructions): the 13-tap launch in the step 0.44-0.45 -> 0.39-0.41 ms, the pyramid alone 3.55-3.59
-        // -> 3.48-3.54 ms, bit-identical.  (Not at 17 taps: there the second path costs the register allocator
-        // 72 dwords of scratch.)
-        if (HW < 8 && i < endz) {
-            const float4 yv = yfilt();
-            shist = ((shist << 1) | (int)(stores && wave_stores)) & 7;
-            return yv;
-        }
-        int np = 1;
-        float w0 = 1.0f, w1 = 0.0f;
-        if (i >= endz) {
-            const int m = i - endz;
-            np = m > HW ? 0 : 2;
-#pragma unroll
-            for (int mm = 0; mm <= HW; mm++)
-                if (mm == m) {
-                    w0 = Ez.w0[mm];
-                    w1 = Ez.w1[mm];
-                }
-        }
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 1
-        for (int k = 0; k < np; k++) {
-            const float4 yv = yfilt();
-            // (the store that follows this plane belongs to the LAST of its requests)
-            shist = ((shist << 1) | (int)(stores && wave_stores && k + 1 == np)) & 7;
-            // (block-uniform; the second request of a virtual plane interpolates in place: w0 * first + w1 * second)
-            if (k == 0)
-                a = yv;
-            else
-                a = Vec<4>::lerp(w0, a, w1, yv);
-        }
-        if (np == 0)
-            shist = ((shist << 1) | (int)(stores && wave_stores)) & 7;   // (a store without a request)
-        return a;
+        return dma_ext_z<HW, 7>(s, Ez, r + P.off, P.n_glob - 1, stores, issue, filter);
     };
-
+    // Register window along z: the 2*HW+1 most recent extended planes.  The loop is unrolled W times so that every
+    // ring position is a compile-time register (as in k_fir_sweep_u1): at step j the window of output q holds plane
+    // q - HW + i in ring[(j + i) % W] -- nothing is ever shifted.
     float4 ring[W];
 #pragma unroll
     for (int i = 0; i < W; i++)
         ring[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // warm-up: planes p0 - HW .. p0 + HW - 1 into ring[0 .. 2*HW - 1] (static positions)
 #pragma unroll
     for (int i = 0; i < 2 * HW; i++)
         ring[i] = ext_z(p0 - HW + i, false);
@@ -429,7 +295,7 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
         for (int j = 0; j < W; j++) {
             const int q = q0 + j;
             if (q < p1) {                              // block-uniform
-                ring[(j + 2 * HW) % W] = ext_z(q + HW, true);
+                ring[(j + 2 * HW) % W] = ext_z(q + HW, wave_stores);
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                 for (int dd = -HW; dd <= HW; dd++)
@@ -439,21 +305,18 @@ __global__ __launch_bounds__(16 * TY) __attribute__((amdgpu_waves_per_eu(4, 4)))
             }
         }
     }
-    // (the re-requests beyond the list are still in flight: they write LDS only, and a wave's
-    // vector-memory operations complete before its program ends)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dma_drain();
 }
 
 template <int HW>
 static void launch_fir_yz(const FirParams &P, const FirTaps &T, const EdgeTab &Ey, const EdgeTab &Ez,
-                          int ty, hipStream_t st)
+                          int ty, int nseg, hipStream_t st)
 {
-    const int nseg = (P.z_hi - P.z_lo + P.ts - 1) / P.ts;
     // 64(x) x 64(y) tiles on tall volumes: half the halo rows of a 32-row tile per output row (measured
     // at 512^3: 1-2 % faster at 5-7 taps, 3-4.5 % at 9-17 taps than 128 x 32); else 128(x) x 32(y) where
     // the rows fill them (512-byte row segments; 2 % faster over the octave-0 pyramid than 64 x 32),
     // 64 x 32 otherwise
-    if ((P.nx & 63) == 0 && (P.ny & 63) == 0 && P.ny >= 128 && P.ts <= 256) {
+    if ((P.nx & 63) == 0 && (P.ny & 63) == 0 && P.ny >= 128 && P.ts <= DMA_MAX_TS) {
         // whole 64 x 64 tiles: rows staged by LDS-DMA, three planes ahead
         // tile height (measured at 512^3, ms, 64 / 32 rows: 5 taps 0.22 / 0.24, 7 taps 0.26 / 0.25, 11 taps
         // 0.32 / 0.31, 17 taps 0.41 / 0.40): two 32-row workgroups per CU hide each other's barriers, a
@@ -500,41 +363,14 @@ int sift3d_hip_fir_yz_u1(const float *d_src, float *d_dst, int nx, int ny, int n
         return SIFT3D_SUCCESS;
     FirParams P;
     FirTaps T;
-    memset(&T, 0, sizeof(T));
-    memcpy(T.k, taps, sizeof(float) * width);
-    memset(&P, 0, sizeof(P));
-    P.src = d_src; P.dst = d_dst;
-    P.nx = nx; P.ny = ny; P.nz = nz;
-    P.axis = 2; P.hw = hw; P.uf = 1.0f; P.uhw = hw;
+    fir_dma_fill(&P, &T, d_src, d_dst, nx, ny, nz, taps, width);
     P.n_glob = n_glob; P.off = off; P.z_lo = z_lo; P.z_hi = z_hi;
     // (tile height of the 64 x 32 fallback; the launcher picks the tile)
     const int ty = 32;
-    {
-        // z segmentation: >= 4096 waves in flight, segments of at least 32 planes
-        long blocks_xy = (long)((nx / 4 + 15) / 16) * ((ny + ty - 1) / ty);
-        if (blocks_xy < 1)
-            blocks_xy = 1;
-        const int n_out = z_hi - z_lo;
-        long want = (512 + blocks_xy - 1) / blocks_xy;
-        long cap = n_out / 32 > 1 ? n_out / 32 : 1;
-        long nseg = want < cap ? want : cap;
-        if (nseg < 1)
-            nseg = 1;
-        if ((n_out + nseg - 1) / nseg > 256)         /* (k_fir_yz_dma's request list) */
-            nseg = (n_out + 255) / 256;
-        P.ts = (int)((n_out + nseg - 1) / nseg);
-    }
+    int nseg;
+    fir_dma_segments((long)((nx / 4 + 15) / 16) * ((ny + ty - 1) / ty), z_hi - z_lo, &P.ts, &nseg);
     const EdgeTab Ey = edge_table(ny, hw), Ez = edge_table(n_glob, hw);
-    switch (hw) {
-    case 1: launch_fir_yz<1>(P, T, Ey, Ez, ty, st); break;
-    case 2: launch_fir_yz<2>(P, T, Ey, Ez, ty, st); break;
-    case 3: launch_fir_yz<3>(P, T, Ey, Ez, ty, st); break;
-    case 4: launch_fir_yz<4>(P, T, Ey, Ez, ty, st); break;
-    case 5: launch_fir_yz<5>(P, T, Ey, Ez, ty, st); break;
-    case 6: launch_fir_yz<6>(P, T, Ey, Ez, ty, st); break;
-    case 7: launch_fir_yz<7>(P, T, Ey, Ez, ty, st); break;
-    default: launch_fir_yz<8>(P, T, Ey, Ez, ty, st); break;
-    }
+    dispatch_int_or<1, 8, 8>(hw, [&](auto H) { launch_fir_yz<decltype(H)::value>(P, T, Ey, Ez, ty, nseg, st); });
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;
 }
