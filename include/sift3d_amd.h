@@ -655,6 +655,150 @@ sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, const 
                                 sift3d_amd_affine_refine_result *result, void *d_work, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* B-spline free-form deformation: an intensity-driven control lattice       */
+/* ------------------------------------------------------------------------ */
+/* A cubic B-spline free-form deformation (FFD) of the fixed grid, driven by the mean squared difference between a
+ * fixed volume F[oz][oy][ox] and a moving volume M[nz][ny][nx], with an explicit bending-energy penalty.  No upstream
+ * counterpart: PARITY UNPINNED, pinned to this contract and its numpy restatement (tests/ffd_restatement.py).
+ *
+ * Lattice.  c[3][gz][gy][gx] float32, channels x, y, z in voxels of the fixed grid, a pull map like every field.  The
+ * spacing delta = (dx, dy, dz) is integer, 1 <= delta <= SIFT3D_AMD_FFD_MAX_SPACING.  Along an axis of o voxels control
+ * i sits at voxel (i - 1) * delta and g = (o - 1) / delta + 4 (integer division; sift3d_amd_ffd_lattice_dim).  Voxel x
+ * has i0 = x / delta, r = x % delta and the four weights w[r][0..3] on the controls i0 .. i0 + 3.  The table w[delta][4]
+ * (sift3d_amd_ffd_weights, host) is made in double and rounded to float, with t = (double) r / (double) delta,
+ * u = 1.0 - t, t2 = t * t, t3 = t2 * t, every operation in this order and unfused:
+ *     w[r][0] = (float)(((u * u) * u) / 6.0)
+ *     w[r][1] = (float)(((3.0 * t3 - 6.0 * t2) + 4.0) / 6.0)
+ *     w[r][2] = (float)((((-3.0 * t3 + 3.0 * t2) + 3.0 * t) + 1.0) / 6.0)
+ *     w[r][3] = (float)(t3 / 6.0)
+ *
+ * Spline value.  s_d(p) = sum_c sum_b sum_a wz[c] * (wy[b] * (wx[a] * c_d[k0 + c][j0 + b][i0 + a])), float, unfused:
+ * s starts at +0 and takes the 64 terms one by one, c outermost, then b, then a (x innermost), each term the three
+ * multiplications in the order written.
+ *
+ * Field export (sift3d_hip_ffd_field) writes d_field[3][oz][oy][ox].  With A (a 3 x 4 pull map)
+ *     field_d(p) = (float)(pull_d(A, p) - (double) p_d) + s_d(p)            (a float addition),
+ * pull "Resampling"'s, word for word, so the first operand is sift3d_hip_affine_field's value; without A (NULL)
+ * field_d = s_d.  The result is an ordinary field: sift3d_hip_warp_field, sift3d_hip_jacobian_det, the similarity,
+ * cubic resampling, composition and inversion entries take it unchanged.  d_work: sift3d_amd_ffd_field_work_bytes()
+ * bytes, 16-byte aligned (the weight tables, copied there by the call).
+ *
+ * Evaluation (sift3d_hip_ffd_evaluate) exports the field of the lattice to d_field, then per fixed voxel p with
+ * u = field(p): the inside test and LINEAR sample m are sift3d_hip_warp_field's, bit for bit; e = m - f (a float
+ * subtraction); g = the gradient of the sample, as in "Intensity-driven affine refinement"; a voxel that is not inside
+ * adds nothing.  In double E = e, G_d = g_d.  The record, sift3d_amd_ffd_record_bytes() bytes, 8-byte aligned:
+ *     uint64 n;  double S_ee = sum E E;  double R;  double gmax;                        (the head, 32 bytes)
+ *     double Gc[3][gz][gy][gx] = sum_p W(p; k, j, i) E G_d;  double dR[3][gz][gy][gx] = dR / dc
+ * W(p; k, j, i) is the product of the float weights of p on control (k, j, i) along x, y and z, widened to double:
+ * Gc is the adjoint of the spline evaluation applied to the force E G.  How the sum is organised is the
+ * implementation's (here: the force E G_d, exact in double, then one pass per axis, z, y, x, each
+ * sum_x (double) w * v in ascending x), but it is a function of the shapes only, without atomics, every partial slot
+ * reduced in a fixed order: a call repeats its bytes.  Every entry of Gc is within gamma_(k + 8) sum |term| of the
+ * exact sum in double (u = 2^-53), k the number of voxels in the control's support.
+ * Bending energy, on the lattice, over the N = (gx - 2)(gy - 2)(gz - 2) controls that have all 26 neighbours: for
+ * each channel the six second derivatives of the spline at the control's own position by the stencils value
+ * (1/6, 4/6, 1/6), first derivative (-1/2, 0, 1/2) / delta and second derivative (1, -2, 1) / delta^2 per axis (double:
+ * 1.0 / 6.0, 4.0 / 6.0, -0.5 / d, 0.5 / d, 1.0 / (d * d), -2.0 / (d * d)), the coefficient of neighbour (a, b, c)
+ * being (sz[c] * sy[b]) * sx[a] and the 27 products added in ascending (c, b, a), and
+ *     R = (1 / N) sum (s_xx^2 + s_yy^2 + s_zz^2 + 2 s_xy^2 + 2 s_xz^2 + 2 s_yz^2),
+ * dR / dc the exact adjoint of the same stencils, (2 / N) sum m_t coef_t s_t.  A lattice sampled from an affine
+ * function has R = 0 in exact arithmetic.  sift3d_hip_ffd_bending writes R and dR alone into a record (n, S_ee, gmax and
+ * Gc are left untouched).
+ * Cost and gradient: E = S_ee / n + bending * R; d_grad[3][gz][gy][gx] = (float)((2.0 / n) * Gc + bending * dR), formed
+ * in double; gmax = the largest |d_grad| as stored.  n == 0 makes E and the gradient NaN.
+ *
+ * Subdivision (sift3d_hip_ffd_refine2) takes the lattice over the grid o_c = (o + 1) / 2 at spacing delta to the
+ * lattice over o at the same delta, the displacements doubled.  Per axis, fine j = 2 i - 1 takes
+ * ((c[i - 1] + 6 c[i]) + c[i + 1]) * 0.125 and fine j = 2 i takes (c[i] + c[i + 1]) * 0.5; x first, then y, then z, then
+ * * 2, all float.  The largest coarse index needed is floor(floor((o - 1) / delta) / 2) + 3 = g_c - 1.
+ *
+ * Driver (sift3d_amd_ffd_refine_device), steepest descent with a step measured in voxels.  Level l's volumes are
+ * sift3d_hip_restrict2 (scale 1) of level l - 1's, held in d_work; A[:][3] is halved going down a level and doubled
+ * going up; the spacing is the same on every level; the coarsest level runs first from a zero lattice, every other
+ * from the subdivision of the coarser level's.  Per level, with s = step0:
+ *   1. evaluate at c (E, n_first = n; trail entry with accepted = 1).  A non-finite E stops the level (FAILED);
+ *   2. stop when the level has made max_evaluations evaluations (EVALUATIONS) or gmax == 0 (FLAT); else
+ *      c' = c - (float)(s / gmax) * grad (float, unfused) and evaluate at c' (E');
+ *   3. a non-finite E' stops the level (FAILED).  Accept when n' >= min_overlap * n_first and E' < E: c = c', the
+ *      evaluation is the next iteration's, s = min(2 s, step_max).  Otherwise s = s / 2;
+ *   4. stop when s < tol (CONVERGED); else 2.
+ * Each evaluation waits for the stream once, for the 32-byte head; the lattices never leave the device.  The result
+ * holds one entry per evaluation in the order run (E, MSD = S_ee / n, R, n, the step s that led to it, accepted, level),
+ * their number and the stop reason of level 0.  d_lattice receives the final lattice of level 0 and d_field its field
+ * (through A when given).  params == NULL takes the defaults.
+ *
+ * The device entries are asynchronous on `stream` (the driver waits as said), allocate nothing, use 64-bit offsets and
+ * check every argument before any device call: -1 on NULL pointers (A may be NULL), dims <= 0, a spacing outside
+ * [1, SIFT3D_AMD_FFD_MAX_SPACING], a lattice shape that is not g, a non-finite A, a bending weight that is negative or
+ * not finite, misalignment (records 8 bytes, work buffers 16, the rest 4), an output that overlaps an input, the work
+ * buffer or another output, levels outside [1, SIFT3D_AMD_DEMONS_MAX_LEVELS], max_evaluations outside
+ * [1, SIFT3D_AMD_FFD_MAX_EVALUATIONS], step0 <= 0, step_max < step0, tol <= 0, min_overlap outside [0, 1]. */
+#define SIFT3D_AMD_FFD_MAX_SPACING 256
+#define SIFT3D_AMD_FFD_MAX_EVALUATIONS 128         /* per level */
+#define SIFT3D_AMD_FFD_MAX_TRAIL (6 * SIFT3D_AMD_FFD_MAX_EVALUATIONS)          /* SIFT3D_AMD_DEMONS_MAX_LEVELS levels */
+#define SIFT3D_AMD_FFD_RECORD_HEAD_BYTES 32
+#define SIFT3D_AMD_FFD_STOP_CONVERGED 0
+#define SIFT3D_AMD_FFD_STOP_EVALUATIONS 1
+#define SIFT3D_AMD_FFD_STOP_FLAT 2
+#define SIFT3D_AMD_FFD_STOP_FAILED 3
+typedef struct {
+    int spacing[3];            /* 8, 8, 8: dx, dy, dz */
+    int levels;                /* 3 */
+    int max_evaluations;       /* 60, per level */
+    double bending;            /* 0.005 */
+    double step0;              /* 1 voxel: the largest control displacement of a level's first step */
+    double step_max;           /* 4 voxels */
+    double tol;                /* 0.01 voxels */
+    double min_overlap;        /* 0.5 of the level's first count */
+} sift3d_amd_ffd_refine_params;
+typedef struct {
+    double E, msd, R;
+    uint64_t n;
+    double step;
+    int accepted, level;
+} sift3d_amd_ffd_evaluation;
+typedef struct {
+    int evaluations, stop;
+    sift3d_amd_ffd_evaluation trail[SIFT3D_AMD_FFD_MAX_TRAIL];
+} sift3d_amd_ffd_refine_result;
+/* host only: g of an axis (0 for o <= 0 or delta <= 0); the table w[delta][4] (-1 on NULL or a spacing out of range) */
+SIFT3D_AMD_API int sift3d_amd_ffd_lattice_dim(int o, int delta);
+SIFT3D_AMD_API int sift3d_amd_ffd_weights(int delta, float *w);
+/* bytes of the buffers below; 0 for bad arguments */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_field_work_bytes(int dx, int dy, int dz);
+SIFT3D_AMD_API size_t sift3d_amd_ffd_record_bytes(int gx, int gy, int gz);
+SIFT3D_AMD_API size_t sift3d_amd_ffd_evaluate_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz);
+SIFT3D_AMD_API size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz);
+SIFT3D_AMD_API size_t
+sift3d_amd_ffd_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz, int levels);
+SIFT3D_AMD_API int
+sift3d_hip_ffd_field(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                     const double *A /*12 or NULL*/, int ox, int oy, int oz, float *d_field, void *d_work, void *stream);
+SIFT3D_AMD_API int
+sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                        const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                        const double *A /*12 or NULL*/, double bending, float *d_field, void *d_record, float *d_grad,
+                        void *d_work, void *stream);
+SIFT3D_AMD_API int
+sift3d_hip_ffd_bending(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, void *d_record,
+                       void *d_work, void *stream);
+/* (ox, oy, oz) is the FINE grid; d_coarse is the lattice over ((ox + 1) / 2, (oy + 1) / 2, (oz + 1) / 2) */
+SIFT3D_AMD_API int
+sift3d_hip_ffd_refine2(const float *d_coarse, int ox, int oy, int oz, int dx, int dy, int dz, float *d_fine,
+                       void *stream);
+SIFT3D_AMD_API void sift3d_amd_ffd_refine_default_params(sift3d_amd_ffd_refine_params *p);
+/* for bindings that restate the layouts: sizeof the params (0), evaluation (1) and result (2) structs, then
+ * SIFT3D_AMD_FFD_RECORD_HEAD_BYTES (3), SIFT3D_AMD_FFD_MAX_EVALUATIONS (4), the most levels (5),
+ * SIFT3D_AMD_FFD_MAX_SPACING (6); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_refine_struct_bytes(int which);
+/* A [12] on the host or NULL (the identity); waits for `stream` once per evaluation and once at the end */
+SIFT3D_AMD_API int
+sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                             const double *A, const sift3d_amd_ffd_refine_params *params,
+                             sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
+                             void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -1033,6 +1033,103 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
                             slices, k, hip.AFFINE_STOPS[res.stop], warped)
 
 
+# ---- B-spline free-form deformation ---------------------------------------------------------------
+FFDRefinement = collections.namedtuple("FFDRefinement", "lattice spacing A field warped trail stop jacobian")
+FFDEvaluation = collections.namedtuple("FFDEvaluation", "E msd R n step accepted level")
+FFDRegistration = collections.namedtuple("FFDRegistration", "registration refinement")
+
+
+def _ffd_lattice_tensor(lattice, what):
+    import torch
+    if _torch_tensor(lattice):
+        return lattice
+    a = np.ascontiguousarray(lattice, np.float32)
+    if a.ndim != 4 or a.shape[0] != 3:
+        raise ValueError("%s: the lattice must be [3, gz, gy, gx]" % what)
+    if not device_available():
+        raise RuntimeError("%s: no HIP device is available; this library has no CPU path" % what)
+    return torch.from_numpy(a).to("cuda")
+
+
+def ffd_field(lattice, spacing, out_shape, A=None):
+    """The displacement field [3, oz, oy, ox] of a cubic B-spline control lattice [3, gz, gy, gx] (channels x, y, z;
+    voxels of the fixed grid) at integer spacing (an int, or (dx, dy, dz)) over a grid out_shape = (oz, oy, ox),
+    through the 3 x 4 pull map A when given (contract: include/sift3d_amd.h, "B-spline free-form deformation").  A
+    torch CUDA float32 tensor on torch's current stream; warp_field, jacobian_determinant, similarity, resample_cubic,
+    compose_fields and invert_field take it as any field."""
+    import torch
+    from . import hip
+    d = hip.ffd_spacing(spacing, "ffd_field")
+    oz, oy, ox = (int(v) for v in out_shape)
+    if tuple(lattice.shape) != hip.ffd_lattice_shape((oz, oy, ox), d):
+        raise ValueError("ffd_field: the lattice must be %s for this grid and spacing, not %s"
+                         % (hip.ffd_lattice_shape((oz, oy, ox), d), tuple(lattice.shape)))
+    L = _ffd_lattice_tensor(lattice, "ffd_field")
+    A0 = None
+    if A is not None:
+        A0 = _affine_or_none(A)
+        if A0 is None or not np.isfinite(A0).all():
+            raise ValueError("ffd_field: A must be a finite 3 x 4 affine pull map or None")
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=L.device)
+    return hip.ffd_field(L, d, field, A0)
+
+
+def ffd_bending_energy(lattice, spacing):
+    """The bending energy R of a control lattice (the mean over the control points with all 26 neighbours of the
+    squared second derivatives of the spline) and its gradient dR/dc float64 [3, gz, gy, gx], computed on the device.
+    Waits for torch's current stream."""
+    from . import hip
+    L = _ffd_lattice_tensor(lattice, "ffd_bending_energy")
+    return hip.ffd_bending(L, hip.ffd_spacing(spacing, "ffd_bending_energy"))
+
+
+def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, **params):
+    """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
+    `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
+    include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
+    (None: the identity).  spacing: control spacing in voxels, an int or (dx, dy, dz), the same on every level.  params:
+    max_evaluations (per level), step0, step_max, tol (voxels), min_overlap.  The volumes are torch CUDA float32
+    tensors [nz, ny, nx], or Images / arrays, which are uploaded.  Returns FFDRefinement(lattice [3, gz, gy, gx], spacing
+    (dx, dy, dz), A, field [3, oz, oy, ox], warped: `moving` through the field, trail: one FFDEvaluation(E, msd, R, n,
+    step, accepted, level) per evaluation in the order run, stop: "converged", "evaluations", "flat" or "failed" of
+    level 0, jacobian: JacobianStats of the field).  Waits for torch's current stream once per evaluation."""
+    from . import hip
+    d = hip.ffd_spacing(spacing, "refine_ffd")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
+            not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
+        raise ValueError("refine_ffd: levels must be in [1, %d]" % hip.AFFINE_MAX_LEVELS)
+    if "max_evaluations" in params and not 1 <= int(params["max_evaluations"]) <= hip.FFD_MAX_EVALUATIONS:
+        raise ValueError("refine_ffd: max_evaluations must be in [1, %d]" % hip.FFD_MAX_EVALUATIONS)
+    if not (np.isfinite(bending) and bending >= 0):
+        raise ValueError("refine_ffd: bending must be finite and not negative")
+    A0 = None
+    if A is not None:
+        A0 = _affine_or_none(A)
+        if A0 is None or not np.isfinite(A0).all():
+            raise ValueError("refine_ffd: A must be a finite 3 x 4 affine pull map or None")
+    p = hip.ffd_refine_params(spacing=d, levels=int(levels), bending=float(bending), **params)
+    F = _similarity_volume(fixed, "refine_ffd", "fixed")
+    M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
+    res, lattice, field = hip.ffd_refine(F, M, A0, p)
+    trail = [FFDEvaluation(e.E, e.msd, e.R, int(e.n), e.step, bool(e.accepted), e.level)
+             for e in res.trail[:res.evaluations]]
+    return FFDRefinement(lattice, d, A0, field, warp_field(M, field), trail, hip.FFD_STOPS[res.stop],
+                         jacobian_determinant(field))
+
+
+def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
+                 ffd_params=None, **detector_kw):
+    """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
+    pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
+    refine_ffd's further keyword arguments.  The volumes are torch CUDA float32 tensors, or Images / arrays, which are
+    uploaded.  Returns FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""
+    F = _similarity_volume(fixed, "register_ffd", "fixed")
+    M = _similarity_volume(moving, "register_ffd", "moving", F.device)
+    reg = register(M, F, nn_thresh, err_thresh, num_iter, seed, refine=True, **detector_kw)
+    ref = refine_ffd(M, F, reg.refinement.A, spacing, levels, bending, **(ffd_params or {}))
+    return FFDRegistration(reg, ref)
+
+
 def label_overlap(labels_fixed, labels_moving, transform=None, num_labels=None):
     """Overlap of two label volumes (float-valued integers 0 .. L-1, as warp_field(..., interp="nearest") takes
     them), the moving one seen through `transform` (as similarity's) with nearest sampling:

@@ -1,0 +1,525 @@
+/* sift3d_ffd.c -- cubic B-spline free-form deformation: the weight table and the stencils on the host, the checked
+ * device entries (field export, evaluation with gradient, bending energy, subdivision) and the steepest-descent driver
+ * (included at the end of sift3d_host.c, after sift3d_affine_refine.c).
+ *
+ * The contract is in include/sift3d_amd.h, "B-spline free-form deformation"; the kernels are in sift3d_ffd.hip, reached
+ * through the launchers below after the checks here.  Arguments are checked before the device is touched, so bad
+ * input is refused on a machine without a GPU too. */
+
+int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                            const float *d_w, const double *A, int ox, int oy, int oz, float *d_field, void *stream);
+int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                               int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
+                               int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
+                               double *d_rec, float *d_grad, double *d_work, void *stream);
+int sift3d_ffd_step_launch(const float *d_c, const float *d_grad, float a, float *d_out, size_t n, void *stream);
+int sift3d_ffd_refine2_launch(const float *d_c, int cx, int cy, int cz, float *d_f, int fx, int fy, int fz,
+                              void *stream);
+
+int sift3d_amd_ffd_lattice_dim(int o, int delta)
+{
+    return o <= 0 || delta <= 0 ? 0 : (o - 1) / delta + 4;
+}
+
+int sift3d_amd_ffd_weights(int delta, float *w)
+{
+    int r;
+    if (!w || delta <= 0 || delta > SIFT3D_AMD_FFD_MAX_SPACING)
+        return refuse("sift3d_amd_ffd_weights", "NULL table or spacing outside [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    for (r = 0; r < delta; r++) {
+        const double t = (double)r / (double)delta, u = 1.0 - t, t2 = t * t, t3 = t2 * t;
+        w[4 * r + 0] = (float)(((u * u) * u) / 6.0);
+        w[4 * r + 1] = (float)(((3.0 * t3 - 6.0 * t2) + 4.0) / 6.0);
+        w[4 * r + 2] = (float)((((-3.0 * t3 + 3.0 * t2) + 3.0 * t) + 1.0) / 6.0);
+        w[4 * r + 3] = (float)(t3 / 6.0);
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* st[axis][order][tap] of the bending energy */
+static void ffd_stencils(const int *delta, double *st)
+{
+    int a;
+    for (a = 0; a < 3; a++) {
+        const double d = (double)delta[a];
+        double *s = st + 9 * a;
+        s[0] = 1.0 / 6.0; s[1] = 4.0 / 6.0; s[2] = 1.0 / 6.0;
+        s[3] = -0.5 / d; s[4] = 0.0; s[5] = 0.5 / d;
+        s[6] = 1.0 / (d * d); s[7] = -2.0 / (d * d); s[8] = 1.0 / (d * d);
+    }
+}
+
+static int ffd_spacing_ok(int dx, int dy, int dz)
+{
+    return dx >= 1 && dy >= 1 && dz >= 1 && dx <= SIFT3D_AMD_FFD_MAX_SPACING && dy <= SIFT3D_AMD_FFD_MAX_SPACING &&
+           dz <= SIFT3D_AMD_FFD_MAX_SPACING;
+}
+
+static int check_ffd_lattice(const char *what, int ox, int oy, int oz, int gx, int gy, int gz, int dx, int dy, int dz)
+{
+    if (check_dims(what, ox, oy, oz))
+        return SIFT3D_FAILURE;
+    if (!ffd_spacing_ok(dx, dy, dz))
+        return refuse(what, "the spacing must be in [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    if (gx != sift3d_amd_ffd_lattice_dim(ox, dx) || gy != sift3d_amd_ffd_lattice_dim(oy, dy) ||
+        gz != sift3d_amd_ffd_lattice_dim(oz, dz))
+        return refuse(what, "the lattice is not (o - 1) / spacing + 4 along every axis");
+    return SIFT3D_SUCCESS;
+}
+
+static size_t ffd_weights_bytes(int dx, int dy, int dz)
+{
+    return ((size_t)dx + dy + dz) * 4 * sizeof(float);
+}
+
+/* the three tables to d_w, x then y then z (the copy is staged by the runtime before the call returns) */
+static int ffd_upload_weights(int dx, int dy, int dz, float *d_w, void *stream)
+{
+    float w[3 * 4 * SIFT3D_AMD_FFD_MAX_SPACING];
+    sift3d_amd_ffd_weights(dx, w);
+    sift3d_amd_ffd_weights(dy, w + 4 * dx);
+    sift3d_amd_ffd_weights(dz, w + 4 * (dx + dy));
+    return sift3d_hip_memcpy_h2d(d_w, w, ffd_weights_bytes(dx, dy, dz), stream);
+}
+
+size_t sift3d_amd_ffd_field_work_bytes(int dx, int dy, int dz)
+{
+    return ffd_spacing_ok(dx, dy, dz) ? ffd_weights_bytes(dx, dy, dz) : 0;
+}
+
+int sift3d_hip_ffd_field(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
+                         int ox, int oy, int oz, float *d_field, void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_field";
+    if (!d_lattice || !d_field || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_ffd_lattice(what, ox, oy, oz, gx, gy, gz, dx, dy, dz) || (A && check_affine(what, A)) ||
+        check_aligned(what, 0, ADDR(d_lattice) | ADDR(d_field) | ADDR(d_work)))
+        return SIFT3D_FAILURE;
+    if (ADDR(d_work) & 15)
+        return refuse(what, "a buffer is misaligned");
+    {
+        const range_t in[] = { { d_lattice, image_bytes(gx, gy, gz, 3) } };
+        const range_t out[] = { { d_field, field_bytes(ox, oy, oz) }, { d_work, ffd_weights_bytes(dx, dy, dz) } };
+        if (ranges_aliased(out, 2, in, 1))
+            return refuse(what, ALIASED);
+    }
+    if (ffd_upload_weights(dx, dy, dz, (float *)d_work, stream))
+        return SIFT3D_FAILURE;
+    return sift3d_ffd_field_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, (const float *)d_work, A, ox, oy, oz,
+                                   d_field, stream);
+}
+
+/* ---- evaluation ---- */
+
+static size_t pad16(size_t bytes)
+{
+    return (bytes + 15) & ~(size_t)15;
+}
+
+size_t sift3d_amd_ffd_record_bytes(int gx, int gy, int gz)
+{
+    if (gx < 4 || gy < 4 || gz < 4)
+        return 0;
+    return SIFT3D_AMD_FFD_RECORD_HEAD_BYTES + 2 * 3 * grid_voxels(gx, gy, gz) * sizeof(double);
+}
+
+/* doubles of the evaluation's scratch behind the weight tables: partial slots, force, the two intermediate arrays of
+ * the adjoint, the second derivatives */
+static size_t ffd_eval_doubles(int ox, int oy, int oz, int gx, int gy, int gz)
+{
+    return 2 * (size_t)SIFT3D_AMD_SIMILARITY_GRID + 3 * grid_voxels(ox, oy, oz) + 3 * grid_voxels(ox, oy, gz) +
+           3 * grid_voxels(ox, gy, gz) + 18 * grid_voxels(gx - 2, gy - 2, gz - 2);
+}
+
+size_t sift3d_amd_ffd_evaluate_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0 || !ffd_spacing_ok(dx, dy, dz))
+        return 0;
+    return pad16(ffd_weights_bytes(dx, dy, dz)) +
+           ffd_eval_doubles(ox, oy, oz, sift3d_amd_ffd_lattice_dim(ox, dx), sift3d_amd_ffd_lattice_dim(oy, dy),
+                            sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double);
+}
+
+int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                            const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
+                            double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_evaluate";
+    int delta[3];
+    double st[27];
+    if (!d_F || !d_M || !d_lattice || !d_field || !d_record || !d_grad || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_ffd_lattice(what, ox, oy, oz, gx, gy, gz, dx, dy, dz) || check_dims(what, nx, ny, nz) ||
+        (A && check_affine(what, A)))
+        return SIFT3D_FAILURE;
+    if (!isfinite(bending) || bending < 0)
+        return refuse(what, "the bending weight must be finite and not negative");
+    if (check_aligned(what, ADDR(d_record), ADDR(d_F) | ADDR(d_M) | ADDR(d_lattice) | ADDR(d_field) | ADDR(d_grad)))
+        return SIFT3D_FAILURE;
+    if (ADDR(d_work) & 15)
+        return refuse(what, "a buffer is misaligned");
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_lattice, image_bytes(gx, gy, gz, 3) } };
+        const range_t out[] = { { d_field, field_bytes(ox, oy, oz) },
+                                { d_record, sift3d_amd_ffd_record_bytes(gx, gy, gz) },
+                                { d_grad, image_bytes(gx, gy, gz, 3) },
+                                { d_work, sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz) } };
+        if (ranges_aliased(out, 4, in, 3))
+            return refuse(what, ALIASED);
+    }
+    delta[0] = dx; delta[1] = dy; delta[2] = dz;
+    ffd_stencils(delta, st);
+    if (ffd_upload_weights(dx, dy, dz, (float *)d_work, stream) ||
+        sift3d_ffd_field_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, (const float *)d_work, A, ox, oy, oz, d_field,
+                                stream))
+        return SIFT3D_FAILURE;
+    return sift3d_ffd_evaluate_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
+                                      dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
+                                      (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream);
+}
+
+size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz)
+{
+    if (gx < 4 || gy < 4 || gz < 4)
+        return 0;
+    return (2 * (size_t)SIFT3D_AMD_SIMILARITY_GRID + 18 * grid_voxels(gx - 2, gy - 2, gz - 2)) * sizeof(double);
+}
+
+int sift3d_hip_ffd_bending(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, void *d_record,
+                           void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_bending";
+    int delta[3];
+    double st[27];
+    if (!d_lattice || !d_record || !d_work)
+        return refuse(what, "NULL argument");
+    if (gx < 4 || gy < 4 || gz < 4)
+        return refuse(what, "a lattice has at least 4 control points along every axis");
+    if (!ffd_spacing_ok(dx, dy, dz))
+        return refuse(what, "the spacing must be in [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    if (check_aligned(what, ADDR(d_record) | ADDR(d_work), ADDR(d_lattice)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_lattice, image_bytes(gx, gy, gz, 3) } };
+        const range_t out[] = { { d_record, sift3d_amd_ffd_record_bytes(gx, gy, gz) },
+                                { d_work, sift3d_amd_ffd_bending_work_bytes(gx, gy, gz) } };
+        if (ranges_aliased(out, 2, in, 1))
+            return refuse(what, ALIASED);
+    }
+    delta[0] = dx; delta[1] = dy; delta[2] = dz;
+    ffd_stencils(delta, st);
+    /* the launcher's scratch layout with an empty image grid: slots, then D */
+    return sift3d_ffd_evaluate_launch(what, NULL, 0, 0, 0, NULL, 0, 0, 0, NULL, d_lattice, gx, gy, gz, dx, dy, dz, NULL,
+                                      st, 0.0, (double *)d_record, NULL, (double *)d_work, stream);
+}
+
+int sift3d_hip_ffd_refine2(const float *d_coarse, int ox, int oy, int oz, int dx, int dy, int dz, float *d_fine,
+                           void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_refine2";
+    int cx, cy, cz, fx, fy, fz;
+    if (!d_coarse || !d_fine)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz))
+        return SIFT3D_FAILURE;
+    if (!ffd_spacing_ok(dx, dy, dz))
+        return refuse(what, "the spacing must be in [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    if (check_aligned(what, 0, ADDR(d_coarse) | ADDR(d_fine)))
+        return SIFT3D_FAILURE;
+    cx = sift3d_amd_ffd_lattice_dim(multires_half(ox), dx);
+    cy = sift3d_amd_ffd_lattice_dim(multires_half(oy), dy);
+    cz = sift3d_amd_ffd_lattice_dim(multires_half(oz), dz);
+    fx = sift3d_amd_ffd_lattice_dim(ox, dx);
+    fy = sift3d_amd_ffd_lattice_dim(oy, dy);
+    fz = sift3d_amd_ffd_lattice_dim(oz, dz);
+    {
+        const range_t in[] = { { d_coarse, image_bytes(cx, cy, cz, 3) } };
+        const range_t out[] = { { d_fine, image_bytes(fx, fy, fz, 3) } };
+        if (ranges_aliased(out, 1, in, 1))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_ffd_refine2_launch(d_coarse, cx, cy, cz, d_fine, fx, fy, fz, stream);
+}
+
+/* ---- the driver ---- */
+
+void sift3d_amd_ffd_refine_default_params(sift3d_amd_ffd_refine_params *p)
+{
+    if (!p)
+        return;
+    p->spacing[0] = p->spacing[1] = p->spacing[2] = 8;
+    p->levels = 3;
+    p->max_evaluations = 60;
+    p->bending = 0.005;
+    p->step0 = 1.0;
+    p->step_max = 4.0;
+    p->tol = 0.01;
+    p->min_overlap = 0.5;
+}
+
+static int ffd_params_ok(const sift3d_amd_ffd_refine_params *p)
+{
+    return ffd_spacing_ok(p->spacing[0], p->spacing[1], p->spacing[2]) && p->levels >= 1 &&
+           p->levels <= SIFT3D_AMD_DEMONS_MAX_LEVELS && p->max_evaluations >= 1 &&
+           p->max_evaluations <= SIFT3D_AMD_FFD_MAX_EVALUATIONS && isfinite(p->bending) && p->bending >= 0 &&
+           isfinite(p->step0) && p->step0 > 0 && isfinite(p->step_max) && p->step_max >= p->step0 &&
+           isfinite(p->tol) && p->tol > 0 && p->min_overlap >= 0 && p->min_overlap <= 1;
+}
+
+size_t sift3d_amd_ffd_refine_struct_bytes(int which)
+{
+    return which == 0   ? sizeof(sift3d_amd_ffd_refine_params)
+           : which == 1 ? sizeof(sift3d_amd_ffd_evaluation)
+           : which == 2 ? sizeof(sift3d_amd_ffd_refine_result)
+           : which == 3 ? (size_t)SIFT3D_AMD_FFD_RECORD_HEAD_BYTES
+           : which == 4 ? (size_t)SIFT3D_AMD_FFD_MAX_EVALUATIONS
+           : which == 5 ? (size_t)SIFT3D_AMD_DEMONS_MAX_LEVELS
+           : which == 6 ? (size_t)SIFT3D_AMD_FFD_MAX_SPACING
+                        : 0;
+}
+
+/* d_work of the driver, each part padded to 16 bytes: the evaluation's work on the level-0 grid (which covers every
+ * coarser one), the record, five float lattices of level 0's size (c, c', their two gradients, the coarser level's
+ * lattice), then per level l = 1 .. levels-1 the restricted fixed and moving volumes */
+static size_t ffd_lattice_bytes(int ox, int oy, int oz, const int *d)
+{
+    return pad16(image_bytes(sift3d_amd_ffd_lattice_dim(ox, d[0]), sift3d_amd_ffd_lattice_dim(oy, d[1]),
+                             sift3d_amd_ffd_lattice_dim(oz, d[2]), 3));
+}
+
+static size_t ffd_record_pad(int ox, int oy, int oz, const int *d)
+{
+    return pad16(sift3d_amd_ffd_record_bytes(sift3d_amd_ffd_lattice_dim(ox, d[0]), sift3d_amd_ffd_lattice_dim(oy, d[1]),
+                                             sift3d_amd_ffd_lattice_dim(oz, d[2])));
+}
+
+size_t sift3d_amd_ffd_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                        int levels)
+{
+    const int d[3] = { dx, dy, dz };
+    size_t total;
+    int l;
+    if (ox <= 0 || oy <= 0 || oz <= 0 || nx <= 0 || ny <= 0 || nz <= 0 || !ffd_spacing_ok(dx, dy, dz) || levels < 1 ||
+        levels > SIFT3D_AMD_DEMONS_MAX_LEVELS)
+        return 0;
+    total = pad16(sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz)) + ffd_record_pad(ox, oy, oz, d) +
+            5 * ffd_lattice_bytes(ox, oy, oz, d);
+    for (l = 1; l < levels; l++) {
+        ox = multires_half(ox); oy = multires_half(oy); oz = multires_half(oz);
+        nx = multires_half(nx); ny = multires_half(ny); nz = multires_half(nz);
+        total += pad4(grid_voxels(ox, oy, oz)) * sizeof(float) + pad4(grid_voxels(nx, ny, nz)) * sizeof(float);
+    }
+    return total;
+}
+
+typedef struct {
+    const float *F, *M;
+    int ox, oy, oz, nx, ny, nz, gx, gy, gz;
+} ffd_level;
+
+typedef struct {
+    uint64_t n;
+    double see, R, gmax;
+} ffd_head;
+
+typedef struct {
+    const int *d;                                /* spacing */
+    const double *st;                            /* stencils */
+    const float *d_w;
+    double *d_rec, *d_eval;
+    float *d_field;
+    double bending;
+    void *stream;
+} ffd_ctx;
+
+/* one evaluation at lattice c on `lv`: the field, the record, R and the gradient, the head's copy to the host and the
+ * wait for it */
+static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv, const double *A, const float *c,
+                        float *grad, ffd_head *h)
+{
+    return sift3d_ffd_field_launch(what, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, A, lv->ox,
+                                   lv->oy, lv->oz, x->d_field, x->stream) ||
+           sift3d_ffd_evaluate_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
+                                      lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
+                                      x->d_rec, grad, x->d_eval, x->stream) ||
+           sift3d_hip_memcpy_d2h(h, x->d_rec, sizeof(*h), x->stream) || sift3d_hip_stream_sync(x->stream);
+}
+
+static double ffd_cost(const ffd_head *h, double bending)
+{
+    return (h->n ? h->see / (double)h->n : NAN) + bending * h->R;
+}
+
+static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_head *h, double bending, double step, int accepted,
+                      int level)
+{
+    sift3d_amd_ffd_evaluation *e = res->trail + res->evaluations++;
+    e->E = ffd_cost(h, bending);
+    e->msd = h->n ? h->see / (double)h->n : NAN;
+    e->R = h->R;
+    e->n = h->n;
+    e->step = step;
+    e->accepted = accepted;
+    e->level = level;
+}
+
+int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                                 sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
+                                 void *stream)
+{
+    static const char what[] = "sift3d_amd_ffd_refine_device";
+    sift3d_amd_ffd_refine_params prm;
+    ffd_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
+    ffd_head rec, trial;
+    ffd_ctx x;
+    double A[12], st[27];
+    float *c, *ct, *g, *gt, *prev;
+    char *w = (char *)d_work;
+    size_t off, lat;
+    int l, i, have_A = A_in != NULL;
+    if (!d_F || !d_M || !result || !d_lattice || !d_field || !d_work)
+        return refuse(what, "NULL argument");
+    if (params)
+        prm = *params;
+    else
+        sift3d_amd_ffd_refine_default_params(&prm);
+    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) || (A_in && check_affine(what, A_in)))
+        return SIFT3D_FAILURE;
+    if (!ffd_params_ok(&prm))
+        return refuse(what, "a parameter is out of range");
+    if (check_aligned(what, 0, ADDR(d_F) | ADDR(d_M) | ADDR(d_lattice) | ADDR(d_field)))
+        return SIFT3D_FAILURE;
+    if (ADDR(d_work) & 15)
+        return refuse(what, "a buffer is misaligned");
+    lv[0] = (ffd_level){ d_F, d_M, ox, oy, oz, nx, ny, nz, sift3d_amd_ffd_lattice_dim(ox, prm.spacing[0]),
+                         sift3d_amd_ffd_lattice_dim(oy, prm.spacing[1]), sift3d_amd_ffd_lattice_dim(oz, prm.spacing[2]) };
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) } };
+        const range_t out[] = { { d_lattice, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3) },
+                                { d_field, field_bytes(ox, oy, oz) },
+                                { d_work, sift3d_amd_ffd_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0],
+                                                                           prm.spacing[1], prm.spacing[2], prm.levels) } };
+        if (ranges_aliased(out, 3, in, 2))
+            return refuse(what, ALIASED);
+    }
+    result->evaluations = 0;
+    result->stop = SIFT3D_AMD_FFD_STOP_EVALUATIONS;
+    for (i = 0; i < 12; i++)
+        A[i] = have_A ? A_in[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    ffd_stencils(prm.spacing, st);
+    lat = ffd_lattice_bytes(ox, oy, oz, prm.spacing);
+    x.d = prm.spacing;
+    x.st = st;
+    x.d_w = (const float *)w;
+    x.d_eval = (double *)(w + pad16(ffd_weights_bytes(prm.spacing[0], prm.spacing[1], prm.spacing[2])));
+    off = pad16(sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, prm.spacing[0], prm.spacing[1], prm.spacing[2]));
+    x.d_rec = (double *)(w + off);
+    off += ffd_record_pad(ox, oy, oz, prm.spacing);
+    c = (float *)(w + off);
+    ct = (float *)(w + off + lat);
+    g = (float *)(w + off + 2 * lat);
+    gt = (float *)(w + off + 3 * lat);
+    prev = (float *)(w + off + 4 * lat);
+    off += 5 * lat;
+    x.d_field = d_field;
+    x.bending = prm.bending;
+    x.stream = stream;
+    if (ffd_upload_weights(prm.spacing[0], prm.spacing[1], prm.spacing[2], (float *)w, stream))
+        return SIFT3D_FAILURE;
+    for (l = 1; l < prm.levels; l++) {                       /* level l from level l - 1; A's shift halves */
+        const ffd_level *f = lv + l - 1;
+        ffd_level *k = lv + l;
+        float *cF = (float *)(w + off), *cM;
+        *k = (ffd_level){ NULL, NULL, multires_half(f->ox), multires_half(f->oy), multires_half(f->oz),
+                          multires_half(f->nx), multires_half(f->ny), multires_half(f->nz), 0, 0, 0 };
+        k->gx = sift3d_amd_ffd_lattice_dim(k->ox, prm.spacing[0]);
+        k->gy = sift3d_amd_ffd_lattice_dim(k->oy, prm.spacing[1]);
+        k->gz = sift3d_amd_ffd_lattice_dim(k->oz, prm.spacing[2]);
+        off += pad4(grid_voxels(k->ox, k->oy, k->oz)) * sizeof(float);
+        cM = (float *)(w + off);
+        off += pad4(grid_voxels(k->nx, k->ny, k->nz)) * sizeof(float);
+        if (sift3d_hip_restrict2(f->F, f->ox, f->oy, f->oz, 1, cF, 1.0f, stream) ||
+            sift3d_hip_restrict2(f->M, f->nx, f->ny, f->nz, 1, cM, 1.0f, stream))
+            return SIFT3D_FAILURE;
+        k->F = cF;
+        k->M = cM;
+        for (i = 3; i < 12; i += 4)
+            A[i] = A[i] * 0.5;
+    }
+    for (l = prm.levels - 1; l >= 0; l--) {
+        const ffd_level *v = lv + l;
+        const size_t nc = 3 * grid_voxels(v->gx, v->gy, v->gz);
+        double s = prm.step0, E;
+        uint64_t n_first;
+        int evals = 1, stop;
+        if (l == prm.levels - 1) {
+            if (sift3d_hip_memset(c, 0, nc * sizeof(float), stream))
+                return SIFT3D_FAILURE;
+        } else {
+            float *t = prev;                                 /* the coarser level's result is in c */
+            prev = c;
+            c = t;
+            if (sift3d_ffd_refine2_launch(prev, lv[l + 1].gx, lv[l + 1].gy, lv[l + 1].gz, c, v->gx, v->gy, v->gz,
+                                          stream))
+                return SIFT3D_FAILURE;
+        }
+        if (ffd_evaluate(what, &x, v, have_A ? A : NULL, c, g, &rec))
+            return SIFT3D_FAILURE;
+        ffd_trail(result, &rec, prm.bending, s, 1, l);
+        n_first = rec.n;
+        E = ffd_cost(&rec, prm.bending);
+        if (!isfinite(E))
+            stop = SIFT3D_AMD_FFD_STOP_FAILED;
+        else
+            for (;;) {
+                double Et;
+                int accept;
+                if (evals >= prm.max_evaluations) {
+                    stop = SIFT3D_AMD_FFD_STOP_EVALUATIONS;
+                    break;
+                }
+                if (rec.gmax == 0.0) {
+                    stop = SIFT3D_AMD_FFD_STOP_FLAT;
+                    break;
+                }
+                if (sift3d_ffd_step_launch(c, g, (float)(s / rec.gmax), ct, nc, stream) ||
+                    ffd_evaluate(what, &x, v, have_A ? A : NULL, ct, gt, &trial))
+                    return SIFT3D_FAILURE;
+                evals++;
+                Et = ffd_cost(&trial, prm.bending);
+                accept = isfinite(Et) && (double)trial.n >= prm.min_overlap * (double)n_first && Et < E;
+                ffd_trail(result, &trial, prm.bending, s, accept, l);
+                if (!isfinite(Et)) {
+                    stop = SIFT3D_AMD_FFD_STOP_FAILED;
+                    break;
+                }
+                if (accept) {
+                    float *t = c;
+                    c = ct; ct = t;
+                    t = g; g = gt; gt = t;
+                    rec = trial;
+                    E = Et;
+                    s = 2.0 * s < prm.step_max ? 2.0 * s : prm.step_max;
+                } else
+                    s = s * 0.5;
+                if (s < prm.tol) {
+                    stop = SIFT3D_AMD_FFD_STOP_CONVERGED;
+                    break;
+                }
+            }
+        result->stop = stop;
+        if (l > 0)
+            for (i = 3; i < 12; i += 4)
+                A[i] = A[i] * 2.0;
+    }
+    /* the final lattice and its field (the last evaluation may have been a rejected trial) */
+    if (sift3d_hip_memcpy_d2d(d_lattice, c, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3), stream) ||
+        sift3d_ffd_field_launch(what, c, lv[0].gx, lv[0].gy, lv[0].gz, prm.spacing[0], prm.spacing[1], prm.spacing[2],
+                                x.d_w, have_A ? A : NULL, ox, oy, oz, d_field, stream) ||
+        sift3d_hip_stream_sync(stream))
+        return SIFT3D_FAILURE;
+    return SIFT3D_SUCCESS;
+}

@@ -1508,3 +1508,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* intensity-driven affine refinement: normal equations entry, LM step, update and the driver */
 #include "sift3d_affine_refine.c"
+
+/* B-spline free-form deformation: weight table, checked entries and the steepest-descent driver */
+#include "sift3d_ffd.c"

@@ -67,6 +67,27 @@ class AffineRefineResult(C.Structure):                     # sift3d_amd_affine_r
                 ("trail", AffineEvaluation * (AFFINE_MAX_LEVELS * AFFINE_MAX_EVALUATIONS))]
 
 
+class FFDRefineParams(C.Structure):                        # sift3d_amd_ffd_refine_params
+    _fields_ = [("spacing", C.c_int * 3), ("levels", C.c_int), ("max_evaluations", C.c_int),
+                ("bending", C.c_double), ("step0", C.c_double), ("step_max", C.c_double), ("tol", C.c_double),
+                ("min_overlap", C.c_double)]
+
+
+class FFDEvaluation(C.Structure):                          # sift3d_amd_ffd_evaluation
+    _fields_ = [("E", C.c_double), ("msd", C.c_double), ("R", C.c_double), ("n", C.c_uint64), ("step", C.c_double),
+                ("accepted", C.c_int), ("level", C.c_int)]
+
+
+FFD_MAX_EVALUATIONS = 128                                  # checked against the library when it is bound (lib())
+FFD_MAX_SPACING = 256
+FFD_RECORD_HEAD_BYTES = 32
+
+
+class FFDRefineResult(C.Structure):                        # sift3d_amd_ffd_refine_result
+    _fields_ = [("evaluations", C.c_int), ("stop", C.c_int),
+                ("trail", FFDEvaluation * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))]
+
+
 _bound = None
 
 
@@ -159,6 +180,23 @@ def lib():
         "sift3d_amd_affine_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                                       C.POINTER(C.c_double), C.POINTER(AffineRefineParams),
                                                       C.POINTER(AffineRefineResult), vp, vp]),
+        "sift3d_amd_ffd_lattice_dim": (C.c_int, [C.c_int, C.c_int]),
+        "sift3d_amd_ffd_weights": (C.c_int, [C.c_int, vp]),
+        "sift3d_amd_ffd_field_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_amd_ffd_record_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_amd_ffd_evaluate_work_bytes": (C.c_size_t, [C.c_int] * 6),
+        "sift3d_amd_ffd_bending_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_amd_ffd_refine_work_bytes": (C.c_size_t, [C.c_int] * 10),
+        "sift3d_hip_ffd_field": (C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_double)] + [C.c_int] * 3 + [vp, vp, vp]),
+        "sift3d_hip_ffd_evaluate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
+                                    + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp]),
+        "sift3d_hip_ffd_bending": (C.c_int, [vp] + [C.c_int] * 6 + [vp, vp, vp]),
+        "sift3d_hip_ffd_refine2": (C.c_int, [vp] + [C.c_int] * 6 + [vp, vp]),
+        "sift3d_amd_ffd_refine_default_params": (None, [C.POINTER(FFDRefineParams)]),
+        "sift3d_amd_ffd_refine_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_amd_ffd_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
+                                                   C.POINTER(FFDRefineResult), vp, vp, vp, vp]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -208,6 +246,11 @@ def lib():
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the affine refinement layouts as %s, the library has %s"
                            % (want, got))
+    want = (C.sizeof(FFDRefineParams), C.sizeof(FFDEvaluation), C.sizeof(FFDRefineResult), FFD_RECORD_HEAD_BYTES,
+            FFD_MAX_EVALUATIONS, AFFINE_MAX_LEVELS, FFD_MAX_SPACING)
+    got = tuple(L.sift3d_amd_ffd_refine_struct_bytes(k) for k in range(7))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the FFD layouts as %s, the library has %s" % (want, got))
     _bound = L
     return L
 
@@ -708,6 +751,175 @@ def affine_refine(F, M, A, params=None, work=None):
                                                  C.byref(p), C.byref(res), work.data_ptr(), current_stream()),
            "sift3d_amd_affine_refine_device")
     return res
+
+
+# ---- B-spline free-form deformation (contract: include/sift3d_amd.h, "B-spline free-form deformation") ----
+FFD_STOPS = ("converged", "evaluations", "flat", "failed")
+FFD_HEAD_DTYPE = np.dtype([("n", "u8"), ("see", "f8"), ("R", "f8"), ("gmax", "f8")])
+assert FFD_HEAD_DTYPE.itemsize == FFD_RECORD_HEAD_BYTES
+
+
+def ffd_spacing(spacing, what="ffd"):
+    """(dx, dy, dz) from an int or three ints in x, y, z order"""
+    d = tuple(spacing) if isinstance(spacing, (tuple, list, np.ndarray, C.Array)) else (spacing,) * 3
+    if len(d) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or
+                          not 1 <= int(v) <= FFD_MAX_SPACING for v in d):
+        raise ValueError("%s: spacing must be an integer or three (x, y, z) in [1, %d]" % (what, FFD_MAX_SPACING))
+    return tuple(int(v) for v in d)
+
+
+def ffd_lattice_shape(out_shape, spacing):
+    """[3, gz, gy, gx] of the lattice over a grid (oz, oy, ox) (sift3d_amd_ffd_lattice_dim)"""
+    oz, oy, ox = (int(v) for v in out_shape)
+    dx, dy, dz = ffd_spacing(spacing)
+    g = [lib().sift3d_amd_ffd_lattice_dim(o, d) for o, d in ((oz, dz), (oy, dy), (ox, dx))]
+    if 0 in g:
+        raise ValueError("ffd_lattice_shape: the grid's dimensions must be positive")
+    return (3,) + tuple(g)
+
+
+def ffd_weights(delta):
+    """the table w [delta, 4] float32 of sift3d_amd_ffd_weights (host)"""
+    if isinstance(delta, bool) or not isinstance(delta, (int, np.integer)) or not 1 <= int(delta) <= FFD_MAX_SPACING:
+        raise ValueError("ffd_weights: spacing must be in [1, %d]" % FFD_MAX_SPACING)
+    w = np.zeros((int(delta), 4), np.float32)
+    if lib().sift3d_amd_ffd_weights(int(delta), w.ctypes.data) != 0:
+        raise ValueError("ffd_weights: refused")
+    return w
+
+
+def _ffd_lattice(lattice, what):
+    _tensor(lattice, "%s: lattice must be a contiguous float32 CUDA tensor [3, gz, gy, gx]" % what, dims=(4,), lead=3)
+    _, gz, gy, gx = lattice.shape
+    return gx, gy, gz
+
+
+def _ffd_A(A, what):
+    return (None, None) if A is None else (lambda a: (a, _dptr(a)))(_affine12(A, what))
+
+
+def ffd_field(lattice, spacing, field, A=None, work=None):
+    """field [3, oz, oy, ox] = the displacement field of the control lattice [3, gz, gy, gx] at integer spacing
+    (dx, dy, dz), through the 3 x 4 pull map A when given (sift3d_hip_ffd_field), on torch's current stream."""
+    gx, gy, gz = _ffd_lattice(lattice, "ffd_field")
+    _field_tensor(field, "ffd_field")
+    _same_device("ffd_field", lattice, field)
+    dx, dy, dz = ffd_spacing(spacing, "ffd_field")
+    _, oz, oy, ox = field.shape
+    a, ap = _ffd_A(A, "ffd_field")
+    work = _work(work, (lib().sift3d_amd_ffd_field_work_bytes(dx, dy, dz) + 3) // 4, lattice, "ffd_field")
+    _check(lib().sift3d_hip_ffd_field(lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap, ox, oy, oz, field.data_ptr(),
+                                      work.data_ptr(), current_stream()), "sift3d_hip_ffd_field")
+    return field
+
+
+def ffd_record(record, lattice_shape):
+    """A device record on the host, waiting for the stream: (n, S_ee, R, gmax, Gc float64 [3, gz, gy, gx], dR same)"""
+    import torch
+    raw = record.view(torch.uint8).cpu().numpy()
+    head = raw[:FFD_RECORD_HEAD_BYTES].view(FFD_HEAD_DTYPE)[0]
+    m = int(np.prod(lattice_shape))
+    body = raw[FFD_RECORD_HEAD_BYTES:FFD_RECORD_HEAD_BYTES + 16 * m].view(np.float64)
+    return (int(head["n"]), float(head["see"]), float(head["R"]), float(head["gmax"]),
+            body[:m].reshape(lattice_shape).copy(), body[m:].reshape(lattice_shape).copy())
+
+
+def _ffd_record_tensor(lattice):
+    import torch
+    _, gz, gy, gx = lattice.shape
+    return torch.zeros(lib().sift3d_amd_ffd_record_bytes(gx, gy, gz) // 8, dtype=torch.int64, device=lattice.device)
+
+
+def ffd_evaluate(F, M, lattice, spacing, A=None, bending=0.0, work=None):
+    """One evaluation of the FFD cost at `lattice` (sift3d_hip_ffd_evaluate) on torch's current stream.  Returns
+    (record, grad, field): the device record (read it with ffd_record), the float32 gradient lattice and the field."""
+    import torch
+    for t in (F, M):
+        _tensor(t, "ffd_evaluate: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    gx, gy, gz = _ffd_lattice(lattice, "ffd_evaluate")
+    _same_device("ffd_evaluate", F, M, lattice)
+    dx, dy, dz = ffd_spacing(spacing, "ffd_evaluate")
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    a, ap = _ffd_A(A, "ffd_evaluate")
+    record = _ffd_record_tensor(lattice)
+    grad = torch.empty_like(lattice)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    need = lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz)
+    work = _work(work, (need + 3) // 4, F, "ffd_evaluate")
+    _check(lib().sift3d_hip_ffd_evaluate(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx, gy,
+                                         gz, dx, dy, dz, ap, float(bending), field.data_ptr(), record.data_ptr(),
+                                         grad.data_ptr(), work.data_ptr(), current_stream()),
+           "sift3d_hip_ffd_evaluate")
+    return record, grad, field
+
+
+def ffd_bending(lattice, spacing, work=None):
+    """(R, dR float64 [3, gz, gy, gx]) of sift3d_hip_ffd_bending, on the host (waits for the stream)"""
+    gx, gy, gz = _ffd_lattice(lattice, "ffd_bending")
+    dx, dy, dz = ffd_spacing(spacing, "ffd_bending")
+    record = _ffd_record_tensor(lattice)
+    work = _work(work, (lib().sift3d_amd_ffd_bending_work_bytes(gx, gy, gz) + 3) // 4, lattice, "ffd_bending")
+    _check(lib().sift3d_hip_ffd_bending(lattice.data_ptr(), gx, gy, gz, dx, dy, dz, record.data_ptr(),
+                                        work.data_ptr(), current_stream()), "sift3d_hip_ffd_bending")
+    rec = ffd_record(record, tuple(lattice.shape))
+    return rec[2], rec[5]
+
+
+def ffd_refine2(coarse, out_shape, spacing):
+    """The lattice over the grid out_shape = (oz, oy, ox) from the lattice over the grid half as fine
+    (sift3d_hip_ffd_refine2), on torch's current stream."""
+    import torch
+    _ffd_lattice(coarse, "ffd_refine2")
+    oz, oy, ox = (int(v) for v in out_shape)
+    dx, dy, dz = ffd_spacing(spacing, "ffd_refine2")
+    if tuple(coarse.shape) != ffd_lattice_shape(((oz + 1) // 2, (oy + 1) // 2, (ox + 1) // 2), (dx, dy, dz)):
+        raise ValueError("ffd_refine2: coarse is not the lattice over the grid half as fine as out_shape")
+    fine = torch.empty(ffd_lattice_shape((oz, oy, ox), (dx, dy, dz)), dtype=torch.float32, device=coarse.device)
+    _check(lib().sift3d_hip_ffd_refine2(coarse.data_ptr(), ox, oy, oz, dx, dy, dz, fine.data_ptr(), current_stream()),
+           "sift3d_hip_ffd_refine2")
+    return fine
+
+
+def ffd_refine_params(**kw):
+    """sift3d_amd_ffd_refine_params: the defaults, overridden by spacing (dx, dy, dz), levels, max_evaluations,
+    bending, step0, step_max, tol, min_overlap"""
+    p = FFDRefineParams()
+    lib().sift3d_amd_ffd_refine_default_params(C.byref(p))
+    names = [f[0] for f in FFDRefineParams._fields_]
+    for k, v in kw.items():
+        if k not in names:
+            raise ValueError("refine_ffd: unknown parameter %r" % (k,))
+        if k == "spacing":
+            v = (C.c_int * 3)(*ffd_spacing(v, "refine_ffd"))
+        setattr(p, k, v)
+    return p
+
+
+def ffd_refine(F, M, A=None, params=None, work=None):
+    """sift3d_amd_ffd_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
+    waits for it once per evaluation).  Returns (FFDRefineResult, lattice, field)."""
+    import torch
+    for t in (F, M):
+        _tensor(t, "ffd_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device("ffd_refine", F, M)
+    a, ap = _ffd_A(A, "ffd_refine")
+    p = params if params is not None else ffd_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    d = tuple(p.spacing)
+    need = lib().sift3d_amd_ffd_refine_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
+    if need == 0:
+        raise ValueError("ffd_refine: levels must be in [1, %d] and the spacing in [1, %d]"
+                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
+    work = _work(work, (need + 3) // 4, F, "ffd_refine")
+    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    res = FFDRefineResult()
+    _check(lib().sift3d_amd_ffd_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap, C.byref(p),
+                                              C.byref(res), lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
+                                              current_stream()), "sift3d_amd_ffd_refine_device")
+    return res, lattice, field
 
 
 def _dense_args(src, out, what):
