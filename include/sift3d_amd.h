@@ -799,6 +799,73 @@ sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const flo
                              void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Masks: regions of interest for similarity, affine and FFD refinement      */
+/* ------------------------------------------------------------------------ */
+/* Which fixed voxels the three intensity-driven stages above count.  Each `_masked` entry below is its unmasked
+ * counterpart with two more arguments, d_WF and d_WM, at the end; this section is the one place the rule is stated.
+ *
+ * A mask is a float32 volume on the grid it belongs to: the fixed mask W_F[oz][oy][ox], the moving mask
+ * W_M[nz][ny][nx].  Either may be NULL: all in.  A mask voxel is IN when w >= 0.5f, one float compare: a NaN, a negative
+ * value and nextafterf(0.5f, 0) are out; 0.5f, 1, 2 and +inf are in; a binary 0 / 1 mask behaves as expected.  The same
+ * test holds at every pyramid level.  Weighted (soft) masks are not provided.
+ *
+ * A fixed voxel p is counted only when all three hold:
+ *   - its q is inside the moving grid (the unmasked sections' test, word for word);
+ *   - W_F(p) is in;
+ *   - W_M sampled at q is in.  The sample is "Resampling"'s NEAREST rule, the voxel at floor(q + 0.5) per axis (double),
+ *     of the same q that drives the intensity sample, whatever interpolation that sample uses.
+ * A masked-out voxel is treated exactly like a voxel whose q is outside: it is skipped, adds nothing to the count, the
+ * sums or the histogram, and the FFD force written at it is 0.  Mask values need not be finite; the volumes must be, as
+ * before, masked-out voxels included (they are read).  Binning, the sums, the partial slots, the order of the
+ * reductions and the record layouts are those of the unmasked sections, word for word: a masked call repeats its
+ * bytes, and they depend on the shapes and the inputs only.  With both masks NULL, or both all in, every masked entry
+ * writes the same bytes as its unmasked counterpart.
+ *
+ * Levels (the two drivers): level l's masks are sift3d_hip_restrict2 (scale 1) of level l - 1's masks - always the
+ * float mask of the level above, never a thresholded copy - held in d_work beside the restricted volumes (per level:
+ * fixed, moving, then the fixed mask and the moving mask where given).  min_overlap compares counts of counted
+ * voxels.  Params and result structs are the unmasked drivers'.
+ *
+ * Arguments are checked before any device call as in the unmasked entries, and in addition: a non-NULL mask must be
+ * 4-byte aligned and must not overlap any output or the work buffer; -1 otherwise.  The masked drivers need
+ * sift3d_amd_*_refine_masked_work_bytes() bytes of d_work (never less than the unmasked figure; 0 for bad arguments),
+ * whether or not a mask is NULL. */
+SIFT3D_AMD_API int
+sift3d_hip_similarity_affine_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    const double *A /*12*/, int interp, int bins, float lo_f, float hi_f, float lo_m,
+                                    float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream,
+                                    const float *d_WF, const float *d_WM);
+SIFT3D_AMD_API int
+sift3d_hip_similarity_field_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                   const float *d_field, int interp, int bins, float lo_f, float hi_f, float lo_m,
+                                   float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream,
+                                   const float *d_WF, const float *d_WM);
+SIFT3D_AMD_API int
+sift3d_hip_affine_normal_eqs_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    const double *A /*12*/, void *d_record, void *d_work, void *stream,
+                                    const float *d_WF, const float *d_WM);
+SIFT3D_AMD_API size_t
+sift3d_amd_affine_refine_masked_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels);
+SIFT3D_AMD_API int
+sift3d_amd_affine_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                       int nz, double *A_io, const sift3d_amd_affine_refine_params *params,
+                                       sift3d_amd_affine_refine_result *result, void *d_work, void *stream,
+                                       const float *d_WF, const float *d_WM);
+SIFT3D_AMD_API int
+sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                               const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                               const double *A /*12 or NULL*/, double bending, float *d_field, void *d_record,
+                               float *d_grad, void *d_work, void *stream, const float *d_WF, const float *d_WM);
+SIFT3D_AMD_API size_t
+sift3d_amd_ffd_refine_masked_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                        int levels);
+SIFT3D_AMD_API int
+sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    const double *A, const sift3d_amd_ffd_refine_params *params,
+                                    sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                    void *d_work, void *stream, const float *d_WF, const float *d_WM);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

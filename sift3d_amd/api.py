@@ -960,7 +960,49 @@ def _own_range(v, given):
     return (lo, hi) if hi > lo else (lo, lo + 1.0)
 
 
-def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fixed=None, range_moving=None):
+def _mask_host(mask, volume, what, name):
+    """A region-of-interest mask (contract: include/sift3d_amd.h, "Masks") checked against its volume before anything
+    is uploaded: None, a CUDA tensor as it is, or a float32 array.  bool and integer masks become float32 (mask != 0),
+    float masks pass as they are (in where >= 0.5).  ValueError on a wrong shape or kind, or on a tensor that is not on
+    the volume's device (the fixed volume's, where both are tensors)."""
+    import torch
+    if mask is None:
+        return None
+    vshape = tuple(volume.shape) if isinstance(volume, Image) or _torch_tensor(volume) else tuple(np.shape(volume))
+    if _torch_tensor(mask):
+        if not mask.is_cuda or (_torch_tensor(volume) and mask.device != volume.device):
+            raise ValueError("%s: %s must be on the fixed volume's device, not %s" % (what, name, mask.device))
+        if mask.dtype == torch.bool or not mask.dtype.is_floating_point:
+            if mask.dtype.is_complex:
+                raise ValueError("%s: %s must be a bool, integer or float mask" % (what, name))
+            mask = mask != 0
+        w = mask.to(torch.float32).contiguous()
+    else:
+        a = np.asarray(mask.data() if isinstance(mask, Image) else mask)
+        if a.dtype == np.bool_ or np.issubdtype(a.dtype, np.integer):
+            a = a != 0
+        elif not np.issubdtype(a.dtype, np.floating):
+            raise ValueError("%s: %s must be a bool, integer or float mask" % (what, name))
+        w = np.ascontiguousarray(a, np.float32)
+    if tuple(w.shape) != vshape:
+        raise ValueError("%s: %s must have its volume's shape %s, not %s" % (what, name, vshape, tuple(w.shape)))
+    return w
+
+
+def _mask_tensor(w, like, what, name):
+    """_mask_host's result on the device of the uploaded volume `like`"""
+    import torch
+    if w is None:
+        return None
+    if not _torch_tensor(w):
+        return torch.from_numpy(w).to(like.device)
+    if w.device != like.device:
+        raise ValueError("%s: %s must be on the fixed volume's device, not %s" % (what, name, w.device))
+    return w
+
+
+def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fixed=None, range_moving=None,
+               mask_fixed=None, mask_moving=None):
     """How well `fixed` agrees with `moving` seen through a pull map, in one pass on the device (contract:
     include/sift3d_amd.h, "Similarity measures"): the fixed voxels whose sample falls inside `moving` give
     Similarity(count, msd, ncc, mi, nmi, entropy_fixed, entropy_moving, entropy_joint, joint [bins, bins] int64
@@ -969,12 +1011,20 @@ def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fi
     displacement_field) or a displacement field [3, oz, oy, ox] on the fixed grid.  The volumes are torch CUDA
     float32 tensors [nz, ny, nx], or Images / arrays, which are uploaded.  A range left None is that volume's own
     min and max, at the cost of one host synchronisation (a constant volume gets hi = lo + 1); values outside a
-    given range count in the end bins.  Reads the result, so it waits for torch's current stream."""
+    given range count in the end bins.  mask_fixed, mask_moving: regions of interest of the volumes' shapes (tensors,
+    arrays or Images; bool and integer masks are in where non-zero, float masks where >= 0.5): a fixed voxel counts only
+    where mask_fixed is in and mask_moving, at the nearest voxel to its sample point, is in too (contract: "Masks").  A
+    range left None is still the whole volume's.  Reads the result, so it waits for torch's current stream."""
     from . import hip
+    WF = _mask_host(mask_fixed, fixed, "similarity", "mask_fixed")
+    WM = _mask_host(mask_moving, moving, "similarity", "mask_moving")
     F = _similarity_volume(fixed, "similarity", "fixed")
     M = _similarity_volume(moving, "similarity", "moving", F.device)
+    WF = _mask_tensor(WF, F, "similarity", "mask_fixed")
+    WM = _mask_tensor(WM, F, "similarity", "mask_moving")
     T = _similarity_transform(transform, F, "similarity")
-    hist, stats = hip.similarity(F, M, T, bins, _own_range(F, range_fixed), _own_range(M, range_moving), interp)
+    hist, stats = hip.similarity(F, M, T, bins, _own_range(F, range_fixed), _own_range(M, range_moving), interp,
+                                 mask_fixed=WF, mask_moving=WM)
     return similarity_measures(hist.cpu().numpy(), hip.similarity_stats(stats))
 
 
@@ -986,7 +1036,8 @@ RefinedRegistration = collections.namedtuple("RefinedRegistration",
 AFFINE_FREE = {"affine": 0xFFF, "translation": 0x888}
 
 
-def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", **params):
+def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", mask_fixed=None, mask_moving=None,
+                  **params):
     """Move the 3 x 4 affine pull map A (fixed voxel -> moving voxel, as similarity's transform; None: the identity,
     which needs no equal shapes) towards a smaller mean squared difference between `fixed` and `moving` seen through
     it, by Levenberg-Marquardt steps on the device's Gauss-Newton normal equations (contract: include/sift3d_amd.h,
@@ -994,10 +1045,11 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     4 d + j frees A[d][j] as centred on the fixed grid.  levels > 1 solves on volumes restricted levels - 1 times
     first.  params: max_evaluations (per level), lambda0, lambda_factor, lambda_min, lambda_max, tol (voxels),
     min_overlap.  The sample is linear.  The volumes are torch CUDA float32 tensors [nz, ny, nx], or Images / arrays,
-    which are uploaded.  Returns AffineRefinement(A, msd, count, accepted, lambdas, levels: one entry per evaluation
-    in the order run; level_slices: {level: slice into those}; evaluations; stop: "converged", "lambda",
-    "evaluations" or "lm_failed" of level 0; warped: `moving` through A on the fixed grid).  Waits for torch's
-    current stream once per evaluation."""
+    which are uploaded.  mask_fixed, mask_moving: regions of interest as similarity's; only voxels in both drive the
+    steps and count towards min_overlap, and coarser levels use the restricted masks.  Returns AffineRefinement(A, msd,
+    count, accepted, lambdas, levels: one entry per evaluation in the order run; level_slices: {level: slice into
+    those}; evaluations; stop: "converged", "lambda", "evaluations" or "lm_failed" of level 0; warped: `moving` through
+    A on the fixed grid).  Waits for torch's current stream once per evaluation."""
     import torch
     from . import hip
     if interp != "linear":
@@ -1015,9 +1067,13 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     if A0 is None or not np.isfinite(A0).all():
         raise ValueError("refine_affine: A must be a finite 3 x 4 affine pull map or None")
     p = hip.affine_refine_params(free_mask=int(mask), levels=int(levels), **params)
+    WF = _mask_host(mask_fixed, fixed, "refine_affine", "mask_fixed")
+    WM = _mask_host(mask_moving, moving, "refine_affine", "mask_moving")
     F = _similarity_volume(fixed, "refine_affine", "fixed")
     M = _similarity_volume(moving, "refine_affine", "moving", F.device)
-    res = hip.affine_refine(F, M, A0, p)
+    WF = _mask_tensor(WF, F, "refine_affine", "mask_fixed")
+    WM = _mask_tensor(WM, F, "refine_affine", "mask_moving")
+    res = hip.affine_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     k = res.evaluations
     trail = res.trail[:k]
     lv = np.array([e.level for e in trail], np.int64)
@@ -1083,16 +1139,18 @@ def ffd_bending_energy(lattice, spacing):
     return hip.ffd_bending(L, hip.ffd_spacing(spacing, "ffd_bending_energy"))
 
 
-def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, **params):
+def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None, **params):
     """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
     `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
     include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
     (None: the identity).  spacing: control spacing in voxels, an int or (dx, dy, dz), the same on every level.  params:
     max_evaluations (per level), step0, step_max, tol (voxels), min_overlap.  The volumes are torch CUDA float32
-    tensors [nz, ny, nx], or Images / arrays, which are uploaded.  Returns FFDRefinement(lattice [3, gz, gy, gx], spacing
-    (dx, dy, dz), A, field [3, oz, oy, ox], warped: `moving` through the field, trail: one FFDEvaluation(E, msd, R, n,
-    step, accepted, level) per evaluation in the order run, stop: "converged", "evaluations", "flat" or "failed" of
-    level 0, jacobian: JacobianStats of the field).  Waits for torch's current stream once per evaluation."""
+    tensors [nz, ny, nx], or Images / arrays, which are uploaded.  mask_fixed, mask_moving: regions of interest as
+    similarity's; the image force is 0 outside them (the bending term still acts everywhere).  Returns
+    FFDRefinement(lattice [3, gz, gy, gx], spacing (dx, dy, dz), A, field [3, oz, oy, ox], warped: `moving` through the
+    field, trail: one FFDEvaluation(E, msd, R, n, step, accepted, level) per evaluation in the order run, stop:
+    "converged", "evaluations", "flat" or "failed" of level 0, jacobian: JacobianStats of the field).  Waits for
+    torch's current stream once per evaluation."""
     from . import hip
     d = hip.ffd_spacing(spacing, "refine_ffd")
     if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
@@ -1108,9 +1166,13 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, **para
         if A0 is None or not np.isfinite(A0).all():
             raise ValueError("refine_ffd: A must be a finite 3 x 4 affine pull map or None")
     p = hip.ffd_refine_params(spacing=d, levels=int(levels), bending=float(bending), **params)
+    WF = _mask_host(mask_fixed, fixed, "refine_ffd", "mask_fixed")
+    WM = _mask_host(mask_moving, moving, "refine_ffd", "mask_moving")
     F = _similarity_volume(fixed, "refine_ffd", "fixed")
     M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
-    res, lattice, field = hip.ffd_refine(F, M, A0, p)
+    WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
+    WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
+    res, lattice, field = hip.ffd_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     trail = [FFDEvaluation(e.E, e.msd, e.R, int(e.n), e.step, bool(e.accepted), e.level)
              for e in res.trail[:res.evaluations]]
     return FFDRefinement(lattice, d, A0, field, warp_field(M, field), trail, hip.FFD_STOPS[res.stop],

@@ -7,7 +7,8 @@
  * the device is touched, so bad input is refused on a machine without a GPU too. */
 
 int sift3d_affine_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
-                                int ny, int nz, const double *A, void *d_record, void *d_work, void *stream);
+                                int ny, int nz, const double *A, void *d_record, void *d_work, void *stream,
+                                const float *d_WF, const float *d_WM);
 
 /* a double per statistic (60 + 12 + 1, and the uint64 count) per partial slot */
 #define AFFINE_NORMAL_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 74 * 8)
@@ -19,22 +20,41 @@ size_t sift3d_amd_affine_normal_work_bytes(int ox, int oy, int oz)
     return AFFINE_NORMAL_WORK_BYTES;
 }
 
-int sift3d_hip_affine_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
-                                 const double *A, void *d_record, void *d_work, void *stream)
+/* the shared body of the two entries: d_WF, d_WM are the masks ("Masks") or NULL */
+static int affine_normal_eqs(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                             int ny, int nz, const double *A, void *d_record, void *d_work, void *stream,
+                             const float *d_WF, const float *d_WM)
 {
-    static const char what[] = "sift3d_hip_affine_normal_eqs";
     if (!d_F || !d_M || !A || !d_record || !d_work)
         return refuse(what, "NULL argument");
     if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) || check_affine(what, A) ||
-        check_aligned(what, ADDR(d_record) | ADDR(d_work), ADDR(d_F) | ADDR(d_M)))
+        check_aligned(what, ADDR(d_record) | ADDR(d_work), ADDR(d_F) | ADDR(d_M) | ADDR(d_WF) | ADDR(d_WM)))
         return SIFT3D_FAILURE;
     {
-        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) } };
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES }, { d_work, AFFINE_NORMAL_WORK_BYTES } };
-        if (ranges_aliased(out, 2, in, 2))
+        if (ranges_aliased(out, 2, in, 4))
             return refuse(what, ALIASED);
     }
-    return sift3d_affine_normal_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record, d_work, stream);
+    return sift3d_affine_normal_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record, d_work, stream, d_WF,
+                                       d_WM);
+}
+
+int sift3d_hip_affine_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const double *A, void *d_record, void *d_work, void *stream)
+{
+    return affine_normal_eqs("sift3d_hip_affine_normal_eqs", d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record, d_work,
+                             stream, NULL, NULL);
+}
+
+int sift3d_hip_affine_normal_eqs_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                        int nz, const double *A, void *d_record, void *d_work, void *stream,
+                                        const float *d_WF, const float *d_WM)
+{
+    return affine_normal_eqs("sift3d_hip_affine_normal_eqs_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record,
+                             d_work, stream, d_WF, d_WM);
 }
 
 /* ---- host arithmetic on a record (the order of every operation is the header's) ---- */
@@ -180,6 +200,54 @@ size_t sift3d_amd_affine_refine_work_bytes(int ox, int oy, int oz, int nx, int n
     return total;
 }
 
+/* ---- the mask pyramid of the two masked drivers (this one and sift3d_ffd.c's): the layout rule, stated once ----
+ * Per level l = 1 .. levels-1, behind that level's restricted fixed and moving volumes: the fixed mask, then the
+ * moving mask, each present only where the caller gave one, each rounded up to a multiple of 16 bytes. */
+
+/* room for both masks on every level below the first (dims > 0, levels >= 1: checked by the callers) */
+static size_t mask_pyramid_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    size_t total = 0;
+    int l;
+    for (l = 1; l < levels; l++) {
+        ox = multires_half(ox); oy = multires_half(oy); oz = multires_half(oz);
+        nx = multires_half(nx); ny = multires_half(ny); nz = multires_half(nz);
+        total += pad4(grid_voxels(ox, oy, oz)) * sizeof(float) + pad4(grid_voxels(nx, ny, nz)) * sizeof(float);
+    }
+    return total;
+}
+
+/* One level's masks at w + *off from the FLOAT masks of the level above (never a thresholded copy), by
+ * sift3d_hip_restrict2 at scale 1; a NULL mask stays NULL and takes no room.  (fo.., fn..: the grids of the level
+ * above.)  *off moves past what was written. */
+static int mask_pyramid_level(const float *fWF, int fox, int foy, int foz, const float *fWM, int fnx, int fny, int fnz,
+                              char *w, size_t *off, const float **cWF, const float **cWM, void *stream)
+{
+    *cWF = *cWM = NULL;
+    if (fWF) {
+        float *c = (float *)(w + *off);
+        *off += pad4(grid_voxels(multires_half(fox), multires_half(foy), multires_half(foz))) * sizeof(float);
+        if (sift3d_hip_restrict2(fWF, fox, foy, foz, 1, c, 1.0f, stream))
+            return SIFT3D_FAILURE;
+        *cWF = c;
+    }
+    if (fWM) {
+        float *c = (float *)(w + *off);
+        *off += pad4(grid_voxels(multires_half(fnx), multires_half(fny), multires_half(fnz))) * sizeof(float);
+        if (sift3d_hip_restrict2(fWM, fnx, fny, fnz, 1, c, 1.0f, stream))
+            return SIFT3D_FAILURE;
+        *cWM = c;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* the masked driver's: the same, and the mask pyramid */
+size_t sift3d_amd_affine_refine_masked_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    const size_t plain = sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz, levels);
+    return plain ? plain + mask_pyramid_bytes(ox, oy, oz, nx, ny, nz, levels) : 0;
+}
+
 /* the largest distance by which the maps A and B move a corner of the grid apart */
 static double affine_corner_move(const double *A, const double *B, int ox, int oy, int oz)
 {
@@ -203,14 +271,18 @@ static double affine_corner_move(const double *A, const double *B, int ox, int o
 typedef struct {
     const float *F, *M;
     int ox, oy, oz, nx, ny, nz;
+    const float *WF, *WM;                                    /* the level's masks, or NULL */
 } affine_level;
 
 /* one evaluation at A on `lv`: the pass, the record's copy to the host and the wait for it */
 static int affine_evaluate(const affine_level *lv, const double *A, void *d_record, void *d_work, void *stream,
                            affine_record *rec)
 {
-    return sift3d_hip_affine_normal_eqs(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, d_record,
-                                        d_work, stream) ||
+    return (lv->WF || lv->WM
+                ? sift3d_hip_affine_normal_eqs_masked(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A,
+                                                      d_record, d_work, stream, lv->WF, lv->WM)
+                : sift3d_hip_affine_normal_eqs(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A,
+                                               d_record, d_work, stream)) ||
            sift3d_hip_memcpy_d2h(rec, d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES, stream) ||
            sift3d_hip_stream_sync(stream);
 }
@@ -226,11 +298,12 @@ static void affine_trail(sift3d_amd_affine_refine_result *res, const affine_reco
     e->level = level;
 }
 
-int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
-                                    double *A_io, const sift3d_amd_affine_refine_params *params,
-                                    sift3d_amd_affine_refine_result *result, void *d_work, void *stream)
+/* the shared body of the two drivers: `masked` selects the work buffer's size; the masks may still be NULL */
+static int affine_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                         int nz, double *A_io, const sift3d_amd_affine_refine_params *params,
+                         sift3d_amd_affine_refine_result *result, void *d_work, void *stream, int masked,
+                         const float *d_WF, const float *d_WM)
 {
-    static const char what[] = "sift3d_amd_affine_refine_device";
     sift3d_amd_affine_refine_params prm;
     affine_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
     affine_record rec, trial;
@@ -249,12 +322,17 @@ int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, co
         return SIFT3D_FAILURE;
     if (!affine_params_ok(&prm))
         return refuse(what, "a parameter is out of range");
-    if (check_aligned(what, ADDR(d_work), ADDR(d_F) | ADDR(d_M)))
+    if (check_aligned(what, ADDR(d_work), ADDR(d_F) | ADDR(d_M) | ADDR(d_WF) | ADDR(d_WM)))
         return SIFT3D_FAILURE;
     {
-        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) } };
-        const range_t out[] = { { d_work, sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.levels) } };
-        if (ranges_aliased(out, 1, in, 2))
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
+        const range_t out[] = { { d_work, masked ? sift3d_amd_affine_refine_masked_work_bytes(ox, oy, oz, nx, ny, nz,
+                                                                                              prm.levels)
+                                                 : sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz,
+                                                                                       prm.levels) } };
+        if (ranges_aliased(out, 1, in, 4))
             return refuse(what, ALIASED);
     }
     result->evaluations = 0;
@@ -262,14 +340,14 @@ int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, co
     memcpy(result->A, A_io, sizeof(result->A));
     d_record = w + AFFINE_NORMAL_WORK_BYTES;
     off = AFFINE_NORMAL_WORK_BYTES + AFFINE_RECORD_PAD;
-    lv[0] = (affine_level){ d_F, d_M, ox, oy, oz, nx, ny, nz };
+    lv[0] = (affine_level){ d_F, d_M, ox, oy, oz, nx, ny, nz, d_WF, d_WM };
     memcpy(A, A_io, sizeof(A));
     for (l = 1; l < prm.levels; l++) {                       /* level l from level l - 1; A's shift halves */
         const affine_level *f = lv + l - 1;
         affine_level *c = lv + l;
         float *cF = (float *)(w + off), *cM;
         *c = (affine_level){ NULL, NULL, multires_half(f->ox), multires_half(f->oy), multires_half(f->oz),
-                             multires_half(f->nx), multires_half(f->ny), multires_half(f->nz) };
+                             multires_half(f->nx), multires_half(f->ny), multires_half(f->nz), NULL, NULL };
         off += pad4(grid_voxels(c->ox, c->oy, c->oz)) * sizeof(float);
         cM = (float *)(w + off);
         off += pad4(grid_voxels(c->nx, c->ny, c->nz)) * sizeof(float);
@@ -278,6 +356,8 @@ int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, co
             return SIFT3D_FAILURE;
         c->F = cF;
         c->M = cM;
+        if (mask_pyramid_level(f->WF, f->ox, f->oy, f->oz, f->WM, f->nx, f->ny, f->nz, w, &off, &c->WF, &c->WM, stream))
+            return SIFT3D_FAILURE;
         for (i = 3; i < 12; i += 4)
             A[i] = A[i] * 0.5;
     }
@@ -334,4 +414,21 @@ int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, co
     memcpy(A_io, A, sizeof(A));
     memcpy(result->A, A, sizeof(A));
     return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    double *A_io, const sift3d_amd_affine_refine_params *params,
+                                    sift3d_amd_affine_refine_result *result, void *d_work, void *stream)
+{
+    return affine_refine("sift3d_amd_affine_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params, result,
+                         d_work, stream, 0, NULL, NULL);
+}
+
+int sift3d_amd_affine_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                           int nz, double *A_io, const sift3d_amd_affine_refine_params *params,
+                                           sift3d_amd_affine_refine_result *result, void *d_work, void *stream,
+                                           const float *d_WF, const float *d_WM)
+{
+    return affine_refine("sift3d_amd_affine_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params,
+                         result, d_work, stream, 1, d_WF, d_WM);
 }

@@ -37,6 +37,7 @@ struct AffArgs {
     GridArgs g;                                  // src = M; ox, oy, oz = F's grid; dst unused
     const float *F;
     double *part;                                // [AFF_STATS][AFF_GRID]; row 73 holds uint64
+    MaskArgs w;                                  // MASKED == true: wf on F's grid, wm on M's; either may be null
 };
 
 __host__ __device__ constexpr int pair3(int d, int e) { return d == 0 ? e : d == 1 ? 2 + e : 5; }           // d <= e < 3
@@ -45,7 +46,9 @@ __host__ __device__ constexpr int pair4(int j, int k) { return j == 0 ? k : j ==
 // (256, 2): the 72 accumulators are 144 VGPRs; the compiler reports 256 VGPRs, two waves per SIMD and nothing spilled
 // (-Rpass-analysis=kernel-resource-usage).  Measured (profiles/microbench/affine_refine_rate_mi355x.txt): 0.888 ms
 // per pass at 512^3, 1.63 x k_similarity's on the same volumes; the direct formulation takes 1.086 ms.
-template <int LINEAR>
+// MASKED (header, "Masks"): as k_similarity's; a masked-out voxel enters with G = 0 and E = 0 like an outside one.
+// MASKED == false compiles to what it compiled to before the parameter existed.
+template <int LINEAR, bool MASKED>
 __global__ __launch_bounds__(256, 2) void k_affine_normal(const AffArgs s)
 {
     __shared__ double slot[AFF_SUMS * 4];
@@ -66,6 +69,25 @@ __global__ __launch_bounds__(256, 2) void k_affine_normal(const AffArgs s)
         const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
         const double yd = (double)y, zd = (double)z;
         const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
+        // MASKED: the two mask values of the lane's four outputs first, all eight loads in flight together, kept as
+        // four flags.  The 72 accumulators leave no registers to hold them across the intensity gathers (it spills);
+        // the stage costs one more round trip per tile (measured: DESIGN.md 3.4.10).  q is pull()'s three
+        // multiply-adds per output, computed here and again in the taps loop rather than kept in 24 registers.
+        bool ok[4] = {true, true, true, true};
+        if (MASKED) {
+            float wf[4], wm[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int x = xt + lx + 16 * k;
+                const double xd = (double)x;
+                const double qx = pull(s.a, xd, rx), qy = pull(s.a + 4, xd, ry), qz = pull(s.a + 8, xd, rz);
+                wf[k] = s.w.wf && row && x < p.ox ? s.w.wf[orow + (size_t)x] : 1.0f;
+                wm[k] = s.w.wm ? s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                ok[k] = mask_in(wf[k]) && mask_in(wm[k]);
+        }
         Taps tp[4];
         float f[4];
         bool live[4];
@@ -93,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void k_affine_normal(const AffArgs s)
 #endif
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const bool counted = live[k] && tp[k].in;
+            const bool counted = MASKED ? live[k] && tp[k].in && ok[k] : live[k] && tp[k].in;
             const float e = m[k] - f[k];
             const double E = counted ? (double)e : 0.0;
             const double G[3] = {counted ? (double)gx[k] : 0.0, counted ? (double)gy[k] : 0.0,
@@ -229,10 +251,11 @@ __global__ __launch_bounds__(256) void k_affine_normal_finish(const double *part
 
 } // namespace
 
-// Launcher for sift3d_affine_refine.c, which has checked every argument (not exported from the library).
+// Launcher for sift3d_affine_refine.c, which has checked every argument (not exported from the library).  d_WF, d_WM:
+// the masks or NULL; with both NULL the unmasked kernels run.
 extern "C" int sift3d_affine_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
                                            int nx, int ny, int nz, const double *A, void *d_record, void *d_work,
-                                           void *stream)
+                                           void *stream, const float *d_WF, const float *d_WM)
 {
     AffArgs s;
     if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
@@ -246,7 +269,10 @@ extern "C" int sift3d_affine_normal_launch(const char *fn, const float *d_F, int
     s.part = (double *)d_work;
     const unsigned grid = s.g.ntiles < AFF_GRID ? s.g.ntiles : AFF_GRID;
     hipStream_t st = (hipStream_t)stream;
-    void (*k)(const AffArgs) = nx >= 2 ? k_affine_normal<2> : k_affine_normal<1>;
+    s.w = MaskArgs{d_WF, d_WM};
+    const bool masked = d_WF || d_WM;
+    void (*k)(const AffArgs) = masked ? (nx >= 2 ? k_affine_normal<2, true> : k_affine_normal<1, true>)
+                                      : (nx >= 2 ? k_affine_normal<2, false> : k_affine_normal<1, false>);
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, s);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_affine_normal_finish, dim3(AFF_STATS), dim3(256), 0, st, (const double *)d_work, grid,

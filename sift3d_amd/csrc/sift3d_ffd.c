@@ -11,7 +11,8 @@ int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int gx, int gy, 
 int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                                int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
                                int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
-                               double *d_rec, float *d_grad, double *d_work, void *stream);
+                               double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
+                               const float *d_WM);
 int sift3d_ffd_step_launch(const float *d_c, const float *d_grad, float a, float *d_out, size_t n, void *stream);
 int sift3d_ffd_refine2_launch(const float *d_c, int cx, int cy, int cz, float *d_f, int fx, int fy, int fz,
                               void *stream);
@@ -141,11 +142,12 @@ size_t sift3d_amd_ffd_evaluate_work_bytes(int ox, int oy, int oz, int dx, int dy
                             sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double);
 }
 
-int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
-                            const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
-                            double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
+/* the shared body of the two entries: d_WF, d_WM are the masks ("Masks") or NULL */
+static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                              int ny, int nz, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                              const double *A, double bending, float *d_field, void *d_record, float *d_grad,
+                              void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
-    static const char what[] = "sift3d_hip_ffd_evaluate";
     int delta[3];
     double st[27];
     if (!d_F || !d_M || !d_lattice || !d_field || !d_record || !d_grad || !d_work)
@@ -155,18 +157,21 @@ int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const floa
         return SIFT3D_FAILURE;
     if (!isfinite(bending) || bending < 0)
         return refuse(what, "the bending weight must be finite and not negative");
-    if (check_aligned(what, ADDR(d_record), ADDR(d_F) | ADDR(d_M) | ADDR(d_lattice) | ADDR(d_field) | ADDR(d_grad)))
+    if (check_aligned(what, ADDR(d_record), ADDR(d_F) | ADDR(d_M) | ADDR(d_lattice) | ADDR(d_field) | ADDR(d_grad) |
+                                                ADDR(d_WF) | ADDR(d_WM)))
         return SIFT3D_FAILURE;
     if (ADDR(d_work) & 15)
         return refuse(what, "a buffer is misaligned");
     {
         const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
-                               { d_lattice, image_bytes(gx, gy, gz, 3) } };
+                               { d_lattice, image_bytes(gx, gy, gz, 3) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_field, field_bytes(ox, oy, oz) },
                                 { d_record, sift3d_amd_ffd_record_bytes(gx, gy, gz) },
                                 { d_grad, image_bytes(gx, gy, gz, 3) },
                                 { d_work, sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz) } };
-        if (ranges_aliased(out, 4, in, 3))
+        if (ranges_aliased(out, 4, in, 5))
             return refuse(what, ALIASED);
     }
     delta[0] = dx; delta[1] = dy; delta[2] = dz;
@@ -177,7 +182,25 @@ int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const floa
         return SIFT3D_FAILURE;
     return sift3d_ffd_evaluate_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
                                       dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
-                                      (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream);
+                                      (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
+                                      d_WM);
+}
+
+int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                            const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
+                            double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
+{
+    return ffd_evaluate_entry("sift3d_hip_ffd_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL);
+}
+
+int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                   const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                   const double *A, double bending, float *d_field, void *d_record, float *d_grad,
+                                   void *d_work, void *stream, const float *d_WF, const float *d_WM)
+{
+    return ffd_evaluate_entry("sift3d_hip_ffd_evaluate_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy,
+                              gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM);
 }
 
 size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz)
@@ -212,7 +235,7 @@ int sift3d_hip_ffd_bending(const float *d_lattice, int gx, int gy, int gz, int d
     ffd_stencils(delta, st);
     /* the launcher's scratch layout with an empty image grid: slots, then D */
     return sift3d_ffd_evaluate_launch(what, NULL, 0, 0, 0, NULL, 0, 0, 0, NULL, d_lattice, gx, gy, gz, dx, dy, dz, NULL,
-                                      st, 0.0, (double *)d_record, NULL, (double *)d_work, stream);
+                                      st, 0.0, (double *)d_record, NULL, (double *)d_work, stream, NULL, NULL);
 }
 
 int sift3d_hip_ffd_refine2(const float *d_coarse, int ox, int oy, int oz, int dx, int dy, int dz, float *d_fine,
@@ -314,9 +337,18 @@ size_t sift3d_amd_ffd_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, 
     return total;
 }
 
+/* the masked driver's: the same, and the mask pyramid (sift3d_affine_refine.c) */
+size_t sift3d_amd_ffd_refine_masked_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                               int levels)
+{
+    const size_t plain = sift3d_amd_ffd_refine_work_bytes(ox, oy, oz, nx, ny, nz, dx, dy, dz, levels);
+    return plain ? plain + mask_pyramid_bytes(ox, oy, oz, nx, ny, nz, levels) : 0;
+}
+
 typedef struct {
     const float *F, *M;
     int ox, oy, oz, nx, ny, nz, gx, gy, gz;
+    const float *WF, *WM;                                    /* the level's masks, or NULL */
 } ffd_level;
 
 typedef struct {
@@ -343,7 +375,7 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
                                    lv->oy, lv->oz, x->d_field, x->stream) ||
            sift3d_ffd_evaluate_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
                                       lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
-                                      x->d_rec, grad, x->d_eval, x->stream) ||
+                                      x->d_rec, grad, x->d_eval, x->stream, lv->WF, lv->WM) ||
            sift3d_hip_memcpy_d2h(h, x->d_rec, sizeof(*h), x->stream) || sift3d_hip_stream_sync(x->stream);
 }
 
@@ -365,12 +397,12 @@ static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_head *h, doub
     e->level = level;
 }
 
-int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
-                                 const double *A_in, const sift3d_amd_ffd_refine_params *params,
-                                 sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
-                                 void *stream)
+/* the shared body of the two drivers: `masked` selects the work buffer's size; the masks may still be NULL */
+static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                      int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                      sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
+                      void *stream, int masked, const float *d_WF, const float *d_WM)
 {
-    static const char what[] = "sift3d_amd_ffd_refine_device";
     sift3d_amd_ffd_refine_params prm;
     ffd_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
     ffd_head rec, trial;
@@ -390,19 +422,24 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
         return SIFT3D_FAILURE;
     if (!ffd_params_ok(&prm))
         return refuse(what, "a parameter is out of range");
-    if (check_aligned(what, 0, ADDR(d_F) | ADDR(d_M) | ADDR(d_lattice) | ADDR(d_field)))
+    if (check_aligned(what, 0, ADDR(d_F) | ADDR(d_M) | ADDR(d_lattice) | ADDR(d_field) | ADDR(d_WF) | ADDR(d_WM)))
         return SIFT3D_FAILURE;
     if (ADDR(d_work) & 15)
         return refuse(what, "a buffer is misaligned");
     lv[0] = (ffd_level){ d_F, d_M, ox, oy, oz, nx, ny, nz, sift3d_amd_ffd_lattice_dim(ox, prm.spacing[0]),
-                         sift3d_amd_ffd_lattice_dim(oy, prm.spacing[1]), sift3d_amd_ffd_lattice_dim(oz, prm.spacing[2]) };
+                         sift3d_amd_ffd_lattice_dim(oy, prm.spacing[1]), sift3d_amd_ffd_lattice_dim(oz, prm.spacing[2]),
+                         d_WF, d_WM };
     {
-        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) } };
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_lattice, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3) },
                                 { d_field, field_bytes(ox, oy, oz) },
-                                { d_work, sift3d_amd_ffd_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0],
-                                                                           prm.spacing[1], prm.spacing[2], prm.levels) } };
-        if (ranges_aliased(out, 3, in, 2))
+                                { d_work, (masked ? sift3d_amd_ffd_refine_masked_work_bytes
+                                                  : sift3d_amd_ffd_refine_work_bytes)(ox, oy, oz, nx, ny, nz,
+                                                                                      prm.spacing[0], prm.spacing[1],
+                                                                                      prm.spacing[2], prm.levels) } };
+        if (ranges_aliased(out, 3, in, 4))
             return refuse(what, ALIASED);
     }
     result->evaluations = 0;
@@ -434,7 +471,7 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
         ffd_level *k = lv + l;
         float *cF = (float *)(w + off), *cM;
         *k = (ffd_level){ NULL, NULL, multires_half(f->ox), multires_half(f->oy), multires_half(f->oz),
-                          multires_half(f->nx), multires_half(f->ny), multires_half(f->nz), 0, 0, 0 };
+                          multires_half(f->nx), multires_half(f->ny), multires_half(f->nz), 0, 0, 0, NULL, NULL };
         k->gx = sift3d_amd_ffd_lattice_dim(k->ox, prm.spacing[0]);
         k->gy = sift3d_amd_ffd_lattice_dim(k->oy, prm.spacing[1]);
         k->gz = sift3d_amd_ffd_lattice_dim(k->oz, prm.spacing[2]);
@@ -446,6 +483,8 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
             return SIFT3D_FAILURE;
         k->F = cF;
         k->M = cM;
+        if (mask_pyramid_level(f->WF, f->ox, f->oy, f->oz, f->WM, f->nx, f->ny, f->nz, w, &off, &k->WF, &k->WM, stream))
+            return SIFT3D_FAILURE;
         for (i = 3; i < 12; i += 4)
             A[i] = A[i] * 0.5;
     }
@@ -522,4 +561,22 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
         sift3d_hip_stream_sync(stream))
         return SIFT3D_FAILURE;
     return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                                 sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
+                                 void *stream)
+{
+    return ffd_refine("sift3d_amd_ffd_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
+                      d_lattice, d_field, d_work, stream, 0, NULL, NULL);
+}
+
+int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                        int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                                        sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                        void *d_work, void *stream, const float *d_WF, const float *d_WM)
+{
+    return ffd_refine("sift3d_amd_ffd_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
+                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM);
 }

@@ -108,9 +108,12 @@ struct FfdForceArgs {
     const float *F, *field;
     double *force;                               // [3][oz][oy][ox]
     double *part;                                // [2][FFD_GRID]: S_ee, then the count as uint64
+    MaskArgs w;                                  // MASKED == true: wf on F's grid, wm on M's; either may be null
 };
 
-template <int LINEAR>
+// MASKED (header, "Masks"): as k_similarity's; the force at a masked-out voxel is 0 like an outside one's.
+// MASKED == false compiles to what it compiled to before the parameter existed.
+template <int LINEAR, bool MASKED>
 __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
 {
     __shared__ double s_see[4];
@@ -129,21 +132,27 @@ __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
         Taps tp[4];
         float f[4];
         bool live[4];
+        float wf[4], wm[4];                                                  // MASKED only
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int x = xt + lx + 16 * k;
             live[k] = row && x < p.ox;
             float ux = 0.0f, uy = 0.0f, uz = 0.0f;
             f[k] = 0.0f;
+            wf[k] = wm[k] = 1.0f;
             if (live[k]) {
                 const float *u = s.field + orow + (size_t)x;
                 ux = u[0];
                 uy = u[ovox];
                 uz = u[2 * ovox];
                 f[k] = s.F[orow + (size_t)x];
+                if (MASKED && s.w.wf)
+                    wf[k] = s.w.wf[orow + (size_t)x];
             }
-            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, (double)x + (double)ux, (double)y + (double)uy,
-                                    (double)z + (double)uz);
+            const double qx = (double)x + (double)ux, qy = (double)y + (double)uy, qz = (double)z + (double)uz;
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
+            if (MASKED && s.w.wm)
+                wm[k] = s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
         }
         float m[4], gx[4], gy[4], gz[4];
 #pragma unroll
@@ -151,7 +160,7 @@ __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
             m[k] = gather_grad<LINEAR>(p.src, tp[k], &gx[k], &gy[k], &gz[k]);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const bool counted = live[k] && tp[k].in;
+            const bool counted = MASKED ? live[k] && tp[k].in && mask_in(wf[k]) && mask_in(wm[k]) : live[k] && tp[k].in;
             const float e = m[k] - f[k];
             const double E = counted ? (double)e : 0.0;
             cnt += counted ? 1u : 0u;
@@ -432,11 +441,12 @@ extern "C" int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int g
 
 // d_rec: {uint64 n; double S_ee, R, gmax} then Gc and dR, [3][gz][gy][gx] doubles each.  d_work: partial slots
 // [2][FFD_GRID] doubles, then the force [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox], D [18][N] doubles.
+// d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.
 extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
                                           int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
                                           int gy, int gz, int dx, int dy, int dz, const float *d_w,
                                           const double *stencils, double bending, double *d_rec, float *d_grad,
-                                          double *d_work, void *stream)
+                                          double *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     hipStream_t st = (hipStream_t)stream;
     const size_t vox = (size_t)ox * oy * oz, cvox = (size_t)gx * gy * gz;
@@ -453,7 +463,10 @@ extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int 
         f.force = force;
         f.part = part;
         const unsigned grid = f.g.ntiles < FFD_GRID ? f.g.ntiles : FFD_GRID;
-        void (*kf)(const FfdForceArgs) = nx >= 2 ? k_ffd_force<2> : k_ffd_force<1>;
+        f.w = MaskArgs{d_WF, d_WM};
+        const bool masked = d_WF || d_WM;
+        void (*kf)(const FfdForceArgs) = masked ? (nx >= 2 ? k_ffd_force<2, true> : k_ffd_force<1, true>)
+                                                : (nx >= 2 ? k_ffd_force<2, false> : k_ffd_force<1, false>);
         hipLaunchKernelGGL(kf, dim3(grid), dim3(256), 0, st, f);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish_count, dim3(1), dim3(256), 0, st, (const unsigned long long *)part + FFD_GRID, grid,

@@ -255,6 +255,24 @@ __device__ __forceinline__ float sample(const GridArgs &p, double qx, double qy,
     return gather<LINEAR>(p.src, taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz), p.fill);
 }
 
+// ---- region-of-interest masks (contract: include/sift3d_amd.h, "Masks") ------------------------------------------
+// A mask is a float volume on its grid; a voxel is in when w >= 0.5f (one compare: a NaN is out).  wf lies on the
+// output grid and is read beside F; wm lies on the source grid and is read at the NEAREST voxel of the q that the
+// intensity sample uses, whatever that sample's interpolation.  Either pointer may be null: all in.
+struct MaskArgs {
+    const float *wf, *wm;
+};
+
+__device__ __forceinline__ bool mask_in(float w) { return w >= 0.5f; }
+
+// The offset of the source-grid mask voxel for a sample at q: the NEAREST taps of the same q, whatever the
+// interpolation of the intensity sample, with taps_at's own clamp (the compiler keeps one copy of the inside test and
+// the selects), so an outside q reads voxel 0 branch-free and needs no test before the load.
+__device__ __forceinline__ size_t mask_offset(int nx, int ny, int nz, double qx, double qy, double qz)
+{
+    return taps_at<0>(nx, ny, nz, qx, qy, qz).r00;
+}
+
 // ---- thin-plate spline: q(p) = affine(p) + (double) s(p), s = sum_i w_i phi(|p - c_i|) ------------------------
 // (contract: include/sift3d_amd.h, "Thin-plate spline").  The radial sum is compute-bound: per voxel-point
 // 3 differences, 3 squares, 2 adds, a correctly rounded sqrt and 3 multiply-adds, all float, unfused.

@@ -8,7 +8,7 @@
 int sift3d_similarity_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                              int nz, const double *A, const float *d_field, int interp, int bins, float lo_f,
                              float s_f, float lo_m, float s_m, unsigned long long *d_hist, void *d_stats, void *d_work,
-                             void *stream);
+                             void *stream, const float *d_WF, const float *d_WM);
 
 #define SIMILARITY_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 7 * 8)    /* a uint64 and six doubles per slot */
 
@@ -37,10 +37,11 @@ static float bin_scale(int bins, float lo, float hi)
     return isfinite(s) && s > 0.0f ? s : 0.0f;
 }
 
-/* the shared body of the two entries: A == NULL is the field one */
+/* the shared body of the four entries: A == NULL is the field one; d_WF, d_WM are the masks ("Masks") or NULL */
 static int similarity(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                       int nz, const double *A, const float *d_field, int interp, int bins, float lo_f, float hi_f,
-                      float lo_m, float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream)
+                      float lo_m, float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream,
+                      const float *d_WF, const float *d_WM)
 {
     float s_f, s_m;
     if (!d_F || !d_M || (!A && !d_field) || !d_hist || !d_stats || !d_work)
@@ -56,18 +57,21 @@ static int similarity(const char *what, const float *d_F, int ox, int oy, int oz
     if (interp != SIFT3D_AMD_INTERP_NEAREST && interp != SIFT3D_AMD_INTERP_LINEAR)
         return refuse(what, "unknown interpolation mode");
     if ((A && check_affine(what, A)) ||
-        check_aligned(what, ADDR(d_hist) | ADDR(d_stats) | ADDR(d_work), ADDR(d_F) | ADDR(d_M) | ADDR(d_field)))
+        check_aligned(what, ADDR(d_hist) | ADDR(d_stats) | ADDR(d_work),
+                      ADDR(d_F) | ADDR(d_M) | ADDR(d_field) | ADDR(d_WF) | ADDR(d_WM)))
         return SIFT3D_FAILURE;
     {
         const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
-                               { d_field, d_field ? field_bytes(ox, oy, oz) : 0 } };
+                               { d_field, d_field ? field_bytes(ox, oy, oz) : 0 },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_hist, (size_t)bins * bins * sizeof(uint64_t) },
                                 { d_stats, SIFT3D_AMD_SIMILARITY_STATS_BYTES }, { d_work, SIMILARITY_WORK_BYTES } };
-        if (ranges_aliased(out, 3, in, d_field ? 3 : 2))
+        if (ranges_aliased(out, 3, in, d_field ? 3 : 2) || ranges_aliased(out, 3, in + 3, 2))
             return refuse(what, ALIASED);
     }
     return sift3d_similarity_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_field, interp, bins, lo_f, s_f, lo_m,
-                                    s_m, (unsigned long long *)d_hist, d_stats, d_work, stream);
+                                    s_m, (unsigned long long *)d_hist, d_stats, d_work, stream, d_WF, d_WM);
 }
 
 int sift3d_hip_similarity_affine(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -78,7 +82,7 @@ int sift3d_hip_similarity_affine(const float *d_F, int ox, int oy, int oz, const
     if (!A)
         return refuse(what, "NULL argument");
     return similarity(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, NULL, interp, bins, lo_f, hi_f, lo_m, hi_m, d_hist,
-                      d_stats, d_work, stream);
+                      d_stats, d_work, stream, NULL, NULL);
 }
 
 int sift3d_hip_similarity_field(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -89,7 +93,31 @@ int sift3d_hip_similarity_field(const float *d_F, int ox, int oy, int oz, const 
     if (!d_field)
         return refuse(what, "NULL argument");
     return similarity(what, d_F, ox, oy, oz, d_M, nx, ny, nz, NULL, d_field, interp, bins, lo_f, hi_f, lo_m, hi_m,
-                      d_hist, d_stats, d_work, stream);
+                      d_hist, d_stats, d_work, stream, NULL, NULL);
+}
+
+int sift3d_hip_similarity_affine_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                        int nz, const double *A, int interp, int bins, float lo_f, float hi_f,
+                                        float lo_m, float hi_m, uint64_t *d_hist, void *d_stats, void *d_work,
+                                        void *stream, const float *d_WF, const float *d_WM)
+{
+    static const char what[] = "sift3d_hip_similarity_affine_masked";
+    if (!A)
+        return refuse(what, "NULL argument");
+    return similarity(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, NULL, interp, bins, lo_f, hi_f, lo_m, hi_m, d_hist,
+                      d_stats, d_work, stream, d_WF, d_WM);
+}
+
+int sift3d_hip_similarity_field_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                       int nz, const float *d_field, int interp, int bins, float lo_f, float hi_f,
+                                       float lo_m, float hi_m, uint64_t *d_hist, void *d_stats, void *d_work,
+                                       void *stream, const float *d_WF, const float *d_WM)
+{
+    static const char what[] = "sift3d_hip_similarity_field_masked";
+    if (!d_field)
+        return refuse(what, "NULL argument");
+    return similarity(what, d_F, ox, oy, oz, d_M, nx, ny, nz, NULL, d_field, interp, bins, lo_f, hi_f, lo_m, hi_m,
+                      d_hist, d_stats, d_work, stream, d_WF, d_WM);
 }
 
 /* ---- host arithmetic on a histogram and a stats record (the order of every sum is the header's) ---- */

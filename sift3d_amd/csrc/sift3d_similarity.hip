@@ -44,6 +44,7 @@ struct SimArgs {
     unsigned long long *hist;                    // [bins][bins]
     unsigned long long *pcnt;                    // [SIM_GRID]
     double *psum;                                // [6][SIM_GRID]
+    MaskArgs w;                                  // MASKED == true: wf on F's grid, wm on M's; either may be null
 };
 
 // b = t < 0 ? 0 : t >= B ? B - 1 : (int) t of the contract (the first test written so that a NaN, which finite
@@ -73,8 +74,11 @@ __device__ __forceinline__ void commit(unsigned *h, int idx, bool counted)
         atomicAdd(h + idx, 1u);
 }
 
-// (256, 4): 4 waves per SIMD, 128 VGPRs, nothing spilled; left to itself the compiler takes 131 (LINEAR) and fits 3
-template <int LINEAR, bool FIELD>
+// (256, 4): 4 waves per SIMD, 128 VGPRs, nothing spilled; left to itself the compiler takes 131 (LINEAR) and fits 3.
+// MASKED (header, "Masks"): W_F comes in beside F and W_M by one nearest gather per output, issued with the intensity
+// gathers; a voxel whose mask value is below 0.5 is treated as one whose q is outside.  MASKED == false compiles to
+// what it compiled to before the parameter existed.
+template <int LINEAR, bool FIELD, bool MASKED>
 __global__ __launch_bounds__(256, 4) void k_similarity(const SimArgs s)
 {
     extern __shared__ __align__(16) unsigned char sim_lds[];
@@ -105,14 +109,18 @@ __global__ __launch_bounds__(256, 4) void k_similarity(const SimArgs s)
         Taps tp[4];
         float f[4];
         bool live[4];
+        float wf[4], wm[4];                                                  // MASKED only
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int x = xt + lx + 16 * k;
             live[k] = row && x < p.ox;
             f[k] = 0.0f;
+            wf[k] = wm[k] = 1.0f;
             float ux = 0.0f, uy = 0.0f, uz = 0.0f;
             if (live[k]) {
                 f[k] = s.F[orow + (size_t)x];
+                if (MASKED && s.w.wf)
+                    wf[k] = s.w.wf[orow + (size_t)x];
                 if (FIELD) {
                     const float *u = s.field + orow + (size_t)x;
                     ux = u[0];
@@ -121,11 +129,12 @@ __global__ __launch_bounds__(256, 4) void k_similarity(const SimArgs s)
                 }
             }
             const double xd = (double)x;
-            if (FIELD)
-                tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, xd + (double)ux, yd + (double)uy, zd + (double)uz);
-            else
-                tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry),
-                                        pull(s.a + 8, xd, rz));
+            const double qx = FIELD ? xd + (double)ux : pull(s.a, xd, rx);
+            const double qy = FIELD ? yd + (double)uy : pull(s.a + 4, xd, ry);
+            const double qz = FIELD ? zd + (double)uz : pull(s.a + 8, xd, rz);
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
+            if (MASKED && s.w.wm)
+                wm[k] = s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
         }
         float m[4];
 #pragma unroll
@@ -133,7 +142,7 @@ __global__ __launch_bounds__(256, 4) void k_similarity(const SimArgs s)
             m[k] = gather<LINEAR>(p.src, tp[k], 0.0f);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const bool counted = live[k] && tp[k].in;
+            const bool counted = MASKED ? live[k] && tp[k].in && mask_in(wf[k]) && mask_in(wm[k]) : live[k] && tp[k].in;
             const int idx = bin_of(f[k], s.lo_f, s.s_f, B) * B + bin_of(m[k], s.lo_m, s.s_m, B);
             commit(h, idx, counted);
             if (counted) {
@@ -194,7 +203,7 @@ __global__ __launch_bounds__(256) void k_similarity_finish(const unsigned long l
     }
 }
 
-template <bool FIELD>
+template <bool FIELD, bool MASKED>
 int run(const char *fn, SimArgs &s, int interp, void *d_stats, void *stream)
 {
     const GridArgs &p = s.g;
@@ -203,9 +212,9 @@ int run(const char *fn, SimArgs &s, int interp, void *d_stats, void *stream)
     const unsigned long long passes = ((unsigned long long)p.ntiles + grid - 1) / grid;
     if (passes * (unsigned long long)(TX * TY * TZ) > 0xffffffffull)
         return launch_fail(fn, "grid too large");
-    void (*k)(const SimArgs) = interp == SIFT3D_AMD_INTERP_NEAREST ? k_similarity<0, FIELD>
-                               : p.nx >= 2                         ? k_similarity<2, FIELD>
-                                                                   : k_similarity<1, FIELD>;
+    void (*k)(const SimArgs) = interp == SIFT3D_AMD_INTERP_NEAREST ? k_similarity<0, FIELD, MASKED>
+                               : p.nx >= 2                         ? k_similarity<2, FIELD, MASKED>
+                                                                   : k_similarity<1, FIELD, MASKED>;
     const size_t hb = (size_t)s.bins * s.bins * sizeof(unsigned);
     const size_t lds = hb > SIM_SLOT_BYTES ? hb : SIM_SLOT_BYTES;
     hipStream_t st = (hipStream_t)stream;
@@ -221,11 +230,13 @@ int run(const char *fn, SimArgs &s, int interp, void *d_stats, void *stream)
 } // namespace
 
 // Launcher for sift3d_similarity.c, which has checked every argument (not exported from the library).  A == NULL:
-// through d_field.  s_f, s_m: the bin scales (float) B / (hi - lo).
+// through d_field.  s_f, s_m: the bin scales (float) B / (hi - lo).  d_WF, d_WM: the masks or NULL; with both NULL the
+// unmasked kernels run.
 extern "C" int sift3d_similarity_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
                                         int nx, int ny, int nz, const double *A, const float *d_field, int interp,
                                         int bins, float lo_f, float s_f, float lo_m, float s_m,
-                                        unsigned long long *d_hist, void *d_stats, void *d_work, void *stream)
+                                        unsigned long long *d_hist, void *d_stats, void *d_work, void *stream,
+                                        const float *d_WF, const float *d_WM)
 {
     SimArgs s;
     if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
@@ -240,5 +251,8 @@ extern "C" int sift3d_similarity_launch(const char *fn, const float *d_F, int ox
     s.hist = d_hist;
     s.pcnt = (unsigned long long *)d_work;
     s.psum = (double *)d_work + SIM_GRID;
-    return A ? run<false>(fn, s, interp, d_stats, stream) : run<true>(fn, s, interp, d_stats, stream);
+    s.w = MaskArgs{d_WF, d_WM};
+    if (d_WF || d_WM)
+        return A ? run<false, true>(fn, s, interp, d_stats, stream) : run<true, true>(fn, s, interp, d_stats, stream);
+    return A ? run<false, false>(fn, s, interp, d_stats, stream) : run<true, false>(fn, s, interp, d_stats, stream);
 }

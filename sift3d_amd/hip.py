@@ -168,7 +168,27 @@ def lib():
         "sift3d_hip_similarity_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
                                                   C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp,
                                                   vp, vp]),
+        "sift3d_hip_similarity_affine_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                          C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_float,
+                                                          C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp]),
+        "sift3d_hip_similarity_field_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                         vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                                         C.c_float, vp, vp, vp, vp, vp, vp]),
         "sift3d_amd_affine_normal_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_affine_normal_eqs_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                          C.c_int, C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
+        "sift3d_amd_affine_refine_masked_work_bytes": (C.c_size_t, [C.c_int] * 7),
+        "sift3d_amd_affine_refine_masked_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                             C.c_int, C.POINTER(C.c_double),
+                                                             C.POINTER(AffineRefineParams),
+                                                             C.POINTER(AffineRefineResult), vp, vp, vp, vp]),
+        "sift3d_hip_ffd_evaluate_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
+                                           + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp,
+                                                              vp, vp]),
+        "sift3d_amd_ffd_refine_masked_work_bytes": (C.c_size_t, [C.c_int] * 10),
+        "sift3d_amd_ffd_refine_masked_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                          C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
+                                                          C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp]),
         "sift3d_hip_affine_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                                    C.POINTER(C.c_double), vp, vp, vp]),
         "sift3d_amd_affine_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, C.POINTER(C.c_double)]),
@@ -587,16 +607,35 @@ def similarity_stats(stats):
     return int(raw[:8].view(np.uint64)[0]), raw[8:].view(np.float64).copy()
 
 
-def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=None, work=None):
+def _masks(what, F, M, mask_fixed, mask_moving):
+    """The two masks of a masked entry (include/sift3d_amd.h, "Masks") as device pointers: each None (NULL: all in) or a
+    contiguous float32 CUDA tensor of its volume's shape on F's device.  Returns None when both are None (the unmasked
+    entry is called), else (pointer or None, pointer or None)."""
+    if mask_fixed is None and mask_moving is None:
+        return None
+    out = []
+    for w, v, name in ((mask_fixed, F, "mask_fixed"), (mask_moving, M, "mask_moving")):
+        if w is not None:
+            _tensor(w, "%s: %s must be a contiguous float32 CUDA tensor of its volume's shape %s on the fixed volume's "
+                    "device" % (what, name, tuple(v.shape)), shape=tuple(v.shape), device=F.device)
+        out.append(None if w is None else w.data_ptr())
+    return tuple(out)
+
+
+def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=None, work=None, mask_fixed=None,
+               mask_moving=None):
     """The joint histogram and moments of the fixed volume F [oz, oy, ox] and the moving volume M [nz, ny, nx] seen
     through a pull map (sift3d_hip_similarity_affine / _field), torch CUDA float32 contiguous, on torch's current
     stream.  transform: a 3 x 4 affine pull map, a field tensor [3, oz, oy, ox], or None: the identity, which needs
     equal shapes.  range_f, range_m: (lo, hi) of the bins.  Returns (hist int64 [bins, bins] indexed [b_f, b_m],
     stats): stats is the device record, read with similarity_stats (which waits for the stream), as reading hist
-    does.  hist, work: the caller's buffers (int64 [bins, bins]; sift3d_amd_similarity_work_bytes bytes)."""
+    does.  hist, work: the caller's buffers (int64 [bins, bins]; sift3d_amd_similarity_work_bytes bytes).  mask_fixed,
+    mask_moving: float32 masks of F's and M's shapes (in where >= 0.5; header, "Masks"); with either given the call goes
+    to the _masked entry, with both None to the unmasked one."""
     import torch
     for t in (F, M):
         _tensor(t, "similarity: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    masks = _masks("similarity", F, M, mask_fixed, mask_moving)
     mode = _interp(interp)
     bins = int(bins)
     if not 2 <= bins <= SIMILARITY_MAX_BINS:
@@ -629,7 +668,11 @@ def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=No
     stats = torch.empty(SIMILARITY_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
     (lo_f, hi_f), (lo_m, hi_m) = ((float(np.float32(v)) for v in r) for r in (range_f, range_m))
     tail = (mode, bins, lo_f, hi_f, lo_m, hi_m, hist.data_ptr(), stats.data_ptr(), work.data_ptr(), current_stream())
-    if field is None:
+    if masks is not None:
+        name = "sift3d_hip_similarity_%s_masked" % ("affine" if field is None else "field")
+        T = a.ctypes.data_as(C.POINTER(C.c_double)) if field is None else field.data_ptr()
+        _check(getattr(lib(), name)(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, T, *tail, *masks), name)
+    elif field is None:
         _check(lib().sift3d_hip_similarity_affine(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
                                                   a.ctypes.data_as(C.POINTER(C.c_double)), *tail),
                "sift3d_hip_similarity_affine")
@@ -671,17 +714,18 @@ def affine_normal_record(record):
     return int(raw["n"]), float(raw["see"]), raw["b"].copy(), raw["H"].copy()
 
 
-def affine_normal_equations(F, M, A, record=None, work=None, raw=False):
+def affine_normal_equations(F, M, A, record=None, work=None, raw=False, mask_fixed=None, mask_moving=None):
     """The Gauss-Newton normal equations of the mean squared difference of the fixed volume F [oz, oy, ox] and the
     moving volume M [nz, ny, nx] seen through the 3 x 4 pull map A, over A's 12 parameters centred on F's grid
     (sift3d_hip_affine_normal_eqs), torch CUDA float32 contiguous, on torch's current stream.  Returns
     (n, S_ee, b [12], H [12, 12]) on the host (which waits for the stream), or with raw=True the device record (read
     it with affine_normal_record).  record, work: the caller's buffers (int64 [158]; sift3d_amd_affine_normal_work_bytes
-    bytes)."""
+    bytes).  mask_fixed, mask_moving: as similarity's (sift3d_hip_affine_normal_eqs_masked)."""
     import torch
     for t in (F, M):
         _tensor(t, "affine_normal_equations: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
     _same_device("affine_normal_equations", F, M)
+    masks = _masks("affine_normal_equations", F, M, mask_fixed, mask_moving)
     a = _affine12(A, "affine_normal_equations")
     oz, oy, ox = F.shape
     nz, ny, nx = M.shape
@@ -691,9 +735,14 @@ def affine_normal_equations(F, M, A, record=None, work=None, raw=False):
             shape=(AFFINE_NORMAL_BYTES // 8,), device=F.device, dtype="int64")
     need = lib().sift3d_amd_affine_normal_work_bytes(ox, oy, oz)
     work = _work(work, (need + 3) // 4, F, "affine_normal_equations")
-    _check(lib().sift3d_hip_affine_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                              record.data_ptr(), work.data_ptr(), current_stream()),
-           "sift3d_hip_affine_normal_eqs")
+    if masks is not None:
+        _check(lib().sift3d_hip_affine_normal_eqs_masked(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                                         record.data_ptr(), work.data_ptr(), current_stream(), *masks),
+               "sift3d_hip_affine_normal_eqs_masked")
+    else:
+        _check(lib().sift3d_hip_affine_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                                  record.data_ptr(), work.data_ptr(), current_stream()),
+               "sift3d_hip_affine_normal_eqs")
     return record if raw else affine_normal_record(record)
 
 
@@ -732,24 +781,34 @@ def affine_refine_params(**kw):
     return p
 
 
-def affine_refine(F, M, A, params=None, work=None):
+def affine_refine(F, M, A, params=None, work=None, mask_fixed=None, mask_moving=None):
     """sift3d_amd_affine_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
-    waits for it once per evaluation).  Returns the AffineRefineResult."""
+    waits for it once per evaluation).  Returns the AffineRefineResult.  mask_fixed, mask_moving: as similarity's
+    (sift3d_amd_affine_refine_masked_device)."""
     for t in (F, M):
         _tensor(t, "affine_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
     _same_device("affine_refine", F, M)
+    masks = _masks("affine_refine", F, M, mask_fixed, mask_moving)
     a = _affine12(A, "affine_refine")
     p = params if params is not None else affine_refine_params()
     oz, oy, ox = F.shape
     nz, ny, nx = M.shape
-    need = lib().sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz, p.levels)
+    bytes_of = lib().sift3d_amd_affine_refine_work_bytes if masks is None else \
+        lib().sift3d_amd_affine_refine_masked_work_bytes
+    need = bytes_of(ox, oy, oz, nx, ny, nz, p.levels)
     if need == 0:
         raise ValueError("affine_refine: levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
     work = _work(work, (need + 3) // 4, F, "affine_refine")
     res = AffineRefineResult()
-    _check(lib().sift3d_amd_affine_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                                 C.byref(p), C.byref(res), work.data_ptr(), current_stream()),
-           "sift3d_amd_affine_refine_device")
+    if masks is not None:
+        _check(lib().sift3d_amd_affine_refine_masked_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
+                                                            _dptr(a), C.byref(p), C.byref(res), work.data_ptr(),
+                                                            current_stream(), *masks),
+               "sift3d_amd_affine_refine_masked_device")
+    else:
+        _check(lib().sift3d_amd_affine_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                                     C.byref(p), C.byref(res), work.data_ptr(), current_stream()),
+               "sift3d_amd_affine_refine_device")
     return res
 
 
@@ -830,12 +889,14 @@ def _ffd_record_tensor(lattice):
     return torch.zeros(lib().sift3d_amd_ffd_record_bytes(gx, gy, gz) // 8, dtype=torch.int64, device=lattice.device)
 
 
-def ffd_evaluate(F, M, lattice, spacing, A=None, bending=0.0, work=None):
+def ffd_evaluate(F, M, lattice, spacing, A=None, bending=0.0, work=None, mask_fixed=None, mask_moving=None):
     """One evaluation of the FFD cost at `lattice` (sift3d_hip_ffd_evaluate) on torch's current stream.  Returns
-    (record, grad, field): the device record (read it with ffd_record), the float32 gradient lattice and the field."""
+    (record, grad, field): the device record (read it with ffd_record), the float32 gradient lattice and the field.
+    mask_fixed, mask_moving: as similarity's (sift3d_hip_ffd_evaluate_masked)."""
     import torch
     for t in (F, M):
         _tensor(t, "ffd_evaluate: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    masks = _masks("ffd_evaluate", F, M, mask_fixed, mask_moving)
     gx, gy, gz = _ffd_lattice(lattice, "ffd_evaluate")
     _same_device("ffd_evaluate", F, M, lattice)
     dx, dy, dz = ffd_spacing(spacing, "ffd_evaluate")
@@ -847,10 +908,12 @@ def ffd_evaluate(F, M, lattice, spacing, A=None, bending=0.0, work=None):
     field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
     need = lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz)
     work = _work(work, (need + 3) // 4, F, "ffd_evaluate")
-    _check(lib().sift3d_hip_ffd_evaluate(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx, gy,
-                                         gz, dx, dy, dz, ap, float(bending), field.data_ptr(), record.data_ptr(),
-                                         grad.data_ptr(), work.data_ptr(), current_stream()),
-           "sift3d_hip_ffd_evaluate")
+    args = (F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap,
+            float(bending), field.data_ptr(), record.data_ptr(), grad.data_ptr(), work.data_ptr(), current_stream())
+    if masks is not None:
+        _check(lib().sift3d_hip_ffd_evaluate_masked(*args, *masks), "sift3d_hip_ffd_evaluate_masked")
+    else:
+        _check(lib().sift3d_hip_ffd_evaluate(*args), "sift3d_hip_ffd_evaluate")
     return record, grad, field
 
 
@@ -896,19 +959,23 @@ def ffd_refine_params(**kw):
     return p
 
 
-def ffd_refine(F, M, A=None, params=None, work=None):
+def ffd_refine(F, M, A=None, params=None, work=None, mask_fixed=None, mask_moving=None):
     """sift3d_amd_ffd_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
-    waits for it once per evaluation).  Returns (FFDRefineResult, lattice, field)."""
+    waits for it once per evaluation).  Returns (FFDRefineResult, lattice, field).  mask_fixed, mask_moving: as
+    similarity's (sift3d_amd_ffd_refine_masked_device)."""
     import torch
     for t in (F, M):
         _tensor(t, "ffd_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
     _same_device("ffd_refine", F, M)
+    masks = _masks("ffd_refine", F, M, mask_fixed, mask_moving)
     a, ap = _ffd_A(A, "ffd_refine")
     p = params if params is not None else ffd_refine_params()
     oz, oy, ox = F.shape
     nz, ny, nx = M.shape
     d = tuple(p.spacing)
-    need = lib().sift3d_amd_ffd_refine_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
+    bytes_of = lib().sift3d_amd_ffd_refine_work_bytes if masks is None else \
+        lib().sift3d_amd_ffd_refine_masked_work_bytes
+    need = bytes_of(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
     if need == 0:
         raise ValueError("ffd_refine: levels must be in [1, %d] and the spacing in [1, %d]"
                          % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
@@ -916,9 +983,12 @@ def ffd_refine(F, M, A=None, params=None, work=None):
     lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
     field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
     res = FFDRefineResult()
-    _check(lib().sift3d_amd_ffd_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap, C.byref(p),
-                                              C.byref(res), lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
-                                              current_stream()), "sift3d_amd_ffd_refine_device")
+    args = (F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap, C.byref(p), C.byref(res), lattice.data_ptr(),
+            field.data_ptr(), work.data_ptr(), current_stream())
+    if masks is not None:
+        _check(lib().sift3d_amd_ffd_refine_masked_device(*args, *masks), "sift3d_amd_ffd_refine_masked_device")
+    else:
+        _check(lib().sift3d_amd_ffd_refine_device(*args), "sift3d_amd_ffd_refine_device")
     return res, lattice, field
 
 
