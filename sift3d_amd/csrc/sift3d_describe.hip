@@ -63,8 +63,8 @@ constexpr int HIST_LDS = 800;
 constexpr int FACE_STRIDE = 20;
 // Phase A -> phase B records, field-major: row f holds field f of half a batch (32 voxels; the
 // records go through LDS half a batch at a time: LDS capacity is what limits the waves per CU).
-// Rows are 36 floats apart: the eight rows that the 24 committer lanes of a half-wave read with
-// ds_read_b128 (four voxels at a time) fall on disjoint bank quads.
+// Rows are 36 floats apart: the eleven rows 0..10 (and the three rows 11..13) that the committer lanes of a
+// half-wave read with one ds_read_b128 (four voxels at a time) fall on disjoint bank quads of the 64 banks.
 constexpr int RROW = 36;
 
 #ifdef SIFT3D_AMD_DIAG
@@ -84,6 +84,22 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// acc + x(quad lane) * x with ONE rounding, the quad lane by quad_perm:[3,0,0,0] (lane 0 of a quad takes lane 3's
+// x, lanes 1..3 take lane 0's).  The compiler's DPP combiner leaves multiply-accumulates alone (it would emit
+// v_mov_b32_dpp + v_fmac_f32), hence the instruction by name -- and its hazards are the compiler's no longer: a
+// DPP operand must not be read within two wait states of a VALU write to that register, nor within five of a VALU
+// write to EXEC.  ROUND rules both out by construction: x is a record word that a ds_read_b128 delivered (no VALU
+// write; where the compiler copies a chunk, the copy sits behind the previous round's bin write, and this round's
+// bin address and bin read -- two instructions -- come before the multiply), and the commit chain is straight-line
+// code whose EXEC is all ones and is written by the scalar unit only.
+__device__ __forceinline__ float quad_fmac(float acc, float x)
+{
+    asm("v_fmac_f32_dpp %0, %1, %1 quad_perm:[3,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "+v"(acc)
+        : "v"(x));
+    return acc;
 }
 
 // cart2bary + the acceptance test of icos_hist_bin (sift.c:276-297, 1268-1286) for one face,
@@ -207,8 +223,7 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     float *const hist = hist_[wv];
-    float(*const mw)[RROW] = &rec_[wv][0];
-    float(*const bw)[RROW] = &rec_[wv][8];
+    float(*const xw)[RROW] = &rec_[wv][0];   // rows 0..7 mw[cell], 8..10 bw[vertex]
     int(*const ab)[RROW] = reinterpret_cast<int(*)[RROW]>(&rec_[wv][11]);
     int *const queue = queue_[wv];
     for (int i = threadIdx.x; i < 20 * 16; i += 64 * DWAVES)
@@ -303,12 +318,20 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     const int xsh = 32 - __builtin_clz((unsigned)max(B.xe - B.xs, 1));
     const int ysh = xsh + 32 - __builtin_clz((unsigned)max(B.ye - B.ys, 1));
     const uint32_t xmask = (1u << xsh) - 1u, ymask = (1u << (ysh - xsh)) - 1u;
-    // phase B roles: each half-wave commits one voxel per round; its lanes 0..23 are the
-    // (trilinear cell corner, face vertex) pairs of that voxel.  Lanes 24..31 repeat lane 0's
-    // work (same address, same value: harmless; giving them scratch slots of their own measured
-    // MORE bank conflicts), which keeps the commit free of predication.
+    // phase B roles: each half-wave commits one voxel per round.  Quad q = l5 >> 2 of the half-wave is trilinear
+    // cell corner q, lane t = l5 & 3 of the quad is face vertex t; lane 3 repeats lane 0's work (same address,
+    // same value: harmless; giving the idle lanes scratch slots of their own measured MORE bank conflicts), which
+    // keeps the commit free of predication.  The term of lane (cell c, vertex j) is mw[c] * bw[j]: the lanes of
+    // a quad share mw[c], and every quad holds bw[0..2], so a lane reads ONE of the two factors from LDS (row pxr:
+    // lane 0 mw[c], lanes 1 and 2 bw[1] and bw[2], lane 3 bw[0]) and takes the other from its quad with the DPP
+    // operand of the commit's multiply (quad_perm:[3,0,0,0]: lane 0 gets lane 3's bw[0], the others lane 0's
+    // mw[c]).  The product commutes bit for bit, so the sums are those of the three-read form.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
+#error "k_describe's commit routes its factors with DPP quad_perm on wave64: validated on gfx942 / gfx950 only"
+#endif
     const int half = lane >> 5, l5 = lane & 31;
-    const int pc = l5 < 24 ? l5 / 3 : 0, pj = l5 < 24 ? l5 - 3 * pc : 0;
+    const int pc = l5 >> 2, pt = l5 & 3, pj = pt < 3 ? pt : 0;
+    const int pxr = pt == 0 ? pc : 8 + pj;
     const int pdx = (pc >> 2) & 1, pdy = (pc >> 1) & 1, pdz = pc & 1;
     // byte offset of this lane's cell corner, in this half-wave's histogram (EXACT: in THE histogram while
     // this half-wave's rounds run -- sequence A: half-wave 0, sequence B: half-wave 1 --, else in the scratch
@@ -403,7 +426,7 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // u.)  The chain of dependent LDS round trips is the longest latency of the kernel and needs
     // almost no VALU, so each pass is issued in one basic block with half of the arithmetic of
     // the NEXT batch (see batch()), which the scheduler interleaves with it.  Records of four
-    // rounds are read with three 16-byte loads, one chunk ahead.
+    // rounds are read with two 16-byte loads, one chunk ahead.
     float *const rrow = &rec_[wv][7 * half][l5];
     auto commit_write = [&](int pass) {
 #pragma unroll
@@ -420,7 +443,7 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // latency, and only the other waves of the SIMD can fill it).  Here every round carries a
     // SLICE of independent work -- a dozen VALU instructions of phase A of this batch, or of the
     // sample requests of the next -- between the bin read and the wait for it; scheduling
-    // barriers keep the slices where they are put.  Records of four rounds are read with three
+    // barriers keep the slices where they are put.  Records of four rounds are read with two
     // 16-byte loads, one chunk ahead.
 #define SB() __builtin_amdgcn_sched_barrier(0)
 // DESC_OPT (bit mask, A/B builds only; the shipped value is the default below):
@@ -435,29 +458,31 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
 #ifndef DESC_OPT
 #define DESC_OPT 7
 #endif
+// COMMIT_ADD(old, x): old + x * (the OTHER factor of the lane's term, which a lane of its quad holds as ITS x: see
+// "phase B roles").  The other factor is the multiply's DPP operand, no instruction of its own: v_mul_f32_dpp
+// (the compiler folds the v_mov_b32_dpp of QUAD_X into the multiply) + v_add_f32, or one v_fmac_f32_dpp.
+#define QUAD_X(v) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x03, 0xf, 0xf, true))
 #if DESC_OPT & 1
-#define COMMIT_ADD(old, m, b) (EXACT ? (old) + (m) * (b) : __builtin_fmaf(m, b, old))
+#define COMMIT_ADD(old, x) (EXACT ? (old) + QUAD_X(x) * (x) : quad_fmac(old, x))
 #else
-#define COMMIT_ADD(old, m, b) ((old) + (m) * (b))
+#define COMMIT_ADD(old, x) ((old) + QUAD_X(x) * (x))
 #endif
 // a value is computed in the slice that names it here (not sunk to its first use in a later one)
 #define KEEP(v) asm volatile("" ::"v"(v))
 #define COMMIT_BEGIN(coff)                                                                    \
     const int coff4 = (coff);                                                                 \
     int4 cb4 = *reinterpret_cast<const int4 *>(&ab[pj][hb]);                                   \
-    float4 cw4 = *reinterpret_cast<const float4 *>(&mw[pc][hb]);                               \
-    float4 cx4 = *reinterpret_cast<const float4 *>(&bw[pj][hb]);                               \
+    float4 cx4 = *reinterpret_cast<const float4 *>(&xw[pxr][hb]);                               \
     int4 nb4 = cb4;                                                                           \
-    float4 nw4 = cw4, nx4 = cx4;
+    float4 nx4 = cx4;
 #define ROUND(u, ...)                                                                         \
     {                                                                                         \
         if (((u) & 3) == 0 && (u) + 4 < 16) {                                                 \
             nb4 = *reinterpret_cast<const int4 *>(&ab[pj][hb + (u) + 4]);                      \
-            nw4 = *reinterpret_cast<const float4 *>(&mw[pc][hb + (u) + 4]);                    \
-            nx4 = *reinterpret_cast<const float4 *>(&bw[pj][hb + (u) + 4]);                    \
+            nx4 = *reinterpret_cast<const float4 *>(&xw[pxr][hb + (u) + 4]);                    \
         }                                                                                     \
         const int mb_[4] = { cb4.x, cb4.y, cb4.z, cb4.w };                                    \
-        const float mv_[4] = { cw4.x, cw4.y, cw4.z, cw4.w }, bv_[4] = { cx4.x, cx4.y, cx4.z, cx4.w }; \
+        const float xv_[4] = { cx4.x, cx4.y, cx4.z, cx4.w };                                  \
         float *bin_ = reinterpret_cast<float *>(reinterpret_cast<char *>(hist) + (mb_[(u) & 3] + coff4)); \
         float old_ = 0.0f;                                                                    \
         if (!DESC_ABLATE(1))                                                                  \
@@ -466,10 +491,9 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
         { __VA_ARGS__ }                                                                       \
         SB();                                                                                 \
         if (!DESC_ABLATE(1))                                                                  \
-            *bin_ = COMMIT_ADD(old_, mv_[(u) & 3], bv_[(u) & 3]);      /* sift.c:1371-1373 */ \
+            *bin_ = COMMIT_ADD(old_, xv_[(u) & 3]);                    /* sift.c:1371-1373 */ \
         if (((u) & 3) == 3) {                                                                 \
             cb4 = nb4;                                                                        \
-            cw4 = nw4;                                                                        \
             cx4 = nx4;                                                                        \
         }                                                                                     \
         SB();                                                                                 \
