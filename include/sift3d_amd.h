@@ -866,6 +866,91 @@ sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, co
                                     void *d_work, void *stream, const float *d_WF, const float *d_WM);
 
 /* ------------------------------------------------------------------------ */
+/* Affine refinement under a linear intensity map (NCC)                      */
+/* ------------------------------------------------------------------------ */
+/* "Intensity-driven affine refinement" with a linear intensity map fitted together with the pull map:
+ *     minimise over A, alpha, beta:   sum over counted p of (alpha * m_A(p) + beta - f(p))^2
+ * The MSD is meaningful only when both volumes share one intensity scale; this cost does not change under any gain
+ * (negative ones included) or offset of either volume.  For a fixed A the best (alpha, beta) is the regression of f on
+ * m and the residual is V_f (1 - ncc^2), so this is Gauss-Newton on 1 - ncc^2.  Every sum that the 14-parameter normal
+ * equations need is free of alpha and beta: one gather-and-reduce pass per evaluation, as for the MSD.  No upstream
+ * counterpart: PARITY UNPINNED, pinned to this contract and its numpy restatement (tests/affine_ncc_restatement.py).
+ *
+ * The pull map, the inside test, the LINEAR sample m, its gradient g, the centring c, P and J[4 d + j] = G_d P_j are
+ * those of "Intensity-driven affine refinement", word for word; d_WF and d_WM are "Masks"' masks, word for word, and
+ * either may be NULL.  Per counted voxel, in double: f = F(p), m the sample, G_d = g_d (floats widened; every product of
+ * two of them is exact).
+ *
+ * The record (sift3d_hip_affine_ncc_normal_eqs), SIFT3D_AMD_AFFINE_NCC_BYTES, 8-byte aligned:
+ *     uint64 n;
+ *     double S_m = sum m, S_f = sum f, S_mm = sum m m, S_fm = sum f m, S_ff = sum f f;
+ *     double u[12] = sum J;   double v[12] = sum J m;   double w[12] = sum J f;
+ *     double H[12][12] = sum J J^T,
+ * H stored in full and symmetric bit for bit: 60 + 36 + 5 = 101 summed doubles and the count.  The rules are the MSD
+ * record's: how a term is factored and in which order the terms are added is the implementation's (every term carries
+ * at most 8 roundings), but it is a function of the shapes only: per-lane sums, per-workgroup partials (one slot per
+ * workgroup of a grid of min(tiles, SIFT3D_AMD_SIMILARITY_GRID) workgroups, whatever the device), then the slots in a
+ * fixed order.  A call repeats its bytes on any device.  (This implementation sums H as sift3d_hip_affine_normal_eqs
+ * does, operation for operation: the two H agree bit for bit.  The five moments are the similarity record's up to the
+ * order of the sums.)  The whole record is written on `stream` by the call; n == 0 leaves it all zero.
+ * The entry is asynchronous on `stream`, allocates nothing, uses 64-bit offsets and checks its arguments before any
+ * device call: -1 on NULL pointers (but the masks), dims <= 0, a non-finite A, a misaligned buffer (record, work: 8
+ * bytes; the rest 4), an output that overlaps an input, a mask, the work buffer or another output, a grid with too many
+ * tiles.  d_work: sift3d_amd_affine_ncc_normal_work_bytes() bytes, 8-byte aligned.
+ *
+ * Fit (sift3d_amd_affine_ncc_fit, host, double, in this order, unfused):
+ *     nd = (double) n;  V_m = S_mm - S_m * S_m / nd;  V_f = S_ff - S_f * S_f / nd;  C = S_fm - S_f * S_m / nd
+ * The fit is defined when n >= 2 and V_m > 0.  Then
+ *     alpha = C / V_m;  beta = (S_f - alpha * S_m) / nd;  cost = max((V_f - alpha * C) / nd, 0)
+ *     ncc   = C / sqrt(V_f * V_m), 0 when V_f <= 0           ("Similarity measures"' formula on these sums)
+ * out = (alpha, beta, cost, ncc).  -1 on a NULL pointer or an undefined fit; out is all NaN when the fit is undefined.
+ *
+ * Step (sift3d_amd_affine_ncc_lm_step, host, double).  The 14 parameters are the 12 of the pull map, then alpha (12) and
+ * beta (13); the system is built at (alpha, beta) of the fit:
+ *     H14[i][j] = (alpha * alpha) * H[i][j]      H14[i][12] = alpha * v[i]      H14[i][13] = alpha * u[i]
+ *     H14[12][12] = S_mm    H14[12][13] = S_m    H14[13][13] = nd
+ *     b14[i] = alpha * ((alpha * v[i] + beta * u[i]) - w[i])
+ *     b14[12] = (alpha * S_mm + beta * S_m) - S_fm      b14[13] = (alpha * S_m + beta * nd) - S_f
+ * (i, j < 12; H14 symmetric).  The free set is the bits of free_mask plus parameters 12 and 13, which are always free.
+ * K = H14 + lambda diag(H14) (K_ii = H14_ii + lambda * H14_ii) on the free set, K delta14 = -b14 by the Cholesky
+ * factorisation and the two triangular solves of sift3d_amd_affine_lm_step (one routine); delta is the first 12 entries
+ * of delta14, 0 outside the free set.  -1, with delta all zero, on that step's refusals (NULL pointers, an empty mask
+ * or bits past 0xFFF, lambda negative or not finite), on an undefined fit (n < 2 included), and when K is not positive
+ * definite (alpha == 0 makes it so).  The update is sift3d_amd_affine_apply_delta.
+ *
+ * Driver (sift3d_amd_affine_ncc_refine_device).  sift3d_amd_affine_refine_device's loop, levels (sift3d_hip_restrict2 of
+ * volumes and masks, the translation halved and doubled) and stop reasons, one loop in the code too, with `cost` of the
+ * fit in the place of S_ee / n.  An evaluation whose fit is undefined has no cost: as a trial it is rejected, and as a
+ * level's first evaluation it stops the level with LM_FAILED (the step refuses).  Params and result are
+ * sift3d_amd_affine_refine_params and sift3d_amd_affine_refine_result as they are; the trail's `msd` field carries
+ * `cost` (NaN where undefined).  fit_out = (alpha, beta, cost, ncc) of the fit at the final A on level 0, all NaN where
+ * that is undefined or no evaluation was made.  Checks, alignment, overlap rules, asynchrony and "allocates nothing"
+ * are the masked MSD driver's, and fit_out must not be NULL.
+ * d_work: sift3d_amd_affine_ncc_refine_work_bytes() bytes, whether or not a mask is NULL: the partial slots, the record
+ * rounded up to 16 bytes, then the levels as in the masked MSD driver. */
+#define SIFT3D_AMD_AFFINE_NCC_BYTES 1488           /* 8 + 5 * 8 + 3 * 12 * 8 + 144 * 8 */
+/* bytes of d_work for sift3d_hip_affine_ncc_normal_eqs on this fixed grid (0 for dims <= 0) */
+SIFT3D_AMD_API size_t sift3d_amd_affine_ncc_normal_work_bytes(int ox, int oy, int oz);
+/* d_F [oz][oy][ox], d_M [nz][ny][nx], d_record the record above; d_WF, d_WM the masks or NULL */
+SIFT3D_AMD_API int
+sift3d_hip_affine_ncc_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const double *A /*12*/, void *d_record, void *d_work, void *stream,
+                                 const float *d_WF, const float *d_WM);
+/* host only: record on the host */
+SIFT3D_AMD_API int sift3d_amd_affine_ncc_fit(const void *record, double *out /*4*/);
+SIFT3D_AMD_API int
+sift3d_amd_affine_ncc_lm_step(const void *record, unsigned free_mask, double lambda, double *delta /*12*/);
+/* bytes of d_work for the driver (0 for bad arguments) */
+SIFT3D_AMD_API size_t
+sift3d_amd_affine_ncc_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels);
+/* A_io [12] and fit_out [4] on the host; waits for `stream` once per evaluation */
+SIFT3D_AMD_API int
+sift3d_amd_affine_ncc_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    double *A_io, const sift3d_amd_affine_refine_params *params,
+                                    sift3d_amd_affine_refine_result *result, double *fit_out /*4*/, void *d_work,
+                                    void *stream, const float *d_WF, const float *d_WM);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Time per pass of the affine normal equations (sift3d_hip_affine_normal_eqs) at 512^3 and 256^3 beside the
-similarity pass (sift3d_hip_similarity_affine, B = 64, LINEAR) on the same volumes and transform, in one run.
+"""Time per pass of the affine normal equations (sift3d_hip_affine_normal_eqs: the MSD; and
+sift3d_hip_affine_ncc_normal_eqs: the fit under a linear intensity map) at 512^3 and 256^3 beside the similarity pass
+(sift3d_hip_similarity_affine, B = 64, LINEAR) on the same volumes and transform, in one run.
 
 Both passes walk the fixed grid and gather the moving volume through the same affine (a rotation of 5 degrees about
 (1, 2, 3) through the centre): 8 B read per voxel, nothing written.  The similarity pass commits a histogram and six
@@ -14,7 +15,9 @@ Times are HIP events around `reps` back-to-back calls, per call, the minimum of 
 
 SIFT3D_AMD_LIB selects another build of the library: one made with `make AFFDEF=-DSIFT3D_AFFINE_REFINE_NAIVE` times
 the direct formulation (72 accumulators updated per voxel) instead of the factored one (tile sums over x, folded
-once per tile).  Registers and occupancy are the compiler's (`hipcc -Rpass-analysis=kernel-resource-usage`); pass
+once per tile); one made with `make AFFDEF=-DSIFT3D_AFFINE_NCC_ONE_KERNEL` times the NCC pass as one kernel at one wave
+per SIMD instead of two kernels at two and three (H, v, S_mm and the count; then u, w and the other moments).
+Registers and occupancy are the compiler's (`hipcc -Rpass-analysis=kernel-resource-usage`); pass
 them in --label to keep them with the numbers."""
 import argparse
 import os
@@ -64,15 +67,22 @@ def run(label, reps):
         work = torch.empty(hip.affine_normal_work_bytes(), dtype=torch.uint8, device="cuda")
         s = _time(lambda: hip.similarity(F, M, A, 64, (lo, hi), (lo, hi), "linear", hist, swork), reps)
         a = _time(lambda: hip.affine_normal_equations(F, M, A, rec, work, raw=True), reps)
+        nrec = torch.empty(hip.AFFINE_NCC_BYTES // 8, dtype=torch.int64, device="cuda")
+        nwork = torch.empty(hip.affine_ncc_normal_work_bytes(), dtype=torch.uint8, device="cuda")
+        cn = _time(lambda: hip.affine_ncc_normal_equations(F, M, A, nrec, nwork, raw=True), reps)
         nbytes = 8.0 * float(n) ** 3
-        for name, t, rel in (("similarity B=64", s, "-"), ("affine_normal_eqs", a, "%.3f" % (min(a) / min(s)))):
+        for name, t, rel in (("similarity B=64", s, "-"), ("affine_normal_eqs", a, "%.3f" % (min(a) / min(s))),
+                             ("affine_ncc_normal_eqs", cn, "%.3f" % (min(cn) / min(s)))):
             print("%-6s %-22s %8.4f [%.4f-%.4f] %13s %8.0f %8.3f" % (
                 "%d^3" % n, name, min(t), min(t), max(t), rel, nbytes / min(t) / 1e6,
                 nbytes / min(t) / 1e-3 / PEAK_BPS))
         count, see, _, H = hip.affine_normal_record(rec)
         scount, sums = hip.similarity_stats(hip.similarity(F, M, A, 64, (lo, hi), (lo, hi), "linear", hist, swork)[1])
         assert count == scount > 0 and abs(see - sums[5]) <= 1e-9 * see and np.array_equal(H, H.T)
-        print("# %d^3: %d of %d voxels counted; msd %.6f" % (n, count, n ** 3, see / count))
+        ncc = hip.affine_ncc_record(nrec)
+        assert int(ncc["n"]) == count and np.array_equal(ncc["H"], H) and abs(ncc["S_ff"] - sums[2]) <= 1e-9 * sums[2]
+        print("# %d^3: %d of %d voxels counted; msd %.6f; ncc pass / msd pass %.3f"
+              % (n, count, n ** 3, see / count, min(cn) / min(a)))
         del F, M
 
 

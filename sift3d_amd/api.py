@@ -619,7 +619,8 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
     fixed voxel), inliers (mask over the matches), num_matches, warped (tensor shaped like fixed)).
     refine=True (or a dict of refine_affine's keyword arguments) runs refine_affine from the RANSAC result and
     returns RefinedRegistration(A, inliers, num_matches, warped, A_ransac, refinement): A and warped are the refined
-    map and its resampling, A_ransac is what refine=False returns as A, refinement the AffineRefinement."""
+    map and its resampling, A_ransac is what refine=False returns as A, refinement the AffineRefinement (the
+    NccAffineRefinement with refine=dict(metric="ncc"))."""
     import torch
     from . import hip
     p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
@@ -1033,11 +1034,13 @@ AffineRefinement = collections.namedtuple(
     "AffineRefinement", "A msd count accepted lambdas levels level_slices evaluations stop warped")
 RefinedRegistration = collections.namedtuple("RefinedRegistration",
                                              "A inliers num_matches warped A_ransac refinement")
+NccAffineRefinement = collections.namedtuple(
+    "NccAffineRefinement", "A cost count accepted lambdas levels level_slices evaluations stop warped ncc gain offset")
 AFFINE_FREE = {"affine": 0xFFF, "translation": 0x888}
 
 
 def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", mask_fixed=None, mask_moving=None,
-                  **params):
+                  metric="msd", **params):
     """Move the 3 x 4 affine pull map A (fixed voxel -> moving voxel, as similarity's transform; None: the identity,
     which needs no equal shapes) towards a smaller mean squared difference between `fixed` and `moving` seen through
     it, by Levenberg-Marquardt steps on the device's Gauss-Newton normal equations (contract: include/sift3d_amd.h,
@@ -1049,9 +1052,17 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     steps and count towards min_overlap, and coarser levels use the restricted masks.  Returns AffineRefinement(A, msd,
     count, accepted, lambdas, levels: one entry per evaluation in the order run; level_slices: {level: slice into
     those}; evaluations; stop: "converged", "lambda", "evaluations" or "lm_failed" of level 0; warped: `moving` through
-    A on the fixed grid).  Waits for torch's current stream once per evaluation."""
+    A on the fixed grid).  Waits for torch's current stream once per evaluation.
+    metric="ncc" fits a linear intensity map together with A, minimising sum (gain * m + offset - f)^2 over the three
+    (Gauss-Newton on 1 - ncc^2; contract: "Affine refinement under a linear intensity map (NCC)"), so the result does
+    not change under a gain (a negative one included) or an offset of either volume, where the MSD's does.  It returns
+    NccAffineRefinement: AffineRefinement's fields with `cost` (the mean squared residual of the fit) in the place of
+    `msd`, then ncc, gain and offset of the fit at the final A.  `warped` is still `moving` through A: its intensities
+    are not remapped (gain * warped + offset is the fitted image).  Any other metric raises ValueError."""
     import torch
     from . import hip
+    if metric not in ("msd", "ncc"):
+        raise ValueError("refine_affine: metric must be 'msd' or 'ncc', not %r" % (metric,))
     if interp != "linear":
         raise ValueError("refine_affine: the sample is linear; interp=%r has no gradient" % (interp,))
     mask = AFFINE_FREE.get(free, free) if isinstance(free, str) else free
@@ -1073,7 +1084,10 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     M = _similarity_volume(moving, "refine_affine", "moving", F.device)
     WF = _mask_tensor(WF, F, "refine_affine", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_affine", "mask_moving")
-    res = hip.affine_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
+    if metric == "ncc":
+        res, fit = hip.affine_ncc_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
+    else:
+        res = hip.affine_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     k = res.evaluations
     trail = res.trail[:k]
     lv = np.array([e.level for e in trail], np.int64)
@@ -1084,9 +1098,12 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     A1 = np.array(res.A[:], np.float64).reshape(3, 4)
     warped = torch.empty_like(F)
     hip.warp_affine(M, warped, A1, "linear")
-    return AffineRefinement(A1, np.array([e.msd for e in trail]), np.array([e.n for e in trail], np.int64),
-                            np.array([bool(e.accepted) for e in trail]), np.array([e.lambda_ for e in trail]), lv,
-                            slices, k, hip.AFFINE_STOPS[res.stop], warped)
+    out = AffineRefinement(A1, np.array([e.msd for e in trail]), np.array([e.n for e in trail], np.int64),
+                           np.array([bool(e.accepted) for e in trail]), np.array([e.lambda_ for e in trail]), lv,
+                           slices, k, hip.AFFINE_STOPS[res.stop], warped)
+    if metric == "ncc":
+        return NccAffineRefinement(*out, ncc=float(fit[3]), gain=float(fit[0]), offset=float(fit[1]))
+    return out
 
 
 # ---- B-spline free-form deformation ---------------------------------------------------------------
@@ -1180,14 +1197,16 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
 
 
 def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
-                 ffd_params=None, **detector_kw):
+                 ffd_params=None, refine=True, **detector_kw):
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
-    refine_ffd's further keyword arguments.  The volumes are torch CUDA float32 tensors, or Images / arrays, which are
+    refine_ffd's further keyword arguments; refine: True, or register's dict of refine_affine's keyword arguments
+    (dict(metric="ncc") for the affine stage; the FFD stage itself minimises the MSD).  The volumes are torch CUDA float32 tensors, or Images / arrays, which are
     uploaded.  Returns FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""
     F = _similarity_volume(fixed, "register_ffd", "fixed")
     M = _similarity_volume(moving, "register_ffd", "moving", F.device)
-    reg = register(M, F, nn_thresh, err_thresh, num_iter, seed, refine=True, **detector_kw)
+    reg = register(M, F, nn_thresh, err_thresh, num_iter, seed, refine=refine if isinstance(refine, dict) else True,
+                   **detector_kw)
     ref = refine_ffd(M, F, reg.refinement.A, spacing, levels, bending, **(ffd_params or {}))
     return FFDRegistration(reg, ref)
 

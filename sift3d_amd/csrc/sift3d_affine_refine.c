@@ -2,16 +2,23 @@
  * Levenberg-Marquardt step and the parameter update on the host, and the driver that iterates them
  * (included at the end of sift3d_host.c, after sift3d_similarity.c).
  *
- * The contract is in include/sift3d_amd.h, "Intensity-driven affine refinement"; the kernels are in
- * sift3d_affine_refine.hip, reached through the launcher below after the checks here.  Arguments are checked before
- * the device is touched, so bad input is refused on a machine without a GPU too. */
+ * The contract is in include/sift3d_amd.h, "Intensity-driven affine refinement" (the MSD) and "Affine refinement under
+ * a linear intensity map (NCC)": two metrics, each with its pass, its record, its cost and its step, and one driver
+ * loop over either (affine_metric).  The kernels are in sift3d_affine_refine.hip, reached through the launchers below
+ * after the checks here.  Arguments are checked before the device is touched, so bad input is refused on a machine
+ * without a GPU too. */
 
 int sift3d_affine_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                                 int ny, int nz, const double *A, void *d_record, void *d_work, void *stream,
                                 const float *d_WF, const float *d_WM);
 
-/* a double per statistic (60 + 12 + 1, and the uint64 count) per partial slot */
+int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                                    int ny, int nz, const double *A, void *d_record, void *d_work, void *stream,
+                                    const float *d_WF, const float *d_WM);
+
+/* a double per statistic (60 + 12 + 1, and the uint64 count) per partial slot; NCC: 60 + 36 + 5 and the count */
 #define AFFINE_NORMAL_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 74 * 8)
+#define AFFINE_NCC_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 102 * 8)
 
 size_t sift3d_amd_affine_normal_work_bytes(int ox, int oy, int oz)
 {
@@ -20,10 +27,18 @@ size_t sift3d_amd_affine_normal_work_bytes(int ox, int oy, int oz)
     return AFFINE_NORMAL_WORK_BYTES;
 }
 
-/* the shared body of the two entries: d_WF, d_WM are the masks ("Masks") or NULL */
+size_t sift3d_amd_affine_ncc_normal_work_bytes(int ox, int oy, int oz)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0)
+        return 0;
+    return AFFINE_NCC_WORK_BYTES;
+}
+
+/* the shared body of the three entries: d_WF, d_WM are the masks ("Masks") or NULL; ncc selects the record, the work
+ * buffer's size and the launcher */
 static int affine_normal_eqs(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                              int ny, int nz, const double *A, void *d_record, void *d_work, void *stream,
-                             const float *d_WF, const float *d_WM)
+                             const float *d_WF, const float *d_WM, int ncc)
 {
     if (!d_F || !d_M || !A || !d_record || !d_work)
         return refuse(what, "NULL argument");
@@ -34,19 +49,21 @@ static int affine_normal_eqs(const char *what, const float *d_F, int ox, int oy,
         const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
                                { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
-        const range_t out[] = { { d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES }, { d_work, AFFINE_NORMAL_WORK_BYTES } };
+        const range_t out[] = { { d_record, ncc ? SIFT3D_AMD_AFFINE_NCC_BYTES : SIFT3D_AMD_AFFINE_NORMAL_BYTES },
+                                { d_work, ncc ? AFFINE_NCC_WORK_BYTES : AFFINE_NORMAL_WORK_BYTES } };
         if (ranges_aliased(out, 2, in, 4))
             return refuse(what, ALIASED);
     }
-    return sift3d_affine_normal_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record, d_work, stream, d_WF,
-                                       d_WM);
+    return (ncc ? sift3d_affine_ncc_normal_launch : sift3d_affine_normal_launch)(what, d_F, ox, oy, oz, d_M, nx, ny, nz,
+                                                                                 A, d_record, d_work, stream, d_WF,
+                                                                                 d_WM);
 }
 
 int sift3d_hip_affine_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
                                  const double *A, void *d_record, void *d_work, void *stream)
 {
     return affine_normal_eqs("sift3d_hip_affine_normal_eqs", d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record, d_work,
-                             stream, NULL, NULL);
+                             stream, NULL, NULL, 0);
 }
 
 int sift3d_hip_affine_normal_eqs_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -54,7 +71,15 @@ int sift3d_hip_affine_normal_eqs_masked(const float *d_F, int ox, int oy, int oz
                                         const float *d_WF, const float *d_WM)
 {
     return affine_normal_eqs("sift3d_hip_affine_normal_eqs_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record,
-                             d_work, stream, d_WF, d_WM);
+                             d_work, stream, d_WF, d_WM, 0);
+}
+
+int sift3d_hip_affine_ncc_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                     int nz, const double *A, void *d_record, void *d_work, void *stream,
+                                     const float *d_WF, const float *d_WM)
+{
+    return affine_normal_eqs("sift3d_hip_affine_ncc_normal_eqs", d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record,
+                             d_work, stream, d_WF, d_WM, 1);
 }
 
 /* ---- host arithmetic on a record (the order of every operation is the header's) ---- */
@@ -64,58 +89,157 @@ typedef struct {
     double see, b[12], H[144];
 } affine_record;
 
-int sift3d_amd_affine_lm_step(const void *record, unsigned free_mask, double lambda, double *delta)
+typedef struct {
+    uint64_t n;
+    double S_m, S_f, S_mm, S_fm, S_ff, u[12], v[12], w[12], H[144];
+} affine_ncc_record;
+
+#define LM_MAX 14                                            /* the 12 parameters, and alpha and beta */
+
+/* K x = y for the m x m matrix whose lower triangle is in K (row stride LM_MAX), factored in place: K = C C^T row by
+ * row, then the two triangular solves; x replaces y.  -1 when K is not positive definite (a zero on the
+ * diagonal included) or the solution is not finite. */
+static int cholesky_solve(double *K, int m, double *y)
 {
-    static const char what[] = "sift3d_amd_affine_lm_step";
-    affine_record r;
-    double K[144], y[12];
-    int idx[12], m = 0, i, j, k;
+    int i, j, k;
+    for (i = 0; i < m; i++) {
+        for (j = 0; j <= i; j++) {
+            double s = K[i * LM_MAX + j];
+            for (k = 0; k < j; k++)
+                s -= K[i * LM_MAX + k] * K[j * LM_MAX + k];
+            if (i == j) {
+                if (!(s > 0.0) || !isfinite(s))
+                    return SIFT3D_FAILURE;
+                K[i * LM_MAX + i] = sqrt(s);
+            } else
+                K[i * LM_MAX + j] = s / K[j * LM_MAX + j];
+        }
+    }
+    for (i = 0; i < m; i++) {                                /* C z = y */
+        double s = y[i];
+        for (k = 0; k < i; k++)
+            s -= K[i * LM_MAX + k] * y[k];
+        y[i] = s / K[i * LM_MAX + i];
+    }
+    for (i = m - 1; i >= 0; i--) {                           /* C^T x = z */
+        double s = y[i];
+        for (k = i + 1; k < m; k++)
+            s -= K[k * LM_MAX + i] * y[k];
+        y[i] = s / K[i * LM_MAX + i];
+        if (!isfinite(y[i]))
+            return SIFT3D_FAILURE;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* the checks the two steps share, and the free parameters among the 12 in idx; their number, 0 to refuse */
+static int lm_free_set(const char *what, const void *record, unsigned free_mask, double lambda, double *delta, int *idx)
+{
+    int m = 0, i;
     if (!record || !delta)
-        return refuse(what, "NULL argument");
+        return refuse(what, "NULL argument"), 0;
     if (!isfinite(lambda) || lambda < 0)
-        return refuse(what, "lambda must be finite and not negative");
-    memcpy(&r, record, sizeof(r));
+        return refuse(what, "lambda must be finite and not negative"), 0;
     for (i = 0; i < 12; i++) {
         delta[i] = 0.0;
         if (free_mask & (1u << i))
             idx[m++] = i;
     }
-    if (r.n == 0 || m == 0 || (free_mask & ~0xFFFu))
+    return free_mask & ~0xFFFu ? 0 : m;
+}
+
+int sift3d_amd_affine_lm_step(const void *record, unsigned free_mask, double lambda, double *delta)
+{
+    affine_record r;
+    double K[LM_MAX * LM_MAX], y[LM_MAX];
+    int idx[LM_MAX], i, j;
+    const int m = lm_free_set("sift3d_amd_affine_lm_step", record, free_mask, lambda, delta, idx);
+    if (m == 0)
         return SIFT3D_FAILURE;
-    /* K = H + lambda diag H on the free set, its lower triangle factored in place: K = C C^T, row by row */
-    for (i = 0; i < m; i++)
-        for (j = 0; j <= i; j++) {
-            const double h = r.H[idx[i] * 12 + idx[j]];
-            K[i * 12 + j] = i == j ? h + lambda * h : h;
-        }
+    memcpy(&r, record, sizeof(r));
+    if (r.n == 0)
+        return SIFT3D_FAILURE;
+    /* K = H + lambda diag H on the free set (its lower triangle), K delta = -b */
     for (i = 0; i < m; i++) {
         for (j = 0; j <= i; j++) {
-            double s = K[i * 12 + j];
-            for (k = 0; k < j; k++)
-                s -= K[i * 12 + k] * K[j * 12 + k];
-            if (i == j) {
-                if (!(s > 0.0) || !isfinite(s))
-                    return SIFT3D_FAILURE;                  /* not positive definite (H_ii == 0 included) */
-                K[i * 12 + i] = sqrt(s);
-            } else
-                K[i * 12 + j] = s / K[j * 12 + j];
+            const double h = r.H[idx[i] * 12 + idx[j]];
+            K[i * LM_MAX + j] = i == j ? h + lambda * h : h;
         }
+        y[i] = -r.b[idx[i]];
     }
-    for (i = 0; i < m; i++) {                                /* C y = -b */
-        double s = -r.b[idx[i]];
-        for (k = 0; k < i; k++)
-            s -= K[i * 12 + k] * y[k];
-        y[i] = s / K[i * 12 + i];
-    }
-    for (i = m - 1; i >= 0; i--) {                           /* C^T delta = y */
-        double s = y[i];
-        for (k = i + 1; k < m; k++)
-            s -= K[k * 12 + i] * y[k];
-        y[i] = s / K[i * 12 + i];
-        if (!isfinite(y[i]))
-            return SIFT3D_FAILURE;
-    }
+    if (cholesky_solve(K, m, y))
+        return SIFT3D_FAILURE;
     for (i = 0; i < m; i++)
+        delta[idx[i]] = y[i];
+    return SIFT3D_SUCCESS;
+}
+
+/* out = alpha, beta, cost, ncc of the record's sums, in the header's order of operations; 0 where the fit is undefined
+ * (out is then all NaN) */
+static int ncc_fit(const affine_ncc_record *r, double *out)
+{
+    const double nd = (double)r->n;
+    double vm, vf, c, alpha;
+    out[0] = out[1] = out[2] = out[3] = NAN;
+    if (r->n < 2)
+        return 0;
+    vm = r->S_mm - r->S_m * r->S_m / nd;
+    vf = r->S_ff - r->S_f * r->S_f / nd;
+    c = r->S_fm - r->S_f * r->S_m / nd;
+    if (!(vm > 0))
+        return 0;
+    alpha = c / vm;
+    out[0] = alpha;
+    out[1] = (r->S_f - alpha * r->S_m) / nd;
+    out[2] = (vf - alpha * c) / nd;
+    if (!(out[2] >= 0))
+        out[2] = 0.0;
+    out[3] = vf <= 0 || vm <= 0 ? 0.0 : c / sqrt(vf * vm);
+    return 1;
+}
+
+int sift3d_amd_affine_ncc_fit(const void *record, double *out)
+{
+    affine_ncc_record r;
+    if (!record || !out)
+        return refuse("sift3d_amd_affine_ncc_fit", "NULL argument");
+    memcpy(&r, record, sizeof(r));
+    return ncc_fit(&r, out) ? SIFT3D_SUCCESS : SIFT3D_FAILURE;
+}
+
+int sift3d_amd_affine_ncc_lm_step(const void *record, unsigned free_mask, double lambda, double *delta)
+{
+    affine_ncc_record r;
+    double K[LM_MAX * LM_MAX], y[LM_MAX], fit[4], alpha, beta, nd;
+    int idx[LM_MAX], i, j;
+    int m = lm_free_set("sift3d_amd_affine_ncc_lm_step", record, free_mask, lambda, delta, idx);
+    if (m == 0)
+        return SIFT3D_FAILURE;
+    memcpy(&r, record, sizeof(r));
+    if (!ncc_fit(&r, fit))
+        return SIFT3D_FAILURE;                              /* n < 2 or V_m <= 0 */
+    alpha = fit[0];
+    beta = fit[1];
+    nd = (double)r.n;
+    idx[m++] = 12;                                           /* alpha and beta are always free */
+    idx[m++] = 13;
+    /* K = H14 + lambda diag H14 on the free set (its lower triangle), K delta = -b14 */
+    for (i = 0; i < m; i++) {
+        const int p = idx[i];
+        for (j = 0; j <= i; j++) {
+            const int q = idx[j];                            /* q <= p */
+            const double h = p < 12    ? (alpha * alpha) * r.H[p * 12 + q]
+                             : p == 12 ? (q < 12 ? alpha * r.v[q] : r.S_mm)
+                                       : (q < 12 ? alpha * r.u[q] : q == 12 ? r.S_m : nd);
+            K[i * LM_MAX + j] = i == j ? h + lambda * h : h;
+        }
+        y[i] = -(p < 12    ? alpha * ((alpha * r.v[p] + beta * r.u[p]) - r.w[p])
+                 : p == 12 ? (alpha * r.S_mm + beta * r.S_m) - r.S_fm
+                           : (alpha * r.S_m + beta * nd) - r.S_f);
+    }
+    if (cholesky_solve(K, m, y))
+        return SIFT3D_FAILURE;                              /* alpha == 0 makes it so */
+    for (i = 0; i < m - 2; i++)
         delta[idx[i]] = y[i];
     return SIFT3D_SUCCESS;
 }
@@ -181,13 +305,47 @@ size_t sift3d_amd_affine_refine_struct_bytes(int which)
                         : 0;
 }
 
+/* ---- the two metrics of the driver ---- */
+typedef union {
+    uint64_t n;                                              /* both records begin with the count */
+    affine_record msd;
+    affine_ncc_record ncc;
+} affine_eval;
+
+static double msd_cost(const affine_eval *e)
+{
+    return e->n ? e->msd.see / (double)e->n : NAN;
+}
+
+static double ncc_cost(const affine_eval *e)
+{
+    double fit[4];
+    ncc_fit(&e->ncc, fit);
+    return fit[2];                                           /* NaN where the fit is undefined */
+}
+
+typedef struct {
+    int ncc;                                                 /* which pass affine_normal_eqs launches */
+    size_t record_bytes, normal_work_bytes;
+    double (*cost)(const affine_eval *);                     /* what a step must lower; NaN: never accepted */
+    int (*step)(const void *record, unsigned free_mask, double lambda, double *delta);
+} affine_metric;
+
+static const affine_metric METRIC_MSD = { 0, SIFT3D_AMD_AFFINE_NORMAL_BYTES, AFFINE_NORMAL_WORK_BYTES, msd_cost,
+                                          sift3d_amd_affine_lm_step };
+static const affine_metric METRIC_NCC = { 1, SIFT3D_AMD_AFFINE_NCC_BYTES, AFFINE_NCC_WORK_BYTES, ncc_cost,
+                                          sift3d_amd_affine_ncc_lm_step };
+
 /* d_work, in bytes: the normal equations' partial slots, the record, then per level l = 1 .. levels-1 the restricted
  * fixed and moving volumes, each rounded up to a multiple of 16 bytes */
-#define AFFINE_RECORD_PAD ((size_t)(SIFT3D_AMD_AFFINE_NORMAL_BYTES + 15) / 16 * 16)
-
-size_t sift3d_amd_affine_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+static size_t affine_record_pad(const affine_metric *mt)
 {
-    size_t total = AFFINE_NORMAL_WORK_BYTES + AFFINE_RECORD_PAD;
+    return (mt->record_bytes + 15) / 16 * 16;
+}
+
+static size_t affine_work_bytes(const affine_metric *mt, int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    size_t total = mt->normal_work_bytes + affine_record_pad(mt);
     int l;
     if (ox <= 0 || oy <= 0 || oz <= 0 || nx <= 0 || ny <= 0 || nz <= 0 || levels < 1 ||
         levels > SIFT3D_AMD_DEMONS_MAX_LEVELS)
@@ -198,6 +356,11 @@ size_t sift3d_amd_affine_refine_work_bytes(int ox, int oy, int oz, int nx, int n
         total += pad4(grid_voxels(ox, oy, oz)) * sizeof(float) + pad4(grid_voxels(nx, ny, nz)) * sizeof(float);
     }
     return total;
+}
+
+size_t sift3d_amd_affine_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    return affine_work_bytes(&METRIC_MSD, ox, oy, oz, nx, ny, nz, levels);
 }
 
 /* ---- the mask pyramid of the two masked drivers (this one and sift3d_ffd.c's): the layout rule, stated once ----
@@ -241,11 +404,22 @@ static int mask_pyramid_level(const float *fWF, int fox, int foy, int foz, const
     return SIFT3D_SUCCESS;
 }
 
-/* the masked driver's: the same, and the mask pyramid */
+/* the drivers that take masks: the same, and the mask pyramid */
+static size_t affine_masked_work_bytes(const affine_metric *mt, int ox, int oy, int oz, int nx, int ny, int nz,
+                                       int levels)
+{
+    const size_t plain = affine_work_bytes(mt, ox, oy, oz, nx, ny, nz, levels);
+    return plain ? plain + mask_pyramid_bytes(ox, oy, oz, nx, ny, nz, levels) : 0;
+}
+
 size_t sift3d_amd_affine_refine_masked_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
 {
-    const size_t plain = sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz, levels);
-    return plain ? plain + mask_pyramid_bytes(ox, oy, oz, nx, ny, nz, levels) : 0;
+    return affine_masked_work_bytes(&METRIC_MSD, ox, oy, oz, nx, ny, nz, levels);
+}
+
+size_t sift3d_amd_affine_ncc_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    return affine_masked_work_bytes(&METRIC_NCC, ox, oy, oz, nx, ny, nz, levels);
 }
 
 /* the largest distance by which the maps A and B move a corner of the grid apart */
@@ -274,45 +448,46 @@ typedef struct {
     const float *WF, *WM;                                    /* the level's masks, or NULL */
 } affine_level;
 
-/* one evaluation at A on `lv`: the pass, the record's copy to the host and the wait for it */
-static int affine_evaluate(const affine_level *lv, const double *A, void *d_record, void *d_work, void *stream,
-                           affine_record *rec)
+/* one evaluation at A on `lv`: the metric's pass, the record's copy to the host and the wait for it */
+static int affine_evaluate(const affine_metric *mt, const affine_level *lv, const double *A, void *d_record,
+                           void *d_work, void *stream, affine_eval *rec)
 {
-    return (lv->WF || lv->WM
-                ? sift3d_hip_affine_normal_eqs_masked(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A,
-                                                      d_record, d_work, stream, lv->WF, lv->WM)
-                : sift3d_hip_affine_normal_eqs(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A,
-                                               d_record, d_work, stream)) ||
-           sift3d_hip_memcpy_d2h(rec, d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES, stream) ||
-           sift3d_hip_stream_sync(stream);
+    const char *what = mt->ncc               ? "sift3d_hip_affine_ncc_normal_eqs"
+                       : lv->WF || lv->WM ? "sift3d_hip_affine_normal_eqs_masked"
+                                          : "sift3d_hip_affine_normal_eqs";
+    return affine_normal_eqs(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, d_record, d_work,
+                             stream, lv->WF, lv->WM, mt->ncc) ||
+           sift3d_hip_memcpy_d2h(rec, d_record, mt->record_bytes, stream) || sift3d_hip_stream_sync(stream);
 }
 
-static void affine_trail(sift3d_amd_affine_refine_result *res, const affine_record *rec, double lambda, int accepted,
+static void affine_trail(sift3d_amd_affine_refine_result *res, uint64_t n, double cost, double lambda, int accepted,
                          int level)
 {
     sift3d_amd_affine_evaluation *e = res->trail + res->evaluations++;
-    e->msd = rec->n ? rec->see / (double)rec->n : NAN;
-    e->n = rec->n;
+    e->msd = cost;
+    e->n = n;
     e->lambda = lambda;
     e->accepted = accepted;
     e->level = level;
 }
 
-/* the shared body of the two drivers: `masked` selects the work buffer's size; the masks may still be NULL */
-static int affine_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
-                         int nz, double *A_io, const sift3d_amd_affine_refine_params *params,
-                         sift3d_amd_affine_refine_result *result, void *d_work, void *stream, int masked,
-                         const float *d_WF, const float *d_WM)
+/* the shared body of the three drivers: `masked` selects the work buffer's size; the masks may still be NULL.  fit_out
+ * (NCC; else NULL): the fit at the final A on level 0, NaN where it is undefined or no evaluation was made. */
+static int affine_refine(const affine_metric *mt, const char *what, const float *d_F, int ox, int oy, int oz,
+                         const float *d_M, int nx, int ny, int nz, double *A_io,
+                         const sift3d_amd_affine_refine_params *params, sift3d_amd_affine_refine_result *result,
+                         double *fit_out, void *d_work, void *stream, int masked, const float *d_WF,
+                         const float *d_WM)
 {
     sift3d_amd_affine_refine_params prm;
     affine_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
-    affine_record rec, trial;
-    double A[12], At[12], delta[12];
+    affine_eval rec, trial;
+    double A[12], At[12], delta[12], cost, cost_t;
     char *w = (char *)d_work;
     void *d_record;
     size_t off;
     int l, i;
-    if (!d_F || !d_M || !A_io || !result || !d_work)
+    if (!d_F || !d_M || !A_io || !result || !d_work || (mt->ncc && !fit_out))
         return refuse(what, "NULL argument");
     if (params)
         prm = *params;
@@ -328,18 +503,19 @@ static int affine_refine(const char *what, const float *d_F, int ox, int oy, int
         const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
                                { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
-        const range_t out[] = { { d_work, masked ? sift3d_amd_affine_refine_masked_work_bytes(ox, oy, oz, nx, ny, nz,
-                                                                                              prm.levels)
-                                                 : sift3d_amd_affine_refine_work_bytes(ox, oy, oz, nx, ny, nz,
-                                                                                       prm.levels) } };
+        size_t (*const bytes_of)(const affine_metric *, int, int, int, int, int, int, int) =
+            masked ? affine_masked_work_bytes : affine_work_bytes;
+        const range_t out[] = { { d_work, bytes_of(mt, ox, oy, oz, nx, ny, nz, prm.levels) } };
         if (ranges_aliased(out, 1, in, 4))
             return refuse(what, ALIASED);
     }
     result->evaluations = 0;
     result->stop = SIFT3D_AMD_AFFINE_STOP_EVALUATIONS;
     memcpy(result->A, A_io, sizeof(result->A));
-    d_record = w + AFFINE_NORMAL_WORK_BYTES;
-    off = AFFINE_NORMAL_WORK_BYTES + AFFINE_RECORD_PAD;
+    if (fit_out)
+        fit_out[0] = fit_out[1] = fit_out[2] = fit_out[3] = NAN;
+    d_record = w + mt->normal_work_bytes;
+    off = mt->normal_work_bytes + affine_record_pad(mt);
     lv[0] = (affine_level){ d_F, d_M, ox, oy, oz, nx, ny, nz, d_WF, d_WM };
     memcpy(A, A_io, sizeof(A));
     for (l = 1; l < prm.levels; l++) {                       /* level l from level l - 1; A's shift halves */
@@ -366,9 +542,10 @@ static int affine_refine(const char *what, const float *d_F, int ox, int oy, int
         double lambda = prm.lambda0;
         uint64_t n_first;
         int evals = 1, stop;
-        if (affine_evaluate(v, A, d_record, w, stream, &rec))
+        if (affine_evaluate(mt, v, A, d_record, w, stream, &rec))
             return SIFT3D_FAILURE;
-        affine_trail(result, &rec, lambda, 1, l);
+        cost = mt->cost(&rec);
+        affine_trail(result, rec.n, cost, lambda, 1, l);
         n_first = rec.n;
         for (;;) {
             int accept;
@@ -376,21 +553,22 @@ static int affine_refine(const char *what, const float *d_F, int ox, int oy, int
                 stop = SIFT3D_AMD_AFFINE_STOP_EVALUATIONS;
                 break;
             }
-            if (sift3d_amd_affine_lm_step(&rec, prm.free_mask, lambda, delta) ||
+            if (mt->step(&rec, prm.free_mask, lambda, delta) ||
                 sift3d_amd_affine_apply_delta(A, delta, v->ox, v->oy, v->oz, At) || check_affine(what, At)) {
                 stop = SIFT3D_AMD_AFFINE_STOP_LM_FAILED;
                 break;
             }
-            if (affine_evaluate(v, At, d_record, w, stream, &trial))
+            if (affine_evaluate(mt, v, At, d_record, w, stream, &trial))
                 return SIFT3D_FAILURE;
             evals++;
-            accept = trial.n > 0 && (double)trial.n >= prm.min_overlap * (double)n_first &&
-                     trial.see / (double)trial.n < rec.see / (double)rec.n;
-            affine_trail(result, &trial, lambda, accept, l);
+            cost_t = mt->cost(&trial);
+            accept = trial.n > 0 && (double)trial.n >= prm.min_overlap * (double)n_first && cost_t < cost;
+            affine_trail(result, trial.n, cost_t, lambda, accept, l);
             if (accept) {
                 const double move = affine_corner_move(A, At, v->ox, v->oy, v->oz);
                 memcpy(A, At, sizeof(A));
                 rec = trial;
+                cost = cost_t;
                 lambda = lambda / prm.lambda_factor;
                 if (lambda < prm.lambda_min)
                     lambda = prm.lambda_min;
@@ -413,6 +591,8 @@ static int affine_refine(const char *what, const float *d_F, int ox, int oy, int
     }
     memcpy(A_io, A, sizeof(A));
     memcpy(result->A, A, sizeof(A));
+    if (fit_out)
+        ncc_fit(&rec.ncc, fit_out);                          /* level 0's last accepted evaluation: the record at A */
     return SIFT3D_SUCCESS;
 }
 
@@ -420,8 +600,8 @@ int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, co
                                     double *A_io, const sift3d_amd_affine_refine_params *params,
                                     sift3d_amd_affine_refine_result *result, void *d_work, void *stream)
 {
-    return affine_refine("sift3d_amd_affine_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params, result,
-                         d_work, stream, 0, NULL, NULL);
+    return affine_refine(&METRIC_MSD, "sift3d_amd_affine_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params,
+                         result, NULL, d_work, stream, 0, NULL, NULL);
 }
 
 int sift3d_amd_affine_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -429,6 +609,15 @@ int sift3d_amd_affine_refine_masked_device(const float *d_F, int ox, int oy, int
                                            sift3d_amd_affine_refine_result *result, void *d_work, void *stream,
                                            const float *d_WF, const float *d_WM)
 {
-    return affine_refine("sift3d_amd_affine_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params,
-                         result, d_work, stream, 1, d_WF, d_WM);
+    return affine_refine(&METRIC_MSD, "sift3d_amd_affine_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io,
+                         params, result, NULL, d_work, stream, 1, d_WF, d_WM);
+}
+
+int sift3d_amd_affine_ncc_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                        int nz, double *A_io, const sift3d_amd_affine_refine_params *params,
+                                        sift3d_amd_affine_refine_result *result, double *fit_out, void *d_work,
+                                        void *stream, const float *d_WF, const float *d_WM)
+{
+    return affine_refine(&METRIC_NCC, "sift3d_amd_affine_ncc_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io,
+                         params, result, fit_out, d_work, stream, 1, d_WF, d_WM);
 }

@@ -22,6 +22,9 @@
 //     LDS as ((w0 + w1) + w2) + w3 into partial slot blockIdx.x, then one finish workgroup per statistic adds the
 //     slots in finish_reduce's fixed order and writes every entry of the record that holds its value: H comes out
 //     full and symmetric bit for bit.
+//
+// k_affine_ncc_normal (below) is the same pass for the fit under a linear intensity map (header, "Affine refinement
+// under a linear intensity map (NCC)"): 101 double sums and the count, in two launches of 73 and 28 sums.
 #include "sift3d_resample.h"
 
 namespace {
@@ -212,6 +215,22 @@ __global__ __launch_bounds__(256, 2) void k_affine_normal(const AffArgs s)
     }
 }
 
+// every entry of the full H[12][12] that holds the distinct value st = 10 * pair3(d, e) + pair4(j, k)
+__device__ void scatter_h(double *H, int st, double v)
+{
+    for (int d = 0; d < 3; d++)
+        for (int e = d; e < 3; e++)
+            for (int j = 0; j < 4; j++)
+                for (int k = j; k < 4; k++) {
+                    if (10 * pair3(d, e) + pair4(j, k) != st)
+                        continue;
+                    H[(4 * d + j) * 12 + 4 * e + k] = v;
+                    H[(4 * d + k) * 12 + 4 * e + j] = v;
+                    H[(4 * e + j) * 12 + 4 * d + k] = v;
+                    H[(4 * e + k) * 12 + 4 * d + j] = v;
+                }
+}
+
 // Workgroup s adds the partial slots 0 .. n-1 of statistic s in a fixed order (finish_reduce) and writes every entry
 // of the record {uint64 n; double S_ee; double b[12]; double H[12][12]} that holds it.
 __global__ __launch_bounds__(256) void k_affine_normal_finish(const double *part, unsigned n, double *rec)
@@ -235,18 +254,270 @@ __global__ __launch_bounds__(256) void k_affine_normal_finish(const double *part
     } else if (st >= AFF_H) {
         b[st - AFF_H] = v;
     } else {
-        for (int d = 0; d < 3; d++)
-            for (int e = d; e < 3; e++)
-                for (int j = 0; j < 4; j++)
-                    for (int k = j; k < 4; k++) {
-                        if (10 * pair3(d, e) + pair4(j, k) != st)
-                            continue;
-                        H[(4 * d + j) * 12 + 4 * e + k] = v;
-                        H[(4 * d + k) * 12 + 4 * e + j] = v;
-                        H[(4 * e + j) * 12 + 4 * d + k] = v;
-                        H[(4 * e + k) * 12 + 4 * d + j] = v;
-                    }
+        scatter_h(H, st, v);
     }
+}
+
+// ---- the fit under a linear intensity map (NCC) ----------------------------------------------------------------------
+// Statistic s: H as above (0 .. 59), then v = sum J m (60 + 4 d + j), u = sum J (72 + ..), w = sum J f (84 + ..), the
+// moments S_m, S_f, S_mm, S_fm, S_ff (96 .. 100) and the count (101).
+constexpr int NCC_V = AFF_H, NCC_U = NCC_V + 12, NCC_W = NCC_U + 12, NCC_MOM = NCC_W + 12;
+constexpr int NCC_SUMS = NCC_MOM + 5;            // doubles
+constexpr int NCC_STATS = NCC_SUMS + 1;          // and the count
+
+// The record is summed by two kernels: PART 1 holds H, v, S_mm and the count (k_affine_normal's 72 + 1 sums with m in
+// the place of E), PART 2 the other 28 (u, w, S_m, S_f, S_fm, S_ff).  PART 0 is the whole record in one kernel, built with
+// -DSIFT3D_AFFINE_NCC_ONE_KERNEL and kept for profiles/microbench/affine_refine_rate.py.  A statistic's chain of
+// additions is the same in either, so the two builds write the same bytes.
+__host__ __device__ constexpr bool ncc_in_part(int part, int st)
+{
+    return part == 0 || (part == 1) == (st < NCC_U || st == NCC_MOM + 2 || st == NCC_SUMS);
+}
+
+// One tile's samples for a lane: its four outputs' f, m and gradient, and whether each is counted (live, inside the
+// moving grid and, MASKED, in both masks).
+struct TileSamples {
+    float f[4], m[4], gx[4], gy[4], gz[4];
+    bool counted[4];
+};
+
+template <int LINEAR, bool MASKED>
+__device__ __forceinline__ void tile_samples(const AffArgs &s, int xt, int y, int z, int lx, TileSamples &t)
+{
+    const GridArgs &p = s.g;
+    const bool row = y < p.oy && z < p.oz;
+    const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+    const double yd = (double)y, zd = (double)z;
+    const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
+    // MASKED: the two mask values of the lane's four outputs first, all eight loads in flight together, kept as
+    // four flags.  The accumulators leave no registers to hold them across the intensity gathers (it spills);
+    // the stage costs one more round trip per tile (measured: DESIGN.md 3.4.10).  q is pull()'s three
+    // multiply-adds per output, computed here and again in the taps loop rather than kept in 24 registers.
+    bool ok[4] = {true, true, true, true};
+    if (MASKED) {
+        float wf[4], wm[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            const double xd = (double)x;
+            const double qx = pull(s.a, xd, rx), qy = pull(s.a + 4, xd, ry), qz = pull(s.a + 8, xd, rz);
+            wf[k] = s.w.wf && row && x < p.ox ? s.w.wf[orow + (size_t)x] : 1.0f;
+            wm[k] = s.w.wm ? s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)] : 1.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            ok[k] = mask_in(wf[k]) && mask_in(wm[k]);
+    }
+    Taps tp[4];
+    bool live[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x = xt + lx + 16 * k;
+        live[k] = row && x < p.ox;
+        t.f[k] = live[k] ? s.F[orow + (size_t)x] : 0.0f;
+        const double xd = (double)x;
+        tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry), pull(s.a + 8, xd, rz));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        t.m[k] = gather_grad<LINEAR>(p.src, tp[k], &t.gx[k], &t.gy[k], &t.gz[k]);
+        t.counted[k] = MASKED ? live[k] && tp[k].in && ok[k] : live[k] && tp[k].in;
+    }
+}
+
+// The per-tile factoring of k_affine_normal, operation for operation.  A voxel adds w, w X (and, for H, (w X) X) into
+// the tile's sums,
+__device__ __forceinline__ void tile_add(double w, double X, double &s0, double &s1)
+{
+    s0 += w;
+    s1 += w * X;
+}
+
+__device__ __forceinline__ void tile_add(double w, double X, double &s0, double &s1, double &s2)
+{
+    const double wx = w * X;
+    s0 += w;
+    s1 += wx;
+    s2 += wx * X;
+}
+
+// once per tile the sums of a pair G_d G_e fold into its ten accumulators (P_j P_k, j <= k),
+__device__ __forceinline__ void fold_pair(double *h, double s0, double s1, double s2, double Y, double Z, double YY,
+                                          double YZ, double ZZ)
+{
+    h[0] += s2;                                                          // X X
+    h[1] += s1 * Y;                                                      // X Y
+    h[2] += s1 * Z;                                                      // X Z
+    h[3] += s1;                                                          // X 1
+    h[4] += s0 * YY;
+    h[5] += s0 * YZ;
+    h[6] += s0 * Y;
+    h[7] += s0 * ZZ;
+    h[8] += s0 * Z;
+    h[9] += s0;
+}
+
+// and those of a quantity with one factor J (G_d, G_d m, G_d f) into its four (P_j).
+__device__ __forceinline__ void fold_row(double *b, double s0, double s1, double Y, double Z)
+{
+    b[0] += s1;
+    b[1] += s0 * Y;
+    b[2] += s0 * Z;
+    b[3] += s0;
+}
+
+// a lane's value summed over its wave by butterfly (s = 32 .. 1)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1)
+        v += __shfl_xor(v, sft);
+    return v;
+}
+
+// The register budget decides the split.  The 96 accumulators and the 5 moments are 202 VGPRs and a tile's 36 sums 72
+// more, past the 256 that two waves per SIMD leave a lane.  As reported by -Rpass-analysis=kernel-resource-usage:
+//   PART 0, (256, 1): 256 VGPRs + 62 - 83 AGPRs, one wave per SIMD, no scratch (at (256, 2) it spills over a hundred
+//                     VGPRs): half the waves are left to hide the gather's latency;
+//   PART 1, (256, 2): 245 - 249 VGPRs, no AGPRs, two waves per SIMD, no scratch;
+//   PART 2, (256, 2): 143 - 160 VGPRs, no AGPRs, three waves per SIMD, no scratch (bounded to four waves, 128 VGPRs, it
+//                     spills 7 - 33 of them; not measured).
+// Measured (profiles/microbench/affine_ncc_rate_mi355x.txt, 512^3, all in one run): k_affine_normal's pass 0.885 ms,
+// the one kernel 2.790 ms (3.15 x), the two kernels together 1.722 ms (1.95 x): one wave per SIMD costs more than a
+// second gather of the volumes does, so the two kernels are the default.
+// k_affine_normal's own body is kept as it was rather than restated on the helpers above: its allocation sits at the
+// 256-VGPR limit, and with tile_add / fold_pair alone in it the compiler spills 8 - 24 VGPRs.
+// The sums of H are k_affine_normal's operation for operation, so H is that kernel's bit for bit.  A voxel that is not
+// counted enters with G = 0, m = 0 and f = 0.  MASKED: as k_affine_normal's.
+template <int LINEAR, bool MASKED, int PART>
+__global__ __launch_bounds__(256, PART == 0 ? 1 : 2) void k_affine_ncc_normal(const AffArgs s)
+{
+    constexpr bool HV = PART != 2, UW = PART != 1;
+    __shared__ double slot[NCC_SUMS * 4];
+    __shared__ unsigned long long cslot[4];
+    const GridArgs &p = s.g;
+    const int lx = threadIdx.x & 15;
+    unsigned long long cnt = 0;
+    double acc[NCC_SUMS];                                                    // the part's own are live, the rest go
+#pragma unroll
+    for (int i = 0; i < NCC_SUMS; i++)
+        acc[i] = 0.0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            break;
+        TileSamples t;
+        tile_samples<LINEAR, MASKED>(s, xt, y, z, lx, t);
+        // tile sums: 0 .. 5 the pairs G_d G_e, 6 + d: G_d m, 9 + d: G_d, 12 + d: G_d f
+        double s0[15], s1[15], s2[6];
+#pragma unroll
+        for (int i = 0; i < 15; i++)
+            s0[i] = s1[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+            s2[i] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool counted = t.counted[k];
+            const double m = counted ? (double)t.m[k] : 0.0, f = counted ? (double)t.f[k] : 0.0;
+            const double G[3] = {counted ? (double)t.gx[k] : 0.0, counted ? (double)t.gy[k] : 0.0,
+                                 counted ? (double)t.gz[k] : 0.0};
+            const double X = (double)(xt + lx + 16 * k) - s.cx;
+            cnt += counted ? 1u : 0u;
+            acc[NCC_MOM + 0] += m;
+            acc[NCC_MOM + 1] += f;
+            acc[NCC_MOM + 2] += m * m;                                       // exact: two floats
+            acc[NCC_MOM + 3] += f * m;
+            acc[NCC_MOM + 4] += f * f;
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                if (HV) {
+#pragma unroll
+                    for (int e2 = d; e2 < 3; e2++) {
+                        const int i = pair3(d, e2);
+                        tile_add(G[d] * G[e2], X, s0[i], s1[i], s2[i]);
+                    }
+                    tile_add(G[d] * m, X, s0[6 + d], s1[6 + d]);
+                }
+                if (UW) {
+                    tile_add(G[d], X, s0[9 + d], s1[9 + d]);
+                    tile_add(G[d] * f, X, s0[12 + d], s1[12 + d]);
+                }
+            }
+        }
+        const double Y = (double)y - s.cy, Z = (double)z - s.cz;
+        if (HV) {
+            const double YY = Y * Y, YZ = Y * Z, ZZ = Z * Z;
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+                fold_pair(acc + 10 * i, s0[i], s1[i], s2[i], Y, Z, YY, YZ, ZZ);
+#pragma unroll
+            for (int d = 0; d < 3; d++)
+                fold_row(acc + NCC_V + 4 * d, s0[6 + d], s1[6 + d], Y, Z);
+        }
+        if (UW) {
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                fold_row(acc + NCC_U + 4 * d, s0[9 + d], s1[9 + d], Y, Z);
+                fold_row(acc + NCC_W + 4 * d, s0[12 + d], s1[12 + d], Y, Z);
+            }
+        }
+    }
+    // as k_affine_normal: the wave by butterfly, then the four waves' values through LDS as ((w0 + w1) + w2) + w3
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int i = 0; i < NCC_SUMS; i++) {
+        if (!ncc_in_part(PART, i))
+            continue;
+        const double v = wave_sum(acc[i]);
+        if (lead)
+            slot[4 * i + wave] = v;
+    }
+    cnt = wave_sum(cnt);
+    if (lead)
+        cslot[wave] = cnt;
+    __syncthreads();
+    if (!ncc_in_part(PART, (int)threadIdx.x))
+        return;
+    if (threadIdx.x < NCC_SUMS) {
+        const double *v = slot + 4 * threadIdx.x;
+        s.part[(size_t)threadIdx.x * AFF_GRID + blockIdx.x] = ((v[0] + v[1]) + v[2]) + v[3];
+    } else if (threadIdx.x == NCC_SUMS) {
+        reinterpret_cast<unsigned long long *>(s.part)[(size_t)NCC_SUMS * AFF_GRID + blockIdx.x] =
+            ((cslot[0] + cslot[1]) + cslot[2]) + cslot[3];
+    }
+}
+
+// Workgroup s adds the partial slots 0 .. n-1 of statistic s in a fixed order (finish_reduce) and writes every entry
+// of the record {uint64 n; double S_m, S_f, S_mm, S_fm, S_ff, u[12], v[12], w[12], H[12][12]} that holds it.
+__global__ __launch_bounds__(256) void k_affine_ncc_finish(const double *part, unsigned n, double *rec)
+{
+    __shared__ double s_sum[256];
+    __shared__ unsigned long long s_cnt[256];
+    const int st = blockIdx.x;
+    if (st == NCC_SUMS) {
+        const unsigned long long c =
+            finish_reduce<Add>(reinterpret_cast<const unsigned long long *>(part) + (size_t)st * AFF_GRID, n, s_cnt);
+        if (threadIdx.x == 0)
+            reinterpret_cast<unsigned long long *>(rec)[0] = c;
+        return;
+    }
+    const double v = finish_reduce<Add>(part + (size_t)st * AFF_GRID, n, s_sum);
+    if (threadIdx.x != 0)
+        return;
+    double *mom = rec + 1, *u = mom + 5, *vv = u + 12, *w = vv + 12, *H = w + 12;
+    if (st >= NCC_MOM)
+        mom[st - NCC_MOM] = v;
+    else if (st >= NCC_W)
+        w[st - NCC_W] = v;
+    else if (st >= NCC_U)
+        u[st - NCC_U] = v;
+    else if (st >= NCC_V)
+        vv[st - NCC_V] = v;
+    else
+        scatter_h(H, st, v);
 }
 
 } // namespace
@@ -276,6 +547,51 @@ extern "C" int sift3d_affine_normal_launch(const char *fn, const float *d_F, int
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, s);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_affine_normal_finish, dim3(AFF_STATS), dim3(256), 0, st, (const double *)d_work, grid,
+                       (double *)d_record);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+// one launch of k_affine_ncc_normal<., ., PART>
+template <int PART>
+static int ncc_pass(const AffArgs &s, unsigned grid, hipStream_t st)
+{
+    const bool masked = s.w.wf || s.w.wm, linear = s.g.nx >= 2;
+    void (*k)(const AffArgs) =
+        masked ? (linear ? k_affine_ncc_normal<2, true, PART> : k_affine_ncc_normal<1, true, PART>)
+               : (linear ? k_affine_ncc_normal<2, false, PART> : k_affine_ncc_normal<1, false, PART>);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, s);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+// The same for sift3d_hip_affine_ncc_normal_eqs: d_record is the NCC record, d_work NCC_STATS rows of partial slots.
+extern "C" int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
+                                               const float *d_M, int nx, int ny, int nz, const double *A,
+                                               void *d_record, void *d_work, void *stream, const float *d_WF,
+                                               const float *d_WM)
+{
+    AffArgs s;
+    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+        return launch_fail(fn, "grid too large");
+    for (int i = 0; i < 12; i++)
+        s.a[i] = A[i];
+    s.cx = (double)(ox - 1) / 2.0;
+    s.cy = (double)(oy - 1) / 2.0;
+    s.cz = (double)(oz - 1) / 2.0;
+    s.F = d_F;
+    s.part = (double *)d_work;
+    s.w = MaskArgs{d_WF, d_WM};
+    const unsigned grid = s.g.ntiles < AFF_GRID ? s.g.ntiles : AFF_GRID;
+    hipStream_t st = (hipStream_t)stream;
+#ifndef SIFT3D_AFFINE_NCC_ONE_KERNEL
+    if (ncc_pass<1>(s, grid, st) || ncc_pass<2>(s, grid, st))
+        return SIFT3D_FAILURE;
+#else
+    if (ncc_pass<0>(s, grid, st))
+        return SIFT3D_FAILURE;
+#endif
+    hipLaunchKernelGGL(k_affine_ncc_finish, dim3(NCC_STATS), dim3(256), 0, st, (const double *)d_work, grid,
                        (double *)d_record);
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;

@@ -60,6 +60,7 @@ class AffineEvaluation(C.Structure):                       # sift3d_amd_affine_e
 AFFINE_MAX_EVALUATIONS = 128                               # checked against the library when it is bound (lib())
 AFFINE_MAX_LEVELS = 6
 AFFINE_NORMAL_BYTES = 1264
+AFFINE_NCC_BYTES = 1488
 
 
 class AffineRefineResult(C.Structure):                     # sift3d_amd_affine_refine_result
@@ -200,6 +201,17 @@ def lib():
         "sift3d_amd_affine_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                                       C.POINTER(C.c_double), C.POINTER(AffineRefineParams),
                                                       C.POINTER(AffineRefineResult), vp, vp]),
+        "sift3d_amd_affine_ncc_normal_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_affine_ncc_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                       C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
+        "sift3d_amd_affine_ncc_fit": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sift3d_amd_affine_ncc_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, C.POINTER(C.c_double)]),
+        "sift3d_amd_affine_ncc_refine_work_bytes": (C.c_size_t, [C.c_int] * 7),
+        "sift3d_amd_affine_ncc_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                          C.c_int, C.POINTER(C.c_double),
+                                                          C.POINTER(AffineRefineParams),
+                                                          C.POINTER(AffineRefineResult), C.POINTER(C.c_double), vp,
+                                                          vp, vp, vp]),
         "sift3d_amd_ffd_lattice_dim": (C.c_int, [C.c_int, C.c_int]),
         "sift3d_amd_ffd_weights": (C.c_int, [C.c_int, vp]),
         "sift3d_amd_ffd_field_work_bytes": (C.c_size_t, [C.c_int] * 3),
@@ -266,6 +278,12 @@ def lib():
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the affine refinement layouts as %s, the library has %s"
                            % (want, got))
+    # the NCC record's size: the one-level driver's work buffer is the partial slots and the record (a multiple of 16)
+    got = (L.sift3d_amd_affine_ncc_refine_work_bytes(1, 1, 1, 1, 1, 1, 1)
+           - L.sift3d_amd_affine_ncc_normal_work_bytes(1, 1, 1))
+    if got != AFFINE_NCC_BYTES:
+        raise RuntimeError("sift3d_amd.hip restates the NCC affine record as %d bytes, the library has %d"
+                           % (AFFINE_NCC_BYTES, got))
     want = (C.sizeof(FFDRefineParams), C.sizeof(FFDEvaluation), C.sizeof(FFDRefineResult), FFD_RECORD_HEAD_BYTES,
             FFD_MAX_EVALUATIONS, AFFINE_MAX_LEVELS, FFD_MAX_SPACING)
     got = tuple(L.sift3d_amd_ffd_refine_struct_bytes(k) for k in range(7))
@@ -810,6 +828,105 @@ def affine_refine(F, M, A, params=None, work=None, mask_fixed=None, mask_moving=
                                                      C.byref(p), C.byref(res), work.data_ptr(), current_stream()),
                "sift3d_amd_affine_refine_device")
     return res
+
+
+# ---- affine refinement under a linear intensity map (contract: "Affine refinement under a linear intensity map (NCC)")
+AFFINE_NCC_RECORD_DTYPE = np.dtype([("n", "u8"), ("S_m", "f8"), ("S_f", "f8"), ("S_mm", "f8"), ("S_fm", "f8"),
+                                    ("S_ff", "f8"), ("u", "f8", (12,)), ("v", "f8", (12,)), ("w", "f8", (12,)),
+                                    ("H", "f8", (12, 12))])
+assert AFFINE_NCC_RECORD_DTYPE.itemsize == AFFINE_NCC_BYTES
+
+
+def affine_ncc_normal_work_bytes(fixed_shape=(1, 1, 1)):
+    """sift3d_amd_affine_ncc_normal_work_bytes for a fixed grid (oz, oy, ox)"""
+    oz, oy, ox = (int(v) for v in fixed_shape)
+    return lib().sift3d_amd_affine_ncc_normal_work_bytes(ox, oy, oz)
+
+
+def affine_ncc_record(record):
+    """The record of affine_ncc_normal_equations() on the host, waiting for the stream: a numpy record of
+    AFFINE_NCC_RECORD_DTYPE (n, S_m, S_f, S_mm, S_fm, S_ff, u, v, w [12], H [12, 12])."""
+    import torch
+    return record.view(torch.uint8)[:AFFINE_NCC_BYTES].cpu().numpy().view(AFFINE_NCC_RECORD_DTYPE)[0].copy()
+
+
+def affine_ncc_normal_equations(F, M, A, record=None, work=None, raw=False, mask_fixed=None, mask_moving=None):
+    """The sums of the Gauss-Newton normal equations of sum (alpha m + beta - f)^2 over A's 12 parameters and the
+    linear intensity map (alpha, beta), of the fixed volume F [oz, oy, ox] and the moving volume M [nz, ny, nx] seen
+    through the 3 x 4 pull map A (sift3d_hip_affine_ncc_normal_eqs), torch CUDA float32 contiguous, on torch's current
+    stream.  Returns the record on the host as affine_ncc_record does (which waits for the stream), or with raw=True
+    the device record.  record, work: the caller's buffers (int64 [186]; sift3d_amd_affine_ncc_normal_work_bytes
+    bytes).  mask_fixed, mask_moving: as similarity's."""
+    import torch
+    what = "affine_ncc_normal_equations"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    a = _affine12(A, what)
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    if record is None:
+        record = torch.empty(AFFINE_NCC_BYTES // 8, dtype=torch.int64, device=F.device)
+    _tensor(record, what + ": record must be a contiguous int64 CUDA tensor [186] on F's device",
+            shape=(AFFINE_NCC_BYTES // 8,), device=F.device, dtype="int64")
+    need = lib().sift3d_amd_affine_ncc_normal_work_bytes(ox, oy, oz)
+    work = _work(work, (need + 3) // 4, F, what)
+    _check(lib().sift3d_hip_affine_ncc_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                                  record.data_ptr(), work.data_ptr(), current_stream(), *masks),
+           "sift3d_hip_affine_ncc_normal_eqs")
+    return record if raw else affine_ncc_record(record)
+
+
+def _ncc_record(rec):
+    """a host record (AFFINE_NCC_RECORD_DTYPE, or a mapping / object with its fields) as a 1-element array"""
+    out = np.zeros(1, AFFINE_NCC_RECORD_DTYPE)
+    for name in AFFINE_NCC_RECORD_DTYPE.names:
+        out[name] = rec[name] if isinstance(rec, (dict, np.void, np.ndarray)) else getattr(rec, name)
+    return out
+
+
+def affine_ncc_fit(rec):
+    """(alpha, beta, cost, ncc) of sift3d_amd_affine_ncc_fit (host) on a record: the regression of f on m, its mean
+    squared residual and the correlation; None where the fit is undefined (n < 2 or no variance in m)."""
+    r = _ncc_record(rec)
+    out = np.zeros(4)
+    rc = lib().sift3d_amd_affine_ncc_fit(r.ctypes.data, _dptr(out))
+    return tuple(float(v) for v in out) if rc == 0 else None
+
+
+def affine_ncc_lm_step(rec, free_mask=AFFINE_FREE_ALL, lam=0.0):
+    """delta float64 [12] of sift3d_amd_affine_ncc_lm_step (host): the first 12 entries of the damped Gauss-Newton
+    step over the freed parameters and (alpha, beta), 0 elsewhere; None where the entry refuses."""
+    r = _ncc_record(rec)
+    delta = np.zeros(12)
+    rc = lib().sift3d_amd_affine_ncc_lm_step(r.ctypes.data, int(free_mask) & 0xFFFFFFFF, float(lam), _dptr(delta))
+    return delta if rc == 0 else None
+
+
+def affine_ncc_refine(F, M, A, params=None, work=None, mask_fixed=None, mask_moving=None):
+    """sift3d_amd_affine_ncc_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the
+    call waits for it once per evaluation).  Returns (AffineRefineResult, fit float64 [4] = alpha, beta, cost, ncc at
+    the final A).  mask_fixed, mask_moving: as similarity's."""
+    for t in (F, M):
+        _tensor(t, "affine_ncc_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device("affine_ncc_refine", F, M)
+    masks = _masks("affine_ncc_refine", F, M, mask_fixed, mask_moving) or (None, None)
+    a = _affine12(A, "affine_ncc_refine")
+    p = params if params is not None else affine_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    need = lib().sift3d_amd_affine_ncc_refine_work_bytes(ox, oy, oz, nx, ny, nz, p.levels)
+    if need == 0:
+        raise ValueError("affine_ncc_refine: levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
+    work = _work(work, (need + 3) // 4, F, "affine_ncc_refine")
+    res = AffineRefineResult()
+    fit = np.zeros(4)
+    _check(lib().sift3d_amd_affine_ncc_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
+                                                     C.byref(p), C.byref(res), _dptr(fit), work.data_ptr(),
+                                                     current_stream(), *masks),
+           "sift3d_amd_affine_ncc_refine_device")
+    return res, fit
 
 
 # ---- B-spline free-form deformation (contract: include/sift3d_amd.h, "B-spline free-form deformation") ----
