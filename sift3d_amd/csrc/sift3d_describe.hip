@@ -63,9 +63,34 @@ constexpr int HIST_LDS = 800;
 constexpr int FACE_STRIDE = 20;
 // Phase A -> phase B records, field-major: row f holds field f of half a batch (32 voxels; the
 // records go through LDS half a batch at a time: LDS capacity is what limits the waves per CU).
-// Rows are 36 floats apart: the eleven rows 0..10 (and the three rows 11..13) that the committer lanes of a
-// half-wave read with one ds_read_b128 (four voxels at a time) fall on disjoint bank quads of the 64 banks.
-constexpr int RROW = 36;
+// The 14 rows lie in 7 super-rows of 64 consecutive floats: super-row i = row i, then row 7 + i.  Lane l of
+// the wave holds field i (l < 32) or 7 + i (l >= 32) of voxel l & 31 (see rp), so it stores at super-row i +
+// 4 * l bytes: the address ds_write_addtid_b32 forms by itself, without an address register.
+// Super-rows are RSUPER = 68 floats apart: row r starts on 4-bank group r (r < 7) or r + 1 (r >= 7) of the 16
+// groups of the 64 banks ds_read_b128 uses.  The committer lanes that one of its lane groups serves all lie in
+// one half-wave (same column offset 16 * half), lanes on the same row read the same address (a broadcast), and the
+// 14 rows start on 14 different groups: the read of rows 0..10 (X) and the read of rows 11..13 (bin addresses)
+// are free of bank conflicts, and the two sets of groups are disjoint.
+constexpr int RSUPER = 68;
+constexpr int REC_FLOATS = 7 * RSUPER;
+constexpr int rec_row(int r) { return r < 7 ? r * RSUPER : (r - 7) * RSUPER + 32; }
+constexpr int rec_group(int r) { return (rec_row(r) / 4) % 16; }
+constexpr bool rec_groups_distinct()
+{
+    for (int a = 0; a < 14; a++)
+        for (int b = a + 1; b < 14; b++)
+            if (rec_group(a) == rec_group(b))
+                return false;
+    return true;
+}
+static_assert(rec_groups_distinct(), "record rows: X (0..10) and bin-address rows (11..13) on disjoint bank groups");
+static_assert(RSUPER % 4 == 0 && RSUPER >= 64, "record rows: 16-byte aligned, 64 lanes per super-row");
+
+// The LDS byte address of a __shared__ object (wave-uniform), for M0.
+__device__ __forceinline__ uint32_t lds_addr(const void *p)
+{
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
+}
 
 #ifdef SIFT3D_AMD_DIAG
 #define DESC_ABLATE_ARG , int ablate
@@ -211,11 +236,11 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
                                                  uint32_t *__restrict__ work, float *__restrict__ part,
                                                  uint32_t *__restrict__ done DESC_ABLATE_ARG)
 {
-    // per wave: 2 * 3200 + 2016 + 1024 B; per workgroup 39.4 KB -> four workgroups = 16 waves per CU
+    // per wave: 2 * 3200 + 1904 + 1024 B; per workgroup 38.9 KB -> four workgroups = 16 waves per CU
     __shared__ float hist_[DWAVES][2 * HIST_LDS];   // one private histogram per half-wave
     // records of half a batch, field-major: rows 0..7 mag * trilinear weight of the eight cells,
     // 8..10 barycentric weights, 11..13 byte address of bin (base cell, face vertex j)
-    __shared__ __attribute__((aligned(16))) float rec_[DWAVES][14][RROW];
+    __shared__ __attribute__((aligned(16))) float rec_[DWAVES][REC_FLOATS];   // rows at rec_row(f)
     __shared__ int queue_[DWAVES][DQ];   // xx | yy<<xsh | zz<<ysh, window-relative, in scan order
     __shared__ __attribute__((aligned(16))) float sface[20 * FACE_STRIDE]; // c_face16 (per-lane face index)
     __shared__ int soct[32];      // c_oct_face
@@ -223,8 +248,12 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     float *const hist = hist_[wv];
-    float(*const xw)[RROW] = &rec_[wv][0];   // rows 0..7 mw[cell], 8..10 bw[vertex]
-    int(*const ab)[RROW] = reinterpret_cast<int(*)[RROW]>(&rec_[wv][11]);
+    float *const rec = rec_[wv];             // rows 0..7 mw[cell], 8..10 bw[vertex], 11..13 bin addresses
+    // M0 of the add-tid stores (records, histogram clear).  Nothing else in this kernel uses M0: every asm block
+    // that needs it sets it first and assumes nothing about it afterwards.  (s_nop: an add-tid store needs one
+    // wait state behind a scalar write of M0, and the compiler does not look into an asm block.)
+    const uint32_t rec_m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(rec));
+    const uint32_t hist_m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(hist));
     int *const queue = queue_[wv];
     for (int i = threadIdx.x; i < 20 * 16; i += 64 * DWAVES)
         sface[(i >> 4) * FACE_STRIDE + (i & 15)] = c_face16[i];
@@ -272,8 +301,13 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     const int pp = split ? (int)(item % DPARTS) : 0;
     if (ki >= n)
         break;
-    for (int i = lane; i < 2 * HIST_LDS; i += 64)
-        hist[i] = 0.0f;
+    // both histograms to zero: 25 add-tid stores of 64 floats each
+    static_assert(2 * HIST_LDS == 25 * 64, "histogram clear: 25 whole-wave stores");
+#define Z4(o) "ds_write_addtid_b32 %0 offset:" #o "\n\tds_write_addtid_b32 %0 offset:" #o "+256\n\t" \
+              "ds_write_addtid_b32 %0 offset:" #o "+512\n\tds_write_addtid_b32 %0 offset:" #o "+768\n\t"
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t" Z4(0) Z4(1024) Z4(2048) Z4(3072) Z4(4096) Z4(5120)
+                 "ds_write_addtid_b32 %0 offset:6144" ::"v"(0.0f), "s"(hist_m0) : "m0", "memory");
+#undef Z4
     wave_sync();
     const sift3d_hip_kp K = kps[ki];
     const sift3d_hip_level L = levels[K.level];
@@ -427,11 +461,18 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // almost no VALU, so each pass is issued in one basic block with half of the arithmetic of
     // the NEXT batch (see batch()), which the scheduler interleaves with it.  Records of four
     // rounds are read with two 16-byte loads, one chunk ahead.
-    float *const rrow = &rec_[wv][7 * half][l5];
+    // committer lane: its X row and its bin-address row, at its half-wave's 16 voxels
+    const float *const xrd = rec + rec_row(pxr) + 16 * half;
+    const int *const ard = reinterpret_cast<const int *>(rec + rec_row(11 + pj) + 16 * half);
+    // the seven record words of a lane go to super-rows 0..6 at 4 * lane bytes: seven add-tid stores (no address
+    // register, half the store-path time of ds_write_b32), M0 = the wave's record block
     auto commit_write = [&](int pass) {
-#pragma unroll
-        for (int i = 0; i < 7; i++)
-            rrow[i * RROW] = rp[pass][i];
+#define RS(i) "ds_write_addtid_b32 %" #i " offset:%c8*" #i "\n\t"
+        asm volatile("s_mov_b32 m0, %7\n\ts_nop 0\n\t" RS(0) RS(1) RS(2) RS(3) RS(4) RS(5) RS(6)
+                     ::"v"(rp[pass][0]), "v"(rp[pass][1]), "v"(rp[pass][2]), "v"(rp[pass][3]), "v"(rp[pass][4]),
+                       "v"(rp[pass][5]), "v"(rp[pass][6]), "s"(rec_m0), "n"(RSUPER * 4)
+                     : "m0", "memory");
+#undef RS
         wave_sync();
     };
     // The commit chain, interleaved BY HAND with the per-voxel arithmetic.  A round is
@@ -471,15 +512,15 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
 #define KEEP(v) asm volatile("" ::"v"(v))
 #define COMMIT_BEGIN(coff)                                                                    \
     const int coff4 = (coff);                                                                 \
-    int4 cb4 = *reinterpret_cast<const int4 *>(&ab[pj][hb]);                                   \
-    float4 cx4 = *reinterpret_cast<const float4 *>(&xw[pxr][hb]);                               \
+    int4 cb4 = *reinterpret_cast<const int4 *>(ard);                                          \
+    float4 cx4 = *reinterpret_cast<const float4 *>(xrd);                                      \
     int4 nb4 = cb4;                                                                           \
     float4 nx4 = cx4;
 #define ROUND(u, ...)                                                                         \
     {                                                                                         \
         if (((u) & 3) == 0 && (u) + 4 < 16) {                                                 \
-            nb4 = *reinterpret_cast<const int4 *>(&ab[pj][hb + (u) + 4]);                      \
-            nx4 = *reinterpret_cast<const float4 *>(&xw[pxr][hb + (u) + 4]);                    \
+            nb4 = *reinterpret_cast<const int4 *>(ard + (u) + 4);                             \
+            nx4 = *reinterpret_cast<const float4 *>(xrd + (u) + 4);                           \
         }                                                                                     \
         const int mb_[4] = { cb4.x, cb4.y, cb4.z, cb4.w };                                    \
         const float xv_[4] = { cx4.x, cx4.y, cx4.z, cx4.w };                                  \
@@ -521,7 +562,6 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
         diag_voxels += (unsigned)cnt;
 #endif
         if (DESC_ABLATE(2)) { prefetch(nstart, ncnt); return; }
-        const int hb = half * 16;
         // (lanes beyond cnt compute on stale -- finite -- values and are discarded below)
         int x, y, z;
         float dx, dy, dz, kx, ky, kz, vbx, vby, vbz, gx, gy, gz, rx, ry, rz, m2;
@@ -681,7 +721,6 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     };
     // the commit passes of the last batch (nothing left to weave in)
     auto commit_tail = [&](int pass) {
-        const int hb = half * 16;
         commit_write(pass);
         {
             COMMIT_BEGIN(coff_a);
