@@ -951,6 +951,102 @@ sift3d_amd_affine_ncc_refine_device(const float *d_F, int ox, int oy, int oz, co
                                     void *stream, const float *d_WF, const float *d_WM);
 
 /* ------------------------------------------------------------------------ */
+/* Mutual-information affine refinement (Mattes)                             */
+/* ------------------------------------------------------------------------ */
+/* "Intensity-driven affine refinement" for two volumes whose intensities are related by an unknown map that need not be
+ * monotone (CT to MR, T1 to T2): the pull map is moved towards a larger mutual information of the fixed bin and a
+ * Parzen-windowed moving bin (Mattes et al.).  The histogram is accumulated in fixed point, so it is exact and a
+ * function of the inputs alone; the device never takes a logarithm: the host turns the integer histogram into the cost
+ * and a table W, and hands W to the second pass.  No upstream counterpart: PARITY UNPINNED, pinned to this contract and
+ * its numpy restatement (tests/affine_mi_restatement.py).
+ *
+ * The pull map, the inside test, the LINEAR sample m, its gradient g, the centring c, P and J[4 d + j] = G_d P_j are
+ * those of "Intensity-driven affine refinement", word for word; d_WF and d_WM are "Masks"' masks, word for word, and
+ * either may be NULL.
+ *
+ * Bins.  B = bins, 4 <= B <= SIFT3D_AMD_PARZEN_MAX_BINS, and per volume a range lo < hi (finite floats); each range is
+ * refused as "Similarity measures" refuses it with this B.
+ * Fixed bin.  b_f is "Similarity measures"' rule on (lo_f, hi_f, B), in float, word for word: s = (float) B / (hi_f -
+ * lo_f), t = (f - lo_f) * s, b_f = t < 0 ? 0 : t >= B ? B - 1 : (int) t.
+ * Moving window.  The moving value is spread over four bins by a cubic B-spline, with one padding bin at each end.
+ * s_m = (double)(B - 3) / ((double) hi_m - (double) lo_m) once on the host; per voxel, double, this order, unfused:
+ *     t   = 1.0 + ((double) m - (double) lo_m) * s_m
+ *     out = t < 1.0 || t > (double)(B - 2)                         (m outside its range)
+ *     t   = clamp(t, 1.0, B - 2)
+ *     k0  = min((int) floor(t) - 1, B - 4)
+ *     r   = t - (double)(k0 + 1)                                   (exact, in [0, 1])
+ *     w[0..3]  = the four cubic weights of "B-spline free-form deformation" at t := r, kept in double
+ *     dw[0..3] = -(u * u) / 2,  (3 * t2 - 4 * r) / 2,  ((-3 * t2 + 2 * r) + 1) / 2,  t2 / 2     (u = 1 - r, t2 = r * r)
+ *     q[k]     = (uint32) llrint(w[k] * 65536.0)                   (round to nearest even)
+ * One inline function (sift3d_parzen.h) states this for the kernels and the host; sift3d_amd_parzen_window exports it.
+ *
+ * Parzen histogram (sift3d_hip_parzen_hist_affine).  Every counted voxel adds q[k] to hist[b_f][k0 + k], k = 0 .. 3, and
+ * 1 to the count: integer adds only, so hist [B][B] uint64 and the uint64 count are exact however they are reduced.
+ * Tiles, grid (min(tiles, SIFT3D_AMD_SIMILARITY_GRID) workgroups), XCD grouping and the merge of workgroup-private
+ * counters into hist are "Similarity measures"'; the private counters are 64 bits wide (a voxel adds up to 43691 to a
+ * bin), so none wraps for any grid the tiling accepts.  Both outputs are zeroed / written on `stream` by the call.
+ * Checks, alignment (hist, count, work: 8 bytes; the rest 4), overlap rules, asynchrony and "allocates nothing" are
+ * sift3d_hip_similarity_affine_masked's.  d_work: sift3d_amd_parzen_hist_work_bytes() bytes.
+ *
+ * Cost and table (sift3d_amd_parzen_mi, host).  With r, c, N of "Similarity measures" on hist: out->n = N, the three
+ * entropies, mi and nmi by that section's formulas (one routine; all NaN when N == 0), msd = ncc = NaN; cost = -mi.
+ *     W[i][j] = log((double) hist[i][j] / (double) c[j]) where hist[i][j] != 0, else 0.0         (W may be NULL)
+ * -1 on a NULL hist or out, or bins out of range.
+ *
+ * MI record (sift3d_hip_affine_mi_normal_eqs).  d_W [B][B] double on the device.  Per counted voxel, double, unfused:
+ *     psi   = out ? 0.0 : s_m * (((dw[0] * W0 + dw[1] * W1) + dw[2] * W2) + dw[3] * W3),   Wk = W[b_f][k0 + k]
+ *     G'_d  = psi * (double) g_d,   J'[4 d + j] = G'_d P_j,   E = -1
+ * The record has the layout of the MSD record, SIFT3D_AMD_AFFINE_NORMAL_BYTES:
+ *     uint64 n;  double S_pp = sum psi psi;  double b[12] = sum J' E;  double H[12][12] = sum J' J'^T,
+ * H full and symmetric bit for bit; partial slots, finish and ordering rules are the MSD record's (a term carries at
+ * most 11 roundings: that record's 8, the two products psi * g_d and their now inexact product).  -mi is, up to a term
+ * that does not depend on A to first order, the mean negative log-likelihood -(1 / n) sum log p(m | f); psi J is its
+ * per-voxel score and sum psi^2 J J^T its Fisher information, so sift3d_amd_affine_lm_step on this record is a damped
+ * Fisher-scoring step, positive semi-definite and free of the scale of psi.  Checks are sift3d_hip_affine_normal_eqs_
+ * masked's, with d_W an 8-byte aligned input.  d_work: sift3d_amd_affine_normal_work_bytes() bytes.
+ *
+ * Driver (sift3d_amd_affine_mi_refine_device).  sift3d_amd_affine_refine_device's loop, levels, masks and stop reasons,
+ * one loop in the code too.  An evaluation is one histogram pass and sift3d_amd_parzen_mi on the host; its n is the
+ * count.  The MI record is computed only at the map the next step starts from (a level's first map and each accepted
+ * trial that does not end the level): one copy of W to the device and one pass; a rejected trial costs the histogram
+ * pass alone.  Accept when n' >= min_overlap * n_first and cost' < cost.  An evaluation with N == 0 has no cost: as a
+ * trial it is rejected, as a level's first evaluation it stops the level with LM_FAILED.  Ranges and bins are level 0's
+ * at every level (restriction averages, so values stay in range).  Params and result are the existing structs; the
+ * trail's `msd` field carries `cost`.  mi_out: the measures at the final A on level 0 (n = N; all NaN and n = 0 when no
+ * evaluation was made).  Checks are the NCC driver's, then bins and ranges; mi_out must not be NULL.
+ * d_work: sift3d_amd_affine_mi_refine_work_bytes() bytes, whatever `bins` is. */
+#define SIFT3D_AMD_PARZEN_MAX_BINS 64
+/* host only: the window of one moving value.  -1 on NULL pointers, bins out of range or a refused range. */
+SIFT3D_AMD_API int
+sift3d_amd_parzen_window(float m, float lo, float hi, int bins, int *k0, uint32_t *q /*4*/, double *dw /*4*/, int *out);
+/* bytes of d_work for sift3d_hip_parzen_hist_affine on this fixed grid (0 for dims <= 0) */
+SIFT3D_AMD_API size_t sift3d_amd_parzen_hist_work_bytes(int ox, int oy, int oz);
+/* d_F [oz][oy][ox], d_M [nz][ny][nx], d_hist [bins][bins] uint64, d_count one uint64; d_WF, d_WM the masks or NULL */
+SIFT3D_AMD_API int
+sift3d_hip_parzen_hist_affine(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                              const double *A /*12*/, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                              uint64_t *d_hist, uint64_t *d_count, void *d_work, void *stream, const float *d_WF,
+                              const float *d_WM);
+/* host only: hist [bins][bins] on the host; W [bins][bins] or NULL */
+SIFT3D_AMD_API int sift3d_amd_parzen_mi(const uint64_t *hist, int bins, sift3d_amd_similarity *out, double *W);
+/* d_W [bins][bins] double on the device; d_record the MSD record's layout */
+SIFT3D_AMD_API int
+sift3d_hip_affine_mi_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                const double *A /*12*/, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                                const double *d_W, void *d_record, void *d_work, void *stream, const float *d_WF,
+                                const float *d_WM);
+/* bytes of d_work for the driver (0 for bad arguments) */
+SIFT3D_AMD_API size_t
+sift3d_amd_affine_mi_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels);
+/* A_io [12] and mi_out on the host; waits for `stream` once per pass */
+SIFT3D_AMD_API int
+sift3d_amd_affine_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                   double *A_io, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                                   const sift3d_amd_affine_refine_params *params,
+                                   sift3d_amd_affine_refine_result *result, sift3d_amd_similarity *mi_out,
+                                   void *d_work, void *stream, const float *d_WF, const float *d_WM);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -620,11 +620,21 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
     refine=True (or a dict of refine_affine's keyword arguments) runs refine_affine from the RANSAC result and
     returns RefinedRegistration(A, inliers, num_matches, warped, A_ransac, refinement): A and warped are the refined
     map and its resampling, A_ransac is what refine=False returns as A, refinement the AffineRefinement (the
-    NccAffineRefinement with refine=dict(metric="ncc"))."""
+    NccAffineRefinement with refine=dict(metric="ncc"), the MiAffineRefinement with refine=dict(metric="mi")).
+    Where the matches give RANSAC no model the call raises RuntimeError, but with refine=dict(metric="mi") it goes on
+    from the identity (A_ransac is then the identity and inliers is all False): keypoints of two modalities often do
+    not match, and that is the pair the mutual information is for."""
     import torch
     from . import hip
     p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
-    A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
+    try:
+        A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
+    except RuntimeError:
+        # across modalities the descriptors often do not match (an inverted contrast already leaves none): the
+        # mutual-information refinement, made for such pairs, then starts from the identity
+        if not (isinstance(refine, dict) and refine.get("metric") == "mi"):
+            raise
+        A, inl = np.eye(3, 4), np.zeros(len(p_mov), bool)
     if refine:
         r = refine_affine(moving, fixed, affine_invert(A), **(refine if isinstance(refine, dict) else {}))
         return RefinedRegistration(affine_invert(r.A), inl, len(p_mov), r.warped, A, r)
@@ -1036,11 +1046,14 @@ RefinedRegistration = collections.namedtuple("RefinedRegistration",
                                              "A inliers num_matches warped A_ransac refinement")
 NccAffineRefinement = collections.namedtuple(
     "NccAffineRefinement", "A cost count accepted lambdas levels level_slices evaluations stop warped ncc gain offset")
+MiAffineRefinement = collections.namedtuple(
+    "MiAffineRefinement", "A cost count accepted lambdas levels level_slices evaluations stop warped mi nmi bins")
+MI_BINS = 32
 AFFINE_FREE = {"affine": 0xFFF, "translation": 0x888}
 
 
 def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", mask_fixed=None, mask_moving=None,
-                  metric="msd", **params):
+                  metric="msd", bins=None, range_fixed=None, range_moving=None, **params):
     """Move the 3 x 4 affine pull map A (fixed voxel -> moving voxel, as similarity's transform; None: the identity,
     which needs no equal shapes) towards a smaller mean squared difference between `fixed` and `moving` seen through
     it, by Levenberg-Marquardt steps on the device's Gauss-Newton normal equations (contract: include/sift3d_amd.h,
@@ -1058,11 +1071,30 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     not change under a gain (a negative one included) or an offset of either volume, where the MSD's does.  It returns
     NccAffineRefinement: AffineRefinement's fields with `cost` (the mean squared residual of the fit) in the place of
     `msd`, then ncc, gain and offset of the fit at the final A.  `warped` is still `moving` through A: its intensities
-    are not remapped (gain * warped + offset is the fitted image).  Any other metric raises ValueError."""
+    are not remapped (gain * warped + offset is the fitted image).
+    metric="mi" maximises the Mattes mutual information of the fixed bin and the Parzen-windowed moving bin (contract:
+    "Mutual-information affine refinement (Mattes)"), for volumes whose intensities are related by an unknown map that
+    need not be monotone (CT to MR, T1 to T2).  bins (None: 32; 4 .. 64) and range_fixed, range_moving ((lo, hi); None:
+    the volume's own min and max, one host synchronisation each) set the histogram and are level 0's on every level.  It
+    returns MiAffineRefinement: NccAffineRefinement's fields without gain and offset, `cost` = -mi per evaluation, then
+    mi and nmi at the final A and bins; `warped` is `moving` through A, not remapped.  bins or a range with another
+    metric, and any other metric, raise ValueError."""
     import torch
     from . import hip
-    if metric not in ("msd", "ncc"):
-        raise ValueError("refine_affine: metric must be 'msd' or 'ncc', not %r" % (metric,))
+    if metric not in ("msd", "ncc", "mi"):
+        raise ValueError("refine_affine: metric must be 'msd', 'ncc' or 'mi', not %r" % (metric,))
+    if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
+        raise ValueError("refine_affine: bins, range_fixed and range_moving belong to metric='mi', not %r" % (metric,))
+    if metric == "mi":
+        bins = MI_BINS if bins is None else bins
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or \
+                not 4 <= int(bins) <= hip.PARZEN_MAX_BINS:
+            raise ValueError("refine_affine: bins must be in [4, %d]" % hip.PARZEN_MAX_BINS)
+        for r, name in ((range_fixed, "range_fixed"), (range_moving, "range_moving")):
+            if r is not None:
+                lo, hi = (float(np.float32(v)) for v in r)
+                if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+                    raise ValueError("refine_affine: %s must be finite with lo < hi" % name)
     if interp != "linear":
         raise ValueError("refine_affine: the sample is linear; interp=%r has no gradient" % (interp,))
     mask = AFFINE_FREE.get(free, free) if isinstance(free, str) else free
@@ -1086,6 +1118,9 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     WM = _mask_tensor(WM, F, "refine_affine", "mask_moving")
     if metric == "ncc":
         res, fit = hip.affine_ncc_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
+    elif metric == "mi":
+        res, sim = hip.affine_mi_refine(F, M, A0, int(bins), _own_range(F, range_fixed), _own_range(M, range_moving),
+                                        p, mask_fixed=WF, mask_moving=WM)
     else:
         res = hip.affine_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     k = res.evaluations
@@ -1103,6 +1138,8 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
                            slices, k, hip.AFFINE_STOPS[res.stop], warped)
     if metric == "ncc":
         return NccAffineRefinement(*out, ncc=float(fit[3]), gain=float(fit[0]), offset=float(fit[1]))
+    if metric == "mi":
+        return MiAffineRefinement(*out, mi=float(sim.mi), nmi=float(sim.nmi), bins=int(bins))
     return out
 
 
@@ -1201,7 +1238,7 @@ def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
     refine_ffd's further keyword arguments; refine: True, or register's dict of refine_affine's keyword arguments
-    (dict(metric="ncc") for the affine stage; the FFD stage itself minimises the MSD).  The volumes are torch CUDA float32 tensors, or Images / arrays, which are
+    (dict(metric="ncc") or dict(metric="mi") for the affine stage; the FFD stage itself minimises the MSD).  The volumes are torch CUDA float32 tensors, or Images / arrays, which are
     uploaded.  Returns FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""
     F = _similarity_volume(fixed, "register_ffd", "fixed")
     M = _similarity_volume(moving, "register_ffd", "moving", F.device)

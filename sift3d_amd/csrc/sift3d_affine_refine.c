@@ -16,6 +16,16 @@ int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F, int ox, in
                                     int ny, int nz, const double *A, void *d_record, void *d_work, void *stream,
                                     const float *d_WF, const float *d_WM);
 
+int sift3d_parzen_hist_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                              int nz, const double *A, int bins, float lo_f, float s_f, float lo_m, float hi_m,
+                              unsigned long long *d_hist, unsigned long long *d_count, void *d_work, void *stream,
+                              const float *d_WF, const float *d_WM);
+
+int sift3d_affine_mi_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                                   int ny, int nz, const double *A, int bins, float lo_f, float s_f, float lo_m,
+                                   float hi_m, const double *d_W, void *d_record, void *d_work, void *stream,
+                                   const float *d_WF, const float *d_WM);
+
 /* a double per statistic (60 + 12 + 1, and the uint64 count) per partial slot; NCC: 60 + 36 + 5 and the count */
 #define AFFINE_NORMAL_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 74 * 8)
 #define AFFINE_NCC_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 102 * 8)
@@ -80,6 +90,128 @@ int sift3d_hip_affine_ncc_normal_eqs(const float *d_F, int ox, int oy, int oz, c
 {
     return affine_normal_eqs("sift3d_hip_affine_ncc_normal_eqs", d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_record,
                              d_work, stream, d_WF, d_WM, 1);
+}
+
+/* ---- Mattes mutual information: the window, the histogram pass, the cost and the table, the record pass ---- */
+#include "sift3d_parzen.h"
+
+#define PARZEN_HIST_WORK_BYTES ((size_t)SIFT3D_AMD_SIMILARITY_GRID * 8)       /* a uint64 count per partial slot */
+
+static int parzen_bins_ok(int bins)
+{
+    return bins >= 4 && bins <= SIFT3D_AMD_PARZEN_MAX_BINS;
+}
+
+/* bins and the two ranges, refused as "Similarity measures" refuses them; *s_f is the fixed volume's float scale */
+static int parzen_check(const char *what, int bins, float lo_f, float hi_f, float lo_m, float hi_m, float *s_f)
+{
+    if (!parzen_bins_ok(bins))
+        return refuse(what, "bins must be in [4, SIFT3D_AMD_PARZEN_MAX_BINS]");
+    *s_f = bin_scale(bins, lo_f, hi_f);
+    if (*s_f == 0.0f || bin_scale(bins, lo_m, hi_m) == 0.0f)
+        return refuse(what, "a range must be finite, lo < hi, and wide enough for bins / (hi - lo) in float");
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_parzen_window(float m, float lo, float hi, int bins, int *k0, uint32_t *q, double *dw, int *out)
+{
+    static const char what[] = "sift3d_amd_parzen_window";
+    float s;
+    if (!k0 || !q || !dw || !out)
+        return refuse(what, "NULL argument");
+    if (parzen_check(what, bins, lo, hi, lo, hi, &s))
+        return SIFT3D_FAILURE;
+    parzen_window(m, lo, parzen_scale(lo, hi, bins), bins, k0, q, dw, out);
+    return SIFT3D_SUCCESS;
+}
+
+size_t sift3d_amd_parzen_hist_work_bytes(int ox, int oy, int oz)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0)
+        return 0;
+    return PARZEN_HIST_WORK_BYTES;
+}
+
+int sift3d_hip_parzen_hist_affine(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                  const double *A, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                                  uint64_t *d_hist, uint64_t *d_count, void *d_work, void *stream, const float *d_WF,
+                                  const float *d_WM)
+{
+    static const char what[] = "sift3d_hip_parzen_hist_affine";
+    float s_f;
+    if (!d_F || !d_M || !A || !d_hist || !d_count || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) ||
+        parzen_check(what, bins, lo_f, hi_f, lo_m, hi_m, &s_f) || check_affine(what, A) ||
+        check_aligned(what, ADDR(d_hist) | ADDR(d_count) | ADDR(d_work),
+                      ADDR(d_F) | ADDR(d_M) | ADDR(d_WF) | ADDR(d_WM)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
+        const range_t out[] = { { d_hist, (size_t)bins * bins * sizeof(uint64_t) }, { d_count, sizeof(uint64_t) },
+                                { d_work, PARZEN_HIST_WORK_BYTES } };
+        if (ranges_aliased(out, 3, in, 4))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_parzen_hist_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m,
+                                     (unsigned long long *)d_hist, (unsigned long long *)d_count, d_work, stream,
+                                     d_WF, d_WM);
+}
+
+int sift3d_amd_parzen_mi(const uint64_t *hist, int bins, sift3d_amd_similarity *out, double *W)
+{
+    static const char what[] = "sift3d_amd_parzen_mi";
+    uint64_t r[SIFT3D_AMD_PARZEN_MAX_BINS], c[SIFT3D_AMD_PARZEN_MAX_BINS], total = 0;
+    int i, j;
+    if (!hist || !out)
+        return refuse(what, "NULL argument");
+    if (!parzen_bins_ok(bins))
+        return refuse(what, "bins must be in [4, SIFT3D_AMD_PARZEN_MAX_BINS]");
+    marginals(hist, bins, r, c);
+    for (i = 0; i < bins; i++)
+        total += r[i];
+    out->n = total;
+    out->msd = out->ncc = NAN;
+    if (total == 0)
+        out->mi = out->nmi = out->entropy_fixed = out->entropy_moving = out->entropy_joint = NAN;
+    else
+        entropy_measures(hist, bins, r, c, total, out);
+    if (W)
+        for (i = 0; i < bins; i++)
+            for (j = 0; j < bins; j++) {
+                const uint64_t h = hist[(size_t)i * bins + j];
+                W[(size_t)i * bins + j] = h ? log((double)h / (double)c[j]) : 0.0;
+            }
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_hip_affine_mi_normal_eqs(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    const double *A, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                                    const double *d_W, void *d_record, void *d_work, void *stream, const float *d_WF,
+                                    const float *d_WM)
+{
+    static const char what[] = "sift3d_hip_affine_mi_normal_eqs";
+    float s_f;
+    if (!d_F || !d_M || !A || !d_W || !d_record || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) ||
+        parzen_check(what, bins, lo_f, hi_f, lo_m, hi_m, &s_f) || check_affine(what, A) ||
+        check_aligned(what, ADDR(d_record) | ADDR(d_work) | ADDR(d_W),
+                      ADDR(d_F) | ADDR(d_M) | ADDR(d_WF) | ADDR(d_WM)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 },
+                               { d_W, (size_t)bins * bins * sizeof(double) } };
+        const range_t out[] = { { d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES }, { d_work, AFFINE_NORMAL_WORK_BYTES } };
+        if (ranges_aliased(out, 2, in, 5))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_affine_mi_normal_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m, d_W,
+                                          d_record, d_work, stream, d_WF, d_WM);
 }
 
 /* ---- host arithmetic on a record (the order of every operation is the header's) ---- */
@@ -326,21 +458,41 @@ static double ncc_cost(const affine_eval *e)
 
 typedef struct {
     int ncc;                                                 /* which pass affine_normal_eqs launches */
+    int mi;                                                  /* an evaluation is the histogram pass (mi_state) */
     size_t record_bytes, normal_work_bytes;
+    size_t extra_bytes;                                      /* of d_work behind the record (MI: hist, count, W) */
     double (*cost)(const affine_eval *);                     /* what a step must lower; NaN: never accepted */
     int (*step)(const void *record, unsigned free_mask, double lambda, double *delta);
 } affine_metric;
 
-static const affine_metric METRIC_MSD = { 0, SIFT3D_AMD_AFFINE_NORMAL_BYTES, AFFINE_NORMAL_WORK_BYTES, msd_cost,
+/* MI, behind the record: the histogram [MAX][MAX] uint64 and the count (copied to the host together), padded to 16
+ * bytes, then W [MAX][MAX] double; the sizes are those of SIFT3D_AMD_PARZEN_MAX_BINS whatever `bins` is */
+#define MI_TABLE_BYTES ((size_t)SIFT3D_AMD_PARZEN_MAX_BINS * SIFT3D_AMD_PARZEN_MAX_BINS * 8)
+#define MI_EXTRA_BYTES (2 * MI_TABLE_BYTES + 16)
+
+static const affine_metric METRIC_MSD = { 0, 0, SIFT3D_AMD_AFFINE_NORMAL_BYTES, AFFINE_NORMAL_WORK_BYTES, 0, msd_cost,
                                           sift3d_amd_affine_lm_step };
-static const affine_metric METRIC_NCC = { 1, SIFT3D_AMD_AFFINE_NCC_BYTES, AFFINE_NCC_WORK_BYTES, ncc_cost,
+static const affine_metric METRIC_NCC = { 1, 0, SIFT3D_AMD_AFFINE_NCC_BYTES, AFFINE_NCC_WORK_BYTES, 0, ncc_cost,
                                           sift3d_amd_affine_ncc_lm_step };
+static const affine_metric METRIC_MI = { 0, 1, SIFT3D_AMD_AFFINE_NORMAL_BYTES, AFFINE_NORMAL_WORK_BYTES,
+                                         MI_EXTRA_BYTES, NULL, sift3d_amd_affine_lm_step };
+
+/* what the MI driver carries from evaluation to evaluation */
+typedef struct {
+    int bins;
+    float lo_f, hi_f, lo_m, hi_m;
+    uint64_t *d_hist;                                        /* in d_work: [bins][bins], then the count */
+    double *d_W;                                             /* in d_work */
+    uint64_t hist[SIFT3D_AMD_PARZEN_MAX_BINS * SIFT3D_AMD_PARZEN_MAX_BINS + 1];     /* the last evaluation's, and count */
+    double W[SIFT3D_AMD_PARZEN_MAX_BINS * SIFT3D_AMD_PARZEN_MAX_BINS];              /* the last evaluation's table */
+    sift3d_amd_similarity sim, sim_trial;                    /* measures at A; at the last evaluation */
+} mi_state;
 
 /* d_work, in bytes: the normal equations' partial slots, the record, then per level l = 1 .. levels-1 the restricted
  * fixed and moving volumes, each rounded up to a multiple of 16 bytes */
 static size_t affine_record_pad(const affine_metric *mt)
 {
-    return (mt->record_bytes + 15) / 16 * 16;
+    return (mt->record_bytes + 15) / 16 * 16 + mt->extra_bytes;
 }
 
 static size_t affine_work_bytes(const affine_metric *mt, int ox, int oy, int oz, int nx, int ny, int nz, int levels)
@@ -422,6 +574,11 @@ size_t sift3d_amd_affine_ncc_refine_work_bytes(int ox, int oy, int oz, int nx, i
     return affine_masked_work_bytes(&METRIC_NCC, ox, oy, oz, nx, ny, nz, levels);
 }
 
+size_t sift3d_amd_affine_mi_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int levels)
+{
+    return affine_masked_work_bytes(&METRIC_MI, ox, oy, oz, nx, ny, nz, levels);
+}
+
 /* the largest distance by which the maps A and B move a corner of the grid apart */
 static double affine_corner_move(const double *A, const double *B, int ox, int oy, int oz)
 {
@@ -448,16 +605,47 @@ typedef struct {
     const float *WF, *WM;                                    /* the level's masks, or NULL */
 } affine_level;
 
-/* one evaluation at A on `lv`: the metric's pass, the record's copy to the host and the wait for it */
-static int affine_evaluate(const affine_metric *mt, const affine_level *lv, const double *A, void *d_record,
-                           void *d_work, void *stream, affine_eval *rec)
+/* one evaluation at A on `lv`: the metric's pass, the record's copy to the host and the wait for it, and the cost.
+ * MI: the histogram pass, histogram and count to the host, sift3d_amd_parzen_mi; rec holds the count alone (the rest
+ * zero) until mi_record fills it, ms->W the table and ms->sim_trial the measures. */
+static int affine_evaluate(const affine_metric *mt, mi_state *ms, const affine_level *lv, const double *A,
+                           void *d_record, void *d_work, void *stream, affine_eval *rec, double *cost)
 {
     const char *what = mt->ncc               ? "sift3d_hip_affine_ncc_normal_eqs"
                        : lv->WF || lv->WM ? "sift3d_hip_affine_normal_eqs_masked"
                                           : "sift3d_hip_affine_normal_eqs";
-    return affine_normal_eqs(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, d_record, d_work,
-                             stream, lv->WF, lv->WM, mt->ncc) ||
-           sift3d_hip_memcpy_d2h(rec, d_record, mt->record_bytes, stream) || sift3d_hip_stream_sync(stream);
+    if (mt->mi) {
+        const size_t cells = (size_t)ms->bins * ms->bins;
+        if (sift3d_hip_parzen_hist_affine(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, ms->bins,
+                                          ms->lo_f, ms->hi_f, ms->lo_m, ms->hi_m, ms->d_hist, ms->d_hist + cells,
+                                          d_work, stream, lv->WF, lv->WM) ||
+            sift3d_hip_memcpy_d2h(ms->hist, ms->d_hist, (cells + 1) * sizeof(uint64_t), stream) ||
+            sift3d_hip_stream_sync(stream) || sift3d_amd_parzen_mi(ms->hist, ms->bins, &ms->sim_trial, ms->W))
+            return SIFT3D_FAILURE;
+        memset(rec, 0, sizeof(*rec));
+        rec->n = ms->hist[cells];
+        *cost = -ms->sim_trial.mi;                           /* NaN when nothing was counted */
+        return SIFT3D_SUCCESS;
+    }
+    if (affine_normal_eqs(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, d_record, d_work,
+                          stream, lv->WF, lv->WM, mt->ncc) ||
+        sift3d_hip_memcpy_d2h(rec, d_record, mt->record_bytes, stream) || sift3d_hip_stream_sync(stream))
+        return SIFT3D_FAILURE;
+    *cost = mt->cost(rec);
+    return SIFT3D_SUCCESS;
+}
+
+/* MI: the record at A, the map of the evaluation that left its table in ms->W: W to the device, the record pass, the
+ * record to the host and the wait for it */
+static int mi_record(mi_state *ms, const affine_level *lv, const double *A, void *d_record, void *d_work, void *stream,
+                     affine_eval *rec)
+{
+    return sift3d_hip_memcpy_h2d(ms->d_W, ms->W, (size_t)ms->bins * ms->bins * sizeof(double), stream) ||
+           sift3d_hip_affine_mi_normal_eqs(lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, A, ms->bins,
+                                           ms->lo_f, ms->hi_f, ms->lo_m, ms->hi_m, ms->d_W, d_record, d_work, stream,
+                                           lv->WF, lv->WM) ||
+           sift3d_hip_memcpy_d2h(&rec->msd, d_record, SIFT3D_AMD_AFFINE_NORMAL_BYTES, stream) ||
+           sift3d_hip_stream_sync(stream);
 }
 
 static void affine_trail(sift3d_amd_affine_refine_result *res, uint64_t n, double cost, double lambda, int accepted,
@@ -471,13 +659,14 @@ static void affine_trail(sift3d_amd_affine_refine_result *res, uint64_t n, doubl
     e->level = level;
 }
 
-/* the shared body of the three drivers: `masked` selects the work buffer's size; the masks may still be NULL.  fit_out
- * (NCC; else NULL): the fit at the final A on level 0, NaN where it is undefined or no evaluation was made. */
+/* the shared body of the four drivers: `masked` selects the work buffer's size; the masks may still be NULL.  fit_out
+ * (NCC; else NULL): the fit at the final A on level 0, NaN where it is undefined or no evaluation was made.  ms (MI;
+ * else NULL): bins and ranges, checked by the caller; ms->sim leaves with the measures at the final A on level 0. */
 static int affine_refine(const affine_metric *mt, const char *what, const float *d_F, int ox, int oy, int oz,
                          const float *d_M, int nx, int ny, int nz, double *A_io,
                          const sift3d_amd_affine_refine_params *params, sift3d_amd_affine_refine_result *result,
                          double *fit_out, void *d_work, void *stream, int masked, const float *d_WF,
-                         const float *d_WM)
+                         const float *d_WM, mi_state *ms)
 {
     sift3d_amd_affine_refine_params prm;
     affine_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
@@ -516,6 +705,10 @@ static int affine_refine(const affine_metric *mt, const char *what, const float 
         fit_out[0] = fit_out[1] = fit_out[2] = fit_out[3] = NAN;
     d_record = w + mt->normal_work_bytes;
     off = mt->normal_work_bytes + affine_record_pad(mt);
+    if (ms) {
+        ms->d_hist = (uint64_t *)(w + off - MI_EXTRA_BYTES);
+        ms->d_W = (double *)(w + off - MI_TABLE_BYTES);
+    }
     lv[0] = (affine_level){ d_F, d_M, ox, oy, oz, nx, ny, nz, d_WF, d_WM };
     memcpy(A, A_io, sizeof(A));
     for (l = 1; l < prm.levels; l++) {                       /* level l from level l - 1; A's shift halves */
@@ -542,9 +735,11 @@ static int affine_refine(const affine_metric *mt, const char *what, const float 
         double lambda = prm.lambda0;
         uint64_t n_first;
         int evals = 1, stop;
-        if (affine_evaluate(mt, v, A, d_record, w, stream, &rec))
+        int stale = mt->mi;                                  /* MI: rec holds no record of A yet */
+        if (affine_evaluate(mt, ms, v, A, d_record, w, stream, &rec, &cost))
             return SIFT3D_FAILURE;
-        cost = mt->cost(&rec);
+        if (ms)
+            ms->sim = ms->sim_trial;
         affine_trail(result, rec.n, cost, lambda, 1, l);
         n_first = rec.n;
         for (;;) {
@@ -553,15 +748,20 @@ static int affine_refine(const affine_metric *mt, const char *what, const float 
                 stop = SIFT3D_AMD_AFFINE_STOP_EVALUATIONS;
                 break;
             }
+            if (stale) {                                     /* the record of the map this step starts from; ms->W
+                                                                is still that map's: no evaluation was made since */
+                if (rec.n && mi_record(ms, v, A, d_record, w, stream, &rec))
+                    return SIFT3D_FAILURE;
+                stale = 0;
+            }
             if (mt->step(&rec, prm.free_mask, lambda, delta) ||
                 sift3d_amd_affine_apply_delta(A, delta, v->ox, v->oy, v->oz, At) || check_affine(what, At)) {
                 stop = SIFT3D_AMD_AFFINE_STOP_LM_FAILED;
                 break;
             }
-            if (affine_evaluate(mt, v, At, d_record, w, stream, &trial))
+            if (affine_evaluate(mt, ms, v, At, d_record, w, stream, &trial, &cost_t))
                 return SIFT3D_FAILURE;
             evals++;
-            cost_t = mt->cost(&trial);
             accept = trial.n > 0 && (double)trial.n >= prm.min_overlap * (double)n_first && cost_t < cost;
             affine_trail(result, trial.n, cost_t, lambda, accept, l);
             if (accept) {
@@ -569,6 +769,9 @@ static int affine_refine(const affine_metric *mt, const char *what, const float 
                 memcpy(A, At, sizeof(A));
                 rec = trial;
                 cost = cost_t;
+                stale = mt->mi;
+                if (ms)
+                    ms->sim = ms->sim_trial;
                 lambda = lambda / prm.lambda_factor;
                 if (lambda < prm.lambda_min)
                     lambda = prm.lambda_min;
@@ -601,7 +804,7 @@ int sift3d_amd_affine_refine_device(const float *d_F, int ox, int oy, int oz, co
                                     sift3d_amd_affine_refine_result *result, void *d_work, void *stream)
 {
     return affine_refine(&METRIC_MSD, "sift3d_amd_affine_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params,
-                         result, NULL, d_work, stream, 0, NULL, NULL);
+                         result, NULL, d_work, stream, 0, NULL, NULL, NULL);
 }
 
 int sift3d_amd_affine_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -610,7 +813,7 @@ int sift3d_amd_affine_refine_masked_device(const float *d_F, int ox, int oy, int
                                            const float *d_WF, const float *d_WM)
 {
     return affine_refine(&METRIC_MSD, "sift3d_amd_affine_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io,
-                         params, result, NULL, d_work, stream, 1, d_WF, d_WM);
+                         params, result, NULL, d_work, stream, 1, d_WF, d_WM, NULL);
 }
 
 int sift3d_amd_affine_ncc_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -619,5 +822,32 @@ int sift3d_amd_affine_ncc_refine_device(const float *d_F, int ox, int oy, int oz
                                         void *stream, const float *d_WF, const float *d_WM)
 {
     return affine_refine(&METRIC_NCC, "sift3d_amd_affine_ncc_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_io,
-                         params, result, fit_out, d_work, stream, 1, d_WF, d_WM);
+                         params, result, fit_out, d_work, stream, 1, d_WF, d_WM, NULL);
+}
+
+int sift3d_amd_affine_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                       int nz, double *A_io, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                                       const sift3d_amd_affine_refine_params *params,
+                                       sift3d_amd_affine_refine_result *result, sift3d_amd_similarity *mi_out,
+                                       void *d_work, void *stream, const float *d_WF, const float *d_WM)
+{
+    static const char what[] = "sift3d_amd_affine_mi_refine_device";
+    mi_state ms;
+    float s_f;
+    int rc;
+    if (!mi_out)
+        return refuse(what, "NULL argument");
+    if (parzen_check(what, bins, lo_f, hi_f, lo_m, hi_m, &s_f))
+        return SIFT3D_FAILURE;
+    ms.bins = bins;
+    ms.lo_f = lo_f; ms.hi_f = hi_f;
+    ms.lo_m = lo_m; ms.hi_m = hi_m;
+    ms.sim.n = 0;
+    ms.sim.msd = ms.sim.ncc = ms.sim.mi = ms.sim.nmi = NAN;
+    ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
+    *mi_out = ms.sim;
+    rc = affine_refine(&METRIC_MI, what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_io, params, result, NULL, d_work, stream, 1,
+                       d_WF, d_WM, &ms);
+    *mi_out = ms.sim;
+    return rc;
 }

@@ -25,7 +25,10 @@
 //
 // k_affine_ncc_normal (below) is the same pass for the fit under a linear intensity map (header, "Affine refinement
 // under a linear intensity map (NCC)"): 101 double sums and the count, in two launches of 73 and 28 sums.
+// k_parzen_hist and k_affine_mi_normal (at the end) are the two passes of the fit under an unknown intensity map
+// (header, "Mutual-information affine refinement (Mattes)").
 #include "sift3d_resample.h"
+#include "sift3d_parzen.h"
 
 namespace {
 
@@ -520,6 +523,291 @@ __global__ __launch_bounds__(256) void k_affine_ncc_finish(const double *part, u
         scatter_h(H, st, v);
 }
 
+// ---- the fit under an unknown intensity map (Mattes mutual information) ----------------------------------------------
+// Header, "Mutual-information affine refinement (Mattes)"; restated in numpy by tests/affine_mi_restatement.py.  Two
+// passes over the fixed grid, both with k_affine_normal's / k_similarity's tiles, tile order, XCD grouping, pull map,
+// inside test and sample; the window of the moving value is sift3d_parzen.h's one function in both and on the host.
+struct MiArgs {
+    AffArgs a;                                   // part: the record pass's partial slots; the histogram pass's counts
+    int bins;
+    float lo_f, s_f, lo_m;                       // s_f: "Similarity measures"' float scale of the fixed bin
+    double s_m;                                  // parzen_scale(lo_m, hi_m, bins)
+    unsigned long long *hist;                    // histogram pass: [bins][bins], zeroed by the launcher
+    const double *W;                             // record pass: [bins][bins]
+};
+
+// The Parzen joint histogram in fixed point.  k_similarity without the moments: per counted voxel four integer adds
+// q[k] into the workgroup's LDS histogram at [b_f][k0 + k], then the workgroup's non-zero words into the global uint64
+// histogram with integer atomics, and its count into partial slot blockIdx.x.  Every add is an integer add, so the bytes
+// are a function of the inputs alone, whatever the order.
+//   - counters: the LDS words are 64-bit (ds_add_u64, no return value; B * B * 8 bytes, 32 KiB at B = 64: four
+//     workgroups fit a CU's 160 KiB, as many as the launch bound allows).  A workgroup visits at most
+//     ceil(tiles / grid) * 1024 < 2^32 voxels and a voxel adds at most 43691 < 2^16 to a word, so a word stays below
+//     2^48; the global words take at most 2^31 * 1024 voxels: below 2^57;
+//   - contention: the four adds of a voxel go to four neighbouring words of one row, and on smooth volumes most lanes
+//     of a wave share b_f and k0: the cost of that against k_similarity's single add is measured, not bounded
+//     (profiles/microbench/affine_mi_rate_mi355x.txt, 512^3, one run): 0.847 ms on a lattice with a noise floor, 1.58 x
+//     k_similarity's 0.537 ms; 1.46 ms (B = 32) and 1.29 ms (B = 64) on a sum of wide Gaussians.  A weight of 0
+//     (r == 0: q[3]) is not added.
+// (256, 4): 111 - 126 VGPRs, four waves per SIMD, no scratch (the masked kernels keep 17 - 18 SGPRs in VGPR lanes).
+template <int LINEAR, bool MASKED>
+__global__ __launch_bounds__(256, 4) void k_parzen_hist(const MiArgs s)
+{
+    extern __shared__ __align__(16) unsigned char mi_lds[];
+    unsigned long long *h = reinterpret_cast<unsigned long long *>(mi_lds);
+    __shared__ unsigned long long cslot[4];
+    const GridArgs &p = s.a.g;
+    const int B = s.bins, BB = B * B;
+    for (int i = threadIdx.x; i < BB; i += 256)
+        h[i] = 0ull;
+    __syncthreads();
+    const int lx = threadIdx.x & 15;
+    unsigned long long cnt = 0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            break;
+        const bool row = y < p.oy && z < p.oz;
+        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+        const double yd = (double)y, zd = (double)z;
+        const double rx = pull_row(s.a.a, yd, zd), ry = pull_row(s.a.a + 4, yd, zd), rz = pull_row(s.a.a + 8, yd, zd);
+        Taps tp[4];
+        float f[4];
+        bool live[4];
+        float wf[4], wm[4];                                                  // MASKED only
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            live[k] = row && x < p.ox;
+            f[k] = 0.0f;
+            wf[k] = wm[k] = 1.0f;
+            if (live[k]) {
+                f[k] = s.a.F[orow + (size_t)x];
+                if (MASKED && s.a.w.wf)
+                    wf[k] = s.a.w.wf[orow + (size_t)x];
+            }
+            const double xd = (double)x;
+            const double qx = pull(s.a.a, xd, rx), qy = pull(s.a.a + 4, xd, ry), qz = pull(s.a.a + 8, xd, rz);
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
+            if (MASKED && s.a.w.wm)
+                wm[k] = s.a.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
+        }
+        float m[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            m[k] = gather<LINEAR>(p.src, tp[k], 0.0f);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool counted = MASKED ? live[k] && tp[k].in && mask_in(wf[k]) && mask_in(wm[k]) : live[k] && tp[k].in;
+            int k0, out;
+            uint32_t q[4];
+            double dw[4];
+            parzen_window(m[k], s.lo_m, s.s_m, B, &k0, q, dw, &out);
+            unsigned long long *w = h + parzen_fixed_bin(f[k], s.lo_f, s.s_f, B) * B + k0;      // k0 + 3 <= B - 1
+            if (counted) {
+                cnt += 1;
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (q[j])
+                        atomicAdd(w + j, (unsigned long long)q[j]);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < BB; i += 256) {
+        const unsigned long long c = h[i];
+        if (c)
+            atomicAdd(s.hist + i, c);
+    }
+    cnt = workgroup_reduce<Add>(cnt, cslot);
+    if (threadIdx.x == 0)
+        reinterpret_cast<unsigned long long *>(s.a.part)[blockIdx.x] = cnt;
+}
+
+// the count's partial slots 0 .. n-1 in finish_reduce's order (integers: any order gives the same)
+__global__ __launch_bounds__(256) void k_parzen_hist_finish(const unsigned long long *pcnt, unsigned n,
+                                                            unsigned long long *count)
+{
+    __shared__ unsigned long long s_cnt[256];
+    const unsigned long long c = finish_reduce<Add>(pcnt, n, s_cnt);
+    if (threadIdx.x == 0)
+        count[0] = c;
+}
+
+// The MI record: k_affine_normal's body, operation for operation, with G_d = psi * g_d and E = -1 (S_ee becomes
+// S_pp = sum psi psi), so the partial slots, the finish kernel (k_affine_normal_finish) and the record's layout are
+// that kernel's.  W comes into LDS once per workgroup (dynamic: B * B * 8 bytes, 32 KiB at B = 64, beside the 2.3 KiB
+// of slots: two workgroups per CU fit, as many as the registers allow).  psi of the lane's four outputs is formed right
+// after the gathers, before the accumulation block, so the window's temporaries are dead when the tile sums are live;
+// m and f are dead after it too.
+// Registers, as reported by -Rpass-analysis=kernel-resource-usage.  Written plainly the kernel spills 2 - 20 VGPRs at
+// (256, 2); two measures bring it to 256 VGPRs, two waves per SIMD and no scratch in <2, false>, <1, false> and
+// <2, true>: a scheduling barrier after each output's psi, so that the four windows' temporaries are not live together,
+// and the four `counted` flags kept as bits of one VGPR across the gathers instead of four lane masks (8 SGPRs; the
+// masked kernels keep 20 SGPRs in VGPR lanes, not in scratch).  <1, true> (masked, nx == 1: a moving volume one
+// voxel wide) still spills 4 VGPRs there and is bounded to one wave per SIMD instead: 256 VGPRs + 3 AGPRs, no scratch.
+// Measured (the same file): 1.15 ms per pass at 512^3 (B = 32; 1.17 ms at B = 64), 1.30 x k_affine_normal's 0.883 ms in
+// the same run, on either content.
+template <int LINEAR, bool MASKED>
+__global__ __launch_bounds__(256, LINEAR == 1 && MASKED ? 1 : 2) void k_affine_mi_normal(const MiArgs sm)
+{
+    extern __shared__ __align__(16) unsigned char mi_lds[];
+    const double *W = reinterpret_cast<const double *>(mi_lds);
+    __shared__ double slot[AFF_SUMS * 4];
+    __shared__ unsigned long long cslot[4];
+    const AffArgs &s = sm.a;
+    const GridArgs &p = s.g;
+    const int B = sm.bins;
+    {
+        double *Wl = reinterpret_cast<double *>(mi_lds);
+        for (int i = threadIdx.x; i < B * B; i += 256)
+            Wl[i] = sm.W[i];
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 15;
+    unsigned long long cnt = 0;
+    double see = 0.0;
+    double acc[AFF_H + AFF_B];
+#pragma unroll
+    for (int i = 0; i < AFF_H + AFF_B; i++)
+        acc[i] = 0.0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            break;
+        const bool row = y < p.oy && z < p.oz;
+        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+        const double yd = (double)y, zd = (double)z;
+        const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
+        // MASKED: as k_affine_normal's, the mask values first, kept as four flags
+        bool ok[4] = {true, true, true, true};
+        if (MASKED) {
+            float wf[4], wm[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int x = xt + lx + 16 * k;
+                const double xd = (double)x;
+                const double qx = pull(s.a, xd, rx), qy = pull(s.a + 4, xd, ry), qz = pull(s.a + 8, xd, rz);
+                wf[k] = s.w.wf && row && x < p.ox ? s.w.wf[orow + (size_t)x] : 1.0f;
+                wm[k] = s.w.wm ? s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                ok[k] = mask_in(wf[k]) && mask_in(wm[k]);
+        }
+        Taps tp[4];
+        float f[4];
+        bool live[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            live[k] = row && x < p.ox;
+            f[k] = live[k] ? s.F[orow + (size_t)x] : 0.0f;
+            const double xd = (double)x;
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry), pull(s.a + 8, xd, rz));
+        }
+        // which of the four outputs are counted, as bits of one register: kept as four lane masks across the gathers
+        // they cost eight SGPRs, and the masked kernels then spill
+        unsigned counted_bits = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            counted_bits |= (MASKED ? live[k] && tp[k].in && ok[k] : live[k] && tp[k].in) ? 1u << k : 0u;
+        float m[4], gx[4], gy[4], gz[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            m[k] = gather_grad<LINEAR>(p.src, tp[k], &gx[k], &gy[k], &gz[k]);
+        // psi = s_m * sum_k dw[k] W[b_f][k0 + k], 0 for a voxel outside the moving range or not counted
+        double psi[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool counted = counted_bits >> k & 1u;
+            int k0, out;
+            uint32_t q[4];
+            double dw[4];
+            parzen_window(m[k], sm.lo_m, sm.s_m, B, &k0, q, dw, &out);
+            const double *w = W + parzen_fixed_bin(f[k], sm.lo_f, sm.s_f, B) * B + k0;          // k0 + 3 <= B - 1
+            const double v = sm.s_m * (((dw[0] * w[0] + dw[1] * w[1]) + dw[2] * w[2]) + dw[3] * w[3]);
+            psi[k] = counted && !out ? v : 0.0;
+            __builtin_amdgcn_sched_barrier(0);                               // one window's temporaries at a time
+        }
+        const double Y = yd - s.cy, Z = zd - s.cz;
+        double s0[9], s1[9], s2[6];
+#pragma unroll
+        for (int i = 0; i < 9; i++)
+            s0[i] = s1[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+            s2[i] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool counted = counted_bits >> k & 1u;
+            const double E = counted ? -1.0 : 0.0;
+            const double G[3] = {psi[k] * (double)gx[k], psi[k] * (double)gy[k], psi[k] * (double)gz[k]};
+            const double X = (double)(xt + lx + 16 * k) - s.cx;
+            cnt += counted ? 1u : 0u;
+            see += psi[k] * psi[k];
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+#pragma unroll
+                for (int e2 = d; e2 < 3; e2++) {
+                    const int i = pair3(d, e2);
+                    const double w = G[d] * G[e2];
+                    const double wx = w * X;
+                    s0[i] += w;
+                    s1[i] += wx;
+                    s2[i] += wx * X;
+                }
+                const double w = G[d] * E;
+                s0[6 + d] += w;
+                s1[6 + d] += w * X;
+            }
+        }
+        const double YY = Y * Y, YZ = Y * Z, ZZ = Z * Z;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double *h = acc + 10 * i;
+            h[0] += s2[i];                                                   // X X
+            h[1] += s1[i] * Y;                                               // X Y
+            h[2] += s1[i] * Z;                                               // X Z
+            h[3] += s1[i];                                                   // X 1
+            h[4] += s0[i] * YY;
+            h[5] += s0[i] * YZ;
+            h[6] += s0[i] * Y;
+            h[7] += s0[i] * ZZ;
+            h[8] += s0[i] * Z;
+            h[9] += s0[i];
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            double *b = acc + AFF_H + 4 * d;
+            b[0] += s1[6 + d];
+            b[1] += s0[6 + d] * Y;
+            b[2] += s0[6 + d] * Z;
+            b[3] += s0[6 + d];
+        }
+    }
+    // as k_affine_normal: the wave by butterfly, then the four waves' values through LDS as ((w0 + w1) + w2) + w3
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int i = 0; i < AFF_SUMS; i++) {
+        const double v = wave_sum(i < AFF_H + AFF_B ? acc[i] : see);
+        if (lead)
+            slot[4 * i + wave] = v;
+    }
+    cnt = wave_sum(cnt);
+    if (lead)
+        cslot[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x < AFF_SUMS) {
+        const double *v = slot + 4 * threadIdx.x;
+        s.part[(size_t)threadIdx.x * AFF_GRID + blockIdx.x] = ((v[0] + v[1]) + v[2]) + v[3];
+    } else if (threadIdx.x == AFF_SUMS) {
+        reinterpret_cast<unsigned long long *>(s.part)[(size_t)AFF_SUMS * AFF_GRID + blockIdx.x] =
+            ((cslot[0] + cslot[1]) + cslot[2]) + cslot[3];
+    }
+}
+
 } // namespace
 
 // Launcher for sift3d_affine_refine.c, which has checked every argument (not exported from the library).  d_WF, d_WM:
@@ -592,6 +880,82 @@ extern "C" int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F,
         return SIFT3D_FAILURE;
 #endif
     hipLaunchKernelGGL(k_affine_ncc_finish, dim3(NCC_STATS), dim3(256), 0, st, (const double *)d_work, grid,
+                       (double *)d_record);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+// ---- Mattes mutual information: the launchers of sift3d_hip_parzen_hist_affine and sift3d_hip_affine_mi_normal_eqs ----
+static bool mi_args(MiArgs &m, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                    const double *A, int bins, float lo_f, float s_f, float lo_m, float hi_m, void *d_work,
+                    const float *d_WF, const float *d_WM)
+{
+    AffArgs &s = m.a;
+    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+        return false;
+    for (int i = 0; i < 12; i++)
+        s.a[i] = A[i];
+    s.cx = (double)(ox - 1) / 2.0;
+    s.cy = (double)(oy - 1) / 2.0;
+    s.cz = (double)(oz - 1) / 2.0;
+    s.F = d_F;
+    s.part = (double *)d_work;
+    s.w = MaskArgs{d_WF, d_WM};
+    m.bins = bins;
+    m.lo_f = lo_f;
+    m.s_f = s_f;
+    m.lo_m = lo_m;
+    m.s_m = parzen_scale(lo_m, hi_m, bins);
+    m.hist = nullptr;
+    m.W = nullptr;
+    return true;
+}
+
+// d_hist [bins][bins] and d_count are zeroed / written on the stream; d_work: SIFT3D_AMD_SIMILARITY_GRID counts
+extern "C" int sift3d_parzen_hist_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
+                                         int nx, int ny, int nz, const double *A, int bins, float lo_f, float s_f,
+                                         float lo_m, float hi_m, unsigned long long *d_hist,
+                                         unsigned long long *d_count, void *d_work, void *stream, const float *d_WF,
+                                         const float *d_WM)
+{
+    MiArgs m;
+    if (!mi_args(m, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m, d_work, d_WF, d_WM))
+        return launch_fail(fn, "grid too large");
+    m.hist = d_hist;
+    const unsigned grid = m.a.g.ntiles < AFF_GRID ? m.a.g.ntiles : AFF_GRID;
+    const bool masked = d_WF || d_WM, linear = nx >= 2;
+    void (*k)(const MiArgs) = masked ? (linear ? k_parzen_hist<2, true> : k_parzen_hist<1, true>)
+                                     : (linear ? k_parzen_hist<2, false> : k_parzen_hist<1, false>);
+    const size_t hb = (size_t)bins * bins * sizeof(unsigned long long);
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(d_hist, 0, hb, st));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), hb, st, m);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_parzen_hist_finish, dim3(1), dim3(256), 0, st, (const unsigned long long *)d_work, grid,
+                       d_count);
+    LAUNCH_CHECK();
+    return SIFT3D_SUCCESS;
+}
+
+// d_record is the MSD record's layout, d_work k_affine_normal's partial slots, d_W [bins][bins] doubles on the device
+extern "C" int sift3d_affine_mi_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
+                                              const float *d_M, int nx, int ny, int nz, const double *A, int bins,
+                                              float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
+                                              void *d_record, void *d_work, void *stream, const float *d_WF,
+                                              const float *d_WM)
+{
+    MiArgs m;
+    if (!mi_args(m, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m, d_work, d_WF, d_WM))
+        return launch_fail(fn, "grid too large");
+    m.W = d_W;
+    const unsigned grid = m.a.g.ntiles < AFF_GRID ? m.a.g.ntiles : AFF_GRID;
+    const bool masked = d_WF || d_WM, linear = nx >= 2;
+    void (*k)(const MiArgs) = masked ? (linear ? k_affine_mi_normal<2, true> : k_affine_mi_normal<1, true>)
+                                     : (linear ? k_affine_mi_normal<2, false> : k_affine_mi_normal<1, false>);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), (size_t)bins * bins * sizeof(double), st, m);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_affine_normal_finish, dim3(AFF_STATS), dim3(256), 0, st, (const double *)d_work, grid,
                        (double *)d_record);
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;

@@ -149,11 +149,26 @@ static void marginals(const uint64_t *hist, int B, uint64_t *r, uint64_t *c)
         }
 }
 
+/* the three entropies, mi and nmi of hist [B][B] with marginals r, c and total N > 0, in the header's order (shared with
+ * sift3d_amd_parzen_mi in sift3d_affine_refine.c) */
+static void entropy_measures(const uint64_t *hist, int B, const uint64_t *r, const uint64_t *c, uint64_t total,
+                             sift3d_amd_similarity *out)
+{
+    const double hf = entropy_of(r, (size_t)B, total);
+    const double hm = entropy_of(c, (size_t)B, total);
+    const double hfm = entropy_of(hist, (size_t)B * B, total);
+    out->entropy_fixed = hf;
+    out->entropy_moving = hm;
+    out->entropy_joint = hfm;
+    out->mi = (hf + hm) - hfm;
+    out->nmi = hfm == 0 ? 0.0 : (hf + hm) / hfm;
+}
+
 int sift3d_amd_similarity_measures(const uint64_t *hist, int bins, const void *stats, sift3d_amd_similarity *out)
 {
     static const char what[] = "sift3d_amd_similarity_measures";
     uint64_t r[SIFT3D_AMD_SIMILARITY_MAX_BINS], c[SIFT3D_AMD_SIMILARITY_MAX_BINS], n, total = 0;
-    double s[6], nd, vf, vm, hf, hm, hfm;
+    double s[6], nd, vf, vm;
     int i;
     if (!hist || !stats || !out)
         return refuse(what, "NULL argument");
@@ -175,14 +190,7 @@ int sift3d_amd_similarity_measures(const uint64_t *hist, int bins, const void *s
     vf = s[2] - s[0] * s[0] / nd;
     vm = s[3] - s[1] * s[1] / nd;
     out->ncc = vf <= 0 || vm <= 0 ? 0.0 : (s[4] - s[0] * s[1] / nd) / sqrt(vf * vm);
-    hf = entropy_of(r, (size_t)bins, total);
-    hm = entropy_of(c, (size_t)bins, total);
-    hfm = entropy_of(hist, (size_t)bins * bins, total);
-    out->entropy_fixed = hf;
-    out->entropy_moving = hm;
-    out->entropy_joint = hfm;
-    out->mi = (hf + hm) - hfm;
-    out->nmi = hfm == 0 ? 0.0 : (hf + hm) / hfm;
+    entropy_measures(hist, bins, r, c, total, out);
     return SIFT3D_SUCCESS;
 }
 

@@ -4,6 +4,7 @@ Device buffers are torch tensors on the current HIP device (torch is only the al
 stream / process-group plumbing); every call takes raw device pointers and runs on torch's
 current stream, so results are ordered with other torch work on that stream.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -66,6 +67,11 @@ AFFINE_NCC_BYTES = 1488
 class AffineRefineResult(C.Structure):                     # sift3d_amd_affine_refine_result
     _fields_ = [("A", C.c_double * 12), ("evaluations", C.c_int), ("stop", C.c_int),
                 ("trail", AffineEvaluation * (AFFINE_MAX_LEVELS * AFFINE_MAX_EVALUATIONS))]
+
+
+class Similarity(C.Structure):                             # sift3d_amd_similarity
+    _fields_ = [("n", C.c_uint64), ("msd", C.c_double), ("ncc", C.c_double), ("mi", C.c_double), ("nmi", C.c_double),
+                ("entropy_fixed", C.c_double), ("entropy_moving", C.c_double), ("entropy_joint", C.c_double)]
 
 
 class FFDRefineParams(C.Structure):                        # sift3d_amd_ffd_refine_params
@@ -212,6 +218,23 @@ def lib():
                                                           C.POINTER(AffineRefineParams),
                                                           C.POINTER(AffineRefineResult), C.POINTER(C.c_double), vp,
                                                           vp, vp, vp]),
+        "sift3d_amd_parzen_window": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+        "sift3d_amd_parzen_hist_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+        "sift3d_hip_parzen_hist_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float, C.c_float,
+                                                    C.c_float, vp, vp, vp, vp, vp, vp]),
+        "sift3d_amd_parzen_mi": (C.c_int, [vp, C.c_int, C.POINTER(Similarity), vp]),
+        "sift3d_hip_affine_mi_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float,
+                                                      C.c_float, C.c_float, vp, vp, vp, vp, vp, vp]),
+        "sift3d_amd_affine_mi_refine_work_bytes": (C.c_size_t, [C.c_int] * 7),
+        "sift3d_amd_affine_mi_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                         C.c_int, C.POINTER(C.c_double), C.c_int, C.c_float,
+                                                         C.c_float, C.c_float, C.c_float,
+                                                         C.POINTER(AffineRefineParams),
+                                                         C.POINTER(AffineRefineResult), C.POINTER(Similarity), vp,
+                                                         vp, vp, vp]),
         "sift3d_amd_ffd_lattice_dim": (C.c_int, [C.c_int, C.c_int]),
         "sift3d_amd_ffd_weights": (C.c_int, [C.c_int, vp]),
         "sift3d_amd_ffd_field_work_bytes": (C.c_size_t, [C.c_int] * 3),
@@ -927,6 +950,147 @@ def affine_ncc_refine(F, M, A, params=None, work=None, mask_fixed=None, mask_mov
                                                      current_stream(), *masks),
            "sift3d_amd_affine_ncc_refine_device")
     return res, fit
+
+
+
+# ---- Mattes mutual-information affine refinement (contract: "Mutual-information affine refinement (Mattes)") ---------
+PARZEN_MAX_BINS = 64
+PARZEN_Q = 65536
+ParzenMeasures = collections.namedtuple("ParzenMeasures", "n mi nmi entropy_fixed entropy_moving entropy_joint cost W")
+
+
+def _parzen_bins(bins, what):
+    bins = int(bins)
+    if not 4 <= bins <= PARZEN_MAX_BINS:
+        raise ValueError("%s: bins must be in [4, %d]" % (what, PARZEN_MAX_BINS))
+    return bins
+
+
+def _parzen_ranges(range_f, range_m):
+    return tuple(float(np.float32(v)) for r in (range_f, range_m) for v in r)
+
+
+def parzen_window(m, lo, hi, bins):
+    """(k0, q uint32 [4], dw float64 [4], out) of sift3d_amd_parzen_window (host): the first of the four bins that the
+    moving value m is spread over, the cubic B-spline weights in fixed point (2^16), their derivatives and whether m
+    lies outside [lo, hi]; None where the entry refuses (bins outside [4, 64], a range that is not finite or empty)."""
+    k0, out = C.c_int(), C.c_int()
+    q = (C.c_uint32 * 4)()
+    dw = (C.c_double * 4)()
+    rc = lib().sift3d_amd_parzen_window(float(np.float32(m)), float(np.float32(lo)), float(np.float32(hi)), int(bins),
+                                        C.byref(k0), q, dw, C.byref(out))
+    return (k0.value, np.array(q[:], np.uint32), np.array(dw[:], np.float64), bool(out.value)) if rc == 0 else None
+
+
+def parzen_histogram(F, M, A, bins, range_f, range_m, hist=None, work=None, mask_fixed=None, mask_moving=None):
+    """The Parzen joint histogram in fixed point of the fixed volume F [oz, oy, ox] and the moving volume M [nz, ny, nx]
+    seen through the 3 x 4 pull map A (sift3d_hip_parzen_hist_affine), torch CUDA float32 contiguous, on torch's current
+    stream.  Returns (hist int64 [bins, bins] indexed [b_f, b_m], count int64 [1]) on the device; reading either waits
+    for the stream.  hist, work: the caller's buffers (int64 [bins, bins]; sift3d_amd_parzen_hist_work_bytes bytes).
+    mask_fixed, mask_moving: as similarity's."""
+    import torch
+    what = "parzen_histogram"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    a = _affine12(A, what)
+    bins = _parzen_bins(bins, what)
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    if hist is None:
+        hist = torch.empty((bins, bins), dtype=torch.int64, device=F.device)
+    _tensor(hist, what + ": hist must be a contiguous int64 CUDA tensor [bins, bins] on F's device",
+            shape=(bins, bins), device=F.device, dtype="int64")
+    count = torch.empty(1, dtype=torch.int64, device=F.device)
+    need = lib().sift3d_amd_parzen_hist_work_bytes(ox, oy, oz)
+    work = _work(work, (need + 3) // 4, F, what)
+    _check(lib().sift3d_hip_parzen_hist_affine(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a), bins,
+                                               *_parzen_ranges(range_f, range_m), hist.data_ptr(), count.data_ptr(),
+                                               work.data_ptr(), current_stream(), *masks),
+           "sift3d_hip_parzen_hist_affine")
+    return hist, count
+
+
+def parzen_mi(hist):
+    """ParzenMeasures(n, mi, nmi, entropy_fixed, entropy_moving, entropy_joint, cost, W) of sift3d_amd_parzen_mi (host)
+    on a histogram [bins, bins] (a tensor is copied to the host, which waits for its stream): n the histogram's total,
+    cost = -mi, W float64 [bins, bins] the table log(hist / column sum) that affine_mi_normal_equations takes."""
+    if hasattr(hist, "cpu"):
+        hist = hist.cpu().numpy()
+    h = np.ascontiguousarray(hist).astype(np.uint64)
+    if h.ndim != 2 or h.shape[0] != h.shape[1]:
+        raise ValueError("parzen_mi: hist must be [bins, bins]")
+    bins = _parzen_bins(h.shape[0], "parzen_mi")
+    out = Similarity()
+    W = np.zeros((bins, bins))
+    _check(lib().sift3d_amd_parzen_mi(h.ctypes.data, bins, C.byref(out), W.ctypes.data), "sift3d_amd_parzen_mi")
+    return ParzenMeasures(int(out.n), out.mi, out.nmi, out.entropy_fixed, out.entropy_moving, out.entropy_joint,
+                          -out.mi, W)
+
+
+def affine_mi_normal_equations(F, M, A, W, range_f, range_m, record=None, work=None, raw=False, mask_fixed=None,
+                               mask_moving=None):
+    """The Fisher-scoring normal equations of the mutual information over A's 12 parameters
+    (sift3d_hip_affine_mi_normal_eqs): the MSD record with the pseudo-gradient psi * g and the pseudo-residual -1, psi
+    from the table W [bins, bins] (float64; a numpy array is uploaded, a CUDA tensor is used as it is).  Returns
+    (n, S_pp, b [12], H [12, 12]) on the host as affine_normal_equations does, or with raw=True the device record.
+    record, work: the caller's buffers (int64 [158]; sift3d_amd_affine_normal_work_bytes bytes).  mask_fixed,
+    mask_moving: as similarity's."""
+    import torch
+    what = "affine_mi_normal_equations"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    a = _affine12(A, what)
+    if not isinstance(W, torch.Tensor):
+        W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(F.device)
+    if W.dim() != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError(what + ": W must be [bins, bins]")
+    bins = _parzen_bins(W.shape[0], what)
+    _tensor(W, what + ": W must be a contiguous float64 tensor [bins, bins] on F's device", shape=(bins, bins),
+            device=F.device, dtype="float64")
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    if record is None:
+        record = torch.empty(AFFINE_NORMAL_BYTES // 8, dtype=torch.int64, device=F.device)
+    _tensor(record, what + ": record must be a contiguous int64 CUDA tensor [158] on F's device",
+            shape=(AFFINE_NORMAL_BYTES // 8,), device=F.device, dtype="int64")
+    need = lib().sift3d_amd_affine_normal_work_bytes(ox, oy, oz)
+    work = _work(work, (need + 3) // 4, F, what)
+    _check(lib().sift3d_hip_affine_mi_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a), bins,
+                                                 *_parzen_ranges(range_f, range_m), W.data_ptr(), record.data_ptr(),
+                                                 work.data_ptr(), current_stream(), *masks),
+           "sift3d_hip_affine_mi_normal_eqs")
+    return record if raw else affine_normal_record(record)
+
+
+def affine_mi_refine(F, M, A, bins, range_f, range_m, params=None, work=None, mask_fixed=None, mask_moving=None):
+    """sift3d_amd_affine_mi_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
+    waits for it once per pass).  Returns (AffineRefineResult, Similarity: the measures at the final A, n the
+    histogram's total).  mask_fixed, mask_moving: as similarity's."""
+    what = "affine_mi_refine"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    a = _affine12(A, what)
+    bins = _parzen_bins(bins, what)
+    p = params if params is not None else affine_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    need = lib().sift3d_amd_affine_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, p.levels)
+    if need == 0:
+        raise ValueError(what + ": levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
+    work = _work(work, (need + 3) // 4, F, what)
+    res = AffineRefineResult()
+    sim = Similarity()
+    _check(lib().sift3d_amd_affine_mi_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a), bins,
+                                                    *_parzen_ranges(range_f, range_m), C.byref(p), C.byref(res),
+                                                    C.byref(sim), work.data_ptr(), current_stream(), *masks),
+           "sift3d_amd_affine_mi_refine_device")
+    return res, sim
 
 
 # ---- B-spline free-form deformation (contract: include/sift3d_amd.h, "B-spline free-form deformation") ----
