@@ -1047,6 +1047,85 @@ sift3d_amd_affine_mi_refine_device(const float *d_F, int ox, int oy, int oz, con
                                    void *d_work, void *stream, const float *d_WF, const float *d_WM);
 
 /* ------------------------------------------------------------------------ */
+/* Mutual-information free-form deformation (Mattes)                         */
+/* ------------------------------------------------------------------------ */
+/* "B-spline free-form deformation" for two volumes whose intensities are related by an unknown map that need not be
+ * monotone: the lattice is moved towards a larger mutual information of "Mutual-information affine refinement
+ * (Mattes)", plus the same bending penalty.  The lattice, the weight table, the spline value, the field export, the
+ * bending energy, the subdivision and the masks are those of "B-spline free-form deformation" and "Masks", word for
+ * word; bins, the two ranges, the fixed bin, the moving window (sift3d_parzen.h), the fixed-point histogram and
+ * sift3d_amd_parzen_mi are those of "Mutual-information affine refinement (Mattes)", word for word.  No upstream
+ * counterpart: PARITY UNPINNED, pinned to this contract and its numpy restatement (tests/ffd_mi_restatement.py).
+ *
+ * Histogram through a field (sift3d_hip_parzen_hist_field).  sift3d_hip_parzen_hist_affine with d_field[3][oz][oy][ox]
+ * in the place of A: the sample point q = p + u(p), the inside test and the LINEAR sample m are sift3d_hip_warp_field's,
+ * bit for bit; a non-finite field entry is outside, as in sift3d_hip_similarity_field_masked.  Bins, ranges, the window,
+ * the fixed-point adds and the 64-bit workgroup-private counters are the affine entry's, word for word; so are the grid,
+ * the merge, the zeroing of both outputs, the masks, checks (d_field a 4-byte aligned input that no output may
+ * overlap), alignment, overlap rules and work size (sift3d_amd_parzen_hist_work_bytes).  hist and count are exact
+ * integers: a function of the inputs alone.
+ *
+ * MI evaluation (sift3d_hip_ffd_mi_evaluate).  The arguments of sift3d_hip_ffd_evaluate_masked, then bins, the two
+ * ranges and d_W [B][B] double on the device (8-byte aligned; sift3d_amd_parzen_mi's table).  The call exports the field
+ * of the lattice to d_field, then per counted fixed voxel (the masked evaluation's test, word for word), with m, g as
+ * there and b_f, k0, dw, out as in the affine section, in double, unfused:
+ *     psi  = out ? 0.0 : s_m * (((dw[0] * W0 + dw[1] * W1) + dw[2] * W2) + dw[3] * W3),   Wk = W[b_f][k0 + k]
+ *     G'_d = psi * (double) g_d,   E = -1
+ * The record has the layout of the FFD record (sift3d_amd_ffd_record_bytes):
+ *     uint64 n;  double S_pp = sum psi psi;  double R;  double gmax;
+ *     double Gc[3][gz][gy][gx] = sum_p W(p; k, j, i) E G'_d;  double dR[3][gz][gy][gx]
+ * n is the count: a voxel with `out` is counted, with psi = 0, so n equals the histogram's count on the same inputs.  R,
+ * dR and gmax are "B-spline free-form deformation"'s.  The rule for everything after the histogram is that section's: a
+ * function of the shapes only, no atomics, every partial slot reduced in a fixed order; a call repeats its bytes.  The
+ * force E G'_d = -(psi * g_d) carries one rounding where E G_d was exact (the sign is exact), so every entry of Gc is
+ * within gamma_(k + 9) sum |term| of the exact sum of the terms W(p; k, j, i) (-(psi g_d)) in double, k the number of
+ * voxels in the control's support; S_pp within gamma_(n + 1) sum psi psi.
+ * Gradient.  d_grad = (float)((1.0 / n) * Gc + bending * dR), formed in double; the cost is -mi + bending * R.  The
+ * factor is 1 / n, not the MSD's 2 / n: with p(b_m | b_f) read off the histogram, -mi is, up to the entropy of the fixed
+ * marginal and a term that does not depend on the lattice to first order, -(1 / n) sum_p log p(m(p) | f(p)); moving a
+ * control by dc moves m(p) by W(p) g_d dc, the window's weights by s_m dw[k] W(p) g_d dc, and the mean log-likelihood
+ * by (1 / n) sum_p W(p) psi g_d dc, so d(-mi) / dc = (1 / n) sum_p W(p) (-1)(psi g_d) = Gc / n.  (A constant added to a
+ * row of W drops out because sum_k dw[k] = 0: the partition of unity of the window, as in the affine section; that
+ * is why W = log(hist / column sum) may stand for log p(b_m | b_f), which differs from it by the row's log-total.)
+ *
+ * Driver (sift3d_amd_ffd_mi_refine_device).  sift3d_amd_ffd_refine_masked_device's arguments, then bins, the two ranges
+ * and mi_out.  sift3d_amd_ffd_refine_device's loop, levels, subdivision, step rule and stop reasons, one loop in the
+ * code too, with cost E = -mi + bending * R.  An evaluation is the field, the histogram pass and the bending value; the
+ * histogram, the count and the head go to the host (one wait) and sift3d_amd_parzen_mi gives -mi and W; its n is the
+ * count.  The force, adjoint, bending-gradient and combine passes run only at the lattice the next step starts from (a
+ * level's first lattice and each accepted trial that does not end the level): one copy of W to the device, the passes
+ * and one more wait, for gmax.  A rejected trial costs the field, the histogram and the bending value alone.  An
+ * evaluation with N == 0 has no cost: as a trial it is rejected (s = s / 2), as a level's first evaluation it stops the
+ * level with FAILED.  Ranges and bins are level 0's on every level.  Params and result are the existing structs; the
+ * trail's `msd` field carries -mi.  mi_out: the measures at the final lattice on level 0 (all NaN and n = 0 when no
+ * evaluation was made).  Checks are the masked FFD driver's, then bins and ranges; mi_out must not be NULL.
+ * d_work: sift3d_amd_ffd_mi_refine_work_bytes() bytes, whatever `bins` is: the masked FFD driver's layout, then the
+ * histogram, the count and W. */
+/* d_F [oz][oy][ox], d_M [nz][ny][nx], d_field [3][oz][oy][ox], d_hist [bins][bins] uint64, d_count one uint64 */
+SIFT3D_AMD_API int
+sift3d_hip_parzen_hist_field(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                             const float *d_field, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                             uint64_t *d_hist, uint64_t *d_count, void *d_work, void *stream, const float *d_WF,
+                             const float *d_WM);
+/* d_work: sift3d_amd_ffd_evaluate_work_bytes() bytes */
+SIFT3D_AMD_API int
+sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                           const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                           const double *A /*12 or NULL*/, double bending, float *d_field, void *d_record,
+                           float *d_grad, void *d_work, void *stream, const float *d_WF, const float *d_WM, int bins,
+                           float lo_f, float hi_f, float lo_m, float hi_m, const double *d_W);
+/* bytes of d_work for the driver (0 for bad arguments) */
+SIFT3D_AMD_API size_t
+sift3d_amd_ffd_mi_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz, int levels);
+/* A [12] on the host or NULL; mi_out on the host; waits for `stream` once per evaluation and once per gradient */
+SIFT3D_AMD_API int
+sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                const double *A, const sift3d_amd_ffd_refine_params *params,
+                                sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
+                                void *stream, const float *d_WF, const float *d_WM, int bins, float lo_f, float hi_f,
+                                float lo_m, float hi_m, sift3d_amd_similarity *mi_out);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -1147,6 +1147,7 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
 FFDRefinement = collections.namedtuple("FFDRefinement", "lattice spacing A field warped trail stop jacobian")
 FFDEvaluation = collections.namedtuple("FFDEvaluation", "E msd R n step accepted level")
 FFDRegistration = collections.namedtuple("FFDRegistration", "registration refinement")
+MiFFDRefinement = collections.namedtuple("MiFFDRefinement", FFDRefinement._fields + ("mi", "nmi", "bins"))
 
 
 def _ffd_lattice_tensor(lattice, what):
@@ -1193,7 +1194,8 @@ def ffd_bending_energy(lattice, spacing):
     return hip.ffd_bending(L, hip.ffd_spacing(spacing, "ffd_bending_energy"))
 
 
-def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None, **params):
+def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None,
+               metric="msd", bins=None, range_fixed=None, range_moving=None, **params):
     """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
     `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
     include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
@@ -1204,8 +1206,31 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     FFDRefinement(lattice [3, gz, gy, gx], spacing (dx, dy, dz), A, field [3, oz, oy, ox], warped: `moving` through the
     field, trail: one FFDEvaluation(E, msd, R, n, step, accepted, level) per evaluation in the order run, stop:
     "converged", "evaluations", "flat" or "failed" of level 0, jacobian: JacobianStats of the field).  Waits for
-    torch's current stream once per evaluation."""
+    torch's current stream once per evaluation.
+    metric="mi" maximises the Mattes mutual information instead (contract: "Mutual-information free-form deformation
+    (Mattes)"; cost -mi + bending * R), for volumes whose intensities are related by an unknown map that need not be
+    monotone, where the MSD fit is wrong.  bins (None: 32; 4 .. 64) and range_fixed, range_moving ((lo, hi); None: the
+    volume's own min and max, one host synchronisation each) set the histogram as in refine_affine and are level 0's on
+    every level.  It returns MiFFDRefinement: FFDRefinement's fields (each trail entry's `msd` holds -mi), then mi and
+    nmi at the final lattice and bins; `warped` is not remapped.  `bending` keeps its default of 0.005 for either
+    metric: the value was chosen for the MSD of volumes of unit-order intensity, and no calibration of it against -mi
+    (which is of order 1 whatever the intensities) is claimed.  bins or a range with metric="msd", and any other
+    metric, raise ValueError."""
     from . import hip
+    if metric not in ("msd", "mi"):
+        raise ValueError("refine_ffd: metric must be 'msd' or 'mi', not %r" % (metric,))
+    if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
+        raise ValueError("refine_ffd: bins, range_fixed and range_moving belong to metric='mi', not %r" % (metric,))
+    if metric == "mi":
+        bins = MI_BINS if bins is None else bins
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or \
+                not 4 <= int(bins) <= hip.PARZEN_MAX_BINS:
+            raise ValueError("refine_ffd: bins must be in [4, %d]" % hip.PARZEN_MAX_BINS)
+        for r, name in ((range_fixed, "range_fixed"), (range_moving, "range_moving")):
+            if r is not None:
+                lo, hi = (float(np.float32(v)) for v in r)
+                if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+                    raise ValueError("refine_ffd: %s must be finite with lo < hi" % name)
     d = hip.ffd_spacing(spacing, "refine_ffd")
     if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
             not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
@@ -1226,20 +1251,29 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
     WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
-    res, lattice, field = hip.ffd_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
+    if metric == "mi":
+        res, lattice, field, sim = hip.ffd_mi_refine(F, M, int(bins), _own_range(F, range_fixed),
+                                                     _own_range(M, range_moving), A0, p, mask_fixed=WF, mask_moving=WM)
+    else:
+        res, lattice, field = hip.ffd_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     trail = [FFDEvaluation(e.E, e.msd, e.R, int(e.n), e.step, bool(e.accepted), e.level)
              for e in res.trail[:res.evaluations]]
-    return FFDRefinement(lattice, d, A0, field, warp_field(M, field), trail, hip.FFD_STOPS[res.stop],
-                         jacobian_determinant(field))
+    out = FFDRefinement(lattice, d, A0, field, warp_field(M, field), trail, hip.FFD_STOPS[res.stop],
+                        jacobian_determinant(field))
+    if metric == "mi":
+        return MiFFDRefinement(*out, mi=float(sim.mi), nmi=float(sim.nmi), bins=int(bins))
+    return out
 
 
 def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
                  ffd_params=None, refine=True, **detector_kw):
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
-    refine_ffd's further keyword arguments; refine: True, or register's dict of refine_affine's keyword arguments
-    (dict(metric="ncc") or dict(metric="mi") for the affine stage; the FFD stage itself minimises the MSD).  The volumes are torch CUDA float32 tensors, or Images / arrays, which are
-    uploaded.  Returns FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""
+    refine_ffd's further keyword arguments (dict(metric="mi") for a mutual-information FFD stage, which then returns
+    a MiFFDRefinement); refine: True, or register's dict of refine_affine's keyword arguments (dict(metric="ncc") or
+    dict(metric="mi") for the affine stage).  The two stages' metrics are chosen separately; either defaults to the
+    MSD.  The volumes are torch CUDA float32 tensors, or Images / arrays, which are uploaded.  Returns
+    FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""
     F = _similarity_volume(fixed, "register_ffd", "fixed")
     M = _similarity_volume(moving, "register_ffd", "moving", F.device)
     reg = register(M, F, nn_thresh, err_thresh, num_iter, seed, refine=refine if isinstance(refine, dict) else True,

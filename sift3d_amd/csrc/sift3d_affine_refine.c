@@ -17,9 +17,9 @@ int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F, int ox, in
                                     const float *d_WF, const float *d_WM);
 
 int sift3d_parzen_hist_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
-                              int nz, const double *A, int bins, float lo_f, float s_f, float lo_m, float hi_m,
-                              unsigned long long *d_hist, unsigned long long *d_count, void *d_work, void *stream,
-                              const float *d_WF, const float *d_WM);
+                              int nz, const double *A, const float *d_field, int bins, float lo_f, float s_f,
+                              float lo_m, float hi_m, unsigned long long *d_hist, unsigned long long *d_count, void *d_work,
+                              void *stream, const float *d_WF, const float *d_WM);
 
 int sift3d_affine_mi_normal_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                                    int ny, int nz, const double *A, int bins, float lo_f, float s_f, float lo_m,
@@ -132,32 +132,58 @@ size_t sift3d_amd_parzen_hist_work_bytes(int ox, int oy, int oz)
     return PARZEN_HIST_WORK_BYTES;
 }
 
+/* the shared body of the two entries: the pull map is A, or with A == NULL the field d_field [3][oz][oy][ox] */
+static int parzen_hist(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                       int nz, const double *A, const float *d_field, int bins, float lo_f, float hi_f, float lo_m,
+                       float hi_m, uint64_t *d_hist, uint64_t *d_count, void *d_work, void *stream, const float *d_WF,
+                       const float *d_WM)
+{
+    float s_f;
+    if (!d_F || !d_M || (!A && !d_field) || !d_hist || !d_count || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) ||
+        parzen_check(what, bins, lo_f, hi_f, lo_m, hi_m, &s_f) || (A && check_affine(what, A)) ||
+        check_aligned(what, ADDR(d_hist) | ADDR(d_count) | ADDR(d_work),
+                      ADDR(d_F) | ADDR(d_M) | ADDR(d_field) | ADDR(d_WF) | ADDR(d_WM)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 },
+                               { d_field, d_field ? field_bytes(ox, oy, oz) : 0 } };
+        const range_t out[] = { { d_hist, (size_t)bins * bins * sizeof(uint64_t) }, { d_count, sizeof(uint64_t) },
+                                { d_work, PARZEN_HIST_WORK_BYTES } };
+        if (ranges_aliased(out, 3, in, 5))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_parzen_hist_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_field, bins, lo_f, s_f, lo_m, hi_m,
+                                     (unsigned long long *)d_hist, (unsigned long long *)d_count, d_work, stream,
+                                     d_WF, d_WM);
+}
+
 int sift3d_hip_parzen_hist_affine(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
                                   const double *A, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
                                   uint64_t *d_hist, uint64_t *d_count, void *d_work, void *stream, const float *d_WF,
                                   const float *d_WM)
 {
     static const char what[] = "sift3d_hip_parzen_hist_affine";
-    float s_f;
-    if (!d_F || !d_M || !A || !d_hist || !d_count || !d_work)
+    if (!A)
         return refuse(what, "NULL argument");
-    if (check_dims(what, ox, oy, oz) || check_dims(what, nx, ny, nz) ||
-        parzen_check(what, bins, lo_f, hi_f, lo_m, hi_m, &s_f) || check_affine(what, A) ||
-        check_aligned(what, ADDR(d_hist) | ADDR(d_count) | ADDR(d_work),
-                      ADDR(d_F) | ADDR(d_M) | ADDR(d_WF) | ADDR(d_WM)))
-        return SIFT3D_FAILURE;
-    {
-        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
-                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
-                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
-        const range_t out[] = { { d_hist, (size_t)bins * bins * sizeof(uint64_t) }, { d_count, sizeof(uint64_t) },
-                                { d_work, PARZEN_HIST_WORK_BYTES } };
-        if (ranges_aliased(out, 3, in, 4))
-            return refuse(what, ALIASED);
-    }
-    return sift3d_parzen_hist_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m,
-                                     (unsigned long long *)d_hist, (unsigned long long *)d_count, d_work, stream,
-                                     d_WF, d_WM);
+    return parzen_hist(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A, NULL, bins, lo_f, hi_f, lo_m, hi_m, d_hist, d_count,
+                       d_work, stream, d_WF, d_WM);
+}
+
+/* "Mutual-information free-form deformation (Mattes)": the same histogram with the sample point of a field */
+int sift3d_hip_parzen_hist_field(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const float *d_field, int bins, float lo_f, float hi_f, float lo_m, float hi_m,
+                                 uint64_t *d_hist, uint64_t *d_count, void *d_work, void *stream, const float *d_WF,
+                                 const float *d_WM)
+{
+    static const char what[] = "sift3d_hip_parzen_hist_field";
+    if (!d_field)
+        return refuse(what, "NULL argument");
+    return parzen_hist(what, d_F, ox, oy, oz, d_M, nx, ny, nz, NULL, d_field, bins, lo_f, hi_f, lo_m, hi_m, d_hist,
+                       d_count, d_work, stream, d_WF, d_WM);
 }
 
 int sift3d_amd_parzen_mi(const uint64_t *hist, int bins, sift3d_amd_similarity *out, double *W)

@@ -534,6 +534,7 @@ struct MiArgs {
     double s_m;                                  // parzen_scale(lo_m, hi_m, bins)
     unsigned long long *hist;                    // histogram pass: [bins][bins], zeroed by the launcher
     const double *W;                             // record pass: [bins][bins]
+    const float *field;                          // histogram pass, FIELD == true: [3][oz][oy][ox]
 };
 
 // The Parzen joint histogram in fixed point.  k_similarity without the moments: per counted voxel four integer adds
@@ -550,8 +551,18 @@ struct MiArgs {
 //     k_similarity's 0.537 ms; 1.46 ms (B = 32) and 1.29 ms (B = 64) on a sum of wide Gaussians.  A weight of 0
 //     (r == 0: q[3]) is not added.
 // (256, 4): 111 - 126 VGPRs, four waves per SIMD, no scratch (the masked kernels keep 17 - 18 SGPRs in VGPR lanes).
-template <int LINEAR, bool MASKED>
-__global__ __launch_bounds__(256, 4) void k_parzen_hist(const MiArgs s)
+// FIELD (header, "Mutual-information free-form deformation (Mattes)"): the sample point is k_warp_field's and
+// k_ffd_force's, q = p + u(p) with u read from s.field (three more coalesced loads per voxel in the place of pull()'s
+// arithmetic; a lane past the grid reads nothing and takes u = 0); everything after q is the same code.  115 - 126
+// VGPRs, four waves per SIMD, no scratch, but <1, false, true> (unmasked, nx == 1), which spills 4 VGPRs there and is
+// bounded to three waves instead (132 VGPRs, no scratch).  FIELD == false compiles to what it compiled to before the
+// parameter existed (the same resource usage and the same code size, function by function).  Measured
+// (profiles/microbench/ffd_mi_rate_mi355x.txt, 512^3, kernel trace, min of 5, one run, the field being the export of
+// the same affine map): 1.004 - 1.014 ms on the lattice with a noise floor, 1.16 x the affine kernel's 0.862 -
+// 0.874 ms (12 B more read per voxel); 1.50 ms (B = 32) and 1.34 ms (B = 64) on the sum of wide Gaussians, 1.04 -
+// 1.05 x: there the contended LDS adds set the time, not the loads.  (Spread of a kernel over its 5 calls: 1 - 3 %.)
+template <int LINEAR, bool MASKED, bool FIELD = false>
+__global__ __launch_bounds__(256, FIELD && LINEAR == 1 && !MASKED ? 3 : 4) void k_parzen_hist(const MiArgs s)
 {
     extern __shared__ __align__(16) unsigned char mi_lds[];
     unsigned long long *h = reinterpret_cast<unsigned long long *>(mi_lds);
@@ -562,6 +573,7 @@ __global__ __launch_bounds__(256, 4) void k_parzen_hist(const MiArgs s)
         h[i] = 0ull;
     __syncthreads();
     const int lx = threadIdx.x & 15;
+    const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;             // FIELD only
     unsigned long long cnt = 0;
     for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
         int xt, y, z;
@@ -570,7 +582,8 @@ __global__ __launch_bounds__(256, 4) void k_parzen_hist(const MiArgs s)
         const bool row = y < p.oy && z < p.oz;
         const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
         const double yd = (double)y, zd = (double)z;
-        const double rx = pull_row(s.a.a, yd, zd), ry = pull_row(s.a.a + 4, yd, zd), rz = pull_row(s.a.a + 8, yd, zd);
+        const double rx = FIELD ? 0.0 : pull_row(s.a.a, yd, zd), ry = FIELD ? 0.0 : pull_row(s.a.a + 4, yd, zd);
+        const double rz = FIELD ? 0.0 : pull_row(s.a.a + 8, yd, zd);
         Taps tp[4];
         float f[4];
         bool live[4];
@@ -579,15 +592,24 @@ __global__ __launch_bounds__(256, 4) void k_parzen_hist(const MiArgs s)
         for (int k = 0; k < 4; k++) {
             const int x = xt + lx + 16 * k;
             live[k] = row && x < p.ox;
+            float ux = 0.0f, uy = 0.0f, uz = 0.0f;                               // FIELD only
             f[k] = 0.0f;
             wf[k] = wm[k] = 1.0f;
             if (live[k]) {
+                if (FIELD) {
+                    const float *u = s.field + orow + (size_t)x;
+                    ux = u[0];
+                    uy = u[ovox];
+                    uz = u[2 * ovox];
+                }
                 f[k] = s.a.F[orow + (size_t)x];
                 if (MASKED && s.a.w.wf)
                     wf[k] = s.a.w.wf[orow + (size_t)x];
             }
             const double xd = (double)x;
-            const double qx = pull(s.a.a, xd, rx), qy = pull(s.a.a + 4, xd, ry), qz = pull(s.a.a + 8, xd, rz);
+            const double qx = FIELD ? xd + (double)ux : pull(s.a.a, xd, rx);
+            const double qy = FIELD ? yd + (double)uy : pull(s.a.a + 4, xd, ry);
+            const double qz = FIELD ? zd + (double)uz : pull(s.a.a + 8, xd, rz);
             tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
             if (MASKED && s.a.w.wm)
                 wm[k] = s.a.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
@@ -886,6 +908,7 @@ extern "C" int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F,
 }
 
 // ---- Mattes mutual information: the launchers of sift3d_hip_parzen_hist_affine and sift3d_hip_affine_mi_normal_eqs ----
+// A == NULL: the histogram through a field (the pull map is not read)
 static bool mi_args(MiArgs &m, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
                     const double *A, int bins, float lo_f, float s_f, float lo_m, float hi_m, void *d_work,
                     const float *d_WF, const float *d_WM)
@@ -894,7 +917,7 @@ static bool mi_args(MiArgs &m, const float *d_F, int ox, int oy, int oz, const f
     if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
         return false;
     for (int i = 0; i < 12; i++)
-        s.a[i] = A[i];
+        s.a[i] = A ? A[i] : 0.0;
     s.cx = (double)(ox - 1) / 2.0;
     s.cy = (double)(oy - 1) / 2.0;
     s.cz = (double)(oz - 1) / 2.0;
@@ -908,12 +931,16 @@ static bool mi_args(MiArgs &m, const float *d_F, int ox, int oy, int oz, const f
     m.s_m = parzen_scale(lo_m, hi_m, bins);
     m.hist = nullptr;
     m.W = nullptr;
+    m.field = nullptr;
     return true;
 }
 
-// d_hist [bins][bins] and d_count are zeroed / written on the stream; d_work: SIFT3D_AMD_SIMILARITY_GRID counts
+// d_hist [bins][bins] and d_count are zeroed / written on the stream; d_work: SIFT3D_AMD_SIMILARITY_GRID counts.
+// The pull map is A, or with A == NULL the field d_field [3][oz][oy][ox] (sift3d_hip_parzen_hist_field, the MI FFD
+// driver).
 extern "C" int sift3d_parzen_hist_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
-                                         int nx, int ny, int nz, const double *A, int bins, float lo_f, float s_f,
+                                         int nx, int ny, int nz, const double *A, const float *d_field, int bins,
+                                         float lo_f, float s_f,
                                          float lo_m, float hi_m, unsigned long long *d_hist,
                                          unsigned long long *d_count, void *d_work, void *stream, const float *d_WF,
                                          const float *d_WM)
@@ -922,10 +949,14 @@ extern "C" int sift3d_parzen_hist_launch(const char *fn, const float *d_F, int o
     if (!mi_args(m, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m, d_work, d_WF, d_WM))
         return launch_fail(fn, "grid too large");
     m.hist = d_hist;
+    m.field = d_field;
     const unsigned grid = m.a.g.ntiles < AFF_GRID ? m.a.g.ntiles : AFF_GRID;
     const bool masked = d_WF || d_WM, linear = nx >= 2;
-    void (*k)(const MiArgs) = masked ? (linear ? k_parzen_hist<2, true> : k_parzen_hist<1, true>)
-                                     : (linear ? k_parzen_hist<2, false> : k_parzen_hist<1, false>);
+    void (*k)(const MiArgs) =
+        A ? (masked ? (linear ? k_parzen_hist<2, true> : k_parzen_hist<1, true>)
+                    : (linear ? k_parzen_hist<2, false> : k_parzen_hist<1, false>))
+          : (masked ? (linear ? k_parzen_hist<2, true, true> : k_parzen_hist<1, true, true>)
+                    : (linear ? k_parzen_hist<2, false, true> : k_parzen_hist<1, false, true>));
     const size_t hb = (size_t)bins * bins * sizeof(unsigned long long);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(d_hist, 0, hb, st));

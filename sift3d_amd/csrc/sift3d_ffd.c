@@ -2,8 +2,10 @@
  * device entries (field export, evaluation with gradient, bending energy, subdivision) and the steepest-descent driver
  * (included at the end of sift3d_host.c, after sift3d_affine_refine.c).
  *
- * The contract is in include/sift3d_amd.h, "B-spline free-form deformation"; the kernels are in sift3d_ffd.hip, reached
- * through the launchers below after the checks here.  Arguments are checked before the device is touched, so bad
+ * The contract is in include/sift3d_amd.h, "B-spline free-form deformation" (the MSD) and "Mutual-information free-form
+ * deformation (Mattes)": two metrics, one evaluation entry body and one driver loop over either.  The kernels are in
+ * sift3d_ffd.hip (the histogram pass in sift3d_affine_refine.hip), reached through the launchers below after the checks
+ * here.  Arguments are checked before the device is touched, so bad
  * input is refused on a machine without a GPU too. */
 
 int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
@@ -13,6 +15,12 @@ int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy,
                                int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
                                double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
                                const float *d_WM);
+int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
+                         const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
+                         int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
+                         double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
+                         double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
+                         const float *d_WM);
 int sift3d_ffd_step_launch(const float *d_c, const float *d_grad, float a, float *d_out, size_t n, void *stream);
 int sift3d_ffd_refine2_launch(const float *d_c, int cx, int cy, int cz, float *d_f, int fx, int fy, int fz,
                               void *stream);
@@ -142,15 +150,24 @@ size_t sift3d_amd_ffd_evaluate_work_bytes(int ox, int oy, int oz, int dx, int dy
                             sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double);
 }
 
-/* the shared body of the two entries: d_WF, d_WM are the masks ("Masks") or NULL */
+/* bins, the two ranges and the table of an MI evaluation */
+typedef struct {
+    int bins;
+    float lo_f, hi_f, lo_m, hi_m;
+    const double *d_W;
+} ffd_mi_args;
+
+/* the shared body of the three entries: d_WF, d_WM are the masks ("Masks") or NULL; mi: the MI evaluation's further
+ * arguments, checked after the FFD entries' own, or NULL (the MSD) */
 static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                               int ny, int nz, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
                               const double *A, double bending, float *d_field, void *d_record, float *d_grad,
-                              void *d_work, void *stream, const float *d_WF, const float *d_WM)
+                              void *d_work, void *stream, const float *d_WF, const float *d_WM, const ffd_mi_args *mi)
 {
     int delta[3];
     double st[27];
-    if (!d_F || !d_M || !d_lattice || !d_field || !d_record || !d_grad || !d_work)
+    float s_f = 0.0f;
+    if (!d_F || !d_M || !d_lattice || !d_field || !d_record || !d_grad || !d_work || (mi && !mi->d_W))
         return refuse(what, "NULL argument");
     if (check_ffd_lattice(what, ox, oy, oz, gx, gy, gz, dx, dy, dz) || check_dims(what, nx, ny, nz) ||
         (A && check_affine(what, A)))
@@ -162,16 +179,20 @@ static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy
         return SIFT3D_FAILURE;
     if (ADDR(d_work) & 15)
         return refuse(what, "a buffer is misaligned");
+    if (mi && (parzen_check(what, mi->bins, mi->lo_f, mi->hi_f, mi->lo_m, mi->hi_m, &s_f) ||
+               check_aligned(what, ADDR(mi->d_W), 0)))
+        return SIFT3D_FAILURE;
     {
         const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
                                { d_lattice, image_bytes(gx, gy, gz, 3) },
                                { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
-                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 },
+                               { mi ? mi->d_W : NULL, mi ? (size_t)mi->bins * mi->bins * sizeof(double) : 0 } };
         const range_t out[] = { { d_field, field_bytes(ox, oy, oz) },
                                 { d_record, sift3d_amd_ffd_record_bytes(gx, gy, gz) },
                                 { d_grad, image_bytes(gx, gy, gz, 3) },
                                 { d_work, sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz) } };
-        if (ranges_aliased(out, 4, in, 5))
+        if (ranges_aliased(out, 4, in, 6))
             return refuse(what, ALIASED);
     }
     delta[0] = dx; delta[1] = dy; delta[2] = dz;
@@ -180,6 +201,12 @@ static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy
         sift3d_ffd_field_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, (const float *)d_work, A, ox, oy, oz, d_field,
                                 stream))
         return SIFT3D_FAILURE;
+    if (mi)
+        return sift3d_ffd_mi_launch(what, 1, 1, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
+                                    dz, (const float *)d_work, st, bending, mi->bins, mi->lo_f, s_f, mi->lo_m, mi->hi_m,
+                                    mi->d_W, (double *)d_record, d_grad,
+                                    (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
+                                    d_WM);
     return sift3d_ffd_evaluate_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
                                       dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
                                       (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
@@ -191,7 +218,7 @@ int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const floa
                             double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
 {
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL, NULL);
 }
 
 int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -200,7 +227,19 @@ int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, con
                                    void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy,
-                              gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM);
+                              gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM,
+                              NULL);
+}
+
+int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                               const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
+                               double bending, float *d_field, void *d_record, float *d_grad, void *d_work,
+                               void *stream, const float *d_WF, const float *d_WM, int bins, float lo_f, float hi_f,
+                               float lo_m, float hi_m, const double *d_W)
+{
+    const ffd_mi_args mi = { bins, lo_f, hi_f, lo_m, hi_m, d_W };
+    return ffd_evaluate_entry("sift3d_hip_ffd_mi_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, &mi);
 }
 
 size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz)
@@ -345,6 +384,15 @@ size_t sift3d_amd_ffd_refine_masked_work_bytes(int ox, int oy, int oz, int nx, i
     return plain ? plain + mask_pyramid_bytes(ox, oy, oz, nx, ny, nz, levels) : 0;
 }
 
+/* the MI driver's: the masked driver's, then the MI affine driver's extra (the histogram and the count, copied to the
+ * host together, then W), sized for SIFT3D_AMD_PARZEN_MAX_BINS whatever `bins` is */
+size_t sift3d_amd_ffd_mi_refine_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                           int levels)
+{
+    const size_t masked = sift3d_amd_ffd_refine_masked_work_bytes(ox, oy, oz, nx, ny, nz, dx, dy, dz, levels);
+    return masked ? masked + MI_EXTRA_BYTES : 0;
+}
+
 typedef struct {
     const float *F, *M;
     int ox, oy, oz, nx, ny, nz, gx, gy, gz;
@@ -356,6 +404,12 @@ typedef struct {
     double see, R, gmax;
 } ffd_head;
 
+/* an evaluation on the host: the record's head and the image term of the cost (S_ee / n, or -mi; NaN when n == 0) */
+typedef struct {
+    ffd_head h;
+    double image;
+} ffd_eval;
+
 typedef struct {
     const int *d;                                /* spacing */
     const double *st;                            /* stencils */
@@ -364,48 +418,102 @@ typedef struct {
     float *d_field;
     double bending;
     void *stream;
+    mi_state *ms;                                /* MI (sift3d_affine_refine.c): bins, ranges, histogram, W; or NULL */
+    float s_f;                                   /* MI: the fixed bin's scale */
 } ffd_ctx;
 
-/* one evaluation at lattice c on `lv`: the field, the record, R and the gradient, the head's copy to the host and the
- * wait for it */
+/* one evaluation at lattice c on `lv`: the field, then
+ *   MSD: the record, R and the gradient, the head's copy to the host and the wait for it;
+ *   MI:  the histogram through the field (its partial counts in the evaluation's partial slots) and R, histogram, count
+ *        and head to the host and the wait for them, sift3d_amd_parzen_mi.  ms->W is left holding the table and
+ *        ms->sim_trial the measures; no gradient is made (ffd_mi_gradient), and e->h.gmax is not meaningful. */
 static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv, const double *A, const float *c,
-                        float *grad, ffd_head *h)
+                        float *grad, ffd_eval *e)
 {
-    return sift3d_ffd_field_launch(what, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, A, lv->ox,
-                                   lv->oy, lv->oz, x->d_field, x->stream) ||
-           sift3d_ffd_evaluate_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
-                                      lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
-                                      x->d_rec, grad, x->d_eval, x->stream, lv->WF, lv->WM) ||
-           sift3d_hip_memcpy_d2h(h, x->d_rec, sizeof(*h), x->stream) || sift3d_hip_stream_sync(x->stream);
+    mi_state *ms = x->ms;
+    if (sift3d_ffd_field_launch(what, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, A, lv->ox, lv->oy,
+                                lv->oz, x->d_field, x->stream))
+        return SIFT3D_FAILURE;
+    if (ms) {
+        const size_t cells = (size_t)ms->bins * ms->bins;
+        if (sift3d_parzen_hist_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, NULL,
+                                      x->d_field, ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m,
+                                      (unsigned long long *)ms->d_hist, (unsigned long long *)(ms->d_hist + cells),
+                                      x->d_eval, x->stream, lv->WF, lv->WM) ||
+            sift3d_ffd_mi_launch(what, 1, 0, NULL, lv->ox, lv->oy, lv->oz, NULL, lv->nx, lv->ny, lv->nz, x->d_field, c,
+                                 lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
+                                 ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
+                                 lv->WF, lv->WM) ||
+            sift3d_hip_memcpy_d2h(ms->hist, ms->d_hist, (cells + 1) * sizeof(uint64_t), x->stream) ||
+            sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || sift3d_hip_stream_sync(x->stream) ||
+            sift3d_amd_parzen_mi(ms->hist, ms->bins, &ms->sim_trial, ms->W))
+            return SIFT3D_FAILURE;
+        e->h.n = ms->hist[cells];
+        e->h.see = 0.0;
+        e->h.gmax = NAN;
+        e->image = -ms->sim_trial.mi;                        /* NaN when nothing was counted */
+        return SIFT3D_SUCCESS;
+    }
+    if (sift3d_ffd_evaluate_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
+                                   lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
+                                   x->d_rec, grad, x->d_eval, x->stream, lv->WF, lv->WM) ||
+        sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || sift3d_hip_stream_sync(x->stream))
+        return SIFT3D_FAILURE;
+    e->image = e->h.n ? e->h.see / (double)e->h.n : NAN;
+    return SIFT3D_SUCCESS;
 }
 
-static double ffd_cost(const ffd_head *h, double bending)
+/* MI: the gradient at c, the lattice of the evaluation that left its table in ms->W, its field in d_field and its
+ * second derivatives in the work buffer (no evaluation was made since): W to the device, the force, adjoint, bending
+ * gradient and combine passes, gmax to the host and the wait for it */
+static int ffd_mi_gradient(const char *what, const ffd_ctx *x, const ffd_level *lv, const float *c, float *grad,
+                           ffd_eval *e)
 {
-    return (h->n ? h->see / (double)h->n : NAN) + bending * h->R;
+    mi_state *ms = x->ms;
+    ffd_head h;
+    if (sift3d_hip_memcpy_h2d(ms->d_W, ms->W, (size_t)ms->bins * ms->bins * sizeof(double), x->stream) ||
+        sift3d_ffd_mi_launch(what, 0, 1, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
+                             lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
+                             ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
+                             lv->WF, lv->WM) ||
+        sift3d_hip_memcpy_d2h(&h, x->d_rec, sizeof(h), x->stream) || sift3d_hip_stream_sync(x->stream))
+        return SIFT3D_FAILURE;
+    e->h.gmax = h.gmax;
+    return SIFT3D_SUCCESS;
 }
 
-static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_head *h, double bending, double step, int accepted,
+static double ffd_cost(const ffd_eval *e, double bending)
+{
+    return e->image + bending * e->h.R;
+}
+
+static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_eval *v, double bending, double step, int accepted,
                       int level)
 {
     sift3d_amd_ffd_evaluation *e = res->trail + res->evaluations++;
-    e->E = ffd_cost(h, bending);
-    e->msd = h->n ? h->see / (double)h->n : NAN;
-    e->R = h->R;
-    e->n = h->n;
+    e->E = ffd_cost(v, bending);
+    e->msd = v->image;
+    e->R = v->h.R;
+    e->n = v->h.n;
     e->step = step;
     e->accepted = accepted;
     e->level = level;
 }
 
-/* the shared body of the two drivers: `masked` selects the work buffer's size; the masks may still be NULL */
+/* the shared body of the three drivers: `masked` selects the work buffer's size; the masks may still be NULL.  ms (MI;
+ * else NULL): bins and ranges, checked here after the FFD drivers' own checks; the cost's image term is -mi, the
+ * gradient is made only at the lattice a step starts from, and ms->sim leaves with the measures at the final lattice on
+ * level 0. */
 static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                       int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
                       sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
-                      void *stream, int masked, const float *d_WF, const float *d_WM)
+                      void *stream, int masked, const float *d_WF, const float *d_WM, mi_state *ms)
 {
     sift3d_amd_ffd_refine_params prm;
     ffd_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
-    ffd_head rec, trial;
+    ffd_eval rec, trial;
+    size_t work_bytes;
+    float s_f = 0.0f;                                        /* MI: the fixed bin's scale */
     ffd_ctx x;
     double A[12], st[27];
     float *c, *ct, *g, *gt, *prev;
@@ -435,13 +543,17 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_lattice, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3) },
                                 { d_field, field_bytes(ox, oy, oz) },
-                                { d_work, (masked ? sift3d_amd_ffd_refine_masked_work_bytes
-                                                  : sift3d_amd_ffd_refine_work_bytes)(ox, oy, oz, nx, ny, nz,
-                                                                                      prm.spacing[0], prm.spacing[1],
-                                                                                      prm.spacing[2], prm.levels) } };
+                                { d_work, (ms       ? sift3d_amd_ffd_mi_refine_work_bytes
+                                           : masked ? sift3d_amd_ffd_refine_masked_work_bytes
+                                                    : sift3d_amd_ffd_refine_work_bytes)(ox, oy, oz, nx, ny, nz,
+                                                                                        prm.spacing[0], prm.spacing[1],
+                                                                                        prm.spacing[2], prm.levels) } };
         if (ranges_aliased(out, 3, in, 4))
             return refuse(what, ALIASED);
+        work_bytes = out[2].bytes;
     }
+    if (ms && parzen_check(what, ms->bins, ms->lo_f, ms->hi_f, ms->lo_m, ms->hi_m, &s_f))
+        return SIFT3D_FAILURE;
     result->evaluations = 0;
     result->stop = SIFT3D_AMD_FFD_STOP_EVALUATIONS;
     for (i = 0; i < 12; i++)
@@ -464,6 +576,12 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     x.d_field = d_field;
     x.bending = prm.bending;
     x.stream = stream;
+    x.ms = ms;
+    x.s_f = s_f;
+    if (ms) {                                                /* behind everything the masked driver lays out */
+        ms->d_hist = (uint64_t *)(w + work_bytes - MI_EXTRA_BYTES);
+        ms->d_W = (double *)(w + work_bytes - MI_TABLE_BYTES);
+    }
     if (ffd_upload_weights(prm.spacing[0], prm.spacing[1], prm.spacing[2], (float *)w, stream))
         return SIFT3D_FAILURE;
     for (l = 1; l < prm.levels; l++) {                       /* level l from level l - 1; A's shift halves */
@@ -494,6 +612,7 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
         double s = prm.step0, E;
         uint64_t n_first;
         int evals = 1, stop;
+        int stale = ms != NULL;                              /* MI: g holds no gradient at c yet */
         if (l == prm.levels - 1) {
             if (sift3d_hip_memset(c, 0, nc * sizeof(float), stream))
                 return SIFT3D_FAILURE;
@@ -507,8 +626,10 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
         }
         if (ffd_evaluate(what, &x, v, have_A ? A : NULL, c, g, &rec))
             return SIFT3D_FAILURE;
+        if (ms)
+            ms->sim = ms->sim_trial;
         ffd_trail(result, &rec, prm.bending, s, 1, l);
-        n_first = rec.n;
+        n_first = rec.h.n;
         E = ffd_cost(&rec, prm.bending);
         if (!isfinite(E))
             stop = SIFT3D_AMD_FFD_STOP_FAILED;
@@ -520,18 +641,24 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                     stop = SIFT3D_AMD_FFD_STOP_EVALUATIONS;
                     break;
                 }
-                if (rec.gmax == 0.0) {
+                if (stale) {                                 /* the gradient at the lattice this step starts from;
+                                                                ms->W is still that lattice's */
+                    if (ffd_mi_gradient(what, &x, v, c, g, &rec))
+                        return SIFT3D_FAILURE;
+                    stale = 0;
+                }
+                if (rec.h.gmax == 0.0) {
                     stop = SIFT3D_AMD_FFD_STOP_FLAT;
                     break;
                 }
-                if (sift3d_ffd_step_launch(c, g, (float)(s / rec.gmax), ct, nc, stream) ||
+                if (sift3d_ffd_step_launch(c, g, (float)(s / rec.h.gmax), ct, nc, stream) ||
                     ffd_evaluate(what, &x, v, have_A ? A : NULL, ct, gt, &trial))
                     return SIFT3D_FAILURE;
                 evals++;
                 Et = ffd_cost(&trial, prm.bending);
-                accept = isfinite(Et) && (double)trial.n >= prm.min_overlap * (double)n_first && Et < E;
+                accept = isfinite(Et) && (double)trial.h.n >= prm.min_overlap * (double)n_first && Et < E;
                 ffd_trail(result, &trial, prm.bending, s, accept, l);
-                if (!isfinite(Et)) {
+                if (!isfinite(Et) && !(ms && trial.h.n == 0)) {      /* MI: a trial that counts nothing is rejected */
                     stop = SIFT3D_AMD_FFD_STOP_FAILED;
                     break;
                 }
@@ -541,6 +668,9 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                     t = g; g = gt; gt = t;
                     rec = trial;
                     E = Et;
+                    stale = ms != NULL;
+                    if (ms)
+                        ms->sim = ms->sim_trial;
                     s = 2.0 * s < prm.step_max ? 2.0 * s : prm.step_max;
                 } else
                     s = s * 0.5;
@@ -569,7 +699,7 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
                                  void *stream)
 {
     return ffd_refine("sift3d_amd_ffd_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 0, NULL, NULL);
+                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL);
 }
 
 int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -578,5 +708,29 @@ int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz
                                         void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     return ffd_refine("sift3d_amd_ffd_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM);
+                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL);
+}
+
+int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                    const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                                    sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                    void *d_work, void *stream, const float *d_WF, const float *d_WM, int bins,
+                                    float lo_f, float hi_f, float lo_m, float hi_m, sift3d_amd_similarity *mi_out)
+{
+    static const char what[] = "sift3d_amd_ffd_mi_refine_device";
+    mi_state ms;
+    int rc;
+    if (!mi_out)
+        return refuse(what, "NULL argument");
+    ms.bins = bins;
+    ms.lo_f = lo_f; ms.hi_f = hi_f;
+    ms.lo_m = lo_m; ms.hi_m = hi_m;
+    ms.sim.n = 0;
+    ms.sim.msd = ms.sim.ncc = ms.sim.mi = ms.sim.nmi = NAN;
+    ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
+    *mi_out = ms.sim;
+    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
+                    d_WF, d_WM, &ms);
+    *mi_out = ms.sim;
+    return rc;
 }

@@ -24,6 +24,7 @@
 //   - reductions: workgroup_reduce into one partial slot per workgroup of a grid that depends on the shapes only, then
 //     finish_reduce.
 #include "sift3d_resample.h"
+#include "sift3d_parzen.h"
 
 namespace {
 
@@ -174,6 +175,111 @@ __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
         }
     }
     const double vs = workgroup_reduce<Add>(see, s_see);
+    const unsigned long long vc = workgroup_reduce<Add>(cnt, s_cnt);
+    if (threadIdx.x == 0) {
+        s.part[blockIdx.x] = vs;
+        reinterpret_cast<unsigned long long *>(s.part)[FFD_GRID + blockIdx.x] = vc;
+    }
+}
+
+// ---- the force of the mutual information (header, "Mutual-information free-form deformation (Mattes)") ------------
+struct FfdMiForceArgs {
+    FfdForceArgs f;                              // part: S_pp, then the count
+    int bins;
+    float lo_f, s_f, lo_m;                       // s_f: "Similarity measures"' float scale of the fixed bin
+    double s_m;                                  // parzen_scale(lo_m, hi_m, bins)
+    const double *W;                             // [bins][bins]
+};
+
+// k_ffd_force's walk and stores with the force E G'_d = -(psi * g_d) in the place of E G_d, psi as k_affine_mi_normal
+// forms it (sift3d_parzen.h's window, W from LDS), and S_pp = sum psi psi in the slot of S_ee.  W comes into dynamic LDS
+// once per workgroup: B * B * 8 bytes, 32 KiB at B = 64, so five workgroups fit a CU's 160 KiB.  A voxel that is not
+// counted, and a counted one outside the moving range (psi = 0), store +0.
+// (256, 4): 124 - 128 VGPRs, no AGPRs, four waves per SIMD and no scratch in all four instantiations
+// (-Rpass-analysis=kernel-resource-usage): there are no 72 accumulators here, so the window's temporaries and the four
+// outputs' taps fit where k_affine_mi_normal needed two waves and scheduling barriers.
+// Measured (profiles/microbench/ffd_mi_rate_mi355x.txt, 512^3, kernel trace, min of 5, one run): 1.29 - 1.35 ms at
+// B = 32 and 64 on either content, 0.996 - 1.001 x k_ffd_force's 1.30 - 1.35 ms in the same run (spread of a kernel
+// 1 %; an earlier run of the same script gave 1.42 - 1.44 ms for both kernels, the same quotients); both are 1.75 -
+// 1.83 x the 0.74 ms that their 44 B per voxel take at 8 TB/s: the window and the four LDS reads hide behind the
+// stores of three doubles per voxel.
+template <int LINEAR, bool MASKED>
+__global__ __launch_bounds__(256, 4) void k_ffd_mi_force(const FfdMiForceArgs sm)
+{
+    extern __shared__ __align__(16) unsigned char ffd_lds[];
+    const double *W = reinterpret_cast<const double *>(ffd_lds);
+    __shared__ double s_spp[4];
+    __shared__ unsigned long long s_cnt[4];
+    const FfdForceArgs &s = sm.f;
+    const GridArgs &p = s.g;
+    const int B = sm.bins;
+    {
+        double *Wl = reinterpret_cast<double *>(ffd_lds);
+        for (int i = threadIdx.x; i < B * B; i += 256)
+            Wl[i] = sm.W[i];
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 15;
+    const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;
+    unsigned long long cnt = 0;
+    double spp = 0.0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            break;
+        const bool row = y < p.oy && z < p.oz;
+        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+        Taps tp[4];
+        float f[4];
+        bool live[4];
+        float wf[4], wm[4];                                                  // MASKED only
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            live[k] = row && x < p.ox;
+            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+            f[k] = 0.0f;
+            wf[k] = wm[k] = 1.0f;
+            if (live[k]) {
+                const float *u = s.field + orow + (size_t)x;
+                ux = u[0];
+                uy = u[ovox];
+                uz = u[2 * ovox];
+                f[k] = s.F[orow + (size_t)x];
+                if (MASKED && s.w.wf)
+                    wf[k] = s.w.wf[orow + (size_t)x];
+            }
+            const double qx = (double)x + (double)ux, qy = (double)y + (double)uy, qz = (double)z + (double)uz;
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
+            if (MASKED && s.w.wm)
+                wm[k] = s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
+        }
+        float m[4], gx[4], gy[4], gz[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            m[k] = gather_grad<LINEAR>(p.src, tp[k], &gx[k], &gy[k], &gz[k]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool counted = MASKED ? live[k] && tp[k].in && mask_in(wf[k]) && mask_in(wm[k]) : live[k] && tp[k].in;
+            int k0, out;
+            uint32_t q[4];
+            double dw[4];
+            parzen_window(m[k], sm.lo_m, sm.s_m, B, &k0, q, dw, &out);
+            const double *w = W + parzen_fixed_bin(f[k], sm.lo_f, sm.s_f, B) * B + k0;          // k0 + 3 <= B - 1
+            const double v = sm.s_m * (((dw[0] * w[0] + dw[1] * w[1]) + dw[2] * w[2]) + dw[3] * w[3]);
+            const bool on = counted && !out;
+            const double psi = on ? v : 0.0;
+            cnt += counted ? 1u : 0u;
+            spp += psi * psi;
+            if (live[k]) {
+                double *o = s.force + orow + (size_t)(xt + lx + 16 * k);
+                o[0] = on ? -(psi * (double)gx[k]) : 0.0;                    // one rounding; the sign is exact
+                o[ovox] = on ? -(psi * (double)gy[k]) : 0.0;
+                o[2 * ovox] = on ? -(psi * (double)gz[k]) : 0.0;
+            }
+        }
+    }
+    const double vs = workgroup_reduce<Add>(spp, s_spp);
     const unsigned long long vc = workgroup_reduce<Add>(cnt, s_cnt);
     if (threadIdx.x == 0) {
         s.part[blockIdx.x] = vs;
@@ -334,13 +440,14 @@ __global__ __launch_bounds__(256) void k_ffd_bend_grad(const FfdBendArgs s)
     }
 }
 
-// grad = (float)((2 / n) * Gc + bending * dR), and the largest |grad| (as stored) into one partial slot per workgroup
+// grad = (float)((scale / n) * Gc + bending * dR), and the largest |grad| (as stored) into one partial slot per
+// workgroup.  scale: 2.0 for the MSD (Gc / n is half its derivative), 1.0 for the mutual information.
 struct FfdCombineArgs {
     const double *rec;                           // rec[0] = n as uint64
     const double *Gc, *dR;
     float *grad;
     double *part;
-    double bending;
+    double bending, scale;
     size_t total;
 };
 
@@ -348,7 +455,7 @@ __global__ __launch_bounds__(256) void k_ffd_combine(const FfdCombineArgs s)
 {
     __shared__ double slot[4];
     const double n = (double)reinterpret_cast<const unsigned long long *>(s.rec)[0];
-    const double two_n = 2.0 / n;
+    const double two_n = s.scale / n;
     double mx = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.total; i += (size_t)gridDim.x * 256) {
         const float g = (float)(two_n * s.Gc[i] + s.bending * s.dR[i]);
@@ -439,14 +546,26 @@ extern "C" int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int g
     return SIFT3D_SUCCESS;
 }
 
+// The parts of an evaluation, in the order they run.  The MSD entries run them all (the bending entry all but the image
+// term); the MI driver runs FFD_BEND_VALUE per evaluation and the other three only where a step starts.
+enum { FFD_IMAGE = 1, FFD_BEND_VALUE = 2, FFD_BEND_GRAD = 4, FFD_COMBINE = 8, FFD_ALL = 15 };
+
+// what the MI force needs beside the MSD force's arguments (NULL: the MSD)
+struct FfdMi {
+    int bins;
+    float lo_f, s_f, lo_m, hi_m;
+    const double *W;                             // device, [bins][bins]
+};
+
 // d_rec: {uint64 n; double S_ee, R, gmax} then Gc and dR, [3][gz][gy][gx] doubles each.  d_work: partial slots
 // [2][FFD_GRID] doubles, then the force [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox], D [18][N] doubles.
-// d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.
-extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
-                                          int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
-                                          int gy, int gz, int dx, int dy, int dz, const float *d_w,
-                                          const double *stencils, double bending, double *d_rec, float *d_grad,
-                                          double *d_work, void *stream, const float *d_WF, const float *d_WM)
+// d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.  FFD_BEND_GRAD reads the D that the
+// last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.
+static int ffd_evaluate_parts(const char *fn, unsigned parts, const FfdMi *mi, const float *d_F, int ox, int oy, int oz,
+                              const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat,
+                              int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
+                              double bending, double *d_rec, float *d_grad, double *d_work, void *stream,
+                              const float *d_WF, const float *d_WM)
 {
     hipStream_t st = (hipStream_t)stream;
     const size_t vox = (size_t)ox * oy * oz, cvox = (size_t)gx * gy * gz;
@@ -454,8 +573,9 @@ extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int 
     double *part = d_work, *force = part + 2 * FFD_GRID, *t1 = force + 3 * vox;
     double *t2 = t1 + 3 * (size_t)gz * oy * ox, *D = t2 + 3 * (size_t)gz * gy * ox;
     double *Gc = d_rec + 4, *dR = Gc + 3 * cvox;
-    if (d_F) {                                   // NULL: the bending entry, no image term
-        FfdForceArgs f;
+    if (parts & FFD_IMAGE) {
+        FfdMiForceArgs fm;
+        FfdForceArgs &f = fm.f;
         if (!grid_args(f.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
             return launch_fail(fn, "grid too large");
         f.F = d_F;
@@ -465,9 +585,22 @@ extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int 
         const unsigned grid = f.g.ntiles < FFD_GRID ? f.g.ntiles : FFD_GRID;
         f.w = MaskArgs{d_WF, d_WM};
         const bool masked = d_WF || d_WM;
-        void (*kf)(const FfdForceArgs) = masked ? (nx >= 2 ? k_ffd_force<2, true> : k_ffd_force<1, true>)
-                                                : (nx >= 2 ? k_ffd_force<2, false> : k_ffd_force<1, false>);
-        hipLaunchKernelGGL(kf, dim3(grid), dim3(256), 0, st, f);
+        if (mi) {
+            fm.bins = mi->bins;
+            fm.lo_f = mi->lo_f;
+            fm.s_f = mi->s_f;
+            fm.lo_m = mi->lo_m;
+            fm.s_m = parzen_scale(mi->lo_m, mi->hi_m, mi->bins);
+            fm.W = mi->W;
+            void (*km)(const FfdMiForceArgs) =
+                masked ? (nx >= 2 ? k_ffd_mi_force<2, true> : k_ffd_mi_force<1, true>)
+                       : (nx >= 2 ? k_ffd_mi_force<2, false> : k_ffd_mi_force<1, false>);
+            hipLaunchKernelGGL(km, dim3(grid), dim3(256), (size_t)mi->bins * mi->bins * sizeof(double), st, fm);
+        } else {
+            void (*kf)(const FfdForceArgs) = masked ? (nx >= 2 ? k_ffd_force<2, true> : k_ffd_force<1, true>)
+                                                    : (nx >= 2 ? k_ffd_force<2, false> : k_ffd_force<1, false>);
+            hipLaunchKernelGGL(kf, dim3(grid), dim3(256), 0, st, f);
+        }
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish_count, dim3(1), dim3(256), 0, st, (const unsigned long long *)part + FFD_GRID, grid,
                            (unsigned long long *)d_rec);
@@ -493,23 +626,55 @@ extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int 
     b.part = part;
     b.dR = dR;
     b.gx = gx; b.gy = gy; b.gz = gz;
-    const unsigned bgrid = flat_grid(N, FFD_GRID);
-    hipLaunchKernelGGL(k_ffd_bend_value, dim3(bgrid), dim3(256), 0, st, b);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ffd_finish<Add>, dim3(1), dim3(256), 0, st, (const double *)part, bgrid, d_rec + 2,
-                       1.0 / (double)N);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ffd_bend_grad, dim3(flat_grid(3 * cvox, MAX_GRID)), dim3(256), 0, st, b);
-    LAUNCH_CHECK();
-    if (!d_F)
-        return SIFT3D_SUCCESS;
-    const FfdCombineArgs c = {d_rec, Gc, dR, d_grad, part, bending, 3 * cvox};
-    const unsigned cgrid = flat_grid(3 * cvox, FFD_GRID);
-    hipLaunchKernelGGL(k_ffd_combine, dim3(cgrid), dim3(256), 0, st, c);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ffd_finish<Max>, dim3(1), dim3(256), 0, st, (const double *)part, cgrid, d_rec + 3, 1.0);
-    LAUNCH_CHECK();
+    if (parts & FFD_BEND_VALUE) {
+        const unsigned bgrid = flat_grid(N, FFD_GRID);
+        hipLaunchKernelGGL(k_ffd_bend_value, dim3(bgrid), dim3(256), 0, st, b);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_ffd_finish<Add>, dim3(1), dim3(256), 0, st, (const double *)part, bgrid, d_rec + 2,
+                           1.0 / (double)N);
+        LAUNCH_CHECK();
+    }
+    if (parts & FFD_BEND_GRAD) {
+        hipLaunchKernelGGL(k_ffd_bend_grad, dim3(flat_grid(3 * cvox, MAX_GRID)), dim3(256), 0, st, b);
+        LAUNCH_CHECK();
+    }
+    if (parts & FFD_COMBINE) {
+        const FfdCombineArgs c = {d_rec, Gc, dR, d_grad, part, bending, mi ? 1.0 : 2.0, 3 * cvox};
+        const unsigned cgrid = flat_grid(3 * cvox, FFD_GRID);
+        hipLaunchKernelGGL(k_ffd_combine, dim3(cgrid), dim3(256), 0, st, c);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_ffd_finish<Max>, dim3(1), dim3(256), 0, st, (const double *)part, cgrid, d_rec + 3, 1.0);
+        LAUNCH_CHECK();
+    }
     return SIFT3D_SUCCESS;
+}
+
+// The MSD evaluation; d_F == NULL: the bending entry, no image term and no combined gradient.
+extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
+                                          int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
+                                          int gy, int gz, int dx, int dy, int dz, const float *d_w,
+                                          const double *stencils, double bending, double *d_rec, float *d_grad,
+                                          double *d_work, void *stream, const float *d_WF, const float *d_WM)
+{
+    return ffd_evaluate_parts(fn, d_F ? FFD_ALL : FFD_BEND_VALUE | FFD_BEND_GRAD, nullptr, d_F, ox, oy, oz, d_M, nx, ny,
+                              nz, d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work,
+                              stream, d_WF, d_WM);
+}
+
+// The MI evaluation.  value != 0: the bending value alone (what every evaluation of the MI driver needs on the device
+// beside the field and the histogram; the image arguments are not read).  gradient != 0: the force of psi from d_W, its
+// adjoint, the bending gradient from the D of the last value pass, and the combined gradient with the factor 1 / n.
+extern "C" int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
+                                    const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat,
+                                    int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
+                                    const double *stencils, double bending, int bins, float lo_f, float s_f, float lo_m,
+                                    float hi_m, const double *d_W, double *d_rec, float *d_grad, double *d_work,
+                                    void *stream, const float *d_WF, const float *d_WM)
+{
+    const FfdMi mi = {bins, lo_f, s_f, lo_m, hi_m, d_W};
+    const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u);
+    return ffd_evaluate_parts(fn, parts, &mi, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
+                              d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
 }
 
 extern "C" int sift3d_ffd_step_launch(const float *d_c, const float *d_grad, float a, float *d_out, size_t n,

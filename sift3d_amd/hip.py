@@ -252,6 +252,18 @@ def lib():
         "sift3d_amd_ffd_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                                    C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
                                                    C.POINTER(FFDRefineResult), vp, vp, vp, vp]),
+        "sift3d_hip_parzen_hist_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                                   C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp,
+                                                   vp, vp]),
+        "sift3d_hip_ffd_mi_evaluate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
+                                       + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp, vp, vp,
+                                                          C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
+        "sift3d_amd_ffd_mi_refine_work_bytes": (C.c_size_t, [C.c_int] * 10),
+        "sift3d_amd_ffd_mi_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
+                                                      C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp, C.c_int,
+                                                      C.c_float, C.c_float, C.c_float, C.c_float,
+                                                      C.POINTER(Similarity)]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -1271,6 +1283,106 @@ def ffd_refine(F, M, A=None, params=None, work=None, mask_fixed=None, mask_movin
     else:
         _check(lib().sift3d_amd_ffd_refine_device(*args), "sift3d_amd_ffd_refine_device")
     return res, lattice, field
+
+
+# ---- Mattes mutual-information free-form deformation ("Mutual-information free-form deformation (Mattes)") ----
+def parzen_histogram_field(F, M, field, bins, range_f, range_m, hist=None, work=None, mask_fixed=None,
+                           mask_moving=None):
+    """parzen_histogram with the displacement field [3, oz, oy, ox] in the place of A (sift3d_hip_parzen_hist_field):
+    (hist int64 [bins, bins], count int64 [1]) on the device, on torch's current stream."""
+    import torch
+    what = "parzen_histogram_field"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _field_tensor(field, what)
+    _same_device(what, F, M, field)
+    if tuple(field.shape[1:]) != tuple(F.shape):
+        raise ValueError(what + ": the field must be [3, oz, oy, ox] on F's grid")
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    bins = _parzen_bins(bins, what)
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    if hist is None:
+        hist = torch.empty((bins, bins), dtype=torch.int64, device=F.device)
+    _tensor(hist, what + ": hist must be a contiguous int64 CUDA tensor [bins, bins] on F's device",
+            shape=(bins, bins), device=F.device, dtype="int64")
+    count = torch.empty(1, dtype=torch.int64, device=F.device)
+    need = lib().sift3d_amd_parzen_hist_work_bytes(ox, oy, oz)
+    work = _work(work, (need + 3) // 4, F, what)
+    _check(lib().sift3d_hip_parzen_hist_field(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, field.data_ptr(),
+                                              bins, *_parzen_ranges(range_f, range_m), hist.data_ptr(), count.data_ptr(),
+                                              work.data_ptr(), current_stream(), *masks),
+           "sift3d_hip_parzen_hist_field")
+    return hist, count
+
+
+def ffd_mi_evaluate(F, M, lattice, spacing, W, range_f, range_m, A=None, bending=0.0, work=None, mask_fixed=None,
+                    mask_moving=None):
+    """ffd_evaluate for the mutual information (sift3d_hip_ffd_mi_evaluate): psi from the table W [bins, bins] (float64;
+    a numpy array is uploaded, a CUDA tensor is used as it is).  Returns (record, grad, field); ffd_record reads the
+    record, whose S_ee slot holds S_pp."""
+    import torch
+    what = "ffd_mi_evaluate"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    gx, gy, gz = _ffd_lattice(lattice, what)
+    _same_device(what, F, M, lattice)
+    dx, dy, dz = ffd_spacing(spacing, what)
+    if not isinstance(W, torch.Tensor):
+        W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(F.device)
+    if W.dim() != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError(what + ": W must be [bins, bins]")
+    bins = _parzen_bins(W.shape[0], what)
+    _tensor(W, what + ": W must be a contiguous float64 tensor [bins, bins] on F's device", shape=(bins, bins),
+            device=F.device, dtype="float64")
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    a, ap = _ffd_A(A, what)
+    record = _ffd_record_tensor(lattice)
+    grad = torch.empty_like(lattice)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    need = lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz)
+    work = _work(work, (need + 3) // 4, F, what)
+    _check(lib().sift3d_hip_ffd_mi_evaluate(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx,
+                                            gy, gz, dx, dy, dz, ap, float(bending), field.data_ptr(),
+                                            record.data_ptr(), grad.data_ptr(), work.data_ptr(), current_stream(),
+                                            *masks, bins, *_parzen_ranges(range_f, range_m), W.data_ptr()),
+           "sift3d_hip_ffd_mi_evaluate")
+    return record, grad, field
+
+
+def ffd_mi_refine(F, M, bins, range_f, range_m, A=None, params=None, work=None, mask_fixed=None, mask_moving=None):
+    """sift3d_amd_ffd_mi_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
+    waits for it once per evaluation and once per gradient).  Returns (FFDRefineResult, lattice, field, Similarity: the
+    measures at the final lattice)."""
+    import torch
+    what = "ffd_mi_refine"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    a, ap = _ffd_A(A, what)
+    bins = _parzen_bins(bins, what)
+    p = params if params is not None else ffd_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    d = tuple(p.spacing)
+    need = lib().sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
+    if need == 0:
+        raise ValueError(what + ": levels must be in [1, %d] and the spacing in [1, %d]"
+                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
+    work = _work(work, (need + 3) // 4, F, what)
+    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    res = FFDRefineResult()
+    sim = Similarity()
+    _check(lib().sift3d_amd_ffd_mi_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap, C.byref(p),
+                                                 C.byref(res), lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
+                                                 current_stream(), *masks, bins, *_parzen_ranges(range_f, range_m),
+                                                 C.byref(sim)),
+           "sift3d_amd_ffd_mi_refine_device")
+    return res, lattice, field, sim
 
 
 def _dense_args(src, out, what):
