@@ -32,7 +32,7 @@
 
 namespace {
 
-constexpr unsigned AFF_GRID = SIFT3D_AMD_SIMILARITY_GRID;
+constexpr unsigned AFF_GRID = REDUCE_GRID;
 constexpr int AFF_H = 60, AFF_B = 12;
 constexpr int AFF_SUMS = AFF_H + AFF_B + 1;      // doubles: H's distinct values, b, S_ee
 constexpr int AFF_STATS = AFF_SUMS + 1;          // and the count
@@ -49,11 +49,183 @@ struct AffArgs {
 __host__ __device__ constexpr int pair3(int d, int e) { return d == 0 ? e : d == 1 ? 2 + e : 5; }           // d <= e < 3
 __host__ __device__ constexpr int pair4(int j, int k) { return j == 0 ? k : j == 1 ? 3 + k : j == 2 ? 5 + k : 9; }   // j <= k < 4
 
-// (256, 2): the 72 accumulators are 144 VGPRs; the compiler reports 256 VGPRs, two waves per SIMD and nothing spilled
-// (-Rpass-analysis=kernel-resource-usage).  Measured (profiles/microbench/affine_refine_rate_mi355x.txt): 0.888 ms
-// per pass at 512^3, 1.63 x k_similarity's on the same volumes; the direct formulation takes 1.086 ms.
-// MASKED (header, "Masks"): as k_similarity's; a masked-out voxel enters with G = 0 and E = 0 like an outside one.
-// MASKED == false compiles to what it compiled to before the parameter existed.
+// ---- what the record kernels share -----------------------------------------------------------------------------------
+// One tile's samples for a lane, the two-stage front-end (the one-stage form is sift3d_resample.h's tile_front): its
+// four outputs' f, m and gradient, and whether each is counted (live, inside the moving grid and, MASKED, in both
+// masks).
+struct TileSamples {
+    float f[4], m[4], gx[4], gy[4], gz[4];
+    bool counted[4];
+};
+
+template <int LINEAR, bool MASKED>
+__device__ __forceinline__ void tile_samples(const AffArgs &s, int xt, int y, int z, int lx, TileSamples &t)
+{
+    const GridArgs &p = s.g;
+    const bool row = y < p.oy && z < p.oz;
+    const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+    const double yd = (double)y, zd = (double)z;
+    const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
+    // MASKED: the two mask values of the lane's four outputs first, all eight loads in flight together, kept as
+    // four flags.  The accumulators leave no registers to hold them across the intensity gathers (it spills);
+    // the stage costs one more round trip per tile (measured: DESIGN.md 3.4.10).  q is pull()'s three
+    // multiply-adds per output, computed here and again in the taps loop rather than kept in 24 registers.
+    bool ok[4] = {true, true, true, true};
+    if (MASKED) {
+        float wf[4], wm[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            const double xd = (double)x;
+            const double qx = pull(s.a, xd, rx), qy = pull(s.a + 4, xd, ry), qz = pull(s.a + 8, xd, rz);
+            wf[k] = s.w.wf && row && x < p.ox ? s.w.wf[orow + (size_t)x] : 1.0f;
+            wm[k] = s.w.wm ? s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)] : 1.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            ok[k] = mask_in(wf[k]) && mask_in(wm[k]);
+    }
+    Taps tp[4];
+    bool live[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x = xt + lx + 16 * k;
+        live[k] = row && x < p.ox;
+        t.f[k] = live[k] ? s.F[orow + (size_t)x] : 0.0f;
+        const double xd = (double)x;
+        tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry), pull(s.a + 8, xd, rz));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        t.m[k] = gather_grad<LINEAR>(p.src, tp[k], &t.gx[k], &t.gy[k], &t.gz[k]);
+        t.counted[k] = MASKED ? live[k] && tp[k].in && ok[k] : live[k] && tp[k].in;
+    }
+}
+
+// The per-tile factoring (top of the file).  A voxel adds w, w X (and, for H, (w X) X) into the tile's sums,
+__device__ __forceinline__ void tile_add(double w, double X, double &s0, double &s1)
+{
+    s0 += w;
+    s1 += w * X;
+}
+
+__device__ __forceinline__ void tile_add(double w, double X, double &s0, double &s1, double &s2)
+{
+    const double wx = w * X;
+    s0 += w;
+    s1 += wx;
+    s2 += wx * X;
+}
+
+// once per tile the sums of a pair G_d G_e fold into its ten accumulators (P_j P_k, j <= k),
+__device__ __forceinline__ void fold_pair(double *h, double s0, double s1, double s2, double Y, double Z, double YY,
+                                          double YZ, double ZZ)
+{
+    h[0] += s2;                                                          // X X
+    h[1] += s1 * Y;                                                      // X Y
+    h[2] += s1 * Z;                                                      // X Z
+    h[3] += s1;                                                          // X 1
+    h[4] += s0 * YY;
+    h[5] += s0 * YZ;
+    h[6] += s0 * Y;
+    h[7] += s0 * ZZ;
+    h[8] += s0 * Z;
+    h[9] += s0;
+}
+
+// and those of a quantity with one factor J (G_d E, G_d, G_d m, G_d f) into its four (P_j).
+__device__ __forceinline__ void fold_row(double *b, double s0, double s1, double Y, double Z)
+{
+    b[0] += s1;
+    b[1] += s0 * Y;
+    b[2] += s0 * Z;
+    b[3] += s0;
+}
+
+// a lane's value summed over its wave by butterfly (s = 32 .. 1)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1)
+        v += __shfl_xor(v, sft);
+    return v;
+}
+
+struct EverySum {
+    __device__ constexpr bool operator()(int) const { return true; }
+};
+
+// The epilogue of the record kernels.  value(i), i = 0 .. NSUMS - 1, are the lane's sums and cnt its count (statistic
+// NSUMS).  Each: the wave by butterfly (wave_sum), then the four waves' values through LDS as ((w0 + w1) + w2) + w3
+// into partial slot blockIdx.x of row i of part [NSUMS + 1][AFF_GRID] (the count's row holds uint64).  in_part(i): the
+// statistics this kernel writes (the NCC record is summed by two kernels).
+template <int NSUMS, typename Value, typename InPart = EverySum>
+__device__ __forceinline__ void record_slots(double *part, Value value, unsigned long long cnt,
+                                             InPart in_part = InPart())
+{
+    __shared__ double slot[NSUMS * 4];
+    __shared__ unsigned long long cslot[4];
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int i = 0; i < NSUMS; i++) {
+        if (!in_part(i))
+            continue;
+        const double v = wave_sum(value(i));
+        if (lead)
+            slot[4 * i + wave] = v;
+    }
+    cnt = wave_sum(cnt);
+    if (lead)
+        cslot[wave] = cnt;
+    __syncthreads();
+    if (!in_part((int)threadIdx.x))
+        return;
+    if (threadIdx.x < NSUMS) {
+        const double *v = slot + 4 * threadIdx.x;
+        part[(size_t)threadIdx.x * AFF_GRID + blockIdx.x] = ((v[0] + v[1]) + v[2]) + v[3];
+    } else if (threadIdx.x == NSUMS) {
+        reinterpret_cast<unsigned long long *>(part)[(size_t)NSUMS * AFF_GRID + blockIdx.x] =
+            ((cslot[0] + cslot[1]) + cslot[2]) + cslot[3];
+    }
+}
+
+// The head of the finish kernels: workgroup st = blockIdx.x adds the partial slots 0 .. n-1 of statistic st in a fixed
+// order (finish_reduce).  The count (st == NSUMS) goes to rec[0] as uint64; true for the one lane that has a sum v to
+// place in the record.
+template <int NSUMS>
+__device__ __forceinline__ bool finish_head(const double *part, unsigned n, double *rec, double &v)
+{
+    __shared__ double s_sum[256];
+    __shared__ unsigned long long s_cnt[256];
+    const int st = blockIdx.x;
+    if (st == NSUMS) {
+        const unsigned long long c =
+            finish_reduce<Add>(reinterpret_cast<const unsigned long long *>(part) + (size_t)st * AFF_GRID, n, s_cnt);
+        if (threadIdx.x == 0)
+            reinterpret_cast<unsigned long long *>(rec)[0] = c;
+        return false;
+    }
+    v = finish_reduce<Add>(part + (size_t)st * AFF_GRID, n, s_sum);
+    return threadIdx.x == 0;
+}
+
+// (256, 2): the 72 accumulators are 144 VGPRs; the compiler reports 256 VGPRs (248 MASKED), two waves per SIMD and
+// nothing spilled (-Rpass-analysis=kernel-resource-usage).  Measured
+// (profiles/microbench/affine_refine_rate_mi355x.txt): 0.888 ms per pass at 512^3, 1.63 x k_similarity's on the same
+// volumes; the direct formulation takes 1.086 ms.
+// MASKED (header, "Masks"): a masked-out voxel enters with G = 0 and E = 0 like an outside one.
+// This kernel alone is written out, front-end, tile sums, fold and epilogue, and not on the shared pieces above: its
+// allocation sits on the 256-VGPR limit and every shared form spills, in bytes of scratch per lane over <1, false>,
+// <1, true>, <2, false>, <2, true> (profiles/microbench/registration_front_end_mi355x.txt):
+//   record_slots alone, the loop as it is                36,  0, 20,  0   (the same with the lambda's captures by
+//     value, with an array in its place, with the LDS declared here, and with a scheduling barrier per statistic);
+//   and fold_pair / fold_row                             36,  0, 20,  0;
+//   tile_samples, tile_add, the folds and record_slots   44, 56, 20, 28   (this is k_affine_mi_normal's text with
+//     E = e and G = g: the one template of the two kernels);
+//   tile_samples and the folds, the epilogue inline      44, 56, 20, 24.
+// So what changes in tile_samples, the tile sums or record_slots changes here too, by hand.
 template <int LINEAR, bool MASKED>
 __global__ __launch_bounds__(256, 2) void k_affine_normal(const AffArgs s)
 {
@@ -238,18 +410,9 @@ __device__ void scatter_h(double *H, int st, double v)
 // of the record {uint64 n; double S_ee; double b[12]; double H[12][12]} that holds it.
 __global__ __launch_bounds__(256) void k_affine_normal_finish(const double *part, unsigned n, double *rec)
 {
-    __shared__ double s_sum[256];
-    __shared__ unsigned long long s_cnt[256];
     const int st = blockIdx.x;
-    if (st == AFF_SUMS) {
-        const unsigned long long c =
-            finish_reduce<Add>(reinterpret_cast<const unsigned long long *>(part) + (size_t)st * AFF_GRID, n, s_cnt);
-        if (threadIdx.x == 0)
-            reinterpret_cast<unsigned long long *>(rec)[0] = c;
-        return;
-    }
-    const double v = finish_reduce<Add>(part + (size_t)st * AFF_GRID, n, s_sum);
-    if (threadIdx.x != 0)
+    double v;
+    if (!finish_head<AFF_SUMS>(part, n, rec, v))
         return;
     double *b = rec + 2, *H = rec + 2 + AFF_B;
     if (st == AFF_SUMS - 1) {
@@ -277,108 +440,6 @@ __host__ __device__ constexpr bool ncc_in_part(int part, int st)
     return part == 0 || (part == 1) == (st < NCC_U || st == NCC_MOM + 2 || st == NCC_SUMS);
 }
 
-// One tile's samples for a lane: its four outputs' f, m and gradient, and whether each is counted (live, inside the
-// moving grid and, MASKED, in both masks).
-struct TileSamples {
-    float f[4], m[4], gx[4], gy[4], gz[4];
-    bool counted[4];
-};
-
-template <int LINEAR, bool MASKED>
-__device__ __forceinline__ void tile_samples(const AffArgs &s, int xt, int y, int z, int lx, TileSamples &t)
-{
-    const GridArgs &p = s.g;
-    const bool row = y < p.oy && z < p.oz;
-    const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
-    const double yd = (double)y, zd = (double)z;
-    const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
-    // MASKED: the two mask values of the lane's four outputs first, all eight loads in flight together, kept as
-    // four flags.  The accumulators leave no registers to hold them across the intensity gathers (it spills);
-    // the stage costs one more round trip per tile (measured: DESIGN.md 3.4.10).  q is pull()'s three
-    // multiply-adds per output, computed here and again in the taps loop rather than kept in 24 registers.
-    bool ok[4] = {true, true, true, true};
-    if (MASKED) {
-        float wf[4], wm[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int x = xt + lx + 16 * k;
-            const double xd = (double)x;
-            const double qx = pull(s.a, xd, rx), qy = pull(s.a + 4, xd, ry), qz = pull(s.a + 8, xd, rz);
-            wf[k] = s.w.wf && row && x < p.ox ? s.w.wf[orow + (size_t)x] : 1.0f;
-            wm[k] = s.w.wm ? s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)] : 1.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            ok[k] = mask_in(wf[k]) && mask_in(wm[k]);
-    }
-    Taps tp[4];
-    bool live[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int x = xt + lx + 16 * k;
-        live[k] = row && x < p.ox;
-        t.f[k] = live[k] ? s.F[orow + (size_t)x] : 0.0f;
-        const double xd = (double)x;
-        tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry), pull(s.a + 8, xd, rz));
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        t.m[k] = gather_grad<LINEAR>(p.src, tp[k], &t.gx[k], &t.gy[k], &t.gz[k]);
-        t.counted[k] = MASKED ? live[k] && tp[k].in && ok[k] : live[k] && tp[k].in;
-    }
-}
-
-// The per-tile factoring of k_affine_normal, operation for operation.  A voxel adds w, w X (and, for H, (w X) X) into
-// the tile's sums,
-__device__ __forceinline__ void tile_add(double w, double X, double &s0, double &s1)
-{
-    s0 += w;
-    s1 += w * X;
-}
-
-__device__ __forceinline__ void tile_add(double w, double X, double &s0, double &s1, double &s2)
-{
-    const double wx = w * X;
-    s0 += w;
-    s1 += wx;
-    s2 += wx * X;
-}
-
-// once per tile the sums of a pair G_d G_e fold into its ten accumulators (P_j P_k, j <= k),
-__device__ __forceinline__ void fold_pair(double *h, double s0, double s1, double s2, double Y, double Z, double YY,
-                                          double YZ, double ZZ)
-{
-    h[0] += s2;                                                          // X X
-    h[1] += s1 * Y;                                                      // X Y
-    h[2] += s1 * Z;                                                      // X Z
-    h[3] += s1;                                                          // X 1
-    h[4] += s0 * YY;
-    h[5] += s0 * YZ;
-    h[6] += s0 * Y;
-    h[7] += s0 * ZZ;
-    h[8] += s0 * Z;
-    h[9] += s0;
-}
-
-// and those of a quantity with one factor J (G_d, G_d m, G_d f) into its four (P_j).
-__device__ __forceinline__ void fold_row(double *b, double s0, double s1, double Y, double Z)
-{
-    b[0] += s1;
-    b[1] += s0 * Y;
-    b[2] += s0 * Z;
-    b[3] += s0;
-}
-
-// a lane's value summed over its wave by butterfly (s = 32 .. 1)
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1)
-        v += __shfl_xor(v, sft);
-    return v;
-}
-
 // The register budget decides the split.  The 96 accumulators and the 5 moments are 202 VGPRs and a tile's 36 sums 72
 // more, past the 256 that two waves per SIMD leave a lane.  As reported by -Rpass-analysis=kernel-resource-usage:
 //   PART 0, (256, 1): 256 VGPRs + 62 - 83 AGPRs, one wave per SIMD, no scratch (at (256, 2) it spills over a hundred
@@ -389,16 +450,12 @@ __device__ __forceinline__ T wave_sum(T v)
 // Measured (profiles/microbench/affine_ncc_rate_mi355x.txt, 512^3, all in one run): k_affine_normal's pass 0.885 ms,
 // the one kernel 2.790 ms (3.15 x), the two kernels together 1.722 ms (1.95 x): one wave per SIMD costs more than a
 // second gather of the volumes does, so the two kernels are the default.
-// k_affine_normal's own body is kept as it was rather than restated on the helpers above: its allocation sits at the
-// 256-VGPR limit, and with tile_add / fold_pair alone in it the compiler spills 8 - 24 VGPRs.
-// The sums of H are k_affine_normal's operation for operation, so H is that kernel's bit for bit.  A voxel that is not
-// counted enters with G = 0, m = 0 and f = 0.  MASKED: as k_affine_normal's.
+// The sums of H are tile_add's and fold_pair's on the same G_d G_e as k_affine_normal's (written out there), so H is
+// that kernel's bit for bit.  A voxel that is not counted enters with G = 0, m = 0 and f = 0.
 template <int LINEAR, bool MASKED, int PART>
 __global__ __launch_bounds__(256, PART == 0 ? 1 : 2) void k_affine_ncc_normal(const AffArgs s)
 {
     constexpr bool HV = PART != 2, UW = PART != 1;
-    __shared__ double slot[NCC_SUMS * 4];
-    __shared__ unsigned long long cslot[4];
     const GridArgs &p = s.g;
     const int lx = threadIdx.x & 15;
     unsigned long long cnt = 0;
@@ -467,48 +524,16 @@ __global__ __launch_bounds__(256, PART == 0 ? 1 : 2) void k_affine_ncc_normal(co
             }
         }
     }
-    // as k_affine_normal: the wave by butterfly, then the four waves' values through LDS as ((w0 + w1) + w2) + w3
-    const int wave = threadIdx.x >> 6;
-    const bool lead = (threadIdx.x & 63) == 0;
-#pragma unroll
-    for (int i = 0; i < NCC_SUMS; i++) {
-        if (!ncc_in_part(PART, i))
-            continue;
-        const double v = wave_sum(acc[i]);
-        if (lead)
-            slot[4 * i + wave] = v;
-    }
-    cnt = wave_sum(cnt);
-    if (lead)
-        cslot[wave] = cnt;
-    __syncthreads();
-    if (!ncc_in_part(PART, (int)threadIdx.x))
-        return;
-    if (threadIdx.x < NCC_SUMS) {
-        const double *v = slot + 4 * threadIdx.x;
-        s.part[(size_t)threadIdx.x * AFF_GRID + blockIdx.x] = ((v[0] + v[1]) + v[2]) + v[3];
-    } else if (threadIdx.x == NCC_SUMS) {
-        reinterpret_cast<unsigned long long *>(s.part)[(size_t)NCC_SUMS * AFF_GRID + blockIdx.x] =
-            ((cslot[0] + cslot[1]) + cslot[2]) + cslot[3];
-    }
+    record_slots<NCC_SUMS>(s.part, [&](int i) { return acc[i]; }, cnt, [](int st) { return ncc_in_part(PART, st); });
 }
 
 // Workgroup s adds the partial slots 0 .. n-1 of statistic s in a fixed order (finish_reduce) and writes every entry
 // of the record {uint64 n; double S_m, S_f, S_mm, S_fm, S_ff, u[12], v[12], w[12], H[12][12]} that holds it.
 __global__ __launch_bounds__(256) void k_affine_ncc_finish(const double *part, unsigned n, double *rec)
 {
-    __shared__ double s_sum[256];
-    __shared__ unsigned long long s_cnt[256];
     const int st = blockIdx.x;
-    if (st == NCC_SUMS) {
-        const unsigned long long c =
-            finish_reduce<Add>(reinterpret_cast<const unsigned long long *>(part) + (size_t)st * AFF_GRID, n, s_cnt);
-        if (threadIdx.x == 0)
-            reinterpret_cast<unsigned long long *>(rec)[0] = c;
-        return;
-    }
-    const double v = finish_reduce<Add>(part + (size_t)st * AFF_GRID, n, s_sum);
-    if (threadIdx.x != 0)
+    double v;
+    if (!finish_head<NCC_SUMS>(part, n, rec, v))
         return;
     double *mom = rec + 1, *u = mom + 5, *vv = u + 12, *w = vv + 12, *H = w + 12;
     if (st >= NCC_MOM)
@@ -525,15 +550,13 @@ __global__ __launch_bounds__(256) void k_affine_ncc_finish(const double *part, u
 
 // ---- the fit under an unknown intensity map (Mattes mutual information) ----------------------------------------------
 // Header, "Mutual-information affine refinement (Mattes)"; restated in numpy by tests/affine_mi_restatement.py.  Two
-// passes over the fixed grid, both with k_affine_normal's / k_similarity's tiles, tile order, XCD grouping, pull map,
-// inside test and sample; the window of the moving value is sift3d_parzen.h's one function in both and on the host.
+// passes over the fixed grid, the histogram with the one-stage front-end (tile_front's, written out in it) and the
+// record on the two-stage one (tile_samples); the window of the moving value is sift3d_parzen.h's one function in both
+// and on the host.
 struct MiArgs {
     AffArgs a;                                   // part: the record pass's partial slots; the histogram pass's counts
-    int bins;
-    float lo_f, s_f, lo_m;                       // s_f: "Similarity measures"' float scale of the fixed bin
-    double s_m;                                  // parzen_scale(lo_m, hi_m, bins)
+    ParzenArgs z;                                // W: the record pass
     unsigned long long *hist;                    // histogram pass: [bins][bins], zeroed by the launcher
-    const double *W;                             // record pass: [bins][bins]
     const float *field;                          // histogram pass, FIELD == true: [3][oz][oy][ox]
 };
 
@@ -550,13 +573,14 @@ struct MiArgs {
 //     (profiles/microbench/affine_mi_rate_mi355x.txt, 512^3, one run): 0.847 ms on a lattice with a noise floor, 1.58 x
 //     k_similarity's 0.537 ms; 1.46 ms (B = 32) and 1.29 ms (B = 64) on a sum of wide Gaussians.  A weight of 0
 //     (r == 0: q[3]) is not added.
-// (256, 4): 111 - 126 VGPRs, four waves per SIMD, no scratch (the masked kernels keep 17 - 18 SGPRs in VGPR lanes).
-// FIELD (header, "Mutual-information free-form deformation (Mattes)"): the sample point is k_warp_field's and
-// k_ffd_force's, q = p + u(p) with u read from s.field (three more coalesced loads per voxel in the place of pull()'s
-// arithmetic; a lane past the grid reads nothing and takes u = 0); everything after q is the same code.  115 - 126
-// VGPRs, four waves per SIMD, no scratch, but <1, false, true> (unmasked, nx == 1), which spills 4 VGPRs there and is
-// bounded to three waves instead (132 VGPRs, no scratch).  FIELD == false compiles to what it compiled to before the
-// parameter existed (the same resource usage and the same code size, function by function).  Measured
+// The front-end is tile_front's, written out here with the field loaded before F: on tile_front one line of
+// ffd_mi_rate.py (parzen_hist_affine, B = 32) came out 0.4 % slower than the parent's spread allows
+// (profiles/microbench/registration_front_end_mi355x.txt), so the kernel kept its body.
+// (256, 4): 111 - 126 VGPRs, four waves per SIMD, no scratch (-Rpass-analysis=kernel-resource-usage).
+// FIELD (header, "Mutual-information free-form deformation (Mattes)"): q = p + u(p) with u read from s.field (three
+// more coalesced loads per voxel in the place of pull()'s arithmetic; a lane past the grid reads nothing and takes
+// u = 0); everything after q is the same code.  115 - 126 VGPRs, four waves per SIMD, no scratch, but <1, false, true>
+// (unmasked, nx == 1), which spills 4 VGPRs there and is bounded to three waves instead (132 VGPRs, no scratch).  Measured
 // (profiles/microbench/ffd_mi_rate_mi355x.txt, 512^3, kernel trace, min of 5, one run, the field being the export of
 // the same affine map): 1.004 - 1.014 ms on the lattice with a noise floor, 1.16 x the affine kernel's 0.862 -
 // 0.874 ms (12 B more read per voxel); 1.50 ms (B = 32) and 1.34 ms (B = 64) on the sum of wide Gaussians, 1.04 -
@@ -568,7 +592,7 @@ __global__ __launch_bounds__(256, FIELD && LINEAR == 1 && !MASKED ? 3 : 4) void 
     unsigned long long *h = reinterpret_cast<unsigned long long *>(mi_lds);
     __shared__ unsigned long long cslot[4];
     const GridArgs &p = s.a.g;
-    const int B = s.bins, BB = B * B;
+    const int B = s.z.bins, BB = B * B;
     for (int i = threadIdx.x; i < BB; i += 256)
         h[i] = 0ull;
     __syncthreads();
@@ -624,8 +648,8 @@ __global__ __launch_bounds__(256, FIELD && LINEAR == 1 && !MASKED ? 3 : 4) void 
             int k0, out;
             uint32_t q[4];
             double dw[4];
-            parzen_window(m[k], s.lo_m, s.s_m, B, &k0, q, dw, &out);
-            unsigned long long *w = h + parzen_fixed_bin(f[k], s.lo_f, s.s_f, B) * B + k0;      // k0 + 3 <= B - 1
+            parzen_window(m[k], s.z.lo_m, s.z.s_m, B, &k0, q, dw, &out);
+            unsigned long long *w = h + parzen_fixed_bin(f[k], s.z.lo_f, s.z.s_f, B) * B + k0;      // k0 + 3 <= B - 1
             if (counted) {
                 cnt += 1;
 #pragma unroll
@@ -656,36 +680,26 @@ __global__ __launch_bounds__(256) void k_parzen_hist_finish(const unsigned long 
         count[0] = c;
 }
 
-// The MI record: k_affine_normal's body, operation for operation, with G_d = psi * g_d and E = -1 (S_ee becomes
-// S_pp = sum psi psi), so the partial slots, the finish kernel (k_affine_normal_finish) and the record's layout are
-// that kernel's.  W comes into LDS once per workgroup (dynamic: B * B * 8 bytes, 32 KiB at B = 64, beside the 2.3 KiB
-// of slots: two workgroups per CU fit, as many as the registers allow).  psi of the lane's four outputs is formed right
-// after the gathers, before the accumulation block, so the window's temporaries are dead when the tile sums are live;
-// m and f are dead after it too.
-// Registers, as reported by -Rpass-analysis=kernel-resource-usage.  Written plainly the kernel spills 2 - 20 VGPRs at
-// (256, 2); two measures bring it to 256 VGPRs, two waves per SIMD and no scratch in <2, false>, <1, false> and
-// <2, true>: a scheduling barrier after each output's psi, so that the four windows' temporaries are not live together,
-// and the four `counted` flags kept as bits of one VGPR across the gathers instead of four lane masks (8 SGPRs; the
-// masked kernels keep 20 SGPRs in VGPR lanes, not in scratch).  <1, true> (masked, nx == 1: a moving volume one
-// voxel wide) still spills 4 VGPRs there and is bounded to one wave per SIMD instead: 256 VGPRs + 3 AGPRs, no scratch.
+// The MI record: the MSD record's sums (tile_samples, tile_add, fold_pair / fold_row, record_slots) with
+// G_d = psi * g_d and E = -1 (S_ee becomes S_pp = sum psi psi), so the partial slots, the finish kernel
+// (k_affine_normal_finish) and the record's layout are k_affine_normal's.  W comes into LDS once per workgroup
+// (parzen_table; dynamic: B * B * 8 bytes, 32 KiB at B = 64, beside the 2.3 KiB of slots: two workgroups per CU fit, as
+// many as the registers allow).  psi of the lane's four outputs (parzen_psi) is formed right after the gathers, before
+// the accumulation block, so the window's temporaries are dead when the tile sums are live; m and f are dead after it
+// too.
+// Registers, as reported by -Rpass-analysis=kernel-resource-usage: 255 - 256 VGPRs, two waves per SIMD and no scratch
+// in <2, false>, <1, false> and <2, true>, with a scheduling barrier after each output's psi, so that the four windows'
+// temporaries are not live together (without it the kernel spills).  <1, true> (masked, nx == 1: a moving volume one
+// voxel wide) still spills there and is bounded to one wave per SIMD instead: 256 VGPRs + 7 AGPRs, no scratch.
 // Measured (the same file): 1.15 ms per pass at 512^3 (B = 32; 1.17 ms at B = 64), 1.30 x k_affine_normal's 0.883 ms in
 // the same run, on either content.
 template <int LINEAR, bool MASKED>
 __global__ __launch_bounds__(256, LINEAR == 1 && MASKED ? 1 : 2) void k_affine_mi_normal(const MiArgs sm)
 {
     extern __shared__ __align__(16) unsigned char mi_lds[];
-    const double *W = reinterpret_cast<const double *>(mi_lds);
-    __shared__ double slot[AFF_SUMS * 4];
-    __shared__ unsigned long long cslot[4];
     const AffArgs &s = sm.a;
     const GridArgs &p = s.g;
-    const int B = sm.bins;
-    {
-        double *Wl = reinterpret_cast<double *>(mi_lds);
-        for (int i = threadIdx.x; i < B * B; i += 256)
-            Wl[i] = sm.W[i];
-    }
-    __syncthreads();
+    const double *W = parzen_table(sm.z, reinterpret_cast<double *>(mi_lds));
     const int lx = threadIdx.x & 15;
     unsigned long long cnt = 0;
     double see = 0.0;
@@ -697,62 +711,18 @@ __global__ __launch_bounds__(256, LINEAR == 1 && MASKED ? 1 : 2) void k_affine_m
         int xt, y, z;
         if (!tile_at(p, base, xt, y, z))
             break;
-        const bool row = y < p.oy && z < p.oz;
-        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
-        const double yd = (double)y, zd = (double)z;
-        const double rx = pull_row(s.a, yd, zd), ry = pull_row(s.a + 4, yd, zd), rz = pull_row(s.a + 8, yd, zd);
-        // MASKED: as k_affine_normal's, the mask values first, kept as four flags
-        bool ok[4] = {true, true, true, true};
-        if (MASKED) {
-            float wf[4], wm[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int x = xt + lx + 16 * k;
-                const double xd = (double)x;
-                const double qx = pull(s.a, xd, rx), qy = pull(s.a + 4, xd, ry), qz = pull(s.a + 8, xd, rz);
-                wf[k] = s.w.wf && row && x < p.ox ? s.w.wf[orow + (size_t)x] : 1.0f;
-                wm[k] = s.w.wm ? s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)] : 1.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                ok[k] = mask_in(wf[k]) && mask_in(wm[k]);
-        }
-        Taps tp[4];
-        float f[4];
-        bool live[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int x = xt + lx + 16 * k;
-            live[k] = row && x < p.ox;
-            f[k] = live[k] ? s.F[orow + (size_t)x] : 0.0f;
-            const double xd = (double)x;
-            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, pull(s.a, xd, rx), pull(s.a + 4, xd, ry), pull(s.a + 8, xd, rz));
-        }
-        // which of the four outputs are counted, as bits of one register: kept as four lane masks across the gathers
-        // they cost eight SGPRs, and the masked kernels then spill
-        unsigned counted_bits = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            counted_bits |= (MASKED ? live[k] && tp[k].in && ok[k] : live[k] && tp[k].in) ? 1u << k : 0u;
-        float m[4], gx[4], gy[4], gz[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            m[k] = gather_grad<LINEAR>(p.src, tp[k], &gx[k], &gy[k], &gz[k]);
-        // psi = s_m * sum_k dw[k] W[b_f][k0 + k], 0 for a voxel outside the moving range or not counted
+        TileSamples t;
+        tile_samples<LINEAR, MASKED>(s, xt, y, z, lx, t);
+        // psi (parzen_psi), 0 for a voxel outside the moving range or not counted
         double psi[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const bool counted = counted_bits >> k & 1u;
-            int k0, out;
-            uint32_t q[4];
-            double dw[4];
-            parzen_window(m[k], sm.lo_m, sm.s_m, B, &k0, q, dw, &out);
-            const double *w = W + parzen_fixed_bin(f[k], sm.lo_f, sm.s_f, B) * B + k0;          // k0 + 3 <= B - 1
-            const double v = sm.s_m * (((dw[0] * w[0] + dw[1] * w[1]) + dw[2] * w[2]) + dw[3] * w[3]);
-            psi[k] = counted && !out ? v : 0.0;
+            int out;
+            const double v = parzen_psi(sm.z, W, t.f[k], t.m[k], &out);
+            psi[k] = t.counted[k] && !out ? v : 0.0;
             __builtin_amdgcn_sched_barrier(0);                               // one window's temporaries at a time
         }
-        const double Y = yd - s.cy, Z = zd - s.cz;
+        // tile sums: 0 .. 5 the pairs G_d G_e, 6 + d: G_d E
         double s0[9], s1[9], s2[6];
 #pragma unroll
         for (int i = 0; i < 9; i++)
@@ -762,9 +732,9 @@ __global__ __launch_bounds__(256, LINEAR == 1 && MASKED ? 1 : 2) void k_affine_m
             s2[i] = 0.0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const bool counted = counted_bits >> k & 1u;
+            const bool counted = t.counted[k];
             const double E = counted ? -1.0 : 0.0;
-            const double G[3] = {psi[k] * (double)gx[k], psi[k] * (double)gy[k], psi[k] * (double)gz[k]};
+            const double G[3] = {psi[k] * (double)t.gx[k], psi[k] * (double)t.gy[k], psi[k] * (double)t.gz[k]};
             const double X = (double)(xt + lx + 16 * k) - s.cx;
             cnt += counted ? 1u : 0u;
             see += psi[k] * psi[k];
@@ -773,64 +743,42 @@ __global__ __launch_bounds__(256, LINEAR == 1 && MASKED ? 1 : 2) void k_affine_m
 #pragma unroll
                 for (int e2 = d; e2 < 3; e2++) {
                     const int i = pair3(d, e2);
-                    const double w = G[d] * G[e2];
-                    const double wx = w * X;
-                    s0[i] += w;
-                    s1[i] += wx;
-                    s2[i] += wx * X;
+                    tile_add(G[d] * G[e2], X, s0[i], s1[i], s2[i]);
                 }
-                const double w = G[d] * E;
-                s0[6 + d] += w;
-                s1[6 + d] += w * X;
+                tile_add(G[d] * E, X, s0[6 + d], s1[6 + d]);
             }
         }
+        const double Y = (double)y - s.cy, Z = (double)z - s.cz;
         const double YY = Y * Y, YZ = Y * Z, ZZ = Z * Z;
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-            double *h = acc + 10 * i;
-            h[0] += s2[i];                                                   // X X
-            h[1] += s1[i] * Y;                                               // X Y
-            h[2] += s1[i] * Z;                                               // X Z
-            h[3] += s1[i];                                                   // X 1
-            h[4] += s0[i] * YY;
-            h[5] += s0[i] * YZ;
-            h[6] += s0[i] * Y;
-            h[7] += s0[i] * ZZ;
-            h[8] += s0[i] * Z;
-            h[9] += s0[i];
-        }
+        for (int i = 0; i < 6; i++)
+            fold_pair(acc + 10 * i, s0[i], s1[i], s2[i], Y, Z, YY, YZ, ZZ);
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            double *b = acc + AFF_H + 4 * d;
-            b[0] += s1[6 + d];
-            b[1] += s0[6 + d] * Y;
-            b[2] += s0[6 + d] * Z;
-            b[3] += s0[6 + d];
-        }
+        for (int d = 0; d < 3; d++)
+            fold_row(acc + AFF_H + 4 * d, s0[6 + d], s1[6 + d], Y, Z);
     }
-    // as k_affine_normal: the wave by butterfly, then the four waves' values through LDS as ((w0 + w1) + w2) + w3
-    const int wave = threadIdx.x >> 6;
-    const bool lead = (threadIdx.x & 63) == 0;
-#pragma unroll
-    for (int i = 0; i < AFF_SUMS; i++) {
-        const double v = wave_sum(i < AFF_H + AFF_B ? acc[i] : see);
-        if (lead)
-            slot[4 * i + wave] = v;
-    }
-    cnt = wave_sum(cnt);
-    if (lead)
-        cslot[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x < AFF_SUMS) {
-        const double *v = slot + 4 * threadIdx.x;
-        s.part[(size_t)threadIdx.x * AFF_GRID + blockIdx.x] = ((v[0] + v[1]) + v[2]) + v[3];
-    } else if (threadIdx.x == AFF_SUMS) {
-        reinterpret_cast<unsigned long long *>(s.part)[(size_t)AFF_SUMS * AFF_GRID + blockIdx.x] =
-            ((cslot[0] + cslot[1]) + cslot[2]) + cslot[3];
-    }
+    record_slots<AFF_SUMS>(s.part, [&](int i) { return i < AFF_H + AFF_B ? acc[i] : see; }, cnt);
 }
 
 } // namespace
+
+// What the launchers below share: the grid of F over M, the map, F's centre, the partial slots and the masks.  false:
+// the grid is too large.  A == NULL (the histogram through a field): the map is not read.
+static bool aff_args(AffArgs &s, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                     const double *A, void *d_work, const float *d_WF, const float *d_WM)
+{
+    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+        return false;
+    for (int i = 0; i < 12; i++)
+        s.a[i] = A ? A[i] : 0.0;
+    s.cx = (double)(ox - 1) / 2.0;
+    s.cy = (double)(oy - 1) / 2.0;
+    s.cz = (double)(oz - 1) / 2.0;
+    s.F = d_F;
+    s.part = (double *)d_work;
+    s.w = MaskArgs{d_WF, d_WM};
+    return true;
+}
 
 // Launcher for sift3d_affine_refine.c, which has checked every argument (not exported from the library).  d_WF, d_WM:
 // the masks or NULL; with both NULL the unmasked kernels run.
@@ -839,22 +787,11 @@ extern "C" int sift3d_affine_normal_launch(const char *fn, const float *d_F, int
                                            void *stream, const float *d_WF, const float *d_WM)
 {
     AffArgs s;
-    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+    if (!aff_args(s, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_work, d_WF, d_WM))
         return launch_fail(fn, "grid too large");
-    for (int i = 0; i < 12; i++)
-        s.a[i] = A[i];
-    s.cx = (double)(ox - 1) / 2.0;
-    s.cy = (double)(oy - 1) / 2.0;
-    s.cz = (double)(oz - 1) / 2.0;
-    s.F = d_F;
-    s.part = (double *)d_work;
-    const unsigned grid = s.g.ntiles < AFF_GRID ? s.g.ntiles : AFF_GRID;
+    const unsigned grid = reduce_grid(s.g.ntiles);
     hipStream_t st = (hipStream_t)stream;
-    s.w = MaskArgs{d_WF, d_WM};
-    const bool masked = d_WF || d_WM;
-    void (*k)(const AffArgs) = masked ? (nx >= 2 ? k_affine_normal<2, true> : k_affine_normal<1, true>)
-                                      : (nx >= 2 ? k_affine_normal<2, false> : k_affine_normal<1, false>);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_affine_normal, nx, d_WF || d_WM), dim3(grid), dim3(256), 0, st, s);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_affine_normal_finish, dim3(AFF_STATS), dim3(256), 0, st, (const double *)d_work, grid,
                        (double *)d_record);
@@ -866,11 +803,8 @@ extern "C" int sift3d_affine_normal_launch(const char *fn, const float *d_F, int
 template <int PART>
 static int ncc_pass(const AffArgs &s, unsigned grid, hipStream_t st)
 {
-    const bool masked = s.w.wf || s.w.wm, linear = s.g.nx >= 2;
-    void (*k)(const AffArgs) =
-        masked ? (linear ? k_affine_ncc_normal<2, true, PART> : k_affine_ncc_normal<1, true, PART>)
-               : (linear ? k_affine_ncc_normal<2, false, PART> : k_affine_ncc_normal<1, false, PART>);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_affine_ncc_normal, s.g.nx, s.w.wf || s.w.wm, PART), dim3(grid), dim3(256), 0,
+                       st, s);
     LAUNCH_CHECK();
     return SIFT3D_SUCCESS;
 }
@@ -882,17 +816,9 @@ extern "C" int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F,
                                                const float *d_WM)
 {
     AffArgs s;
-    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+    if (!aff_args(s, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_work, d_WF, d_WM))
         return launch_fail(fn, "grid too large");
-    for (int i = 0; i < 12; i++)
-        s.a[i] = A[i];
-    s.cx = (double)(ox - 1) / 2.0;
-    s.cy = (double)(oy - 1) / 2.0;
-    s.cz = (double)(oz - 1) / 2.0;
-    s.F = d_F;
-    s.part = (double *)d_work;
-    s.w = MaskArgs{d_WF, d_WM};
-    const unsigned grid = s.g.ntiles < AFF_GRID ? s.g.ntiles : AFF_GRID;
+    const unsigned grid = reduce_grid(s.g.ntiles);
     hipStream_t st = (hipStream_t)stream;
 #ifndef SIFT3D_AFFINE_NCC_ONE_KERNEL
     if (ncc_pass<1>(s, grid, st) || ncc_pass<2>(s, grid, st))
@@ -908,33 +834,6 @@ extern "C" int sift3d_affine_ncc_normal_launch(const char *fn, const float *d_F,
 }
 
 // ---- Mattes mutual information: the launchers of sift3d_hip_parzen_hist_affine and sift3d_hip_affine_mi_normal_eqs ----
-// A == NULL: the histogram through a field (the pull map is not read)
-static bool mi_args(MiArgs &m, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
-                    const double *A, int bins, float lo_f, float s_f, float lo_m, float hi_m, void *d_work,
-                    const float *d_WF, const float *d_WM)
-{
-    AffArgs &s = m.a;
-    if (!grid_args(s.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
-        return false;
-    for (int i = 0; i < 12; i++)
-        s.a[i] = A ? A[i] : 0.0;
-    s.cx = (double)(ox - 1) / 2.0;
-    s.cy = (double)(oy - 1) / 2.0;
-    s.cz = (double)(oz - 1) / 2.0;
-    s.F = d_F;
-    s.part = (double *)d_work;
-    s.w = MaskArgs{d_WF, d_WM};
-    m.bins = bins;
-    m.lo_f = lo_f;
-    m.s_f = s_f;
-    m.lo_m = lo_m;
-    m.s_m = parzen_scale(lo_m, hi_m, bins);
-    m.hist = nullptr;
-    m.W = nullptr;
-    m.field = nullptr;
-    return true;
-}
-
 // d_hist [bins][bins] and d_count are zeroed / written on the stream; d_work: SIFT3D_AMD_SIMILARITY_GRID counts.
 // The pull map is A, or with A == NULL the field d_field [3][oz][oy][ox] (sift3d_hip_parzen_hist_field, the MI FFD
 // driver).
@@ -946,17 +845,15 @@ extern "C" int sift3d_parzen_hist_launch(const char *fn, const float *d_F, int o
                                          const float *d_WM)
 {
     MiArgs m;
-    if (!mi_args(m, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m, d_work, d_WF, d_WM))
+    if (!aff_args(m.a, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_work, d_WF, d_WM))
         return launch_fail(fn, "grid too large");
+    m.z = parzen_args(bins, lo_f, s_f, lo_m, hi_m, nullptr);
     m.hist = d_hist;
     m.field = d_field;
-    const unsigned grid = m.a.g.ntiles < AFF_GRID ? m.a.g.ntiles : AFF_GRID;
-    const bool masked = d_WF || d_WM, linear = nx >= 2;
-    void (*k)(const MiArgs) =
-        A ? (masked ? (linear ? k_parzen_hist<2, true> : k_parzen_hist<1, true>)
-                    : (linear ? k_parzen_hist<2, false> : k_parzen_hist<1, false>))
-          : (masked ? (linear ? k_parzen_hist<2, true, true> : k_parzen_hist<1, true, true>)
-                    : (linear ? k_parzen_hist<2, false, true> : k_parzen_hist<1, false, true>));
+    const unsigned grid = reduce_grid(m.a.g.ntiles);
+    const bool masked = d_WF || d_WM;
+    void (*k)(const MiArgs) = A ? PICK_LINEAR_MASKED(k_parzen_hist, nx, masked, false)
+                                : PICK_LINEAR_MASKED(k_parzen_hist, nx, masked, true);
     const size_t hb = (size_t)bins * bins * sizeof(unsigned long long);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(d_hist, 0, hb, st));
@@ -976,15 +873,15 @@ extern "C" int sift3d_affine_mi_normal_launch(const char *fn, const float *d_F, 
                                               const float *d_WM)
 {
     MiArgs m;
-    if (!mi_args(m, d_F, ox, oy, oz, d_M, nx, ny, nz, A, bins, lo_f, s_f, lo_m, hi_m, d_work, d_WF, d_WM))
+    if (!aff_args(m.a, d_F, ox, oy, oz, d_M, nx, ny, nz, A, d_work, d_WF, d_WM))
         return launch_fail(fn, "grid too large");
-    m.W = d_W;
-    const unsigned grid = m.a.g.ntiles < AFF_GRID ? m.a.g.ntiles : AFF_GRID;
-    const bool masked = d_WF || d_WM, linear = nx >= 2;
-    void (*k)(const MiArgs) = masked ? (linear ? k_affine_mi_normal<2, true> : k_affine_mi_normal<1, true>)
-                                     : (linear ? k_affine_mi_normal<2, false> : k_affine_mi_normal<1, false>);
+    m.z = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
+    m.hist = nullptr;
+    m.field = nullptr;
+    const unsigned grid = reduce_grid(m.a.g.ntiles);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), (size_t)bins * bins * sizeof(double), st, m);
+    hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_affine_mi_normal, nx, d_WF || d_WM), dim3(grid), dim3(256),
+                       (size_t)bins * bins * sizeof(double), st, m);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_affine_normal_finish, dim3(AFF_STATS), dim3(256), 0, st, (const double *)d_work, grid,
                        (double *)d_record);

@@ -9,7 +9,8 @@
 //     plane and channel leaves with one coalesced 256-byte store, no exchange through LDS.  The contract's sum (64
 //     terms of 3 multiplies and an add, per channel, unfused) is 768 VALU operations per voxel against 12 B written:
 //     the kernel is bound by VALU work and by the 192 lattice loads per voxel (L1 hits), not by HBM.
-//   - evaluation: k_ffd_force is k_affine_normal's walk with k_warp_field's taps (the field is read, not the spline):
+//   - evaluation: k_ffd_force is k_similarity's walk through a field (the field is read, not the spline; the
+//     front-end is written out in it, k_ffd_mi_force calls sift3d_resample.h's tile_front):
 //     per counted voxel e = m - f and the gradient (gather_grad), n and S_ee reduced as the affine pass does, and the
 //     force E G_d (exact in double) stored, three doubles per voxel.  The adjoint of the spline is SEPARABLE:
 //     k_ffd_adjoint sums one axis, sum_x w(x, i) v(x) in ascending x, one lane per output, and is launched for z, then
@@ -28,7 +29,7 @@
 
 namespace {
 
-constexpr unsigned FFD_GRID = SIFT3D_AMD_SIMILARITY_GRID;
+constexpr unsigned FFD_GRID = REDUCE_GRID;
 
 struct FfdLattice {
     const float *c;                              // [3][gz][gy][gx]
@@ -112,8 +113,12 @@ struct FfdForceArgs {
     MaskArgs w;                                  // MASKED == true: wf on F's grid, wm on M's; either may be null
 };
 
-// MASKED (header, "Masks"): as k_similarity's; the force at a masked-out voxel is 0 like an outside one's.
-// MASKED == false compiles to what it compiled to before the parameter existed.
+// MASKED (header, "Masks"): the force at a masked-out voxel is 0 like an outside one's.
+// This kernel keeps its own front-end (tile_front's with the field loaded before F): on tile_front it compiled to
+// fewer registers (k_ffd_force<2, true>: 132 -> 123 VGPRs, 3 -> 4 waves per SIMD) and ran 3 % slower on the masked
+// evaluation of mask_rate.py (profiles/microbench/registration_front_end_mi355x.txt).
+// As reported by -Rpass-analysis=kernel-resource-usage: 120 - 132 VGPRs with nx >= 2 (four waves per SIMD unmasked,
+// three masked), 129 - 158 and three waves with nx == 1; no scratch.
 template <int LINEAR, bool MASKED>
 __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
 {
@@ -185,19 +190,16 @@ __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
 // ---- the force of the mutual information (header, "Mutual-information free-form deformation (Mattes)") ------------
 struct FfdMiForceArgs {
     FfdForceArgs f;                              // part: S_pp, then the count
-    int bins;
-    float lo_f, s_f, lo_m;                       // s_f: "Similarity measures"' float scale of the fixed bin
-    double s_m;                                  // parzen_scale(lo_m, hi_m, bins)
-    const double *W;                             // [bins][bins]
+    ParzenArgs z;
 };
 
-// k_ffd_force's walk and stores with the force E G'_d = -(psi * g_d) in the place of E G_d, psi as k_affine_mi_normal
-// forms it (sift3d_parzen.h's window, W from LDS), and S_pp = sum psi psi in the slot of S_ee.  W comes into dynamic LDS
-// once per workgroup: B * B * 8 bytes, 32 KiB at B = 64, so five workgroups fit a CU's 160 KiB.  A voxel that is not
+// k_ffd_force's sums and stores on tile_front, with the force E G'_d = -(psi * g_d) in the place of E G_d, psi being
+// sift3d_parzen.h's parzen_psi (W from LDS), and S_pp = sum psi psi in the slot of S_ee.  W comes into dynamic LDS once
+// per workgroup: B * B * 8 bytes, 32 KiB at B = 64, so five workgroups fit a CU's 160 KiB.  A voxel that is not
 // counted, and a counted one outside the moving range (psi = 0), store +0.
 // (256, 4): 124 - 128 VGPRs, no AGPRs, four waves per SIMD and no scratch in all four instantiations
 // (-Rpass-analysis=kernel-resource-usage): there are no 72 accumulators here, so the window's temporaries and the four
-// outputs' taps fit where k_affine_mi_normal needed two waves and scheduling barriers.
+// outputs' taps fit where k_affine_mi_normal needs two waves and scheduling barriers.
 // Measured (profiles/microbench/ffd_mi_rate_mi355x.txt, 512^3, kernel trace, min of 5, one run): 1.29 - 1.35 ms at
 // B = 32 and 64 on either content, 0.996 - 1.001 x k_ffd_force's 1.30 - 1.35 ms in the same run (spread of a kernel
 // 1 %; an earlier run of the same script gave 1.42 - 1.44 ms for both kernels, the same quotients); both are 1.75 -
@@ -207,18 +209,11 @@ template <int LINEAR, bool MASKED>
 __global__ __launch_bounds__(256, 4) void k_ffd_mi_force(const FfdMiForceArgs sm)
 {
     extern __shared__ __align__(16) unsigned char ffd_lds[];
-    const double *W = reinterpret_cast<const double *>(ffd_lds);
     __shared__ double s_spp[4];
     __shared__ unsigned long long s_cnt[4];
     const FfdForceArgs &s = sm.f;
     const GridArgs &p = s.g;
-    const int B = sm.bins;
-    {
-        double *Wl = reinterpret_cast<double *>(ffd_lds);
-        for (int i = threadIdx.x; i < B * B; i += 256)
-            Wl[i] = sm.W[i];
-    }
-    __syncthreads();
+    const double *W = parzen_table(sm.z, reinterpret_cast<double *>(ffd_lds));
     const int lx = threadIdx.x & 15;
     const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;
     unsigned long long cnt = 0;
@@ -227,52 +222,23 @@ __global__ __launch_bounds__(256, 4) void k_ffd_mi_force(const FfdMiForceArgs sm
         int xt, y, z;
         if (!tile_at(p, base, xt, y, z))
             break;
-        const bool row = y < p.oy && z < p.oz;
-        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
-        Taps tp[4];
-        float f[4];
-        bool live[4];
-        float wf[4], wm[4];                                                  // MASKED only
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int x = xt + lx + 16 * k;
-            live[k] = row && x < p.ox;
-            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-            f[k] = 0.0f;
-            wf[k] = wm[k] = 1.0f;
-            if (live[k]) {
-                const float *u = s.field + orow + (size_t)x;
-                ux = u[0];
-                uy = u[ovox];
-                uz = u[2 * ovox];
-                f[k] = s.F[orow + (size_t)x];
-                if (MASKED && s.w.wf)
-                    wf[k] = s.w.wf[orow + (size_t)x];
-            }
-            const double qx = (double)x + (double)ux, qy = (double)y + (double)uy, qz = (double)z + (double)uz;
-            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
-            if (MASKED && s.w.wm)
-                wm[k] = s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
-        }
+        TileFront t;
+        tile_front<LINEAR, true, MASKED>(p, nullptr, s.field, s.F, s.w, xt, y, z, t);
         float m[4], gx[4], gy[4], gz[4];
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            m[k] = gather_grad<LINEAR>(p.src, tp[k], &gx[k], &gy[k], &gz[k]);
+            m[k] = gather_grad<LINEAR>(p.src, t.tp[k], &gx[k], &gy[k], &gz[k]);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const bool counted = MASKED ? live[k] && tp[k].in && mask_in(wf[k]) && mask_in(wm[k]) : live[k] && tp[k].in;
-            int k0, out;
-            uint32_t q[4];
-            double dw[4];
-            parzen_window(m[k], sm.lo_m, sm.s_m, B, &k0, q, dw, &out);
-            const double *w = W + parzen_fixed_bin(f[k], sm.lo_f, sm.s_f, B) * B + k0;          // k0 + 3 <= B - 1
-            const double v = sm.s_m * (((dw[0] * w[0] + dw[1] * w[1]) + dw[2] * w[2]) + dw[3] * w[3]);
+            const bool counted = tile_counted<MASKED>(t, k);
+            int out;
+            const double v = parzen_psi(sm.z, W, t.f[k], m[k], &out);
             const bool on = counted && !out;
             const double psi = on ? v : 0.0;
             cnt += counted ? 1u : 0u;
             spp += psi * psi;
-            if (live[k]) {
-                double *o = s.force + orow + (size_t)(xt + lx + 16 * k);
+            if (t.live[k]) {
+                double *o = s.force + t.orow + (size_t)(xt + lx + 16 * k);
                 o[0] = on ? -(psi * (double)gx[k]) : 0.0;                    // one rounding; the sign is exact
                 o[ovox] = on ? -(psi * (double)gy[k]) : 0.0;
                 o[2 * ovox] = on ? -(psi * (double)gz[k]) : 0.0;
@@ -550,22 +516,16 @@ extern "C" int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int g
 // term); the MI driver runs FFD_BEND_VALUE per evaluation and the other three only where a step starts.
 enum { FFD_IMAGE = 1, FFD_BEND_VALUE = 2, FFD_BEND_GRAD = 4, FFD_COMBINE = 8, FFD_ALL = 15 };
 
-// what the MI force needs beside the MSD force's arguments (NULL: the MSD)
-struct FfdMi {
-    int bins;
-    float lo_f, s_f, lo_m, hi_m;
-    const double *W;                             // device, [bins][bins]
-};
-
 // d_rec: {uint64 n; double S_ee, R, gmax} then Gc and dR, [3][gz][gy][gx] doubles each.  d_work: partial slots
 // [2][FFD_GRID] doubles, then the force [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox], D [18][N] doubles.
 // d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.  FFD_BEND_GRAD reads the D that the
-// last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.
-static int ffd_evaluate_parts(const char *fn, unsigned parts, const FfdMi *mi, const float *d_F, int ox, int oy, int oz,
-                              const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat,
-                              int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
-                              double bending, double *d_rec, float *d_grad, double *d_work, void *stream,
-                              const float *d_WF, const float *d_WM)
+// last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.  mi: what the MI
+// force needs beside the MSD force's arguments (NULL: the MSD).
+static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const float *d_F, int ox, int oy,
+                              int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
+                              const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
+                              const double *stencils, double bending, double *d_rec, float *d_grad, double *d_work,
+                              void *stream, const float *d_WF, const float *d_WM)
 {
     hipStream_t st = (hipStream_t)stream;
     const size_t vox = (size_t)ox * oy * oz, cvox = (size_t)gx * gy * gz;
@@ -582,24 +542,15 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const FfdMi *mi, c
         f.field = d_field;
         f.force = force;
         f.part = part;
-        const unsigned grid = f.g.ntiles < FFD_GRID ? f.g.ntiles : FFD_GRID;
+        const unsigned grid = reduce_grid(f.g.ntiles);
         f.w = MaskArgs{d_WF, d_WM};
         const bool masked = d_WF || d_WM;
         if (mi) {
-            fm.bins = mi->bins;
-            fm.lo_f = mi->lo_f;
-            fm.s_f = mi->s_f;
-            fm.lo_m = mi->lo_m;
-            fm.s_m = parzen_scale(mi->lo_m, mi->hi_m, mi->bins);
-            fm.W = mi->W;
-            void (*km)(const FfdMiForceArgs) =
-                masked ? (nx >= 2 ? k_ffd_mi_force<2, true> : k_ffd_mi_force<1, true>)
-                       : (nx >= 2 ? k_ffd_mi_force<2, false> : k_ffd_mi_force<1, false>);
-            hipLaunchKernelGGL(km, dim3(grid), dim3(256), (size_t)mi->bins * mi->bins * sizeof(double), st, fm);
+            fm.z = *mi;
+            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_mi_force, nx, masked), dim3(grid), dim3(256),
+                               (size_t)mi->bins * mi->bins * sizeof(double), st, fm);
         } else {
-            void (*kf)(const FfdForceArgs) = masked ? (nx >= 2 ? k_ffd_force<2, true> : k_ffd_force<1, true>)
-                                                    : (nx >= 2 ? k_ffd_force<2, false> : k_ffd_force<1, false>);
-            hipLaunchKernelGGL(kf, dim3(grid), dim3(256), 0, st, f);
+            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force, nx, masked), dim3(grid), dim3(256), 0, st, f);
         }
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish_count, dim3(1), dim3(256), 0, st, (const unsigned long long *)part + FFD_GRID, grid,
@@ -671,7 +622,7 @@ extern "C" int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, con
                                     float hi_m, const double *d_W, double *d_rec, float *d_grad, double *d_work,
                                     void *stream, const float *d_WF, const float *d_WM)
 {
-    const FfdMi mi = {bins, lo_f, s_f, lo_m, hi_m, d_W};
+    const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
     const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u);
     return ffd_evaluate_parts(fn, parts, &mi, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
                               d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);

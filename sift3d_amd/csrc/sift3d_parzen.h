@@ -1,7 +1,9 @@
 /* sift3d_parzen.h -- the Parzen window of "Mutual-information affine refinement (Mattes)" (include/sift3d_amd.h): the
- * one statement of its arithmetic, compiled into the two kernels (sift3d_affine_refine.hip) and into the host
- * (sift3d_amd_parzen_window in sift3d_affine_refine.c), so that the three cannot drift apart.  Plain C and HIP; every
- * operation in double, in the header's order, unfused (both builds compile with -ffp-contract=off). */
+ * one statement of its arithmetic, compiled into the kernels (k_parzen_hist and k_affine_mi_normal in
+ * sift3d_affine_refine.hip, k_ffd_mi_force in sift3d_ffd.hip) and into the host (sift3d_amd_parzen_window in
+ * sift3d_affine_refine.c), so that they cannot drift apart.  Plain C and HIP; every operation in double, in the
+ * header's order, unfused (both builds compile with -ffp-contract=off).  The kernels' arguments, the table in LDS and
+ * psi, which the record kernel and the FFD's force share, are at the end (HIP only). */
 #ifndef SIFT3D_PARZEN_H
 #define SIFT3D_PARZEN_H
 
@@ -58,5 +60,41 @@ PARZEN_FN void parzen_window(float m, float lo, double s, int B, int *k0, uint32
         dw[3] = t2 / 2.0;
     }
 }
+
+#ifdef __HIPCC__
+/* what a kernel needs of the two histograms' binning, and the table of the record pass and of the FFD's force */
+struct ParzenArgs {
+    int bins;
+    float lo_f, s_f, lo_m;                       /* s_f: "Similarity measures"' float scale of the fixed bin */
+    double s_m;                                  /* parzen_scale(lo_m, hi_m, bins) */
+    const double *W;                             /* [bins][bins] on the device; the histogram pass does not read it */
+};
+
+static inline ParzenArgs parzen_args(int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W)
+{
+    return ParzenArgs{bins, lo_f, s_f, lo_m, parzen_scale(lo_m, hi_m, bins), d_W};
+}
+
+/* W into the workgroup's LDS (bins * bins doubles), once per workgroup; every lane calls it */
+__device__ __forceinline__ const double *parzen_table(const ParzenArgs &z, double *lds)
+{
+    for (int i = threadIdx.x; i < z.bins * z.bins; i += 256)
+        lds[i] = z.W[i];
+    __syncthreads();
+    return lds;
+}
+
+/* psi = s_m * sum_k dw[k] W[b_f][k0 + k] for the fixed value f and the moving value m, W being parzen_table's; *out:
+ * m lies outside the moving range (the caller takes psi = counted && !out ? value : 0) */
+__device__ __forceinline__ double parzen_psi(const ParzenArgs &z, const double *W, float f, float m, int *out)
+{
+    int k0;
+    uint32_t q[4];
+    double dw[4];
+    parzen_window(m, z.lo_m, z.s_m, z.bins, &k0, q, dw, out);
+    const double *w = W + parzen_fixed_bin(f, z.lo_f, z.s_f, z.bins) * z.bins + k0;             /* k0 + 3 <= B - 1 */
+    return z.s_m * (((dw[0] * w[0] + dw[1] * w[1]) + dw[2] * w[2]) + dw[3] * w[3]);
+}
+#endif
 
 #endif

@@ -1,5 +1,6 @@
 // sift3d_resample.h -- the sampling and tiling core of the resampling kernels (sift3d_warp.hip, sift3d_bspline.hip,
-// sift3d_demons.hip).  Every kernel built from these pieces is reproduced bit for bit by a numpy restatement, so
+// sift3d_demons.hip) and of the registration sum kernels (sift3d_similarity.hip, sift3d_affine_refine.hip,
+// sift3d_ffd.hip).  Every kernel built from these pieces is reproduced bit for bit by a numpy restatement, so
 // the order of the arithmetic below is part of the library's contract, and this is the one place that states it:
 //
 //   A (3 x 4, row-major) is a PULL map: output voxel (x, y, z) reads the source at
@@ -9,8 +10,9 @@
 //             in float, along x for the four (y, z) corner rows, then along y, then along z;
 //   nearest : the value at floor(q + 0.5).
 //
-// Everything here is __device__ __forceinline__ or a plain inline host helper: a kernel that uses a piece compiles
-// to what it compiled to when the piece was written out in it.
+// Everything here is __device__ __forceinline__ or a plain inline host helper.  What the compiler made of each kernel
+// before and after a piece moved here is on record: profiles/microbench/resample_refactor_mi355x.txt (the resampling
+// kernels) and registration_front_end_mi355x.txt (the sum kernels).
 #ifndef SIFT3D_RESAMPLE_H
 #define SIFT3D_RESAMPLE_H
 
@@ -272,6 +274,87 @@ __device__ __forceinline__ size_t mask_offset(int nx, int ny, int nz, double qx,
 {
     return taps_at<0>(nx, ny, nz, qx, qy, qz).r00;
 }
+
+// ---- the one-stage tile front-end of the registration sum kernels ---------------------------------------------------
+// k_similarity, k_parzen_hist, k_ffd_force and k_ffd_mi_force walk the fixed grid F as the warps walk their output
+// (tile_at) and reduce instead of storing.  For the lane's four outputs x = xt + lx + 16 k of row (y, z): F, W_F beside
+// it, the sample point q (the affine pull map `a`, or FIELD: p + u(p) with u read from field [3][oz][oy][ox]), the
+// taps of q on the moving grid and W_M at q's nearest voxel, every load issued before the caller's gathers.  An output
+// past the grid reads neither F, nor the field, nor W_F (f = 0, u = 0, w = 1), samples inside M and is not counted.
+// k_ffd_mi_force calls tile_front.  k_similarity, k_parzen_hist and k_ffd_force restate it in their own bodies (the
+// last two with the field loaded before F): each compiled and wrote the same bytes on tile_front, and each had a timing
+// line beyond the parent's spread there (profiles/microbench/registration_front_end_mi355x.txt; their comments).
+// (The record kernels of sift3d_affine_refine.hip have no registers for the masks beside the gathers: tile_samples
+// there is the two-stage form.)
+struct TileFront {
+    Taps tp[4];
+    float f[4];
+    float wf[4], wm[4];                          // MASKED only
+    bool live[4];
+    size_t orow;                                 // the row's offset on the fixed grid
+};
+
+template <int LINEAR, bool FIELD, bool MASKED>
+__device__ __forceinline__ void tile_front(const GridArgs &p, const double *a, const float *field, const float *F,
+                                           const MaskArgs &w, int xt, int y, int z, TileFront &t)
+{
+    const int lx = threadIdx.x & 15;
+    const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;             // FIELD only
+    const bool row = y < p.oy && z < p.oz;
+    const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+    const double yd = (double)y, zd = (double)z;
+    double rx = 0.0, ry = 0.0, rz = 0.0;
+    if (!FIELD) {
+        rx = pull_row(a, yd, zd);
+        ry = pull_row(a + 4, yd, zd);
+        rz = pull_row(a + 8, yd, zd);
+    }
+    t.orow = orow;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x = xt + lx + 16 * k;
+        t.live[k] = row && x < p.ox;
+        t.f[k] = 0.0f;
+        t.wf[k] = t.wm[k] = 1.0f;
+        float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+        if (t.live[k]) {
+            t.f[k] = F[orow + (size_t)x];
+            if (MASKED && w.wf)
+                t.wf[k] = w.wf[orow + (size_t)x];
+            if (FIELD) {
+                const float *u = field + orow + (size_t)x;
+                ux = u[0];
+                uy = u[ovox];
+                uz = u[2 * ovox];
+            }
+        }
+        const double xd = (double)x;
+        const double qx = FIELD ? xd + (double)ux : pull(a, xd, rx);
+        const double qy = FIELD ? yd + (double)uy : pull(a + 4, xd, ry);
+        const double qz = FIELD ? zd + (double)uz : pull(a + 8, xd, rz);
+        t.tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
+        if (MASKED && w.wm)
+            t.wm[k] = w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
+    }
+}
+
+// output k of the tile enters the sums: on the grid, q inside the moving grid and, MASKED, in both masks
+template <bool MASKED>
+__device__ __forceinline__ bool tile_counted(const TileFront &t, int k)
+{
+    return MASKED ? t.live[k] && t.tp[k].in && mask_in(t.wf[k]) && mask_in(t.wm[k]) : t.live[k] && t.tp[k].in;
+}
+
+// ---- launch helpers of those kernels ----------------------------------------------------------------------------------
+// min(tiles, SIFT3D_AMD_SIMILARITY_GRID) workgroups walk the tiles: the size does not depend on the device, so the bits
+// of the sums depend on the shapes only
+constexpr unsigned REDUCE_GRID = SIFT3D_AMD_SIMILARITY_GRID;
+static inline unsigned reduce_grid(unsigned ntiles) { return ntiles < REDUCE_GRID ? ntiles : REDUCE_GRID; }
+
+// K<LINEAR, MASKED, ...> for a linear sample of a moving grid nx wide (2: nx >= 2, 1: nx == 1), with masks or without
+#define PICK_LINEAR_MASKED(K, nx, masked, ...)                                                                         \
+    ((masked) ? ((nx) >= 2 ? K<2, true, ##__VA_ARGS__> : K<1, true, ##__VA_ARGS__>)                                    \
+              : ((nx) >= 2 ? K<2, false, ##__VA_ARGS__> : K<1, false, ##__VA_ARGS__>))
 
 // ---- thin-plate spline: q(p) = affine(p) + (double) s(p), s = sum_i w_i phi(|p - c_i|) ------------------------
 // (contract: include/sift3d_amd.h, "Thin-plate spline").  The radial sum is compute-bound: per voxel-point

@@ -30,7 +30,7 @@
 
 namespace {
 
-constexpr unsigned SIM_GRID = SIFT3D_AMD_SIMILARITY_GRID;
+constexpr unsigned SIM_GRID = REDUCE_GRID;
 constexpr int SIM_STATS = 7;                     // count, sum f, m, ff, mm, fm, dd
 constexpr size_t SIM_SLOT_BYTES = SIM_STATS * 4 * sizeof(double);    // workgroup_reduce: 4 slots per statistic
 
@@ -74,10 +74,14 @@ __device__ __forceinline__ void commit(unsigned *h, int idx, bool counted)
         atomicAdd(h + idx, 1u);
 }
 
-// (256, 4): 4 waves per SIMD, 128 VGPRs, nothing spilled; left to itself the compiler takes 131 (LINEAR) and fits 3.
+// The front-end written out below is the text of sift3d_resample.h's tile_front (this kernel's was taken for it).  On
+// tile_front the kernel compiled to the same registers and occupancy and wrote the same bytes, and one of its twenty
+// timing lines came out 0.0002 ms beyond the parent's spread (profiles/microbench/registration_front_end_mi355x.txt),
+// so it kept its body: what changes in tile_front changes here too, by hand.
+// (256, 4): 116 - 128 VGPRs (LINEAR; 56 - 70 nearest), 4 waves per SIMD, nothing spilled
+// (-Rpass-analysis=kernel-resource-usage); left to itself the compiler takes 131 (LINEAR) and fits 3.
 // MASKED (header, "Masks"): W_F comes in beside F and W_M by one nearest gather per output, issued with the intensity
-// gathers; a voxel whose mask value is below 0.5 is treated as one whose q is outside.  MASKED == false compiles to
-// what it compiled to before the parameter existed.
+// gathers; a voxel whose mask value is below 0.5 is treated as one whose q is outside.
 template <int LINEAR, bool FIELD, bool MASKED>
 __global__ __launch_bounds__(256, 4) void k_similarity(const SimArgs s)
 {
@@ -207,7 +211,7 @@ template <bool FIELD, bool MASKED>
 int run(const char *fn, SimArgs &s, int interp, void *d_stats, void *stream)
 {
     const GridArgs &p = s.g;
-    const unsigned grid = p.ntiles < SIM_GRID ? p.ntiles : SIM_GRID;
+    const unsigned grid = reduce_grid(p.ntiles);
     // uint32 counters: passes * 1024 voxels per workgroup (true for every ntiles grid_args accepts; kept as a check)
     const unsigned long long passes = ((unsigned long long)p.ntiles + grid - 1) / grid;
     if (passes * (unsigned long long)(TX * TY * TZ) > 0xffffffffull)

@@ -79,17 +79,17 @@ def selection_key(family, c):
         return (family, linear_of(c.interp, nx), vec_of(c))
     if family == "compose":                                 # sift3d_warp.hip 712 (linear only: ux >= 2 ? 2 : 1)
         return (family, c.mode, linear_of("linear", nx), c.stats, vec_of(c))
-    if family == "similarity":                              # sift3d_similarity.hip 215 (and 255: FIELD, MASKED)
+    if family == "similarity":                              # sift3d_similarity.hip run(); FIELD, MASKED: its launcher
         return (family, linear_of(c.interp, nx), c.field, masked)
-    if family == "msd":                                     # sift3d_affine_refine.hip 833
+    if family == "msd":                                     # sift3d_affine_normal_launch
         return (family, linear_of("linear", nx), masked)
-    if family == "ncc":                                     # sift3d_affine_refine.hip 849
+    if family == "ncc":                                     # sift3d_affine_refine.hip ncc_pass()
         return (family, linear_of("linear", nx), masked)
-    if family == "parzen":                                  # sift3d_affine_refine.hip 927
+    if family == "parzen":                                  # sift3d_parzen_hist_launch
         return (family, linear_of("linear", nx), masked)
-    if family == "mi":                                      # sift3d_affine_refine.hip 953
+    if family == "mi":                                      # sift3d_affine_mi_normal_launch
         return (family, linear_of("linear", nx), masked)
-    if family == "ffd":                                     # sift3d_ffd.hip 468
+    if family == "ffd":                                     # sift3d_ffd.hip ffd_evaluate_parts()
         return (family, linear_of("linear", nx), masked)
     raise KeyError(family)
 
