@@ -1834,8 +1834,18 @@ SIFT3D_AMD_API int
 sift3d_hip_describe_parts(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp,
                           uint32_t n, uint32_t n_exact, float *d_hist, float *d_hist2, float *d_wlut,
                           void *d_part, void *stream);
-/* Clock probe of the last descriptor launch through d_wlut (the fast kernel; exact != 0: the reference-order
- * one): shader cycles and ticks of the constant 100 MHz counter during which the launch's first -- persistent --
+/* The same with the lattice variant of the fast kernel for the LAST n_lattice records of the list (a launch of
+ * its own behind the generic fast one).  The caller's contract for each of those records: it sits on a voxel
+ * (cx, cy, cz integral), its sd has the bits of its level's sd, and sift3d_hip_describe_lattice_level() of that
+ * level's units and sd is 1.  The variant computes the generic kernel's bits with fewer instructions per voxel;
+ * records that do not qualify belong in front of the range. */
+SIFT3D_AMD_API int sift3d_hip_describe_lattice_level(float ux, float uy, float uz, double sd);
+SIFT3D_AMD_API int
+sift3d_hip_describe_lattice(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp,
+                            uint32_t n, uint32_t n_exact, uint32_t n_lattice, float *d_hist, float *d_hist2,
+                            float *d_wlut, void *d_part, void *stream);
+/* Clock probe of the last descriptor launch through d_wlut (the fast kernel -- its lattice launch when there
+ * was one --; exact != 0: the reference-order one): shader cycles and ticks of the constant 100 MHz counter during which the launch's first -- persistent --
  * wave was alive.  cycles / (ticks / 1e8) = the clock the device held under the kernel.  Blocks on `stream`. */
 SIFT3D_AMD_API int
 sift3d_hip_describe_clock(const float *d_wlut, int nlevels, int exact, uint64_t *cycles, uint64_t *ticks,

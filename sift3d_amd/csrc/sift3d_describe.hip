@@ -115,10 +115,13 @@ __device__ __forceinline__ void wave_sync()
 // x, lanes 1..3 take lane 0's).  The compiler's DPP combiner leaves multiply-accumulates alone (it would emit
 // v_mov_b32_dpp + v_fmac_f32), hence the instruction by name -- and its hazards are the compiler's no longer: a
 // DPP operand must not be read within two wait states of a VALU write to that register, nor within five of a VALU
-// write to EXEC.  ROUND rules both out by construction: x is a record word that a ds_read_b128 delivered (no VALU
-// write; where the compiler copies a chunk, the copy sits behind the previous round's bin write, and this round's
-// bin address and bin read -- two instructions -- come before the multiply), and the commit chain is straight-line
-// code whose EXEC is all ones and is written by the scalar unit only.
+// write to EXEC.  ROUND rules both out by construction: x is a record word that a ds_read_b128 delivered straight
+// into the register the multiply reads -- no VALU instruction writes it: the chunks of a pass alternate between
+// two register sets that are loaded two to four rounds before their first use, so the source holds no copy of a
+// chunk, and no round depends on a bin-address add standing between a copy and the multiply (with the addresses
+// formed off the chain, DESC_OPT 64, the rounds with empty slices have no VALU instruction at all between the bin
+// write and the multiply; the kernel's ISA shows no write to a multiply's x within the ten instructions before
+// it) --, and the commit chain is straight-line code whose EXEC is all ones and is written by the scalar unit only.
 __device__ __forceinline__ float quad_fmac(float acc, float x)
 {
     asm("v_fmac_f32_dpp %0, %1, %1 quad_perm:[3,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1"
@@ -227,7 +230,14 @@ constexpr int DPARTS = 4;   // parts a window is summed in (fast variant; see k_
 // correctly rounded sqrtf (sift.c:1331), the sum of squares of normalize_desc a sequential double sum in
 // element order (sift.c:1407-1416): the histogram is the reference's bit for bit.  Twice the commit rounds:
 // ~1.5x the time per window voxel.
-template <bool EXACT>
+//
+// LATTICE (fast variant only; DESC_OPT 8): every record of the launch sits on a voxel, carries its level's own
+// scale and lives at a level whose weight table qualified (k_desc_wlut) -- the host sorts such records into a
+// range of their own (sift3d_hip_describe_lattice_level, order_keypoints), as it does for EXACT.  These are the
+// conditions the generic kernel tests per wave to use the table; here they hold by contract, so the table is
+// used unconditionally (no expf code in the loop) and the window-relative coordinates come from the integer offsets
+// the table index is formed from (see pass 0).  Every value is the generic kernel's bit for bit.
+template <bool EXACT, bool LATTICE = false>
 __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level *__restrict__ levels,
                                                  const sift3d_hip_kp *__restrict__ kps, uint32_t first,
                                                  uint32_t n,
@@ -259,7 +269,8 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
         sface[(i >> 4) * FACE_STRIDE + (i & 15)] = c_face16[i];
     if (threadIdx.x < 32) {
         soct[threadIdx.x] = c_oct_face[threadIdx.x];
-        sexp[threadIdx.x] = s3d_exp2_tab[threadIdx.x];
+        if (!LATTICE)
+            sexp[threadIdx.x] = s3d_exp2_tab[threadIdx.x];
     }
     __syncthreads();              // the only workgroup barrier: from here on the waves are independent
     // clock probe (round 5): the first wave of the launch lives as long as the kernel (the waves are
@@ -316,7 +327,9 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // the keypoint carries the level's own scale and sits on a voxel
     const float *__restrict__ wtab = nullptr;
     const int icx = (int)K.cx, icy = (int)K.cy, icz = (int)K.cz;
-    if (wlut) {
+    if (LATTICE) {
+        wtab = wlut + (size_t)K.level * WL_STRIDE + WL_HEAD;   // (the host's contract: see above)
+    } else if (wlut) {
         const float *tab = wlut + (size_t)K.level * WL_STRIDE;
         const long long sdbits = ((long long)__float_as_int(tab[3]) << 32) | (unsigned)__float_as_int(tab[2]);
         if (tab[0] == 1.0f && sdbits == __double_as_longlong(K.sd) && (float)icx == K.cx &&
@@ -326,8 +339,9 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
 
     typedef const float __attribute__((address_space(1))) *gfloat_p;
     // (without a table the batch still issues its -- then unused -- weight load: any valid address)
-    const gfloat_p wsrc = wtab ? (gfloat_p)wtab : (gfloat_p) reinterpret_cast<const float *>(levels);
-    const int wmask = wtab ? -1 : 0;
+    const bool have_tab = LATTICE || wtab;
+    const gfloat_p wsrc = have_tab ? (gfloat_p)wtab : (gfloat_p) reinterpret_cast<const float *>(levels);
+    const int wmask = have_tab ? -1 : 0;
 
     const float sigma = (float)(K.sd * 7.071067812);                  // sift.c:1453
     const float rad = (float)(2.0 * (double)sigma);                   // sift.c:1454
@@ -374,7 +388,6 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     const int coff_a = corner4 + (EXACT ? (half == 0 ? 0 : HIST_LDS * 4) : half * (HIST_LDS * 4));
     const int coff_b = corner4 + (half == 1 ? 0 : HIST_LDS * 4);
     (void)coff_b;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
     uint32_t qhead = 0, qtail = 0; // wave-uniform
     bool pend = false;             // registers pv/ppk hold the batch starting at qhead
@@ -406,6 +419,8 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     // their HBM/L2 latency overlaps the previous batch's binning and commit.
     float pv[7] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
     int ppk = 0;
+    // LATTICE: the voxel's offsets from the (integral) centre, kept from the table index for the batch's pass 0
+    int pwi = 0, pwj = 0, pwl = 0;
     // level samples are read through a global-address-space pointer (the pointer comes out of a
     // table in memory, which would otherwise make these flat loads); nx*ny < 2^31
     const gfloat_p gdata = (gfloat_p)L.data;
@@ -425,10 +440,11 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
             // the Gaussian weight is a seventh (L2-resident) load, in flight with the samples
             const int i = x - icx, j = y - icy, l = B.zs + (int)((uint32_t)ppk >> ysh) - icz;
             pv[6] = wtab[i * i + j * j + l * l];
+            pwi = i; pwj = j; pwl = l;
         }
     };
     auto prefetch_weight = [&]() {
-        if (wtab)
+        if (LATTICE || wtab)
             return;
         const int x = B.xs + (int)((uint32_t)ppk & xmask), y = B.ys + (int)(((uint32_t)ppk >> xsh) & ymask);
         const float dx = ((float)x - K.cx) * L.ux;                 // sift.c:102-104
@@ -496,8 +512,15 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
 //     bin fed by a few voxels with a small b0 only agrees with the reference to 1e-5 relative if that
 //     noise is reproduced bit for bit (the FMA / v_rcp_f32 variant was 5 % faster and is not used)
 //   4 window scan: a cheap test with margins decides, the exact one only where a lane is in doubt
+//   8 records that qualify (see LATTICE) take the lattice variant in a launch of their own: table weights
+//     unconditionally, window coordinates from the integer offsets of the table index
+//  (16 was the gradient's three scalings folded into one factor in the lattice variant: no gain, taken out)
+//  32 queue positions of the scan by v_mbcnt (both kernels)
+//  64 the commit's bin addresses formed off the chain, chunk requests behind the bin read (see ROUND)
+// (24-bit forms of the integer multiplies are not an option: v_mul_lo_u32 and v_mad_u64_u32 issue at the rate of
+// v_mul_u32_u24 / v_mad_i32_i24 on this part, profiles/microbench/valu_rate_mi355x.txt)
 #ifndef DESC_OPT
-#define DESC_OPT 7
+#define DESC_OPT 111
 #endif
 // COMMIT_ADD(old, x): old + x * (the OTHER factor of the lane's term, which a lane of its quad holds as ITS x: see
 // "phase B roles").  The other factor is the multiply's DPP operand, no instruction of its own: v_mul_f32_dpp
@@ -510,6 +533,57 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
 #endif
 // a value is computed in the slice that names it here (not sunk to its first use in a later one)
 #define KEEP(v) asm volatile("" ::"v"(v))
+#if (DESC_OPT & 64)
+// Bin addresses off the chain (fast variants): the four LDS addresses of a record chunk -- bin offset + the lane's
+// corner + the histogram's base -- are formed in the slice of the round AFTER the one that requested the chunk (its
+// ds_read_b128 has returned by then: that round waited for its own, later, bin read), two or three rounds before
+// their first use, and the bin is read and written by that address.  A round is then
+//     ds_write_b32 (previous sum) ; ds_read_b32 (bin) | chunk request | slice | s_waitcnt, v_fmac_f32_dpp
+// with no VALU instruction between the write and the dependent read, and the chunk requests behind the bin read
+// instead of ahead of it.  Chunks alternate between two register sets (rounds 0..3 and 8..11 the first, 4..7 and
+// 12..15 the second), so no chunk is ever copied.  EXACT keeps the add in the chain.
+typedef __attribute__((address_space(3))) float *lds_float_p;
+#define LDS_F32(a) (*(lds_float_p)(uintptr_t)(uint32_t)(a))
+#define OFFCHAIN (!EXACT)
+#define CHUNK_ADDR(q)                                                                         \
+    aq_[q] = make_int4(bq_[q].x + coffh, bq_[q].y + coffh, bq_[q].z + coffh, bq_[q].w + coffh); \
+    KEEP(aq_[q].x); KEEP(aq_[q].y); KEEP(aq_[q].z); KEEP(aq_[q].w);
+#define COMMIT_BEGIN(coff)                                                                    \
+    const int coffh = (coff) + (int)lds_addr(hist);                                           \
+    int4 bq_[2], aq_[2];                                                                      \
+    float4 xq_[2];                                                                            \
+    bq_[0] = *reinterpret_cast<const int4 *>(ard);                                            \
+    xq_[0] = *reinterpret_cast<const float4 *>(xrd);                                          \
+    bq_[1] = bq_[0];                                                                          \
+    xq_[1] = xq_[0];                                                                          \
+    CHUNK_ADDR(0)                                                                             \
+    aq_[1] = aq_[0];
+#define ROUND(u, ...)                                                                         \
+    {                                                                                         \
+        constexpr int cur_ = ((u) >> 2) & 1, nxt_ = cur_ ^ 1;                                 \
+        const int mb_[4] = { bq_[cur_].x, bq_[cur_].y, bq_[cur_].z, bq_[cur_].w };            \
+        const int ma_[4] = { aq_[cur_].x, aq_[cur_].y, aq_[cur_].z, aq_[cur_].w };            \
+        const float xv_[4] = { xq_[cur_].x, xq_[cur_].y, xq_[cur_].z, xq_[cur_].w };          \
+        const int addr_ = OFFCHAIN ? ma_[(u) & 3] : mb_[(u) & 3] + coffh;                     \
+        float old_ = 0.0f;                                                                    \
+        if (!DESC_ABLATE(1))                                                                  \
+            old_ = LDS_F32(addr_);                                                            \
+        SB();                                                                                 \
+        if (((u) & 3) == 0 && (u) + 4 < 16) {                                                 \
+            bq_[nxt_] = *reinterpret_cast<const int4 *>(ard + (u) + 4);                       \
+            xq_[nxt_] = *reinterpret_cast<const float4 *>(xrd + (u) + 4);                     \
+            SB();                                                                             \
+        }                                                                                     \
+        { __VA_ARGS__ }                                                                       \
+        if (OFFCHAIN && ((u) & 3) == 1 && (u) + 3 < 16) {                                     \
+            CHUNK_ADDR(nxt_)                                                                  \
+        }                                                                                     \
+        SB();                                                                                 \
+        if (!DESC_ABLATE(1))                                                                  \
+            LDS_F32(addr_) = COMMIT_ADD(old_, xv_[(u) & 3]);           /* sift.c:1371-1373 */ \
+        SB();                                                                                 \
+    }
+#else
 #define COMMIT_BEGIN(coff)                                                                    \
     const int coff4 = (coff);                                                                 \
     int4 cb4 = *reinterpret_cast<const int4 *>(ard);                                          \
@@ -539,6 +613,7 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
         }                                                                                     \
         SB();                                                                                 \
     }
+#endif
     // EXACT: the same 16 rounds for half-wave 1's voxels (sequence B), after half-wave 0's
 #define CHAIN_B()                                                                             \
     if (EXACT) {                                                                              \
@@ -575,11 +650,25 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
         commit_write(0);
         {
             COMMIT_BEGIN(coff_a);
-            ROUND(0, x = B.xs + (int)((uint32_t)pk & xmask); y = B.ys + (int)(((uint32_t)pk >> xsh) & ymask);
-                     z = B.zs + (int)((uint32_t)pk >> ysh);
-                     dx = ((float)x - K.cx) * L.ux; KEEP(dx);)             // sift.c:102-104
-            ROUND(1, dy = ((float)y - K.cy) * L.uy; dz = ((float)z - K.cz) * L.uz; KEEP(dy); KEEP(dz);
-                     // IM_GET_GRAD_ISO (sift.c:140-145, immacros.h:105-111)
+            // LATTICE: the centre is integral, so (float)x - K.cx is exactly (float)(x - icx) (both operands and the
+            // difference are integers below 2^24): the offsets kept from the table index give the same dx, dy, dz
+            // without unpacking the voxel again
+            ROUND(0, if (LATTICE && (DESC_OPT & 8)) {
+                         dx = (float)pwi * L.ux; dy = (float)pwj * L.uy; dz = (float)pwl * L.uz;
+                         KEEP(dy); KEEP(dz);
+                     } else {
+                         x = B.xs + (int)((uint32_t)pk & xmask); y = B.ys + (int)(((uint32_t)pk >> xsh) & ymask);
+                         z = B.zs + (int)((uint32_t)pk >> ysh);
+                         dx = ((float)x - K.cx) * L.ux;                    // sift.c:102-104
+                     }
+                     KEEP(dx);)
+            // IM_GET_GRAD_ISO (sift.c:140-145, immacros.h:105-111), then the Gaussian weight (sift.c:1498, see
+            // prefetch_weight): three separately rounded scalings in both variants.  (Folding them into one factor
+            // for the lattice variant, fl(d * fl(0.5 * iu * w)), measured no gain -- DESIGN.md 3.3 -- and is
+            // not built; tests/test_describe_lattice_host.py keeps the restatement of where the forms differ.)
+            ROUND(1, if (!(LATTICE && (DESC_OPT & 8))) {
+                         dy = ((float)y - K.cy) * L.uy; dz = ((float)z - K.cz) * L.uz; KEEP(dy); KEEP(dz);
+                     }
                      gx = 0.5f * (cv[0] - cv[1]); gy = 0.5f * (cv[2] - cv[3]); gz = 0.5f * (cv[4] - cv[5]);)
             ROUND(2, gx *= iux; gy *= iuy; gz *= iuz;
                      gx = gx * cv[6]; gy = gy * cv[6]; gz = gz * cv[6];)   // sift.c:1498, see prefetch_weight
@@ -669,7 +758,8 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
             // table the load is a dummy and prefetch_weight() computes the weight)
             ROUND(3, pv[4] = np_[zs32]; pv[5] = *(np_ - zs32);
                      const int i = nx_ - icx; const int j = ny_ - icy; const int l = B.zs + (int)((uint32_t)ppk >> ysh) - icz;
-                     pv[6] = wsrc[(i * i + j * j + l * l) & wmask];)
+                     pv[6] = wsrc[(i * i + j * j + l * l) & wmask];
+                     if (LATTICE && (DESC_OPT & 8)) { pwi = i; pwj = j; pwl = l; })
             // trilinear cell weights (sift.c:1318-1320, 1361-1363): weight = wx * wy * wz,
             // value = mag * weight * bary.  A corner beyond the last cell is skipped by the
             // reference (sift.c:1349-1352).  The commit is free of predication -- all 24 lanes
@@ -845,7 +935,15 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
                 continue;
             // queue position = the number of accepted voxels at lower positions: both voxels of every lower lane,
             // and this lane's first for its second
+#if DESC_OPT & 32
+            // (v_mbcnt counts a mask's bits below the lane and adds: four instructions, no lane-mask registers)
+            const uint32_t before = __builtin_amdgcn_mbcnt_hi(
+                (uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, __builtin_amdgcn_mbcnt_hi(
+                (uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u))));
+#else
+            const unsigned long long lt_mask = (1ull << lane) - 1ull;
             const uint32_t before = (uint32_t)__popcll(m0 & lt_mask) + (uint32_t)__popcll(m1 & lt_mask);
+#endif
             if (in0)
                 queue[(qtail + before) & (DQ - 1)] = pk0;
             if (in1)
@@ -976,7 +1074,9 @@ __global__ __launch_bounds__(64 * DWAVES) void k_describe(const sift3d_hip_level
     wave_sync();                  // (the histogram is cleared for the next keypoint behind these reads)
     }
     if (probe) {
-        unsigned long long *slot = reinterpret_cast<unsigned long long *>(work - (EXACT ? 0 : 1) + (EXACT ? 4 : 8));
+        // (work: counter 0 of the reference-order launch, 1 of the fast one, 2 of the lattice one)
+        unsigned long long *slot =
+            reinterpret_cast<unsigned long long *>(work - (EXACT ? 0 : LATTICE ? 2 : 1) + (EXACT ? 4 : 8));
         slot[0] = (unsigned long long)(clock64() - probe_c0);
         slot[1] = (unsigned long long)(wall_clock64() - probe_w0);
     }
@@ -1598,15 +1698,36 @@ size_t sift3d_hip_describe_part_bytes(uint32_t n)
     return n ? (size_t)n * DPARTS * HIST_USED * sizeof(float) + (size_t)n * sizeof(uint32_t) : 0;
 }
 
+// The host's side of the lattice variant's contract (k_describe, LATTICE): 1 when the records of a level with
+// these units, scale and row length may take it, provided they sit on a voxel and carry exactly this sd.  A
+// restatement of k_desc_wlut's `ok` that is the stricter of the two wherever they could round differently (the
+// table's length is compared with a margin) and admits units within 2^-10 .. 2^10 only.
+int sift3d_hip_describe_lattice_level(float ux, float uy, float uz, double sd)
+{
+    const float sigma = (float)(sd * 7.071067812);
+    const float rad = (float)(2.0 * (double)sigma);
+    int e;
+    const float mant = frexpf(ux, &e);
+    const float rad2 = rad * rad, u2 = ux * ux;
+    return ux == uy && ux == uz && mant == 0.5f && ux >= 0.0009765625f && ux <= 1024.0f &&
+           rad2 / u2 < 0.999f * (float)(WL_STRIDE - WL_HEAD - 1) && u2 * (float)WL_STRIDE < 16777216.0f;
+}
+
 // records [0, n_exact) take the reference-order kernel, [n_exact, n) the fast one, its windows in DPARTS parts
 // through d_part (sift3d_hip_describe_part_bytes(n - n_exact) bytes; nullptr: a temporary allocation, freed
-// behind a stream synchronisation -- the entries that take no scratch)
+// behind a stream synchronisation -- the entries that take no scratch).  The last n_lattice records of the
+// fast range take the lattice variant, in a launch of its own behind the generic one (the caller's contract:
+// sift3d_hip_describe_lattice_level; needs the weight tables).
 static int describe_launch(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp, uint32_t n,
-                           uint32_t n_exact, float *d_hist, float *d_hist2, const float *d_wlut,
-                           void *d_part, void *stream)
+                           uint32_t n_exact, uint32_t n_lattice, float *d_hist, float *d_hist2,
+                           const float *d_wlut, void *d_part, void *stream)
 {
     if (n_exact > n)
         n_exact = n;
+    if (!(DESC_OPT & 8) || !d_wlut)
+        n_lattice = 0;
+    if (n_lattice > n - n_exact)
+        return launch_fail("sift3d_hip_describe", "more lattice records than fast records");
 #ifdef SIFT3D_AMD_DIAG
     // diagnostic build only (wrong results): 1 skips the commit, 2 the whole batch -- used by
     // profiles/ scripts to attribute the kernel's time to scan / per-voxel terms / commit
@@ -1634,10 +1755,20 @@ static int describe_launch(const sift3d_hip_level *d_levels, int nlevels, const 
         float *parts = reinterpret_cast<float *>(d_part);
         uint32_t *done = reinterpret_cast<uint32_t *>(parts + (size_t)nf * DPARTS * HIST_USED);
         hipError_t e = hipMemsetAsync(done, 0, (size_t)nf * sizeof(uint32_t), (hipStream_t)stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_describe<false>, dim3(describe_grid(nf * DPARTS, work != nullptr)),
-                               dim3(64 * DWAVES), 0, (hipStream_t)stream, d_levels, d_kp, n_exact, n, d_hist,
-                               d_hist2, d_wlut, work ? work + 1 : nullptr, parts, done DESC_ABLATE_PASS);
+        // (generic records [n_exact, n - n_lattice), lattice records [n - n_lattice, n): disjoint slices of the
+        // part scratch; the kernel indexes it by the record's position behind `first`)
+        const uint32_t ng = nf - n_lattice;
+        if (e == hipSuccess && ng) {
+            hipLaunchKernelGGL((k_describe<false, false>), dim3(describe_grid(ng * DPARTS, work != nullptr)),
+                               dim3(64 * DWAVES), 0, (hipStream_t)stream, d_levels, d_kp, n_exact, n - n_lattice,
+                               d_hist, d_hist2, d_wlut, work ? work + 1 : nullptr, parts, done DESC_ABLATE_PASS);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && n_lattice) {
+            hipLaunchKernelGGL((k_describe<false, true>), dim3(describe_grid(n_lattice * DPARTS, true)),
+                               dim3(64 * DWAVES), 0, (hipStream_t)stream, d_levels, d_kp, n - n_lattice, n,
+                               d_hist, d_hist2, d_wlut, work + 2, parts + (size_t)ng * DPARTS * HIST_USED,
+                               done + ng DESC_ABLATE_PASS);
             e = hipGetLastError();
         }
         if (tmp) {
@@ -1658,21 +1789,31 @@ int sift3d_hip_describe(const sift3d_hip_level *d_levels, const sift3d_hip_kp *d
 {
     if (!n)
         return SIFT3D_SUCCESS;
-    return describe_launch(d_levels, 0, d_kp, n, 0, d_hist, nullptr, nullptr, nullptr, stream);
+    return describe_launch(d_levels, 0, d_kp, n, 0, 0, d_hist, nullptr, nullptr, nullptr, stream);
 }
 
-// (d_part: scratch of sift3d_hip_describe_part_bytes(n - n_exact) bytes, or NULL)
-int sift3d_hip_describe_parts(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp,
-                              uint32_t n, uint32_t n_exact, float *d_hist, float *d_hist2, float *d_wlut,
-                              void *d_part, void *stream)
+// (d_part: scratch of sift3d_hip_describe_part_bytes(n - n_exact) bytes, or NULL; the last n_lattice records:
+// see describe_launch)
+int sift3d_hip_describe_lattice(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp,
+                                uint32_t n, uint32_t n_exact, uint32_t n_lattice, float *d_hist, float *d_hist2,
+                                float *d_wlut, void *d_part, void *stream)
 {
     if (!n)
         return SIFT3D_SUCCESS;
     if (!d_wlut || nlevels < 1)
-        return describe_launch(d_levels, 0, d_kp, n, n_exact, d_hist, d_hist2, nullptr, d_part, stream);
+        return describe_launch(d_levels, 0, d_kp, n, n_exact, 0, d_hist, d_hist2, nullptr, d_part, stream);
     hipLaunchKernelGGL(k_desc_wlut, dim3(nlevels), dim3(256), 0, (hipStream_t)stream, d_levels, nlevels,
                        d_wlut);
-    return describe_launch(d_levels, nlevels, d_kp, n, n_exact, d_hist, d_hist2, d_wlut, d_part, stream);
+    return describe_launch(d_levels, nlevels, d_kp, n, n_exact, n_lattice, d_hist, d_hist2, d_wlut, d_part,
+                           stream);
+}
+
+int sift3d_hip_describe_parts(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp,
+                              uint32_t n, uint32_t n_exact, float *d_hist, float *d_hist2, float *d_wlut,
+                              void *d_part, void *stream)
+{
+    return sift3d_hip_describe_lattice(d_levels, nlevels, d_kp, n, n_exact, 0, d_hist, d_hist2, d_wlut, d_part,
+                                       stream);
 }
 
 int sift3d_hip_describe_ex(const sift3d_hip_level *d_levels, int nlevels, const sift3d_hip_kp *d_kp,

@@ -1005,27 +1005,44 @@ static int ensure_kp_list(sift3d_detector *d, int num)
     return SIFT3D_SUCCESS;
 }
 
-/* Bucket b = level (reference-order kernel) or ngl + level (fast commit): the kernel is chosen per keypoint,
- * from its own sd (exact_desc_keypoint). */
-static inline int desc_bucket(const sift3d_detector *d, const keypoint_t *k)
+/* 1 when the keypoint may take the lattice variant of the fast kernel (sift3d_hip_describe_lattice's contract):
+ * it sits on a voxel -- the test on the float centre that the kernel would make --, carries the bits of its
+ * level's sd, and the level qualifies.  What detect produces on an isotropic volume always does. */
+static inline int lattice_keypoint(const sift3d_detector *d, const keypoint_t *k)
 {
-    return k->s + 1 + (exact_desc_keypoint(d->exact_desc, k->sd, k->o, d->units) ? 0 : d->ngl);
+    const sift3d_hip_level *L = d->h_levels + (k->o * d->ngl + k->s + 1);
+    const float c[3] = { (float)k->xd, (float)k->yd, (float)k->zd };
+    int a;
+    for (a = 0; a < 3; a++)
+        if (!(c[a] >= 0.0f && c[a] < 8388608.0f && (float)(int)c[a] == c[a]))
+            return 0;
+    return memcmp(&k->sd, &L->sd, sizeof(double)) == 0 &&
+           sift3d_hip_describe_lattice_level(L->ux, L->uy, L->uz, L->sd);
 }
 
-/* Launch order: the keypoints of the reference-order kernel first, then the others; within each part
- * widest windows first.  The window radius in level voxels grows with the level index s only
- * (14.14 * sigma0 * 2^(s/K)) for detect's keypoints, and a keypoint of the last level costs ~4x one of
+/* Bucket b = level (reference-order kernel), ngl + level (fast commit) or 2 * ngl + level (fast commit, lattice
+ * variant): the kernel is chosen per keypoint, from its own sd (exact_desc_keypoint) and centre. */
+static inline int desc_bucket(const sift3d_detector *d, const keypoint_t *k)
+{
+    if (exact_desc_keypoint(d->exact_desc, k->sd, k->o, d->units))
+        return k->s + 1;
+    return k->s + 1 + (lattice_keypoint(d, k) ? 2 : 1) * d->ngl;
+}
+
+/* Launch order: the keypoints of the reference-order kernel first, then the others, those of the lattice
+ * variant last (*n_lattice of them); within each part widest windows first.  The window radius in level
+ * voxels grows with the level index s only (14.14 * sigma0 * 2^(s/K)) for detect's keypoints, and a keypoint of the last level costs ~4x one of
  * the first; longest-job-first keeps the tail of the one-wave-per-keypoint kernel short.  row1 sends
  * every histogram to its keypoint's row.
  * A stable counting sort by (kernel, level) on a few threads: per-thread counts per bucket, then every
  * thread places the keypoints of its part of the list.  Fills d->h_kp; returns the number of keypoints
  * of the reference-order kernel, which lead the list. */
-static size_t order_keypoints(sift3d_detector *d, const sift3d_keypoint_store *kp)
+static size_t order_keypoints(sift3d_detector *d, const sift3d_keypoint_store *kp, size_t *n_lattice)
 {
     const size_t num = kp->num;
     const int nt = host_threads(num), nlv = d->ngl;       /* s + 1 in [0, ngl) */
-    size_t cnt[HOST_THREADS_MAX][2 * DESC_LV_MAX], start[HOST_THREADS_MAX][2 * DESC_LV_MAX];
-    size_t n_exact = 0;
+    size_t cnt[HOST_THREADS_MAX][3 * DESC_LV_MAX], start[HOST_THREADS_MAX][3 * DESC_LV_MAX];
+    size_t n_exact = 0, lattice_first = num;
     memset(cnt, 0, sizeof(cnt));
 #pragma omp parallel num_threads(nt)
     {
@@ -1039,10 +1056,13 @@ static size_t order_keypoints(sift3d_detector *d, const sift3d_keypoint_store *k
         {
             size_t pos = 0;
             int b, u;
-            for (b = 0; b < 2 * nlv; b++) {
-                const int bk = b < nlv ? nlv - 1 - b : 3 * nlv - 1 - b;   /* levels descending in each part */
+            for (b = 0; b < 3 * nlv; b++) {
+                /* levels descending in each part */
+                const int bk = b < nlv ? nlv - 1 - b : b < 2 * nlv ? 3 * nlv - 1 - b : 5 * nlv - 1 - b;
                 if (b == nlv)
                     n_exact = pos;         /* (the exact ones lead the list) */
+                if (b == 2 * nlv)
+                    lattice_first = pos;
                 for (u = 0; u < nth; u++) {
                     start[u][bk] = pos;
                     pos += cnt[u][bk];
@@ -1062,6 +1082,7 @@ static size_t order_keypoints(sift3d_detector *d, const sift3d_keypoint_store *k
             r->sd = k->sd;
         }
     }
+    *n_lattice = num - lattice_first;
     return n_exact;
 }
 
@@ -1104,12 +1125,12 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
     const int num = (int)kp->num;
     const double t_start = now_s();
     int i;
-    size_t n_exact;
+    size_t n_exact, n_lattice;
     uint64_t rng;
 
     if (verify_keys(d, kp) || check_window_packing(d, kp) || ensure_kp_list(d, num))
         return SIFT3D_FAILURE;
-    n_exact = order_keypoints(d, kp);
+    n_exact = order_keypoints(d, kp, &n_lattice);
     if (ensure_descriptor_store(d, desc, (size_t)num))
         return SIFT3D_FAILURE;
     d->t_pending &= ~2;
@@ -1135,9 +1156,10 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
             d->dpart_bytes = need + need / 8;
         }
         if (!dev_view || !kp_view ||
-            sift3d_hip_describe_parts(d->d_levels, d->num_octaves * d->ngl, kp_view, (uint32_t)num,
-                                      (uint32_t)n_exact, dev_view, desc->keep_device ? desc->d_hist : NULL,
-                                      d->d_wlut, need ? d->d_dpart : NULL, d->stream))
+            sift3d_hip_describe_lattice(d->d_levels, d->num_octaves * d->ngl, kp_view, (uint32_t)num,
+                                        (uint32_t)n_exact, (uint32_t)n_lattice, dev_view,
+                                        desc->keep_device ? desc->d_hist : NULL, d->d_wlut,
+                                        need ? d->d_dpart : NULL, d->stream))
             return SIFT3D_FAILURE;
     }
     sift3d_hip_event_record(d->ev[7], d->stream);
