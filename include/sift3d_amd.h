@@ -1126,6 +1126,106 @@ sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const 
                                 float lo_m, float hi_m, sift3d_amd_similarity *mi_out);
 
 /* ------------------------------------------------------------------------ */
+/* Jacobian penalty: a volume (folding) term on a field and in the FFD drivers */
+/* ------------------------------------------------------------------------ */
+/* A penalty on the SAME discrete Jacobian that sift3d_hip_jacobian_det reports ("Displacement fields", steps 1 - 3), not
+ * on the analytic derivative of a spline: what an optimiser lowers here is what the caller later reads as `folded`.  It
+ * is defined on any field u[3][oz][oy][ox], N = ox oy oz, with a reference determinant `ref` (double, finite, not 0: the
+ * determinant that counts as "no volume change", 1 for a field around the identity, det of A's linear part for a field
+ * around A).  No upstream counterpart: PARITY UNPINNED, pinned to this contract and its numpy restatement
+ * (tests/jacobian_penalty_restatement.py).  Double, unfused, unless stated.
+ *
+ * Per voxel p:
+ *   j_de(p) float and det(p) double: "Displacement fields" steps 1 - 3 (det before its rounding to float in step 4);
+ *   r = det / ref;
+ *   r >= 1/4 :  phi = (r + 1.0 / r) - 2.0,                     phi' = 1.0 - 1.0 / (r * r);
+ *   otherwise (r <= 0 and a NaN r included), t = r - 0.25:
+ *               phi = (2.25 - 15.0 * t) + 64.0 * (t * t),      phi' = -15.0 + 128.0 * t.
+ * phi is the symmetric volume term (r - 1)^2 / r, phi(r) = phi(1 / r), continued below 1/4 by its own second-order
+ * Taylor polynomial there (phi(1/4) = 9/4, phi'(1/4) = -15, phi''(1/4) = 128): C^1 (C^2) at 1/4, finite for every finite
+ * r, so a folded field needs no special case; only IEEE add, multiply and divide.  A NaN r gives a NaN phi.
+ * Record (SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES of device memory, 8-byte aligned; after the call completes):
+ *   uint64 nonpos = the number of voxels with !(r > 0) (a NaN counts);
+ *   double sum    = sum_p phi(r_p): per-workgroup partials (one slot per workgroup of a grid of min(tiles,
+ *                   SIFT3D_AMD_SIMILARITY_GRID) workgroups, whatever the device; a tile is 64 x 4 x 8 voxels, x fastest),
+ *                   then the slots in a fixed order; no atomics: its bits depend on the shapes and the field only, and it
+ *                   is within gamma_(N) sum |phi| of the exact sum of the phi;
+ *   double rmin, rmax over the non-NaN r (+inf, -inf when there is none): order-independent.
+ *   The penalty is P = sum / N (the caller's division).
+ * Gradient in sum form (d_grad, double [3][oz][oy][ox], the layout of the FFD force): d P / d u_d(q) = S_d(q) / N,
+ *   S_d(q) = sum_e sum_p K_de(p) D_e[p][q],      K_de(p) = a(p) * C_de(p),      a(p) = phi'(r_p) / ref
+ *   C(p): the cofactors of j(p) from the float j widened to double.  With d1 < d2 the two rows other than d and e1 < e2
+ *         the two columns other than e,
+ *           d + e even:  C_de = j[d1][e1] * j[d2][e2] - j[d2][e1] * j[d1][e2]
+ *           d + e odd :  C_de = j[d2][e1] * j[d1][e2] - j[d1][e1] * j[d2][e2]
+ *         (each product of two floats is exact in double, so every entry is one rounded difference, with its sign);
+ *   D_e:  the matrix of numpy.gradient along axis e (0: x, 1: y, 2: z), g_e(p) = sum_q D_e[p][q] u(q), n the axis'
+ *         length and i the coordinate of q along it: D_e[i - 1][i] = 1/2 (1 when i - 1 == 0), D_e[i + 1][i] = -1/2 (-1
+ *         when i + 1 == n - 1), D_e[0][0] = -1, D_e[n - 1][n - 1] = 1, every other entry 0, and all of D_e is 0 when
+ *         n == 1;
+ *   order: from +0.0, S = S + (a(p) * C_de(p)) * D_e[p][q], axis e ascending, then p ascending (q - 1, q, q + 1 along
+ *         e); a p with D_e[p][q] == 0 is not a term (nothing is added for it, a NaN there stays there).  The last
+ *         multiply is exact.  One lane owns one S_d(q) and there are no atomics, so S is defined bit for bit.
+ *
+ * Lattice gradient (sift3d_hip_ffd_jacobian_gradient): the record of the field, and GJ [3][gz][gy][gx] double =
+ * sum_p W(p; k, j, i) S_d(p) on the lattice of the field's grid at spacing (dx, dy, dz): S through the adjoint of the
+ * spline exactly as the force of "B-spline free-form deformation" goes through it (one axis at a time, z, then y, then
+ * x, each sum ascending from +0, double, unfused), so d P / d c = GJ / N and every entry is within gamma_(k + 8) sum
+ * |term| of the exact sum of its terms, k the voxels under the control.  d_work: sift3d_amd_ffd_jacobian_gradient_
+ * work_bytes() bytes, 16-byte aligned.  Checks as below, with the spacing in [1, SIFT3D_AMD_FFD_MAX_SPACING].
+ *
+ * sift3d_hip_jacobian_penalty: asynchronous on `stream`, allocates nothing, 64-bit offsets.  d_grad may be NULL (the
+ * record alone; the record's bytes are the same either way).  d_work: sift3d_amd_jacobian_penalty_work_bytes() bytes, 8-
+ * byte aligned.  -1 before any device call on a NULL d_field, d_record or d_work, dims <= 0, a `ref` that is not finite
+ * or is 0, misalignment (d_field 4 B, the rest 8 B), an output (record, gradient, work) that overlaps the field or
+ * another output.
+ *
+ * Driver (sift3d_amd_ffd_refine_jacobian_device).  sift3d_amd_ffd_mi_refine_device's arguments with bins == 0 meaning
+ * the MSD of "B-spline free-form deformation" (the ranges are then not read and mi_out may be NULL; it is filled as by
+ * that driver otherwise) and masks that may be NULL with either metric; then `jacobian` (the weight, finite, >= 0) and
+ * `penalty`, a caller array of SIFT3D_AMD_FFD_MAX_TRAIL entries parallel to result->trail: {P, rmin, nonpos} of every
+ * evaluation's field.  The loop, levels, subdivision, step rule and stop reasons are that driver's, one loop in the code
+ * too, with
+ *     E    = (image + bending * R) + jacobian * P               (image: S_ee / n, or -mi)
+ *     grad = (float)(((scale / n) * Gc + bending * dR) + (jacobian / N) * GJ)        (scale: 2, or 1 for -mi)
+ * where P = sum / N on the level's grid with ref = A[0] * (A[5] * A[10] - A[6] * A[9]) - A[1] * (A[4] * A[10] - A[6] *
+ * A[8]) + A[2] * (A[4] * A[9] - A[5] * A[8]) (double, this order, unfused, on the host; 1.0 without A; the same on every
+ * level), and GJ [3][gz][gy][gx] is S through the adjoint of the spline, the three passes of the evaluation (z, then y,
+ * then x) on S in the place of the force.  The penalty acts on every voxel of the grid: masks limit the image force only,
+ * as with the bending term.  With jacobian == 0 the two formulas are the existing drivers', to the letter (no third term
+ * is added), P is still recorded, and lattice, field and trail are those drivers' byte for byte.  A non-finite P makes E
+ * non-finite: the existing rule for a non-finite E applies.  The value pass runs in every evaluation; the gradient pass
+ * runs where the image force runs (every evaluation of the MSD, the MI driver's gradient step).  -1 before any device
+ * call on what the MI driver refuses (bins and ranges only when bins != 0), a NULL `penalty`, a `jacobian` that is not
+ * finite or is negative, an A whose linear part has determinant 0.  d_work: sift3d_amd_ffd_refine_jacobian_work_bytes()
+ * bytes: the MI driver's layout, then the penalty's record, GJ and the penalty's work. */
+#define SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES 32
+typedef struct {
+    double P;                                       /* sum / N */
+    double rmin;
+    uint64_t nonpos;
+} sift3d_amd_ffd_penalty;
+/* bytes of d_work (0 for bad arguments) */
+SIFT3D_AMD_API size_t sift3d_amd_jacobian_penalty_work_bytes(int ox, int oy, int oz);
+SIFT3D_AMD_API int sift3d_hip_jacobian_penalty(const float *d_field, int ox, int oy, int oz, double ref, void *d_record,
+                                               double *d_grad /*NULL: value only*/, void *d_work, void *stream);
+SIFT3D_AMD_API size_t sift3d_amd_ffd_jacobian_gradient_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz);
+SIFT3D_AMD_API int sift3d_hip_ffd_jacobian_gradient(const float *d_field, int ox, int oy, int oz, int dx, int dy, int dz,
+                                                    double ref, void *d_record, double *d_GJ, void *d_work,
+                                                    void *stream);
+SIFT3D_AMD_API size_t
+sift3d_amd_ffd_refine_jacobian_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                          int levels);
+/* A [12] on the host or NULL; mi_out (NULL allowed when bins == 0) and penalty on the host */
+SIFT3D_AMD_API int
+sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                      const double *A, const sift3d_amd_ffd_refine_params *params,
+                                      sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                      void *d_work, void *stream, const float *d_WF, const float *d_WM, int bins,
+                                      float lo_f, float hi_f, float lo_m, float hi_m, sift3d_amd_similarity *mi_out,
+                                      double jacobian, sift3d_amd_ffd_penalty *penalty);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

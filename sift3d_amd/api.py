@@ -1148,6 +1148,43 @@ FFDRefinement = collections.namedtuple("FFDRefinement", "lattice spacing A field
 FFDEvaluation = collections.namedtuple("FFDEvaluation", "E msd R n step accepted level")
 FFDRegistration = collections.namedtuple("FFDRegistration", "registration refinement")
 MiFFDRefinement = collections.namedtuple("MiFFDRefinement", FFDRefinement._fields + ("mi", "nmi", "bins"))
+# what refine_ffd(jacobian > 0) returns: the metric's refinement, then the penalty's trail and weight
+FFDPenalty = collections.namedtuple("FFDPenalty", "P rmin nonpositive")
+JacFFDRefinement = collections.namedtuple("JacFFDRefinement", FFDRefinement._fields + ("penalty", "jacobian_weight"))
+JacMiFFDRefinement = collections.namedtuple("JacMiFFDRefinement",
+                                            MiFFDRefinement._fields + ("penalty", "jacobian_weight"))
+JacobianPenalty = collections.namedtuple("JacobianPenalty", "value nonpositive min max gradient")
+
+
+def jacobian_penalty(field, ref_det=1.0, gradient=False):
+    """The volume (folding) penalty of a displacement field [3, oz, oy, ox] (a torch CUDA float32 tensor, or an array,
+    which is uploaded), on the discrete Jacobian that jacobian_determinant reports (contract: include/sift3d_amd.h,
+    "Jacobian penalty"): with r = det / ref_det per voxel, the mean of (r - 1)^2 / r, continued below r = 1/4 by its
+    second-order Taylor polynomial so that folded voxels have a finite value and a slope that unfolds them.  ref_det:
+    the determinant that counts as no volume change (finite, not 0).  Returns JacobianPenalty(value, nonpositive: the
+    voxels with r <= 0 or NaN, min, max of r, gradient: d value / d field as a float64 CUDA tensor [3, oz, oy, ox] when
+    asked for, else None).  Waits for torch's current stream."""
+    import torch
+    from . import hip
+    ref_det = float(ref_det)
+    if not np.isfinite(ref_det) or ref_det == 0.0:
+        raise ValueError("jacobian_penalty: ref_det must be finite and not 0")
+    if not _torch_tensor(field):
+        f = _host_field(field, "jacobian_penalty")
+        if not device_available():
+            raise RuntimeError("jacobian_penalty: no HIP device is available; this library has no CPU path")
+        field = torch.from_numpy(f).to("cuda")
+    rec, S = hip.jacobian_penalty(field, ref_det, bool(gradient))
+    nonpos, total, rmin, rmax = hip.jacobian_penalty_record(rec)
+    n = field[0].numel()
+    return JacobianPenalty(total / n, nonpos, rmin, rmax, None if S is None else S / float(n))
+
+
+def jacobian_reference(A):
+    """the determinant of the linear part of a 3 x 4 map in the contract's order ("Jacobian penalty")"""
+    A = np.asarray(A, np.float64).reshape(-1)
+    return float(A[0] * (A[5] * A[10] - A[6] * A[9]) - A[1] * (A[4] * A[10] - A[6] * A[8]) +
+                 A[2] * (A[4] * A[9] - A[5] * A[8]))
 
 
 def _ffd_lattice_tensor(lattice, what):
@@ -1195,7 +1232,7 @@ def ffd_bending_energy(lattice, spacing):
 
 
 def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None,
-               metric="msd", bins=None, range_fixed=None, range_moving=None, **params):
+               metric="msd", bins=None, range_fixed=None, range_moving=None, jacobian=0.0, **params):
     """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
     `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
     include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
@@ -1215,8 +1252,17 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     nmi at the final lattice and bins; `warped` is not remapped.  `bending` keeps its default of 0.005 for either
     metric: the value was chosen for the MSD of volumes of unit-order intensity, and no calibration of it against -mi
     (which is of order 1 whatever the intensities) is claimed.  bins or a range with metric="msd", and any other
-    metric, raise ValueError."""
+    metric, raise ValueError.
+    jacobian > 0 adds jacobian * (the Jacobian penalty of the field, jacobian_penalty with ref_det = det of A's linear
+    part) to the cost of either metric, with or without masks (contract: "Jacobian penalty"): the optimiser then keeps
+    away from the folding that `jacobian.folded` counts, without the smoothing that a larger `bending` buys it with.
+    The result is then a JacFFDRefinement (JacMiFFDRefinement): the metric's fields, then penalty: one FFDPenalty(P,
+    rmin, nonpositive) per trail entry, and jacobian_weight.  No calibration of the weight against the image term is
+    claimed.  jacobian == 0 is the call without it."""
     from . import hip
+    jacobian = float(jacobian)
+    if not (np.isfinite(jacobian) and jacobian >= 0):
+        raise ValueError("refine_ffd: jacobian must be finite and not negative")
     if metric not in ("msd", "mi"):
         raise ValueError("refine_ffd: metric must be 'msd' or 'mi', not %r" % (metric,))
     if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
@@ -1244,6 +1290,8 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         A0 = _affine_or_none(A)
         if A0 is None or not np.isfinite(A0).all():
             raise ValueError("refine_ffd: A must be a finite 3 x 4 affine pull map or None")
+        if jacobian > 0 and jacobian_reference(A0) == 0.0:
+            raise ValueError("refine_ffd: jacobian > 0 needs an A whose linear part has a determinant that is not 0")
     p = hip.ffd_refine_params(spacing=d, levels=int(levels), bending=float(bending), **params)
     WF = _mask_host(mask_fixed, fixed, "refine_ffd", "mask_fixed")
     WM = _mask_host(mask_moving, moving, "refine_ffd", "mask_moving")
@@ -1251,7 +1299,13 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
     WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
-    if metric == "mi":
+    penalty = None
+    if jacobian > 0:
+        mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
+            if metric == "mi" else {}
+        res, lattice, field, sim, penalty = hip.ffd_refine_jacobian(F, M, jacobian, A=A0, params=p, mask_fixed=WF,
+                                                                    mask_moving=WM, **mi)
+    elif metric == "mi":
         res, lattice, field, sim = hip.ffd_mi_refine(F, M, int(bins), _own_range(F, range_fixed),
                                                      _own_range(M, range_moving), A0, p, mask_fixed=WF, mask_moving=WM)
     else:
@@ -1261,7 +1315,10 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     out = FFDRefinement(lattice, d, A0, field, warp_field(M, field), trail, hip.FFD_STOPS[res.stop],
                         jacobian_determinant(field))
     if metric == "mi":
-        return MiFFDRefinement(*out, mi=float(sim.mi), nmi=float(sim.nmi), bins=int(bins))
+        out = MiFFDRefinement(*out, mi=float(sim.mi), nmi=float(sim.nmi), bins=int(bins))
+    if penalty is not None:
+        kind = JacMiFFDRefinement if metric == "mi" else JacFFDRefinement
+        return kind(*out, penalty=[FFDPenalty(*q) for q in penalty], jacobian_weight=jacobian)
     return out
 
 

@@ -6,8 +6,28 @@
  * deformation (Mattes)": two metrics, one evaluation entry body and one driver loop over either.  The kernels are in
  * sift3d_ffd.hip (the histogram pass in sift3d_affine_refine.hip), reached through the launchers below after the checks
  * here.  Arguments are checked before the device is touched, so bad
- * input is refused on a machine without a GPU too. */
+ * input is refused on a machine without a GPU too.
+ *
+ * The Jacobian penalty (header, "Jacobian penalty"; kernels in sift3d_jacobian_penalty.hip) has its checked entry here
+ * and is the optional third term of the driver's cost. */
+#include "sift3d_ffd_jac.h"
 
+int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
+                                   double *d_rec, double *d_S, double *d_work, void *stream);
+int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                                   int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
+                                   int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
+                                   double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
+                                   const float *d_WM, const sift3d_ffd_jac *jac);
+int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
+                             const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
+                             int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
+                             double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
+                             double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
+                             const float *d_WM, const sift3d_ffd_jac *jac);
+int sift3d_ffd_jacobian_gradient_launch(const char *fn, const float *d_field, int ox, int oy, int oz, int gx, int gy,
+                                        int gz, int dx, int dy, int dz, const float *d_w, double ref, double *d_rec,
+                                        double *d_GJ, double *d_work, void *stream);
 int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
                             const float *d_w, const double *A, int ox, int oy, int oz, float *d_field, void *stream);
 int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
@@ -305,6 +325,91 @@ int sift3d_hip_ffd_refine2(const float *d_coarse, int ox, int oy, int oz, int dx
     return sift3d_ffd_refine2_launch(d_coarse, cx, cy, cz, d_fine, fx, fy, fz, stream);
 }
 
+/* ---- Jacobian penalty of a field ---- */
+
+size_t sift3d_amd_jacobian_penalty_work_bytes(int ox, int oy, int oz)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0)
+        return 0;
+    return (4 * (size_t)SIFT3D_AMD_SIMILARITY_GRID + grid_voxels(ox, oy, oz)) * sizeof(double);
+}
+
+int sift3d_hip_jacobian_penalty(const float *d_field, int ox, int oy, int oz, double ref, void *d_record, double *d_grad,
+                                void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_hip_jacobian_penalty";
+    if (!d_field || !d_record || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz))
+        return SIFT3D_FAILURE;
+    if (!isfinite(ref) || ref == 0.0)
+        return refuse(what, "the reference determinant must be finite and not 0");
+    if (check_aligned(what, ADDR(d_record) | ADDR(d_grad) | ADDR(d_work), ADDR(d_field)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_field, field_bytes(ox, oy, oz) } };
+        const range_t out[] = { { d_record, SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES },
+                                { d_work, sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz) },
+                                { d_grad, d_grad ? 3 * grid_voxels(ox, oy, oz) * sizeof(double) : 0 } };
+        if (ranges_aliased(out, 3, in, 1))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_jacobian_penalty_launch(what, d_field, ox, oy, oz, ref, (double *)d_record, d_grad, (double *)d_work,
+                                          stream);
+}
+
+/* the weight tables, S and the adjoint's two intermediate arrays, then the penalty's work */
+static size_t ffd_jacobian_gradient_doubles(int ox, int oy, int oz, int gy, int gz)
+{
+    return 3 * grid_voxels(ox, oy, oz) + 3 * grid_voxels(ox, oy, gz) + 3 * grid_voxels(ox, gy, gz);
+}
+
+size_t sift3d_amd_ffd_jacobian_gradient_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz)
+{
+    if (ox <= 0 || oy <= 0 || oz <= 0 || !ffd_spacing_ok(dx, dy, dz))
+        return 0;
+    return pad16(ffd_weights_bytes(dx, dy, dz)) +
+           ffd_jacobian_gradient_doubles(ox, oy, oz, sift3d_amd_ffd_lattice_dim(oy, dy),
+                                         sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double) +
+           sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz);
+}
+
+int sift3d_hip_ffd_jacobian_gradient(const float *d_field, int ox, int oy, int oz, int dx, int dy, int dz, double ref,
+                                     void *d_record, double *d_GJ, void *d_work, void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_jacobian_gradient";
+    int gx, gy, gz;
+    if (!d_field || !d_record || !d_GJ || !d_work)
+        return refuse(what, "NULL argument");
+    if (check_dims(what, ox, oy, oz))
+        return SIFT3D_FAILURE;
+    if (!ffd_spacing_ok(dx, dy, dz))
+        return refuse(what, "the spacing must be in [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    if (!isfinite(ref) || ref == 0.0)
+        return refuse(what, "the reference determinant must be finite and not 0");
+    if (check_aligned(what, ADDR(d_record) | ADDR(d_GJ), ADDR(d_field)))
+        return SIFT3D_FAILURE;
+    if (ADDR(d_work) & 15)
+        return refuse(what, "a buffer is misaligned");
+    gx = sift3d_amd_ffd_lattice_dim(ox, dx);
+    gy = sift3d_amd_ffd_lattice_dim(oy, dy);
+    gz = sift3d_amd_ffd_lattice_dim(oz, dz);
+    {
+        const range_t in[] = { { d_field, field_bytes(ox, oy, oz) } };
+        const range_t out[] = { { d_record, SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES },
+                                { d_GJ, 3 * grid_voxels(gx, gy, gz) * sizeof(double) },
+                                { d_work, sift3d_amd_ffd_jacobian_gradient_work_bytes(ox, oy, oz, dx, dy, dz) } };
+        if (ranges_aliased(out, 3, in, 1))
+            return refuse(what, ALIASED);
+    }
+    if (ffd_upload_weights(dx, dy, dz, (float *)d_work, stream))
+        return SIFT3D_FAILURE;
+    return sift3d_ffd_jacobian_gradient_launch(what, d_field, ox, oy, oz, gx, gy, gz, dx, dy, dz, (const float *)d_work,
+                                               ref, (double *)d_record, d_GJ,
+                                               (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))),
+                                               stream);
+}
+
 /* ---- the driver ---- */
 
 void sift3d_amd_ffd_refine_default_params(sift3d_amd_ffd_refine_params *p)
@@ -404,10 +509,19 @@ typedef struct {
     double see, R, gmax;
 } ffd_head;
 
-/* an evaluation on the host: the record's head and the image term of the cost (S_ee / n, or -mi; NaN when n == 0) */
+/* the penalty's record ("Jacobian penalty") */
+typedef struct {
+    uint64_t nonpos;
+    double sum, rmin, rmax;
+} ffd_jac_head;
+
+/* an evaluation on the host: the record's head and the image term of the cost (S_ee / n, or -mi; NaN when n == 0);
+ * with a penalty its record and P = sum / N */
 typedef struct {
     ffd_head h;
     double image;
+    ffd_jac_head j;
+    double P;
 } ffd_eval;
 
 typedef struct {
@@ -420,13 +534,26 @@ typedef struct {
     void *stream;
     mi_state *ms;                                /* MI (sift3d_affine_refine.c): bins, ranges, histogram, W; or NULL */
     float s_f;                                   /* MI: the fixed bin's scale */
+    const sift3d_ffd_jac *jac;                   /* the Jacobian penalty's weight and buffers; or NULL */
 } ffd_ctx;
+
+/* with a penalty: its record to the host, ahead of the wait that the caller makes */
+static int ffd_jac_fetch(const ffd_ctx *x, ffd_eval *e)
+{
+    return x->jac ? sift3d_hip_memcpy_d2h(&e->j, x->jac->d_rec, sizeof(e->j), x->stream) : SIFT3D_SUCCESS;
+}
+
+static void ffd_jac_mean(const ffd_ctx *x, const ffd_level *lv, ffd_eval *e)
+{
+    e->P = x->jac ? e->j.sum / (double)grid_voxels(lv->ox, lv->oy, lv->oz) : 0.0;
+}
 
 /* one evaluation at lattice c on `lv`: the field, then
  *   MSD: the record, R and the gradient, the head's copy to the host and the wait for it;
  *   MI:  the histogram through the field (its partial counts in the evaluation's partial slots) and R, histogram, count
  *        and head to the host and the wait for them, sift3d_amd_parzen_mi.  ms->W is left holding the table and
- *        ms->sim_trial the measures; no gradient is made (ffd_mi_gradient), and e->h.gmax is not meaningful. */
+ *        ms->sim_trial the measures; no gradient is made (ffd_mi_gradient), and e->h.gmax is not meaningful.
+ * With a penalty (x->jac) its passes run with the others and its record comes to the host in the same wait. */
 static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv, const double *A, const float *c,
                         float *grad, ffd_eval *e)
 {
@@ -440,58 +567,72 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
                                       x->d_field, ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m,
                                       (unsigned long long *)ms->d_hist, (unsigned long long *)(ms->d_hist + cells),
                                       x->d_eval, x->stream, lv->WF, lv->WM) ||
-            sift3d_ffd_mi_launch(what, 1, 0, NULL, lv->ox, lv->oy, lv->oz, NULL, lv->nx, lv->ny, lv->nz, x->d_field, c,
-                                 lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
-                                 ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
-                                 lv->WF, lv->WM) ||
+            sift3d_ffd_mi_jac_launch(what, 1, 0, NULL, lv->ox, lv->oy, lv->oz, NULL, lv->nx, lv->ny, lv->nz, x->d_field,
+                                     c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
+                                     ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval,
+                                     x->stream, lv->WF, lv->WM, x->jac) ||
             sift3d_hip_memcpy_d2h(ms->hist, ms->d_hist, (cells + 1) * sizeof(uint64_t), x->stream) ||
-            sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || sift3d_hip_stream_sync(x->stream) ||
+            sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
+            sift3d_hip_stream_sync(x->stream) ||
             sift3d_amd_parzen_mi(ms->hist, ms->bins, &ms->sim_trial, ms->W))
             return SIFT3D_FAILURE;
         e->h.n = ms->hist[cells];
         e->h.see = 0.0;
         e->h.gmax = NAN;
         e->image = -ms->sim_trial.mi;                        /* NaN when nothing was counted */
+        ffd_jac_mean(x, lv, e);
         return SIFT3D_SUCCESS;
     }
-    if (sift3d_ffd_evaluate_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
-                                   lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
-                                   x->d_rec, grad, x->d_eval, x->stream, lv->WF, lv->WM) ||
-        sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || sift3d_hip_stream_sync(x->stream))
+    if (sift3d_ffd_evaluate_jac_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field,
+                                       c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
+                                       x->d_rec, grad, x->d_eval, x->stream, lv->WF, lv->WM, x->jac) ||
+        sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
+        sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
     e->image = e->h.n ? e->h.see / (double)e->h.n : NAN;
+    ffd_jac_mean(x, lv, e);
     return SIFT3D_SUCCESS;
 }
 
 /* MI: the gradient at c, the lattice of the evaluation that left its table in ms->W, its field in d_field and its
  * second derivatives in the work buffer (no evaluation was made since): W to the device, the force, adjoint, bending
- * gradient and combine passes, gmax to the host and the wait for it */
+ * gradient and combine passes (with a penalty of weight > 0, its value and gradient passes on the same field: the same
+ * record once more, S and GJ), gmax to the host and the wait for it */
 static int ffd_mi_gradient(const char *what, const ffd_ctx *x, const ffd_level *lv, const float *c, float *grad,
                            ffd_eval *e)
 {
     mi_state *ms = x->ms;
     ffd_head h;
     if (sift3d_hip_memcpy_h2d(ms->d_W, ms->W, (size_t)ms->bins * ms->bins * sizeof(double), x->stream) ||
-        sift3d_ffd_mi_launch(what, 0, 1, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
-                             lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
-                             ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
-                             lv->WF, lv->WM) ||
+        sift3d_ffd_mi_jac_launch(what, 0, 1, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
+                                 lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
+                                 ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
+                                 lv->WF, lv->WM, x->jac && x->jac->weight > 0 ? x->jac : NULL) ||
         sift3d_hip_memcpy_d2h(&h, x->d_rec, sizeof(h), x->stream) || sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
     e->h.gmax = h.gmax;
     return SIFT3D_SUCCESS;
 }
 
-static double ffd_cost(const ffd_eval *e, double bending)
+/* jacobian: the penalty's weight; 0 (also: no penalty) adds no third term */
+static double ffd_cost(const ffd_eval *e, double bending, double jacobian)
 {
-    return e->image + bending * e->h.R;
+    const double two = e->image + bending * e->h.R;
+    return jacobian > 0 ? two + jacobian * e->P : two;
 }
 
-static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_eval *v, double bending, double step, int accepted,
-                      int level)
+/* penalty: the caller's array parallel to the trail, or NULL */
+static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_eval *v, double bending, double jacobian,
+                      sift3d_amd_ffd_penalty *penalty, double step, int accepted, int level)
 {
     sift3d_amd_ffd_evaluation *e = res->trail + res->evaluations++;
-    e->E = ffd_cost(v, bending);
+    if (penalty) {
+        sift3d_amd_ffd_penalty *q = penalty + (e - res->trail);
+        q->P = v->P;
+        q->rmin = v->j.rmin;
+        q->nonpos = v->j.nonpos;
+    }
+    e->E = ffd_cost(v, bending, jacobian);
     e->msd = v->image;
     e->R = v->h.R;
     e->n = v->h.n;
@@ -503,12 +644,15 @@ static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_eval *v, doub
 /* the shared body of the three drivers: `masked` selects the work buffer's size; the masks may still be NULL.  ms (MI;
  * else NULL): bins and ranges, checked here after the FFD drivers' own checks; the cost's image term is -mi, the
  * gradient is made only at the lattice a step starts from, and ms->sim leaves with the measures at the final lattice on
- * level 0. */
+ * level 0.  penalty (the Jacobian driver; else NULL): the array parallel to the trail; `jacobian` is the weight and
+ * `ref` the reference determinant, both checked by the caller, and the work buffer is that driver's. */
 static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                       int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
                       sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
-                      void *stream, int masked, const float *d_WF, const float *d_WM, mi_state *ms)
+                      void *stream, int masked, const float *d_WF, const float *d_WM, mi_state *ms, double jacobian,
+                      double ref, sift3d_amd_ffd_penalty *penalty)
 {
+    sift3d_ffd_jac jac;
     sift3d_amd_ffd_refine_params prm;
     ffd_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
     ffd_eval rec, trial;
@@ -543,7 +687,8 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_lattice, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3) },
                                 { d_field, field_bytes(ox, oy, oz) },
-                                { d_work, (ms       ? sift3d_amd_ffd_mi_refine_work_bytes
+                                { d_work, (penalty  ? sift3d_amd_ffd_refine_jacobian_work_bytes
+                                           : ms     ? sift3d_amd_ffd_mi_refine_work_bytes
                                            : masked ? sift3d_amd_ffd_refine_masked_work_bytes
                                                     : sift3d_amd_ffd_refine_work_bytes)(ox, oy, oz, nx, ny, nz,
                                                                                         prm.spacing[0], prm.spacing[1],
@@ -578,6 +723,17 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     x.stream = stream;
     x.ms = ms;
     x.s_f = s_f;
+    x.jac = NULL;
+    if (penalty) {                                           /* behind everything the MI driver lays out */
+        work_bytes = sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
+                                                         prm.spacing[2], prm.levels);
+        jac.weight = jacobian;
+        jac.ref = ref;
+        jac.d_rec = (double *)(w + work_bytes);
+        jac.d_GJ = (double *)(w + work_bytes + SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES);
+        jac.d_work = jac.d_GJ + 3 * grid_voxels(lv[0].gx, lv[0].gy, lv[0].gz);
+        x.jac = &jac;
+    }
     if (ms) {                                                /* behind everything the masked driver lays out */
         ms->d_hist = (uint64_t *)(w + work_bytes - MI_EXTRA_BYTES);
         ms->d_W = (double *)(w + work_bytes - MI_TABLE_BYTES);
@@ -628,9 +784,9 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
             return SIFT3D_FAILURE;
         if (ms)
             ms->sim = ms->sim_trial;
-        ffd_trail(result, &rec, prm.bending, s, 1, l);
+        ffd_trail(result, &rec, prm.bending, jacobian, penalty, s, 1, l);
         n_first = rec.h.n;
-        E = ffd_cost(&rec, prm.bending);
+        E = ffd_cost(&rec, prm.bending, jacobian);
         if (!isfinite(E))
             stop = SIFT3D_AMD_FFD_STOP_FAILED;
         else
@@ -655,9 +811,9 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                     ffd_evaluate(what, &x, v, have_A ? A : NULL, ct, gt, &trial))
                     return SIFT3D_FAILURE;
                 evals++;
-                Et = ffd_cost(&trial, prm.bending);
+                Et = ffd_cost(&trial, prm.bending, jacobian);
                 accept = isfinite(Et) && (double)trial.h.n >= prm.min_overlap * (double)n_first && Et < E;
-                ffd_trail(result, &trial, prm.bending, s, accept, l);
+                ffd_trail(result, &trial, prm.bending, jacobian, penalty, s, accept, l);
                 if (!isfinite(Et) && !(ms && trial.h.n == 0)) {      /* MI: a trial that counts nothing is rejected */
                     stop = SIFT3D_AMD_FFD_STOP_FAILED;
                     break;
@@ -699,7 +855,7 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
                                  void *stream)
 {
     return ffd_refine("sift3d_amd_ffd_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL);
+                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL, 0.0, 1.0, NULL);
 }
 
 int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -708,7 +864,7 @@ int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz
                                         void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     return ffd_refine("sift3d_amd_ffd_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL);
+                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL, 0.0, 1.0, NULL);
 }
 
 int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -730,7 +886,60 @@ int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, co
     ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
     *mi_out = ms.sim;
     rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, &ms);
+                    d_WF, d_WM, &ms, 0.0, 1.0, NULL);
     *mi_out = ms.sim;
+    return rc;
+}
+
+/* the Jacobian driver's: the MI driver's, then the penalty's record, GJ on the finest lattice and the penalty's work on
+ * the finest grid (which cover every coarser level's) */
+size_t sift3d_amd_ffd_refine_jacobian_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                                 int levels)
+{
+    const size_t mi = sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, dx, dy, dz, levels);
+    if (!mi)
+        return 0;
+    return mi + SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES +
+           3 * grid_voxels(sift3d_amd_ffd_lattice_dim(ox, dx), sift3d_amd_ffd_lattice_dim(oy, dy),
+                           sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double) +
+           sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz);
+}
+
+int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                          int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                                          sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                          void *d_work, void *stream, const float *d_WF, const float *d_WM, int bins,
+                                          float lo_f, float hi_f, float lo_m, float hi_m, sift3d_amd_similarity *mi_out,
+                                          double jacobian, sift3d_amd_ffd_penalty *penalty)
+{
+    static const char what[] = "sift3d_amd_ffd_refine_jacobian_device";
+    mi_state ms;
+    double ref = 1.0;
+    int rc;
+    if (!penalty || (bins != 0 && !mi_out))
+        return refuse(what, "NULL argument");
+    if (!isfinite(jacobian) || jacobian < 0)
+        return refuse(what, "the Jacobian weight must be finite and not negative");
+    if (A_in) {
+        const double *A = A_in;
+        if (check_affine(what, A))
+            return SIFT3D_FAILURE;
+        ref = A[0] * (A[5] * A[10] - A[6] * A[9]) - A[1] * (A[4] * A[10] - A[6] * A[8]) +
+              A[2] * (A[4] * A[9] - A[5] * A[8]);
+        if (!isfinite(ref) || ref == 0.0)
+            return refuse(what, "the linear part of A must have a finite determinant that is not 0");
+    }
+    ms.bins = bins;
+    ms.lo_f = lo_f; ms.hi_f = hi_f;
+    ms.lo_m = lo_m; ms.hi_m = hi_m;
+    ms.sim.n = 0;
+    ms.sim.msd = ms.sim.ncc = ms.sim.mi = ms.sim.nmi = NAN;
+    ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
+    if (mi_out)
+        *mi_out = ms.sim;
+    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
+                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty);
+    if (mi_out)
+        *mi_out = ms.sim;
     return rc;
 }

@@ -26,6 +26,11 @@
 //     finish_reduce.
 #include "sift3d_resample.h"
 #include "sift3d_parzen.h"
+#include "sift3d_ffd_jac.h"
+
+// sift3d_jacobian_penalty.hip
+extern "C" int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
+                                              double *d_rec, double *d_S, double *d_work, void *stream);
 
 namespace {
 
@@ -433,6 +438,25 @@ __global__ __launch_bounds__(256) void k_ffd_combine(const FfdCombineArgs s)
         s.part[blockIdx.x] = r;
 }
 
+// k_ffd_combine with the Jacobian penalty's term (header, "Jacobian penalty"): grad = (float)(((scale / n) * Gc +
+// bending * dR) + jn * GJ), jn = jacobian / N made on the host.  A kernel of its own: the evaluations without the
+// penalty launch k_ffd_combine as before.
+__global__ __launch_bounds__(256) void k_ffd_combine_jac(const FfdCombineArgs s, const double *GJ, double jn)
+{
+    __shared__ double slot[4];
+    const double n = (double)reinterpret_cast<const unsigned long long *>(s.rec)[0];
+    const double two_n = s.scale / n;
+    double mx = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.total; i += (size_t)gridDim.x * 256) {
+        const float g = (float)((two_n * s.Gc[i] + s.bending * s.dR[i]) + jn * GJ[i]);
+        s.grad[i] = g;
+        mx = fmax(mx, (double)fabsf(g));
+    }
+    const double r = workgroup_reduce<Max>(mx, slot);
+    if (threadIdx.x == 0)
+        s.part[blockIdx.x] = r;
+}
+
 __global__ __launch_bounds__(256) void k_ffd_step(const float *c, const float *grad, float a, float *out, size_t n)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
@@ -514,14 +538,34 @@ extern "C" int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int g
 
 // The parts of an evaluation, in the order they run.  The MSD entries run them all (the bending entry all but the image
 // term); the MI driver runs FFD_BEND_VALUE per evaluation and the other three only where a step starts.
-enum { FFD_IMAGE = 1, FFD_BEND_VALUE = 2, FFD_BEND_GRAD = 4, FFD_COMBINE = 8, FFD_ALL = 15 };
+// FFD_JAC_VALUE, FFD_JAC_GRAD (with a penalty only; one of the two): the penalty's record from the field, alone or with S
+// and its adjoint GJ.  They run after the image term, whose force buffer S takes over once Gc is formed.
+enum { FFD_IMAGE = 1, FFD_BEND_VALUE = 2, FFD_BEND_GRAD = 4, FFD_COMBINE = 8, FFD_ALL = 15, FFD_JAC_VALUE = 16,
+       FFD_JAC_GRAD = 32 };
+
+// the adjoint of the spline on src [3][oz][oy][ox] -> dst [3][gz][gy][gx]: z, y, x
+static int ffd_adjoint_passes(const double *src, double *t1, double *t2, double *dst, const float *d_w, int ox, int oy,
+                              int oz, int gx, int gy, int gz, int dx, int dy, int dz, hipStream_t st)
+{
+    const FfdAdjArgs az = {src, t1, d_w + 4 * (size_t)(dx + dy), (size_t)oy * ox, 3 * (size_t)gz * oy * ox, oz, gz, dz};
+    const FfdAdjArgs ay = {t1, t2, d_w + 4 * (size_t)dx, (size_t)ox, 3 * (size_t)gz * gy * ox, oy, gy, dy};
+    const FfdAdjArgs ax = {t2, dst, d_w, 1, 3 * (size_t)gx * gy * gz, ox, gx, dx};
+    const FfdAdjArgs *pass[3] = {&az, &ay, &ax};
+    for (int i = 0; i < 3; i++) {
+        hipLaunchKernelGGL(k_ffd_adjoint, dim3(flat_grid(pass[i]->total, MAX_GRID)), dim3(256), 0, st, *pass[i]);
+        LAUNCH_CHECK();
+    }
+    return SIFT3D_SUCCESS;
+}
 
 // d_rec: {uint64 n; double S_ee, R, gmax} then Gc and dR, [3][gz][gy][gx] doubles each.  d_work: partial slots
 // [2][FFD_GRID] doubles, then the force [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox], D [18][N] doubles.
 // d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.  FFD_BEND_GRAD reads the D that the
 // last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.  mi: what the MI
-// force needs beside the MSD force's arguments (NULL: the MSD).
-static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const float *d_F, int ox, int oy,
+// force needs beside the MSD force's arguments (NULL: the MSD).  jac: the penalty's buffers (NULL: none); the combine
+// takes its term when jac->weight > 0.
+static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const sift3d_ffd_jac *jac,
+                              const float *d_F, int ox, int oy,
                               int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
                               const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
                               const double *stencils, double bending, double *d_rec, float *d_grad, double *d_work,
@@ -558,15 +602,15 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish<Add>, dim3(1), dim3(256), 0, st, (const double *)part, grid, d_rec + 1, 1.0);
         LAUNCH_CHECK();
-        // the adjoint: z, y, x
-        const FfdAdjArgs az = {force, t1, d_w + 4 * (size_t)(dx + dy), (size_t)oy * ox, 3 * (size_t)gz * oy * ox, oz, gz, dz};
-        const FfdAdjArgs ay = {t1, t2, d_w + 4 * (size_t)dx, (size_t)ox, 3 * (size_t)gz * gy * ox, oy, gy, dy};
-        const FfdAdjArgs ax = {t2, Gc, d_w, 1, 3 * cvox, ox, gx, dx};
-        const FfdAdjArgs *pass[3] = {&az, &ay, &ax};
-        for (int i = 0; i < 3; i++) {
-            hipLaunchKernelGGL(k_ffd_adjoint, dim3(flat_grid(pass[i]->total, MAX_GRID)), dim3(256), 0, st, *pass[i]);
-            LAUNCH_CHECK();
-        }
+        if (ffd_adjoint_passes(force, t1, t2, Gc, d_w, ox, oy, oz, gx, gy, gz, dx, dy, dz, st))
+            return SIFT3D_FAILURE;
+    }
+    if (jac && (parts & (FFD_JAC_VALUE | FFD_JAC_GRAD))) {
+        const bool with_grad = parts & FFD_JAC_GRAD;
+        if (sift3d_jacobian_penalty_launch(fn, d_field, ox, oy, oz, jac->ref, jac->d_rec, with_grad ? force : nullptr,
+                                           jac->d_work, stream) ||
+            (with_grad && ffd_adjoint_passes(force, t1, t2, jac->d_GJ, d_w, ox, oy, oz, gx, gy, gz, dx, dy, dz, st)))
+            return SIFT3D_FAILURE;
     }
     // the bending energy and its gradient
     FfdBendArgs b;
@@ -592,7 +636,11 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
     if (parts & FFD_COMBINE) {
         const FfdCombineArgs c = {d_rec, Gc, dR, d_grad, part, bending, mi ? 1.0 : 2.0, 3 * cvox};
         const unsigned cgrid = flat_grid(3 * cvox, FFD_GRID);
-        hipLaunchKernelGGL(k_ffd_combine, dim3(cgrid), dim3(256), 0, st, c);
+        if (jac && jac->weight > 0.0)
+            hipLaunchKernelGGL(k_ffd_combine_jac, dim3(cgrid), dim3(256), 0, st, c, (const double *)jac->d_GJ,
+                               jac->weight / (double)vox);
+        else
+            hipLaunchKernelGGL(k_ffd_combine, dim3(cgrid), dim3(256), 0, st, c);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish<Max>, dim3(1), dim3(256), 0, st, (const double *)part, cgrid, d_rec + 3, 1.0);
         LAUNCH_CHECK();
@@ -600,21 +648,55 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
     return SIFT3D_SUCCESS;
 }
 
-// The MSD evaluation; d_F == NULL: the bending entry, no image term and no combined gradient.
+// the penalty's parts of an evaluation that forms a gradient, or of one that does not
+static unsigned ffd_jac_parts(const sift3d_ffd_jac *jac, bool gradient)
+{
+    return !jac ? 0u : gradient && jac->weight > 0.0 ? FFD_JAC_GRAD : FFD_JAC_VALUE;
+}
+
+// The MSD evaluation; d_F == NULL: the bending entry, no image term and no combined gradient.  jac: the Jacobian
+// penalty of the field, or NULL.
+extern "C" int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
+                                              const float *d_M, int nx, int ny, int nz, const float *d_field,
+                                              const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                                              const float *d_w, const double *stencils, double bending, double *d_rec,
+                                              float *d_grad, double *d_work, void *stream, const float *d_WF,
+                                              const float *d_WM, const sift3d_ffd_jac *jac)
+{
+    return ffd_evaluate_parts(fn, d_F ? FFD_ALL | ffd_jac_parts(jac, true) : FFD_BEND_VALUE | FFD_BEND_GRAD, nullptr,
+                              jac, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w,
+                              stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+}
+
 extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
                                           int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
                                           int gy, int gz, int dx, int dy, int dz, const float *d_w,
                                           const double *stencils, double bending, double *d_rec, float *d_grad,
                                           double *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
-    return ffd_evaluate_parts(fn, d_F ? FFD_ALL : FFD_BEND_VALUE | FFD_BEND_GRAD, nullptr, d_F, ox, oy, oz, d_M, nx, ny,
-                              nz, d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work,
-                              stream, d_WF, d_WM);
+    return sift3d_ffd_evaluate_jac_launch(fn, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
+                                          d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM, nullptr);
 }
 
 // The MI evaluation.  value != 0: the bending value alone (what every evaluation of the MI driver needs on the device
 // beside the field and the histogram; the image arguments are not read).  gradient != 0: the force of psi from d_W, its
 // adjoint, the bending gradient from the D of the last value pass, and the combined gradient with the factor 1 / n.
+// jac: the Jacobian penalty of the field, or NULL: its record with either of value and gradient, S and GJ with gradient.
+extern "C" int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy,
+                                        int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
+                                        const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                                        const float *d_w, const double *stencils, double bending, int bins, float lo_f,
+                                        float s_f, float lo_m, float hi_m, const double *d_W, double *d_rec,
+                                        float *d_grad, double *d_work, void *stream, const float *d_WF,
+                                        const float *d_WM, const sift3d_ffd_jac *jac)
+{
+    const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
+    const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u) |
+                           ffd_jac_parts(jac, gradient != 0);
+    return ffd_evaluate_parts(fn, parts, &mi, jac, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy,
+                              dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+}
+
 extern "C" int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
                                     const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat,
                                     int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
@@ -622,10 +704,22 @@ extern "C" int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, con
                                     float hi_m, const double *d_W, double *d_rec, float *d_grad, double *d_work,
                                     void *stream, const float *d_WF, const float *d_WM)
 {
-    const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
-    const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u);
-    return ffd_evaluate_parts(fn, parts, &mi, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
-                              d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+    return sift3d_ffd_mi_jac_launch(fn, value, gradient, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz,
+                                    dx, dy, dz, d_w, stencils, bending, bins, lo_f, s_f, lo_m, hi_m, d_W, d_rec, d_grad,
+                                    d_work, stream, d_WF, d_WM, nullptr);
+}
+
+// The penalty of a field and its gradient over the lattice of that grid: the record, S and its adjoint GJ.  d_work: S
+// [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox] doubles, then the penalty's work.
+extern "C" int sift3d_ffd_jacobian_gradient_launch(const char *fn, const float *d_field, int ox, int oy, int oz, int gx,
+                                                   int gy, int gz, int dx, int dy, int dz, const float *d_w, double ref,
+                                                   double *d_rec, double *d_GJ, double *d_work, void *stream)
+{
+    const size_t vox = (size_t)ox * oy * oz;
+    double *S = d_work, *t1 = S + 3 * vox, *t2 = t1 + 3 * (size_t)gz * oy * ox, *jwork = t2 + 3 * (size_t)gz * gy * ox;
+    if (sift3d_jacobian_penalty_launch(fn, d_field, ox, oy, oz, ref, d_rec, S, jwork, stream))
+        return SIFT3D_FAILURE;
+    return ffd_adjoint_passes(S, t1, t2, d_GJ, d_w, ox, oy, oz, gx, gy, gz, dx, dy, dz, (hipStream_t)stream);
 }
 
 extern "C" int sift3d_ffd_step_launch(const float *d_c, const float *d_grad, float a, float *d_out, size_t n,

@@ -95,6 +95,12 @@ class FFDRefineResult(C.Structure):                        # sift3d_amd_ffd_refi
                 ("trail", FFDEvaluation * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))]
 
 
+class FFDPenalty(C.Structure):                             # sift3d_amd_ffd_penalty
+    _fields_ = [("P", C.c_double), ("rmin", C.c_double), ("nonpos", C.c_uint64)]
+
+
+JACOBIAN_PENALTY_RECORD_BYTES = 32
+
 _bound = None
 
 
@@ -264,6 +270,17 @@ def lib():
                                                       C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp, C.c_int,
                                                       C.c_float, C.c_float, C.c_float, C.c_float,
                                                       C.POINTER(Similarity)]),
+        "sift3d_amd_jacobian_penalty_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_hip_jacobian_penalty": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]),
+        "sift3d_amd_ffd_jacobian_gradient_work_bytes": (C.c_size_t, [C.c_int] * 6),
+        "sift3d_hip_ffd_jacobian_gradient": (C.c_int, [vp] + [C.c_int] * 6 + [C.c_double, vp, vp, vp, vp]),
+        "sift3d_amd_ffd_refine_jacobian_work_bytes": (C.c_size_t, [C.c_int] * 10),
+        "sift3d_amd_ffd_refine_jacobian_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                            C.c_int, C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
+                                                            C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp,
+                                                            C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                            C.POINTER(Similarity), C.c_double,
+                                                            C.POINTER(FFDPenalty)]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -1383,6 +1400,90 @@ def ffd_mi_refine(F, M, bins, range_f, range_m, A=None, params=None, work=None, 
                                                  C.byref(sim)),
            "sift3d_amd_ffd_mi_refine_device")
     return res, lattice, field, sim
+
+
+# ---- Jacobian penalty ("Jacobian penalty") ----
+def jacobian_penalty_record(record):
+    """(nonpos, sum, rmin, rmax) of a penalty record (a CUDA tensor of JACOBIAN_PENALTY_RECORD_BYTES); waits for the
+    stream"""
+    import torch
+    raw = record.view(torch.uint8)[:JACOBIAN_PENALTY_RECORD_BYTES].cpu().numpy()
+    v = raw[8:32].view(np.float64)
+    return int(raw[:8].view(np.uint64)[0]), float(v[0]), float(v[1]), float(v[2])
+
+
+def jacobian_penalty(field, ref=1.0, gradient=False, work=None):
+    """sift3d_hip_jacobian_penalty on torch's current stream: field [3, oz, oy, ox] torch CUDA float32, ref the
+    reference determinant.  Returns (record: int64 CUDA tensor, read by jacobian_penalty_record; S: float64 CUDA tensor
+    [3, oz, oy, ox], the gradient in sum form, or None)."""
+    import torch
+    what = "jacobian_penalty"
+    _field_tensor(field, what)
+    _, oz, oy, ox = field.shape
+    need = lib().sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz)
+    work = _work(work, (need + 3) // 4, field, what)
+    record = torch.empty(JACOBIAN_PENALTY_RECORD_BYTES // 8, dtype=torch.int64, device=field.device)
+    S = torch.empty((3, oz, oy, ox), dtype=torch.float64, device=field.device) if gradient else None
+    _check(lib().sift3d_hip_jacobian_penalty(field.data_ptr(), ox, oy, oz, float(ref), record.data_ptr(),
+                                             None if S is None else S.data_ptr(), work.data_ptr(), current_stream()),
+           "sift3d_hip_jacobian_penalty")
+    return record, S
+
+
+def ffd_jacobian_gradient(field, spacing, ref=1.0, work=None):
+    """sift3d_hip_ffd_jacobian_gradient on torch's current stream: (record, GJ float64 CUDA tensor [3, gz, gy, gx]), the
+    penalty of the field and the derivative of its sum over the control lattice of the field's grid at `spacing`"""
+    import torch
+    what = "ffd_jacobian_gradient"
+    _field_tensor(field, what)
+    _, oz, oy, ox = field.shape
+    dx, dy, dz = ffd_spacing(spacing, what)
+    need = lib().sift3d_amd_ffd_jacobian_gradient_work_bytes(ox, oy, oz, dx, dy, dz)
+    work = _work(work, (need + 3) // 4, field, what)
+    record = torch.empty(JACOBIAN_PENALTY_RECORD_BYTES // 8, dtype=torch.int64, device=field.device)
+    GJ = torch.empty(ffd_lattice_shape((oz, oy, ox), (dx, dy, dz)), dtype=torch.float64, device=field.device)
+    _check(lib().sift3d_hip_ffd_jacobian_gradient(field.data_ptr(), ox, oy, oz, dx, dy, dz, float(ref),
+                                                  record.data_ptr(), GJ.data_ptr(), work.data_ptr(), current_stream()),
+           "sift3d_hip_ffd_jacobian_gradient")
+    return record, GJ
+
+
+def ffd_refine_jacobian(F, M, jacobian, bins=0, range_f=(0.0, 1.0), range_m=(0.0, 1.0), A=None, params=None, work=None,
+                        mask_fixed=None, mask_moving=None):
+    """sift3d_amd_ffd_refine_jacobian_device on torch CUDA float32 contiguous volumes, on torch's current stream: the
+    FFD drivers with the Jacobian penalty of weight `jacobian`; bins == 0: the MSD (the ranges are not read), else the
+    mutual information as ffd_mi_refine.  Returns (FFDRefineResult, lattice, field, Similarity or None, penalty: one
+    (P, rmin, nonpos) per trail entry)."""
+    import torch
+    what = "ffd_refine_jacobian"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    a, ap = _ffd_A(A, what)
+    bins = _parzen_bins(bins, what) if bins else 0
+    p = params if params is not None else ffd_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    d = tuple(p.spacing)
+    need = lib().sift3d_amd_ffd_refine_jacobian_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
+    if need == 0:
+        raise ValueError(what + ": levels must be in [1, %d] and the spacing in [1, %d]"
+                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
+    work = _work(work, (need + 3) // 4, F, what)
+    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    res = FFDRefineResult()
+    sim = Similarity()
+    pen = (FFDPenalty * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
+    ranges = _parzen_ranges(range_f, range_m) if bins else (0.0, 1.0, 0.0, 1.0)
+    _check(lib().sift3d_amd_ffd_refine_jacobian_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap,
+                                                       C.byref(p), C.byref(res), lattice.data_ptr(), field.data_ptr(),
+                                                       work.data_ptr(), current_stream(), *masks, bins, *ranges,
+                                                       C.byref(sim), float(jacobian), pen),
+           "sift3d_amd_ffd_refine_jacobian_device")
+    penalty = [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
+    return res, lattice, field, (sim if bins else None), penalty
 
 
 def _dense_args(src, out, what):
