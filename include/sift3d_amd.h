@@ -1226,6 +1226,86 @@ sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int oz, 
                                       double jacobian, sift3d_amd_ffd_penalty *penalty);
 
 /* ------------------------------------------------------------------------ */
+/* Multi-channel free-form deformation: the MSD of a stack of channels        */
+/* ------------------------------------------------------------------------ */
+/* "B-spline free-form deformation" driven by the squared difference summed over nc >= 1 channels: the dense descriptor
+ * images of the two volumes (12 unit-length channels, which do not change under a gain or an offset of either volume),
+ * or several contrasts of one subject.  No upstream counterpart: PARITY UNPINNED, pinned to this contract and its numpy
+ * restatement (tests/ffd_channels_restatement.py).
+ *
+ * Inputs.  F[nc][oz][oy][ox] and M[nc][nz][ny][nx] float32, planar; one lattice, one field and one pair of masks
+ * (W_F[oz][oy][ox], W_M[nz][ny][nx], either may be NULL) for all channels.
+ * Per fixed voxel p with u = field(p): the sample point q = p + u(p), the inside test, the mask rule and the taps are
+ * those of sift3d_hip_ffd_evaluate_masked, word for word, and are the same for every channel.  Per channel c, on
+ * channel c of M with those taps: the LINEAR sample m_c and its gradient g_c (float, unfused, as in "Intensity-driven
+ * affine refinement"); e_c = m_c - f_c, a float subtraction; in double E_c = e_c, g_cd widened.
+ * Force.  Each product E_c g_cd is exact in double (two floats).  The additions are in double, in ascending c, and start
+ * from channel 0's product, not from +0.0:
+ *     S_d(p) = ((E_0 g_0d + E_1 g_1d) + E_2 g_2d) + ...
+ * A voxel that is not counted stores +0.0.  With nc == 1 this is the single-channel force, signed zeros included.  S_d
+ * is defined bit for bit.  After sift3d_hip_ffd_evaluate_channels it is left in d_work as double [3][oz][oy][ox] at
+ * byte offset 16 * (dx + dy + dz) + 16 * SIFT3D_AMD_SIMILARITY_GRID (behind the weight tables and the partial slots).
+ * Record: the layout of the FFD record (sift3d_amd_ffd_record_bytes).
+ *     n counts voxels, not voxel-channels;
+ *     S_ee = sum_p sum_c E_c E_c, in an order that is a function of the shapes only (per lane c ascending within a voxel,
+ *     then the partial slots of "B-spline free-form deformation"), no atomics: a call repeats its bytes; within
+ *     gamma_(nc * ox oy oz + 8) sum E_c E_c of the exact sum;
+ *     Gc[3][gz][gy][gx] = sum_p W(p; k, j, i) S_d(p): the adjoint passes of that section applied to S.  The computed
+ *     S_d is sum_c E_c g_cd (1 + theta_c) with |theta_c| <= gamma_(nc - 1) (nc - 1 additions of exact products), and the
+ *     adjoint adds at most k + 8 roundings to each of its terms as there (k the voxels under the control), so every
+ *     entry of Gc is within gamma_(k + nc + 8) sum_p sum_c |W E_c g_cd| of the exact sum: the single-channel bound plus
+ *     the nc - 1 additions of S;
+ *     R, dR and gmax are that section's.
+ * Cost and gradient: E = S_ee / n + bending * R (+ jacobian * P); d_grad = (float)((2.0 / n) * Gc + bending * dR) (+ the
+ * penalty's term), through the combine passes of the single-channel evaluation, unchanged.  With nc == 1 the record,
+ * the gradient and the field are sift3d_hip_ffd_evaluate_masked's byte for byte.
+ * sift3d_hip_ffd_evaluate_channels: the arguments of sift3d_hip_ffd_evaluate_masked with nc behind the moving grid.
+ * d_work: sift3d_amd_ffd_evaluate_channels_work_bytes() bytes, 16-byte aligned: the single-channel figure, one force
+ * volume whatever nc is.
+ *
+ * Driver (sift3d_amd_ffd_refine_channels_device).  The caller supplies every level's stacks and masks, level 0 the
+ * finest, as in "Multi-resolution demons": how they are made is the caller's choice (restrict2 of the level above, or
+ * features computed on the restricted volumes), and the driver restricts nothing.  Every dimension of level l >= 1,
+ * fixed and moving, must be the half (n + 1) / 2 of level l - 1's.  The loop, the halving of A[:][3] per level, the
+ * subdivision, the step rule, the stop reasons and the trail are sift3d_amd_ffd_refine_device's, one loop in the code
+ * too; the trail's msd is S_ee / n.  params->levels must equal `levels` (NULL params: the defaults, so levels == 3).
+ * `jacobian` and `penalty` are sift3d_amd_ffd_refine_jacobian_device's: penalty == NULL runs without the penalty (and
+ * jacobian must be 0); otherwise P is recorded per evaluation and jacobian > 0 adds the third term.
+ * d_work: sift3d_amd_ffd_refine_channels_work_bytes() bytes for level 0's fixed grid, 16-byte aligned: the evaluation's
+ * work, the record, five lattices, then the penalty's record, GJ and work.
+ *
+ * Refusals, before any device call: those of sift3d_hip_ffd_evaluate_masked and of the masked driver, and nc < 1, a NULL
+ * level table or a NULL d_F or d_M of a level, levels outside [1, SIFT3D_AMD_DEMONS_MAX_LEVELS] or != params->levels,
+ * dimensions that are not the halving chain, a level's stack or mask that is misaligned (4 bytes) or overlaps an output
+ * or the work buffer, a Jacobian weight that is negative, not finite, or not 0 without `penalty`; -1. */
+typedef struct {
+    const float *d_F;          /* fixed stack  [nc][oz][oy][ox] */
+    int ox, oy, oz;
+    const float *d_M;          /* moving stack [nc][nz][ny][nx] */
+    int nx, ny, nz;
+    const float *d_WF;         /* fixed mask [oz][oy][ox], or NULL */
+    const float *d_WM;         /* moving mask [nz][ny][nx], or NULL */
+} sift3d_amd_ffd_level;
+/* for bindings that restate the layout: sizeof the level struct (0), then the offsets of d_F (1), ox (2), d_M (3),
+ * nx (4), d_WF (5), d_WM (6); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_level_struct_bytes(int which);
+SIFT3D_AMD_API size_t sift3d_amd_ffd_evaluate_channels_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz);
+SIFT3D_AMD_API int
+sift3d_hip_ffd_evaluate_channels(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 int nc, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                 const double *A /*12 or NULL*/, double bending, float *d_field, void *d_record,
+                                 float *d_grad, void *d_work, void *stream, const float *d_WF, const float *d_WM);
+/* bytes of d_work for the driver, (ox, oy, oz) level 0's fixed grid (0 for bad arguments) */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_refine_channels_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz);
+/* level [levels] (host memory, level 0 the finest); A [12] on the host or NULL; penalty on the host or NULL */
+SIFT3D_AMD_API int
+sift3d_amd_ffd_refine_channels_device(const sift3d_amd_ffd_level *level, int levels, int nc, const double *A,
+                                      const sift3d_amd_ffd_refine_params *params,
+                                      sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                      void *d_work, void *stream, double jacobian,
+                                      sift3d_amd_ffd_penalty *penalty /*NULL when jacobian == 0*/);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

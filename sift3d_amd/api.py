@@ -1012,6 +1012,19 @@ def _mask_tensor(w, like, what, name):
     return w
 
 
+def _stack_tensor(v, what, name, device=None):
+    """a channel stack as a contiguous CUDA float32 tensor [nc, nz, ny, nx]: a tensor as it is, an array uploaded"""
+    import torch
+    from . import hip
+    if not _torch_tensor(v):
+        a = np.ascontiguousarray(v, np.float32)
+        if not device_available():
+            raise RuntimeError("%s: no HIP device is available; this library has no CPU path" % what)
+        v = torch.from_numpy(a).to(device if device is not None else "cuda")
+    hip._tensor(v, "%s: %s must be a contiguous float32 CUDA tensor [nc, nz, ny, nx]" % (what, name), dims=(4,))
+    return v
+
+
 def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fixed=None, range_moving=None,
                mask_fixed=None, mask_moving=None):
     """How well `fixed` agrees with `moving` seen through a pull map, in one pass on the device (contract:
@@ -1232,7 +1245,8 @@ def ffd_bending_energy(lattice, spacing):
 
 
 def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None,
-               metric="msd", bins=None, range_fixed=None, range_moving=None, jacobian=0.0, **params):
+               metric="msd", bins=None, range_fixed=None, range_moving=None, jacobian=0.0, features="intensity",
+               sigma=1.6, **params):
     """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
     `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
     include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
@@ -1258,8 +1272,33 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     away from the folding that `jacobian.folded` counts, without the smoothing that a larger `bending` buys it with.
     The result is then a JacFFDRefinement (JacMiFFDRefinement): the metric's fields, then penalty: one FFDPenalty(P,
     rmin, nonpositive) per trail entry, and jacobian_weight.  No calibration of the weight against the image term is
-    claimed.  jacobian == 0 is the call without it."""
+    claimed.  jacobian == 0 is the call without it.
+    features="descriptors" (3-D volumes) drives the deformation by the squared difference of the two volumes' dense
+    descriptor images summed over their 12 channels instead of the intensities (contract: "Multi-channel free-form
+    deformation"): the descriptors do not change under a gain or an offset of either volume, so this is the MSD fit for
+    volumes that differ by one.  Per level both volumes are restricted (restrict_volume) and the descriptors computed
+    on the restricted volumes with the same window `sigma` in that level's voxels: refine_field's rule.  No bin is
+    reoriented under the deformation (demons does not either).  With features="intensity", fixed [nc, oz, oy, ox] and
+    moving [nc, nz, ny, nx] of the same nc are the channels themselves (two contrasts of one subject, say), restricted
+    per level.  Masks stay 3-D, on the grids of the stacks; level l's are restrict_volume of level l - 1's float masks.
+    jacobian > 0 works as above.  The result is an FFDRefinement (JacFFDRefinement); the trail's `msd` is S_ee / n
+    with n counting voxels, and `warped` is `moving` through the field, every channel of a 4-D input.  metric="mi",
+    bins or ranges together with channels, any other `features`, a 4-D volume beside a 3-D one or with
+    features="descriptors", and stacks of unequal nc raise ValueError."""
     from . import hip
+    if features not in ("intensity", "descriptors"):
+        raise ValueError("refine_ffd: features must be 'intensity' or 'descriptors', not %r" % (features,))
+    dims = tuple(3 if isinstance(v, Image) else v.dim() if _torch_tensor(v) else np.ndim(v) for v in (fixed, moving))
+    if dims not in ((3, 3), (4, 4)) or (features == "descriptors" and dims != (3, 3)):
+        raise ValueError("refine_ffd: fixed and moving must both be volumes [nz, ny, nx]%s, not %d-D and %d-D"
+                         % ("" if features == "descriptors" else " or both stacks [nc, nz, ny, nx]", *dims))
+    channels = features == "descriptors" or dims == (4, 4)
+    if channels and metric != "msd":
+        raise ValueError("refine_ffd: channels (features='descriptors' or 4-D volumes) are driven by the MSD alone, "
+                         "not metric=%r" % (metric,))
+    if dims == (4, 4) and tuple(fixed.shape)[0] != tuple(moving.shape)[0]:
+        raise ValueError("refine_ffd: fixed and moving must have the same number of channels, not %d and %d"
+                         % (tuple(fixed.shape)[0], tuple(moving.shape)[0]))
     jacobian = float(jacobian)
     if not (np.isfinite(jacobian) and jacobian >= 0):
         raise ValueError("refine_ffd: jacobian must be finite and not negative")
@@ -1293,14 +1332,31 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         if jacobian > 0 and jacobian_reference(A0) == 0.0:
             raise ValueError("refine_ffd: jacobian > 0 needs an A whose linear part has a determinant that is not 0")
     p = hip.ffd_refine_params(spacing=d, levels=int(levels), bending=float(bending), **params)
-    WF = _mask_host(mask_fixed, fixed, "refine_ffd", "mask_fixed")
-    WM = _mask_host(mask_moving, moving, "refine_ffd", "mask_moving")
-    F = _similarity_volume(fixed, "refine_ffd", "fixed")
-    M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
+    WF = _mask_host(mask_fixed, fixed[0] if dims[0] == 4 else fixed, "refine_ffd", "mask_fixed")
+    WM = _mask_host(mask_moving, moving[0] if dims[1] == 4 else moving, "refine_ffd", "mask_moving")
+    if dims == (4, 4):
+        F = _stack_tensor(fixed, "refine_ffd", "fixed")
+        M = _stack_tensor(moving, "refine_ffd", "moving", F.device)
+    else:
+        F = _similarity_volume(fixed, "refine_ffd", "fixed")
+        M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
     WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
     penalty = None
-    if jacobian > 0:
+    if channels:
+        # every level's volumes (and float masks) by restriction; descriptors of each level's own volumes
+        fv, mv, wf, wm = [F], [M], [WF], [WM]
+        for _ in range(1, int(levels)):
+            fv.append(hip.restrict2(fv[-1]))
+            mv.append(hip.restrict2(mv[-1]))
+            wf.append(None if wf[-1] is None else hip.restrict2(wf[-1]))
+            wm.append(None if wm[-1] is None else hip.restrict2(wm[-1]))
+        if features == "descriptors":
+            fv = [dense_descriptors(v, sigma) for v in fv]
+            mv = [dense_descriptors(v, sigma) for v in mv]
+        res, lattice, field, penalty = hip.ffd_refine_channels(fv, mv, A0, p, masks_fixed=wf, masks_moving=wm,
+                                                               jacobian=jacobian if jacobian > 0 else None)
+    elif jacobian > 0:
         mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
             if metric == "mi" else {}
         res, lattice, field, sim, penalty = hip.ffd_refine_jacobian(F, M, jacobian, A=A0, params=p, mask_fixed=WF,
@@ -1327,7 +1383,8 @@ def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
     refine_ffd's further keyword arguments (dict(metric="mi") for a mutual-information FFD stage, which then returns
-    a MiFFDRefinement); refine: True, or register's dict of refine_affine's keyword arguments (dict(metric="ncc") or
+    a MiFFDRefinement; dict(features="descriptors") for an FFD stage driven by the dense descriptors' 12 channels,
+    which needs no common intensity scale); refine: True, or register's dict of refine_affine's keyword arguments (dict(metric="ncc") or
     dict(metric="mi") for the affine stage).  The two stages' metrics are chosen separately; either defaults to the
     MSD.  The volumes are torch CUDA float32 tensors, or Images / arrays, which are uploaded.  Returns
     FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""

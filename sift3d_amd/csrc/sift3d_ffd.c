@@ -9,7 +9,12 @@
  * input is refused on a machine without a GPU too.
  *
  * The Jacobian penalty (header, "Jacobian penalty"; kernels in sift3d_jacobian_penalty.hip) has its checked entry here
- * and is the optional third term of the driver's cost. */
+ * and is the optional third term of the driver's cost.
+ *
+ * "Multi-channel free-form deformation": the same entry body and the same driver loop over stacks of nc channels, the
+ * driver's levels supplied by the caller instead of restricted here. */
+#include <stddef.h>
+
 #include "sift3d_ffd_jac.h"
 
 int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
@@ -25,6 +30,11 @@ int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient, const floa
                              double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
                              double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
                              const float *d_WM, const sift3d_ffd_jac *jac);
+int sift3d_ffd_evaluate_channels_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
+                                        int nx, int ny, int nz, int nc, const float *d_field, const float *d_lat, int gx,
+                                        int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
+                                        double bending, double *d_rec, float *d_grad, double *d_work, void *stream,
+                                        const float *d_WF, const float *d_WM, const sift3d_ffd_jac *jac);
 int sift3d_ffd_jacobian_gradient_launch(const char *fn, const float *d_field, int ox, int oy, int oz, int gx, int gy,
                                         int gz, int dx, int dy, int dz, const float *d_w, double ref, double *d_rec,
                                         double *d_GJ, double *d_work, void *stream);
@@ -177,13 +187,16 @@ typedef struct {
     const double *d_W;
 } ffd_mi_args;
 
-/* the shared body of the three entries: d_WF, d_WM are the masks ("Masks") or NULL; mi: the MI evaluation's further
- * arguments, checked after the FFD entries' own, or NULL (the MSD) */
+/* the shared body of the four entries: d_WF, d_WM are the masks ("Masks") or NULL; mi: the MI evaluation's further
+ * arguments, checked after the FFD entries' own, or NULL (the MSD); nc: 0 (one volume each, the single-channel kernels)
+ * or the channels of the stacks d_F and d_M (the channels entry, which has checked nc >= 1) */
 static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                               int ny, int nz, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
                               const double *A, double bending, float *d_field, void *d_record, float *d_grad,
-                              void *d_work, void *stream, const float *d_WF, const float *d_WM, const ffd_mi_args *mi)
+                              void *d_work, void *stream, const float *d_WF, const float *d_WM, const ffd_mi_args *mi,
+                              int nc)
 {
+    const int ch = nc ? nc : 1;
     int delta[3];
     double st[27];
     float s_f = 0.0f;
@@ -203,7 +216,7 @@ static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy
                check_aligned(what, ADDR(mi->d_W), 0)))
         return SIFT3D_FAILURE;
     {
-        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, ch) }, { d_M, image_bytes(nx, ny, nz, ch) },
                                { d_lattice, image_bytes(gx, gy, gz, 3) },
                                { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 },
@@ -227,6 +240,12 @@ static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy
                                     mi->d_W, (double *)d_record, d_grad,
                                     (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
                                     d_WM);
+    if (nc)
+        return sift3d_ffd_evaluate_channels_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, nc, d_field, d_lattice, gx,
+                                                   gy, gz, dx, dy, dz, (const float *)d_work, st, bending,
+                                                   (double *)d_record, d_grad,
+                                                   (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))),
+                                                   stream, d_WF, d_WM, NULL);
     return sift3d_ffd_evaluate_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
                                       dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
                                       (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
@@ -238,7 +257,7 @@ int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const floa
                             double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
 {
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL, NULL);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL, NULL, 0);
 }
 
 int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -248,7 +267,25 @@ int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, con
 {
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy,
                               gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM,
-                              NULL);
+                              NULL, 0);
+}
+
+/* one force volume whatever nc is: the single-channel evaluation's work */
+size_t sift3d_amd_ffd_evaluate_channels_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz)
+{
+    return sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz);
+}
+
+int sift3d_hip_ffd_evaluate_channels(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                     int nc, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                     const double *A, double bending, float *d_field, void *d_record, float *d_grad,
+                                     void *d_work, void *stream, const float *d_WF, const float *d_WM)
+{
+    static const char what[] = "sift3d_hip_ffd_evaluate_channels";
+    if (check_channels(what, nc))
+        return SIFT3D_FAILURE;
+    return ffd_evaluate_entry(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx, dy, dz, A, bending,
+                              d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, NULL, nc);
 }
 
 int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -259,7 +296,7 @@ int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const f
 {
     const ffd_mi_args mi = { bins, lo_f, hi_f, lo_m, hi_m, d_W };
     return ffd_evaluate_entry("sift3d_hip_ffd_mi_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, &mi);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, &mi, 0);
 }
 
 size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz)
@@ -447,6 +484,18 @@ size_t sift3d_amd_ffd_refine_struct_bytes(int which)
                         : 0;
 }
 
+size_t sift3d_amd_ffd_level_struct_bytes(int which)
+{
+    return which == 0   ? sizeof(sift3d_amd_ffd_level)
+           : which == 1 ? offsetof(sift3d_amd_ffd_level, d_F)
+           : which == 2 ? offsetof(sift3d_amd_ffd_level, ox)
+           : which == 3 ? offsetof(sift3d_amd_ffd_level, d_M)
+           : which == 4 ? offsetof(sift3d_amd_ffd_level, nx)
+           : which == 5 ? offsetof(sift3d_amd_ffd_level, d_WF)
+           : which == 6 ? offsetof(sift3d_amd_ffd_level, d_WM)
+                        : 0;
+}
+
 /* d_work of the driver, each part padded to 16 bytes: the evaluation's work on the level-0 grid (which covers every
  * coarser one), the record, five float lattices of level 0's size (c, c', their two gradients, the coarser level's
  * lattice), then per level l = 1 .. levels-1 the restricted fixed and moving volumes */
@@ -535,6 +584,7 @@ typedef struct {
     mi_state *ms;                                /* MI (sift3d_affine_refine.c): bins, ranges, histogram, W; or NULL */
     float s_f;                                   /* MI: the fixed bin's scale */
     const sift3d_ffd_jac *jac;                   /* the Jacobian penalty's weight and buffers; or NULL */
+    int nc;                                      /* the channels of the levels' stacks; 0: single volumes */
 } ffd_ctx;
 
 /* with a penalty: its record to the host, ahead of the wait that the caller makes */
@@ -583,9 +633,14 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
         ffd_jac_mean(x, lv, e);
         return SIFT3D_SUCCESS;
     }
-    if (sift3d_ffd_evaluate_jac_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field,
-                                       c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
-                                       x->d_rec, grad, x->d_eval, x->stream, lv->WF, lv->WM, x->jac) ||
+    if ((x->nc ? sift3d_ffd_evaluate_channels_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
+                                                     x->nc, x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1],
+                                                     x->d[2], x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval,
+                                                     x->stream, lv->WF, lv->WM, x->jac)
+               : sift3d_ffd_evaluate_jac_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
+                                                x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2],
+                                                x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval, x->stream,
+                                                lv->WF, lv->WM, x->jac)) ||
         sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
         sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
@@ -641,17 +696,28 @@ static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_eval *v, doub
     e->level = level;
 }
 
-/* the shared body of the three drivers: `masked` selects the work buffer's size; the masks may still be NULL.  ms (MI;
+/* the channels driver's work without the penalty's: the evaluation's, the record and the five lattices */
+static size_t ffd_channels_base_bytes(int ox, int oy, int oz, const int *d)
+{
+    return pad16(sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, d[0], d[1], d[2])) + ffd_record_pad(ox, oy, oz, d) +
+           5 * ffd_lattice_bytes(ox, oy, oz, d);
+}
+
+/* the shared body of the drivers: `masked` selects the work buffer's size; the masks may still be NULL.  ms (MI;
  * else NULL): bins and ranges, checked here after the FFD drivers' own checks; the cost's image term is -mi, the
  * gradient is made only at the lattice a step starts from, and ms->sim leaves with the measures at the final lattice on
  * level 0.  penalty (the Jacobian driver; else NULL): the array parallel to the trail; `jacobian` is the weight and
- * `ref` the reference determinant, both checked by the caller, and the work buffer is that driver's. */
+ * `ref` the reference determinant, both checked by the caller, and the work buffer is that driver's.
+ * src (the channels driver; else NULL): the caller's levels, checked by the caller, of nc channels each.  d_F .. d_WM
+ * are then level 0's; the other levels are taken from src where the other drivers restrict the level above, and the
+ * work buffer is sift3d_amd_ffd_refine_channels_work_bytes(). */
 static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                       int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
                       sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
                       void *stream, int masked, const float *d_WF, const float *d_WM, mi_state *ms, double jacobian,
-                      double ref, sift3d_amd_ffd_penalty *penalty)
+                      double ref, sift3d_amd_ffd_penalty *penalty, const sift3d_amd_ffd_level *src, int nc)
 {
+    const int ch = src ? nc : 1;
     sift3d_ffd_jac jac;
     sift3d_amd_ffd_refine_params prm;
     ffd_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
@@ -682,17 +748,19 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                          sift3d_amd_ffd_lattice_dim(oy, prm.spacing[1]), sift3d_amd_ffd_lattice_dim(oz, prm.spacing[2]),
                          d_WF, d_WM };
     {
-        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, ch) }, { d_M, image_bytes(nx, ny, nz, ch) },
                                { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_lattice, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3) },
                                 { d_field, field_bytes(ox, oy, oz) },
-                                { d_work, (penalty  ? sift3d_amd_ffd_refine_jacobian_work_bytes
-                                           : ms     ? sift3d_amd_ffd_mi_refine_work_bytes
-                                           : masked ? sift3d_amd_ffd_refine_masked_work_bytes
-                                                    : sift3d_amd_ffd_refine_work_bytes)(ox, oy, oz, nx, ny, nz,
-                                                                                        prm.spacing[0], prm.spacing[1],
-                                                                                        prm.spacing[2], prm.levels) } };
+                                { d_work, src ? sift3d_amd_ffd_refine_channels_work_bytes(ox, oy, oz, prm.spacing[0],
+                                                                                          prm.spacing[1], prm.spacing[2])
+                                              : (penalty  ? sift3d_amd_ffd_refine_jacobian_work_bytes
+                                                 : ms     ? sift3d_amd_ffd_mi_refine_work_bytes
+                                                 : masked ? sift3d_amd_ffd_refine_masked_work_bytes
+                                                          : sift3d_amd_ffd_refine_work_bytes)(
+                                                    ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
+                                                    prm.spacing[2], prm.levels) } };
         if (ranges_aliased(out, 3, in, 4))
             return refuse(what, ALIASED);
         work_bytes = out[2].bytes;
@@ -724,9 +792,12 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     x.ms = ms;
     x.s_f = s_f;
     x.jac = NULL;
-    if (penalty) {                                           /* behind everything the MI driver lays out */
-        work_bytes = sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
-                                                         prm.spacing[2], prm.levels);
+    x.nc = src ? nc : 0;
+    if (penalty) {                                           /* behind everything the MI driver lays out (channels:
+                                                                behind the lattices) */
+        work_bytes = src ? ffd_channels_base_bytes(ox, oy, oz, prm.spacing)
+                         : sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
+                                                               prm.spacing[2], prm.levels);
         jac.weight = jacobian;
         jac.ref = ref;
         jac.d_rec = (double *)(w + work_bytes);
@@ -749,16 +820,24 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
         k->gx = sift3d_amd_ffd_lattice_dim(k->ox, prm.spacing[0]);
         k->gy = sift3d_amd_ffd_lattice_dim(k->oy, prm.spacing[1]);
         k->gz = sift3d_amd_ffd_lattice_dim(k->oz, prm.spacing[2]);
-        off += pad4(grid_voxels(k->ox, k->oy, k->oz)) * sizeof(float);
-        cM = (float *)(w + off);
-        off += pad4(grid_voxels(k->nx, k->ny, k->nz)) * sizeof(float);
-        if (sift3d_hip_restrict2(f->F, f->ox, f->oy, f->oz, 1, cF, 1.0f, stream) ||
-            sift3d_hip_restrict2(f->M, f->nx, f->ny, f->nz, 1, cM, 1.0f, stream))
-            return SIFT3D_FAILURE;
-        k->F = cF;
-        k->M = cM;
-        if (mask_pyramid_level(f->WF, f->ox, f->oy, f->oz, f->WM, f->nx, f->ny, f->nz, w, &off, &k->WF, &k->WM, stream))
-            return SIFT3D_FAILURE;
+        if (src) {                                           /* the caller's level: the halving chain, checked */
+            k->F = src[l].d_F;
+            k->M = src[l].d_M;
+            k->WF = src[l].d_WF;
+            k->WM = src[l].d_WM;
+        } else {
+            off += pad4(grid_voxels(k->ox, k->oy, k->oz)) * sizeof(float);
+            cM = (float *)(w + off);
+            off += pad4(grid_voxels(k->nx, k->ny, k->nz)) * sizeof(float);
+            if (sift3d_hip_restrict2(f->F, f->ox, f->oy, f->oz, 1, cF, 1.0f, stream) ||
+                sift3d_hip_restrict2(f->M, f->nx, f->ny, f->nz, 1, cM, 1.0f, stream))
+                return SIFT3D_FAILURE;
+            k->F = cF;
+            k->M = cM;
+            if (mask_pyramid_level(f->WF, f->ox, f->oy, f->oz, f->WM, f->nx, f->ny, f->nz, w, &off, &k->WF, &k->WM,
+                                   stream))
+                return SIFT3D_FAILURE;
+        }
         for (i = 3; i < 12; i += 4)
             A[i] = A[i] * 0.5;
     }
@@ -855,7 +934,7 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
                                  void *stream)
 {
     return ffd_refine("sift3d_amd_ffd_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL, 0.0, 1.0, NULL);
+                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL, 0.0, 1.0, NULL, NULL, 0);
 }
 
 int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -864,7 +943,7 @@ int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz
                                         void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     return ffd_refine("sift3d_amd_ffd_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL, 0.0, 1.0, NULL);
+                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL, 0.0, 1.0, NULL, NULL, 0);
 }
 
 int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -886,7 +965,7 @@ int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, co
     ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
     *mi_out = ms.sim;
     rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, &ms, 0.0, 1.0, NULL);
+                    d_WF, d_WM, &ms, 0.0, 1.0, NULL, NULL, 0);
     *mi_out = ms.sim;
     return rc;
 }
@@ -905,6 +984,21 @@ size_t sift3d_amd_ffd_refine_jacobian_work_bytes(int ox, int oy, int oz, int nx,
            sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz);
 }
 
+/* the penalty's reference determinant: det of A's linear part, 1.0 without A; refused when not finite or 0 */
+static int ffd_jacobian_ref(const char *what, const double *A, double *ref)
+{
+    *ref = 1.0;
+    if (!A)
+        return SIFT3D_SUCCESS;
+    if (check_affine(what, A))
+        return SIFT3D_FAILURE;
+    *ref = A[0] * (A[5] * A[10] - A[6] * A[9]) - A[1] * (A[4] * A[10] - A[6] * A[8]) +
+           A[2] * (A[4] * A[9] - A[5] * A[8]);
+    if (!isfinite(*ref) || *ref == 0.0)
+        return refuse(what, "the linear part of A must have a finite determinant that is not 0");
+    return SIFT3D_SUCCESS;
+}
+
 int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                                           int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
                                           sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
@@ -920,15 +1014,8 @@ int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int 
         return refuse(what, "NULL argument");
     if (!isfinite(jacobian) || jacobian < 0)
         return refuse(what, "the Jacobian weight must be finite and not negative");
-    if (A_in) {
-        const double *A = A_in;
-        if (check_affine(what, A))
-            return SIFT3D_FAILURE;
-        ref = A[0] * (A[5] * A[10] - A[6] * A[9]) - A[1] * (A[4] * A[10] - A[6] * A[8]) +
-              A[2] * (A[4] * A[9] - A[5] * A[8]);
-        if (!isfinite(ref) || ref == 0.0)
-            return refuse(what, "the linear part of A must have a finite determinant that is not 0");
-    }
+    if (ffd_jacobian_ref(what, A_in, &ref))
+        return SIFT3D_FAILURE;
     ms.bins = bins;
     ms.lo_f = lo_f; ms.hi_f = hi_f;
     ms.lo_m = lo_m; ms.hi_m = hi_m;
@@ -938,8 +1025,87 @@ int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int 
     if (mi_out)
         *mi_out = ms.sim;
     rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty);
+                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty, NULL, 0);
     if (mi_out)
         *mi_out = ms.sim;
     return rc;
+}
+
+/* ---- the channels driver ("Multi-channel free-form deformation") ---- */
+
+/* the evaluation's work, the record and the five lattices on the finest grid, then the penalty's record, GJ and work
+ * (whether or not a penalty is asked for); no volume is held: the caller supplies every level */
+size_t sift3d_amd_ffd_refine_channels_work_bytes(int ox, int oy, int oz, int dx, int dy, int dz)
+{
+    const int d[3] = { dx, dy, dz };
+    if (ox <= 0 || oy <= 0 || oz <= 0 || !ffd_spacing_ok(dx, dy, dz))
+        return 0;
+    return ffd_channels_base_bytes(ox, oy, oz, d) + SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES +
+           3 * grid_voxels(sift3d_amd_ffd_lattice_dim(ox, dx), sift3d_amd_ffd_lattice_dim(oy, dy),
+                           sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double) +
+           sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz);
+}
+
+int sift3d_amd_ffd_refine_channels_device(const sift3d_amd_ffd_level *level, int levels, int nc, const double *A_in,
+                                          const sift3d_amd_ffd_refine_params *params,
+                                          sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                          void *d_work, void *stream, double jacobian,
+                                          sift3d_amd_ffd_penalty *penalty)
+{
+    static const char what[] = "sift3d_amd_ffd_refine_channels_device";
+    sift3d_amd_ffd_refine_params prm;
+    double ref = 1.0;
+    size_t work_bytes;
+    int l;
+    if (!level || !result || !d_lattice || !d_field || !d_work)
+        return refuse(what, "NULL argument");
+    if (levels < 1 || levels > SIFT3D_AMD_DEMONS_MAX_LEVELS)
+        return refuse(what, "levels must be in [1, SIFT3D_AMD_DEMONS_MAX_LEVELS]");
+    if (check_channels(what, nc))
+        return SIFT3D_FAILURE;
+    if (params)
+        prm = *params;
+    else
+        sift3d_amd_ffd_refine_default_params(&prm);
+    if (prm.levels != levels)
+        return refuse(what, "params->levels must equal levels");
+    if (!ffd_params_ok(&prm))
+        return refuse(what, "a parameter is out of range");
+    if (!isfinite(jacobian) || jacobian < 0)
+        return refuse(what, "the Jacobian weight must be finite and not negative");
+    if (jacobian != 0 && !penalty)
+        return refuse(what, "a Jacobian weight needs the penalty array");
+    if (penalty && ffd_jacobian_ref(what, A_in, &ref))
+        return SIFT3D_FAILURE;
+    work_bytes = sift3d_amd_ffd_refine_channels_work_bytes(level->ox, level->oy, level->oz, prm.spacing[0],
+                                                           prm.spacing[1], prm.spacing[2]);
+    for (l = 0; l < levels; l++) {
+        const sift3d_amd_ffd_level *v = level + l;
+        if (!v->d_F || !v->d_M)
+            return refuse(what, "NULL level pointer");
+        if (check_dims(what, v->ox, v->oy, v->oz) || check_dims(what, v->nx, v->ny, v->nz))
+            return SIFT3D_FAILURE;
+        if (l && (v->ox != multires_half(v[-1].ox) || v->oy != multires_half(v[-1].oy) ||
+                  v->oz != multires_half(v[-1].oz) || v->nx != multires_half(v[-1].nx) ||
+                  v->ny != multires_half(v[-1].ny) || v->nz != multires_half(v[-1].nz)))
+            return refuse(what, "a level is not the half of the level above");
+        if (check_aligned(what, 0, ADDR(v->d_F) | ADDR(v->d_M) | ADDR(v->d_WF) | ADDR(v->d_WM)))
+            return SIFT3D_FAILURE;
+        if (l) {                                             /* level 0 is checked with the outputs by the body */
+            const range_t in[] = { { v->d_F, image_bytes(v->ox, v->oy, v->oz, nc) },
+                                   { v->d_M, image_bytes(v->nx, v->ny, v->nz, nc) },
+                                   { v->d_WF, v->d_WF ? image_bytes(v->ox, v->oy, v->oz, 1) : 0 },
+                                   { v->d_WM, v->d_WM ? image_bytes(v->nx, v->ny, v->nz, 1) : 0 } };
+            const range_t out[] = { { d_lattice, image_bytes(sift3d_amd_ffd_lattice_dim(level->ox, prm.spacing[0]),
+                                                             sift3d_amd_ffd_lattice_dim(level->oy, prm.spacing[1]),
+                                                             sift3d_amd_ffd_lattice_dim(level->oz, prm.spacing[2]), 3) },
+                                    { d_field, field_bytes(level->ox, level->oy, level->oz) },
+                                    { d_work, work_bytes } };
+            if (ranges_aliased(out, 3, in, 4))
+                return refuse(what, ALIASED);
+        }
+    }
+    return ffd_refine(what, level->d_F, level->ox, level->oy, level->oz, level->d_M, level->nx, level->ny, level->nz,
+                      A_in, &prm, result, d_lattice, d_field, d_work, stream, 1, level->d_WF, level->d_WM, NULL,
+                      jacobian, ref, penalty, level, nc);
 }

@@ -192,6 +192,130 @@ __global__ __launch_bounds__(256) void k_ffd_force(const FfdForceArgs s)
     }
 }
 
+// ---- the force of a channel stack (header, "Multi-channel free-form deformation") ---------------------------------
+#ifndef FFD_CHANNELS_UNROLL
+#define FFD_CHANNELS_UNROLL 2                    // channels per iteration of the sweep (FFDDEF=-DFFD_CHANNELS_UNROLL=n)
+#endif
+
+struct FfdChannelsArgs {
+    FfdForceArgs f;                              // F [nc][oz][oy][ox], g.src = M [nc][nz][ny][nx]; one field, one mask pair
+    int nc;
+};
+
+// One channel of a lane's four outputs: e = m - f (float), E = e widened, S_d = E g_d (FIRST: channel 0) or
+// S_d + E g_d, and S_ee += E E in the order k = 0 .. 3.  An output that is not counted has E = 0; what it leaves in S
+// is replaced by +0 at the store.  The F reads of outputs past the grid go to the channel's voxel 0: no branch.
+template <int LINEAR, bool FIRST>
+__device__ __forceinline__ void ffd_channel_terms(const float *Fc, const float *Mc, const Taps (&tp)[4],
+                                                  const size_t (&foff)[4], const bool (&counted)[4], double (&S)[4][3],
+                                                  double &see)
+{
+    float f[4], m[4], gx[4], gy[4], gz[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        f[k] = Fc[foff[k]];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        m[k] = gather_grad<LINEAR>(Mc, tp[k], &gx[k], &gy[k], &gz[k]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float e = m[k] - f[k];
+        const double E = counted[k] ? (double)e : 0.0;
+        see += E * E;
+        const double px = E * (double)gx[k], py = E * (double)gy[k], pz = E * (double)gz[k];   // exact: two floats
+        S[k][0] = FIRST ? px : S[k][0] + px;
+        S[k][1] = FIRST ? py : S[k][1] + py;
+        S[k][2] = FIRST ? pz : S[k][2] + pz;
+    }
+}
+
+// k_ffd_force over nc channels in one pass: the tile geometry, the partial slots and the front-end (field before F,
+// masks, taps) are k_ffd_force's and run once per voxel; then the channels are swept with F advancing by ovox and M by
+// mvox (64-bit), the twelve double accumulators of the lane's four outputs staying in registers, and the force is
+// stored once after the last channel.  Channel 0 is peeled so that S starts from its product, not from +0 (with nc == 1
+// the stores are k_ffd_force's, signed zeros included); the other channels run two to an iteration, so that the eight
+// 8-byte gathers of two channels' outputs are in flight together.  S_ee adds E_c E_c in the order (c, k), which with
+// nc == 1 is k_ffd_force's order.
+// As reported by -Rpass-analysis=kernel-resource-usage: 234 - 236 VGPRs and two waves per SIMD with nx >= 2 (two
+// channels' gathers of four outputs beside the twelve accumulators and the taps), 256 VGPRs + 48 - 50 AGPRs and one wave
+// with nx == 1; no scratch.
+// Measured (profiles/microbench/ffd_channels_rate_mi355x.txt, kernel trace, min of 5, spread of a kernel under 2 %): at
+// 512^3 1.44 / 2.37 / 6.21 ms at nc = 1 / 3 / 12 against 1.35 / 4.08 / 16.23 ms for nc launches of k_ffd_force in the same
+// run, 1.07 / 0.58 / 0.38 x (256^3: 1.17 / 0.62 / 0.39 x), and 1.95 / 2.35 / 2.80 x the (36 + 8 nc) B per voxel of the
+// bytes model at 8 TB/s.  A further channel costs 0.43 ms, 8 B per voxel at 2.5 TB/s: the sweep is bound by the latency
+// of its gathers at two waves per SIMD, not by HBM.  One channel per iteration (FFD_CHANNELS_UNROLL=1: 158 - 160 VGPRs,
+// three waves) took 1.31 / 2.29 / 6.98 ms in a run where this build took 1.44 / 2.34 / 6.19 and 1.48 / 2.44 / 6.29; three
+// per iteration (256 VGPRs + 14 AGPRs, one wave) 2.69 / 3.98 / 8.97 ms.  Two is kept for the twelve channels of the
+// descriptors; with one channel k_ffd_force itself is 7 - 17 % faster than this kernel.
+template <int LINEAR, bool MASKED>
+__global__ __launch_bounds__(256) void k_ffd_force_channels(const FfdChannelsArgs sc)
+{
+    __shared__ double s_see[4];
+    __shared__ unsigned long long s_cnt[4];
+    const FfdForceArgs &s = sc.f;
+    const GridArgs &p = s.g;
+    const int lx = threadIdx.x & 15;
+    const size_t ovox = (size_t)p.ox * (size_t)p.oy * (size_t)p.oz;
+    const size_t mvox = (size_t)p.nx * (size_t)p.ny * (size_t)p.nz;
+    unsigned long long cnt = 0;
+    double see = 0.0;
+    for (unsigned base = 0; base < p.ntiles; base += gridDim.x) {
+        int xt, y, z;
+        if (!tile_at(p, base, xt, y, z))
+            break;
+        const bool row = y < p.oy && z < p.oz;
+        const size_t orow = ((size_t)z * (size_t)p.oy + (size_t)y) * (size_t)p.ox;
+        Taps tp[4];
+        size_t foff[4];
+        bool live[4], counted[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = xt + lx + 16 * k;
+            live[k] = row && x < p.ox;
+            foff[k] = live[k] ? orow + (size_t)x : 0;
+            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+            float wf = 1.0f, wm = 1.0f;                                      // MASKED only
+            if (live[k]) {
+                const float *u = s.field + orow + (size_t)x;
+                ux = u[0];
+                uy = u[ovox];
+                uz = u[2 * ovox];
+                if (MASKED && s.w.wf)
+                    wf = s.w.wf[orow + (size_t)x];
+            }
+            const double qx = (double)x + (double)ux, qy = (double)y + (double)uy, qz = (double)z + (double)uz;
+            tp[k] = taps_at<LINEAR>(p.nx, p.ny, p.nz, qx, qy, qz);
+            if (MASKED && s.w.wm)
+                wm = s.w.wm[mask_offset(p.nx, p.ny, p.nz, qx, qy, qz)];
+            counted[k] = MASKED ? live[k] && tp[k].in && mask_in(wf) && mask_in(wm) : live[k] && tp[k].in;
+            cnt += counted[k] ? 1u : 0u;
+        }
+        double S[4][3];
+        const float *Fc = s.F, *Mc = p.src;
+        ffd_channel_terms<LINEAR, true>(Fc, Mc, tp, foff, counted, S, see);
+#pragma unroll FFD_CHANNELS_UNROLL
+        for (int c = 1; c < sc.nc; c++) {
+            Fc += ovox;
+            Mc += mvox;
+            ffd_channel_terms<LINEAR, false>(Fc, Mc, tp, foff, counted, S, see);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (live[k]) {
+                double *o = s.force + orow + (size_t)(xt + lx + 16 * k);
+                o[0] = counted[k] ? S[k][0] : 0.0;
+                o[ovox] = counted[k] ? S[k][1] : 0.0;
+                o[2 * ovox] = counted[k] ? S[k][2] : 0.0;
+            }
+    }
+    const double vs = workgroup_reduce<Add>(see, s_see);
+    const unsigned long long vc = workgroup_reduce<Add>(cnt, s_cnt);
+    if (threadIdx.x == 0) {
+        s.part[blockIdx.x] = vs;
+        reinterpret_cast<unsigned long long *>(s.part)[FFD_GRID + blockIdx.x] = vc;
+    }
+}
+
 // ---- the force of the mutual information (header, "Mutual-information free-form deformation (Mattes)") ------------
 struct FfdMiForceArgs {
     FfdForceArgs f;                              // part: S_pp, then the count
@@ -563,8 +687,9 @@ static int ffd_adjoint_passes(const double *src, double *t1, double *t2, double 
 // d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.  FFD_BEND_GRAD reads the D that the
 // last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.  mi: what the MI
 // force needs beside the MSD force's arguments (NULL: the MSD).  jac: the penalty's buffers (NULL: none); the combine
-// takes its term when jac->weight > 0.
-static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const sift3d_ffd_jac *jac,
+// takes its term when jac->weight > 0.  nc: 0 from the single-channel entries, which launch k_ffd_force or
+// k_ffd_mi_force as before; >= 1: d_F and d_M are stacks of nc channels and k_ffd_force_channels runs (mi == NULL).
+static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const sift3d_ffd_jac *jac, int nc,
                               const float *d_F, int ox, int oy,
                               int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
                               const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
@@ -593,6 +718,11 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
             fm.z = *mi;
             hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_mi_force, nx, masked), dim3(grid), dim3(256),
                                (size_t)mi->bins * mi->bins * sizeof(double), st, fm);
+        } else if (nc >= 1) {
+            FfdChannelsArgs fc;
+            fc.f = f;
+            fc.nc = nc;
+            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force_channels, nx, masked), dim3(grid), dim3(256), 0, st, fc);
         } else {
             hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force, nx, masked), dim3(grid), dim3(256), 0, st, f);
         }
@@ -664,8 +794,23 @@ extern "C" int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, 
                                               const float *d_WM, const sift3d_ffd_jac *jac)
 {
     return ffd_evaluate_parts(fn, d_F ? FFD_ALL | ffd_jac_parts(jac, true) : FFD_BEND_VALUE | FFD_BEND_GRAD, nullptr,
-                              jac, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w,
+                              jac, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w,
                               stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+}
+
+// The evaluation of a stack of nc >= 1 channels (header, "Multi-channel free-form deformation"): the MSD evaluation
+// with k_ffd_force_channels in the place of k_ffd_force, every other pass unchanged.
+extern "C" int sift3d_ffd_evaluate_channels_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
+                                                   const float *d_M, int nx, int ny, int nz, int nc,
+                                                   const float *d_field, const float *d_lat, int gx, int gy, int gz,
+                                                   int dx, int dy, int dz, const float *d_w, const double *stencils,
+                                                   double bending, double *d_rec, float *d_grad, double *d_work,
+                                                   void *stream, const float *d_WF, const float *d_WM,
+                                                   const sift3d_ffd_jac *jac)
+{
+    return ffd_evaluate_parts(fn, FFD_ALL | ffd_jac_parts(jac, true), nullptr, jac, nc, d_F, ox, oy, oz, d_M, nx, ny, nz,
+                              d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work,
+                              stream, d_WF, d_WM);
 }
 
 extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
@@ -693,7 +838,7 @@ extern "C" int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient,
     const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
     const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u) |
                            ffd_jac_parts(jac, gradient != 0);
-    return ffd_evaluate_parts(fn, parts, &mi, jac, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy,
+    return ffd_evaluate_parts(fn, parts, &mi, jac, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy,
                               dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
 }
 

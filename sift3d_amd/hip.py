@@ -101,6 +101,12 @@ class FFDPenalty(C.Structure):                             # sift3d_amd_ffd_pena
 
 JACOBIAN_PENALTY_RECORD_BYTES = 32
 
+
+class FFDLevel(C.Structure):                               # sift3d_amd_ffd_level
+    _fields_ = [("d_F", C.c_void_p), ("ox", C.c_int), ("oy", C.c_int), ("oz", C.c_int), ("d_M", C.c_void_p),
+                ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("d_WF", C.c_void_p), ("d_WM", C.c_void_p)]
+
+
 _bound = None
 
 
@@ -281,6 +287,16 @@ def lib():
                                                             C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                                             C.POINTER(Similarity), C.c_double,
                                                             C.POINTER(FFDPenalty)]),
+        "sift3d_amd_ffd_level_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_amd_ffd_evaluate_channels_work_bytes": (C.c_size_t, [C.c_int] * 6),
+        "sift3d_hip_ffd_evaluate_channels": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                       C.c_int, vp] + [C.c_int] * 6
+                                             + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+        "sift3d_amd_ffd_refine_channels_work_bytes": (C.c_size_t, [C.c_int] * 6),
+        "sift3d_amd_ffd_refine_channels_device": (C.c_int, [C.POINTER(FFDLevel), C.c_int, C.c_int,
+                                                            C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
+                                                            C.POINTER(FFDRefineResult), vp, vp, vp, vp, C.c_double,
+                                                            C.POINTER(FFDPenalty)]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -341,6 +357,10 @@ def lib():
     got = tuple(L.sift3d_amd_ffd_refine_struct_bytes(k) for k in range(7))
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the FFD layouts as %s, the library has %s" % (want, got))
+    want = (C.sizeof(FFDLevel),) + tuple(getattr(FFDLevel, f).offset for f in ("d_F", "ox", "d_M", "nx", "d_WF", "d_WM"))
+    got = tuple(L.sift3d_amd_ffd_level_struct_bytes(k) for k in range(7))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the FFD level as %s, the library has %s" % (want, got))
     _bound = L
     return L
 
@@ -1484,6 +1504,97 @@ def ffd_refine_jacobian(F, M, jacobian, bins=0, range_f=(0.0, 1.0), range_m=(0.0
            "sift3d_amd_ffd_refine_jacobian_device")
     penalty = [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
     return res, lattice, field, (sim if bins else None), penalty
+
+
+# ---- multi-channel free-form deformation ("Multi-channel free-form deformation") ----
+def _ffd_stacks(F, M, what, level=""):
+    """(nc, fixed grid, moving grid) of a pair of contiguous float32 CUDA stacks [nc, z, y, x] with one nc"""
+    for t in (F, M):
+        _tensor(t, "%s: %sF and M must be contiguous float32 CUDA tensors [nc, nz, ny, nx]" % (what, level), dims=(4,))
+    _same_device(what, F, M)
+    if F.shape[0] != M.shape[0] or F.shape[0] < 1:
+        raise ValueError("%s: %sF and M must have the same number of channels, at least one" % (what, level))
+    return int(F.shape[0]), tuple(F.shape[1:]), tuple(M.shape[1:])
+
+
+def _ffd_stack_masks(what, F, M, mask_fixed, mask_moving):
+    """(d_WF, d_WM) pointers or None of masks on the grids of the stacks F and M"""
+    for w, t, name in ((mask_fixed, F, "mask_fixed"), (mask_moving, M, "mask_moving")):
+        if w is not None:
+            _tensor(w, "%s: %s must be a contiguous float32 CUDA tensor of its stack's grid %s"
+                    % (what, name, tuple(t.shape[1:])), shape=tuple(t.shape[1:]), device=t.device)
+    return tuple(None if w is None else w.data_ptr() for w in (mask_fixed, mask_moving))
+
+
+def ffd_evaluate_channels(F, M, lattice, spacing, A=None, bending=0.0, work=None, mask_fixed=None, mask_moving=None):
+    """ffd_evaluate for stacks F [nc, oz, oy, ox] and M [nc, nz, ny, nx] (sift3d_hip_ffd_evaluate_channels) on torch's
+    current stream.  Returns (record, grad, field, work): the force S is left in `work` (the header gives its offset)."""
+    import torch
+    what = "ffd_evaluate_channels"
+    nc, (oz, oy, ox), (nz, ny, nx) = _ffd_stacks(F, M, what)
+    masks = _ffd_stack_masks(what, F, M, mask_fixed, mask_moving)
+    gx, gy, gz = _ffd_lattice(lattice, what)
+    _same_device(what, F, lattice)
+    dx, dy, dz = ffd_spacing(spacing, what)
+    a, ap = _ffd_A(A, what)
+    record = _ffd_record_tensor(lattice)
+    grad = torch.empty_like(lattice)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    need = lib().sift3d_amd_ffd_evaluate_channels_work_bytes(ox, oy, oz, dx, dy, dz)
+    work = _work(work, (need + 3) // 4, F, what)
+    _check(lib().sift3d_hip_ffd_evaluate_channels(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, nc,
+                                                  lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap, float(bending),
+                                                  field.data_ptr(), record.data_ptr(), grad.data_ptr(),
+                                                  work.data_ptr(), current_stream(), *masks),
+           "sift3d_hip_ffd_evaluate_channels")
+    return record, grad, field, work
+
+
+def ffd_refine_channels(Fs, Ms, A=None, params=None, work=None, masks_fixed=None, masks_moving=None, jacobian=None):
+    """sift3d_amd_ffd_refine_channels_device on torch's current stream: Fs, Ms are the fixed and moving stacks per
+    level, level 0 the finest, every level the half ((n + 1) // 2 per axis) of the one above; masks_fixed, masks_moving:
+    one mask per level on that level's grid, or None.  jacobian: None runs without the penalty, a weight >= 0 with it.
+    Returns (FFDRefineResult, lattice, field, penalty: one (P, rmin, nonpos) per trail entry, or None)."""
+    import torch
+    what = "ffd_refine_channels"
+    levels = len(Fs)
+    if not (1 <= levels <= AFFINE_MAX_LEVELS) or len(Ms) != levels:
+        raise ValueError("%s: 1 .. %d levels of fixed and as many of moving stacks" % (what, AFFINE_MAX_LEVELS))
+    p = params if params is not None else ffd_refine_params(levels=levels)
+    if p.levels != levels:
+        raise ValueError("%s: params.levels must be the number of levels given" % what)
+    WFs = [None] * levels if masks_fixed is None else list(masks_fixed)
+    WMs = [None] * levels if masks_moving is None else list(masks_moving)
+    if len(WFs) != levels or len(WMs) != levels:
+        raise ValueError("%s: one mask (or None) per level" % what)
+    tab = (FFDLevel * levels)()
+    nc0 = None
+    for l, (F, M) in enumerate(zip(Fs, Ms)):
+        nc, fg, mg = _ffd_stacks(F, M, what, "level %d " % l)
+        if F.device != Fs[0].device or nc0 not in (None, nc):
+            raise ValueError("%s: level %d differs in channels or device" % (what, l))
+        nc0 = nc
+        if l and (fg != half_shape(Fs[l - 1].shape[1:]) or mg != half_shape(Ms[l - 1].shape[1:])):
+            raise ValueError("%s: level %d is not the half of level %d" % (what, l, l - 1))
+        wf, wm = _ffd_stack_masks(what, F, M, WFs[l], WMs[l])
+        tab[l] = FFDLevel(F.data_ptr(), fg[2], fg[1], fg[0], M.data_ptr(), mg[2], mg[1], mg[0], wf, wm)
+    a, ap = _ffd_A(A, what)
+    oz, oy, ox = Fs[0].shape[1:]
+    d = tuple(p.spacing)
+    need = lib().sift3d_amd_ffd_refine_channels_work_bytes(ox, oy, oz, d[0], d[1], d[2])
+    if need == 0:
+        raise ValueError(what + ": the spacing must be in [1, %d]" % FFD_MAX_SPACING)
+    work = _work(work, (need + 3) // 4, Fs[0], what)
+    lattice = torch.empty(ffd_lattice_shape((oz, oy, ox), d), dtype=torch.float32, device=Fs[0].device)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=Fs[0].device)
+    res = FFDRefineResult()
+    pen = None if jacobian is None else (FFDPenalty * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
+    _check(lib().sift3d_amd_ffd_refine_channels_device(tab, levels, nc0, ap, C.byref(p), C.byref(res),
+                                                       lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
+                                                       current_stream(), 0.0 if jacobian is None else float(jacobian),
+                                                       pen), "sift3d_amd_ffd_refine_channels_device")
+    penalty = None if pen is None else [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
+    return res, lattice, field, penalty
 
 
 def _dense_args(src, out, what):
