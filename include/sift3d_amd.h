@@ -1306,6 +1306,124 @@ sift3d_amd_ffd_refine_channels_device(const sift3d_amd_ffd_level *level, int lev
                                       sift3d_amd_ffd_penalty *penalty /*NULL when jacobian == 0*/);
 
 /* ------------------------------------------------------------------------ */
+/* FFD landmarks: the spline at points, and a matched-point term in the FFD drivers */
+/* ------------------------------------------------------------------------ */
+/* The cubic B-spline of "B-spline free-form deformation" evaluated at arbitrary points of the fixed grid instead of its
+ * voxels, the adjoint of that evaluation, and the corresponding-points term built from the two: "these two points
+ * correspond" next to the image term of the FFD drivers.  No upstream counterpart: PARITY UNPINNED, pinned to this
+ * contract and its numpy restatement (tests/ffd_landmarks_restatement.py).  All arithmetic is double, unfused, in the
+ * order written.
+ *
+ * Point weights.  Along an axis with spacing delta and lattice size g, for a coordinate x (double, voxels of the fixed
+ * grid): v = x / (double) delta, i0 = floor(v), t = v - (double) i0, and the four weights are the formulas of
+ * sift3d_amd_ffd_weights with this t, left in double (not rounded to float).  A point is INSIDE when every coordinate is
+ * finite and 0 <= i0 <= g - 4 on every axis: the lattice's own support 0 <= x < (g - 3) delta, which contains the grid.
+ * Spline at a point: s_d(p) = sum_c sum_b sum_a wz[c] * (wy[b] * (wx[a] * (double) c_d[k0 + c][j0 + b][i0 + a])), from
+ * +0, the 64 terms one by one in the voxel spline's order (c outermost, x innermost).
+ * Map: T_d(p) = q_d + s_d(p), q_d = A[d][0] x + ((A[d][1] y + A[d][2] z) + A[d][3]) with A, q_d = p_d with A NULL.
+ *
+ * sift3d_hip_ffd_points: T [m][3] double from P [m][3] double (device memory, xyz), m >= 1; a point that is not inside
+ * gets three NaNs.  Asynchronous on `stream`, allocates nothing.  -1 before any device call on a NULL d_lattice, d_P or
+ * d_T, a lattice dimension < 4, a spacing outside [1, SIFT3D_AMD_FFD_MAX_SPACING], m < 1, a non-finite A, misalignment
+ * (lattice 4 B, d_P and d_T 8 B), a d_T that overlaps the lattice or d_P.
+ *
+ * Landmarks.  Host arrays P [m][3] (fixed voxels, xyz), Q [m][3] (moving voxels) and w [m] (NULL: all 1), 1 <= m <=
+ * SIFT3D_AMD_FFD_MAX_LANDMARKS.  A landmark whose P is not inside is not COUNTED (no error).  The residual of a counted
+ * landmark is r_i = T(P_i) - Q_i.  Record (SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES of device memory, 8-byte aligned):
+ *   uint64 counted;
+ *   double S     = sum_i w_i * ((rx rx + ry ry) + rz rz);
+ *   double Omega = sum_i w_i;
+ *   double rmax  = max_i sqrt((rx rx + ry ry) + rz rz), fmax from +0 (correctly rounded sqrt);
+ * every sum and the maximum over the counted landmarks only (all four are 0 when there is none).
+ * Optional outputs (device memory, 8-byte aligned, NULL to leave out; the record's bytes are the same either way):
+ *   d_r  [m][3] double: the residuals in the caller's order, +0 where not counted;
+ *   d_GL [3][gz][gy][gx] double = sum_i (w_i * ((wz * wy) * wx)) * r_{i,d} over the counted landmarks whose support
+ *        holds the control (wx = wx[i - i0] and so on): the derivative of S / 2 over the control points.
+ * counted, rmax and every entry of d_r are defined to the bit.  S and Omega are within gamma_(m + 8) sum |term| of the
+ * exact sums; each entry of GL within gamma_(k + 8) sum |term|, k the landmarks in that control's support.  The sums are
+ * organised as follows, a function of the inputs only, without atomics, so that a call repeats its bytes: the host puts
+ * the counted landmarks in the order of their cells (k0, j0, i0), i0 fastest, by a stable counting sort; S and Omega:
+ * one lane per landmark in that order, per-workgroup partials of a grid of min(ceil(counted / 256), 128) workgroups,
+ * then the slots in a fixed order; GL: one lane per control visits the at most 64 cells of its support in ascending
+ * order and each cell's landmarks in ascending order, from +0.
+ * sift3d_hip_ffd_landmarks: d_work of sift3d_amd_ffd_landmarks_work_bytes(m, gx, gy, gz) bytes, 16-byte aligned.  It
+ * waits for `stream` once before it returns.  -1 before any device call on a NULL d_lattice, P, Q, d_work or d_record,
+ * a lattice dimension < 4, a bad spacing, a non-finite A, m out of range, a non-finite Q or w, a negative w,
+ * misalignment, an output (record, work, d_r, d_GL) that overlaps the lattice or another output.
+ *
+ * Evaluation (sift3d_hip_ffd_evaluate_landmarks): one evaluation of the MSD cost with the term, as the driver makes it
+ * on level 0.  sift3d_hip_ffd_evaluate_masked's arguments and outputs, then `jacobian` with d_jac (the penalty's record,
+ * GJ [3][gz][gy][gx] double at byte 32, then the penalty's work; NULL: no penalty, and jacobian must be 0), the landmarks,
+ * landmark_weight and d_lm (the landmark record, GL [3][gz][gy][gx] double at byte 32, then the landmarks' work), both of
+ * sift3d_amd_ffd_evaluate_landmarks_bytes(which = 1 / 0, ...) bytes, 8-byte aligned.  d_grad is the driver's formula
+ * below with l = 0; landmark_weight == 0 (jacobian == 0) launches the combine without that term.  It waits for `stream`
+ * once before it returns.  Refusals: those of the two entries it is made of.
+ *
+ * Driver (sift3d_amd_ffd_refine_landmarks_device).  sift3d_amd_ffd_refine_jacobian_device's arguments with their
+ * meanings (bins == 0: the MSD, otherwise the mutual information; the masks may be NULL; jacobian >= 0, and `penalty`
+ * may be NULL only when jacobian == 0: the penalty is then not evaluated at all), then P, Q, w, m as above,
+ * landmark_weight (lambda, finite, >= 0) and landmarks_out, a host array of SIFT3D_AMD_FFD_MAX_TRAIL entries parallel
+ * to result->trail.  The loop, levels, subdivision, step rule and stop reasons are that driver's, one loop in the code
+ * too.  Level l uses P * 0.5^l and Q * 0.5^l (exact), the level's lattice for the inside test, and the level's A.  The
+ * term is reported in level-0 units on every level: L = (4^l * S) / Omega and rmax * 2^l; L = 0 and no gradient term
+ * when Omega == 0.
+ *     E    = base_E + lambda * L
+ *     grad = (float)(base_g + ((lambda * (2 * 4^l)) / Omega) * GL)
+ * with base_E and base_g the double expressions of the existing drivers, to the letter ("Jacobian penalty").  With
+ * lambda == 0 no term is added to either formula, L is still recorded, and lattice, field, trail (and `penalty`) are
+ * the existing drivers' byte for byte.  The value pass runs in every evaluation; the adjoint runs where the image force
+ * runs (every evaluation of the MSD, the MI driver's gradient step); S, Omega and rmax come to the host in the
+ * evaluation's existing wait.  The inside test, the scaling and the ordering by cell are made once per level.
+ * -1 before any device call on what that driver refuses (without `penalty` only when jacobian != 0), what
+ * sift3d_hip_ffd_landmarks refuses of P, Q, w and m, a NULL landmarks_out, a landmark_weight that is not finite or is
+ * negative.  d_work: sift3d_amd_ffd_refine_landmarks_work_bytes() bytes, 16-byte aligned: the Jacobian driver's layout,
+ * then the landmark record, GL and the landmarks' work. */
+#define SIFT3D_AMD_FFD_MAX_LANDMARKS 65536
+#define SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES 32
+typedef struct {
+    double L;                                       /* (4^l * S) / Omega, 0 when Omega == 0 */
+    double rmax;                                    /* in level-0 voxels */
+    uint64_t counted;
+} sift3d_amd_ffd_landmark_term;
+/* for bindings that restate them: sizeof the term (0), SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES (1),
+ * SIFT3D_AMD_FFD_MAX_LANDMARKS (2), SIFT3D_AMD_FFD_MAX_TRAIL (3); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_landmarks_struct_bytes(int which);
+SIFT3D_AMD_API int sift3d_hip_ffd_points(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                         const double *A /*12 or NULL*/, const double *d_P, int m, double *d_T,
+                                         void *stream);
+/* bytes of d_work (0 for bad arguments) */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_landmarks_work_bytes(int m, int gx, int gy, int gz);
+/* A, P, Q, w on the host */
+SIFT3D_AMD_API int sift3d_hip_ffd_landmarks(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                            const double *A /*12 or NULL*/, const double *P, const double *Q,
+                                            const double *w /*NULL: all 1*/, int m, void *d_work, void *d_record,
+                                            double *d_r /*or NULL*/, double *d_GL /*or NULL*/, void *stream);
+/* bytes of d_lm (which == 0) and of d_jac (which == 1); 0 for bad arguments */
+SIFT3D_AMD_API size_t sift3d_amd_ffd_evaluate_landmarks_bytes(int which, int m, int ox, int oy, int oz, int dx, int dy,
+                                                              int dz);
+SIFT3D_AMD_API int
+sift3d_hip_ffd_evaluate_landmarks(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                  const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                  const double *A /*12 or NULL*/, double bending, float *d_field, void *d_record,
+                                  float *d_grad, void *d_work, void *stream, const float *d_WF, const float *d_WM,
+                                  double jacobian, void *d_jac /*NULL when jacobian == 0*/, const double *P,
+                                  const double *Q, const double *w, int m, double landmark_weight, void *d_lm);
+SIFT3D_AMD_API size_t
+sift3d_amd_ffd_refine_landmarks_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                           int levels, int m);
+/* A [12], mi_out (NULL allowed when bins == 0), penalty (NULL allowed when jacobian == 0), P, Q, w and landmarks_out on
+ * the host */
+SIFT3D_AMD_API int
+sift3d_amd_ffd_refine_landmarks_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                       int nz, const double *A, const sift3d_amd_ffd_refine_params *params,
+                                       sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                       void *d_work, void *stream, const float *d_WF, const float *d_WM, int bins,
+                                       float lo_f, float hi_f, float lo_m, float hi_m, sift3d_amd_similarity *mi_out,
+                                       double jacobian, sift3d_amd_ffd_penalty *penalty, const double *P,
+                                       const double *Q, const double *w, int m, double landmark_weight,
+                                       sift3d_amd_ffd_landmark_term *landmarks_out);
+
+/* ------------------------------------------------------------------------ */
 /* Dense descriptors: a 12-bin icosahedral gradient histogram per voxel      */
 /* ------------------------------------------------------------------------ */
 /* Upstream SIFT3D's dense descriptor image, non-rotating variant; the fork removed the code

@@ -624,9 +624,14 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
     Where the matches give RANSAC no model the call raises RuntimeError, but with refine=dict(metric="mi") it goes on
     from the identity (A_ransac is then the identity and inliers is all False): keypoints of two modalities often do
     not match, and that is the pair the mutual information is for."""
+    p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
+    return _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine)
+
+
+def _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine):
+    """register() from the matched points on: RANSAC, the optional affine refinement, the resampling"""
     import torch
     from . import hip
-    p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
     try:
         A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
     except RuntimeError:
@@ -1167,6 +1172,11 @@ JacFFDRefinement = collections.namedtuple("JacFFDRefinement", FFDRefinement._fie
 JacMiFFDRefinement = collections.namedtuple("JacMiFFDRefinement",
                                             MiFFDRefinement._fields + ("penalty", "jacobian_weight"))
 JacobianPenalty = collections.namedtuple("JacobianPenalty", "value nonpositive min max gradient")
+# what refine_ffd(landmarks=...) returns: the class of the same call without landmarks, then the term's trail and weight
+FFDLandmarkTerm = collections.namedtuple("FFDLandmarkTerm", "L rmax counted")
+LANDMARK_REFINEMENTS = {k: collections.namedtuple("Lm" + k.__name__, k._fields + ("landmarks", "landmark_weight"))
+                        for k in (FFDRefinement, MiFFDRefinement, JacFFDRefinement, JacMiFFDRefinement)}
+FFD_LANDMARK_WEIGHT = 0.01
 
 
 def jacobian_penalty(field, ref_det=1.0, gradient=False):
@@ -1244,9 +1254,35 @@ def ffd_bending_energy(lattice, spacing):
     return hip.ffd_bending(L, hip.ffd_spacing(spacing, "ffd_bending_energy"))
 
 
+def ffd_transform_points(lattice, spacing, points, A=None):
+    """Map points of the fixed grid through a finished free-form deformation: T(p) = A p + s(p), s the cubic B-spline
+    of the control lattice [3, gz, gy, gx] at integer `spacing`, evaluated at the points themselves in double (contract:
+    include/sift3d_amd.h, "FFD landmarks").  It is the FFD's tps_apply: with r = refine_ffd(...),
+    ffd_transform_points(r.lattice, r.spacing, p, r.A) is where the fixed-grid points p [n, 3] (x, y, z in voxels) land
+    in the moving volume, which is what a target registration error at annotated landmarks needs.  A: the 3 x 4 pull
+    map the lattice was fitted around (None: the identity).  Returns (T [n, 3] float64, inside [n] bool): a point is
+    inside where the lattice's support 0 <= x < (g - 3) * spacing holds it on every axis (the fixed grid is inside);
+    the rows of T that are not inside are NaN.  Computed on the device; waits for torch's current stream."""
+    from . import hip
+    d = hip.ffd_spacing(spacing, "ffd_transform_points")
+    P = hip._points(points, "ffd_transform_points", "points")
+    A0 = None
+    if A is not None:
+        A0 = _affine_or_none(A)
+        if A0 is None or not np.isfinite(A0).all():
+            raise ValueError("ffd_transform_points: A must be a finite 3 x 4 affine pull map or None")
+    if not _torch_tensor(lattice) and (np.ndim(lattice) != 4 or np.shape(lattice)[0] != 3):
+        raise ValueError("ffd_transform_points: the lattice must be [3, gz, gy, gx]")
+    if len(P) == 0:
+        return np.zeros((0, 3)), np.zeros(0, bool)
+    L = _ffd_lattice_tensor(lattice, "ffd_transform_points")
+    T = hip.ffd_points(L, d, P, A0).cpu().numpy()
+    return T, ~np.isnan(T).any(axis=1)
+
+
 def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None,
                metric="msd", bins=None, range_fixed=None, range_moving=None, jacobian=0.0, features="intensity",
-               sigma=1.6, **params):
+               sigma=1.6, landmarks=None, landmark_weight=FFD_LANDMARK_WEIGHT, **params):
     """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
     `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
     include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
@@ -1284,8 +1320,28 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     jacobian > 0 works as above.  The result is an FFDRefinement (JacFFDRefinement); the trail's `msd` is S_ee / n
     with n counting voxels, and `warped` is `moving` through the field, every channel of a 4-D input.  metric="mi",
     bins or ranges together with channels, any other `features`, a 4-D volume beside a 3-D one or with
-    features="descriptors", and stacks of unequal nc raise ValueError."""
+    features="descriptors", and stacks of unequal nc raise ValueError.
+    landmarks=(p_fixed, p_moving) or (p_fixed, p_moving, weights), n x 3 arrays in voxels (x, y, z) and n weights >= 0,
+    adds landmark_weight * L to the cost of either metric, with or without masks and the Jacobian penalty (contract:
+    "FFD landmarks"): L is the weighted mean squared distance between the mapped fixed points T(p_fixed) and p_moving,
+    in level-0 voxels^2 on every level.  It pulls the lattice across displacements beyond the image gradient's capture
+    range and anchors the fit where the image term is flat or masked out.  A fixed point outside the lattice's support
+    is not counted.  The result is the class the call would otherwise return with two more fields (LmFFDRefinement,
+    LmMiFFDRefinement, LmJacFFDRefinement, LmJacMiFFDRefinement): landmarks, one FFDLandmarkTerm(L, rmax, counted) per
+    trail entry, and landmark_weight.  The default weight 0.01 was the best of three tried on one synthetic pair; no
+    calibration against the image term is claimed.  landmark_weight == 0 records L and leaves the fit unchanged.
+    Landmarks together with channels are not supported and raise ValueError, as do bad shapes, n outside [1, 65536],
+    non-finite moving points or weights, negative weights, and a non-finite or negative landmark_weight."""
     from . import hip
+    lm = None
+    if landmarks is not None:
+        if not isinstance(landmarks, (tuple, list)) or len(landmarks) not in (2, 3):
+            raise ValueError("refine_ffd: landmarks must be (p_fixed, p_moving) or (p_fixed, p_moving, weights)")
+        lm = hip.ffd_landmark_arrays(landmarks[0], landmarks[1], landmarks[2] if len(landmarks) == 3 else None,
+                                     "refine_ffd")
+        landmark_weight = float(landmark_weight)
+        if not (np.isfinite(landmark_weight) and landmark_weight >= 0):
+            raise ValueError("refine_ffd: landmark_weight must be finite and not negative")
     if features not in ("intensity", "descriptors"):
         raise ValueError("refine_ffd: features must be 'intensity' or 'descriptors', not %r" % (features,))
     dims = tuple(3 if isinstance(v, Image) else v.dim() if _torch_tensor(v) else np.ndim(v) for v in (fixed, moving))
@@ -1293,6 +1349,9 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         raise ValueError("refine_ffd: fixed and moving must both be volumes [nz, ny, nx]%s, not %d-D and %d-D"
                          % ("" if features == "descriptors" else " or both stacks [nc, nz, ny, nx]", *dims))
     channels = features == "descriptors" or dims == (4, 4)
+    if channels and lm is not None:
+        raise ValueError("refine_ffd: landmarks together with channels (features='descriptors' or 4-D volumes) are not "
+                         "supported")
     if channels and metric != "msd":
         raise ValueError("refine_ffd: channels (features='descriptors' or 4-D volumes) are driven by the MSD alone, "
                          "not metric=%r" % (metric,))
@@ -1342,8 +1401,14 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         M = _similarity_volume(moving, "refine_ffd", "moving", F.device)
     WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
-    penalty = None
-    if channels:
+    penalty = terms = None
+    if lm is not None:
+        mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
+            if metric == "mi" else {}
+        res, lattice, field, sim, penalty, terms = hip.ffd_refine_landmarks(
+            F, M, *lm, landmark_weight=landmark_weight, jacobian=jacobian if jacobian > 0 else None, A=A0, params=p,
+            mask_fixed=WF, mask_moving=WM, **mi)
+    elif channels:
         # every level's volumes (and float masks) by restriction; descriptors of each level's own volumes
         fv, mv, wf, wm = [F], [M], [WF], [WM]
         for _ in range(1, int(levels)):
@@ -1374,12 +1439,16 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         out = MiFFDRefinement(*out, mi=float(sim.mi), nmi=float(sim.nmi), bins=int(bins))
     if penalty is not None:
         kind = JacMiFFDRefinement if metric == "mi" else JacFFDRefinement
-        return kind(*out, penalty=[FFDPenalty(*q) for q in penalty], jacobian_weight=jacobian)
+        out = kind(*out, penalty=[FFDPenalty(*q) for q in penalty], jacobian_weight=jacobian)
+    if terms is not None:
+        out = LANDMARK_REFINEMENTS[type(out)](*out, landmarks=[FFDLandmarkTerm(*t) for t in terms],
+                                              landmark_weight=landmark_weight)
     return out
 
 
 def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
-                 ffd_params=None, refine=True, **detector_kw):
+                 ffd_params=None, refine=True, landmarks=False, landmark_weight=FFD_LANDMARK_WEIGHT,
+                 landmark_err_thresh=DEFORMABLE_ERR_THRESH, **detector_kw):
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
     refine_ffd's further keyword arguments (dict(metric="mi") for a mutual-information FFD stage, which then returns
@@ -1387,12 +1456,25 @@ def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.
     which needs no common intensity scale); refine: True, or register's dict of refine_affine's keyword arguments (dict(metric="ncc") or
     dict(metric="mi") for the affine stage).  The two stages' metrics are chosen separately; either defaults to the
     MSD.  The volumes are torch CUDA float32 tensors, or Images / arrays, which are uploaded.  Returns
-    FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement)."""
+    FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement).
+    landmarks=True keeps the matched keypoints for the FFD stage (they are detected once): the inliers of ransac_affine
+    on the same matches at landmark_err_thresh (DEFORMABLE_ERR_THRESH, wider than err_thresh for
+    register_deformable's reason: a match that a deformation moved off the affine model is the one the deformable stage
+    wants) with the same num_iter and seed go to refine_ffd as landmarks (fixed xyz, moving xyz) with landmark_weight.
+    Where RANSAC finds no such inlier the FFD stage runs without the term."""
     F = _similarity_volume(fixed, "register_ffd", "fixed")
     M = _similarity_volume(moving, "register_ffd", "moving", F.device)
-    reg = register(M, F, nn_thresh, err_thresh, num_iter, seed, refine=refine if isinstance(refine, dict) else True,
-                   **detector_kw)
-    ref = refine_ffd(M, F, reg.refinement.A, spacing, levels, bending, **(ffd_params or {}))
+    p_mov, p_fix = _matched_points(M, F, nn_thresh, detector_kw, "register_ffd")
+    reg = _register_matched(M, F, p_mov, p_fix, err_thresh, num_iter, seed, refine if isinstance(refine, dict) else True)
+    kw = dict(ffd_params or {})
+    if landmarks:
+        try:
+            _, inl = ransac_affine(p_mov, p_fix, landmark_err_thresh, num_iter, seed)
+        except RuntimeError:
+            inl = np.zeros(len(p_mov), bool)
+        if inl.any():
+            kw.update(landmarks=(p_fix[inl], p_mov[inl]), landmark_weight=landmark_weight)
+    ref = refine_ffd(M, F, reg.refinement.A, spacing, levels, bending, **kw)
     return FFDRegistration(reg, ref)
 
 

@@ -12,11 +12,30 @@
  * and is the optional third term of the driver's cost.
  *
  * "Multi-channel free-form deformation": the same entry body and the same driver loop over stacks of nc channels, the
- * driver's levels supplied by the caller instead of restricted here. */
+ * driver's levels supplied by the caller instead of restricted here.
+ *
+ * "FFD landmarks" (kernels in sift3d_ffd_landmarks.hip): the spline at points, the landmark record with its residuals
+ * and adjoint, whose landmarks the host puts in cell order, and the optional last term of the driver's cost. */
 #include <stddef.h>
 
 #include "sift3d_ffd_jac.h"
+#include "sift3d_ffd_landmarks.h"
 
+int sift3d_ffd_points_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                             const double *A, const double *d_P, int m, double *d_T, void *stream);
+int sift3d_ffd_landmarks_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                                const sift3d_ffd_lm *lm, int adjoint, double *d_r, void *stream);
+int sift3d_ffd_evaluate_lm_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
+                                  int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
+                                  int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
+                                  double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
+                                  const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm);
+int sift3d_ffd_mi_lm_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
+                            const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
+                            int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
+                            double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
+                            double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
+                            const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm);
 int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
                                    double *d_rec, double *d_S, double *d_work, void *stream);
 int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
@@ -180,6 +199,11 @@ size_t sift3d_amd_ffd_evaluate_work_bytes(int ox, int oy, int oz, int dx, int dy
                             sift3d_amd_ffd_lattice_dim(oz, dz)) * sizeof(double);
 }
 
+/* the landmarks of an evaluation (defined with the landmark entries below) */
+struct ffd_lm_host_s;
+static int ffd_lm_prepare(struct ffd_lm_host_s *h, sift3d_ffd_lm *lm, int gx, int gy, int gz, const int *d, double scale,
+                          void *stream);
+
 /* bins, the two ranges and the table of an MI evaluation */
 typedef struct {
     int bins;
@@ -189,12 +213,14 @@ typedef struct {
 
 /* the shared body of the four entries: d_WF, d_WM are the masks ("Masks") or NULL; mi: the MI evaluation's further
  * arguments, checked after the FFD entries' own, or NULL (the MSD); nc: 0 (one volume each, the single-channel kernels)
- * or the channels of the stacks d_F and d_M (the channels entry, which has checked nc >= 1) */
+ * or the channels of the stacks d_F and d_M (the channels entry, which has checked nc >= 1); lm (the landmarks entry,
+ * which has checked them and their buffers; else NULL): the landmark term, lmh its host side, and jac the penalty or
+ * NULL (the MSD of single volumes only) */
 static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                               int ny, int nz, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
                               const double *A, double bending, float *d_field, void *d_record, float *d_grad,
                               void *d_work, void *stream, const float *d_WF, const float *d_WM, const ffd_mi_args *mi,
-                              int nc)
+                              int nc, const sift3d_ffd_jac *jac, struct ffd_lm_host_s *lmh, sift3d_ffd_lm *lm)
 {
     const int ch = nc ? nc : 1;
     int delta[3];
@@ -234,6 +260,14 @@ static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy
         sift3d_ffd_field_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, (const float *)d_work, A, ox, oy, oz, d_field,
                                 stream))
         return SIFT3D_FAILURE;
+    if (lm) {
+        if (ffd_lm_prepare(lmh, lm, gx, gy, gz, delta, 1.0, stream))
+            return SIFT3D_FAILURE;
+        return sift3d_ffd_evaluate_lm_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx,
+                                             dy, dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
+                                             (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream,
+                                             d_WF, d_WM, jac, lm);
+    }
     if (mi)
         return sift3d_ffd_mi_launch(what, 1, 1, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
                                     dz, (const float *)d_work, st, bending, mi->bins, mi->lo_f, s_f, mi->lo_m, mi->hi_m,
@@ -257,7 +291,8 @@ int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const floa
                             double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
 {
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL, NULL, 0);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL, NULL, 0, NULL, NULL,
+                              NULL);
 }
 
 int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -267,7 +302,7 @@ int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, con
 {
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy,
                               gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM,
-                              NULL, 0);
+                              NULL, 0, NULL, NULL, NULL);
 }
 
 /* one force volume whatever nc is: the single-channel evaluation's work */
@@ -285,7 +320,7 @@ int sift3d_hip_ffd_evaluate_channels(const float *d_F, int ox, int oy, int oz, c
     if (check_channels(what, nc))
         return SIFT3D_FAILURE;
     return ffd_evaluate_entry(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx, dy, dz, A, bending,
-                              d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, NULL, nc);
+                              d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, NULL, nc, NULL, NULL, NULL);
 }
 
 int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -296,7 +331,8 @@ int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const f
 {
     const ffd_mi_args mi = { bins, lo_f, hi_f, lo_m, hi_m, d_W };
     return ffd_evaluate_entry("sift3d_hip_ffd_mi_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, &mi, 0);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, &mi, 0, NULL, NULL,
+                              NULL);
 }
 
 size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz)
@@ -447,6 +483,271 @@ int sift3d_hip_ffd_jacobian_gradient(const float *d_field, int ox, int oy, int o
                                                stream);
 }
 
+/* ---- points and landmarks ("FFD landmarks") ---- */
+
+int sift3d_hip_ffd_points(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
+                          const double *d_P, int m, double *d_T, void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_points";
+    if (!d_lattice || !d_P || !d_T)
+        return refuse(what, "NULL argument");
+    if (gx < 4 || gy < 4 || gz < 4)
+        return refuse(what, "a lattice has at least 4 control points along every axis");
+    if (!ffd_spacing_ok(dx, dy, dz))
+        return refuse(what, "the spacing must be in [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    if (m < 1)
+        return refuse(what, "the number of points must be positive");
+    if ((A && check_affine(what, A)) || check_aligned(what, ADDR(d_P) | ADDR(d_T), ADDR(d_lattice)))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_lattice, image_bytes(gx, gy, gz, 3) }, { d_P, (size_t)m * 3 * sizeof(double) } };
+        const range_t out[] = { { d_T, (size_t)m * 3 * sizeof(double) } };
+        if (ranges_aliased(out, 1, in, 2))
+            return refuse(what, ALIASED);
+    }
+    return sift3d_ffd_points_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, A, d_P, m, d_T, stream);
+}
+
+size_t sift3d_amd_ffd_landmarks_work_bytes(int m, int gx, int gy, int gz)
+{
+    if (m < 1 || m > SIFT3D_AMD_FFD_MAX_LANDMARKS || gx < 4 || gy < 4 || gz < 4)
+        return 0;
+    return pad16(sift3d_ffd_lm_doubles((size_t)m) * sizeof(double) +
+                 ((size_t)m + grid_voxels(gx - 3, gy - 3, gz - 3) + 1) * sizeof(uint32_t));
+}
+
+size_t sift3d_amd_ffd_landmarks_struct_bytes(int which)
+{
+    return which == 0   ? sizeof(sift3d_amd_ffd_landmark_term)
+           : which == 1 ? (size_t)SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES
+           : which == 2 ? (size_t)SIFT3D_AMD_FFD_MAX_LANDMARKS
+           : which == 3 ? (size_t)SIFT3D_AMD_FFD_MAX_TRAIL
+                        : 0;
+}
+
+/* the caller's landmarks and the host's staging of one level's: the rows of the work buffer that the host fills
+ * (sift3d_ffd_landmarks.h), one allocation */
+typedef struct ffd_lm_host_s {
+    const double *P, *Q, *w;                     /* w may be NULL: all 1 */
+    int m;
+    double weight;                               /* the driver's lambda */
+    sift3d_amd_ffd_landmark_term *out;           /* the driver's array parallel to the trail */
+    double up;                                   /* the driver's 2^l on level l */
+    double *rows;                                /* [7][m] */
+    uint32_t *orig, *start, *cell;               /* [m], [cells + 1] of the finest lattice, [m] */
+} ffd_lm_host;
+
+static int check_landmarks(const char *what, const double *P, const double *Q, const double *w, int m)
+{
+    int i;
+    if (!P || !Q)
+        return refuse(what, "NULL argument");
+    if (m < 1 || m > SIFT3D_AMD_FFD_MAX_LANDMARKS)
+        return refuse(what, "the number of landmarks must be in [1, SIFT3D_AMD_FFD_MAX_LANDMARKS]");
+    for (i = 0; i < 3 * m; i++)
+        if (!isfinite(Q[i]))
+            return refuse(what, "a moving landmark is not finite");
+    for (i = 0; w && i < m; i++)
+        if (!isfinite(w[i]) || w[i] < 0)
+            return refuse(what, "a landmark weight must be finite and not negative");
+    return SIFT3D_SUCCESS;
+}
+
+/* cells: those of the finest lattice the staging is used with */
+static int ffd_lm_host_alloc(const char *what, ffd_lm_host *h, size_t cells)
+{
+    const size_t m = (size_t)h->m;
+    h->rows = (double *)calloc(7 * m * sizeof(double) + (2 * m + cells + 1) * sizeof(uint32_t), 1);
+    if (!h->rows)
+        return refuse(what, "out of host memory");
+    h->orig = (uint32_t *)(h->rows + 7 * m);
+    h->start = h->orig + m;
+    h->cell = h->start + cells + 1;
+    return SIFT3D_SUCCESS;
+}
+
+/* the point rule of one axis: 1 and the cell where the coordinate is finite and 0 <= floor(x / delta) <= g - 4 */
+static int ffd_lm_axis(double x, int delta, int g, uint32_t *i0)
+{
+    const double f = floor(x / (double)delta);
+    if (!(f >= 0.0 && f <= (double)(g - 4)))
+        return 0;
+    *i0 = (uint32_t)f;
+    return 1;
+}
+
+/* One level's landmarks to lm->d_work: P and Q times `scale` (a power of two: exact), the inside test on the lattice
+ * (gx, gy, gz) at spacing d, a stable counting sort by cell (k0, j0, i0), i0 fastest, and the copies (staged by the
+ * runtime before the call returns, as the weight tables').  lm->n leaves with the number inside. */
+static int ffd_lm_prepare(ffd_lm_host *h, sift3d_ffd_lm *lm, int gx, int gy, int gz, const int *d, double scale,
+                          void *stream)
+{
+    const size_t m = (size_t)h->m, cells = grid_voxels(gx - 3, gy - 3, gz - 3);
+    double *dev_rows = (double *)lm->d_work + 3 * (size_t)SIFT3D_FFD_LM_GRID;
+    uint32_t *dev_orig = (uint32_t *)(dev_rows + 22 * m);
+    size_t i, c;
+    memset(h->start, 0, (cells + 1) * sizeof(uint32_t));
+    for (i = 0; i < m; i++) {
+        uint32_t i0, j0, k0;
+        if (ffd_lm_axis(h->P[3 * i] * scale, d[0], gx, &i0) && ffd_lm_axis(h->P[3 * i + 1] * scale, d[1], gy, &j0) &&
+            ffd_lm_axis(h->P[3 * i + 2] * scale, d[2], gz, &k0)) {
+            h->cell[i] = (uint32_t)(((size_t)k0 * (size_t)(gy - 3) + j0) * (size_t)(gx - 3) + i0);
+            h->start[h->cell[i] + 1]++;
+        } else
+            h->cell[i] = UINT32_MAX;
+    }
+    for (c = 0; c < cells; c++)
+        h->start[c + 1] += h->start[c];
+    lm->n = (int)h->start[cells];
+    for (i = 0; i < m; i++) {                                /* start[c] runs up to the end of cell c ... */
+        int k;
+        uint32_t pos;
+        if (h->cell[i] == UINT32_MAX)
+            continue;
+        pos = h->start[h->cell[i]]++;
+        for (k = 0; k < 3; k++) {
+            h->rows[(size_t)k * m + pos] = h->P[3 * i + k] * scale;
+            h->rows[(size_t)(3 + k) * m + pos] = h->Q[3 * i + k] * scale;
+        }
+        h->rows[6 * m + pos] = h->w ? h->w[i] : 1.0;
+        h->orig[pos] = (uint32_t)i;
+    }
+    for (c = cells; c > 0; c--)                              /* ... and is put back to its beginning */
+        h->start[c] = h->start[c - 1];
+    h->start[0] = 0;
+    if (sift3d_hip_memcpy_h2d(dev_rows, h->rows, 7 * m * sizeof(double), stream) ||
+        sift3d_hip_memcpy_h2d(dev_orig, h->orig, m * sizeof(uint32_t), stream) ||
+        sift3d_hip_memcpy_h2d(dev_orig + m, h->start, (cells + 1) * sizeof(uint32_t), stream))
+        return SIFT3D_FAILURE;
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_hip_ffd_landmarks(const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
+                             const double *P, const double *Q, const double *w, int m, void *d_work, void *d_record,
+                             double *d_r, double *d_GL, void *stream)
+{
+    static const char what[] = "sift3d_hip_ffd_landmarks";
+    const int d[3] = { dx, dy, dz };
+    ffd_lm_host h = { P, Q, w, m, 0.0, NULL, 1.0, NULL, NULL, NULL, NULL };
+    sift3d_ffd_lm lm;
+    int rc;
+    if (!d_lattice || !d_work || !d_record)
+        return refuse(what, "NULL argument");
+    if (gx < 4 || gy < 4 || gz < 4)
+        return refuse(what, "a lattice has at least 4 control points along every axis");
+    if (!ffd_spacing_ok(dx, dy, dz))
+        return refuse(what, "the spacing must be in [1, SIFT3D_AMD_FFD_MAX_SPACING]");
+    if ((A && check_affine(what, A)) || check_landmarks(what, P, Q, w, m) ||
+        check_aligned(what, ADDR(d_record) | ADDR(d_r) | ADDR(d_GL), ADDR(d_lattice)))
+        return SIFT3D_FAILURE;
+    if (ADDR(d_work) & 15)
+        return refuse(what, "a buffer is misaligned");
+    {
+        const range_t in[] = { { d_lattice, image_bytes(gx, gy, gz, 3) } };
+        const range_t out[] = { { d_record, SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES },
+                                { d_work, sift3d_amd_ffd_landmarks_work_bytes(m, gx, gy, gz) },
+                                { d_r, d_r ? (size_t)m * 3 * sizeof(double) : 0 },
+                                { d_GL, d_GL ? 3 * grid_voxels(gx, gy, gz) * sizeof(double) : 0 } };
+        if (ranges_aliased(out, 4, in, 1))
+            return refuse(what, ALIASED);
+    }
+    if (ffd_lm_host_alloc(what, &h, grid_voxels(gx - 3, gy - 3, gz - 3)))
+        return SIFT3D_FAILURE;
+    lm.weight = 0.0;
+    lm.scale = 2.0;
+    lm.A = A;
+    lm.m = m;
+    lm.d_rec = (double *)d_record;
+    lm.d_GL = d_GL;
+    lm.d_work = d_work;
+    rc = ffd_lm_prepare(&h, &lm, gx, gy, gz, d, 1.0, stream) ||
+         (d_r && sift3d_hip_memset(d_r, 0, (size_t)m * 3 * sizeof(double), stream)) ||
+         sift3d_ffd_landmarks_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, &lm, d_GL != NULL, d_r, stream);
+    if (sift3d_hip_stream_sync(stream))                      /* the staging is released only behind its copies */
+        rc = SIFT3D_FAILURE;
+    free(h.rows);
+    return rc ? SIFT3D_FAILURE : SIFT3D_SUCCESS;
+}
+
+/* the evaluation with the landmark term: d_lm holds the landmark record, GL and the landmarks' work; d_jac the penalty's
+ * record, GJ and the penalty's work */
+size_t sift3d_amd_ffd_evaluate_landmarks_bytes(int which, int m, int ox, int oy, int oz, int dx, int dy, int dz)
+{
+    const int gx = sift3d_amd_ffd_lattice_dim(ox, dx), gy = sift3d_amd_ffd_lattice_dim(oy, dy);
+    const int gz = sift3d_amd_ffd_lattice_dim(oz, dz);
+    const size_t lm = sift3d_amd_ffd_landmarks_work_bytes(m, gx, gy, gz);
+    if (ox <= 0 || oy <= 0 || oz <= 0 || !ffd_spacing_ok(dx, dy, dz) || (which == 0 && !lm) || which < 0 || which > 1)
+        return 0;
+    return 32 + 3 * grid_voxels(gx, gy, gz) * sizeof(double) +
+           (which == 0 ? lm : sift3d_amd_jacobian_penalty_work_bytes(ox, oy, oz));
+}
+
+static int ffd_jacobian_ref(const char *what, const double *A, double *ref);
+
+int sift3d_hip_ffd_evaluate_landmarks(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                      const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
+                                      const double *A, double bending, float *d_field, void *d_record, float *d_grad,
+                                      void *d_work, void *stream, const float *d_WF, const float *d_WM, double jacobian,
+                                      void *d_jac, const double *P, const double *Q, const double *w, int m,
+                                      double landmark_weight, void *d_lm)
+{
+    static const char what[] = "sift3d_hip_ffd_evaluate_landmarks";
+    ffd_lm_host h = { P, Q, w, m, landmark_weight, NULL, 1.0, NULL, NULL, NULL, NULL };
+    sift3d_ffd_jac jac;
+    sift3d_ffd_lm lm;
+    double ref = 1.0;
+    int rc;
+    if (!d_F || !d_M || !d_lattice || !d_field || !d_record || !d_grad || !d_work || !d_lm)
+        return refuse(what, "NULL argument");
+    if (check_ffd_lattice(what, ox, oy, oz, gx, gy, gz, dx, dy, dz) || check_dims(what, nx, ny, nz))
+        return SIFT3D_FAILURE;
+    if (!isfinite(jacobian) || jacobian < 0)
+        return refuse(what, "the Jacobian weight must be finite and not negative");
+    if (jacobian != 0 && !d_jac)
+        return refuse(what, "a Jacobian weight needs the penalty's buffer");
+    if (!isfinite(landmark_weight) || landmark_weight < 0)
+        return refuse(what, "the landmark weight must be finite and not negative");
+    if (check_landmarks(what, P, Q, w, m) || (d_jac && ffd_jacobian_ref(what, A, &ref)) ||
+        check_aligned(what, ADDR(d_jac) | ADDR(d_lm), 0))
+        return SIFT3D_FAILURE;
+    {
+        const range_t in[] = { { d_F, image_bytes(ox, oy, oz, 1) }, { d_M, image_bytes(nx, ny, nz, 1) },
+                               { d_lattice, image_bytes(gx, gy, gz, 3) },
+                               { d_WF, d_WF ? image_bytes(ox, oy, oz, 1) : 0 },
+                               { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 },
+                               { d_field, field_bytes(ox, oy, oz) },
+                               { d_record, sift3d_amd_ffd_record_bytes(gx, gy, gz) },
+                               { d_grad, image_bytes(gx, gy, gz, 3) },
+                               { d_work, sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz) } };
+        const range_t out[] = { { d_lm, sift3d_amd_ffd_evaluate_landmarks_bytes(0, m, ox, oy, oz, dx, dy, dz) },
+                                { d_jac, d_jac ? sift3d_amd_ffd_evaluate_landmarks_bytes(1, m, ox, oy, oz, dx, dy, dz)
+                                               : 0 } };
+        if (ranges_aliased(out, 2, in, 9))
+            return refuse(what, ALIASED);
+    }
+    if (ffd_lm_host_alloc(what, &h, grid_voxels(gx - 3, gy - 3, gz - 3)))
+        return SIFT3D_FAILURE;
+    jac.weight = jacobian;
+    jac.ref = ref;
+    jac.d_rec = (double *)d_jac;
+    jac.d_GJ = jac.d_rec + 4;
+    jac.d_work = jac.d_GJ + 3 * grid_voxels(gx, gy, gz);
+    lm.weight = landmark_weight;
+    lm.scale = 2.0;
+    lm.A = A;
+    lm.n = 0;
+    lm.m = m;
+    lm.d_rec = (double *)d_lm;
+    lm.d_GL = lm.d_rec + 4;
+    lm.d_work = lm.d_GL + 3 * grid_voxels(gx, gy, gz);
+    rc = ffd_evaluate_entry(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx, dy, dz, A, bending,
+                            d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, NULL, 0, d_jac ? &jac : NULL, &h, &lm);
+    if (rc == SIFT3D_SUCCESS && sift3d_hip_stream_sync(stream))
+        rc = SIFT3D_FAILURE;                                 /* the staging is released only behind its copies */
+    free(h.rows);
+    return rc;
+}
+
 /* ---- the driver ---- */
 
 void sift3d_amd_ffd_refine_default_params(sift3d_amd_ffd_refine_params *p)
@@ -571,6 +872,8 @@ typedef struct {
     double image;
     ffd_jac_head j;
     double P;
+    double lm[3];                                /* with landmarks: S, Omega, rmax of their record */
+    double L;                                    /* and the term in level-0 units: 4^l S / Omega, 0 when Omega == 0 */
 } ffd_eval;
 
 typedef struct {
@@ -585,6 +888,7 @@ typedef struct {
     float s_f;                                   /* MI: the fixed bin's scale */
     const sift3d_ffd_jac *jac;                   /* the Jacobian penalty's weight and buffers; or NULL */
     int nc;                                      /* the channels of the levels' stacks; 0: single volumes */
+    const sift3d_ffd_lm *lm;                     /* the landmark term's weight and buffers on this level; or NULL */
 } ffd_ctx;
 
 /* with a penalty: its record to the host, ahead of the wait that the caller makes */
@@ -596,6 +900,18 @@ static int ffd_jac_fetch(const ffd_ctx *x, ffd_eval *e)
 static void ffd_jac_mean(const ffd_ctx *x, const ffd_level *lv, ffd_eval *e)
 {
     e->P = x->jac ? e->j.sum / (double)grid_voxels(lv->ox, lv->oy, lv->oz) : 0.0;
+}
+
+/* with landmarks: S, Omega and rmax of their record to the host, ahead of the same wait */
+static int ffd_lm_fetch(const ffd_ctx *x, ffd_eval *e)
+{
+    return x->lm ? sift3d_hip_memcpy_d2h(e->lm, x->lm->d_rec + 1, sizeof(e->lm), x->stream) : SIFT3D_SUCCESS;
+}
+
+/* lm->scale is 2 * 4^l */
+static void ffd_lm_mean(const ffd_ctx *x, ffd_eval *e)
+{
+    e->L = x->lm && e->lm[1] != 0.0 ? ((0.5 * x->lm->scale) * e->lm[0]) / e->lm[1] : 0.0;
 }
 
 /* one evaluation at lattice c on `lv`: the field, then
@@ -617,13 +933,13 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
                                       x->d_field, ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m,
                                       (unsigned long long *)ms->d_hist, (unsigned long long *)(ms->d_hist + cells),
                                       x->d_eval, x->stream, lv->WF, lv->WM) ||
-            sift3d_ffd_mi_jac_launch(what, 1, 0, NULL, lv->ox, lv->oy, lv->oz, NULL, lv->nx, lv->ny, lv->nz, x->d_field,
-                                     c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
-                                     ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval,
-                                     x->stream, lv->WF, lv->WM, x->jac) ||
+            sift3d_ffd_mi_lm_launch(what, 1, 0, NULL, lv->ox, lv->oy, lv->oz, NULL, lv->nx, lv->ny, lv->nz, x->d_field,
+                                    c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
+                                    ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval,
+                                    x->stream, lv->WF, lv->WM, x->jac, x->lm) ||
             sift3d_hip_memcpy_d2h(ms->hist, ms->d_hist, (cells + 1) * sizeof(uint64_t), x->stream) ||
             sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
-            sift3d_hip_stream_sync(x->stream) ||
+            ffd_lm_fetch(x, e) || sift3d_hip_stream_sync(x->stream) ||
             sift3d_amd_parzen_mi(ms->hist, ms->bins, &ms->sim_trial, ms->W))
             return SIFT3D_FAILURE;
         e->h.n = ms->hist[cells];
@@ -631,63 +947,78 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
         e->h.gmax = NAN;
         e->image = -ms->sim_trial.mi;                        /* NaN when nothing was counted */
         ffd_jac_mean(x, lv, e);
+        ffd_lm_mean(x, e);
         return SIFT3D_SUCCESS;
     }
     if ((x->nc ? sift3d_ffd_evaluate_channels_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
                                                      x->nc, x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1],
                                                      x->d[2], x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval,
                                                      x->stream, lv->WF, lv->WM, x->jac)
-               : sift3d_ffd_evaluate_jac_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
-                                                x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2],
-                                                x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval, x->stream,
-                                                lv->WF, lv->WM, x->jac)) ||
+               : sift3d_ffd_evaluate_lm_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
+                                               x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2],
+                                               x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval, x->stream,
+                                               lv->WF, lv->WM, x->jac, x->lm)) ||
         sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
-        sift3d_hip_stream_sync(x->stream))
+        ffd_lm_fetch(x, e) || sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
     e->image = e->h.n ? e->h.see / (double)e->h.n : NAN;
     ffd_jac_mean(x, lv, e);
+    ffd_lm_mean(x, e);
     return SIFT3D_SUCCESS;
 }
 
 /* MI: the gradient at c, the lattice of the evaluation that left its table in ms->W, its field in d_field and its
  * second derivatives in the work buffer (no evaluation was made since): W to the device, the force, adjoint, bending
  * gradient and combine passes (with a penalty of weight > 0, its value and gradient passes on the same field: the same
- * record once more, S and GJ), gmax to the host and the wait for it */
+ * record once more, S and GJ; with landmarks of weight > 0 their value and adjoint passes likewise), gmax to the host
+ * and the wait for it */
 static int ffd_mi_gradient(const char *what, const ffd_ctx *x, const ffd_level *lv, const float *c, float *grad,
                            ffd_eval *e)
 {
     mi_state *ms = x->ms;
     ffd_head h;
     if (sift3d_hip_memcpy_h2d(ms->d_W, ms->W, (size_t)ms->bins * ms->bins * sizeof(double), x->stream) ||
-        sift3d_ffd_mi_jac_launch(what, 0, 1, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
-                                 lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
-                                 ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
-                                 lv->WF, lv->WM, x->jac && x->jac->weight > 0 ? x->jac : NULL) ||
+        sift3d_ffd_mi_lm_launch(what, 0, 1, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
+                                lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
+                                ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
+                                lv->WF, lv->WM, x->jac && x->jac->weight > 0 ? x->jac : NULL,
+                                x->lm && x->lm->weight > 0 ? x->lm : NULL) ||
         sift3d_hip_memcpy_d2h(&h, x->d_rec, sizeof(h), x->stream) || sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
     e->h.gmax = h.gmax;
     return SIFT3D_SUCCESS;
 }
 
-/* jacobian: the penalty's weight; 0 (also: no penalty) adds no third term */
-static double ffd_cost(const ffd_eval *e, double bending, double jacobian)
+/* jacobian: the penalty's weight; 0 (also: no penalty) adds no third term.  lambda: the landmark term's weight, as
+ * jacobian */
+static double ffd_cost(const ffd_eval *e, double bending, double jacobian, double lambda)
 {
     const double two = e->image + bending * e->h.R;
-    return jacobian > 0 ? two + jacobian * e->P : two;
+    const double base = jacobian > 0 ? two + jacobian * e->P : two;
+    return lambda > 0 ? base + lambda * e->L : base;
 }
 
-/* penalty: the caller's array parallel to the trail, or NULL */
+/* penalty: the caller's array parallel to the trail, or NULL; lmh: the landmarks with theirs, or NULL (n: those counted
+ * on this level) */
 static void ffd_trail(sift3d_amd_ffd_refine_result *res, const ffd_eval *v, double bending, double jacobian,
-                      sift3d_amd_ffd_penalty *penalty, double step, int accepted, int level)
+                      sift3d_amd_ffd_penalty *penalty, const ffd_lm_host *lmh, int n, double step, int accepted,
+                      int level)
 {
     sift3d_amd_ffd_evaluation *e = res->trail + res->evaluations++;
+    const double lambda = lmh ? lmh->weight : 0.0;
+    if (lmh) {
+        sift3d_amd_ffd_landmark_term *t = lmh->out + (e - res->trail);
+        t->L = v->L;
+        t->rmax = v->lm[2] * lmh->up;
+        t->counted = (uint64_t)n;
+    }
     if (penalty) {
         sift3d_amd_ffd_penalty *q = penalty + (e - res->trail);
         q->P = v->P;
         q->rmin = v->j.rmin;
         q->nonpos = v->j.nonpos;
     }
-    e->E = ffd_cost(v, bending, jacobian);
+    e->E = ffd_cost(v, bending, jacobian, lambda);
     e->msd = v->image;
     e->R = v->h.R;
     e->n = v->h.n;
@@ -710,15 +1041,21 @@ static size_t ffd_channels_base_bytes(int ox, int oy, int oz, const int *d)
  * `ref` the reference determinant, both checked by the caller, and the work buffer is that driver's.
  * src (the channels driver; else NULL): the caller's levels, checked by the caller, of nc channels each.  d_F .. d_WM
  * are then level 0's; the other levels are taken from src where the other drivers restrict the level above, and the
- * work buffer is sift3d_amd_ffd_refine_channels_work_bytes(). */
+ * work buffer is sift3d_amd_ffd_refine_channels_work_bytes().
+ * lmh (the landmarks driver; else NULL; never with src): the landmarks, checked by the caller, their weight and the
+ * array parallel to the trail, with staging for level 0's lattice; the work buffer is that driver's whether or not
+ * there is a penalty. */
 static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                       int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
                       sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
                       void *stream, int masked, const float *d_WF, const float *d_WM, mi_state *ms, double jacobian,
-                      double ref, sift3d_amd_ffd_penalty *penalty, const sift3d_amd_ffd_level *src, int nc)
+                      double ref, sift3d_amd_ffd_penalty *penalty, const sift3d_amd_ffd_level *src, int nc,
+                      ffd_lm_host *lmh)
 {
     const int ch = src ? nc : 1;
+    const double lambda = lmh ? lmh->weight : 0.0;
     sift3d_ffd_jac jac;
+    sift3d_ffd_lm lm;
     sift3d_amd_ffd_refine_params prm;
     ffd_level lv[SIFT3D_AMD_DEMONS_MAX_LEVELS];
     ffd_eval rec, trial;
@@ -753,7 +1090,10 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                                { d_WM, d_WM ? image_bytes(nx, ny, nz, 1) : 0 } };
         const range_t out[] = { { d_lattice, image_bytes(lv[0].gx, lv[0].gy, lv[0].gz, 3) },
                                 { d_field, field_bytes(ox, oy, oz) },
-                                { d_work, src ? sift3d_amd_ffd_refine_channels_work_bytes(ox, oy, oz, prm.spacing[0],
+                                { d_work, lmh ? sift3d_amd_ffd_refine_landmarks_work_bytes(
+                                                    ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
+                                                    prm.spacing[2], prm.levels, lmh->m)
+                                          : src ? sift3d_amd_ffd_refine_channels_work_bytes(ox, oy, oz, prm.spacing[0],
                                                                                           prm.spacing[1], prm.spacing[2])
                                               : (penalty  ? sift3d_amd_ffd_refine_jacobian_work_bytes
                                                  : ms     ? sift3d_amd_ffd_mi_refine_work_bytes
@@ -793,11 +1133,25 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     x.s_f = s_f;
     x.jac = NULL;
     x.nc = src ? nc : 0;
-    if (penalty) {                                           /* behind everything the MI driver lays out (channels:
-                                                                behind the lattices) */
+    x.lm = NULL;
+    lm.n = 0;
+    if (lmh) {                                               /* behind everything the Jacobian driver lays out */
+        char *at = w + pad16(sift3d_amd_ffd_refine_jacobian_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0],
+                                                                       prm.spacing[1], prm.spacing[2], prm.levels));
+        lm.weight = lambda;
+        lm.m = lmh->m;
+        lm.A = have_A ? A : NULL;
+        lm.d_rec = (double *)at;
+        lm.d_GL = (double *)(at + SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES);
+        lm.d_work = lm.d_GL + 3 * grid_voxels(lv[0].gx, lv[0].gy, lv[0].gz);
+        x.lm = &lm;
+    }
+    if (penalty || lmh)                                      /* the MI driver's share of the larger buffer */
         work_bytes = src ? ffd_channels_base_bytes(ox, oy, oz, prm.spacing)
                          : sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
                                                                prm.spacing[2], prm.levels);
+    if (penalty) {                                           /* behind everything the MI driver lays out (channels:
+                                                                behind the lattices) */
         jac.weight = jacobian;
         jac.ref = ref;
         jac.d_rec = (double *)(w + work_bytes);
@@ -859,13 +1213,19 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                                           stream))
                 return SIFT3D_FAILURE;
         }
+        if (lmh) {                                           /* this level's landmarks: P, Q times 0.5^l, in cell order */
+            lmh->up = ldexp(1.0, l);
+            lm.scale = 2.0 * ldexp(1.0, 2 * l);
+            if (ffd_lm_prepare(lmh, &lm, v->gx, v->gy, v->gz, prm.spacing, ldexp(1.0, -l), stream))
+                return SIFT3D_FAILURE;
+        }
         if (ffd_evaluate(what, &x, v, have_A ? A : NULL, c, g, &rec))
             return SIFT3D_FAILURE;
         if (ms)
             ms->sim = ms->sim_trial;
-        ffd_trail(result, &rec, prm.bending, jacobian, penalty, s, 1, l);
+        ffd_trail(result, &rec, prm.bending, jacobian, penalty, lmh, lm.n, s, 1, l);
         n_first = rec.h.n;
-        E = ffd_cost(&rec, prm.bending, jacobian);
+        E = ffd_cost(&rec, prm.bending, jacobian, lambda);
         if (!isfinite(E))
             stop = SIFT3D_AMD_FFD_STOP_FAILED;
         else
@@ -890,9 +1250,9 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                     ffd_evaluate(what, &x, v, have_A ? A : NULL, ct, gt, &trial))
                     return SIFT3D_FAILURE;
                 evals++;
-                Et = ffd_cost(&trial, prm.bending, jacobian);
+                Et = ffd_cost(&trial, prm.bending, jacobian, lambda);
                 accept = isfinite(Et) && (double)trial.h.n >= prm.min_overlap * (double)n_first && Et < E;
-                ffd_trail(result, &trial, prm.bending, jacobian, penalty, s, accept, l);
+                ffd_trail(result, &trial, prm.bending, jacobian, penalty, lmh, lm.n, s, accept, l);
                 if (!isfinite(Et) && !(ms && trial.h.n == 0)) {      /* MI: a trial that counts nothing is rejected */
                     stop = SIFT3D_AMD_FFD_STOP_FAILED;
                     break;
@@ -934,7 +1294,7 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
                                  void *stream)
 {
     return ffd_refine("sift3d_amd_ffd_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL, 0.0, 1.0, NULL, NULL, 0);
+                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL, 0.0, 1.0, NULL, NULL, 0, NULL);
 }
 
 int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -943,7 +1303,7 @@ int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz
                                         void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     return ffd_refine("sift3d_amd_ffd_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL, 0.0, 1.0, NULL, NULL, 0);
+                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL, 0.0, 1.0, NULL, NULL, 0, NULL);
 }
 
 int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -965,7 +1325,7 @@ int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, co
     ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
     *mi_out = ms.sim;
     rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, &ms, 0.0, 1.0, NULL, NULL, 0);
+                    d_WF, d_WM, &ms, 0.0, 1.0, NULL, NULL, 0, NULL);
     *mi_out = ms.sim;
     return rc;
 }
@@ -1025,7 +1385,77 @@ int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int 
     if (mi_out)
         *mi_out = ms.sim;
     rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty, NULL, 0);
+                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty, NULL, 0, NULL);
+    if (mi_out)
+        *mi_out = ms.sim;
+    return rc;
+}
+
+/* ---- the landmarks driver ("FFD landmarks") ---- */
+
+/* the Jacobian driver's (padded to 16), then the landmark record, GL on the finest lattice and the landmarks' work for
+ * the finest lattice (which cover every coarser level's) */
+size_t sift3d_amd_ffd_refine_landmarks_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz, int dx, int dy, int dz,
+                                                  int levels, int m)
+{
+    const size_t jac = sift3d_amd_ffd_refine_jacobian_work_bytes(ox, oy, oz, nx, ny, nz, dx, dy, dz, levels);
+    const int gx = sift3d_amd_ffd_lattice_dim(ox, dx), gy = sift3d_amd_ffd_lattice_dim(oy, dy);
+    const int gz = sift3d_amd_ffd_lattice_dim(oz, dz);
+    const size_t lm = jac ? sift3d_amd_ffd_landmarks_work_bytes(m, gx, gy, gz) : 0;
+    if (!lm)
+        return 0;
+    return pad16(jac) + SIFT3D_AMD_FFD_LANDMARKS_RECORD_BYTES + 3 * grid_voxels(gx, gy, gz) * sizeof(double) + lm;
+}
+
+int sift3d_amd_ffd_refine_landmarks_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                           int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
+                                           sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
+                                           void *d_work, void *stream, const float *d_WF, const float *d_WM, int bins,
+                                           float lo_f, float hi_f, float lo_m, float hi_m,
+                                           sift3d_amd_similarity *mi_out, double jacobian,
+                                           sift3d_amd_ffd_penalty *penalty, const double *P, const double *Q,
+                                           const double *w, int m, double landmark_weight,
+                                           sift3d_amd_ffd_landmark_term *landmarks_out)
+{
+    static const char what[] = "sift3d_amd_ffd_refine_landmarks_device";
+    ffd_lm_host h = { P, Q, w, m, landmark_weight, landmarks_out, 1.0, NULL, NULL, NULL, NULL };
+    sift3d_amd_ffd_refine_params prm;
+    mi_state ms;
+    double ref = 1.0;
+    int rc;
+    if (!landmarks_out || (bins != 0 && !mi_out))
+        return refuse(what, "NULL argument");
+    if (!isfinite(jacobian) || jacobian < 0)
+        return refuse(what, "the Jacobian weight must be finite and not negative");
+    if (jacobian != 0 && !penalty)
+        return refuse(what, "a Jacobian weight needs the penalty array");
+    if (!isfinite(landmark_weight) || landmark_weight < 0)
+        return refuse(what, "the landmark weight must be finite and not negative");
+    if (check_landmarks(what, P, Q, w, m) || (penalty && ffd_jacobian_ref(what, A_in, &ref)))
+        return SIFT3D_FAILURE;
+    if (params)
+        prm = *params;
+    else
+        sift3d_amd_ffd_refine_default_params(&prm);
+    if (check_dims(what, ox, oy, oz))                        /* what the staging's size is made of */
+        return SIFT3D_FAILURE;
+    if (!ffd_params_ok(&prm))
+        return refuse(what, "a parameter is out of range");
+    ms.bins = bins;
+    ms.lo_f = lo_f; ms.hi_f = hi_f;
+    ms.lo_m = lo_m; ms.hi_m = hi_m;
+    ms.sim.n = 0;
+    ms.sim.msd = ms.sim.ncc = ms.sim.mi = ms.sim.nmi = NAN;
+    ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
+    if (mi_out)
+        *mi_out = ms.sim;
+    if (ffd_lm_host_alloc(what, &h, grid_voxels(sift3d_amd_ffd_lattice_dim(ox, prm.spacing[0]) - 3,
+                                                sift3d_amd_ffd_lattice_dim(oy, prm.spacing[1]) - 3,
+                                                sift3d_amd_ffd_lattice_dim(oz, prm.spacing[2]) - 3)))
+        return SIFT3D_FAILURE;
+    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, &prm, result, d_lattice, d_field, d_work, stream, 1,
+                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty, NULL, 0, &h);
+    free(h.rows);                                            /* every copy from it was staged when its call returned */
     if (mi_out)
         *mi_out = ms.sim;
     return rc;
@@ -1107,5 +1537,5 @@ int sift3d_amd_ffd_refine_channels_device(const sift3d_amd_ffd_level *level, int
     }
     return ffd_refine(what, level->d_F, level->ox, level->oy, level->oz, level->d_M, level->nx, level->ny, level->nz,
                       A_in, &prm, result, d_lattice, d_field, d_work, stream, 1, level->d_WF, level->d_WM, NULL,
-                      jacobian, ref, penalty, level, nc);
+                      jacobian, ref, penalty, level, nc, NULL);
 }

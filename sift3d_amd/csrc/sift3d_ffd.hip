@@ -27,7 +27,11 @@
 #include "sift3d_resample.h"
 #include "sift3d_parzen.h"
 #include "sift3d_ffd_jac.h"
+#include "sift3d_ffd_landmarks.h"
 
+// sift3d_ffd_landmarks.hip
+extern "C" int sift3d_ffd_landmarks_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy,
+                                           int dz, const sift3d_ffd_lm *lm, int adjoint, double *d_r, void *stream);
 // sift3d_jacobian_penalty.hip
 extern "C" int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
                                               double *d_rec, double *d_S, double *d_work, void *stream);
@@ -581,6 +585,32 @@ __global__ __launch_bounds__(256) void k_ffd_combine_jac(const FfdCombineArgs s,
         s.part[blockIdx.x] = r;
 }
 
+// The combine with the landmark term (header, "FFD landmarks"): grad = (float)(base + (lk / Omega) * GL), base being
+// k_ffd_combine's expression (JAC: k_ffd_combine_jac's), lk = lambda * (2 * 4^l) made on the host and Omega read from
+// the landmark record; Omega == 0 adds no term.  A kernel of its own: the evaluations without landmarks launch
+// k_ffd_combine or k_ffd_combine_jac as before.
+template <bool JAC>
+__global__ __launch_bounds__(256) void k_ffd_combine_lm(const FfdCombineArgs s, const double *GJ, double jn,
+                                                        const double *GL, const double *lrec, double lk)
+{
+    __shared__ double slot[4];
+    const double n = (double)reinterpret_cast<const unsigned long long *>(s.rec)[0];
+    const double two_n = s.scale / n;
+    const double omega = lrec[2], f = lk / omega;
+    double mx = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.total; i += (size_t)gridDim.x * 256) {
+        double b = two_n * s.Gc[i] + s.bending * s.dR[i];
+        if (JAC)
+            b = b + jn * GJ[i];
+        const float g = (float)(omega == 0.0 ? b : b + f * GL[i]);
+        s.grad[i] = g;
+        mx = fmax(mx, (double)fabsf(g));
+    }
+    const double r = workgroup_reduce<Max>(mx, slot);
+    if (threadIdx.x == 0)
+        s.part[blockIdx.x] = r;
+}
+
 __global__ __launch_bounds__(256) void k_ffd_step(const float *c, const float *grad, float a, float *out, size_t n)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
@@ -664,8 +694,10 @@ extern "C" int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int g
 // term); the MI driver runs FFD_BEND_VALUE per evaluation and the other three only where a step starts.
 // FFD_JAC_VALUE, FFD_JAC_GRAD (with a penalty only; one of the two): the penalty's record from the field, alone or with S
 // and its adjoint GJ.  They run after the image term, whose force buffer S takes over once Gc is formed.
+// FFD_LM_VALUE, FFD_LM_GRAD (with landmarks only; one of the two): the landmark record from the lattice, alone or with
+// the adjoint GL.
 enum { FFD_IMAGE = 1, FFD_BEND_VALUE = 2, FFD_BEND_GRAD = 4, FFD_COMBINE = 8, FFD_ALL = 15, FFD_JAC_VALUE = 16,
-       FFD_JAC_GRAD = 32 };
+       FFD_JAC_GRAD = 32, FFD_LM_VALUE = 64, FFD_LM_GRAD = 128 };
 
 // the adjoint of the spline on src [3][oz][oy][ox] -> dst [3][gz][gy][gx]: z, y, x
 static int ffd_adjoint_passes(const double *src, double *t1, double *t2, double *dst, const float *d_w, int ox, int oy,
@@ -689,7 +721,9 @@ static int ffd_adjoint_passes(const double *src, double *t1, double *t2, double 
 // force needs beside the MSD force's arguments (NULL: the MSD).  jac: the penalty's buffers (NULL: none); the combine
 // takes its term when jac->weight > 0.  nc: 0 from the single-channel entries, which launch k_ffd_force or
 // k_ffd_mi_force as before; >= 1: d_F and d_M are stacks of nc channels and k_ffd_force_channels runs (mi == NULL).
-static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const sift3d_ffd_jac *jac, int nc,
+// lm: the landmark term's buffers (NULL: none); the combine takes its term when lm->weight > 0.
+static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const sift3d_ffd_jac *jac,
+                              const sift3d_ffd_lm *lm, int nc,
                               const float *d_F, int ox, int oy,
                               int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
                               const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
@@ -742,6 +776,9 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
             (with_grad && ffd_adjoint_passes(force, t1, t2, jac->d_GJ, d_w, ox, oy, oz, gx, gy, gz, dx, dy, dz, st)))
             return SIFT3D_FAILURE;
     }
+    if (lm && (parts & (FFD_LM_VALUE | FFD_LM_GRAD)) &&
+        sift3d_ffd_landmarks_launch(fn, d_lat, gx, gy, gz, dx, dy, dz, lm, (parts & FFD_LM_GRAD) != 0, nullptr, stream))
+        return SIFT3D_FAILURE;
     // the bending energy and its gradient
     FfdBendArgs b;
     for (int i = 0; i < 27; i++)
@@ -766,7 +803,14 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
     if (parts & FFD_COMBINE) {
         const FfdCombineArgs c = {d_rec, Gc, dR, d_grad, part, bending, mi ? 1.0 : 2.0, 3 * cvox};
         const unsigned cgrid = flat_grid(3 * cvox, FFD_GRID);
-        if (jac && jac->weight > 0.0)
+        const bool with_jac = jac && jac->weight > 0.0;
+        if (lm && lm->weight > 0.0) {
+            void (*k)(const FfdCombineArgs, const double *, double, const double *, const double *, double) =
+                with_jac ? k_ffd_combine_lm<true> : k_ffd_combine_lm<false>;
+            hipLaunchKernelGGL(k, dim3(cgrid), dim3(256), 0, st, c, with_jac ? (const double *)jac->d_GJ : nullptr,
+                               with_jac ? jac->weight / (double)vox : 0.0, (const double *)lm->d_GL,
+                               (const double *)lm->d_rec, lm->weight * lm->scale);
+        } else if (with_jac)
             hipLaunchKernelGGL(k_ffd_combine_jac, dim3(cgrid), dim3(256), 0, st, c, (const double *)jac->d_GJ,
                                jac->weight / (double)vox);
         else
@@ -784,8 +828,27 @@ static unsigned ffd_jac_parts(const sift3d_ffd_jac *jac, bool gradient)
     return !jac ? 0u : gradient && jac->weight > 0.0 ? FFD_JAC_GRAD : FFD_JAC_VALUE;
 }
 
+// the landmark term's parts, as the penalty's
+static unsigned ffd_lm_parts(const sift3d_ffd_lm *lm, bool gradient)
+{
+    return !lm ? 0u : gradient && lm->weight > 0.0 ? FFD_LM_GRAD : FFD_LM_VALUE;
+}
+
 // The MSD evaluation; d_F == NULL: the bending entry, no image term and no combined gradient.  jac: the Jacobian
-// penalty of the field, or NULL.
+// penalty of the field, or NULL.  lm: the landmark term, or NULL.
+extern "C" int sift3d_ffd_evaluate_lm_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
+                                             const float *d_M, int nx, int ny, int nz, const float *d_field,
+                                             const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                                             const float *d_w, const double *stencils, double bending, double *d_rec,
+                                             float *d_grad, double *d_work, void *stream, const float *d_WF,
+                                             const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm)
+{
+    return ffd_evaluate_parts(fn, d_F ? FFD_ALL | ffd_jac_parts(jac, true) | ffd_lm_parts(lm, true)
+                                      : FFD_BEND_VALUE | FFD_BEND_GRAD,
+                              nullptr, jac, lm, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy,
+                              dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+}
+
 extern "C" int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
                                               const float *d_M, int nx, int ny, int nz, const float *d_field,
                                               const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
@@ -793,9 +856,8 @@ extern "C" int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, 
                                               float *d_grad, double *d_work, void *stream, const float *d_WF,
                                               const float *d_WM, const sift3d_ffd_jac *jac)
 {
-    return ffd_evaluate_parts(fn, d_F ? FFD_ALL | ffd_jac_parts(jac, true) : FFD_BEND_VALUE | FFD_BEND_GRAD, nullptr,
-                              jac, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w,
-                              stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+    return sift3d_ffd_evaluate_lm_launch(fn, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
+                                         d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM, jac, nullptr);
 }
 
 // The evaluation of a stack of nc >= 1 channels (header, "Multi-channel free-form deformation"): the MSD evaluation
@@ -808,7 +870,7 @@ extern "C" int sift3d_ffd_evaluate_channels_launch(const char *fn, const float *
                                                    void *stream, const float *d_WF, const float *d_WM,
                                                    const sift3d_ffd_jac *jac)
 {
-    return ffd_evaluate_parts(fn, FFD_ALL | ffd_jac_parts(jac, true), nullptr, jac, nc, d_F, ox, oy, oz, d_M, nx, ny, nz,
+    return ffd_evaluate_parts(fn, FFD_ALL | ffd_jac_parts(jac, true), nullptr, jac, nullptr, nc, d_F, ox, oy, oz, d_M, nx, ny, nz,
                               d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work,
                               stream, d_WF, d_WM);
 }
@@ -827,6 +889,22 @@ extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int 
 // beside the field and the histogram; the image arguments are not read).  gradient != 0: the force of psi from d_W, its
 // adjoint, the bending gradient from the D of the last value pass, and the combined gradient with the factor 1 / n.
 // jac: the Jacobian penalty of the field, or NULL: its record with either of value and gradient, S and GJ with gradient.
+// lm: the landmark term, or NULL: its record with either, GL with gradient.
+extern "C" int sift3d_ffd_mi_lm_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy,
+                                       int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
+                                       const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
+                                       const float *d_w, const double *stencils, double bending, int bins, float lo_f,
+                                       float s_f, float lo_m, float hi_m, const double *d_W, double *d_rec,
+                                       float *d_grad, double *d_work, void *stream, const float *d_WF,
+                                       const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm)
+{
+    const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
+    const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u) |
+                           ffd_jac_parts(jac, gradient != 0) | ffd_lm_parts(lm, gradient != 0);
+    return ffd_evaluate_parts(fn, parts, &mi, jac, lm, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx,
+                              dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+}
+
 extern "C" int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy,
                                         int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
                                         const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
@@ -835,11 +913,9 @@ extern "C" int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient,
                                         float *d_grad, double *d_work, void *stream, const float *d_WF,
                                         const float *d_WM, const sift3d_ffd_jac *jac)
 {
-    const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
-    const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u) |
-                           ffd_jac_parts(jac, gradient != 0);
-    return ffd_evaluate_parts(fn, parts, &mi, jac, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy,
-                              dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
+    return sift3d_ffd_mi_lm_launch(fn, value, gradient, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx,
+                                   dy, dz, d_w, stencils, bending, bins, lo_f, s_f, lo_m, hi_m, d_W, d_rec, d_grad, d_work,
+                                   stream, d_WF, d_WM, jac, nullptr);
 }
 
 extern "C" int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,

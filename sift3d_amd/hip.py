@@ -102,6 +102,14 @@ class FFDPenalty(C.Structure):                             # sift3d_amd_ffd_pena
 JACOBIAN_PENALTY_RECORD_BYTES = 32
 
 
+class FFDLandmarkTerm(C.Structure):                        # sift3d_amd_ffd_landmark_term
+    _fields_ = [("L", C.c_double), ("rmax", C.c_double), ("counted", C.c_uint64)]
+
+
+FFD_MAX_LANDMARKS = 65536                                  # checked against the library when it is bound (lib())
+FFD_LANDMARKS_RECORD_BYTES = 32
+
+
 class FFDLevel(C.Structure):                               # sift3d_amd_ffd_level
     _fields_ = [("d_F", C.c_void_p), ("ox", C.c_int), ("oy", C.c_int), ("oz", C.c_int), ("d_M", C.c_void_p),
                 ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("d_WF", C.c_void_p), ("d_WM", C.c_void_p)]
@@ -297,6 +305,24 @@ def lib():
                                                             C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
                                                             C.POINTER(FFDRefineResult), vp, vp, vp, vp, C.c_double,
                                                             C.POINTER(FFDPenalty)]),
+        "sift3d_amd_ffd_landmarks_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_hip_ffd_points": (C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_double), vp, C.c_int, vp, vp]),
+        "sift3d_amd_ffd_landmarks_work_bytes": (C.c_size_t, [C.c_int] * 4),
+        "sift3d_hip_ffd_landmarks": (C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_double), vp, vp, vp, C.c_int, vp, vp,
+                                                                     vp, vp, vp]),
+        "sift3d_amd_ffd_evaluate_landmarks_bytes": (C.c_size_t, [C.c_int] * 8),
+        "sift3d_hip_ffd_evaluate_landmarks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
+                                              + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp,
+                                                                 vp, vp, C.c_double, vp, vp, vp, vp, C.c_int,
+                                                                 C.c_double, vp]),
+        "sift3d_amd_ffd_refine_landmarks_work_bytes": (C.c_size_t, [C.c_int] * 11),
+        "sift3d_amd_ffd_refine_landmarks_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                                             C.c_int, C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
+                                                             C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp,
+                                                             C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                             C.POINTER(Similarity), C.c_double,
+                                                             C.POINTER(FFDPenalty), vp, vp, vp, C.c_int, C.c_double,
+                                                             C.POINTER(FFDLandmarkTerm)]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -361,6 +387,11 @@ def lib():
     got = tuple(L.sift3d_amd_ffd_level_struct_bytes(k) for k in range(7))
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the FFD level as %s, the library has %s" % (want, got))
+    want = (C.sizeof(FFDLandmarkTerm), FFD_LANDMARKS_RECORD_BYTES, FFD_MAX_LANDMARKS,
+            AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS)
+    got = tuple(L.sift3d_amd_ffd_landmarks_struct_bytes(k) for k in range(4))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the FFD landmark layouts as %s, the library has %s" % (want, got))
     _bound = L
     return L
 
@@ -1504,6 +1535,162 @@ def ffd_refine_jacobian(F, M, jacobian, bins=0, range_f=(0.0, 1.0), range_m=(0.0
            "sift3d_amd_ffd_refine_jacobian_device")
     penalty = [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
     return res, lattice, field, (sim if bins else None), penalty
+
+
+# ---- points and landmarks ("FFD landmarks") ----
+def _points(a, what, name):
+    """an n x 3 array as contiguous float64 on the host"""
+    a = np.ascontiguousarray(a, np.float64)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s: %s must be n x 3 (x, y, z)" % (what, name))
+    return a
+
+
+def ffd_landmark_arrays(P, Q, w, what):
+    """(P, Q, w or None) as the entries take them; ValueError on what they refuse of the landmarks"""
+    P, Q = _points(P, what, "the fixed landmarks"), _points(Q, what, "the moving landmarks")
+    if len(P) != len(Q) or not 1 <= len(P) <= FFD_MAX_LANDMARKS:
+        raise ValueError("%s: the two point lists must have one length in [1, %d]" % (what, FFD_MAX_LANDMARKS))
+    if not np.isfinite(Q).all():
+        raise ValueError("%s: the moving landmarks must be finite" % what)
+    if w is not None:
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (len(P),) or not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("%s: the landmark weights must be n finite values that are not negative" % what)
+    return P, Q, w
+
+
+def ffd_points(lattice, spacing, points, A=None):
+    """T [m, 3] float64 CUDA tensor: the points [m, 3] (float64, x y z in voxels of the fixed grid; a CUDA tensor is
+    used as it is, an array is uploaded) through the lattice and the pull map A (sift3d_hip_ffd_points), on torch's
+    current stream; three NaNs where a point is outside the lattice's support."""
+    import torch
+    what = "ffd_points"
+    gx, gy, gz = _ffd_lattice(lattice, what)
+    dx, dy, dz = ffd_spacing(spacing, what)
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(_points(points, what, "points")).to(lattice.device)
+    _tensor(points, what + ": points must be a contiguous float64 CUDA tensor [m, 3] on the lattice's device",
+            dims=(2,), device=lattice.device, dtype="float64")
+    if points.shape[1] != 3 or points.shape[0] < 1:
+        raise ValueError(what + ": points must be [m, 3] with m >= 1")
+    a, ap = _ffd_A(A, what)
+    T = torch.empty_like(points)
+    _check(lib().sift3d_hip_ffd_points(lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap, points.data_ptr(),
+                                       int(points.shape[0]), T.data_ptr(), current_stream()), "sift3d_hip_ffd_points")
+    return T
+
+
+def ffd_landmarks_record(record):
+    """(counted, S, Omega, rmax) of a landmark record (a CUDA tensor of FFD_LANDMARKS_RECORD_BYTES); waits for the
+    stream"""
+    import torch
+    raw = record.view(torch.uint8)[:FFD_LANDMARKS_RECORD_BYTES].cpu().numpy()
+    v = raw[8:32].view(np.float64)
+    return int(raw[:8].view(np.uint64)[0]), float(v[0]), float(v[1]), float(v[2])
+
+
+def ffd_landmarks(lattice, spacing, P, Q, w=None, A=None, residuals=True, gradient=True, work=None):
+    """sift3d_hip_ffd_landmarks on torch's current stream: lattice a CUDA float32 tensor [3, gz, gy, gx]; P, Q n x 3
+    host arrays (fixed and moving voxels, xyz), w n weights or None.  Returns (record: int64 CUDA tensor, read by
+    ffd_landmarks_record; r: float64 CUDA tensor [n, 3] or None; GL: float64 CUDA tensor [3, gz, gy, gx] or None)."""
+    import torch
+    what = "ffd_landmarks"
+    gx, gy, gz = _ffd_lattice(lattice, what)
+    dx, dy, dz = ffd_spacing(spacing, what)
+    P, Q, w = ffd_landmark_arrays(P, Q, w, what)
+    m = len(P)
+    a, ap = _ffd_A(A, what)
+    work = _work(work, (lib().sift3d_amd_ffd_landmarks_work_bytes(m, gx, gy, gz) + 3) // 4, lattice, what)
+    record = torch.empty(FFD_LANDMARKS_RECORD_BYTES // 8, dtype=torch.int64, device=lattice.device)
+    r = torch.empty((m, 3), dtype=torch.float64, device=lattice.device) if residuals else None
+    GL = torch.empty(tuple(lattice.shape), dtype=torch.float64, device=lattice.device) if gradient else None
+    _check(lib().sift3d_hip_ffd_landmarks(lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap, P.ctypes.data, Q.ctypes.data,
+                                          None if w is None else w.ctypes.data, m, work.data_ptr(), record.data_ptr(),
+                                          None if r is None else r.data_ptr(), None if GL is None else GL.data_ptr(),
+                                          current_stream()), "sift3d_hip_ffd_landmarks")
+    return record, r, GL
+
+
+def ffd_evaluate_landmarks(F, M, lattice, spacing, P, Q, w=None, landmark_weight=0.0, A=None, bending=0.0, jacobian=None,
+                           mask_fixed=None, mask_moving=None):
+    """One evaluation of the FFD cost with the landmark term (sift3d_hip_ffd_evaluate_landmarks) on torch's current
+    stream.  jacobian: None evaluates without the Jacobian penalty, a weight >= 0 with it.  Returns (record, grad,
+    field, lm, jac): ffd_evaluate's three, then the landmarks' buffer (float64 CUDA tensor: the record in its first
+    four words, read by ffd_landmarks_record, then GL [3, gz, gy, gx]) and the penalty's (the same with GJ) or None."""
+    import torch
+    what = "ffd_evaluate_landmarks"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    gx, gy, gz = _ffd_lattice(lattice, what)
+    _same_device(what, F, M, lattice)
+    dx, dy, dz = ffd_spacing(spacing, what)
+    P, Q, w = ffd_landmark_arrays(P, Q, w, what)
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    a, ap = _ffd_A(A, what)
+    record = _ffd_record_tensor(lattice)
+    grad = torch.empty_like(lattice)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    work = _work(None, (lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz) + 3) // 4, F, what)
+    size = lib().sift3d_amd_ffd_evaluate_landmarks_bytes
+    lm = torch.zeros(size(0, len(P), ox, oy, oz, dx, dy, dz) // 8 + 1, dtype=torch.float64, device=F.device)
+    jac = None if jacobian is None else \
+        torch.zeros(size(1, len(P), ox, oy, oz, dx, dy, dz) // 8 + 1, dtype=torch.float64, device=F.device)
+    _check(lib().sift3d_hip_ffd_evaluate_landmarks(
+        F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap,
+        float(bending), field.data_ptr(), record.data_ptr(), grad.data_ptr(), work.data_ptr(), current_stream(), *masks,
+        0.0 if jacobian is None else float(jacobian), None if jac is None else jac.data_ptr(), P.ctypes.data,
+        Q.ctypes.data, None if w is None else w.ctypes.data, len(P), float(landmark_weight), lm.data_ptr()),
+        "sift3d_hip_ffd_evaluate_landmarks")
+    return record, grad, field, lm, jac
+
+
+def ffd_refine_landmarks(F, M, P, Q, w=None, landmark_weight=0.0, jacobian=None, bins=0, range_f=(0.0, 1.0),
+                         range_m=(0.0, 1.0), A=None, params=None, work=None, mask_fixed=None, mask_moving=None):
+    """sift3d_amd_ffd_refine_landmarks_device on torch CUDA float32 contiguous volumes, on torch's current stream: the
+    FFD drivers with the landmark term of weight `landmark_weight` on the landmarks P, Q (n x 3 host arrays, fixed and
+    moving voxels) with weights w (None: all 1).  jacobian: None runs without the Jacobian penalty, a weight >= 0 with
+    it; bins == 0: the MSD, else the mutual information as ffd_mi_refine.  Returns (FFDRefineResult, lattice, field,
+    Similarity or None, penalty: one (P, rmin, nonpos) per trail entry or None, landmarks: one (L, rmax, counted) per
+    trail entry)."""
+    import torch
+    what = "ffd_refine_landmarks"
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M)
+    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    P, Q, w = ffd_landmark_arrays(P, Q, w, what)
+    a, ap = _ffd_A(A, what)
+    bins = _parzen_bins(bins, what) if bins else 0
+    p = params if params is not None else ffd_refine_params()
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    d = tuple(p.spacing)
+    need = lib().sift3d_amd_ffd_refine_landmarks_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels, len(P))
+    if need == 0:
+        raise ValueError(what + ": levels must be in [1, %d] and the spacing in [1, %d]"
+                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
+    work = _work(work, (need + 3) // 4, F, what)
+    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
+    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    res = FFDRefineResult()
+    sim = Similarity()
+    pen = None if jacobian is None else (FFDPenalty * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
+    terms = (FFDLandmarkTerm * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
+    ranges = _parzen_ranges(range_f, range_m) if bins else (0.0, 1.0, 0.0, 1.0)
+    _check(lib().sift3d_amd_ffd_refine_landmarks_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap,
+                                                        C.byref(p), C.byref(res), lattice.data_ptr(), field.data_ptr(),
+                                                        work.data_ptr(), current_stream(), *masks, bins, *ranges,
+                                                        C.byref(sim), 0.0 if jacobian is None else float(jacobian), pen,
+                                                        P.ctypes.data, Q.ctypes.data,
+                                                        None if w is None else w.ctypes.data, len(P),
+                                                        float(landmark_weight), terms),
+           "sift3d_amd_ffd_refine_landmarks_device")
+    penalty = None if pen is None else [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
+    landmarks = [(t.L, t.rmax, int(t.counted)) for t in terms[:res.evaluations]]
+    return res, lattice, field, (sim if bins else None), penalty, landmarks
 
 
 # ---- multi-channel free-form deformation ("Multi-channel free-form deformation") ----
