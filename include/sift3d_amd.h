@@ -2095,6 +2095,14 @@ SIFT3D_AMD_API int
 sift3d_hip_orient_tab_part(const sift3d_hip_level *d_levels, int nlevels, int lv_lo, int lv_hi,
                            const sift3d_hip_cand *d_cand, uint32_t first, uint32_t n, double corner_thresh,
                            float *d_R, int32_t *d_keep, void *d_tab, uint32_t max_cand, int slot, void *stream);
+/* A LIMIT of all three entries: the serial sums queue a window's voxels with their window-relative x and y in 10
+ * bits each, so the clipped window box -- max(floor(c - rad / u), 1) .. min(ceil(c + rad / u), n - 2) with rad =
+ * 4.5 sd (sift.c:93-99, 936, 1125) -- may span at most 1024 voxels in x and in y; beyond that the orientations are
+ * silently wrong, and from 2048 on the kernel can read outside the box.  The entries do not check it (they see
+ * device memory only).  sift3d_hip_orient_window_fits() is the check on the level's numbers alone: 0 when
+ * min(n - 2, 2 ceil(4.5 sd / u) + 1) exceeds 1023 on x or y, else 1.  The detector and the slab driver refuse such
+ * a level with a message instead of orienting its candidates. */
+SIFT3D_AMD_API int sift3d_hip_orient_window_fits(int nx, int ny, double ux, double uy, double sd);
 
 typedef struct {
     float R[9];

@@ -16,6 +16,8 @@ Fixture families:
                candidate list, keypoints (R, sd, stale strength), descriptors, sort order
   g5_*         larger volumes: candidate/keypoint lists, R, descriptor subset + row sums
   g6_abi       the names the reference library exports and its CLI imports (JSON)
+  g7_*         describe on caller-made keypoint lists
+  g8_*         assign_eig_ori on caller-made candidate lists: status, conf, R per entry
 """
 import argparse
 import hashlib
@@ -478,6 +480,127 @@ def g7_all():
     return out
 
 
+def noise_volume(n, seed, blur_sigma=0.0):
+    """White PCG64 noise, optionally blurred with the oracle's own blur (tests/util.golden_input restates this)."""
+    nx, ny, nz = n
+    vol = np.random.Generator(np.random.PCG64(seed)).standard_normal((nz, ny, nx)).astype(np.float32)
+    return so.blur(vol, so.gauss_taps(blur_sigma)) if blur_sigma else vol
+
+
+def _g8_voxels(rng, dims, n):
+    """n random voxels with 1 <= x <= nx - 2 (and y, z alike): what the extrema stage guarantees."""
+    return np.stack([rng.integers(1, d - 1, n) for d in dims], 1)
+
+
+def _g8_faces(rng, dims, per_face=8):
+    """Voxels on the six face-adjacent layers (x = 1, x = nx - 2, ...) and the eight corners (1, 1, 1) ...
+    (nx - 2, ny - 2, nz - 2)."""
+    out = []
+    for ax in range(3):
+        for v in (1, dims[ax] - 2):
+            p = _g8_voxels(rng, dims, per_face)
+            p[:, ax] = v
+            out.append(p)
+    out.append(np.array([[x, y, z] for z in (1, dims[2] - 2) for y in (1, dims[1] - 2) for x in (1, dims[0] - 2)]))
+    return np.concatenate(out)
+
+
+def _g8_survey_lists(p, rng):
+    """Every level s = -1 .. K + 1 of octaves 0 and 1 at the level's own sd: 150 / 40 random voxels per level, and
+    the face layers and corners on the finest and the coarsest level."""
+    K = 3
+    os_, xyz, sd = [], [], []
+    for o, n in ((0, 150), (1, 40)):
+        dims = _level_dims(p, o)
+        for s in range(-1, K + 2):
+            v = _g8_voxels(rng, dims, n)
+            if (o, s) in ((0, -1), (1, K + 1)):
+                v = np.concatenate([v, _g8_faces(rng, dims)])
+            os_ += [(o, s)] * len(v)
+            xyz.append(v)
+            sd += [_level_sd(p, o, s)] * len(v)
+    return {"list": (np.array(os_), np.concatenate(xyz), np.array(sd), 1.0)}
+
+
+def _g8_sd_lists(sds, n=300):
+    """The same n voxels of level (0, 0) with each of the scales `sds` (grouped by sd)."""
+    def make(p, rng):
+        v = _g8_voxels(rng, _level_dims(p, 0), n)
+        return {"list": (np.array([(0, 0)] * (n * len(sds))), np.concatenate([v] * len(sds)),
+                         np.repeat(np.array(sds, np.float64), n), 1.0)}
+    return make
+
+
+def _g8_faint_lists(p, rng):
+    """The same 300 voxels of level (0, 0) at sd 1.6 with the LEVEL multiplied by 1, 1e-5 and 1e-6 (sift.c:997)."""
+    v = _g8_voxels(rng, _level_dims(p, 0), 300)
+    return {name: (np.array([(0, 0)] * len(v)), v, np.full(len(v), 1.6), f)
+            for name, f in (("x1", 1.0), ("x1e-5", 1e-5), ("x1e-6", 1e-6))}
+
+
+def g8_list(name, vol, input_spec, make_lists, units=(1, 1, 1)):
+    """assign_eig_ori (sift.c:926-1085) on CALLER-MADE candidate lists of the reference's own pyramid of `vol`:
+    make_lists(probe, rng) -> {case: (os (n, 2), xyz (n, 3), sd (n,), level scale)}.  Stored per case: the list, the
+    reference's status (0 success, 1 REJECT), conf and R; and conf_maxdiff, the largest |conf_oracle - conf_ref| over
+    the entries both accept (the oracle's eigen routine stands in for LAPACK dsyevd)."""
+    p = refprobe.Probe()
+    assert p.detect(vol, units) == 0
+    o = so.Oracle()
+    assert o.detect(vol, units) == 0
+    d = {"units": np.array(units, np.float64), "dims": np.array(vol.shape[::-1], np.int32),
+         "input_digest": np.array(digest(vol)), "num_octaves": np.array(p.num_octaves),
+         "input_spec": np.array(json.dumps(input_spec))}
+    rng = np.random.Generator(np.random.PCG64(int(hashlib.sha1(name.encode()).hexdigest()[:8], 16)))
+    lists = make_lists(p, rng)
+    info, maxdiff = {}, 0.0
+    for case, (os_, xyz, sd, scale) in lists.items():
+        os_ = np.asarray(os_, np.int32).reshape(-1, 2)
+        xyz = np.asarray(xyz, np.int32).reshape(-1, 3)
+        sd = np.asarray(sd, np.float64)
+        status, conf, R = p.orient(os_, xyz, sd, scale)
+        assert set(np.unique(status)) <= {0, 1}, "assign_eig_ori failed"
+        for k, v in (("os", os_), ("xyz", xyz), ("sd", sd), ("scale", np.array(scale, np.float32)), ("status", status),
+                     ("conf", conf), ("R", R)):
+            d["%s_%s" % (case, k)] = v
+        # the oracle on its own (bit-identical) levels
+        st_o, cf_o = np.zeros_like(status), np.zeros_like(conf)
+        for key in sorted(set(map(tuple, os_.tolist()))):
+            m = (os_[:, 0] == key[0]) & (os_[:, 1] == key[1])
+            lv, lu, _ = o.level(0, *key)
+            assert digest(lv) == digest(p.level(0, *key)[0])
+            _, _, cf_o[m], st_o[m] = so.orient_conf(lv * np.float32(scale), lu, sd[m], xyz[m])
+        bad = np.nonzero(st_o != status)[0]
+        assert len(bad) == 0, "status differs at %s of %s/%s" % (bad[:8], name, case)
+        ok = status == 0
+        if ok.any():
+            maxdiff = max(maxdiff, float(np.abs(cf_o - conf)[ok].max()))
+        info[case] = dict(n=int(len(os_)), success=int(ok.sum()))
+    d["cases"] = np.array(json.dumps(list(lists)))
+    d["conf_maxdiff"] = np.array(maxdiff)
+    info["conf_maxdiff"] = maxdiff
+    print(name, "conf_maxdiff %.3g" % maxdiff, flush=True)
+    p.close()
+    o.close()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
+    return {name: info}
+
+
+def g8_orient():
+    out = {}
+    out.update(g8_list("g8_survey", so.synth_survey(64), dict(gen="survey", n=64, nblob=200), _g8_survey_lists))
+    out.update(g8_list("g8_aniso", so.synth_survey((70, 50, 41)), dict(gen="survey", n=[70, 50, 41]),
+                       _g8_survey_lists, units=(1.0, 1.5, 0.7)))
+    # sd pairs on either side of the weight LUT's limit (sd / u < 3.07) and of the table's quad capacity
+    out.update(g8_list("g8_scales", so.synth_survey(40), dict(gen="survey", n=40),
+                       _g8_sd_lists((1.5, 1.6, 3.0, 3.2, 4.2, 4.3))))
+    out.update(g8_list("g8_noise", noise_volume((40, 40, 40), 8), dict(gen="noise", n=[40, 40, 40], seed=8),
+                       _g8_sd_lists((1.6, 2.5))))
+    out.update(g8_list("g8_noise_blur", noise_volume((40, 40, 40), 8, 1.5),
+                       dict(gen="noise", n=[40, 40, 40], seed=8, blur_sigma=1.5), _g8_sd_lists((1.6, 2.5))))
+    out.update(g8_list("g8_faint", so.synth_survey(40), dict(gen="survey", n=40), _g8_faint_lists))
+    return out
+
+
 def g6_abi():
     """The link-level contract as data, for machines without the reference: the names the unmodified
     reference library exports (libsift3D_ref.so) and the names its own CLI -- cli/kpSift3D.c compiled unchanged
@@ -533,6 +656,8 @@ def main():
         "g6_abi": g6_abi,
         # describe on caller-made keypoint lists (g7_*)
         "g7": g7_all,
+        # orientation (assign_eig_ori) on caller-made candidate lists (g8_*)
+        "g8": g8_orient,
     }
     if a.big:
         jobs["g5_128"] = lambda: end_to_end(

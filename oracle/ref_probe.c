@@ -245,6 +245,51 @@ PROBE int probe_set_kp(probe_ctx *c, int n, const int *os, const double *xyzsd, 
     return 0;
 }
 
+/* assign_eig_ori (sift.c:926-1085) on CALLER-MADE candidates, after probe_detect has built the pyramid:
+ * entry i is voxel xyz[3i..] of Gaussian level (os[2i], os[2i+1]) with sigma = ori_sig_fctr * sd[i] (sift.c:1125; sd
+ * is an argument so that a list can use scales the level does not have).  status[i] is what the function returned
+ * (SIFT3D_SUCCESS 0, REJECT 1, SIFT3D_FAILURE), conf[i] its corner score, R + 9i its matrix (zeros unless 0).
+ * scale != 1: the function sees a copy of the level with every voxel multiplied by `scale` in float (the
+ * detector normalises its input, sift.c:649, so a faint LEVEL cannot be had by scaling the volume). */
+PROBE int probe_orient(probe_ctx *c, int n, const int *os, const int *xyz, const double *sd, float scale,
+                       int *status, double *conf, float *R)
+{
+    sift3d_mat_rm M;
+    sift3d_image cp;
+    float *buf = NULL;
+    int i, co = -1, cs = 0;
+    if (init_Mat_rm(&M, IM_NDIMS, IM_NDIMS, SIFT3D_FLOAT, SIFT3D_TRUE))
+        return -1;
+    for (i = 0; i < n; i++) {
+        const sift3d_image *im = SIFT3D_PYR_IM_GET(&c->det->gpyr, os[2 * i], os[2 * i + 1]);
+        sift3d_cvec vcenter;
+        if (scale != 1.0f) {
+            if (co != os[2 * i] || cs != os[2 * i + 1]) {
+                size_t k;
+                buf = (float *)realloc(buf, im->size * sizeof(float));
+                for (k = 0; k < im->size; k++)
+                    buf[k] = im->data[k] * scale;
+                cp = *im;
+                cp.data = buf;
+                co = os[2 * i];
+                cs = os[2 * i + 1];
+            }
+            im = &cp;
+        }
+        vcenter.x = (float)(double)xyz[3 * i];
+        vcenter.y = (float)(double)xyz[3 * i + 1];
+        vcenter.z = (float)(double)xyz[3 * i + 2];
+        conf[i] = 0.0;
+        status[i] = assign_eig_ori(im, &vcenter, ori_sig_fctr * sd[i], &M, conf + i);
+        memset(R + 9 * i, 0, 9 * sizeof(float));
+        if (status[i] == SIFT3D_SUCCESS)
+            memcpy(R + 9 * i, M.u.data_float, 9 * sizeof(float));
+    }
+    cleanup_Mat_rm(&M);
+    free(buf);
+    return 0;
+}
+
 PROBE void probe_sort(probe_ctx *c, int limit)
 {
     sift3d_keypoint_store_sort_by_strength(c->kp, limit);

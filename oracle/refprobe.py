@@ -24,6 +24,12 @@ def available():
     return os.path.exists(LIB_PATH)
 
 
+def has_orient():
+    """The library that is there has the probe_orient hook (one built before the hook existed, and not rebuilt
+    since -- `make -C oracle ref` needs the reference sources --, does not)."""
+    return available() and hasattr(lib(), "probe_orient")
+
+
 _libs = {}
 
 
@@ -49,6 +55,8 @@ def lib(cuboid=False):
         L.probe_describe.argtypes = [C.c_void_p]
         L.probe_sort.argtypes = [C.c_void_p, C.c_int]
         L.probe_set_kp.argtypes = [C.c_void_p, C.c_int, _i32p, _f64p, _f32p]
+        if hasattr(L, "probe_orient"):      # (a library built from an older ref_probe.c lacks the hook)
+            L.probe_orient.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_float, _i32p, _f64p, _f32p]
         for n in ("probe_num_octaves", "probe_num_cand", "probe_num_kp"):
             getattr(L, n).argtypes = [C.c_void_p]
         L.probe_get_cand.argtypes = [C.c_void_p, _i32p, _f32p, _f64p]
@@ -167,6 +175,18 @@ class Probe:
         R = np.ascontiguousarray(R, np.float32).reshape(-1, 9)
         assert len(os_) == len(xyzsd) == len(R)
         return self.L.probe_set_kp(self.h, len(os_), os_, xyzsd, R)
+
+    def orient(self, os_, xyz, sd, scale=1.0):
+        """assign_eig_ori at caller-made candidates of the pyramid detect() built: os_ (n, 2), xyz (n, 3) voxels,
+        sd (n,); scale multiplies the level (float).  Returns status (0 success, 1 REJECT, else failure), conf, R."""
+        os_ = np.ascontiguousarray(os_, np.int32).reshape(-1, 2)
+        xyz = np.ascontiguousarray(xyz, np.int32).reshape(-1, 3)
+        sd = np.ascontiguousarray(sd, np.float64).reshape(-1)
+        n = len(os_)
+        assert len(xyz) == n and len(sd) == n
+        status, conf, R = np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros((n, 9), np.float32)
+        assert self.L.probe_orient(self.h, n, os_, xyz, sd, float(scale), status, conf, R) == 0
+        return status, conf, R.reshape(n, 3, 3)
 
     def sort(self, limit):
         self.L.probe_sort(self.h, int(limit))

@@ -939,10 +939,10 @@ static inline void grad_iso(const orc_level_t *im, int x, int y, int z, float *g
     g[2] *= 1.0f / (float)im->uz;
 }
 
-/* assign_eig_ori + assign_orientation_thresh, sift.c:926-1102.
- * Returns 0 keep, 1 reject. */
-static int orient_one(const orc_ctx *c, const orc_level_t *im, const float *ctr,
-                      double sigma, float *R)
+/* assign_eig_ori, sift.c:926-1085.  Returns 0 success, 1 REJECT; *conf is the corner
+ * score (0 on REJECT, sift.c:1070-1072). */
+static int orient_eig(const orc_level_t *im, const float *ctr, double sigma, float *R,
+                      double *conf)
 {
     const double win_radius = sigma * k_ori_rad_fctr;       /* sift.c:936 */
     const float uxf = (float)im->ux, uyf = (float)im->uy, uzf = (float)im->uz;
@@ -950,6 +950,7 @@ static int orient_one(const orc_ctx *c, const orc_level_t *im, const float *ctr,
     float win[3] = { 0.0f, 0.0f, 0.0f }, v[2][3], vr[3];
     int xs, xe, ys, ye, zs, ze, x, y, z, i;
 
+    *conf = 0.0;
     if (sigma < 0)
         return 1;
     sphere_bounds(ctr[0], win_radius, 0, 1, uxf, im->nx, &xs, &xe);
@@ -1008,7 +1009,18 @@ static int orient_one(const orc_ctx *c, const orc_level_t *im, const float *ctr,
     R[0 * 3 + 2] = v[0][1] * v[1][2] - v[0][2] * v[1][1];   /* sift.c:1054-1059 */
     R[1 * 3 + 2] = v[0][2] * v[1][0] - v[0][0] * v[1][2];
     R[2 * 3 + 2] = v[0][0] * v[1][1] - v[0][1] * v[1][0];
-    return corner < c->corner_thresh ? 1 : 0;               /* sift.c:1100-1101 */
+    *conf = corner;                                         /* sift.c:1062-1063 */
+    return 0;
+}
+
+/* assign_orientation_thresh, sift.c:1091-1102.  Returns 0 keep, 1 reject. */
+static int orient_one(const orc_ctx *c, const orc_level_t *im, const float *ctr,
+                      double sigma, float *R)
+{
+    double conf;
+    if (orient_eig(im, ctr, sigma, R, &conf))
+        return 1;
+    return conf < c->corner_thresh ? 1 : 0;                 /* sift.c:1100-1101 */
 }
 
 /* assign_orientations, sift.c:1109-1167 */
@@ -1274,17 +1286,29 @@ static void slab_level(orc_level_t *L, const float *data, int nx, int ny, int nz
     L->nz_glob = nz_glob;
 }
 
+int orc_orient_conf(const float *data, int nx, int ny, int nz_loc, int z_off, int nz_glob,
+                    const double *units, double sd, int x, int y, int z_glob,
+                    double corner_thresh, float *R, double *conf, int *status)
+{
+    orc_level_t L;
+    const float ctr[3] = { (float)(double)x, (float)(double)y, (float)(double)z_glob };
+    double cf;
+    int st;
+    slab_level(&L, data, nx, ny, nz_loc, z_off, nz_glob, units, sd);
+    st = orient_eig(&L, ctr, k_ori_sig_fctr * sd, R, &cf);
+    if (conf)
+        *conf = cf;
+    if (status)
+        *status = st;
+    return !st && !(cf < corner_thresh);                    /* 1 = kept, sift.c:1100-1101 */
+}
+
 int orc_orient_slab(const float *data, int nx, int ny, int nz_loc, int z_off, int nz_glob,
                     const double *units, double sd, int x, int y, int z_glob,
                     double corner_thresh, float *R)
 {
-    orc_ctx c;
-    orc_level_t L;
-    const float ctr[3] = { (float)(double)x, (float)(double)y, (float)(double)z_glob };
-    memset(&c, 0, sizeof(c));
-    c.corner_thresh = corner_thresh;
-    slab_level(&L, data, nx, ny, nz_loc, z_off, nz_glob, units, sd);
-    return !orient_one(&c, &L, ctr, k_ori_sig_fctr * sd, R); /* 1 = kept */
+    return orc_orient_conf(data, nx, ny, nz_loc, z_off, nz_glob, units, sd, x, y, z_glob,
+                           corner_thresh, R, NULL, NULL);
 }
 
 void orc_describe_slab(const float *data, int nx, int ny, int nz_loc, int z_off, int nz_glob,

@@ -99,6 +99,9 @@ def lib():
         L.orc_dogmax.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.orc_filter.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), _f32p]
         L.orc_mesh.argtypes = [C.c_void_p, _f32p, _i32p]
+        L.orc_orient_conf.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f64p,
+                                      C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, _f32p,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.orc_timings.restype = C.POINTER(C.c_double)
         L.orc_timings.argtypes = [C.c_void_p]
         L.sift3d_amd_synth_survey.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -153,6 +156,29 @@ def eigen3(A):
     L = np.zeros(3)
     lib().orc_eigen3(A, Q, L)
     return Q.reshape(3, 3), L
+
+
+def orient_conf(level, units, sd, xyz, corner_thresh=0.0, off=0, nz_glob=None):
+    """assign_eig_ori (orc_orient_conf) at the voxels xyz (n, 3; z GLOBAL) of one level array
+    [nz_loc, ny, nx] holding planes [off, off + nz_loc) of nz_glob; sd a scalar or one per voxel.
+    Returns keep (n,) int32 -- status == 0 and not conf < corner_thresh --, R (n, 9) float32,
+    conf (n,) float64 and status (n,) int32 (0 success, 1 REJECT)."""
+    level = np.ascontiguousarray(level, np.float32)
+    nzl, ny, nx = level.shape
+    xyz = np.asarray(xyz, np.int64).reshape(-1, 3)
+    n = len(xyz)
+    sd = np.broadcast_to(np.asarray(sd, np.float64), (n,))
+    u = np.ascontiguousarray(units, np.float64)
+    keep, R = np.zeros(n, np.int32), np.zeros((n, 9), np.float32)
+    conf, status = np.zeros(n, np.float64), np.zeros(n, np.int32)
+    f = lib().orc_orient_conf
+    cf, st = C.c_double(), C.c_int()
+    for i in range(n):
+        keep[i] = f(level, nx, ny, nzl, int(off), int(nzl if nz_glob is None else nz_glob), u, float(sd[i]),
+                    int(xyz[i, 0]), int(xyz[i, 1]), int(xyz[i, 2]), float(corner_thresh), R[i],
+                    C.byref(cf), C.byref(st))
+        conf[i], status[i] = cf.value, st.value
+    return keep, R, conf, status
 
 
 def synth_survey(n, nblob=None, seed=0):

@@ -259,6 +259,15 @@ static int orient_part(sift3d_detector *d, int lv_lo, int lv_hi, uint32_t first,
     int32_t *k_view = (int32_t *)sift3d_hip_host_device_ptr(d->h_keep);
     if (!r_view || !k_view)
         return SIFT3D_FAILURE;
+    /* the serial sums pack window-relative x and y into 10 bits each (sift3d_hip_orient_window_fits) */
+    for (int t = lv_lo; n && t < lv_hi; t++) {
+        const sift3d_hip_level *L = d->h_levels + t;
+        if (!sift3d_hip_orient_window_fits(L->nx, L->ny, (double)L->ux, (double)L->uy, L->sd)) {
+            ERR("sift3d_amd: the orientation window of a %d x %d level with units (%f, %f) at scale %f is wider "
+                "than 1023 voxels \n", L->nx, L->ny, (double)L->ux, (double)L->uy, L->sd);
+            return SIFT3D_FAILURE;
+        }
+    }
     return sift3d_hip_orient_tab_part(d->d_levels, d->num_octaves * d->ngl, lv_lo, lv_hi, d->d_cand, first, n,
                                       d->corner_thresh, r_view, k_view, d->orient_serial ? NULL : d->d_otab,
                                       d->cand_cap, slot, stream);

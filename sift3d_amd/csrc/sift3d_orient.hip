@@ -929,6 +929,27 @@ __attribute__((visibility("default"))) unsigned long long sift3d_amd_diag_orient
 }
 #endif
 
+// orient_serial queues a window's voxels as window-relative x and y in 10 bits each (pk): the clipped box
+// (bounds_d: max(floor(c - rad / u), 1) .. min(ceil(c + rad / u), n - 2), rad = 4.5 sd) must span at most 1024
+// voxels in x and in y.  The bound on its width from the level alone is min(n - 2, 2 ceil(rad / u) + 1); a level
+// fits when that is at most 1023 on both axes.  Host arithmetic on numbers: no volume is touched.
+int sift3d_hip_orient_window_fits(int nx, int ny, double ux, double uy, double sd)
+{
+    const int n[2] = { nx, ny };
+    const double u[2] = { ux, uy };
+    for (int a = 0; a < 2; a++) {
+        double w = (double)n[a] - 2.0;
+        if (u[a] > 0.0 && sd > 0.0) {                                     // (else: the whole row)
+            const double win = 2.0 * ceil(1.5 * sd * 3.0 / u[a]) + 1.0;   // ori_sig_fctr, ori_rad_fctr
+            if (win < w)
+                w = win;
+        }
+        if (w > 1023.0)
+            return 0;
+    }
+    return 1;
+}
+
 int sift3d_hip_orient(const sift3d_hip_level *d_levels, const sift3d_hip_cand *d_cand, uint32_t n,
                       double corner_thresh, float *d_R, int32_t *d_keep, void *stream)
 {

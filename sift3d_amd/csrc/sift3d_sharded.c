@@ -939,6 +939,16 @@ int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
     sift3d_hip_event_record(S->ev2, S->stream);
     if (S->world > 1 && S->o_shard > 0)
         SH_COMM(sift3d_hip_stream_wait_event(S->stream, S->ev_halo));    /* the window halos have arrived */
+    /* the serial sums pack window-relative x and y into 10 bits each (sift3d_hip_orient_window_fits) */
+    for (int t = 0; count && !S->failed && t < S->num_octaves * S->ngl; t++) {
+        const sift3d_hip_level *L = S->h_levels + t;
+        if (!sift3d_hip_orient_window_fits(L->nx, L->ny, (double)L->ux, (double)L->uy, L->sd)) {
+            ERR("sift3d_amd_sharded: the orientation window of a %d x %d level with units (%f, %f) at scale %f is "
+                "wider than 1023 voxels \n", L->nx, L->ny, (double)L->ux, (double)L->uy, L->sd);
+            SH_DO(1);
+            count = 0;
+        }
+    }
     if (count) {
         const size_t need = sift3d_hip_orient_tab_bytes(S->num_octaves * S->ngl, S->cand_cap);
         if (need > S->otab_bytes) {

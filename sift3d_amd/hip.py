@@ -168,6 +168,7 @@ def lib():
         "sift3d_hip_orient_tab": (C.c_int, [vp, C.c_int, vp, C.c_uint32, C.c_double, vp, vp, vp, C.c_uint32, vp]),
         "sift3d_hip_orient_tab_part": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, C.c_uint32,
                                                  C.c_double, vp, vp, vp, C.c_uint32, C.c_int, vp]),
+        "sift3d_hip_orient_window_fits": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
         "sift3d_hip_describe": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
         "sift3d_hip_set_mesh": (C.c_int, [C.POINTER(C.c_float)]),
         "sift3d_hip_synth_lattice": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]),
@@ -2257,16 +2258,34 @@ def orient(d_levels, cands, corner_thresh):
     return R.cpu().numpy(), keep.cpu().numpy()
 
 
-def orient_tab(d_levels, nlevels, cands, corner_thresh, parts=None):
+def orient_window_fits(nx, ny, ux, uy, sd):
+    """The host check of the orientation kernels' 10-bit window packing for one level's numbers (no volume): 1 =
+    the clipped window box spans at most 1023 voxels in x and in y."""
+    return lib().sift3d_hip_orient_window_fits(int(nx), int(ny), float(ux), float(uy), float(sd))
+
+
+def orient_tab_bytes(nlevels, n):
+    """sift3d_hip_orient_tab_bytes: the scratch of orient_tab for nlevels levels and up to n candidates."""
+    return int(lib().sift3d_hip_orient_tab_bytes(int(nlevels), int(n)))
+
+
+def orient_tab(d_levels, nlevels, cands, corner_thresh, parts=None, tab=None):
     """sift3d_hip_orient_tab over the whole list, or -- parts = [(lv_lo, lv_hi, first, n), (..)] -- the list
-    in two parts that run at the same time on two streams (sift3d_hip_orient_tab_part)."""
+    in two parts that run at the same time on two streams (sift3d_hip_orient_tab_part).  tab: a caller-owned
+    scratch (contiguous uint8 CUDA tensor of at least orient_tab_bytes(nlevels, n) bytes, zeroed when it was
+    allocated) used instead of a fresh one -- the window tables in it survive from call to call."""
     import torch
     n = len(cands)
     L = lib()
     dc = torch.from_numpy(np.ascontiguousarray(cands).view(np.uint8)).cuda()
     R = torch.zeros((n, 9), dtype=torch.float32, device="cuda")
     keep = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-    tab = torch.zeros(L.sift3d_hip_orient_tab_bytes(nlevels, n), dtype=torch.uint8, device="cuda")
+    if tab is None:
+        tab = torch.zeros(L.sift3d_hip_orient_tab_bytes(nlevels, n), dtype=torch.uint8, device="cuda")
+    elif (not isinstance(tab, torch.Tensor) or not tab.is_cuda or tab.dtype != torch.uint8 or
+          not tab.is_contiguous() or tab.numel() < L.sift3d_hip_orient_tab_bytes(nlevels, n)):
+        raise ValueError("orient_tab: tab must be a contiguous uint8 CUDA tensor of at least "
+                         "sift3d_hip_orient_tab_bytes(nlevels, n) bytes")
     torch.cuda.synchronize()
     if parts is None:
         _check(L.sift3d_hip_orient_tab(d_levels.data_ptr(), nlevels, dc.data_ptr(), n, float(corner_thresh),

@@ -247,3 +247,57 @@ def test_g7_caller_keypoints(oracle_mod, name):
                                       g[case + "_desc_xyzsd"], err_msg=case)
         np.testing.assert_array_equal(d["hist"], g[case + "_hist"], err_msg=case)
         assert util.assert_desc_projection(d["hist"], g[case + "_proj"], rtol=1e-12) < 1e-12
+
+
+# ----------------------------------------------------------------------------------------
+# orientation on caller-made candidate lists (tests/golden/g8_*): every level of two octaves,
+# face layers and corners, scales a level does not have, noise, faint levels
+# ----------------------------------------------------------------------------------------
+def g8_check(oracle_mod, g, level_fn):
+    """orc_orient_conf on every list of a g8 fixture against the reference's assign_eig_ori: status equal for
+    every candidate, R within 1e-5 relative on the accepted ones, conf within 1e-5 (a cosine of float vectors;
+    the oracle's eigen routine stands in for LAPACK dsyevd, so it need not be bit-equal)."""
+    from tests import orient_cases as oc
+    worst = 0.0
+    for case in oc.g8_cases(g):
+        c = oc.g8_case(g, case)
+        levels, cands, order = oc.g8_list(c, level_fn)
+        R, conf, status = oc.oracle(oracle_mod, levels, cands)
+        np.testing.assert_array_equal(status, c["status"][order], err_msg=case)
+        ok = status == 0
+        assert set(np.unique(status)) <= {0, 1} and (conf[~ok] == 0).all()
+        if ok.any():
+            assert util.rel_err(R[ok], c["R"][order][ok].reshape(-1, 9)) <= oc.RTOL, case
+            worst = max(worst, float(np.abs(conf - c["conf"][order])[ok].max()))
+    assert worst <= 1e-5
+    assert float(g["conf_maxdiff"]) <= 1e-5
+    return worst
+
+
+@pytest.mark.parametrize("name", ["g8_survey", "g8_aniso", "g8_scales", "g8_noise", "g8_noise_blur", "g8_faint"])
+def test_g8_caller_candidates(oracle_mod, name):
+    g = util.load(name)
+    o = oracle_mod.Oracle()
+    assert o.detect(util.golden_input(g, oracle_mod), tuple(g["units"])) == 0
+    assert o.num_octaves == int(g["num_octaves"])
+    g8_check(oracle_mod, g, lambda oc_, s: o.level(0, oc_, s)[:2])
+
+
+@pytest.mark.refprobe
+def test_g8_regenerates(oracle_mod):
+    """One list made again from the reference build (where oracle/_ref exists and has the hook) equals the
+    committed fixture."""
+    from oracle import refprobe
+    if not refprobe.has_orient():
+        pytest.skip("oracle/_ref is not built here, or was built before ref_probe.c had probe_orient")
+    from tests import orient_cases as oc
+    g = util.load("g8_noise")
+    p = refprobe.Probe()
+    assert p.detect(util.golden_input(g, oracle_mod), tuple(g["units"])) == 0
+    for case in oc.g8_cases(g):
+        c = oc.g8_case(g, case)
+        status, conf, R = p.orient(c["os"], c["xyz"], c["sd"], float(c["scale"]))
+        np.testing.assert_array_equal(status, c["status"])
+        np.testing.assert_array_equal(conf, c["conf"])
+        np.testing.assert_array_equal(R, c["R"])
+    p.close()

@@ -33,6 +33,12 @@ def golden_input(g, so):
         nx, ny, nz = spec["n"]
         c = np.random.Generator(np.random.PCG64(spec["seed"])).standard_normal(nx).astype(np.float32)
         vol = np.ascontiguousarray(np.broadcast_to(c, (nz, ny, nx)), np.float32)
+    elif spec["gen"] == "noise":
+        # white PCG64 noise, optionally blurred with the oracle's own blur (oracle/make_golden.py noise_volume)
+        nx, ny, nz = spec["n"]
+        vol = np.random.Generator(np.random.PCG64(spec["seed"])).standard_normal((nz, ny, nx)).astype(np.float32)
+        if spec.get("blur_sigma"):
+            vol = so.blur(vol, so.gauss_taps(spec["blur_sigma"]))
     else:
         vol = so.synth_lattice(spec["n"], seed=spec["seed"])
     assert digest(vol) == str(g["input_digest"]), "synthetic generator drifted"
