@@ -1734,6 +1734,89 @@ sift3d_amd_demons_multires_device(const sift3d_amd_demons_level *level, int leve
                                   float *d_work, void *d_stats, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Log-domain demons                                                        */
+/* ------------------------------------------------------------------------ */
+/* Log-domain demons keeps a stationary velocity field v [3][nz][ny][nx] on the fixed grid and reads the moving
+ * features through exp(v); the inverse map is exp(-v), one more exponential, and forces from both directions make
+ * the result independent of which volume is called fixed (Vercauteren et al., Symmetric log-domain diffeomorphic
+ * registration, MICCAI 2008).  No upstream counterpart: pinned to this contract.  Float arithmetic, unfused.
+ *
+ * Lie bracket and BCH update (sift3d_hip_field_bracket).  a, b, out are fields [3][oz][oy][ox] on one grid.  Per
+ * voxel, g^a_de = d a_d / d x_e by step 1 of the Jacobian above (numpy.gradient's rules: (a[i+1] - a[i-1]) * 0.5f
+ * inside, one-sided differences at the ends, 0 on an axis of length 1), g^b_de the same on b, then
+ *   t_d  = (g^a_d0 * b_0 + g^a_d1 * b_1) + g^a_d2 * b_2
+ *   s_d  = (g^b_d0 * a_0 + g^b_d1 * a_1) + g^b_d2 * a_2
+ *   br_d = t_d - s_d
+ * i.e. [a, b] = J_a b - J_b a; for linear fields a = A p, b = B p it is (A B - B A) p.  With it
+ * exp(a + b + [a, b] / 2) ~ exp(a) o exp(b) in this library's composition order COMPOSE(u = exp a, v = exp b).
+ * Modes: SIFT3D_AMD_FIELD_BRACKET: out_d = br_d.  SIFT3D_AMD_FIELD_BCH1: out_d = (a_d + b_d) + 0.5f * br_d.
+ * NaN and inf propagate as IEEE arithmetic has them.  d_a == d_b is allowed (BRACKET then gives zeros wherever the
+ * fields are finite); d_out must not overlap d_a or d_b (neighbours are read).
+ *
+ * Signed exponential (sift3d_amd_field_exp_signed_device): negate == 0 is sift3d_amd_field_exp_device bit for bit;
+ * negate == 1 scales by w_0 = v * (-2^-K), the same float multiply with the sign flipped, then squares K times:
+ * exp(-v).  K == 0 with negate gives v * -1.0f.
+ *
+ * Iteration, mode LOG (symmetric == 0), Kv = velocity_squarings in [0, SIFT3D_AMD_FIELD_MAX_SQUARINGS]:
+ *   1. e = exp(v) with Kv squarings (Kv == 0: v itself);
+ *   2. W = sift3d_hip_warp_field(M, e, LINEAR, fill 0);
+ *   3. delta, stats[k] = force(F, W, e), the force of "Dense demons refinement" bit for bit;
+ *   4. sigma_fluid > 0: delta blurred as in step 3 there;
+ *   5. bch == 0: v_d = v_d + delta_d (float add); bch == 1: v <- BCH1(v, delta) (a = v, b = delta);
+ *   6. sigma_diffusion > 0: each of v's 3 channels blurred as in step 5 there.
+ * Mode SYMMETRIC (symmetric == 1) needs equal fixed and moving shapes at every level.  Steps 1-4 give delta_f; then
+ * e- = exp(-v) (the signed exponential, Kv squarings), W_b = warp_field(F, e-), delta_b = force(M, W_b, e-) (its
+ * statistics are discarded), the same fluid blur on delta_b; with n = -v (v * -1.0f),
+ *   bch == 0: Z_f = v + delta_f, Z_b = n + delta_b;  bch == 1: Z_f = BCH1(v, delta_f), Z_b = BCH1(n, delta_b);
+ *   5'. v_d = 0.5f * (Z_f,d - Z_b,d);
+ * then step 6.  Exchanging F and M exchanges Z_f and Z_b bit for bit (every operation above commutes with exact
+ * negation of its field argument), so the run started from -v ends at -v: equal bits but for the sign of zeros
+ * (x - x is +0 in both runs).
+ * Statistics: one SIFT3D_AMD_DEMONS_STATS_BYTES record per iteration, the forward force's.
+ *
+ * Pyramid (sift3d_amd_logdemons_device): that of "Multi-resolution demons" with v in place of u: restrict2 (scale
+ * 0.5f) down, the iterations of each level coarsest first, field_prolong2 up (a velocity in voxels of its grid
+ * rescales like a displacement).  levels == 1 is the flat run; the level table, the statistics' order and the
+ * refusals are sift3d_amd_demons_multires_device's, plus bch or symmetric outside {0, 1}, Kv out of range, and
+ * unequal fixed and moving shapes under SYMMETRIC.  iterations == 0 everywhere leaves v untouched (levels == 1).
+ * d_work holds sift3d_amd_logdemons_work_floats floats; with n = nx*ny*nz of the finest level, pad4(x) = x rounded
+ * up to a multiple of 4 and n_l the voxels of level l:
+ *   pad4(8192 + 4 s + (nc + 14 + 6 s) n) + sum_{l = 1 .. levels-1} pad4(3 n_l),     s = symmetric
+ * (the force's partials, with s the backward statistics; W (nc n), delta (3 n), the blur's intermediates (2 n), the
+ * exponential's two buffers (6 n), the BCH output (3 n); with s delta_b and Z_b (6 n); then the coarser levels'
+ * velocities).
+ *
+ * Out of scope: a start displacement field or affine map under the velocity (v starts from the caller's velocity
+ * or zero); BCH terms beyond the first bracket; a device-side choice of Kv; the backward statistics; masks, physical
+ * spacing, multi-GPU.
+ *
+ * Measured on an MI355X: on the 176^3 lattice case from zero, three levels, the forward error of
+ * LOG is 1.0087 (median) and 1.0006 (p90) times the diffeomorphic update's, SYMMETRIC's 1.0086 and 1.0081; neither
+ * exp(v) nor exp(-v) folds; exp(-v) is the inverse to a median of 0.164 voxel (forward 0.133).  At 512^3 the bracket
+ * kernel takes 1.49 x the Jacobian kernel's time (the bound set for it: 36 / 16 = 2.25, the ratio of their bytes).
+ *
+ * All entries are asynchronous on `stream`, allocate nothing, do not synchronise with the host, use 64-bit offsets
+ * and check their arguments before any device call (-1): NULL pointers, dims <= 0, an unknown mode, misalignment
+ * (d_stats and d_work 8 B, the rest 4 B), an output that overlaps an input, the work buffer or another output. */
+#define SIFT3D_AMD_FIELD_BRACKET 0
+#define SIFT3D_AMD_FIELD_BCH1 1
+SIFT3D_AMD_API int
+sift3d_hip_field_bracket(const float *d_a, const float *d_b, int ox, int oy, int oz, float *d_out, int mode,
+                         void *stream);
+/* d_work: sift3d_amd_field_exp_work_floats floats */
+SIFT3D_AMD_API int
+sift3d_amd_field_exp_signed_device(const float *d_v, int ox, int oy, int oz, int squarings, int negate, float *d_out,
+                                   float *d_work, void *stream);
+/* device scratch of sift3d_amd_logdemons_device, in floats, for a finest fixed grid (nx, ny, nz): the formula above
+ * (0 for bad arguments) */
+SIFT3D_AMD_API size_t sift3d_amd_logdemons_work_floats(int nx, int ny, int nz, int nc, int symmetric, int levels);
+/* level [levels] (host memory, level 0 the finest); d_v [3][nz_0][ny_0][nx_0] in / out */
+SIFT3D_AMD_API int
+sift3d_amd_logdemons_device(const sift3d_amd_demons_level *level, int levels, int nc, float *d_v, double alpha,
+                            double sigma_fluid, double sigma_diffusion, int symmetric, int bch, int velocity_squarings,
+                            float *d_work, void *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

@@ -13,6 +13,7 @@ import collections
 import ctypes as C
 import math
 import os
+import warnings
 
 import numpy as np
 
@@ -1582,6 +1583,13 @@ DenseRegistration = collections.namedtuple("DenseRegistration",
 MultiresRefinement = collections.namedtuple("MultiresRefinement", "field warped msd jacobian level_slices")
 MultiresRegistration = collections.namedtuple("MultiresRegistration",
                                               "A tps inliers num_matches field warped msd jacobian level_slices")
+# what refine_field returns for update "logdomain" / "symmetric": velocity is the stationary velocity field, field =
+# exp(velocity) and inverse = exp(-velocity) (both with the run's squarings), jacobian / inverse_jacobian their
+# jacobian_determinant, scaled_max = max|velocity| 2^-Kv (Vercauteren's criterion wants it <= 0.5)
+LogDemonsRefinement = collections.namedtuple(
+    "LogDemonsRefinement", "field inverse velocity warped msd jacobian inverse_jacobian scaled_max")
+MultiresLogDemonsRefinement = collections.namedtuple(
+    "MultiresLogDemonsRefinement", LogDemonsRefinement._fields + ("level_slices",))
 DEMONS_MAX_LEVELS = 6
 
 # Defaults chosen by a sweep on a case the end-to-end test (tests/test_demons.py) does not use: synth_survey(160,
@@ -1613,6 +1621,7 @@ def _mean_or_nan(sums, counts):
 
 
 DEMONS_UPDATES = ("additive", "diffeomorphic")
+LOGDEMONS_UPDATES = ("logdomain", "symmetric")
 
 
 def demons_squarings(alpha):
@@ -1629,7 +1638,8 @@ def demons_squarings(alpha):
 
 def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA,
                  sigma_fluid=DEMONS_SIGMA_FLUID, sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors",
-                 sigma=1.6, update="additive", squarings=None, levels=1, level_iterations=None):
+                 sigma=1.6, update="additive", squarings=None, levels=1, level_iterations=None, velocity=None, bch=1,
+                 max_motion=16.0, velocity_squarings=None):
     """Dense demons refinement (contract: include/sift3d_amd.h, "Dense demons refinement") of a displacement
     field [3, nz, ny, nx] on fixed's grid (a pull map fixed voxel -> moving voxel; None: start from zero) so that
     the moving features warped through it agree with the fixed ones at every voxel.  moving, fixed: torch CUDA
@@ -1648,13 +1658,32 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     (a low-pass: pass levels=1 to keep it exactly), refined there for level_iterations[levels - 1] iterations, handed
     up and refined again, down to level_iterations[0] on the full grid; level_iterations None: `iterations` at every
     level.  Returns MultiresRefinement: as above, msd holding every level's iterations in the order run (the
-    coarsest first), and level_slices, where msd[level_slices[l]] is level l's part (level 0 the finest)."""
+    coarsest first), and level_slices, where msd[level_slices[l]] is level l's part (level 0 the finest).
+    update "logdomain" or "symmetric" ("Log-domain demons"): the state is a stationary velocity field (`velocity`
+    [3, nz, ny, nx], None: zero; `field` must be None) read through its exponential; "symmetric" adds the force of
+    the exchanged pair, so that exchanging moving and fixed negates the velocity (the two shapes must agree).  bch 1:
+    the update with the first Lie bracket, 0: the plain sum.  velocity_squarings: the squarings Kv of every
+    exponential, None: field_squarings(max_motion), enough for velocities up to max_motion voxels; a warning is
+    issued when the result's max|v| 2^-Kv exceeds 0.5.  `squarings` is not used.  Returns LogDemonsRefinement (with
+    levels > 1 MultiresLogDemonsRefinement, which adds level_slices): field = exp(v), inverse = exp(-v), velocity,
+    warped (moving through field), msd, jacobian and inverse_jacobian (of field and inverse), scaled_max."""
     import torch
     from . import hip
+    log = update in LOGDEMONS_UPDATES
+    if log:
+        # (ahead of the tensor checks: these depend on the arguments alone)
+        if field is not None:
+            raise ValueError("update %r keeps a velocity, not a displacement: pass `velocity`, not `field`"
+                             % (update,))
+        if bch not in (0, 1):
+            raise ValueError("bch must be 0 or 1, not %r" % (bch,))
+        if update == "symmetric" and tuple(np.shape(moving)) != tuple(np.shape(fixed)):
+            raise ValueError("update 'symmetric' needs moving %s and fixed %s of one shape"
+                             % (tuple(np.shape(moving)), tuple(np.shape(fixed))))
     _volume_tensor(moving, "refine_field", "moving")
     _volume_tensor(fixed, "refine_field", "fixed")
-    if update not in DEMONS_UPDATES:
-        raise ValueError("update must be 'additive' or 'diffeomorphic', not %r" % (update,))
+    if not log and update not in DEMONS_UPDATES:
+        raise ValueError("update must be 'additive', 'diffeomorphic', 'logdomain' or 'symmetric', not %r" % (update,))
     levels = int(levels)
     if not 1 <= levels <= DEMONS_MAX_LEVELS:
         raise ValueError("levels must be in 1 .. %d, not %r" % (DEMONS_MAX_LEVELS, levels))
@@ -1674,6 +1703,9 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
         Ms = [dense_descriptors(v, sigma) for v in mv]
     else:
         Fs, Ms = fv, mv
+    if log:
+        return _refine_velocity(moving, fixed, Fs, Ms, its, velocity, alpha, sigma_fluid, sigma_diffusion,
+                                update == "symmetric", bch, max_motion, velocity_squarings)
     if field is None:
         u = torch.zeros((3,) + tuple(fixed.shape), dtype=torch.float32, device=fixed.device)
     else:
@@ -1695,6 +1727,37 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
         slices[l] = slice(at, at + its[l])
         at += its[l]
     return MultiresRefinement(u, warped, msd, jacobian_determinant(u), tuple(slices))
+
+
+def _refine_velocity(moving, fixed, Fs, Ms, its, velocity, alpha, sigma_fluid, sigma_diffusion, symmetric, bch,
+                     max_motion, velocity_squarings):
+    """refine_field's log-domain updates, after its checks: Fs, Ms the feature stacks per level"""
+    import torch
+    from . import hip
+    levels = len(Fs)
+    if velocity is None:
+        v = torch.zeros((3,) + tuple(fixed.shape), dtype=torch.float32, device=fixed.device)
+    else:
+        hip._field_tensor(velocity, "refine_field", "velocity")
+        v = velocity.clone()
+    Kv = field_squarings(max_motion) if velocity_squarings is None else int(velocity_squarings)
+    stats = hip.logdemons(Fs, Ms, v, its, alpha, sigma_fluid, sigma_diffusion, symmetric, bch, Kv)
+    msd = _mean_or_nan(*hip.demons_stats(stats))
+    u = field_exp(v, Kv)
+    w = field_exp(v, Kv, negate=True)
+    scaled_max = float(torch.sqrt((v.double() ** 2).sum(0)).max()) * 2.0 ** -Kv
+    if scaled_max > 0.5:
+        warnings.warn("refine_field: max|v| 2^-Kv = %.3g exceeds 0.5 voxel with Kv = %d: the exponentials are "
+                      "inaccurate; raise max_motion or velocity_squarings" % (scaled_max, Kv))
+    r = (u, w, v, warp_field(moving, u, "linear", 0.0), msd, jacobian_determinant(u), jacobian_determinant(w),
+         scaled_max)
+    if levels == 1:
+        return LogDemonsRefinement(*r)
+    slices, at = [None] * levels, 0
+    for l in range(levels - 1, -1, -1):
+        slices[l] = slice(at, at + its[l])
+        at += its[l]
+    return MultiresLogDemonsRefinement(*(r + (tuple(slices),)))
 
 
 def restrict_volume(volume, scale=1.0):
@@ -1774,8 +1837,17 @@ def field_squarings(max_norm):
     return K
 
 
-def field_exp(v, squarings=None):
-    """exp(v) by scaling and squaring: w_0 = v 2^-K, w_{k+1} = w_k o w_k.  v [3, oz, oy, ox] torch CUDA float32.
+def lie_bracket(a, b):
+    """The Lie bracket [a, b] = J_a b - J_b a of two fields [3, oz, oy, ox] on one grid (torch CUDA float32), J the
+    Jacobian by numpy.gradient's differences ("Log-domain demons"); exp(a + b + [a, b] / 2) approximates
+    compose_fields(exp a, exp b).  One kernel on torch's current stream; returns a new tensor."""
+    from . import hip
+    return hip.field_bracket(a, b, None, "bracket")
+
+
+def field_exp(v, squarings=None, negate=False):
+    """exp(v) by scaling and squaring: w_0 = v 2^-K, w_{k+1} = w_k o w_k; negate: exp(-v), the inverse map, from
+    w_0 = v (-2^-K).  v [3, oz, oy, ox] torch CUDA float32.
     squarings None: the smallest K >= 0 with max|v| 2^-K <= 0.5 voxel (Vercauteren et al., 2009); computing max|v|
     in torch costs one host synchronisation.  Returns a new tensor on torch's current stream."""
     import torch
@@ -1784,7 +1856,7 @@ def field_exp(v, squarings=None):
     if squarings is None:
         squarings = field_squarings(float(torch.sqrt((v.double() ** 2).sum(0)).max()))
     out = torch.empty_like(v)
-    return hip.field_exp(v, out, squarings)
+    return hip.field_exp(v, out, squarings, negate=bool(negate))
 
 
 def invert_field(u, out_shape, iterations=INVERT_ITERATIONS, init=None):

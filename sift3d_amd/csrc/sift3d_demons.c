@@ -1,15 +1,16 @@
 /* sift3d_demons.c -- dense demons refinement of a displacement field: the checked force, the two grid transfers
  * and the one driver behind sift3d_amd_demons_device, sift3d_amd_demons_device_ex and
- * sift3d_amd_demons_multires_device (included at the end of sift3d_host.c, after sift3d_field_ops.c).
+ * sift3d_amd_demons_multires_device, and sift3d_amd_logdemons_device, which runs its own iteration (logdemons_run)
+ * through the same driver (included at the end of sift3d_host.c, after sift3d_field_ops.c).
  *
- * The contract is in include/sift3d_amd.h, "Dense demons refinement", "Diffeomorphic demons" and "Multi-resolution
- * demons".  The force and the additive update are kernels of sift3d_demons.hip and the transfers kernels of
- * sift3d_multires.hip, reached through the launchers below after the checks here; the warp is
- * sift3d_hip_warp_field, the exponential field_exp_run, and the smoothing the detector's own blur (blur_level) per
- * channel, as for the dense descriptors.  A demons problem is a list of levels (one for the two single-level
- * entries): demons_drive validates it once, builds the two Gaussian filters once and runs demons_run, which
- * checks nothing, on every level.  Arguments are checked before the device is touched, so bad input is refused on
- * a machine without a GPU too. */
+ * The contract is in include/sift3d_amd.h, "Dense demons refinement", "Diffeomorphic demons", "Multi-resolution
+ * demons" and "Log-domain demons".  The force and the additive update are kernels of sift3d_demons.hip, the bracket
+ * and the symmetric update of sift3d_field_bracket.hip and the transfers kernels of sift3d_multires.hip, reached
+ * through the launchers below after the checks here; the warp is sift3d_hip_warp_field, the exponential
+ * field_exp_run, and the smoothing the detector's own blur (blur_level) per channel, as for the dense descriptors.
+ * A demons problem is a list of levels (one for the two single-level entries): demons_drive validates it once,
+ * builds the two Gaussian filters once and runs demons_run or logdemons_run, which check nothing, on every level.
+ * Arguments are checked before the device is touched, so bad input is refused on a machine without a GPU too. */
 
 int sift3d_demons_force_launch(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx,
                                int my, int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work,
@@ -18,6 +19,8 @@ int sift3d_demons_field_add_launch(float *d_u, const float *d_step, size_t n, vo
 int sift3d_restrict2_launch(const float *d_src, int nx, int ny, int nz, int nc, float *d_dst, float scale,
                             void *stream);
 int sift3d_field_prolong2_launch(const float *d_coarse, float *d_fine, int nx, int ny, int nz, void *stream);
+int sift3d_velocity_symmetrize_launch(float *d_v, const float *d_zf, const float *d_zb, size_t n, int bch,
+                                      void *stream);
 
 static int check_alpha(const char *what, double alpha)
 {
@@ -135,14 +138,38 @@ static size_t pad4(size_t floats)
     return (floats + 3) & ~(size_t)3;
 }
 
+/* One level's scratch of log-domain demons, as offsets in floats into d_work: the force's partials at 0 (SYMMETRIC:
+ * then the backward statistics, 4 floats), W (nc planes), delta (3), the blur's two intermediates, e = exp(+-v) and
+ * the exponential's second buffer (3 each; after the forces: n = -v), z (3: the BCH output, Z_f); SYMMETRIC adds
+ * delta_b and Z_b (3 each).  The header states the total. */
+typedef struct {
+    size_t bstats, W, step, tmp, e, pp, z, stepb, zb, total;
+} logdemons_layout;
+
+static logdemons_layout logdemons_layout_of(size_t n, int nc, int symmetric)
+{
+    logdemons_layout l;
+    l.bstats = SIFT3D_AMD_DEMONS_FORCE_WORK_BYTES / sizeof(float);
+    l.W = l.bstats + (symmetric ? 4 : 0);
+    l.step = l.W + (size_t)nc * n;
+    l.tmp = l.step + 3 * n;
+    l.e = l.tmp + 2 * n;
+    l.pp = l.e + 3 * n;
+    l.z = l.pp + 3 * n;
+    l.stepb = l.z + 3 * n;
+    l.zb = l.stepb + (symmetric ? 3 * n : 0);
+    l.total = l.zb + (symmetric ? 3 * n : 0);
+    return l;
+}
+
 /* Where level l's field (l >= 1) starts in the pyramid's d_work, in floats, under a finest grid (nx, ny, nz): after
  * level 0's scratch, which every level uses in turn, and the fields of levels 1 .. l-1, each padded to a multiple
  * of 4 floats so that every field is 16-byte aligned when d_work is.  l == levels gives the whole buffer.  A level
  * field is safe from its own level's scratch only because no coarser level needs more scratch than level 0 (a
  * halved grid has no more voxels); demons_validate refuses a level for which that does not hold. */
-static size_t multires_field_offset(int nx, int ny, int nz, int nc, int update, int l)
+static size_t pyramid_field_offset(size_t scratch, int nx, int ny, int nz, int l)
 {
-    size_t at = pad4(sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, update));
+    size_t at = pad4(scratch);
     int k;
     for (k = 1; k < l; k++) {
         nx = multires_half(nx); ny = multires_half(ny); nz = multires_half(nz);
@@ -156,16 +183,33 @@ size_t sift3d_amd_demons_multires_work_floats(int nx, int ny, int nz, int nc, in
     if (levels < 1 || levels > SIFT3D_AMD_DEMONS_MAX_LEVELS ||
         !sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, update))
         return 0;
-    return multires_field_offset(nx, ny, nz, nc, update, levels);
+    return pyramid_field_offset(sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, update), nx, ny, nz, levels);
 }
 
 /* ---- the driver ---- */
 
+/* logdomain == 0: the displacement drivers (update, squarings); 1: log-domain demons, squarings = Kv, and update is
+ * not read */
 typedef struct {
     int nc;
     double alpha, sigma_fluid, sigma_diffusion;
     int update, squarings;
+    int logdomain, symmetric, bch;
 } demons_params;
+
+/* one level's scratch in floats */
+static size_t demons_scratch(const demons_params *p, int nx, int ny, int nz)
+{
+    return p->logdomain ? logdemons_layout_of(grid_voxels(nx, ny, nz), p->nc, p->symmetric).total
+                        : sift3d_amd_demons_work_floats_ex(nx, ny, nz, p->nc, p->update);
+}
+
+static int check_log(const char *what, const demons_params *p)
+{
+    if (p->symmetric != 0 && p->symmetric != 1)
+        return refuse(what, "symmetric must be 0 or 1");
+    return p->bch != 0 && p->bch != 1 ? refuse(what, "bch must be 0 or 1") : SIFT3D_SUCCESS;
+}
 
 /* 0 when the problem may run: level [levels] (level 0 the finest), the field d_u on level 0's grid, work_floats
  * floats of d_work, one statistics record per iteration (room for one when there is none) */
@@ -180,8 +224,9 @@ static int demons_validate(const char *what, const sift3d_amd_demons_level *leve
         return refuse(what, "NULL argument");
     if (levels < 1 || levels > SIFT3D_AMD_DEMONS_MAX_LEVELS)
         return refuse(what, "levels must be in [1, SIFT3D_AMD_DEMONS_MAX_LEVELS]");
-    if (check_update(what, p->update) || check_squarings(what, p->squarings) || check_channels(what, p->nc) ||
-        check_alpha(what, p->alpha) || check_sigmas(what, p->sigma_fluid, p->sigma_diffusion))
+    if ((p->logdomain ? check_log(what, p) : check_update(what, p->update)) ||
+        check_squarings(what, p->squarings) || check_channels(what, p->nc) || check_alpha(what, p->alpha) ||
+        check_sigmas(what, p->sigma_fluid, p->sigma_diffusion))
         return SIFT3D_FAILURE;
     for (l = 0; l < levels; l++) {
         const sift3d_amd_demons_level *v = level + l;
@@ -194,8 +239,9 @@ static int demons_validate(const char *what, const sift3d_amd_demons_level *leve
                       v->nz != multires_half(v[-1].nz) || v->mx != multires_half(v[-1].mx) ||
                       v->my != multires_half(v[-1].my) || v->mz != multires_half(v[-1].mz)))
             return refuse(what, "a level's dimensions are not the halves of the level above");
-        if (sift3d_amd_demons_work_floats_ex(v->nx, v->ny, v->nz, p->nc, p->update) >
-            sift3d_amd_demons_work_floats_ex(level->nx, level->ny, level->nz, p->nc, p->update))
+        if (p->logdomain && p->symmetric && (v->nx != v->mx || v->ny != v->my || v->nz != v->mz))
+            return refuse(what, "the symmetric update needs fixed and moving volumes of one shape");
+        if (demons_scratch(p, v->nx, v->ny, v->nz) > demons_scratch(p, level->nx, level->ny, level->nz))
             return refuse(what, "a level needs more scratch than the finest");
         total += (size_t)v->iterations;
         or4 |= ADDR(v->d_F) | ADDR(v->d_M);
@@ -256,7 +302,7 @@ static int demons_run(const sift3d_amd_demons_level *v, const demons_params *p, 
         /* e = exp(delta): w_0 = delta * 2^-K, then K squarings between d_pp and d_step (delta is read only by the
          * scaling); K == 0: e = delta itself */
         if (p->squarings > 0) {
-            if (field_exp_run(d_step, v->nx, v->ny, v->nz, p->squarings, d_pp, d_step, stream))
+            if (field_exp_run(d_step, v->nx, v->ny, v->nz, p->squarings, 1.0, d_pp, d_step, stream))
                 return SIFT3D_FAILURE;
             e = d_pp;
         }
@@ -264,6 +310,61 @@ static int demons_run(const sift3d_amd_demons_level *v, const demons_params *p, 
                                         SIFT3D_AMD_FIELD_COMPOSE, NULL, NULL, stream) ||
             (p->sigma_diffusion > 0 ? demons_blur3(d_unew, d_u, dims, fd, d_tmp, stream)
                                     : sift3d_hip_memcpy_d2d(d_u, d_unew, 3 * n * sizeof(float), stream)))
+            return SIFT3D_FAILURE;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* v->iterations iterations of log-domain demons on one level's velocity d_v, unchecked ("Log-domain demons": LOG, or
+ * SYMMETRIC with p->symmetric); arguments as demons_run's */
+static int logdemons_run(const sift3d_amd_demons_level *v, const demons_params *p, float *d_v, const filter_t *ff,
+                         const filter_t *fd, float *d_work, char *d_stats, void *stream)
+{
+    const int dims[3] = { v->nx, v->ny, v->nz };
+    const size_t n = grid_voxels(v->nx, v->ny, v->nz);
+    const logdemons_layout at = logdemons_layout_of(n, p->nc, p->symmetric);
+    float *d_W = d_work + at.W, *d_step = d_work + at.step, *d_tmp = d_work + at.tmp, *d_e = d_work + at.e,
+          *d_pp = d_work + at.pp, *d_z = d_work + at.z, *d_stepb = d_work + at.stepb, *d_zb = d_work + at.zb;
+    const int K = p->squarings;
+    int k;
+    for (k = 0; k < v->iterations; k++) {
+        /* e = exp(v); K == 0: v itself */
+        const float *e = K > 0 ? d_e : d_v;
+        if ((K > 0 && field_exp_run(d_v, v->nx, v->ny, v->nz, K, 1.0, d_e, d_pp, stream)) ||
+            sift3d_hip_warp_field(v->d_M, v->mx, v->my, v->mz, p->nc, e, v->nx, v->ny, v->nz, d_W,
+                                  SIFT3D_AMD_INTERP_LINEAR, 0.0f, stream) ||
+            sift3d_demons_force_launch(v->d_F, v->nx, v->ny, v->nz, d_W, e, v->mx, v->my, v->mz, p->nc, p->alpha,
+                                       d_step, d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * k, d_work, stream) ||
+            (p->sigma_fluid > 0 && demons_blur3(d_step, d_step, dims, ff, d_tmp, stream)))
+            return SIFT3D_FAILURE;
+        if (!p->symmetric) {
+            if (p->bch ? (sift3d_field_bracket_launch(d_v, d_step, v->nx, v->ny, v->nz, d_z, SIFT3D_AMD_FIELD_BCH1,
+                                                      stream) ||
+                          (p->sigma_diffusion > 0 ? demons_blur3(d_z, d_v, dims, fd, d_tmp, stream)
+                                                  : sift3d_hip_memcpy_d2d(d_v, d_z, 3 * n * sizeof(float), stream)))
+                       : (sift3d_demons_field_add_launch(d_v, d_step, 3 * n, stream) ||
+                          (p->sigma_diffusion > 0 && demons_blur3(d_v, d_v, dims, fd, d_tmp, stream))))
+                return SIFT3D_FAILURE;
+            continue;
+        }
+        /* the backward force: the roles of F and M exchanged (one shape), read through e- = exp(-v) */
+        if (field_exp_run(d_v, v->nx, v->ny, v->nz, K, -1.0, d_e, d_pp, stream) ||
+            sift3d_hip_warp_field(v->d_F, v->nx, v->ny, v->nz, p->nc, d_e, v->nx, v->ny, v->nz, d_W,
+                                  SIFT3D_AMD_INTERP_LINEAR, 0.0f, stream) ||
+            sift3d_demons_force_launch(v->d_M, v->nx, v->ny, v->nz, d_W, d_e, v->nx, v->ny, v->nz, p->nc, p->alpha,
+                                       d_stepb, d_work + at.bstats, d_work, stream) ||
+            (p->sigma_fluid > 0 && demons_blur3(d_stepb, d_stepb, dims, ff, d_tmp, stream)))
+            return SIFT3D_FAILURE;
+        if (p->bch) {
+            /* n = -v into e's buffer, which the forces have finished with */
+            if (sift3d_field_scale_launch(d_e, d_v, 3 * n, -1.0f, stream) ||
+                sift3d_field_bracket_launch(d_v, d_step, v->nx, v->ny, v->nz, d_z, SIFT3D_AMD_FIELD_BCH1, stream) ||
+                sift3d_field_bracket_launch(d_e, d_stepb, v->nx, v->ny, v->nz, d_zb, SIFT3D_AMD_FIELD_BCH1, stream) ||
+                sift3d_velocity_symmetrize_launch(d_v, d_z, d_zb, 3 * n, 1, stream))
+                return SIFT3D_FAILURE;
+        } else if (sift3d_velocity_symmetrize_launch(d_v, d_step, d_stepb, 3 * n, 0, stream))
+            return SIFT3D_FAILURE;
+        if (p->sigma_diffusion > 0 && demons_blur3(d_v, d_v, dims, fd, d_tmp, stream))
             return SIFT3D_FAILURE;
     }
     return SIFT3D_SUCCESS;
@@ -283,7 +384,8 @@ static int demons_drive(const char *what, const sift3d_amd_demons_level *level, 
     /* the level fields: level 0 is d_u, the others follow the finest level's scratch in d_work */
     u[0] = d_u;
     for (l = 1; l < levels; l++) {
-        u[l] = d_work + multires_field_offset(level->nx, level->ny, level->nz, p->nc, p->update, l);
+        u[l] = d_work + pyramid_field_offset(demons_scratch(p, level->nx, level->ny, level->nz), level->nx, level->ny,
+                                             level->nz, l);
         if (sift3d_restrict2_launch(u[l - 1], level[l - 1].nx, level[l - 1].ny, level[l - 1].nz, 3, u[l], 0.5f,
                                     stream))
             return SIFT3D_FAILURE;
@@ -295,8 +397,9 @@ static int demons_drive(const char *what, const sift3d_amd_demons_level *level, 
                       (p->sigma_diffusion > 0 && gauss_filter(&fd, p->sigma_diffusion))))
         goto done;
     for (l = levels - 1; l >= 0; l--) {
-        if (demons_run(level + l, p, u[l], &ff, &fd, d_work,
-                       (char *)d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * rec, stream))
+        if ((p->logdomain ? logdemons_run : demons_run)(level + l, p, u[l], &ff, &fd, d_work,
+                                                  (char *)d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * rec,
+                                                  stream))
             goto done;
         rec += (size_t)level[l].iterations;
         if (l > 0 &&
@@ -316,7 +419,7 @@ int sift3d_amd_demons_device_ex(const float *d_F, int nx, int ny, int nz, const 
                                 void *stream)
 {
     const sift3d_amd_demons_level v = { d_F, nx, ny, nz, d_M, mx, my, mz, iterations };
-    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, update, squarings };
+    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, update, squarings, 0, 0, 0 };
     return demons_drive("sift3d_amd_demons_device_ex", &v, 1, &p, d_u, d_work,
                         sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, update), d_stats, stream);
 }
@@ -326,7 +429,7 @@ int sift3d_amd_demons_device(const float *d_F, int nx, int ny, int nz, const flo
                              double sigma_diffusion, float *d_work, void *d_stats, void *stream)
 {
     const sift3d_amd_demons_level v = { d_F, nx, ny, nz, d_M, mx, my, mz, iterations };
-    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, SIFT3D_AMD_DEMONS_ADDITIVE, 0 };
+    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, SIFT3D_AMD_DEMONS_ADDITIVE, 0, 0, 0, 0 };
     return demons_drive("sift3d_amd_demons_device", &v, 1, &p, d_u, d_work,
                         sift3d_amd_demons_work_floats(nx, ny, nz, nc), d_stats, stream);
 }
@@ -335,9 +438,28 @@ int sift3d_amd_demons_multires_device(const sift3d_amd_demons_level *level, int 
                                       double alpha, double sigma_fluid, double sigma_diffusion, int update,
                                       int squarings, float *d_work, void *d_stats, void *stream)
 {
-    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, update, squarings };
+    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, update, squarings, 0, 0, 0 };
     /* (a NULL level table is refused by the driver before the size matters) */
     const size_t need = level ? sift3d_amd_demons_multires_work_floats(level->nx, level->ny, level->nz, nc, update,
                                                                        levels) : 0;
     return demons_drive("sift3d_amd_demons_multires_device", level, levels, &p, d_u, d_work, need, d_stats, stream);
+}
+
+size_t sift3d_amd_logdemons_work_floats(int nx, int ny, int nz, int nc, int symmetric, int levels)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nc < 1 || (symmetric != 0 && symmetric != 1) || levels < 1 ||
+        levels > SIFT3D_AMD_DEMONS_MAX_LEVELS)
+        return 0;
+    return pyramid_field_offset(logdemons_layout_of(grid_voxels(nx, ny, nz), nc, symmetric).total, nx, ny, nz, levels);
+}
+
+int sift3d_amd_logdemons_device(const sift3d_amd_demons_level *level, int levels, int nc, float *d_v, double alpha,
+                                double sigma_fluid, double sigma_diffusion, int symmetric, int bch,
+                                int velocity_squarings, float *d_work, void *d_stats, void *stream)
+{
+    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, 0, velocity_squarings, 1, symmetric, bch };
+    /* (a NULL level table and a bad `symmetric` are refused by the driver before the size matters) */
+    const size_t need = level ? sift3d_amd_logdemons_work_floats(level->nx, level->ny, level->nz, nc, symmetric, levels)
+                              : 0;
+    return demons_drive("sift3d_amd_logdemons_device", level, levels, &p, d_v, d_work, need, d_stats, stream);
 }

@@ -358,6 +358,11 @@ def lib():
         "sift3d_amd_demons_multires_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "sift3d_amd_demons_multires_device": (C.c_int, [C.POINTER(DemonsLevel), C.c_int, C.c_int, vp, C.c_double,
                                                         C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_hip_field_bracket": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+        "sift3d_amd_field_exp_signed_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_amd_logdemons_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sift3d_amd_logdemons_device": (C.c_int, [C.POINTER(DemonsLevel), C.c_int, C.c_int, vp, C.c_double,
+                                                  C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -2023,9 +2028,10 @@ def field_compose(u, v, out=None, mode="compose", stats=None, work=None):
     return stats
 
 
-def field_exp(v, out, squarings, work=None):
-    """out = exp(v) by scaling and squaring (sift3d_amd_field_exp_device): v, out [3, oz, oy, ox] torch CUDA
-    float32, on torch's current stream."""
+def field_exp(v, out, squarings, work=None, negate=False):
+    """out = exp(v) by scaling and squaring (sift3d_amd_field_exp_device), or exp(-v) with negate
+    (sift3d_amd_field_exp_signed_device: the scaling's factor is -2^-K): v, out [3, oz, oy, ox] torch CUDA float32,
+    on torch's current stream."""
     _field_tensor(v, "field_exp", "v")
     _field_tensor(out, "field_exp", "out")
     if out.shape != v.shape:
@@ -2033,8 +2039,40 @@ def field_exp(v, out, squarings, work=None):
     _same_device("field_exp", v, out)
     _, oz, oy, ox = v.shape
     work = _work(work, lib().sift3d_amd_field_exp_work_floats(ox, oy, oz), v, "field_exp")
+    if negate:
+        _check(lib().sift3d_amd_field_exp_signed_device(v.data_ptr(), ox, oy, oz, int(squarings), 1, out.data_ptr(),
+                                                        work.data_ptr(), current_stream()),
+               "sift3d_amd_field_exp_signed_device")
+        return out
     _check(lib().sift3d_amd_field_exp_device(v.data_ptr(), ox, oy, oz, int(squarings), out.data_ptr(),
                                              work.data_ptr(), current_stream()), "sift3d_amd_field_exp_device")
+    return out
+
+
+FIELD_BRACKET_MODE = {"bracket": 0, "bch1": 1}
+
+
+def field_bracket(a, b, out=None, mode="bracket"):
+    """The Lie bracket [a, b] = J_a b - J_b a (mode "bracket") or the first-order BCH update a + b + [a, b] / 2
+    (mode "bch1") of two fields (sift3d_hip_field_bracket; contract in include/sift3d_amd.h, "Log-domain demons"):
+    a, b, out [3, oz, oy, ox] torch CUDA float32 on one grid (out None: allocated), on torch's current stream.  a may
+    be b; out must be neither."""
+    import torch
+    _field_tensor(a, "field_bracket", "a")
+    _field_tensor(b, "field_bracket", "b")
+    if mode not in FIELD_BRACKET_MODE:
+        raise ValueError("field_bracket: mode must be 'bracket' or 'bch1', not %r" % (mode,))
+    if b.shape != a.shape:
+        raise ValueError("field_bracket: b %s is not shaped like a %s" % (tuple(b.shape), tuple(a.shape)))
+    if out is None:
+        out = torch.empty_like(a)
+    _field_tensor(out, "field_bracket", "out")
+    if out.shape != a.shape:
+        raise ValueError("field_bracket: out %s is not shaped like a %s" % (tuple(out.shape), tuple(a.shape)))
+    _same_device("field_bracket", a, b, out)
+    _, oz, oy, ox = a.shape
+    _check(lib().sift3d_hip_field_bracket(a.data_ptr(), b.data_ptr(), ox, oy, oz, out.data_ptr(),
+                                          FIELD_BRACKET_MODE[mode], current_stream()), "sift3d_hip_field_bracket")
     return out
 
 
@@ -2104,6 +2142,31 @@ def field_prolong2(coarse, fine):
     return fine
 
 
+def _demons_levels(what, Fs, Ms, field, iterations):
+    """The level table of a pyramid driver and its checks: (table, levels, nc, iterations per level)"""
+    levels = len(Fs)
+    if not (1 <= levels <= DEMONS_MAX_LEVELS) or len(Ms) != levels:
+        raise ValueError("%s: 1 .. %d levels of fixed and as many of moving features" % (what, DEMONS_MAX_LEVELS))
+    its = [int(k) for k in iterations]
+    if len(its) != levels or any(k < 0 for k in its):
+        raise ValueError("%s: iterations must hold one count >= 0 per level" % what)
+    _field_tensor(field, what)
+    tab = (DemonsLevel * levels)()
+    nc0 = None
+    for l, (F, M) in enumerate(zip(Fs, Ms)):
+        # a level's checks are those of demons; only level 0 has its field here (the others' are in the work buffer)
+        level = "level %d " % l
+        nc, (nx, ny, nz), (mx, my, mz) = (_demons_pair(F, M, what, level) if l else
+                                          _demons_images(F, M, field, what, level))
+        if F.device != field.device or nc0 not in (None, nc):
+            raise ValueError("%s: level %d differs in channels or is not on the field's device" % (what, l))
+        nc0 = nc
+        if l and ((nz, ny, nx) != half_shape(Fs[l - 1].shape[-3:]) or (mz, my, mx) != half_shape(Ms[l - 1].shape[-3:])):
+            raise ValueError("%s: level %d is not the half of level %d" % (what, l, l - 1))
+        tab[l] = DemonsLevel(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, its[l])
+    return tab, levels, nc0, its
+
+
 def demons_multires(Fs, Ms, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None,
                     update="additive", squarings=0):
     """Coarse-to-fine demons (sift3d_amd_demons_multires_device; contract in include/sift3d_amd.h,
@@ -2114,27 +2177,8 @@ def demons_multires(Fs, Ms, field, iterations, alpha, sigma_fluid=0.0, sigma_dif
     iteration in the order run, the coarsest level's first (read it with demons_stats)."""
     import torch
     what = "demons_multires"
-    levels = len(Fs)
-    if not (1 <= levels <= DEMONS_MAX_LEVELS) or len(Ms) != levels:
-        raise ValueError("demons_multires: 1 .. %d levels of fixed and as many of moving features" % DEMONS_MAX_LEVELS)
-    its = [int(k) for k in iterations]
-    if len(its) != levels or any(k < 0 for k in its):
-        raise ValueError("demons_multires: iterations must hold one count >= 0 per level")
     mode = _demons_update(update, what)
-    _field_tensor(field, what)
-    tab = (DemonsLevel * levels)()
-    nc0 = None
-    for l, (F, M) in enumerate(zip(Fs, Ms)):
-        # a level's checks are those of demons; only level 0 has its field here (the others' are in the work buffer)
-        level = "level %d " % l
-        nc, (nx, ny, nz), (mx, my, mz) = (_demons_pair(F, M, what, level) if l else
-                                          _demons_images(F, M, field, what, level))
-        if F.device != field.device or nc0 not in (None, nc):
-            raise ValueError("demons_multires: level %d differs in channels or is not on the field's device" % l)
-        nc0 = nc
-        if l and ((nz, ny, nx) != half_shape(Fs[l - 1].shape[-3:]) or (mz, my, mx) != half_shape(Ms[l - 1].shape[-3:])):
-            raise ValueError("demons_multires: level %d is not the half of level %d" % (l, l - 1))
-        tab[l] = DemonsLevel(F.data_ptr(), nx, ny, nz, M.data_ptr(), mx, my, mz, its[l])
+    tab, levels, nc0, its = _demons_levels(what, Fs, Ms, field, iterations)
     _, nz, ny, nx = field.shape
     work = _work(work, lib().sift3d_amd_demons_multires_work_floats(nx, ny, nz, nc0, mode, levels), field, what)
     total = sum(its)
@@ -2143,6 +2187,34 @@ def demons_multires(Fs, Ms, field, iterations, alpha, sigma_fluid=0.0, sigma_dif
                                                    float(sigma_fluid), float(sigma_diffusion), mode,
                                                    int(squarings), work.data_ptr(), stats.data_ptr(),
                                                    current_stream()), "sift3d_amd_demons_multires_device")
+    return stats[:total * DEMONS_STATS_BYTES // 8]
+
+
+def logdemons(Fs, Ms, velocity, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, symmetric=False, bch=1,
+              velocity_squarings=0, work=None):
+    """Log-domain demons (sift3d_amd_logdemons_device; contract in include/sift3d_amd.h, "Log-domain demons"): the
+    stationary velocity [3, nz, ny, nx] on Fs[0]'s grid is refined in place so that the moving features read through
+    exp(velocity) approach the fixed ones.  Fs, Ms, iterations: the levels as in demons_multires (one level: a flat
+    run).  symmetric: forces from both directions (fixed and moving shapes must agree); bch 0: v += delta, 1: the
+    BCH update with the first Lie bracket; velocity_squarings: the squarings of every exponential.  torch CUDA
+    float32, on torch's current stream, no host synchronisation.  Returns the stats tensor: 16 bytes per iteration
+    in the order run (read it with demons_stats)."""
+    import torch
+    what = "logdemons"
+    if bch not in (0, 1):
+        raise ValueError("logdemons: bch must be 0 or 1, not %r" % (bch,))
+    tab, levels, nc0, its = _demons_levels(what, Fs, Ms, velocity, iterations)
+    sym = 1 if symmetric else 0
+    if sym and any(tuple(F.shape) != tuple(M.shape) for F, M in zip(Fs, Ms)):
+        raise ValueError("logdemons: the symmetric update needs fixed and moving volumes of one shape")
+    _, nz, ny, nx = velocity.shape
+    work = _work(work, lib().sift3d_amd_logdemons_work_floats(nx, ny, nz, nc0, sym, levels), velocity, what)
+    total = sum(its)
+    stats = torch.empty(max(total, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=velocity.device)
+    _check(lib().sift3d_amd_logdemons_device(tab, levels, nc0, velocity.data_ptr(), float(alpha), float(sigma_fluid),
+                                             float(sigma_diffusion), sym, int(bch), int(velocity_squarings),
+                                             work.data_ptr(), stats.data_ptr(), current_stream()),
+           "sift3d_amd_logdemons_device")
     return stats[:total * DEMONS_STATS_BYTES // 8]
 
 
