@@ -1787,8 +1787,8 @@ sift3d_amd_demons_multires_device(const sift3d_amd_demons_level *level, int leve
  * velocities).
  *
  * Out of scope: a start displacement field or affine map under the velocity (v starts from the caller's velocity
- * or zero); BCH terms beyond the first bracket; a device-side choice of Kv; the backward statistics; masks, physical
- * spacing, multi-GPU.
+ * or zero); BCH terms beyond the first bracket; a device-side choice of Kv; the backward statistics; physical
+ * spacing, multi-GPU.  (Masks: "Masks in demons" below.)
  *
  * Measured on an MI355X: on the 176^3 lattice case from zero, three levels, the forward error of
  * LOG is 1.0087 (median) and 1.0006 (p90) times the diffeomorphic update's, SYMMETRIC's 1.0086 and 1.0081; neither
@@ -1815,6 +1815,72 @@ SIFT3D_AMD_API int
 sift3d_amd_logdemons_device(const sift3d_amd_demons_level *level, int levels, int nc, float *d_v, double alpha,
                             double sigma_fluid, double sigma_diffusion, int symmetric, int bch, int velocity_squarings,
                             float *d_work, void *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Masks in demons                                                          */
+/* ------------------------------------------------------------------------ */
+/* Regions of interest for the dense path: which fixed voxels the demons force counts.  A delta on "Dense demons
+ * refinement" and "Masks"; everything not restated here is theirs, word for word.
+ *
+ * The masks: W_F [nz][ny][nx] on the fixed grid, W_M [mz][my][mx] on the moving grid, float32, one plane each whatever
+ * nc.  Either may be NULL: all in.  A voxel is in when w >= 0.5f ("Masks"' rule: a NaN, a negative value and
+ * nextafterf(0.5f, 0) are out; 0.5f, 1, 2 and +inf are in).
+ *
+ * The masked force delta = force_masked(F, W, u, W_F, W_M) replaces step 1 of the force by counted(p): all of
+ *   - inside(p), the unmasked test;
+ *   - W_F(p) is in;
+ *   - W_M at the voxel floor(q_d + 0.5) per axis (double) is in, for the same q_d = (double) p_d + (double) u_d(p) that
+ *     the inside test uses ("Resampling"'s NEAREST rule; for an inside q the voxel is on the grid).
+ * A voxel that is not counted gets delta(p) = +0.0f on all three channels and adds nothing to the statistics.  Steps
+ * 2 - 5 are unchanged; the statistics are the sum of s_d and the count over the counted voxels, through the unmasked partial
+ * slots in the unmasked order.  The derivative stencils still read F and W at masked-out neighbours: the volumes must
+ * be finite everywhere, masked-out voxels included; mask values need not be.  With both masks NULL, or both all in, a
+ * masked entry writes the bytes of its unmasked counterpart.
+ *
+ * Iterations: step 2 of "Dense demons refinement" (ADDITIVE and DIFFEOMORPHIC) and step 3 of LOG use force_masked with
+ * the level's masks; every other step is word for word.  The fluid and diffusion blurs are the unmasked ones: they
+ * carry the field into masked-out voxels, where it is the smooth extension of its surroundings and no measurement.
+ * With both sigmas 0 and the additive update a voxel that is never counted keeps its start bits (u + 0.0f; a start -0.0f
+ * becomes +0.0f).  What F holds where the whole 3 x 3 x 3 neighbourhood of a voxel is out of W_F never reaches the
+ * result: the stencil reaches one voxel and W does not depend on F.
+ * SYMMETRIC: the backward force is force_masked(M, W_b, e-, W_M, W_F): the roles exchange with the volumes, W_M tested
+ * at p and W_F at floor(p + e-(p) + 0.5).  Exchanging (F, W_F) with (M, W_M) therefore exchanges Z_f and Z_b bit for
+ * bit, as the unmasked property does.
+ * Levels: the caller passes the masks per level, as it passes the feature stacks; a mask's dimensions are those of its
+ * level's fixed or moving grid; each pointer of each level may be NULL independently.  (sift3d_amd.api restricts the
+ * float masks with sift3d_hip_restrict2, scale 1, level by level, never a thresholded copy, as "Masks"' drivers do.)
+ * No new scratch: the work-float figures are the unmasked ones.
+ *
+ * Entries: sift3d_hip_demons_force_masked is sift3d_hip_demons_force with d_WF, d_WM at the end ("Masks"' convention).
+ * sift3d_amd_demons_masked_device takes masks [levels] after the level table and the rest as
+ * sift3d_amd_demons_multires_device (levels == 1: the flat run; masks == NULL: the unmasked entry bit for bit);
+ * sift3d_amd_logdemons_masked_device the same over sift3d_amd_logdemons_device.  Refusals (-1, before any device call)
+ * are the unmasked entries', and: a non-NULL mask that is not 4-byte aligned; a non-NULL mask that overlaps d_u / d_v,
+ * d_step, d_stats or d_work.
+ *
+ * Out of scope: weighted (soft) masks; masks in the keypoint stages of registration and in label overlap; a
+ * mask-aware (normalised) smoothing of the field. */
+typedef struct {
+    const float *d_WF;         /* fixed mask  [nz][ny][nx] of the level, or NULL */
+    const float *d_WM;         /* moving mask [mz][my][mx] of the level, or NULL */
+} sift3d_amd_demons_level_masks;
+SIFT3D_AMD_API int
+sift3d_hip_demons_force_masked(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx,
+                               int my, int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work,
+                               void *stream, const float *d_WF, const float *d_WM);
+/* level [levels], masks [levels] or NULL (host memory, level 0 the finest); d_u [3][nz_0][ny_0][nx_0] in / out; d_work
+ * sift3d_amd_demons_multires_work_floats floats */
+SIFT3D_AMD_API int
+sift3d_amd_demons_masked_device(const sift3d_amd_demons_level *level, const sift3d_amd_demons_level_masks *masks,
+                                int levels, int nc, float *d_u, double alpha, double sigma_fluid,
+                                double sigma_diffusion, int update, int squarings, float *d_work, void *d_stats,
+                                void *stream);
+/* the same for a velocity; d_work sift3d_amd_logdemons_work_floats floats */
+SIFT3D_AMD_API int
+sift3d_amd_logdemons_masked_device(const sift3d_amd_demons_level *level, const sift3d_amd_demons_level_masks *masks,
+                                   int levels, int nc, float *d_v, double alpha, double sigma_fluid,
+                                   double sigma_diffusion, int symmetric, int bch, int velocity_squarings,
+                                   float *d_work, void *d_stats, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */

@@ -1639,7 +1639,7 @@ def demons_squarings(alpha):
 def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA,
                  sigma_fluid=DEMONS_SIGMA_FLUID, sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors",
                  sigma=1.6, update="additive", squarings=None, levels=1, level_iterations=None, velocity=None, bch=1,
-                 max_motion=16.0, velocity_squarings=None):
+                 max_motion=16.0, velocity_squarings=None, mask_fixed=None, mask_moving=None):
     """Dense demons refinement (contract: include/sift3d_amd.h, "Dense demons refinement") of a displacement
     field [3, nz, ny, nx] on fixed's grid (a pull map fixed voxel -> moving voxel; None: start from zero) so that
     the moving features warped through it agree with the fixed ones at every voxel.  moving, fixed: torch CUDA
@@ -1666,7 +1666,16 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     exponential, None: field_squarings(max_motion), enough for velocities up to max_motion voxels; a warning is
     issued when the result's max|v| 2^-Kv exceeds 0.5.  `squarings` is not used.  Returns LogDemonsRefinement (with
     levels > 1 MultiresLogDemonsRefinement, which adds level_slices): field = exp(v), inverse = exp(-v), velocity,
-    warped (moving through field), msd, jacobian and inverse_jacobian (of field and inverse), scaled_max."""
+    warped (moving through field), msd, jacobian and inverse_jacobian (of field and inverse), scaled_max.
+    mask_fixed, mask_moving ("Masks in demons"): regions of interest on fixed's and moving's grids, each None (all in)
+    or a bool, integer or float array or CUDA tensor of its volume's shape (in where non-zero; floats in where >= 0.5).
+    A fixed voxel drives the force only where it samples inside, is in mask_fixed and lands (nearest voxel) in
+    mask_moving; elsewhere the force is 0 and the field is what the two blurs carry there, the smooth extension of its
+    surroundings.  msd is then the mean over the counted voxels.  Every update accepts masks; "symmetric" exchanges
+    them with the volumes in its backward force.  With levels > 1 level l's mask is the restriction (restrict_volume)
+    of level l - 1's float mask, never a thresholded copy.  With features "descriptors" the descriptor images are
+    still computed from the whole volumes: the masks act on the force only.  With both None the calls are the
+    unmasked ones."""
     import torch
     from . import hip
     log = update in LOGDEMONS_UPDATES
@@ -1680,6 +1689,9 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
         if update == "symmetric" and tuple(np.shape(moving)) != tuple(np.shape(fixed)):
             raise ValueError("update 'symmetric' needs moving %s and fixed %s of one shape"
                              % (tuple(np.shape(moving)), tuple(np.shape(fixed))))
+    # (the masks against their volumes' shapes too: before anything is uploaded)
+    wf = _mask_host(mask_fixed, fixed, "refine_field", "mask_fixed")
+    wm = _mask_host(mask_moving, moving, "refine_field", "mask_moving")
     _volume_tensor(moving, "refine_field", "moving")
     _volume_tensor(fixed, "refine_field", "fixed")
     if not log and update not in DEMONS_UPDATES:
@@ -1694,10 +1706,21 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     if features not in ("descriptors", "intensity"):
         raise ValueError("features must be 'descriptors' or 'intensity', not %r" % (features,))
     its = [int(iterations)] * levels if level_iterations is None else level_iterations
+    wf = _mask_tensor(wf, fixed, "refine_field", "mask_fixed")
+    wm = _mask_tensor(wm, fixed, "refine_field", "mask_moving")     # (on the fixed volume's device, as every mask)
     fv, mv = [fixed], [moving]
     for _ in range(1, levels):
         fv.append(hip.restrict2(fv[-1]))
         mv.append(hip.restrict2(mv[-1]))
+    # the masks per level: the restriction of the float mask of the level above (None stays None)
+    WFs, WMs = [wf], [wm]
+    for _ in range(1, levels):
+        WFs.append(None if WFs[-1] is None else hip.restrict2(WFs[-1]))
+        WMs.append(None if WMs[-1] is None else hip.restrict2(WMs[-1]))
+    if wf is None:
+        WFs = None
+    if wm is None:
+        WMs = None
     if features == "descriptors":
         Fs = [dense_descriptors(v, sigma) for v in fv]
         Ms = [dense_descriptors(v, sigma) for v in mv]
@@ -1705,7 +1728,7 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
         Fs, Ms = fv, mv
     if log:
         return _refine_velocity(moving, fixed, Fs, Ms, its, velocity, alpha, sigma_fluid, sigma_diffusion,
-                                update == "symmetric", bch, max_motion, velocity_squarings)
+                                update == "symmetric", bch, max_motion, velocity_squarings, WFs, WMs)
     if field is None:
         u = torch.zeros((3,) + tuple(fixed.shape), dtype=torch.float32, device=fixed.device)
     else:
@@ -1715,9 +1738,11 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     if update != "additive":
         K = demons_squarings(alpha) if squarings is None else int(squarings)
     if levels == 1:
-        stats = hip.demons(Fs[0], Ms[0], u, its[0], alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
+        stats = hip.demons(Fs[0], Ms[0], u, its[0], alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K,
+                           mask_fixed=wf, mask_moving=wm)
     else:
-        stats = hip.demons_multires(Fs, Ms, u, its, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K)
+        stats = hip.demons_multires(Fs, Ms, u, its, alpha, sigma_fluid, sigma_diffusion, update=update, squarings=K,
+                                    masks_fixed=WFs, masks_moving=WMs)
     msd = _mean_or_nan(*hip.demons_stats(stats))
     warped = warp_field(moving, u, "linear", 0.0)
     if levels == 1:
@@ -1730,8 +1755,9 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
 
 
 def _refine_velocity(moving, fixed, Fs, Ms, its, velocity, alpha, sigma_fluid, sigma_diffusion, symmetric, bch,
-                     max_motion, velocity_squarings):
-    """refine_field's log-domain updates, after its checks: Fs, Ms the feature stacks per level"""
+                     max_motion, velocity_squarings, WFs=None, WMs=None):
+    """refine_field's log-domain updates, after its checks: Fs, Ms the feature stacks per level, WFs, WMs the masks per
+    level or None"""
     import torch
     from . import hip
     levels = len(Fs)
@@ -1741,7 +1767,8 @@ def _refine_velocity(moving, fixed, Fs, Ms, its, velocity, alpha, sigma_fluid, s
         hip._field_tensor(velocity, "refine_field", "velocity")
         v = velocity.clone()
     Kv = field_squarings(max_motion) if velocity_squarings is None else int(velocity_squarings)
-    stats = hip.logdemons(Fs, Ms, v, its, alpha, sigma_fluid, sigma_diffusion, symmetric, bch, Kv)
+    stats = hip.logdemons(Fs, Ms, v, its, alpha, sigma_fluid, sigma_diffusion, symmetric, bch, Kv, masks_fixed=WFs,
+                          masks_moving=WMs)
     msd = _mean_or_nan(*hip.demons_stats(stats))
     u = field_exp(v, Kv)
     w = field_exp(v, Kv, negate=True)
@@ -1787,17 +1814,18 @@ def prolong_field(field, out_shape):
 
 def register_dense(moving, fixed, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA, sigma_fluid=DEMONS_SIGMA_FLUID,
                    sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, update="additive",
-                   squarings=None, levels=1, level_iterations=None, **deformable_kw):
+                   squarings=None, levels=1, level_iterations=None, mask_fixed=None, mask_moving=None, **deformable_kw):
     """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field (update,
     squarings, levels and level_iterations as there).  Returns DenseRegistration(A, tps, inliers, num_matches (as
     register_deformable), field, warped, msd, jacobian (as refine_field)); with levels > 1 MultiresRegistration,
-    which adds refine_field's level_slices."""
+    which adds refine_field's level_slices.  mask_fixed, mask_moving: handed to the refine_field stage only (as
+    there); the keypoint and spline stages see the whole volumes."""
     _volume_tensor(moving, "register_dense", "moving")
     _volume_tensor(fixed, "register_dense", "fixed")
     d = register_deformable(moving, fixed, **deformable_kw)
     u = displacement_field(d.tps, tuple(fixed.shape), fixed.device)
     r = refine_field(moving, fixed, u, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma, update,
-                     squarings, levels, level_iterations)
+                     squarings, levels, level_iterations, mask_fixed=mask_fixed, mask_moving=mask_moving)
     if int(levels) > 1:
         return MultiresRegistration(d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped, r.msd, r.jacobian,
                                     r.level_slices)

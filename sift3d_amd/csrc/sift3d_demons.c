@@ -1,7 +1,9 @@
 /* sift3d_demons.c -- dense demons refinement of a displacement field: the checked force, the two grid transfers
  * and the one driver behind sift3d_amd_demons_device, sift3d_amd_demons_device_ex and
  * sift3d_amd_demons_multires_device, and sift3d_amd_logdemons_device, which runs its own iteration (logdemons_run)
- * through the same driver (included at the end of sift3d_host.c, after sift3d_field_ops.c).
+ * through the same driver, and the masked forms of the force and of the two pyramid entries ("Masks in demons": the
+ * same functions with the masks, which the unmasked entries pass as NULL) (included at the end of sift3d_host.c, after
+ * sift3d_field_ops.c).
  *
  * The contract is in include/sift3d_amd.h, "Dense demons refinement", "Diffeomorphic demons", "Multi-resolution
  * demons" and "Log-domain demons".  The force and the additive update are kernels of sift3d_demons.hip, the bracket
@@ -14,7 +16,7 @@
 
 int sift3d_demons_force_launch(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx,
                                int my, int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work,
-                               void *stream);
+                               void *stream, const float *d_WF, const float *d_WM);
 int sift3d_demons_field_add_launch(float *d_u, const float *d_step, size_t n, void *stream);
 int sift3d_restrict2_launch(const float *d_src, int nx, int ny, int nz, int nc, float *d_dst, float scale,
                             void *stream);
@@ -33,11 +35,22 @@ static int check_update(const char *what, int update)
                ? refuse(what, "unknown update") : SIFT3D_SUCCESS;
 }
 
-int sift3d_hip_demons_force(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx,
-                            int my, int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work,
-                            void *stream)
+/* a non-NULL mask (n voxels) is 4-byte aligned and overlaps none of the nout ranges the call writes */
+static int check_demons_mask(const char *what, const float *d_w, size_t n, const range_t *out, int nout)
 {
-    static const char what[] = "sift3d_hip_demons_force";
+    const range_t r = { d_w, n * sizeof(float) };
+    if (!d_w)
+        return SIFT3D_SUCCESS;
+    if (check_aligned(what, 0, ADDR(d_w)))
+        return SIFT3D_FAILURE;
+    return ranges_aliased(out, nout, &r, 1) ? refuse(what, ALIASED) : SIFT3D_SUCCESS;
+}
+
+/* the shared body of the two force entries: d_WF, d_WM are the masks ("Masks in demons") or NULL */
+static int demons_force_entry(const char *what, const float *d_F, int nx, int ny, int nz, const float *d_W,
+                              const float *d_u, int mx, int my, int mz, int nc, double alpha, float *d_step,
+                              void *d_stats, void *d_work, void *stream, const float *d_WF, const float *d_WM)
+{
     if (!d_F || !d_W || !d_u || !d_step || !d_stats || !d_work)
         return refuse(what, "NULL argument");
     if (check_dims(what, nx, ny, nz) || check_dims(what, mx, my, mz) || check_channels(what, nc) ||
@@ -51,9 +64,28 @@ int sift3d_hip_demons_force(const float *d_F, int nx, int ny, int nz, const floa
                                 { d_work, SIFT3D_AMD_DEMONS_FORCE_WORK_BYTES } };
         if (ranges_aliased(out, 3, in, 3))
             return refuse(what, ALIASED);
+        if (check_demons_mask(what, d_WF, grid_voxels(nx, ny, nz), out, 3) ||
+            check_demons_mask(what, d_WM, grid_voxels(mx, my, mz), out, 3))
+            return SIFT3D_FAILURE;
     }
     return sift3d_demons_force_launch(d_F, nx, ny, nz, d_W, d_u, mx, my, mz, nc, alpha, d_step, d_stats, d_work,
-                                      stream);
+                                      stream, d_WF, d_WM);
+}
+
+int sift3d_hip_demons_force(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx,
+                            int my, int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work,
+                            void *stream)
+{
+    return demons_force_entry("sift3d_hip_demons_force", d_F, nx, ny, nz, d_W, d_u, mx, my, mz, nc, alpha, d_step,
+                              d_stats, d_work, stream, NULL, NULL);
+}
+
+int sift3d_hip_demons_force_masked(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx,
+                                   int my, int mz, int nc, double alpha, float *d_step, void *d_stats, void *d_work,
+                                   void *stream, const float *d_WF, const float *d_WM)
+{
+    return demons_force_entry("sift3d_hip_demons_force_masked", d_F, nx, ny, nz, d_W, d_u, mx, my, mz, nc, alpha,
+                              d_step, d_stats, d_work, stream, d_WF, d_WM);
 }
 
 /* ---- the grid transfers ---- */
@@ -211,9 +243,10 @@ static int check_log(const char *what, const demons_params *p)
     return p->bch != 0 && p->bch != 1 ? refuse(what, "bch must be 0 or 1") : SIFT3D_SUCCESS;
 }
 
-/* 0 when the problem may run: level [levels] (level 0 the finest), the field d_u on level 0's grid, work_floats
- * floats of d_work, one statistics record per iteration (room for one when there is none) */
-static int demons_validate(const char *what, const sift3d_amd_demons_level *level, int levels, const demons_params *p,
+/* 0 when the problem may run: level [levels] (level 0 the finest), masks [levels] or NULL, the field d_u on level
+ * 0's grid, work_floats floats of d_work, one statistics record per iteration (room for one when there is none) */
+static int demons_validate(const char *what, const sift3d_amd_demons_level *level,
+                           const sift3d_amd_demons_level_masks *masks, int levels, const demons_params *p,
                            const float *d_u, const float *d_work, size_t work_floats, const void *d_stats)
 {
     range_t in[2 * SIFT3D_AMD_DEMONS_MAX_LEVELS];
@@ -256,6 +289,10 @@ static int demons_validate(const char *what, const sift3d_amd_demons_level *leve
                                 { d_stats, (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * (total > 0 ? total : 1) } };
         if (ranges_aliased(out, 3, in, 2 * levels))
             return refuse(what, ALIASED);
+        for (l = 0; masks && l < levels; l++)
+            if (check_demons_mask(what, masks[l].d_WF, grid_voxels(level[l].nx, level[l].ny, level[l].nz), out, 3) ||
+                check_demons_mask(what, masks[l].d_WM, grid_voxels(level[l].mx, level[l].my, level[l].mz), out, 3))
+                return SIFT3D_FAILURE;
     }
     return SIFT3D_SUCCESS;
 }
@@ -273,10 +310,11 @@ static int demons_blur3(const float *src, float *dst, const int *dims, const fil
     return SIFT3D_SUCCESS;
 }
 
-/* v->iterations iterations of one level on its field d_u, unchecked; ff, fd: the filters of the two sigmas (read
- * only where the sigma is positive); one statistics record per iteration from d_stats on */
-static int demons_run(const sift3d_amd_demons_level *v, const demons_params *p, float *d_u, const filter_t *ff,
-                      const filter_t *fd, float *d_work, char *d_stats, void *stream)
+/* v->iterations iterations of one level on its field d_u, unchecked; d_WF, d_WM: the level's masks or NULL; ff, fd:
+ * the filters of the two sigmas (read only where the sigma is positive); one statistics record per iteration from
+ * d_stats on */
+static int demons_run(const sift3d_amd_demons_level *v, const float *d_WF, const float *d_WM, const demons_params *p,
+                      float *d_u, const filter_t *ff, const filter_t *fd, float *d_work, char *d_stats, void *stream)
 {
     const int dims[3] = { v->nx, v->ny, v->nz };
     const size_t n = grid_voxels(v->nx, v->ny, v->nz);
@@ -289,7 +327,8 @@ static int demons_run(const sift3d_amd_demons_level *v, const demons_params *p, 
         if (sift3d_hip_warp_field(v->d_M, v->mx, v->my, v->mz, p->nc, d_u, v->nx, v->ny, v->nz, d_W,
                                   SIFT3D_AMD_INTERP_LINEAR, 0.0f, stream) ||
             sift3d_demons_force_launch(v->d_F, v->nx, v->ny, v->nz, d_W, d_u, v->mx, v->my, v->mz, p->nc, p->alpha,
-                                       d_step, d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * k, d_work, stream))
+                                       d_step, d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * k, d_work, stream,
+                                       d_WF, d_WM))
             return SIFT3D_FAILURE;
         if (p->sigma_fluid > 0 && demons_blur3(d_step, d_step, dims, ff, d_tmp, stream))
             return SIFT3D_FAILURE;
@@ -317,8 +356,9 @@ static int demons_run(const sift3d_amd_demons_level *v, const demons_params *p, 
 
 /* v->iterations iterations of log-domain demons on one level's velocity d_v, unchecked ("Log-domain demons": LOG, or
  * SYMMETRIC with p->symmetric); arguments as demons_run's */
-static int logdemons_run(const sift3d_amd_demons_level *v, const demons_params *p, float *d_v, const filter_t *ff,
-                         const filter_t *fd, float *d_work, char *d_stats, void *stream)
+static int logdemons_run(const sift3d_amd_demons_level *v, const float *d_WF, const float *d_WM,
+                         const demons_params *p, float *d_v, const filter_t *ff, const filter_t *fd, float *d_work,
+                         char *d_stats, void *stream)
 {
     const int dims[3] = { v->nx, v->ny, v->nz };
     const size_t n = grid_voxels(v->nx, v->ny, v->nz);
@@ -334,7 +374,8 @@ static int logdemons_run(const sift3d_amd_demons_level *v, const demons_params *
             sift3d_hip_warp_field(v->d_M, v->mx, v->my, v->mz, p->nc, e, v->nx, v->ny, v->nz, d_W,
                                   SIFT3D_AMD_INTERP_LINEAR, 0.0f, stream) ||
             sift3d_demons_force_launch(v->d_F, v->nx, v->ny, v->nz, d_W, e, v->mx, v->my, v->mz, p->nc, p->alpha,
-                                       d_step, d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * k, d_work, stream) ||
+                                       d_step, d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * k, d_work, stream,
+                                       d_WF, d_WM) ||
             (p->sigma_fluid > 0 && demons_blur3(d_step, d_step, dims, ff, d_tmp, stream)))
             return SIFT3D_FAILURE;
         if (!p->symmetric) {
@@ -347,12 +388,13 @@ static int logdemons_run(const sift3d_amd_demons_level *v, const demons_params *
                 return SIFT3D_FAILURE;
             continue;
         }
-        /* the backward force: the roles of F and M exchanged (one shape), read through e- = exp(-v) */
+        /* the backward force: the roles of F and M, and of their masks, exchanged (one shape), read through
+         * e- = exp(-v) */
         if (field_exp_run(d_v, v->nx, v->ny, v->nz, K, -1.0, d_e, d_pp, stream) ||
             sift3d_hip_warp_field(v->d_F, v->nx, v->ny, v->nz, p->nc, d_e, v->nx, v->ny, v->nz, d_W,
                                   SIFT3D_AMD_INTERP_LINEAR, 0.0f, stream) ||
             sift3d_demons_force_launch(v->d_M, v->nx, v->ny, v->nz, d_W, d_e, v->nx, v->ny, v->nz, p->nc, p->alpha,
-                                       d_stepb, d_work + at.bstats, d_work, stream) ||
+                                       d_stepb, d_work + at.bstats, d_work, stream, d_WM, d_WF) ||
             (p->sigma_fluid > 0 && demons_blur3(d_stepb, d_stepb, dims, ff, d_tmp, stream)))
             return SIFT3D_FAILURE;
         if (p->bch) {
@@ -372,14 +414,15 @@ static int logdemons_run(const sift3d_amd_demons_level *v, const demons_params *
 
 /* The three entries: validate once, restrict the field down the pyramid (nothing with one level), build the two
  * filters once when there is an iteration to run, then per level, coarsest first, run it and hand its field up. */
-static int demons_drive(const char *what, const sift3d_amd_demons_level *level, int levels, const demons_params *p,
-                        float *d_u, float *d_work, size_t work_floats, void *d_stats, void *stream)
+static int demons_drive(const char *what, const sift3d_amd_demons_level *level,
+                        const sift3d_amd_demons_level_masks *masks, int levels, const demons_params *p, float *d_u,
+                        float *d_work, size_t work_floats, void *d_stats, void *stream)
 {
     float *u[SIFT3D_AMD_DEMONS_MAX_LEVELS];
     filter_t ff, fd;
     size_t rec = 0, total = 0;
     int l, rc = SIFT3D_FAILURE;
-    if (demons_validate(what, level, levels, p, d_u, d_work, work_floats, d_stats))
+    if (demons_validate(what, level, masks, levels, p, d_u, d_work, work_floats, d_stats))
         return SIFT3D_FAILURE;
     /* the level fields: level 0 is d_u, the others follow the finest level's scratch in d_work */
     u[0] = d_u;
@@ -397,7 +440,8 @@ static int demons_drive(const char *what, const sift3d_amd_demons_level *level, 
                       (p->sigma_diffusion > 0 && gauss_filter(&fd, p->sigma_diffusion))))
         goto done;
     for (l = levels - 1; l >= 0; l--) {
-        if ((p->logdomain ? logdemons_run : demons_run)(level + l, p, u[l], &ff, &fd, d_work,
+        if ((p->logdomain ? logdemons_run : demons_run)(level + l, masks ? masks[l].d_WF : NULL,
+                                                  masks ? masks[l].d_WM : NULL, p, u[l], &ff, &fd, d_work,
                                                   (char *)d_stats + (size_t)SIFT3D_AMD_DEMONS_STATS_BYTES * rec,
                                                   stream))
             goto done;
@@ -420,7 +464,7 @@ int sift3d_amd_demons_device_ex(const float *d_F, int nx, int ny, int nz, const 
 {
     const sift3d_amd_demons_level v = { d_F, nx, ny, nz, d_M, mx, my, mz, iterations };
     const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, update, squarings, 0, 0, 0 };
-    return demons_drive("sift3d_amd_demons_device_ex", &v, 1, &p, d_u, d_work,
+    return demons_drive("sift3d_amd_demons_device_ex", &v, NULL, 1, &p, d_u, d_work,
                         sift3d_amd_demons_work_floats_ex(nx, ny, nz, nc, update), d_stats, stream);
 }
 
@@ -430,7 +474,7 @@ int sift3d_amd_demons_device(const float *d_F, int nx, int ny, int nz, const flo
 {
     const sift3d_amd_demons_level v = { d_F, nx, ny, nz, d_M, mx, my, mz, iterations };
     const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, SIFT3D_AMD_DEMONS_ADDITIVE, 0, 0, 0, 0 };
-    return demons_drive("sift3d_amd_demons_device", &v, 1, &p, d_u, d_work,
+    return demons_drive("sift3d_amd_demons_device", &v, NULL, 1, &p, d_u, d_work,
                         sift3d_amd_demons_work_floats(nx, ny, nz, nc), d_stats, stream);
 }
 
@@ -442,7 +486,20 @@ int sift3d_amd_demons_multires_device(const sift3d_amd_demons_level *level, int 
     /* (a NULL level table is refused by the driver before the size matters) */
     const size_t need = level ? sift3d_amd_demons_multires_work_floats(level->nx, level->ny, level->nz, nc, update,
                                                                        levels) : 0;
-    return demons_drive("sift3d_amd_demons_multires_device", level, levels, &p, d_u, d_work, need, d_stats, stream);
+    return demons_drive("sift3d_amd_demons_multires_device", level, NULL, levels, &p, d_u, d_work, need, d_stats,
+                        stream);
+}
+
+int sift3d_amd_demons_masked_device(const sift3d_amd_demons_level *level, const sift3d_amd_demons_level_masks *masks,
+                                    int levels, int nc, float *d_u, double alpha, double sigma_fluid,
+                                    double sigma_diffusion, int update, int squarings, float *d_work, void *d_stats,
+                                    void *stream)
+{
+    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, update, squarings, 0, 0, 0 };
+    const size_t need = level ? sift3d_amd_demons_multires_work_floats(level->nx, level->ny, level->nz, nc, update,
+                                                                       levels) : 0;
+    return demons_drive("sift3d_amd_demons_masked_device", level, masks, levels, &p, d_u, d_work, need, d_stats,
+                        stream);
 }
 
 size_t sift3d_amd_logdemons_work_floats(int nx, int ny, int nz, int nc, int symmetric, int levels)
@@ -461,5 +518,17 @@ int sift3d_amd_logdemons_device(const sift3d_amd_demons_level *level, int levels
     /* (a NULL level table and a bad `symmetric` are refused by the driver before the size matters) */
     const size_t need = level ? sift3d_amd_logdemons_work_floats(level->nx, level->ny, level->nz, nc, symmetric, levels)
                               : 0;
-    return demons_drive("sift3d_amd_logdemons_device", level, levels, &p, d_v, d_work, need, d_stats, stream);
+    return demons_drive("sift3d_amd_logdemons_device", level, NULL, levels, &p, d_v, d_work, need, d_stats, stream);
+}
+
+int sift3d_amd_logdemons_masked_device(const sift3d_amd_demons_level *level,
+                                       const sift3d_amd_demons_level_masks *masks, int levels, int nc, float *d_v,
+                                       double alpha, double sigma_fluid, double sigma_diffusion, int symmetric, int bch,
+                                       int velocity_squarings, float *d_work, void *d_stats, void *stream)
+{
+    const demons_params p = { nc, alpha, sigma_fluid, sigma_diffusion, 0, velocity_squarings, 1, symmetric, bch };
+    const size_t need = level ? sift3d_amd_logdemons_work_floats(level->nx, level->ny, level->nz, nc, symmetric, levels)
+                              : 0;
+    return demons_drive("sift3d_amd_logdemons_masked_device", level, masks, levels, &p, d_v, d_work, need, d_stats,
+                        stream);
 }

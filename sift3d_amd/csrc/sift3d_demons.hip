@@ -14,12 +14,25 @@
 // butterfly, per workgroup through LDS into partial slot blockIdx.x; k_demons_finish adds the slots in a fixed
 // order.  The grid is min(tiles, DEM_GRID) workgroups whatever the device, so the bits of the sum depend on the
 // shape alone.
+//
+// k_demons_force<true> is the masked force (contract: "Masks in demons"): W_F is read beside u, W_M gathered at q's
+// nearest voxel (mask_offset: an outside q reads voxel 0, no branch), and a plane is counted when it is inside and in
+// both masks.  The tile loop has no barrier and a wave's DPP neighbours are its own lanes, so a wave none of whose
+// lanes has a counted plane in the tile writes its zeros and skips the channel loop: it reads u and W_F (and W_M) only.
+// The flags are needed before the first channel's loads for that, so <true> waits for u where <false> does not.  For
+// the skipped work to shorten the kernel, <true> also deals the runs of tiles to the XCDs in rotation (below).
+// <false> is the unmasked kernel's code unchanged.
 #include "sift3d_resample.h"
 
 namespace {
 
 constexpr int DEM_TX = 64, DEM_TY = 4, DEM_K = 2;    // planes per lane: 2 beat 4
 constexpr unsigned DEM_GRID = SIFT3D_AMD_DEMONS_FORCE_WORK_BYTES / 16;    // partial slots: double + uint64
+// the masked kernel's wave-uniform skip: 2 (the default) with the runs of tiles dealt to the XCDs in rotation, 1
+// without the rotation, 0 compiles the skip out (-DSIFT3D_DEMONS_MASK_SKIP=n; profiles/microbench/demons_mask_rate.py)
+#ifndef SIFT3D_DEMONS_MASK_SKIP
+#define SIFT3D_DEMONS_MASK_SKIP 2
+#endif
 
 struct ForceArgs {
     const float *F, *W, *u;
@@ -30,6 +43,7 @@ struct ForceArgs {
     int nx, ny, nz, mx, my, mz, nc;
     int tiles_x, tiles_z;
     unsigned ntiles;
+    const float *wf, *wm;                        // <true> only: the masks, either may be null (all in)
 };
 
 // the value of lane - 1 (SR) or lane + 1 (SL) of the wave; the wave's first (last) lane gets `edge`
@@ -86,6 +100,7 @@ __device__ __forceinline__ void load_channel(const ForceArgs &p, const float *__
     }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
 {
     __shared__ double s_sum[4];
@@ -101,8 +116,21 @@ __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
     // planes a tile shares with the one below (its z - 1 and z0 planes) were read by the same workgroup just before
     // and come from cache, not HBM (numbered x fastest, as k_jacobian_det's, they were read twice from HBM)
     const unsigned per = (p.ntiles + gridDim.x - 1) / gridDim.x;
-    const unsigned t_end = min(p.ntiles, blockIdx.x * per + per);
-    for (unsigned t = blockIdx.x * per; t < t_end; t++) {
+    // The run of tiles, and the partial slot, of this workgroup.  <true>: consecutive workgroups go to consecutive XCDs
+    // (8) and consecutive runs are z stretches of one column, so XCD k would get the same stretches of every column,
+    // and under a compact region of interest the XCDs of the middle stretches would do all the work while the others skip
+    // theirs (measured at 256^3: a mask in for z < nz / 2 saved nothing).  Rotating each aligned group of 8 runs deals
+    // every stretch to every XCD.  The rotation steps once per band of 4 tile rows (16 y): rotating by the group's own
+    // index also balanced, but put the runs of neighbouring tile rows, which share their edge rows in L2, on different
+    // XCDs and cost the all-in mask 6 %.  A permutation of the runs: each slot still holds its own run's sums, so the
+    // 8 XCDs and their round-robin dispatch are an assumption about time only, never about the bytes.
+    unsigned blk = blockIdx.x;
+    if (MASKED && SIFT3D_DEMONS_MASK_SKIP == 2 && (blk | 7u) < gridDim.x) {
+        const unsigned ty_g = ((blk & ~7u) * per) / ((unsigned)p.tiles_z * (unsigned)p.tiles_x);
+        blk = (blk & ~7u) | ((blk + (ty_g >> 2)) & 7u);
+    }
+    const unsigned t_end = min(p.ntiles, blk * per + per);
+    for (unsigned t = blk * per; t < t_end; t++) {
         const unsigned txy = t / (unsigned)p.tiles_z;
         const int tz = (int)(t - txy * (unsigned)p.tiles_z);
         const int tx = (int)(txy % (unsigned)p.tiles_x), ty = (int)(txy / (unsigned)p.tiles_x);
@@ -130,16 +158,34 @@ __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
                 const double qx = (double)x + (double)ux, qy = (double)y + (double)uy;
                 const double qz = (double)z + (double)uz;
                 in[k] = inside(qx, qy, qz, p.mx, p.my, p.mz);                // warp_field's (a NaN is outside)
+                if (MASKED) {
+                    // W_F beside u; W_M at q's nearest voxel (voxel 0 for an outside q: the inside test decides)
+                    const float wf = p.wf ? p.wf[o] : 1.0f;
+                    const float wm = p.wm ? p.wm[mask_offset(p.mx, p.my, p.mz, qx, qy, qz)] : 1.0f;
+                    in[k] = in[k] && mask_in(wf) && mask_in(wm);
+                }
             }
+        }
+        // <true>, wave-uniform: when no lane of the wave counts a plane of this tile, nothing of the channel loop is
+        // used: no channel is run, the sums stay 0.0 and the stores below write the zeros
+        int ncr = p.nc;
+        if (MASKED && SIFT3D_DEMONS_MASK_SKIP) {
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < DEM_K; k++)
+                any = any || in[k];
+            if (__ballot(any) == 0ull)
+                ncr = 0;
         }
         // Channels outer, the lane's planes inner: the planes z0 - 1 .. z0 + DEM_K of a channel are loaded once and
         // serve as centres and z neighbours.  Software-pipelined over the channels: channel c + 1's loads are issued
         // before channel c's f64 sums, so a wave has two channels' loads in flight.  Voxels outside are computed too
         // (every address is on the fixed grid) and masked at the end.
         ChanLoads cur, nxt;
-        load_channel(p, Fb, Wb, 0, col, z0, nk, dxe, dym, dyp, plane, vox, cur);
-        for (int c = 0; c < p.nc; c++) {
-            if (c + 1 < p.nc)
+        if (!MASKED || ncr > 0)
+            load_channel(p, Fb, Wb, 0, col, z0, nk, dxe, dym, dyp, plane, vox, cur);
+        for (int c = 0; c < ncr; c++) {
+            if (c + 1 < ncr)
                 load_channel(p, Fb, Wb, c + 1, col, z0, nk, dxe, dym, dyp, plane, vox, nxt);
 #pragma unroll
             for (int k = 0; k < DEM_K; k++) {
@@ -191,8 +237,8 @@ __global__ __launch_bounds__(256) void k_demons_force(const ForceArgs p)
     lsum = workgroup_reduce<Add>(lsum, s_sum);
     lcnt = workgroup_reduce<Add>(lcnt, s_cnt);
     if (threadIdx.x == 0) {
-        p.psum[blockIdx.x] = lsum;
-        p.pcnt[blockIdx.x] = lcnt;
+        p.psum[blk] = lsum;
+        p.pcnt[blk] = lcnt;
     }
 }
 
@@ -232,9 +278,10 @@ __global__ __launch_bounds__(256) void k_field_add(float *__restrict__ u, const 
 } // namespace
 
 // Launchers for sift3d_demons.c, which has checked every argument (not exported from the library).
+// d_WF, d_WM: the masks or NULL; with both NULL the unmasked kernel runs.
 extern "C" int sift3d_demons_force_launch(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u,
                                           int mx, int my, int mz, int nc, double alpha, float *d_step, void *d_stats,
-                                          void *d_work, void *stream)
+                                          void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     ForceArgs p;
     p.F = d_F; p.W = d_W; p.u = d_u;
@@ -245,6 +292,7 @@ extern "C" int sift3d_demons_force_launch(const float *d_F, int nx, int ny, int 
     p.nx = nx; p.ny = ny; p.nz = nz;
     p.mx = mx; p.my = my; p.mz = mz;
     p.nc = nc;
+    p.wf = d_WF; p.wm = d_WM;
     p.tiles_x = (nx + DEM_TX - 1) / DEM_TX;
     p.tiles_z = (nz + DEM_K - 1) / DEM_K;
     const unsigned long long nt = (unsigned long long)p.tiles_x * ((ny + DEM_TY - 1) / DEM_TY) * p.tiles_z;
@@ -253,7 +301,7 @@ extern "C" int sift3d_demons_force_launch(const float *d_F, int nx, int ny, int 
     p.ntiles = (unsigned)nt;
     const unsigned grid = p.ntiles < DEM_GRID ? p.ntiles : DEM_GRID;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_demons_force, dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((d_WF || d_WM ? k_demons_force<true> : k_demons_force<false>), dim3(grid), dim3(256), 0, st, p);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_demons_finish, dim3(1), dim3(256), 0, st, p.psum, p.pcnt, grid, (double *)d_stats,
                        (unsigned long long *)((char *)d_stats + 8));

@@ -38,6 +38,10 @@ class DemonsLevel(C.Structure):
                 ("mx", C.c_int), ("my", C.c_int), ("mz", C.c_int), ("iterations", C.c_int)]
 
 
+class DemonsLevelMasks(C.Structure):
+    _fields_ = [("d_WF", C.c_void_p), ("d_WM", C.c_void_p)]
+
+
 CAND_DTYPE = np.dtype([("idx", "u4"), ("tag", "i4"), ("val", "f4")])
 KP_DTYPE = np.dtype([("R", "f4", (9,)), ("cx", "f4"), ("cy", "f4"), ("cz", "f4"),
                      ("level", "i4"), ("row1", "u4"), ("sd", "f8")], align=True)
@@ -363,6 +367,14 @@ def lib():
         "sift3d_amd_logdemons_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "sift3d_amd_logdemons_device": (C.c_int, [C.POINTER(DemonsLevel), C.c_int, C.c_int, vp, C.c_double,
                                                   C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_hip_demons_force_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "sift3d_amd_demons_masked_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
+                                                      C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                      C.c_int, vp, vp, vp]),
+        "sift3d_amd_logdemons_masked_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
+                                                         C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                         C.c_int, C.c_int, vp, vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -1921,12 +1933,26 @@ def demons_stats(stats):
     return raw[:, :8].copy().view(np.float64)[:, 0], raw[:, 8:].copy().view(np.uint64)[:, 0]
 
 
-def demons_force(F, W, field, step, alpha, moving_shape=None, stats=None, work=None):
+class _Grid:
+    """A stand-in for a volume in _masks: the grid (nz, ny, nx) a demons mask lies on (one plane whatever nc)"""
+    def __init__(self, shape):
+        self.shape = tuple(int(v) for v in shape)
+
+
+def _demons_masks(what, F, moving_grid, mask_fixed, mask_moving):
+    """_masks for demons features: the masks are [nz, ny, nx] on F's grid and [mz, my, mx] = moving_grid"""
+    return _masks(what, F if F.dim() == 3 else F[0], _Grid(moving_grid), mask_fixed, mask_moving)
+
+
+def demons_force(F, W, field, step, alpha, moving_shape=None, stats=None, work=None, mask_fixed=None,
+                 mask_moving=None):
     """One demons force (sift3d_hip_demons_force; contract in include/sift3d_amd.h, "Dense demons refinement"):
     step [3, nz, ny, nx] from the fixed features F and the warped moving features W ([nz, ny, nx] or
     [nc, nz, ny, nx]) and the field [3, nz, ny, nx]; moving_shape (mz, my, mx) is the moving grid of the inside
     test (None: the fixed grid).  torch CUDA float32, on torch's current stream.  Returns the stats tensor
-    (16 bytes; read it with demons_stats)."""
+    (16 bytes; read it with demons_stats).  mask_fixed [nz, ny, nx], mask_moving [mz, my, mx]: float32 masks (in where
+    >= 0.5; header, "Masks in demons"); with either given the call goes to sift3d_hip_demons_force_masked, with both
+    None to the unmasked entry."""
     import torch
     nc, (nx, ny, nz), _ = _demons_images(F, W, field, "demons_force")
     if tuple(W.shape[-3:]) != tuple(F.shape[-3:]):
@@ -1934,14 +1960,18 @@ def demons_force(F, W, field, step, alpha, moving_shape=None, stats=None, work=N
     _field_tensor(step, "demons_force", "step")
     if tuple(step.shape) != tuple(field.shape) or step.device != F.device:
         raise ValueError("demons_force: step must be shaped like the field, on its device")
-    mz, my, mx = (nz, ny, nx) if moving_shape is None else (int(v) for v in moving_shape)
+    mz, my, mx = (nz, ny, nx) if moving_shape is None else tuple(int(v) for v in moving_shape)
     if stats is None:
         stats = torch.empty(DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
     if work is None:
         work = torch.empty(DEMONS_FORCE_WORK_BYTES // 8, dtype=torch.int64, device=F.device)
-    _check(lib().sift3d_hip_demons_force(F.data_ptr(), nx, ny, nz, W.data_ptr(), field.data_ptr(), mx, my, mz, nc,
-                                         float(alpha), step.data_ptr(), stats.data_ptr(), work.data_ptr(),
-                                         current_stream()), "sift3d_hip_demons_force")
+    masks = _demons_masks("demons_force", F, (mz, my, mx), mask_fixed, mask_moving)
+    args = (F.data_ptr(), nx, ny, nz, W.data_ptr(), field.data_ptr(), mx, my, mz, nc, float(alpha), step.data_ptr(),
+            stats.data_ptr(), work.data_ptr(), current_stream())
+    if masks is not None:
+        _check(lib().sift3d_hip_demons_force_masked(*args, *masks), "sift3d_hip_demons_force_masked")
+    else:
+        _check(lib().sift3d_hip_demons_force(*args), "sift3d_hip_demons_force")
     return stats
 
 
@@ -1955,14 +1985,18 @@ def _demons_update(update, what):
 
 
 def demons(F, M, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None, update="additive",
-           squarings=0):
+           squarings=0, mask_fixed=None, mask_moving=None):
     """`iterations` demons iterations (sift3d_amd_demons_device_ex): the field [3, nz, ny, nx] is refined in
     place so that the moving features M ([mz, my, mx] or [nc, mz, my, mx]) warped through it approach the fixed
     features F ([nz, ny, nx] / [nc, nz, ny, nx]).  update "additive": u += delta (`squarings` is not used);
     "diffeomorphic": u <- u o exp(delta) with `squarings` squarings.  torch CUDA float32, on torch's current
     stream, no host synchronisation.  Returns the stats tensor (16 bytes per iteration; read it with
-    demons_stats)."""
+    demons_stats).  mask_fixed, mask_moving: as demons_force's, on F's and M's grids (with either given:
+    sift3d_amd_demons_masked_device with one level)."""
     import torch
+    if mask_fixed is not None or mask_moving is not None:
+        return _demons_pyramid("demons", [F], [M], field, [iterations], alpha, sigma_fluid, sigma_diffusion, work,
+                               update, int(squarings) if update == "diffeomorphic" else 0, [mask_fixed], [mask_moving])
     nc, (nx, ny, nz), (mx, my, mz) = _demons_images(F, M, field, "demons")
     iterations = int(iterations)
     if iterations < 0:
@@ -2167,42 +2201,79 @@ def _demons_levels(what, Fs, Ms, field, iterations):
     return tab, levels, nc0, its
 
 
+def _demons_mask_lists(what, levels, masks_fixed, masks_moving):
+    """masks_fixed, masks_moving (None, or one mask or None per level) as two lists of `levels` entries; checked ahead
+    of the tensors, as it depends on the arguments alone"""
+    WFs = [None] * levels if masks_fixed is None else list(masks_fixed)
+    WMs = [None] * levels if masks_moving is None else list(masks_moving)
+    if len(WFs) != levels or len(WMs) != levels:
+        raise ValueError("%s: masks_fixed and masks_moving must hold one mask (or None) per level" % what)
+    return WFs, WMs
+
+
+def _demons_level_masks(what, Fs, Ms, WFs, WMs):
+    """The mask table of a masked pyramid driver, or None when every mask is None (the unmasked entry is called): one
+    mask (or None) per level on that level's fixed / moving grid"""
+    levels = len(Fs)
+    if all(w is None for w in WFs + WMs):
+        return None
+    tab = (DemonsLevelMasks * levels)()
+    for l, (F, M) in enumerate(zip(Fs, Ms)):
+        wf, wm = _demons_masks("%s: level %d" % (what, l), F, M.shape[-3:], WFs[l], WMs[l]) or (None, None)
+        tab[l] = DemonsLevelMasks(wf, wm)
+    return tab
+
+
 def demons_multires(Fs, Ms, field, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, work=None,
-                    update="additive", squarings=0):
+                    update="additive", squarings=0, masks_fixed=None, masks_moving=None):
     """Coarse-to-fine demons (sift3d_amd_demons_multires_device; contract in include/sift3d_amd.h,
     "Multi-resolution demons"): Fs, Ms are the fixed and moving feature stacks per level, level 0 the finest, every
     level the half ((n + 1) // 2 per axis) of the one above; iterations one count per level; the field
     [3, nz, ny, nx] on Fs[0]'s grid is restricted to the coarsest level, refined there and handed up, in place.
     torch CUDA float32, on torch's current stream, no host synchronisation.  Returns the stats tensor: 16 bytes per
-    iteration in the order run, the coarsest level's first (read it with demons_stats)."""
+    iteration in the order run, the coarsest level's first (read it with demons_stats).  masks_fixed, masks_moving:
+    None, or one float32 mask (or None) per level on that level's fixed / moving grid (header, "Masks in demons"); with
+    any mask given the call goes to sift3d_amd_demons_masked_device, with none to the unmasked entry."""
+    return _demons_pyramid("demons_multires", Fs, Ms, field, iterations, alpha, sigma_fluid, sigma_diffusion, work,
+                           update, squarings, masks_fixed, masks_moving)
+
+
+def _demons_pyramid(what, Fs, Ms, field, iterations, alpha, sigma_fluid, sigma_diffusion, work, update, squarings,
+                    masks_fixed, masks_moving):
+    """demons_multires, and demons with a mask (one level), under the caller's name in the messages"""
     import torch
-    what = "demons_multires"
     mode = _demons_update(update, what)
+    WFs, WMs = _demons_mask_lists(what, len(Fs), masks_fixed, masks_moving)
     tab, levels, nc0, its = _demons_levels(what, Fs, Ms, field, iterations)
+    wtab = _demons_level_masks(what, Fs, Ms, WFs, WMs)
     _, nz, ny, nx = field.shape
     work = _work(work, lib().sift3d_amd_demons_multires_work_floats(nx, ny, nz, nc0, mode, levels), field, what)
     total = sum(its)
     stats = torch.empty(max(total, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
-    _check(lib().sift3d_amd_demons_multires_device(tab, levels, nc0, field.data_ptr(), float(alpha),
-                                                   float(sigma_fluid), float(sigma_diffusion), mode,
-                                                   int(squarings), work.data_ptr(), stats.data_ptr(),
-                                                   current_stream()), "sift3d_amd_demons_multires_device")
+    tail = (levels, nc0, field.data_ptr(), float(alpha), float(sigma_fluid), float(sigma_diffusion), mode,
+            int(squarings), work.data_ptr(), stats.data_ptr(), current_stream())
+    if wtab is not None:
+        _check(lib().sift3d_amd_demons_masked_device(tab, wtab, *tail), "sift3d_amd_demons_masked_device")
+    else:
+        _check(lib().sift3d_amd_demons_multires_device(tab, *tail), "sift3d_amd_demons_multires_device")
     return stats[:total * DEMONS_STATS_BYTES // 8]
 
 
 def logdemons(Fs, Ms, velocity, iterations, alpha, sigma_fluid=0.0, sigma_diffusion=0.0, symmetric=False, bch=1,
-              velocity_squarings=0, work=None):
+              velocity_squarings=0, work=None, masks_fixed=None, masks_moving=None):
     """Log-domain demons (sift3d_amd_logdemons_device; contract in include/sift3d_amd.h, "Log-domain demons"): the
     stationary velocity [3, nz, ny, nx] on Fs[0]'s grid is refined in place so that the moving features read through
     exp(velocity) approach the fixed ones.  Fs, Ms, iterations: the levels as in demons_multires (one level: a flat
     run).  symmetric: forces from both directions (fixed and moving shapes must agree); bch 0: v += delta, 1: the
     BCH update with the first Lie bracket; velocity_squarings: the squarings of every exponential.  torch CUDA
     float32, on torch's current stream, no host synchronisation.  Returns the stats tensor: 16 bytes per iteration
-    in the order run (read it with demons_stats)."""
+    in the order run (read it with demons_stats).  masks_fixed, masks_moving: as demons_multires's
+    (sift3d_amd_logdemons_masked_device; the backward force of the symmetric update exchanges them)."""
     import torch
     what = "logdemons"
     if bch not in (0, 1):
         raise ValueError("logdemons: bch must be 0 or 1, not %r" % (bch,))
+    WFs, WMs = _demons_mask_lists(what, len(Fs), masks_fixed, masks_moving)
     tab, levels, nc0, its = _demons_levels(what, Fs, Ms, velocity, iterations)
     sym = 1 if symmetric else 0
     if sym and any(tuple(F.shape) != tuple(M.shape) for F, M in zip(Fs, Ms)):
@@ -2211,10 +2282,13 @@ def logdemons(Fs, Ms, velocity, iterations, alpha, sigma_fluid=0.0, sigma_diffus
     work = _work(work, lib().sift3d_amd_logdemons_work_floats(nx, ny, nz, nc0, sym, levels), velocity, what)
     total = sum(its)
     stats = torch.empty(max(total, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=velocity.device)
-    _check(lib().sift3d_amd_logdemons_device(tab, levels, nc0, velocity.data_ptr(), float(alpha), float(sigma_fluid),
-                                             float(sigma_diffusion), sym, int(bch), int(velocity_squarings),
-                                             work.data_ptr(), stats.data_ptr(), current_stream()),
-           "sift3d_amd_logdemons_device")
+    wtab = _demons_level_masks(what, Fs, Ms, WFs, WMs)
+    tail = (levels, nc0, velocity.data_ptr(), float(alpha), float(sigma_fluid), float(sigma_diffusion), sym, int(bch),
+            int(velocity_squarings), work.data_ptr(), stats.data_ptr(), current_stream())
+    if wtab is not None:
+        _check(lib().sift3d_amd_logdemons_masked_device(tab, wtab, *tail), "sift3d_amd_logdemons_masked_device")
+    else:
+        _check(lib().sift3d_amd_logdemons_device(tab, *tail), "sift3d_amd_logdemons_device")
     return stats[:total * DEMONS_STATS_BYTES // 8]
 
 
