@@ -18,6 +18,8 @@ Fixture families:
   g6_abi       the names the reference library exports and its CLI imports (JSON)
   g7_*         describe on caller-made keypoint lists
   g8_*         assign_eig_ori on caller-made candidate lists: status, conf, R per entry
+  g9_*         detect_extrema on caller-made DoG levels (ties, thresholds, borders, subnormal and
+               overflowing levels, both builds): the recipes and the reference's records
 """
 import argparse
 import hashlib
@@ -601,6 +603,42 @@ def g8_orient():
     return out
 
 
+def g9_names():
+    from tests import extrema_cases as xc
+    return sorted({f for f, _, _, _, _ in xc.G9})
+
+
+def g9_fixture(name):
+    """detect_extrema (sift.c:735-871) on the caller-made DoG levels of tests/extrema_cases.py (probe_extrema): per
+    case of the fixture its recipe (seed, shape, plants -- not the arrays), state, peak_thresh and build, and the
+    reference's records as (s, z, y, x) rows and strengths in its own order."""
+    from tests import extrema_cases as xc
+    d, cases = {}, []
+    for f, recipe, state, peak, cuboid in xc.G9:
+        if f != name:
+            continue
+        p = refprobe.Probe(cuboid_extrema=cuboid)
+        D, _ = xc.build(recipe, state)
+        szyx, strength = p.extrema(D, peak)
+        p.close()
+        i = len(cases)
+        d["case%d_szyx" % i], d["case%d_strength" % i] = szyx.astype(np.int32), strength.astype(np.float32)
+        cases.append(dict(recipe=recipe, state=state, peak=peak, cuboid=cuboid, n=int(len(szyx))))
+    d["cases"] = np.array(json.dumps(cases))
+    return d
+
+
+def g9_extrema():
+    out = {}
+    for name in g9_names():
+        d = g9_fixture(name)
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
+        out[name] = {c["recipe"]["name"] + "/state%d/peak%g%s" % (c["state"], c["peak"], "/cuboid" * c["cuboid"]): c["n"]
+                     for c in json.loads(str(d["cases"]))}
+        print(name, out[name], flush=True)
+    return out
+
+
 def g6_abi():
     """The link-level contract as data, for machines without the reference: the names the unmodified
     reference library exports (libsift3D_ref.so) and the names its own CLI -- cli/kpSift3D.c compiled unchanged
@@ -658,6 +696,8 @@ def main():
         "g7": g7_all,
         # orientation (assign_eig_ori) on caller-made candidate lists (g8_*)
         "g8": g8_orient,
+        # detect_extrema on caller-made DoG levels (g9_*)
+        "g9": g9_extrema,
     }
     if a.big:
         jobs["g5_128"] = lambda: end_to_end(

@@ -290,6 +290,50 @@ PROBE int probe_orient(probe_ctx *c, int n, const int *os, const int *xyz, const
     return 0;
 }
 
+/* detect_extrema (sift.c:735-871) on CALLER-MADE DoG levels: `dog` holds nlev levels of nx * ny * nz floats, one
+ * after the other, which stand in for the detector's DoG pyramid (one octave, first level -1 as the detector's own:
+ * keypoint levels s = 0 .. nlev - 3) while the function runs; peak is its peak_thresh for the call.  The candidates
+ * are left where probe_detect leaves them (probe_num_cand / probe_get_cand).  The function reads nothing else of
+ * the detector, so the context needs no image. */
+PROBE int probe_extrema(probe_ctx *c, const float *dog, int nlev, int nx, int ny, int nz, double peak)
+{
+    sift3d_detector *const det = c->det;
+    const sift3d_pyramid saved = det->dog;
+    const double saved_peak = det->peak_thresh;
+    sift3d_image *lv;
+    int i, ret;
+    if (nlev < 3 || !(lv = (sift3d_image *)calloc((size_t)nlev, sizeof(*lv))))
+        return -1;
+    for (i = 0; i < nlev; i++)
+        wrap_image(lv + i, (float *)dog + (size_t)i * nx * ny * nz, nx, ny, nz, 1.0, 1.0, 1.0);
+    det->dog.levels = lv;
+    det->dog.first_octave = 0;
+    det->dog.num_octaves = 1;
+    det->dog.first_level = -1;
+    det->dog.num_levels = nlev;
+    det->peak_thresh = peak;
+    c->kp->slab.num = 0;        /* (the function sizes the store only when it finds a candidate) */
+    ret = detect_extrema(det, c->kp);
+    det->dog = saved;
+    det->peak_thresh = saved_peak;
+    free(lv);
+    if (ret)
+        return -1;
+    c->ncand = (int)c->kp->slab.num;
+    c->cand = (probe_cand *)realloc(c->cand, sizeof(probe_cand) * (c->ncand + 1));
+    for (i = 0; i < c->ncand; i++) {
+        const sift3d_keypoint *k = c->kp->buf + i;
+        c->cand[i].o = k->o;
+        c->cand[i].s = k->s;
+        c->cand[i].x = (int)k->xd;
+        c->cand[i].y = (int)k->yd;
+        c->cand[i].z = (int)k->zd;
+        c->cand[i].strength = k->strength;
+        c->cand[i].sd = k->sd;
+    }
+    return 0;
+}
+
 PROBE void probe_sort(probe_ctx *c, int limit)
 {
     sift3d_keypoint_store_sort_by_strength(c->kp, limit);

@@ -30,6 +30,12 @@ def has_orient():
     return available() and hasattr(lib(), "probe_orient")
 
 
+def has_extrema(cuboid=False):
+    """The library that is there has the probe_extrema hook."""
+    path = LIB_PATH_CUBOID if cuboid else LIB_PATH
+    return os.path.exists(path) and hasattr(lib(cuboid), "probe_extrema")
+
+
 _libs = {}
 
 
@@ -57,6 +63,8 @@ def lib(cuboid=False):
         L.probe_set_kp.argtypes = [C.c_void_p, C.c_int, _i32p, _f64p, _f32p]
         if hasattr(L, "probe_orient"):      # (a library built from an older ref_probe.c lacks the hook)
             L.probe_orient.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_float, _i32p, _f64p, _f32p]
+        if hasattr(L, "probe_extrema"):
+            L.probe_extrema.argtypes = [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
         for n in ("probe_num_octaves", "probe_num_cand", "probe_num_kp"):
             getattr(L, n).argtypes = [C.c_void_p]
         L.probe_get_cand.argtypes = [C.c_void_p, _i32p, _f32p, _f64p]
@@ -187,6 +195,16 @@ class Probe:
         status, conf, R = np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros((n, 9), np.float32)
         assert self.L.probe_orient(self.h, n, os_, xyz, sd, float(scale), status, conf, R) == 0
         return status, conf, R.reshape(n, 3, 3)
+
+    def extrema(self, dog, peak):
+        """detect_extrema on caller-made DoG levels (a list of [nz, ny, nx] arrays of one shape) with peak_thresh
+        `peak`: (s, z, y, x) int32 rows and strengths in the reference's order."""
+        dog = np.ascontiguousarray(np.stack([np.asarray(d, np.float32) for d in dog]))
+        nlev, nz, ny, nx = dog.shape
+        assert self.L.probe_extrema(self.h, dog.reshape(-1), nlev, nx, ny, nz, float(peak)) == 0
+        c = self.candidates()
+        assert (c["osxyz"][:, 0] == 0).all()
+        return np.ascontiguousarray(c["osxyz"][:, [1, 4, 3, 2]]), c["strength"]
 
     def sort(self, limit):
         self.L.probe_sort(self.h, int(limit))

@@ -27,6 +27,14 @@ class ExtremaLevel(C.Structure):
                 ("d_absmax", C.c_void_p), ("z_lo", C.c_int), ("z_hi", C.c_int), ("tag", C.c_int)]
 
 
+class ExtremaOct(C.Structure):                             # sift3d_hip_extrema_oct
+    _fields_ = [("d_g", C.POINTER(C.c_void_p)), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("tag0", C.c_int), ("d_work", C.c_void_p), ("work_bytes", C.c_size_t)]
+
+
+EXTREMA_MAX_OCT = 12                                       # SIFT3D_HIP_EXTREMA_MAX_OCT
+
+
 class Level(C.Structure):
     _fields_ = [("data", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("z_off", C.c_int), ("nz_glob", C.c_int), ("ux", C.c_float), ("uy", C.c_float),
@@ -167,6 +175,17 @@ def lib():
                                          C.c_double, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_extrema_mode": (C.c_int, [C.POINTER(ExtremaLevel), C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_double, C.c_int, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
+        "sift3d_hip_extrema_gauss6": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_double, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
+        "sift3d_hip_extrema_gauss6_phase": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_double, vp, C.c_uint32, vp, vp, C.c_size_t, vp,
+                                                      C.c_int]),
+        "sift3d_hip_extrema_gauss6_est_phase": (C.c_int, [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          C.c_double, vp, C.c_uint32, vp, vp, C.c_size_t, vp,
+                                                          C.c_int]),
+        "sift3d_hip_extrema_gauss6_finish": (C.c_int, [C.POINTER(ExtremaOct), C.c_int, C.c_double, vp, C.c_uint32,
+                                                       vp, vp]),
+        "sift3d_hip_dogmax_sub": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, vp, vp]),
         "sift3d_hip_orient": (C.c_int, [vp, vp, C.c_uint32, C.c_double, vp, vp, vp]),
         "sift3d_hip_orient_tab_bytes": (C.c_size_t, [C.c_int, C.c_uint32]),
         "sift3d_hip_orient_tab": (C.c_int, [vp, C.c_int, vp, C.c_uint32, C.c_double, vp, vp, vp, C.c_uint32, vp]),
@@ -2387,6 +2406,80 @@ def extrema(levels, nx, ny, nz, peak_thresh, cap=1 << 18, cuboid=False):
             break
         cap = n + n // 4 + 1024
     return out[:n * CAND_DTYPE.itemsize].cpu().numpy().view(CAND_DTYPE).copy()
+
+
+# ---- the extrema stage on the caller's buffers ----------------------------------------------------------------------
+# d_out / d_count / d_work: tensors or raw device addresses (an output carved out of a larger buffer).  Records are
+# appended at *d_count, which the caller initialises; nothing is allocated, grown or read back here.  A return of 1
+# ("configuration not covered", nothing done) reaches the caller as a value; any other non-zero code raises.
+
+def _ptr(t):
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def _covered(rc, what):
+    if rc not in (0, 1):
+        _check(rc, what)
+    return rc
+
+
+def _gauss_ptrs(gauss):
+    assert len(gauss) == 6
+    return (C.c_void_p * 6)(*[_ptr(t) for t in gauss])
+
+
+def extrema_work_bytes(nx, ny, nz, nlevels=3):
+    return int(lib().sift3d_hip_extrema_work_bytes(nx, ny, nz, nlevels))
+
+
+def extrema_into(levels, nx, ny, nz, peak_thresh, d_out, cap, d_count, d_work, work_bytes, cuboid=False):
+    """sift3d_hip_extrema_mode with the caller's d_out, cap and starting count (levels as for extrema())."""
+    arr = (ExtremaLevel * len(levels))()
+    for i, lv in enumerate(levels):
+        arr[i] = ExtremaLevel(_ptr(lv["prev"]), _ptr(lv["cur"]), _ptr(lv["next"]), _ptr(lv["absmax"]), lv["z_lo"],
+                              lv["z_hi"], lv["tag"])
+    return _covered(lib().sift3d_hip_extrema_mode(arr, len(levels), nx, ny, nz, float(peak_thresh), int(bool(cuboid)),
+                                                  _ptr(d_out), int(cap), _ptr(d_count), _ptr(d_work),
+                                                  int(work_bytes), current_stream()), "sift3d_hip_extrema_mode")
+
+
+def extrema_gauss6(gauss, d_absmax, nx, ny, nz, z_lo, z_hi, tag0, peak_thresh, d_out, cap, d_count, d_work,
+                   work_bytes, phase=None):
+    """sift3d_hip_extrema_gauss6 (phase None) or sift3d_hip_extrema_gauss6_phase (0: both, 1: sweep, 2: scan + emit)
+    on six Gaussian levels; d_absmax: the octave's five max|DoG|."""
+    L, g = lib(), _gauss_ptrs(gauss)
+    a = (g, _ptr(d_absmax), nx, ny, nz, z_lo, z_hi, tag0, float(peak_thresh), _ptr(d_out), int(cap), _ptr(d_count),
+         _ptr(d_work), int(work_bytes), current_stream())
+    if phase is None:
+        return _covered(L.sift3d_hip_extrema_gauss6(*a), "sift3d_hip_extrema_gauss6")
+    return _covered(L.sift3d_hip_extrema_gauss6_phase(*(a + (int(phase),))), "sift3d_hip_extrema_gauss6_phase")
+
+
+def extrema_gauss6_est_phase(gauss, d_est, d_exact, nx, ny, nz, tag0, peak_thresh, d_out, cap, d_count, d_work,
+                             work_bytes, phase):
+    """sift3d_hip_extrema_gauss6_est_phase: d_est the lower bounds (dogmax_sub), d_exact zeroed before phase 1."""
+    return _covered(lib().sift3d_hip_extrema_gauss6_est_phase(
+        _gauss_ptrs(gauss), _ptr(d_est), _ptr(d_exact), nx, ny, nz, tag0, float(peak_thresh), _ptr(d_out), int(cap),
+        _ptr(d_count), _ptr(d_work), int(work_bytes), current_stream(), int(phase)),
+        "sift3d_hip_extrema_gauss6_est_phase")
+
+
+def extrema_gauss6_finish(octs, peak_thresh, d_out, cap, d_count):
+    """sift3d_hip_extrema_gauss6_finish: octs = dicts(gauss, nx, ny, nz, tag0, d_work, work_bytes) of what phase 1 of
+    each octave was given."""
+    keep = [_gauss_ptrs(o["gauss"]) for o in octs]
+    arr = (ExtremaOct * max(len(octs), 1))()
+    for i, o in enumerate(octs):
+        arr[i] = ExtremaOct(keep[i], o["nx"], o["ny"], o["nz"], o["tag0"], _ptr(o["d_work"]), int(o["work_bytes"]))
+    return _covered(lib().sift3d_hip_extrema_gauss6_finish(arr, len(octs), float(peak_thresh), _ptr(d_out), int(cap),
+                                                           _ptr(d_count), current_stream()),
+                    "sift3d_hip_extrema_gauss6_finish")
+
+
+def dogmax_sub(gauss, nx, ny, nz, d_est):
+    """sift3d_hip_dogmax_sub: the sub-lattice maxima of the five |DoG| levels maxed into d_est[0..4]."""
+    return _covered(lib().sift3d_hip_dogmax_sub(_gauss_ptrs(gauss), nx, ny, nz, _ptr(d_est), current_stream()),
+                    "sift3d_hip_dogmax_sub")
 
 
 
