@@ -1883,6 +1883,105 @@ sift3d_amd_logdemons_masked_device(const sift3d_amd_demons_level *level, const s
                                    float *d_work, void *d_stats, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Distance transforms and surface distances                                 */
+/* ------------------------------------------------------------------------ */
+/* The exact Euclidean distance transform (EDT) of a mask, the signed distance of a set, the six-neighbour surface of
+ * a label and, from them, the distances between the surfaces of two segmentations: Hausdorff, HD95 and the average
+ * symmetric surface distance, the measures reported beside Dice ("Similarity measures").  No upstream counterpart:
+ * PARITY UNPINNED, pinned to this contract and its numpy restatement (tests/distance_restatement.py), every device
+ * output bit for bit.  None of it uses the sampling core.
+ *
+ * Feature set.  A mask is a float32 volume [nz][ny][nx].  A voxel is IN when w >= 0.5f ("Masks": one float compare, so a
+ * NaN is out).  The features are the voxels that are IN; with invert != 0, the voxels that are OUT.
+ *
+ * Weights.  spacing is three doubles (sx, sy, sz), the voxel's edge lengths; NULL: all 1.  Each must be finite and lie
+ * in [1e-6, 1e6].  w_a = (float) (s_a * s_a): the product in double, rounded once to float.  Every dimension is at most
+ * SIFT3D_AMD_DISTANCE_MAX_DIM = 4096, so every integer d * d below is exact in float32.
+ *
+ * Squared distance.  For an output voxel p and a feature voxel q with integer offsets dx, dy, dz:
+ *     c(p, q) = ((w_x (*) (float) (dx dx)) (+) (w_y (*) (float) (dy dy))) (+) (w_z (*) (float) (dz dz))
+ * where (*) and (+) are float32 multiply and add, unfused.  D2(p) = the minimum of c(p, q) over every feature voxel q,
+ * +inf when there is no feature; D(p) = sqrtf(D2(p)), correctly rounded.
+ * The device builds it in three per-axis passes, which reproduce that minimum bit for bit because (*) and (+) are
+ * monotone: the x pass writes g1 = w_x (*) (float) (min dx dx) (+inf in a row without a feature), the y pass
+ * g2(y) = min over y' of g1(y') (+) (w_y (*) (float) ((y - y') (y - y'))), the z pass the same along z, and each line
+ * minimum is exact on the rounded values: the search walks outwards from y and stops where w (*) (float) (r r) alone
+ * reaches the best value so far, beyond which no candidate can be smaller, ties included.  With unit spacing every
+ * value is an integer: D2 is the integer squared distance rounded once to float (exact below 2^24).  A line without a
+ * feature costs its whole length per voxel: O(n) per voxel per pass in the worst case.
+ *
+ * Signed distance of the set of IN voxels: +sqrtf(D2 to the set) at voxels outside it, -sqrtf(D2 to its complement) at
+ * voxels inside it; +inf everywhere when the set is empty, -inf everywhere when it is the whole grid.
+ *
+ * Surface of a label.  S_k = {p : L(p) == (float) k} for a label volume L (float-valued integers, as label overlap
+ * takes them).  p is on the surface dS_k when p is in S_k and at least one of its six face neighbours is not; a
+ * neighbour beyond the grid is not.  The surface volume holds 1.0f there and 0.0f elsewhere, and *d_count their number.
+ *
+ * Surface distances for label k, both label volumes on one grid [nz][ny][nx]: d_fm is the multiset
+ * {D to dM_k at p : p in dF_k}, d_mf the other direction.  sift3d_hip_surface_collect appends sqrtf(d2[p]) for every p
+ * whose surface value is IN, in no particular order (the order in which the device collects is not part of the
+ * contract; the sorted arrays are), adds their number to *d_count - also where it exceeds `capacity` - and writes
+ * nothing at or past d_list[capacity].
+ *
+ * Measures (host, double), from the two lists sorted ascending, n_f and n_m their lengths:
+ *   sum_fm, sum_mf = acc after: acc = 0.0; for each d in ascending order: acc = acc + (double) d
+ *   max_fm, max_mf = the last elements; mean_fm = sum_fm / n_f, mean_mf = sum_mf / n_m
+ *   hausdorff = max(max_fm, max_mf);  assd = (sum_fm + sum_mf) / (n_f + n_m)
+ *   hd95: d[0 .. n-1] = both lists merged ascending, n = n_f + n_m; pos = 0.95 * (n - 1), i = floor(pos),
+ *         hd95 = d[i] + (pos - i) * (d[min(i + 1, n - 1)] - d[i])   (the linear percentile of the pooled list)
+ * When either surface is empty every measure is NaN; the counts are still reported.
+ *
+ * The sift3d_hip_ entries are asynchronous on `stream`, allocate nothing, use 64-bit offsets and check their arguments
+ * before any device call: -1 on NULL pointers, dims <= 0 or > SIFT3D_AMD_DISTANCE_MAX_DIM (n_voxels == 0 or beyond its
+ * cube, a capacity beyond it), a spacing that is not finite or outside [1e-6, 1e6], a buffer that is not 4-byte aligned
+ * (8-byte: a counter, the driver's d_work), an output that overlaps an input, the work buffer or another output.
+ * d_work of the three transform entries: sift3d_amd_distance_work_bytes() bytes = two volumes; sift3d_hip_distance_sq
+ * and sift3d_hip_distance touch the first of them only (the ping-pong between the passes), the signed entry both. */
+#define SIFT3D_AMD_DISTANCE_MAX_DIM 4096
+typedef struct {
+    uint64_t n_f, n_m;                          /* voxels on the fixed and the moving surface */
+    double hausdorff, hd95, assd, mean_fm, mean_mf, max_fm, max_mf;
+} sift3d_amd_surface_result;
+/* bytes of d_work for the three transform entries (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_distance_work_bytes(int nx, int ny, int nz);
+/* d_out [nz][ny][nx] = D2 */
+SIFT3D_AMD_API int
+sift3d_hip_distance_sq(const float *d_mask, int nx, int ny, int nz, const double *spacing /*3 or NULL*/, int invert,
+                       float *d_out, void *d_work, void *stream);
+/* d_out = D = sqrtf(D2), the root taken by the last pass */
+SIFT3D_AMD_API int
+sift3d_hip_distance(const float *d_mask, int nx, int ny, int nz, const double *spacing /*3 or NULL*/, int invert,
+                    float *d_out, void *d_work, void *stream);
+/* d_out = the signed distance of the set of IN voxels */
+SIFT3D_AMD_API int
+sift3d_hip_distance_signed(const float *d_mask, int nx, int ny, int nz, const double *spacing /*3 or NULL*/,
+                           float *d_out, void *d_work, void *stream);
+/* d_surface [nz][ny][nx] float 0 / 1; *d_count (device, 8-byte aligned) = the number of surface voxels */
+SIFT3D_AMD_API int
+sift3d_hip_label_surface(const float *d_labels, int nx, int ny, int nz, int label, float *d_surface,
+                         uint64_t *d_count, void *stream);
+/* d_surface, d_d2 [n_voxels]; d_list [capacity]; *d_count (device, 8-byte aligned) = the number of surface voxels */
+SIFT3D_AMD_API int
+sift3d_hip_surface_collect(const float *d_surface, const float *d_d2, size_t n_voxels, float *d_list,
+                           size_t capacity, uint64_t *d_count, void *stream);
+/* host only: two lists sorted ascending on the host (a list may be NULL when its length is 0).  -1 on a NULL out or a
+ * NULL list of non-zero length. */
+SIFT3D_AMD_API int
+sift3d_amd_surface_measures(const float *d_fm, uint64_t n_f, const float *d_mf, uint64_t n_m,
+                            sift3d_amd_surface_result *out);
+/* The driver: results[l] for labels[l], l = 0 .. n_labels - 1 (1 <= n_labels <= SIFT3D_AMD_SIMILARITY_MAX_BINS), of the
+ * label volumes d_LF and d_LM on one grid; labels, spacing and results on the host.  Per label: the two surfaces, the
+ * transform of each, the two lists, sorted on the host (the only host allocation), and the measures.  SYNCHRONOUS: it
+ * waits for `stream` once per label to read the two surface counts - a label with an empty surface ends there - and
+ * once more to receive the two lists.  d_work: sift3d_amd_surface_distances_work_bytes() bytes (0 for bad dims),
+ * 8-byte aligned: five volumes and the counters. */
+SIFT3D_AMD_API size_t sift3d_amd_surface_distances_work_bytes(int nx, int ny, int nz);
+SIFT3D_AMD_API int
+sift3d_amd_surface_distances_device(const float *d_LF, const float *d_LM, int nx, int ny, int nz, const int *labels,
+                                    int n_labels, const double *spacing /*3 or NULL*/,
+                                    sift3d_amd_surface_result *results, void *d_work, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Multi-GPU: one process per GPU, the volume cut into Z-slabs               */
 /* ------------------------------------------------------------------------ */
 

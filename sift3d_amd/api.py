@@ -36,6 +36,11 @@ class _Measures(C.Structure):                               # sift3d_amd_similar
                                                                   "entropy_moving", "entropy_joint")]
 
 
+class _SurfaceResult(C.Structure):                          # sift3d_amd_surface_result
+    _fields_ = [("n_f", C.c_uint64), ("n_m", C.c_uint64)] + [(k, C.c_double) for k in (
+        "hausdorff", "hd95", "assd", "mean_fm", "mean_mf", "max_fm", "max_mf")]
+
+
 _bound = None
 
 
@@ -123,6 +128,7 @@ def lib():
         "sift3d_amd_image_bspline_warp_field": (C.c_int, [vp, _f32p, C.c_float, vp]),
         "sift3d_amd_similarity_measures": (C.c_int, [_u64p, C.c_int, vp, C.POINTER(_Measures)]),
         "sift3d_amd_label_overlap": (C.c_int, [_u64p, C.c_int, _f64p, _f64p, _u64p, _u64p]),
+        "sift3d_amd_surface_measures": (C.c_int, [_f32p, C.c_uint64, _f32p, C.c_uint64, C.POINTER(_SurfaceResult)]),
         "sift3d_amd_image_dense_descriptors": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_image_dense_descriptors_rotate": (C.c_int, [vp, C.c_double, _f32p]),
         "sift3d_amd_device_available": (C.c_int, []),
@@ -1509,6 +1515,93 @@ def label_overlap_measures(confusion):
     if lib().sift3d_amd_label_overlap(h.reshape(-1), L, dice, jac, vf, vm) != 0:
         raise RuntimeError("sift3d_amd_label_overlap failed")
     return LabelOverlap(h.astype(np.int64), dice, jac, vf.astype(np.int64), vm.astype(np.int64))
+
+
+# ---- distance transforms and surface distances ------------------------------------------------------------------
+SurfaceMeasures = collections.namedtuple("SurfaceMeasures",
+                                         "hausdorff hd95 assd mean_fm mean_mf max_fm max_mf n_fixed n_moving")
+SurfaceDistances = collections.namedtuple("SurfaceDistances", SurfaceMeasures._fields + ("labels",))
+_SURFACE_FIELDS = ("hausdorff", "hd95", "assd", "mean_fm", "mean_mf", "max_fm", "max_mf", "n_f", "n_m")
+
+
+def distance_transform(mask, spacing=None, squared=False, signed=False, invert=False):
+    """The exact Euclidean distance transform of a mask [nz, ny, nx] on the device (contract: include/sift3d_amd.h,
+    "Distance transforms and surface distances"): at every voxel the distance to the nearest feature voxel, a voxel
+    of the mask (bool and integer masks: non-zero; float masks: >= 0.5), or with invert=True a voxel outside it; +inf
+    where there is no feature.  spacing = (sx, sy, sz), the voxel's edge lengths (None: 1); squared=True: the squared
+    distance.  signed=True: the signed distance of the mask, positive outside it and negative inside (it takes neither
+    squared nor invert).  A torch CUDA tensor gives a tensor (torch's current stream); an array or an Image gives a
+    numpy array (blocking)."""
+    from . import hip
+    what = "distance_transform"
+    if signed and (squared or invert):
+        raise ValueError("distance_transform: signed=True takes neither squared nor invert")
+    hip._spacing(spacing, what)
+    w = _mask_host(mask, mask, what, "mask")
+    if len(w.shape) != 3:
+        raise ValueError("distance_transform: mask must be a volume [nz, ny, nx]")
+    host = not _torch_tensor(w)
+    if host:
+        import torch
+        if not device_available():
+            raise RuntimeError("distance_transform: no HIP device is available; this library has no CPU path")
+        w = torch.from_numpy(w).to("cuda")
+    out = hip.distance(w, spacing, "signed" if signed else "sq" if squared else "root", invert)
+    return out.cpu().numpy() if host else out
+
+
+def surface_measures(d_fm, d_mf):
+    """The surface-distance measures of two lists of distances sorted ascending (sift3d_amd_surface_measures; host,
+    double): SurfaceMeasures(hausdorff, hd95, assd, mean_fm, mean_mf, max_fm, max_mf, n_fixed, n_moving); every
+    measure is NaN when either list is empty."""
+    a, b = (np.ascontiguousarray(d, np.float32).reshape(-1) for d in (d_fm, d_mf))
+    out = _SurfaceResult()
+    if lib().sift3d_amd_surface_measures(a, len(a), b, len(b), C.byref(out)) != 0:
+        raise RuntimeError("sift3d_amd_surface_measures failed")
+    return SurfaceMeasures(*(getattr(out, k) for k in _SURFACE_FIELDS))
+
+
+def surface_distances(labels_fixed, labels_moving, transform=None, num_labels=None, labels=None, spacing=None):
+    """Distances between the surfaces of two label volumes (float-valued integers, as label_overlap takes them), per
+    label (contract: "Distance transforms and surface distances"): SurfaceDistances(hausdorff, hd95, assd, mean_fm,
+    mean_mf, max_fm, max_mf, n_fixed, n_moving, labels), arrays indexed like `labels`, in the units of `spacing` =
+    (sx, sy, sz) (None: voxels).  A label's surface is its voxels with a face neighbour of another label or beyond the
+    grid; *_fm are taken at the fixed surface's voxels to the moving surface, *_mf the other way; a label absent from
+    either volume gives NaN.  labels: the labels to report, default 1 .. L-1 with L = num_labels or the largest label of
+    either volume + 1 (one host synchronisation).  transform (as label_overlap's: a 3 x 4 affine pull map, a TPS or a
+    displacement field on the fixed grid): the moving labels are first resampled onto the fixed grid with nearest
+    sampling (0 outside); without one the two shapes must agree.  Blocking."""
+    from . import hip
+    import torch
+    what = "surface_distances"
+    hip._spacing(spacing, what)
+    sf, sm = (tuple(v.shape) if hasattr(v, "shape") else np.shape(v) for v in (labels_fixed, labels_moving))
+    if transform is None and sf != sm:
+        raise ValueError("surface_distances: transform=None needs label volumes of one shape, not %s and %s" % (sf, sm))
+    if labels is not None:
+        labels = np.asarray(labels).reshape(-1)
+        if not 1 <= len(labels) <= SIMILARITY_MAX_BINS or not np.issubdtype(labels.dtype, np.integer):
+            raise ValueError("surface_distances: labels must be between 1 and %d integers" % SIMILARITY_MAX_BINS)
+    F = _similarity_volume(labels_fixed, what, "labels_fixed")
+    M = _similarity_volume(labels_moving, what, "labels_moving", F.device)
+    T = _similarity_transform(transform, F, what)
+    if T is not None:
+        warped = torch.empty_like(F)
+        if _torch_tensor(T):
+            hip.warp_field(M, warped, T, "nearest", 0.0)
+        else:
+            hip.warp_affine(M, warped, T, "nearest", 0.0)
+        M = warped
+    if labels is None:
+        L = int(num_labels) if num_labels is not None else int(max(float(F.max()), float(M.max()))) + 1
+        L = max(L, 2)
+        if L - 1 > SIMILARITY_MAX_BINS:
+            raise ValueError("surface_distances: at most %d labels, not %d" % (SIMILARITY_MAX_BINS, L - 1))
+        labels = np.arange(1, L)
+    res = hip.surface_distances(F, M, labels, spacing)
+    cols = [np.array([getattr(r, k) for r in res], np.int64 if k in ("n_f", "n_m") else np.float64)
+            for k in _SURFACE_FIELDS]
+    return SurfaceDistances(*cols, np.asarray(labels, np.int64))
 
 
 # ---- dense descriptors: a 12-bin gradient histogram per voxel ------------------------------------

@@ -1511,3 +1511,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* B-spline free-form deformation: weight table, checked entries and the steepest-descent driver */
 #include "sift3d_ffd.c"
+
+/* Euclidean distance transforms, label surfaces and the surface-distance measures */
+#include "sift3d_distance.c"

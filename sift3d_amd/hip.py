@@ -127,6 +127,11 @@ class FFDLevel(C.Structure):                               # sift3d_amd_ffd_leve
                 ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("d_WF", C.c_void_p), ("d_WM", C.c_void_p)]
 
 
+class SurfaceResult(C.Structure):                          # sift3d_amd_surface_result
+    _fields_ = [("n_f", C.c_uint64), ("n_m", C.c_uint64)] + [(k, C.c_double) for k in (
+        "hausdorff", "hd95", "assd", "mean_fm", "mean_mf", "max_fm", "max_mf")]
+
+
 _bound = None
 
 
@@ -394,6 +399,16 @@ def lib():
         "sift3d_amd_logdemons_masked_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
                                                          C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                                          C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_amd_distance_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_hip_distance_sq": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
+        "sift3d_hip_distance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
+        "sift3d_hip_distance_signed": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp, vp, vp]),
+        "sift3d_hip_label_surface": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_hip_surface_collect": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]),
+        "sift3d_amd_surface_distances_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_amd_surface_distances_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                          C.c_int, C.POINTER(C.c_double), C.POINTER(SurfaceResult),
+                                                          vp, vp]),
         "sift3d_hip_test_expf": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "sift3d_hip_test_eigen3": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "sift3d_hip_last_error": (C.c_char_p, []),
@@ -838,6 +853,126 @@ def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=No
         _check(lib().sift3d_hip_similarity_field(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
                                                  field.data_ptr(), *tail), "sift3d_hip_similarity_field")
     return hist, stats
+
+
+# ---- distance transforms and surface distances (contract: include/sift3d_amd.h, "Distance transforms and surface
+# distances") ------------------------------------------------------------------------------------------------------
+DISTANCE_MAX_DIM = 4096
+
+
+def _spacing(spacing, what):
+    """(sx, sy, sz) as a float64 [3] and its pointer, or (None, None): all 1.  ValueError on anything the entries would
+    refuse."""
+    if spacing is None:
+        return None, None
+    s = np.ascontiguousarray(spacing, np.float64)
+    if s.shape != (3,) or not np.all(np.isfinite(s)) or np.any(s < 1e-6) or np.any(s > 1e6):
+        raise ValueError("%s: spacing must be three finite values (sx, sy, sz) in [1e-6, 1e6]" % what)
+    return s, s.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _distance_volume(t, what, name):
+    _tensor(t, "%s: %s must be a contiguous 3-D float32 CUDA tensor" % (what, name), dims=(3,))
+    if max(t.shape) > DISTANCE_MAX_DIM or min(t.shape) < 1:
+        raise ValueError("%s: every dimension of %s must be in [1, %d]" % (what, name, DISTANCE_MAX_DIM))
+
+
+def distance_work_bytes(shape):
+    nz, ny, nx = shape
+    return lib().sift3d_amd_distance_work_bytes(nx, ny, nz)
+
+
+def distance(mask, spacing=None, mode="sq", invert=False, out=None, work=None):
+    """The Euclidean distance transform of a mask [nz, ny, nx] (torch CUDA float32 contiguous; in where >= 0.5) on
+    torch's current stream.  mode "sq": the squared distance D2 to the nearest feature voxel (sift3d_hip_distance_sq),
+    "root": D = sqrtf(D2) (sift3d_hip_distance), "signed": the signed distance of the set of in voxels
+    (sift3d_hip_distance_signed; invert must be False).  spacing: (sx, sy, sz) or None: all 1.  invert: the features
+    are the voxels that are out.  out, work: the caller's buffers (mask's shape; distance_work_bytes bytes)."""
+    import torch
+    what = "distance"
+    _distance_volume(mask, what, "mask")
+    if mode not in ("sq", "root", "signed"):
+        raise ValueError("distance: mode must be 'sq', 'root' or 'signed', not %r" % (mode,))
+    if mode == "signed" and invert:
+        raise ValueError("distance: the signed distance takes no invert")
+    keep, sp = _spacing(spacing, what)
+    if out is None:
+        out = torch.empty_like(mask)
+    _tensor(out, "distance: out must be a contiguous float32 CUDA tensor of the mask's shape on its device",
+            shape=tuple(mask.shape), device=mask.device)
+    nz, ny, nx = mask.shape
+    work = _work(work, (lib().sift3d_amd_distance_work_bytes(nx, ny, nz) + 3) // 4, mask, what)
+    if mode == "signed":
+        _check(lib().sift3d_hip_distance_signed(mask.data_ptr(), nx, ny, nz, sp, out.data_ptr(), work.data_ptr(),
+                                                current_stream()), "sift3d_hip_distance_signed")
+    else:
+        name = "sift3d_hip_distance_sq" if mode == "sq" else "sift3d_hip_distance"
+        _check(getattr(lib(), name)(mask.data_ptr(), nx, ny, nz, sp, int(bool(invert)), out.data_ptr(),
+                                    work.data_ptr(), current_stream()), name)
+    return out
+
+
+def label_surface(labels, label, surface=None, count=None):
+    """The six-neighbour surface of one label of a label volume [nz, ny, nx] (sift3d_hip_label_surface), torch CUDA
+    float32, on torch's current stream: (surface float32 0 / 1 of labels' shape, count int64 [1] on the device)."""
+    import torch
+    _distance_volume(labels, "label_surface", "labels")
+    if surface is None:
+        surface = torch.empty_like(labels)
+    _tensor(surface, "label_surface: surface must be a contiguous float32 CUDA tensor of labels' shape on its device",
+            shape=tuple(labels.shape), device=labels.device)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=labels.device)
+    _tensor(count, "label_surface: count must be an int64 CUDA tensor [1] on labels' device", shape=(1,),
+            device=labels.device, dtype="int64")
+    nz, ny, nx = labels.shape
+    _check(lib().sift3d_hip_label_surface(labels.data_ptr(), nx, ny, nz, int(label), surface.data_ptr(),
+                                          count.data_ptr(), current_stream()), "sift3d_hip_label_surface")
+    return surface, count
+
+
+def surface_collect(surface, d2, out, count=None):
+    """Appends sqrtf(d2) at the voxels where `surface` is in (>= 0.5) to the list `out` (float32 CUDA [capacity]) in no
+    particular order (sift3d_hip_surface_collect), on torch's current stream; returns (out, count int64 [1] on the
+    device): the number of surface voxels, also where it exceeds the capacity, past which nothing is written."""
+    import torch
+    _distance_volume(surface, "surface_collect", "surface")
+    _tensor(d2, "surface_collect: d2 must be a contiguous float32 CUDA tensor of surface's shape on its device",
+            shape=tuple(surface.shape), device=surface.device)
+    _tensor(out, "surface_collect: out must be a contiguous 1-D float32 CUDA tensor on surface's device", dims=(1,),
+            device=surface.device)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=surface.device)
+    _tensor(count, "surface_collect: count must be an int64 CUDA tensor [1] on surface's device", shape=(1,),
+            device=surface.device, dtype="int64")
+    _check(lib().sift3d_hip_surface_collect(surface.data_ptr(), d2.data_ptr(), surface.numel(), out.data_ptr(),
+                                            out.numel(), count.data_ptr(), current_stream()),
+           "sift3d_hip_surface_collect")
+    return out, count
+
+
+def surface_distances(LF, LM, labels, spacing=None, work=None):
+    """The surface-distance measures of the label volumes LF and LM (torch CUDA float32 contiguous, one shape) for every
+    label of `labels` (sift3d_amd_surface_distances_device): a list of SurfaceResult records.  Synchronous: it waits
+    for torch's current stream twice per label."""
+    what = "surface_distances"
+    _distance_volume(LF, what, "labels_fixed")
+    _tensor(LM, "surface_distances: both label volumes must be contiguous float32 CUDA tensors of one shape on one "
+            "device", shape=tuple(LF.shape), device=LF.device)
+    lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+    if not 1 <= len(lab) <= SIMILARITY_MAX_BINS:
+        raise ValueError("surface_distances: between 1 and %d labels, not %d" % (SIMILARITY_MAX_BINS, len(lab)))
+    keep, sp = _spacing(spacing, what)
+    nz, ny, nx = LF.shape
+    work = _work(work, (lib().sift3d_amd_surface_distances_work_bytes(nx, ny, nz) + 3) // 4, LF, what)
+    if work.data_ptr() % 8:
+        raise ValueError("surface_distances: work must be 8-byte aligned")
+    res = (SurfaceResult * len(lab))()
+    _check(lib().sift3d_amd_surface_distances_device(LF.data_ptr(), LM.data_ptr(), nx, ny, nz,
+                                                     lab.ctypes.data_as(C.POINTER(C.c_int)), len(lab), sp, res,
+                                                     work.data_ptr(), current_stream()),
+           "sift3d_amd_surface_distances_device")
+    return list(res)
 
 
 # ---- intensity-driven affine refinement (contract: include/sift3d_amd.h, "Intensity-driven affine refinement") ----
