@@ -2094,7 +2094,8 @@ SIFT3D_AMD_API int sift3d_hip_memcpy2d_d2h(void *h_dst, size_t dst_pitch, const 
                                            size_t src_pitch, size_t width, size_t height, void *stream);
 SIFT3D_AMD_API int sift3d_hip_stream_wait_event(void *stream, void *ev);
 /* descriptor rows (768 floats) out of the ranks' gathered blocks into the global order: row g = row
- * (d_map[g] & 0xffffff) of block (d_map[g] >> 24) */
+ * (d_map[g] & 0xffffff) of block (d_map[g] >> 24); blocks are blk_bytes apart.  The rows move as float4: d_dst,
+ * d_all and blk_bytes are multiples of 16 bytes.  n == 0 is a success that touches nothing. */
 SIFT3D_AMD_API int sift3d_hip_rows_scatter(float *d_dst, const void *d_all, size_t blk_bytes,
                                            const uint32_t *d_map, uint32_t n, void *stream);
 /* d_dst[i] = max over r of d_rows[r * n + i] (the reduction step of the thread transport's all-reduce) */
@@ -2442,7 +2443,16 @@ sift3d_hip_describe_ex(const sift3d_hip_level *d_levels, int nlevels, const sift
 /* Device stages of the slab driver's keypoint exchange (sift3d_slab.hip): per-(octave, level) counts of a
  * rank's candidates; the rank's block of the all-gather (|DoG| of every candidate, then the kept candidates as
  * 56-byte records {o, s, x, y, z (global), R[9]} in order); the global list built from the gathered blocks
- * (64-byte records {.., strength, pad} behind a 64-byte header whose first int32 is the ranks' status). */
+ * (64-byte records {.., strength, pad} behind a 64-byte header whose first int32 is the ranks' status).
+ *
+ * sift3d_hip_slab_count: d_cnt[2 key] = candidates, d_cnt[2 key + 1] = kept candidates (d_keep != 0) of key
+ * (tag / ngl) * K + (tag % ngl - 1), 1 <= nkey <= 256 (else failure); d_cnt is zeroed first, also when n == 0.
+ * Contract on the tags: a candidate's tag is the index of its Gaussian level in the level table, o * ngl + s + 1
+ * with 0 <= o and 0 <= s < K (K <= ngl - 1), that is tag >= 0 and tag % ngl in 1 ... K, and its key lies below
+ * nkey.  The extrema stage produces nothing else; what the kernels do with other tags is not defined.
+ * sift3d_hip_slab_pack: n == 0 is a success that touches nothing; more than 256 * 64 * 1024 candidates are refused
+ * before any launch.  d_scratch: sift3d_hip_slab_pack_scratch_bytes(n) bytes.  A level has fewer than 2^32 voxels
+ * (idx is a uint32); the records' z is idx / (nx ny) + z_off of the candidate's level. */
 SIFT3D_AMD_API int sift3d_hip_slab_count(const sift3d_hip_cand *d_cand, const int32_t *d_keep, uint32_t n,
                                          int ngl, int K, int nkey, int32_t *d_cnt, void *stream);
 SIFT3D_AMD_API size_t sift3d_hip_slab_pack_scratch_bytes(uint32_t n);
@@ -2452,6 +2462,23 @@ SIFT3D_AMD_API int sift3d_hip_slab_pack(const sift3d_hip_level *d_levels, const 
 SIFT3D_AMD_API int sift3d_hip_slab_build(const void *d_all, size_t blk_bytes, size_t roff, size_t toff,
                                          int world, int nkey, const uint32_t *d_tab, uint32_t tot_k,
                                          uint32_t tot_c, void *d_out, void *stream);
+/* Host only, no device call: the table sift3d_hip_slab_build searches and the layout of a rank's block, from the
+ * gathered count blocks (`world` blocks of 2 nkey int32 as sift3d_hip_slab_count writes them, cnt_stride bytes
+ * apart).  tab: 2 (nkey world + 1) + 2 world (nkey + 1) words,
+ *   [segk: nseg + 1][segc: nseg + 1][ck: world * (nkey + 1)][cc: world * (nkey + 1)],  nseg = nkey * world:
+ * segk / segc[key * world + rank] = where segment (key, rank) starts in the global order of the kept / of all
+ * candidates (keys major, ranks in slab order inside a key; the last entry is the total), ck / cc[rank * (nkey + 1)
+ * + key] = where key starts in the rank's own records / values.  A rank's block is [values: 4 max(maxc, 1) bytes]
+ * [records at roff: 56 max(maxk, 1) bytes][status word at toff], each part rounded up to 16 bytes, blk = toff + 16.
+ * Failure (nothing promised about tab): NULL pointers, world < 1, nkey outside 1 ... 256, a stride shorter than a
+ * block, a negative count, or a total of candidates or of kept candidates that does not fit a uint32_t. */
+typedef struct {
+    size_t tot_c, tot_k;            /* candidates / kept candidates of all ranks */
+    size_t maxc, maxk;              /* the largest rank's */
+    size_t roff, toff, blk;         /* byte offsets of the records and the status word in a block; block size */
+} sift3d_amd_slab_layout;
+SIFT3D_AMD_API int sift3d_amd_slab_table(const void *cnt, size_t cnt_stride, int world, int nkey, uint32_t *tab,
+                                         sift3d_amd_slab_layout *lay);
 
 /* Icosahedron face table for the descriptor kernel (init_geometry, sift.c:148-259;
  * per-face constants of cart2bary, sift.c:276-297).  20 records of

@@ -678,6 +678,60 @@ typedef struct {          /* a record of the global list as sift3d_hip_slab_buil
     int32_t pad;
 } sh_out;
 
+/* The tables sift3d_hip_slab_build searches and the layout of a rank's block of the second all-gather, from the
+ * gathered count blocks (host only; include/sift3d_amd.h).  Per rank: prefix sums over keys (ck kept, cc
+ * candidates); per (key, rank), keys major: the segment starts of the two global orders. */
+int sift3d_amd_slab_table(const void *cnt, size_t cnt_stride, int world, int nkey, uint32_t *tab,
+                          sift3d_amd_slab_layout *lay)
+{
+    const int W = world, nseg = nkey * W;
+    uint32_t *segk, *segc, *ck, *cc;
+    size_t maxc = 0, maxk = 0, tot_c = 0, tot_k = 0;
+    int r, k;
+    if (!cnt || !tab || !lay || W < 1 || nkey < 1 || nkey > 256 || cnt_stride < sizeof(int32_t) * 2 * (size_t)nkey)
+        return SIFT3D_FAILURE;
+    /* every total is a uint32 in the tables and in the kernel's arguments: the counts are non-negative int32, at
+     * most 256 * world of them, so the sums below cannot wrap a size_t before they are checked */
+    for (r = 0; r < W; r++) {
+        const int32_t *a = (const int32_t *)((const char *)cnt + cnt_stride * (size_t)r);
+        for (k = 0; k < nkey; k++) {
+            if (a[2 * k] < 0 || a[2 * k + 1] < 0)
+                return SIFT3D_FAILURE;
+            tot_c += (size_t)a[2 * k];
+            tot_k += (size_t)a[2 * k + 1];
+        }
+    }
+    if (tot_c > UINT32_MAX || tot_k > UINT32_MAX)
+        return SIFT3D_FAILURE;
+    tot_c = tot_k = 0;
+    segk = tab; segc = segk + nseg + 1; ck = segc + nseg + 1; cc = ck + (size_t)W * (nkey + 1);
+    for (r = 0; r < W; r++) {
+        const int32_t *a = (const int32_t *)((const char *)cnt + cnt_stride * (size_t)r);
+        ck[(size_t)r * (nkey + 1)] = cc[(size_t)r * (nkey + 1)] = 0;
+        for (k = 0; k < nkey; k++) {
+            cc[(size_t)r * (nkey + 1) + k + 1] = cc[(size_t)r * (nkey + 1) + k] + (uint32_t)a[2 * k];
+            ck[(size_t)r * (nkey + 1) + k + 1] = ck[(size_t)r * (nkey + 1) + k] + (uint32_t)a[2 * k + 1];
+        }
+        if (cc[(size_t)r * (nkey + 1) + nkey] > maxc) maxc = cc[(size_t)r * (nkey + 1) + nkey];
+        if (ck[(size_t)r * (nkey + 1) + nkey] > maxk) maxk = ck[(size_t)r * (nkey + 1) + nkey];
+    }
+    for (k = 0; k < nkey; k++)
+        for (r = 0; r < W; r++) {
+            segc[(size_t)k * W + r] = (uint32_t)tot_c;
+            segk[(size_t)k * W + r] = (uint32_t)tot_k;
+            tot_c += cc[(size_t)r * (nkey + 1) + k + 1] - cc[(size_t)r * (nkey + 1) + k];
+            tot_k += ck[(size_t)r * (nkey + 1) + k + 1] - ck[(size_t)r * (nkey + 1) + k];
+        }
+    segc[nseg] = (uint32_t)tot_c;
+    segk[nseg] = (uint32_t)tot_k;
+    lay->tot_c = tot_c; lay->tot_k = tot_k; lay->maxc = maxc; lay->maxk = maxk;
+    /* a rank's block: [values of all its candidates][its kept records][status word] */
+    lay->roff = (sizeof(float) * (maxc ? maxc : 1) + 15) & ~(size_t)15;
+    lay->toff = lay->roff + ((56 * (maxk ? maxk : 1) + 15) & ~(size_t)15);
+    lay->blk = lay->toff + 16;
+    return SIFT3D_SUCCESS;
+}
+
 int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
 {
     const double t_start = now_s();
@@ -979,8 +1033,9 @@ int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
         const size_t cnt_bytes = ((sizeof(int32_t) * 2 * (size_t)nkey + 15) & ~(size_t)15) + 16;
         const int W = S->world, nseg = nkey * W;
         int32_t *h_cnt, *h_stat;
-        uint32_t *h_tab, *segk, *segc, *ck, *cc;
-        size_t maxc = 0, maxk = 0, tot_c = 0, tot_k = 0, roff, toff, blk, tab_words;
+        uint32_t *h_tab;
+        sift3d_amd_slab_layout lay;
+        size_t tot_c, tot_k, roff, toff, blk, tab_words;
         int any_failed = 0;
         /* [W blocks gathered][mine] */
         if (sh_ensure_dev(&S->d_cnt, &S->cnt_cap, cnt_bytes * (size_t)(W + 1)) ||
@@ -1011,33 +1066,16 @@ int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
             sh_ensure_dev(&S->d_tab, &S->tab_cap, sizeof(uint32_t) * tab_words))
             return SIFT3D_FAILURE;
         h_tab = (uint32_t *)S->h_tab;
-        segk = h_tab; segc = segk + nseg + 1; ck = segc + nseg + 1; cc = ck + (size_t)W * (nkey + 1);
-        for (r = 0; r < W; r++) {
-            const int32_t *a = (const int32_t *)((const char *)h_cnt + cnt_bytes * (size_t)r);
-            ck[(size_t)r * (nkey + 1)] = cc[(size_t)r * (nkey + 1)] = 0;
-            for (k = 0; k < nkey; k++) {
-                cc[(size_t)r * (nkey + 1) + k + 1] = cc[(size_t)r * (nkey + 1) + k] + (uint32_t)a[2 * k];
-                ck[(size_t)r * (nkey + 1) + k + 1] = ck[(size_t)r * (nkey + 1) + k] + (uint32_t)a[2 * k + 1];
-            }
-            if (cc[(size_t)r * (nkey + 1) + nkey] > maxc) maxc = cc[(size_t)r * (nkey + 1) + nkey];
-            if (ck[(size_t)r * (nkey + 1) + nkey] > maxk) maxk = ck[(size_t)r * (nkey + 1) + nkey];
+        if (sift3d_amd_slab_table(h_cnt, cnt_bytes, W, nkey, h_tab, &lay) != SIFT3D_SUCCESS) {
+            ERR("sift3d_amd_sharded_detect: the candidate counts of the %d ranks do not fit 32 bits \n", W);
+            return SIFT3D_FAILURE;               /* on every rank: all of them see the same counts */
         }
-        for (k = 0; k < nkey; k++)
-            for (r = 0; r < W; r++) {
-                segc[(size_t)k * W + r] = (uint32_t)tot_c;
-                segk[(size_t)k * W + r] = (uint32_t)tot_k;
-                tot_c += cc[(size_t)r * (nkey + 1) + k + 1] - cc[(size_t)r * (nkey + 1) + k];
-                tot_k += ck[(size_t)r * (nkey + 1) + k + 1] - ck[(size_t)r * (nkey + 1) + k];
-            }
-        segc[nseg] = (uint32_t)tot_c;
-        segk[nseg] = (uint32_t)tot_k;
+        tot_c = lay.tot_c; tot_k = lay.tot_k;
         S->ncand = (int)tot_c;
         if (S->inject == 3)
             S->failed = -3;
         /* this rank's block: [values of all its candidates][its kept records][status word] */
-        roff = (sizeof(float) * (maxc ? maxc : 1) + 15) & ~(size_t)15;
-        toff = roff + ((56 * (maxk ? maxk : 1) + 15) & ~(size_t)15);
-        blk = toff + 16;
+        roff = lay.roff; toff = lay.toff; blk = lay.blk;
         if (sh_ensure_dev(&S->d_xchg, &S->xchg_bytes, blk * (size_t)(W + 1)) ||
             sh_ensure_dev(&S->d_out, &S->out_cap, 64 + 64 * (tot_k ? tot_k : 1)) ||
             sh_ensure_pinned(&S->h_xchg, &S->hxchg_cap, 64 + 64 * (tot_k ? tot_k : 1)) ||

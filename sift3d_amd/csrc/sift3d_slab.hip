@@ -255,7 +255,9 @@ int sift3d_hip_rows_scatter(float *d_dst, const void *d_all, size_t blk_bytes, c
     return SIFT3D_SUCCESS;
 }
 
-// per-(octave, level) counts of this rank: d_cnt[2 key] candidates, d_cnt[2 key + 1] kept (nkey <= 256)
+// per-(octave, level) counts of this rank: d_cnt[2 key] candidates, d_cnt[2 key + 1] kept (nkey <= 256).
+// Contract on the tags (include/sift3d_amd.h): tag = o * ngl + s + 1 with 0 <= s < K, i.e. tag % ngl in 1 ... K,
+// and key = o * K + s < nkey; nothing is defined for other tags.
 int sift3d_hip_slab_count(const sift3d_hip_cand *d_cand, const int32_t *d_keep, uint32_t n, int ngl, int K,
                           int nkey, int32_t *d_cnt, void *stream)
 {
@@ -264,7 +266,7 @@ int sift3d_hip_slab_count(const sift3d_hip_cand *d_cand, const int32_t *d_keep, 
     HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * 2 * (size_t)nkey, (hipStream_t)stream));
     if (!n)
         return SIFT3D_SUCCESS;
-    const uint32_t nb = (n + 255) / 256;
+    const uint32_t nb = (uint32_t)(((uint64_t)n + 255) / 256);      // (no wrap for n near 2^32)
     hipLaunchKernelGGL(k_slab_count, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, (hipStream_t)stream, d_cand,
                        d_keep, n, ngl, K, nkey, d_cnt);
     LAUNCH_CHECK();
@@ -273,7 +275,7 @@ int sift3d_hip_slab_count(const sift3d_hip_cand *d_cand, const int32_t *d_keep, 
 
 size_t sift3d_hip_slab_pack_scratch_bytes(uint32_t n)
 {
-    return sizeof(uint32_t) * ((size_t)(n + SLAB_PER_BLOCK - 1) / SLAB_PER_BLOCK + 1);
+    return sizeof(uint32_t) * (((size_t)n + SLAB_PER_BLOCK - 1) / SLAB_PER_BLOCK + 1);
 }
 
 // this rank's block of the all-gather: d_vals[q] = |DoG| of candidate q; d_recs = the kept candidates as
@@ -284,7 +286,7 @@ int sift3d_hip_slab_pack(const sift3d_hip_level *d_levels, const sift3d_hip_cand
 {
     if (!n)
         return SIFT3D_SUCCESS;
-    const uint32_t nb = (n + SLAB_PER_BLOCK - 1) / SLAB_PER_BLOCK;
+    const uint32_t nb = (uint32_t)(((uint64_t)n + SLAB_PER_BLOCK - 1) / SLAB_PER_BLOCK);
     if (nb > 256 * 64)
         return SIFT3D_FAILURE;
     uint32_t *bsum = (uint32_t *)d_scratch;
@@ -300,7 +302,7 @@ int sift3d_hip_slab_pack(const sift3d_hip_level *d_levels, const sift3d_hip_cand
 int sift3d_hip_slab_build(const void *d_all, size_t blk_bytes, size_t roff, size_t toff, int world, int nkey,
                           const uint32_t *d_tab, uint32_t tot_k, uint32_t tot_c, void *d_out, void *stream)
 {
-    const uint32_t nb = (tot_k + 255) / 256;
+    const uint32_t nb = (uint32_t)(((uint64_t)tot_k + 255) / 256);
     hipLaunchKernelGGL(k_slab_build, dim3(nb ? nb : 1), dim3(256), 0, (hipStream_t)stream, (const char *)d_all,
                        blk_bytes, roff, toff, world, nkey, d_tab, tot_k, tot_c, (char *)d_out);
     LAUNCH_CHECK();

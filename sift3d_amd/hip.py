@@ -58,6 +58,18 @@ LEVEL_DTYPE = np.dtype([("data", "u8"), ("nx", "i4"), ("ny", "i4"), ("nz", "i4")
                         ("uz", "f4"), ("octave", "i4"), ("sd", "f8")], align=True)
 assert LEVEL_DTYPE.itemsize == C.sizeof(Level)
 assert KP_DTYPE.itemsize == 64 and CAND_DTYPE.itemsize == 12
+# the records of the slab driver's keypoint exchange (sift3d_slab.hip): as packed by a rank, as built for the host
+SLAB_REC_DTYPE = np.dtype([("o", "i4"), ("s", "i4"), ("x", "i4"), ("y", "i4"), ("z", "i4"), ("R", "f4", (9,))])
+SLAB_OUT_DTYPE = np.dtype([("o", "i4"), ("s", "i4"), ("x", "i4"), ("y", "i4"), ("z", "i4"), ("R", "f4", (9,)),
+                           ("strength", "f4"), ("pad", "i4")])
+SLAB_HEADER_BYTES = 64
+ROW_FLOATS = 768
+assert SLAB_REC_DTYPE.itemsize == 56 and SLAB_OUT_DTYPE.itemsize == 64
+
+
+class SlabLayout(C.Structure):                             # sift3d_amd_slab_layout
+    _fields_ = [(f, C.c_size_t) for f in ("tot_c", "tot_k", "maxc", "maxk", "roff", "toff", "blk")]
+
 
 class AffineRefineParams(C.Structure):                     # sift3d_amd_affine_refine_params
     _fields_ = [("free_mask", C.c_uint), ("levels", C.c_int), ("max_evaluations", C.c_int),
@@ -198,6 +210,14 @@ def lib():
                                                  C.c_double, vp, vp, vp, C.c_uint32, C.c_int, vp]),
         "sift3d_hip_orient_window_fits": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
         "sift3d_hip_describe": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
+        "sift3d_hip_slab_count": (C.c_int, [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "sift3d_hip_slab_pack_scratch_bytes": (C.c_size_t, [C.c_uint32]),
+        "sift3d_hip_slab_pack": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, vp]),
+        "sift3d_amd_slab_table": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, vp, C.POINTER(SlabLayout)]),
+        "sift3d_hip_slab_build": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_uint32,
+                                            C.c_uint32, vp, vp]),
+        "sift3d_hip_rows_scatter": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_uint32, vp]),
+        "sift3d_hip_max_rows": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "sift3d_hip_set_mesh": (C.c_int, [C.POINTER(C.c_float)]),
         "sift3d_hip_synth_lattice": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]),
         "sift3d_hip_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
@@ -2724,3 +2744,96 @@ def describe_rcp_check(e_lo, n_exp):
     _check(f(int(e_lo), int(n_exp), C.byref(bad), C.byref(first), current_stream()),
            "sift3d_hip_describe_rcp_check")
     return int(bad.value), int(first.value)
+
+
+# ---- the device stages of the slab driver's keypoint exchange on the caller's buffers (sift3d_slab.hip) -------------
+# Every buffer is the caller's (a slice of a larger tensor is fine: guard bands around it stay the caller's business);
+# nothing is allocated, sized or read back here.  What the C entries refuse (nkey, n) reaches the caller as RuntimeError.
+
+def _dev_bytes(t, need, what, name, dtype=None):
+    _tensor(t, "%s: %s must be a contiguous %sCUDA tensor of >= %d bytes" % (what, name, dtype + " " if dtype else "",
+                                                                             need), dtype=dtype)
+    if t.numel() * t.element_size() < need:
+        raise ValueError("%s: %s holds fewer than %d bytes" % (what, name, need))
+    return t.data_ptr()
+
+
+def slab_count(cand, keep, n, ngl, K, nkey, cnt):
+    """sift3d_hip_slab_count: cand n CAND_DTYPE records (uint8 tensor), keep int32 [>= n], cnt int32 [2 nkey]."""
+    what, n = "slab_count", int(n)
+    _tensor(cnt, "slab_count: cnt must be a contiguous int32 CUDA tensor [2 * nkey]", shape=(2 * max(int(nkey), 0),),
+            dtype="int32")
+    _check(lib().sift3d_hip_slab_count(_dev_bytes(cand, CAND_DTYPE.itemsize * n, what, "cand", "uint8"),
+                                       _dev_bytes(keep, 4 * n, what, "keep", "int32"), n, int(ngl), int(K),
+                                       int(nkey), cnt.data_ptr(), current_stream()), "sift3d_hip_slab_count")
+
+
+def slab_pack_scratch_bytes(n):
+    return int(lib().sift3d_hip_slab_pack_scratch_bytes(int(n)))
+
+
+def slab_pack(d_levels, cand, keep, R, n, ngl, vals, recs, scratch):
+    """sift3d_hip_slab_pack: vals float32 [>= n]; recs a uint8 tensor of whole SLAB_REC_DTYPE records, room for every
+    kept candidate (the caller's count); scratch >= slab_pack_scratch_bytes(n) bytes."""
+    what, n = "slab_pack", int(n)
+    _tensor(d_levels, "slab_pack: d_levels must be the uint8 CUDA tensor of level_table()", dtype="uint8")
+    _dev_bytes(recs, 0, what, "recs", "uint8")
+    if d_levels.numel() % LEVEL_DTYPE.itemsize or recs.numel() % SLAB_REC_DTYPE.itemsize:
+        raise ValueError("slab_pack: d_levels / recs must hold whole records")
+    _check(lib().sift3d_hip_slab_pack(d_levels.data_ptr(), _dev_bytes(cand, CAND_DTYPE.itemsize * n, what, "cand",
+                                                                      "uint8"),
+                                      _dev_bytes(keep, 4 * n, what, "keep", "int32"),
+                                      _dev_bytes(R, 36 * n, what, "R", "float32"), n, int(ngl),
+                                      _dev_bytes(vals, 4 * n, what, "vals", "float32"), recs.data_ptr(),
+                                      _dev_bytes(scratch, slab_pack_scratch_bytes(n), what, "scratch"),
+                                      current_stream()), "sift3d_hip_slab_pack")
+
+
+def slab_table_words(world, nkey):
+    return 2 * (nkey * world + 1) + 2 * world * (nkey + 1)
+
+
+def slab_table(cnt, nkey):
+    """sift3d_amd_slab_table (host): cnt a C-contiguous int32 numpy array [world, >= 2 nkey], a row per rank ->
+    (the table as uint32 words, the layout as a dict of the header's fields)."""
+    cnt = np.asarray(cnt)
+    if cnt.dtype != np.int32 or cnt.ndim != 2 or not cnt.flags.c_contiguous or cnt.shape[0] < 1:
+        raise ValueError("slab_table: cnt must be a C-contiguous int32 array [world, >= 2 * nkey]")
+    world, nkey = cnt.shape[0], int(nkey)
+    tab = np.zeros(slab_table_words(world, min(max(nkey, 1), 256)), np.uint32)
+    lay = SlabLayout()
+    _check(lib().sift3d_amd_slab_table(cnt.ctypes.data, cnt.strides[0], world, nkey, tab.ctypes.data, C.byref(lay)),
+           "sift3d_amd_slab_table")
+    return tab, {f: int(getattr(lay, f)) for f, _ in SlabLayout._fields_}
+
+
+def slab_build(all_blocks, blk_bytes, roff, toff, world, nkey, tab, tot_k, tot_c, out):
+    """sift3d_hip_slab_build: all_blocks world blocks of blk_bytes; tab the words of slab_table on the device; out
+    SLAB_HEADER_BYTES + tot_k SLAB_OUT_DTYPE records."""
+    what = "slab_build"
+    _check(lib().sift3d_hip_slab_build(_dev_bytes(all_blocks, int(world) * int(blk_bytes), what, "all_blocks"),
+                                       int(blk_bytes), int(roff), int(toff), int(world), int(nkey),
+                                       _dev_bytes(tab, 4 * slab_table_words(int(world), int(nkey)), what, "tab"),
+                                       int(tot_k), int(tot_c),
+                                       _dev_bytes(out, SLAB_HEADER_BYTES + SLAB_OUT_DTYPE.itemsize * int(tot_k), what,
+                                                  "out"), current_stream()), "sift3d_hip_slab_build")
+
+
+def rows_scatter(dst, all_blocks, blk_bytes, rows_map, n):
+    """sift3d_hip_rows_scatter: dst float32 [>= n * ROW_FLOATS], row g = row (map[g] & 0xffffff) of block map[g] >> 24;
+    blk_bytes and both buffers on 16-byte boundaries (the rows move as float4)."""
+    what, n = "rows_scatter", int(n)
+    p = (_dev_bytes(dst, 4 * ROW_FLOATS * n, what, "dst", "float32"), _dev_bytes(all_blocks, 0, what, "all_blocks"),
+         _dev_bytes(rows_map, 4 * n, what, "rows_map"))
+    if int(blk_bytes) % 16 or (n and (p[0] % 16 or p[1] % 16)):
+        raise ValueError("rows_scatter: blk_bytes, dst and all_blocks must be multiples of 16 bytes")
+    _check(lib().sift3d_hip_rows_scatter(p[0], p[1], int(blk_bytes), p[2], n, current_stream()),
+           "sift3d_hip_rows_scatter")
+
+
+def max_rows(dst, rows, nrows, n):
+    """sift3d_hip_max_rows: dst[i] = max over r of rows[r * n + i] (float32 tensors of >= n and >= nrows * n)."""
+    what, nrows, n = "max_rows", int(nrows), int(n)
+    _check(lib().sift3d_hip_max_rows(_dev_bytes(dst, 4 * max(n, 0), what, "dst", "float32"),
+                                     _dev_bytes(rows, 4 * max(nrows, 0) * max(n, 0), what, "rows", "float32"), nrows, n,
+                                     current_stream()), "sift3d_hip_max_rows")
