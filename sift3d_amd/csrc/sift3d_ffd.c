@@ -4,9 +4,9 @@
  *
  * The contract is in include/sift3d_amd.h, "B-spline free-form deformation" (the MSD) and "Mutual-information free-form
  * deformation (Mattes)": two metrics, one evaluation entry body and one driver loop over either.  The kernels are in
- * sift3d_ffd.hip (the histogram pass in sift3d_affine_refine.hip), reached through the launchers below after the checks
- * here.  Arguments are checked before the device is touched, so bad
- * input is refused on a machine without a GPU too.
+ * sift3d_ffd.hip (the histogram pass in sift3d_affine_refine.hip), reached through the launchers of sift3d_ffd_eval.h
+ * after the checks here.  Arguments are checked before the device is touched, so bad input is refused on a machine
+ * without a GPU too.
  *
  * The Jacobian penalty (header, "Jacobian penalty"; kernels in sift3d_jacobian_penalty.hip) has its checked entry here
  * and is the optional third term of the driver's cost.
@@ -18,61 +18,7 @@
  * and adjoint, whose landmarks the host puts in cell order, and the optional last term of the driver's cost. */
 #include <stddef.h>
 
-#include "sift3d_ffd_jac.h"
-#include "sift3d_ffd_landmarks.h"
-
-int sift3d_ffd_points_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                             const double *A, const double *d_P, int m, double *d_T, void *stream);
-int sift3d_ffd_landmarks_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                                const sift3d_ffd_lm *lm, int adjoint, double *d_r, void *stream);
-int sift3d_ffd_evaluate_lm_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
-                                  int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
-                                  int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
-                                  double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
-                                  const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm);
-int sift3d_ffd_mi_lm_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
-                            const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
-                            int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
-                            double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
-                            double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
-                            const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm);
-int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
-                                   double *d_rec, double *d_S, double *d_work, void *stream);
-int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
-                                   int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
-                                   int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
-                                   double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
-                                   const float *d_WM, const sift3d_ffd_jac *jac);
-int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
-                             const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
-                             int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
-                             double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
-                             double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
-                             const float *d_WM, const sift3d_ffd_jac *jac);
-int sift3d_ffd_evaluate_channels_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
-                                        int nx, int ny, int nz, int nc, const float *d_field, const float *d_lat, int gx,
-                                        int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
-                                        double bending, double *d_rec, float *d_grad, double *d_work, void *stream,
-                                        const float *d_WF, const float *d_WM, const sift3d_ffd_jac *jac);
-int sift3d_ffd_jacobian_gradient_launch(const char *fn, const float *d_field, int ox, int oy, int oz, int gx, int gy,
-                                        int gz, int dx, int dy, int dz, const float *d_w, double ref, double *d_rec,
-                                        double *d_GJ, double *d_work, void *stream);
-int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                            const float *d_w, const double *A, int ox, int oy, int oz, float *d_field, void *stream);
-int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
-                               int ny, int nz, const float *d_field, const float *d_lat, int gx, int gy, int gz,
-                               int dx, int dy, int dz, const float *d_w, const double *stencils, double bending,
-                               double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
-                               const float *d_WM);
-int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
-                         const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
-                         int gy, int gz, int dx, int dy, int dz, const float *d_w, const double *stencils,
-                         double bending, int bins, float lo_f, float s_f, float lo_m, float hi_m, const double *d_W,
-                         double *d_rec, float *d_grad, double *d_work, void *stream, const float *d_WF,
-                         const float *d_WM);
-int sift3d_ffd_step_launch(const float *d_c, const float *d_grad, float a, float *d_out, size_t n, void *stream);
-int sift3d_ffd_refine2_launch(const float *d_c, int cx, int cy, int cz, float *d_f, int fx, int fy, int fz,
-                              void *stream);
+#include "sift3d_ffd_eval.h"
 
 int sift3d_amd_ffd_lattice_dim(int o, int delta)
 {
@@ -211,18 +157,41 @@ typedef struct {
     const double *d_W;
 } ffd_mi_args;
 
-/* the shared body of the four entries: d_WF, d_WM are the masks ("Masks") or NULL; mi: the MI evaluation's further
- * arguments, checked after the FFD entries' own, or NULL (the MSD); nc: 0 (one volume each, the single-channel kernels)
- * or the channels of the stacks d_F and d_M (the channels entry, which has checked nc >= 1); lm (the landmarks entry,
- * which has checked them and their buffers; else NULL): the landmark term, lmh its host side, and jac the penalty or
- * NULL (the MSD of single volumes only) */
+/* The parts (sift3d_ffd_eval.h) of the evaluation e.  value: the bending value; gradient: the image term, the bending
+ * gradient and the combined gradient.  The MSD evaluates with both; the MI driver with the value per evaluation and the
+ * gradient where a step starts.  A penalty and landmarks that e names run with either: their gradient pass where a
+ * gradient is formed and their weight is > 0, else their record alone. */
+static unsigned ffd_parts(const sift3d_ffd_eval *e, int value, int gradient)
+{
+    const unsigned jac = !e->jac ? 0u : gradient && e->jac->weight > 0.0 ? FFD_JAC_GRAD : FFD_JAC_VALUE;
+    const unsigned lm = !e->lm ? 0u : gradient && e->lm->weight > 0.0 ? FFD_LM_GRAD : FFD_LM_VALUE;
+    return (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u) | jac | lm;
+}
+
+/* what an entry has beside sift3d_hip_ffd_evaluate's arguments; all zero: nothing */
+typedef struct {
+    const float *d_WF, *d_WM;                    /* the masks ("Masks") or NULL */
+    const ffd_mi_args *mi;                       /* the MI evaluation's further arguments, checked after the FFD
+                                                    entries' own, or NULL (the MSD) */
+    int nc;                                      /* 0 (one volume each, the single-channel kernels) or the channels of
+                                                    the stacks d_F and d_M (the channels entry, which has checked it) */
+    const sift3d_ffd_jac *jac;                   /* the penalty or NULL (the landmarks entry only) */
+    struct ffd_lm_host_s *lmh;                   /* the landmarks entry, which has checked them and their buffers (else
+                                                    NULL): the host side of the landmark term, */
+    sift3d_ffd_lm *lm;                           /* and the term */
+} ffd_entry_opts;
+
+/* the shared body of the evaluation entries */
 static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx,
                               int ny, int nz, const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz,
                               const double *A, double bending, float *d_field, void *d_record, float *d_grad,
-                              void *d_work, void *stream, const float *d_WF, const float *d_WM, const ffd_mi_args *mi,
-                              int nc, const sift3d_ffd_jac *jac, struct ffd_lm_host_s *lmh, sift3d_ffd_lm *lm)
+                              void *d_work, void *stream, const ffd_entry_opts *o)
 {
-    const int ch = nc ? nc : 1;
+    const float *d_WF = o->d_WF, *d_WM = o->d_WM;
+    const ffd_mi_args *mi = o->mi;
+    const int ch = o->nc ? o->nc : 1;
+    sift3d_ffd_mi z;
+    sift3d_ffd_eval e;
     int delta[3];
     double st[27];
     float s_f = 0.0f;
@@ -258,41 +227,28 @@ static int ffd_evaluate_entry(const char *what, const float *d_F, int ox, int oy
     ffd_stencils(delta, st);
     if (ffd_upload_weights(dx, dy, dz, (float *)d_work, stream) ||
         sift3d_ffd_field_launch(what, d_lattice, gx, gy, gz, dx, dy, dz, (const float *)d_work, A, ox, oy, oz, d_field,
-                                stream))
+                                stream) ||
+        (o->lm && ffd_lm_prepare(o->lmh, o->lm, gx, gy, gz, delta, 1.0, stream)))
         return SIFT3D_FAILURE;
-    if (lm) {
-        if (ffd_lm_prepare(lmh, lm, gx, gy, gz, delta, 1.0, stream))
-            return SIFT3D_FAILURE;
-        return sift3d_ffd_evaluate_lm_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx,
-                                             dy, dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
-                                             (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream,
-                                             d_WF, d_WM, jac, lm);
-    }
     if (mi)
-        return sift3d_ffd_mi_launch(what, 1, 1, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
-                                    dz, (const float *)d_work, st, bending, mi->bins, mi->lo_f, s_f, mi->lo_m, mi->hi_m,
-                                    mi->d_W, (double *)d_record, d_grad,
-                                    (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
-                                    d_WM);
-    if (nc)
-        return sift3d_ffd_evaluate_channels_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, nc, d_field, d_lattice, gx,
-                                                   gy, gz, dx, dy, dz, (const float *)d_work, st, bending,
-                                                   (double *)d_record, d_grad,
-                                                   (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))),
-                                                   stream, d_WF, d_WM, NULL);
-    return sift3d_ffd_evaluate_launch(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lattice, gx, gy, gz, dx, dy,
-                                      dz, (const float *)d_work, st, bending, (double *)d_record, d_grad,
-                                      (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))), stream, d_WF,
-                                      d_WM);
+        z = (sift3d_ffd_mi){ mi->bins, mi->lo_f, s_f, mi->lo_m, mi->hi_m, mi->d_W };
+    e = (sift3d_ffd_eval){ .d_F = d_F, .d_M = d_M, .ox = ox, .oy = oy, .oz = oz, .nx = nx, .ny = ny, .nz = nz,
+                           .nc = o->nc, .d_WF = d_WF, .d_WM = d_WM, .d_field = d_field, .d_lat = d_lattice, .gx = gx,
+                           .gy = gy, .gz = gz, .dx = dx, .dy = dy, .dz = dz, .d_w = (const float *)d_work,
+                           .stencils = st, .bending = bending, .mi = mi ? &z : NULL, .jac = o->jac, .lm = o->lm,
+                           .d_rec = (double *)d_record, .d_grad = d_grad,
+                           .d_work = (double *)((char *)d_work + pad16(ffd_weights_bytes(dx, dy, dz))),
+                           .stream = stream };
+    return sift3d_ffd_evaluate_launch(what, ffd_parts(&e, 1, 1), &e);
 }
 
 int sift3d_hip_ffd_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
                             const float *d_lattice, int gx, int gy, int gz, int dx, int dy, int dz, const double *A,
                             double bending, float *d_field, void *d_record, float *d_grad, void *d_work, void *stream)
 {
+    const ffd_entry_opts o = { .nc = 0 };
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, NULL, NULL, NULL, 0, NULL, NULL,
-                              NULL);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, &o);
 }
 
 int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -300,9 +256,9 @@ int sift3d_hip_ffd_evaluate_masked(const float *d_F, int ox, int oy, int oz, con
                                    const double *A, double bending, float *d_field, void *d_record, float *d_grad,
                                    void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
+    const ffd_entry_opts o = { .d_WF = d_WF, .d_WM = d_WM };
     return ffd_evaluate_entry("sift3d_hip_ffd_evaluate_masked", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy,
-                              gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM,
-                              NULL, 0, NULL, NULL, NULL);
+                              gz, dx, dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, &o);
 }
 
 /* one force volume whatever nc is: the single-channel evaluation's work */
@@ -317,10 +273,11 @@ int sift3d_hip_ffd_evaluate_channels(const float *d_F, int ox, int oy, int oz, c
                                      void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
     static const char what[] = "sift3d_hip_ffd_evaluate_channels";
+    const ffd_entry_opts o = { .d_WF = d_WF, .d_WM = d_WM, .nc = nc };
     if (check_channels(what, nc))
         return SIFT3D_FAILURE;
     return ffd_evaluate_entry(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx, dy, dz, A, bending,
-                              d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, NULL, nc, NULL, NULL, NULL);
+                              d_field, d_record, d_grad, d_work, stream, &o);
 }
 
 int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -330,9 +287,9 @@ int sift3d_hip_ffd_mi_evaluate(const float *d_F, int ox, int oy, int oz, const f
                                float lo_m, float hi_m, const double *d_W)
 {
     const ffd_mi_args mi = { bins, lo_f, hi_f, lo_m, hi_m, d_W };
+    const ffd_entry_opts o = { .d_WF = d_WF, .d_WM = d_WM, .mi = &mi };
     return ffd_evaluate_entry("sift3d_hip_ffd_mi_evaluate", d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx,
-                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, &mi, 0, NULL, NULL,
-                              NULL);
+                              dy, dz, A, bending, d_field, d_record, d_grad, d_work, stream, &o);
 }
 
 size_t sift3d_amd_ffd_bending_work_bytes(int gx, int gy, int gz)
@@ -346,6 +303,7 @@ int sift3d_hip_ffd_bending(const float *d_lattice, int gx, int gy, int gz, int d
                            void *d_work, void *stream)
 {
     static const char what[] = "sift3d_hip_ffd_bending";
+    sift3d_ffd_eval e;
     int delta[3];
     double st[27];
     if (!d_lattice || !d_record || !d_work)
@@ -366,8 +324,9 @@ int sift3d_hip_ffd_bending(const float *d_lattice, int gx, int gy, int gz, int d
     delta[0] = dx; delta[1] = dy; delta[2] = dz;
     ffd_stencils(delta, st);
     /* the launcher's scratch layout with an empty image grid: slots, then D */
-    return sift3d_ffd_evaluate_launch(what, NULL, 0, 0, 0, NULL, 0, 0, 0, NULL, d_lattice, gx, gy, gz, dx, dy, dz, NULL,
-                                      st, 0.0, (double *)d_record, NULL, (double *)d_work, stream, NULL, NULL);
+    e = (sift3d_ffd_eval){ .d_lat = d_lattice, .gx = gx, .gy = gy, .gz = gz, .dx = dx, .dy = dy, .dz = dz, .stencils = st,
+                           .d_rec = (double *)d_record, .d_work = (double *)d_work, .stream = stream };
+    return sift3d_ffd_evaluate_launch(what, FFD_BEND_VALUE | FFD_BEND_GRAD, &e);
 }
 
 int sift3d_hip_ffd_refine2(const float *d_coarse, int ox, int oy, int oz, int dx, int dy, int dz, float *d_fine,
@@ -695,6 +654,7 @@ int sift3d_hip_ffd_evaluate_landmarks(const float *d_F, int ox, int oy, int oz, 
     ffd_lm_host h = { P, Q, w, m, landmark_weight, NULL, 1.0, NULL, NULL, NULL, NULL };
     sift3d_ffd_jac jac;
     sift3d_ffd_lm lm;
+    const ffd_entry_opts o = { .d_WF = d_WF, .d_WM = d_WM, .jac = d_jac ? &jac : NULL, .lmh = &h, .lm = &lm };
     double ref = 1.0;
     int rc;
     if (!d_F || !d_M || !d_lattice || !d_field || !d_record || !d_grad || !d_work || !d_lm)
@@ -741,7 +701,7 @@ int sift3d_hip_ffd_evaluate_landmarks(const float *d_F, int ox, int oy, int oz, 
     lm.d_GL = lm.d_rec + 4;
     lm.d_work = lm.d_GL + 3 * grid_voxels(gx, gy, gz);
     rc = ffd_evaluate_entry(what, d_F, ox, oy, oz, d_M, nx, ny, nz, d_lattice, gx, gy, gz, dx, dy, dz, A, bending,
-                            d_field, d_record, d_grad, d_work, stream, d_WF, d_WM, NULL, 0, d_jac ? &jac : NULL, &h, &lm);
+                            d_field, d_record, d_grad, d_work, stream, &o);
     if (rc == SIFT3D_SUCCESS && sift3d_hip_stream_sync(stream))
         rc = SIFT3D_FAILURE;                                 /* the staging is released only behind its copies */
     free(h.rows);
@@ -885,7 +845,7 @@ typedef struct {
     double bending;
     void *stream;
     mi_state *ms;                                /* MI (sift3d_affine_refine.c): bins, ranges, histogram, W; or NULL */
-    float s_f;                                   /* MI: the fixed bin's scale */
+    sift3d_ffd_mi mi;                            /* MI: ms' bins, ranges and device table with the fixed bin's scale */
     const sift3d_ffd_jac *jac;                   /* the Jacobian penalty's weight and buffers; or NULL */
     int nc;                                      /* the channels of the levels' stacks; 0: single volumes */
     const sift3d_ffd_lm *lm;                     /* the landmark term's weight and buffers on this level; or NULL */
@@ -914,6 +874,18 @@ static void ffd_lm_mean(const ffd_ctx *x, ffd_eval *e)
     e->L = x->lm && e->lm[1] != 0.0 ? ((0.5 * x->lm->scale) * e->lm[0]) / e->lm[1] : 0.0;
 }
 
+/* the descriptor of an evaluation at lattice c on `lv`, its gradient going to `grad` */
+static sift3d_ffd_eval ffd_describe(const ffd_ctx *x, const ffd_level *lv, const float *c, float *grad)
+{
+    const sift3d_ffd_eval d = { .d_F = lv->F, .d_M = lv->M, .ox = lv->ox, .oy = lv->oy, .oz = lv->oz, .nx = lv->nx,
+                                .ny = lv->ny, .nz = lv->nz, .nc = x->nc, .d_WF = lv->WF, .d_WM = lv->WM,
+                                .d_field = x->d_field, .d_lat = c, .gx = lv->gx, .gy = lv->gy, .gz = lv->gz,
+                                .dx = x->d[0], .dy = x->d[1], .dz = x->d[2], .d_w = x->d_w, .stencils = x->st,
+                                .bending = x->bending, .mi = x->ms ? &x->mi : NULL, .jac = x->jac, .lm = x->lm,
+                                .d_rec = x->d_rec, .d_grad = grad, .d_work = x->d_eval, .stream = x->stream };
+    return d;
+}
+
 /* one evaluation at lattice c on `lv`: the field, then
  *   MSD: the record, R and the gradient, the head's copy to the host and the wait for it;
  *   MI:  the histogram through the field (its partial counts in the evaluation's partial slots) and R, histogram, count
@@ -924,19 +896,17 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
                         float *grad, ffd_eval *e)
 {
     mi_state *ms = x->ms;
+    const sift3d_ffd_eval d = ffd_describe(x, lv, c, grad);
     if (sift3d_ffd_field_launch(what, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, A, lv->ox, lv->oy,
                                 lv->oz, x->d_field, x->stream))
         return SIFT3D_FAILURE;
     if (ms) {
         const size_t cells = (size_t)ms->bins * ms->bins;
         if (sift3d_parzen_hist_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, NULL,
-                                      x->d_field, ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m,
+                                      x->d_field, ms->bins, ms->lo_f, x->mi.s_f, ms->lo_m, ms->hi_m,
                                       (unsigned long long *)ms->d_hist, (unsigned long long *)(ms->d_hist + cells),
                                       x->d_eval, x->stream, lv->WF, lv->WM) ||
-            sift3d_ffd_mi_lm_launch(what, 1, 0, NULL, lv->ox, lv->oy, lv->oz, NULL, lv->nx, lv->ny, lv->nz, x->d_field,
-                                    c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending,
-                                    ms->bins, ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval,
-                                    x->stream, lv->WF, lv->WM, x->jac, x->lm) ||
+            sift3d_ffd_evaluate_launch(what, ffd_parts(&d, 1, 0), &d) ||
             sift3d_hip_memcpy_d2h(ms->hist, ms->d_hist, (cells + 1) * sizeof(uint64_t), x->stream) ||
             sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
             ffd_lm_fetch(x, e) || sift3d_hip_stream_sync(x->stream) ||
@@ -950,14 +920,7 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
         ffd_lm_mean(x, e);
         return SIFT3D_SUCCESS;
     }
-    if ((x->nc ? sift3d_ffd_evaluate_channels_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
-                                                     x->nc, x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1],
-                                                     x->d[2], x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval,
-                                                     x->stream, lv->WF, lv->WM, x->jac)
-               : sift3d_ffd_evaluate_lm_launch(what, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz,
-                                               x->d_field, c, lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2],
-                                               x->d_w, x->st, x->bending, x->d_rec, grad, x->d_eval, x->stream,
-                                               lv->WF, lv->WM, x->jac, x->lm)) ||
+    if (sift3d_ffd_evaluate_launch(what, ffd_parts(&d, 1, 1), &d) ||
         sift3d_hip_memcpy_d2h(&e->h, x->d_rec, sizeof(e->h), x->stream) || ffd_jac_fetch(x, e) ||
         ffd_lm_fetch(x, e) || sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
@@ -970,19 +933,20 @@ static int ffd_evaluate(const char *what, const ffd_ctx *x, const ffd_level *lv,
 /* MI: the gradient at c, the lattice of the evaluation that left its table in ms->W, its field in d_field and its
  * second derivatives in the work buffer (no evaluation was made since): W to the device, the force, adjoint, bending
  * gradient and combine passes (with a penalty of weight > 0, its value and gradient passes on the same field: the same
- * record once more, S and GJ; with landmarks of weight > 0 their value and adjoint passes likewise), gmax to the host
- * and the wait for it */
+ * record once more, S and GJ; with landmarks of weight > 0 their value and adjoint passes likewise; with weight 0
+ * neither runs at all), gmax to the host and the wait for it */
 static int ffd_mi_gradient(const char *what, const ffd_ctx *x, const ffd_level *lv, const float *c, float *grad,
                            ffd_eval *e)
 {
     mi_state *ms = x->ms;
+    sift3d_ffd_eval d = ffd_describe(x, lv, c, grad);
     ffd_head h;
+    if (d.jac && !(d.jac->weight > 0))
+        d.jac = NULL;
+    if (d.lm && !(d.lm->weight > 0))
+        d.lm = NULL;
     if (sift3d_hip_memcpy_h2d(ms->d_W, ms->W, (size_t)ms->bins * ms->bins * sizeof(double), x->stream) ||
-        sift3d_ffd_mi_lm_launch(what, 0, 1, lv->F, lv->ox, lv->oy, lv->oz, lv->M, lv->nx, lv->ny, lv->nz, x->d_field, c,
-                                lv->gx, lv->gy, lv->gz, x->d[0], x->d[1], x->d[2], x->d_w, x->st, x->bending, ms->bins,
-                                ms->lo_f, x->s_f, ms->lo_m, ms->hi_m, ms->d_W, x->d_rec, grad, x->d_eval, x->stream,
-                                lv->WF, lv->WM, x->jac && x->jac->weight > 0 ? x->jac : NULL,
-                                x->lm && x->lm->weight > 0 ? x->lm : NULL) ||
+        sift3d_ffd_evaluate_launch(what, ffd_parts(&d, 0, 1), &d) ||
         sift3d_hip_memcpy_d2h(&h, x->d_rec, sizeof(h), x->stream) || sift3d_hip_stream_sync(x->stream))
         return SIFT3D_FAILURE;
     e->h.gmax = h.gmax;
@@ -1034,24 +998,43 @@ static size_t ffd_channels_base_bytes(int ox, int oy, int oz, const int *d)
            5 * ffd_lattice_bytes(ox, oy, oz, d);
 }
 
-/* the shared body of the drivers: `masked` selects the work buffer's size; the masks may still be NULL.  ms (MI;
- * else NULL): bins and ranges, checked here after the FFD drivers' own checks; the cost's image term is -mi, the
- * gradient is made only at the lattice a step starts from, and ms->sim leaves with the measures at the final lattice on
- * level 0.  penalty (the Jacobian driver; else NULL): the array parallel to the trail; `jacobian` is the weight and
- * `ref` the reference determinant, both checked by the caller, and the work buffer is that driver's.
- * src (the channels driver; else NULL): the caller's levels, checked by the caller, of nc channels each.  d_F .. d_WM
- * are then level 0's; the other levels are taken from src where the other drivers restrict the level above, and the
- * work buffer is sift3d_amd_ffd_refine_channels_work_bytes().
- * lmh (the landmarks driver; else NULL; never with src): the landmarks, checked by the caller, their weight and the
- * array parallel to the trail, with staging for level 0's lattice; the work buffer is that driver's whether or not
- * there is a penalty. */
+/* what a driver has beside sift3d_amd_ffd_refine_device's arguments; all zero: nothing */
+typedef struct {
+    int masked;                                  /* selects the work buffer's size; the masks may still be NULL */
+    const float *d_WF, *d_WM;
+    mi_state *ms;                                /* MI (else NULL): bins and ranges, checked by the body after the FFD
+                                                    drivers' own checks; the cost's image term is -mi, the gradient is
+                                                    made only at the lattice a step starts from, and ms->sim leaves with
+                                                    the measures at the final lattice on level 0 */
+    double jacobian, ref;                        /* with `penalty`: the weight and the reference determinant, both
+                                                    checked by the caller */
+    sift3d_amd_ffd_penalty *penalty;             /* the Jacobian driver (else NULL): the array parallel to the trail;
+                                                    the work buffer is that driver's */
+    const sift3d_amd_ffd_level *src;             /* the channels driver (else NULL): the caller's levels, checked by the
+                                                    caller, of nc channels each.  d_F .. d_WM are then level 0's; the
+                                                    other levels are taken from src where the other drivers restrict
+                                                    the level above, and the work buffer is
+                                                    sift3d_amd_ffd_refine_channels_work_bytes() */
+    int nc;
+    ffd_lm_host *lmh;                            /* the landmarks driver (else NULL; never with src): the landmarks,
+                                                    checked by the caller, their weight and the array parallel to the
+                                                    trail, with staging for level 0's lattice; the work buffer is that
+                                                    driver's whether or not there is a penalty */
+} ffd_refine_opts;
+
+/* the shared body of the drivers */
 static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
                       int nz, const double *A_in, const sift3d_amd_ffd_refine_params *params,
                       sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
-                      void *stream, int masked, const float *d_WF, const float *d_WM, mi_state *ms, double jacobian,
-                      double ref, sift3d_amd_ffd_penalty *penalty, const sift3d_amd_ffd_level *src, int nc,
-                      ffd_lm_host *lmh)
+                      void *stream, const ffd_refine_opts *o)
 {
+    const float *d_WF = o->d_WF, *d_WM = o->d_WM;
+    mi_state *ms = o->ms;
+    const double jacobian = o->jacobian;
+    sift3d_amd_ffd_penalty *penalty = o->penalty;
+    const sift3d_amd_ffd_level *src = o->src;
+    ffd_lm_host *lmh = o->lmh;
+    const int nc = o->nc;
     const int ch = src ? nc : 1;
     const double lambda = lmh ? lmh->weight : 0.0;
     sift3d_ffd_jac jac;
@@ -1097,7 +1080,7 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
                                                                                           prm.spacing[1], prm.spacing[2])
                                               : (penalty  ? sift3d_amd_ffd_refine_jacobian_work_bytes
                                                  : ms     ? sift3d_amd_ffd_mi_refine_work_bytes
-                                                 : masked ? sift3d_amd_ffd_refine_masked_work_bytes
+                                                 : o->masked ? sift3d_amd_ffd_refine_masked_work_bytes
                                                           : sift3d_amd_ffd_refine_work_bytes)(
                                                     ox, oy, oz, nx, ny, nz, prm.spacing[0], prm.spacing[1],
                                                     prm.spacing[2], prm.levels) } };
@@ -1130,7 +1113,6 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     x.bending = prm.bending;
     x.stream = stream;
     x.ms = ms;
-    x.s_f = s_f;
     x.jac = NULL;
     x.nc = src ? nc : 0;
     x.lm = NULL;
@@ -1153,7 +1135,7 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     if (penalty) {                                           /* behind everything the MI driver lays out (channels:
                                                                 behind the lattices) */
         jac.weight = jacobian;
-        jac.ref = ref;
+        jac.ref = o->ref;
         jac.d_rec = (double *)(w + work_bytes);
         jac.d_GJ = (double *)(w + work_bytes + SIFT3D_AMD_JACOBIAN_PENALTY_RECORD_BYTES);
         jac.d_work = jac.d_GJ + 3 * grid_voxels(lv[0].gx, lv[0].gy, lv[0].gz);
@@ -1162,6 +1144,7 @@ static int ffd_refine(const char *what, const float *d_F, int ox, int oy, int oz
     if (ms) {                                                /* behind everything the masked driver lays out */
         ms->d_hist = (uint64_t *)(w + work_bytes - MI_EXTRA_BYTES);
         ms->d_W = (double *)(w + work_bytes - MI_TABLE_BYTES);
+        x.mi = (sift3d_ffd_mi){ ms->bins, ms->lo_f, s_f, ms->lo_m, ms->hi_m, ms->d_W };
     }
     if (ffd_upload_weights(prm.spacing[0], prm.spacing[1], prm.spacing[2], (float *)w, stream))
         return SIFT3D_FAILURE;
@@ -1293,8 +1276,9 @@ int sift3d_amd_ffd_refine_device(const float *d_F, int ox, int oy, int oz, const
                                  sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field, void *d_work,
                                  void *stream)
 {
+    const ffd_refine_opts o = { .masked = 0 };
     return ffd_refine("sift3d_amd_ffd_refine_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 0, NULL, NULL, NULL, 0.0, 1.0, NULL, NULL, 0, NULL);
+                      d_lattice, d_field, d_work, stream, &o);
 }
 
 int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
@@ -1302,8 +1286,9 @@ int sift3d_amd_ffd_refine_masked_device(const float *d_F, int ox, int oy, int oz
                                         sift3d_amd_ffd_refine_result *result, float *d_lattice, float *d_field,
                                         void *d_work, void *stream, const float *d_WF, const float *d_WM)
 {
+    const ffd_refine_opts o = { .masked = 1, .d_WF = d_WF, .d_WM = d_WM };
     return ffd_refine("sift3d_amd_ffd_refine_masked_device", d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result,
-                      d_lattice, d_field, d_work, stream, 1, d_WF, d_WM, NULL, 0.0, 1.0, NULL, NULL, 0, NULL);
+                      d_lattice, d_field, d_work, stream, &o);
 }
 
 int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
@@ -1314,6 +1299,7 @@ int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, co
 {
     static const char what[] = "sift3d_amd_ffd_mi_refine_device";
     mi_state ms;
+    const ffd_refine_opts o = { .masked = 1, .d_WF = d_WF, .d_WM = d_WM, .ms = &ms };
     int rc;
     if (!mi_out)
         return refuse(what, "NULL argument");
@@ -1324,8 +1310,7 @@ int sift3d_amd_ffd_mi_refine_device(const float *d_F, int ox, int oy, int oz, co
     ms.sim.msd = ms.sim.ncc = ms.sim.mi = ms.sim.nmi = NAN;
     ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
     *mi_out = ms.sim;
-    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, &ms, 0.0, 1.0, NULL, NULL, 0, NULL);
+    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, &o);
     *mi_out = ms.sim;
     return rc;
 }
@@ -1367,6 +1352,7 @@ int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int 
                                           double jacobian, sift3d_amd_ffd_penalty *penalty)
 {
     static const char what[] = "sift3d_amd_ffd_refine_jacobian_device";
+    ffd_refine_opts o;
     mi_state ms;
     double ref = 1.0;
     int rc;
@@ -1384,8 +1370,9 @@ int sift3d_amd_ffd_refine_jacobian_device(const float *d_F, int ox, int oy, int 
     ms.sim.entropy_fixed = ms.sim.entropy_moving = ms.sim.entropy_joint = NAN;
     if (mi_out)
         *mi_out = ms.sim;
-    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty, NULL, 0, NULL);
+    o = (ffd_refine_opts){ .masked = 1, .d_WF = d_WF, .d_WM = d_WM, .ms = bins != 0 ? &ms : NULL,
+                           .jacobian = jacobian, .ref = ref, .penalty = penalty };
+    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, params, result, d_lattice, d_field, d_work, stream, &o);
     if (mi_out)
         *mi_out = ms.sim;
     return rc;
@@ -1420,6 +1407,7 @@ int sift3d_amd_ffd_refine_landmarks_device(const float *d_F, int ox, int oy, int
     static const char what[] = "sift3d_amd_ffd_refine_landmarks_device";
     ffd_lm_host h = { P, Q, w, m, landmark_weight, landmarks_out, 1.0, NULL, NULL, NULL, NULL };
     sift3d_amd_ffd_refine_params prm;
+    ffd_refine_opts o;
     mi_state ms;
     double ref = 1.0;
     int rc;
@@ -1453,8 +1441,9 @@ int sift3d_amd_ffd_refine_landmarks_device(const float *d_F, int ox, int oy, int
                                                 sift3d_amd_ffd_lattice_dim(oy, prm.spacing[1]) - 3,
                                                 sift3d_amd_ffd_lattice_dim(oz, prm.spacing[2]) - 3)))
         return SIFT3D_FAILURE;
-    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, &prm, result, d_lattice, d_field, d_work, stream, 1,
-                    d_WF, d_WM, bins != 0 ? &ms : NULL, jacobian, ref, penalty, NULL, 0, &h);
+    o = (ffd_refine_opts){ .masked = 1, .d_WF = d_WF, .d_WM = d_WM, .ms = bins != 0 ? &ms : NULL,
+                           .jacobian = jacobian, .ref = ref, .penalty = penalty, .lmh = &h };
+    rc = ffd_refine(what, d_F, ox, oy, oz, d_M, nx, ny, nz, A_in, &prm, result, d_lattice, d_field, d_work, stream, &o);
     free(h.rows);                                            /* every copy from it was staged when its call returned */
     if (mi_out)
         *mi_out = ms.sim;
@@ -1483,6 +1472,7 @@ int sift3d_amd_ffd_refine_channels_device(const sift3d_amd_ffd_level *level, int
                                           sift3d_amd_ffd_penalty *penalty)
 {
     static const char what[] = "sift3d_amd_ffd_refine_channels_device";
+    ffd_refine_opts o;
     sift3d_amd_ffd_refine_params prm;
     double ref = 1.0;
     size_t work_bytes;
@@ -1535,7 +1525,8 @@ int sift3d_amd_ffd_refine_channels_device(const sift3d_amd_ffd_level *level, int
                 return refuse(what, ALIASED);
         }
     }
+    o = (ffd_refine_opts){ .masked = 1, .d_WF = level->d_WF, .d_WM = level->d_WM, .jacobian = jacobian, .ref = ref,
+                           .penalty = penalty, .src = level, .nc = nc };
     return ffd_refine(what, level->d_F, level->ox, level->oy, level->oz, level->d_M, level->nx, level->ny, level->nz,
-                      A_in, &prm, result, d_lattice, d_field, d_work, stream, 1, level->d_WF, level->d_WM, NULL,
-                      jacobian, ref, penalty, level, nc, NULL);
+                      A_in, &prm, result, d_lattice, d_field, d_work, stream, &o);
 }

@@ -26,15 +26,7 @@
 //     finish_reduce.
 #include "sift3d_resample.h"
 #include "sift3d_parzen.h"
-#include "sift3d_ffd_jac.h"
-#include "sift3d_ffd_landmarks.h"
-
-// sift3d_ffd_landmarks.hip
-extern "C" int sift3d_ffd_landmarks_launch(const char *fn, const float *d_lat, int gx, int gy, int gz, int dx, int dy,
-                                           int dz, const sift3d_ffd_lm *lm, int adjoint, double *d_r, void *stream);
-// sift3d_jacobian_penalty.hip
-extern "C" int sift3d_jacobian_penalty_launch(const char *fn, const float *d_field, int ox, int oy, int oz, double ref,
-                                              double *d_rec, double *d_S, double *d_work, void *stream);
+#include "sift3d_ffd_eval.h"
 
 namespace {
 
@@ -539,8 +531,12 @@ __global__ __launch_bounds__(256) void k_ffd_bend_grad(const FfdBendArgs s)
     }
 }
 
-// grad = (float)((scale / n) * Gc + bending * dR), and the largest |grad| (as stored) into one partial slot per
-// workgroup.  scale: 2.0 for the MSD (Gc / n is half its derivative), 1.0 for the mutual information.
+// grad = (float)(b) and the largest |grad| (as stored) into one partial slot per workgroup, with
+//   b = (scale / n) * Gc + bending * dR; scale: 2.0 for the MSD (Gc / n is half its derivative), 1.0 for the MI;
+//   JAC (header, "Jacobian penalty"): b = b + jn * GJ, jn = jacobian / N made on the host;
+//   LM (header, "FFD landmarks"): b = b + (lk / Omega) * GL, lk = lambda * (2 * 4^l) made on the host and Omega read
+//   from the landmark record; Omega == 0 adds no term.
+// The terms are added in this order, each product rounded before its sum.
 struct FfdCombineArgs {
     const double *rec;                           // rec[0] = n as uint64
     const double *Gc, *dR;
@@ -548,61 +544,25 @@ struct FfdCombineArgs {
     double *part;
     double bending, scale;
     size_t total;
+    const double *GJ;                            // JAC only
+    double jn;
+    const double *GL, *lrec;                     // LM only
+    double lk;
 };
 
+template <bool JAC, bool LM>
 __global__ __launch_bounds__(256) void k_ffd_combine(const FfdCombineArgs s)
 {
     __shared__ double slot[4];
     const double n = (double)reinterpret_cast<const unsigned long long *>(s.rec)[0];
     const double two_n = s.scale / n;
-    double mx = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.total; i += (size_t)gridDim.x * 256) {
-        const float g = (float)(two_n * s.Gc[i] + s.bending * s.dR[i]);
-        s.grad[i] = g;
-        mx = fmax(mx, (double)fabsf(g));
-    }
-    const double r = workgroup_reduce<Max>(mx, slot);
-    if (threadIdx.x == 0)
-        s.part[blockIdx.x] = r;
-}
-
-// k_ffd_combine with the Jacobian penalty's term (header, "Jacobian penalty"): grad = (float)(((scale / n) * Gc +
-// bending * dR) + jn * GJ), jn = jacobian / N made on the host.  A kernel of its own: the evaluations without the
-// penalty launch k_ffd_combine as before.
-__global__ __launch_bounds__(256) void k_ffd_combine_jac(const FfdCombineArgs s, const double *GJ, double jn)
-{
-    __shared__ double slot[4];
-    const double n = (double)reinterpret_cast<const unsigned long long *>(s.rec)[0];
-    const double two_n = s.scale / n;
-    double mx = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.total; i += (size_t)gridDim.x * 256) {
-        const float g = (float)((two_n * s.Gc[i] + s.bending * s.dR[i]) + jn * GJ[i]);
-        s.grad[i] = g;
-        mx = fmax(mx, (double)fabsf(g));
-    }
-    const double r = workgroup_reduce<Max>(mx, slot);
-    if (threadIdx.x == 0)
-        s.part[blockIdx.x] = r;
-}
-
-// The combine with the landmark term (header, "FFD landmarks"): grad = (float)(base + (lk / Omega) * GL), base being
-// k_ffd_combine's expression (JAC: k_ffd_combine_jac's), lk = lambda * (2 * 4^l) made on the host and Omega read from
-// the landmark record; Omega == 0 adds no term.  A kernel of its own: the evaluations without landmarks launch
-// k_ffd_combine or k_ffd_combine_jac as before.
-template <bool JAC>
-__global__ __launch_bounds__(256) void k_ffd_combine_lm(const FfdCombineArgs s, const double *GJ, double jn,
-                                                        const double *GL, const double *lrec, double lk)
-{
-    __shared__ double slot[4];
-    const double n = (double)reinterpret_cast<const unsigned long long *>(s.rec)[0];
-    const double two_n = s.scale / n;
-    const double omega = lrec[2], f = lk / omega;
+    const double omega = LM ? s.lrec[2] : 0.0, f = s.lk / omega;             // LM only
     double mx = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.total; i += (size_t)gridDim.x * 256) {
         double b = two_n * s.Gc[i] + s.bending * s.dR[i];
         if (JAC)
-            b = b + jn * GJ[i];
-        const float g = (float)(omega == 0.0 ? b : b + f * GL[i]);
+            b = b + s.jn * s.GJ[i];
+        const float g = (float)(!LM || omega == 0.0 ? b : b + f * s.GL[i]);
         s.grad[i] = g;
         mx = fmax(mx, (double)fabsf(g));
     }
@@ -690,15 +650,6 @@ extern "C" int sift3d_ffd_field_launch(const char *fn, const float *d_lat, int g
     return SIFT3D_SUCCESS;
 }
 
-// The parts of an evaluation, in the order they run.  The MSD entries run them all (the bending entry all but the image
-// term); the MI driver runs FFD_BEND_VALUE per evaluation and the other three only where a step starts.
-// FFD_JAC_VALUE, FFD_JAC_GRAD (with a penalty only; one of the two): the penalty's record from the field, alone or with S
-// and its adjoint GJ.  They run after the image term, whose force buffer S takes over once Gc is formed.
-// FFD_LM_VALUE, FFD_LM_GRAD (with landmarks only; one of the two): the landmark record from the lattice, alone or with
-// the adjoint GL.
-enum { FFD_IMAGE = 1, FFD_BEND_VALUE = 2, FFD_BEND_GRAD = 4, FFD_COMBINE = 8, FFD_ALL = 15, FFD_JAC_VALUE = 16,
-       FFD_JAC_GRAD = 32, FFD_LM_VALUE = 64, FFD_LM_GRAD = 128 };
-
 // the adjoint of the spline on src [3][oz][oy][ox] -> dst [3][gz][gy][gx]: z, y, x
 static int ffd_adjoint_passes(const double *src, double *t1, double *t2, double *dst, const float *d_w, int ox, int oy,
                               int oz, int gx, int gy, int gz, int dx, int dy, int dz, hipStream_t st)
@@ -714,51 +665,44 @@ static int ffd_adjoint_passes(const double *src, double *t1, double *t2, double 
     return SIFT3D_SUCCESS;
 }
 
-// d_rec: {uint64 n; double S_ee, R, gmax} then Gc and dR, [3][gz][gy][gx] doubles each.  d_work: partial slots
-// [2][FFD_GRID] doubles, then the force [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox], D [18][N] doubles.
-// d_WF, d_WM: the masks or NULL; with both NULL the unmasked force kernels run.  FFD_BEND_GRAD reads the D that the
-// last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.  mi: what the MI
-// force needs beside the MSD force's arguments (NULL: the MSD).  jac: the penalty's buffers (NULL: none); the combine
-// takes its term when jac->weight > 0.  nc: 0 from the single-channel entries, which launch k_ffd_force or
-// k_ffd_mi_force as before; >= 1: d_F and d_M are stacks of nc channels and k_ffd_force_channels runs (mi == NULL).
-// lm: the landmark term's buffers (NULL: none); the combine takes its term when lm->weight > 0.
-static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *mi, const sift3d_ffd_jac *jac,
-                              const sift3d_ffd_lm *lm, int nc,
-                              const float *d_F, int ox, int oy,
-                              int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
-                              const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
-                              const double *stencils, double bending, double *d_rec, float *d_grad, double *d_work,
-                              void *stream, const float *d_WF, const float *d_WM)
+// The parts `parts` (sift3d_ffd_eval.h) of the evaluation e.  e->d_work: partial slots [2][FFD_GRID] doubles, then the
+// force [3][oz][oy][ox], t1 [3][gz][oy][ox], t2 [3][gz][gy][ox], D [18][N] doubles.  FFD_BEND_GRAD reads the D that the
+// last FFD_BEND_VALUE on this d_work left, FFD_COMBINE the n that the last FFD_IMAGE left in d_rec.
+extern "C" int sift3d_ffd_evaluate_launch(const char *fn, unsigned parts, const sift3d_ffd_eval *e)
 {
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)e->stream;
+    const sift3d_ffd_jac *jac = e->jac;
+    const sift3d_ffd_lm *lm = e->lm;
+    const int ox = e->ox, oy = e->oy, oz = e->oz, gx = e->gx, gy = e->gy, gz = e->gz;
     const size_t vox = (size_t)ox * oy * oz, cvox = (size_t)gx * gy * gz;
     const size_t N = (size_t)(gx - 2) * (gy - 2) * (gz - 2);
-    double *part = d_work, *force = part + 2 * FFD_GRID, *t1 = force + 3 * vox;
+    double *part = e->d_work, *force = part + 2 * FFD_GRID, *t1 = force + 3 * vox;
     double *t2 = t1 + 3 * (size_t)gz * oy * ox, *D = t2 + 3 * (size_t)gz * gy * ox;
-    double *Gc = d_rec + 4, *dR = Gc + 3 * cvox;
+    double *d_rec = e->d_rec, *Gc = d_rec + 4, *dR = Gc + 3 * cvox;
     if (parts & FFD_IMAGE) {
         FfdMiForceArgs fm;
         FfdForceArgs &f = fm.f;
-        if (!grid_args(f.g, d_M, nx, ny, nz, nullptr, ox, oy, oz, 0.0f))
+        if (!grid_args(f.g, e->d_M, e->nx, e->ny, e->nz, nullptr, ox, oy, oz, 0.0f))
             return launch_fail(fn, "grid too large");
-        f.F = d_F;
-        f.field = d_field;
+        f.F = e->d_F;
+        f.field = e->d_field;
         f.force = force;
         f.part = part;
         const unsigned grid = reduce_grid(f.g.ntiles);
-        f.w = MaskArgs{d_WF, d_WM};
-        const bool masked = d_WF || d_WM;
-        if (mi) {
-            fm.z = *mi;
-            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_mi_force, nx, masked), dim3(grid), dim3(256),
-                               (size_t)mi->bins * mi->bins * sizeof(double), st, fm);
-        } else if (nc >= 1) {
+        f.w = MaskArgs{e->d_WF, e->d_WM};
+        const bool masked = e->d_WF || e->d_WM;
+        if (e->mi) {
+            const sift3d_ffd_mi &m = *e->mi;
+            fm.z = parzen_args(m.bins, m.lo_f, m.s_f, m.lo_m, m.hi_m, m.d_W);
+            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_mi_force, e->nx, masked), dim3(grid), dim3(256),
+                               (size_t)m.bins * m.bins * sizeof(double), st, fm);
+        } else if (e->nc >= 1) {
             FfdChannelsArgs fc;
             fc.f = f;
-            fc.nc = nc;
-            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force_channels, nx, masked), dim3(grid), dim3(256), 0, st, fc);
+            fc.nc = e->nc;
+            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force_channels, e->nx, masked), dim3(grid), dim3(256), 0, st, fc);
         } else {
-            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force, nx, masked), dim3(grid), dim3(256), 0, st, f);
+            hipLaunchKernelGGL(PICK_LINEAR_MASKED(k_ffd_force, e->nx, masked), dim3(grid), dim3(256), 0, st, f);
         }
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish_count, dim3(1), dim3(256), 0, st, (const unsigned long long *)part + FFD_GRID, grid,
@@ -766,24 +710,26 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish<Add>, dim3(1), dim3(256), 0, st, (const double *)part, grid, d_rec + 1, 1.0);
         LAUNCH_CHECK();
-        if (ffd_adjoint_passes(force, t1, t2, Gc, d_w, ox, oy, oz, gx, gy, gz, dx, dy, dz, st))
+        if (ffd_adjoint_passes(force, t1, t2, Gc, e->d_w, ox, oy, oz, gx, gy, gz, e->dx, e->dy, e->dz, st))
             return SIFT3D_FAILURE;
     }
     if (jac && (parts & (FFD_JAC_VALUE | FFD_JAC_GRAD))) {
         const bool with_grad = parts & FFD_JAC_GRAD;
-        if (sift3d_jacobian_penalty_launch(fn, d_field, ox, oy, oz, jac->ref, jac->d_rec, with_grad ? force : nullptr,
-                                           jac->d_work, stream) ||
-            (with_grad && ffd_adjoint_passes(force, t1, t2, jac->d_GJ, d_w, ox, oy, oz, gx, gy, gz, dx, dy, dz, st)))
+        if (sift3d_jacobian_penalty_launch(fn, e->d_field, ox, oy, oz, jac->ref, jac->d_rec, with_grad ? force : nullptr,
+                                           jac->d_work, e->stream) ||
+            (with_grad &&
+             ffd_adjoint_passes(force, t1, t2, jac->d_GJ, e->d_w, ox, oy, oz, gx, gy, gz, e->dx, e->dy, e->dz, st)))
             return SIFT3D_FAILURE;
     }
     if (lm && (parts & (FFD_LM_VALUE | FFD_LM_GRAD)) &&
-        sift3d_ffd_landmarks_launch(fn, d_lat, gx, gy, gz, dx, dy, dz, lm, (parts & FFD_LM_GRAD) != 0, nullptr, stream))
+        sift3d_ffd_landmarks_launch(fn, e->d_lat, gx, gy, gz, e->dx, e->dy, e->dz, lm, (parts & FFD_LM_GRAD) != 0, nullptr,
+                                    e->stream))
         return SIFT3D_FAILURE;
     // the bending energy and its gradient
     FfdBendArgs b;
     for (int i = 0; i < 27; i++)
-        (&b.st[0][0][0])[i] = stencils[i];
-    b.c = d_lat;
+        (&b.st[0][0][0])[i] = e->stencils[i];
+    b.c = e->d_lat;
     b.D = D;
     b.part = part;
     b.dR = dR;
@@ -801,133 +747,20 @@ static int ffd_evaluate_parts(const char *fn, unsigned parts, const ParzenArgs *
         LAUNCH_CHECK();
     }
     if (parts & FFD_COMBINE) {
-        const FfdCombineArgs c = {d_rec, Gc, dR, d_grad, part, bending, mi ? 1.0 : 2.0, 3 * cvox};
+        const bool with_jac = jac && jac->weight > 0.0, with_lm = lm && lm->weight > 0.0;
+        const FfdCombineArgs c = {d_rec, Gc, dR, e->d_grad, part, e->bending, e->mi ? 1.0 : 2.0, 3 * cvox,
+                                  with_jac ? jac->d_GJ : nullptr, with_jac ? jac->weight / (double)vox : 0.0,
+                                  with_lm ? lm->d_GL : nullptr, with_lm ? lm->d_rec : nullptr,
+                                  with_lm ? lm->weight * lm->scale : 0.0};
         const unsigned cgrid = flat_grid(3 * cvox, FFD_GRID);
-        const bool with_jac = jac && jac->weight > 0.0;
-        if (lm && lm->weight > 0.0) {
-            void (*k)(const FfdCombineArgs, const double *, double, const double *, const double *, double) =
-                with_jac ? k_ffd_combine_lm<true> : k_ffd_combine_lm<false>;
-            hipLaunchKernelGGL(k, dim3(cgrid), dim3(256), 0, st, c, with_jac ? (const double *)jac->d_GJ : nullptr,
-                               with_jac ? jac->weight / (double)vox : 0.0, (const double *)lm->d_GL,
-                               (const double *)lm->d_rec, lm->weight * lm->scale);
-        } else if (with_jac)
-            hipLaunchKernelGGL(k_ffd_combine_jac, dim3(cgrid), dim3(256), 0, st, c, (const double *)jac->d_GJ,
-                               jac->weight / (double)vox);
-        else
-            hipLaunchKernelGGL(k_ffd_combine, dim3(cgrid), dim3(256), 0, st, c);
+        void (*k)(const FfdCombineArgs) = with_lm ? (with_jac ? k_ffd_combine<true, true> : k_ffd_combine<false, true>)
+                                                  : (with_jac ? k_ffd_combine<true, false> : k_ffd_combine<false, false>);
+        hipLaunchKernelGGL(k, dim3(cgrid), dim3(256), 0, st, c);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ffd_finish<Max>, dim3(1), dim3(256), 0, st, (const double *)part, cgrid, d_rec + 3, 1.0);
         LAUNCH_CHECK();
     }
     return SIFT3D_SUCCESS;
-}
-
-// the penalty's parts of an evaluation that forms a gradient, or of one that does not
-static unsigned ffd_jac_parts(const sift3d_ffd_jac *jac, bool gradient)
-{
-    return !jac ? 0u : gradient && jac->weight > 0.0 ? FFD_JAC_GRAD : FFD_JAC_VALUE;
-}
-
-// the landmark term's parts, as the penalty's
-static unsigned ffd_lm_parts(const sift3d_ffd_lm *lm, bool gradient)
-{
-    return !lm ? 0u : gradient && lm->weight > 0.0 ? FFD_LM_GRAD : FFD_LM_VALUE;
-}
-
-// The MSD evaluation; d_F == NULL: the bending entry, no image term and no combined gradient.  jac: the Jacobian
-// penalty of the field, or NULL.  lm: the landmark term, or NULL.
-extern "C" int sift3d_ffd_evaluate_lm_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
-                                             const float *d_M, int nx, int ny, int nz, const float *d_field,
-                                             const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                                             const float *d_w, const double *stencils, double bending, double *d_rec,
-                                             float *d_grad, double *d_work, void *stream, const float *d_WF,
-                                             const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm)
-{
-    return ffd_evaluate_parts(fn, d_F ? FFD_ALL | ffd_jac_parts(jac, true) | ffd_lm_parts(lm, true)
-                                      : FFD_BEND_VALUE | FFD_BEND_GRAD,
-                              nullptr, jac, lm, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy,
-                              dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
-}
-
-extern "C" int sift3d_ffd_evaluate_jac_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
-                                              const float *d_M, int nx, int ny, int nz, const float *d_field,
-                                              const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                                              const float *d_w, const double *stencils, double bending, double *d_rec,
-                                              float *d_grad, double *d_work, void *stream, const float *d_WF,
-                                              const float *d_WM, const sift3d_ffd_jac *jac)
-{
-    return sift3d_ffd_evaluate_lm_launch(fn, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
-                                         d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM, jac, nullptr);
-}
-
-// The evaluation of a stack of nc >= 1 channels (header, "Multi-channel free-form deformation"): the MSD evaluation
-// with k_ffd_force_channels in the place of k_ffd_force, every other pass unchanged.
-extern "C" int sift3d_ffd_evaluate_channels_launch(const char *fn, const float *d_F, int ox, int oy, int oz,
-                                                   const float *d_M, int nx, int ny, int nz, int nc,
-                                                   const float *d_field, const float *d_lat, int gx, int gy, int gz,
-                                                   int dx, int dy, int dz, const float *d_w, const double *stencils,
-                                                   double bending, double *d_rec, float *d_grad, double *d_work,
-                                                   void *stream, const float *d_WF, const float *d_WM,
-                                                   const sift3d_ffd_jac *jac)
-{
-    return ffd_evaluate_parts(fn, FFD_ALL | ffd_jac_parts(jac, true), nullptr, jac, nullptr, nc, d_F, ox, oy, oz, d_M, nx, ny, nz,
-                              d_field, d_lat, gx, gy, gz, dx, dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work,
-                              stream, d_WF, d_WM);
-}
-
-extern "C" int sift3d_ffd_evaluate_launch(const char *fn, const float *d_F, int ox, int oy, int oz, const float *d_M,
-                                          int nx, int ny, int nz, const float *d_field, const float *d_lat, int gx,
-                                          int gy, int gz, int dx, int dy, int dz, const float *d_w,
-                                          const double *stencils, double bending, double *d_rec, float *d_grad,
-                                          double *d_work, void *stream, const float *d_WF, const float *d_WM)
-{
-    return sift3d_ffd_evaluate_jac_launch(fn, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx, dy, dz,
-                                          d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM, nullptr);
-}
-
-// The MI evaluation.  value != 0: the bending value alone (what every evaluation of the MI driver needs on the device
-// beside the field and the histogram; the image arguments are not read).  gradient != 0: the force of psi from d_W, its
-// adjoint, the bending gradient from the D of the last value pass, and the combined gradient with the factor 1 / n.
-// jac: the Jacobian penalty of the field, or NULL: its record with either of value and gradient, S and GJ with gradient.
-// lm: the landmark term, or NULL: its record with either, GL with gradient.
-extern "C" int sift3d_ffd_mi_lm_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy,
-                                       int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
-                                       const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                                       const float *d_w, const double *stencils, double bending, int bins, float lo_f,
-                                       float s_f, float lo_m, float hi_m, const double *d_W, double *d_rec,
-                                       float *d_grad, double *d_work, void *stream, const float *d_WF,
-                                       const float *d_WM, const sift3d_ffd_jac *jac, const sift3d_ffd_lm *lm)
-{
-    const ParzenArgs mi = parzen_args(bins, lo_f, s_f, lo_m, hi_m, d_W);
-    const unsigned parts = (value ? FFD_BEND_VALUE : 0u) | (gradient ? FFD_IMAGE | FFD_BEND_GRAD | FFD_COMBINE : 0u) |
-                           ffd_jac_parts(jac, gradient != 0) | ffd_lm_parts(lm, gradient != 0);
-    return ffd_evaluate_parts(fn, parts, &mi, jac, lm, 0, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx,
-                              dy, dz, d_w, stencils, bending, d_rec, d_grad, d_work, stream, d_WF, d_WM);
-}
-
-extern "C" int sift3d_ffd_mi_jac_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy,
-                                        int oz, const float *d_M, int nx, int ny, int nz, const float *d_field,
-                                        const float *d_lat, int gx, int gy, int gz, int dx, int dy, int dz,
-                                        const float *d_w, const double *stencils, double bending, int bins, float lo_f,
-                                        float s_f, float lo_m, float hi_m, const double *d_W, double *d_rec,
-                                        float *d_grad, double *d_work, void *stream, const float *d_WF,
-                                        const float *d_WM, const sift3d_ffd_jac *jac)
-{
-    return sift3d_ffd_mi_lm_launch(fn, value, gradient, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz, dx,
-                                   dy, dz, d_w, stencils, bending, bins, lo_f, s_f, lo_m, hi_m, d_W, d_rec, d_grad, d_work,
-                                   stream, d_WF, d_WM, jac, nullptr);
-}
-
-extern "C" int sift3d_ffd_mi_launch(const char *fn, int value, int gradient, const float *d_F, int ox, int oy, int oz,
-                                    const float *d_M, int nx, int ny, int nz, const float *d_field, const float *d_lat,
-                                    int gx, int gy, int gz, int dx, int dy, int dz, const float *d_w,
-                                    const double *stencils, double bending, int bins, float lo_f, float s_f, float lo_m,
-                                    float hi_m, const double *d_W, double *d_rec, float *d_grad, double *d_work,
-                                    void *stream, const float *d_WF, const float *d_WM)
-{
-    return sift3d_ffd_mi_jac_launch(fn, value, gradient, d_F, ox, oy, oz, d_M, nx, ny, nz, d_field, d_lat, gx, gy, gz,
-                                    dx, dy, dz, d_w, stencils, bending, bins, lo_f, s_f, lo_m, hi_m, d_W, d_rec, d_grad,
-                                    d_work, stream, d_WF, d_WM, nullptr);
 }
 
 // The penalty of a field and its gradient over the lattice of that grid: the record, S and its adjoint GJ.  d_work: S

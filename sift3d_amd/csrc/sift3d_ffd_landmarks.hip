@@ -18,7 +18,7 @@
 //     and an add per channel, seven loads that the lanes of neighbouring controls share.  No atomics and nothing staged
 //     through LDS; the order is a function of the points and the lattice shape only.
 #include "sift3d_resample.h"
-#include "sift3d_ffd_landmarks.h"
+#include "sift3d_ffd_eval.h"
 
 namespace {
 

@@ -31,6 +31,7 @@
 //     three waves per SIMD) was not separated.  An MSD evaluation with the penalty is 1.94 x one without (14.3 against
 //     7.4 ms, HIP events), of which k_jp_grad is 3.1 ms, the value pass 1.8 ms and the second adjoint 2.0 ms.
 #include "sift3d_resample.h"
+#include "sift3d_ffd_eval.h"
 
 namespace {
 

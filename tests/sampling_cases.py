@@ -89,7 +89,7 @@ def selection_key(family, c):
         return (family, linear_of("linear", nx), masked)
     if family == "mi":                                      # sift3d_affine_mi_normal_launch
         return (family, linear_of("linear", nx), masked)
-    if family == "ffd":                                     # sift3d_ffd.hip ffd_evaluate_parts()
+    if family == "ffd":                                     # sift3d_ffd.hip sift3d_ffd_evaluate_launch()
         return (family, linear_of("linear", nx), masked)
     raise KeyError(family)
 

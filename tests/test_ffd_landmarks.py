@@ -195,6 +195,51 @@ def test_gradient_bit_for_bit_from_the_device_sums(hip, k, jacobian):
             assert np.array_equal(old[1].cpu().numpy(), grad.cpu().numpy())
 
 
+def grid_cap_shape(hip):
+    """tests/test_ffd.py's grid-cap shape: more tiles than workgroups, a second, partial pass over them"""
+    G = hip.SIMILARITY_GRID
+    ty = int(np.ceil(np.sqrt(G + 1)))
+    tz = -(-(G + 1) // ty)
+    assert G < ty * tz < 2 * G
+    return (4 * (tz - 1) + 1, 4 * (ty - 1) + 1, 2), (2, 16, 16)
+
+
+# the two smallest grids; the grid cap of the image passes; a lattice of more elements than the combine's 256 lanes times
+# its SIMILARITY_GRID workgroups, so that its lanes take a second element: without the landmark term and with it
+COMBINE_CASES = [(2, 0.0), (0, 0.0), ("grid cap", 0.0), ("stride", 0.0), ("stride", 0.37)]
+
+
+@pytest.mark.parametrize("case, lam", COMBINE_CASES)
+def test_penalty_gradient_bit_for_bit_from_the_device_sums(hip, case, lam):
+    """the combine with the penalty's term and landmarks of weight 0 (their record is made, no term is added), and on the
+    large lattice with both terms: d_grad = (float)(((2 / n) * Gc + bending * dR) + (jacobian / N) * GJ [+ ((lambda * 2) /
+    Omega) * GL]) from the device's own sums, and gmax its largest magnitude"""
+    from tests.test_similarity import volumes
+    shape, spacing = grid_cap_shape(hip) if case == "grid cap" else ((56, 56, 56), (1, 1, 1)) if case == "stride" \
+        else GRIDS[case]
+    seed = 90 + COMBINE_CASES.index((case, lam))
+    F, M = volumes(shape, (shape[0] + 1, shape[1] + 2, shape[2] + 1), seed)
+    c = random_lattice(shape, spacing, seed + 10, 0.75)
+    rng = np.random.default_rng(seed + 20)
+    P = rng.uniform(0.0, 1.0, (100, 3)) * (np.array(shape[::-1]) - 1.0)
+    Q = P + rng.uniform(-2.0, 2.0, (100, 3))
+    jacobian, bend, cvox = 0.3, 0.01, int(np.prod(c.shape[1:]))
+    assert (case == "stride") == (3 * cvox > 256 * hip.SIMILARITY_GRID)
+    rec, grad, fld, lm, jac = hip.ffd_evaluate_landmarks(dev(F), dev(M), dev(c), spacing, P, Q, None, lam, rotating(shape),
+                                                        bend, jacobian)
+    n, see, R, gmax, Gc, dR = hip.ffd_record(rec, c.shape)
+    counted, S, Om, rmax = hip.ffd_landmarks_record(lm)
+    GJ = jac.cpu().numpy()[4:4 + 3 * cvox].reshape(c.shape)
+    GL = lm.cpu().numpy()[4:4 + 3 * cvox].reshape(c.shape)
+    assert n > 0 and counted > 0 and Om > 0 and GJ.any() and GL.any() == (lam > 0)
+    g = ((2.0 / np.float64(n)) * Gc + bend * dR) + (jacobian / np.float64(F.size)) * GJ
+    if lam > 0:
+        g = g + ((lam * 2.0) / Om) * GL
+    g = g.astype(np.float32)
+    print("%s: n %d counted %d gmax %.9g |GJ| %.3g" % (case, n, counted, gmax, np.abs(GJ).max()))
+    assert np.array_equal(grad.cpu().numpy(), g) and gmax == float(np.abs(g).max()), (case, lam)
+
+
 # ---- the driver ------------------------------------------------------------------------------------------------------
 def trail_bytes(res):
     return C.string_at(C.addressof(res), 8 + 48 * res.evaluations)       # evaluations, stop and the entries run
