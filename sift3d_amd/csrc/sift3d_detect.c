@@ -233,21 +233,11 @@ static int host_threads(size_t n)
     return t;
 }
 
-/* scratch of the orientation kernels: sized by the level count and the candidate capacity */
+/* scratch of the orientation kernels: sized by the level count and the candidate capacity; its zeroing is
+ * complete before any stream's kernels use it */
 static int orient_scratch(sift3d_detector *d)
 {
-    const size_t need = sift3d_hip_orient_tab_bytes(d->num_octaves * d->ngl, d->cand_cap);
-    if (need > d->otab_bytes) {
-        sift3d_hip_free(d->d_otab);
-        d->otab_bytes = 0;
-        d->d_otab = sift3d_hip_malloc(need);
-        /* zeroed once: the tables carry a validity mark (they are kept between calls); complete before any
-         * stream's kernels use it */
-        if (!d->d_otab || sift3d_hip_memset(d->d_otab, 0, need, d->stream) || sift3d_hip_stream_sync(d->stream))
-            return SIFT3D_FAILURE;
-        d->otab_bytes = need;
-    }
-    return SIFT3D_SUCCESS;
+    return orient_tab_reserve(&d->d_otab, &d->otab_bytes, d->num_octaves * d->ngl, d->cand_cap, d->stream, 1);
 }
 
 /* Candidates first .. first + n - 1 (all of levels lv_lo .. lv_hi - 1) through the orientation kernels.  R and
@@ -998,15 +988,8 @@ enum { DESC_LV_MAX = 32 };     /* Gaussian levels per octave that order_keypoint
 /* the describe kernel's input list (page-locked), for num keypoints */
 static int ensure_kp_list(sift3d_detector *d, int num)
 {
-    if ((uint32_t)num > d->kp_cap) {
-        const uint32_t cap = (uint32_t)num + (uint32_t)num / 4 + 256;
-        sift3d_hip_host_free(d->h_kp);
-        d->kp_cap = 0;
-        d->h_kp = (sift3d_hip_kp *)sift3d_hip_host_alloc(sizeof(sift3d_hip_kp) * (size_t)cap);
-        if (!d->h_kp)
-            return SIFT3D_FAILURE;
-        d->kp_cap = cap;
-    }
+    if (describe_list_reserve(&d->h_kp, &d->kp_cap, (uint32_t)num))
+        return SIFT3D_FAILURE;
     if (d->ngl > DESC_LV_MAX) {
         ERR("sift3d_amd: at most %d Gaussian levels per octave are supported \n", DESC_LV_MAX);
         return SIFT3D_FAILURE;
@@ -1081,14 +1064,7 @@ static size_t order_keypoints(sift3d_detector *d, const sift3d_keypoint_store *k
         /* (implicit barrier) */
         for (q = lo; q < hi; q++) {
             const keypoint_t *k = kp->buf + q;
-            sift3d_hip_kp *r = d->h_kp + start[t][desc_bucket(d, k)]++;
-            memcpy(r->R, k->R, sizeof(r->R));
-            r->cx = (float)k->xd;                  /* sift.c:1474-1476 */
-            r->cy = (float)k->yd;
-            r->cz = (float)k->zd;
-            r->level = k->o * d->ngl + k->s + 1;
-            r->row1 = (uint32_t)q + 1u;
-            r->sd = k->sd;
+            describe_record(d->h_kp + start[t][desc_bucket(d, k)]++, k, d->ngl, q);
         }
     }
     *n_lattice = num - lattice_first;
@@ -1098,25 +1074,8 @@ static size_t order_keypoints(sift3d_detector *d, const sift3d_keypoint_store *k
 /* do_extract_descriptors, sift.c:1561-1596: the store sized for num descriptors of the detector's image */
 static int ensure_descriptor_store(const sift3d_detector *d, sift3d_descriptor_store *desc, size_t num)
 {
-    desc->nx = d->odims[0][0];
-    desc->ny = d->odims[0][1];
-    desc->nz = d->odims[0][2];
-    /* the store's histogram array is page-locked and device-visible */
-    if (!desc->pinned || num > desc->cap) {
-        const size_t cap = num + num / 8 + 64;
-        desc_store_release(desc);
-        desc->hist = (float *)sift3d_hip_host_alloc(sizeof(float) * DESC_NUMEL * cap);
-        desc->xyzsd = (double *)malloc(sizeof(double) * 4 * cap);
-        if (!desc->hist || !desc->xyzsd) {
-            desc->pinned = desc->hist != NULL;
-            desc_store_release(desc);
-            return SIFT3D_FAILURE;
-        }
-        desc->pinned = 1;
-        desc->cap = cap;
-    }
-    desc->num = num;
-    desc->d_num = 0;
+    if (desc_store_reserve(desc, num, d->odims[0][0], d->odims[0][1], d->odims[0][2]))
+        return SIFT3D_FAILURE;
     if (desc->keep_device && num > desc->d_cap) {
         sift3d_hip_free(desc->d_hist);
         desc->d_cap = 0;
@@ -1133,7 +1092,6 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
 {
     const int num = (int)kp->num;
     const double t_start = now_s();
-    int i;
     size_t n_exact, n_lattice;
     uint64_t rng;
 
@@ -1145,43 +1103,12 @@ int sift3d_extract_descriptors(sift3d_detector *const d, const sift3d_keypoint_s
     d->t_pending &= ~2;
     rng = range_start("sift3d: descriptors");
     sift3d_hip_event_record(d->ev[6], d->stream);
-    /* (the kernel reads the 64-byte record of a keypoint once, as its wave starts: straight from the
-     * page-locked host list -- no copy, no DMA set-up between the host loops and the launch) */
-    /* The kernel stores each histogram straight into the store's page-locked array (mapped
-     * into the device's address space): the 3 KB per keypoint trickle over PCIe while the other
-     * keypoints are still being computed, so there is no device staging buffer and no D2H
-     * copy after the kernel.  (A chunked kernel/copy pipeline measured slower: every chunk
-     * pays the kernel's long tail.) */
-    {
-        float *dev_view = (float *)sift3d_hip_host_device_ptr(desc->hist);
-        const sift3d_hip_kp *kp_view = (const sift3d_hip_kp *)sift3d_hip_host_device_ptr(d->h_kp);
-        const size_t need = sift3d_hip_describe_part_bytes((uint32_t)(num - (int)n_exact));
-        if (need > d->dpart_bytes) {
-            sift3d_hip_free(d->d_dpart);
-            d->dpart_bytes = 0;
-            d->d_dpart = sift3d_hip_malloc(need + need / 8);
-            if (!d->d_dpart)
-                return SIFT3D_FAILURE;
-            d->dpart_bytes = need + need / 8;
-        }
-        if (!dev_view || !kp_view ||
-            sift3d_hip_describe_lattice_a32(d->d_levels, d->num_octaves * d->ngl, kp_view, (uint32_t)num,
-                                            (uint32_t)n_exact, (uint32_t)n_lattice, dev_view,
-                                            desc->keep_device ? desc->d_hist : NULL, d->d_wlut,
-                                            need ? d->d_dpart : NULL, d->stream,
-                                            sift3d_hip_describe_addr32_records(d->h_levels, d->num_octaves * d->ngl,
-                                                                               d->h_kp, (uint32_t)num)))
-            return SIFT3D_FAILURE;
-    }
+    if (describe_enqueue(d->d_levels, d->h_levels, d->num_octaves * d->ngl, d->h_kp, (uint32_t)num,
+                         (uint32_t)n_exact, (uint32_t)n_lattice, desc, desc->keep_device ? desc->d_hist : NULL,
+                         d->d_wlut, &d->d_dpart, &d->dpart_bytes, d->stream))
+        return SIFT3D_FAILURE;
     sift3d_hip_event_record(d->ev[7], d->stream);
-    for (i = 0; i < num; i++) {
-        const keypoint_t *k = kp->buf + i;
-        const double f = ldexp(1.0, k->o);             /* sift.c:1459, 1530-1533 */
-        desc->xyzsd[4 * (size_t)i] = k->xd * f;
-        desc->xyzsd[4 * (size_t)i + 1] = k->yd * f;
-        desc->xyzsd[4 * (size_t)i + 2] = k->zd * f;
-        desc->xyzsd[4 * (size_t)i + 3] = k->sd;
-    }
+    desc_store_fill_xyzsd(desc, kp->buf, NULL, 0, (size_t)num);      /* (beside the kernel) */
     if (sift3d_hip_stream_sync(d->stream))
         return SIFT3D_FAILURE;
     range_stop(rng);

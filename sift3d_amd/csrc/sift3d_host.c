@@ -1426,6 +1426,128 @@ static void range_stop(uint64_t id)
         g_roctx.stop(id);
 }
 
+/* ------------------------------------------------------------------------ */
+/* what the single-GPU driver (sift3d_detect.c) and the Z-slab driver       */
+/* (sift3d_sharded.c) both do around the orientation and describe kernels   */
+/* ------------------------------------------------------------------------ */
+/* Scratch of the orientation kernels (sift3d_hip_orient_tab_bytes), grown for nlevels levels and cand_cap
+ * candidates.  Zeroed once, on `stream`: the tables carry a validity mark (they are kept between calls); sync: the
+ * zeroing has ended on return (for a caller whose kernels use the scratch on other streams, too). */
+static int orient_tab_reserve(void **d_otab, size_t *bytes, int nlevels, uint32_t cand_cap, void *stream, int sync)
+{
+    const size_t need = sift3d_hip_orient_tab_bytes(nlevels, cand_cap);
+    if (need <= *bytes)
+        return SIFT3D_SUCCESS;
+    sift3d_hip_free(*d_otab);
+    *bytes = 0;
+    *d_otab = sift3d_hip_malloc(need);
+    if (!*d_otab || sift3d_hip_memset(*d_otab, 0, need, stream) || (sync && sift3d_hip_stream_sync(stream)))
+        return SIFT3D_FAILURE;
+    *bytes = need;
+    return SIFT3D_SUCCESS;
+}
+
+/* do_extract_descriptors, sift.c:1561-1596: the store sized for num descriptors of an nx x ny x nz image.  Its
+ * histogram array is page-locked and device-visible; the rows are about to be rewritten, so a device copy kept
+ * by an earlier call is stale. */
+static int desc_store_reserve(sift3d_descriptor_store *desc, size_t num, int nx, int ny, int nz)
+{
+    desc->nx = nx; desc->ny = ny; desc->nz = nz;
+    if (!desc->pinned || num > desc->cap) {
+        const size_t cap = num + num / 8 + 64;
+        desc_store_release(desc);
+        desc->hist = (float *)sift3d_hip_host_alloc(sizeof(float) * DESC_NUMEL * cap);
+        desc->xyzsd = (double *)malloc(sizeof(double) * 4 * cap);
+        if (!desc->hist || !desc->xyzsd) {
+            desc->pinned = desc->hist != NULL;
+            desc_store_release(desc);
+            return SIFT3D_FAILURE;
+        }
+        desc->pinned = 1;
+        desc->cap = cap;
+    }
+    desc->num = num;
+    desc->d_num = 0;
+    return SIFT3D_SUCCESS;
+}
+
+/* rows [lo, hi) of the store's coordinates, in octave-0 voxels (sift.c:1459, 1530-1533): row q is keypoint idx[q]
+ * of the list (idx = NULL: keypoint q) */
+static void desc_store_fill_xyzsd(sift3d_descriptor_store *desc, const keypoint_t *buf, const int *idx, size_t lo,
+                                  size_t hi)
+{
+    size_t q;
+    for (q = lo; q < hi; q++) {
+        const keypoint_t *k = buf + (idx ? (size_t)idx[q] : q);
+        const double f = ldexp(1.0, k->o);
+        desc->xyzsd[4 * q] = k->xd * f;
+        desc->xyzsd[4 * q + 1] = k->yd * f;
+        desc->xyzsd[4 * q + 2] = k->zd * f;
+        desc->xyzsd[4 * q + 3] = k->sd;
+    }
+}
+
+/* the describe kernel's record of keypoint k (levels of ngl Gaussian levels per octave), its histogram to `row` */
+static inline void describe_record(sift3d_hip_kp *r, const keypoint_t *k, int ngl, size_t row)
+{
+    memcpy(r->R, k->R, sizeof(r->R));
+    r->cx = (float)k->xd; r->cy = (float)k->yd; r->cz = (float)k->zd;   /* sift.c:1474-1476 */
+    r->level = k->o * ngl + k->s + 1;
+    r->row1 = (uint32_t)row + 1u;
+    r->sd = k->sd;
+}
+
+/* the describe kernel's input list (page-locked: the kernel reads it in place), for num keypoints */
+static int describe_list_reserve(sift3d_hip_kp **h_kp, uint32_t *kp_cap, uint32_t num)
+{
+    if (num > *kp_cap) {
+        const uint32_t cap = num + num / 4 + 256;
+        sift3d_hip_host_free(*h_kp);
+        *kp_cap = 0;
+        *h_kp = (sift3d_hip_kp *)sift3d_hip_host_alloc(sizeof(sift3d_hip_kp) * (size_t)cap);
+        if (!*h_kp)
+            return SIFT3D_FAILURE;
+        *kp_cap = cap;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* the scratch of the describe kernel's split windows, for the n_fast keypoints of the fast kernel */
+static int describe_parts_reserve(void **d_dpart, size_t *bytes, uint32_t n_fast)
+{
+    const size_t need = sift3d_hip_describe_part_bytes(n_fast);
+    if (need > *bytes) {
+        sift3d_hip_free(*d_dpart);
+        *bytes = 0;
+        *d_dpart = sift3d_hip_malloc(need + need / 8);
+        if (!*d_dpart)
+            return SIFT3D_FAILURE;
+        *bytes = need + need / 8;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* The launch: n records of h_kp (the n_exact of the reference-order kernel first, the n_lattice of the lattice
+ * variant last), histograms into the store.  The kernel reads the 64-byte record of a keypoint once, as its wave
+ * starts, straight from the page-locked list, and stores each histogram straight into the store's page-locked
+ * array (both mapped into the device's address space): the 3 KB per keypoint trickle over PCIe while the other
+ * keypoints are still being computed, so there is no staging buffer and no copy on either side of the kernel.  (A
+ * chunked kernel/copy pipeline measured slower: every chunk pays the kernel's long tail.)  d_rows: a second copy
+ * of the rows in device memory, or NULL. */
+static int describe_enqueue(const sift3d_hip_level *d_levels, const sift3d_hip_level *h_levels, int nlevels,
+                            const sift3d_hip_kp *h_kp, uint32_t n, uint32_t n_exact, uint32_t n_lattice,
+                            sift3d_descriptor_store *desc, float *d_rows, float *d_wlut, void **d_dpart,
+                            size_t *dpart_bytes, void *stream)
+{
+    float *dev_view = (float *)sift3d_hip_host_device_ptr(desc->hist);
+    const sift3d_hip_kp *kp_view = (const sift3d_hip_kp *)sift3d_hip_host_device_ptr((void *)h_kp);
+    if (describe_parts_reserve(d_dpart, dpart_bytes, n - n_exact) || !dev_view || !kp_view)
+        return SIFT3D_FAILURE;
+    return sift3d_hip_describe_lattice_a32(d_levels, nlevels, kp_view, n, n_exact, n_lattice, dev_view, d_rows,
+                                           d_wlut, n - n_exact ? *d_dpart : NULL, stream,
+                                           sift3d_hip_describe_addr32_records(h_levels, nlevels, h_kp, n));
+}
+
 /* the hot path: the detect and describe drivers (their statics are used by the files included below) */
 #include "sift3d_detect.c"
 

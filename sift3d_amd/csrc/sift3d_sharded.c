@@ -15,6 +15,10 @@
  *   gather    all-gather of the per-level candidate counts, the candidates' |DoG| values and the
  *             ORIENTED keypoints (rejected candidates never leave their rank).
  *
+ * The ORDER in which one detect call issues them is the invariant every rank keeps, whatever fails
+ * locally (SH_DO / SH_COMM below).  sift3d_amd_sharded_detect is the list of the stages that issue
+ * them; DESIGN.md section 5, "The exchanges of one detect call, in order", is the list itself.
+ *
  * Ranks are concatenated in slab order inside each (octave, level), which reproduces the
  * reference's global (o, s, z, y, x) order and its stale-strength quirk (sift.c:372-384), so the
  * result equals the single-GPU result bit for bit (tests/test_gpu_sharded.py).  Mirror rules
@@ -31,7 +35,7 @@
  * reference halves dimensions with integer division, imutil.c:1545-1547, so rows that are not
  * whole quads are a normal case).  Octaves the DoG-free extrema sweep does not cover store their
  * DoG levels and take sift3d_hip_extrema_mode, exactly as the single-GPU path does
- * (sift3d_host.c: detect_on_device).  tests/sharded_py.py is the same orchestration in Python on a
+ * (sift3d_detect.c: detect_on_device).  tests/sharded_py.py is the same orchestration in Python on a
  * pluggable compute backend: test infrastructure for the gloo runs on the CPU oracle. */
 
 #include <dlfcn.h>
@@ -48,11 +52,6 @@ typedef struct {
     int z0, z1;         /* owned (or, on replicated octaves, work-split) planes, global */
     int nz_glob;
 } sh_level;
-
-typedef struct {          /* an oriented keypoint as exchanged between ranks */
-    int32_t o, s, x, y, z;
-    float R[9];
-} sh_gkp;
 
 struct sift3d_amd_sharded {
     sift3d_amd_transport T;
@@ -72,28 +71,28 @@ struct sift3d_amd_sharded {
     int win_reach[SH_MAX_NGL];
     filter_t filt[SH_MAX_NGL];
     /* device state */
-    void *stream, *comm_stream, *ev_x, *ev_halo, *ev0, *ev1, *ev2, *ev3, *ev4;
-    void *oct_stream, *ev_fork, *ev_join;   /* extrema sweeps of octaves >= 1 beside octave 0's */
     /* The pyramid's three dependency chains, as in the single-GPU path (detect_on_device): [0] octave 0,
      * [1] the first levels of the octaves >= 1 (their down-sampling source included), [2] their last
      * levels, which nothing but their own DoG waits for.  A chain has its stream, its scratch volumes and
-     * its pair of events around the z-halo exchange (which always travels on comm_stream). */
+     * its pair of events around the z-halo exchange (which always travels on comm_stream).  The extrema
+     * sweeps of the octaves >= 1 run on chain 1's stream beside octave 0's. */
     struct sh_chain {
         void *stream;
         float *tmp_a, *tmp_b;
         void *ev_x, *ev_halo;
     } chain[3];
-    void *side_stream, *ev_oct[SH_MAX_OCT], *ev_join2, *ev_tr;
-    float *d_tmp2_a, *d_tmp2_b, *d_tmp3_a, *d_tmp3_b;
-    void *d_work2;                          /* their work areas, kept until the ordered emission */
+    void *stream;                    /* = chain[0].stream, the main stream: every collective but the halos */
+    void *comm_stream;
+    void *ev[5];                     /* the marks between the stages that t[] is read from (sh_end) */
+    void *ev_fork, *ev_join, *ev_join2, *ev_tr, *ev_oct[SH_MAX_OCT];
+    void *d_work2;                          /* work areas of the side sweeps, kept until the ordered emission */
     size_t work2_off[SH_MAX_OCT], work2_sz[SH_MAX_OCT], work2_bytes;
     sh_level G[SH_MAX_OCT][SH_MAX_NGL];
     float *D[SH_MAX_OCT][SH_MAX_NDL];   /* stored DoG levels (geometry of G[o][*]), where needed */
-    sh_level tmp_a, tmp_b, im;       /* scratch levels of octave 0 size (re-described per octave) */
-    float *d_tmp_a, *d_tmp_b, *d_im, *d_raw, *d_stage;
-    size_t tmp_elems, stage_elems;
+    float *d_im, *d_raw, *d_stage;
+    size_t stage_elems;
     int in_z0, in_z1;
-    float *d_scalars;                /* [0] input max, [1] candidate count, [8 + 5 o + k] dogmax */
+    float *d_scalars;                /* [0] input max, [1] candidate count, [8 + ndl o + k] dogmax */
     sift3d_hip_level h_levels[SH_MAX_OCT * SH_MAX_NGL], *d_levels;
     void *d_work;
     size_t work_bytes;
@@ -132,6 +131,60 @@ static double sh_scale(const sift3d_amd_sharded *S, int o, int s)
 }
 
 static size_t sh_plane(const sift3d_amd_sharded *S, int o) { return (size_t)S->dims[o][0] * S->dims[o][1]; }
+
+/* ---- what the stages ask of the driver's arrays (d_scalars: laid out as the struct says) ---- */
+static inline float *sh_dogmax_slot(const sift3d_amd_sharded *S, int o) { return S->d_scalars + 8 + S->ndl * o; }
+static inline uint32_t *sh_cand_counter(const sift3d_amd_sharded *S) { return (uint32_t *)(S->d_scalars + 1); }
+/* the capacity of the candidate arrays, or the one the next detect starts from */
+static inline uint32_t sh_cand_capacity(const sift3d_amd_sharded *S)
+{
+    return S->cand_cap ? S->cand_cap : S->cand_cap0 ? S->cand_cap0 : (1u << 18);
+}
+/* the planes [*lo, *hi) of octave o's level buffers that this rank owns (replicated octaves: all of them) */
+static inline void sh_owned(const sift3d_amd_sharded *S, int o, int *lo, int *hi)
+{
+    const sh_level *L = &S->G[o][0];
+    *lo = sh_sharded(S, o) ? L->z0 - L->off : 0;
+    *hi = sh_sharded(S, o) ? L->z1 - L->off : L->nloc;
+}
+/* the Gaussian levels of octave o from plane `first` of their buffers on */
+static inline void sh_level_ptrs(const sift3d_amd_sharded *S, int o, int first, const float **g)
+{
+    int s;
+    for (s = 0; s < S->ngl; s++)
+        g[s] = S->G[o][s].t + (size_t)first * sh_plane(S, o);
+}
+/* the extrema work area of octave o (side: the sweeps run side by side and those of the octaves >= 1 keep theirs
+ * between the two phases) */
+static inline void *sh_extrema_work(const sift3d_amd_sharded *S, int o, int side, size_t *bytes)
+{
+    *bytes = side && o > 0 ? S->work2_sz[o] : S->work_bytes;
+    return side && o > 0 ? (void *)((char *)S->d_work2 + S->work2_off[o]) : S->d_work;
+}
+/* The rank that owns keypoint k -- describes it, and sends its row in the descriptor gather: the one whose
+ * planes of octave k->o hold k->zd (bounds ascend; what lies outside the volume goes to the first or last rank).
+ * One rank: 0. */
+static inline int sh_owner(const sift3d_amd_sharded *S, const keypoint_t *k)
+{
+    int r = 0;
+    while (r < S->world - 1 && !(k->zd < (double)S->bounds[k->o][r + 1]))
+        r++;
+    return r;
+}
+/* the slabs zb[0 .. world] in which the first replicated octave t leaves the ranks' down-sampling; returns the
+ * planes of the largest (at least 1) */
+static int sh_transition_slabs(const sift3d_amd_sharded *S, int t, int *zb)
+{
+    const int mzg = S->dims[t][2];
+    int r, mxn = 1;
+    for (r = 0; r < S->world; r++)
+        zb[r] = (S->b0[r] >> t) < mzg ? (S->b0[r] >> t) : mzg;
+    zb[S->world] = mzg;
+    for (r = 0; r < S->world; r++)
+        if (zb[r + 1] - zb[r] > mxn)
+            mxn = zb[r + 1] - zb[r];
+    return mxn;
+}
 
 /* ---- geometry ------------------------------------------------------------------------------ */
 static int sh_geometry(sift3d_amd_sharded *S)
@@ -174,62 +227,177 @@ static int sh_geometry(sift3d_amd_sharded *S)
     return SIFT3D_SUCCESS;
 }
 
-static void sh_free_level(sh_level *L)
+/* ---- the driver's resources ------------------------------------------------------------------ */
+/* what every stream of the driver holds has ended */
+static int sh_sync_streams(const sift3d_amd_sharded *S)
 {
-    sift3d_hip_free(L->t);
-    L->t = NULL;
+    void *const st[4] = { S->stream, S->comm_stream, S->chain[1].stream, S->chain[2].stream };
+    int i, rc = SIFT3D_SUCCESS;
+    for (i = 0; i < 4; i++)
+        if (st[i] && sift3d_hip_stream_sync(st[i]))
+            rc = SIFT3D_FAILURE;
+    return rc;
+}
+
+static void sh_free_cand(sift3d_amd_sharded *S)
+{
+    sift3d_hip_free(S->d_cand); sift3d_hip_free(S->d_R); sift3d_hip_free(S->d_keep);
+    S->d_cand = NULL; S->d_R = NULL; S->d_keep = NULL;
+    S->cand_cap = 0;
 }
 
 void sift3d_amd_sharded_free(sift3d_amd_sharded *S)
 {
-    int o, s;
+    int o, s, i;
     if (!S)
         return;
-    if (S->stream)
-        sift3d_hip_stream_sync(S->stream);
-    if (S->comm_stream)
-        sift3d_hip_stream_sync(S->comm_stream);
-    if (S->oct_stream)
-        sift3d_hip_stream_sync(S->oct_stream);
-    if (S->side_stream)
-        sift3d_hip_stream_sync(S->side_stream);
+    sh_sync_streams(S);
     for (o = 0; o < SH_MAX_OCT; o++) {
         for (s = 0; s < SH_MAX_NGL; s++)
-            sh_free_level(&S->G[o][s]);
+            sift3d_hip_free(S->G[o][s].t);
         for (s = 0; s < SH_MAX_NDL; s++)
             sift3d_hip_free(S->D[o][s]);
+        sift3d_hip_event_destroy(S->ev_oct[o]);
     }
     for (s = 0; s < SH_MAX_NGL; s++)
         free(S->filt[s].taps);
-    sift3d_hip_free(S->d_tmp_a); sift3d_hip_free(S->d_tmp_b); sift3d_hip_free(S->d_im);
-    sift3d_hip_free(S->d_tmp2_a); sift3d_hip_free(S->d_tmp2_b); sift3d_hip_free(S->d_tmp3_a);
-    sift3d_hip_free(S->d_tmp3_b);
-    sift3d_hip_free(S->d_raw); sift3d_hip_free(S->d_stage); sift3d_hip_free(S->d_scalars);
-    sift3d_hip_free(S->d_levels); sift3d_hip_free(S->d_work); sift3d_hip_free(S->d_work2);
-    sift3d_hip_free(S->d_cand);
-    sift3d_hip_free(S->d_R); sift3d_hip_free(S->d_keep); sift3d_hip_free(S->d_xchg);
-    sift3d_hip_free(S->d_wlut); sift3d_hip_free(S->d_otab); sift3d_hip_free(S->d_dpart);
+    sh_free_cand(S);
+    sift3d_hip_free(S->d_im); sift3d_hip_free(S->d_raw); sift3d_hip_free(S->d_stage); sift3d_hip_free(S->d_scalars);
+    sift3d_hip_free(S->d_levels); sift3d_hip_free(S->d_work); sift3d_hip_free(S->d_work2); sift3d_hip_free(S->d_xchg);
+    sift3d_hip_free(S->d_wlut); sift3d_hip_free(S->d_otab); sift3d_hip_free(S->d_dpart); sift3d_hip_free(S->d_cnt);
+    sift3d_hip_free(S->d_tab); sift3d_hip_free(S->d_out); sift3d_hip_free(S->d_pack); sift3d_hip_free(S->d_gath);
     sift3d_hip_host_free(S->h_xchg); sift3d_hip_host_free(S->h_kp);
-    sift3d_hip_free(S->d_cnt); sift3d_hip_free(S->d_tab); sift3d_hip_free(S->d_out); sift3d_hip_free(S->d_pack);
-    sift3d_hip_free(S->d_gath);
     sift3d_hip_host_free(S->h_cnt); sift3d_hip_host_free(S->h_tab);
-    sift3d_hip_event_destroy(S->ev_x); sift3d_hip_event_destroy(S->ev_halo);
-    sift3d_hip_event_destroy(S->ev0); sift3d_hip_event_destroy(S->ev1);
-    sift3d_hip_event_destroy(S->ev2); sift3d_hip_event_destroy(S->ev3); sift3d_hip_event_destroy(S->ev4);
     sift3d_hip_event_destroy(S->ev_fork); sift3d_hip_event_destroy(S->ev_join);
     sift3d_hip_event_destroy(S->ev_join2); sift3d_hip_event_destroy(S->ev_tr);
-    sift3d_hip_event_destroy(S->chain[1].ev_x); sift3d_hip_event_destroy(S->chain[1].ev_halo);
-    sift3d_hip_event_destroy(S->chain[2].ev_x); sift3d_hip_event_destroy(S->chain[2].ev_halo);
-    {
-        int oo;
-        for (oo = 0; oo < SH_MAX_OCT; oo++)
-            sift3d_hip_event_destroy(S->ev_oct[oo]);
+    for (i = 0; i < 5; i++)
+        sift3d_hip_event_destroy(S->ev[i]);
+    for (i = 2; i >= 0; i--) {
+        struct sh_chain *C = &S->chain[i];
+        sift3d_hip_free(C->tmp_a); sift3d_hip_free(C->tmp_b);
+        sift3d_hip_event_destroy(C->ev_x); sift3d_hip_event_destroy(C->ev_halo);
+        if (i == 0)
+            sift3d_hip_stream_destroy(S->comm_stream);
+        sift3d_hip_stream_destroy(C->stream);
     }
-    sift3d_hip_stream_destroy(S->side_stream);
-    sift3d_hip_stream_destroy(S->oct_stream);
-    sift3d_hip_stream_destroy(S->comm_stream);
-    sift3d_hip_stream_destroy(S->stream);
     free(S);
+}
+
+/* the streams and events (the streams in this order: main, communication, the two side chains) */
+static int sh_create_streams(sift3d_amd_sharded *S)
+{
+    void **const ev[4] = { &S->ev_fork, &S->ev_join, &S->ev_join2, &S->ev_tr };
+    int i, o;
+    S->stream = S->chain[0].stream = sift3d_hip_stream_create();
+    S->comm_stream = sift3d_hip_stream_create();
+    S->chain[1].stream = sift3d_hip_stream_create_high();
+    S->chain[2].stream = sift3d_hip_stream_create_high();
+    if (!S->stream || !S->comm_stream || !S->chain[1].stream || !S->chain[2].stream)
+        return SIFT3D_FAILURE;
+    for (i = 0; i < 3; i++)
+        if (!(S->chain[i].ev_x = sift3d_hip_event_create()) || !(S->chain[i].ev_halo = sift3d_hip_event_create()))
+            return SIFT3D_FAILURE;
+    for (i = 0; i < 5; i++)
+        if (!(S->ev[i] = sift3d_hip_event_create()))
+            return SIFT3D_FAILURE;
+    for (i = 0; i < 4; i++)
+        if (!(*ev[i] = sift3d_hip_event_create()))
+            return SIFT3D_FAILURE;
+    for (o = 0; o < S->num_octaves; o++)
+        if (!(S->ev_oct[o] = sift3d_hip_event_create()))
+            return SIFT3D_FAILURE;
+    return SIFT3D_SUCCESS;
+}
+
+/* the Gaussian levels (and, where the DoG-free sweep does not apply, the DoG levels) of every octave: the owned
+ * planes and the halo around them; with them the sizes of the extrema work areas */
+static int sh_alloc_levels(sift3d_amd_sharded *S)
+{
+    int o, s;
+    for (o = 0; o < S->num_octaves; o++) {
+        const int nzo = S->dims[o][2];
+        const int z0 = S->bounds[o][S->rank], z1 = S->bounds[o][S->rank + 1];
+        const int off = sh_sharded(S, o) ? (z0 - S->halo > 0 ? z0 - S->halo : 0) : 0;
+        const int hi = sh_sharded(S, o) ? (z1 + S->halo < nzo ? z1 + S->halo : nzo) : nzo;
+        const size_t bytes = sh_plane(S, o) * (size_t)(hi - off) * sizeof(float);
+        const size_t w = sift3d_hip_extrema_work_bytes(S->dims[o][0], S->dims[o][1], hi - off, S->K);
+        S->work_bytes = w > S->work_bytes ? w : S->work_bytes;
+        if (o >= 1) {
+            S->work2_off[o] = S->work2_bytes;
+            S->work2_sz[o] = w;
+            S->work2_bytes += (w + 255) & ~(size_t)255;
+        }
+        /* (all levels of an octave share one geometry -- the fused sweeps take them as a stack; only
+         * the keypoint levels 1..K USE the full window halo, the others a blur's or the extrema
+         * test's reach) */
+        for (s = 0; s < S->ngl; s++) {
+            sh_level *L = &S->G[o][s];
+            L->off = off; L->nloc = hi - off; L->z0 = z0; L->z1 = z1; L->nz_glob = nzo;
+            if (!(L->t = (float *)sift3d_hip_malloc(bytes)))
+                return SIFT3D_FAILURE;
+        }
+        for (s = 0; s < S->ndl && !S->dog_free[o]; s++)
+            if (!(S->D[o][s] = (float *)sift3d_hip_malloc(bytes)))
+                return SIFT3D_FAILURE;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* the chains' scratch volumes, the input slab, the transition's staging, scalars, tables and work areas */
+static int sh_alloc_scratch(sift3d_amd_sharded *S)
+{
+    const size_t n0 = sh_plane(S, 0) * (size_t)S->G[0][0].nloc;
+    const size_t n1 = S->num_octaves > 1 ? sh_plane(S, 1) * (size_t)S->G[1][0].nloc : 4;
+    int zb[SH_MAX_WORLD + 1], i;
+    for (i = 0; i < 3; i++) {
+        struct sh_chain *C = &S->chain[i];
+        C->tmp_a = (float *)sift3d_hip_malloc((i ? n1 : n0) * sizeof(float));
+        C->tmp_b = (float *)sift3d_hip_malloc((i ? n1 : n0) * sizeof(float));
+        if (!C->tmp_a || !C->tmp_b)
+            return SIFT3D_FAILURE;
+    }
+    S->in_z0 = sh_sharded(S, 0) ? S->bounds[0][S->rank] : 0;
+    S->in_z1 = sh_sharded(S, 0) ? S->bounds[0][S->rank + 1] : S->nz;
+    S->d_im = (float *)sift3d_hip_malloc(n0 * sizeof(float));
+    S->d_raw = (float *)sift3d_hip_malloc(sh_plane(S, 0) * (size_t)(S->in_z1 - S->in_z0) * sizeof(float));
+    /* staging of the sharded -> replicated transition: this rank's down-sampled slab, then the
+     * world slabs gathered (all padded to the largest) */
+    S->stage_elems = 16;
+    if (S->world > 1 && S->o_shard >= 1 && S->o_shard < S->num_octaves)
+        S->stage_elems = (size_t)sh_transition_slabs(S, S->o_shard, zb) * sh_plane(S, S->o_shard) *
+                         (size_t)(S->world + 1);
+    S->d_stage = (float *)sift3d_hip_malloc(S->stage_elems * sizeof(float));
+    S->d_scalars = (float *)sift3d_hip_malloc(sizeof(float) * (8 + SH_MAX_NDL * SH_MAX_OCT));
+    S->d_levels = (sift3d_hip_level *)sift3d_hip_malloc(sizeof(sift3d_hip_level) * SH_MAX_OCT * SH_MAX_NGL);
+    S->d_work = sift3d_hip_malloc(S->work_bytes);
+    if (S->work2_bytes && !(S->d_work2 = sift3d_hip_malloc(S->work2_bytes)))
+        return SIFT3D_FAILURE;
+    S->d_wlut = (float *)sift3d_hip_malloc(sizeof(float) *
+                                           sift3d_hip_describe_wlut_floats(S->num_octaves * S->ngl));
+    return S->d_wlut && S->d_im && S->d_raw && S->d_stage && S->d_scalars && S->d_levels && S->d_work
+               ? SIFT3D_SUCCESS : SIFT3D_FAILURE;
+}
+
+/* level table (window kernels), on the host and on the device */
+static int sh_level_table(sift3d_amd_sharded *S)
+{
+    int o, s;
+    for (o = 0; o < S->num_octaves; o++)
+        for (s = 0; s < S->ngl; s++) {
+            sift3d_hip_level *L = &S->h_levels[o * S->ngl + s];
+            L->data = S->G[o][s].t;
+            L->nx = S->dims[o][0]; L->ny = S->dims[o][1]; L->nz = S->G[o][s].nloc;
+            L->z_off = S->G[o][s].off;
+            L->nz_glob = S->dims[o][2];
+            L->ux = (float)(S->units[0] * ldexp(1.0, o));
+            L->uy = (float)(S->units[1] * ldexp(1.0, o));
+            L->uz = (float)(S->units[2] * ldexp(1.0, o));
+            L->octave = o;
+            L->sd = sh_scale(S, o, s - 1);
+        }
+    return sift3d_hip_memcpy_h2d(S->d_levels, S->h_levels, sizeof(sift3d_hip_level) * (size_t)S->num_octaves * S->ngl,
+                                 S->stream) ||
+           sift3d_hip_stream_sync(S->stream);
 }
 
 sift3d_amd_sharded *sift3d_amd_sharded_create(int nx, int ny, int nz, const sift3d_amd_transport *T,
@@ -238,7 +406,6 @@ sift3d_amd_sharded *sift3d_amd_sharded_create(int nx, int ny, int nz, const sift
 {
     sift3d_amd_sharded *S;
     int o, s, i, hw_max = 0, blur_reach;
-    size_t work = 0, n0;
     if (!T || T->world < 1 || T->world > SH_MAX_WORLD || T->rank < 0 || T->rank >= T->world ||
         nx < 8 || ny < 8 || nz < 8 || !(ux > 0) || !(uy > 0) || !(uz > 0))
         return NULL;
@@ -303,116 +470,7 @@ sift3d_amd_sharded *sift3d_amd_sharded_create(int nx, int ny, int nz, const sift
      * (sift3d_hip_dogmax_stack / sift3d_hip_extrema_gauss6); other octaves store their DoG levels */
     for (o = 0; o < S->num_octaves; o++)
         S->dog_free[o] = !S->cuboid && S->ngl == 6 && (S->dims[o][0] & 3) == 0;
-    if (!(S->stream = sift3d_hip_stream_create()) || !(S->comm_stream = sift3d_hip_stream_create()) ||
-        !(S->ev_x = sift3d_hip_event_create()) || !(S->ev_halo = sift3d_hip_event_create()) ||
-        !(S->ev0 = sift3d_hip_event_create()) || !(S->ev1 = sift3d_hip_event_create()) ||
-        !(S->ev2 = sift3d_hip_event_create()) || !(S->ev3 = sift3d_hip_event_create()) ||
-        !(S->ev4 = sift3d_hip_event_create()) ||
-        !(S->oct_stream = sift3d_hip_stream_create_high()) || !(S->ev_fork = sift3d_hip_event_create()) ||
-        !(S->ev_join = sift3d_hip_event_create()) || !(S->side_stream = sift3d_hip_stream_create_high()) ||
-        !(S->ev_join2 = sift3d_hip_event_create()) || !(S->ev_tr = sift3d_hip_event_create()) ||
-        !(S->chain[1].ev_x = sift3d_hip_event_create()) || !(S->chain[1].ev_halo = sift3d_hip_event_create()) ||
-        !(S->chain[2].ev_x = sift3d_hip_event_create()) || !(S->chain[2].ev_halo = sift3d_hip_event_create()) ||
-        upload_mesh())
-        goto fail;
-    for (o = 0; o < S->num_octaves; o++)
-        if (!(S->ev_oct[o] = sift3d_hip_event_create()))
-            goto fail;
-    /* levels */
-    for (o = 0; o < S->num_octaves; o++) {
-        const int nzo = S->dims[o][2];
-        const int z0 = S->bounds[o][S->rank], z1 = S->bounds[o][S->rank + 1];
-        const int off = sh_sharded(S, o) ? (z0 - S->halo > 0 ? z0 - S->halo : 0) : 0;
-        const int hi = sh_sharded(S, o) ? (z1 + S->halo < nzo ? z1 + S->halo : nzo) : nzo;
-        const size_t w = sift3d_hip_extrema_work_bytes(S->dims[o][0], S->dims[o][1], hi - off, S->K);
-        work = w > work ? w : work;
-        if (o >= 1) {
-            S->work2_off[o] = S->work2_bytes;
-            S->work2_sz[o] = w;
-            S->work2_bytes += (w + 255) & ~(size_t)255;
-        }
-        /* (all levels of an octave share one geometry -- the fused sweeps take them as a stack; only
-         * the keypoint levels 1..K USE the full window halo, the others a blur's or the extrema
-         * test's reach) */
-        for (s = 0; s < S->ngl; s++) {
-            sh_level *L = &S->G[o][s];
-            L->off = off; L->nloc = hi - off; L->z0 = z0; L->z1 = z1; L->nz_glob = nzo;
-            if (!(L->t = (float *)sift3d_hip_malloc(sh_plane(S, o) * (size_t)L->nloc * sizeof(float))))
-                goto fail;
-        }
-        if (!S->dog_free[o])
-            for (s = 0; s < S->ndl; s++)
-                if (!(S->D[o][s] = (float *)sift3d_hip_malloc(sh_plane(S, o) * (size_t)(hi - off) * sizeof(float))))
-                    goto fail;
-    }
-    n0 = sh_plane(S, 0) * (size_t)S->G[0][0].nloc;
-    S->tmp_elems = n0;
-    S->in_z0 = sh_sharded(S, 0) ? S->bounds[0][S->rank] : 0;
-    S->in_z1 = sh_sharded(S, 0) ? S->bounds[0][S->rank + 1] : nz;
-    S->d_tmp_a = (float *)sift3d_hip_malloc(n0 * sizeof(float));
-    S->d_tmp_b = (float *)sift3d_hip_malloc(n0 * sizeof(float));
-    S->d_im = (float *)sift3d_hip_malloc(n0 * sizeof(float));
-    {
-        const size_t n1 = S->num_octaves > 1 ? sh_plane(S, 1) * (size_t)S->G[1][0].nloc : 4;
-        S->d_tmp2_a = (float *)sift3d_hip_malloc(n1 * sizeof(float));
-        S->d_tmp2_b = (float *)sift3d_hip_malloc(n1 * sizeof(float));
-        S->d_tmp3_a = (float *)sift3d_hip_malloc(n1 * sizeof(float));
-        S->d_tmp3_b = (float *)sift3d_hip_malloc(n1 * sizeof(float));
-        if (!S->d_tmp2_a || !S->d_tmp2_b || !S->d_tmp3_a || !S->d_tmp3_b)
-            goto fail;
-    }
-    S->d_raw = (float *)sift3d_hip_malloc(sh_plane(S, 0) * (size_t)(S->in_z1 - S->in_z0) * sizeof(float));
-    /* staging of the sharded -> replicated transition: this rank's down-sampled slab, then the
-     * world slabs gathered (all padded to the largest) */
-    {
-        size_t stage = 16;
-        if (S->world > 1 && S->o_shard >= 1 && S->o_shard < S->num_octaves) {
-            const int t = S->o_shard, mzg = S->dims[t][2];
-            int r, mxn = 1;
-            for (r = 0; r < S->world; r++) {
-                int lo = S->b0[r] >> t, hi = r + 1 < S->world ? S->b0[r + 1] >> t : mzg;
-                lo = lo < mzg ? lo : mzg;
-                hi = hi < mzg ? hi : mzg;
-                if (hi - lo > mxn)
-                    mxn = hi - lo;
-            }
-            stage = (size_t)mxn * sh_plane(S, t) * (size_t)(S->world + 1);
-        }
-        S->stage_elems = stage;
-        S->d_stage = (float *)sift3d_hip_malloc(stage * sizeof(float));
-    }
-    S->d_scalars = (float *)sift3d_hip_malloc(sizeof(float) * (8 + SH_MAX_NDL * SH_MAX_OCT));
-    S->d_levels = (sift3d_hip_level *)sift3d_hip_malloc(sizeof(sift3d_hip_level) * SH_MAX_OCT * SH_MAX_NGL);
-    S->d_work = sift3d_hip_malloc(work);
-    S->work_bytes = work;
-    if (S->work2_bytes && !(S->d_work2 = sift3d_hip_malloc(S->work2_bytes)))
-        goto fail;
-    S->d_wlut = (float *)sift3d_hip_malloc(sizeof(float) *
-                                           sift3d_hip_describe_wlut_floats(S->num_octaves * S->ngl));
-    if (!S->d_wlut || !S->d_tmp_a || !S->d_tmp_b || !S->d_im || !S->d_raw || !S->d_stage || !S->d_scalars ||
-        !S->d_levels || !S->d_work)
-        goto fail;
-    S->chain[0].stream = S->stream;      S->chain[0].tmp_a = S->d_tmp_a;  S->chain[0].tmp_b = S->d_tmp_b;
-    S->chain[0].ev_x = S->ev_x;          S->chain[0].ev_halo = S->ev_halo;
-    S->chain[1].stream = S->oct_stream;  S->chain[1].tmp_a = S->d_tmp2_a; S->chain[1].tmp_b = S->d_tmp2_b;
-    S->chain[2].stream = S->side_stream; S->chain[2].tmp_a = S->d_tmp3_a; S->chain[2].tmp_b = S->d_tmp3_b;
-    /* level table (window kernels) */
-    for (o = 0; o < S->num_octaves; o++)
-        for (s = 0; s < S->ngl; s++) {
-            sift3d_hip_level *L = &S->h_levels[o * S->ngl + s];
-            L->data = S->G[o][s].t;
-            L->nx = S->dims[o][0]; L->ny = S->dims[o][1]; L->nz = S->G[o][s].nloc;
-            L->z_off = S->G[o][s].off;
-            L->nz_glob = S->dims[o][2];
-            L->ux = (float)(ux * ldexp(1.0, o));
-            L->uy = (float)(uy * ldexp(1.0, o));
-            L->uz = (float)(uz * ldexp(1.0, o));
-            L->octave = o;
-            L->sd = sh_scale(S, o, s - 1);
-        }
-    if (sift3d_hip_memcpy_h2d(S->d_levels, S->h_levels,
-                              sizeof(sift3d_hip_level) * (size_t)S->num_octaves * S->ngl, S->stream) ||
-        sift3d_hip_stream_sync(S->stream))
+    if (sh_create_streams(S) || upload_mesh() || sh_alloc_levels(S) || sh_alloc_scratch(S) || sh_level_table(S))
         goto fail;
     return S;
 fail:
@@ -472,13 +530,10 @@ static int sh_halo_range(sift3d_amd_sharded *S, float *t, const sh_level *L, siz
                      (size_t)(h - d0) * plane * sizeof(float), stream);
 }
 
-static int sh_halo(sift3d_amd_sharded *S, float *t, const sh_level *L, size_t plane, int h, void *stream)
-{
-    return sh_halo_range(S, t, L, plane, 0, h, stream);
-}
-
-static int sh_fir(sift3d_amd_sharded *S, const float *src, float *dst, int o, int nloc, int axis,
-                  const filter_t *f, float uf, int off, int z_lo, int z_hi, void *stream)
+/* one FIR pass along `axis` over planes [z_lo, z_hi) of a level buffer of octave o (nloc planes from global
+ * plane `off`) */
+static sift3d_hip_fir_args sh_fir_args(const sift3d_amd_sharded *S, const float *src, float *dst, int o, int nloc,
+                                       int axis, const filter_t *f, float uf, int off, int z_lo, int z_hi)
 {
     sift3d_hip_fir_args a;
     memset(&a, 0, sizeof(a));
@@ -488,6 +543,13 @@ static int sh_fir(sift3d_amd_sharded *S, const float *src, float *dst, int o, in
     a.unit_factor = uf;
     a.n_glob = S->dims[o][2]; a.off = off;
     a.z_lo = z_lo; a.z_hi = z_hi;
+    return a;
+}
+
+static int sh_fir(sift3d_amd_sharded *S, const float *src, float *dst, int o, int nloc, int axis,
+                  const filter_t *f, float uf, int off, int z_lo, int z_hi, void *stream)
+{
+    const sift3d_hip_fir_args a = sh_fir_args(S, src, dst, o, nloc, axis, f, uf, off, z_lo, z_hi);
     return sift3d_hip_fir(&a, stream);
 }
 
@@ -498,7 +560,17 @@ static int sh_fir(sift3d_amd_sharded *S, const float *src, float *dst, int o, in
  * its status word travels behind the first all-gather of the step (the counts) and behind the second (the
  * records), and EVERY rank returns SIFT3D_FAILURE at the same point, with the transport in step for the next
  * call -- the reference's "every stage returns -1 to its caller" (immacros.h:27-32), across ranks.  A
- * failure of the transport itself is everybody's by nature and returns at once. */
+ * failure of the transport itself is everybody's by nature and returns at once.
+ *
+ * The contract of every stage of sift3d_amd_sharded_detect (and of sh_blur below them):
+ *   - it returns non-zero only for what is everybody's failure -- a transport error (SH_COMM), or a condition
+ *     that every rank computes alike (the geometry, the gathered counts, the status words) -- and the caller
+ *     returns at once (sh_begin also refuses, before anything is issued, arguments no call can run with);
+ *   - a local failure only marks S->failed (SH_DO), and the stage still issues its exchanges;
+ *   - the exception: the exchange buffers themselves (sh_exchange_counts, sh_exchange_records).  Where they
+ *     cannot be allocated there is nothing to send in, and the stage returns;
+ *   - local work is guarded by !S->failed, the candidate count or an owned range that is not empty; an exchange
+ *     by nothing but the geometry. */
 #define SH_DO(call)                                        \
     do {                                                   \
         if (!S->failed && (call))                          \
@@ -509,6 +581,13 @@ static int sh_fir(sift3d_amd_sharded *S, const float *src, float *dst, int o, in
         if (call)                                          \
             return SIFT3D_FAILURE;                         \
     } while (0)
+
+/* the failing rank's own line of a call that fails on every rank */
+static void sh_report_local_failure(const sift3d_amd_sharded *S)
+{
+    if (S->failed)
+        ERR("sift3d_amd_sharded_detect: rank %d failed locally (mark %d) \n", S->rank, S->failed);
+}
 
 /* test hook: the next detect (where = 1: before the pyramid, 2: after the extrema, 3: between the two
  * all-gathers) or describe-gather (4) of THIS rank fails locally */
@@ -524,62 +603,45 @@ int sift3d_amd_sharded_inject_failure(sift3d_amd_sharded *S, int where)
  * that overflows them */
 int sift3d_amd_sharded_set_candidate_capacity(sift3d_amd_sharded *S, int cap)
 {
-    if (!S || cap < 0)
+    if (!S || cap < 0 || sh_sync_streams(S))
         return SIFT3D_FAILURE;
-    if ((S->stream && sift3d_hip_stream_sync(S->stream)) || (S->comm_stream && sift3d_hip_stream_sync(S->comm_stream)) ||
-        (S->oct_stream && sift3d_hip_stream_sync(S->oct_stream)) ||
-        (S->side_stream && sift3d_hip_stream_sync(S->side_stream)))
-        return SIFT3D_FAILURE;
-    sift3d_hip_free(S->d_cand); sift3d_hip_free(S->d_R); sift3d_hip_free(S->d_keep);
-    S->d_cand = NULL;
-    S->d_R = NULL;
-    S->d_keep = NULL;
-    S->cand_cap = 0;
+    sh_free_cand(S);
     S->cand_cap0 = (uint32_t)cap;
     return SIFT3D_SUCCESS;
 }
 
 int sift3d_amd_sharded_candidate_capacity(const sift3d_amd_sharded *S)
 {
-    if (!S)
-        return -1;
-    return (int)(S->cand_cap ? S->cand_cap : S->cand_cap0 ? S->cand_cap0 : (1u << 18));
+    return S ? (int)sh_cand_capacity(S) : -1;
 }
 
-/* apply_Sep_FIR_filter (imutil.c:1127-1206) on a level: src -> dst (same geometry).  Sharded
- * octaves: x (and y) on the owned planes, halo exchange of the z pass's input overlapped with the
- * z pass of the interior planes. */
+/* apply_Sep_FIR_filter (imutil.c:1127-1206) on level s of octave o: src -> G[o][s], with filter s.  Sharded
+ * octaves: x (and y) on the owned planes, halo exchange of the z pass's input (on the communication stream, in
+ * host issue order) overlapped with the z pass of the interior planes. */
 /* d_scale_max (the first blur of the pyramid only, else NULL): the blur of src / *d_scale_max -- im_scale
  * folded into the x pass (sift3d_hip_fir_x_scaled); returns 2 without doing anything when that x pass does
  * not cover the configuration (the same answer on every rank) */
-static int sh_blur(sift3d_amd_sharded *S, const struct sh_chain *C, int o, const float *src, const sh_level *Lg,
-                   float *dst, const filter_t *f, const float *d_scale_max)
+static int sh_blur(sift3d_amd_sharded *S, const struct sh_chain *C, int o, int s, const float *src,
+                   const float *d_scale_max)
 {
+    const sh_level *Lg = &S->G[o][s];
+    const filter_t *f = &S->filt[s];
+    float *dst = Lg->t;
     const size_t plane = sh_plane(S, o);
     const int nx = S->dims[o][0], ny = S->dims[o][1], nzo = S->dims[o][2];
     const float ufx = (float)(1.0 / (S->units[0] * ldexp(1.0, o)));
     const float ufy = (float)(1.0 / (S->units[1] * ldexp(1.0, o)));
     const float ufz = (float)(1.0 / (S->units[2] * ldexp(1.0, o)));
     const int hw = f->width / 2;
-    const int a = sh_sharded(S, o) ? Lg->z0 - Lg->off : 0;
-    const int b = sh_sharded(S, o) ? Lg->z1 - Lg->off : Lg->nloc;
     const int reach = (int)ceilf((float)hw * ufz) + 1;
     const int exch = S->world > 1 && sh_sharded(S, o);
     float *zin;
-    int fused, ia, ib;
+    int fused, a, b, ia, ib;
+    sh_owned(S, o, &a, &b);
     if (d_scale_max) {
-        sift3d_hip_fir_args fa;
-        int rc;
-        memset(&fa, 0, sizeof(fa));
-        fa.src = src; fa.dst = C->tmp_a;
-        fa.nx = nx; fa.ny = ny; fa.nz = Lg->nloc;
-        fa.axis = 0; fa.width = f->width; fa.taps = f->taps;
-        fa.unit_factor = ufx;
-        fa.n_glob = nzo; fa.off = 0;
-        fa.z_lo = a; fa.z_hi = b;
+        const sift3d_hip_fir_args fa = sh_fir_args(S, src, C->tmp_a, o, Lg->nloc, 0, f, ufx, 0, a, b);
         /* (whether this x pass covers the configuration does not depend on the rank) */
-        rc = sift3d_hip_fir_x_scaled_covers(&fa) ? 0 : 1;
-        if (rc == 1)
+        if (!sift3d_hip_fir_x_scaled_covers(&fa))
             return 2;
         SH_DO(sift3d_hip_fir_x_scaled(&fa, d_scale_max, C->stream) != SIFT3D_SUCCESS);
     } else {
@@ -597,9 +659,8 @@ static int sh_blur(sift3d_amd_sharded *S, const struct sh_chain *C, int o, const
     if (ib < ia)
         ia = ib = a;                                     /* thin slab: everything after the exchange */
     if (exch) {
-        SH_COMM(sift3d_hip_event_record(C->ev_x, C->stream) ||
-                sift3d_hip_stream_wait_event(S->comm_stream, C->ev_x) ||
-                sh_halo(S, zin, Lg, plane, reach, S->comm_stream) ||
+        SH_COMM(stream_after(S->comm_stream, C->ev_x, C->stream) ||
+                sh_halo_range(S, zin, Lg, plane, 0, reach, S->comm_stream) ||
                 sift3d_hip_event_record(C->ev_halo, S->comm_stream));
     }
 #define SH_ZPASS(lo_, hi_)                                                                           \
@@ -622,30 +683,21 @@ static int sh_blur(sift3d_amd_sharded *S, const struct sh_chain *C, int o, const
     return SIFT3D_SUCCESS;
 }
 
-/* a device buffer of at least `bytes` (grown with a quarter of slack) */
-static int sh_ensure_dev(void **p, size_t *cap, size_t bytes)
+/* a buffer of at least `bytes` (grown with a quarter of slack) in device memory, or in page-locked host memory */
+static int sh_ensure(void **p, size_t *cap, size_t bytes, int pinned)
 {
     if (bytes <= *cap)
         return SIFT3D_SUCCESS;
-    sift3d_hip_free(*p);
+    (pinned ? sift3d_hip_host_free : sift3d_hip_free)(*p);
     *cap = 0;
-    if (!(*p = sift3d_hip_malloc(bytes + bytes / 4)))
+    *p = (pinned ? sift3d_hip_host_alloc : sift3d_hip_malloc)(bytes + bytes / 4);
+    if (!*p)
         return SIFT3D_FAILURE;
     *cap = bytes + bytes / 4;
     return SIFT3D_SUCCESS;
 }
-
-static int sh_ensure_pinned(void **p, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap)
-        return SIFT3D_SUCCESS;
-    sift3d_hip_host_free(*p);
-    *cap = 0;
-    if (!(*p = sift3d_hip_host_alloc(bytes + bytes / 4)))
-        return SIFT3D_FAILURE;
-    *cap = bytes + bytes / 4;
-    return SIFT3D_SUCCESS;
-}
+static int sh_ensure_dev(void **p, size_t *cap, size_t bytes) { return sh_ensure(p, cap, bytes, 0); }
+static int sh_ensure_pinned(void **p, size_t *cap, size_t bytes) { return sh_ensure(p, cap, bytes, 1); }
 
 /* all-gather of one device block per rank, on the main stream (one rank: a copy) */
 static int sh_allgather_dev(sift3d_amd_sharded *S, const void *d_mine, void *d_all, size_t bytes)
@@ -659,8 +711,7 @@ static int sh_ensure_cand(sift3d_amd_sharded *S, uint32_t cap)
 {
     if (cap <= S->cand_cap)
         return SIFT3D_SUCCESS;
-    sift3d_hip_free(S->d_cand); sift3d_hip_free(S->d_R); sift3d_hip_free(S->d_keep);
-    S->cand_cap = 0;
+    sh_free_cand(S);
     S->d_cand = (sift3d_hip_cand *)sift3d_hip_malloc(sizeof(sift3d_hip_cand) * (size_t)cap);
     S->d_R = (float *)sift3d_hip_malloc(sizeof(float) * 9 * (size_t)cap);
     S->d_keep = (int32_t *)sift3d_hip_malloc(sizeof(int32_t) * (size_t)cap);
@@ -732,576 +783,588 @@ int sift3d_amd_slab_table(const void *cnt, size_t cnt_stride, int world, int nke
     return SIFT3D_SUCCESS;
 }
 
-int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
+/* What the stages of ONE detect call pass to each other: every field is set by the stage that decides it and
+ * only read after that.  Nothing of it outlives the call. */
+typedef struct {
+    double t_start;
+    int nkey;                    /* (octave, keypoint level) pairs: the keys of the global order */
+    int all_free;                /* every octave takes the DoG-free sweep */
+    uint32_t count;              /* this rank's candidates; 0 once it has failed */
+    size_t cnt_bytes;            /* a rank's block of the first all-gather: 2 counts per key, status word */
+    size_t tab_words;            /* words of the segment tables */
+    sift3d_amd_slab_layout lay;  /* totals of all ranks, a rank's block of the second all-gather */
+} sh_run;
+
+/* the two status words this rank sends, behind the gathered counts in the page-locked count buffer */
+static inline int32_t *sh_status_words(const sift3d_amd_sharded *S, const sh_run *r)
 {
-    const double t_start = now_s();
-    uint32_t count = 0;
-    int o, s, r, k, attempt, nkey, all_free = 1;
+    return (int32_t *)((char *)S->h_cnt + r->cnt_bytes * (size_t)S->world);
+}
+
+/* arguments, the failure mark, and set_im_SIFT3D: scale by the GLOBAL max|v| (sift.c:645-649; im_scale itself is
+ * folded into the first blur, or run there).  EXCHANGE: all-reduce of one float, main stream. */
+static int sh_begin(sift3d_amd_sharded *S, const sift3d_keypoint_store *kp, sh_run *r)
+{
+    int o;
+    memset(r, 0, sizeof(*r));
+    r->t_start = now_s();
     if (!S || !kp)
         return SIFT3D_FAILURE;
-    nkey = S->num_octaves * S->K;
-    if (nkey > 256)
+    r->nkey = S->num_octaves * S->K;
+    if (r->nkey > 256)
         return SIFT3D_FAILURE;
+    r->all_free = 1;
     for (o = 0; o < S->num_octaves; o++)
-        all_free = all_free && S->dog_free[o];
+        r->all_free = r->all_free && S->dog_free[o];
     S->failed = S->inject == 1 ? -1 : 0;
+    sift3d_hip_event_record(S->ev[4], S->stream);
+    SH_DO(sift3d_hip_memset(S->d_scalars, 0, sizeof(float) * (8 + SH_MAX_NDL * SH_MAX_OCT), S->stream) ||
+          sift3d_hip_absmax(S->d_raw, sh_plane(S, 0) * (size_t)(S->in_z1 - S->in_z0), S->d_scalars, S->stream));
+    if (S->world > 1)
+        SH_COMM(S->T.allreduce_max(S->T.ctx, S->d_scalars, 1, S->stream));
+    return SIFT3D_SUCCESS;
+}
 
-    /* set_im_SIFT3D: scale by the GLOBAL max|v| (sift.c:645-649) */
-    sift3d_hip_event_record(S->ev4, S->stream);
-    {
-        const size_t n_in = sh_plane(S, 0) * (size_t)(S->in_z1 - S->in_z0);
-        SH_DO(sift3d_hip_memset(S->d_scalars, 0, sizeof(float) * (8 + SH_MAX_NDL * SH_MAX_OCT), S->stream) ||
-              sift3d_hip_absmax(S->d_raw, n_in, S->d_scalars, S->stream));
-        if (S->world > 1)
-            SH_COMM(S->T.allreduce_max(S->T.ctx, S->d_scalars, 1, S->stream));
-        /* (im_scale itself: folded into the first blur below, or run there) */
+/* the first blur reads the raw slab and scales as it stages (im_scale folded into the x pass: the scaled image is
+ * not stored); where that x pass does not apply, scale first.  EXCHANGE: the blur's halo. */
+static int sh_first_blur(sift3d_amd_sharded *S)
+{
+    const struct sh_chain *C0 = &S->chain[0];
+    int a0, b0, rc;
+    sh_owned(S, 0, &a0, &b0);
+    /* (d_raw holds the owned planes only: plane index a0 of the level buffer is its plane 0) */
+    rc = sh_blur(S, C0, 0, 0, S->d_raw - (size_t)a0 * sh_plane(S, 0), S->d_scalars);
+    if (rc == 2) {
+        SH_DO(sift3d_hip_scale(S->d_raw, S->d_im + (size_t)a0 * sh_plane(S, 0),
+                               sh_plane(S, 0) * (size_t)(S->in_z1 - S->in_z0), S->d_scalars, S->stream));
+        return sh_blur(S, C0, 0, 0, S->d_im, NULL);
     }
-    /* build_gpyr, sift.c:662-711 -- on three dependency chains, as the single-GPU path builds it
-     * (detect_on_device): octave o + 1 starts from level K of octave o (sift.c:696-704) and the levels after
-     * K feed nothing but their octave's DoG, so once level K of octave 0 exists the smaller octaves --
-     * short launches that cannot fill the device -- are built on a second stream BESIDE the last levels of
-     * octave 0, their own last levels on a third, and all are joined before the DoG stage.  The z-halo
-     * exchanges of all chains travel on the one communication stream in the order the host issues them
-     * (the same on every rank); the collective of the sharded -> replicated transition stays on the main
-     * stream, where every other collective of a step is issued. */
-    sift3d_hip_event_record(S->ev0, S->stream);
-    {
-        const int forked = S->num_octaves > 1 && S->K + 1 < S->ngl;
-        const struct sh_chain *C0 = &S->chain[0];
-        for (o = 0; o < S->num_octaves; o++) {
-            const struct sh_chain *Ca = (o > 0 && forked) ? &S->chain[1] : C0;     /* levels 1 .. K */
-            const struct sh_chain *Cb = (o > 0 && forked) ? &S->chain[2] : C0;     /* levels K + 1 .. */
-            if (o == 0) {
-                /* the first blur reads the raw slab and scales as it stages (im_scale folded into the x
-                 * pass: the scaled image is not stored); where that x pass does not apply, scale first */
-                const sh_level *L0 = &S->G[0][0];
-                const int a0 = sh_sharded(S, 0) ? L0->z0 - L0->off : 0;
-                const size_t n_in = sh_plane(S, 0) * (size_t)(S->in_z1 - S->in_z0);
-                /* (d_raw holds the owned planes only: plane index a0 of the level buffer is its plane 0) */
-                int rc = sh_blur(S, C0, 0, S->d_raw - (size_t)a0 * sh_plane(S, 0), L0, L0->t, &S->filt[0],
-                                 S->d_scalars);
-                if (rc == 2) {
-                    SH_DO(sift3d_hip_scale(S->d_raw, S->d_im + (size_t)a0 * sh_plane(S, 0), n_in, S->d_scalars,
-                                           S->stream));
-                    SH_COMM(sh_blur(S, C0, 0, S->d_im, L0, L0->t, &S->filt[0], NULL));
-                } else if (rc != SIFT3D_SUCCESS) {
-                    return SIFT3D_FAILURE;
-                }
-            }
-            for (s = 1; s <= S->K && s < S->ngl; s++)
-                SH_COMM(sh_blur(S, Ca, o, S->G[o][s - 1].t, &S->G[o][s], S->G[o][s].t, &S->filt[s], NULL));
-            if (forked) {
-                /* level K exists: the next octave (chain 1) and this octave's last levels (chain 2, or the
-                 * main stream for octave 0) go their own ways */
-                if (o == 0)
-                    SH_COMM(sift3d_hip_event_record(S->ev_fork, S->stream) ||
-                            sift3d_hip_stream_wait_event(S->oct_stream, S->ev_fork));
-                else
-                    SH_COMM(sift3d_hip_event_record(S->ev_oct[o], Ca->stream) ||
-                            sift3d_hip_stream_wait_event(Cb->stream, S->ev_oct[o]));
-            }
-            if (o != S->num_octaves - 1) {
-                /* level max(s_end - 2, first_level) = Gaussian index K, sift.c:696-704; on the stream that
-                 * builds the next octave */
-                void *ds = forked ? S->oct_stream : S->stream;
-                const sh_level *src = &S->G[o][S->K];
-                sh_level *dst = &S->G[o + 1][0];
-                const int mx = S->dims[o + 1][0], my = S->dims[o + 1][1], mzg = S->dims[o + 1][2];
-                const size_t pl_s = sh_plane(S, o), pl_d = sh_plane(S, o + 1);
-                if (sh_sharded(S, o) && !sh_sharded(S, o + 1)) {
-                    /* transition to the replicated octaves: down-sample the owned planes into a
-                     * staging slab, all-gather the slabs (padded to the largest) */
-                    int zb[SH_MAX_WORLD + 1], mxn = 1;
-                    for (r = 0; r < S->world; r++) {
-                        zb[r] = S->b0[r] >> (o + 1);
-                        if (zb[r] > mzg) zb[r] = mzg;
-                    }
-                    zb[S->world] = mzg;
-                    for (r = 0; r < S->world; r++)
-                        if (zb[r + 1] - zb[r] > mxn) mxn = zb[r + 1] - zb[r];
-                    {
-                        const int z0 = zb[S->rank], z1 = zb[S->rank + 1];
-                        float *mine = S->d_stage, *all;
-                        const size_t slab = (size_t)mxn * pl_d;
-                        if (slab * (size_t)(S->world + 1) > S->stage_elems)
-                            return SIFT3D_FAILURE;       /* (geometry: the same on every rank) */
-                        all = mine + slab;
-                        SH_DO(sift3d_hip_memset(mine, 0, slab * sizeof(float), ds));
-                        if (z1 > z0)
-                            SH_DO(sift3d_hip_downsample2(src->t + (size_t)(2 * z0 - src->off) * pl_s,
-                                                         S->dims[o][0], S->dims[o][1], mine, mx, my, z1 - z0, ds));
-                        /* the collective on the main stream (behind what that stream holds), the next
-                         * octave behind the collective */
-                        if (ds != S->stream)
-                            SH_COMM(sift3d_hip_event_record(S->ev_tr, ds) ||
-                                    sift3d_hip_stream_wait_event(S->stream, S->ev_tr));
-                        SH_COMM(S->T.allgather(S->T.ctx, mine, all, slab * sizeof(float), S->stream));
-                        for (r = 0; r < S->world; r++)
-                            if (zb[r + 1] > zb[r])
-                                SH_DO(sift3d_hip_memcpy_d2d(dst->t + (size_t)zb[r] * pl_d, all + (size_t)r * slab,
-                                                            (size_t)(zb[r + 1] - zb[r]) * pl_d * sizeof(float),
-                                                            S->stream));
-                        if (ds != S->stream)
-                            SH_COMM(sift3d_hip_event_record(S->ev_tr, S->stream) ||
-                                    sift3d_hip_stream_wait_event(ds, S->ev_tr));
-                    }
-                } else {
-                    const int z0 = sh_sharded(S, o + 1) ? dst->z0 : 0, z1 = sh_sharded(S, o + 1) ? dst->z1 : mzg;
-                    if (z1 > z0)
-                        SH_DO(sift3d_hip_downsample2(src->t + (size_t)(2 * z0 - src->off) * pl_s, S->dims[o][0],
-                                                     S->dims[o][1], dst->t + (size_t)(z0 - dst->off) * pl_d, mx,
-                                                     my, z1 - z0, ds));
-                }
-            }
-            for (s = S->K + 1; s < S->ngl; s++)
-                SH_COMM(sh_blur(S, Cb, o, S->G[o][s - 1].t, &S->G[o][s], S->G[o][s].t, &S->filt[s], NULL));
+    return rc;
+}
+
+/* octave o + 1 from Gaussian level K of octave o (max(s_end - 2, first_level), sift.c:696-704), both sharded or
+ * both replicated: the owned planes, on stream ds */
+static void sh_downsample(sift3d_amd_sharded *S, int o, void *ds)
+{
+    const sh_level *src = &S->G[o][S->K];
+    sh_level *dst = &S->G[o + 1][0];
+    const int z0 = sh_sharded(S, o + 1) ? dst->z0 : 0, z1 = sh_sharded(S, o + 1) ? dst->z1 : S->dims[o + 1][2];
+    if (z1 > z0)
+        SH_DO(sift3d_hip_downsample2(src->t + (size_t)(2 * z0 - src->off) * sh_plane(S, o), S->dims[o][0],
+                                     S->dims[o][1], dst->t + (size_t)(z0 - dst->off) * sh_plane(S, o + 1),
+                                     S->dims[o + 1][0], S->dims[o + 1][1], z1 - z0, ds));
+}
+
+/* The same across the transition to the replicated octaves: down-sample the owned planes into a staging slab,
+ * all-gather the slabs (padded to the largest), copy them into place.  EXCHANGE: the all-gather, on the MAIN
+ * stream (behind what that stream holds), where every other collective of a step is issued; stream ds, which
+ * builds the next octave, goes on behind it. */
+static int sh_transition(sift3d_amd_sharded *S, int o, void *ds)
+{
+    const sh_level *src = &S->G[o][S->K];
+    sh_level *dst = &S->G[o + 1][0];
+    const size_t pl_d = sh_plane(S, o + 1);
+    int zb[SH_MAX_WORLD + 1], r;
+    const size_t slab = (size_t)sh_transition_slabs(S, o + 1, zb) * pl_d;
+    const int z0 = zb[S->rank], z1 = zb[S->rank + 1];
+    float *mine = S->d_stage, *all = mine + slab;
+    if (slab * (size_t)(S->world + 1) > S->stage_elems)
+        return SIFT3D_FAILURE;       /* (geometry: the same on every rank) */
+    SH_DO(sift3d_hip_memset(mine, 0, slab * sizeof(float), ds));
+    if (z1 > z0)
+        SH_DO(sift3d_hip_downsample2(src->t + (size_t)(2 * z0 - src->off) * sh_plane(S, o), S->dims[o][0],
+                                     S->dims[o][1], mine, S->dims[o + 1][0], S->dims[o + 1][1], z1 - z0, ds));
+    if (ds != S->stream)
+        SH_COMM(stream_after(S->stream, S->ev_tr, ds));
+    SH_COMM(S->T.allgather(S->T.ctx, mine, all, slab * sizeof(float), S->stream));
+    for (r = 0; r < S->world; r++)
+        if (zb[r + 1] > zb[r])
+            SH_DO(sift3d_hip_memcpy_d2d(dst->t + (size_t)zb[r] * pl_d, all + (size_t)r * slab,
+                                        (size_t)(zb[r + 1] - zb[r]) * pl_d * sizeof(float), S->stream));
+    if (ds != S->stream)
+        SH_COMM(stream_after(ds, S->ev_tr, S->stream));
+    return SIFT3D_SUCCESS;
+}
+
+/* build_gpyr, sift.c:662-711 -- on three dependency chains, as the single-GPU path builds it
+ * (detect_on_device): octave o + 1 starts from level K of octave o (sift.c:696-704) and the levels after
+ * K feed nothing but their octave's DoG, so once level K of octave 0 exists the smaller octaves --
+ * short launches that cannot fill the device -- are built on a second stream BESIDE the last levels of
+ * octave 0, their own last levels on a third, and all are joined before the DoG stage.
+ * EXCHANGES: the z-halo exchange of every blur of a sharded octave; those of all chains travel on the one
+ * communication stream in the order the host issues them here (the same on every rank): octave by octave, levels
+ * 0 (octave 0 only), 1 .. K, then K + 1 .. ngl - 1.  Between the two groups of the last sharded octave: the
+ * transition's all-gather. */
+static int sh_pyramid(sift3d_amd_sharded *S)
+{
+    const int forked = S->num_octaves > 1 && S->K + 1 < S->ngl;
+    int o, s;
+    SH_COMM(sh_first_blur(S));
+    for (o = 0; o < S->num_octaves; o++) {
+        const struct sh_chain *Ca = &S->chain[o > 0 && forked ? 1 : 0];        /* levels 1 .. K */
+        const struct sh_chain *Cb = &S->chain[o > 0 && forked ? 2 : 0];        /* levels K + 1 .. */
+        for (s = 1; s <= S->K && s < S->ngl; s++)
+            SH_COMM(sh_blur(S, Ca, o, s, S->G[o][s - 1].t, NULL));
+        /* level K exists: the next octave (chain 1) and this octave's last levels (chain 2, or the main stream
+         * for octave 0) go their own ways */
+        if (forked && o == 0)
+            SH_COMM(stream_after(S->chain[1].stream, S->ev_fork, S->stream));
+        else if (forked)
+            SH_COMM(stream_after(Cb->stream, S->ev_oct[o], Ca->stream));
+        if (o != S->num_octaves - 1) {
+            void *ds = forked ? S->chain[1].stream : S->stream;      /* the stream that builds the next octave */
+            if (sh_sharded(S, o) && !sh_sharded(S, o + 1))
+                SH_COMM(sh_transition(S, o, ds));
+            else
+                sh_downsample(S, o, ds);
         }
-        if (forked)
-            SH_COMM(sift3d_hip_event_record(S->ev_join, S->oct_stream) ||
-                    sift3d_hip_stream_wait_event(S->stream, S->ev_join) ||
-                    sift3d_hip_event_record(S->ev_join2, S->side_stream) ||
-                    sift3d_hip_stream_wait_event(S->stream, S->ev_join2));
+        for (s = S->K + 1; s < S->ngl; s++)
+            SH_COMM(sh_blur(S, Cb, o, s, S->G[o][s - 1].t, NULL));
     }
-    sift3d_hip_event_record(S->ev1, S->stream);
+    if (forked)
+        SH_COMM(stream_after(S->stream, S->ev_join, S->chain[1].stream) ||
+                stream_after(S->stream, S->ev_join2, S->chain[2].stream));
+    return SIFT3D_SUCCESS;
+}
 
-    /* The nearest halo plane of every level of the sharded octaves: the extrema test looks one plane
-     * past the slab, and stored DoG levels are formed on it */
+/* The nearest halo plane of every level of the sharded octaves: the extrema test looks one plane past the slab,
+ * and stored DoG levels are formed on it.  EXCHANGES: one halo per level, main stream. */
+static int sh_nearest_halos(sift3d_amd_sharded *S)
+{
+    int o, s;
     for (o = 0; o < S->o_shard; o++)
         for (s = 0; s < S->ngl; s++)
             SH_COMM(sh_halo_range(S, S->G[o][s].t, &S->G[o][s], sh_plane(S, o), 0, 1, S->stream));
+    return SIFT3D_SUCCESS;
+}
 
-    /* dogmax (sift.c:821-826) of every octave on the owned planes (every plane is owned by some
-     * rank), one all-reduce for all of them.  Octaves of the DoG-free sweep store no DoG level; the
-     * others form theirs (build_dog, sift.c:713-732) on the owned planes and one plane around them
-     * -- the neighbours' planes are theirs to count, but a maximum does not mind a plane twice. */
+/* the stored DoG levels of octave o (build_dog, sift.c:713-732) and their maxima, on the owned planes [lo, hi) and
+ * one plane around them -- the neighbours' planes are theirs to count, but a maximum does not mind a plane twice */
+static void sh_dog_octave(sift3d_amd_sharded *S, int o, int lo, int hi)
+{
+    const int lo2 = lo > 0 ? lo - 1 : 0, hi2 = hi < S->G[o][0].nloc ? hi + 1 : S->G[o][0].nloc;
+    const size_t n2 = (size_t)(hi2 - lo2) * sh_plane(S, o);
+    const float *g[SH_MAX_NGL];
+    float *dd[SH_MAX_NDL];
+    int s, rc = 0;
+    sh_level_ptrs(S, o, lo2, g);
+    for (s = 0; s < S->ndl; s++)
+        dd[s] = S->D[o][s] + (size_t)lo2 * sh_plane(S, o);
+    if (!S->failed)
+        rc = sift3d_hip_dog_stack(g, dd, S->ngl, n2, sh_dogmax_slot(S, o), S->stream);
+    if (rc == 1) {
+        for (s = 0; s < S->ndl; s++)
+            SH_DO(sift3d_hip_subtract_absmax(g[s], g[s + 1], dd[s], n2, sh_dogmax_slot(S, o) + s, S->stream));
+    } else if (rc != SIFT3D_SUCCESS) {
+        SH_DO(1);
+    }
+}
+
+/* dogmax (sift.c:821-826) of every octave on the owned planes (every plane is owned by some rank), one all-reduce
+ * for all of them.  Octaves of the DoG-free sweep store no DoG level; the others form theirs.
+ * EXCHANGE: all-reduce of ndl * num_octaves floats, main stream. */
+static int sh_dog_stage(sift3d_amd_sharded *S)
+{
+    int o, lo, hi;
     for (o = 0; o < S->num_octaves; o++) {
-        const sh_level *L = &S->G[o][0];
-        const size_t plane = sh_plane(S, o);
-        const int lo = sh_sharded(S, o) ? L->z0 - L->off : 0;
-        const int hi = sh_sharded(S, o) ? L->z1 - L->off : L->nloc;
         const float *g[SH_MAX_NGL];
+        sh_owned(S, o, &lo, &hi);
+        if (hi <= lo)
+            continue;
         if (S->dog_free[o]) {
-            for (s = 0; s < S->ngl; s++)
-                g[s] = S->G[o][s].t + (size_t)lo * plane;
-            if (hi > lo)
-                SH_DO(sift3d_hip_dogmax_stack(g, S->ngl, (size_t)(hi - lo) * plane,
-                                              S->d_scalars + 8 + S->ndl * o, S->stream) != SIFT3D_SUCCESS);
+            sh_level_ptrs(S, o, lo, g);
+            SH_DO(sift3d_hip_dogmax_stack(g, S->ngl, (size_t)(hi - lo) * sh_plane(S, o), sh_dogmax_slot(S, o),
+                                          S->stream) != SIFT3D_SUCCESS);
         } else {
-            const int lo2 = lo > 0 ? lo - 1 : 0, hi2 = hi < L->nloc ? hi + 1 : L->nloc;
-            const size_t n2 = (size_t)(hi2 - lo2) * plane;
-            float *dd[SH_MAX_NDL];
-            int rc = 0;
-            if (hi <= lo)
-                continue;
-            for (s = 0; s < S->ngl; s++)
-                g[s] = S->G[o][s].t + (size_t)lo2 * plane;
-            for (s = 0; s < S->ndl; s++)
-                dd[s] = S->D[o][s] + (size_t)lo2 * plane;
-            if (!S->failed)
-                rc = sift3d_hip_dog_stack(g, dd, S->ngl, n2, S->d_scalars + 8 + S->ndl * o, S->stream);
-            if (rc == 1) {
-                for (s = 0; s < S->ndl; s++)
-                    SH_DO(sift3d_hip_subtract_absmax(g[s], g[s + 1], dd[s], n2,
-                                                     S->d_scalars + 8 + S->ndl * o + s, S->stream));
-            } else if (rc != SIFT3D_SUCCESS) {
-                SH_DO(1);
-            }
+            sh_dog_octave(S, o, lo, hi);
         }
     }
     if (S->world > 1)
         SH_COMM(S->T.allreduce_max(S->T.ctx, S->d_scalars + 8, S->ndl * S->num_octaves, S->stream));
+    return SIFT3D_SUCCESS;
+}
 
-    /* The windows of the orientation and descriptor kernels reach win_reach[s] planes into the
-     * neighbours' slabs: the largest exchange of a step.  It travels on the communication stream
-     * WHILE the extrema are found, and is awaited before the orientation kernel.  (No collective is
-     * issued on the compute stream in between: one communicator, one order.) */
-    if (S->world > 1 && S->o_shard > 0) {
-        SH_COMM(sift3d_hip_event_record(S->ev_x, S->stream) ||
-                sift3d_hip_stream_wait_event(S->comm_stream, S->ev_x));
-        for (o = 0; o < S->o_shard; o++)
-            for (s = 0; s < S->ngl; s++)
-                SH_COMM(sh_halo_range(S, S->G[o][s].t, &S->G[o][s], sh_plane(S, o), 1, S->win_reach[s],
-                                      S->comm_stream));
-        SH_COMM(sift3d_hip_event_record(S->ev_halo, S->comm_stream));
-    }
+/* The windows of the orientation and descriptor kernels reach win_reach[s] planes into the neighbours' slabs: the
+ * largest exchange of a step.  EXCHANGES: one halo per level of the sharded octaves, on the communication stream
+ * WHILE the extrema are found; awaited by sh_orient_stage.  (No collective is issued on the compute stream in
+ * between: one communicator, one order.) */
+static int sh_window_halos_begin(sift3d_amd_sharded *S)
+{
+    int o, s;
+    if (S->world == 1 || S->o_shard == 0)
+        return SIFT3D_SUCCESS;
+    SH_COMM(stream_after(S->comm_stream, S->chain[0].ev_x, S->stream));
+    for (o = 0; o < S->o_shard; o++)
+        for (s = 0; s < S->ngl; s++)
+            SH_COMM(sh_halo_range(S, S->G[o][s].t, &S->G[o][s], sh_plane(S, o), 1, S->win_reach[s],
+                                  S->comm_stream));
+    SH_COMM(sift3d_hip_event_record(S->chain[0].ev_halo, S->comm_stream));
+    return SIFT3D_SUCCESS;
+}
 
-    /* detect_extrema (sift.c:735-871) on the owned planes, assign_orientations (sift.c:1109-1167)
-     * for the local candidates */
-    SH_DO(sh_ensure_cand(S, S->cand_cap ? S->cand_cap : S->cand_cap0 ? S->cand_cap0 : (1u << 18)));
-    for (attempt = 0; attempt < 2 && !S->failed; attempt++) {
-        /* with every octave on the DoG-free sweep: the sweeps of octaves >= 1 (short launches) beside
-         * octave 0's on a second stream, then scan + emission in octave order
-         * (sift3d_hip_extrema_gauss6_phase); otherwise octave by octave */
-        const int side = all_free && S->num_octaves > 1 && S->d_work2 != NULL;
-        int phase;
-        SH_DO(sift3d_hip_memset(S->d_scalars + 1, 0, sizeof(uint32_t), S->stream));
-        if (side)
-            SH_COMM(sift3d_hip_event_record(S->ev_fork, S->stream) ||
-                    sift3d_hip_stream_wait_event(S->oct_stream, S->ev_fork));
-        for (phase = side ? 1 : 0; phase <= (side ? 2 : 0); phase++) {
-            for (o = 0; o < S->num_octaves; o++) {
-                const sh_level *L = &S->G[o][0];
-                const int nzo = S->dims[o][2];
-                const int zl = (L->z0 > 1 ? L->z0 : 1) - L->off;
-                int zh = (L->z1 < nzo - 1 ? L->z1 : nzo - 1) - L->off;
-                const float *g[SH_MAX_NGL];
-                void *wk = side && o > 0 ? (void *)((char *)S->d_work2 + S->work2_off[o]) : S->d_work;
-                const size_t wb = side && o > 0 ? S->work2_sz[o] : S->work_bytes;
-                if (zh < zl)
-                    zh = zl;
-                for (s = 0; s < S->ngl; s++)
-                    g[s] = S->G[o][s].t;
-                if (L->nloc < 3 || zh <= zl)
-                    continue;                            /* no interior plane on this rank */
-                if (S->dog_free[o]) {
-                    SH_DO(sift3d_hip_extrema_gauss6_phase(g, S->d_scalars + 8 + S->ndl * o, S->dims[o][0],
-                                                          S->dims[o][1], L->nloc, zl, zh, o * S->ngl + 1,
-                                                          S->peak_thresh, S->d_cand, S->cand_cap,
-                                                          (uint32_t *)(S->d_scalars + 1), wk, wb,
-                                                          phase == 1 && o > 0 ? S->oct_stream : S->stream,
-                                                          phase) != SIFT3D_SUCCESS);
-                } else {
-                    sift3d_hip_extrema_level lv[SH_MAX_K];
-                    for (s = 0; s < S->K; s++) {
-                        lv[s].prev = S->D[o][s];
-                        lv[s].cur = S->D[o][s + 1];
-                        lv[s].next = S->D[o][s + 2];
-                        lv[s].d_absmax = S->d_scalars + 8 + S->ndl * o + s + 1;
-                        lv[s].z_lo = zl;
-                        lv[s].z_hi = zh;
-                        lv[s].tag = o * S->ngl + s + 1;          /* Gaussian level (o, s) of the table */
-                    }
-                    SH_DO(sift3d_hip_extrema_mode(lv, S->K, S->dims[o][0], S->dims[o][1], L->nloc, S->peak_thresh,
-                                                  S->cuboid, S->d_cand, S->cand_cap,
-                                                  (uint32_t *)(S->d_scalars + 1), wk, wb, S->stream));
-                }
-            }
-            if (phase == 1)
-                SH_COMM(sift3d_hip_event_record(S->ev_join, S->oct_stream) ||
-                        sift3d_hip_stream_wait_event(S->stream, S->ev_join));
+/* the extrema sweep of octave o on this rank's interior planes: the DoG-free sweep's phase (0: all of it; side by
+ * side 1: the sweep, on chain 1's stream for the octaves >= 1, 2: scan + emission) or, on stored DoG levels,
+ * sift3d_hip_extrema_mode */
+static void sh_sweep_octave(sift3d_amd_sharded *S, int o, int side, int phase)
+{
+    const sh_level *L = &S->G[o][0];
+    const int nzo = S->dims[o][2];
+    const int zl = (L->z0 > 1 ? L->z0 : 1) - L->off, zh = (L->z1 < nzo - 1 ? L->z1 : nzo - 1) - L->off;
+    size_t wb;
+    void *wk = sh_extrema_work(S, o, side, &wb);
+    int s;
+    if (L->nloc < 3 || zh <= zl)
+        return;                              /* no interior plane on this rank */
+    if (S->dog_free[o]) {
+        const float *g[SH_MAX_NGL];
+        sh_level_ptrs(S, o, 0, g);
+        SH_DO(sift3d_hip_extrema_gauss6_phase(g, sh_dogmax_slot(S, o), S->dims[o][0], S->dims[o][1], L->nloc, zl, zh,
+                                              o * S->ngl + 1, S->peak_thresh, S->d_cand, S->cand_cap,
+                                              sh_cand_counter(S), wk, wb,
+                                              phase == 1 && o > 0 ? S->chain[1].stream : S->stream,
+                                              phase) != SIFT3D_SUCCESS);
+    } else {
+        sift3d_hip_extrema_level lv[SH_MAX_K];
+        for (s = 0; s < S->K; s++) {
+            lv[s].prev = S->D[o][s];
+            lv[s].cur = S->D[o][s + 1];
+            lv[s].next = S->D[o][s + 2];
+            lv[s].d_absmax = sh_dogmax_slot(S, o) + s + 1;
+            lv[s].z_lo = zl; lv[s].z_hi = zh;
+            lv[s].tag = o * S->ngl + s + 1;          /* Gaussian level (o, s) of the table */
         }
-        SH_DO(sift3d_hip_memcpy_d2h(&count, S->d_scalars + 1, sizeof(count), S->stream));
+        SH_DO(sift3d_hip_extrema_mode(lv, S->K, S->dims[o][0], S->dims[o][1], L->nloc, S->peak_thresh, S->cuboid,
+                                      S->d_cand, S->cand_cap, sh_cand_counter(S), wk, wb, S->stream));
+    }
+}
+
+/* detect_extrema (sift.c:735-871) on the owned planes: at most two attempts -- a list that does not fit the
+ * candidate arrays is still counted, the arrays are grown to hold it, and the sweeps run once more.  No exchange. */
+static int sh_extrema_stage(sift3d_amd_sharded *S, sh_run *r)
+{
+    /* with every octave on the DoG-free sweep: the sweeps of octaves >= 1 (short launches) beside octave 0's on a
+     * second stream, then scan + emission in octave order (sift3d_hip_extrema_gauss6_phase); otherwise octave by
+     * octave */
+    const int side = r->all_free && S->num_octaves > 1 && S->d_work2 != NULL;
+    int attempt, phase, o;
+    SH_DO(sh_ensure_cand(S, sh_cand_capacity(S)));
+    for (attempt = 0; attempt < 2 && !S->failed; attempt++) {
+        SH_DO(sift3d_hip_memset(sh_cand_counter(S), 0, sizeof(uint32_t), S->stream));
+        if (side)
+            SH_COMM(stream_after(S->chain[1].stream, S->ev_fork, S->stream));
+        for (phase = side ? 1 : 0; phase <= (side ? 2 : 0); phase++) {
+            for (o = 0; o < S->num_octaves; o++)
+                sh_sweep_octave(S, o, side, phase);
+            if (phase == 1)
+                SH_COMM(stream_after(S->stream, S->ev_join, S->chain[1].stream));
+        }
+        SH_DO(sift3d_hip_memcpy_d2h(&r->count, sh_cand_counter(S), sizeof(r->count), S->stream));
         SH_COMM(sift3d_hip_stream_sync(S->stream));
-        if (S->failed || count <= S->cand_cap)
+        if (S->failed || r->count <= S->cand_cap)
             break;
-        SH_DO(sh_ensure_cand(S, count + count / 4 + 1024));
+        SH_DO(sh_ensure_cand(S, r->count + r->count / 4 + 1024));
     }
     if (S->inject == 2)
         S->failed = -2;
     if (S->failed)
-        count = 0;
-    sift3d_hip_event_record(S->ev2, S->stream);
+        r->count = 0;
+    return SIFT3D_SUCCESS;
+}
+
+/* assign_orientations (sift.c:1109-1167) for the local candidates, once the window halos have arrived.  No
+ * exchange (the wait closes sh_window_halos_begin's). */
+static int sh_orient_stage(sift3d_amd_sharded *S, sh_run *r)
+{
+    const int nlev = S->num_octaves * S->ngl;
     if (S->world > 1 && S->o_shard > 0)
-        SH_COMM(sift3d_hip_stream_wait_event(S->stream, S->ev_halo));    /* the window halos have arrived */
+        SH_COMM(sift3d_hip_stream_wait_event(S->stream, S->chain[0].ev_halo));
     /* the serial sums pack window-relative x and y into 10 bits each (sift3d_hip_orient_window_fits) */
-    for (int t = 0; count && !S->failed && t < S->num_octaves * S->ngl; t++) {
+    for (int t = 0; r->count && !S->failed && t < nlev; t++) {
         const sift3d_hip_level *L = S->h_levels + t;
         if (!sift3d_hip_orient_window_fits(L->nx, L->ny, (double)L->ux, (double)L->uy, L->sd)) {
             ERR("sift3d_amd_sharded: the orientation window of a %d x %d level with units (%f, %f) at scale %f is "
                 "wider than 1023 voxels \n", L->nx, L->ny, (double)L->ux, (double)L->uy, L->sd);
             SH_DO(1);
-            count = 0;
+            r->count = 0;
         }
     }
-    if (count) {
-        const size_t need = sift3d_hip_orient_tab_bytes(S->num_octaves * S->ngl, S->cand_cap);
-        if (need > S->otab_bytes) {
-            sift3d_hip_free(S->d_otab);
-            S->otab_bytes = 0;
-            S->d_otab = sift3d_hip_malloc(need);
-            /* zeroed once: the tables carry a validity mark (they are kept between calls) */
-            if (!S->d_otab || sift3d_hip_memset(S->d_otab, 0, need, S->stream))
-                SH_DO(1);
-            else
-                S->otab_bytes = need;
-        }
-        SH_DO(sift3d_hip_orient_tab(S->d_levels, S->num_octaves * S->ngl, S->d_cand, count, S->corner_thresh,
-                                    S->d_R, S->d_keep, S->d_otab, S->cand_cap, S->stream));
+    if (r->count) {
+        SH_DO(orient_tab_reserve(&S->d_otab, &S->otab_bytes, nlev, S->cand_cap, S->stream, 0));
+        SH_DO(sift3d_hip_orient_tab(S->d_levels, nlev, S->d_cand, r->count, S->corner_thresh, S->d_R, S->d_keep,
+                                    S->d_otab, S->cand_cap, S->stream));
         if (S->failed)
-            count = 0;
+            r->count = 0;
     }
-    sift3d_hip_event_record(S->ev3, S->stream);
-    S->t_gather0 = now_s();
+    return SIFT3D_SUCCESS;
+}
 
-    /* The exchange: per-(octave, level) counts, the candidates' |DoG| values and the ORIENTED
-     * keypoints -- device to device: the counts (with this rank's status word behind them) in a first
-     * all-gather, whose result the host needs to size the second; values + records in ONE block per rank in
-     * the second; the global list is then built by a kernel on every rank (sift3d_hip_slab_build: (o, s) major,
-     * ranks in slab order inside a level -- their z ranges are disjoint and ascending --, a rank's own
-     * (z, y, x) order inside its segment) and read back once. */
-    {
-        const size_t cnt_bytes = ((sizeof(int32_t) * 2 * (size_t)nkey + 15) & ~(size_t)15) + 16;
-        const int W = S->world, nseg = nkey * W;
-        int32_t *h_cnt, *h_stat;
-        uint32_t *h_tab;
-        sift3d_amd_slab_layout lay;
-        size_t tot_c, tot_k, roff, toff, blk, tab_words;
-        int any_failed = 0;
-        /* [W blocks gathered][mine] */
-        if (sh_ensure_dev(&S->d_cnt, &S->cnt_cap, cnt_bytes * (size_t)(W + 1)) ||
-            sh_ensure_pinned(&S->h_cnt, &S->hcnt_cap, cnt_bytes * (size_t)W + 64))
-            return SIFT3D_FAILURE;               /* (the exchange buffers themselves: nothing to send in) */
-        h_cnt = (int32_t *)S->h_cnt;
-        h_stat = (int32_t *)((char *)S->h_cnt + cnt_bytes * (size_t)W);      /* two words sent from here */
-        {
-            char *mine = (char *)S->d_cnt + cnt_bytes * (size_t)W;
-            SH_DO(sift3d_hip_slab_count(S->d_cand, S->d_keep, count, S->ngl, S->K, nkey, (int32_t *)mine,
-                                        S->stream));
-            h_stat[0] = S->failed;
-            SH_COMM(sift3d_hip_memcpy_h2d(mine + cnt_bytes - 16, h_stat, sizeof(int32_t), S->stream) ||
-                    sh_allgather_dev(S, mine, S->d_cnt, cnt_bytes) ||
-                    sift3d_hip_memcpy_d2h(h_cnt, S->d_cnt, cnt_bytes * (size_t)W, S->stream) ||
-                    sift3d_hip_stream_sync(S->stream));
-        }
-        for (r = 0; r < W; r++)
-            any_failed |= *(const int32_t *)((const char *)h_cnt + cnt_bytes * (size_t)(r + 1) - 16) != 0;
-        if (any_failed) {
-            if (S->failed)
-                ERR("sift3d_amd_sharded_detect: rank %d failed locally (mark %d) \n", S->rank, S->failed);
-            return SIFT3D_FAILURE;               /* on every rank, here */
-        }
-        /* prefix sums over keys per rank (ck kept, cc candidates), segment starts of the global orders */
-        tab_words = 2 * ((size_t)nseg + 1) + 2 * (size_t)W * (nkey + 1);
-        if (sh_ensure_pinned(&S->h_tab, &S->htab_cap, sizeof(uint32_t) * tab_words) ||
-            sh_ensure_dev(&S->d_tab, &S->tab_cap, sizeof(uint32_t) * tab_words))
-            return SIFT3D_FAILURE;
-        h_tab = (uint32_t *)S->h_tab;
-        if (sift3d_amd_slab_table(h_cnt, cnt_bytes, W, nkey, h_tab, &lay) != SIFT3D_SUCCESS) {
-            ERR("sift3d_amd_sharded_detect: the candidate counts of the %d ranks do not fit 32 bits \n", W);
-            return SIFT3D_FAILURE;               /* on every rank: all of them see the same counts */
-        }
-        tot_c = lay.tot_c; tot_k = lay.tot_k;
-        S->ncand = (int)tot_c;
-        if (S->inject == 3)
-            S->failed = -3;
-        /* this rank's block: [values of all its candidates][its kept records][status word] */
-        roff = lay.roff; toff = lay.toff; blk = lay.blk;
-        if (sh_ensure_dev(&S->d_xchg, &S->xchg_bytes, blk * (size_t)(W + 1)) ||
-            sh_ensure_dev(&S->d_out, &S->out_cap, 64 + 64 * (tot_k ? tot_k : 1)) ||
-            sh_ensure_pinned(&S->h_xchg, &S->hxchg_cap, 64 + 64 * (tot_k ? tot_k : 1)) ||
-            sh_ensure_dev(&S->d_pack, &S->pack_cap, sift3d_hip_slab_pack_scratch_bytes(S->cand_cap)))
-            return SIFT3D_FAILURE;
-        /* keypoint store: dimensions of the first octave (sift.c:756-759) */
-        kp->nx = S->nx; kp->ny = S->ny; kp->nz = S->nz;
-        SH_DO(kp_store_resize(kp, tot_k));
-        {
-            char *mine = (char *)S->d_xchg + blk * (size_t)W;
-            SH_DO(sift3d_hip_memcpy_h2d(S->d_tab, h_tab, sizeof(uint32_t) * tab_words, S->stream));
-            SH_DO(sift3d_hip_slab_pack(S->d_levels, S->d_cand, S->d_keep, S->d_R, count, S->ngl, (float *)mine,
-                                       mine + roff, S->d_pack, S->stream));
-            h_stat[1] = S->failed;
-            SH_COMM(sift3d_hip_memcpy_h2d(mine + toff, h_stat + 1, sizeof(int32_t), S->stream) ||
-                    sh_allgather_dev(S, mine, S->d_xchg, blk));
-            /* (copy_Keypoint omits `strength`, sift.c:372-384: slot j keeps GLOBAL candidate j's value) */
-            SH_DO(sift3d_hip_slab_build(S->d_xchg, blk, roff, toff, W, nkey, (const uint32_t *)S->d_tab,
-                                        (uint32_t)tot_k, (uint32_t)tot_c, S->d_out, S->stream));
-            SH_COMM(sift3d_hip_memcpy_d2h(S->h_xchg, S->d_out, 64 + 64 * tot_k, S->stream) ||
-                    sift3d_hip_stream_sync(S->stream));
-        }
-        if (S->failed || *(const int32_t *)S->h_xchg != 0) {
-            if (S->failed)
-                ERR("sift3d_amd_sharded_detect: rank %d failed locally (mark %d) \n", S->rank, S->failed);
-            return SIFT3D_FAILURE;               /* on every rank: the status words are in everybody's list */
-        }
-        {
-            /* the records into the store: a few threads, each on a contiguous part; a segment holds one
-             * (octave, level), i.e. one scale (imutil.c:1578-1579) */
-            const sh_out *rec = (const sh_out *)((const char *)S->h_xchg + 64);
-            const int nt = host_threads(tot_k);
-            double sdk[256];
-            for (k = 0; k < nkey; k++)
-                sdk[k] = sh_scale(S, k / S->K, k % S->K);
+/* The exchange of the keypoints: per-(octave, level) counts, the candidates' |DoG| values and the
+ * ORIENTED keypoints -- device to device.  First the counts, with this rank's status word behind them: the host
+ * needs the result to size the second all-gather.  EXCHANGE: all-gather of cnt_bytes per rank, main stream.
+ * Returns failure, on every rank, when any rank has failed so far. */
+static int sh_exchange_counts(sift3d_amd_sharded *S, sh_run *r)
+{
+    const int W = S->world;
+    char *mine;
+    int32_t *h_stat;
+    int q, any_failed = 0;
+    r->cnt_bytes = ((sizeof(int32_t) * 2 * (size_t)r->nkey + 15) & ~(size_t)15) + 16;
+    /* [W blocks gathered][mine] */
+    if (sh_ensure_dev(&S->d_cnt, &S->cnt_cap, r->cnt_bytes * (size_t)(W + 1)) ||
+        sh_ensure_pinned(&S->h_cnt, &S->hcnt_cap, r->cnt_bytes * (size_t)W + 64))
+        return SIFT3D_FAILURE;               /* (the exchange buffers themselves: nothing to send in) */
+    mine = (char *)S->d_cnt + r->cnt_bytes * (size_t)W;
+    h_stat = sh_status_words(S, r);
+    SH_DO(sift3d_hip_slab_count(S->d_cand, S->d_keep, r->count, S->ngl, S->K, r->nkey, (int32_t *)mine, S->stream));
+    h_stat[0] = S->failed;
+    SH_COMM(sift3d_hip_memcpy_h2d(mine + r->cnt_bytes - 16, h_stat, sizeof(int32_t), S->stream) ||
+            sh_allgather_dev(S, mine, S->d_cnt, r->cnt_bytes) ||
+            sift3d_hip_memcpy_d2h(S->h_cnt, S->d_cnt, r->cnt_bytes * (size_t)W, S->stream) ||
+            sift3d_hip_stream_sync(S->stream));
+    for (q = 0; q < W; q++)
+        any_failed |= *(const int32_t *)((const char *)S->h_cnt + r->cnt_bytes * (size_t)(q + 1) - 16) != 0;
+    if (any_failed)
+        sh_report_local_failure(S);
+    return any_failed ? SIFT3D_FAILURE : SIFT3D_SUCCESS;
+}
+
+/* Then values + records in ONE block per rank; the global list is built by a kernel on every rank
+ * (sift3d_hip_slab_build: (o, s) major, ranks in slab order inside a level -- their z ranges are disjoint and
+ * ascending --, a rank's own (z, y, x) order inside its segment) and read back once.  EXCHANGE: all-gather of
+ * lay.blk bytes per rank, main stream.  Returns failure, on every rank, when any rank has failed. */
+static int sh_exchange_records(sift3d_amd_sharded *S, sh_run *r, sift3d_keypoint_store *kp)
+{
+    const int W = S->world;
+    const sift3d_amd_slab_layout *lay = &r->lay;
+    int32_t *h_stat = sh_status_words(S, r);
+    char *mine;
+    /* prefix sums over keys per rank (ck kept, cc candidates), segment starts of the global orders */
+    r->tab_words = 2 * ((size_t)r->nkey * W + 1) + 2 * (size_t)W * (r->nkey + 1);
+    if (sh_ensure_pinned(&S->h_tab, &S->htab_cap, sizeof(uint32_t) * r->tab_words) ||
+        sh_ensure_dev(&S->d_tab, &S->tab_cap, sizeof(uint32_t) * r->tab_words))
+        return SIFT3D_FAILURE;
+    if (sift3d_amd_slab_table(S->h_cnt, r->cnt_bytes, W, r->nkey, (uint32_t *)S->h_tab, &r->lay) != SIFT3D_SUCCESS) {
+        ERR("sift3d_amd_sharded_detect: the candidate counts of the %d ranks do not fit 32 bits \n", W);
+        return SIFT3D_FAILURE;               /* on every rank: all of them see the same counts */
+    }
+    S->ncand = (int)lay->tot_c;
+    if (S->inject == 3)
+        S->failed = -3;
+    /* this rank's block: [values of all its candidates][its kept records][status word] */
+    if (sh_ensure_dev(&S->d_xchg, &S->xchg_bytes, lay->blk * (size_t)(W + 1)) ||
+        sh_ensure_dev(&S->d_out, &S->out_cap, 64 + 64 * (lay->tot_k ? lay->tot_k : 1)) ||
+        sh_ensure_pinned(&S->h_xchg, &S->hxchg_cap, 64 + 64 * (lay->tot_k ? lay->tot_k : 1)) ||
+        sh_ensure_dev(&S->d_pack, &S->pack_cap, sift3d_hip_slab_pack_scratch_bytes(S->cand_cap)))
+        return SIFT3D_FAILURE;
+    /* keypoint store: dimensions of the first octave (sift.c:756-759) */
+    kp->nx = S->nx; kp->ny = S->ny; kp->nz = S->nz;
+    SH_DO(kp_store_resize(kp, lay->tot_k));
+    mine = (char *)S->d_xchg + lay->blk * (size_t)W;
+    SH_DO(sift3d_hip_memcpy_h2d(S->d_tab, S->h_tab, sizeof(uint32_t) * r->tab_words, S->stream));
+    SH_DO(sift3d_hip_slab_pack(S->d_levels, S->d_cand, S->d_keep, S->d_R, r->count, S->ngl, (float *)mine,
+                               mine + lay->roff, S->d_pack, S->stream));
+    h_stat[1] = S->failed;
+    SH_COMM(sift3d_hip_memcpy_h2d(mine + lay->toff, h_stat + 1, sizeof(int32_t), S->stream) ||
+            sh_allgather_dev(S, mine, S->d_xchg, lay->blk));
+    /* (copy_Keypoint omits `strength`, sift.c:372-384: slot j keeps GLOBAL candidate j's value) */
+    SH_DO(sift3d_hip_slab_build(S->d_xchg, lay->blk, lay->roff, lay->toff, W, r->nkey, (const uint32_t *)S->d_tab,
+                                (uint32_t)lay->tot_k, (uint32_t)lay->tot_c, S->d_out, S->stream));
+    SH_COMM(sift3d_hip_memcpy_d2h(S->h_xchg, S->d_out, 64 + 64 * lay->tot_k, S->stream) ||
+            sift3d_hip_stream_sync(S->stream));
+    if (S->failed || *(const int32_t *)S->h_xchg != 0) {
+        sh_report_local_failure(S);
+        return SIFT3D_FAILURE;               /* on every rank: the status words are in everybody's list */
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* the records into the store: a few threads, each on a contiguous part; a segment holds one (octave, level),
+ * i.e. one scale (imutil.c:1578-1579) */
+static void sh_fill_store(const sift3d_amd_sharded *S, const sh_run *r, sift3d_keypoint_store *kp)
+{
+    const sh_out *rec = (const sh_out *)((const char *)S->h_xchg + 64);
+    const size_t tot_k = r->lay.tot_k;
+    const int nt = host_threads(tot_k);
+    double sdk[256];
+    int k;
+    for (k = 0; k < r->nkey; k++)
+        sdk[k] = sh_scale(S, k / S->K, k % S->K);
 #pragma omp parallel num_threads(nt)
-            {
-                const int nth = omp_get_num_threads(), t = omp_get_thread_num();   /* (the team's real size) */
-                const size_t lo = tot_k * (size_t)t / nth, hi = tot_k * (size_t)(t + 1) / nth;
-                size_t g;
-                for (g = lo; g < hi; g++) {
-                    keypoint_t *kk = kp->buf + g;
-                    kk->o = rec[g].o; kk->s = rec[g].s;
-                    kk->xd = rec[g].x; kk->yd = rec[g].y; kk->zd = rec[g].z;
-                    kk->sd = sdk[rec[g].o * S->K + rec[g].s];
-                    memcpy(kk->R, rec[g].R, sizeof(kk->R));
-                    kk->strength = rec[g].strength;
-                }
-            }
+    {
+        const int nth = omp_get_num_threads(), t = omp_get_thread_num();   /* (the team's real size) */
+        const size_t lo = tot_k * (size_t)t / nth, hi = tot_k * (size_t)(t + 1) / nth;
+        size_t g;
+        for (g = lo; g < hi; g++) {
+            keypoint_t *kk = kp->buf + g;
+            kk->o = rec[g].o; kk->s = rec[g].s;
+            kk->xd = rec[g].x; kk->yd = rec[g].y; kk->zd = rec[g].z;
+            kk->sd = sdk[rec[g].o * S->K + rec[g].s];
+            memcpy(kk->R, rec[g].R, sizeof(kk->R));
+            kk->strength = rec[g].strength;
         }
     }
-    S->t[0] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev0, S->ev1);
-    S->t[3] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev1, S->ev2);
-    S->t[4] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev2, S->ev3);
+}
+
+/* the call's timers: S->t[] as the struct says, from the marks the driver recorded between the stages */
+static void sh_end(sift3d_amd_sharded *S, const sh_run *r)
+{
+    S->t[0] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev[0], S->ev[1]);
+    S->t[3] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev[1], S->ev[2]);
+    S->t[4] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev[2], S->ev[3]);
     S->t[5] = now_s() - S->t_gather0;
-    S->t[6] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev4, S->ev0);
-    S->t[1] = now_s() - t_start;
+    S->t[6] = 1e-3 * sift3d_hip_event_elapsed_ms(S->ev[4], S->ev[0]);
+    S->t[1] = now_s() - r->t_start;
+}
+
+/* One detect call: the stages in the order in which they issue their exchanges (each stage's comment names its
+ * own; DESIGN.md section 5 has the whole list), with the marks of the stage timers between them. */
+int sift3d_amd_sharded_detect(sift3d_amd_sharded *S, sift3d_keypoint_store *kp)
+{
+    sh_run r;
+    if (sh_begin(S, kp, &r))
+        return SIFT3D_FAILURE;
+    sift3d_hip_event_record(S->ev[0], S->stream);
+    if (sh_pyramid(S))
+        return SIFT3D_FAILURE;
+    sift3d_hip_event_record(S->ev[1], S->stream);
+    if (sh_nearest_halos(S) || sh_dog_stage(S) || sh_window_halos_begin(S) || sh_extrema_stage(S, &r))
+        return SIFT3D_FAILURE;
+    sift3d_hip_event_record(S->ev[2], S->stream);
+    if (sh_orient_stage(S, &r))
+        return SIFT3D_FAILURE;
+    sift3d_hip_event_record(S->ev[3], S->stream);
+    S->t_gather0 = now_s();
+    if (sh_exchange_counts(S, &r) || sh_exchange_records(S, &r, kp))
+        return SIFT3D_FAILURE;
+    sh_fill_store(S, &r, kp);
+    sh_end(S, &r);
     return SIFT3D_SUCCESS;
 }
 
 /* ---- describe ------------------------------------------------------------------------------ */
+enum { SH_LVM = 16 };     /* keypoint levels per octave that sh_order_keypoints has buckets for */
+typedef char sh_levels_fit_the_buckets[SH_MAX_K <= SH_LVM ? 1 : -1];
+
+static inline int sh_level_missing(const sift3d_amd_sharded *S, const keypoint_t *k)
+{
+    return k->o < 0 || k->o >= S->num_octaves || k->s < 0 || k->s >= S->K;
+}
+
+/* The keypoints this rank owns, in list order, into own_idx: counted and placed by a few threads, each on a
+ * contiguous part of the list.  Returns their number, or -1 for a list with a level the pyramid does not have. */
+static int sh_own_keypoints(const sift3d_amd_sharded *S, const sift3d_keypoint_store *kp, int *own_idx)
+{
+    const size_t num = kp->num;
+    const int nt = host_threads(num);
+    size_t pre[HOST_THREADS_MAX + 1], total = 0;
+    int bad = 0;
+    pre[0] = 0;
+#pragma omp parallel num_threads(nt) reduction(| : bad)
+    {
+        const int nth = omp_get_num_threads(), t = omp_get_thread_num();  /* (the team's real size) */
+        const size_t lo = num * t / nth, hi = num * (t + 1) / nth;
+        size_t q, jj = 0;
+        for (q = lo; q < hi; q++) {
+            if (sh_level_missing(S, kp->buf + q))
+                bad = 1;
+            else
+                jj += sh_owner(S, kp->buf + q) == S->rank;
+        }
+        pre[t + 1] = jj;
+#pragma omp barrier
+#pragma omp single
+        {
+            int u;
+            for (u = 0; u < nth; u++)
+                pre[u + 1] += pre[u];
+            total = pre[nth];
+        }
+        /* (implicit barrier) */
+        jj = pre[t];
+        for (q = lo; q < hi; q++)
+            if (!sh_level_missing(S, kp->buf + q) && sh_owner(S, kp->buf + q) == S->rank)
+                own_idx[jj++] = (int)q;
+    }
+    return bad ? -1 : (int)total;
+}
+
+/* Launch order of this rank's n keypoints: widest windows first, each histogram to its own row (a stable counting
+ * sort by level, as order_keypoints of the single-GPU driver, but with ONE threshold for all of a level: the
+ * first level that takes the reference-order kernel).  Fills S->h_kp and the rows' coordinates; returns the
+ * number of keypoints of the reference-order kernel, which lead the list. */
+static size_t sh_order_keypoints(sift3d_amd_sharded *S, const sift3d_keypoint_store *kp, const int *own_idx, int n,
+                                 sift3d_descriptor_store *desc)
+{
+    const int nt = host_threads((size_t)n);
+    /* (Gaussian index of the first level that takes the reference-order kernel; keypoint level s has
+     * Gaussian index s + 1) */
+    const int s_exact = exact_desc_first_level(S->exact_desc, S->ngl, S->K, S->sigma0, S->units) - 1;
+    size_t cnt[HOST_THREADS_MAX][SH_LVM], start[HOST_THREADS_MAX][SH_LVM], n_exact = 0;
+    memset(cnt, 0, sizeof(cnt));
+#pragma omp parallel num_threads(nt)
+    {
+        const int nth = omp_get_num_threads(), t = omp_get_thread_num();
+        const size_t lo = (size_t)n * t / nth, hi = (size_t)n * (t + 1) / nth;
+        size_t q;
+        for (q = lo; q < hi; q++)
+            cnt[t][kp->buf[own_idx[q]].s]++;
+#pragma omp barrier
+#pragma omp single
+        {
+            size_t p = 0;
+            int lv, u;
+            for (lv = S->K - 1; lv >= 0; lv--) {
+                if (lv == s_exact - 1)
+                    n_exact = p;           /* (widest windows first: the exact ones lead the list) */
+                for (u = 0; u < nth; u++) {
+                    start[u][lv] = p;
+                    p += cnt[u][lv];
+                }
+            }
+            if (s_exact <= 0)
+                n_exact = p;
+        }
+        /* (implicit barrier) */
+        for (q = lo; q < hi; q++)
+            describe_record(S->h_kp + start[t][kp->buf[own_idx[q]].s]++, kp->buf + own_idx[q], S->ngl, q);
+        desc_store_fill_xyzsd(desc, kp->buf, own_idx, lo, hi);
+    }
+    return n_exact;
+}
+
 /* Descriptors of the keypoints this rank owns (by z).  own_idx (capacity: the number of
  * keypoints) receives their positions in `kp`; desc their descriptors in that order.  The union
- * over ranks covers every keypoint exactly once. */
+ * over ranks covers every keypoint exactly once.  No exchange. */
 int sift3d_amd_sharded_describe(sift3d_amd_sharded *S, const sift3d_keypoint_store *kp,
                                 sift3d_descriptor_store *desc, int *own_idx, int *n_own)
 {
     const double t_start = now_s();
-    int n = 0, num;
-    size_t n_exact = 0;
+    size_t n_exact;
+    int n;
     if (!S || !kp || !desc || !own_idx || !n_own)
         return SIFT3D_FAILURE;
-    num = (int)kp->num;
-    {
-        /* the keypoints this rank owns, in list order: counted and placed by a few threads, each on a
-         * contiguous part of the list */
-        const int nt = host_threads((size_t)num);
-        size_t pre[HOST_THREADS_MAX + 1], total = 0;
-        int bad = 0;
-        pre[0] = 0;
-#pragma omp parallel num_threads(nt) reduction(| : bad)
-        {
-            const int nth = omp_get_num_threads(), t = omp_get_thread_num();  /* (the team's real size) */
-            const size_t lo = (size_t)num * t / nth, hi = (size_t)num * (t + 1) / nth;
-            size_t q, jj = 0;
-#define SH_OWN(k_) (S->world == 1 || ((k_)->zd >= (double)S->bounds[(k_)->o][S->rank] &&          \
-                                      (k_)->zd < (double)S->bounds[(k_)->o][S->rank + 1]))
-            for (q = lo; q < hi; q++) {
-                const keypoint_t *k = kp->buf + q;
-                if (k->o < 0 || k->o >= S->num_octaves || k->s < 0 || k->s >= S->K) {
-                    bad = 1;
-                    continue;
-                }
-                jj += SH_OWN(k) ? 1 : 0;
-            }
-            pre[t + 1] = jj;
-#pragma omp barrier
-#pragma omp single
-            {
-                int u;
-                for (u = 0; u < nth; u++)
-                    pre[u + 1] += pre[u];
-                total = pre[nth];
-            }
-            /* (implicit barrier) */
-            jj = pre[t];
-            for (q = lo; q < hi; q++) {
-                const keypoint_t *k = kp->buf + q;
-                if (k->o < 0 || k->o >= S->num_octaves || k->s < 0 || k->s >= S->K)
-                    continue;
-                if (SH_OWN(k))
-                    own_idx[jj++] = (int)q;
-            }
-#undef SH_OWN
-        }
-        if (bad)
-            return SIFT3D_FAILURE;
-        n = (int)total;
-    }
+    n = sh_own_keypoints(S, kp, own_idx);
+    if (n < 0)
+        return SIFT3D_FAILURE;
     *n_own = n;
-    desc->nx = S->nx; desc->ny = S->ny; desc->nz = S->nz;
-    if (!desc->pinned || (size_t)n > desc->cap) {
-        const size_t cap = (size_t)n + (size_t)n / 8 + 64;
-        desc_store_release(desc);
-        desc->hist = (float *)sift3d_hip_host_alloc(sizeof(float) * DESC_NUMEL * cap);
-        desc->xyzsd = (double *)malloc(sizeof(double) * 4 * cap);
-        if (!desc->hist || !desc->xyzsd) {
-            desc->pinned = desc->hist != NULL;
-            desc_store_release(desc);
-            return SIFT3D_FAILURE;
-        }
-        desc->pinned = 1;
-        desc->cap = cap;
-    }
-    desc->num = (size_t)n;
-    desc->d_num = 0;                 /* (rows are rewritten: a device copy kept by an earlier call is stale) */
+    if (desc_store_reserve(desc, (size_t)n, S->nx, S->ny, S->nz))
+        return SIFT3D_FAILURE;
     if (!n)
         return SIFT3D_SUCCESS;
-    if ((uint32_t)n > S->kp_cap) {
-        const uint32_t cap = (uint32_t)n + (uint32_t)n / 4 + 256;
-        sift3d_hip_host_free(S->h_kp);
-        S->kp_cap = 0;
-        S->h_kp = (sift3d_hip_kp *)sift3d_hip_host_alloc(sizeof(sift3d_hip_kp) * (size_t)cap);
-        if (!S->h_kp)
-            return SIFT3D_FAILURE;
-        S->kp_cap = cap;
-    }
-    /* launch order: widest windows first, each histogram to its own row (a stable counting sort by level,
-     * as in sift3d_extract_descriptors) */
-    {
-        enum { LVM = 16 };
-        const int nt = host_threads((size_t)n);
-        /* (Gaussian index of the first level that takes the reference-order kernel; keypoint level s has
-         * Gaussian index s + 1) */
-        const int s_exact = exact_desc_first_level(S->exact_desc, S->ngl, S->K, S->sigma0, S->units) - 1;
-        size_t cnt[HOST_THREADS_MAX][LVM], start[HOST_THREADS_MAX][LVM];
-        if (S->K > LVM)
-            return SIFT3D_FAILURE;
-        memset(cnt, 0, sizeof(cnt));
-#pragma omp parallel num_threads(nt)
-        {
-            const int nth = omp_get_num_threads(), t = omp_get_thread_num();
-            const size_t lo = (size_t)n * t / nth, hi = (size_t)n * (t + 1) / nth;
-            size_t q;
-            for (q = lo; q < hi; q++)
-                cnt[t][kp->buf[own_idx[q]].s]++;
-#pragma omp barrier
-#pragma omp single
-            {
-                size_t p = 0;
-                int lv, u;
-                for (lv = S->K - 1; lv >= 0; lv--) {
-                    if (lv == s_exact - 1)
-                        n_exact = p;           /* (widest windows first: the exact ones lead the list) */
-                    for (u = 0; u < nth; u++) {
-                        start[u][lv] = p;
-                        p += cnt[u][lv];
-                    }
-                }
-                if (s_exact <= 0)
-                    n_exact = p;
-            }
-            /* (implicit barrier) */
-            for (q = lo; q < hi; q++) {
-                const keypoint_t *k = kp->buf + own_idx[q];
-                const double f = ldexp(1.0, k->o);                 /* sift.c:1459, 1530-1533 */
-                sift3d_hip_kp *r = S->h_kp + start[t][k->s]++;
-                memcpy(r->R, k->R, sizeof(r->R));
-                r->cx = (float)k->xd; r->cy = (float)k->yd; r->cz = (float)k->zd;   /* sift.c:1474-1476 */
-                r->level = k->o * S->ngl + k->s + 1;
-                r->row1 = (uint32_t)q + 1u;
-                r->sd = k->sd;
-                desc->xyzsd[4 * q] = k->xd * f;
-                desc->xyzsd[4 * q + 1] = k->yd * f;
-                desc->xyzsd[4 * q + 2] = k->zd * f;
-                desc->xyzsd[4 * q + 3] = k->sd;
-            }
-        }
-    }
-    {
-        /* (the kernel reads a keypoint's record once, as its wave starts: from the page-locked list in place) */
-        float *dev_view = (float *)sift3d_hip_host_device_ptr(desc->hist);
-        const sift3d_hip_kp *kp_view = (const sift3d_hip_kp *)sift3d_hip_host_device_ptr(S->h_kp);
-        const size_t need = sift3d_hip_describe_part_bytes((uint32_t)n - (uint32_t)n_exact);
-        if (need > S->dpart_bytes) {
-            sift3d_hip_free(S->d_dpart);
-            S->dpart_bytes = 0;
-            S->d_dpart = sift3d_hip_malloc(need + need / 8);
-            if (!S->d_dpart)
-                return SIFT3D_FAILURE;
-            S->dpart_bytes = need + need / 8;
-        }
-        if (!dev_view || !kp_view ||
-            sift3d_hip_describe_lattice_a32(S->d_levels, S->num_octaves * S->ngl, kp_view, (uint32_t)n,
-                                            (uint32_t)n_exact, 0, dev_view, NULL, S->d_wlut,
-                                            need ? S->d_dpart : NULL, S->stream,
-                                            sift3d_hip_describe_addr32_records(S->h_levels, S->num_octaves * S->ngl,
-                                                                               S->h_kp, (uint32_t)n)) ||
-            sift3d_hip_stream_sync(S->stream))
-            return SIFT3D_FAILURE;
-    }
+    if (describe_list_reserve(&S->h_kp, &S->kp_cap, (uint32_t)n))
+        return SIFT3D_FAILURE;
+    n_exact = sh_order_keypoints(S, kp, own_idx, n, desc);
+    /* (no lattice variant, no rows in device memory) */
+    if (describe_enqueue(S->d_levels, S->h_levels, S->num_octaves * S->ngl, S->h_kp, (uint32_t)n, (uint32_t)n_exact,
+                         0, desc, NULL, S->d_wlut, &S->d_dpart, &S->dpart_bytes, S->stream) ||
+        sift3d_hip_stream_sync(S->stream))
+        return SIFT3D_FAILURE;
     S->t[2] = now_s() - t_start;
     return SIFT3D_SUCCESS;
 }
 
 /* ---- descriptor gather ("computed by the owning rank and gathered (N x 771 f32)") ---- */
+/* EXCHANGE: one all-gather of the ranks' row blocks (padded to the largest, status word behind), main stream. */
 int sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *S, const sift3d_keypoint_store *kp,
                                           const sift3d_descriptor_store *own, const int *own_idx, int n_own,
                                           sift3d_descriptor_store *all, int root)
@@ -1311,7 +1374,7 @@ int sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *S, const sift3d_ke
     size_t cnt[SH_MAX_WORLD];
     uint32_t *map = NULL;
     int32_t *h_stat;
-    int r, want, failed = 0, any = 0;
+    int r, want, failed = 0, any = 0, rc = SIFT3D_FAILURE;
     if (!S || !kp || !own || !all || (n_own > 0 && !own_idx) || root >= W)
         return SIFT3D_FAILURE;
     num = kp->num;
@@ -1319,7 +1382,7 @@ int sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *S, const sift3d_ke
     if (S->inject == 4)
         failed = -4;
     /* who owns which keypoint follows from the list and the slab bounds: every rank derives every rank's
-     * rows (the rule of sift3d_amd_sharded_describe) */
+     * rows (sh_owner, the rule of sift3d_amd_sharded_describe) */
     memset(cnt, 0, sizeof(cnt));
     map = (uint32_t *)malloc(sizeof(uint32_t) * (num ? num : 1));
     if (!map)
@@ -1327,17 +1390,14 @@ int sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *S, const sift3d_ke
     /* (the counts size the exchange: every rank must arrive at the same ones, whatever failed locally) */
     for (q = 0; q < num; q++) {
         const keypoint_t *k = kp->buf + q;
-        int rr = 0;
+        int rr;
         if (k->o < 0 || k->o >= S->num_octaves) {
             failed = failed ? failed : __LINE__;       /* (the list is the same on every rank) */
             if (map)
                 map[q] = 0;
             continue;
         }
-        if (W > 1)
-            for (rr = 0; rr < W - 1; rr++)
-                if (k->zd < (double)S->bounds[k->o][rr + 1])
-                    break;
+        rr = sh_owner(S, k);
         if (map)
             map[q] = ((uint32_t)rr << 24) | (uint32_t)(cnt[rr] & 0xffffffu);
         cnt[rr]++;
@@ -1346,17 +1406,15 @@ int sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *S, const sift3d_ke
         if (cnt[r] > maxn)
             maxn = cnt[r];
     if (maxn >= (1u << 24))
-        return SIFT3D_FAILURE;                         /* (the same on every rank) */
+        goto done;                                     /* (the same on every rank) */
     if (!failed && (size_t)(n_own < 0 ? 0 : n_own) != cnt[S->rank])
         failed = __LINE__;                             /* desc_own is not this rank's describe result */
     if (!failed && (own->num != cnt[S->rank] || (cnt[S->rank] && !own->hist)))
         failed = __LINE__;
     blk = DESC_NUMEL * sizeof(float) * (maxn ? maxn : 1) + 16;
     if (sh_ensure_dev(&S->d_gath, &S->gath_cap, blk * (size_t)(W + 1)) ||
-        sh_ensure_pinned(&S->h_cnt, &S->hcnt_cap, 16 * (size_t)W + 64)) {
-        free(map);
-        return SIFT3D_FAILURE;                         /* (the exchange buffers themselves) */
-    }
+        sh_ensure_pinned(&S->h_cnt, &S->hcnt_cap, 16 * (size_t)W + 64))
+        goto done;                                     /* (the exchange buffers themselves) */
     h_stat = (int32_t *)((char *)S->h_cnt + 16 * (size_t)W);
     {
         char *mine = (char *)S->d_gath + blk * (size_t)W;
@@ -1367,68 +1425,37 @@ int sift3d_amd_sharded_gather_descriptors(sift3d_amd_sharded *S, const sift3d_ke
         if (sift3d_hip_memcpy_h2d(mine + blk - 16, h_stat, sizeof(int32_t), S->stream) ||
             sh_allgather_dev(S, mine, S->d_gath, blk) ||
             sift3d_hip_memcpy2d_d2h(S->h_cnt, 16, (char *)S->d_gath + blk - 16, blk, 16, (size_t)W, S->stream) ||
-            sift3d_hip_stream_sync(S->stream)) {
-            free(map);
-            return SIFT3D_FAILURE;
-        }
+            sift3d_hip_stream_sync(S->stream))
+            goto done;
     }
     for (r = 0; r < W; r++)
         any |= *(const int32_t *)((const char *)S->h_cnt + 16 * (size_t)r) != 0;
     if (any) {
         if (failed)
             ERR("sift3d_amd_sharded_gather_descriptors: rank %d failed locally (mark %d) \n", S->rank, failed);
-        free(map);
-        return SIFT3D_FAILURE;                         /* on every rank, here */
+        goto done;                                     /* on every rank, here */
     }
-    if (want && !map)
-        return SIFT3D_FAILURE;                         /* (unreachable: a missing map was reported above) */
-    if (want) {
+    if (want && (!map || desc_store_reserve(all, num, S->nx, S->ny, S->nz)))
+        goto done;                                     /* (no map: reported above, so not reached with one) */
+    rc = SIFT3D_SUCCESS;
+    if (want && num) {
         /* rows into the global order on the device, one copy into the store's page-locked array */
-        const size_t cap = num + num / 8 + 64;
-        void *d_map = NULL, *d_rows = NULL;
-        int rc = SIFT3D_SUCCESS;
-        if (!all->pinned || num > all->cap) {
-            desc_store_release(all);
-            all->hist = (float *)sift3d_hip_host_alloc(sizeof(float) * DESC_NUMEL * cap);
-            all->xyzsd = (double *)malloc(sizeof(double) * 4 * cap);
-            if (!all->hist || !all->xyzsd) {
-                all->pinned = all->hist != NULL;
-                desc_store_release(all);
-                free(map);
-                return SIFT3D_FAILURE;
-            }
-            all->pinned = 1;
-            all->cap = cap;
-        }
-        all->nx = S->nx; all->ny = S->ny; all->nz = S->nz;
-        all->num = num;
-        all->d_num = 0;
-        if (num) {
-            d_map = sift3d_hip_malloc(sizeof(uint32_t) * num);
-            d_rows = sift3d_hip_malloc(sizeof(float) * DESC_NUMEL * num);
-            if (!d_map || !d_rows ||
-                sift3d_hip_memcpy_h2d(d_map, map, sizeof(uint32_t) * num, S->stream) ||
-                sift3d_hip_rows_scatter((float *)d_rows, S->d_gath, blk, (const uint32_t *)d_map, (uint32_t)num,
-                                        S->stream) ||
-                sift3d_hip_memcpy_d2h(all->hist, d_rows, sizeof(float) * DESC_NUMEL * num, S->stream) ||
-                sift3d_hip_stream_sync(S->stream))
-                rc = SIFT3D_FAILURE;
-            sift3d_hip_free(d_map);
-            sift3d_hip_free(d_rows);
-        }
-        for (q = 0; q < num; q++) {
-            const keypoint_t *k = kp->buf + q;
-            const double f = ldexp(1.0, k->o);             /* sift.c:1459, 1530-1533 */
-            all->xyzsd[4 * q] = k->xd * f;
-            all->xyzsd[4 * q + 1] = k->yd * f;
-            all->xyzsd[4 * q + 2] = k->zd * f;
-            all->xyzsd[4 * q + 3] = k->sd;
-        }
-        free(map);
-        return rc;
+        void *d_map = sift3d_hip_malloc(sizeof(uint32_t) * num);
+        void *d_rows = sift3d_hip_malloc(sizeof(float) * DESC_NUMEL * num);
+        if (!d_map || !d_rows ||
+            sift3d_hip_memcpy_h2d(d_map, map, sizeof(uint32_t) * num, S->stream) ||
+            sift3d_hip_rows_scatter((float *)d_rows, S->d_gath, blk, (const uint32_t *)d_map, (uint32_t)num,
+                                    S->stream) ||
+            sift3d_hip_memcpy_d2h(all->hist, d_rows, sizeof(float) * DESC_NUMEL * num, S->stream) ||
+            sift3d_hip_stream_sync(S->stream))
+            rc = SIFT3D_FAILURE;
+        sift3d_hip_free(d_map);
+        sift3d_hip_free(d_rows);
+        desc_store_fill_xyzsd(all, kp->buf, NULL, 0, num);
     }
+done:
     free(map);
-    return SIFT3D_SUCCESS;
+    return rc;
 }
 
 /* ---- RCCL transport (librccl is loaded at run time: single-GPU users do not need it) -------- */

@@ -271,12 +271,18 @@ def _run_thread_ranks(world, dims, transport, det_kw=None, seed=5, synth_on_devi
 @pytest.mark.parametrize("world,dims,det_kw", [
     (2, (64, 72, 256), None), (3, (48, 48, 320), None), (4, (64, 64, 512), None),
     (2, (130, 126, 244), None), (2, (64, 72, 256), dict(cuboid_extrema=True)),
-    (3, (50, 46, 330), dict(num_kp_levels=4, cuboid_extrema=True, peak_thresh=0.05))])
+    (3, (50, 46, 330), dict(num_kp_levels=4, cuboid_extrema=True, peak_thresh=0.05)),
+    # the describe launch lists: at sigma0 = 2 the keypoints of level s = 2 (sd / 2^o = 3.175, a window above
+    # exact_desc_first_level's 1.9e5 voxels) take the reference-order kernel and the others the fast one, so
+    # both ranks launch with 0 < n_exact < n (the CPU oracle: 262 keypoints, 54 of them at s = 2, 9 and 6 of
+    # those in the two halves of octave 0); with exact_descriptors = 1 all do, and there is no part scratch
+    (2, (64, 72, 256), dict(sigma0=2.0)), (2, (64, 72, 256), dict(exact_descriptors=1))])
 def test_c_slab_driver_over_stream_ordered_transport(world, dims, det_kw):
     """The configurations of test_c_slab_driver_equals_single_gpu with the exchanges ordered by HIP
     events ALONE (sift3d_thread_transport.c: what ncclSend/ncclRecv guarantee and no more): every halo
     exchange on the communication stream must be fenced against the chain streams that produce and
-    consume its planes by the driver's own events -- a missing edge is a bit difference here."""
+    consume its planes by the driver's own events -- a missing edge is a bit difference here.  Two more
+    cases pin the slab driver's mixed and all-exact descriptor lists."""
     import torch
     from sift3d_amd import api
     if not torch.cuda.is_available():
@@ -288,13 +294,60 @@ def test_c_slab_driver_over_stream_ordered_transport(world, dims, det_kw):
     assert det.extract_descriptors(kp, desc) == 0
     k, m = kp.records(), desc.to_mat_rm()
     assert len(k) > 5
+    if det_kw and "sigma0" in det_kw:
+        # both kernels have work: level s = 2 is the exact one's, the levels below it the fast one's
+        assert (k["s"] == 2).any() and (k["s"] < 2).any()
     covered = np.zeros(len(k), int)
     for g in res:
         assert g["ncand"] == det.num_candidates() and g["o_shard"] >= 1
         for f in ("o", "s", "xd", "yd", "zd", "sd", "strength", "R"):
             np.testing.assert_array_equal(g["kp"][f], k[f], err_msg=f)
         np.testing.assert_array_equal(g["mat"], m[g["idx"]])
+        if det_kw and "sigma0" in det_kw:
+            own_s = k["s"][g["idx"]]                 # (this rank's own list is mixed, too)
+            assert (own_s == 2).any() and (own_s < 2).any()
         covered[g["idx"]] += 1
+    np.testing.assert_array_equal(covered, 1)
+
+
+def test_c_slab_driver_second_call_on_another_volume():
+    """What a call leaves for the next (candidate arrays, the orientation table's validity mark, stores
+    reused at another row count): detect + describe on one volume, then a new slab in the same job and
+    detect + describe + gather -- the second result is the single-GPU API's on the second volume, bit for
+    bit."""
+    import torch
+    from sift3d_amd import api
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no HIP device is visible")
+    world, dims = 2, (64, 72, 256)
+    vol2 = api.synth_lattice(dims, seed=6)
+
+    def body(rank, job):
+        job.detect()
+        _, desc = job.describe()
+        n_first = len(desc.to_mat_rm())
+        z0, z1 = job.in_own
+        job.set_local_volume(vol2[z0:z1])
+        job.detect()
+        idx, desc = job.describe()
+        g = job.gather_descriptors(-1)
+        return n_first, job.keypoints(), idx.copy(), desc.to_mat_rm().copy(), g.to_mat_rm(), job.ncand
+
+    out, _ = _thread_ranks(world, dims, body)
+    det, kp, desc = api.Detector(), api.KeypointStore(), api.DescriptorStore()
+    assert det.detect_keypoints(api.Image.from_array(vol2), kp) == 0
+    assert det.extract_descriptors(kp, desc) == 0
+    k, m = kp.records(), desc.to_mat_rm()
+    assert len(k) > 5
+    covered = np.zeros(len(k), int)
+    for r in range(world):
+        n_first, kk, idx, own, allm, ncand = out[r]
+        assert n_first > 0 and ncand == det.num_candidates()
+        for f in ("o", "s", "xd", "yd", "zd", "sd", "strength", "R"):
+            np.testing.assert_array_equal(kk[f], k[f], err_msg="rank %d field %s" % (r, f))
+        np.testing.assert_array_equal(own, m[idx], err_msg="rank %d" % r)
+        np.testing.assert_array_equal(allm, m, err_msg="rank %d" % r)
+        covered[idx] += 1
     np.testing.assert_array_equal(covered, 1)
 
 
