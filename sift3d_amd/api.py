@@ -1077,6 +1077,34 @@ MI_BINS = 32
 AFFINE_FREE = {"affine": 0xFFF, "translation": 0x888}
 
 
+def _mi_bins(what, bins):
+    """bins of metric="mi" (None: MI_BINS), an integer in [4, hip.PARZEN_MAX_BINS]"""
+    from . import hip
+    bins = MI_BINS if bins is None else bins
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 4 <= int(bins) <= hip.PARZEN_MAX_BINS:
+        raise ValueError("%s: bins must be in [4, %d]" % (what, hip.PARZEN_MAX_BINS))
+    return bins
+
+
+def _mi_ranges(what, range_fixed, range_moving):
+    """each range of metric="mi" is None (the volume's own) or finite (lo, hi) with lo < hi as float32"""
+    for r, name in ((range_fixed, "range_fixed"), (range_moving, "range_moving")):
+        if r is not None:
+            lo, hi = (float(np.float32(v)) for v in r)
+            if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+                raise ValueError("%s: %s must be finite with lo < hi" % (what, name))
+
+
+def _levels_and_evaluations(what, levels, params, max_evaluations):
+    """levels an integer in [1, hip.AFFINE_MAX_LEVELS]; params' max_evaluations, where given, in [1, max_evaluations]"""
+    from . import hip
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
+            not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
+        raise ValueError("%s: levels must be in [1, %d]" % (what, hip.AFFINE_MAX_LEVELS))
+    if "max_evaluations" in params and not 1 <= int(params["max_evaluations"]) <= max_evaluations:
+        raise ValueError("%s: max_evaluations must be in [1, %d]" % (what, max_evaluations))
+
+
 def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", mask_fixed=None, mask_moving=None,
                   metric="msd", bins=None, range_fixed=None, range_moving=None, **params):
     """Move the 3 x 4 affine pull map A (fixed voxel -> moving voxel, as similarity's transform; None: the identity,
@@ -1111,26 +1139,15 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
         raise ValueError("refine_affine: bins, range_fixed and range_moving belong to metric='mi', not %r" % (metric,))
     if metric == "mi":
-        bins = MI_BINS if bins is None else bins
-        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or \
-                not 4 <= int(bins) <= hip.PARZEN_MAX_BINS:
-            raise ValueError("refine_affine: bins must be in [4, %d]" % hip.PARZEN_MAX_BINS)
-        for r, name in ((range_fixed, "range_fixed"), (range_moving, "range_moving")):
-            if r is not None:
-                lo, hi = (float(np.float32(v)) for v in r)
-                if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-                    raise ValueError("refine_affine: %s must be finite with lo < hi" % name)
+        bins = _mi_bins("refine_affine", bins)
+        _mi_ranges("refine_affine", range_fixed, range_moving)
     if interp != "linear":
         raise ValueError("refine_affine: the sample is linear; interp=%r has no gradient" % (interp,))
     mask = AFFINE_FREE.get(free, free) if isinstance(free, str) else free
     if isinstance(mask, bool) or not isinstance(mask, (int, np.integer)) or not 1 <= int(mask) <= 0xFFF:
         raise ValueError("refine_affine: free must be 'affine', 'translation' or a mask in [1, 0xFFF], not %r"
                          % (free,))
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
-            not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
-        raise ValueError("refine_affine: levels must be in [1, %d]" % hip.AFFINE_MAX_LEVELS)
-    if "max_evaluations" in params and not 1 <= int(params["max_evaluations"]) <= hip.AFFINE_MAX_EVALUATIONS:
-        raise ValueError("refine_affine: max_evaluations must be in [1, %d]" % hip.AFFINE_MAX_EVALUATIONS)
+    _levels_and_evaluations("refine_affine", levels, params, hip.AFFINE_MAX_EVALUATIONS)
     A0 = np.eye(3, 4) if A is None else _affine_or_none(A)
     if A0 is None or not np.isfinite(A0).all():
         raise ValueError("refine_affine: A must be a finite 3 x 4 affine pull map or None")
@@ -1373,21 +1390,10 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
         raise ValueError("refine_ffd: bins, range_fixed and range_moving belong to metric='mi', not %r" % (metric,))
     if metric == "mi":
-        bins = MI_BINS if bins is None else bins
-        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or \
-                not 4 <= int(bins) <= hip.PARZEN_MAX_BINS:
-            raise ValueError("refine_ffd: bins must be in [4, %d]" % hip.PARZEN_MAX_BINS)
-        for r, name in ((range_fixed, "range_fixed"), (range_moving, "range_moving")):
-            if r is not None:
-                lo, hi = (float(np.float32(v)) for v in r)
-                if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-                    raise ValueError("refine_ffd: %s must be finite with lo < hi" % name)
+        bins = _mi_bins("refine_ffd", bins)
+        _mi_ranges("refine_ffd", range_fixed, range_moving)
     d = hip.ffd_spacing(spacing, "refine_ffd")
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
-            not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
-        raise ValueError("refine_ffd: levels must be in [1, %d]" % hip.AFFINE_MAX_LEVELS)
-    if "max_evaluations" in params and not 1 <= int(params["max_evaluations"]) <= hip.FFD_MAX_EVALUATIONS:
-        raise ValueError("refine_ffd: max_evaluations must be in [1, %d]" % hip.FFD_MAX_EVALUATIONS)
+    _levels_and_evaluations("refine_ffd", levels, params, hip.FFD_MAX_EVALUATIONS)
     if not (np.isfinite(bending) and bending >= 0):
         raise ValueError("refine_ffd: bending must be finite and not negative")
     A0 = None
@@ -1409,9 +1415,9 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
     penalty = terms = None
+    mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
+        if metric == "mi" else {}
     if lm is not None:
-        mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
-            if metric == "mi" else {}
         res, lattice, field, sim, penalty, terms = hip.ffd_refine_landmarks(
             F, M, *lm, landmark_weight=landmark_weight, jacobian=jacobian if jacobian > 0 else None, A=A0, params=p,
             mask_fixed=WF, mask_moving=WM, **mi)
@@ -1429,13 +1435,10 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         res, lattice, field, penalty = hip.ffd_refine_channels(fv, mv, A0, p, masks_fixed=wf, masks_moving=wm,
                                                                jacobian=jacobian if jacobian > 0 else None)
     elif jacobian > 0:
-        mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
-            if metric == "mi" else {}
         res, lattice, field, sim, penalty = hip.ffd_refine_jacobian(F, M, jacobian, A=A0, params=p, mask_fixed=WF,
                                                                     mask_moving=WM, **mi)
     elif metric == "mi":
-        res, lattice, field, sim = hip.ffd_mi_refine(F, M, int(bins), _own_range(F, range_fixed),
-                                                     _own_range(M, range_moving), A0, p, mask_fixed=WF, mask_moving=WM)
+        res, lattice, field, sim = hip.ffd_mi_refine(F, M, A=A0, params=p, mask_fixed=WF, mask_moving=WM, **mi)
     else:
         res, lattice, field = hip.ffd_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     trail = [FFDEvaluation(e.E, e.msd, e.R, int(e.n), e.step, bool(e.accepted), e.level)

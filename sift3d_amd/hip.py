@@ -153,6 +153,15 @@ def lib():
         return _bound
     L = _native.load()
     vp = C.c_void_p
+    # the argument runs that the registration entries share, stated once
+    dp = C.POINTER(C.c_double)                             # A: the 3 x 4 pull map (NULL where the entry allows it)
+    pair = [vp, C.c_int, C.c_int, C.c_int] * 2             # the fixed volume and its grid, the moving volume and its
+    lattice = [vp] + [C.c_int] * 6                         # the control lattice, its dimensions and the spacing
+    parzen = [C.c_float] * 4                               # after bins: lo_f, hi_f, lo_m, hi_m
+    masks = [vp, vp]                                       # d_WF, d_WM
+    affine_refine = [dp, C.POINTER(AffineRefineParams), C.POINTER(AffineRefineResult)]
+    ffd_refine = [dp, C.POINTER(FFDRefineParams), C.POINTER(FFDRefineResult)]
+    ffd_outputs = [vp] * 5                                 # field, record, grad, work, stream
     sig = {
         "sift3d_hip_device_count": (C.c_int, []),
         "sift3d_hip_set_device": (C.c_int, [C.c_int]),
@@ -220,90 +229,56 @@ def lib():
         "sift3d_hip_max_rows": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "sift3d_hip_set_mesh": (C.c_int, [C.POINTER(C.c_float)]),
         "sift3d_hip_synth_lattice": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]),
-        "sift3d_hip_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                             C.POINTER(C.c_double), C.c_int, C.c_float, vp]),
-        "sift3d_hip_warp_tps": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                          C.POINTER(C.c_double), vp, C.c_int, C.c_int, C.c_float, vp]),
+        "sift3d_hip_warp_affine": (C.c_int, pair + [dp, C.c_int, C.c_float, vp]),
+        "sift3d_hip_warp_tps": (C.c_int, pair + [dp, vp, C.c_int, C.c_int, C.c_float, vp]),
         "sift3d_hip_warp_tps_launches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-        "sift3d_hip_affine_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp]),
-        "sift3d_hip_tps_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp, C.c_int, vp]),
+        "sift3d_hip_affine_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, vp]),
+        "sift3d_hip_tps_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, vp, C.c_int, vp]),
         "sift3d_hip_tps_field_launches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "sift3d_hip_warp_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                             vp, C.c_int, C.c_float, vp]),
         "sift3d_hip_jacobian_det": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "sift3d_hip_bspline_work_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
         "sift3d_hip_bspline_prefilter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "sift3d_hip_bspline_warp_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                     C.POINTER(C.c_double), C.c_float, vp]),
+        "sift3d_hip_bspline_warp_affine": (C.c_int, pair + [dp, C.c_float, vp]),
         "sift3d_hip_bspline_warp_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
                                                     C.c_int, vp, C.c_float, vp]),
         "sift3d_amd_similarity_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-        "sift3d_hip_similarity_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                   C.POINTER(C.c_double), C.c_int, C.c_int, C.c_float, C.c_float,
-                                                   C.c_float, C.c_float, vp, vp, vp, vp]),
-        "sift3d_hip_similarity_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
-                                                  C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp,
-                                                  vp, vp]),
-        "sift3d_hip_similarity_affine_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                          C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_float,
-                                                          C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp]),
-        "sift3d_hip_similarity_field_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                         vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
-                                                         C.c_float, vp, vp, vp, vp, vp, vp]),
+        "sift3d_hip_similarity_affine": (C.c_int, pair + [dp, C.c_int, C.c_int] + parzen + [vp, vp, vp, vp]),
+        "sift3d_hip_similarity_field": (C.c_int, pair + [vp, C.c_int, C.c_int] + parzen + [vp, vp, vp, vp]),
+        "sift3d_hip_similarity_affine_masked": (C.c_int, pair + [dp, C.c_int, C.c_int] + parzen + [vp, vp, vp, vp]
+                                                + masks),
+        "sift3d_hip_similarity_field_masked": (C.c_int, pair + [vp, C.c_int, C.c_int] + parzen + [vp, vp, vp, vp]
+                                               + masks),
         "sift3d_amd_affine_normal_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-        "sift3d_hip_affine_normal_eqs_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                          C.c_int, C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
+        "sift3d_hip_affine_normal_eqs_masked": (C.c_int, pair + [dp, vp, vp, vp] + masks),
         "sift3d_amd_affine_refine_masked_work_bytes": (C.c_size_t, [C.c_int] * 7),
-        "sift3d_amd_affine_refine_masked_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                             C.c_int, C.POINTER(C.c_double),
-                                                             C.POINTER(AffineRefineParams),
-                                                             C.POINTER(AffineRefineResult), vp, vp, vp, vp]),
-        "sift3d_hip_ffd_evaluate_masked": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
-                                           + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp,
-                                                              vp, vp]),
+        "sift3d_amd_affine_refine_masked_device": (C.c_int, pair + affine_refine + [vp, vp] + masks),
+        "sift3d_hip_ffd_evaluate_masked": (C.c_int, pair + lattice + [dp, C.c_double] + ffd_outputs + masks),
         "sift3d_amd_ffd_refine_masked_work_bytes": (C.c_size_t, [C.c_int] * 10),
-        "sift3d_amd_ffd_refine_masked_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                          C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
-                                                          C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp]),
-        "sift3d_hip_affine_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                   C.POINTER(C.c_double), vp, vp, vp]),
-        "sift3d_amd_affine_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, C.POINTER(C.c_double)]),
-        "sift3d_amd_affine_apply_delta": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,
-                                                    C.c_int, C.POINTER(C.c_double)]),
+        "sift3d_amd_ffd_refine_masked_device": (C.c_int, pair + ffd_refine + [vp, vp, vp, vp] + masks),
+        "sift3d_hip_affine_normal_eqs": (C.c_int, pair + [dp, vp, vp, vp]),
+        "sift3d_amd_affine_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, dp]),
+        "sift3d_amd_affine_apply_delta": (C.c_int, [dp, dp, C.c_int, C.c_int, C.c_int, dp]),
         "sift3d_amd_affine_refine_struct_bytes": (C.c_size_t, [C.c_int]),
         "sift3d_amd_affine_refine_default_params": (None, [C.POINTER(AffineRefineParams)]),
         "sift3d_amd_affine_refine_work_bytes": (C.c_size_t, [C.c_int] * 7),
-        "sift3d_amd_affine_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                      C.POINTER(C.c_double), C.POINTER(AffineRefineParams),
-                                                      C.POINTER(AffineRefineResult), vp, vp]),
+        "sift3d_amd_affine_refine_device": (C.c_int, pair + affine_refine + [vp, vp]),
         "sift3d_amd_affine_ncc_normal_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-        "sift3d_hip_affine_ncc_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                       C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
-        "sift3d_amd_affine_ncc_fit": (C.c_int, [vp, C.POINTER(C.c_double)]),
-        "sift3d_amd_affine_ncc_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, C.POINTER(C.c_double)]),
+        "sift3d_hip_affine_ncc_normal_eqs": (C.c_int, pair + [dp, vp, vp, vp] + masks),
+        "sift3d_amd_affine_ncc_fit": (C.c_int, [vp, dp]),
+        "sift3d_amd_affine_ncc_lm_step": (C.c_int, [vp, C.c_uint, C.c_double, dp]),
         "sift3d_amd_affine_ncc_refine_work_bytes": (C.c_size_t, [C.c_int] * 7),
-        "sift3d_amd_affine_ncc_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                          C.c_int, C.POINTER(C.c_double),
-                                                          C.POINTER(AffineRefineParams),
-                                                          C.POINTER(AffineRefineResult), C.POINTER(C.c_double), vp,
-                                                          vp, vp, vp]),
+        "sift3d_amd_affine_ncc_refine_device": (C.c_int, pair + affine_refine + [dp, vp, vp] + masks),
         "sift3d_amd_parzen_window": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int),
-                                               C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+                                               C.POINTER(C.c_uint32), dp, C.POINTER(C.c_int)]),
         "sift3d_amd_parzen_hist_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-        "sift3d_hip_parzen_hist_affine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                    C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float, C.c_float,
-                                                    C.c_float, vp, vp, vp, vp, vp, vp]),
+        "sift3d_hip_parzen_hist_affine": (C.c_int, pair + [dp, C.c_int] + parzen + [vp, vp, vp, vp] + masks),
         "sift3d_amd_parzen_mi": (C.c_int, [vp, C.c_int, C.POINTER(Similarity), vp]),
-        "sift3d_hip_affine_mi_normal_eqs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                      C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float,
-                                                      C.c_float, C.c_float, vp, vp, vp, vp, vp, vp]),
+        "sift3d_hip_affine_mi_normal_eqs": (C.c_int, pair + [dp, C.c_int] + parzen + [vp, vp, vp, vp] + masks),
         "sift3d_amd_affine_mi_refine_work_bytes": (C.c_size_t, [C.c_int] * 7),
-        "sift3d_amd_affine_mi_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                         C.c_int, C.POINTER(C.c_double), C.c_int, C.c_float,
-                                                         C.c_float, C.c_float, C.c_float,
-                                                         C.POINTER(AffineRefineParams),
-                                                         C.POINTER(AffineRefineResult), C.POINTER(Similarity), vp,
-                                                         vp, vp, vp]),
+        "sift3d_amd_affine_mi_refine_device": (C.c_int, pair + [dp, C.c_int] + parzen + affine_refine[1:]  # A is ahead
+                                               + [C.POINTER(Similarity), vp, vp] + masks),
         "sift3d_amd_ffd_lattice_dim": (C.c_int, [C.c_int, C.c_int]),
         "sift3d_amd_ffd_weights": (C.c_int, [C.c_int, vp]),
         "sift3d_amd_ffd_field_work_bytes": (C.c_size_t, [C.c_int] * 3),
@@ -311,67 +286,46 @@ def lib():
         "sift3d_amd_ffd_evaluate_work_bytes": (C.c_size_t, [C.c_int] * 6),
         "sift3d_amd_ffd_bending_work_bytes": (C.c_size_t, [C.c_int] * 3),
         "sift3d_amd_ffd_refine_work_bytes": (C.c_size_t, [C.c_int] * 10),
-        "sift3d_hip_ffd_field": (C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_double)] + [C.c_int] * 3 + [vp, vp, vp]),
-        "sift3d_hip_ffd_evaluate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
-                                    + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp]),
-        "sift3d_hip_ffd_bending": (C.c_int, [vp] + [C.c_int] * 6 + [vp, vp, vp]),
+        "sift3d_hip_ffd_field": (C.c_int, lattice + [dp] + [C.c_int] * 3 + [vp, vp, vp]),
+        "sift3d_hip_ffd_evaluate": (C.c_int, pair + lattice + [dp, C.c_double] + ffd_outputs),
+        "sift3d_hip_ffd_bending": (C.c_int, lattice + [vp, vp, vp]),
         "sift3d_hip_ffd_refine2": (C.c_int, [vp] + [C.c_int] * 6 + [vp, vp]),
         "sift3d_amd_ffd_refine_default_params": (None, [C.POINTER(FFDRefineParams)]),
         "sift3d_amd_ffd_refine_struct_bytes": (C.c_size_t, [C.c_int]),
-        "sift3d_amd_ffd_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                   C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
-                                                   C.POINTER(FFDRefineResult), vp, vp, vp, vp]),
-        "sift3d_hip_parzen_hist_field": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
-                                                   C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp,
-                                                   vp, vp]),
-        "sift3d_hip_ffd_mi_evaluate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
-                                       + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp, vp, vp,
-                                                          C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
+        "sift3d_amd_ffd_refine_device": (C.c_int, pair + ffd_refine + [vp, vp, vp, vp]),
+        "sift3d_hip_parzen_hist_field": (C.c_int, pair + [vp, C.c_int] + parzen + [vp, vp, vp, vp] + masks),
+        "sift3d_hip_ffd_mi_evaluate": (C.c_int, pair + lattice + [dp, C.c_double] + ffd_outputs + masks + [C.c_int]
+                                       + parzen + [vp]),
         "sift3d_amd_ffd_mi_refine_work_bytes": (C.c_size_t, [C.c_int] * 10),
-        "sift3d_amd_ffd_mi_refine_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                      C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
-                                                      C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp, C.c_int,
-                                                      C.c_float, C.c_float, C.c_float, C.c_float,
-                                                      C.POINTER(Similarity)]),
+        "sift3d_amd_ffd_mi_refine_device": (C.c_int, pair + ffd_refine + [vp, vp, vp, vp] + masks + [C.c_int] + parzen
+                                            + [C.POINTER(Similarity)]),
         "sift3d_amd_jacobian_penalty_work_bytes": (C.c_size_t, [C.c_int] * 3),
         "sift3d_hip_jacobian_penalty": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]),
         "sift3d_amd_ffd_jacobian_gradient_work_bytes": (C.c_size_t, [C.c_int] * 6),
         "sift3d_hip_ffd_jacobian_gradient": (C.c_int, [vp] + [C.c_int] * 6 + [C.c_double, vp, vp, vp, vp]),
         "sift3d_amd_ffd_refine_jacobian_work_bytes": (C.c_size_t, [C.c_int] * 10),
-        "sift3d_amd_ffd_refine_jacobian_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                            C.c_int, C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
-                                                            C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp,
-                                                            C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                                            C.POINTER(Similarity), C.c_double,
-                                                            C.POINTER(FFDPenalty)]),
+        "sift3d_amd_ffd_refine_jacobian_device": (C.c_int, pair + ffd_refine + [vp, vp, vp, vp] + masks + [C.c_int]
+                                                  + parzen + [C.POINTER(Similarity), C.c_double,
+                                                              C.POINTER(FFDPenalty)]),
         "sift3d_amd_ffd_level_struct_bytes": (C.c_size_t, [C.c_int]),
         "sift3d_amd_ffd_evaluate_channels_work_bytes": (C.c_size_t, [C.c_int] * 6),
-        "sift3d_hip_ffd_evaluate_channels": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                                       C.c_int, vp] + [C.c_int] * 6
-                                             + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+        "sift3d_hip_ffd_evaluate_channels": (C.c_int, pair + [C.c_int] + lattice + [dp, C.c_double] + ffd_outputs
+                                             + masks),
         "sift3d_amd_ffd_refine_channels_work_bytes": (C.c_size_t, [C.c_int] * 6),
-        "sift3d_amd_ffd_refine_channels_device": (C.c_int, [C.POINTER(FFDLevel), C.c_int, C.c_int,
-                                                            C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
-                                                            C.POINTER(FFDRefineResult), vp, vp, vp, vp, C.c_double,
-                                                            C.POINTER(FFDPenalty)]),
+        "sift3d_amd_ffd_refine_channels_device": (C.c_int, [C.POINTER(FFDLevel), C.c_int, C.c_int] + ffd_refine
+                                                  + [vp, vp, vp, vp, C.c_double, C.POINTER(FFDPenalty)]),
         "sift3d_amd_ffd_landmarks_struct_bytes": (C.c_size_t, [C.c_int]),
-        "sift3d_hip_ffd_points": (C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_double), vp, C.c_int, vp, vp]),
+        "sift3d_hip_ffd_points": (C.c_int, lattice + [dp, vp, C.c_int, vp, vp]),
         "sift3d_amd_ffd_landmarks_work_bytes": (C.c_size_t, [C.c_int] * 4),
-        "sift3d_hip_ffd_landmarks": (C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_double), vp, vp, vp, C.c_int, vp, vp,
-                                                                     vp, vp, vp]),
+        "sift3d_hip_ffd_landmarks": (C.c_int, lattice + [dp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         "sift3d_amd_ffd_evaluate_landmarks_bytes": (C.c_size_t, [C.c_int] * 8),
-        "sift3d_hip_ffd_evaluate_landmarks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
-                                              + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp, vp,
-                                                                 vp, vp, C.c_double, vp, vp, vp, vp, C.c_int,
-                                                                 C.c_double, vp]),
+        "sift3d_hip_ffd_evaluate_landmarks": (C.c_int, pair + lattice + [dp, C.c_double] + ffd_outputs + masks
+                                              + [C.c_double, vp, vp, vp, vp, C.c_int, C.c_double, vp]),
         "sift3d_amd_ffd_refine_landmarks_work_bytes": (C.c_size_t, [C.c_int] * 11),
-        "sift3d_amd_ffd_refine_landmarks_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
-                                                             C.c_int, C.POINTER(C.c_double), C.POINTER(FFDRefineParams),
-                                                             C.POINTER(FFDRefineResult), vp, vp, vp, vp, vp, vp,
-                                                             C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                                             C.POINTER(Similarity), C.c_double,
-                                                             C.POINTER(FFDPenalty), vp, vp, vp, C.c_int, C.c_double,
-                                                             C.POINTER(FFDLandmarkTerm)]),
+        "sift3d_amd_ffd_refine_landmarks_device": (C.c_int, pair + ffd_refine + [vp, vp, vp, vp] + masks + [C.c_int]
+                                                   + parzen + [C.POINTER(Similarity), C.c_double,
+                                                               C.POINTER(FFDPenalty), vp, vp, vp, C.c_int, C.c_double,
+                                                               C.POINTER(FFDLandmarkTerm)]),
         "sift3d_hip_dense_bin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            vp, vp]),
         "sift3d_hip_dense_normalize": (C.c_int, [vp, C.c_size_t, vp]),
@@ -605,6 +559,30 @@ def _work(work, need, like, what, dtype=None):
     return work
 
 
+def _byte_work(what, work, need, like, refuses=None):
+    """_work for a driver that states its size in bytes.  refuses: what to say where the library answers 0 bytes,
+    which is how the refinement drivers refuse their levels or spacing."""
+    if need == 0 and refuses:
+        raise ValueError("%s: %s" % (what, refuses))
+    return _work(work, (need + 3) // 4, like, what)
+
+
+def _buffer(what, name, t, shape, like, says=None):
+    """An int64 output that the caller may bring: allocated (not cleared) on the device of `like` when t is None, else
+    the caller's, which must be contiguous, of exactly `shape` (`says` where the message names it otherwise) there."""
+    import torch
+    if t is None:
+        return torch.empty(shape, dtype=torch.int64, device=like.device)
+    _tensor(t, "%s: %s must be a contiguous int64 CUDA tensor %s on F's device" % (what, name, says or list(shape)),
+            shape=shape, device=like.device, dtype="int64")
+    return t
+
+
+def _run(name, *args):
+    """the library's entry `name` on args; RuntimeError with the library's message where it fails"""
+    _check(getattr(lib(), name)(*args), name)
+
+
 def _warp_pair(src, dst, what):
     for t in (src, dst):
         _tensor(t, "%s: src and dst must be contiguous 3-D float32 CUDA tensors" % what, dims=(3,))
@@ -815,6 +793,26 @@ def _masks(what, F, M, mask_fixed, mask_moving):
     return tuple(out)
 
 
+def _pair(what, F, M, mask_fixed=None, mask_moving=None, *more):
+    """The prelude of a wrapper over a fixed volume F [oz, oy, ox] and a moving volume M [nz, ny, nx]: both contiguous
+    3-D float32 CUDA tensors, on one device with the tensors of `more` (checked by the caller as tensors), the masks as
+    _masks takes them.  Returns (head, masks): head = (F, ox, oy, oz, M, nx, ny, nz) as every entry's arguments begin,
+    so head[1:4] is the fixed grid and head[5:8] the moving one; masks as _masks returns them."""
+    for t in (F, M):
+        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
+    _same_device(what, F, M, *more)
+    oz, oy, ox = F.shape
+    nz, ny, nx = M.shape
+    return (F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz), _masks(what, F, M, mask_fixed, mask_moving)
+
+
+def _masked_entry(name, masks):
+    """(entry, mask arguments) of the measures that come as two entries (the MSD's and similarity's): `name` without
+    masks, name + "_masked" with the two pointers only when a mask is given.  The general entries take the two
+    pointers always, NULL for none: `masks or (None, None)`."""
+    return (name, ()) if masks is None else (name + "_masked", masks)
+
+
 def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=None, work=None, mask_fixed=None,
                mask_moving=None):
     """The joint histogram and moments of the fixed volume F [oz, oy, ox] and the moving volume M [nz, ny, nx] seen
@@ -826,15 +824,12 @@ def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=No
     mask_moving: float32 masks of F's and M's shapes (in where >= 0.5; header, "Masks"); with either given the call goes
     to the _masked entry, with both None to the unmasked one."""
     import torch
-    for t in (F, M):
-        _tensor(t, "similarity: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    masks = _masks("similarity", F, M, mask_fixed, mask_moving)
+    head, masks = _pair("similarity", F, M, mask_fixed, mask_moving)
     mode = _interp(interp)
     bins = int(bins)
     if not 2 <= bins <= SIMILARITY_MAX_BINS:
         raise ValueError("similarity: bins must be in [2, %d]" % SIMILARITY_MAX_BINS)
     oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
     field = None
     if transform is None:
         if F.shape != M.shape:
@@ -845,33 +840,19 @@ def similarity(F, M, transform, bins, range_f, range_m, interp="linear", hist=No
         field = transform
         _tensor(field, "similarity: a field must be a contiguous float32 CUDA tensor [3, oz, oy, ox] on F's grid",
                 shape=(3, oz, oy, ox))
-        _same_device("similarity", F, M, field)
+        _same_device("similarity", F, field)
     else:
         a = np.ascontiguousarray(transform, np.float64)
         if a.shape not in ((3, 4), (12,)):
             raise ValueError("similarity: transform must be a 3 x 4 affine pull map, a field tensor or None")
         a = a.reshape(12)
-        _same_device("similarity", F, M)
-    if hist is None:
-        hist = torch.empty((bins, bins), dtype=torch.int64, device=F.device)
-    _tensor(hist, "similarity: hist must be a contiguous int64 CUDA tensor [bins, bins] on F's device",
-            shape=(bins, bins), device=F.device, dtype="int64")
-    need = lib().sift3d_amd_similarity_work_bytes(ox, oy, oz, bins)
-    work = _work(work, (need + 3) // 4, F, "similarity")
+    hist = _buffer("similarity", "hist", hist, (bins, bins), F, "[bins, bins]")
+    work = _byte_work("similarity", work, lib().sift3d_amd_similarity_work_bytes(ox, oy, oz, bins), F)
     stats = torch.empty(SIMILARITY_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
     (lo_f, hi_f), (lo_m, hi_m) = ((float(np.float32(v)) for v in r) for r in (range_f, range_m))
-    tail = (mode, bins, lo_f, hi_f, lo_m, hi_m, hist.data_ptr(), stats.data_ptr(), work.data_ptr(), current_stream())
-    if masks is not None:
-        name = "sift3d_hip_similarity_%s_masked" % ("affine" if field is None else "field")
-        T = a.ctypes.data_as(C.POINTER(C.c_double)) if field is None else field.data_ptr()
-        _check(getattr(lib(), name)(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, T, *tail, *masks), name)
-    elif field is None:
-        _check(lib().sift3d_hip_similarity_affine(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
-                                                  a.ctypes.data_as(C.POINTER(C.c_double)), *tail),
-               "sift3d_hip_similarity_affine")
-    else:
-        _check(lib().sift3d_hip_similarity_field(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
-                                                 field.data_ptr(), *tail), "sift3d_hip_similarity_field")
+    name, masks = _masked_entry("sift3d_hip_similarity_" + ("affine" if field is None else "field"), masks)
+    _run(name, *head, _dptr(a) if field is None else field.data_ptr(), mode, bins, lo_f, hi_f, lo_m, hi_m,
+         hist.data_ptr(), stats.data_ptr(), work.data_ptr(), current_stream(), *masks)
     return hist, stats
 
 
@@ -1034,28 +1015,13 @@ def affine_normal_equations(F, M, A, record=None, work=None, raw=False, mask_fix
     (n, S_ee, b [12], H [12, 12]) on the host (which waits for the stream), or with raw=True the device record (read
     it with affine_normal_record).  record, work: the caller's buffers (int64 [158]; sift3d_amd_affine_normal_work_bytes
     bytes).  mask_fixed, mask_moving: as similarity's (sift3d_hip_affine_normal_eqs_masked)."""
-    import torch
-    for t in (F, M):
-        _tensor(t, "affine_normal_equations: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device("affine_normal_equations", F, M)
-    masks = _masks("affine_normal_equations", F, M, mask_fixed, mask_moving)
-    a = _affine12(A, "affine_normal_equations")
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    if record is None:
-        record = torch.empty(AFFINE_NORMAL_BYTES // 8, dtype=torch.int64, device=F.device)
-    _tensor(record, "affine_normal_equations: record must be a contiguous int64 CUDA tensor [158] on F's device",
-            shape=(AFFINE_NORMAL_BYTES // 8,), device=F.device, dtype="int64")
-    need = lib().sift3d_amd_affine_normal_work_bytes(ox, oy, oz)
-    work = _work(work, (need + 3) // 4, F, "affine_normal_equations")
-    if masks is not None:
-        _check(lib().sift3d_hip_affine_normal_eqs_masked(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                                         record.data_ptr(), work.data_ptr(), current_stream(), *masks),
-               "sift3d_hip_affine_normal_eqs_masked")
-    else:
-        _check(lib().sift3d_hip_affine_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                                  record.data_ptr(), work.data_ptr(), current_stream()),
-               "sift3d_hip_affine_normal_eqs")
+    what = "affine_normal_equations"
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
+    a = _affine12(A, what)
+    record = _buffer(what, "record", record, (AFFINE_NORMAL_BYTES // 8,), F)
+    work = _byte_work(what, work, lib().sift3d_amd_affine_normal_work_bytes(*head[1:4]), F)
+    name, masks = _masked_entry("sift3d_hip_affine_normal_eqs", masks)
+    _run(name, *head, _dptr(a), record.data_ptr(), work.data_ptr(), current_stream(), *masks)
     return record if raw else affine_normal_record(record)
 
 
@@ -1094,35 +1060,28 @@ def affine_refine_params(**kw):
     return p
 
 
+def _affine_refine(what, stem, F, M, A, params, work, mask_fixed, mask_moving, before=(), after=None):
+    """The body of the affine refinement drivers, stem + "_device" sized by stem + "_work_bytes": the pair, A, `before`
+    (the MI driver's bins and ranges), params (None: the defaults), the result, `after` (where the driver leaves its
+    fit or measures), work, the stream, both masks.  after=None is the MSD driver, which takes nothing there and has
+    its masked entry (_masked_entry).  Returns the AffineRefineResult."""
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
+    a = _affine12(A, what)
+    p = params if params is not None else affine_refine_params()
+    stem, masks = _masked_entry(stem, masks) if after is None else (stem, masks or (None, None))
+    need = getattr(lib(), stem + "_work_bytes")(*head[1:4], *head[5:8], p.levels)
+    work = _byte_work(what, work, need, F, "levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
+    res = AffineRefineResult()
+    _run(stem + "_device", *head, _dptr(a), *before, C.byref(p), C.byref(res), *(after or ()), work.data_ptr(),
+         current_stream(), *masks)
+    return res
+
+
 def affine_refine(F, M, A, params=None, work=None, mask_fixed=None, mask_moving=None):
     """sift3d_amd_affine_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
     waits for it once per evaluation).  Returns the AffineRefineResult.  mask_fixed, mask_moving: as similarity's
     (sift3d_amd_affine_refine_masked_device)."""
-    for t in (F, M):
-        _tensor(t, "affine_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device("affine_refine", F, M)
-    masks = _masks("affine_refine", F, M, mask_fixed, mask_moving)
-    a = _affine12(A, "affine_refine")
-    p = params if params is not None else affine_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    bytes_of = lib().sift3d_amd_affine_refine_work_bytes if masks is None else \
-        lib().sift3d_amd_affine_refine_masked_work_bytes
-    need = bytes_of(ox, oy, oz, nx, ny, nz, p.levels)
-    if need == 0:
-        raise ValueError("affine_refine: levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
-    work = _work(work, (need + 3) // 4, F, "affine_refine")
-    res = AffineRefineResult()
-    if masks is not None:
-        _check(lib().sift3d_amd_affine_refine_masked_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz,
-                                                            _dptr(a), C.byref(p), C.byref(res), work.data_ptr(),
-                                                            current_stream(), *masks),
-               "sift3d_amd_affine_refine_masked_device")
-    else:
-        _check(lib().sift3d_amd_affine_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                                     C.byref(p), C.byref(res), work.data_ptr(), current_stream()),
-               "sift3d_amd_affine_refine_device")
-    return res
+    return _affine_refine("affine_refine", "sift3d_amd_affine_refine", F, M, A, params, work, mask_fixed, mask_moving)
 
 
 # ---- affine refinement under a linear intensity map (contract: "Affine refinement under a linear intensity map (NCC)")
@@ -1152,24 +1111,13 @@ def affine_ncc_normal_equations(F, M, A, record=None, work=None, raw=False, mask
     stream.  Returns the record on the host as affine_ncc_record does (which waits for the stream), or with raw=True
     the device record.  record, work: the caller's buffers (int64 [186]; sift3d_amd_affine_ncc_normal_work_bytes
     bytes).  mask_fixed, mask_moving: as similarity's."""
-    import torch
     what = "affine_ncc_normal_equations"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
     a = _affine12(A, what)
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    if record is None:
-        record = torch.empty(AFFINE_NCC_BYTES // 8, dtype=torch.int64, device=F.device)
-    _tensor(record, what + ": record must be a contiguous int64 CUDA tensor [186] on F's device",
-            shape=(AFFINE_NCC_BYTES // 8,), device=F.device, dtype="int64")
-    need = lib().sift3d_amd_affine_ncc_normal_work_bytes(ox, oy, oz)
-    work = _work(work, (need + 3) // 4, F, what)
-    _check(lib().sift3d_hip_affine_ncc_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                                  record.data_ptr(), work.data_ptr(), current_stream(), *masks),
-           "sift3d_hip_affine_ncc_normal_eqs")
+    record = _buffer(what, "record", record, (AFFINE_NCC_BYTES // 8,), F)
+    work = _byte_work(what, work, lib().sift3d_amd_affine_ncc_normal_work_bytes(*head[1:4]), F)
+    _run("sift3d_hip_affine_ncc_normal_eqs", *head, _dptr(a), record.data_ptr(), work.data_ptr(), current_stream(),
+         *(masks or (None, None)))
     return record if raw else affine_ncc_record(record)
 
 
@@ -1203,26 +1151,10 @@ def affine_ncc_refine(F, M, A, params=None, work=None, mask_fixed=None, mask_mov
     """sift3d_amd_affine_ncc_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the
     call waits for it once per evaluation).  Returns (AffineRefineResult, fit float64 [4] = alpha, beta, cost, ncc at
     the final A).  mask_fixed, mask_moving: as similarity's."""
-    for t in (F, M):
-        _tensor(t, "affine_ncc_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device("affine_ncc_refine", F, M)
-    masks = _masks("affine_ncc_refine", F, M, mask_fixed, mask_moving) or (None, None)
-    a = _affine12(A, "affine_ncc_refine")
-    p = params if params is not None else affine_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    need = lib().sift3d_amd_affine_ncc_refine_work_bytes(ox, oy, oz, nx, ny, nz, p.levels)
-    if need == 0:
-        raise ValueError("affine_ncc_refine: levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
-    work = _work(work, (need + 3) // 4, F, "affine_ncc_refine")
-    res = AffineRefineResult()
     fit = np.zeros(4)
-    _check(lib().sift3d_amd_affine_ncc_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a),
-                                                     C.byref(p), C.byref(res), _dptr(fit), work.data_ptr(),
-                                                     current_stream(), *masks),
-           "sift3d_amd_affine_ncc_refine_device")
+    res = _affine_refine("affine_ncc_refine", "sift3d_amd_affine_ncc_refine", F, M, A, params, work, mask_fixed,
+                         mask_moving, after=(_dptr(fit),))
     return res, fit
-
 
 
 # ---- Mattes mutual-information affine refinement (contract: "Mutual-information affine refinement (Mattes)") ---------
@@ -1260,28 +1192,38 @@ def parzen_histogram(F, M, A, bins, range_f, range_m, hist=None, work=None, mask
     stream.  Returns (hist int64 [bins, bins] indexed [b_f, b_m], count int64 [1]) on the device; reading either waits
     for the stream.  hist, work: the caller's buffers (int64 [bins, bins]; sift3d_amd_parzen_hist_work_bytes bytes).
     mask_fixed, mask_moving: as similarity's."""
-    import torch
     what = "parzen_histogram"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
     a = _affine12(A, what)
+    return _parzen_hist(what, "sift3d_hip_parzen_hist_affine", F, head, masks, _dptr(a), bins, range_f, range_m, hist,
+                        work)
+
+
+def _parzen_hist(what, name, F, head, masks, T, bins, range_f, range_m, hist, work):
+    """The body of the two Parzen histograms after the pair (_pair's head and masks) and the pull map or field T:
+    returns (hist, count)."""
+    import torch
     bins = _parzen_bins(bins, what)
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    if hist is None:
-        hist = torch.empty((bins, bins), dtype=torch.int64, device=F.device)
-    _tensor(hist, what + ": hist must be a contiguous int64 CUDA tensor [bins, bins] on F's device",
-            shape=(bins, bins), device=F.device, dtype="int64")
+    hist = _buffer(what, "hist", hist, (bins, bins), F, "[bins, bins]")
     count = torch.empty(1, dtype=torch.int64, device=F.device)
-    need = lib().sift3d_amd_parzen_hist_work_bytes(ox, oy, oz)
-    work = _work(work, (need + 3) // 4, F, what)
-    _check(lib().sift3d_hip_parzen_hist_affine(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a), bins,
-                                               *_parzen_ranges(range_f, range_m), hist.data_ptr(), count.data_ptr(),
-                                               work.data_ptr(), current_stream(), *masks),
-           "sift3d_hip_parzen_hist_affine")
+    work = _byte_work(what, work, lib().sift3d_amd_parzen_hist_work_bytes(*head[1:4]), F)
+    _run(name, *head, T, bins, *_parzen_ranges(range_f, range_m), hist.data_ptr(), count.data_ptr(), work.data_ptr(),
+         current_stream(), *(masks or (None, None)))
     return hist, count
+
+
+def _parzen_table(what, W, F):
+    """(W, bins) of the table W [bins, bins] that the MI kernels take psi from: a host array is uploaded to F's device
+    as float64, a tensor must be contiguous float64 [bins, bins] there."""
+    import torch
+    if not isinstance(W, torch.Tensor):
+        W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(F.device)
+    if W.dim() != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError(what + ": W must be [bins, bins]")
+    bins = _parzen_bins(W.shape[0], what)
+    _tensor(W, what + ": W must be a contiguous float64 tensor [bins, bins] on F's device", shape=(bins, bins),
+            device=F.device, dtype="float64")
+    return W, bins
 
 
 def parzen_mi(hist):
@@ -1309,32 +1251,14 @@ def affine_mi_normal_equations(F, M, A, W, range_f, range_m, record=None, work=N
     (n, S_pp, b [12], H [12, 12]) on the host as affine_normal_equations does, or with raw=True the device record.
     record, work: the caller's buffers (int64 [158]; sift3d_amd_affine_normal_work_bytes bytes).  mask_fixed,
     mask_moving: as similarity's."""
-    import torch
     what = "affine_mi_normal_equations"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
     a = _affine12(A, what)
-    if not isinstance(W, torch.Tensor):
-        W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(F.device)
-    if W.dim() != 2 or W.shape[0] != W.shape[1]:
-        raise ValueError(what + ": W must be [bins, bins]")
-    bins = _parzen_bins(W.shape[0], what)
-    _tensor(W, what + ": W must be a contiguous float64 tensor [bins, bins] on F's device", shape=(bins, bins),
-            device=F.device, dtype="float64")
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    if record is None:
-        record = torch.empty(AFFINE_NORMAL_BYTES // 8, dtype=torch.int64, device=F.device)
-    _tensor(record, what + ": record must be a contiguous int64 CUDA tensor [158] on F's device",
-            shape=(AFFINE_NORMAL_BYTES // 8,), device=F.device, dtype="int64")
-    need = lib().sift3d_amd_affine_normal_work_bytes(ox, oy, oz)
-    work = _work(work, (need + 3) // 4, F, what)
-    _check(lib().sift3d_hip_affine_mi_normal_eqs(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a), bins,
-                                                 *_parzen_ranges(range_f, range_m), W.data_ptr(), record.data_ptr(),
-                                                 work.data_ptr(), current_stream(), *masks),
-           "sift3d_hip_affine_mi_normal_eqs")
+    W, bins = _parzen_table(what, W, F)
+    record = _buffer(what, "record", record, (AFFINE_NORMAL_BYTES // 8,), F)
+    work = _byte_work(what, work, lib().sift3d_amd_affine_normal_work_bytes(*head[1:4]), F)
+    _run("sift3d_hip_affine_mi_normal_eqs", *head, _dptr(a), bins, *_parzen_ranges(range_f, range_m), W.data_ptr(),
+         record.data_ptr(), work.data_ptr(), current_stream(), *(masks or (None, None)))
     return record if raw else affine_normal_record(record)
 
 
@@ -1343,30 +1267,15 @@ def affine_mi_refine(F, M, A, bins, range_f, range_m, params=None, work=None, ma
     waits for it once per pass).  Returns (AffineRefineResult, Similarity: the measures at the final A, n the
     histogram's total).  mask_fixed, mask_moving: as similarity's."""
     what = "affine_mi_refine"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
-    a = _affine12(A, what)
-    bins = _parzen_bins(bins, what)
-    p = params if params is not None else affine_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    need = lib().sift3d_amd_affine_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, p.levels)
-    if need == 0:
-        raise ValueError(what + ": levels must be in [1, %d]" % AFFINE_MAX_LEVELS)
-    work = _work(work, (need + 3) // 4, F, what)
-    res = AffineRefineResult()
     sim = Similarity()
-    _check(lib().sift3d_amd_affine_mi_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, _dptr(a), bins,
-                                                    *_parzen_ranges(range_f, range_m), C.byref(p), C.byref(res),
-                                                    C.byref(sim), work.data_ptr(), current_stream(), *masks),
-           "sift3d_amd_affine_mi_refine_device")
+    res = _affine_refine(what, "sift3d_amd_affine_mi_refine", F, M, A, params, work, mask_fixed, mask_moving,
+                         before=(_parzen_bins(bins, what), *_parzen_ranges(range_f, range_m)), after=(C.byref(sim),))
     return res, sim
 
 
 # ---- B-spline free-form deformation (contract: include/sift3d_amd.h, "B-spline free-form deformation") ----
 FFD_STOPS = ("converged", "evaluations", "flat", "failed")
+_FFD_TRAIL = AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS       # the entries of a driver's trail and of the terms' beside it
 FFD_HEAD_DTYPE = np.dtype([("n", "u8"), ("see", "f8"), ("R", "f8"), ("gmax", "f8")])
 assert FFD_HEAD_DTYPE.itemsize == FFD_RECORD_HEAD_BYTES
 
@@ -1446,28 +1355,35 @@ def ffd_evaluate(F, M, lattice, spacing, A=None, bending=0.0, work=None, mask_fi
     """One evaluation of the FFD cost at `lattice` (sift3d_hip_ffd_evaluate) on torch's current stream.  Returns
     (record, grad, field): the device record (read it with ffd_record), the float32 gradient lattice and the field.
     mask_fixed, mask_moving: as similarity's (sift3d_hip_ffd_evaluate_masked)."""
+    what = "ffd_evaluate"
+    _ffd_lattice(lattice, what)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving, lattice)
+    args, out, work = _ffd_evaluate_args(what, head, F, lattice, spacing, A, bending, work)
+    name, masks = _masked_entry("sift3d_hip_ffd_evaluate", masks)
+    _run(name, *args, *masks)
+    return out
+
+
+def _ffd_outputs(F, lattice):
+    """(record, grad, field) of an FFD evaluation at `lattice` over the grid of the volume or stack F: the record
+    cleared (ffd_record reads its whole length), the float32 gradient lattice and the field [3, oz, oy, ox]"""
     import torch
-    for t in (F, M):
-        _tensor(t, "ffd_evaluate: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    masks = _masks("ffd_evaluate", F, M, mask_fixed, mask_moving)
-    gx, gy, gz = _ffd_lattice(lattice, "ffd_evaluate")
-    _same_device("ffd_evaluate", F, M, lattice)
-    dx, dy, dz = ffd_spacing(spacing, "ffd_evaluate")
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    a, ap = _ffd_A(A, "ffd_evaluate")
-    record = _ffd_record_tensor(lattice)
-    grad = torch.empty_like(lattice)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    need = lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz)
-    work = _work(work, (need + 3) // 4, F, "ffd_evaluate")
-    args = (F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap,
-            float(bending), field.data_ptr(), record.data_ptr(), grad.data_ptr(), work.data_ptr(), current_stream())
-    if masks is not None:
-        _check(lib().sift3d_hip_ffd_evaluate_masked(*args, *masks), "sift3d_hip_ffd_evaluate_masked")
-    else:
-        _check(lib().sift3d_hip_ffd_evaluate(*args), "sift3d_hip_ffd_evaluate")
-    return record, grad, field
+    return (_ffd_record_tensor(lattice), torch.empty_like(lattice),
+            torch.empty((3,) + tuple(F.shape[-3:]), dtype=torch.float32, device=F.device))
+
+
+def _ffd_evaluate_args(what, head, F, lattice, spacing, A, bending, work,
+                       bytes_of="sift3d_amd_ffd_evaluate_work_bytes"):
+    """What the FFD evaluation entries take up to the stream, from the pair's `head` (the stacks': with nc) on: the
+    lattice and spacing, A, bending, the outputs of _ffd_outputs and the work buffer (the caller's, or `bytes_of` bytes
+    allocated here).  Returns (args, (record, grad, field), work)."""
+    gx, gy, gz = _ffd_lattice(lattice, what)
+    d = ffd_spacing(spacing, what)
+    a, ap = _ffd_A(A, what)
+    record, grad, field = out = _ffd_outputs(F, lattice)
+    work = _byte_work(what, work, getattr(lib(), bytes_of)(*head[1:4], *d), F)
+    return (*head, lattice.data_ptr(), gx, gy, gz, *d, ap, float(bending), field.data_ptr(), record.data_ptr(),
+            grad.data_ptr(), work.data_ptr(), current_stream()), out, work
 
 
 def ffd_bending(lattice, spacing, work=None):
@@ -1516,33 +1432,42 @@ def ffd_refine(F, M, A=None, params=None, work=None, mask_fixed=None, mask_movin
     """sift3d_amd_ffd_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
     waits for it once per evaluation).  Returns (FFDRefineResult, lattice, field).  mask_fixed, mask_moving: as
     similarity's (sift3d_amd_ffd_refine_masked_device)."""
+    return _ffd_refine_pair("ffd_refine", "sift3d_amd_ffd_refine", F, M, A, params, work, mask_fixed, mask_moving)
+
+
+def _ffd_refine(what, stem, head, like, grid, ap, p, work, need, refuses, tail):
+    """The body of every FFD refinement driver, stem + "_device": after `head` (the pair, or the levels' table) it
+    takes A (ap: _ffd_A's pointer), params, the result, the lattice over `grid` = (oz, oy, ox) and the field, allocated
+    here on the device of `like`, the work buffer of `need` bytes (0: ValueError with `refuses`), the stream, and
+    `tail`.  Returns (FFDRefineResult, lattice, field)."""
     import torch
-    for t in (F, M):
-        _tensor(t, "ffd_refine: F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device("ffd_refine", F, M)
-    masks = _masks("ffd_refine", F, M, mask_fixed, mask_moving)
-    a, ap = _ffd_A(A, "ffd_refine")
-    p = params if params is not None else ffd_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    d = tuple(p.spacing)
-    bytes_of = lib().sift3d_amd_ffd_refine_work_bytes if masks is None else \
-        lib().sift3d_amd_ffd_refine_masked_work_bytes
-    need = bytes_of(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
-    if need == 0:
-        raise ValueError("ffd_refine: levels must be in [1, %d] and the spacing in [1, %d]"
-                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
-    work = _work(work, (need + 3) // 4, F, "ffd_refine")
-    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
+    work = _byte_work(what, work, need, like, refuses)
+    lattice = torch.empty(ffd_lattice_shape(grid, tuple(p.spacing)), dtype=torch.float32, device=like.device)
+    field = torch.empty((3,) + tuple(grid), dtype=torch.float32, device=like.device)
     res = FFDRefineResult()
-    args = (F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap, C.byref(p), C.byref(res), lattice.data_ptr(),
-            field.data_ptr(), work.data_ptr(), current_stream())
-    if masks is not None:
-        _check(lib().sift3d_amd_ffd_refine_masked_device(*args, *masks), "sift3d_amd_ffd_refine_masked_device")
-    else:
-        _check(lib().sift3d_amd_ffd_refine_device(*args), "sift3d_amd_ffd_refine_device")
+    _run(stem + "_device", *head, ap, C.byref(p), C.byref(res), lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
+         current_stream(), *tail)
     return res, lattice, field
+
+
+def _ffd_refine_pair(what, stem, F, M, A, params, work, mask_fixed, mask_moving, tail=None, count=()):
+    """_ffd_refine for the drivers over one pair of volumes, sized by stem + "_work_bytes" of the two grids, the
+    spacing, the levels and `count` (the landmarks').  params None: the defaults.  tail: what the general drivers take
+    after both masks; None is the MSD driver, which has its masked entry (_masked_entry)."""
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
+    a, ap = _ffd_A(A, what)
+    p = params if params is not None else ffd_refine_params()
+    stem, tail = _masked_entry(stem, masks) if tail is None else (stem, (*(masks or (None, None)), *tail))
+    need = getattr(lib(), stem + "_work_bytes")(*head[1:4], *head[5:8], *p.spacing, p.levels, *count)
+    return _ffd_refine(what, stem, head, F, F.shape, ap, p, work, need,
+                       "levels must be in [1, %d] and the spacing in [1, %d]" % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING),
+                       tail)
+
+
+def _trail(entries, res, *fields):
+    """What a driver left beside its trail (FFDPenalty, FFDLandmarkTerm), one tuple of `fields` per evaluation; None
+    where the term was not asked for"""
+    return None if entries is None else [tuple(getattr(e, f) for f in fields) for e in entries[:res.evaluations]]
 
 
 # ---- Mattes mutual-information free-form deformation ("Mutual-information free-form deformation (Mattes)") ----
@@ -1550,30 +1475,13 @@ def parzen_histogram_field(F, M, field, bins, range_f, range_m, hist=None, work=
                            mask_moving=None):
     """parzen_histogram with the displacement field [3, oz, oy, ox] in the place of A (sift3d_hip_parzen_hist_field):
     (hist int64 [bins, bins], count int64 [1]) on the device, on torch's current stream."""
-    import torch
     what = "parzen_histogram_field"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
     _field_tensor(field, what)
-    _same_device(what, F, M, field)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving, field)
     if tuple(field.shape[1:]) != tuple(F.shape):
         raise ValueError(what + ": the field must be [3, oz, oy, ox] on F's grid")
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
-    bins = _parzen_bins(bins, what)
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    if hist is None:
-        hist = torch.empty((bins, bins), dtype=torch.int64, device=F.device)
-    _tensor(hist, what + ": hist must be a contiguous int64 CUDA tensor [bins, bins] on F's device",
-            shape=(bins, bins), device=F.device, dtype="int64")
-    count = torch.empty(1, dtype=torch.int64, device=F.device)
-    need = lib().sift3d_amd_parzen_hist_work_bytes(ox, oy, oz)
-    work = _work(work, (need + 3) // 4, F, what)
-    _check(lib().sift3d_hip_parzen_hist_field(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, field.data_ptr(),
-                                              bins, *_parzen_ranges(range_f, range_m), hist.data_ptr(), count.data_ptr(),
-                                              work.data_ptr(), current_stream(), *masks),
-           "sift3d_hip_parzen_hist_field")
-    return hist, count
+    return _parzen_hist(what, "sift3d_hip_parzen_hist_field", F, head, masks, field.data_ptr(), bins, range_f, range_m,
+                        hist, work)
 
 
 def ffd_mi_evaluate(F, M, lattice, spacing, W, range_f, range_m, A=None, bending=0.0, work=None, mask_fixed=None,
@@ -1581,78 +1489,40 @@ def ffd_mi_evaluate(F, M, lattice, spacing, W, range_f, range_m, A=None, bending
     """ffd_evaluate for the mutual information (sift3d_hip_ffd_mi_evaluate): psi from the table W [bins, bins] (float64;
     a numpy array is uploaded, a CUDA tensor is used as it is).  Returns (record, grad, field); ffd_record reads the
     record, whose S_ee slot holds S_pp."""
-    import torch
     what = "ffd_mi_evaluate"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
-    gx, gy, gz = _ffd_lattice(lattice, what)
-    _same_device(what, F, M, lattice)
-    dx, dy, dz = ffd_spacing(spacing, what)
-    if not isinstance(W, torch.Tensor):
-        W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(F.device)
-    if W.dim() != 2 or W.shape[0] != W.shape[1]:
-        raise ValueError(what + ": W must be [bins, bins]")
-    bins = _parzen_bins(W.shape[0], what)
-    _tensor(W, what + ": W must be a contiguous float64 tensor [bins, bins] on F's device", shape=(bins, bins),
-            device=F.device, dtype="float64")
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    a, ap = _ffd_A(A, what)
-    record = _ffd_record_tensor(lattice)
-    grad = torch.empty_like(lattice)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    need = lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz)
-    work = _work(work, (need + 3) // 4, F, what)
-    _check(lib().sift3d_hip_ffd_mi_evaluate(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx,
-                                            gy, gz, dx, dy, dz, ap, float(bending), field.data_ptr(),
-                                            record.data_ptr(), grad.data_ptr(), work.data_ptr(), current_stream(),
-                                            *masks, bins, *_parzen_ranges(range_f, range_m), W.data_ptr()),
-           "sift3d_hip_ffd_mi_evaluate")
-    return record, grad, field
+    _ffd_lattice(lattice, what)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving, lattice)
+    W, bins = _parzen_table(what, W, F)
+    args, out, work = _ffd_evaluate_args(what, head, F, lattice, spacing, A, bending, work)
+    _run("sift3d_hip_ffd_mi_evaluate", *args, *(masks or (None, None)), bins, *_parzen_ranges(range_f, range_m),
+         W.data_ptr())
+    return out
 
 
 def ffd_mi_refine(F, M, bins, range_f, range_m, A=None, params=None, work=None, mask_fixed=None, mask_moving=None):
     """sift3d_amd_ffd_mi_refine_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call
     waits for it once per evaluation and once per gradient).  Returns (FFDRefineResult, lattice, field, Similarity: the
     measures at the final lattice)."""
-    import torch
     what = "ffd_mi_refine"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
-    a, ap = _ffd_A(A, what)
-    bins = _parzen_bins(bins, what)
-    p = params if params is not None else ffd_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    d = tuple(p.spacing)
-    need = lib().sift3d_amd_ffd_mi_refine_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
-    if need == 0:
-        raise ValueError(what + ": levels must be in [1, %d] and the spacing in [1, %d]"
-                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
-    work = _work(work, (need + 3) // 4, F, what)
-    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    res = FFDRefineResult()
     sim = Similarity()
-    _check(lib().sift3d_amd_ffd_mi_refine_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap, C.byref(p),
-                                                 C.byref(res), lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
-                                                 current_stream(), *masks, bins, *_parzen_ranges(range_f, range_m),
-                                                 C.byref(sim)),
-           "sift3d_amd_ffd_mi_refine_device")
-    return res, lattice, field, sim
+    tail = (_parzen_bins(bins, what), *_parzen_ranges(range_f, range_m), C.byref(sim))
+    return (*_ffd_refine_pair(what, "sift3d_amd_ffd_mi_refine", F, M, A, params, work, mask_fixed, mask_moving, tail),
+            sim)
 
 
 # ---- Jacobian penalty ("Jacobian penalty") ----
+def _term_record(record, nbytes):
+    """a term's device record, a count and three doubles in its first nbytes = 32, on the host; waits for the stream"""
+    import torch
+    raw = record.view(torch.uint8)[:nbytes].cpu().numpy()
+    v = raw[8:32].view(np.float64)
+    return int(raw[:8].view(np.uint64)[0]), float(v[0]), float(v[1]), float(v[2])
+
+
 def jacobian_penalty_record(record):
     """(nonpos, sum, rmin, rmax) of a penalty record (a CUDA tensor of JACOBIAN_PENALTY_RECORD_BYTES); waits for the
     stream"""
-    import torch
-    raw = record.view(torch.uint8)[:JACOBIAN_PENALTY_RECORD_BYTES].cpu().numpy()
-    v = raw[8:32].view(np.float64)
-    return int(raw[:8].view(np.uint64)[0]), float(v[0]), float(v[1]), float(v[2])
+    return _term_record(record, JACOBIAN_PENALTY_RECORD_BYTES)
 
 
 def jacobian_penalty(field, ref=1.0, gradient=False, work=None):
@@ -1697,36 +1567,13 @@ def ffd_refine_jacobian(F, M, jacobian, bins=0, range_f=(0.0, 1.0), range_m=(0.0
     FFD drivers with the Jacobian penalty of weight `jacobian`; bins == 0: the MSD (the ranges are not read), else the
     mutual information as ffd_mi_refine.  Returns (FFDRefineResult, lattice, field, Similarity or None, penalty: one
     (P, rmin, nonpos) per trail entry)."""
-    import torch
     what = "ffd_refine_jacobian"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
-    a, ap = _ffd_A(A, what)
     bins = _parzen_bins(bins, what) if bins else 0
-    p = params if params is not None else ffd_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    d = tuple(p.spacing)
-    need = lib().sift3d_amd_ffd_refine_jacobian_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels)
-    if need == 0:
-        raise ValueError(what + ": levels must be in [1, %d] and the spacing in [1, %d]"
-                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
-    work = _work(work, (need + 3) // 4, F, what)
-    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    res = FFDRefineResult()
-    sim = Similarity()
-    pen = (FFDPenalty * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
     ranges = _parzen_ranges(range_f, range_m) if bins else (0.0, 1.0, 0.0, 1.0)
-    _check(lib().sift3d_amd_ffd_refine_jacobian_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap,
-                                                       C.byref(p), C.byref(res), lattice.data_ptr(), field.data_ptr(),
-                                                       work.data_ptr(), current_stream(), *masks, bins, *ranges,
-                                                       C.byref(sim), float(jacobian), pen),
-           "sift3d_amd_ffd_refine_jacobian_device")
-    penalty = [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
-    return res, lattice, field, (sim if bins else None), penalty
+    sim, pen = Similarity(), (FFDPenalty * _FFD_TRAIL)()
+    res, lattice, field = _ffd_refine_pair(what, "sift3d_amd_ffd_refine_jacobian", F, M, A, params, work, mask_fixed,
+                                           mask_moving, (bins, *ranges, C.byref(sim), float(jacobian), pen))
+    return res, lattice, field, (sim if bins else None), _trail(pen, res, "P", "rmin", "nonpos")
 
 
 # ---- points and landmarks ("FFD landmarks") ----
@@ -1750,6 +1597,11 @@ def ffd_landmark_arrays(P, Q, w, what):
         if w.shape != (len(P),) or not np.isfinite(w).all() or (w < 0).any():
             raise ValueError("%s: the landmark weights must be n finite values that are not negative" % what)
     return P, Q, w
+
+
+def _landmark_args(P, Q, w, landmark_weight):
+    """ffd_landmark_arrays' three and the term's weight as the evaluation and the driver with landmarks take them"""
+    return P.ctypes.data, Q.ctypes.data, None if w is None else w.ctypes.data, len(P), float(landmark_weight)
 
 
 def ffd_points(lattice, spacing, points, A=None):
@@ -1776,10 +1628,7 @@ def ffd_points(lattice, spacing, points, A=None):
 def ffd_landmarks_record(record):
     """(counted, S, Omega, rmax) of a landmark record (a CUDA tensor of FFD_LANDMARKS_RECORD_BYTES); waits for the
     stream"""
-    import torch
-    raw = record.view(torch.uint8)[:FFD_LANDMARKS_RECORD_BYTES].cpu().numpy()
-    v = raw[8:32].view(np.float64)
-    return int(raw[:8].view(np.uint64)[0]), float(v[0]), float(v[1]), float(v[2])
+    return _term_record(record, FFD_LANDMARKS_RECORD_BYTES)
 
 
 def ffd_landmarks(lattice, spacing, P, Q, w=None, A=None, residuals=True, gradient=True, work=None):
@@ -1812,31 +1661,18 @@ def ffd_evaluate_landmarks(F, M, lattice, spacing, P, Q, w=None, landmark_weight
     four words, read by ffd_landmarks_record, then GL [3, gz, gy, gx]) and the penalty's (the same with GJ) or None."""
     import torch
     what = "ffd_evaluate_landmarks"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
-    gx, gy, gz = _ffd_lattice(lattice, what)
-    _same_device(what, F, M, lattice)
-    dx, dy, dz = ffd_spacing(spacing, what)
+    _ffd_lattice(lattice, what)
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving, lattice)
     P, Q, w = ffd_landmark_arrays(P, Q, w, what)
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    a, ap = _ffd_A(A, what)
-    record = _ffd_record_tensor(lattice)
-    grad = torch.empty_like(lattice)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    work = _work(None, (lib().sift3d_amd_ffd_evaluate_work_bytes(ox, oy, oz, dx, dy, dz) + 3) // 4, F, what)
+    args, out, _ = _ffd_evaluate_args(what, head, F, lattice, spacing, A, bending, None)
+    sizes = (len(P), *head[1:4], *ffd_spacing(spacing, what))
     size = lib().sift3d_amd_ffd_evaluate_landmarks_bytes
-    lm = torch.zeros(size(0, len(P), ox, oy, oz, dx, dy, dz) // 8 + 1, dtype=torch.float64, device=F.device)
-    jac = None if jacobian is None else \
-        torch.zeros(size(1, len(P), ox, oy, oz, dx, dy, dz) // 8 + 1, dtype=torch.float64, device=F.device)
-    _check(lib().sift3d_hip_ffd_evaluate_landmarks(
-        F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap,
-        float(bending), field.data_ptr(), record.data_ptr(), grad.data_ptr(), work.data_ptr(), current_stream(), *masks,
-        0.0 if jacobian is None else float(jacobian), None if jac is None else jac.data_ptr(), P.ctypes.data,
-        Q.ctypes.data, None if w is None else w.ctypes.data, len(P), float(landmark_weight), lm.data_ptr()),
-        "sift3d_hip_ffd_evaluate_landmarks")
-    return record, grad, field, lm, jac
+    lm = torch.zeros(size(0, *sizes) // 8 + 1, dtype=torch.float64, device=F.device)
+    jac = None if jacobian is None else torch.zeros(size(1, *sizes) // 8 + 1, dtype=torch.float64, device=F.device)
+    _run("sift3d_hip_ffd_evaluate_landmarks", *args, *(masks or (None, None)),
+         0.0 if jacobian is None else float(jacobian), None if jac is None else jac.data_ptr(),
+         *_landmark_args(P, Q, w, landmark_weight), lm.data_ptr())
+    return (*out, lm, jac)
 
 
 def ffd_refine_landmarks(F, M, P, Q, w=None, landmark_weight=0.0, jacobian=None, bins=0, range_f=(0.0, 1.0),
@@ -1847,42 +1683,18 @@ def ffd_refine_landmarks(F, M, P, Q, w=None, landmark_weight=0.0, jacobian=None,
     it; bins == 0: the MSD, else the mutual information as ffd_mi_refine.  Returns (FFDRefineResult, lattice, field,
     Similarity or None, penalty: one (P, rmin, nonpos) per trail entry or None, landmarks: one (L, rmax, counted) per
     trail entry)."""
-    import torch
     what = "ffd_refine_landmarks"
-    for t in (F, M):
-        _tensor(t, what + ": F and M must be contiguous 3-D float32 CUDA tensors", dims=(3,))
-    _same_device(what, F, M)
-    masks = _masks(what, F, M, mask_fixed, mask_moving) or (None, None)
     P, Q, w = ffd_landmark_arrays(P, Q, w, what)
-    a, ap = _ffd_A(A, what)
     bins = _parzen_bins(bins, what) if bins else 0
-    p = params if params is not None else ffd_refine_params()
-    oz, oy, ox = F.shape
-    nz, ny, nx = M.shape
-    d = tuple(p.spacing)
-    need = lib().sift3d_amd_ffd_refine_landmarks_work_bytes(ox, oy, oz, nx, ny, nz, d[0], d[1], d[2], p.levels, len(P))
-    if need == 0:
-        raise ValueError(what + ": levels must be in [1, %d] and the spacing in [1, %d]"
-                         % (AFFINE_MAX_LEVELS, FFD_MAX_SPACING))
-    work = _work(work, (need + 3) // 4, F, what)
-    lattice = torch.empty(ffd_lattice_shape(F.shape, d), dtype=torch.float32, device=F.device)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    res = FFDRefineResult()
-    sim = Similarity()
-    pen = None if jacobian is None else (FFDPenalty * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
-    terms = (FFDLandmarkTerm * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
     ranges = _parzen_ranges(range_f, range_m) if bins else (0.0, 1.0, 0.0, 1.0)
-    _check(lib().sift3d_amd_ffd_refine_landmarks_device(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, ap,
-                                                        C.byref(p), C.byref(res), lattice.data_ptr(), field.data_ptr(),
-                                                        work.data_ptr(), current_stream(), *masks, bins, *ranges,
-                                                        C.byref(sim), 0.0 if jacobian is None else float(jacobian), pen,
-                                                        P.ctypes.data, Q.ctypes.data,
-                                                        None if w is None else w.ctypes.data, len(P),
-                                                        float(landmark_weight), terms),
-           "sift3d_amd_ffd_refine_landmarks_device")
-    penalty = None if pen is None else [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
-    landmarks = [(t.L, t.rmax, int(t.counted)) for t in terms[:res.evaluations]]
-    return res, lattice, field, (sim if bins else None), penalty, landmarks
+    sim, terms = Similarity(), (FFDLandmarkTerm * _FFD_TRAIL)()
+    pen = None if jacobian is None else (FFDPenalty * _FFD_TRAIL)()
+    tail = (bins, *ranges, C.byref(sim), 0.0 if jacobian is None else float(jacobian), pen,
+            *_landmark_args(P, Q, w, landmark_weight), terms)
+    res, lattice, field = _ffd_refine_pair(what, "sift3d_amd_ffd_refine_landmarks", F, M, A, params, work, mask_fixed,
+                                           mask_moving, tail, count=(len(P),))
+    return (res, lattice, field, (sim if bins else None), _trail(pen, res, "P", "rmin", "nonpos"),
+            _trail(terms, res, "L", "rmax", "counted"))
 
 
 # ---- multi-channel free-form deformation ("Multi-channel free-form deformation") ----
@@ -1908,25 +1720,16 @@ def _ffd_stack_masks(what, F, M, mask_fixed, mask_moving):
 def ffd_evaluate_channels(F, M, lattice, spacing, A=None, bending=0.0, work=None, mask_fixed=None, mask_moving=None):
     """ffd_evaluate for stacks F [nc, oz, oy, ox] and M [nc, nz, ny, nx] (sift3d_hip_ffd_evaluate_channels) on torch's
     current stream.  Returns (record, grad, field, work): the force S is left in `work` (the header gives its offset)."""
-    import torch
     what = "ffd_evaluate_channels"
     nc, (oz, oy, ox), (nz, ny, nx) = _ffd_stacks(F, M, what)
     masks = _ffd_stack_masks(what, F, M, mask_fixed, mask_moving)
-    gx, gy, gz = _ffd_lattice(lattice, what)
+    _ffd_lattice(lattice, what)
     _same_device(what, F, lattice)
-    dx, dy, dz = ffd_spacing(spacing, what)
-    a, ap = _ffd_A(A, what)
-    record = _ffd_record_tensor(lattice)
-    grad = torch.empty_like(lattice)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=F.device)
-    need = lib().sift3d_amd_ffd_evaluate_channels_work_bytes(ox, oy, oz, dx, dy, dz)
-    work = _work(work, (need + 3) // 4, F, what)
-    _check(lib().sift3d_hip_ffd_evaluate_channels(F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, nc,
-                                                  lattice.data_ptr(), gx, gy, gz, dx, dy, dz, ap, float(bending),
-                                                  field.data_ptr(), record.data_ptr(), grad.data_ptr(),
-                                                  work.data_ptr(), current_stream(), *masks),
-           "sift3d_hip_ffd_evaluate_channels")
-    return record, grad, field, work
+    head = (F.data_ptr(), ox, oy, oz, M.data_ptr(), nx, ny, nz, nc)
+    args, out, work = _ffd_evaluate_args(what, head, F, lattice, spacing, A, bending, work,
+                                         "sift3d_amd_ffd_evaluate_channels_work_bytes")
+    _run("sift3d_hip_ffd_evaluate_channels", *args, *masks)
+    return (*out, work)
 
 
 def ffd_refine_channels(Fs, Ms, A=None, params=None, work=None, masks_fixed=None, masks_moving=None, jacobian=None):
@@ -1934,7 +1737,6 @@ def ffd_refine_channels(Fs, Ms, A=None, params=None, work=None, masks_fixed=None
     level, level 0 the finest, every level the half ((n + 1) // 2 per axis) of the one above; masks_fixed, masks_moving:
     one mask per level on that level's grid, or None.  jacobian: None runs without the penalty, a weight >= 0 with it.
     Returns (FFDRefineResult, lattice, field, penalty: one (P, rmin, nonpos) per trail entry, or None)."""
-    import torch
     what = "ffd_refine_channels"
     levels = len(Fs)
     if not (1 <= levels <= AFFINE_MAX_LEVELS) or len(Ms) != levels:
@@ -1959,21 +1761,12 @@ def ffd_refine_channels(Fs, Ms, A=None, params=None, work=None, masks_fixed=None
         tab[l] = FFDLevel(F.data_ptr(), fg[2], fg[1], fg[0], M.data_ptr(), mg[2], mg[1], mg[0], wf, wm)
     a, ap = _ffd_A(A, what)
     oz, oy, ox = Fs[0].shape[1:]
-    d = tuple(p.spacing)
-    need = lib().sift3d_amd_ffd_refine_channels_work_bytes(ox, oy, oz, d[0], d[1], d[2])
-    if need == 0:
-        raise ValueError(what + ": the spacing must be in [1, %d]" % FFD_MAX_SPACING)
-    work = _work(work, (need + 3) // 4, Fs[0], what)
-    lattice = torch.empty(ffd_lattice_shape((oz, oy, ox), d), dtype=torch.float32, device=Fs[0].device)
-    field = torch.empty((3, oz, oy, ox), dtype=torch.float32, device=Fs[0].device)
-    res = FFDRefineResult()
-    pen = None if jacobian is None else (FFDPenalty * (AFFINE_MAX_LEVELS * FFD_MAX_EVALUATIONS))()
-    _check(lib().sift3d_amd_ffd_refine_channels_device(tab, levels, nc0, ap, C.byref(p), C.byref(res),
-                                                       lattice.data_ptr(), field.data_ptr(), work.data_ptr(),
-                                                       current_stream(), 0.0 if jacobian is None else float(jacobian),
-                                                       pen), "sift3d_amd_ffd_refine_channels_device")
-    penalty = None if pen is None else [(q.P, q.rmin, int(q.nonpos)) for q in pen[:res.evaluations]]
-    return res, lattice, field, penalty
+    need = lib().sift3d_amd_ffd_refine_channels_work_bytes(ox, oy, oz, *p.spacing)
+    pen = None if jacobian is None else (FFDPenalty * _FFD_TRAIL)()
+    res, lattice, field = _ffd_refine(what, "sift3d_amd_ffd_refine_channels", (tab, levels, nc0), Fs[0], (oz, oy, ox),
+                                      ap, p, work, need, "the spacing must be in [1, %d]" % FFD_MAX_SPACING,
+                                      (0.0 if jacobian is None else float(jacobian), pen))
+    return res, lattice, field, _trail(pen, res, "P", "rmin", "nonpos")
 
 
 def _dense_args(src, out, what):
