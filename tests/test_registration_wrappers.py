@@ -3,7 +3,9 @@ work size they ask for against the library's own, whose buffer they write, and t
 The numbers they compute are held elsewhere (tests/test_affine_*.py, test_ffd*.py, test_masks.py,
 test_registration_bytes.py); the volumes here are as small as the entries take, so every case is a handful of launches.
 
-CALLS, inputs, faults, work_bytes and plain are also what a script needs to run two versions of hip.py side by side."""
+CALLS, inputs, faults, work_bytes and plain are also what a script needs to run two versions of hip.py side by side;
+tests/test_calling_contracts.py runs the same calls on a second, larger set of inputs (a Set other than S)."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -16,6 +18,9 @@ SPACING = (3, 2, 4)                                        # (dx, dy, dz)
 LEVELS, EVALUATIONS, BINS, CHANNELS = 2, 3, 4, 2
 RANGE = (0.0, 1.0)
 BENDING, JACOBIAN, LANDMARK_WEIGHT = 0.01, 0.1, 0.05
+# what inputs() is built from; S is the set of every test of this file
+Set = collections.namedtuple("Set", "fshape mshape spacing levels evaluations bins channels")
+S = Set(FSHAPE, MSHAPE, SPACING, LEVELS, EVALUATIONS, BINS, CHANNELS)
 
 CALLS = {
     "affine_normal_equations": lambda h, x, kw: h.affine_normal_equations(x["F"], x["M"], x["A"], raw=True, **kw),
@@ -70,8 +75,16 @@ def call(h, name, x, **kw):
     return CALLS[name](h, x, kw)
 
 
-def inputs(h):
-    """the one set of inputs of every case; nothing in it is written by a call"""
+def pyramid(h, shape, levels):
+    """the grids of `levels` levels under (and with) shape = (nz, ny, nx), each the half of the one above"""
+    out = [tuple(shape)]
+    while len(out) < levels:
+        out.append(h.half_shape(out[-1]))
+    return out
+
+
+def inputs(h, s=S):
+    """the one set of inputs of every case (of the set s); nothing in it is written by a call"""
     import torch
     rng = np.random.default_rng(17)
 
@@ -80,40 +93,55 @@ def inputs(h):
 
     def volume(*shape):
         return dev(rng.random(shape, dtype=np.float32))
-    lattice = h.ffd_lattice_shape(FSHAPE, SPACING)
-    P = np.array([[1.5, 2.0, 1.0], [4.0, 3.5, 2.5], [5.5, 1.0, 3.0]])   # x, y, z inside the fixed grid
+    lattice = h.ffd_lattice_shape(s.fshape, s.spacing)
+    P = np.array([[1.5, 2.0, 1.0], [4.0, 3.5, 2.5], [5.5, 1.0, 3.0]])   # x, y, z inside S's fixed grid
     return dict(
-        F=volume(*FSHAPE), M=volume(*MSHAPE), A=np.array([[1, 0, 0, 0.3], [0, 1, 0, -0.2], [0, 0, 1, 0.1]]),
-        lattice=dev((rng.random(lattice, dtype=np.float32) - 0.5) * 0.6), spacing=SPACING,
-        field=dev((rng.random((3,) + FSHAPE, dtype=np.float32) - 0.5) * 0.6),
-        bins=BINS, W=np.log(rng.random((BINS, BINS)) + 0.5), P=P, Q=P + [0.4, -0.3, 0.2],
+        set=s, F=volume(*s.fshape), M=volume(*s.mshape), A=np.array([[1, 0, 0, 0.3], [0, 1, 0, -0.2], [0, 0, 1, 0.1]]),
+        lattice=dev((rng.random(lattice, dtype=np.float32) - 0.5) * 0.6), spacing=s.spacing,
+        field=dev((rng.random((3,) + tuple(s.fshape), dtype=np.float32) - 0.5) * 0.6),
+        bins=s.bins, W=np.log(rng.random((s.bins, s.bins)) + 0.5), P=P, Q=P + [0.4, -0.3, 0.2],
         w=np.array([1.0, 2.0, 0.5]),
-        Fs=[volume(CHANNELS, *FSHAPE), volume(CHANNELS, *h.half_shape(FSHAPE))],
-        Ms=[volume(CHANNELS, *MSHAPE), volume(CHANNELS, *h.half_shape(MSHAPE))],
-        ap=h.affine_refine_params(levels=LEVELS, max_evaluations=EVALUATIONS),
-        fp=h.ffd_refine_params(spacing=SPACING, levels=LEVELS, max_evaluations=EVALUATIONS))
+        Fs=[volume(s.channels, *g) for g in pyramid(h, s.fshape, s.levels)],
+        Ms=[volume(s.channels, *g) for g in pyramid(h, s.mshape, s.levels)],
+        ap=h.affine_refine_params(levels=s.levels, max_evaluations=s.evaluations),
+        fp=h.ffd_refine_params(spacing=s.spacing, levels=s.levels, max_evaluations=s.evaluations))
 
 
-def mask_kw(h, name, WF, WM):
-    """the wrapper's mask arguments from level 0's two masks (None: absent); the coarser level of the stacks gets ones
-    where level 0 has a mask"""
+def mask_kw(h, name, WF, WM, levels=LEVELS):
+    """the wrapper's mask arguments from level 0's two masks (None: absent); the coarser levels of the stacks (`levels`
+    in all) get ones where level 0 has a mask"""
     import torch
     if name != "ffd_refine_channels":
         return dict(mask_fixed=WF, mask_moving=WM)
 
-    def levels(W, shape):
-        return None if W is None else [W, torch.ones(h.half_shape(shape), dtype=torch.float32, device="cuda")]
-    return dict(masks_fixed=levels(WF, FSHAPE), masks_moving=levels(WM, MSHAPE))
+    def per_level(W):
+        return None if W is None else [W] + [torch.ones(g, dtype=torch.float32, device="cuda")
+                                             for g in pyramid(h, W.shape, levels)[1:]]
+    return dict(masks_fixed=per_level(WF), masks_moving=per_level(WM))
 
 
-def work_bytes(h, name, n_landmarks=3):
-    """the library's own size of the work buffer for the wrapper's call on inputs() without masks"""
+def some_masks(s=S, seed=23):
+    """(WF, WM): masks of 0 and 1 on the two grids of the set s, about four voxels in five in, neither all ones"""
+    import torch
+    rng = np.random.default_rng(seed)
+    out = [torch.from_numpy((rng.random(g) < 0.8).astype(np.float32)).cuda() for g in (s.fshape, s.mshape)]
+    assert all(0 < float(W.sum()) < W.numel() for W in out)
+    return tuple(out)
+
+
+MASKED_SIZE = {"affine_refine", "ffd_refine"}       # the drivers with a size function of their own for the masked entry
+
+
+def work_bytes(h, name, n_landmarks=3, masked=False, s=S):
+    """the library's own size of the work buffer for the wrapper's call on inputs(h, s), without masks or (masked) with
+    one: the two MSD drivers have their *_masked_work_bytes, every other entry one size for both"""
     L = h.lib()
-    f, m, d = FSHAPE[::-1], MSHAPE[::-1], SPACING
+    f, m, d = tuple(s.fshape)[::-1], tuple(s.mshape)[::-1], s.spacing
+    stem = name + "_masked" if masked and name in MASKED_SIZE else name
     if name in AFFINE_REFINES:
-        return getattr(L, "sift3d_amd_%s_work_bytes" % name)(*f, *m, LEVELS)
+        return getattr(L, "sift3d_amd_%s_work_bytes" % stem)(*f, *m, s.levels)
     if name in FFD_REFINES - STACKS:
-        return getattr(L, "sift3d_amd_%s_work_bytes" % name)(*f, *m, *d, LEVELS,
+        return getattr(L, "sift3d_amd_%s_work_bytes" % stem)(*f, *m, *d, s.levels,
                                                              *((n_landmarks,) if name in LANDMARKS else ()))
     return {"affine_normal_equations": lambda: L.sift3d_amd_affine_normal_work_bytes(*f),
             "affine_ncc_normal_equations": lambda: L.sift3d_amd_affine_ncc_normal_work_bytes(*f),
@@ -218,16 +246,22 @@ def test_refusals_carry_the_wrappers_name(hip, x, name):
 
 @pytest.mark.parametrize("name", [n for n in NAMES if n not in NO_WORK])
 def test_work_is_the_librarys_size(hip, x, name):
+    """need - 1 bytes are refused and need accepted, without masks and with two that are not all ones (where the
+    masked entry has a size of its own, that one; never less than the unmasked)"""
     import torch
-    need = work_bytes(hip, name)
-    assert need > 0
-    with pytest.raises(ValueError) as e:
-        call(hip, name, x, work=torch.empty(need - 1, dtype=torch.uint8, device="cuda"))
-    assert str(e.value).startswith(name + ": work "), str(e.value)
-    work = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = call(hip, name, x, work=work)
-    if name == "ffd_evaluate_channels":
-        assert out[3] is work
+    for masked in (False, True):
+        kw = mask_kw(hip, name, *some_masks()) if masked else {}
+        need = work_bytes(hip, name, masked=masked)
+        assert need >= work_bytes(hip, name) > 0
+        if name in MASKED_SIZE:
+            assert masked == (need > work_bytes(hip, name))
+        with pytest.raises(ValueError) as e:
+            call(hip, name, x, work=torch.empty(need - 1, dtype=torch.uint8, device="cuda"), **kw)
+        assert str(e.value).startswith(name + ": work "), (masked, str(e.value))
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+        out = call(hip, name, x, work=work, **kw)
+        if name == "ffd_evaluate_channels":
+            assert out[3] is work
 
 
 @pytest.mark.parametrize("name", sorted(set(RECORD) | HIST))
