@@ -1047,6 +1047,171 @@ sift3d_amd_affine_mi_refine_device(const float *d_F, int ox, int oy, int oz, con
                                    void *d_work, void *stream, const float *d_WF, const float *d_WM);
 
 /* ------------------------------------------------------------------------ */
+/* Initial transforms: moments and candidate search                          */
+/* ------------------------------------------------------------------------ */
+/* Every intensity refinement here is a local descent and has to be handed a start.  This section makes one from the
+ * two volumes alone: the moments of each (centre of mass, principal axes), a list of candidate rigid pull maps about
+ * the two centres (the centres alone, the four proper rotations that map one principal frame onto the other, or a
+ * coarse grid of rotations and offsets), all candidates scored in one call at a coarse level, and the best of them
+ * carried to level 0.  Everything is in voxels.  No upstream counterpart: PARITY UNPINNED, pinned to this contract and
+ * to its numpy restatement (tests/affine_init_restatement.py).
+ *
+ * Moments (sift3d_hip_moments).  Per voxel p of V[nz][ny][nx]: w = V(p) - floor (a float subtraction); the voxel counts
+ * when w > 0 (a NaN never does) and, with a mask d_W, when the mask is in ("Masks": in where >= 0.5).  Its weight is
+ * W = (double) w (SIFT3D_AMD_MOMENTS_INTENSITY) or W = 1.0 (SIFT3D_AMD_MOMENTS_BINARY, the geometric form: moments
+ * weighted by intensity change with the contrast, so the binary form is the one that serves two modalities).
+ * Coordinates are centred on the grid, P = p - c, c = ((nx-1)/2, (ny-1)/2, (nz-1)/2), exact in double: the centring
+ * of the affine normal equations.  The record, SIFT3D_AMD_MOMENTS_BYTES, 8-byte aligned:
+ *     bytes 0-7 uint64 n; then ten doubles: S0 = sum W; S1[3] = sum W P_d; S2[6] = sum (W P_d) P_e for (d, e) = xx, xy,
+ *     xz, yy, yz, zz; the products unfused, in the order written.
+ * The sums are per-lane, then per-workgroup partials (one slot per workgroup of a grid of min(tiles,
+ * SIFT3D_AMD_SIMILARITY_GRID) workgroups, whatever the device; a tile is 64 x 4 x 4 voxels), then the slots in a fixed
+ * order: a call repeats its bytes, and the bytes depend on the shapes only.  n == 0 leaves the record all zero.
+ * The entry is asynchronous on `stream`, allocates nothing, uses 64-bit offsets and checks its arguments before any
+ * device call: -1 on NULL pointers (d_W may be NULL), dims <= 0, a floor that is not finite, an unknown weight, a
+ * misaligned buffer (record, work: 8 bytes; the rest 4), an output that overlaps an input or the other output, a grid
+ * with too many tiles.  d_work: sift3d_amd_moments_work_bytes() bytes.
+ *
+ * Frame (sift3d_amd_moments_frame; host, double).  mu = S1 / S0, centroid = c + mu, C_de = S2_de / S0 - mu_d mu_e; the
+ * eigen-decomposition of C by cyclic Jacobi (rotations (0,1), (0,2), (1,2) per sweep; theta = (C_qq - C_pp) / (2 C_pq),
+ * t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c; until the squared off-diagonal sum is
+ * at most 1e-60 of the squared absolute trace).  lambda[3]: the eigenvalues, descending (equal ones in the order of
+ * their diagonal position); axes[9]: the eigenvectors as ROWS.  Signs: in rows 0 and 1 the component of largest
+ * magnitude is positive (the lowest index among equal magnitudes); row 2 = row 0 x row 1, so det = +1 always.
+ * -1, with nothing written, when n == 0, S0 <= 0 or anything is not finite.
+ *
+ * Batched similarity (sift3d_hip_similarity_affine_batch, _masked).  K affine pull maps A[K][12] (host), 1 <= K <=
+ * SIFT3D_AMD_SIMILARITY_BATCH_MAX, scored in one call.  The contract is one sentence: candidate k's histogram
+ * d_hist[k][bins][bins] and stats record (d_stats + k * SIFT3D_AMD_SIMILARITY_STATS_BYTES) are, byte for byte, what
+ * sift3d_hip_similarity_affine (_masked) writes for A_k with the same other arguments.  bins == 0 with d_hist == NULL
+ * asks for the stats records alone: no histogram, in memory or in LDS (what MSD and NCC scoring use); bins == 0 with a
+ * histogram, or bins > 0 without one, is refused.  The maps are read from the caller's array inside the call (they
+ * travel as kernel arguments), so the array may be reused when the call returns; the entry waits for nothing.  It
+ * refuses what the single entry refuses, for every candidate, before any device call: a non-finite A_k anywhere gives
+ * -1 and nothing is launched.  d_work: sift3d_amd_similarity_batch_work_bytes() bytes, 8-byte aligned.
+ *
+ * Candidates (sift3d_amd_affine_init_candidates; host, double).  A candidate is a rigid pull map about the two
+ * centroids, q = R (p - c_F) + c_M + t, stored as L = R and
+ *     A[d][3] = (c_M[d] + t[d]) - ((R[d][0] c_Fx + R[d][1] c_Fy) + R[d][2] c_Fz)        (unfused).
+ *   CENTROID: K = 1, R = I, t = 0.
+ *   AXES:     K = 5.  Candidate 0 is the centroid one; candidates 1-4 are R = V_M^T (D_s V_F), V the axes matrices
+ *             (rows are eigenvectors), D_s = diag(1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1) in that order: the four
+ *             proper rotations that map F's principal frame onto M's.
+ *   SEARCH:   R = Rz(gamma) (Ry(beta) Rx(alpha)); each angle runs over -range_deg[d] .. +range_deg[d] in steps of
+ *             step_deg, value i of 2 floor(range / step) + 1 being (i - floor(range / step)) * step (range 0: the single
+ *             value 0); crossed with offsets t_d over -range_vox[d] .. +range_vox[d] in steps of step_vox, formed the
+ *             same way.  The index runs alpha fastest, then beta, gamma, t_x, t_y, t_z.  cos and sin are taken of
+ *             a * (pi / 180) in double; a matrix product's entry is (a0 b0 + a1 b1) + a2 b2, unfused.  The defaults
+ *             (90, 90, 90 by 30 degrees, no offsets) make 343 candidates.
+ * *K on entry: the maps A_out holds; on return: the count.  A_out == NULL asks for the count alone.  -1 on a frame that
+ * is not finite, an unknown mode, a range < 0 or a step <= 0 (or either not finite), more than
+ * SIFT3D_AMD_INIT_MAX_CANDIDATES candidates, or an A_out that is too small.
+ *
+ * Ranking (sift3d_amd_affine_init_rank; host).  stats: K records; hist: K histograms (MI; else it may be NULL).  Cost:
+ *   MSD: msd;  NCC: 1 - ncc^2 (a negative gain is as good as a positive one, as in the NCC refinement);  MI: -mi, of
+ *   sift3d_amd_similarity_measures on the candidate's histogram.  NaN when n_k == 0.
+ * A candidate is eligible when n_k >= min_overlap * max_j n_j, n_k > 0 and its cost is finite.  order_out lists the
+ * *count_out eligible candidates by ascending cost, ties going to the lower index.  cost_out and n_out (K each) are
+ * written for every candidate.  -1 when none is eligible (the outputs are written all the same), or on bad arguments.
+ *
+ * Driver (sift3d_amd_affine_init_device).
+ *   1. levels' = sift3d_amd_affine_init_levels(): the largest l <= levels for which no axis of either volume falls
+ *      below 8 on level l - 1.  Volumes and masks are restricted levels' - 1 times, as sift3d_amd_affine_refine_device
+ *      restricts them (sift3d_hip_restrict2 at scale 1; the masks as floats).
+ *   2. The moments of both on the coarsest level (floor_f, floor_m, weight; each volume's mask).
+ *   3. The frames and the candidates there; range_vox and step_vox are level-0 voxels and are halved per level.
+ *   4. The scores, LINEAR, through the batch entry in chunks of at most SIFT3D_AMD_SIMILARITY_BATCH_MAX: one copy to
+ *      the host and one wait per chunk (and one for the two moments records).  MI scores with bins and the two ranges;
+ *      MSD and NCC with bins == 0.
+ *   5. The ranking.  The best map goes to level 0 as the affine driver carries a map up: the translation column
+ *      doubles per level.  The frames are reported in level-0 voxels (centroid x 2, lambda x 4 per level).
+ * costs_out, counts_out: K doubles / uint64 for every candidate's cost and count, or NULL.  The driver keeps host
+ * scratch of its own (malloc) for the candidates and a chunk's records.  -1 on bad arguments (as the refinement
+ * drivers), when a volume has nothing above its floor, or when no candidate is eligible (result->K, levels and the
+ * frames are then written, and the caller's arrays too). */
+#define SIFT3D_AMD_MOMENTS_BYTES 88                /* 8 + 10 * 8 */
+#define SIFT3D_AMD_MOMENTS_INTENSITY 0
+#define SIFT3D_AMD_MOMENTS_BINARY 1
+#define SIFT3D_AMD_SIMILARITY_BATCH_MAX 1024
+#define SIFT3D_AMD_INIT_MAX_CANDIDATES 16384
+#define SIFT3D_AMD_INIT_KEEP 16
+#define SIFT3D_AMD_INIT_CENTROID 0
+#define SIFT3D_AMD_INIT_AXES 1
+#define SIFT3D_AMD_INIT_SEARCH 2
+#define SIFT3D_AMD_INIT_MSD 0
+#define SIFT3D_AMD_INIT_NCC 1
+#define SIFT3D_AMD_INIT_MI 2
+typedef struct {
+    double centroid[3], axes[9], lambda[3];
+} sift3d_amd_frame;
+typedef struct {
+    int mode, metric, levels, weight;
+    float floor_f, floor_m;
+    int bins;                                    /* MI */
+    float lo_f, hi_f, lo_m, hi_m;                /* MI */
+    double range_deg[3], step_deg;               /* SEARCH: about x, y, z */
+    double range_vox[3], step_vox;               /* SEARCH: level-0 voxels */
+    double min_overlap;
+} sift3d_amd_affine_init_params;
+typedef struct {
+    double A[12];                                /* the best candidate on level 0 */
+    int index, K, levels, kept;                  /* its index; the candidates; the levels run; entries of keep_* */
+    double cost;
+    uint64_t n;
+    sift3d_amd_frame frame_f, frame_m;   /* level-0 voxels */
+    int keep_index[SIFT3D_AMD_INIT_KEEP];        /* the best candidates, ascending cost */
+    double keep_cost[SIFT3D_AMD_INIT_KEEP];
+    uint64_t keep_n[SIFT3D_AMD_INIT_KEEP];
+} sift3d_amd_affine_init_result;
+/* bytes of d_work for sift3d_hip_moments on this grid (0 for dims <= 0) */
+SIFT3D_AMD_API size_t sift3d_amd_moments_work_bytes(int nx, int ny, int nz);
+/* d_V [nz][ny][nx]; d_W its mask or NULL; d_record the record above */
+SIFT3D_AMD_API int
+sift3d_hip_moments(const float *d_V, int nx, int ny, int nz, const float *d_W, int weight, float floor, void *d_record,
+                   void *d_work, void *stream);
+/* host only: record on the host */
+SIFT3D_AMD_API int
+sift3d_amd_moments_frame(const void *record, int nx, int ny, int nz, double *centroid /*3*/, double *axes /*9*/,
+                         double *lambda /*3*/);
+/* bytes of d_work for a batch call with these arguments (0 for dims <= 0, bins or K out of range, too many tiles) */
+SIFT3D_AMD_API size_t sift3d_amd_similarity_batch_work_bytes(int ox, int oy, int oz, int bins, int K);
+/* A [K][12] on the host; d_hist [K][bins][bins] uint64 or NULL (bins == 0); d_stats K records */
+SIFT3D_AMD_API int
+sift3d_hip_similarity_affine_batch(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                   const double *A, int K, int interp, int bins, float lo_f, float hi_f, float lo_m,
+                                   float hi_m, uint64_t *d_hist, void *d_stats, void *d_work, void *stream);
+SIFT3D_AMD_API int
+sift3d_hip_similarity_affine_batch_masked(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny,
+                                          int nz, const double *A, int K, int interp, int bins, float lo_f, float hi_f,
+                                          float lo_m, float hi_m, uint64_t *d_hist, void *d_stats, void *d_work,
+                                          void *stream, const float *d_WF, const float *d_WM);
+SIFT3D_AMD_API void sift3d_amd_affine_init_default_params(sift3d_amd_affine_init_params *p);
+/* sizeof the params (0), the frame (1), the result (2); SIFT3D_AMD_MOMENTS_BYTES (3), SIFT3D_AMD_SIMILARITY_BATCH_MAX
+ * (4), SIFT3D_AMD_INIT_MAX_CANDIDATES (5), SIFT3D_AMD_INIT_KEEP (6); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_affine_init_struct_bytes(int which);
+/* host only; params NULL: the defaults */
+SIFT3D_AMD_API int
+sift3d_amd_affine_init_candidates(int mode, const sift3d_amd_frame *frame_F,
+                                  const sift3d_amd_frame *frame_M, const sift3d_amd_affine_init_params *params,
+                                  double *A_out /* K x 12 */, int *K);
+/* host only */
+SIFT3D_AMD_API int
+sift3d_amd_affine_init_rank(int metric, int K, const void *stats, const uint64_t *hist, int bins, double min_overlap,
+                            double *cost_out, uint64_t *n_out, int *order_out, int *count_out);
+/* the levels the driver runs for `levels` asked (0 for levels < 1) */
+SIFT3D_AMD_API int sift3d_amd_affine_init_levels(int ox, int oy, int oz, int nx, int ny, int nz, int levels);
+/* bytes of d_work for the driver (0 for bad arguments); params NULL: the defaults */
+SIFT3D_AMD_API size_t
+sift3d_amd_affine_init_work_bytes(int ox, int oy, int oz, int nx, int ny, int nz,
+                                  const sift3d_amd_affine_init_params *params);
+/* d_WF, d_WM the masks or NULL; result, costs_out, counts_out on the host; waits for `stream` */
+SIFT3D_AMD_API int
+sift3d_amd_affine_init_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                              const float *d_WF, const float *d_WM, const sift3d_amd_affine_init_params *params,
+                              sift3d_amd_affine_init_result *result, double *costs_out, uint64_t *counts_out,
+                              void *d_work, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Mutual-information free-form deformation (Mattes)                         */
 /* ------------------------------------------------------------------------ */
 /* "B-spline free-form deformation" for two volumes whose intensities are related by an unknown map that need not be

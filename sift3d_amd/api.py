@@ -619,7 +619,8 @@ def _matched_points(moving, fixed, nn_thresh, detector_kw, what):
     return d_mov.xyz()[hit], d_fix.xyz()[m[hit]]
 
 
-def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1, refine=False, **detector_kw):
+def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1, refine=False, init=None,
+             **detector_kw):
     """Register two volumes (torch CUDA float32 tensors [nz, ny, nx]): detect + describe both,
     match the descriptors, fit the moving -> fixed affine by RANSAC and resample `moving` into
     `fixed`'s grid.  detector_kw go to Detector().  Returns Registration(A (3 x 4, moving voxel ->
@@ -630,26 +631,39 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
     NccAffineRefinement with refine=dict(metric="ncc"), the MiAffineRefinement with refine=dict(metric="mi")).
     Where the matches give RANSAC no model the call raises RuntimeError, but with refine=dict(metric="mi") it goes on
     from the identity (A_ransac is then the identity and inliers is all False): keypoints of two modalities often do
-    not match, and that is the pair the mutual information is for."""
+    not match, and that is the pair the mutual information is for.
+    init: a mode of init_affine or a dict of its keyword arguments.  Where RANSAC finds no model the flow then goes on
+    from init_affine's map, for any metric, instead of raising or taking the identity (A_ransac and inliers as above);
+    its metric and masks default to the refinement's.  Where RANSAC finds a model init is not used."""
     p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
-    return _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine)
+    return _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine, init)
 
 
-def _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine):
+def _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine, init=None):
     """register() from the matched points on: RANSAC, the optional affine refinement, the resampling"""
     import torch
     from . import hip
+    start = None                                            # the pull map to go on from, where RANSAC gave none
     try:
         A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
     except RuntimeError:
         # across modalities the descriptors often do not match (an inverted contrast already leaves none): the
-        # mutual-information refinement, made for such pairs, then starts from the identity
-        if not (isinstance(refine, dict) and refine.get("metric") == "mi"):
+        # mutual-information refinement, made for such pairs, then starts from the identity, and any refinement from
+        # init_affine's map where the caller asked for one
+        rkw = refine if isinstance(refine, dict) else {}
+        if init is not None:
+            start = init_affine(moving, fixed, **_init_keywords(
+                init, "register", metric=rkw.get("metric", "msd"), mask_fixed=rkw.get("mask_fixed"),
+                mask_moving=rkw.get("mask_moving"))).A
+        elif rkw.get("metric") != "mi":
             raise
         A, inl = np.eye(3, 4), np.zeros(len(p_mov), bool)
     if refine:
-        r = refine_affine(moving, fixed, affine_invert(A), **(refine if isinstance(refine, dict) else {}))
+        r = refine_affine(moving, fixed, affine_invert(A) if start is None else start,
+                          **(refine if isinstance(refine, dict) else {}))
         return RefinedRegistration(affine_invert(r.A), inl, len(p_mov), r.warped, A, r)
+    if start is not None:
+        A = affine_invert(start)
     warped = torch.empty_like(fixed)
     hip.warp_affine(moving, warped, affine_invert(A), "linear")
     return Registration(A, inl, len(p_mov), warped)
@@ -1105,8 +1119,99 @@ def _levels_and_evaluations(what, levels, params, max_evaluations):
         raise ValueError("%s: max_evaluations must be in [1, %d]" % (what, max_evaluations))
 
 
+AffineInit = collections.namedtuple(
+    "AffineInit", "A cost count index candidates costs counts centroid_fixed centroid_moving axes_fixed axes_moving "
+                  "order")
+INIT_BINS = 32
+
+
+def _init_keywords(init, what, **defaults):
+    """init_affine's keyword arguments from an `init` argument: a mode name or a dict of them; `defaults` fill in what
+    it leaves out"""
+    if isinstance(init, str):
+        kw = dict(mode=init)
+    elif isinstance(init, dict):
+        kw = dict(init)
+    else:
+        raise ValueError("%s: init must be a mode name ('centroid', 'axes', 'search') or a dict of init_affine's "
+                         "keyword arguments, not %r" % (what, init))
+    for k, v in defaults.items():
+        if v is not None:
+            kw.setdefault(k, v)
+    return kw
+
+
+def init_affine(moving, fixed, mode="search", metric="mi", levels=3, weight="binary", floor_fixed=None,
+                floor_moving=None, mask_fixed=None, mask_moving=None, bins=None, range_fixed=None, range_moving=None,
+                **search):
+    """A start for refine_affine made from the two volumes alone (contract: include/sift3d_amd.h, "Initial transforms:
+    moments and candidate search"): rigid candidate pull maps (fixed voxel -> moving voxel) about the two centres of
+    mass, all scored by `metric` ("msd", "ncc", "mi") in one call on volumes restricted levels - 1 times (fewer where an
+    axis would fall below 8), the best one returned on the full grids.  mode: "centroid" (the centres aligned, no
+    rotation), "axes" (that, and the four proper rotations that map the fixed volume's principal axes onto the moving
+    volume's), "search" (a grid of rotations Rz Ry Rx and offsets: range_deg and range_vox (a number or three, about /
+    along x, y, z), step_deg, step_vox; the defaults, 90 degrees by 30 and no offsets, make 343 candidates).  The
+    moments are taken over the voxels above a floor (None: the volume's minimum, one host synchronisation), with
+    weight "binary" (geometric: what two modalities share) or "intensity".  bins (None: 32) and range_fixed,
+    range_moving (None: the volume's own) are the histogram's for "mi".  min_overlap (0.5): a candidate must count that
+    share of the best-overlapping candidate's voxels.  mask_fixed, mask_moving: as similarity's; they bound the moments
+    too.  Returns AffineInit(A, cost, count, index: of the best candidate; candidates [K, 3, 4]: all of them on the full
+    grids; costs, counts [K]; centroid_fixed, centroid_moving (x, y, z), axes_fixed, axes_moving (rows); order: the best
+    candidates by ascending cost, 16 at most).  RuntimeError where a volume has nothing above its floor or no candidate
+    is eligible."""
+    from . import hip
+    what = "init_affine"
+    if metric not in hip.INIT_METRIC:
+        raise ValueError("%s: metric must be 'msd', 'ncc' or 'mi', not %r" % (what, metric))
+    if mode not in hip.INIT_MODE:
+        raise ValueError("%s: mode must be 'centroid', 'axes' or 'search', not %r" % (what, mode))
+    if weight not in hip.MOMENTS_WEIGHT:
+        raise ValueError("%s: weight must be 'binary' or 'intensity', not %r" % (what, weight))
+    if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
+        raise ValueError("%s: bins, range_fixed and range_moving belong to metric='mi', not %r" % (what, metric))
+    for k in search:
+        if k not in ("range_deg", "step_deg", "range_vox", "step_vox", "min_overlap"):
+            raise ValueError("%s: unknown parameter %r" % (what, k))
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
+            not 1 <= int(levels) <= hip.AFFINE_MAX_LEVELS:
+        raise ValueError("%s: levels must be in [1, %d]" % (what, hip.AFFINE_MAX_LEVELS))
+    if metric == "mi":
+        bins = INIT_BINS if bins is None else bins
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or \
+                not 2 <= int(bins) <= hip.SIMILARITY_MAX_BINS:
+            raise ValueError("%s: bins must be in [2, %d]" % (what, hip.SIMILARITY_MAX_BINS))
+        _mi_ranges(what, range_fixed, range_moving)
+    WF = _mask_host(mask_fixed, fixed, what, "mask_fixed")
+    WM = _mask_host(mask_moving, moving, what, "mask_moving")
+    F = _similarity_volume(fixed, what, "fixed")
+    M = _similarity_volume(moving, what, "moving", F.device)
+    WF = _mask_tensor(WF, F, what, "mask_fixed")
+    WM = _mask_tensor(WM, F, what, "mask_moving")
+    kw = dict(mode=mode, metric=metric, levels=int(levels), weight=weight, **search)
+    kw["floor_f"] = float(F.min()) if floor_fixed is None else float(floor_fixed)
+    kw["floor_m"] = float(M.min()) if floor_moving is None else float(floor_moving)
+    if metric == "mi":
+        (kw["lo_f"], kw["hi_f"]), (kw["lo_m"], kw["hi_m"]) = _own_range(F, range_fixed), _own_range(M, range_moving)
+        kw["bins"] = int(bins)
+    p = hip.affine_init_params(**kw)
+    res, costs, counts = hip.affine_init(F, M, p, mask_fixed=WF, mask_moving=WM)
+    # every candidate on the full grids, as the driver made them on the coarsest: the frames and offsets there (exact:
+    # powers of two), the translation column back up
+    scale = 2.0 ** (res.levels - 1)
+    frames = [(np.array(f.centroid[:]) / scale, np.array(f.axes[:]), np.array(f.lambda_[:]))
+              for f in (res.frame_f, res.frame_m)]
+    kw["range_vox"] = np.array(p.range_vox[:]) / scale
+    kw["step_vox"] = p.step_vox / scale
+    cands = hip.affine_init_candidates(mode, frames[0], frames[1], hip.affine_init_params(**kw))
+    cands[:, :, 3] *= scale
+    return AffineInit(np.array(res.A[:], np.float64).reshape(3, 4), float(res.cost), int(res.n), int(res.index), cands,
+                      costs, counts.astype(np.int64), np.array(res.frame_f.centroid[:]),
+                      np.array(res.frame_m.centroid[:]), np.array(res.frame_f.axes[:]).reshape(3, 3),
+                      np.array(res.frame_m.axes[:]).reshape(3, 3), np.array(res.keep_index[:res.kept], np.int64))
+
+
 def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear", mask_fixed=None, mask_moving=None,
-                  metric="msd", bins=None, range_fixed=None, range_moving=None, **params):
+                  metric="msd", bins=None, range_fixed=None, range_moving=None, init=None, **params):
     """Move the 3 x 4 affine pull map A (fixed voxel -> moving voxel, as similarity's transform; None: the identity,
     which needs no equal shapes) towards a smaller mean squared difference between `fixed` and `moving` seen through
     it, by Levenberg-Marquardt steps on the device's Gauss-Newton normal equations (contract: include/sift3d_amd.h,
@@ -1131,11 +1236,16 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     the volume's own min and max, one host synchronisation each) set the histogram and are level 0's on every level.  It
     returns MiAffineRefinement: NccAffineRefinement's fields without gain and offset, `cost` = -mi per evaluation, then
     mi and nmi at the final A and bins; `warped` is `moving` through A, not remapped.  bins or a range with another
-    metric, and any other metric, raise ValueError."""
+    metric, and any other metric, raise ValueError.
+    init: a mode of init_affine ("centroid", "axes", "search") or a dict of its keyword arguments: the refinement then
+    starts from init_affine's map, for pairs that the identity does not bring into the capture range.  Its metric,
+    masks, bins and ranges default to the refinement's own.  Only with A=None: ValueError otherwise."""
     import torch
     from . import hip
     if metric not in ("msd", "ncc", "mi"):
         raise ValueError("refine_affine: metric must be 'msd', 'ncc' or 'mi', not %r" % (metric,))
+    if init is not None and A is not None:
+        raise ValueError("refine_affine: init makes the start itself; it goes with A=None only")
     if metric != "mi" and not (bins is None and range_fixed is None and range_moving is None):
         raise ValueError("refine_affine: bins, range_fixed and range_moving belong to metric='mi', not %r" % (metric,))
     if metric == "mi":
@@ -1158,6 +1268,12 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     M = _similarity_volume(moving, "refine_affine", "moving", F.device)
     WF = _mask_tensor(WF, F, "refine_affine", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_affine", "mask_moving")
+    if init is not None:
+        mi = dict(bins=bins, range_fixed=range_fixed, range_moving=range_moving) if metric == "mi" else {}
+        ikw = _init_keywords(init, "refine_affine", metric=metric, mask_fixed=WF, mask_moving=WM)
+        if ikw["metric"] == "mi":
+            ikw = _init_keywords(ikw, "refine_affine", **mi)
+        A0 = init_affine(M, F, **ikw).A
     if metric == "ncc":
         res, fit = hip.affine_ncc_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     elif metric == "mi":
@@ -1458,7 +1574,7 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
 
 def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
                  ffd_params=None, refine=True, landmarks=False, landmark_weight=FFD_LANDMARK_WEIGHT,
-                 landmark_err_thresh=DEFORMABLE_ERR_THRESH, **detector_kw):
+                 landmark_err_thresh=DEFORMABLE_ERR_THRESH, init=None, **detector_kw):
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
     refine_ffd's further keyword arguments (dict(metric="mi") for a mutual-information FFD stage, which then returns
@@ -1471,11 +1587,12 @@ def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.
     on the same matches at landmark_err_thresh (DEFORMABLE_ERR_THRESH, wider than err_thresh for
     register_deformable's reason: a match that a deformation moved off the affine model is the one the deformable stage
     wants) with the same num_iter and seed go to refine_ffd as landmarks (fixed xyz, moving xyz) with landmark_weight.
-    Where RANSAC finds no such inlier the FFD stage runs without the term."""
+    Where RANSAC finds no such inlier the FFD stage runs without the term.  init: register's."""
     F = _similarity_volume(fixed, "register_ffd", "fixed")
     M = _similarity_volume(moving, "register_ffd", "moving", F.device)
     p_mov, p_fix = _matched_points(M, F, nn_thresh, detector_kw, "register_ffd")
-    reg = _register_matched(M, F, p_mov, p_fix, err_thresh, num_iter, seed, refine if isinstance(refine, dict) else True)
+    reg = _register_matched(M, F, p_mov, p_fix, err_thresh, num_iter, seed, refine if isinstance(refine, dict) else True,
+                            init)
     kw = dict(ffd_params or {})
     if landmarks:
         try:

@@ -1636,3 +1636,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* Euclidean distance transforms, label surfaces and the surface-distance measures */
 #include "sift3d_distance.c"
+
+/* initial transforms: moments, batched similarity, candidate maps, ranking and the driver */
+#include "sift3d_init.c"

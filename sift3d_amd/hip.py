@@ -93,6 +93,31 @@ class AffineRefineResult(C.Structure):                     # sift3d_amd_affine_r
                 ("trail", AffineEvaluation * (AFFINE_MAX_LEVELS * AFFINE_MAX_EVALUATIONS))]
 
 
+class Frame(C.Structure):                                  # sift3d_amd_frame
+    _fields_ = [("centroid", C.c_double * 3), ("axes", C.c_double * 9), ("lambda_", C.c_double * 3)]
+
+
+class AffineInitParams(C.Structure):                       # sift3d_amd_affine_init_params
+    _fields_ = [("mode", C.c_int), ("metric", C.c_int), ("levels", C.c_int), ("weight", C.c_int),
+                ("floor_f", C.c_float), ("floor_m", C.c_float), ("bins", C.c_int),
+                ("lo_f", C.c_float), ("hi_f", C.c_float), ("lo_m", C.c_float), ("hi_m", C.c_float),
+                ("range_deg", C.c_double * 3), ("step_deg", C.c_double),
+                ("range_vox", C.c_double * 3), ("step_vox", C.c_double), ("min_overlap", C.c_double)]
+
+
+MOMENTS_BYTES = 88                                         # checked against the library when it is bound (lib())
+SIMILARITY_BATCH_MAX = 1024
+INIT_MAX_CANDIDATES = 16384
+INIT_KEEP = 16
+
+
+class AffineInitResult(C.Structure):                       # sift3d_amd_affine_init_result
+    _fields_ = [("A", C.c_double * 12), ("index", C.c_int), ("K", C.c_int), ("levels", C.c_int), ("kept", C.c_int),
+                ("cost", C.c_double), ("n", C.c_uint64), ("frame_f", Frame), ("frame_m", Frame),
+                ("keep_index", C.c_int * INIT_KEEP), ("keep_cost", C.c_double * INIT_KEEP),
+                ("keep_n", C.c_uint64 * INIT_KEEP)]
+
+
 class Similarity(C.Structure):                             # sift3d_amd_similarity
     _fields_ = [("n", C.c_uint64), ("msd", C.c_double), ("ncc", C.c_double), ("mi", C.c_double), ("nmi", C.c_double),
                 ("entropy_fixed", C.c_double), ("entropy_moving", C.c_double), ("entropy_joint", C.c_double)]
@@ -250,6 +275,24 @@ def lib():
                                                 + masks),
         "sift3d_hip_similarity_field_masked": (C.c_int, pair + [vp, C.c_int, C.c_int] + parzen + [vp, vp, vp, vp]
                                                + masks),
+        "sift3d_amd_moments_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_hip_moments": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]),
+        "sift3d_amd_moments_frame": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp]),
+        "sift3d_amd_similarity_batch_work_bytes": (C.c_size_t, [C.c_int] * 5),
+        "sift3d_hip_similarity_affine_batch": (C.c_int, pair + [dp, C.c_int, C.c_int, C.c_int] + parzen
+                                               + [vp, vp, vp, vp]),
+        "sift3d_hip_similarity_affine_batch_masked": (C.c_int, pair + [dp, C.c_int, C.c_int, C.c_int] + parzen
+                                                      + [vp, vp, vp, vp] + masks),
+        "sift3d_amd_affine_init_default_params": (None, [C.POINTER(AffineInitParams)]),
+        "sift3d_amd_affine_init_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_amd_affine_init_candidates": (C.c_int, [C.c_int, C.POINTER(Frame), C.POINTER(Frame),
+                                                        C.POINTER(AffineInitParams), dp, C.POINTER(C.c_int)]),
+        "sift3d_amd_affine_init_rank": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, dp, vp, vp,
+                                                  C.POINTER(C.c_int)]),
+        "sift3d_amd_affine_init_levels": (C.c_int, [C.c_int] * 7),
+        "sift3d_amd_affine_init_work_bytes": (C.c_size_t, [C.c_int] * 6 + [C.POINTER(AffineInitParams)]),
+        "sift3d_amd_affine_init_device": (C.c_int, pair + masks + [C.POINTER(AffineInitParams),
+                                                                   C.POINTER(AffineInitResult), dp, vp, vp, vp]),
         "sift3d_amd_affine_normal_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
         "sift3d_hip_affine_normal_eqs_masked": (C.c_int, pair + [dp, vp, vp, vp] + masks),
         "sift3d_amd_affine_refine_masked_work_bytes": (C.c_size_t, [C.c_int] * 7),
@@ -418,6 +461,12 @@ def lib():
     got = tuple(L.sift3d_amd_ffd_landmarks_struct_bytes(k) for k in range(4))
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the FFD landmark layouts as %s, the library has %s" % (want, got))
+    want = (C.sizeof(AffineInitParams), C.sizeof(Frame), C.sizeof(AffineInitResult), MOMENTS_BYTES,
+            SIMILARITY_BATCH_MAX, INIT_MAX_CANDIDATES, INIT_KEEP)
+    got = tuple(L.sift3d_amd_affine_init_struct_bytes(k) for k in range(7))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the initial-transform layouts as %s, the library has %s"
+                           % (want, got))
     _bound = L
     return L
 
@@ -1271,6 +1320,194 @@ def affine_mi_refine(F, M, A, bins, range_f, range_m, params=None, work=None, ma
     res = _affine_refine(what, "sift3d_amd_affine_mi_refine", F, M, A, params, work, mask_fixed, mask_moving,
                          before=(_parzen_bins(bins, what), *_parzen_ranges(range_f, range_m)), after=(C.byref(sim),))
     return res, sim
+
+
+# ---- initial transforms (contract: include/sift3d_amd.h, "Initial transforms: moments and candidate search") ----
+MOMENTS_WEIGHT = {"intensity": 0, "binary": 1}
+INIT_MODE = {"centroid": 0, "axes": 1, "search": 2}
+INIT_METRIC = {"msd": 0, "ncc": 1, "mi": 2}
+MOMENTS_DTYPE = np.dtype([("n", "u8"), ("S0", "f8"), ("S1", "f8", (3,)), ("S2", "f8", (6,))])
+assert MOMENTS_DTYPE.itemsize == MOMENTS_BYTES
+
+
+def _named(table, value, what, name):
+    if value not in table:
+        raise ValueError("%s: %s must be one of %s, not %r" % (what, name, sorted(table), value))
+    return table[value]
+
+
+def moments_record(record):
+    """The record of moments() on the host, waiting for the stream: a numpy record (n, S0, S1 [3], S2 [6])."""
+    import torch
+    return record.view(torch.uint8)[:MOMENTS_BYTES].cpu().numpy().view(MOMENTS_DTYPE)[0].copy()
+
+
+def moments(V, weight="binary", floor=0.0, mask=None, record=None, work=None, raw=False):
+    """The count, mass and first and second moments about the grid's centre of the voxels of V [nz, ny, nx] above
+    `floor` (sift3d_hip_moments), torch CUDA float32 contiguous, on torch's current stream.  weight: "binary" or
+    "intensity".  mask: a float32 mask of V's shape (in where >= 0.5) or None.  Returns the record on the host (which
+    waits for the stream; moments_record), or with raw=True the device record.  record, work: the caller's buffers
+    (int64 [11]; sift3d_amd_moments_work_bytes bytes)."""
+    what = "moments"
+    _tensor(V, what + ": V must be a contiguous 3-D float32 CUDA tensor", dims=(3,))
+    if mask is not None:
+        _tensor(mask, "%s: mask must be a contiguous float32 CUDA tensor of V's shape %s on V's device"
+                % (what, tuple(V.shape)), shape=tuple(V.shape), device=V.device)
+    nz, ny, nx = V.shape
+    record = _buffer(what, "record", record, (MOMENTS_BYTES // 8,), V)
+    work = _byte_work(what, work, lib().sift3d_amd_moments_work_bytes(nx, ny, nz), V)
+    _run("sift3d_hip_moments", V.data_ptr(), nx, ny, nz, None if mask is None else mask.data_ptr(),
+         _named(MOMENTS_WEIGHT, weight, what, "weight"), float(np.float32(floor)), record.data_ptr(), work.data_ptr(),
+         current_stream())
+    return record if raw else moments_record(record)
+
+
+def moments_frame(record, shape):
+    """(centroid [3], axes [3, 3] with the eigenvectors as rows, lambda [3]) of sift3d_amd_moments_frame (host) for a
+    moments record of a grid shape = (nz, ny, nx), (x, y, z) order throughout; None where the entry refuses (nothing
+    counted, or not finite)."""
+    rec = np.zeros(1, MOMENTS_DTYPE)
+    rec[0] = record
+    nz, ny, nx = (int(v) for v in shape)
+    c, a, lam = np.zeros(3), np.zeros(9), np.zeros(3)
+    if lib().sift3d_amd_moments_frame(rec.ctypes.data, nx, ny, nz, _dptr(c), _dptr(a), _dptr(lam)) != 0:
+        return None
+    return c, a.reshape(3, 3), lam
+
+
+def _affine_list(A, what):
+    a = np.ascontiguousarray(A, np.float64)
+    if a.ndim < 2 or a.shape[1:] not in ((3, 4), (12,)):
+        raise ValueError("%s: A must be K affine pull maps [K, 3, 4]" % what)
+    return a.reshape(len(a), 12).copy()
+
+
+def similarity_batch(F, M, A, bins=0, range_f=(0.0, 1.0), range_m=(0.0, 1.0), interp="linear", hist=None, stats=None,
+                     work=None, mask_fixed=None, mask_moving=None):
+    """similarity() for K affine pull maps A [K, 3, 4] in one call (sift3d_hip_similarity_affine_batch / _masked), on
+    torch's current stream: candidate k's histogram and stats record are similarity()'s for A[k], byte for byte.
+    bins=0: no histograms (MSD and NCC need none).  Returns (hist int64 [K, bins, bins] or None, stats int64 [K, 7]:
+    row k read with similarity_stats).  hist, stats, work: the caller's buffers
+    (sift3d_amd_similarity_batch_work_bytes bytes).  mask_fixed, mask_moving: as similarity's."""
+    what = "similarity_batch"
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
+    mode = _interp(interp)
+    a = _affine_list(A, what)
+    K, bins = len(a), int(bins)
+    if not 1 <= K <= SIMILARITY_BATCH_MAX:
+        raise ValueError("%s: K must be in [1, %d]" % (what, SIMILARITY_BATCH_MAX))
+    if bins != 0 and not 2 <= bins <= SIMILARITY_MAX_BINS:
+        raise ValueError("%s: bins must be 0 or in [2, %d]" % (what, SIMILARITY_MAX_BINS))
+    if bins == 0 and hist is not None:
+        raise ValueError("%s: bins=0 takes no hist" % what)
+    if bins:
+        hist = _buffer(what, "hist", hist, (K, bins, bins), F, "[K, bins, bins]")
+    stats = _buffer(what, "stats", stats, (K, SIMILARITY_STATS_BYTES // 8), F)
+    work = _byte_work(what, work, lib().sift3d_amd_similarity_batch_work_bytes(*head[1:4], bins, K), F,
+                      "the fixed grid has too many tiles")
+    (lo_f, hi_f), (lo_m, hi_m) = ((float(np.float32(v)) for v in r) for r in (range_f, range_m))
+    name, masks = _masked_entry("sift3d_hip_similarity_affine_batch", masks)
+    _run(name, *head, _dptr(a), K, mode, bins, lo_f, hi_f, lo_m, hi_m, hist.data_ptr() if bins else None,
+         stats.data_ptr(), work.data_ptr(), current_stream(), *masks)
+    return hist, stats
+
+
+def affine_init_params(**kw):
+    """sift3d_amd_affine_init_params: the defaults, overridden by mode, metric and weight (names or numbers), levels,
+    floor_f, floor_m, bins, lo_f, hi_f, lo_m, hi_m, range_deg and range_vox (a number or three, about / along x, y, z),
+    step_deg, step_vox, min_overlap"""
+    p = AffineInitParams()
+    lib().sift3d_amd_affine_init_default_params(C.byref(p))
+    names = [f[0] for f in AffineInitParams._fields_]
+    tables = {"mode": INIT_MODE, "metric": INIT_METRIC, "weight": MOMENTS_WEIGHT}
+    for k, v in kw.items():
+        if k not in names:
+            raise ValueError("affine_init: unknown parameter %r" % (k,))
+        if k in tables and isinstance(v, str):
+            v = _named(tables[k], v, "affine_init", k)
+        if k in ("range_deg", "range_vox"):
+            v = (C.c_double * 3)(*(np.broadcast_to(np.asarray(v, np.float64), (3,))))
+        setattr(p, k, v)
+    return p
+
+
+def _frame(f, what):
+    if isinstance(f, Frame):
+        return f
+    c, a, lam = f
+    out = Frame()
+    out.centroid[:] = np.asarray(c, np.float64).reshape(3)
+    out.axes[:] = np.asarray(a, np.float64).reshape(9)
+    out.lambda_[:] = np.asarray(lam, np.float64).reshape(3)
+    return out
+
+
+def affine_init_candidates(mode, frame_F, frame_M, params=None):
+    """A [K, 3, 4] of sift3d_amd_affine_init_candidates (host): the candidate pull maps of `mode` ("centroid", "axes",
+    "search") about the two frames, each (centroid, axes, lambda) as moments_frame returns it or a Frame; params: an
+    AffineInitParams for the search ranges (None: the defaults)."""
+    what = "affine_init_candidates"
+    fF, fM = _frame(frame_F, what), _frame(frame_M, what)
+    mode = _named(INIT_MODE, mode, what, "mode") if isinstance(mode, str) else int(mode)
+    pp = None if params is None else C.byref(params)
+    K = C.c_int(0)
+    if lib().sift3d_amd_affine_init_candidates(mode, C.byref(fF), C.byref(fM), pp, None, C.byref(K)) != 0:
+        raise ValueError("%s: %s" % (what, lib().sift3d_hip_last_error().decode() or "refused"))
+    A = np.zeros((K.value, 12))
+    if lib().sift3d_amd_affine_init_candidates(mode, C.byref(fF), C.byref(fM), pp, _dptr(A), C.byref(K)) != 0:
+        raise ValueError("%s: refused" % what)
+    return A.reshape(-1, 3, 4)
+
+
+def affine_init_rank(metric, stats, hist=None, min_overlap=0.5):
+    """(costs float64 [K], counts uint64 [K], order: the eligible candidates by ascending cost) of
+    sift3d_amd_affine_init_rank (host) on K stats records (int64 [K, 7], host or device) and, for "mi", K histograms
+    [K, bins, bins]; order is empty where the entry finds no candidate eligible."""
+    import torch
+    what = "affine_init_rank"
+    metric = _named(INIT_METRIC, metric, what, "metric") if isinstance(metric, str) else int(metric)
+
+    def host(t, dtype):
+        return np.ascontiguousarray(t.cpu().numpy() if isinstance(t, torch.Tensor) else t).view(dtype)
+    st = host(stats, np.uint64).reshape(-1, SIMILARITY_STATS_BYTES // 8)
+    K = len(st)
+    bins = 0
+    hp = None
+    if hist is not None:
+        hs = host(hist, np.uint64)
+        if hs.ndim != 3 or hs.shape[0] != K or hs.shape[1] != hs.shape[2]:
+            raise ValueError("%s: hist must be [K, bins, bins]" % what)
+        bins, hp = hs.shape[1], hs.ctypes.data
+    if not (metric in INIT_METRIC.values() and 1 <= K <= INIT_MAX_CANDIDATES and 0 <= min_overlap <= 1
+            and (metric != INIT_METRIC["mi"] or (hp is not None and 2 <= bins <= SIMILARITY_MAX_BINS))):
+        raise ValueError("%s: K in [1, %d], min_overlap in [0, 1] and, for \"mi\", histograms of 2 to %d bins"
+                         % (what, INIT_MAX_CANDIDATES, SIMILARITY_MAX_BINS))
+    cost, n, order = np.zeros(K), np.zeros(K, np.uint64), np.zeros(K, np.int32)
+    m = C.c_int(0)
+    lib().sift3d_amd_affine_init_rank(metric, K, st.ctypes.data, hp, bins, float(min_overlap), _dptr(cost),
+                                      n.ctypes.data, order.ctypes.data, C.byref(m))      # -1: none eligible, m == 0
+    return cost, n, order[:m.value].copy()
+
+
+def affine_init(F, M, params=None, work=None, mask_fixed=None, mask_moving=None):
+    """sift3d_amd_affine_init_device on torch CUDA float32 contiguous volumes, on torch's current stream (the call waits
+    for it once for the moments and once per chunk of candidates).  params: an AffineInitParams (None: the defaults).
+    Returns (AffineInitResult, costs float64 [K], counts uint64 [K]); RuntimeError where the library refuses or finds
+    no candidate eligible.  mask_fixed, mask_moving: as similarity's."""
+    what = "affine_init"
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
+    p = params if params is not None else affine_init_params()
+    need = lib().sift3d_amd_affine_init_work_bytes(*head[1:4], *head[5:8], C.byref(p))
+    work = _byte_work(what, work, need, F, "a parameter is out of range")
+    K = C.c_int(0)
+    f = Frame()
+    if lib().sift3d_amd_affine_init_candidates(p.mode, C.byref(f), C.byref(f), C.byref(p), None, C.byref(K)) != 0:
+        raise ValueError("%s: a parameter is out of range" % what)
+    costs, counts = np.full(K.value, np.nan), np.zeros(K.value, np.uint64)
+    res = AffineInitResult()
+    _run("sift3d_amd_affine_init_device", *head, *(masks or (None, None)), C.byref(p), C.byref(res), _dptr(costs),
+         counts.ctypes.data, work.data_ptr(), current_stream())
+    return res, costs, counts
 
 
 # ---- B-spline free-form deformation (contract: include/sift3d_amd.h, "B-spline free-form deformation") ----
