@@ -191,6 +191,42 @@ SIFT3D_AMD_API int
 sift3d_hip_nn2(const float *d_A, int nA, const float *d_B, int nB, int dim, int *d_j1, float *d_d1,
                float *d_d2, float *d_work, void *stream);
 
+/* ---- Transform-guided (spatially gated) nearest neighbours ----
+ * The same search over the candidates inside a spatial gate only.  Set A has positions pa_i -- A's keypoints
+ * MAPPED INTO B's FRAME by the caller --, set B positions pb_j; d_posA / d_posB: float32, n x 4 (x, y, z and an
+ * ignored float), 16-byte aligned.  r2 = (float)(radius * radius), the product taken in double.
+ *   gate(i, j):  dx = pa_i.x - pb_j.x, dy, dz likewise, all in f32
+ *                d2 = (dx*dx + dy*dy) + dz*dz          (no contraction)
+ *                d2 <= r2                              (a NaN anywhere: false)
+ * Swapping the roles only negates dx, dy, dz: a backward search (B against A) over the SAME two position arrays
+ * evaluates bit-identical d2, so the gate is symmetric by construction.
+ * For every row of A: the lexicographic (distance, original index) top-2 over the gated candidates.  The
+ * distance of a pair is bit for bit sift3d_hip_nn2's (the same fma chain, |b|^2 - 2 a.b, max(|a|^2 + e, 0)
+ * after the merge).  No candidate: d_j1 = -1, d_d1 = d_d2 = +inf; one candidate: d_d2 = +inf.  With r2 = +inf
+ * and finite positions the three outputs equal sift3d_hip_nn2's bit for bit.
+ * d_permA / d_permB (int32, NULL: the identity): the row order in which the kernel walks each set -- block row r
+ * is original row perm[r]; a permutation is trusted to be one.  Results never depend on it (ties go to the
+ * smaller ORIGINAL index); what depends on it is the work: the box of every 128-row block is computed first
+ * (fminf / fmaxf; a point with a NaN coordinate stays out), and a block of A skips a block of B when
+ *   gap2 = (gx*gx + gy*gy) + gz*gz > r2,   g = max(0, max(loA - hiB, loB - hiA)) per axis, in f32.
+ * f32 rounding is monotone, so every pair of the two blocks has d2 >= gap2: the skip is exact, no epsilon.
+ * d_visited (NULL or 2 counters): set to {block pairs visited, block pairs in all}, a pure function of the
+ * positions, the permutations and r2.  Nothing synchronises with the host.
+ * Refused before any device call: what sift3d_hip_nn2 refuses, a NULL or misaligned position array, r2 < 0 or NaN.
+ * d_work: sift3d_hip_nn2_gated_work_floats(nA, nB) floats
+ *   = sift3d_hip_nn2_work_floats(nA, nB) + 8 (ceil(nA / 128) + ceil(nB / 128)). */
+SIFT3D_AMD_API size_t sift3d_hip_nn2_gated_work_floats(int nA, int nB);
+SIFT3D_AMD_API int
+sift3d_hip_nn2_gated(const float *d_A, int nA, const float *d_B, int nB, int dim, const float *d_posA,
+                     const float *d_posB, float r2, const int *d_permA, const int *d_permB, int *d_j1,
+                     float *d_d1, float *d_d2, unsigned long long *d_visited, float *d_work, void *stream);
+
+/* A row order that makes 128-row blocks spatially compact (device-free).  perm[0 .. n) = the indices of the n
+ * points xyz[3 i ..] sorted by (key, index); key = the Morton interleave (bit 3 b + k of the key = bit b of axis
+ * k's cell) of floor(p / cell) per axis, offset by the smallest cell of the set on that axis and clamped to 21
+ * bits.  Points with a non-finite coordinate go last, by index.  cell > 0 (+inf: the identity). */
+SIFT3D_AMD_API int sift3d_amd_spatial_order(const double *xyz, int n, double cell, int *perm);
+
 /* match_ab[i] (i < size of a) = index in b of the descriptor matched to descriptor i of a, or -1:
  * nearest neighbour accepted when (nearest distance) / (second nearest) < nn_thresh (e.g. 0.8)
  * in BOTH directions and mutual. */
@@ -211,6 +247,19 @@ SIFT3D_AMD_API int sift3d_amd_matcher_match(sift3d_amd_matcher *, const sift3d_d
                                             const sift3d_descriptor_store *b, double nn_thresh,
                                             int *match_ab);
 SIFT3D_AMD_API double sift3d_amd_matcher_seconds(const sift3d_amd_matcher *);
+/* Guided matching: sift3d_amd_matcher_match's rule on the gated searches.  pred_a: the position of every
+ * descriptor of a predicted in b's frame (3 doubles each; rounded to nearest float, as b's own coordinates);
+ * radius > 0 (+inf allowed).  Both sets are walked in sift3d_amd_spatial_order(.., cell = radius); the forward
+ * and the backward search take the same two position arrays.  Accepted: forward ratio test, backward ratio
+ * test, mutual, and -- when max_distance > 0 -- d1 <= (float)(max_distance * max_distance) on the squared
+ * descriptor distance (a sole candidate in the gate passes the ratio test against +inf: the cap guards that
+ * case).  Without max_distance every blind match (i -> j) with gate(i, j) true is also a guided match.
+ * sift3d_amd_matcher_blocks: the block pairs visited and in all of the last guided match, both searches summed. */
+SIFT3D_AMD_API int sift3d_amd_matcher_match_guided(sift3d_amd_matcher *, const sift3d_descriptor_store *a,
+                                                   const sift3d_descriptor_store *b, const double *pred_a,
+                                                   double radius, double nn_thresh, double max_distance,
+                                                   int *match_ab);
+SIFT3D_AMD_API int sift3d_amd_matcher_blocks(const sift3d_amd_matcher *, uint64_t *visited, uint64_t *total);
 SIFT3D_AMD_API int sift3d_amd_descriptor_store_keep_device(sift3d_descriptor_store *, int on);
 SIFT3D_AMD_API int
 sift3d_amd_descriptor_store_xyz(const sift3d_descriptor_store *, int i, double *xyz /*3*/);

@@ -514,6 +514,10 @@ class Matcher:
                                                np.ctypeslib.ndpointer(np.int32)]
         L.sift3d_amd_matcher_seconds.argtypes = [C.c_void_p]
         L.sift3d_amd_matcher_seconds.restype = C.c_double
+        L.sift3d_amd_matcher_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      np.ctypeslib.ndpointer(np.float64), C.c_double, C.c_double,
+                                                      C.c_double, np.ctypeslib.ndpointer(np.int32)]
+        L.sift3d_amd_matcher_blocks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         self.h = L.sift3d_amd_make_matcher()
         if not self.h:
             raise RuntimeError("sift3d_amd_make_matcher failed (no HIP device?)")
@@ -525,9 +529,35 @@ class Matcher:
             raise RuntimeError("sift3d_amd_matcher_match failed")
         return out[:len(desc_a)]
 
+    def match_guided(self, desc_a, desc_b, pred_a, radius, nn_thresh=0.8, max_distance=None):
+        """match() among the candidates within `radius` (voxels of desc_b's frame) of where a transform predicts each
+        descriptor of desc_a (sift3d_amd_matcher_match_guided).  pred_a: the predicted positions (n x 3), or a 3 x 4
+        push map (a's voxel -> b's voxel), applied to desc_a.xyz() in float64.  max_distance: the largest accepted
+        descriptor distance of a match, or None."""
+        n = len(desc_a)
+        pred = np.ascontiguousarray(pred_a, np.float64)
+        if pred.shape == (3, 4):
+            pred = desc_a.xyz().reshape(-1, 3) @ pred[:, :3].T + pred[:, 3]
+        if pred.shape != (n, 3):
+            raise ValueError("match_guided: pred_a must be %d x 3 positions or a 3 x 4 map, not %r" % (n, pred.shape))
+        pred = np.ascontiguousarray(pred).reshape(-1)
+        out = np.full(max(n, 1), -1, np.int32)
+        if lib().sift3d_amd_matcher_match_guided(self.h, desc_a.h, desc_b.h, pred if n else np.zeros(3), float(radius),
+                                                 float(nn_thresh), 0.0 if max_distance is None else float(max_distance),
+                                                 out) != 0:
+            raise RuntimeError("sift3d_amd_matcher_match_guided failed")
+        return out[:n]
+
     def seconds(self):
         """Device seconds of the two nearest-neighbour searches of the last match."""
         return float(lib().sift3d_amd_matcher_seconds(self.h))
+
+    def blocks(self):
+        """(visited, total) 128 x 128 block pairs of the last match_guided, both searches summed."""
+        v, t = C.c_uint64(), C.c_uint64()
+        if lib().sift3d_amd_matcher_blocks(self.h, C.byref(v), C.byref(t)) != 0:
+            raise RuntimeError("sift3d_amd_matcher_blocks failed")
+        return int(v.value), int(t.value)
 
     def free(self):
         if getattr(self, "h", None) and lib is not None:
@@ -543,6 +573,19 @@ def nn_match(desc_a, desc_b, nn_thresh=0.8):
     if lib().sift3d_amd_nn_match(desc_a.h, desc_b.h, float(nn_thresh), out) != 0:
         raise RuntimeError("sift3d_amd_nn_match failed")
     return out[:len(desc_a)]
+
+
+def spatial_order(xyz, cell):
+    """The row order match_guided walks a set in (sift3d_amd_spatial_order): the indices of the points xyz (n x 3)
+    sorted by the Morton key of their cell of size `cell`, then by index; non-finite points last."""
+    p = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    perm = np.zeros(max(len(p), 1), np.int32)
+    L = lib()
+    L.sift3d_amd_spatial_order.argtypes = [np.ctypeslib.ndpointer(np.float64), C.c_int, C.c_double,
+                                           np.ctypeslib.ndpointer(np.int32)]
+    if L.sift3d_amd_spatial_order(p.reshape(-1) if len(p) else np.zeros(3), len(p), float(cell), perm) != 0:
+        raise ValueError("spatial_order: cell must be positive, not %r" % (cell,))
+    return perm[:len(p)]
 
 
 def ransac_affine(src, dst, err_thresh=5.0, num_iter=500, seed=1):
@@ -592,9 +635,10 @@ def warp_affine(image_or_array, A, out_shape, interp="linear", fill=0.0):
 Registration = collections.namedtuple("Registration", "A inliers num_matches warped")
 
 
-def _matched_points(moving, fixed, nn_thresh, detector_kw, what):
+def _matched_points(moving, fixed, nn_thresh, detector_kw, what, keep_stores=False):
     """Detect + describe both volumes (torch CUDA float32 tensors [nz, ny, nx]) and match the
-    descriptors: (moving xyz, fixed xyz) of the matched pairs, in voxels."""
+    descriptors: (moving xyz, fixed xyz) of the matched pairs, in voxels; with keep_stores also the two
+    descriptor stores (moving's, fixed's), for a guided second match."""
     import torch
     from . import hip
     for name, v in (("moving", moving), ("fixed", fixed)):
@@ -616,11 +660,51 @@ def _matched_points(moving, fixed, nn_thresh, detector_kw, what):
     d_mov, d_fix = stores
     m = Matcher().match(d_mov, d_fix, nn_thresh)
     hit = np.nonzero(m >= 0)[0]
+    if keep_stores:
+        return d_mov.xyz()[hit], d_fix.xyz()[m[hit]], (d_mov, d_fix)
     return d_mov.xyz()[hit], d_fix.xyz()[m[hit]]
 
 
+FirstPass = collections.namedtuple("FirstPass", "A inliers num_matches")
+
+
+def _rematch_keywords(rematch, nn_thresh, what):
+    """rematch=None | radius | dict(radius=, nn_thresh=, max_distance=) -> match_guided's keyword arguments, or None"""
+    if rematch is None:
+        return None
+    kw = dict(rematch) if isinstance(rematch, dict) else dict(radius=rematch)
+    bad = set(kw) - {"radius", "nn_thresh", "max_distance"}
+    if bad or "radius" not in kw or not float(kw["radius"]) > 0:
+        raise ValueError("%s: rematch must be a positive radius or dict(radius=, nn_thresh=, max_distance=), not %r"
+                         % (what, rematch))
+    kw.setdefault("nn_thresh", nn_thresh)
+    return kw
+
+
+def _matched_points_guided(moving, fixed, nn_thresh, detector_kw, what, rematch, err_thresh, num_iter, seed):
+    """_matched_points, then -- with rematch, and where RANSAC finds a model A in the matches -- the matches of
+    Matcher.match_guided under A instead.  Returns (moving xyz, fixed xyz, first): first is FirstPass(A, inliers,
+    num_matches) of the blind pass, or None where nothing was rematched (the points are then the blind matches')."""
+    kw = _rematch_keywords(rematch, nn_thresh, what)
+    if kw is None:
+        return _matched_points(moving, fixed, nn_thresh, detector_kw, what) + (None,)
+    p_mov, p_fix, (d_mov, d_fix) = _matched_points(moving, fixed, nn_thresh, detector_kw, what, keep_stores=True)
+    try:
+        A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
+    except RuntimeError:
+        return p_mov, p_fix, None                           # no model: nothing to guide
+    m = Matcher().match_guided(d_mov, d_fix, A, **kw)
+    hit = np.nonzero(m >= 0)[0]
+    return d_mov.xyz()[hit], d_fix.xyz()[m[hit]], FirstPass(A, inl, len(p_mov))
+
+
+def _with_first(result, first):
+    """the result tuple's sibling with the first pass behind it (GUIDED_REGISTRATIONS), where there was one"""
+    return result if first is None else GUIDED_REGISTRATIONS[type(result)](*result, first)
+
+
 def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1, refine=False, init=None,
-             **detector_kw):
+             rematch=None, **detector_kw):
     """Register two volumes (torch CUDA float32 tensors [nz, ny, nx]): detect + describe both,
     match the descriptors, fit the moving -> fixed affine by RANSAC and resample `moving` into
     `fixed`'s grid.  detector_kw go to Detector().  Returns Registration(A (3 x 4, moving voxel ->
@@ -634,9 +718,16 @@ def register(moving, fixed, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
     not match, and that is the pair the mutual information is for.
     init: a mode of init_affine or a dict of its keyword arguments.  Where RANSAC finds no model the flow then goes on
     from init_affine's map, for any metric, instead of raising or taking the identity (A_ransac and inliers as above);
-    its metric and masks default to the refinement's.  Where RANSAC finds a model init is not used."""
-    p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register")
-    return _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine, init)
+    its metric and masks default to the refinement's.  Where RANSAC finds a model init is not used.
+    rematch: a radius in fixed voxels, or dict(radius=, nn_thresh=, max_distance=) for Matcher.match_guided.  After
+    the first RANSAC gives A the descriptors are matched again among the candidates within the radius of where A
+    puts them, and RANSAC (same err_thresh, num_iter, seed) and everything after it run on the new matches.  The
+    result is then the GuidedRegistration / GuidedRefinedRegistration sibling, whose last field `first` is
+    FirstPass(A, inliers, num_matches) of the first pass.  Where the first RANSAC finds no model there is nothing to
+    guide and the call behaves as without rematch."""
+    p_mov, p_fix, first = _matched_points_guided(moving, fixed, nn_thresh, detector_kw, "register", rematch, err_thresh,
+                                                 num_iter, seed)
+    return _with_first(_register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine, init), first)
 
 
 def _register_matched(moving, fixed, p_mov, p_fix, err_thresh, num_iter, seed, refine, init=None):
@@ -747,21 +838,24 @@ DEFORMABLE_SMOOTHING = 30.0
 
 
 def register_deformable(moving, fixed, nn_thresh=0.8, err_thresh=DEFORMABLE_ERR_THRESH, num_iter=500, seed=1,
-                        smoothing=DEFORMABLE_SMOOTHING, max_control_points=2048, **detector_kw):
+                        smoothing=DEFORMABLE_SMOOTHING, max_control_points=2048, rematch=None, **detector_kw):
     """Deformable registration of two volumes (torch CUDA float32 tensors [nz, ny, nx]): detect +
     describe both, match, fit the moving -> fixed affine by RANSAC (err_thresh), then fit a
     thin-plate spline fixed -> moving through the RANSAC inliers (smoothing, at most
     max_control_points of them) and resample `moving` into `fixed`'s grid through it.  Returns
     DeformableRegistration(A (3 x 4, moving voxel -> fixed voxel), tps (TPS, fixed voxel -> moving voxel),
-    inliers (mask over the matches), num_matches, warped (tensor shaped like fixed))."""
+    inliers (mask over the matches), num_matches, warped (tensor shaped like fixed)).
+    rematch: register's; the spline then goes through the inliers of the guided matches, and the result is the
+    GuidedDeformableRegistration sibling with `first` behind it."""
     import torch
     from . import hip
-    p_mov, p_fix = _matched_points(moving, fixed, nn_thresh, detector_kw, "register_deformable")
+    p_mov, p_fix, first = _matched_points_guided(moving, fixed, nn_thresh, detector_kw, "register_deformable", rematch,
+                                                 err_thresh, num_iter, seed)
     A, inl = ransac_affine(p_mov, p_fix, err_thresh, num_iter, seed)
     tps = tps_fit(p_fix[inl], p_mov[inl], smoothing, max_control_points)
     warped = torch.empty_like(fixed)
     hip.warp_tps(moving, warped, tps, "linear")
-    return DeformableRegistration(A, tps, inl, len(p_mov), warped)
+    return _with_first(DeformableRegistration(A, tps, inl, len(p_mov), warped), first)
 
 
 # ---- displacement fields: export, resampling through a field, Jacobian -----------------------------
@@ -1083,6 +1177,9 @@ AffineRefinement = collections.namedtuple(
     "AffineRefinement", "A msd count accepted lambdas levels level_slices evaluations stop warped")
 RefinedRegistration = collections.namedtuple("RefinedRegistration",
                                              "A inliers num_matches warped A_ransac refinement")
+# the registration results after a guided second match (rematch=): the same fields, then the first pass
+GUIDED_REGISTRATIONS = {k: collections.namedtuple("Guided" + k.__name__, k._fields + ("first",))
+                        for k in (Registration, RefinedRegistration, DeformableRegistration)}
 NccAffineRefinement = collections.namedtuple(
     "NccAffineRefinement", "A cost count accepted lambdas levels level_slices evaluations stop warped ncc gain offset")
 MiAffineRefinement = collections.namedtuple(
@@ -1574,7 +1671,7 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
 
 def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.8, err_thresh=3.0, num_iter=500, seed=1,
                  ffd_params=None, refine=True, landmarks=False, landmark_weight=FFD_LANDMARK_WEIGHT,
-                 landmark_err_thresh=DEFORMABLE_ERR_THRESH, init=None, **detector_kw):
+                 landmark_err_thresh=DEFORMABLE_ERR_THRESH, init=None, rematch=None, **detector_kw):
     """register(refine=True) (keypoints, RANSAC, intensity-driven affine refinement), then refine_ffd from its refined
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
     refine_ffd's further keyword arguments (dict(metric="mi") for a mutual-information FFD stage, which then returns
@@ -1587,12 +1684,15 @@ def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.
     on the same matches at landmark_err_thresh (DEFORMABLE_ERR_THRESH, wider than err_thresh for
     register_deformable's reason: a match that a deformation moved off the affine model is the one the deformable stage
     wants) with the same num_iter and seed go to refine_ffd as landmarks (fixed xyz, moving xyz) with landmark_weight.
-    Where RANSAC finds no such inlier the FFD stage runs without the term.  init: register's."""
+    Where RANSAC finds no such inlier the FFD stage runs without the term.  init: register's.
+    rematch: register's; the affine stage and the landmarks then come from the guided matches, and `registration` is
+    the GuidedRefinedRegistration."""
     F = _similarity_volume(fixed, "register_ffd", "fixed")
     M = _similarity_volume(moving, "register_ffd", "moving", F.device)
-    p_mov, p_fix = _matched_points(M, F, nn_thresh, detector_kw, "register_ffd")
-    reg = _register_matched(M, F, p_mov, p_fix, err_thresh, num_iter, seed, refine if isinstance(refine, dict) else True,
-                            init)
+    p_mov, p_fix, first = _matched_points_guided(M, F, nn_thresh, detector_kw, "register_ffd", rematch, err_thresh,
+                                                 num_iter, seed)
+    reg = _with_first(_register_matched(M, F, p_mov, p_fix, err_thresh, num_iter, seed,
+                                        refine if isinstance(refine, dict) else True, init), first)
     kw = dict(ffd_params or {})
     if landmarks:
         try:

@@ -8,7 +8,10 @@
  *   matching   nearest / second-nearest neighbour under L2 on the 768-float descriptors
  *              (sift3d_hip_nn2, matrix cores), Lowe's ratio test on the two distances, and the
  *              forward-backward check (a match must be mutual);
- *   fitting    12-parameter affine y = A [x; 1] by least squares inside RANSAC: random minimal
+ *   guided     the same rule among the candidates within a radius of where a first transform predicts each
+ *              keypoint (sift3d_hip_nn2_gated over rows walked in Morton order, sift3d_amd_spatial_order);
+ *              restated in tests/match_guided_restatement.py;
+ *   fitting   12-parameter affine y = A [x; 1] by least squares inside RANSAC: random minimal
  *              samples of 4 matches, inliers by residual, best consensus refit on its inliers.
  * The matcher's decisions and RANSAC (the generator, the picks, the fits, the consensus and the refits)
  * are pinned bit for bit to a numpy restatement (tests/match_restatement.py); the whole flow is
@@ -27,6 +30,12 @@ struct sift3d_amd_matcher {
     float *d_up[2];                    /* upload buffers for stores without a device copy */
     size_t up_cap[2];
     double seconds;                    /* device seconds of the two searches of the last match */
+    /* guided matching: positions (n x 4 floats) and row orders of both sets, a's first */
+    float *d_pos, *h_pos;
+    int *d_perm, *h_perm;
+    size_t pos_cap;                    /* their capacity, in descriptors (na + nb) */
+    unsigned long long *d_vis;         /* {visited, total} block pairs of the forward and of the backward search */
+    uint64_t blocks[2];                /* their sums over the last guided match */
 };
 
 int sift3d_amd_descriptor_store_keep_device(sift3d_descriptor_store *d, int on)
@@ -71,6 +80,8 @@ void sift3d_amd_free_matcher(sift3d_amd_matcher *m)
     sift3d_hip_free(m->d_work); sift3d_hip_free(m->d_d12); sift3d_hip_free(m->d_j);
     sift3d_hip_free(m->d_up[0]); sift3d_hip_free(m->d_up[1]);
     sift3d_hip_host_free(m->h_d12); sift3d_hip_host_free(m->h_j);
+    sift3d_hip_free(m->d_pos); sift3d_hip_free(m->d_perm); sift3d_hip_free(m->d_vis);
+    sift3d_hip_host_free(m->h_pos); sift3d_hip_host_free(m->h_perm);
     sift3d_hip_event_destroy(m->ev0); sift3d_hip_event_destroy(m->ev1);
     sift3d_hip_stream_destroy(m->stream);
     free(m);
@@ -97,6 +108,61 @@ static const float *reg_device_hist(sift3d_amd_matcher *m, const sift3d_descript
     return m->d_up[which];
 }
 
+/* scratch for a search pair: work floats (one buffer serves both directions) and results for tot = na + nb rows */
+static int reg_matcher_reserve(sift3d_amd_matcher *m, size_t need, size_t tot)
+{
+    if (need > m->work_floats) {
+        sift3d_hip_free(m->d_work);
+        m->work_floats = 0;
+        if (!(m->d_work = (float *)sift3d_hip_malloc(sizeof(float) * (need + need / 4))))
+            return SIFT3D_FAILURE;
+        m->work_floats = need + need / 4;
+    }
+    if (tot > m->res_cap) {
+        const size_t cap = tot + tot / 4;
+        sift3d_hip_free(m->d_d12); sift3d_hip_free(m->d_j);
+        sift3d_hip_host_free(m->h_d12); sift3d_hip_host_free(m->h_j);
+        m->res_cap = 0;
+        m->d_d12 = (float *)sift3d_hip_malloc(sizeof(float) * 2 * cap);
+        m->d_j = (int *)sift3d_hip_malloc(sizeof(int) * cap);
+        m->h_d12 = (float *)sift3d_hip_host_alloc(sizeof(float) * 2 * cap);
+        m->h_j = (int *)sift3d_hip_host_alloc(sizeof(int) * cap);
+        if (!m->d_d12 || !m->d_j || !m->h_d12 || !m->h_j)
+            return SIFT3D_FAILURE;
+        m->res_cap = cap;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+/* After the two searches were queued behind ev0: time them, fetch their results and decide.  r2: the squared
+ * ratio; max_distance > 0 caps the nearest descriptor distance as well (guided matching). */
+static int reg_matcher_decide(sift3d_amd_matcher *m, int na, int nb, float r2, double max_distance, int *match_ab)
+{
+    const size_t tot = (size_t)na + (size_t)nb;
+    const float *fd1 = m->h_d12, *fd2 = m->h_d12 + tot;
+    const float cap2 = (float)(max_distance * max_distance);
+    const int *hj = m->h_j;
+    int i;
+    if (sift3d_hip_event_record(m->ev1, m->stream) ||
+        sift3d_hip_memcpy_d2h(m->h_d12, m->d_d12, sizeof(float) * 2 * tot, m->stream) ||
+        sift3d_hip_memcpy_d2h(m->h_j, m->d_j, sizeof(int) * tot, m->stream) ||
+        sift3d_hip_stream_sync(m->stream))
+        return SIFT3D_FAILURE;
+    m->seconds = 1e-3 * sift3d_hip_event_elapsed_ms(m->ev0, m->ev1);
+    for (i = 0; i < na; i++) {
+        const int j = hj[i];
+        /* ratio test on squared distances; forward-backward consistency */
+        if (j < 0 || !(fd1[i] < r2 * fd2[i]))
+            continue;
+        if (hj[na + j] != i || !(fd1[na + j] < r2 * fd2[na + j]))
+            continue;
+        if (max_distance > 0 && !(fd1[i] <= cap2))
+            continue;
+        match_ab[i] = j;
+    }
+    return SIFT3D_SUCCESS;
+}
+
 /* match_ab[i] = index into b of the match of descriptor i of a, or -1.  nn_thresh: the largest
  * accepted ratio (nearest distance) / (second nearest distance), e.g. 0.8. */
 int sift3d_amd_matcher_match(sift3d_amd_matcher *m, const sift3d_descriptor_store *a,
@@ -116,27 +182,8 @@ int sift3d_amd_matcher_match(sift3d_amd_matcher *m, const sift3d_descriptor_stor
     {
         /* one scratch buffer serves both directions: size it for the larger of the two */
         const size_t wf = sift3d_hip_nn2_work_floats(na, nb), wb = sift3d_hip_nn2_work_floats(nb, na);
-        const size_t need = wf > wb ? wf : wb, tot = (size_t)na + (size_t)nb;
-        if (need > m->work_floats) {
-            sift3d_hip_free(m->d_work);
-            m->work_floats = 0;
-            if (!(m->d_work = (float *)sift3d_hip_malloc(sizeof(float) * (need + need / 4))))
-                return SIFT3D_FAILURE;
-            m->work_floats = need + need / 4;
-        }
-        if (tot > m->res_cap) {
-            const size_t cap = tot + tot / 4;
-            sift3d_hip_free(m->d_d12); sift3d_hip_free(m->d_j);
-            sift3d_hip_host_free(m->h_d12); sift3d_hip_host_free(m->h_j);
-            m->res_cap = 0;
-            m->d_d12 = (float *)sift3d_hip_malloc(sizeof(float) * 2 * cap);
-            m->d_j = (int *)sift3d_hip_malloc(sizeof(int) * cap);
-            m->h_d12 = (float *)sift3d_hip_host_alloc(sizeof(float) * 2 * cap);
-            m->h_j = (int *)sift3d_hip_host_alloc(sizeof(int) * cap);
-            if (!m->d_d12 || !m->d_j || !m->h_d12 || !m->h_j)
-                return SIFT3D_FAILURE;
-            m->res_cap = cap;
-        }
+        if (reg_matcher_reserve(m, wf > wb ? wf : wb, (size_t)na + (size_t)nb))
+            return SIFT3D_FAILURE;
     }
     if (!(da = reg_device_hist(m, a, 0)) || !(db = reg_device_hist(m, b, 1)))
         return SIFT3D_FAILURE;
@@ -147,26 +194,169 @@ int sift3d_amd_matcher_match(sift3d_amd_matcher *m, const sift3d_descriptor_stor
         if (sift3d_hip_event_record(m->ev0, m->stream) ||
             sift3d_hip_nn2(da, na, db, nb, DESC_NUMEL, m->d_j, d1, d2, m->d_work, m->stream) ||
             sift3d_hip_nn2(db, nb, da, na, DESC_NUMEL, m->d_j + na, d1 + na, d2 + na, m->d_work, m->stream) ||
-            sift3d_hip_event_record(m->ev1, m->stream) ||
-            sift3d_hip_memcpy_d2h(m->h_d12, m->d_d12, sizeof(float) * 2 * tot, m->stream) ||
-            sift3d_hip_memcpy_d2h(m->h_j, m->d_j, sizeof(int) * tot, m->stream) ||
-            sift3d_hip_stream_sync(m->stream))
+            reg_matcher_decide(m, na, nb, r2, 0.0, match_ab))
             return SIFT3D_FAILURE;
-        m->seconds = 1e-3 * sift3d_hip_event_elapsed_ms(m->ev0, m->ev1);
-        {
-            const float *fd1 = m->h_d12, *fd2 = m->h_d12 + tot;
-            const int *hj = m->h_j;
-            for (i = 0; i < na; i++) {
-                const int j = hj[i];
-                /* ratio test on squared distances; forward-backward consistency */
-                if (j < 0 || !(fd1[i] < r2 * fd2[i]))
-                    continue;
-                if (hj[na + j] != i || !(fd1[na + j] < r2 * fd2[na + j]))
-                    continue;
-                match_ab[i] = j;
-            }
-        }
     }
+    return SIFT3D_SUCCESS;
+}
+
+/* ---- guided matching ---------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t key;
+    int idx;
+} reg_order_item;
+
+static int reg_order_cmp(const void *pa, const void *pb)
+{
+    const reg_order_item *a = (const reg_order_item *)pa, *b = (const reg_order_item *)pb;
+    if (a->key != b->key)
+        return a->key < b->key ? -1 : 1;
+    return a->idx < b->idx ? -1 : a->idx > b->idx;
+}
+
+/* perm = the points sorted by (Morton key of their cell, index); see include/sift3d_amd.h */
+int sift3d_amd_spatial_order(const double *xyz, int n, double cell, int *perm)
+{
+    reg_order_item *it;
+    double lo[3] = { 0.0, 0.0, 0.0 };
+    int i, k, any = 0;
+    if (n < 0 || !(cell > 0) || (n > 0 && (!xyz || !perm)))
+        return SIFT3D_FAILURE;
+    if (!n)
+        return SIFT3D_SUCCESS;
+    if (!(it = (reg_order_item *)malloc(sizeof(*it) * (size_t)n)))
+        return SIFT3D_FAILURE;
+    /* the smallest cell of the finite points, per axis */
+    for (i = 0; i < n; i++) {
+        const double *p = xyz + 3 * (size_t)i;
+        if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])))
+            continue;
+        for (k = 0; k < 3; k++) {
+            const double c = floor(p[k] / cell);
+            if (!any || c < lo[k])
+                lo[k] = c;
+        }
+        any = 1;
+    }
+    for (i = 0; i < n; i++) {
+        const double *p = xyz + 3 * (size_t)i;
+        uint64_t key = 0;
+        it[i].idx = i;
+        if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) {
+            it[i].key = UINT64_MAX;             /* behind every Morton key (63 bits) */
+            continue;
+        }
+        for (k = 0; k < 3; k++) {
+            const double off = floor(p[k] / cell) - lo[k];
+            const uint64_t c = off < 2097151.0 ? (uint64_t)off : 2097151u;      /* 21 bits */
+            int b;
+            for (b = 0; b < 21; b++)
+                key |= ((c >> b) & 1u) << (3 * b + k);
+        }
+        it[i].key = key;
+    }
+    qsort(it, (size_t)n, sizeof(*it), reg_order_cmp);
+    for (i = 0; i < n; i++)
+        perm[i] = it[i].idx;
+    free(it);
+    return SIFT3D_SUCCESS;
+}
+
+/* positions (n x 4 floats) and row orders of both sets, in host and device memory */
+static int reg_matcher_reserve_guided(sift3d_amd_matcher *m, size_t tot)
+{
+    if (!m->d_vis && !(m->d_vis = (unsigned long long *)sift3d_hip_malloc(sizeof(unsigned long long) * 4)))
+        return SIFT3D_FAILURE;
+    if (tot > m->pos_cap) {
+        const size_t cap = tot + tot / 4;
+        sift3d_hip_free(m->d_pos); sift3d_hip_free(m->d_perm);
+        sift3d_hip_host_free(m->h_pos); sift3d_hip_host_free(m->h_perm);
+        m->pos_cap = 0;
+        m->d_pos = (float *)sift3d_hip_malloc(sizeof(float) * 4 * cap);
+        m->d_perm = (int *)sift3d_hip_malloc(sizeof(int) * cap);
+        m->h_pos = (float *)sift3d_hip_host_alloc(sizeof(float) * 4 * cap);
+        m->h_perm = (int *)sift3d_hip_host_alloc(sizeof(int) * cap);
+        if (!m->d_pos || !m->d_perm || !m->h_pos || !m->h_perm)
+            return SIFT3D_FAILURE;
+        m->pos_cap = cap;
+    }
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_matcher_match_guided(sift3d_amd_matcher *m, const sift3d_descriptor_store *a,
+                                    const sift3d_descriptor_store *b, const double *pred_a, double radius,
+                                    double nn_thresh, double max_distance, int *match_ab)
+{
+    const int na = a ? (int)a->num : 0, nb = b ? (int)b->num : 0;
+    const float r2 = (float)(nn_thresh * nn_thresh), gate2 = (float)(radius * radius);
+    const size_t tot = (size_t)na + (size_t)nb;
+    const float *da, *db;
+    double *xb;
+    int i, k;
+    if (!m || !a || !b || !match_ab || nn_thresh <= 0 || !(radius > 0) || (na && !pred_a))
+        return SIFT3D_FAILURE;
+    for (i = 0; i < na; i++)
+        match_ab[i] = -1;
+    m->seconds = 0.0;
+    m->blocks[0] = m->blocks[1] = 0;
+    if (!na || !nb)
+        return SIFT3D_SUCCESS;
+    {
+        const size_t wf = sift3d_hip_nn2_gated_work_floats(na, nb), wb = sift3d_hip_nn2_gated_work_floats(nb, na);
+        if (reg_matcher_reserve(m, wf > wb ? wf : wb, tot) || reg_matcher_reserve_guided(m, tot))
+            return SIFT3D_FAILURE;
+    }
+    /* a's rows: the predicted positions, ordered by them; b's: its own coordinates.  Both rounded to nearest. */
+    if (!(xb = (double *)malloc(sizeof(double) * 3 * (size_t)nb)))
+        return SIFT3D_FAILURE;
+    for (i = 0; i < nb; i++)
+        memcpy(xb + 3 * (size_t)i, b->xyzsd + 4 * (size_t)i, sizeof(double) * 3);
+    if (sift3d_amd_spatial_order(pred_a, na, radius, m->h_perm) ||
+        sift3d_amd_spatial_order(xb, nb, radius, m->h_perm + na)) {
+        free(xb);
+        return SIFT3D_FAILURE;
+    }
+    for (i = 0; i < na; i++) {
+        for (k = 0; k < 3; k++)
+            m->h_pos[4 * (size_t)i + k] = (float)pred_a[3 * (size_t)i + k];
+        m->h_pos[4 * (size_t)i + 3] = 0.0f;
+    }
+    for (i = 0; i < nb; i++) {
+        for (k = 0; k < 3; k++)
+            m->h_pos[4 * ((size_t)na + i) + k] = (float)xb[3 * (size_t)i + k];
+        m->h_pos[4 * ((size_t)na + i) + 3] = 0.0f;
+    }
+    free(xb);
+    if (!(da = reg_device_hist(m, a, 0)) || !(db = reg_device_hist(m, b, 1)))
+        return SIFT3D_FAILURE;
+    {
+        float *d1 = m->d_d12, *d2 = m->d_d12 + tot;
+        const float *pa = m->d_pos, *pb = m->d_pos + 4 * (size_t)na;
+        const int *qa = m->d_perm, *qb = m->d_perm + na;
+        unsigned long long hv[4];
+        /* forward (a -> b) and backward (b -> a) over the SAME two position arrays: the gate is symmetric */
+        if (sift3d_hip_memcpy_h2d(m->d_pos, m->h_pos, sizeof(float) * 4 * tot, m->stream) ||
+            sift3d_hip_memcpy_h2d(m->d_perm, m->h_perm, sizeof(int) * tot, m->stream) ||
+            sift3d_hip_event_record(m->ev0, m->stream) ||
+            sift3d_hip_nn2_gated(da, na, db, nb, DESC_NUMEL, pa, pb, gate2, qa, qb, m->d_j, d1, d2, m->d_vis,
+                                 m->d_work, m->stream) ||
+            sift3d_hip_nn2_gated(db, nb, da, na, DESC_NUMEL, pb, pa, gate2, qb, qa, m->d_j + na, d1 + na, d2 + na,
+                                 m->d_vis + 2, m->d_work, m->stream) ||
+            reg_matcher_decide(m, na, nb, r2, max_distance, match_ab) ||
+            sift3d_hip_memcpy_d2h(hv, m->d_vis, sizeof(hv), m->stream) || sift3d_hip_stream_sync(m->stream))
+            return SIFT3D_FAILURE;
+        m->blocks[0] = hv[0] + hv[2];
+        m->blocks[1] = hv[1] + hv[3];
+    }
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_matcher_blocks(const sift3d_amd_matcher *m, uint64_t *visited, uint64_t *total)
+{
+    if (!m || !visited || !total)
+        return SIFT3D_FAILURE;
+    *visited = m->blocks[0];
+    *total = m->blocks[1];
     return SIFT3D_SUCCESS;
 }
 

@@ -216,6 +216,9 @@ def lib():
         "sift3d_hip_fir_x_scaled": (C.c_int, [C.POINTER(FirArgs), vp, vp]),
         "sift3d_hip_nn2_work_floats": (C.c_size_t, [C.c_int, C.c_int]),
         "sift3d_hip_nn2": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+        "sift3d_hip_nn2_gated_work_floats": (C.c_size_t, [C.c_int, C.c_int]),
+        "sift3d_hip_nn2_gated": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp,
+                                           vp, vp, vp]),
         "sift3d_hip_subtract_absmax": (C.c_int, [vp, vp, vp, C.c_size_t, vp, vp]),
         "sift3d_hip_dog_stack": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, vp, vp]),
         "sift3d_hip_dogmax_stack": (C.c_int, [C.POINTER(vp), C.c_int, C.c_size_t, vp, vp]),
@@ -566,7 +569,46 @@ def nn2(a, b):
     return j[:na], d1[:na], d2[:na]
 
 
-INTERP = {"nearest": 0, "linear": 1}
+def nn2_gated_work_floats(na, nb):
+    return int(lib().sift3d_hip_nn2_gated_work_floats(int(na), int(nb)))
+
+
+def nn2_gated(a, b, pos_a, pos_b, radius, perm_a=None, perm_b=None, work=None):
+    """nn2 over the candidates inside the spatial gate only (sift3d_hip_nn2_gated).  pos_a / pos_b: CUDA float32
+    tensors [n, 4] (x, y, z, ignored), a's already mapped into b's frame; radius: the gate's, +inf allowed; perm_a /
+    perm_b: int32 row orders (None: the identity); work: a float32 tensor of at least nn2_gated_work_floats(na, nb)
+    elements, or None.  Returns (index int32, squared distance, second squared distance, block pairs visited, block
+    pairs in all)."""
+    import torch
+    assert a.is_contiguous() and b.is_contiguous() and a.shape[1] == b.shape[1]
+    na, nb = a.shape[0], b.shape[0]
+    for p, n, name in ((pos_a, na, "pos_a"), (pos_b, nb, "pos_b")):
+        if p.dtype != torch.float32 or tuple(p.shape) != (n, 4) or not p.is_contiguous() or p.device != a.device:
+            raise ValueError("nn2_gated: %s must be a contiguous float32 tensor [%d, 4] on %s" % (name, n, a.device))
+    for p, n, name in ((perm_a, na, "perm_a"), (perm_b, nb, "perm_b")):
+        if p is not None and (p.dtype != torch.int32 or tuple(p.shape) != (n,) or not p.is_contiguous()
+                              or p.device != a.device):
+            raise ValueError("nn2_gated: %s must be a contiguous int32 tensor [%d] on %s" % (name, n, a.device))
+    need = nn2_gated_work_floats(na, nb)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float32, device=a.device)
+    elif work.dtype != torch.float32 or work.numel() < need or not work.is_contiguous() or work.device != a.device:
+        raise ValueError("nn2_gated: work must be a contiguous float32 tensor of at least %d elements" % need)
+    r2 = np.float32(float(radius) * float(radius))
+    j = torch.empty(max(na, 1), dtype=torch.int32, device=a.device)
+    d1 = torch.empty(max(na, 1), dtype=torch.float32, device=a.device)
+    d2 = torch.empty_like(d1)
+    vis = torch.zeros(2, dtype=torch.int64, device=a.device)
+    _check(lib().sift3d_hip_nn2_gated(a.data_ptr(), na, b.data_ptr(), nb, a.shape[1], pos_a.data_ptr(),
+                                      pos_b.data_ptr(), float(r2), perm_a.data_ptr() if perm_a is not None else None,
+                                      perm_b.data_ptr() if perm_b is not None else None, j.data_ptr(), d1.data_ptr(),
+                                      d2.data_ptr(), vis.data_ptr(), work.data_ptr(), current_stream()),
+           "sift3d_hip_nn2_gated")
+    v = vis.tolist()
+    return j[:na], d1[:na], d2[:na], int(v[0]), int(v[1])
+
+
+INTERP ={"nearest": 0, "linear": 1}
 
 
 def _interp(interp):
