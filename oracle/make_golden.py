@@ -14,6 +14,7 @@ Fixture families:
   g2_fir       1-D interpolating FIR per axis, three widths x units 1/2/4 (+ anisotropic)
   g3_*         end-to-end dumps: level digests, small levels in full, dogmax-free
                candidate list, keypoints (R, sd, stale strength), descriptors, sort order
+               (g3_spikes64, g3_integer48, g3_subnormal48: zero-background, integer and subnormal inputs)
   g5_*         larger volumes: candidate/keypoint lists, R, descriptor subset + row sums
   g6_abi       the names the reference library exports and its CLI imports (JSON)
   g7_*         describe on caller-made keypoint lists
@@ -36,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import refprobe  # noqa: E402
 from oracle import sift3d_oracle as so  # noqa: E402
+from tests import pyramid_content  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 
@@ -196,6 +198,14 @@ def end_to_end(name, vol, units=(1, 1, 1), full_levels_below=17, desc_stride=1, 
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
     return {name: dict(cand=int(len(c["sd"])), kp=int(len(k["strength"])),
                        t_detect=round(t_detect, 2), t_describe=round(t_desc, 2))}
+
+
+def end_to_end_content(case):
+    """g3_<case>: a volume of tests/pyramid_content.py (zero background, integers, a subnormal input) with the
+    detector parameters that belong to it."""
+    vol, kw = pyramid_content.detect_volume(case, so)
+    return end_to_end("g3_" + case, vol, params=kw,
+                      input_spec=dict(gen="content", case=case, seed=pyramid_content.DETECT_SEED))
 
 
 def end_to_end_digest(name, vol, stride=97, input_spec=None):
@@ -690,6 +700,11 @@ def main():
                                       input_spec=dict(gen="lattice", n=[50, 44, 40], seed=9)),
         "g3_lat": lambda: end_to_end("g3_lattice48", so.synth_lattice(48, seed=7),
                                      input_spec=dict(gen="lattice", n=48, seed=7)),
+        # content the other g3_* never hold: twelve spikes on exact zero (the reference's levels then hold
+        # subnormals), CT-like integers with plateaus, a subnormal input that its maximum divides back to order 1
+        "g3_spikes64": lambda: end_to_end_content("spikes64"),
+        "g3_integer48": lambda: end_to_end_content("integer48"),
+        "g3_subnormal48": lambda: end_to_end_content("subnormal48"),
         "g4_csv": g4_csv,
         "g6_abi": g6_abi,
         # describe on caller-made keypoint lists (g7_*)

@@ -39,6 +39,11 @@ def golden_input(g, so):
         vol = np.random.Generator(np.random.PCG64(spec["seed"])).standard_normal((nz, ny, nx)).astype(np.float32)
         if spec.get("blur_sigma"):
             vol = so.blur(vol, so.gauss_taps(spec["blur_sigma"]))
+    elif spec["gen"] == "content":
+        # an end-to-end volume of tests/pyramid_content.py (zero background, integers, a subnormal input)
+        from tests import pyramid_content
+        vol, kw = pyramid_content.detect_volume(spec["case"], so)
+        assert spec["seed"] == pyramid_content.DETECT_SEED and kw == golden_params(g)
     else:
         vol = so.synth_lattice(spec["n"], seed=spec["seed"])
     assert digest(vol) == str(g["input_digest"]), "synthetic generator drifted"
