@@ -1081,14 +1081,45 @@ def _similarity_transform(transform, fixed, what):
     return torch.from_numpy(_host_field(transform, what)).to(fixed.device)
 
 
-def _own_range(v, given):
-    """(lo, hi) as given, else the volume's own min and max (one host synchronisation); hi = lo + 1 when constant"""
+def _range_accepted(lo, hi, bins):
+    """bin_scale() of the entries (sift3d_similarity.c) != 0: both ends finite floats, lo < hi, bins / (hi - lo) finite"""
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        lo, hi = np.float32(lo), np.float32(hi)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            return False
+        s = np.float32(bins) / (hi - lo)
+    return bool(np.isfinite(s) and s > 0)
+
+
+def _own_range(v, given, bins=SIMILARITY_MAX_BINS):
+    """(lo, hi) as given, else the volume's own min and max (one host synchronisation); hi = lo + 1 when constant.
+    Where the entries would refuse that pair as floats (a constant beyond 2**24, whose lo + 1 rounds to lo; a span too
+    narrow for bins / (hi - lo)) the range is widened by doubling until they accept it: upwards from lo, or downwards
+    from hi where the float range ends above.  It always contains [min, max].  ValueError for a volume that is not
+    finite or whose max - min overflows float."""
     import torch
     if given is not None:
         lo, hi = given
         return float(lo), float(hi)
     lo, hi = (float(t) for t in torch.aminmax(v))
-    return (lo, hi) if hi > lo else (lo, lo + 1.0)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("the volume must be finite to take its own range (min %r, max %r)" % (lo, hi))
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= SIMILARITY_MAX_BINS:
+        bins = SIMILARITY_MAX_BINS                            # (the entry refuses such a count itself)
+    pair = (lo, hi) if hi > lo else (lo, lo + 1.0)
+    if _range_accepted(*pair, bins):
+        return pair
+    fmax = float(np.finfo(np.float32).max)
+    if hi - lo > fmax:
+        raise ValueError("the volume's own range [%r, %r] is wider than the largest float: give a range" % (lo, hi))
+    for up in (True, False):
+        w = max(pair[1] - pair[0], abs(lo) * 2.0 ** -52, 2.0 ** -150)       # (lo + 1.0 may be lo in double as well)
+        while w <= 2.0 * fmax:
+            w *= 2.0
+            wide = (lo, lo + w) if up else (hi - w, hi)
+            if _range_accepted(*wide, bins):
+                return wide
+    raise ValueError("the volume's own range [%r, %r] cannot be widened within float: give a range" % (lo, hi))
 
 
 def _mask_host(mask, volume, what, name):
@@ -1154,8 +1185,9 @@ def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fi
     transform: None (the identity; equal shapes), a 3 x 4 affine pull map, a TPS (exported with
     displacement_field) or a displacement field [3, oz, oy, ox] on the fixed grid.  The volumes are torch CUDA
     float32 tensors [nz, ny, nx], or Images / arrays, which are uploaded.  A range left None is that volume's own
-    min and max, at the cost of one host synchronisation (a constant volume gets hi = lo + 1); values outside a
-    given range count in the end bins.  mask_fixed, mask_moving: regions of interest of the volumes' shapes (tensors,
+    min and max, at the cost of one host synchronisation (a constant volume gets hi = lo + 1; a pair too narrow for
+    the bins in float is widened until it is not; ValueError for a volume that is not finite or whose max - min
+    overflows float); values outside a given range count in the end bins.  mask_fixed, mask_moving: regions of interest of the volumes' shapes (tensors,
     arrays or Images; bool and integer masks are in where non-zero, float masks where >= 0.5): a fixed voxel counts only
     where mask_fixed is in and mask_moving, at the nearest voxel to its sample point, is in too (contract: "Masks").  A
     range left None is still the whole volume's.  Reads the result, so it waits for torch's current stream."""
@@ -1167,8 +1199,8 @@ def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fi
     WF = _mask_tensor(WF, F, "similarity", "mask_fixed")
     WM = _mask_tensor(WM, F, "similarity", "mask_moving")
     T = _similarity_transform(transform, F, "similarity")
-    hist, stats = hip.similarity(F, M, T, bins, _own_range(F, range_fixed), _own_range(M, range_moving), interp,
-                                 mask_fixed=WF, mask_moving=WM)
+    hist, stats = hip.similarity(F, M, T, bins, _own_range(F, range_fixed, bins), _own_range(M, range_moving, bins),
+                                 interp, mask_fixed=WF, mask_moving=WM)
     return similarity_measures(hist.cpu().numpy(), hip.similarity_stats(stats))
 
 
@@ -1288,7 +1320,8 @@ def init_affine(moving, fixed, mode="search", metric="mi", levels=3, weight="bin
     kw["floor_f"] = float(F.min()) if floor_fixed is None else float(floor_fixed)
     kw["floor_m"] = float(M.min()) if floor_moving is None else float(floor_moving)
     if metric == "mi":
-        (kw["lo_f"], kw["hi_f"]), (kw["lo_m"], kw["hi_m"]) = _own_range(F, range_fixed), _own_range(M, range_moving)
+        (kw["lo_f"], kw["hi_f"]) = _own_range(F, range_fixed, int(bins))
+        (kw["lo_m"], kw["hi_m"]) = _own_range(M, range_moving, int(bins))
         kw["bins"] = int(bins)
     p = hip.affine_init_params(**kw)
     res, costs, counts = hip.affine_init(F, M, p, mask_fixed=WF, mask_moving=WM)
@@ -1330,7 +1363,8 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     metric="mi" maximises the Mattes mutual information of the fixed bin and the Parzen-windowed moving bin (contract:
     "Mutual-information affine refinement (Mattes)"), for volumes whose intensities are related by an unknown map that
     need not be monotone (CT to MR, T1 to T2).  bins (None: 32; 4 .. 64) and range_fixed, range_moving ((lo, hi); None:
-    the volume's own min and max, one host synchronisation each) set the histogram and are level 0's on every level.  It
+    the volume's own min and max, one host synchronisation each, widened and refused with ValueError as similarity's)
+    set the histogram and are level 0's on every level.  It
     returns MiAffineRefinement: NccAffineRefinement's fields without gain and offset, `cost` = -mi per evaluation, then
     mi and nmi at the final A and bins; `warped` is `moving` through A, not remapped.  bins or a range with another
     metric, and any other metric, raise ValueError.
@@ -1374,8 +1408,8 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     if metric == "ncc":
         res, fit = hip.affine_ncc_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     elif metric == "mi":
-        res, sim = hip.affine_mi_refine(F, M, A0, int(bins), _own_range(F, range_fixed), _own_range(M, range_moving),
-                                        p, mask_fixed=WF, mask_moving=WM)
+        res, sim = hip.affine_mi_refine(F, M, A0, int(bins), _own_range(F, range_fixed, int(bins)),
+                                        _own_range(M, range_moving, int(bins)), p, mask_fixed=WF, mask_moving=WM)
     else:
         res = hip.affine_refine(F, M, A0, p, mask_fixed=WF, mask_moving=WM)
     k = res.evaluations
@@ -1534,8 +1568,8 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     metric="mi" maximises the Mattes mutual information instead (contract: "Mutual-information free-form deformation
     (Mattes)"; cost -mi + bending * R), for volumes whose intensities are related by an unknown map that need not be
     monotone, where the MSD fit is wrong.  bins (None: 32; 4 .. 64) and range_fixed, range_moving ((lo, hi); None: the
-    volume's own min and max, one host synchronisation each) set the histogram as in refine_affine and are level 0's on
-    every level.  It returns MiFFDRefinement: FFDRefinement's fields (each trail entry's `msd` holds -mi), then mi and
+    volume's own min and max, one host synchronisation each, widened and refused with ValueError as similarity's) set
+    the histogram as in refine_affine and are level 0's on every level.  It returns MiFFDRefinement: FFDRefinement's fields (each trail entry's `msd` holds -mi), then mi and
     nmi at the final lattice and bins; `warped` is not remapped.  `bending` keeps its default of 0.005 for either
     metric: the value was chosen for the MSD of volumes of unit-order intensity, and no calibration of it against -mi
     (which is of order 1 whatever the intensities) is claimed.  bins or a range with metric="msd", and any other
@@ -1628,7 +1662,8 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     WF = _mask_tensor(WF, F, "refine_ffd", "mask_fixed")
     WM = _mask_tensor(WM, F, "refine_ffd", "mask_moving")
     penalty = terms = None
-    mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed), range_m=_own_range(M, range_moving)) \
+    mi = dict(bins=int(bins), range_f=_own_range(F, range_fixed, int(bins)),
+              range_m=_own_range(M, range_moving, int(bins))) \
         if metric == "mi" else {}
     if lm is not None:
         res, lattice, field, sim, penalty, terms = hip.ffd_refine_landmarks(

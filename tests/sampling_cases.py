@@ -215,11 +215,16 @@ def _grid(shape):
     return x, y, z
 
 
-def build(c):
-    """The arrays of a case (numpy): F, M, A, WF, WM (None where absent) and, by family, field, u / v, lattice, tps."""
+def build(c, content=None):
+    """The arrays of a case (numpy): F, M, A, WF, WM (None where absent) and, by family, field, u / v, lattice, tps.
+    content: a generator (shape, seed) -> float32 volume (tests/registration_content.py) whose output replaces F, M and
+    the src made from M; everything else is drawn as without it, from the same seeded stream."""
     rng = np.random.default_rng([c.seed, FAMILIES.index(c.family), 5])
     d = types.SimpleNamespace()
     d.F, d.M = volumes(c.fshape, c.mshape, c.seed)
+    if content is not None:
+        d.F, d.M = (np.ascontiguousarray(content(s, c.seed + k), F32) for k, s in enumerate((c.fshape, c.mshape)))
+        assert d.F.shape == c.fshape and d.M.shape == c.mshape
     one = [n == 1 for n in c.mshape[::-1]]                  # moving axes (x, y, z) of length 1
     axis = rng.standard_normal(3)
     lin = rot(axis, float(rng.uniform(-8.0, 8.0))) * rng.uniform(0.9, 1.1, 3)[None, :]

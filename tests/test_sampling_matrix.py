@@ -108,16 +108,16 @@ def run_store(hip, c, d):
     return None
 
 
-def run_similarity(hip, c, d, ones=False, plain=False):
+def run_similarity(hip, c, d, ones=False, plain=False, rng=sc.RANGE):
     WF, WM = (None, None) if plain else masks_of(d, ones, c)
     T = d.field if c.field else d.A
-    hist, stats = hip.similarity(dev(d.F), dev(d.M), dev(T) if c.field else T, c.bins, sc.RANGE, sc.RANGE, c.interp,
+    hist, stats = hip.similarity(dev(d.F), dev(d.M), dev(T) if c.field else T, c.bins, rng, rng, c.interp,
                                  mask_fixed=dev(WF), mask_moving=dev(WM))
     count, sums = hip.similarity_stats(stats)
     hist = hist.cpu().numpy()
     if not (ones or plain):
         what = ident(c)
-        want_hist, want = mr.joint(d.F, d.M, T, c.bins, sc.RANGE, sc.RANGE, c.interp, WF, WM)
+        want_hist, want = mr.joint(d.F, d.M, T, c.bins, rng, rng, c.interp, WF, WM)
         np.testing.assert_array_equal(hist, want_hist.astype(np.int64), err_msg=what)
         assert count == want.count == int(want_hist.sum()), (what, count, want.count)
         for k, name in enumerate(("f", "m", "ff", "mm", "fm", "dd")):
@@ -158,29 +158,29 @@ def run_ncc(hip, c, d, ones=False, plain=False):
     return (raw.cpu().numpy().tobytes(),)
 
 
-def run_parzen(hip, c, d, ones=False, plain=False):
+def run_parzen(hip, c, d, ones=False, plain=False, rng=sc.RANGE):
     WF, WM = (None, None) if plain else masks_of(d, ones, c)
-    hist, count = hip.parzen_histogram(dev(d.F), dev(d.M), d.A, c.bins, sc.RANGE, sc.RANGE, mask_fixed=dev(WF),
+    hist, count = hip.parzen_histogram(dev(d.F), dev(d.M), d.A, c.bins, rng, rng, mask_fixed=dev(WF),
                                        mask_moving=dev(WM))
     hist, count = hist.cpu().numpy(), int(count.cpu().numpy()[0])
     if not (ones or plain):
         what = ident(c)
-        want, n, qsum = am.histogram(d.F, d.M, d.A, c.bins, sc.RANGE, sc.RANGE, WF, WM)
+        want, n, qsum = am.histogram(d.F, d.M, d.A, c.bins, rng, rng, WF, WM)
         np.testing.assert_array_equal(hist, want, err_msg=what)
         assert count == n, (what, count, n)
         assert int(hist.sum()) == qsum and abs(qsum - 65536 * n) <= 2 * n, what
     return hist.tobytes(), count
 
 
-def run_mi(hip, c, d, ones=False, plain=False):
+def run_mi(hip, c, d, ones=False, plain=False, rng=sc.RANGE):
     WF, WM = (None, None) if plain else masks_of(d, ones, c)
-    W = am.measures(am.histogram(d.F, d.M, d.A, c.bins, sc.RANGE, sc.RANGE, d.WF, d.WM)[0]).W     # one table for all runs
-    raw = hip.affine_mi_normal_equations(dev(d.F), dev(d.M), d.A, W, sc.RANGE, sc.RANGE, raw=True, mask_fixed=dev(WF),
+    W = am.measures(am.histogram(d.F, d.M, d.A, c.bins, rng, rng, d.WF, d.WM)[0]).W               # one table for all runs
+    raw = hip.affine_mi_normal_equations(dev(d.F), dev(d.M), d.A, W, rng, rng, raw=True, mask_fixed=dev(WF),
                                          mask_moving=dev(WM))
     if not (ones or plain):
         what = ident(c)
         n, spp, b, H = hip.affine_normal_record(raw)
-        want = am.record(d.F, d.M, d.A, W, c.bins, sc.RANGE, sc.RANGE, WF, WM)
+        want = am.record(d.F, d.M, d.A, W, c.bins, rng, rng, WF, WM)
         assert n == want.n, (what, n, want.n)
         assert np.array_equal(H, H.T), what
         g = gamma(want.n + 11)
@@ -213,18 +213,22 @@ def run_ffd(hip, c, d, ones=False, plain=False):
 RUN = {"similarity": run_similarity, "msd": run_msd, "ncc": run_ncc, "parzen": run_parzen, "mi": run_mi, "ffd": run_ffd}
 
 
-def run_case(hip, c, identity=False):
+RANGED = ("similarity", "parzen", "mi")                      # the families whose run takes the bins' range
+
+
+def run_case(hip, c, identity=False, d=None, rng=sc.RANGE):
     """One case on the device against its restatement.  identity: a masked case also with all-ones masks and with no
-    masks, whose bytes must agree."""
-    d = sc.build(c)
+    masks, whose bytes must agree.  d: the case's arrays where they are not build(c)'s; rng: the range of the bins."""
+    d = sc.build(c) if d is None else d
     # the restatements reach q through the identity map 1 * q + ((0 * y + 0 * z) + 0): with an infinite entry numpy
     # reports the 0 * inf (a NaN: outside, as the infinity is)
     with np.errstate(invalid="ignore" if c.nonfinite else "warn"):
         if c.family in sc.STORE_FAMILIES:
             return run_store(hip, c, d)
-        RUN[c.family](hip, c, d)
+        kw = dict(rng=rng) if c.family in RANGED else {}
+        RUN[c.family](hip, c, d, **kw)
         if identity and (c.wf or c.wm):
-            ones, plain = RUN[c.family](hip, c, d, ones=True), RUN[c.family](hip, c, d, plain=True)
+            ones, plain = RUN[c.family](hip, c, d, ones=True, **kw), RUN[c.family](hip, c, d, plain=True, **kw)
             assert ones == plain, ident(c)
 
 
