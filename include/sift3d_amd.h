@@ -2097,6 +2097,117 @@ sift3d_amd_logdemons_masked_device(const sift3d_amd_demons_level *level, const s
                                    float *d_work, void *d_stats, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Local cross-correlation                                                  */
+/* ------------------------------------------------------------------------ */
+/* The squared correlation of two volumes over a small window around every voxel (the CC metric of ANTs / SyN), its
+ * exact derivative with respect to the warped volume as a demons-style force, and a driver that climbs it.  It is the
+ * measure for a SPATIALLY VARYING intensity relation (bias fields, contrast uptake, drift along z), which the MSD
+ * force follows and which one global gain and offset ("NCC affine refinement") cannot absorb.  No upstream
+ * counterpart: PARITY UNPINNED, pinned to this contract and its numpy restatement (tests/lncc_restatement.py).
+ *
+ * Inputs.  Fixed F[nz][ny][nx]; W[nz][ny][nx], the moving volume warped onto the fixed grid (LINEAR, fill 0); the
+ * field u[3][nz][ny][nx] that made W; the moving dims (mx, my, mz); optional masks W_F (fixed grid) and W_M (moving
+ * grid) with the conventions of "Masks in demons"; radius r in [1, SIFT3D_AMD_LNCC_MAX_RADIUS].  One channel.  Voxel
+ * units.  F and W must be finite.
+ *
+ * Validity.  v(p) = 1 where p is counted by k_demons_force<true>'s rule, word for word: inside(p) (warp_field's test
+ * of q_d = (double) p_d + (double) u_d(p) against (mx, my, mz)), W_F(p) in, W_M at floor(q_d + 0.5) in; a NULL mask is
+ * all in.  Elsewhere v(p) = 0.
+ *
+ * Window sums.  N(p) is the set of grid voxels q with |q_d - p_d| <= r on every axis, clipped to the grid.  For a
+ * per-voxel double t, box(t)(p) is summed separably in three steps: the x sums over the offsets -r .. r ascending, the
+ * y sums of those ascending, the z sums of those ascending.  Every sum starts from +0.0, an off-grid position adds
+ * +0.0, additions are unfused.  THIS ORDER IS PART OF THE CONTRACT: it makes the outputs comparable byte for byte.
+ * The six sums, with the floats promoted to double first so that every product is exact:
+ *   n = box(v), sf = box(v F), sw = box(v W), sff = box(v F F), sww = box(v W W), sfw = box(v F W)
+ * where a voxel with v = 0 contributes +0.0 to each whatever F and W hold there (a select, not a multiply).
+ *
+ * Per voxel, in double, in this written order:
+ *   A = sfw - (sf * sw) / n,  B = sff - (sf * sf) / n,  C = sww - (sw * sw) / n
+ * p is COUNTED when v(p) = 1, n >= 2, B > tau * sff and C > tau * sww, tau = 2^-30: a window that is flat in either
+ * volume carries no correlation, and the relative test keeps the rule free of the intensity scale.  Counted voxels get
+ *   cc = (A * A) / (B * C),  a = (2 * A) / (B * C),  b = (2 * cc) / C,  mf = sf / n,  mw = sw / n
+ * and uncounted ones cc = a = b = 0.  cc is the SQUARED correlation: a locally inverted contrast scores like a direct
+ * one (cc = 1 for W = alpha F + beta with alpha of either sign).
+ *
+ * Outputs of the statistics pass (sift3d_hip_lncc): the optional map d_cc, float [nz][ny][nx] = (float) cc; the
+ * optional coefficient volumes d_coef, DOUBLE [4][nz][ny][nx] = a, a * mf, b, b * mw (+0.0 where uncounted; double
+ * because a scales with 1 / intensity^2 and leaves float's range on subnormal and huge content); and d_stats, a
+ * record with the layout and reduction rule of SIFT3D_AMD_DEMONS_STATS_BYTES: bytes 0-7 the double sum of cc over the
+ * counted voxels, bytes 8-15 the uint64 count; per-workgroup partials reduced in a fixed order, no float atomics; the
+ * order of that one sum is not part of the contract.
+ *
+ * Exact gradient and force (sift3d_hip_lncc_force).  With validity held fixed, d cc(p) / d W(q) = a(p) (F(q) - mf(p))
+ * - b(p) (W(q) - mw(p)) for valid q in N(p).  Windows are symmetric, so the derivative of sum_p cc(p) is
+ *   g(q) = (F(q) * box(a)(q) - box(a mf)(q)) - (W(q) * box(b)(q) - box(b mw)(q))
+ * in double, with that grouping and the same box order.  The force is phi_e(q) = (float)(g(q) * (double) d_e W(q)) at
+ * voxels with v(q) = 1 and +0.0f elsewhere; d_e is the derivative of "Dense demons refinement" step 3
+ * (numpy.gradient's rules on the fixed grid, in float).  Moving u along +phi increases the mean cc.
+ *
+ * Normalisation of a field to a step length (sift3d_hip_field_normalize): m2 = max_p (((double) phi_x^2 +
+ * (double) phi_y^2) + (double) phi_z^2), exact and order-free; s = (float)(step / sqrt(m2)); every component is
+ * replaced by s * phi_e (float multiply).  m2 == 0 leaves the field as it is.  No host synchronisation: the scale is
+ * read from device memory by the kernel that applies it.  The field is assumed finite.
+ *
+ * Iteration k (sift3d_amd_demons_lncc_device), every stage on `stream`:
+ *   1. W = sift3d_hip_warp_field(M, u, LINEAR, fill 0);
+ *   2. the statistics, giving the coefficients and stats[k];
+ *   3. phi = the force;
+ *   4. sigma_fluid > 0: phi blurred exactly as step 3 of "Dense demons refinement";
+ *   5. phi normalised to `step` voxels (positive and finite);
+ *   6. ADDITIVE: u += phi.  DIFFEOMORPHIC: u <- COMPOSE(u, exp(phi)) with `squarings` squarings, step 4' of
+ *      "Diffeomorphic demons" word for word;
+ *   7. sigma_diffusion > 0: u blurred as step 5 there.
+ * stats[k] is therefore the statistic before iteration k's update.  Levels, restriction and prolongation follow
+ * "Multi-resolution demons" unchanged (levels == 1 is the flat run); the caller passes the masks per level as in
+ * "Masks in demons" (masks == NULL: none).  The radius is in voxels of the level it runs on.
+ * d_work of the driver holds sift3d_amd_demons_lncc_work_floats floats: with n the finest level's voxels,
+ * pad4(12292 + 15 n (+ 6 n for DIFFEOMORPHIC)) + sum_{l >= 1} pad4(3 n_l) (the partials and the normalisation's work;
+ * the coefficients, 8 n; v, W, phi, the blur's intermediates; u_new and the exponential's second buffer).
+ *
+ * Refusals, -1 before any device call: NULL pointers (d_cc, d_coef of the statistics pass and the masks may be NULL),
+ * dims <= 0, radius out of range, step not positive and finite, the sigmas', update's, squarings' and levels' rules of
+ * the demons drivers, misalignment (d_stats, d_work and doubles 8 B, floats 4 B), any output or the work buffer
+ * overlapping an input, a mask or another output.  All entries are asynchronous on `stream`, allocate nothing, do no
+ * host synchronisation and use 64-bit offsets.
+ *
+ * Out of scope: LNCC in the log-domain and symmetric updates, in FFD and in the affine stage; more than one channel;
+ * Gaussian windows, or a signed (un-squared) correlation; radii above 4; physical or anisotropic spacing; multi-GPU;
+ * any convergence test that stops the iteration early. */
+#define SIFT3D_AMD_LNCC_MAX_RADIUS 4
+/* the per-workgroup partials at the head of the two passes' d_work */
+#define SIFT3D_AMD_LNCC_PARTIAL_BYTES 32768
+/* d_work of sift3d_hip_field_normalize: the partial maxima, then m2 (double) and s (float) */
+#define SIFT3D_AMD_FIELD_NORMALIZE_WORK_BYTES 16400
+/* d_work of sift3d_hip_lncc and sift3d_hip_lncc_force, in bytes: the partials and v (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_lncc_work_bytes(int nx, int ny, int nz);
+/* the statistics pass: d_F, d_W [nz][ny][nx], d_u [3][nz][ny][nx], d_WF, d_WM masks or NULL, d_cc float [nz][ny][nx]
+ * or NULL, d_coef double [4][nz][ny][nx] or NULL, d_stats 16 B */
+SIFT3D_AMD_API int
+sift3d_hip_lncc(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx, int my, int mz,
+                const float *d_WF, const float *d_WM, int radius, float *d_cc /*NULL*/, double *d_coef /*NULL*/,
+                void *d_stats, void *d_work, void *stream);
+/* the force: d_coef as the statistics pass wrote it (same inputs, masks and radius), d_force [3][nz][ny][nx] */
+SIFT3D_AMD_API int
+sift3d_hip_lncc_force(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_u, int mx, int my,
+                      int mz, const float *d_WF, const float *d_WM, int radius, const double *d_coef, float *d_force,
+                      void *d_work, void *stream);
+/* d_field [3][nz][ny][nx] in / out; d_work SIFT3D_AMD_FIELD_NORMALIZE_WORK_BYTES, 8-byte aligned */
+SIFT3D_AMD_API int
+sift3d_hip_field_normalize(float *d_field, int nx, int ny, int nz, double step, void *d_work, void *stream);
+/* device scratch of sift3d_amd_demons_lncc_device, in floats, for a finest fixed grid (nx, ny, nz) (0 for bad
+ * arguments) */
+SIFT3D_AMD_API size_t sift3d_amd_demons_lncc_work_floats(int nx, int ny, int nz, int update, int levels);
+/* level [levels], masks [levels] or NULL (host memory, level 0 the finest; one channel per volume); then the radius
+ * where sift3d_amd_demons_masked_device has nc and the step where it has alpha; d_u [3][nz_0][ny_0][nx_0] in / out;
+ * d_stats 16 B per iteration in the order run, coarsest level first (room for one when there is none) */
+SIFT3D_AMD_API int
+sift3d_amd_demons_lncc_device(const sift3d_amd_demons_level *level, const sift3d_amd_demons_level_masks *masks,
+                              int levels, int radius, float *d_u, double step, double sigma_fluid,
+                              double sigma_diffusion, int update, int squarings, float *d_work, void *d_stats,
+                              void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Distance transforms and surface distances                                 */
 /* ------------------------------------------------------------------------ */
 /* The exact Euclidean distance transform (EDT) of a mask, the signed distance of a set, the six-neighbour surface of

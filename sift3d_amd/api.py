@@ -1204,6 +1204,55 @@ def similarity(fixed, moving, transform=None, bins=64, interp="linear", range_fi
     return similarity_measures(hist.cpu().numpy(), hip.similarity_stats(stats))
 
 
+LocalNcc = collections.namedtuple("LocalNcc", "value count map")
+LNCC_MAX_RADIUS = 4
+
+
+def _lncc_radius(radius, what):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= LNCC_MAX_RADIUS:
+        raise ValueError("%s: radius must be an integer in 1 .. %d, not %r" % (what, LNCC_MAX_RADIUS, radius))
+    return int(radius)
+
+
+def local_ncc(fixed, moving, transform=None, radius=2, mask_fixed=None, mask_moving=None, return_map=False):
+    """The local (windowed) squared cross-correlation of `fixed` and `moving` seen through a pull map (contract:
+    include/sift3d_amd.h, "Local cross-correlation"; the CC metric of ANTs): per fixed voxel the squared correlation
+    of the two volumes over the (2 radius + 1)^3 window around it, which does not change under a gain and offset that
+    vary slowly in space.  Returns LocalNcc(value = the mean over the counted voxels (NaN when nothing is counted),
+    count, map = the float32 map [nz, ny, nx] as a CUDA tensor when return_map, else None).  A voxel is counted where
+    it samples inside `moving`, is in both masks, has a second valid voxel in its window and neither volume is flat
+    there.  transform: as similarity's (None, a 3 x 4 pull map, a TPS or a displacement field); it is turned into a
+    field with displacement_field and `moving` is warped with warp_field (linear, fill 0).  The volumes and masks: as
+    similarity's.  Reads the result, so it waits for torch's current stream."""
+    import torch
+    from . import hip
+    r = _lncc_radius(radius, "local_ncc")
+    WF = _mask_host(mask_fixed, fixed, "local_ncc", "mask_fixed")
+    WM = _mask_host(mask_moving, moving, "local_ncc", "mask_moving")
+    shapes = [tuple(v.shape) if hasattr(v, "shape") else tuple(np.shape(v)) for v in (fixed, moving)]
+    if transform is None and shapes[0] != shapes[1]:
+        raise ValueError("local_ncc: without a transform fixed %s and moving %s must have one shape" % tuple(shapes))
+    F = _similarity_volume(fixed, "local_ncc", "fixed")
+    M = _similarity_volume(moving, "local_ncc", "moving", F.device)
+    WF = _mask_tensor(WF, F, "local_ncc", "mask_fixed")
+    WM = _mask_tensor(WM, F, "local_ncc", "mask_moving")
+    T = _similarity_transform(transform, F, "local_ncc")
+    if T is None:
+        u = torch.zeros((3,) + tuple(F.shape), dtype=torch.float32, device=F.device)
+    elif _torch_tensor(T):
+        hip._field_tensor(T, "local_ncc")
+        if tuple(T.shape[1:]) != tuple(F.shape):
+            raise ValueError("local_ncc: the field %s is not on the fixed grid %s" % (tuple(T.shape), tuple(F.shape)))
+        u = T
+    else:
+        u = displacement_field(T, tuple(F.shape), F.device)
+    W = warp_field(M, u, "linear", 0.0)
+    cc = torch.empty(tuple(F.shape), dtype=torch.float32, device=F.device) if return_map else None
+    stats = hip.lncc(F, W, u, r, tuple(M.shape), cc=cc, mask_fixed=WF, mask_moving=WM)
+    sums, counts = hip.demons_stats(stats)
+    return LocalNcc(float(_mean_or_nan(sums, counts)[0]), int(counts[0]), cc)
+
+
 # ---- intensity-driven affine refinement ----------------------------------------------------------
 AffineRefinement = collections.namedtuple(
     "AffineRefinement", "A msd count accepted lambdas levels level_slices evaluations stop warped")
@@ -1938,6 +1987,14 @@ LogDemonsRefinement = collections.namedtuple(
     "LogDemonsRefinement", "field inverse velocity warped msd jacobian inverse_jacobian scaled_max")
 MultiresLogDemonsRefinement = collections.namedtuple(
     "MultiresLogDemonsRefinement", LogDemonsRefinement._fields + ("level_slices",))
+# what refine_field returns for force "lncc": lncc[k] is the mean local squared cross-correlation over the counted
+# voxels before iteration k's update
+LnccRefinement = collections.namedtuple("LnccRefinement", "field warped lncc jacobian")
+MultiresLnccRefinement = collections.namedtuple("MultiresLnccRefinement", "field warped lncc jacobian level_slices")
+# what register_dense returns for force "lncc": DenseRegistration / MultiresRegistration with lncc in the place of msd
+LnccRegistration = collections.namedtuple("LnccRegistration", "A tps inliers num_matches field warped lncc jacobian")
+MultiresLnccRegistration = collections.namedtuple("MultiresLnccRegistration",
+                                                  LnccRegistration._fields + ("level_slices",))
 DEMONS_MAX_LEVELS = 6
 
 # Defaults chosen by a sweep on a case the end-to-end test (tests/test_demons.py) does not use: synth_survey(160,
@@ -1987,7 +2044,8 @@ def demons_squarings(alpha):
 def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA,
                  sigma_fluid=DEMONS_SIGMA_FLUID, sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors",
                  sigma=1.6, update="additive", squarings=None, levels=1, level_iterations=None, velocity=None, bch=1,
-                 max_motion=16.0, velocity_squarings=None, mask_fixed=None, mask_moving=None):
+                 max_motion=16.0, velocity_squarings=None, mask_fixed=None, mask_moving=None, force="demons", radius=2,
+                 step=0.5):
     """Dense demons refinement (contract: include/sift3d_amd.h, "Dense demons refinement") of a displacement
     field [3, nz, ny, nx] on fixed's grid (a pull map fixed voxel -> moving voxel; None: start from zero) so that
     the moving features warped through it agree with the fixed ones at every voxel.  moving, fixed: torch CUDA
@@ -2023,9 +2081,28 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     them with the volumes in its backward force.  With levels > 1 level l's mask is the restriction (restrict_volume)
     of level l - 1's float mask, never a thresholded copy.  With features "descriptors" the descriptor images are
     still computed from the whole volumes: the masks act on the force only.  With both None the calls are the
-    unmasked ones."""
+    unmasked ones.
+    force "lncc" ("Local cross-correlation"): the force is the exact derivative of the local squared cross-correlation
+    over (2 radius + 1)^3 windows, for volumes whose intensity relation varies in space (bias fields, contrast uptake),
+    which the demons force would follow.  Every iteration moves the field by at most `step` voxels (alpha is not
+    used); it needs features "intensity" and update "additive" or "diffeomorphic" (squarings None: 0, the step being
+    at most `step` <= 0.5 voxel by default).  Returns LnccRefinement(field, warped, lncc, jacobian), with levels > 1
+    MultiresLnccRefinement, which adds level_slices; lncc[k] is the mean cc over the counted voxels before iteration
+    k's update (NaN when there is none).  force "demons", the default, is everything above, untouched."""
     import torch
     from . import hip
+    if force not in ("demons", "lncc"):
+        raise ValueError("force must be 'demons' or 'lncc', not %r" % (force,))
+    if force == "lncc":
+        # (ahead of the tensor checks and of any upload: these depend on the arguments alone)
+        if features != "intensity":
+            raise ValueError("force 'lncc' needs features 'intensity', not %r" % (features,))
+        if update not in DEMONS_UPDATES:
+            raise ValueError("force 'lncc' needs update 'additive' or 'diffeomorphic', not %r" % (update,))
+        radius = _lncc_radius(radius, "refine_field")
+        if isinstance(step, bool) or not isinstance(step, (int, float, np.integer, np.floating)) or \
+                not (math.isfinite(step) and step > 0):
+            raise ValueError("refine_field: step must be positive and finite, not %r" % (step,))
     log = update in LOGDEMONS_UPDATES
     if log:
         # (ahead of the tensor checks: these depend on the arguments alone)
@@ -2082,6 +2159,15 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     else:
         hip._field_tensor(field, "refine_field")
         u = field.clone()
+    if force == "lncc":
+        K = 0 if update == "additive" or squarings is None else int(squarings)
+        stats = hip.demons_lncc(Fs, Ms, u, its, radius, step, sigma_fluid, sigma_diffusion, update=update, squarings=K,
+                                masks_fixed=WFs, masks_moving=WMs)
+        cc = _mean_or_nan(*hip.demons_stats(stats))
+        warped = warp_field(moving, u, "linear", 0.0)
+        if levels == 1:
+            return LnccRefinement(u, warped, cc, jacobian_determinant(u))
+        return MultiresLnccRefinement(u, warped, cc, jacobian_determinant(u), _level_slices(its))
     K = 0
     if update != "additive":
         K = demons_squarings(alpha) if squarings is None else int(squarings)
@@ -2100,6 +2186,15 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
         slices[l] = slice(at, at + its[l])
         at += its[l]
     return MultiresRefinement(u, warped, msd, jacobian_determinant(u), tuple(slices))
+
+
+def _level_slices(its):
+    """level l's slice of the per-iteration records, which run the coarsest level first (level 0 the finest)"""
+    slices, at = [None] * len(its), 0
+    for l in range(len(its) - 1, -1, -1):
+        slices[l] = slice(at, at + its[l])
+        at += its[l]
+    return tuple(slices)
 
 
 def _refine_velocity(moving, fixed, Fs, Ms, its, velocity, alpha, sigma_fluid, sigma_diffusion, symmetric, bch,
@@ -2162,22 +2257,30 @@ def prolong_field(field, out_shape):
 
 def register_dense(moving, fixed, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA, sigma_fluid=DEMONS_SIGMA_FLUID,
                    sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, update="additive",
-                   squarings=None, levels=1, level_iterations=None, mask_fixed=None, mask_moving=None, **deformable_kw):
+                   squarings=None, levels=1, level_iterations=None, mask_fixed=None, mask_moving=None, force="demons",
+                   radius=2, step=0.5, **deformable_kw):
     """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field (update,
     squarings, levels and level_iterations as there).  Returns DenseRegistration(A, tps, inliers, num_matches (as
     register_deformable), field, warped, msd, jacobian (as refine_field)); with levels > 1 MultiresRegistration,
     which adds refine_field's level_slices.  mask_fixed, mask_moving: handed to the refine_field stage only (as
-    there); the keypoint and spline stages see the whole volumes."""
+    there); the keypoint and spline stages see the whole volumes.  force, radius, step: refine_field's; with force
+    "lncc" the result is LnccRegistration (levels > 1: MultiresLnccRegistration), which has refine_field's lncc where
+    the others have msd."""
     _volume_tensor(moving, "register_dense", "moving")
     _volume_tensor(fixed, "register_dense", "fixed")
     d = register_deformable(moving, fixed, **deformable_kw)
     u = displacement_field(d.tps, tuple(fixed.shape), fixed.device)
     r = refine_field(moving, fixed, u, iterations, alpha, sigma_fluid, sigma_diffusion, features, sigma, update,
-                     squarings, levels, level_iterations, mask_fixed=mask_fixed, mask_moving=mask_moving)
+                     squarings, levels, level_iterations, mask_fixed=mask_fixed, mask_moving=mask_moving, force=force,
+                     radius=radius, step=step)
+    head = (d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped)
+    if force == "lncc":
+        if int(levels) > 1:
+            return MultiresLnccRegistration(*head, r.lncc, r.jacobian, r.level_slices)
+        return LnccRegistration(*head, r.lncc, r.jacobian)
     if int(levels) > 1:
-        return MultiresRegistration(d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped, r.msd, r.jacobian,
-                                    r.level_slices)
-    return DenseRegistration(d.A, d.tps, d.inliers, d.num_matches, r.field, r.warped, r.msd, r.jacobian)
+        return MultiresRegistration(*head, r.msd, r.jacobian, r.level_slices)
+    return DenseRegistration(*head, r.msd, r.jacobian)
 
 
 # ---- field composition, exponential and inverse ---------------------------------------------------------------

@@ -1639,3 +1639,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* initial transforms: moments, batched similarity, candidate maps, ranking and the driver */
 #include "sift3d_init.c"
+
+/* local cross-correlation: the checked passes, the field normalisation and the demons-style driver */
+#include "sift3d_lncc.c"

@@ -6,6 +6,7 @@ current stream, so results are ordered with other torch work on that stream.
 """
 import collections
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -419,6 +420,16 @@ def lib():
         "sift3d_amd_logdemons_masked_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
                                                          C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                                          C.c_int, C.c_int, vp, vp, vp]),
+        "sift3d_amd_lncc_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_hip_lncc": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + masks +
+                            [C.c_int, vp, vp, vp, vp, vp]),
+        "sift3d_hip_lncc_force": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int] + masks +
+                                  [C.c_int, vp, vp, vp, vp]),
+        "sift3d_hip_field_normalize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]),
+        "sift3d_amd_demons_lncc_work_floats": (C.c_size_t, [C.c_int] * 5),
+        "sift3d_amd_demons_lncc_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
+                                                    C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                    C.c_int, vp, vp, vp]),
         "sift3d_amd_distance_work_bytes": (C.c_size_t, [C.c_int] * 3),
         "sift3d_hip_distance_sq": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
         "sift3d_hip_distance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
@@ -2535,6 +2546,115 @@ def logdemons(Fs, Ms, velocity, iterations, alpha, sigma_fluid=0.0, sigma_diffus
         _check(lib().sift3d_amd_logdemons_masked_device(tab, wtab, *tail), "sift3d_amd_logdemons_masked_device")
     else:
         _check(lib().sift3d_amd_logdemons_device(tab, *tail), "sift3d_amd_logdemons_device")
+    return stats[:total * DEMONS_STATS_BYTES // 8]
+
+
+LNCC_MAX_RADIUS = 4
+FIELD_NORMALIZE_WORK_BYTES = 16400
+
+
+def _lncc_radius(radius, what):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= LNCC_MAX_RADIUS:
+        raise ValueError("%s: radius must be an integer in 1 .. %d, not %r" % (what, LNCC_MAX_RADIUS, radius))
+    return int(radius)
+
+
+def _lncc_step(step, what):
+    if isinstance(step, bool) or not isinstance(step, (int, float, np.integer, np.floating)) or \
+            not (math.isfinite(step) and step > 0):
+        raise ValueError("%s: step must be positive and finite, not %r" % (what, step))
+    return float(step)
+
+
+def _lncc_pass(what, F, W, field, moving_shape, radius, mask_fixed, mask_moving, work):
+    """The checks the two windowed passes share: F, W [nz, ny, nx] and the field [3, nz, ny, nx] on one grid and
+    device, the masks as demons_force's.  Returns (the entry's arguments up to the radius, work)."""
+    for t, name in ((F, "F"), (W, "W")):
+        _tensor(t, "%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx]" % (what, name), dims=(3,))
+    _demons_images(F, W, field, what)
+    if tuple(W.shape) != tuple(F.shape):
+        raise ValueError("%s: W %s is not on the fixed grid %s" % (what, tuple(W.shape), tuple(F.shape)))
+    r = _lncc_radius(radius, what)
+    nz, ny, nx = F.shape
+    mz, my, mx = (nz, ny, nx) if moving_shape is None else tuple(int(v) for v in moving_shape)
+    masks = _demons_masks(what, F, (mz, my, mx), mask_fixed, mask_moving) or (None, None)
+    work = _byte_work(what, work, lib().sift3d_amd_lncc_work_bytes(nx, ny, nz), F)
+    return (F.data_ptr(), nx, ny, nz, W.data_ptr(), field.data_ptr(), mx, my, mz) + tuple(masks) + (r,), work
+
+
+def lncc(F, W, field, radius=2, moving_shape=None, cc=None, coef=None, stats=None, work=None, mask_fixed=None,
+         mask_moving=None):
+    """The statistics pass of local cross-correlation (sift3d_hip_lncc; contract in include/sift3d_amd.h, "Local
+    cross-correlation"): the fixed volume F and the warped moving volume W [nz, ny, nx], the field [3, nz, ny, nx] that
+    made W, moving_shape (mz, my, mx) the moving grid of the validity test (None: the fixed grid).  cc: a float32
+    tensor [nz, ny, nx] that receives the map, or None; coef: a float64 tensor [4, nz, ny, nx] that receives the
+    coefficient volumes, or None.  mask_fixed, mask_moving: as demons_force's.  torch CUDA, on torch's current stream.
+    Returns the stats tensor (16 bytes: the sum of cc over the counted voxels and their count; demons_stats)."""
+    import torch
+    head, work = _lncc_pass("lncc", F, W, field, moving_shape, radius, mask_fixed, mask_moving, work)
+    if cc is not None:
+        _tensor(cc, "lncc: cc must be a contiguous float32 CUDA tensor of F's shape on its device",
+                shape=tuple(F.shape), device=F.device)
+    if coef is not None:
+        _tensor(coef, "lncc: coef must be a contiguous float64 CUDA tensor [4, nz, ny, nx] on F's device",
+                shape=(4,) + tuple(F.shape), device=F.device, dtype="float64")
+    if stats is None:
+        stats = torch.empty(DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=F.device)
+    _run("sift3d_hip_lncc", *head, None if cc is None else cc.data_ptr(), None if coef is None else coef.data_ptr(),
+         stats.data_ptr(), work.data_ptr(), current_stream())
+    return stats
+
+
+def lncc_force(F, W, field, coef, force, radius=2, moving_shape=None, work=None, mask_fixed=None, mask_moving=None):
+    """The force of local cross-correlation (sift3d_hip_lncc_force): force [3, nz, ny, nx] float32 from the coefficient
+    volumes coef (float64 [4, nz, ny, nx]) that lncc wrote for the same F, W, field, masks and radius.  Returns force."""
+    head, work = _lncc_pass("lncc_force", F, W, field, moving_shape, radius, mask_fixed, mask_moving, work)
+    _tensor(coef, "lncc_force: coef must be a contiguous float64 CUDA tensor [4, nz, ny, nx] on F's device",
+            shape=(4,) + tuple(F.shape), device=F.device, dtype="float64")
+    _field_tensor(force, "lncc_force", "force")
+    if tuple(force.shape) != tuple(field.shape) or force.device != F.device:
+        raise ValueError("lncc_force: force must be shaped like the field, on its device")
+    _run("sift3d_hip_lncc_force", *head, coef.data_ptr(), force.data_ptr(), work.data_ptr(), current_stream())
+    return force
+
+
+def field_normalize(field, step, work=None):
+    """The field [3, nz, ny, nx] scaled in place so that its longest vector is `step` voxels
+    (sift3d_hip_field_normalize); an all-zero field is left as it is.  No host synchronisation.  Returns field."""
+    s = _lncc_step(step, "field_normalize")
+    _field_tensor(field, "field_normalize")
+    work = _byte_work("field_normalize", work, FIELD_NORMALIZE_WORK_BYTES, field)
+    _, nz, ny, nx = field.shape
+    _run("sift3d_hip_field_normalize", field.data_ptr(), nx, ny, nz, s, work.data_ptr(), current_stream())
+    return field
+
+
+def demons_lncc(Fs, Ms, field, iterations, radius=2, step=0.5, sigma_fluid=0.0, sigma_diffusion=0.0, work=None,
+                update="additive", squarings=0, masks_fixed=None, masks_moving=None):
+    """Demons-style ascent of the local cross-correlation (sift3d_amd_demons_lncc_device; contract in
+    include/sift3d_amd.h, "Local cross-correlation"): Fs, Ms are the fixed and moving volumes [nz, ny, nx] per level,
+    level 0 the finest (one level: a flat run), iterations one count per level; the field [3, nz, ny, nx] on Fs[0]'s
+    grid is refined in place.  Every iteration moves the field by at most `step` voxels.  update, squarings,
+    masks_fixed, masks_moving: as demons_multires's.  torch CUDA float32, on torch's current stream, no host
+    synchronisation.  Returns the stats tensor: 16 bytes per iteration in the order run (demons_stats: the sum of cc
+    over the counted voxels and their count, before the iteration's update)."""
+    import torch
+    what = "demons_lncc"
+    mode = _demons_update(update, what)
+    r = _lncc_radius(radius, what)
+    s = _lncc_step(step, what)
+    WFs, WMs = _demons_mask_lists(what, len(Fs), masks_fixed, masks_moving)
+    for t in list(Fs) + list(Ms):
+        _tensor(t, "%s: every level's volumes must be contiguous float32 CUDA tensors [nz, ny, nx]" % what, dims=(3,))
+    tab, levels, _, its = _demons_levels(what, Fs, Ms, field, iterations)
+    wtab = _demons_level_masks(what, Fs, Ms, WFs, WMs)
+    _, nz, ny, nx = field.shape
+    work = _work(work, lib().sift3d_amd_demons_lncc_work_floats(nx, ny, nz, mode, levels), field, what)
+    total = sum(its)
+    stats = torch.empty(max(total, 1) * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
+    _run("sift3d_amd_demons_lncc_device", tab, wtab, levels, r, field.data_ptr(), s, float(sigma_fluid),
+         float(sigma_diffusion), mode, int(squarings) if mode else 0, work.data_ptr(), stats.data_ptr(),
+         current_stream())
     return stats[:total * DEMONS_STATS_BYTES // 8]
 
 
