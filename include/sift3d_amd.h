@@ -2208,6 +2208,160 @@ sift3d_amd_demons_lncc_device(const sift3d_amd_demons_level *level, const sift3d
                               void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Block matching                                                            */
+/* ------------------------------------------------------------------------ */
+/* Rigid / affine registration by block matching with a trimmed least-squares fit (Ourselin et al. 2001, the scheme of
+ * NiftyReg's reg_aladin): every 4^3 block of the fixed volume looks for its best-correlated position in the warped
+ * moving volume inside a search cube, the matched point pairs go to a least-trimmed-squares (LTS) fit, and this is
+ * repeated coarse to fine.  It needs no keypoints, tolerates a spatially varying gain (the score is a local
+ * correlation) and trims outliers instead of averaging them in.  No upstream counterpart: PARITY UNPINNED, pinned to
+ * this contract and its numpy restatement (tests/block_match_restatement.py); the device records bit for bit.
+ *
+ * Inputs (sift3d_hip_block_match).  F[nz][ny][nx], the fixed volume; W[nz][ny][nx], the moving volume already warped
+ * onto the fixed grid; both finite float32, voxel units.  Optional float masks V_F and V_W on the same grid: a voxel
+ * is in where w >= 0.5f (the rule of "Masks"); NULL is all in.  Radius R in [1, SIFT3D_AMD_BLOCK_MAX_RADIUS].
+ *
+ * Blocks.  Edge 4: block (bx, by, bz) covers voxels 4 b .. 4 b + 3 on every axis; nb_d = n_d / 4 (integer division),
+ * trailing voxels belong to no block; -1 when any nb_d == 0.  The block's voxel i = x + 4 y + 16 z (local), 0 .. 63.
+ * Candidates.  d = (dx, dy, dz) in [-R, R]^3, k = ((dz + R)(2R + 1) + (dy + R))(2R + 1) + (dx + R).
+ *
+ * Sums, all in double, each from +0.0 with i ascending and one add per term:
+ *   sF = sum (double) F_i, sFF = sum (double) F_i (double) F_i; per candidate, with W_i the voxel of W at the block's
+ *   voxel i + d:  sW, sWW, sFW = sum (double) F_i (double) W_i.
+ * A product of two floats is exact in double, so the contract is the same with and without fused multiply-add.
+ *   vF = sFF - (sF sF) / 64,  vW = sWW - (sW sW) / 64,  c = sFW - (sF sW) / 64,  cc = (c c) / (vF vW)  (that grouping)
+ *
+ * Validity.  A block is valid when all 64 voxels are in V_F and vF > sFF 2^-40 (a relative floor: below it the
+ * variance of float data is rounding noise; an all-zero block fails it since 0 > 0 is false).  A candidate is valid
+ * when the shifted block lies wholly inside the grid, all 64 of its W voxels are in V_W and vW > sWW 2^-40.  A valid
+ * block without a valid candidate is invalid.
+ * Choice.  The valid candidate of greatest cc (compared as doubles); equal cc: the smaller dx^2 + dy^2 + dz^2, then
+ * the smaller k.
+ * Sub-voxel step, in double.  Per axis a, c0 the winner's cc and c-, c+ those of its two neighbours along a: when both
+ * neighbours lie in the search cube and are valid candidates and den = (c- - 2 c0) + c+ < 0, the offset is
+ * o_a = 0.5 (c- - c+) / den clamped to [-0.5, 0.5]; otherwise o_a = 0.  (Without this step the driver below stalls
+ * near 0.8 voxel: once most kept blocks report displacement 0 the trimmed fit keeps exactly those.)
+ *
+ * Outputs, planar over [nbz][nby][nbx]: d_disp float [3] (x, y, z) = (float) ((double) d_a + o_a), 0 for an invalid
+ * block; d_cc float = (float) cc, -1.0f invalid; d_var DOUBLE = vF, the driver's selection key, 0.0 invalid (double:
+ * vF of huge content leaves float's range).
+ * Asynchronous on `stream`, allocates nothing, no host synchronisation, 64-bit offsets.  This implementation needs no
+ * work buffer: sift3d_amd_block_match_work_bytes is 0 and d_work may be NULL; it is never read or written.
+ * -1 before any device call on NULL pointers (the masks and d_work may be NULL), dims <= 0 or any dim < 4, R out of
+ * range, misalignment (d_var 8 B, floats 4 B), an output overlapping an input, a mask or another output.
+ *
+ * Trimmed fit (sift3d_amd_fit_trimmed; host).  n point pairs src_i -> dst_i (n x 3 doubles each), a model
+ * (TRANSLATION, RIGID, AFFINE) and per-axis scales S_src, S_dst (NULL = 1): with x = S_src src and y = S_dst dst the
+ * model y ~ L x + t is fitted and returned as T = S_dst^-1 [L | t] S_src (3 x 4, row-major), so RIGID is rigid in
+ * physical space for anisotropic voxels.  TRANSLATION: L = I, t the difference of the centroids.  RIGID: the
+ * least-squares rotation about the centroids by Horn's unit quaternion (the dominant eigenvector of the 4 x 4 matrix
+ * of the cross-covariance, cyclic Jacobi), so det L = +1 always, also for reflection-prone sets.  AFFINE: the normal
+ * equations of the centred points, solved in double.  Sums run serially in index order (the result does not depend
+ * on the thread count); only the residuals are computed in an OpenMP region.
+ * LTS loop.  1. fit on all n; 2. r_i = |L x_i + t - y_i|^2; 3. keep the k = max(ceil(keep n), n_min) smallest, ties
+ * to the lower index, n_min = 1 / 3 / 4; 4. stop when the kept set equals the set of the last fit or after max_iter
+ * refits, else refit on the kept set and go to 2.  `used` marks the pairs the returned T was fitted to; *iterations
+ * is the number of refits.
+ * -1 on NULL pointers (scales, used may be NULL), n < n_min, an unknown model, keep outside (0, 1], max_iter < 0,
+ * non-finite points, scales not positive and finite, or a degenerate set in any fit: with l1 >= l2 >= l3 the
+ * eigenvalues of the scatter matrix of the fitted x about their centroid, RIGID refuses l2 <= 1e-10 l1 (collinear),
+ * AFFINE l3 <= 1e-10 l1 (coplanar), both l1 == 0; RIGID checks the y likewise.  TRANSLATION has no degenerate set.
+ *
+ * Driver (sift3d_amd_block_register_device).  Fixed F (ox, oy, oz) and moving M (nx, ny, nz) on the device, optional
+ * masks, the start pull map A (fixed voxel -> moving voxel, sift3d_hip_warp_affine's convention).  Levels follow
+ * sift3d_amd_affine_refine_device word for word: volumes and FLOAT masks by sift3d_hip_restrict2 at scale 1, A[:][3]
+ * halved going down a level and doubled going up, the coarsest level first.  Every level's fixed grid must be >= 8 on
+ * every axis, else -1.  Per iteration on a level:
+ *   1. W = warp_affine(M, A, LINEAR, fill 0);
+ *   2. V_W = warp_affine(the level's moving mask, or a volume of ones, A, NEAREST, fill 0);
+ *   3. sift3d_hip_block_match(F, W, V_F = the level's fixed mask or NULL, V_W, radius);
+ *   4. the three records to the host and ONE wait for the stream (the trade of sift3d_amd_affine_refine_device);
+ *   5. of the valid blocks (cc >= 0) the ceil(keep_blocks n_valid) of largest d_var, ties to the lower block index;
+ *   6. pairs in block-index order: src_i = the block's centre (4 b + 1.5 per axis), dst_i = A (src_i + disp_i) in
+ *      warp_affine's order of operations;
+ *   7. A' = sift3d_amd_fit_trimmed(src, dst, model, keep_inliers, 20, spacing_fixed, spacing_moving) (the spacings
+ *      of level 0 serve every level: both double per level, which leaves T unchanged);
+ *   8. fewer than n_min valid blocks or a refused fit: FAILED, A stays, the level ends.  Else move = the largest
+ *      distance |A' p - A p| over the 8 corners p of the level's fixed grid, A = A'; move < tol: CONVERGED; the
+ *      level's `iterations` done: ITERATIONS; else 1.
+ * The result holds the final A (also written to A_io), one trail entry per iteration in the order run (level, the A
+ * it started from and the A it produced (the start again when FAILED), n_valid, n_selected, n_used, the mean cc over
+ * the used pairs, the rms of their residuals |L x + t - y| in the fit's scaled units, the corner move; the last three
+ * NaN when FAILED) and the stop reason of level 0.  params == NULL takes the defaults below.
+ * d_work holds sift3d_amd_block_register_work_floats floats, 8-byte aligned: with n_l, m_l the voxels of the fixed and
+ * moving grid on level l and b_0 the blocks of level 0,
+ *   pad4(6 b_0) + 2 pad4(n_0) + [no moving mask: pad4(m_0)] + sum_{l >= 1} (pad4(n_l) + pad4(m_l)
+ *   + [fixed mask: pad4(n_l)] + [moving mask: pad4(m_l)])
+ * (the records: var, disp, cc; W; V_W; the ones; the level volumes and masks).  The host copies of the records are
+ * allocated and freed by the call.
+ * -1 before any device call on NULL pointers, dims <= 0, a level's fixed grid below 8, a non-finite A, an unknown
+ * model, levels outside [1, SIFT3D_AMD_DEMONS_MAX_LEVELS], iterations outside [1, SIFT3D_AMD_BLOCK_MAX_ITERATIONS],
+ * radius out of range, keep_blocks or keep_inliers outside (0, 1], tol < 0 or not finite, spacings not positive and
+ * finite, misalignment (d_work 8 B, volumes 4 B), a work buffer that overlaps a volume or mask.
+ *
+ * Out of scope: block edges other than 4, overlapping blocks, search steps other than 1; skipping low-variance
+ * blocks on the device; a similarity (7-parameter) model; non-affine start transforms; more than one channel;
+ * multi-GPU; wiring into the keypoint and FFD registration pipelines. */
+#define SIFT3D_AMD_BLOCK_MAX_RADIUS 6
+#define SIFT3D_AMD_BLOCK_MAX_ITERATIONS 64          /* per level */
+#define SIFT3D_AMD_BLOCK_MAX_TRAIL (6 * SIFT3D_AMD_BLOCK_MAX_ITERATIONS)       /* SIFT3D_AMD_DEMONS_MAX_LEVELS levels */
+#define SIFT3D_AMD_MODEL_TRANSLATION 0
+#define SIFT3D_AMD_MODEL_RIGID 1
+#define SIFT3D_AMD_MODEL_AFFINE 2
+#define SIFT3D_AMD_BLOCK_STOP_CONVERGED 0
+#define SIFT3D_AMD_BLOCK_STOP_ITERATIONS 1
+#define SIFT3D_AMD_BLOCK_STOP_FAILED 2
+/* bytes of d_work for sift3d_hip_block_match: 0, this implementation needs none */
+SIFT3D_AMD_API size_t sift3d_amd_block_match_work_bytes(int nx, int ny, int nz, int radius);
+/* d_F, d_W [nz][ny][nx]; d_VF, d_VW masks or NULL; d_disp float [3][nbz][nby][nbx], d_cc float and d_var double
+ * [nbz][nby][nbx]; d_work may be NULL */
+SIFT3D_AMD_API int
+sift3d_hip_block_match(const float *d_F, int nx, int ny, int nz, const float *d_W, const float *d_VF,
+                       const float *d_VW, int radius, float *d_disp, float *d_cc, double *d_var, void *d_work,
+                       void *stream);
+/* host only */
+SIFT3D_AMD_API int
+sift3d_amd_fit_trimmed(const double *src, const double *dst, int n, int model, double keep, int max_iter,
+                       const double *scale_src /*3 or NULL*/, const double *scale_dst /*3 or NULL*/, double *T /*12*/,
+                       unsigned char *used /*n or NULL*/, int *iterations);
+typedef struct {
+    int model;                 /* SIFT3D_AMD_MODEL_RIGID */
+    int levels;                /* 3 */
+    int iterations;            /* 5, per level */
+    int radius;                /* 3 */
+    double keep_blocks;        /* 0.5 of the valid blocks, by variance */
+    double keep_inliers;       /* 0.5 of the pairs, by residual */
+    double tol;                /* 0.01 voxels */
+    double spacing_fixed[3];   /* 1, 1, 1 (x, y, z) */
+    double spacing_moving[3];  /* 1, 1, 1 */
+} sift3d_amd_block_register_params;
+typedef struct {
+    int level, n_valid, n_selected, n_used;
+    double A_in[12], A_out[12];
+    double mean_cc, rms, move;
+} sift3d_amd_block_iteration;
+typedef struct {
+    double A[12];
+    int iterations, stop;
+    sift3d_amd_block_iteration trail[SIFT3D_AMD_BLOCK_MAX_TRAIL];
+} sift3d_amd_block_register_result;
+SIFT3D_AMD_API void sift3d_amd_block_register_default_params(sift3d_amd_block_register_params *p);
+/* for bindings that restate the layouts: sizeof the params (0), iteration (1) and result (2) structs, then
+ * SIFT3D_AMD_BLOCK_MAX_ITERATIONS (3), SIFT3D_AMD_BLOCK_MAX_RADIUS (4); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_block_register_struct_bytes(int which);
+/* device scratch of the driver in floats (0 for bad arguments, a level's fixed grid below 8 among them) */
+SIFT3D_AMD_API size_t
+sift3d_amd_block_register_work_floats(int ox, int oy, int oz, int nx, int ny, int nz, int levels, int mask_fixed,
+                                      int mask_moving);
+/* d_F [oz][oy][ox], d_M [nz][ny][nx], d_WF / d_WM masks on those grids or NULL; A_io [12] on the host, in / out;
+ * waits for `stream` once per iteration */
+SIFT3D_AMD_API int
+sift3d_amd_block_register_device(const float *d_F, int ox, int oy, int oz, const float *d_M, int nx, int ny, int nz,
+                                 const float *d_WF, const float *d_WM, double *A_io,
+                                 const sift3d_amd_block_register_params *params,
+                                 sift3d_amd_block_register_result *result, float *d_work, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Distance transforms and surface distances                                 */
 /* ------------------------------------------------------------------------ */
 /* The exact Euclidean distance transform (EDT) of a mask, the signed distance of a set, the six-neighbour surface of

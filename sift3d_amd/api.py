@@ -1481,6 +1481,160 @@ def refine_affine(moving, fixed, A=None, levels=1, free="affine", interp="linear
     return out
 
 
+# ---- block matching -------------------------------------------------------------------------------
+BlockMatches = collections.namedtuple("BlockMatches", "points_fixed points_moving cc variance")
+TrimmedFit = collections.namedtuple("TrimmedFit", "A used iterations")
+BlockRegistration = collections.namedtuple("BlockRegistration", "A warped trail stop")
+BlockIteration = collections.namedtuple(
+    "BlockIteration", "level A_in A_out n_valid n_selected n_used mean_cc rms move")
+BLOCK_MODELS = ("translation", "rigid", "affine")
+
+
+def _block_model(model, what):
+    if model not in BLOCK_MODELS:
+        raise ValueError("%s: model must be 'translation', 'rigid' or 'affine', not %r" % (what, model))
+    return model
+
+
+def _unit_fraction(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 < v <= 1:
+        raise ValueError("%s: %s must be in (0, 1], not %r" % (what, name, v))
+    return float(v)
+
+
+def _volume_shape(v):
+    return tuple(int(n) for n in (v.shape if hasattr(v, "shape") else np.shape(v)))
+
+
+def _affine_start(A, what, name="A"):
+    A0 = np.eye(3, 4) if A is None else _affine_or_none(A)
+    if A0 is None or not np.isfinite(A0).all():
+        raise ValueError("%s: %s must be a finite 3 x 4 affine pull map or None" % (what, name))
+    return A0
+
+
+def block_match(fixed, moving, transform=None, radius=3, mask_fixed=None, mask_moving=None):
+    """Match every 4^3 block of `fixed` to its best-correlated position in `moving` seen through the 3 x 4 pull map
+    `transform` (None: the identity), inside a (2 radius + 1)^3 search cube with a sub-voxel step (contract:
+    include/sift3d_amd.h, "Block matching").  The score is the squared local correlation, so a gain and offset that
+    vary in space do not disturb it.  Returns BlockMatches(points_fixed: the centres of the valid blocks, n x 3 (x, y,
+    z) in fixed voxels; points_moving: where each lands in `moving`, transform (centre + displacement); cc; variance:
+    the block's sum of squared deviations, the key the driver selects blocks by).  A block is valid when it lies in
+    mask_fixed, is not flat, and has a candidate that lies in the grid, in the warped mask_moving, and is not flat.
+    The volumes and masks: as similarity's.  Reads the result, so it waits for torch's current stream."""
+    import torch
+    from . import hip
+    what = "block_match"
+    r = hip._block_radius(radius, what)
+    A = _affine_start(transform, what, "transform")
+    if len(_volume_shape(fixed)) == 3 and min(_volume_shape(fixed)) < 4:
+        raise ValueError("%s: fixed %s must hold a block of 4 voxels on every axis" % (what, _volume_shape(fixed)))
+    WF = _mask_host(mask_fixed, fixed, what, "mask_fixed")
+    WM = _mask_host(mask_moving, moving, what, "mask_moving")
+    F = _similarity_volume(fixed, what, "fixed")
+    M = _similarity_volume(moving, what, "moving", F.device)
+    WF = _mask_tensor(WF, F, what, "mask_fixed")
+    WM = _mask_tensor(WM, F, what, "mask_moving")
+    W = torch.empty_like(F)
+    hip.warp_affine(M, W, A, "linear")
+    VW = torch.empty_like(F)
+    hip.warp_affine(WM if WM is not None else torch.ones_like(M), VW, A, "nearest")
+    disp, cc, var = hip.block_match(F, W, r, WF, VW)
+    cc = cc.cpu().numpy().reshape(-1)
+    keep = np.nonzero(cc >= 0)[0]
+    nbz, nby, nbx = var.shape
+    centres = np.stack([4.0 * (keep % nbx) + 1.5, 4.0 * (keep // nbx % nby) + 1.5, 4.0 * (keep // (nbx * nby)) + 1.5], 1)
+    q = centres + disp.cpu().numpy().reshape(3, -1)[:, keep].T.astype(np.float64)
+    return BlockMatches(centres, q @ A[:, :3].T + A[:, 3], cc[keep], var.cpu().numpy().reshape(-1)[keep])
+
+
+def fit_transform(src, dst, model="rigid", keep=0.5, spacing_src=None, spacing_dst=None, max_iter=20):
+    """The least-trimmed-squares fit of a "translation", "rigid" or "affine" map dst ~ A [src; 1] to n x 3 point pairs
+    (contract: "Block matching", the trimmed fit): fit, keep the ceil(keep n) pairs of smallest residual, refit, until
+    the kept set repeats or max_iter refits.  Outliers below the share 1 - keep do not move the result.  spacing_src,
+    spacing_dst: voxel sizes (x, y, z) of the two point spaces; "rigid" is then rigid in physical space.  Returns
+    TrimmedFit(A [3, 4], used: the pairs A was fitted to, iterations: the refits).  Host only.  ValueError where the
+    points are too few, not finite or degenerate for the model (collinear for rigid, coplanar for affine)."""
+    from . import hip
+    what = "fit_transform"
+    _block_model(model, what)
+    _unit_fraction(keep, what, "keep")
+    for v, name in ((src, "src"), (dst, "dst")):
+        a = np.asarray(v, np.float64)
+        if a.ndim != 2 or a.shape[1] != 3 or not np.isfinite(a).all():
+            raise ValueError("%s: %s must be finite n x 3 points" % (what, name))
+    if np.shape(src) != np.shape(dst):
+        raise ValueError("%s: dst must have the shape of src" % what)
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        raise ValueError("%s: max_iter must be a non-negative integer, not %r" % (what, max_iter))
+    hip._scale3(spacing_src, what, "spacing_src")
+    hip._scale3(spacing_dst, what, "spacing_dst")
+    out = hip.fit_trimmed(src, dst, model, keep, int(max_iter), spacing_src, spacing_dst)
+    if out is None:
+        raise ValueError("%s: src and dst are too few or degenerate for model=%r" % (what, model))
+    return TrimmedFit(*out)
+
+
+def register_blocks(moving, fixed, A=None, model="rigid", levels=3, iterations=5, radius=3, keep_blocks=0.5,
+                    keep_inliers=0.5, tol=0.01, mask_fixed=None, mask_moving=None, spacing_fixed=None,
+                    spacing_moving=None, init=None):
+    """Register `moving` to `fixed` by block matching with a trimmed fit, coarse to fine (contract:
+    include/sift3d_amd.h, "Block matching"; Ourselin et al. 2001): per iteration `moving` is warped by the current pull
+    map, every 4^3 block of `fixed` finds its best-correlated position within `radius` voxels, the keep_blocks share of
+    the blocks with the most variance give point pairs, and a `model` ("translation", "rigid", "affine") is fitted to
+    the keep_inliers share of the pairs that agree best.  It needs no keypoints, follows a gain that varies in space,
+    and trims what does not match (lesions, missing tissue).  A: the start (fixed voxel -> moving voxel; None: the
+    identity); init: as refine_affine's, with A=None only.  levels: the coarsest first, each halving the grid (every
+    level's fixed grid must keep 8 voxels per axis); iterations: per level; tol: a level stops when no corner of its
+    grid moves by that many voxels.  spacing_fixed, spacing_moving: voxel sizes (x, y, z), so that "rigid" is rigid in
+    physical space.  The volumes and masks: as refine_affine's.  Returns BlockRegistration(A, warped: `moving` through
+    A on the fixed grid, trail: one BlockIteration per iteration in the order run, stop: "converged", "iterations" or
+    "failed" of level 0).  Waits for torch's current stream once per iteration."""
+    import torch
+    from . import hip
+    what = "register_blocks"
+    _block_model(model, what)
+    if init is not None and A is not None:
+        raise ValueError("%s: init makes the start itself; it goes with A=None only" % what)
+    _levels_and_evaluations(what, levels, {}, 1)
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or \
+            not 1 <= iterations <= hip.BLOCK_MAX_ITERATIONS:
+        raise ValueError("%s: iterations must be in [1, %d], not %r" % (what, hip.BLOCK_MAX_ITERATIONS, iterations))
+    r = hip._block_radius(radius, what)
+    _unit_fraction(keep_blocks, what, "keep_blocks")
+    _unit_fraction(keep_inliers, what, "keep_inliers")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or \
+            not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("%s: tol must be finite and not negative, not %r" % (what, tol))
+    kw = dict(model=model, levels=int(levels), iterations=int(iterations), radius=r, keep_blocks=float(keep_blocks),
+              keep_inliers=float(keep_inliers), tol=float(tol))
+    for v, name in ((spacing_fixed, "spacing_fixed"), (spacing_moving, "spacing_moving")):
+        if hip._scale3(v, what, name) is not None:
+            kw[name] = v
+    A0 = _affine_start(A, what)
+    shape = _volume_shape(fixed)
+    for _ in range(int(levels)):
+        if len(shape) == 3 and min(shape) < 8:
+            raise ValueError("%s: levels=%d leaves a fixed grid below 8 voxels on an axis of %s"
+                             % (what, levels, _volume_shape(fixed)))
+        shape = tuple((v + 1) // 2 for v in shape)
+    WF = _mask_host(mask_fixed, fixed, what, "mask_fixed")
+    WM = _mask_host(mask_moving, moving, what, "mask_moving")
+    F = _similarity_volume(fixed, what, "fixed")
+    M = _similarity_volume(moving, what, "moving", F.device)
+    WF = _mask_tensor(WF, F, what, "mask_fixed")
+    WM = _mask_tensor(WM, F, what, "mask_moving")
+    if init is not None:
+        A0 = init_affine(M, F, **_init_keywords(init, what, mask_fixed=WF, mask_moving=WM)).A
+    res = hip.block_register(F, M, A0, hip.block_register_params(**kw), mask_fixed=WF, mask_moving=WM)
+    A1 = np.array(res.A[:], np.float64).reshape(3, 4)
+    warped = torch.empty_like(F)
+    hip.warp_affine(M, warped, A1, "linear")
+    trail = [BlockIteration(e.level, np.array(e.A_in[:]).reshape(3, 4), np.array(e.A_out[:]).reshape(3, 4), e.n_valid,
+                            e.n_selected, e.n_used, e.mean_cc, e.rms, e.move) for e in res.trail[:res.iterations]]
+    return BlockRegistration(A1, warped, trail, hip.BLOCK_STOPS[res.stop])
+
+
 # ---- B-spline free-form deformation ---------------------------------------------------------------
 FFDRefinement = collections.namedtuple("FFDRefinement", "lattice spacing A field warped trail stop jacobian")
 FFDEvaluation = collections.namedtuple("FFDEvaluation", "E msd R n step accepted level")

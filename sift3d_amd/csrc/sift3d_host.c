@@ -1642,3 +1642,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* local cross-correlation: the checked passes, the field normalisation and the demons-style driver */
 #include "sift3d_lncc.c"
+
+/* block matching: the checked matching entry, the trimmed point-pair fit and the coarse-to-fine driver */
+#include "sift3d_block_fit.c"

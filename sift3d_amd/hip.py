@@ -94,6 +94,27 @@ class AffineRefineResult(C.Structure):                     # sift3d_amd_affine_r
                 ("trail", AffineEvaluation * (AFFINE_MAX_LEVELS * AFFINE_MAX_EVALUATIONS))]
 
 
+class BlockRegisterParams(C.Structure):                    # sift3d_amd_block_register_params
+    _fields_ = [("model", C.c_int), ("levels", C.c_int), ("iterations", C.c_int), ("radius", C.c_int),
+                ("keep_blocks", C.c_double), ("keep_inliers", C.c_double), ("tol", C.c_double),
+                ("spacing_fixed", C.c_double * 3), ("spacing_moving", C.c_double * 3)]
+
+
+class BlockIteration(C.Structure):                         # sift3d_amd_block_iteration
+    _fields_ = [("level", C.c_int), ("n_valid", C.c_int), ("n_selected", C.c_int), ("n_used", C.c_int),
+                ("A_in", C.c_double * 12), ("A_out", C.c_double * 12), ("mean_cc", C.c_double), ("rms", C.c_double),
+                ("move", C.c_double)]
+
+
+BLOCK_MAX_ITERATIONS = 64                                  # checked against the library when it is bound (lib())
+BLOCK_MAX_RADIUS = 6
+
+
+class BlockRegisterResult(C.Structure):                    # sift3d_amd_block_register_result
+    _fields_ = [("A", C.c_double * 12), ("iterations", C.c_int), ("stop", C.c_int),
+                ("trail", BlockIteration * (AFFINE_MAX_LEVELS * BLOCK_MAX_ITERATIONS))]
+
+
 class Frame(C.Structure):                                  # sift3d_amd_frame
     _fields_ = [("centroid", C.c_double * 3), ("axes", C.c_double * 9), ("lambda_", C.c_double * 3)]
 
@@ -430,6 +451,18 @@ def lib():
         "sift3d_amd_demons_lncc_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
                                                     C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                                     C.c_int, vp, vp, vp]),
+        "sift3d_amd_block_match_work_bytes": (C.c_size_t, [C.c_int] * 4),
+        "sift3d_hip_block_match": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+        "sift3d_amd_fit_trimmed": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double,
+                                             C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), vp, C.POINTER(C.c_int)]),
+        "sift3d_amd_block_register_default_params": (None, [C.POINTER(BlockRegisterParams)]),
+        "sift3d_amd_block_register_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_amd_block_register_work_floats": (C.c_size_t, [C.c_int] * 9),
+        "sift3d_amd_block_register_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                       vp, vp, C.POINTER(C.c_double),
+                                                       C.POINTER(BlockRegisterParams), C.POINTER(BlockRegisterResult),
+                                                       vp, vp]),
         "sift3d_amd_distance_work_bytes": (C.c_size_t, [C.c_int] * 3),
         "sift3d_hip_distance_sq": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
         "sift3d_hip_distance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
@@ -481,6 +514,11 @@ def lib():
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the initial-transform layouts as %s, the library has %s"
                            % (want, got))
+    want = (C.sizeof(BlockRegisterParams), C.sizeof(BlockIteration), C.sizeof(BlockRegisterResult),
+            BLOCK_MAX_ITERATIONS, BLOCK_MAX_RADIUS)
+    got = tuple(L.sift3d_amd_block_register_struct_bytes(k) for k in range(5))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the block-matching layouts as %s, the library has %s" % (want, got))
     _bound = L
     return L
 
@@ -2656,6 +2694,132 @@ def demons_lncc(Fs, Ms, field, iterations, radius=2, step=0.5, sigma_fluid=0.0, 
          float(sigma_diffusion), mode, int(squarings) if mode else 0, work.data_ptr(), stats.data_ptr(),
          current_stream())
     return stats[:total * DEMONS_STATS_BYTES // 8]
+
+
+# ---- block matching (contract: include/sift3d_amd.h, "Block matching") ----------------------------------------------
+BLOCK_MODEL = {"translation": 0, "rigid": 1, "affine": 2}
+BLOCK_STOPS = ("converged", "iterations", "failed")
+
+
+def _block_radius(radius, what):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= BLOCK_MAX_RADIUS:
+        raise ValueError("%s: radius must be an integer in 1 .. %d, not %r" % (what, BLOCK_MAX_RADIUS, radius))
+    return int(radius)
+
+
+def block_match(F, W, radius=3, valid_fixed=None, valid_warped=None, work=None, stream=None):
+    """sift3d_hip_block_match: every 4^3 block of the fixed volume F [nz, ny, nx] finds its best-correlated position in
+    W (the moving volume warped onto F's grid) inside the (2 radius + 1)^3 search cube.  valid_fixed, valid_warped:
+    float32 masks on the same grid (in where >= 0.5) or None.  work: a CUDA tensor of at least
+    sift3d_amd_block_match_work_bytes bytes or None (this build needs none).  stream: a stream handle, or None for
+    torch's current stream.  torch CUDA float32 contiguous; no host synchronisation.  Returns (disp float32
+    [3, nbz, nby, nbx] (x, y, z), cc float32 [nbz, nby, nbx], var float64 [nbz, nby, nbx]); an invalid block has
+    disp 0, cc -1, var 0."""
+    import torch
+    what = "block_match"
+    for t, name in ((F, "F"), (W, "W")):
+        _tensor(t, "%s: %s must be a contiguous float32 CUDA tensor [nz, ny, nx]" % (what, name), dims=(3,))
+    if tuple(W.shape) != tuple(F.shape) or W.device != F.device:
+        raise ValueError("%s: W %s is not on the fixed grid %s and device" % (what, tuple(W.shape), tuple(F.shape)))
+    r = _block_radius(radius, what)
+    nz, ny, nx = F.shape
+    if min(nx, ny, nz) < 4:
+        raise ValueError("%s: F %s must hold a block of 4 voxels on every axis" % (what, tuple(F.shape)))
+    for w, name in ((valid_fixed, "valid_fixed"), (valid_warped, "valid_warped")):
+        if w is not None:
+            _tensor(w, "%s: %s must be a contiguous float32 CUDA tensor of F's shape %s on its device"
+                    % (what, name, tuple(F.shape)), shape=tuple(F.shape), device=F.device)
+    need = lib().sift3d_amd_block_match_work_bytes(nx, ny, nz, r)
+    if work is not None or need:
+        work = _byte_work(what, work, need, F)
+    nb = (nz // 4, ny // 4, nx // 4)
+    disp = torch.empty((3,) + nb, dtype=torch.float32, device=F.device)
+    cc = torch.empty(nb, dtype=torch.float32, device=F.device)
+    var = torch.empty(nb, dtype=torch.float64, device=F.device)
+    _run("sift3d_hip_block_match", F.data_ptr(), nx, ny, nz, W.data_ptr(),
+         None if valid_fixed is None else valid_fixed.data_ptr(),
+         None if valid_warped is None else valid_warped.data_ptr(), r, disp.data_ptr(), cc.data_ptr(), var.data_ptr(),
+         work.data_ptr() if work is not None and work.numel() else None,
+         current_stream() if stream is None else stream)
+    return disp, cc, var
+
+
+def _scale3(v, what, name):
+    if v is None:
+        return None
+    a = np.ascontiguousarray(v, np.float64)
+    if a.shape != (3,) or not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError("%s: %s must be three positive finite numbers (x, y, z), not %r" % (what, name, v))
+    return a.copy()
+
+
+def fit_trimmed(src, dst, model="rigid", keep=0.5, max_iter=20, scale_src=None, scale_dst=None):
+    """sift3d_amd_fit_trimmed (host): the least-trimmed-squares fit of dst ~ T [src; 1] on n x 3 float64 points.
+    Returns (T [3, 4], used bool [n], refits), or None where the entry refuses (too few or non-finite points, a
+    degenerate set).  ValueError on arguments that no point set could make valid."""
+    what = "fit_trimmed"
+    if model not in BLOCK_MODEL:
+        raise ValueError("%s: model must be 'translation', 'rigid' or 'affine', not %r" % (what, model))
+    if isinstance(keep, bool) or not isinstance(keep, (int, float, np.integer, np.floating)) or not 0 < keep <= 1:
+        raise ValueError("%s: keep must be in (0, 1], not %r" % (what, keep))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        raise ValueError("%s: max_iter must be a non-negative integer, not %r" % (what, max_iter))
+    s = np.ascontiguousarray(src, np.float64)
+    d = np.ascontiguousarray(dst, np.float64)
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError("%s: src must be n x 3 points" % what)
+    if d.shape != s.shape:
+        raise ValueError("%s: dst must have src's shape %s" % (what, s.shape))
+    ss, sd = _scale3(scale_src, what, "scale_src"), _scale3(scale_dst, what, "scale_dst")
+    T = np.zeros(12)
+    used = np.zeros(max(len(s), 1), np.uint8)
+    its = C.c_int(0)
+    rc = lib().sift3d_amd_fit_trimmed(_dptr(s), _dptr(d), len(s), BLOCK_MODEL[model], float(keep), int(max_iter),
+                                      None if ss is None else _dptr(ss), None if sd is None else _dptr(sd), _dptr(T),
+                                      used.ctypes.data, C.byref(its))
+    if rc != 0:
+        return None
+    return T.reshape(3, 4), used[:len(s)].astype(bool), int(its.value)
+
+
+def block_register_params(**kw):
+    """sift3d_amd_block_register_params: the defaults, overridden by model (a name), levels, iterations, radius,
+    keep_blocks, keep_inliers, tol, spacing_fixed, spacing_moving"""
+    p = BlockRegisterParams()
+    lib().sift3d_amd_block_register_default_params(C.byref(p))
+    names = [f[0] for f in BlockRegisterParams._fields_]
+    for k, v in kw.items():
+        if k not in names:
+            raise ValueError("block_register: unknown parameter %r" % (k,))
+        if k == "model":
+            if v not in BLOCK_MODEL:
+                raise ValueError("block_register: model must be 'translation', 'rigid' or 'affine', not %r" % (v,))
+            v = BLOCK_MODEL[v]
+        elif k.startswith("spacing"):
+            v = (C.c_double * 3)(*_scale3(v, "block_register", k))
+        setattr(p, k, v)
+    return p
+
+
+def block_register(F, M, A, params=None, work=None, mask_fixed=None, mask_moving=None):
+    """sift3d_amd_block_register_device on torch CUDA float32 contiguous volumes F [oz, oy, ox] and M [nz, ny, nx], on
+    torch's current stream (the call waits for it once per iteration).  A: the 3 x 4 start pull map.  Returns the
+    BlockRegisterResult."""
+    what = "block_register"
+    head, masks = _pair(what, F, M, mask_fixed, mask_moving)
+    masks = masks or (None, None)
+    a = _affine12(A, what)
+    p = params if params is not None else block_register_params()
+    need = lib().sift3d_amd_block_register_work_floats(*head[1:4], *head[5:8], p.levels, masks[0] is not None,
+                                                       masks[1] is not None)
+    if need == 0:
+        raise ValueError("%s: levels must be in [1, %d] and every level's fixed grid at least 8 voxels on every axis"
+                         % (what, AFFINE_MAX_LEVELS))
+    work = _work(work, need + (need & 1), F, what)
+    res = BlockRegisterResult()
+    _run("sift3d_amd_block_register_device", *head, *masks, _dptr(a), C.byref(p), C.byref(res), work.data_ptr(),
+         current_stream())
+    return res
 
 
 def absmax(src, out):
