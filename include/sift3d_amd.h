@@ -2208,6 +2208,86 @@ sift3d_amd_demons_lncc_device(const sift3d_amd_demons_level *level, const sift3d
                               void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* MIND self-similarity descriptors                                         */
+/* ------------------------------------------------------------------------ */
+/* The self-similarity context of the modality-independent neighbourhood descriptor (MIND-SSC: Heinrich et al.,
+ * MICCAI 2013; MIND: Heinrich et al., MedIA 2012): every voxel gets 12 channels that say how much the patches around
+ * it resemble EACH OTHER within the same volume.  The channels of two volumes are therefore comparable with a plain
+ * squared difference whatever relates the two intensity scales, an inverted contrast included, and the stack
+ * [12][nz][ny][nx] is a drop-in for the channel stacks of "Multi-channel free-form deformation" and of every demons
+ * update.  No upstream counterpart: PARITY UNPINNED, pinned to this contract and its numpy restatement
+ * (tests/mind_restatement.py); the device reproduces every output but the one sum of d_stats bit for bit.
+ *
+ * Inputs.  I[nz][ny][nx], float32 and finite; the patch radius r in [1, SIFT3D_AMD_MIND_MAX_RADIUS]; the dilation d
+ * in [1, SIFT3D_AMD_MIND_MAX_DILATION]; the clamps 0 <= vlo <= vhi of the variance (vhi may be +inf).  Voxel units.
+ *
+ * Neighbours and pairs.  The six neighbours of a voxel are, in (x, y, z),
+ *   n0 = (+d, 0, 0), n1 = (-d, 0, 0), n2 = (0, +d, 0), n3 = (0, -d, 0), n4 = (0, 0, +d), n5 = (0, 0, -d).
+ * Channel k = 0 .. 11 is the pair (i, j) of this list, in this order:
+ *   (0,2) (0,3) (0,4) (0,5) (1,2) (1,3) (1,4) (1,5) (2,4) (2,5) (3,4) (3,5)
+ * the twelve pairs at distance sqrt(2) d; the three opposite pairs (distance 2 d) are left out.
+ *
+ * Per-voxel distances.  s_i(q) = I(clamp(q + n_i)), every coordinate clamped to the grid (replicated edges);
+ * e_k(q) = ((double) s_i(q) - (double) s_j(q))^2, the difference and the square formed in double, unfused;
+ * D_k(p) = box_r(e_k)(p) by the rule "Window sums" of "Local cross-correlation", word for word: windows clipped to the
+ * grid, x then y then z, each ascending from +0.0, an off-grid position adding +0.0, additions unfused.
+ *
+ * Variance and clamp, in double, in this written order:
+ *   S = D_0 + D_1 + ... + D_11 ascending from +0.0,  V = S / 12.0,  Vc = min(max(V, vlo), vhi),
+ *   Dmin = min_k D_k,  t_k = (D_k - Dmin) / Vc, except that Vc == 0 gives t_k = 0
+ * (a flat neighbourhood gives twelve exact ones).  Subtracting Dmin is the usual normalisation by the largest
+ * channel: the largest channel of every voxel is exactly 1.0f.
+ *
+ * Descriptor.  out_k(p) = (float) cexp(t_k), where cexp(t) is the contract's exponential of -t, a fixed sequence of
+ * double operations (multiplies and adds separate, nothing fused) that numpy reproduces bit for bit:
+ *   t >= 104 gives +0.0 (exp(-104) is below half the smallest float);
+ *   otherwise y = t * SIFT3D_AMD_MIND_LOG2E, n = floor(y), f = y - n (exact, 0 <= f < 1),
+ *   p = c_10;  p = p * f + c_k for k = 9, 8, ..., 0  (Horner; 2^-f by its Taylor polynomial of degree 10),
+ *   cexp = p * 2^-n (the exact power of two; n <= 150, so nothing leaves the normal doubles).
+ * The coefficients c_k = (-ln 2)^k / k!, rounded to double:
+ *   c_0  =  0x1.0000000000000p+0    c_1 = -0x1.62e42fefa39efp-1    c_2 =  0x1.ebfbdff82c58fp-3
+ *   c_3  = -0x1.c6b08d704a0c0p-5    c_4 =  0x1.3b2ab6fba4e77p-7    c_5 = -0x1.5d87fe78a6731p-10
+ *   c_6  =  0x1.430912f86c787p-13   c_7 = -0x1.ffcbfc588b0c7p-17   c_8 =  0x1.62c0223a5c824p-20
+ *   c_9  = -0x1.b5253d395e7c4p-24   c_10 = 0x1.e4cf5158b8ecap-28
+ * and SIFT3D_AMD_MIND_LOG2E = 0x1.71547652b82fep+0.  The series alternates, so its truncation error is below the first
+ * term left out, (ln 2)^11 / 11! = 4.4e-10; with the roundings of the doubles (1e-15) and the one rounding to float
+ * the result is within 1 ulp of the float nearest exp(-t).  cexp(0) = 1 exactly.
+ *
+ * Invariance.  The descriptor is unchanged under I -> a I + b for either sign of a, provided vlo and vhi are scaled
+ * by a^2 (every D_k and V scale with a^2, t_k does not); it is EXACTLY unchanged, the same bytes, for a a power of two
+ * and b = 0 while nothing under- or overflows.
+ *
+ * Outputs, each optional (NULL), at least one given: d_out, float [12][nz][ny][nx], the descriptor; d_D, double
+ * [12][nz][ny][nx], the distances D_k; d_V, double [nz][ny][nx], the UNCLAMPED V; d_stats, 16 bytes with the layout
+ * and reduction rule of SIFT3D_AMD_DEMONS_STATS_BYTES: bytes 0-7 the double sum of V over all voxels, bytes 8-15 the
+ * uint64 voxel count; per-workgroup partials reduced in a fixed order, no float atomics; the order of that one sum
+ * is not part of the contract.  (The mean of V is what the clamps are usually stated against: vlo = 1e-3 mean,
+ * vhi = 1e3 mean.)
+ *
+ * d_work holds sift3d_amd_mind_work_bytes bytes (the partials).
+ *
+ * Refusals, -1 before any device call: NULL d_src or d_work, or all four outputs NULL; dims <= 0; radius or dilation
+ * out of range; vlo negative or NaN, vhi < vlo or NaN; misalignment (doubles, d_stats and d_work 8 B, floats 4 B);
+ * any output or the work buffer overlapping the input or another output.  The entry is asynchronous on `stream`,
+ * allocates nothing, does no host synchronisation and uses 64-bit offsets.
+ *
+ * Out of scope: the plain six-channel MIND; Gaussian patch weights; radii above 2; physical or anisotropic spacing;
+ * 4-D input; MIND together with the LNCC force, with mutual information, and in the affine stage; reorientation of
+ * the neighbourhood under the deformation; multi-GPU. */
+#define SIFT3D_AMD_MIND_CHANNELS 12
+#define SIFT3D_AMD_MIND_MAX_RADIUS 2
+#define SIFT3D_AMD_MIND_MAX_DILATION 4
+#define SIFT3D_AMD_MIND_LOG2E 0x1.71547652b82fep+0
+/* d_work of sift3d_hip_mind_ssc, in bytes: the per-workgroup partials (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_mind_work_bytes(int nx, int ny, int nz);
+/* d_src [nz][ny][nx]; d_out float [12][nz][ny][nx], d_D double [12][nz][ny][nx], d_V double [nz][ny][nx], d_stats
+ * 16 B: each may be NULL, not all */
+SIFT3D_AMD_API int
+sift3d_hip_mind_ssc(const float *d_src, int nx, int ny, int nz, int radius, int dilation, double vlo, double vhi,
+                    float *d_out /*NULL*/, double *d_D /*NULL*/, double *d_V /*NULL*/, void *d_stats /*NULL*/,
+                    void *d_work, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Block matching                                                            */
 /* ------------------------------------------------------------------------ */
 /* Rigid / affine registration by block matching with a trimmed least-squares fit (Ourselin et al. 2001, the scheme of

@@ -1756,7 +1756,7 @@ def ffd_transform_points(lattice, spacing, points, A=None):
 
 def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_fixed=None, mask_moving=None,
                metric="msd", bins=None, range_fixed=None, range_moving=None, jacobian=0.0, features="intensity",
-               sigma=1.6, landmarks=None, landmark_weight=FFD_LANDMARK_WEIGHT, **params):
+               sigma=1.6, landmarks=None, landmark_weight=FFD_LANDMARK_WEIGHT, mind=None, **params):
     """Fit a cubic B-spline free-form deformation of the fixed grid that lowers the mean squared difference between
     `fixed` and `moving` seen through it, plus bending * (bending energy), by steepest descent coarse to fine (contract:
     include/sift3d_amd.h, "B-spline free-form deformation").  A: the 3 x 4 affine pull map the deformation is added to
@@ -1792,9 +1792,15 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
     moving [nc, nz, ny, nx] of the same nc are the channels themselves (two contrasts of one subject, say), restricted
     per level.  Masks stay 3-D, on the grids of the stacks; level l's are restrict_volume of level l - 1's float masks.
     jacobian > 0 works as above.  The result is an FFDRefinement (JacFFDRefinement); the trail's `msd` is S_ee / n
-    with n counting voxels, and `warped` is `moving` through the field, every channel of a 4-D input.  metric="mi",
+    with n counting voxels, and `warped` is `moving` through the field, every channel of a 4-D input.
+    features="mind" (3-D volumes) is features="descriptors" with the MIND-SSC self-similarity descriptors (mind_ssc;
+    contract: "MIND self-similarity descriptors") in the place of the dense gradient histograms: they do not change
+    under a gain of EITHER sign and an offset, so this is the fit for volumes of different modalities, an inverted
+    contrast included.  mind: a dict of mind_ssc's keyword arguments (None: its defaults); every level's stack is
+    mind_ssc of that level's own restricted volume.  `sigma` is not used.  metric="mi",
     bins or ranges together with channels, any other `features`, a 4-D volume beside a 3-D one or with
-    features="descriptors", and stacks of unequal nc raise ValueError.
+    features="descriptors" or "mind", `mind` with other features or with keys that are not mind_ssc's, and stacks of
+    unequal nc raise ValueError.
     landmarks=(p_fixed, p_moving) or (p_fixed, p_moving, weights), n x 3 arrays in voxels (x, y, z) and n weights >= 0,
     adds landmark_weight * L to the cost of either metric, with or without masks and the Jacobian penalty (contract:
     "FFD landmarks"): L is the weighted mean squared distance between the mapped fixed points T(p_fixed) and p_moving,
@@ -1816,19 +1822,20 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         landmark_weight = float(landmark_weight)
         if not (np.isfinite(landmark_weight) and landmark_weight >= 0):
             raise ValueError("refine_ffd: landmark_weight must be finite and not negative")
-    if features not in ("intensity", "descriptors"):
-        raise ValueError("refine_ffd: features must be 'intensity' or 'descriptors', not %r" % (features,))
+    if features not in ("intensity", "descriptors", "mind"):
+        raise ValueError("refine_ffd: features must be 'intensity', 'descriptors' or 'mind', not %r" % (features,))
+    mind = _mind_keywords("refine_ffd", features, mind)
     dims = tuple(3 if isinstance(v, Image) else v.dim() if _torch_tensor(v) else np.ndim(v) for v in (fixed, moving))
-    if dims not in ((3, 3), (4, 4)) or (features == "descriptors" and dims != (3, 3)):
+    if dims not in ((3, 3), (4, 4)) or (features != "intensity" and dims != (3, 3)):
         raise ValueError("refine_ffd: fixed and moving must both be volumes [nz, ny, nx]%s, not %d-D and %d-D"
-                         % ("" if features == "descriptors" else " or both stacks [nc, nz, ny, nx]", *dims))
-    channels = features == "descriptors" or dims == (4, 4)
+                         % ("" if features != "intensity" else " or both stacks [nc, nz, ny, nx]", *dims))
+    channels = features != "intensity" or dims == (4, 4)
     if channels and lm is not None:
-        raise ValueError("refine_ffd: landmarks together with channels (features='descriptors' or 4-D volumes) are not "
-                         "supported")
+        raise ValueError("refine_ffd: landmarks together with channels (features='descriptors' or 'mind', or 4-D "
+                         "volumes) are not supported")
     if channels and metric != "msd":
-        raise ValueError("refine_ffd: channels (features='descriptors' or 4-D volumes) are driven by the MSD alone, "
-                         "not metric=%r" % (metric,))
+        raise ValueError("refine_ffd: channels (features='descriptors' or 'mind', or 4-D volumes) are driven by the "
+                         "MSD alone, not metric=%r" % (metric,))
     if dims == (4, 4) and tuple(fixed.shape)[0] != tuple(moving.shape)[0]:
         raise ValueError("refine_ffd: fixed and moving must have the same number of channels, not %d and %d"
                          % (tuple(fixed.shape)[0], tuple(moving.shape)[0]))
@@ -1883,6 +1890,9 @@ def refine_ffd(moving, fixed, A=None, spacing=8, levels=3, bending=0.005, mask_f
         if features == "descriptors":
             fv = [dense_descriptors(v, sigma) for v in fv]
             mv = [dense_descriptors(v, sigma) for v in mv]
+        elif features == "mind":
+            fv = [mind_ssc(v, **mind) for v in fv]
+            mv = [mind_ssc(v, **mind) for v in mv]
         res, lattice, field, penalty = hip.ffd_refine_channels(fv, mv, A0, p, masks_fixed=wf, masks_moving=wm,
                                                                jacobian=jacobian if jacobian > 0 else None)
     elif jacobian > 0:
@@ -1914,7 +1924,8 @@ def register_ffd(moving, fixed, spacing=8, levels=3, bending=0.005, nn_thresh=0.
     pull map (fixed voxel -> moving voxel: the refinement's A, the inverse of the registration's).  ffd_params:
     refine_ffd's further keyword arguments (dict(metric="mi") for a mutual-information FFD stage, which then returns
     a MiFFDRefinement; dict(features="descriptors") for an FFD stage driven by the dense descriptors' 12 channels,
-    which needs no common intensity scale); refine: True, or register's dict of refine_affine's keyword arguments (dict(metric="ncc") or
+    which needs no common intensity scale; dict(features="mind") for one driven by the MIND-SSC descriptors, which
+    survive an inverted contrast too); refine: True, or register's dict of refine_affine's keyword arguments (dict(metric="ncc") or
     dict(metric="mi") for the affine stage).  The two stages' metrics are chosen separately; either defaults to the
     MSD.  The volumes are torch CUDA float32 tensors, or Images / arrays, which are uploaded.  Returns
     FFDRegistration(registration: register's RefinedRegistration, refinement: the FFDRefinement).
@@ -2079,6 +2090,49 @@ def _torch_tensor(volume):
     return isinstance(volume, torch.Tensor)
 
 
+MIND_KEYWORDS = ("radius", "dilation", "floor", "ceiling")
+
+
+def _mind_keywords(what, features, mind):
+    """the dict `mind` of refine_ffd / refine_field checked: mind_ssc's keyword arguments, with features 'mind' only"""
+    if mind is None:
+        return {}
+    if features != "mind":
+        raise ValueError("%s: mind belongs to features='mind', not %r" % (what, features))
+    if not isinstance(mind, dict) or any(k not in MIND_KEYWORDS for k in mind):
+        raise ValueError("%s: mind must be a dict with keys among %s, not %r" % (what, ", ".join(MIND_KEYWORDS), mind))
+    return dict(mind)
+
+
+def mind_ssc(volume, radius=1, dilation=2, floor=1e-3, ceiling=1e3):
+    """The MIND-SSC self-similarity descriptors of a volume (contract: include/sift3d_amd.h, "MIND self-similarity
+    descriptors"; Heinrich et al. 2013): per voxel 12 channels exp(-(D_k - min D) / V), D_k the squared difference of
+    two patches of radius `radius` (1 .. 2) around two of the voxel's six neighbours at distance `dilation` (1 .. 4),
+    V their mean.  The channels describe the volume's own local structure, so those of two modalities compare with a
+    plain squared difference: they are unchanged under a gain of either sign and an offset.  V is clamped to
+    [floor, ceiling] x (the mean of V over the volume), Heinrich's clamps; floor=None: no floor, ceiling=None: no
+    ceiling.  A constant volume gives all ones.  volume: a torch CUDA float32 tensor [nz, ny, nx]; returns a tensor
+    [12, nz, ny, nx] on torch's current stream.  The mean costs a first pass over the volume and one host
+    synchronisation; with floor and ceiling both None there is neither."""
+    from . import hip
+    _volume_tensor(volume, "mind_ssc", "volume")
+    for v, name in ((floor, "floor"), (ceiling, "ceiling")):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating))
+                              or not (float(v) >= 0 and math.isfinite(v))):
+            raise ValueError("mind_ssc: %s must be None or a finite number >= 0, not %r" % (name, v))
+    if floor is not None and ceiling is not None and float(ceiling) < float(floor):
+        raise ValueError("mind_ssc: ceiling %r is below floor %r" % (ceiling, floor))
+    if floor is None and ceiling is None:
+        return hip.mind_ssc(volume, None, radius, dilation)
+    import torch
+    stats = torch.empty(hip.DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=volume.device)
+    hip.mind_ssc(volume, False, radius, dilation, stats=stats)
+    s, n = hip.demons_stats(stats)
+    mean = float(s[0]) / int(n[0])
+    return hip.mind_ssc(volume, None, radius, dilation, 0.0 if floor is None else float(floor) * mean,
+                        math.inf if ceiling is None else float(ceiling) * mean)
+
+
 def dense_descriptors(volume, sigma=1.6, units=None, rotate=False):
     """Dense descriptor image (contract: include/sift3d_amd.h, "Dense descriptors"): one unit-length
     12-bin icosahedral gradient histogram per voxel, windowed by a Gaussian of `sigma` world units.
@@ -2204,7 +2258,10 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     field [3, nz, ny, nx] on fixed's grid (a pull map fixed voxel -> moving voxel; None: start from zero) so that
     the moving features warped through it agree with the fixed ones at every voxel.  moving, fixed: torch CUDA
     float32 tensors [nz, ny, nx] (shapes may differ).  features: "descriptors" (the dense descriptor images of
-    both, window sigma, 12 channels) or "intensity" (the volumes themselves: classic demons).  update: "additive"
+    both, window sigma, 12 channels), "mind" (the MIND-SSC self-similarity descriptors of both, mind_ssc's 12 channels,
+    which survive an inverted contrast: the stacks for volumes of different modalities; with levels > 1 of every
+    level's own restricted volume, as "descriptors"; ("mind", dict) hands mind_ssc the dict's keyword arguments) or
+    "intensity" (the volumes themselves: classic demons).  update: "additive"
     (u += delta) or "diffeomorphic" (u <- u o exp(delta), "Field composition, exponential and inverse"), with
     `squarings` squarings of the exponential; None picks demons_squarings(alpha), which is 0 at the default alpha 2:
     the update is then u o delta, a composition with the step itself.  The caller's field is not modified.
@@ -2245,6 +2302,9 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     k's update (NaN when there is none).  force "demons", the default, is everything above, untouched."""
     import torch
     from . import hip
+    mind = None
+    if isinstance(features, tuple) and len(features) == 2 and features[0] == "mind":
+        features, mind = features
     if force not in ("demons", "lncc"):
         raise ValueError("force must be 'demons' or 'lncc', not %r" % (force,))
     if force == "lncc":
@@ -2282,8 +2342,9 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
         level_iterations = [int(k) for k in level_iterations]
         if len(level_iterations) != levels or any(k < 0 for k in level_iterations):
             raise ValueError("level_iterations must hold one count >= 0 per level")
-    if features not in ("descriptors", "intensity"):
-        raise ValueError("features must be 'descriptors' or 'intensity', not %r" % (features,))
+    if features not in ("descriptors", "intensity", "mind"):
+        raise ValueError("features must be 'descriptors', 'intensity' or 'mind', not %r" % (features,))
+    mind = _mind_keywords("refine_field", features, mind)
     its = [int(iterations)] * levels if level_iterations is None else level_iterations
     wf = _mask_tensor(wf, fixed, "refine_field", "mask_fixed")
     wm = _mask_tensor(wm, fixed, "refine_field", "mask_moving")     # (on the fixed volume's device, as every mask)
@@ -2303,6 +2364,9 @@ def refine_field(moving, fixed, field=None, iterations=DEMONS_ITERATIONS, alpha=
     if features == "descriptors":
         Fs = [dense_descriptors(v, sigma) for v in fv]
         Ms = [dense_descriptors(v, sigma) for v in mv]
+    elif features == "mind":
+        Fs = [mind_ssc(v, **mind) for v in fv]
+        Ms = [mind_ssc(v, **mind) for v in mv]
     else:
         Fs, Ms = fv, mv
     if log:
@@ -2412,14 +2476,18 @@ def prolong_field(field, out_shape):
 def register_dense(moving, fixed, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA, sigma_fluid=DEMONS_SIGMA_FLUID,
                    sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, update="additive",
                    squarings=None, levels=1, level_iterations=None, mask_fixed=None, mask_moving=None, force="demons",
-                   radius=2, step=0.5, **deformable_kw):
+                   radius=2, step=0.5, mind=None, **deformable_kw):
     """register_deformable, then the displacement field of its spline over fixed's grid, then refine_field (update,
     squarings, levels and level_iterations as there).  Returns DenseRegistration(A, tps, inliers, num_matches (as
     register_deformable), field, warped, msd, jacobian (as refine_field)); with levels > 1 MultiresRegistration,
     which adds refine_field's level_slices.  mask_fixed, mask_moving: handed to the refine_field stage only (as
     there); the keypoint and spline stages see the whole volumes.  force, radius, step: refine_field's; with force
     "lncc" the result is LnccRegistration (levels > 1: MultiresLnccRegistration), which has refine_field's lncc where
-    the others have msd."""
+    the others have msd.  features="mind" drives the refine_field stage by the MIND-SSC descriptors, mind: a dict of
+    mind_ssc's keyword arguments for it (the keypoint and spline stages still match the gradient descriptors, which do
+    not survive an inverted contrast)."""
+    if mind is not None:                                        # (ahead of the tensor checks: the arguments alone)
+        features = (features, _mind_keywords("register_dense", features, mind))
     _volume_tensor(moving, "register_dense", "moving")
     _volume_tensor(fixed, "register_dense", "fixed")
     d = register_deformable(moving, fixed, **deformable_kw)

@@ -1645,3 +1645,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* block matching: the checked matching entry, the trimmed point-pair fit and the coarse-to-fine driver */
 #include "sift3d_block_fit.c"
+
+/* MIND-SSC self-similarity descriptors: the checked entry */
+#include "sift3d_mind.c"

@@ -451,6 +451,9 @@ def lib():
         "sift3d_amd_demons_lncc_device": (C.c_int, [C.POINTER(DemonsLevel), C.POINTER(DemonsLevelMasks), C.c_int,
                                                     C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                                     C.c_int, vp, vp, vp]),
+        "sift3d_amd_mind_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_hip_mind_ssc": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                vp, vp, vp, vp, vp, vp]),
         "sift3d_amd_block_match_work_bytes": (C.c_size_t, [C.c_int] * 4),
         "sift3d_hip_block_match": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         "sift3d_amd_fit_trimmed": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double,
@@ -2694,6 +2697,70 @@ def demons_lncc(Fs, Ms, field, iterations, radius=2, step=0.5, sigma_fluid=0.0, 
          float(sigma_diffusion), mode, int(squarings) if mode else 0, work.data_ptr(), stats.data_ptr(),
          current_stream())
     return stats[:total * DEMONS_STATS_BYTES // 8]
+
+
+# ---- MIND-SSC self-similarity descriptors (contract: include/sift3d_amd.h, "MIND self-similarity descriptors") -----
+MIND_CHANNELS = 12
+MIND_MAX_RADIUS = 2
+MIND_MAX_DILATION = 4
+
+
+def _mind_int(value, hi, what, name):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= value <= hi:
+        raise ValueError("%s: %s must be an integer in 1 .. %d, not %r" % (what, name, hi, value))
+    return int(value)
+
+
+def _mind_clamps(vlo, vhi, what):
+    for v in (vlo, vhi):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s: vlo and vhi must be numbers, not %r" % (what, v))
+    vlo, vhi = float(vlo), float(vhi)
+    if not (vlo >= 0 and vhi >= vlo):
+        raise ValueError("%s: the clamps must satisfy 0 <= vlo <= vhi, not %r and %r" % (what, vlo, vhi))
+    return vlo, vhi
+
+
+def mind_ssc(src, out=None, radius=1, dilation=2, vlo=0.0, vhi=math.inf, D=None, V=None, stats=None, work=None):
+    """The MIND-SSC descriptor of a volume (sift3d_hip_mind_ssc; contract in include/sift3d_amd.h, "MIND
+    self-similarity descriptors"): src [nz, ny, nx] float32; out: a float32 tensor [12, nz, ny, nx] that receives the
+    descriptor, None: allocated.  radius: the patch radius (1 .. 2), dilation: the neighbours' distance (1 .. 4), vlo,
+    vhi: the clamps of the variance.  D: a float64 tensor [12, nz, ny, nx] that receives the distances, or None; V: a
+    float64 tensor [nz, ny, nx] that receives the unclamped variance, or None; stats: an int64 tensor of 2 words that
+    receives the sum of V and the voxel count (demons_stats), or None.  out=False asks for no descriptor (then one of
+    D, V, stats must be given).  torch CUDA, on torch's current stream, no host synchronisation.  Returns out (None
+    with out=False)."""
+    import torch
+    what = "mind_ssc"
+    _tensor(src, "%s: src must be a contiguous float32 CUDA tensor [nz, ny, nx]" % what, dims=(3,))
+    r = _mind_int(radius, MIND_MAX_RADIUS, what, "radius")
+    d = _mind_int(dilation, MIND_MAX_DILATION, what, "dilation")
+    vlo, vhi = _mind_clamps(vlo, vhi, what)
+    shape = tuple(src.shape)
+    nz, ny, nx = shape
+    if out is None:
+        out = torch.empty((MIND_CHANNELS,) + shape, dtype=torch.float32, device=src.device)
+    elif out is False:
+        out = None
+        if D is None and V is None and stats is None:
+            raise ValueError("%s: out=False needs one of D, V and stats" % what)
+    else:
+        _tensor(out, "%s: out must be a contiguous float32 CUDA tensor [12, nz, ny, nx] on src's device" % what,
+                shape=(MIND_CHANNELS,) + shape, device=src.device)
+    if D is not None:
+        _tensor(D, "%s: D must be a contiguous float64 CUDA tensor [12, nz, ny, nx] on src's device" % what,
+                shape=(MIND_CHANNELS,) + shape, device=src.device, dtype="float64")
+    if V is not None:
+        _tensor(V, "%s: V must be a contiguous float64 CUDA tensor [nz, ny, nx] on src's device" % what,
+                shape=shape, device=src.device, dtype="float64")
+    if stats is not None:
+        _tensor(stats, "%s: stats must be a contiguous int64 CUDA tensor of %d words on src's device"
+                % (what, DEMONS_STATS_BYTES // 8), shape=(DEMONS_STATS_BYTES // 8,), device=src.device, dtype="int64")
+    work = _byte_work(what, work, lib().sift3d_amd_mind_work_bytes(nx, ny, nz), src)
+    _run("sift3d_hip_mind_ssc", src.data_ptr(), nx, ny, nz, r, d, vlo, vhi, *(None if t is None else t.data_ptr()
+                                                                                for t in (out, D, V, stats)),
+         work.data_ptr(), current_stream())
+    return out
 
 
 # ---- block matching (contract: include/sift3d_amd.h, "Block matching") ----------------------------------------------
