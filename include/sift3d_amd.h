@@ -2442,6 +2442,147 @@ sift3d_amd_block_register_device(const float *d_F, int ox, int oy, int oz, const
                                  sift3d_amd_block_register_result *result, float *d_work, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Discrete displacement search                                              */
+/* ------------------------------------------------------------------------ */
+/* Deformable registration by discrete optimisation over a dense displacement label space (Heinrich et al., "MRF-based
+ * deformable registration and ventilation estimation of lung CT", TMI 2013; Heinrich et al., "Non-parametric discrete
+ * registration with convex optimisation", WBIR 2014): the matching cost of every block at every displacement of a
+ * search cube is sampled into a cost volume, one displacement per block is picked under a quadratic coupling to a
+ * smooth field, the field is smoothed, the coupling tightened, and this is repeated coarse to fine.  There is no
+ * gradient and no dependence on the start inside the search range, so motions larger than the local structure's
+ * period are found; the result is the start field that demons and FFD want.  No upstream counterpart: PARITY UNPINNED,
+ * pinned to this contract and its numpy restatement (tests/discrete_restatement.py); the device reproduces every
+ * output but the one order-free sum of the statistics record bit for bit.
+ *
+ * Blocks and labels.  Those of "Block matching", word for word.  Edge 4: block (bx, by, bz) covers voxels
+ * 4 b .. 4 b + 3 on every axis; nb_d = n_d / 4 (integer division), trailing voxels belong to no block; -1 when any
+ * nb_d == 0.  The block's voxel i = x + 4 y + 16 z (local), 0 .. 63.  Labels d = (dx, dy, dz) in [-R, R]^3,
+ * k = ((dz + R)(2R + 1) + (dy + R))(2R + 1) + (dx + R), K = (2R + 1)^3, R in [1, SIFT3D_AMD_DISCRETE_MAX_RADIUS].
+ *
+ * Cost volume (sift3d_hip_cost_volume).  F[nc][nz][ny][nx], the fixed feature stack; W[nc][nz][ny][nx], the moving
+ * stack already warped onto the fixed grid; both finite float32; nc in [1, SIFT3D_AMD_DISCRETE_MAX_CHANNELS].  Optional
+ * float masks V_F, V_W on the grid: a voxel is in where w >= 0.5f (the rule of "Masks"); NULL is all in.
+ * Per block b and label k, in double, from +0.0, channels c ascending outermost and voxels i ascending inside,
+ * nothing fused:
+ *   e = (double) F_c,i - (double) W_c,i+d  (exact),  s = e * e,  acc = acc + s;   cost = (float) (acc / (64.0 * nc)).
+ * A label is valid when the shifted block lies wholly inside the grid and all its 64 voxels are in V_W; a block is
+ * valid when all its 64 voxels are in V_F.  An invalid label, and every label of an invalid block, gets +inf.  A
+ * finite sum that rounds past FLT_MAX gives +inf too: the two are indistinguishable on purpose, both mean "never
+ * choose".  Output d_cost, float [nbz][nby][nbx][K], the label index fastest: sift3d_amd_cost_volume_bytes bytes (0
+ * for bad arguments; 2.3 GB at 256^3 and R = 6).  This implementation needs no work buffer:
+ * sift3d_amd_cost_volume_work_bytes is 0 and d_work may be NULL; it is never read or written.
+ *
+ * Coupled selection (sift3d_hip_cost_select).  u[3][nbz][nby][nbx], the block field the choice is coupled to (float
+ * x, y, z, in voxels).  Per block and label, in double, unfused:
+ *   ex = (double) dx - (double) u_x (ey, ez likewise),  q = (ex ex + ey ey) + ez ez,  val = (double) cost + theta q.
+ * The choice is the smallest val; equal val: the smaller dx^2 + dy^2 + dz^2, then the smaller k.  Outputs: v[3], the
+ * chosen label as float; d_data[nb], the chosen label's cost.  A block whose smallest val is +inf is empty: its v is
+ * u's bytes and its d_data +inf.  d_stats: 16 bytes with the layout and reduction rule of
+ * SIFT3D_AMD_DEMONS_STATS_BYTES: bytes 0-7 the double sum of (double) d_data over the non-empty blocks, bytes 8-15 the
+ * uint64 count of the non-empty blocks; per-workgroup partials reduced in a fixed order, no float atomics; the order
+ * of that one sum is not part of the contract.  theta >= 0 and finite; theta = 0 is the plain arg-min.  d_work holds
+ * SIFT3D_AMD_COST_SELECT_WORK_BYTES bytes (the partials).
+ *
+ * Block-field smoothing (sift3d_hip_block_field_smooth).  Per channel the separable binomial with clamped indices,
+ *   B_x(a)(i) = (0.25f a[max(i - 1, 0)] + 0.5f a[i]) + 0.25f a[min(i + 1, n - 1)],
+ * along x, then y, then z, in float and unfused: one pass; `passes` in [0, SIFT3D_AMD_DISCRETE_MAX_PASSES] of them, 0
+ * copies.  Its own rule rather than the detector's blur: it holds on grids of one block per axis.  d_work holds
+ * sift3d_amd_block_field_smooth_work_bytes bytes: one more field with passes >= 2, else 0 (d_work may then be NULL).
+ *
+ * Expansion (sift3d_hip_block_field_expand).  The block field goes to a voxel field w[3][nz][ny][nx] by trilinear
+ * interpolation between the block centres 4 b + 1.5.  Per axis, t = ((float) p - 1.5f) * 0.25f clamped to
+ * [0, nb - 1], i0 = (int) floorf(t), i1 = min(i0 + 1, nb - 1), f = t - (float) i0; (1 - f) a[i0] + f a[i1] along x,
+ * then y, then z, unfused.  Voxels past the last block centre take the edge value.  nb_d == n_d / 4 is required.
+ *
+ * Driver (sift3d_amd_discrete_register_device).  The levels are sift3d_amd_demons_level stacks exactly as
+ * sift3d_amd_demons_multires_device takes them (level 0 the finest, every level the half of the one above, the caller
+ * makes the stacks, levels in [1, SIFT3D_AMD_DEMONS_MAX_LEVELS]; `iterations` is not read).  u_0 = d_u; fields go down
+ * by restrict2 at scale 0.5f, the masks d_VF (level 0's fixed grid) and d_VM (its moving grid) by restrict2 at scale
+ * 1.  Per level l, the coarsest first:
+ *   1. W = warp_field(M_l, u_l, LINEAR, fill 0), every channel;
+ *   2. V_W = warp_field(the level's moving mask, or a volume of ones, u_l, NEAREST, fill 0);
+ *   3. C = cost_volume(F_l, W, V_F = the level's fixed mask or NULL, V_W, radius);
+ *   4. b = 0;
+ *   5. for theta_j of params->theta[0 .. n_theta - 1], n_theta in [1, SIFT3D_AMD_DISCRETE_MAX_THETAS]:
+ *   6.    v = cost_select(C, b, theta_j), its record to d_stats[next];
+ *   7.    b = block_field_smooth(v, passes);
+ *   8. (the first theta's selection runs against b = 0 with theta_0 like any other: it is not special-cased)
+ *   9. w = block_field_expand(b); u_l = field_compose(u_l, w) = w(p) + u_l(p + w(p)) (SIFT3D_AMD_FIELD_COMPOSE);
+ *      l > 0: u_(l-1) = field_prolong2(u_l).
+ * d_stats receives one 16-byte record per (level, theta) in the order run.  A level whose fixed grid is below 4 on an
+ * axis is refused.  Asynchronous on `stream`, no host synchronisation, allocates nothing.  d_work holds
+ * sift3d_amd_discrete_register_work_floats floats, 8-byte aligned: with n_l, m_l the voxels of the fixed and moving
+ * grid on level l, b_0 the blocks of level 0 and P = SIFT3D_AMD_COST_SELECT_WORK_BYTES / 4,
+ *   pad4(P) + pad4(nc n_0) + pad4(n_0) + [no moving mask: pad4(m_0)] + pad4(b_0 K) + 3 pad4(3 b_0) + pad4(b_0)
+ *   + 2 pad4(3 n_0) + sum_{l >= 1} (pad4(3 n_l) + [fixed mask: pad4(n_l)] + [moving mask: pad4(m_l)])
+ * (the partials; W; V_W; the ones; C; v, b and the smoothing's second buffer; the chosen costs; w and the composed
+ * field; the coarser fields and masks).  params == NULL takes the defaults below.
+ *
+ * Refusals, -1 before any device call: NULL pointers (the masks, and a work buffer of zero bytes, may be NULL);
+ * dims <= 0 or a grid with nb_d == 0; nc, radius, passes or n_theta out of range; a theta that is negative or not
+ * finite; dimensions off the halving chain; misalignment (statistics and work 8 B, the rest 4 B); any output or work
+ * buffer overlapping an input or another output.  Every entry uses 64-bit offsets (nb K passes 2^31 early).
+ *
+ * Out of scope: label steps other than 1 voxel; sub-label refinement; block edges other than 4 and overlapping
+ * blocks; MRF, tree or belief-propagation regularisers; symmetric (two-way) search; physical spacing; a cost other
+ * than the channel SSD (LNCC and MI are out); multi-GPU; wiring into register_ffd / register_dense / refine_field. */
+#define SIFT3D_AMD_DISCRETE_MAX_RADIUS 6
+#define SIFT3D_AMD_DISCRETE_MAX_CHANNELS 16
+#define SIFT3D_AMD_DISCRETE_MAX_PASSES 16
+#define SIFT3D_AMD_DISCRETE_MAX_THETAS 16
+#define SIFT3D_AMD_COST_SELECT_WORK_BYTES 16384     /* 1024 slots of a double and a uint64 */
+/* the default schedule of the coupling: the six values of WBIR 2014, a factor ~3 apart, times 0.03: the mean squared
+ * difference of MIND channels of matching blocks is near 0.05 and of unrelated ones near 0.15, not 1 */
+#define SIFT3D_AMD_DISCRETE_DEFAULT_THETAS { 0.00009, 0.0003, 0.0009, 0.003, 0.009, 0.03 }
+/* bytes of d_cost, float [nbz][nby][nbx][K]; 0 for bad arguments (a dimension below 4, radius out of range) */
+SIFT3D_AMD_API size_t sift3d_amd_cost_volume_bytes(int nx, int ny, int nz, int radius);
+/* bytes of d_work for sift3d_hip_cost_volume: 0, this implementation needs none */
+SIFT3D_AMD_API size_t sift3d_amd_cost_volume_work_bytes(int nx, int ny, int nz, int nc, int radius);
+/* d_F, d_W [nc][nz][ny][nx]; d_VF, d_VW masks [nz][ny][nx] or NULL; d_cost float [nbz][nby][nbx][K]; d_work may be
+ * NULL */
+SIFT3D_AMD_API int
+sift3d_hip_cost_volume(const float *d_F, const float *d_W, int nc, int nx, int ny, int nz, const float *d_VF,
+                       const float *d_VW, int radius, float *d_cost, void *d_work, void *stream);
+/* bytes of d_work for sift3d_hip_cost_select: SIFT3D_AMD_COST_SELECT_WORK_BYTES (0 for bad dims) */
+SIFT3D_AMD_API size_t sift3d_amd_cost_select_work_bytes(int nbx, int nby, int nbz);
+/* d_cost [nbz][nby][nbx][K]; d_u, d_v float [3][nbz][nby][nbx]; d_data float [nbz][nby][nbx]; d_stats 16 B */
+SIFT3D_AMD_API int
+sift3d_hip_cost_select(const float *d_cost, int nbx, int nby, int nbz, int radius, const float *d_u, double theta,
+                       float *d_v, float *d_data, void *d_stats, void *d_work, void *stream);
+/* bytes of d_work for sift3d_hip_block_field_smooth: 12 nb with passes >= 2, else 0 (0 for bad arguments too) */
+SIFT3D_AMD_API size_t sift3d_amd_block_field_smooth_work_bytes(int nbx, int nby, int nbz, int passes);
+/* d_src, d_dst float [3][nbz][nby][nbx]; d_work may be NULL where the size above is 0 */
+SIFT3D_AMD_API int
+sift3d_hip_block_field_smooth(const float *d_src, float *d_dst, int nbx, int nby, int nbz, int passes, void *d_work,
+                              void *stream);
+/* d_b float [3][nbz][nby][nbx], nb_d == n_d / 4; d_w float [3][nz][ny][nx] */
+SIFT3D_AMD_API int
+sift3d_hip_block_field_expand(const float *d_b, int nbx, int nby, int nbz, float *d_w, int nx, int ny, int nz,
+                              void *stream);
+typedef struct {
+    int radius;                /* 4 */
+    int passes;                /* 2 */
+    int n_theta;               /* 6 */
+    double theta[SIFT3D_AMD_DISCRETE_MAX_THETAS];  /* SIFT3D_AMD_DISCRETE_DEFAULT_THETAS */
+} sift3d_amd_discrete_register_params;
+SIFT3D_AMD_API void sift3d_amd_discrete_register_default_params(sift3d_amd_discrete_register_params *p);
+/* for bindings that restate the layouts: sizeof the params struct (0), then SIFT3D_AMD_DISCRETE_MAX_RADIUS (1),
+ * _MAX_CHANNELS (2), _MAX_THETAS (3), _MAX_PASSES (4), SIFT3D_AMD_COST_SELECT_WORK_BYTES (5); 0 otherwise */
+SIFT3D_AMD_API size_t sift3d_amd_discrete_register_struct_bytes(int which);
+/* device scratch of the driver in floats, for level 0's fixed grid (nx, ny, nz) and moving grid (mx, my, mz); 0 for
+ * bad arguments, a level's fixed grid below 4 among them */
+SIFT3D_AMD_API size_t
+sift3d_amd_discrete_register_work_floats(int nx, int ny, int nz, int mx, int my, int mz, int nc, int levels,
+                                         int radius, int mask_fixed, int mask_moving);
+/* level [levels] (level 0 the finest); d_VF, d_VM masks on level 0's fixed / moving grid or NULL; d_u float
+ * [3][nz][ny][nx] on level 0's fixed grid, in / out; d_stats 16 B per (level, theta) */
+SIFT3D_AMD_API int
+sift3d_amd_discrete_register_device(const sift3d_amd_demons_level *level, int levels, int nc, const float *d_VF,
+                                    const float *d_VM, float *d_u,
+                                    const sift3d_amd_discrete_register_params *params, void *d_stats, float *d_work,
+                                    void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Distance transforms and surface distances                                 */
 /* ------------------------------------------------------------------------ */
 /* The exact Euclidean distance transform (EDT) of a mask, the signed distance of a set, the six-neighbour surface of

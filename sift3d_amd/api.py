@@ -2473,6 +2473,154 @@ def prolong_field(field, out_shape):
     return hip.field_prolong2(field, fine)
 
 
+# ---- discrete displacement search ------------------------------------------------------------------------------------
+CostVolume = collections.namedtuple("CostVolume", "cost radius blocks")
+DiscreteRegistration = collections.namedtuple("DiscreteRegistration", "field warped data level_slices jacobian")
+DISCRETE_FEATURES = ("mind", "intensity", "descriptors")
+
+
+def _discrete_features(what, features, mind):
+    """(kind, mind keywords, (fixed stack, moving stack) or None) of the `features` of cost_volume / register_discrete:
+    "mind", "intensity", "descriptors", ("mind", dict), or a pair of CUDA stacks [nc, nz, ny, nx]"""
+    from . import hip
+    if isinstance(features, tuple) and len(features) == 2 and features[0] == "mind":
+        if mind is not None:
+            raise ValueError("%s: features ('mind', dict) and mind= are two ways to say one thing" % what)
+        features, mind = features
+    if isinstance(features, (tuple, list)) and len(features) == 2 and all(_torch_tensor(t) for t in features):
+        if mind is not None:
+            raise ValueError("%s: mind needs features 'mind'" % what)
+        for t, name in zip(features, ("fixed", "moving")):
+            hip._tensor(t, "%s: the %s stack must be a contiguous float32 CUDA tensor [nc, nz, ny, nx]" % (what, name),
+                        dims=(4,))
+        if features[0].shape[0] != features[1].shape[0] or not 1 <= features[0].shape[0] <= hip.DISCRETE_MAX_CHANNELS:
+            raise ValueError("%s: the stacks must hold the same 1 .. %d channels" % (what, hip.DISCRETE_MAX_CHANNELS))
+        return "stacks", {}, tuple(features)
+    if not isinstance(features, str) or features not in DISCRETE_FEATURES:
+        raise ValueError("%s: features must be 'mind', 'intensity', 'descriptors' or a pair of CUDA stacks "
+                         "[nc, nz, ny, nx], not %r" % (what, features))
+    return features, _mind_keywords(what, features, mind), None
+
+
+def _discrete_stacks(kind, mind, fv, mv):
+    """the feature stacks of the level volumes fv, mv (lists, level 0 first)"""
+    if kind == "mind":
+        return [mind_ssc(v, **mind) for v in fv], [mind_ssc(v, **mind) for v in mv]
+    if kind == "descriptors":
+        return [dense_descriptors(v) for v in fv], [dense_descriptors(v) for v in mv]
+    return fv, mv
+
+
+def _discrete_start(what, transform, F, device):
+    """the start field [3, nz, ny, nx] on F's grid of None, a 3 x 4 pull map, a TPS or a field (cloned)"""
+    import torch
+    from . import hip
+    grid = tuple(F.shape[-3:])
+    if transform is None:
+        return torch.zeros((3,) + grid, dtype=torch.float32, device=device)
+    if _torch_tensor(transform):
+        hip._field_tensor(transform, what)
+        if tuple(transform.shape[1:]) != grid:
+            raise ValueError("%s: the field %s is not on the fixed grid %s" % (what, tuple(transform.shape), grid))
+        return transform.clone()
+    if not isinstance(transform, TPS):
+        transform = _affine_start(transform, what, "the transform")
+    return displacement_field(transform, grid, device)
+
+
+def cost_volume(fixed, moving, transform=None, radius=4, features="mind", mask_fixed=None, mask_moving=None):
+    """The cost volume of "Discrete displacement search" (include/sift3d_amd.h): for every 4^3 block of `fixed` and
+    every displacement d in [-radius, radius]^3 the mean squared difference of the feature channels of the block and
+    of `moving`, seen through `transform` and shifted by d.  features: "mind" (mind_ssc of both volumes; ("mind", dict)
+    hands it the dict's keyword arguments), "intensity" (the volumes), "descriptors" (dense_descriptors) or a pair
+    (fixed stack, moving stack) of CUDA tensors [nc, nz, ny, nx], with which fixed and moving are not read and may be
+    None.  transform: None, a 3 x 4 pull map, a TPS or a displacement field on the fixed grid.  mask_fixed,
+    mask_moving: as similarity's; a block with a voxel out of mask_fixed and a label whose shifted block has a voxel
+    outside the grid or out of the warped mask_moving hold +inf.  Returns CostVolume(cost: a CUDA float32 tensor
+    [nbz, nby, nbx, (2 radius + 1)^3], the label index k = ((dz + R)(2R + 1) + (dy + R))(2R + 1) + (dx + R); radius;
+    blocks = (nbz, nby, nbx)).  On torch's current stream, no host synchronisation."""
+    import torch
+    from . import hip
+    what = "cost_volume"
+    r = hip._discrete_int(radius, 1, hip.DISCRETE_MAX_RADIUS, what, "radius")
+    kind, mind, stacks = _discrete_features(what, features, None)
+    if stacks is None:
+        WF = _mask_host(mask_fixed, fixed, what, "mask_fixed")
+        WM = _mask_host(mask_moving, moving, what, "mask_moving")
+        F = _similarity_volume(fixed, what, "fixed")
+        M = _similarity_volume(moving, what, "moving", F.device)
+        Fs, Ms = _discrete_stacks(kind, mind, [F], [M])
+        Fs, Ms = Fs[0], Ms[0]
+    else:
+        Fs, Ms = stacks
+        F, M = Fs[0], Ms[0]
+        WF = _mask_host(mask_fixed, F, what, "mask_fixed")
+        WM = _mask_host(mask_moving, M, what, "mask_moving")
+    if min(F.shape) < 4:
+        raise ValueError("%s: fixed %s must hold a block of 4 voxels on every axis" % (what, tuple(F.shape)))
+    WF = _mask_tensor(WF, F, what, "mask_fixed")
+    WM = _mask_tensor(WM, F, what, "mask_moving")
+    u = _discrete_start(what, transform, F, F.device)
+    W = warp_field(Ms, u, "linear", 0.0)
+    VW = warp_field(WM if WM is not None else torch.ones_like(M), u, "nearest", 0.0)
+    cost = hip.cost_volume(Fs, W, r, WF, VW)
+    return CostVolume(cost, r, tuple(cost.shape[:3]))
+
+
+def register_discrete(moving, fixed, field=None, features="mind", mind=None, levels=3, radius=4, thetas=None, passes=2,
+                      mask_fixed=None, mask_moving=None):
+    """Deformable registration by discrete displacement search (contract: include/sift3d_amd.h, "Discrete displacement
+    search"; Heinrich et al., TMI 2013 and WBIR 2014): coarse to fine, per level the cost volume of every 4^3 block
+    over the displacements [-radius, radius]^3, then per coupling weight of `thetas` (None: the library's schedule)
+    one displacement per block of smallest cost + theta |d - b|^2 against the smooth block field b, and `passes`
+    binomial passes over the choice; the level's field is composed with the result.  There is no gradient and no
+    dependence on the start inside the search range, radius 2^(levels - 1) voxels at the coarsest level: it finds the
+    motions a demons or FFD stage cannot reach, and its field is their start (refine_field(moving, fixed, r.field,
+    ...)).  moving, fixed: torch CUDA float32 tensors [nz, ny, nx] (shapes may differ).  features: as cost_volume's;
+    with levels > 1 every level's stack is made from that level's own restricted volumes (a pair of stacks is
+    restricted itself).  field: the start, None, a 3 x 4 pull map, a TPS or a displacement field on fixed's grid (not
+    modified).  mask_fixed, mask_moving: as refine_field's.  Every level's fixed grid must hold a block of 4 voxels on
+    every axis.  Returns DiscreteRegistration(field, warped = moving through the field (linear, fill 0; None with a
+    pair of stacks), data [levels * len(thetas)]: the mean chosen data cost per (level, theta) in the order run, the
+    coarsest level first (NaN where every block is empty), level_slices (data[level_slices[l]] is level l's part),
+    jacobian = jacobian_determinant(field)).  Waits for torch's current stream once, to read the statistics."""
+    from . import hip
+    what = "register_discrete"
+    kind, mind, stacks = _discrete_features(what, features, mind)
+    levels = int(levels)
+    if not 1 <= levels <= DEMONS_MAX_LEVELS:
+        raise ValueError("%s: levels must be in 1 .. %d, not %r" % (what, DEMONS_MAX_LEVELS, levels))
+    p = hip.discrete_register_params(radius, passes, thetas)
+    if stacks is None:
+        wf = _mask_host(mask_fixed, fixed, what, "mask_fixed")
+        wm = _mask_host(mask_moving, moving, what, "mask_moving")
+        _volume_tensor(moving, what, "moving")
+        _volume_tensor(fixed, what, "fixed")
+        F0, M0 = fixed, moving
+    else:
+        F0, M0 = stacks
+        wf = _mask_host(mask_fixed, F0[0], what, "mask_fixed")
+        wm = _mask_host(mask_moving, M0[0], what, "mask_moving")
+    g = tuple(F0.shape[-3:])
+    for _ in range(1, levels):
+        g = hip.half_shape(g)
+    if min(g) < 4:
+        raise ValueError("%s: the coarsest of %d levels, %s, does not hold a block of 4 voxels on every axis"
+                         % (what, levels, g))
+    wf = _mask_tensor(wf, F0, what, "mask_fixed")
+    wm = _mask_tensor(wm, F0, what, "mask_moving")
+    fv, mv = [F0], [M0]
+    for _ in range(1, levels):
+        fv.append(hip.restrict2(fv[-1]))
+        mv.append(hip.restrict2(mv[-1]))
+    Fs, Ms = _discrete_stacks(kind, mind, fv, mv)
+    u = _discrete_start(what, field, F0, F0.device)
+    stats = hip.discrete_register(Fs, Ms, u, p, wf, wm)
+    data = _mean_or_nan(*hip.demons_stats(stats))
+    warped = None if stacks is not None else warp_field(moving, u, "linear", 0.0)
+    return DiscreteRegistration(u, warped, data, _level_slices([p.n_theta] * levels), jacobian_determinant(u))
+
+
 def register_dense(moving, fixed, iterations=DEMONS_ITERATIONS, alpha=DEMONS_ALPHA, sigma_fluid=DEMONS_SIGMA_FLUID,
                    sigma_diffusion=DEMONS_SIGMA_DIFFUSION, features="descriptors", sigma=1.6, update="additive",
                    squarings=None, levels=1, level_iterations=None, mask_fixed=None, mask_moving=None, force="demons",

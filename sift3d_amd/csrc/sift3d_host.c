@@ -1648,3 +1648,6 @@ int sift3d_amd_copy_level(const sift3d_detector *d, int which, int o, int s, flo
 
 /* MIND-SSC self-similarity descriptors: the checked entry */
 #include "sift3d_mind.c"
+
+/* discrete displacement search: the checked entries of its four kernels and the coarse-to-fine driver */
+#include "sift3d_discrete.c"

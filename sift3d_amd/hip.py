@@ -115,6 +115,18 @@ class BlockRegisterResult(C.Structure):                    # sift3d_amd_block_re
                 ("trail", BlockIteration * (AFFINE_MAX_LEVELS * BLOCK_MAX_ITERATIONS))]
 
 
+DISCRETE_MAX_RADIUS = 6                                    # checked against the library when it is bound (lib())
+DISCRETE_MAX_CHANNELS = 16
+DISCRETE_MAX_THETAS = 16
+DISCRETE_MAX_PASSES = 16
+COST_SELECT_WORK_BYTES = 16384
+
+
+class DiscreteRegisterParams(C.Structure):                 # sift3d_amd_discrete_register_params
+    _fields_ = [("radius", C.c_int), ("passes", C.c_int), ("n_theta", C.c_int),
+                ("theta", C.c_double * DISCRETE_MAX_THETAS)]
+
+
 class Frame(C.Structure):                                  # sift3d_amd_frame
     _fields_ = [("centroid", C.c_double * 3), ("axes", C.c_double * 9), ("lambda_", C.c_double * 3)]
 
@@ -466,6 +478,20 @@ def lib():
                                                        vp, vp, C.POINTER(C.c_double),
                                                        C.POINTER(BlockRegisterParams), C.POINTER(BlockRegisterResult),
                                                        vp, vp]),
+        "sift3d_amd_cost_volume_bytes": (C.c_size_t, [C.c_int] * 4),
+        "sift3d_amd_cost_volume_work_bytes": (C.c_size_t, [C.c_int] * 5),
+        "sift3d_hip_cost_volume": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
+        "sift3d_amd_cost_select_work_bytes": (C.c_size_t, [C.c_int] * 3),
+        "sift3d_hip_cost_select": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, vp,
+                                             vp]),
+        "sift3d_amd_block_field_smooth_work_bytes": (C.c_size_t, [C.c_int] * 4),
+        "sift3d_hip_block_field_smooth": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "sift3d_hip_block_field_expand": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "sift3d_amd_discrete_register_default_params": (None, [C.POINTER(DiscreteRegisterParams)]),
+        "sift3d_amd_discrete_register_struct_bytes": (C.c_size_t, [C.c_int]),
+        "sift3d_amd_discrete_register_work_floats": (C.c_size_t, [C.c_int] * 11),
+        "sift3d_amd_discrete_register_device": (C.c_int, [C.POINTER(DemonsLevel), C.c_int, C.c_int, vp, vp, vp,
+                                                          C.POINTER(DiscreteRegisterParams), vp, vp, vp]),
         "sift3d_amd_distance_work_bytes": (C.c_size_t, [C.c_int] * 3),
         "sift3d_hip_distance_sq": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
         "sift3d_hip_distance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]),
@@ -522,6 +548,11 @@ def lib():
     got = tuple(L.sift3d_amd_block_register_struct_bytes(k) for k in range(5))
     if got != want:
         raise RuntimeError("sift3d_amd.hip restates the block-matching layouts as %s, the library has %s" % (want, got))
+    want = (C.sizeof(DiscreteRegisterParams), DISCRETE_MAX_RADIUS, DISCRETE_MAX_CHANNELS, DISCRETE_MAX_THETAS,
+            DISCRETE_MAX_PASSES, COST_SELECT_WORK_BYTES)
+    got = tuple(L.sift3d_amd_discrete_register_struct_bytes(k) for k in range(6))
+    if got != want:
+        raise RuntimeError("sift3d_amd.hip restates the discrete-search layouts as %s, the library has %s" % (want, got))
     _bound = L
     return L
 
@@ -2887,6 +2918,193 @@ def block_register(F, M, A, params=None, work=None, mask_fixed=None, mask_moving
     _run("sift3d_amd_block_register_device", *head, *masks, _dptr(a), C.byref(p), C.byref(res), work.data_ptr(),
          current_stream())
     return res
+
+
+# ---- discrete displacement search (contract: include/sift3d_amd.h, "Discrete displacement search") -------------------
+def _discrete_int(value, lo, hi, what, name):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+        raise ValueError("%s: %s must be an integer in %d .. %d, not %r" % (what, name, lo, hi, value))
+    return int(value)
+
+
+def _discrete_theta(theta, what):
+    if isinstance(theta, bool) or not isinstance(theta, (int, float, np.integer, np.floating)) or \
+            not (math.isfinite(theta) and theta >= 0):
+        raise ValueError("%s: theta must be finite and not negative, not %r" % (what, theta))
+    return float(theta)
+
+
+def _block_field(t, what, name, shape=None, device=None):
+    _tensor(t, "%s: %s must be a contiguous float32 CUDA tensor [3, nbz, nby, nbx]%s" %
+            (what, name, "" if shape is None else " = %s on the device of the other tensors" % (tuple(shape),)),
+            dims=(4,), lead=3, shape=shape, device=device)
+
+
+def cost_volume(F, W, radius=4, valid_fixed=None, valid_warped=None, cost=None, work=None):
+    """sift3d_hip_cost_volume: the mean squared channel difference of every 4^3 block of the fixed stack F [nz, ny, nx]
+    or [nc, nz, ny, nx] against W (the moving stack warped onto F's grid) at every displacement of the
+    (2 radius + 1)^3 label cube.  valid_fixed, valid_warped: float32 masks [nz, ny, nx] (in where >= 0.5) or None.
+    cost: a float32 tensor [nbz, nby, nbx, K] that receives the result, None: allocated.  work: a CUDA tensor of at
+    least sift3d_amd_cost_volume_work_bytes bytes or None (this build needs none).  torch CUDA float32 contiguous, on
+    torch's current stream, no host synchronisation.  Returns cost; an invalid label or block holds +inf."""
+    import torch
+    what = "cost_volume"
+    nc, (nx, ny, nz), _ = _demons_pair(F, W, what)
+    if tuple(W.shape) != tuple(F.shape):
+        raise ValueError("%s: W %s is not on the fixed grid %s" % (what, tuple(W.shape), tuple(F.shape)))
+    r = _discrete_int(radius, 1, DISCRETE_MAX_RADIUS, what, "radius")
+    if not 1 <= nc <= DISCRETE_MAX_CHANNELS:
+        raise ValueError("%s: 1 .. %d channels, not %d" % (what, DISCRETE_MAX_CHANNELS, nc))
+    if min(nx, ny, nz) < 4:
+        raise ValueError("%s: F %s must hold a block of 4 voxels on every axis" % (what, tuple(F.shape)))
+    grid = tuple(F.shape[-3:])
+    for w, name in ((valid_fixed, "valid_fixed"), (valid_warped, "valid_warped")):
+        if w is not None:
+            _tensor(w, "%s: %s must be a contiguous float32 CUDA tensor of F's grid %s on its device"
+                    % (what, name, grid), shape=grid, device=F.device)
+    shape = (nz // 4, ny // 4, nx // 4, (2 * r + 1) ** 3)
+    if cost is None:
+        cost = torch.empty(shape, dtype=torch.float32, device=F.device)
+    else:
+        _tensor(cost, "%s: cost must be a contiguous float32 CUDA tensor %s on F's device" % (what, shape),
+                shape=shape, device=F.device)
+    need = lib().sift3d_amd_cost_volume_work_bytes(nx, ny, nz, nc, r)
+    if work is not None or need:
+        work = _byte_work(what, work, need, F)
+    _run("sift3d_hip_cost_volume", F.data_ptr(), W.data_ptr(), nc, nx, ny, nz,
+         None if valid_fixed is None else valid_fixed.data_ptr(),
+         None if valid_warped is None else valid_warped.data_ptr(), r, cost.data_ptr(),
+         work.data_ptr() if work is not None and work.numel() else None, current_stream())
+    return cost
+
+
+def _cost_radius(cost, what):
+    _tensor(cost, "%s: cost must be a contiguous float32 CUDA tensor [nbz, nby, nbx, K]" % what, dims=(4,))
+    K = cost.shape[3]
+    r = (round(K ** (1.0 / 3)) - 1) // 2
+    if not 1 <= r <= DISCRETE_MAX_RADIUS or (2 * r + 1) ** 3 != K or min(cost.shape[:3]) < 1:
+        raise ValueError("%s: cost %s does not hold (2 R + 1)^3 labels, R in 1 .. %d, per block"
+                         % (what, tuple(cost.shape), DISCRETE_MAX_RADIUS))
+    return r
+
+
+def cost_select(cost, u, theta, v=None, data=None, stats=None, work=None):
+    """sift3d_hip_cost_select: per block of the cost volume [nbz, nby, nbx, K] the label d of smallest
+    cost + theta |d - u|^2 (ties: the smaller |d|^2, then the smaller index).  u: the block field [3, nbz, nby, nbx]
+    the choice is coupled to.  v [3, nbz, nby, nbx], data [nbz, nby, nbx] (the chosen costs), stats (an int64 tensor
+    of 2 words: the sum of data over the non-empty blocks and their count, read with demons_stats): the outputs, None:
+    allocated.  An empty block (every label +inf) keeps u and has data +inf.  On torch's current stream, no host
+    synchronisation.  Returns (v, data, stats)."""
+    import torch
+    what = "cost_select"
+    r = _cost_radius(cost, what)
+    nb = tuple(cost.shape[:3])
+    th = _discrete_theta(theta, what)
+    _block_field(u, what, "u", (3,) + nb, cost.device)
+    if v is None:
+        v = torch.empty_like(u)
+    else:
+        _block_field(v, what, "v", (3,) + nb, cost.device)
+    if data is None:
+        data = torch.empty(nb, dtype=torch.float32, device=cost.device)
+    else:
+        _tensor(data, "%s: data must be a contiguous float32 CUDA tensor %s on cost's device" % (what, nb), shape=nb,
+                device=cost.device)
+    stats = _buffer(what, "stats", stats, (DEMONS_STATS_BYTES // 8,), cost)
+    nbz, nby, nbx = nb
+    work = _byte_work(what, work, lib().sift3d_amd_cost_select_work_bytes(nbx, nby, nbz), cost)
+    _run("sift3d_hip_cost_select", cost.data_ptr(), nbx, nby, nbz, r, u.data_ptr(), th, v.data_ptr(), data.data_ptr(),
+         stats.data_ptr(), work.data_ptr(), current_stream())
+    return v, data, stats
+
+
+def block_field_smooth(src, passes=2, dst=None, work=None):
+    """sift3d_hip_block_field_smooth: `passes` (0 .. 16) passes of the separable binomial (1/4, 1/2, 1/4) with clamped
+    indices over every channel of the block field src [3, nbz, nby, nbx]; dst: the output, None: allocated.  On
+    torch's current stream.  Returns dst."""
+    import torch
+    what = "block_field_smooth"
+    _block_field(src, what, "src")
+    n = _discrete_int(passes, 0, DISCRETE_MAX_PASSES, what, "passes")
+    if dst is None:
+        dst = torch.empty_like(src)
+    else:
+        _block_field(dst, what, "dst", tuple(src.shape), src.device)
+    nbz, nby, nbx = src.shape[1:]
+    need = lib().sift3d_amd_block_field_smooth_work_bytes(nbx, nby, nbz, n)
+    if work is not None or need:
+        work = _byte_work(what, work, need, src)
+    _run("sift3d_hip_block_field_smooth", src.data_ptr(), dst.data_ptr(), nbx, nby, nbz, n,
+         work.data_ptr() if work is not None and work.numel() else None, current_stream())
+    return dst
+
+
+def block_field_expand(b, shape, w=None):
+    """sift3d_hip_block_field_expand: the block field b [3, nbz, nby, nbx] carried to the voxel grid shape =
+    (nz, ny, nx), nb = n // 4 per axis, by trilinear interpolation between the block centres 4 b + 1.5 (edge values
+    outside them).  w: the output [3, nz, ny, nx], None: allocated.  On torch's current stream.  Returns w."""
+    import torch
+    what = "block_field_expand"
+    _block_field(b, what, "b")
+    nz, ny, nx = (int(n) for n in shape)
+    if min(nz, ny, nx) < 4 or tuple(b.shape[1:]) != (nz // 4, ny // 4, nx // 4):
+        raise ValueError("%s: b %s is not the block grid of %s" % (what, tuple(b.shape), (nz, ny, nx)))
+    if w is None:
+        w = torch.empty((3, nz, ny, nx), dtype=torch.float32, device=b.device)
+    else:
+        _tensor(w, "%s: w must be a contiguous float32 CUDA tensor %s on b's device" % (what, (3, nz, ny, nx)),
+                shape=(3, nz, ny, nx), device=b.device)
+    _run("sift3d_hip_block_field_expand", b.data_ptr(), nx // 4, ny // 4, nz // 4, w.data_ptr(), nx, ny, nz,
+         current_stream())
+    return w
+
+
+def discrete_register_params(radius=None, passes=None, thetas=None):
+    """sift3d_amd_discrete_register_params: the defaults, overridden by radius, passes and thetas (1 .. 16 values)"""
+    what = "discrete_register"
+    p = DiscreteRegisterParams()
+    lib().sift3d_amd_discrete_register_default_params(C.byref(p))
+    if radius is not None:
+        p.radius = _discrete_int(radius, 1, DISCRETE_MAX_RADIUS, what, "radius")
+    if passes is not None:
+        p.passes = _discrete_int(passes, 0, DISCRETE_MAX_PASSES, what, "passes")
+    if thetas is not None:
+        th = [_discrete_theta(t, what) for t in thetas]
+        if not 1 <= len(th) <= DISCRETE_MAX_THETAS:
+            raise ValueError("%s: 1 .. %d thetas, not %d" % (what, DISCRETE_MAX_THETAS, len(th)))
+        p.n_theta = len(th)
+        for j in range(DISCRETE_MAX_THETAS):
+            p.theta[j] = th[j] if j < len(th) else 0.0
+    return p
+
+
+def discrete_register(Fs, Ms, field, params=None, mask_fixed=None, mask_moving=None, work=None):
+    """Coarse-to-fine discrete displacement search (sift3d_amd_discrete_register_device): Fs, Ms are the fixed and
+    moving feature stacks per level as demons_multires takes them (level 0 the finest, every level the half of the one
+    above); the field [3, nz, ny, nx] on Fs[0]'s grid is the start and is updated in place.  params: a
+    DiscreteRegisterParams (discrete_register_params), None: the defaults.  mask_fixed, mask_moving: float32 masks on
+    level 0's fixed / moving grid or None (the driver restricts them).  torch CUDA float32, on torch's current stream,
+    no host synchronisation.  Returns the stats tensor: 16 bytes per (level, theta) in the order run, the coarsest
+    level's first (read it with demons_stats)."""
+    import torch
+    what = "discrete_register"
+    p = params if params is not None else discrete_register_params()
+    tab, levels, nc, _ = _demons_levels(what, Fs, Ms, field, [0] * len(Fs))
+    if not 1 <= nc <= DISCRETE_MAX_CHANNELS:
+        raise ValueError("%s: 1 .. %d channels, not %d" % (what, DISCRETE_MAX_CHANNELS, nc))
+    wf, wm = _demons_masks(what, Fs[0], Ms[0].shape[-3:], mask_fixed, mask_moving) or (None, None)
+    _, nz, ny, nx = field.shape
+    mz, my, mx = Ms[0].shape[-3:]
+    need = lib().sift3d_amd_discrete_register_work_floats(nx, ny, nz, mx, my, mz, nc, levels, p.radius,
+                                                          wf is not None, wm is not None)
+    if need == 0:
+        raise ValueError("%s: every level's fixed grid must hold a block of 4 voxels on every axis" % what)
+    work = _work(work, need, field, what)
+    total = levels * p.n_theta
+    stats = torch.empty(total * DEMONS_STATS_BYTES // 8, dtype=torch.int64, device=field.device)
+    _run("sift3d_amd_discrete_register_device", tab, levels, nc, wf, wm, field.data_ptr(), C.byref(p),
+         stats.data_ptr(), work.data_ptr(), current_stream())
+    return stats
 
 
 def absmax(src, out):
